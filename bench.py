@@ -18,7 +18,13 @@ the data path (RCCL / gloo carry the timing barrier, the max-over-ranks and the 
 of the token lists).  `python bench.py --gpus N` with no WORLD_SIZE in the environment starts the
 N ranks itself (before any GPU call); under torch.distributed.run it is one of the ranks.
 
+A plain run times the headline leg only and prints its line.  `--full` adds everything else this
+benchmark measures and checks: the host-memory and synchronous-GetResults legs, per-stage timings and
+the GEMM roofline, the CPU baseline with `oracle_match`, and on one GPU the configs[2] / [3] / [4] legs.
+`--dump-outputs DIR` writes the token ids and timestamps of the last timed step as .npy files.
+
     python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full
     python bench.py --gpus 8 --total-utts 256 --beam 4                              # configs[2]
     python bench.py --gpus 8 --preset conformer-zh --total-utts 64 --batch 8 --seconds 30   # configs[4]
     python bench.py --gpus 2 --dist-backend gloo                                    # rehearsal on one GPU
@@ -82,6 +88,27 @@ def log(*a):
     print(*a, file=sys.stderr, flush=True)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d, results, first_id):
+    """--dump-outputs: what a caller of the timed path receives for each utterance of the last timed step, its token ids and their
+    frame timestamps, as [utterances, longest] float64 arrays padded with -1; beside them each row's token count and utterance id.
+    Rows beyond the 64 MB budget are left out (the first utterances are kept)."""
+    width = max([len(t) for t, _ in results] + [1])
+    rows = min(len(results), max(1, DUMP_LIMIT_BYTES // (8 * (2 * width + 2))))
+    tok = np.full((rows, width), -1.0)
+    ts = np.full((rows, width), -1.0)
+    for u, (t, s) in enumerate(results[:rows]):
+        tok[u, :len(t)] = t
+        ts[u, :len(s)] = s
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "tokens.npy"), tok)
+    np.save(os.path.join(d, "timestamps.npy"), ts)
+    np.save(os.path.join(d, "token_counts.npy"), np.array([len(t) for t, _ in results[:rows]], np.float64))
+    np.save(os.path.join(d, "utterance_ids.npy"), np.arange(first_id, first_id + rows, dtype=np.float64))
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -105,6 +132,11 @@ def parse_args(argv=None):
                     help="distinct sets of utterances the timed steps cycle through (step s decodes set s %% R: other audio, other emission "
                          "pattern and search length from step to step; every set is checked once against the oracle sample)")
     ap.add_argument("--dump-results", default="", help="rank 0 writes every utterance's (tokens, timestamps) of the last step here (JSON)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline leg: the host-memory and synchronous legs, stage timings and GEMM roofline, the CPU baseline "
+                         "and oracle match, and the secondary legs (each still subject to its --no-* switch)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 writes the last timed step's token ids and timestamps of every utterance as float64 .npy files under DIR")
     ap.add_argument("--launch-check", action="store_true", help="rendezvous + shard bookkeeping only; no GPU work (CPU test of the launcher)")
     return ap.parse_args(argv)
 
@@ -312,9 +344,9 @@ def run_secondary(timeout_s=240):
     here = os.path.dirname(os.path.abspath(__file__))
     legs = {
         "beam4_c2_shard": [sys.executable, os.path.join(here, "bench.py"), "--beam", "4", "--steps", "16", "--warmup", "2",
-                           "--no-host-leg", "--no-secondary"],
+                           "--no-host-leg", "--no-secondary", "--full"],
         "conformer_zh_c4_shard": [sys.executable, os.path.join(here, "bench.py"), "--preset", "conformer-zh", "--batch", "8",
-                                  "--seconds", "30", "--steps", "16", "--warmup", "2", "--no-host-leg", "--no-secondary"],
+                                  "--seconds", "30", "--steps", "16", "--warmup", "2", "--no-host-leg", "--no-secondary", "--full"],
         "streaming_c3": [sys.executable, os.path.join(here, "bench_streaming.py"), "--check", "8"],
     }
     out = {}
@@ -480,7 +512,7 @@ def main():
     log(f"[bench] rank {rank}: timed leg, samples resident in HBM")
     res_sets, elapsed = timed(False)
     host_elapsed = None
-    if not args.no_host_leg:
+    if args.full and not args.no_host_leg:
         log(f"[bench] rank {rank}: timed leg, samples in host memory (pipelined)")
         res_h, host_elapsed = timed(True)
         assert res_h == res_sets, "results from host memory and from device memory differ"
@@ -489,7 +521,7 @@ def main():
     # ONE synchronous GetResults (samples H2D, batched fbank, pad, encoder, search, tokens D2H -- nothing of the next batch overlaps it),
     # Tokens / Timestamps pulled into host lists.  Same utterance sets, same rotation; results must equal the pipelined legs'.
     sync_elapsed = None
-    if not args.no_host_leg and not args.no_pipeline:
+    if args.full and not args.no_host_leg and not args.no_pipeline:
         import ctypes as C
         L = model._L
 
@@ -524,7 +556,7 @@ def main():
 
     # one synchronous pass over the first batch: per-stage HIP-event timings + pipelined == synchronous check
     stages = it = gemm_rows = None
-    if nb:
+    if args.full and nb:
         res_sync = model.offline_greedy_from_samples_dev(dev[0][0], n_each, my_batches[0][1])
         stages = model.timing()
         assert res_sync == res[0], "pipelined and synchronous results differ"
@@ -621,7 +653,7 @@ def main():
             out["roofline"]["committed_profile"] = {"mfma_busy": mb, "source": mb_note}
             # north_star: "rocprof HBM GB/s ... against gfx950 peak" -- the HBM-bound kernels of the batch, each against the 8 TB/s peak
             out["roofline"]["hbm_kernels"] = pmc_hbm_kernels() if default_workload else None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             n_cpu = args.cpu_utts or my_batches[0][1]
             whole = my_batches[0] == (0, n_cpu)
             log(f"[bench] CPU restatement on {host_cores()} host threads ({cpu_model()})")
@@ -648,13 +680,16 @@ def main():
         if args.dump_results:
             with open(args.dump_results, "w") as f:
                 json.dump({"results": allres, "batches_per_rank": nb, "n_gpus": world}, f)
+        if args.dump_outputs:
+            last = (args.steps - 1) % R                 # the utterance set the last timed step decoded
+            dump_outputs(args.dump_outputs, ([allres] + other_sets)[last], last * total)
     for r in range(R):
         for h, d in zip(host[r], dev[r]):
             model.device_free(d)
             model.host_free(h)
     model.close()
     if rank == 0:
-        if world == 1 and default_workload and not args.no_secondary:
+        if args.full and world == 1 and default_workload and not args.no_secondary:
             out["secondary"] = run_secondary()   # the GPU is free again: one child program per leg
             bad_match = bad_match or any(("error" in v) or v.get("exit_code") for v in out["secondary"].values())
         print(json.dumps(out), flush=True)

@@ -8,6 +8,7 @@ import os
 import re
 import shutil
 import subprocess
+import sys
 
 import pytest
 
@@ -37,7 +38,7 @@ def _src(tree, f):
 
 
 @needs_ref
-def test_patches_apply_and_put_the_branch_in_front_of_the_onnx_constructors(patched_tree):
+def test_patches_apply_and_put_the_branch_in_front_of_the_onnx_constructors(patched_tree, tmp_path):
     off = _src(patched_tree, "OfflineRecognizer.cs")
     on = _src(patched_tree, "OnlineRecognizer.cs")
     st = _src(patched_tree, "OnlineStream.cs")
@@ -68,10 +69,17 @@ def test_patches_apply_and_put_the_branch_in_front_of_the_onnx_constructors(patc
     disp = on[on.index("protected virtual void Dispose(bool disposing)"):]
     m = re.search(r"if \(_onlineProj != null\)\s*\{\s*_onlineProj\.Dispose\(\);\s*\}\s*_hipModel\?\.Dispose\(\);", disp)
     assert m, "_hipModel?.Dispose() must follow the closing brace of the _onlineProj null check"
-    # regenerating the patches from tools/make_csharp_patches.py gives what is committed
-    r = subprocess.run(["python", os.path.join(ROOT, "tools", "make_csharp_patches.py")], capture_output=True, text=True, cwd=ROOT)
+    # regenerating the patches from tools/make_csharp_patches.py gives what is committed (the generator runs from a copy, so that it
+    # writes its patches into a scratch tree and not over the committed ones)
+    os.makedirs(tmp_path / "tools")
+    os.makedirs(tmp_path / "csharp" / "patches")
+    shutil.copy(os.path.join(ROOT, "tools", "make_csharp_patches.py"), tmp_path / "tools")
+    r = subprocess.run([sys.executable, str(tmp_path / "tools" / "make_csharp_patches.py")], capture_output=True, text=True, cwd=tmp_path,
+                       env=dict(os.environ, K2_REFERENCE=REF))
     assert r.returncode == 0, r.stderr
-    assert subprocess.run(["git", "diff", "--quiet", "--", "csharp/patches"], cwd=ROOT).returncode == 0, "csharp/patches is stale"
+    for f in FILES:
+        new = open(tmp_path / "csharp" / "patches" / (f + ".patch"), "rb").read()
+        assert new == open(os.path.join(ROOT, "csharp", "patches", f + ".patch"), "rb").read(), f"csharp/patches/{f}.patch is stale"
 
 
 @needs_ref

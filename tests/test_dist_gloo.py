@@ -112,7 +112,7 @@ def test_two_ranks_through_the_product_equal_one_process(tmp_path):
     process decoding the same batches: rank-order concatenation == the single-process result, for greedy and for beam 4."""
     import json
     common = ["--preset", "zipformer2-tiny-test", "--total-utts", "6", "--batch", "3", "--seconds", "1.2", "--steps", "1",
-              "--warmup", "0", "--no-cpu-baseline"]
+              "--warmup", "0", "--no-cpu-baseline", "--full"]
     for extra in ([], ["--beam", "4"]):
         one, two = str(tmp_path / "one.json"), str(tmp_path / "two.json")
         r1 = _bench("--gpus", "1", *common, *extra, "--dump-results", one)

@@ -5,7 +5,7 @@
 R=$PWD; O=$R/gpurun_out/$1; F=${2:-k_attn}; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 rm -rf $O/trace
-rocprofv3 --kernel-trace --output-format csv -d $O/trace -- python3 $R/bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-host-leg --no-secondary > $O/bench.json 2> $O/bench.err
+rocprofv3 --kernel-trace --output-format csv -d $O/trace -- python3 $R/bench.py --full --steps 4 --warmup 2 --no-cpu-baseline --no-host-leg --no-secondary > $O/bench.json 2> $O/bench.err
 echo "rc $?" > $O/summary.txt
 python3 $R/tools/per_grid_stats.py $(ls $O/trace/*/*_kernel_trace.csv | head -1) 9 $F >> $O/summary.txt
 rm -rf $O/trace

@@ -10,12 +10,12 @@ R=$PWD
 O=$R/gpurun_out/refresh_$TAG
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --steps 8 --warmup 2 --no-secondary > $O/bench_under_rocprof.json 2> $O/stats.err
-rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pmc_fetch -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-secondary > /dev/null 2> $O/pmc_fetch.err
-rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/pmc_write -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-secondary > /dev/null 2> $O/pmc_write.err
-rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $O/pmc_mfma -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-secondary > /dev/null 2> $O/pmc_mfma.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_beam4 -- python3 $R/bench.py --beam 4 --steps 8 --warmup 2 --no-host-leg --no-cpu-baseline --no-secondary > /dev/null 2> $O/stats_beam4.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_conformer_zh -- python3 $R/bench.py --preset conformer-zh --batch 8 --seconds 30 --steps 8 --warmup 2 --no-host-leg --no-cpu-baseline --no-secondary > /dev/null 2> $O/stats_conformer_zh.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --full --steps 8 --warmup 2 --no-secondary > $O/bench_under_rocprof.json 2> $O/stats.err
+rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pmc_fetch -- python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-secondary > /dev/null 2> $O/pmc_fetch.err
+rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/pmc_write -- python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-secondary > /dev/null 2> $O/pmc_write.err
+rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $O/pmc_mfma -- python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-secondary > /dev/null 2> $O/pmc_mfma.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_beam4 -- python3 $R/bench.py --full --beam 4 --steps 8 --warmup 2 --no-host-leg --no-cpu-baseline --no-secondary > /dev/null 2> $O/stats_beam4.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_conformer_zh -- python3 $R/bench.py --full --preset conformer-zh --batch 8 --seconds 30 --steps 8 --warmup 2 --no-host-leg --no-cpu-baseline --no-secondary > /dev/null 2> $O/stats_conformer_zh.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_streaming -- python3 $R/bench_streaming.py --streams 128 --seconds 20 --no-cpu-baseline > /dev/null 2> $O/stats_streaming.err
 cd $R
 python3 tools/summarize_stats.py $(ls $O/stats/*/*_kernel_stats.csv | head -1) 33 $O/${TAG}_offline_kernel_stats.csv > /dev/null
@@ -32,7 +32,7 @@ python3 tools/summarize_stats.py $(ls $O/stats_conformer_zh/*/*_kernel_stats.csv
 # `roofline.committed_profile.source` and `roofline.hbm_kernels.from` cite are files of the set they are committed with
 # (tests/test_abi.py::test_profiles_named_in_committed_bench_records_exist).  The record under rocprofv3 was taken before the summaries
 # existed: its citations are rewritten from this run's line.
-K2HIP_PROFILE_DIR=$O python3 bench.py --steps 20 --warmup 3 2> $O/bench.err | tail -1 > $O/${TAG}_bench.json   # carries the configs[2] / [3] / [4] legs under "secondary"
+K2HIP_PROFILE_DIR=$O python3 bench.py --full --steps 20 --warmup 3 2> $O/bench.err | tail -1 > $O/${TAG}_bench.json   # carries the configs[2] / [3] / [4] legs under "secondary"
 python3 - $O/bench_under_rocprof.json $O/${TAG}_bench.json $O/${TAG}_bench_under_rocprof.json <<'PY'
 import json, sys
 under = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -61,7 +61,7 @@ def main():
             "kernel": "gemm_f32_mfma* (all instantiations, cycle-weighted)",
             "launches_sampled": int(gn),
             "mfma_busy": round(gm / (N_SIMD * gg / N_XCD), 4),
-            "method": "rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES GRBM_GUI_ACTIVE (own pass) over `python3 bench.py --steps 2 "
+            "method": "rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES GRBM_GUI_ACTIVE (own pass) over `python3 bench.py --full --steps 2 "
                       "--warmup 1 --no-cpu-baseline --no-secondary`; mfma_busy = sum MFMA_BUSY / (1024 SIMDs x sum GRBM_GUI_ACTIVE / 8 XCDs)",
             "source": os.path.join("profiles", os.path.basename(out)),
         }
