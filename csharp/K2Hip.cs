@@ -63,6 +63,15 @@ namespace K2TransducerAsr.Hip
         [DllImport(Lib)] internal static extern int k2hip_online_stream_get_tokens(IntPtr stream, long[] tokens, int cap);
         [DllImport(Lib)] internal static extern int k2hip_online_stream_get_timestamps(IntPtr stream, int[] timestamps, int cap);
         [DllImport(Lib)] internal static extern int k2hip_online_stream_get_hyp(IntPtr stream, long[] hyp2);
+        [DllImport(Lib)] internal static extern int k2hip_online_stream_get_score(IntPtr stream, out float score);
+        [DllImport(Lib)] internal static extern int k2hip_beam_stream_create(IntPtr model, int beam, out IntPtr stream);
+        [DllImport(Lib)] internal static extern int k2hip_beam_stream_destroy(IntPtr stream);
+        [DllImport(Lib)] internal static extern int k2hip_beam_stream_reset(IntPtr stream);
+        [DllImport(Lib)] internal static extern int k2hip_beam_search_chunk(IntPtr model, IntPtr[] streams, int B, float[] encoderOut, int Tc);
+        [DllImport(Lib)] internal static extern int k2hip_beam_stream_num_tokens(IntPtr stream);
+        [DllImport(Lib)] internal static extern int k2hip_beam_stream_get_tokens(IntPtr stream, long[] tokens, int cap);
+        [DllImport(Lib)] internal static extern int k2hip_beam_stream_get_timestamps(IntPtr stream, int[] timestamps, int cap);
+        [DllImport(Lib)] internal static extern int k2hip_beam_stream_get_score(IntPtr stream, out float score);
 
         [DllImport(Lib)] internal static extern int k2hip_model_meta(IntPtr model, string key, byte[] buf, int cap);
         [DllImport(Lib)] internal static extern int k2hip_set_decoding_method(IntPtr model, string method, int beam);

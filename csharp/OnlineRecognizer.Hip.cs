@@ -29,6 +29,9 @@
 //                                runs the model's own search, as :33-36 would select it)
 //   "greedy_search_operators"    the reference's UNCHANGED loop (:85-219) over OnlineProjOfHip's operators (csharp/OnlineProjOfHip.cs;
 //                                streaming Zipformer2 transducers only), for A/B comparisons against the ONNX path
+//   "modified_beam_search"       the fused route under k2hip_set_decoding_method(.., beam 4): hypotheses carried from chunk to chunk
+//                                (no reference counterpart; include/k2hip.h).  Tokens / Timestamps are re-read after every step (the
+//                                best hypothesis can revise earlier tokens); timestamps are absolute frame indexes
 using System;
 using System.Collections.Generic;
 using System.IO;
@@ -108,6 +111,8 @@ namespace K2TransducerAsr
             _hipModel = new HipOnlineModel(k2wPath, device);
             _tokens = File.ReadAllLines(tokensFilePath);                                // :24
             _hipFused = decodingMethod != "greedy_search_operators";
+            if (decodingMethod == "modified_beam_search")
+                K2Hip.Check(K2Hip.k2hip_set_decoding_method(_hipModel.Handle, "modified_beam_search", 4), "OnlineRecognizer: decoding method");
             if (_hipFused)
             {
                 _forwardBatch = new ForwardBatchOnline(this.ForwardBatchGreedySearchHip);

@@ -52,6 +52,7 @@ extern "C" {
 typedef struct k2hip_model k2hip_model_t;
 typedef struct k2hip_offline_stream k2hip_offline_stream_t;
 typedef struct k2hip_online_stream k2hip_online_stream_t;
+typedef struct k2hip_beam_stream k2hip_beam_stream_t;
 typedef struct k2hip_tokens k2hip_tokens_t;
 
 /* Fixed ids of the reference: OfflineModel.cs:18-20. */
@@ -274,7 +275,21 @@ int32_t k2hip_offline_stream_get_ctc_state(const k2hip_offline_stream_t* s, int3
  * DESIGN.md): per stream at most `beam` hypotheses, log-softmax over the vocabulary, top-`beam` over
  * beam x V, equal token sequences merged by logaddexp, best hypothesis by length-normalised log-prob.
  * The setting is per model handle and applies to every BATCH entry point (k2hip_offline_greedy*,
- * k2hip_offline_recognizer_get_results, submit/wait); the single-stream path stays greedy. */
+ * k2hip_offline_recognizer_get_results, submit/wait) and to the streaming step (k2hip_online_step); the single-stream
+ * offline path stays greedy, and a CTC model (zipformer2ctc) keeps its own CTC search under either setting.
+ *
+ * Streaming under modified_beam_search: after every k2hip_online_step a stream holds exactly what the offline search
+ * (k2hip_beam_search, same tie-breaks) gives over ALL encoder frames the stream has produced so far -- its hypotheses live on
+ * from one chunk to the next.  Start state: one hypothesis [blank, blank], log-prob 0.  Skip set {blank, unk} as offline
+ * (not the greedy streaming rule {blank, unk, 1} of OnlineRecognizer.cs:181: the reference has no beam search, the project's
+ * beam semantics hold).  Equal token sequences are merged on exact whole-sequence equality.  After each step:
+ *   Tokens = [blank, blank] + the best hypothesis (highest log-prob / (length + 2), first in insertion order on ties),
+ *   Hyp = its last two tokens, Timestamps = ABSOLUTE encoder frame indexes (frames of earlier chunks + t; the greedy path keeps
+ *   the reference's chunk-relative ones), k2hip_online_stream_get_score = its log-prob.
+ * The best hypothesis can revise earlier tokens: n_new_tokens is the SIGNED change of its length, and a host re-reads Tokens
+ * after every step instead of appending.  A stream keeps the method and beam it decoded its first chunk with: after a change of
+ * the setting, k2hip_online_step fails with K2HIP_ERR_INVALID for it until k2hip_online_stream_reset (which clears the
+ * hypotheses). */
 int32_t k2hip_set_decoding_method(k2hip_model_t* model, const char* method /* "greedy_search" | "modified_beam_search" */,
                                   int32_t beam /* 1..8, ignored for greedy_search */);
 /* operator level: modified beam search over a host encoder_out [B,T',J]; scores [B] (optional) = log-prob of the
@@ -283,6 +298,20 @@ int32_t k2hip_beam_search(k2hip_model_t* model, const float* enc_out, int32_t B,
                           int32_t* timestamps, int32_t* n_tokens, int32_t max_tokens, float* scores);
 /* log-probs of the hypotheses returned by the last synchronous batch call made under modified_beam_search */
 int32_t k2hip_last_scores(k2hip_model_t* model, float* scores, int32_t B);
+/* operator level of the STREAMING beam search, for hosts that run their own encoder (csharp/OnlineProjOfHip.cs) and for tests:
+ * a k2hip_beam_stream_t is one stream's hypotheses (host memory; no device slot).  k2hip_beam_search_chunk continues every
+ * stream's search over Tc more frames of encoder_out [B, Tc, J] (any Tc >= 1, may vary between calls; all streams of a call
+ * share one beam); afterwards a stream holds what k2hip_beam_search gives over all frames fed so far: tokens WITHOUT the
+ * [blank, blank] prefix (as k2hip_beam_search), absolute timestamps, the log-prob of the best hypothesis.  A failed call
+ * changes no stream.  The fused step (k2hip_online_step) runs the same kernel. */
+int32_t k2hip_beam_stream_create(k2hip_model_t* model, int32_t beam /* 1..8 */, k2hip_beam_stream_t** out);
+int32_t k2hip_beam_stream_destroy(k2hip_beam_stream_t* s);
+int32_t k2hip_beam_stream_reset(k2hip_beam_stream_t* s);   /* back to the start state */
+int32_t k2hip_beam_search_chunk(k2hip_model_t* model, k2hip_beam_stream_t* const* streams, int32_t B, const float* enc_out, int32_t Tc);
+int32_t k2hip_beam_stream_num_tokens(const k2hip_beam_stream_t* s);
+int32_t k2hip_beam_stream_get_tokens(const k2hip_beam_stream_t* s, int64_t* tokens, int32_t cap);
+int32_t k2hip_beam_stream_get_timestamps(const k2hip_beam_stream_t* s, int32_t* timestamps, int32_t cap);
+int32_t k2hip_beam_stream_get_score(const k2hip_beam_stream_t* s, float* score);
 
 /* OfflineRecognizer.GetResults (:85-91) minus DecodeMulti: runs the fused batch
  * path on the streams' feature buffers, stores Tokens/Timestamps in each stream
@@ -337,6 +366,10 @@ int32_t k2hip_online_stream_is_finished(k2hip_online_stream_t* s, int32_t is_end
  * (RemoveChunk :102-117 drops ShiftLength frames), its Hyp / Tokens / Timestamps / caches are updated;
  * decoded[i] = 1 for those, 0 for streams that had no chunk (the reference removes them from the
  * caller's list, :117-120); n_new_tokens[i] = symbols emitted in this chunk.
+ * Under modified_beam_search (k2hip_set_decoding_method) the chunk continues the stream's beam search instead: Tokens /
+ * Timestamps / Hyp become the best hypothesis over all frames so far (absolute timestamps), n_new_tokens[i] is the signed change
+ * of its length -- re-read Tokens, earlier ones can change -- and a stream whose method or beam changed since its first chunk
+ * fails the call with K2HIP_ERR_INVALID until it is reset.
  * On failure no stream's host-side state has moved (no chunk removed, no token appended), but the DEVICE caches of the streams
  * that were being decoded may have advanced in place; those streams are marked and every later k2hip_online_step that names one
  * returns K2HIP_ERR_INVALID until k2hip_online_stream_reset -- the same chunk is never fed into caches that already moved. */
@@ -367,6 +400,9 @@ int32_t k2hip_online_stream_num_timestamps(const k2hip_online_stream_t* s);
 int32_t k2hip_online_stream_get_tokens(const k2hip_online_stream_t* s, int64_t* tokens, int32_t cap);
 int32_t k2hip_online_stream_get_timestamps(const k2hip_online_stream_t* s, int32_t* timestamps, int32_t cap);
 int32_t k2hip_online_stream_get_hyp(const k2hip_online_stream_t* s, int64_t* hyp2);
+/* log-prob of the best hypothesis of a stream under modified_beam_search (0 before its first chunk); K2HIP_ERR_INVALID for a
+ * stream that decodes with greedy_search */
+int32_t k2hip_online_stream_get_score(const k2hip_online_stream_t* s, float* score);
 /* copy one cache out of the stream's device slot (parity tests / debugging):
  * kind 0 cached_key [left,32H], 1 cached_nonlin_attn [left,3D/4], 2/3 cached_val1/2 [left,12H],
  * 4/5 cached_conv1/2 [D,K/2], 6 embed_states [128,3,19] (layer ignored); out == NULL queries n.

@@ -11,6 +11,7 @@ from __future__ import annotations
 
 from . import config, k2w, synth  # noqa: F401
 from .binding import (  # noqa: F401
+    BeamStream,
     K2HipError,
     Model,
     OfflineRecognizer,
@@ -27,6 +28,7 @@ from .binding import (  # noqa: F401
 )
 
 __all__ = [
+    "BeamStream",
     "K2HipError",
     "Model",
     "OfflineRecognizer",

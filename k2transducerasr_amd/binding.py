@@ -592,6 +592,15 @@ def _bind_online(L):
     L.k2hip_online_stream_get_timestamps.argtypes = [vp, ip, C.c_int32]
     L.k2hip_online_stream_get_hyp.argtypes = [vp, lp]
     L.k2hip_online_stream_state.argtypes = [vp, C.c_int32, C.c_int32, fp, C.c_int64, lp]
+    L.k2hip_online_stream_get_score.argtypes = [vp, fp]
+    L.k2hip_beam_stream_create.argtypes = [vp, C.c_int32, C.POINTER(vp)]
+    L.k2hip_beam_stream_destroy.argtypes = [vp]
+    L.k2hip_beam_stream_reset.argtypes = [vp]
+    L.k2hip_beam_search_chunk.argtypes = [vp, C.POINTER(vp), C.c_int32, fp, C.c_int32]
+    L.k2hip_beam_stream_num_tokens.argtypes = [vp]
+    L.k2hip_beam_stream_get_tokens.argtypes = [vp, lp, C.c_int32]
+    L.k2hip_beam_stream_get_timestamps.argtypes = [vp, ip, C.c_int32]
+    L.k2hip_beam_stream_get_score.argtypes = [vp, fp]
     L._online_bound = True
 
 
@@ -657,6 +666,13 @@ class OnlineStream:
         out = np.zeros(2, np.int64)
         self._m._chk(self._L.k2hip_online_stream_get_hyp(self._h, _l(out)))
         return out.tolist()
+
+    @property
+    def score(self) -> float:
+        """log-prob of the best hypothesis under modified_beam_search (k2hip_online_stream_get_score)"""
+        out = C.c_float()
+        self._m._chk(self._L.k2hip_online_stream_get_score(self._h, C.byref(out)))
+        return out.value
 
     @property
     def processed_len(self) -> int:
@@ -726,12 +742,73 @@ class OnlineProj:
         return self.model.joiner_proj(enc, dec)
 
 
-class OnlineRecognizer:
-    """OnlineRecognizer.cs:11-84 with decodingMethod = "greedy_search" on the HIP backend."""
+class BeamStream:
+    """Operator level of the streaming modified beam search (k2hip_beam_stream_*): one stream's hypotheses, continued over
+    encoder frames the caller computed (BeamStream.search_chunk).  tokens exclude the [blank, blank] prefix; timestamps are
+    absolute frame indexes."""
 
-    def __init__(self, weights_path: str, device: int = 0):
+    def __init__(self, model: Model, beam: int = 4):
+        self._m = model
+        self._L = model._L
+        _bind_online(self._L)
+        h = C.c_void_p()
+        model._chk(self._L.k2hip_beam_stream_create(model.handle, beam, C.byref(h)))
+        self._h = h
+        self.beam = beam
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.k2hip_beam_stream_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self):
+        self._m._chk(self._L.k2hip_beam_stream_reset(self._h))
+
+    @staticmethod
+    def search_chunk(streams: Sequence["BeamStream"], enc_out):
+        """continue every stream's search over enc_out [B, Tc, J] (k2hip_beam_search_chunk)"""
+        m = streams[0]._m
+        e = _f32(enc_out)
+        B, Tc = len(streams), e.shape[1]
+        assert e.ndim == 3 and e.shape[0] == B, e.shape
+        arr = (C.c_void_p * B)(*[s._h.value for s in streams])
+        m._chk(m._L.k2hip_beam_search_chunk(m.handle, arr, B, _f(e), Tc))
+
+    @property
+    def tokens(self) -> List[int]:
+        n = self._L.k2hip_beam_stream_num_tokens(self._h)
+        out = np.zeros(max(n, 1), np.int64)
+        self._m._chk(self._L.k2hip_beam_stream_get_tokens(self._h, _l(out), n))
+        return out[:n].tolist()
+
+    @property
+    def timestamps(self) -> List[int]:
+        n = self._L.k2hip_beam_stream_num_tokens(self._h)
+        out = np.zeros(max(n, 1), np.int32)
+        self._m._chk(self._L.k2hip_beam_stream_get_timestamps(self._h, _i(out), n))
+        return out[:n].tolist()
+
+    @property
+    def score(self) -> float:
+        out = C.c_float()
+        self._m._chk(self._L.k2hip_beam_stream_get_score(self._h, C.byref(out)))
+        return out.value
+
+
+class OnlineRecognizer:
+    """OnlineRecognizer.cs:11-84 on the HIP backend; decoding_method "greedy_search" (the reference's) or "modified_beam_search"
+    (hypotheses carried from chunk to chunk: include/k2hip.h)."""
+
+    def __init__(self, weights_path: str, device: int = 0, decoding_method: str = "greedy_search", beam: int = 4):
         self.model = Model(weights_path, device)
         _bind_online(self.model._L)
+        self.model.set_decoding_method(decoding_method, beam)
         a, b, c = C.c_int32(), C.c_int32(), C.c_int32()
         self.model._chk(self.model._L.k2hip_online_chunk_info(self.model.handle, C.byref(a), C.byref(b), C.byref(c)))
         self.chunk_length, self.shift_length, self.frames_per_chunk = a.value, b.value, c.value

@@ -3,11 +3,13 @@
 // OfflineRecognizer.cs:77-91,289-296).
 #include <algorithm>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <new>
 
 #include "text.h"
 #include "engine.h"
+#include "beam_hist.h"
 #include "../../include/k2hip_debug.h"
 
 using namespace k2hip;
@@ -118,6 +120,17 @@ struct k2hip_online_stream {
     // attention rings are idempotent: their position comes from chunks_done); feeding the same chunk again would then silently
     // corrupt the transcript.  Such a stream refuses every further step until k2hip_online_stream_reset.
     bool poisoned = false;
+    // decoding method the stream decoded its first chunk with (-1: none yet, 0: greedy_search, K: modified_beam_search with beam K);
+    // it holds until k2hip_online_stream_reset
+    int method = -1;
+    // modified_beam_search: the hypotheses carried between chunks; Tokens / Timestamps / Hyp are its best hypothesis
+    std::unique_ptr<BeamHistory> beam;
+};
+
+// operator level of the streaming beam search: one stream's hypotheses, fed encoder frames by the caller (k2hip_beam_search_chunk)
+struct k2hip_beam_stream {
+    k2hip_model* model;
+    BeamHistory hist;
 };
 
 // one stream's encoder caches as the operator-level API sees them (IOnlineProj's List<List<float[]>>): a slot of the device pool
@@ -771,11 +784,19 @@ int32_t k2hip_online_step(k2hip_model_t* model, k2hip_online_stream_t* const* st
         const Config& c = e.model().cfg();
         K2_REQUIRE(c.streaming || c.lstm, "this model is not a streaming export");
         const size_t chunk_floats = (size_t)c.chunk_T * c.feat, shift_floats = (size_t)c.shift * c.feat;
+        int K = 0;   // the search of this tick: 0 = greedy (and a CTC model's own search), K = modified beam search with beam K
+        if (!c.ctc) {
+            EngineLock lk(e);
+            K = e.beam();
+        }
         std::vector<int> idx;
         for (int i = 0; i < B; i++) {
             NEED(streams[i]);
             K2_REQUIRE(streams[i]->model == model, "stream %d belongs to another model", i);
             K2_REQUIRE(!streams[i]->poisoned, "stream %d took part in a chunk step that failed: its caches are undefined, reset it first", i);
+            K2_REQUIRE(streams[i]->method < 0 || streams[i]->method == K,
+                       "stream %d started decoding with %s (beam %d); the decoding method changed since -- reset the stream first", i,
+                       streams[i]->method > 0 ? "modified_beam_search" : "greedy_search", streams[i]->method);
             decoded[i] = 0;
             n_new_tokens[i] = 0;
             if ((size_t)online_logical_floats(streams[i]) >= chunk_floats) idx.push_back(i);   // GetDecodeChunk (:82-100)
@@ -833,13 +854,32 @@ int32_t k2hip_online_step(k2hip_model_t* model, k2hip_online_stream_t* const* st
             nch[r] = (int)(s->chunks_done % (1LL << 30));  // the kernels only need it modulo the ring lengths; (1 << 30) % KL drift is
                                                            // irrelevant before 2^30 chunks (~10 years of audio)
         }
-        std::vector<int64_t> tok((size_t)R * Tp);
-        std::vector<int32_t> ts((size_t)R * Tp), n(R);
+        std::vector<int64_t> tok;
+        std::vector<int32_t> ts, n;
+        std::vector<int> bin, bout;   // modified beam search: the streams' saved hypotheses in, the surviving ones out
+        const BeamResumeLayout RL{std::max(K, 1), Tp};
+        if (K > 0) {
+            bin.resize((size_t)R * RL.in_ints());
+            bout.resize((size_t)R * RL.out_ints());
+            for (int r = 0; r < R; r++) {
+                k2hip_online_stream* s = streams[idx[r]];
+                if (!s->beam) s->beam.reset(new BeamHistory(K, K2HIP_BLANK_ID));
+                s->beam->fill_in(bin.data() + (size_t)r * RL.in_ints(), Tp);
+            }
+        } else {
+            tok.resize((size_t)R * Tp);
+            ts.resize((size_t)R * Tp);
+            n.resize(R);
+        }
         if (!all_mirrored) fb.finish();   // the step reads some stream's chunk from host memory: the frames must be there
         try {
             EngineLock lk(e);
-            e.online_step(slots.data(), chunks.data(), hyps.data(), plens.data(), nch.data(), R, tok.data(), ts.data(), n.data(),
-                          all_mirrored ? heads.data() : nullptr);
+            if (K > 0)
+                e.online_step_beam(slots.data(), chunks.data(), plens.data(), nch.data(), R, K, bin.data(), bout.data(),
+                                   all_mirrored ? heads.data() : nullptr);
+            else
+                e.online_step(slots.data(), chunks.data(), hyps.data(), plens.data(), nch.data(), R, tok.data(), ts.data(), n.data(),
+                              all_mirrored ? heads.data() : nullptr);
         } catch (...) {
             // Host-side nothing has moved (RemoveChunk happens below), but the device caches of these streams may have: the step
             // updates the conv / embed caches in place.  A search exchange timeout is retried inside the engine and does not come
@@ -861,11 +901,20 @@ int32_t k2hip_online_step(k2hip_model_t* model, k2hip_online_stream_t* const* st
                 remirror.push_back(s);
             }
             s->chunks_done++;
-            for (int k = 0; k < n[r]; k++) {
+            s->method = K;
+            if (K > 0) {
+                // the best hypothesis replaces the result (it may revise earlier tokens): n_new_tokens = change of its length
+                const int64_t before = (int64_t)s->beam->tokens().size();
+                s->beam->apply_out(bout.data() + (size_t)r * RL.out_ints(), Tp);
+                s->hyp[0] = s->beam->hyp_last(0);
+                s->hyp[1] = s->beam->hyp_last(1);
+                n_new_tokens[idx[r]] = (int32_t)((int64_t)s->beam->tokens().size() - before);
+            }
+            for (int k = 0; K == 0 && k < n[r]; k++) {
                 s->tokens.push_back(tok[(size_t)r * Tp + k]);          // :183
                 s->timestamps.push_back(ts[(size_t)r * Tp + k]);       // :184 (chunk-relative frame index)
             }
-            if (!c.ctc) {  // the CTC delegate leaves Hyp alone (OnlineRecognizer.cs:302-310)
+            if (!c.ctc && K == 0) {  // the CTC delegate leaves Hyp alone (OnlineRecognizer.cs:302-310)
                 s->hyp[0] = s->tokens[s->tokens.size() - 2];           // :208
                 s->hyp[1] = s->tokens[s->tokens.size() - 1];
             }
@@ -873,7 +922,7 @@ int32_t k2hip_online_step(k2hip_model_t* model, k2hip_online_stream_t* const* st
             else if (c.zip1) s->processed_len += (c.chunk_T - 7) / 2;  // no processed_lens state in v1; kept as a frame counter
             else s->processed_len += (c.chunk_T - 7) / 2 - 3;      // new_processed_lens = processed_lens + x_lens
             decoded[idx[r]] = 1;
-            n_new_tokens[idx[r]] = n[r];
+            if (K == 0) n_new_tokens[idx[r]] = n[r];
         }
         if (!remirror.empty()) {
             EngineLock lk(e);
@@ -960,20 +1009,100 @@ int32_t k2hip_online_encoder(k2hip_model_t* model, k2hip_online_state_t* const* 
 }
 
 int64_t k2hip_online_stream_processed_len(const k2hip_online_stream_t* s) { return s ? (int64_t)s->processed_len : -1; }
-int32_t k2hip_online_stream_num_tokens(const k2hip_online_stream_t* s) { return s ? (int32_t)s->tokens.size() : -1; }
-int32_t k2hip_online_stream_num_timestamps(const k2hip_online_stream_t* s) { return s ? (int32_t)s->timestamps.size() : -1; }
+// Tokens / Timestamps: the greedy stream's own lists, or the best hypothesis of a stream under modified_beam_search
+static const std::vector<int64_t>& online_tokens(const k2hip_online_stream* s) { return s->method > 0 ? s->beam->tokens() : s->tokens; }
+static const std::vector<int32_t>& online_timestamps(const k2hip_online_stream* s) { return s->method > 0 ? s->beam->timestamps() : s->timestamps; }
+int32_t k2hip_online_stream_num_tokens(const k2hip_online_stream_t* s) { return s ? (int32_t)online_tokens(s).size() : -1; }
+int32_t k2hip_online_stream_num_timestamps(const k2hip_online_stream_t* s) { return s ? (int32_t)online_timestamps(s).size() : -1; }
 int32_t k2hip_online_stream_get_tokens(const k2hip_online_stream_t* s, int64_t* tokens, int32_t cap) {
     return guard([&] {
         NEED(s);
-        if ((int)s->tokens.size() > cap) failf(K2HIP_ERR_CAPACITY, "stream holds %zu tokens", s->tokens.size());
-        if (!s->tokens.empty()) { NEED(tokens); memcpy(tokens, s->tokens.data(), sizeof(int64_t) * s->tokens.size()); }
+        const std::vector<int64_t>& t = online_tokens(s);
+        if ((int)t.size() > cap) failf(K2HIP_ERR_CAPACITY, "stream holds %zu tokens", t.size());
+        if (!t.empty()) { NEED(tokens); memcpy(tokens, t.data(), sizeof(int64_t) * t.size()); }
     });
 }
 int32_t k2hip_online_stream_get_timestamps(const k2hip_online_stream_t* s, int32_t* timestamps, int32_t cap) {
     return guard([&] {
         NEED(s);
-        if ((int)s->timestamps.size() > cap) failf(K2HIP_ERR_CAPACITY, "stream holds %zu timestamps", s->timestamps.size());
-        if (!s->timestamps.empty()) { NEED(timestamps); memcpy(timestamps, s->timestamps.data(), sizeof(int32_t) * s->timestamps.size()); }
+        const std::vector<int32_t>& t = online_timestamps(s);
+        if ((int)t.size() > cap) failf(K2HIP_ERR_CAPACITY, "stream holds %zu timestamps", t.size());
+        if (!t.empty()) { NEED(timestamps); memcpy(timestamps, t.data(), sizeof(int32_t) * t.size()); }
+    });
+}
+int32_t k2hip_online_stream_get_score(const k2hip_online_stream_t* s, float* score) {
+    return guard([&] {
+        NEED(s); NEED(score);
+        K2_REQUIRE(s->method != 0, "the stream decodes with greedy_search: it has no hypothesis score");
+        *score = s->method > 0 ? s->beam->score() : 0.f;   // (no chunk yet: the start hypothesis, log-prob 0)
+    });
+}
+
+// ---- operator level of the streaming beam search ---------------------------------------------------------------------------------
+int32_t k2hip_beam_stream_create(k2hip_model_t* model, int32_t beam, k2hip_beam_stream_t** out) {
+    return guard([&] {
+        NEED(model); NEED(out);
+        *out = nullptr;
+        K2_REQUIRE(beam >= 1 && beam <= kMaxBeam, "beam stream: beam %d out of range [1,%d]", beam, kMaxBeam);
+        K2_REQUIRE(!model->engine.model().cfg().ctc, "beam stream: a CTC model has no transducer search");
+        *out = new k2hip_beam_stream{model, BeamHistory(beam, K2HIP_BLANK_ID)};
+    });
+}
+int32_t k2hip_beam_stream_destroy(k2hip_beam_stream_t* s) {
+    return guard([&] { delete s; });
+}
+int32_t k2hip_beam_stream_reset(k2hip_beam_stream_t* s) {
+    return guard([&] {
+        NEED(s);
+        s->hist.reset();
+    });
+}
+int32_t k2hip_beam_search_chunk(k2hip_model_t* model, k2hip_beam_stream_t* const* streams, int32_t B, const float* enc_out, int32_t Tc) {
+    return guard([&] {
+        NEED(model); NEED(streams); NEED(enc_out);
+        K2_REQUIRE(B > 0 && Tc >= 1, "beam search chunk: bad shape B=%d Tc=%d", B, Tc);
+        std::vector<const k2hip_beam_stream*> seen(streams, streams + B);
+        for (int b = 0; b < B; b++) {
+            NEED(streams[b]);
+            K2_REQUIRE(streams[b]->model == model, "beam stream %d belongs to another model", b);
+            K2_REQUIRE(streams[b]->hist.beam() == streams[0]->hist.beam(), "beam stream %d has beam %d, stream 0 has %d: one beam per call", b,
+                       streams[b]->hist.beam(), streams[0]->hist.beam());
+        }
+        std::sort(seen.begin(), seen.end());
+        K2_REQUIRE(std::adjacent_find(seen.begin(), seen.end()) == seen.end(), "beam search chunk: the same stream appears twice");
+        const int K = streams[0]->hist.beam();
+        const BeamResumeLayout L{K, Tc};
+        std::vector<int> bin((size_t)B * L.in_ints()), bout((size_t)B * L.out_ints());
+        for (int b = 0; b < B; b++) streams[b]->hist.fill_in(bin.data() + (size_t)b * L.in_ints(), Tc);
+        {
+            EngineLock lk(model->engine);
+            model->engine.beam_chunk_host(enc_out, B, Tc, K, bin.data(), bout.data());
+        }
+        // (only after success: a failed call leaves every stream as it was)
+        for (int b = 0; b < B; b++) streams[b]->hist.apply_out(bout.data() + (size_t)b * L.out_ints(), Tc);
+    });
+}
+int32_t k2hip_beam_stream_num_tokens(const k2hip_beam_stream_t* s) { return s ? (int32_t)s->hist.tokens().size() - 2 : -1; }
+int32_t k2hip_beam_stream_get_tokens(const k2hip_beam_stream_t* s, int64_t* tokens, int32_t cap) {
+    return guard([&] {
+        NEED(s);
+        const std::vector<int64_t>& t = s->hist.tokens();
+        if ((int)t.size() - 2 > cap) failf(K2HIP_ERR_CAPACITY, "beam stream holds %zu tokens", t.size() - 2);
+        if (t.size() > 2) { NEED(tokens); memcpy(tokens, t.data() + 2, sizeof(int64_t) * (t.size() - 2)); }
+    });
+}
+int32_t k2hip_beam_stream_get_timestamps(const k2hip_beam_stream_t* s, int32_t* timestamps, int32_t cap) {
+    return guard([&] {
+        NEED(s);
+        const std::vector<int32_t>& t = s->hist.timestamps();
+        if ((int)t.size() > cap) failf(K2HIP_ERR_CAPACITY, "beam stream holds %zu timestamps", t.size());
+        if (!t.empty()) { NEED(timestamps); memcpy(timestamps, t.data(), sizeof(int32_t) * t.size()); }
+    });
+}
+int32_t k2hip_beam_stream_get_score(const k2hip_beam_stream_t* s, float* score) {
+    return guard([&] {
+        NEED(s); NEED(score);
+        *score = s->hist.score();
     });
 }
 int32_t k2hip_online_stream_get_hyp(const k2hip_online_stream_t* s, int64_t* hyp2) {

@@ -10,6 +10,10 @@
 //   per stream: log_softmax + hyp score, top-K over K*V by (score desc, flat index asc), expand,
 //   merge equal token sequences by logaddexp (first-inserted hypothesis keeps its timestamps)   k_beam_step
 // Hypotheses live in double-buffered device arrays [2][B][K][cap]; ys excludes the ctx-blank prefix.
+// Streaming (BeamArgs::rin / rout, kernels.h BeamResumeLayout): the search starts from a stream's saved hypotheses instead of
+// [blank, blank]; a hypothesis is then (saved index org, suffix ys of this chunk), its decoder context falls back to the saved
+// context while the suffix is shorter than 2, and the merge test of two candidates from different saved hypotheses goes through the
+// host's relation table.  With rin == null every one of these is the offline search's own behaviour.
 #include <type_traits>
 
 #include "kernels.h"
@@ -30,6 +34,23 @@ __global__ void k_beam_init(BeamState s, int B) {
     s.ctx[2 * i] = K2HIP_BLANK_ID;
     s.ctx[2 * i + 1] = K2HIP_BLANK_ID;
     if (k == 0) s.nhyp[i / s.K] = 1;
+}
+// the saved hypotheses of every stream (resume): hypothesis k = saved hypothesis k with an empty suffix
+__global__ void k_beam_resume_init(BeamState s, int B) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B * s.K) return;
+    const int K = s.K, k = i % K, b = i / K;
+    const BeamResumeLayout L{K, s.Tp};
+    const int* in = s.rin + (long long)b * L.in_ints();
+    const int nh = in[0];
+    s.lp[i] = k < nh ? __int_as_float(in[L.in_lp() + k]) : -INFINITY;
+    s.n[i] = 0;
+    s.n[B * K + i] = 0;
+    s.org[i] = k;
+    s.org[B * K + i] = 0;
+    s.ctx[2 * i] = k < nh ? in[L.in_ctx() + 2 * k] : K2HIP_BLANK_ID;
+    s.ctx[2 * i + 1] = k < nh ? in[L.in_ctx() + 2 * k + 1] : K2HIP_BLANK_ID;
+    if (k == 0) s.nhyp[b] = nh;
 }
 
 // relu(Conv1d(k = 2) over (emb[y0], emb[y1]))[co]  (id < 0 -> zero embedding)
@@ -108,6 +129,11 @@ struct HypView {
     // debug tap (k2hip_debug.h, K2HIP_BEAM_TRACE) or null: this frame's record of this stream, 2 K + 1 words = the selected candidates'
     // flat indexes (slot * V + token) in rank order, their scores (float bits), the number of hypotheses after the merges
     int* trace = nullptr;
+    // resume (null: the offline search): saved-hypothesis index of each hypothesis at frame t / t + 1, the stream's in block
+    const int* org_c = nullptr;
+    int* org_n = nullptr;
+    const int* rin = nullptr;
+    int Tp = 0;
 };
 constexpr int kStepScratchInts = 4 * kMaxBeam + 4 + 2 * kMaxBeam * kMaxBeam;
 // one workgroup of NT threads per stream; lg: the hypotheses' logits, ldl floats per row; scratch: kStepScratchInts ints of LDS
@@ -226,13 +252,37 @@ __device__ void beam_step_body(const HypView& hv, const float* lg, int ldl, int 
             int r = 1, base = 0;
             while (base + r <= pi) { base += r; r++; }
             const int q = pi - base;
-            const int hr = topi[r] / V, tr = topi[r] % V, hq = topi[q] / V, tq = topi[q] % V;
+            int hr = topi[r] / V, tr = topi[r] % V, hq = topi[q] / V, tq = topi[q] % V;
+            // resume: candidates from different saved hypotheses -- r's saved sequence must be q's plus x (or the other way round, then
+            // the two swap roles): the sequences are equal iff x + suffix_r == suffix_q
+            int xl = 0;
+            const int* xp = nullptr;
+            bool e = true;
+            if (hv.org_c) {
+                const BeamResumeLayout L{K, hv.Tp};
+                const int orr = hv.org_c[hr], oq = hv.org_c[hq];
+                if (orr != oq) {
+                    const int lrq = hv.rin[L.in_rel() + orr * K + oq], lqr = hv.rin[L.in_rel() + oq * K + orr];
+                    if (lrq > 0) {
+                        xl = lrq;
+                        xp = hv.rin + L.in_relx() + (orr * K + oq) * hv.Tp;
+                    } else if (lqr > 0) {
+                        xl = lqr;
+                        xp = hv.rin + L.in_relx() + (oq * K + orr) * hv.Tp;
+                        const int h = hr, tk = tr;
+                        hr = hq; tr = tq; hq = h; tq = tk;
+                    } else {
+                        e = false;
+                    }
+                }
+            }
             const bool realr = tr != K2HIP_BLANK_ID && tr != K2HIP_UNK_ID, realq = tq != K2HIP_BLANK_ID && tq != K2HIP_UNK_ID;
             const int lenr = n_c[hr] + (realr ? 1 : 0), lenq = n_c[hq] + (realq ? 1 : 0);
-            bool e = lenr == lenq;
+            e = e && xl + lenr == lenq;
             if (e) {
-                for (int i = lane; i < lenr; i += 64) {
-                    const int x = (i < n_c[hr]) ? ys_c[(long long)hr * hv.cap + i] : tr;
+                for (int i = lane; i < lenq; i += 64) {
+                    const int j = i - xl;
+                    const int x = j < 0 ? xp[i] : (j < n_c[hr]) ? ys_c[(long long)hr * hv.cap + j] : tr;
                     const int y = (i < n_c[hq]) ? ys_c[(long long)hq * hv.cap + i] : tq;
                     e = e && x == y;
                 }
@@ -301,6 +351,7 @@ __device__ void beam_step_body(const HypView& hv, const float* lg, int ldl, int 
             hv.ctx[2 * k] = K2HIP_BLANK_ID;
             hv.ctx[2 * k + 1] = K2HIP_BLANK_ID;
             n_n[k] = 0;
+            if (hv.org_n) hv.org_n[k] = 0;
         }
         *hv.nhyp = nN;
         if (hv.trace) hv.trace[2 * K] = nN;
@@ -330,9 +381,17 @@ __device__ void beam_step_body(const HypView& hv, const float* lg, int ldl, int 
                 nn++;
             }
             n_n[slot] = nn;
-            // decoder context of the new hypothesis: last two of [blank, blank] + ys
-            long long y1 = nn >= 1 ? (realr ? tr : ys_c[(long long)hr * hv.cap + n0 - 1]) : K2HIP_BLANK_ID;
-            long long y0 = K2HIP_BLANK_ID;
+            // decoder context of the new hypothesis: last two of [c0, c1] + ys, [c0, c1] = the saved hypothesis' context (resume) or
+            // [blank, blank]
+            long long c0 = K2HIP_BLANK_ID, c1 = K2HIP_BLANK_ID;
+            if (hv.org_c) {
+                const int o = hv.org_c[hr];
+                hv.org_n[slot] = o;
+                c0 = hv.rin[BeamResumeLayout{K, hv.Tp}.in_ctx() + 2 * o];
+                c1 = hv.rin[BeamResumeLayout{K, hv.Tp}.in_ctx() + 2 * o + 1];
+            }
+            long long y1 = nn >= 1 ? (realr ? tr : ys_c[(long long)hr * hv.cap + n0 - 1]) : c1;
+            long long y0 = nn == 1 ? c1 : c0;
             if (nn >= 2) y0 = realr ? ys_c[(long long)hr * hv.cap + n0 - 1] : ys_c[(long long)hr * hv.cap + n0 - 2];
             hv.ctx[2 * slot] = y0;
             hv.ctx[2 * slot + 1] = y1;
@@ -357,7 +416,55 @@ __global__ __launch_bounds__(BT) void k_beam_step(BeamState s, const float* __re
     hv.ctx = s.ctx + 2 * (long long)b * K;
     hv.nhyp = s.nhyp + b;
     hv.trace = trace ? trace + ((long long)b * Tp + t) * (2 * K + 1) : nullptr;
+    if (s.org) {
+        hv.org_c = s.org + cur * BK + b * K;
+        hv.org_n = s.org + nxt * BK + b * K;
+        hv.rin = s.rin + (long long)b * BeamResumeLayout{K, s.Tp}.in_ints();
+        hv.Tp = s.Tp;
+    }
     beam_step_body<BT>(hv, logits + (long long)b * K * V, V, V, t, scratch);
+}
+
+// resume: every surviving hypothesis of the stream into its out block, and the best one (get_most_probable over the WHOLE
+// sequences: length = |saved| + |suffix| + the 2 ctx blanks, first maximum).  ys / ts / n / org: the final parity's [K][cap] / [K]
+// arrays of the stream.  Called by all threads of a workgroup.
+__device__ void beam_resume_write(const int* in, int* out, int K, int Tp, int cap, int nh, const float* lp, const long long* ctx,
+                                  const int* n, const int* org, const int* ys, const int* ts) {
+    const BeamResumeLayout L{K, Tp};
+    const int tid = threadIdx.x;
+    if (tid == 0) {
+        int best = 0;
+        float bs = -INFINITY;
+        for (int k = 0; k < nh; k++) {
+            const float v = lp[k] / (float)(in[L.in_len() + org[k]] + n[k] + 2);
+            if (k == 0 || v > bs) { bs = v; best = k; }
+        }
+        out[0] = nh;
+        out[1] = best;
+    }
+    for (int k = tid; k < K; k += blockDim.x) {
+        const bool live = k < nh;
+        out[L.out_org() + k] = live ? org[k] : 0;
+        out[L.out_n() + k] = live ? n[k] : 0;
+        out[L.out_lp() + k] = __float_as_int(live ? lp[k] : -INFINITY);
+        out[L.out_ctx() + 2 * k] = live ? (int)ctx[2 * k] : K2HIP_BLANK_ID;
+        out[L.out_ctx() + 2 * k + 1] = live ? (int)ctx[2 * k + 1] : K2HIP_BLANK_ID;
+    }
+    for (int i = tid; i < nh * Tp; i += blockDim.x) {
+        const int k = i / Tp, j = i - k * Tp;
+        if (j < n[k] && j < cap) {
+            out[L.out_ys() + i] = ys[(long long)k * cap + j];
+            out[L.out_ts() + i] = ts[(long long)k * cap + j];
+        }
+    }
+}
+__global__ void k_beam_resume_final(BeamState s, int fin, int B, int* __restrict__ rout) {
+    const int b = blockIdx.x, K = s.K;
+    const long long BK = (long long)B * K;
+    const BeamResumeLayout L{K, s.Tp};
+    beam_resume_write(s.rin + (long long)b * L.in_ints(), rout + (long long)b * L.out_ints(), K, s.Tp, s.cap, s.nhyp[b], s.lp + b * K,
+                      s.ctx + 2 * (long long)b * K, s.n + fin * BK + b * K, s.org + fin * BK + b * K,
+                      s.ys + (fin * BK + (long long)b * K) * s.cap, s.ts + (fin * BK + (long long)b * K) * s.cap);
 }
 
 // ---- the whole search of a stream in one kernel (small vocabularies: the model's all-contexts decoder table) -----------------
@@ -377,9 +484,10 @@ __device__ __forceinline__ void bstore_granule(unsigned long long* g, unsigned e
 __device__ __forceinline__ unsigned long long bload_granule(const unsigned long long* g) {
     return __hip_atomic_load((bgu64*)g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-// LDS (floats): actT[J GF] | psum | lg[GF][Vp] | ctx[2 GF] (long long) | lp[GF] | n[2][GF] | nhyp, pad | scratch | ys[2][K][cap] | ts[2][K][cap]
+// LDS (floats): actT[J GF] | psum | lg[GF][Vp] | ctx[2 GF] (long long) | lp[GF] | n[2][GF] | org[2][GF] | nhyp, pad | scratch |
+// ys[2][K][cap] | ts[2][K][cap]
 __host__ __device__ inline size_t beam_loop_lds_floats(int J, int Vp, int K, int cap, bool hyp_in_lds) {
-    return (size_t)J * GF + kPsumFloats + (size_t)GF * Vp + 4 * GF + GF + 2 * GF + 4 + kStepScratchInts + 4 + (hyp_in_lds ? 4 * (size_t)K * cap : 0);
+    return (size_t)J * GF + kPsumFloats + (size_t)GF * Vp + 4 * GF + GF + 2 * GF + 2 * GF + 4 + kStepScratchInts + 4 + (hyp_in_lds ? 4 * (size_t)K * cap : 0);
 }
 template <int NH>   // NH = 1: beam <= 4, the sweep forms only rows 0..3
 __global__ __launch_bounds__(GT) void k_beam_loop(DecJoinW w, BeamLoopArgs a) {
@@ -390,7 +498,8 @@ __global__ __launch_bounds__(GT) void k_beam_loop(DecJoinW w, BeamLoopArgs a) {
     long long* ctx = reinterpret_cast<long long*>(lg + GF * w.Vp);   // (J GF, the psum size and GF Vp are multiples of 4 floats)
     float* lp = reinterpret_cast<float*>(ctx + 2 * GF);
     int* nbuf = reinterpret_cast<int*>(lp + GF);       // [2][GF]
-    int* nhyp = nbuf + 2 * GF;
+    int* orgb = nbuf + 2 * GF;                          // [2][GF] (resume)
+    int* nhyp = orgb + 2 * GF;
     int* scratch = nhyp + 4;
     int* ys = a.ys_g ? a.ys_g + (size_t)blockIdx.x * 2 * a.K * a.cap : scratch + kStepScratchInts + 4;
     int* ts = a.ys_g ? a.ts_g + (size_t)blockIdx.x * 2 * a.K * a.cap : ys + 2 * a.K * a.cap;
@@ -399,13 +508,26 @@ __global__ __launch_bounds__(GT) void k_beam_loop(DecJoinW w, BeamLoopArgs a) {
     if (tid == 0) xfail = 0;
     const int b = a.xg ? blockIdx.x >> 1 : blockIdx.x, slab = a.xg ? blockIdx.x & 1 : 0;
     const float* enc = a.enc + (long long)b * a.Tp * w.J;
-    if (tid < GF) {   // k_beam_init
-        lp[tid] = tid == 0 ? 0.f : -INFINITY;
+    const BeamResumeLayout RL{K, a.Tp};
+    const int* rin = a.rin ? a.rin + (long long)b * RL.in_ints() : nullptr;
+    if (tid < GF) {   // k_beam_init / k_beam_resume_init
         nbuf[tid] = 0;
         nbuf[GF + tid] = 0;
-        ctx[2 * tid] = K2HIP_BLANK_ID;
-        ctx[2 * tid + 1] = K2HIP_BLANK_ID;
-        if (tid == 0) *nhyp = 1;
+        orgb[tid] = tid;
+        orgb[GF + tid] = 0;
+        if (rin) {
+            const int nh = rin[0];
+            const bool live = tid < nh && tid < K;
+            lp[tid] = live ? __int_as_float(rin[RL.in_lp() + tid]) : -INFINITY;
+            ctx[2 * tid] = live ? rin[RL.in_ctx() + 2 * tid] : K2HIP_BLANK_ID;
+            ctx[2 * tid + 1] = live ? rin[RL.in_ctx() + 2 * tid + 1] : K2HIP_BLANK_ID;
+            if (tid == 0) *nhyp = nh;
+        } else {
+            lp[tid] = tid == 0 ? 0.f : -INFINITY;
+            ctx[2 * tid] = K2HIP_BLANK_ID;
+            ctx[2 * tid + 1] = K2HIP_BLANK_ID;
+            if (tid == 0) *nhyp = 1;
+        }
     }
     __syncthreads();
     const int kper = w.J >> 3, ncg = w.Vp >> 2;
@@ -537,12 +659,23 @@ __global__ __launch_bounds__(GT) void k_beam_loop(DecJoinW w, BeamLoopArgs a) {
         hv.ys_n = ys + (size_t)(cur ^ 1) * K * a.cap; hv.ts_n = ts + (size_t)(cur ^ 1) * K * a.cap; hv.n_n = nbuf + (cur ^ 1) * GF;
         hv.lp = lp; hv.ctx = ctx; hv.nhyp = nhyp;
         hv.trace = (a.trace && slab == 0) ? a.trace + ((long long)b * a.Tp + t) * (2 * K + 1) : nullptr;
+        if (rin) {
+            hv.org_c = orgb + cur * GF;
+            hv.org_n = orgb + (cur ^ 1) * GF;
+            hv.rin = rin;
+            hv.Tp = a.Tp;
+        }
         beam_step_body<GT>(hv, lg, w.Vp, w.V, t, scratch);
         __syncthreads();
     }
     // k_beam_final: max of log_prob / len(ys) (len counts the 2 ctx blanks), first maximum
     const int fin = a.Tp & 1;
     const int* n_f = nbuf + fin * GF;
+    if (rin) {   // (resume runs one workgroup per stream: no slabs)
+        beam_resume_write(rin, a.rout + (long long)b * RL.out_ints(), K, a.Tp, a.cap, *nhyp, lp, ctx, n_f, orgb + fin * GF,
+                          ys + (size_t)fin * K * a.cap, ts + (size_t)fin * K * a.cap);
+        return;
+    }
     int best = 0;
     float bs = lp[0] / (float)(n_f[0] + 2);
     for (int k = 1; k < *nhyp; k++) {
@@ -613,7 +746,7 @@ void beam_search(const Ctx& ctx, const DecJoinW& w, const BeamArgs& a) {
             // the offline co-residency budget: the frame's sweep is bound by ONE CU's fetch of the 1 MB matrix, two CUs halve it, and the
             // exchange of the 4 x 256 logits costs less than the half sweep (search alone 5.5 -> 4.45 ms for the headline batch).  The
             // slabs wait for each other (bounded; *overflow = 2 on a timeout): the launch is kept for a repeat with one slab.
-            const bool two = !ctx.one_part && tunables().beam_parts != 1 && K <= 4 && (w.Vp >> 2) <= 128 && (w.Vp >> 2) > 64 && 2 * B <= std::max(device_cu_count() / 4, 2);
+            const bool two = !a.rin && !ctx.one_part && tunables().beam_parts != 1 && K <= 4 && (w.Vp >> 2) <= 128 && (w.Vp >> 2) > 64 && 2 * B <= std::max(device_cu_count() / 4, 2);
             unsigned long long* xg = two ? ar.take<unsigned long long>((int64_t)B * 2 * 2 * 4 * 256) : nullptr;
             // (hypotheses in device memory: every workgroup keeps its own copy, so two slabs need twice the space)
             int* ys_g = hyp_in_lds ? nullptr : ar.take<int>((int64_t)(two ? 2 : 1) * 2 * M * cap);
@@ -626,6 +759,7 @@ void beam_search(const Ctx& ctx, const DecJoinW& w, const BeamArgs& a) {
             la.ys_g = ys_g; la.ts_g = ts_g;
             la.xg = xg;
             la.trace = a.trace;
+            la.rin = a.rin; la.rout = a.rout;
             K2_HIP(hipMemsetAsync(a.overflow, 0, sizeof(int), ctx.stream));
             static LdsAttrOnce lds_attr;
             static LdsAttrOnce lds_attr1;
@@ -661,12 +795,18 @@ void beam_search(const Ctx& ctx, const DecJoinW& w, const BeamArgs& a) {
     s.ctx_next = s.ctx;
     s.nhyp = ar.take<int>(B);
     s.nhyp_next = s.nhyp;
+    if (a.rin) {
+        s.org = ar.take<int>((int64_t)2 * M);
+        s.rin = a.rin;
+        s.Tp = a.Tp;
+    }
     float* hbuf = ar.take<float>((int64_t)M * w.DD);
     float* act = ar.take<float>((int64_t)M * w.J);
     float* logits = ar.take<float>((int64_t)M * w.V);
     if (!ctx.dry) {
         K2_HIP(hipMemsetAsync(a.overflow, 0, sizeof(int), ctx.stream));
-        hipLaunchKernelGGL(k_beam_init, dim3(cdiv(M, 256)), dim3(256), 0, ctx.stream, s, B);
+        if (a.rin) hipLaunchKernelGGL(k_beam_resume_init, dim3(cdiv(M, 256)), dim3(256), 0, ctx.stream, s, B);
+        else hipLaunchKernelGGL(k_beam_init, dim3(cdiv(M, 256)), dim3(256), 0, ctx.stream, s, B);
         K2_HIP(hipGetLastError());
     }
     for (int t = 0; t < a.Tp; t++) {
@@ -688,8 +828,9 @@ void beam_search(const Ctx& ctx, const DecJoinW& w, const BeamArgs& a) {
         }
     }
     if (!ctx.dry) {
-        hipLaunchKernelGGL(k_beam_final, dim3(B), dim3(256), 0, ctx.stream, s, a.Tp & 1, B, a.tokens, a.timestamps, a.n_tokens, a.scores,
-                           a.max_tokens, a.overflow);
+        if (a.rin) hipLaunchKernelGGL(k_beam_resume_final, dim3(B), dim3(256), 0, ctx.stream, s, a.Tp & 1, B, a.rout);
+        else hipLaunchKernelGGL(k_beam_final, dim3(B), dim3(256), 0, ctx.stream, s, a.Tp & 1, B, a.tokens, a.timestamps, a.n_tokens, a.scores,
+                                a.max_tokens, a.overflow);
         K2_HIP(hipGetLastError());
     }
 }

@@ -1,0 +1,230 @@
+// Host side of the streaming modified beam search: the hypotheses a stream carries from one chunk to the next.
+//
+// The device search of a chunk starts from the saved hypotheses (beam.hip, BeamResumeLayout) and never sees their whole token
+// sequences; what it needs of them is, per pair (a, b), whether H_a = H_b + x with a short x (|x| <= T' of the chunk).  The histories
+// live here as two trees of refcounted nodes:
+//   - SeqTree, hash-consed: one node per distinct token sequence ((parent, token) -> node), so node identity IS sequence identity
+//     and the relation of a pair costs at most T' parent steps, whatever the length of the transcript.  (Without hash-consing a
+//     prefix that was pruned and later spelled again would get a second node: a false "different".)
+//   - PathTree, plain: (parent, token, timestamp) per hypothesis -- two hypotheses with the same tokens may carry different
+//     timestamps (the first-inserted one's are kept at a merge, but an equal sequence can be spelled again later).
+// Nodes no hypothesis reaches any more are freed (and their slot reused), so memory follows the live beam, not the stream's age.
+// Plain C++ (no HIP): tests/native builds it on the CPU.
+#pragma once
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <unordered_map>
+#include <vector>
+
+namespace k2hip {
+
+// nodes with parent links and reference counts (children + holders); node 0 is the root (the empty sequence) and is never freed
+class RefTree {
+  public:
+    struct Node {
+        int parent, tok, ts, depth, refs;
+    };
+    RefTree() { clear(); }
+    void clear() {
+        nodes_.assign(1, Node{-1, -1, -1, 0, 1});
+        free_.clear();
+    }
+    const Node& operator[](int i) const { return nodes_[(size_t)i]; }
+    int parent(int i) const { return nodes_[(size_t)i].parent; }
+    int depth(int i) const { return nodes_[(size_t)i].depth; }
+    void ref(int i) { nodes_[(size_t)i].refs++; }
+    // drops one reference; a node nobody refers to is freed, then its parent loses the reference the child held
+    template <typename OnFree>
+    void unref(int i, OnFree&& on_free) {
+        while (i > 0 && --nodes_[(size_t)i].refs == 0) {
+            on_free(i);
+            const int p = nodes_[(size_t)i].parent;
+            free_.push_back(i);
+            i = p;
+        }
+    }
+    size_t live() const { return nodes_.size() - free_.size(); }
+
+  protected:
+    int make(int parent, int tok, int ts) {
+        int id;
+        const Node n{parent, tok, ts, nodes_[(size_t)parent].depth + 1, 0};
+        if (!free_.empty()) {
+            id = free_.back();
+            free_.pop_back();
+            nodes_[(size_t)id] = n;
+        } else {
+            id = (int)nodes_.size();
+            nodes_.push_back(n);
+        }
+        nodes_[(size_t)parent].refs++;
+        return id;
+    }
+    std::vector<Node> nodes_;
+    std::vector<int> free_;
+};
+
+class SeqTree : public RefTree {
+  public:
+    void clear() {
+        RefTree::clear();
+        index_.clear();
+    }
+    // the node of sequence(parent) + [tok], created if it does not exist
+    int child(int parent, int tok) {
+        const uint64_t key = ((uint64_t)(uint32_t)parent << 32) | (uint32_t)tok;
+        auto it = index_.find(key);
+        if (it != index_.end()) return it->second;
+        const int id = make(parent, tok, -1);
+        index_.emplace(key, id);
+        return id;
+    }
+    void unref(int i) {
+        RefTree::unref(i, [&](int n) { index_.erase(((uint64_t)(uint32_t)nodes_[(size_t)n].parent << 32) | (uint32_t)nodes_[(size_t)n].tok); });
+    }
+    // |x| if sequence(a) = sequence(b) + x with 0 < |x| <= cap (x's tokens into x[0..|x|)), else -1
+    int extension(int a, int b, int cap, int* x) const {
+        const int L = depth(a) - depth(b);
+        if (L <= 0 || L > cap) return -1;
+        int p = a;
+        for (int i = L - 1; i >= 0; i--) {
+            x[i] = nodes_[(size_t)p].tok;
+            p = nodes_[(size_t)p].parent;
+        }
+        return p == b ? L : -1;
+    }
+
+  private:
+    std::unordered_map<uint64_t, int> index_;
+};
+
+class PathTree : public RefTree {
+  public:
+    int child(int parent, int tok, int ts) { return make(parent, tok, ts); }
+    void unref(int i) {
+        RefTree::unref(i, [](int) {});
+    }
+};
+
+// One stream's hypotheses between chunks and its result (the best hypothesis, materialised incrementally).
+class BeamHistory {
+  public:
+    struct Hyp {
+        int seq, path;     // SeqTree / PathTree nodes
+        float lp;
+        int ctx[2];        // decoder context: the last two tokens of [blank, blank] + ys
+    };
+    explicit BeamHistory(int K = 1, int blank = 0) : K_(K), blank_(blank) { reset(); }
+    int beam() const { return K_; }
+    void reset() {
+        seq_.clear();
+        path_.clear();
+        hyps_.assign(1, Hyp{0, 0, 0.f, {blank_, blank_}});
+        best_ = 0;
+        frames_ = 0;
+        mat_path_ = 0;
+        mat_ids_.clear();
+        tokens_.assign(2, blank_);
+        timestamps_.clear();
+    }
+    const std::vector<Hyp>& hyps() const { return hyps_; }
+    int best() const { return best_; }
+    long long frames() const { return frames_; }
+    float score() const { return hyps_[(size_t)best_].lp; }
+    // Tokens = [blank, blank] + ys of the best hypothesis; Timestamps = its absolute frame indexes
+    const std::vector<int64_t>& tokens() const { return tokens_; }
+    const std::vector<int32_t>& timestamps() const { return timestamps_; }
+    const SeqTree& seq_tree() const { return seq_; }
+
+    // the device search's in block (kernels.h BeamResumeLayout{K, Tp}) for the next chunk of Tp frames
+    void fill_in(int* in, int Tp) const {
+        const int K = K_, nh = (int)hyps_.size();
+        const int o_lp = 1, o_ctx = 1 + K, o_len = 1 + 3 * K, o_rel = 1 + 4 * K, o_relx = 1 + 4 * K + K * K;
+        memset(in, 0, sizeof(int) * (size_t)(o_relx + K * K * Tp));
+        in[0] = nh;
+        for (int k = 0; k < K; k++) {
+            const bool live = k < nh;
+            const float lp = live ? hyps_[(size_t)k].lp : -INFINITY;
+            memcpy(&in[o_lp + k], &lp, sizeof(float));
+            in[o_ctx + 2 * k] = live ? hyps_[(size_t)k].ctx[0] : blank_;
+            in[o_ctx + 2 * k + 1] = live ? hyps_[(size_t)k].ctx[1] : blank_;
+            in[o_len + k] = live ? seq_.depth(hyps_[(size_t)k].seq) : 0;
+            for (int j = 0; j < K; j++) {
+                int& r = in[o_rel + k * K + j];
+                if (k == j) r = 0;
+                else if (!live || j >= nh) r = -1;
+                else r = seq_.extension(hyps_[(size_t)k].seq, hyps_[(size_t)j].seq, Tp, &in[o_relx + (k * K + j) * Tp]);
+            }
+        }
+    }
+    // the device search's out block of that chunk: the new hypotheses, the best one, the result
+    void apply_out(const int* out, int Tp) {
+        const int K = K_, nh = out[0];
+        const int o_org = 2, o_n = 2 + K, o_lp = 2 + 2 * K, o_ctx = 2 + 3 * K, o_ys = 2 + 5 * K, o_ts = 2 + 5 * K + K * Tp;
+        std::vector<Hyp> nx((size_t)nh);
+        for (int k = 0; k < nh; k++) {
+            const Hyp& p = hyps_[(size_t)out[o_org + k]];
+            int sq = p.seq, ph = p.path;
+            for (int i = 0; i < out[o_n + k]; i++) {
+                const int tok = out[o_ys + k * Tp + i];
+                sq = seq_.child(sq, tok);
+                ph = path_.child(ph, tok, (int)(frames_ + out[o_ts + k * Tp + i]));
+            }
+            Hyp& h = nx[(size_t)k];
+            h.seq = sq;
+            h.path = ph;
+            memcpy(&h.lp, &out[o_lp + k], sizeof(float));
+            h.ctx[0] = out[o_ctx + 2 * k];
+            h.ctx[1] = out[o_ctx + 2 * k + 1];
+            seq_.ref(sq);
+            path_.ref(ph);
+        }
+        for (const Hyp& h : hyps_) {   // (after the new ones hold their references: shared prefixes survive)
+            seq_.unref(h.seq);
+            path_.unref(h.path);
+        }
+        hyps_.swap(nx);
+        best_ = out[1];
+        frames_ += Tp;
+        materialise(hyps_[(size_t)best_].path);
+    }
+    int hyp_last(int i) const { return hyps_[(size_t)best_].ctx[i]; }
+
+  private:
+    // tokens_ / timestamps_ := the path of node `to`; only the part past the longest prefix still shared with the last result is
+    // rewritten (the last result's end node is referenced, so ids on its path are not reused while mat_ids_ names them)
+    void materialise(int to) {
+        std::vector<int> tail;
+        int p = to;
+        while (p != 0 && !(path_.depth(p) <= (int)mat_ids_.size() && mat_ids_[(size_t)path_.depth(p) - 1] == p)) {
+            tail.push_back(p);
+            p = path_.parent(p);
+        }
+        const size_t keep = (size_t)path_.depth(p);
+        mat_ids_.resize(keep);
+        tokens_.resize(2 + keep);
+        timestamps_.resize(keep);
+        for (size_t i = tail.size(); i-- > 0;) {
+            mat_ids_.push_back(tail[i]);
+            tokens_.push_back(path_[tail[i]].tok);
+            timestamps_.push_back(path_[tail[i]].ts);
+        }
+        path_.ref(to);
+        path_.unref(mat_path_);
+        mat_path_ = to;
+    }
+
+    int K_, blank_;
+    SeqTree seq_;
+    PathTree path_;
+    std::vector<Hyp> hyps_;
+    int best_ = 0;
+    long long frames_ = 0;
+    int mat_path_ = 0;
+    std::vector<int> mat_ids_;
+    std::vector<int64_t> tokens_;
+    std::vector<int32_t> timestamps_;
+};
+
+}  // namespace k2hip

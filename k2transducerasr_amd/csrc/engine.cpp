@@ -714,6 +714,48 @@ void Engine::beam_device(const Ctx& c, const float* enc, int B, int Tp, long lon
     beam_search(c, decjoin(), a);
 }
 
+// modified beam search resumed from saved hypotheses (streaming chunk; BeamResumeLayout{K, Tp} blocks on the device)
+void Engine::beam_resume_device(const Ctx& c, const float* enc, int B, int Tp, int K, const int* d_in, int* d_out, int* d_overflow) {
+    BeamArgs a;
+    a.enc = enc; a.out_w = model_->w("joiner.output_linear.weight");
+    a.dproj_w = model_->w("joiner.decoder_proj.weight");
+    a.B = B; a.Tp = Tp; a.beam = K;
+    a.tokens = nullptr; a.timestamps = nullptr; a.n_tokens = nullptr; a.scores = nullptr; a.max_tokens = 0;
+    a.overflow = d_overflow;
+    a.rin = d_in; a.rout = d_out;
+    beam_search(c, decjoin(), a);
+}
+
+void Engine::beam_chunk_host(const float* enc, int B, int Tp, int K, const int* beam_in, int* beam_out) {
+    K2_REQUIRE(B > 0 && Tp > 0, "beam chunk: bad shape B=%d T'=%d", B, Tp);
+    K2_REQUIRE(K >= 1 && K <= kMaxBeam, "beam chunk: beam %d out of range [1,%d]", K, kMaxBeam);
+    const Config& cf = model_->cfg();
+    K2_REQUIRE(!cf.ctc, "beam chunk: a CTC model has no transducer search");
+    const BeamResumeLayout L{K, Tp};
+    // ONE upload [enc | in blocks] and ONE download [flag | out blocks]
+    const int64_t nb_enc = (int64_t)sizeof(float) * B * Tp * cf.J, nb_in = (int64_t)sizeof(int) * B * L.in_ints(),
+                  nb_out = (int64_t)sizeof(int) * B * L.out_ints();
+    const int64_t o_in = align_up(nb_enc, 16), o_ovf = align_up(o_in + nb_in, 16), in_bytes = o_ovf + 16;
+    K2_HIP(hipSetDevice(device_));
+    char* stage = static_cast<char*>(pinned_in(in_bytes));
+    memcpy(stage, enc, (size_t)nb_enc);
+    memcpy(stage + o_in, beam_in, (size_t)nb_in);
+    memset(stage + o_ovf, 0, 16);
+    int* d_ovf = nullptr;
+    run_sized([&](const Ctx& c) {
+        char* d = c.arena->take<char>(in_bytes + nb_out);
+        d_ovf = reinterpret_cast<int*>(d + o_ovf);
+        if (!c.dry) K2_HIP(hipMemcpyAsync(d, stage, (size_t)in_bytes, hipMemcpyHostToDevice, c.stream));
+        beam_resume_device(c, reinterpret_cast<const float*>(d), B, Tp, K, reinterpret_cast<const int*>(d + o_in),
+                           reinterpret_cast<int*>(d + in_bytes), d_ovf);
+    });
+    char* pin = static_cast<char*>(pinned(16 + nb_out));
+    K2_HIP(hipMemcpyAsync(pin, d_ovf, (size_t)(16 + nb_out), hipMemcpyDeviceToHost, stream_));
+    K2_HIP(hipStreamSynchronize(stream_));
+    if (*reinterpret_cast<int*>(pin)) failf(K2HIP_ERR_HIP, "beam chunk: a hypothesis outgrew its buffer");
+    memcpy(beam_out, pin + 16, (size_t)nb_out);
+}
+
 // Back-off of the parted searches.  A search whose column slabs are not co-resident (other handles or processes on the GPU hold the
 // CUs) spins to its bound, reports the timeout and is repeated with one workgroup per stream -- correct, but the timeout costs
 // milliseconds, every call (four streaming recognizers on one GPU: 12.6 ms per tick against 4.2).  After a timeout the next 4

@@ -109,6 +109,13 @@ class Engine {
     // on the device and `chunks` is not read
     void online_step(const int* slots, const float* const* chunks, const long long* hyps, const long long* plens, const int* nchunks, int B,
                      int64_t* tokens, int32_t* ts, int32_t* n_tokens, const int* fifo_heads = nullptr);
+    // the same tick under modified beam search with beam K, resumed from each stream's saved hypotheses: beam_in [B] blocks of
+    // BeamResumeLayout{K, T'}.in_ints() ints (uploaded with the tick's inputs), beam_out [B] blocks of out_ints() (the tick's one
+    // download).  Transducer models only.
+    void online_step_beam(const int* slots, const float* const* chunks, const long long* plens, const int* nchunks, int B, int K,
+                          const int* beam_in, int* beam_out, const int* fifo_heads = nullptr);
+    // operator level of the resumed search: enc [B, Tp, J] host, in / out blocks of BeamResumeLayout{K, Tp} (host)
+    void beam_chunk_host(const float* enc, int B, int Tp, int K, const int* beam_in, int* beam_out);
 
     void set_instrument(bool on) { instrument_ = on; }
     const std::vector<GemmLaunchRec>& gemm_log() const { return gemm_log_; }
@@ -158,6 +165,10 @@ class Engine {
                     int* d_overflow);
     void beam_device(const Ctx& c, const float* enc, int B, int Tp, long long* d_tok, int* d_ts, int* d_n, int max_tokens,
                      int* d_overflow);
+    void beam_resume_device(const Ctx& c, const float* enc, int B, int Tp, int K, const int* d_in, int* d_out, int* d_overflow);
+    struct OnlineBeamIO { int K; const int* in; int* out; };
+    void online_step_impl(const int* slots, const float* const* chunks, const long long* hyps, const long long* plens, const int* nchunks,
+                          int B, int64_t* tokens, int32_t* ts, int32_t* n_tokens, const int* fifo_heads, const OnlineBeamIO* beam);
     // LSTM transducer (lstm_engine.cpp)
     int lstm_out_frames(int T) const;
     float* lstm_embed(const Ctx& c, const float* x, int B, int T, int* T_out);

@@ -424,6 +424,9 @@ struct BeamLoopArgs {
     // logits per frame as tagged granules xg[b][frame parity][slab][4][256]; null = one workgroup per stream
     unsigned long long* xg;
     int* trace = nullptr;   // debug tap [B][Tp][2 K + 1] (beam_step_body) or null
+    // streaming resume (BeamResume below): per-stream in / out blocks, or null for the offline search
+    const int* rin = nullptr;
+    int* rout = nullptr;
 };
 struct GreedyLaunch {
     bool valid = false;  // a launch with inter-workgroup waits (parts > 1 / two beam slabs) that can be repeated without them
@@ -445,8 +448,33 @@ void greedy_rounds(const Ctx& ctx, const DecJoinW& w, const float* out_w, const 
 
 // ---- modified beam search (beam.hip) ------------------------------------------------------------
 constexpr int kMaxBeam = 8;
+// A search that resumes from saved hypotheses (streaming: one chunk of Tp frames per call).  Hypothesis j of the saved set is
+// H_j (its whole token sequence, which only the host keeps); inside the chunk a hypothesis is (saved index, suffix of <= Tp tokens).
+// Two candidates from different saved hypotheses spell the same sequence only if one saved sequence is the other plus a short
+// suffix x: rel[a][b] = |x| when H_a = H_b + x with 0 < |x| <= Tp (x = relx[a][b]), else -1 (0 on the diagonal).
+// Per stream, `in` (ints):  [nhyp | lp[K] (float bits) | ctx[K][2] | len[K] (|H_j|) | rel[K][K] | relx[K][K][Tp]]
+//             `out` (ints): [nhyp | best | org[K] | n[K] | lp[K] (float bits) | ctx[K][2] | ys[K][Tp] | ts[K][Tp] (chunk-relative)]
+struct BeamResumeLayout {
+    int K, Tp;
+    __host__ __device__ int in_ints() const { return 1 + 4 * K + K * K + K * K * Tp; }
+    __host__ __device__ int in_lp() const { return 1; }
+    __host__ __device__ int in_ctx() const { return 1 + K; }
+    __host__ __device__ int in_len() const { return 1 + 3 * K; }
+    __host__ __device__ int in_rel() const { return 1 + 4 * K; }
+    __host__ __device__ int in_relx() const { return 1 + 4 * K + K * K; }
+    __host__ __device__ int out_ints() const { return 2 + 5 * K + 2 * K * Tp; }
+    __host__ __device__ int out_org() const { return 2; }
+    __host__ __device__ int out_n() const { return 2 + K; }
+    __host__ __device__ int out_lp() const { return 2 + 2 * K; }
+    __host__ __device__ int out_ctx() const { return 2 + 3 * K; }
+    __host__ __device__ int out_ys() const { return 2 + 5 * K; }
+    __host__ __device__ int out_ts() const { return 2 + 5 * K + K * Tp; }
+};
 struct BeamState {       // device arrays; hypotheses double-buffered by frame parity
     int K, cap;
+    int* org = nullptr;  // [2][B][K] saved-hypothesis index of each hypothesis (resume only)
+    const int* rin = nullptr;   // resume in blocks [B][in_ints] or null
+    int Tp = 0;
     int* ys;             // [2][B][K][cap] tokens without the ctx-blank prefix
     int* ts;             // [2][B][K][cap]
     int* n;              // [2][B][K]
@@ -466,6 +494,10 @@ struct BeamArgs {
     int max_tokens;
     int* overflow;
     int* trace = nullptr;  // debug tap [B][Tp][2 beam + 1] or null (k2hip_debug.h: k2hip_debug_beam_trace)
+    // streaming resume (BeamResumeLayout): start from the saved hypotheses in rin [B][in_ints] instead of [blank, blank] and write
+    // every surviving hypothesis to rout [B][out_ints] instead of the best one to tokens / timestamps / n_tokens / scores
+    const int* rin = nullptr;
+    int* rout = nullptr;
 };
 void beam_search(const Ctx& ctx, const DecJoinW& w, const BeamArgs& a);
 

@@ -491,6 +491,18 @@ float* Engine::online_encoder_zip2(const Ctx& c, const float* d_x, const int* d_
 
 void Engine::online_step(const int* slots, const float* const* chunks, const long long* hyps, const long long* plens, const int* nchunks, int B,
                          int64_t* tokens, int32_t* ts, int32_t* n_tokens, const int* fifo_heads) {
+    online_step_impl(slots, chunks, hyps, plens, nchunks, B, tokens, ts, n_tokens, fifo_heads, nullptr);
+}
+void Engine::online_step_beam(const int* slots, const float* const* chunks, const long long* plens, const int* nchunks, int B, int K,
+                              const int* beam_in, int* beam_out, const int* fifo_heads) {
+    K2_REQUIRE(K >= 1 && K <= kMaxBeam, "online beam search: beam %d out of range [1,%d]", K, kMaxBeam);
+    K2_REQUIRE(!model_->cfg().ctc, "online beam search: a CTC model runs its own search");
+    std::vector<long long> hyps(2 * (size_t)B, K2HIP_BLANK_ID);   // (the greedy search's context input; unused by the beam search)
+    OnlineBeamIO io{K, beam_in, beam_out};
+    online_step_impl(slots, chunks, hyps.data(), plens, nchunks, B, nullptr, nullptr, nullptr, fifo_heads, &io);
+}
+void Engine::online_step_impl(const int* slots, const float* const* chunks, const long long* hyps, const long long* plens, const int* nchunks,
+                              int B, int64_t* tokens, int32_t* ts, int32_t* n_tokens, const int* fifo_heads, const OnlineBeamIO* beam) {
     online_ensure_pool();
     K2_REQUIRE(B > 0, "online_step: no ready stream");
     const Model& m = *model_;
@@ -505,9 +517,14 @@ void Engine::online_step(const int* slots, const float* const* chunks, const lon
     // ONE upload per tick: [chunks' frames (only when they are not on the device yet) | plens | hyps | slots | chunk counts | FIFO heads |
     // overflow flag = 0], packed in pinned staging in the device block's layout (five small copies from pageable memory + a memset were
     // six blit launches of ~4 us each at the head of the step); ONE download: [tokens | timestamps | counts | overflow flag]
+    // Under beam search the upload carries the streams' saved hypotheses and relation tables too (in front of the flag), and the
+    // download is [flag | the surviving hypotheses' out blocks] instead of the greedy tokens.
+    const BeamResumeLayout RL{beam ? beam->K : 1, Tp};
+    const int64_t nb_bin = beam ? (int64_t)sizeof(int) * RL.in_ints() * B : 0, nb_bout = beam ? (int64_t)sizeof(int) * RL.out_ints() * B : 0;
     const int64_t nb_x = from_fifo ? 0 : (int64_t)sizeof(float) * chunk_floats * B;
     const int64_t o_plen = align_up(nb_x, 16), o_hyp = o_plen + 8 * (int64_t)B, o_slots = o_hyp + 16 * (int64_t)B, o_chunks = o_slots + 4 * (int64_t)B,
-                  o_heads = o_chunks + 4 * (int64_t)B, o_ovf = align_up(o_heads + 4 * (int64_t)B, 16), in_bytes = o_ovf + 16;
+                  o_heads = o_chunks + 4 * (int64_t)B, o_bin = align_up(o_heads + 4 * (int64_t)B, 16), o_ovf = align_up(o_bin + nb_bin, 16),
+                  in_bytes = o_ovf + 16;
     char* stage = static_cast<char*>(pinned_in(in_bytes));
     if (!from_fifo)
         for (int b = 0; b < B; b++) memcpy(stage + (size_t)b * chunk_floats * sizeof(float), chunks[b], sizeof(float) * chunk_floats);
@@ -517,8 +534,9 @@ void Engine::online_step(const int* slots, const float* const* chunks, const lon
     memcpy(stage + o_chunks, nchunks, sizeof(int) * B);
     if (from_fifo) memcpy(stage + o_heads, fifo_heads, sizeof(int) * B);
     else memset(stage + o_heads, 0, sizeof(int) * B);
+    if (beam) memcpy(stage + o_bin, beam->in, (size_t)nb_bin);
     memset(stage + o_ovf, 0, 16);
-    const int64_t nb_tok = (int64_t)B * Tp * 8, nb_ts = (int64_t)B * Tp * 4, nb_n = (int64_t)B * 4;
+    const int64_t nb_tok = beam ? nb_bout : (int64_t)B * Tp * 8, nb_ts = beam ? 0 : (int64_t)B * Tp * 4, nb_n = beam ? 0 : (int64_t)B * 4;
     run_sized([&](const Ctx& c) {
         Arena& ar = *c.arena;
         // one device block: the inputs, the overflow flag (uploaded as zero: the last 16 bytes of the input part), the outputs right
@@ -535,6 +553,8 @@ void Engine::online_step(const int* slots, const float* const* chunks, const lon
         int* d_slots = reinterpret_cast<int*>(d_in + o_slots);
         int* d_chunks = reinterpret_cast<int*>(d_in + o_chunks);
         int* d_heads = reinterpret_cast<int*>(d_in + o_heads);
+        const int* d_bin = reinterpret_cast<const int*>(d_in + o_bin);
+        int* d_bout = reinterpret_cast<int*>(d_out);
         if (!c.dry) {
             K2_HIP(hipEventRecord(ev_[0], c.stream));
             K2_HIP(hipMemcpyAsync(d_in, stage, (size_t)in_bytes, hipMemcpyHostToDevice, c.stream));
@@ -551,6 +571,11 @@ void Engine::online_step(const int* slots, const float* const* chunks, const lon
             float* enc = cf.lstm ? lstm_chunk(c, d_x, d_slots, B) : cf.zip1 ? zip1_chunk(c, d_x, d_slots, B, &tc) : conformer_chunk(c, d_x, d_slots, d_plen, B, &tc);
             K2_REQUIRE(tc == Tp, "internal: chunk yields %d frames, expected %d", tc, Tp);
             if (ev_ok) K2_HIP(hipEventRecord(ev_[3], c.stream));
+            if (beam) {
+                beam_resume_device(c, enc, B, Tp, beam->K, d_bin, d_bout, d_ovf);
+                if (ev_ok) K2_HIP(hipEventRecord(ev_[4], c.stream));
+                return;
+            }
             GreedyArgs a;
             a.enc = enc; a.B = B; a.Tp = Tp; a.t0 = nullptr; a.skip1 = 1; a.max_sym = INT_MAX;
             a.tokens = d_tok; a.timestamps = d_ts; a.n_tokens = d_n; a.max_tokens = Tp; a.overflow = d_ovf; a.init_ctx = d_hyp;
@@ -567,6 +592,11 @@ void Engine::online_step(const int* slots, const float* const* chunks, const lon
             if (ev_ok) K2_HIP(hipEventRecord(ev_[4], c.stream));
             return;
         }
+        if (beam) {   // modified beam search resumed from the streams' saved hypotheses, on the tick's encoder buffer
+            beam_resume_device(c, enc, B, Tp, beam->K, d_bin, d_bout, d_ovf);
+            if (ev_ok) K2_HIP(hipEventRecord(ev_[4], c.stream));
+            return;
+        }
         // OnlineRecognizer.cs:135-202: decoder on the streams' hyps, T' joiner steps, skip {blank, unk, 1}
         GreedyArgs a;
         a.enc = enc; a.B = B; a.Tp = Tp; a.t0 = nullptr; a.skip1 = 1; a.max_sym = INT_MAX;
@@ -575,7 +605,16 @@ void Engine::online_step(const int* slots, const float* const* chunks, const lon
         else greedy_rounds(c, decjoin(), model_->w("joiner.output_linear.weight"), a);
         if (ev_ok) K2_HIP(hipEventRecord(ev_[4], c.stream));
     });
-    finish_tokens(d_tok, d_ts, d_n, d_ovf, B, Tp, tokens, ts, n_tokens);
+    if (beam) {   // ONE download: [flag | out blocks]
+        char* pin = static_cast<char*>(pinned(16 + nb_bout));
+        K2_HIP(hipMemcpyAsync(pin, d_ovf, (size_t)(16 + nb_bout), hipMemcpyDeviceToHost, stream_));
+        K2_HIP(hipEventRecord(ev_[5], stream_));
+        K2_HIP(hipStreamSynchronize(stream_));
+        if (*reinterpret_cast<int*>(pin)) failf(K2HIP_ERR_HIP, "online beam search: a hypothesis outgrew its buffer");
+        memcpy(beam->out, pin + 16, (size_t)nb_bout);
+    } else {
+        finish_tokens(d_tok, d_ts, d_n, d_ovf, B, Tp, tokens, ts, n_tokens);
+    }
     auto el = [&](int a, int b) { float ms = 0; (void)hipEventElapsedTime(&ms, ev_[a], ev_[b]); return ms; };
     timing_.fbank_ms = 0;
     timing_.pad_ms = 0;

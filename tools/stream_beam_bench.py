@@ -1,0 +1,87 @@
+"""Streaming tick under modified beam search next to greedy, on the same audio.
+
+    python tools/stream_beam_bench.py [preset] [streams] [seconds] [beam]      (defaults: zipformer2-streaming-zh 128 20 4)
+
+N streams of the synthetic `preset` model each buffer an utterance of `seconds` s; the tool decodes all of them chunk by chunk
+(one k2hip_online_step per tick over the whole group) once with greedy_search and once with modified_beam_search, reports the
+median ms per tick of each, and holds the first few streams' beam results to the CPU oracle (k2o_modified_beam_search over the
+oracle's own concatenated chunks; a difference is excused only where the oracle's margin at the first differing frame is below
+LOGIT_TOL).  One JSON line on stdout."""
+import json
+import os
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+
+from k2transducerasr_amd import OnlineRecognizer  # noqa: E402
+from k2transducerasr_amd.synth import synth_utterance, write_synthetic_model  # noqa: E402
+
+preset = sys.argv[1] if len(sys.argv) > 1 else "zipformer2-streaming-zh"
+N = int(sys.argv[2]) if len(sys.argv) > 2 else 128
+secs = float(sys.argv[3]) if len(sys.argv) > 3 else 20.0
+beam = int(sys.argv[4]) if len(sys.argv) > 4 else 4
+CHECK = 3
+DISTINCT = 8
+
+
+def run(rec, feats, method, k):
+    rec.model.set_decoding_method(method, k)
+    hs = [rec.create_online_stream() for _ in feats]
+    for h, f in zip(hs, feats):
+        h.add_features(f)
+    group = rec.batch(hs)
+    ms = []
+    while True:
+        t0 = time.perf_counter()
+        dec, _ = rec.get_results(group)
+        dt = (time.perf_counter() - t0) * 1e3
+        if not any(dec):
+            break
+        ms.append(dt)
+    res = [(h.tokens[2:], h.timestamps) for h in hs]
+    for h in hs:
+        h.close()
+    return ms, res
+
+
+def main():
+    with tempfile.TemporaryDirectory() as d:
+        path = os.path.join(d, f"{preset}.k2w")
+        write_synthetic_model(path, preset)
+        rec = OnlineRecognizer(path)
+        from oracle.online import OnlineOracle
+        ora = OnlineOracle(path)
+        base = [ora.fbank(synth_utterance(300 + u, secs)) for u in range(DISTINCT)]
+        feats = [base[u % DISTINCT] for u in range(N)]
+        run(rec, feats[: min(N, 8)], "greedy_search", 0)          # warm-up: arenas, decoder tables
+        g_ms, _ = run(rec, feats, "greedy_search", 0)
+        b_ms, b_res = run(rec, feats, "modified_beam_search", beam)
+        import parity
+        from test_online_beam_gpu import oracle_frames
+        exact = excused = 0
+        for u in range(min(CHECK, N)):
+            enc, _ = oracle_frames(ora, base[u % DISTINCT])
+            (want,), margins = ora.modified_beam_search(enc[None], beam, want_margins=True)
+            got = b_res[u]
+            if (list(got[0]), list(got[1])) == (want[0], want[1]):
+                exact += 1
+                continue
+            t = min([a for a, (x, y) in enumerate(zip(got[1], want[1])) if x != y] + [min(len(got[1]), len(want[1]))])
+            frame = want[1][t] if t < len(want[1]) else got[1][t]
+            if margins[0, min(frame, margins.shape[1] - 1)] >= parity.LOGIT_TOL:
+                raise SystemExit(f"stream {u}: beam result differs from the oracle at frame {frame} (margin {margins[0, frame]:.2e})")
+            excused += 1
+        # the first ticks include one-time work (pos-emb tables, arena growth): the median is the steady tick
+        print(json.dumps({"preset": preset, "streams": N, "seconds": secs, "beam": beam, "ticks": len(b_ms),
+                          "greedy_ms_per_tick": round(float(np.median(g_ms)), 3), "beam_ms_per_tick": round(float(np.median(b_ms)), 3),
+                          "beam_over_greedy": round(float(np.median(b_ms) / np.median(g_ms)), 3),
+                          "oracle_checked": min(CHECK, N), "oracle_exact": exact, "oracle_excused": excused}))
+
+
+if __name__ == "__main__":
+    main()
