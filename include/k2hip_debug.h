@@ -52,6 +52,23 @@ int32_t k2hip_debug_stream_mirrored(const k2hip_online_stream_t* s, int32_t* ok)
  * kernel does not write shows.  tests/test_gemm_gpu.py compares the result with a float64 product computed on the host. */
 int32_t k2hip_debug_gemm_run(k2hip_model_t* model, const float* A, const float* W, const float* bias, const float* res, float* C,
                              int32_t M, int32_t N, int32_t K, int32_t act, int32_t glu, int32_t glu_cols, int32_t cfg);
+/* ---- other encoder kernels ---------------------------------------------------------------------- */
+/* ONE launch of the launcher named `op` (csrc/kernels.h: attn_scores_softmax, attn_av_out, attn_av_out_ring, attn_proj_av_out_ring,
+ * nonlin_av_out_ring, attn_stream_ring, attn_stream, glu_causal_conv, biasnorm, bypass, biasnorm_bypass, biasnorm_bypass_downsample,
+ * downsample, downsample_full, upsample_combine, upsample_combine_downsample, glu_dwconv1d_swoosh, glu_dwconv1d_dswish, dwconv1d_swoosh,
+ * dwconv7x7) on host operands, on the engine's stream.  iargs: the launcher's integer arguments in its own order (a RingRef counts as
+ * slot_stride, off; downsample_full's segments put n, ld[n], col1[n], lz_Td, lz_ds, lz_Do in front).  bufs / buf_bytes: its pointer
+ * arguments in order (a RingRef as pool, slots, chunks; the segments as src[n], lz_orig, lz_xd, lz_scale), each uploaded whole -- in
+ * place operands (x of attn_av_out, the state pool, int arrays) work as they are; NULL or 0 bytes passes a null pointer.  Every buffer
+ * sits between two 16 KB guards of 0xff bytes (NaN): a read past either end that reaches the result shows as NaN, and a guard that
+ * changed fails the call (K2HIP_ERR_INVALID, naming the buffer).  After the launch the buffers flagged in out_mask (bit k = bufs[k]) are
+ * downloaded.  A shape the launcher refuses returns K2HIP_ERR_UNSUPPORTED with nothing launched and nothing downloaded.  Branch
+ * switches (K2HIP_ATTN_LONG, K2HIP_DW1D_TT, K2HIP_DW7_TILED) go through k2hip_debug_set_switch.  tests/test_kernels_gpu.py compares each
+ * kernel with a float64 reference computed on the host. */
+int32_t k2hip_debug_op_run(k2hip_model_t* model, const char* op, const int64_t* iargs, int32_t n_iargs, void* const* bufs,
+                           const int64_t* buf_bytes, int32_t n_bufs, uint32_t out_mask);
+
+/* ---- GEMM tuning ------------------------------------------------------------------------------- */
 /* time `iters` launches of a shape / configuration on pseudo-random operands (tools/gemm_lab.py, gemm_tune.py) */
 int32_t k2hip_debug_gemm(k2hip_model_t* model, int32_t M, int32_t N, int32_t K, int32_t act, int32_t with_res, int32_t cfg,
                          int32_t iters, float* ms);

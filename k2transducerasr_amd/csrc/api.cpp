@@ -1206,6 +1206,16 @@ int32_t k2hip_debug_gemm_run(k2hip_model_t* model, const float* A, const float* 
     });
 }
 
+int32_t k2hip_debug_op_run(k2hip_model_t* model, const char* op, const int64_t* iargs, int32_t n_iargs, void* const* bufs,
+                           const int64_t* buf_bytes, int32_t n_bufs, uint32_t out_mask) {
+    return guard([&] {
+        NEED(model); NEED(op);
+        if (!Engine::debug_op) failf(K2HIP_ERR_UNSUPPORTED, "debug_op_run: this build has no kernels");
+        EngineLock lk(model->engine);
+        (model->engine.*Engine::debug_op)(op, iargs, n_iargs, bufs, buf_bytes, n_bufs, out_mask);
+    });
+}
+
 int32_t k2hip_debug_gemm_trace(k2hip_model_t* model, int32_t M, int32_t N, int32_t K, int32_t act,
                                                                        int32_t with_res, int32_t cfg, unsigned long long* out, int64_t cap,
                                                                        int32_t* n_wg, int32_t* n_waves) {

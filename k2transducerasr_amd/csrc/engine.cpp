@@ -1561,6 +1561,191 @@ void Engine::debug_gemm_host(const float* hA, const float* hW, const float* hb, 
     K2_HIP(copy_blocking(hC, d.C, sizeof(float) * (size_t)M * ldo, hipMemcpyDeviceToHost));
 }
 
+// test hook: ONE launch of a launcher of kernels.h on the caller's host operands (tests/test_kernels_gpu.py).  Buffer k of the call is
+// uploaded into an allocation with kGuard bytes of 0xff (NaN) on either side, so a read past either end whose value reaches the result
+// shows as NaN; after the launch the guards must still hold 0xff, else a write went past the buffer and the call fails naming it.
+// A launcher that refuses the shape (a false return, a K2_REQUIRE) fails as K2HIP_ERR_UNSUPPORTED before anything is launched or
+// downloaded.  iargs: the launcher's int arguments in its own order, a RingRef counting as (slot_stride, off); bufs: its pointer
+// arguments in order, a RingRef as (pool, slots, chunks), a FullDimSegs as (src[0 .. n), lz_orig, lz_xd, lz_scale) with its ints
+// (n, ld[0 .. n), col1[0 .. n), lz_Td, lz_ds, lz_Do) in front of the launcher's.  A null buffer (or 0 bytes) passes nullptr.
+static const bool kDebugOpSet = (Engine::debug_op = &Engine::debug_op_host, true);
+void Engine::debug_op_host(const char* op, const int64_t* iargs, int n_iargs, void* const* bufs, const int64_t* buf_bytes, int n_bufs,
+                           uint32_t out_mask) {
+    K2_HIP(hipSetDevice(device_));
+    K2_REQUIRE(op && n_iargs >= 0 && n_bufs >= 0 && n_bufs <= 32 && (n_iargs == 0 || iargs) && (n_bufs == 0 || (bufs && buf_bytes)),
+               "debug_op_run: bad arguments");
+    constexpr int64_t kGuard = 16 * 1024;
+    struct Bufs {
+        hipStream_t stream;
+        std::vector<char*> base;
+        ~Bufs() {
+            (void)hipStreamSynchronize(stream);   // (a launcher that failed after a launch: nothing is freed under a running kernel)
+            for (char* p : base) (void)hipFree(p);
+        }
+    } d{stream_, {}};
+    std::vector<void*> dev(n_bufs, nullptr);
+    for (int k = 0; k < n_bufs; k++) {
+        K2_REQUIRE(buf_bytes[k] >= 0 && buf_bytes[k] % 4 == 0, "debug_op_run: buffer %d has %lld bytes", k, (long long)buf_bytes[k]);
+        if (!bufs[k] || buf_bytes[k] == 0) continue;
+        char* p = nullptr;
+        const size_t total = (size_t)(2 * kGuard + buf_bytes[k]);
+        K2_HIP(hipMalloc(&p, total));
+        d.base.push_back(p);
+        K2_HIP(fill_blocking(p, 0xff, total));
+        K2_HIP(copy_blocking(p + kGuard, bufs[k], (size_t)buf_bytes[k], hipMemcpyHostToDevice));
+        dev[k] = p + kGuard;
+    }
+    int ni = 0, nbuf = 0;
+    auto I = [&]() -> int {
+        K2_REQUIRE(ni < n_iargs, "debug_op_run %s: too few int arguments (%d)", op, n_iargs);
+        return (int)iargs[ni++];
+    };
+    auto L = [&]() -> long long {
+        K2_REQUIRE(ni < n_iargs, "debug_op_run %s: too few int arguments (%d)", op, n_iargs);
+        return (long long)iargs[ni++];
+    };
+    auto P = [&]() -> float* {
+        K2_REQUIRE(nbuf < n_bufs, "debug_op_run %s: too few buffers (%d)", op, n_bufs);
+        return static_cast<float*>(dev[nbuf++]);
+    };
+    auto ring = [&]() {   // (pool, slots, chunks) buffers, (slot_stride, off) ints
+        RingRef r;
+        r.slot_stride = L(); r.off = L();
+        r.pool = P(); r.slots = reinterpret_cast<const int*>(P()); r.chunks = reinterpret_cast<const int*>(P());
+        return r;
+    };
+    Ctx c = make_ctx(false);
+    c.instrument = false;
+    c.stats = nullptr;
+    const std::string name = op;
+    bool took = true;
+    try {
+        if (name == "attn_scores_softmax") {
+            const int ld = I();
+            float *qkp = P(), *pp = P(), *aw = P();
+            const int B = I(), T = I(), Tp = I(), H = I(), qh = I(), koff0 = I(), poff0 = I();
+            attn_scores_softmax(c, qkp, ld, pp, aw, B, T, Tp, H, qh, koff0, poff0);
+        } else if (name == "attn_av_out") {
+            float *aw = P(), *v = P(), *wout = P(), *bias = P(), *x = P();
+            const int B = I(), T = I(), KL = I(), Tp = I(), H = I(), vh = I(), D = I();
+            took = attn_av_out(c, aw, v, wout, bias, x, B, T, KL, Tp, H, vh, D);
+        } else if (name == "attn_av_out_ring") {
+            float* aw = P();
+            const RingRef r = ring();
+            float *newrows = P(), *wout = P(), *bias = P(), *x = P();
+            const int B = I(), T = I(), KL = I(), Tp = I(), H = I(), vh = I(), D = I();
+            took = attn_av_out_ring(c, aw, r, newrows, wout, bias, x, B, T, KL, Tp, H, vh, D);
+        } else if (name == "attn_proj_av_out_ring") {
+            float* aw = P();
+            const RingRef r = ring();
+            float *xin = P(), *win = P(), *bin = P(), *wout = P(), *bias = P(), *xout = P();
+            const int B = I(), T = I(), KL = I(), Tp = I(), H = I(), vh = I(), D = I();
+            attn_proj_av_out_ring(c, aw, r, xin, win, bin, wout, bias, xout, B, T, KL, Tp, H, vh, D);
+        } else if (name == "nonlin_av_out_ring") {
+            float* aw = P();
+            const RingRef r = ring();
+            float* hid = P();
+            const int ldh = I();
+            float *wout = P(), *bias = P(), *x = P();
+            const int B = I(), T = I(), KL = I(), Tp = I(), Hc = I(), D = I();
+            nonlin_av_out_ring(c, aw, r, hid, ldh, wout, bias, x, B, T, KL, Tp, Hc, D);
+        } else if (name == "attn_stream_ring" || name == "attn_stream") {
+            float* qkp = P();
+            const int ld = I();
+            RingRef r;
+            float* kcat = nullptr;
+            if (name == "attn_stream_ring") r = ring(); else kcat = P();
+            float* pp = P();
+            const long long* plen = reinterpret_cast<const long long*>(P());
+            float* aw = P();
+            const int B = I(), Tc = I(), Lc = I(), KLp = I(), H = I(), ds = I(), left50 = I();
+            if (kcat) attn_stream(c, qkp, ld, kcat, pp, plen, aw, B, Tc, Lc, KLp, H, ds, left50);
+            else attn_stream_ring(c, qkp, ld, r, pp, plen, aw, B, Tc, Lc, KLp, H, ds, left50);
+        } else if (name == "glu_causal_conv") {
+            float *x2 = P(), *pool = P();
+            const long long ss = L(), off = L();
+            const int* slots = reinterpret_cast<const int*>(P());
+            float *wc = P(), *bc = P(), *ww = P(), *bw = P(), *sc = P(), *y = P();
+            const int B = I(), Tc = I(), D = I(), K = I();
+            glu_causal_conv(c, x2, pool, ss, off, slots, wc, bc, ww, bw, sc, y, B, Tc, D, K);
+        } else if (name == "biasnorm") {
+            float *x = P(), *bias = P(), *ls = P(), *y = P();
+            const int M = I(), D = I();
+            biasnorm(c, x, bias, ls, y, M, D);
+        } else if (name == "bypass") {
+            float *orig = P(), *x = P(), *scale = P(), *y = P();
+            const int M = I(), D = I();
+            bypass(c, orig, x, scale, y, M, D);
+        } else if (name == "biasnorm_bypass") {
+            float *x = P(), *orig = P(), *nb = P(), *ls = P(), *scale = P(), *y = P();
+            const int M = I(), D = I();
+            biasnorm_bypass(c, x, orig, nb, ls, scale, y, M, D);
+        } else if (name == "biasnorm_bypass_downsample") {
+            float *x = P(), *orig = P(), *nb = P(), *ls = P(), *scale = P(), *y = P(), *bias2 = P(), *xd2 = P();
+            const int B = I(), T = I(), D = I(), ds2 = I(), D2 = I();
+            biasnorm_bypass_downsample(c, x, orig, nb, ls, scale, y, bias2, xd2, B, T, D, ds2, D2);
+        } else if (name == "downsample") {
+            float *x = P(), *bias = P(), *y = P();
+            const int B = I(), T = I(), D = I(), ds = I(), Din = I();
+            downsample(c, x, bias, y, B, T, D, ds, Din);
+        } else if (name == "downsample_full") {
+            FullDimSegs s;
+            s.n = I();
+            K2_REQUIRE(s.n >= 1 && s.n <= 8, "debug_op_run downsample_full: %d segments", s.n);
+            for (int k = 0; k < s.n; k++) s.ld[k] = I();
+            for (int k = 0; k < s.n; k++) s.col1[k] = I();
+            s.lz_Td = I(); s.lz_ds = I(); s.lz_Do = I();
+            for (int k = 0; k < s.n; k++) s.src[k] = P();
+            s.lz_orig = P(); s.lz_xd = P(); s.lz_scale = P();
+            float *bias = P(), *y = P();
+            const int B = I(), T = I(), D = I(), ds = I();
+            downsample_full(c, s, bias, y, B, T, D, ds);
+        } else if (name == "upsample_combine") {
+            float *orig = P(), *xd = P(), *scale = P(), *y = P();
+            const int B = I(), T = I(), Td = I(), D = I(), ds = I(), Dorig = I();
+            upsample_combine(c, orig, xd, scale, y, B, T, Td, D, ds, Dorig);
+        } else if (name == "upsample_combine_downsample") {
+            float *orig = P(), *xd = P(), *scale = P(), *y = P(), *bias2 = P(), *xd2 = P();
+            const int B = I(), T = I(), Td = I(), D = I(), ds = I(), Dorig = I(), D2 = I(), ds2 = I();
+            upsample_combine_downsample(c, orig, xd, scale, y, bias2, xd2, B, T, Td, D, ds, Dorig, D2, ds2);
+        } else if (name == "glu_dwconv1d_swoosh" || name == "glu_dwconv1d_dswish" || name == "dwconv1d_swoosh") {
+            float *x = P(), *w = P(), *b = P(), *y = P();
+            const int B = I(), T = I(), D = I(), K = I();
+            if (name == "glu_dwconv1d_swoosh") glu_dwconv1d_swoosh(c, x, w, b, y, B, T, D, K);
+            else if (name == "glu_dwconv1d_dswish") glu_dwconv1d_dswish(c, x, w, b, y, B, T, D, K);
+            else dwconv1d_swoosh(c, x, w, b, y, B, T, D, K);
+        } else if (name == "dwconv7x7") {
+            float *x = P(), *w = P(), *b = P(), *y = P();
+            const int B = I(), Tin = I(), Tout = I(), tpad = I(), F = I(), C = I();
+            dwconv7x7(c, x, w, b, y, B, Tin, Tout, tpad, F, C);
+        } else {
+            failf(K2HIP_ERR_INVALID, "debug_op_run: unknown op '%s'", op);
+        }
+    } catch (const Error& e) {
+        // a shape the launcher refuses; argument-count mistakes of the caller stay INVALID
+        if (e.code == K2HIP_ERR_INVALID && strncmp(e.what(), "debug_op_run", 12) != 0) throw Error(K2HIP_ERR_UNSUPPORTED, e.what());
+        throw;
+    }
+    if (!took) failf(K2HIP_ERR_UNSUPPORTED, "debug_op_run %s: the launcher does not take this shape", op);
+    K2_REQUIRE(ni == n_iargs && nbuf == n_bufs, "debug_op_run %s: %d int arguments and %d buffers passed, %d and %d used", op, n_iargs, n_bufs, ni,
+               nbuf);
+    K2_HIP(hipStreamSynchronize(stream_));
+    std::vector<unsigned char> g((size_t)kGuard);
+    for (int k = 0; k < n_bufs; k++) {
+        if (!dev[k]) continue;
+        const char* p = static_cast<const char*>(dev[k]);
+        for (int side = 0; side < 2; side++) {
+            K2_HIP(copy_blocking(g.data(), side ? p + buf_bytes[k] : p - kGuard, (size_t)kGuard, hipMemcpyDeviceToHost));
+            for (int64_t i = 0; i < kGuard; i++)
+                if (g[(size_t)i] != 0xff)
+                    failf(K2HIP_ERR_INVALID, "debug_op_run %s: buffer %d written %s its end (guard byte %lld)", op, k, side ? "past" : "before",
+                          (long long)(side ? i : kGuard - i));
+        }
+    }
+    for (int k = 0; k < n_bufs; k++)
+        if (dev[k] && (out_mask >> k & 1u)) K2_HIP(copy_blocking(bufs[k], dev[k], (size_t)buf_bytes[k], hipMemcpyDeviceToHost));
+}
+
 // tuning hook: ONE launch of the ring kernel `cfg` (>= 100) with in-kernel s_memtime stamps; out [n_wg][n_waves][64]
 void Engine::debug_gemm_trace(int M, int N, int K, int act, bool with_res, int cfg, unsigned long long* out, int64_t cap, int* n_wg, int* n_waves) {
     K2_HIP(hipSetDevice(device_));

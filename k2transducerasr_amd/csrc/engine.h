@@ -139,6 +139,15 @@ class Engine {
     void debug_gemm_host(const float* A, const float* W, const float* bias, const float* res, float* C, int M, int N, int K, int act,
                          int glu, int glu_cols, int cfg);
     void debug_gemm_trace(int M, int N, int K, int act, bool with_res, int cfg, unsigned long long* out, int64_t cap, int* n_wg, int* n_waves);
+    // test hook: ONE launch of the launcher `op` (kernels.h) on host operands, every buffer uploaded into a NaN-guarded allocation, the
+    // guards checked after the launch, the buffers flagged in out_mask downloaded (k2hip_debug.h: k2hip_debug_op_run)
+    void debug_op_host(const char* op, const int64_t* iargs, int n_iargs, void* const* bufs, const int64_t* buf_bytes, int n_bufs,
+                       uint32_t out_mask);
+    // ... reached by api.cpp through this pointer, which engine.cpp sets when the library loads: the host-only builds of api.cpp
+    // (tests/native, over a CPU stand-in of the engine) have no kernels to launch, the pointer stays null there and the hook reports
+    // K2HIP_ERR_UNSUPPORTED
+    using DebugOpFn = void (Engine::*)(const char*, const int64_t*, int, void* const*, const int64_t*, int, uint32_t);
+    static inline DebugOpFn debug_op = nullptr;
     void* dev_alloc(int64_t bytes);
     void dev_free(void* p);
     void dev_upload(void* dst, const void* src, int64_t bytes);

@@ -27,6 +27,7 @@ struct Tunables {
                                   // instead of inside the in_proj GEMM's epilogue (round 5)
     int conformer_gemm_scores = 0;  // K2HIP_CONFORMER_GEMM_SCORES: two batched GEMMs + gather/softmax (the long-utterance form)
     int dw7_tiled = 0;            // K2HIP_DW7_TILED: the one-shot LDS-tiled 7x7 depthwise conv also for long inputs (default: the sliding LDS-DMA form)
+    int dw1d_tt = 0;              // K2HIP_DW1D_TT: outputs per thread of the depthwise Conv1d (8 / 4 / 2; 0 = by grid size; tests/test_kernels_gpu.py forces each)
     int lstm_seq = 0;             // K2HIP_LSTM_SEQ: layer-by-layer LSTM instead of the layer wavefront
     int greedy_one_part = 0;      // K2HIP_GREEDY_ONE_PART: one workgroup per stream in the search
     int greedy_parts = 0;         // K2HIP_GREEDY_PARTS: vocabulary slabs per stream (0 = automatic)
@@ -46,7 +47,6 @@ struct Tunables {
     // ---- tuning probes (-DK2HIP_DEV builds only)
     K2HIP_DEV_SWITCH(gemm_cfg, -1);         // K2HIP_GEMM_CFG: force one tile configuration
     K2HIP_DEV_SWITCH(xcd_panels, 0);        // K2HIP_XCD_PANELS: 1 = every GEMM's tiles as bands of M per XCD (rounds 1 - 3)
-    K2HIP_DEV_SWITCH(dw1d_tt, 0);           // K2HIP_DW1D_TT: outputs per thread of the depthwise Conv1d (8 / 4 / 2; 0 = by grid size)
     K2HIP_DEV_SWITCH(greedy_stamps, 0);     // K2HIP_GREEDY_STAMPS: the persistent search reports where a round's time goes (stderr, synchronous)
     K2HIP_DEV_SWITCH(conformer_stamps, 0);  // K2HIP_CONFORMER_STAMPS: the Conformer scores kernel reports its phases (stderr, synchronous)
 };

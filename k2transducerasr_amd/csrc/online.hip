@@ -466,19 +466,34 @@ void cat_keep(const Ctx& ctx, float* pool, long long slot_stride, long long off,
                        Tc - keep_back, n1);
     K2_HIP(hipGetLastError());
 }
+// The streaming score kernels hold a stream's whole [Tc][L + Tc] score block in dynamic LDS, past HIP's default 64 KB from e.g. a chunk
+// of 32 frames with a left context of 512: the launch limit is raised to the CU's 160 KB as in attn_scores_launch, and a longer context
+// is refused with this error in the dry pass (tests/test_kernels_gpu.py runs 69.6 KB, exactly 160 KB and one frame more).
+constexpr int kStreamScoresLdsMax = 160 * 1024;
+static size_t stream_scores_lds(int Tc, int L) {
+    const size_t lds = sizeof(float) * (size_t)Tc * (size_t)(L + Tc);
+    K2_REQUIRE(Tc > 0 && L >= 0 && lds <= (size_t)kStreamScoresLdsMax,
+               "streaming attention: chunk of %d frames with a left context of %d needs %zu bytes of LDS (at most %d)", Tc, L, lds,
+               kStreamScoresLdsMax);
+    return lds;
+}
 void attn_stream_ring(const Ctx& ctx, const float* qkp, int ld, const RingRef& keys, const float* pp, const long long* plen, float* aw, int B,
                       int Tc, int L, int KLp, int H, int ds, int left50) {
     ctx.add_flops(0.0, 2.0 * 36 * (double)Tc * (L + Tc) * B * H, 0);
+    const size_t lds = stream_scores_lds(Tc, L);   // (in front of the dry return: refused before any cache has advanced)
     if (ctx.dry) return;
-    size_t lds = sizeof(float) * Tc * (L + Tc);
+    static LdsAttrOnce lds_attr;
+    lds_attr.ensure(k_attn_stream_ring, kStreamScoresLdsMax);
     hipLaunchKernelGGL(k_attn_stream_ring, dim3(B, H), dim3(256), lds, ctx.stream, qkp, ld, keys, pp, plen, aw, B, Tc, L, KLp, H, ds, left50);
     K2_HIP(hipGetLastError());
 }
 void attn_stream(const Ctx& ctx, const float* qkp, int ld, const float* kcat, const float* pp, const long long* plen,
                  float* aw, int B, int Tc, int L, int KLp, int H, int ds, int left50) {
     ctx.add_flops(0.0, 2.0 * 36 * (double)Tc * (L + Tc) * B * H, 0);
+    const size_t lds = stream_scores_lds(Tc, L);
     if (ctx.dry) return;
-    size_t lds = sizeof(float) * Tc * (L + Tc);
+    static LdsAttrOnce lds_attr;
+    lds_attr.ensure(k_attn_stream, kStreamScoresLdsMax);
     hipLaunchKernelGGL(k_attn_stream, dim3(B, H), dim3(256), lds, ctx.stream, qkp, ld, kcat, pp, plen, aw, B, Tc, L, KLp, H, ds, left50);
     K2_HIP(hipGetLastError());
 }

@@ -75,6 +75,7 @@ const Entry kEntries[] = {
     {"K2HIP_NO_FUSED_CONV", &Tunables::no_fused_conv, true},
     {"K2HIP_CONFORMER_GEMM_SCORES", &Tunables::conformer_gemm_scores, true},
     {"K2HIP_DW7_TILED", &Tunables::dw7_tiled, true},
+    {"K2HIP_DW1D_TT", &Tunables::dw1d_tt, false},
     {"K2HIP_LSTM_SEQ", &Tunables::lstm_seq, true},
     {"K2HIP_GREEDY_ONE_PART", &Tunables::greedy_one_part, true},
     {"K2HIP_GREEDY_PARTS", &Tunables::greedy_parts, false},
@@ -90,7 +91,6 @@ const Entry kEntries[] = {
 #ifdef K2HIP_DEV   // tuning probes: a -DK2HIP_DEV build only (make DEV=1)
     {"K2HIP_GEMM_CFG", &Tunables::gemm_cfg, false},
     {"K2HIP_XCD_PANELS", &Tunables::xcd_panels, false},
-    {"K2HIP_DW1D_TT", &Tunables::dw1d_tt, false},
     {"K2HIP_GREEDY_STAMPS", &Tunables::greedy_stamps, true},
     {"K2HIP_CONFORMER_STAMPS", &Tunables::conformer_stamps, true},
 #endif
