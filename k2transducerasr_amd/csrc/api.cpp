@@ -1221,8 +1221,6 @@ int32_t k2hip_debug_gemm_trace(k2hip_model_t* model, int32_t M, int32_t N, int32
                                                                        int32_t* n_wg, int32_t* n_waves) {
     return guard([&] {
         NEED(model); NEED(out); NEED(n_wg); NEED(n_waves);
-        K2_REQUIRE((cfg >= 100 && cfg < 1000) || cfg >= 2000 || cfg == 0 || cfg == 5 || cfg == 7 || (cfg >= 9 && cfg <= 11),
-                   "trace: LDS-DMA (0, 5, 7, 9, 10, 11), ring (100+) and pipelined (2000+) configurations only");
         EngineLock lk(model->engine);
         model->engine.debug_gemm_trace(M, N, K, act, with_res != 0, cfg, out, cap, n_wg, n_waves);
     });

@@ -1422,6 +1422,21 @@ void Engine::wait_ticket(int ticket, int64_t* tokens, int32_t* ts, int32_t* n_to
     memcpy(n_tokens, pin + nb_tok + nb_ts, nb_n);
 }
 
+namespace {
+struct DevBufs {  // device buffers of a tuning / test hook, freed on every way out
+    std::vector<void*> p;
+    template <typename T>
+    T* alloc(size_t n) {
+        p.push_back(nullptr);
+        K2_HIP(hipMalloc(&p.back(), sizeof(T) * n));
+        return static_cast<T*>(p.back());
+    }
+    ~DevBufs() {
+        for (void* q : p) (void)hipFree(q);
+    }
+};
+}  // namespace
+
 // tuning hook: average time of one Linear-shaped GEMM on uniform random data under the forced configuration `cfg`; max_err
 // (optional) = largest |difference| from the register-staged 64x64 kernel on the same operands
 float Engine::debug_gemm(int M, int N, int K, int act, bool with_res, int iters, int cfg, float* max_err) {
@@ -1429,13 +1444,13 @@ float Engine::debug_gemm(int M, int N, int K, int act, bool with_res, int iters,
     std::vector<float> h((size_t)std::max((int64_t)M * K, std::max((int64_t)N * K, (int64_t)M * N)));
     uint32_t s = 12345u;
     for (auto& v : h) { s = s * 1664525u + 1013904223u; v = ((s >> 8) * (1.0f / 8388608.0f)) - 1.0f; }
-    float *A, *W, *C, *C2, *Rb, *b;
-    K2_HIP(hipMalloc(&A, sizeof(float) * (size_t)M * K));
-    K2_HIP(hipMalloc(&W, sizeof(float) * (size_t)N * K));
-    K2_HIP(hipMalloc(&C, sizeof(float) * (size_t)M * N));
-    K2_HIP(hipMalloc(&C2, sizeof(float) * (size_t)M * N));
-    K2_HIP(hipMalloc(&Rb, sizeof(float) * (size_t)M * N));
-    K2_HIP(hipMalloc(&b, sizeof(float) * (size_t)N));
+    DevBufs dev;
+    float* A = dev.alloc<float>((size_t)M * K);
+    float* W = dev.alloc<float>((size_t)N * K);
+    float* C = dev.alloc<float>((size_t)M * N);
+    float* C2 = dev.alloc<float>((size_t)M * N);
+    float* Rb = dev.alloc<float>((size_t)M * N);
+    float* b = dev.alloc<float>((size_t)N);
     K2_HIP(fill_blocking(W, 0, sizeof(float) * (size_t)N * K));   // (the last 7 / 3 elements below are not covered by the shifted copies)
     K2_HIP(fill_blocking(Rb, 0, sizeof(float) * (size_t)M * N));
     K2_HIP(copy_blocking(A, h.data(), sizeof(float) * (size_t)M * K, hipMemcpyHostToDevice));
@@ -1445,82 +1460,65 @@ float Engine::debug_gemm(int M, int N, int K, int act, bool with_res, int iters,
     Ctx c = make_ctx(false);
     c.instrument = false;
     c.stats = nullptr;
+    GemmForceGuard force(cfg);
     float ms = 0;
     if (act >= 100) {  // the gated epilogue (101: value * sigmoid(gate) over all columns, 102: value * tanh(gate) over the first 2N/3,
                        // the rest passed through) against the plain GEMM + the gating done on the host
         const int mode = act - 100, gc = mode == 2 ? (2 * N / 3) / 32 * 32 : N, ldo = gc / 2 + (N - gc);
-        try {
-            K2_REQUIRE((mode == 1 || mode == 2) && N % 32 == 0 && gc >= 32 && max_err, "debug_gemm: gated mode needs N %% 32 == 0 and max_err");
-            GemmArgs g;
-            g.A = A; g.lda = K; g.W = W; g.ldw = K; g.bias = b; g.C = C; g.ldc = ldo; g.M = M; g.N = N; g.K = K; g.glu = mode; g.glu_cols = gc == N ? 0 : gc;
-            debug_force_gemm_cfg(cfg);
-            gemm(c, g);
-            K2_HIP(hipEventRecord(ev_[6], stream_));
-            for (int i = 0; i < iters; i++) gemm(c, g);
-            K2_HIP(hipEventRecord(ev_[7], stream_));
-            debug_force_gemm_cfg(2 + 64);
-            linear(c, A, K, W, b, C2, N, M, K, N, ACT_NONE, nullptr, 0);
-            K2_HIP(hipStreamSynchronize(stream_));
-            K2_HIP(hipEventElapsedTime(&ms, ev_[6], ev_[7]));
-            std::vector<float> h1((size_t)M * ldo), h2((size_t)M * N);
-            K2_HIP(copy_blocking(h1.data(), C, sizeof(float) * h1.size(), hipMemcpyDeviceToHost));
-            K2_HIP(copy_blocking(h2.data(), C2, sizeof(float) * h2.size(), hipMemcpyDeviceToHost));
-            float e = 0;
-            for (int m = 0; m < M; m++)
-                for (int col = 0; col < N; col++) {
-                    float want;
-                    int oc;
-                    if (col < gc) {
-                        if (col & 16) continue;  // a gate column
-                        const float v = h2[(size_t)m * N + col], gt = h2[(size_t)m * N + col + 16];
-                        want = mode == 2 ? v * tanhf(gt) : v / (1.0f + expf(-gt));
-                        oc = ((col >> 5) << 4) + (col & 15);
-                    } else {
-                        want = h2[(size_t)m * N + col];
-                        oc = gc / 2 + (col - gc);
-                    }
-                    const float d = fabsf(h1[(size_t)m * ldo + oc] - want);
-                    e = (d > e || d != d) ? (d != d ? INFINITY : d) : e;
-                }
-            *max_err = e;
-        } catch (...) {
-            debug_force_gemm_cfg(-1);
-            (void)hipFree(A); (void)hipFree(W); (void)hipFree(C); (void)hipFree(C2); (void)hipFree(Rb); (void)hipFree(b);
-            throw;
-        }
-        debug_force_gemm_cfg(-1);
-        (void)hipFree(A); (void)hipFree(W); (void)hipFree(C); (void)hipFree(C2); (void)hipFree(Rb); (void)hipFree(b);
-        return ms / std::max(1, iters);
-    }
-    try {
-        debug_force_gemm_cfg(cfg);
-        for (int i = 0; i < 3; i++) linear(c, A, K, W, b, C, N, M, K, N, act, with_res ? Rb : nullptr, N);
+        K2_REQUIRE((mode == 1 || mode == 2) && N % 32 == 0 && gc >= 32 && max_err, "debug_gemm: gated mode needs N %% 32 == 0 and max_err");
+        GemmArgs g;
+        g.A = A; g.lda = K; g.W = W; g.ldw = K; g.bias = b; g.C = C; g.ldc = ldo; g.M = M; g.N = N; g.K = K; g.glu = mode; g.glu_cols = gc == N ? 0 : gc;
+        gemm(c, g);
         K2_HIP(hipEventRecord(ev_[6], stream_));
-        for (int i = 0; i < iters; i++) linear(c, A, K, W, b, C, N, M, K, N, act, with_res ? Rb : nullptr, N);
+        for (int i = 0; i < iters; i++) gemm(c, g);
         K2_HIP(hipEventRecord(ev_[7], stream_));
+        debug_force_gemm_cfg(2 + 64);
+        linear(c, A, K, W, b, C2, N, M, K, N, ACT_NONE, nullptr, 0);
         K2_HIP(hipStreamSynchronize(stream_));
         K2_HIP(hipEventElapsedTime(&ms, ev_[6], ev_[7]));
-        if (max_err) {
-            debug_force_gemm_cfg(2 + 64);
-            linear(c, A, K, W, b, C2, N, M, K, N, act, with_res ? Rb : nullptr, N);
-            K2_HIP(hipStreamSynchronize(stream_));
-            std::vector<float> h1((size_t)M * N), h2((size_t)M * N);
-            K2_HIP(copy_blocking(h1.data(), C, sizeof(float) * h1.size(), hipMemcpyDeviceToHost));
-            K2_HIP(copy_blocking(h2.data(), C2, sizeof(float) * h2.size(), hipMemcpyDeviceToHost));
-            float e = 0;
-            for (size_t i = 0; i < h1.size(); i++) {
-                const float d = fabsf(h1[i] - h2[i]);
+        std::vector<float> h1((size_t)M * ldo), h2((size_t)M * N);
+        K2_HIP(copy_blocking(h1.data(), C, sizeof(float) * h1.size(), hipMemcpyDeviceToHost));
+        K2_HIP(copy_blocking(h2.data(), C2, sizeof(float) * h2.size(), hipMemcpyDeviceToHost));
+        float e = 0;
+        for (int m = 0; m < M; m++)
+            for (int col = 0; col < N; col++) {
+                float want;
+                int oc;
+                if (col < gc) {
+                    if (col & 16) continue;  // a gate column
+                    const float v = h2[(size_t)m * N + col], gt = h2[(size_t)m * N + col + 16];
+                    want = mode == 2 ? v * tanhf(gt) : v / (1.0f + expf(-gt));
+                    oc = ((col >> 5) << 4) + (col & 15);
+                } else {
+                    want = h2[(size_t)m * N + col];
+                    oc = gc / 2 + (col - gc);
+                }
+                const float d = fabsf(h1[(size_t)m * ldo + oc] - want);
                 e = (d > e || d != d) ? (d != d ? INFINITY : d) : e;
             }
-            *max_err = e;
-        }
-    } catch (...) {
-        debug_force_gemm_cfg(-1);
-        (void)hipFree(A); (void)hipFree(W); (void)hipFree(C); (void)hipFree(C2); (void)hipFree(Rb); (void)hipFree(b);
-        throw;
+        *max_err = e;
+        return ms / std::max(1, iters);
     }
-    debug_force_gemm_cfg(-1);
-    (void)hipFree(A); (void)hipFree(W); (void)hipFree(C); (void)hipFree(C2); (void)hipFree(Rb); (void)hipFree(b);
+    for (int i = 0; i < 3; i++) linear(c, A, K, W, b, C, N, M, K, N, act, with_res ? Rb : nullptr, N);
+    K2_HIP(hipEventRecord(ev_[6], stream_));
+    for (int i = 0; i < iters; i++) linear(c, A, K, W, b, C, N, M, K, N, act, with_res ? Rb : nullptr, N);
+    K2_HIP(hipEventRecord(ev_[7], stream_));
+    K2_HIP(hipStreamSynchronize(stream_));
+    K2_HIP(hipEventElapsedTime(&ms, ev_[6], ev_[7]));
+    if (max_err) {
+        debug_force_gemm_cfg(2 + 64);
+        linear(c, A, K, W, b, C2, N, M, K, N, act, with_res ? Rb : nullptr, N);
+        K2_HIP(hipStreamSynchronize(stream_));
+        std::vector<float> h1((size_t)M * N), h2((size_t)M * N);
+        K2_HIP(copy_blocking(h1.data(), C, sizeof(float) * h1.size(), hipMemcpyDeviceToHost));
+        K2_HIP(copy_blocking(h2.data(), C2, sizeof(float) * h2.size(), hipMemcpyDeviceToHost));
+        float e = 0;
+        for (size_t i = 0; i < h1.size(); i++) {
+            const float d = fabsf(h1[i] - h2[i]);
+            e = (d > e || d != d) ? (d != d ? INFINITY : d) : e;
+        }
+        *max_err = e;
+    }
     return ms / iters;
 }
 
@@ -1531,34 +1529,32 @@ void Engine::debug_gemm_host(const float* hA, const float* hW, const float* hb, 
     K2_REQUIRE(glu == 0 || (N % 32 == 0 && (glu_cols == 0 || (glu_cols % 32 == 0 && glu_cols <= N))), "debug_gemm_host: gated form needs N %% 32 == 0");
     const int gc = glu ? (glu_cols ? glu_cols : N) : 0;
     const int ldo = glu ? gc / 2 + (N - gc) : N;
-    struct Bufs {
-        float *A = nullptr, *W = nullptr, *C = nullptr, *R = nullptr, *b = nullptr;
-        ~Bufs() { (void)hipFree(A); (void)hipFree(W); (void)hipFree(C); (void)hipFree(R); (void)hipFree(b); debug_force_gemm_cfg(-1); }
-    } d;
-    K2_HIP(hipMalloc(&d.A, sizeof(float) * (size_t)M * K));
-    K2_HIP(hipMalloc(&d.W, sizeof(float) * (size_t)N * K));
-    K2_HIP(hipMalloc(&d.C, sizeof(float) * (size_t)M * ldo));
-    K2_HIP(copy_blocking(d.A, hA, sizeof(float) * (size_t)M * K, hipMemcpyHostToDevice));
-    K2_HIP(copy_blocking(d.W, hW, sizeof(float) * (size_t)N * K, hipMemcpyHostToDevice));
-    K2_HIP(fill_blocking(d.C, 0xff, sizeof(float) * (size_t)M * ldo));   // NaN pattern: an element the kernel never writes fails the comparison
+    DevBufs dev;
+    float* A = dev.alloc<float>((size_t)M * K);
+    float* W = dev.alloc<float>((size_t)N * K);
+    float* C = dev.alloc<float>((size_t)M * ldo);
+    float *R = nullptr, *b = nullptr;
+    K2_HIP(copy_blocking(A, hA, sizeof(float) * (size_t)M * K, hipMemcpyHostToDevice));
+    K2_HIP(copy_blocking(W, hW, sizeof(float) * (size_t)N * K, hipMemcpyHostToDevice));
+    K2_HIP(fill_blocking(C, 0xff, sizeof(float) * (size_t)M * ldo));   // NaN pattern: an element the kernel never writes fails the comparison
     if (hb) {
-        K2_HIP(hipMalloc(&d.b, sizeof(float) * (size_t)N));
-        K2_HIP(copy_blocking(d.b, hb, sizeof(float) * (size_t)N, hipMemcpyHostToDevice));
+        b = dev.alloc<float>((size_t)N);
+        K2_HIP(copy_blocking(b, hb, sizeof(float) * (size_t)N, hipMemcpyHostToDevice));
     }
     if (hres) {
-        K2_HIP(hipMalloc(&d.R, sizeof(float) * (size_t)M * ldo));
-        K2_HIP(copy_blocking(d.R, hres, sizeof(float) * (size_t)M * ldo, hipMemcpyHostToDevice));
+        R = dev.alloc<float>((size_t)M * ldo);
+        K2_HIP(copy_blocking(R, hres, sizeof(float) * (size_t)M * ldo, hipMemcpyHostToDevice));
     }
     Ctx c = make_ctx(false);
     c.instrument = false;
     c.stats = nullptr;
     GemmArgs g;
-    g.A = d.A; g.lda = K; g.W = d.W; g.ldw = K; g.bias = d.b; g.C = d.C; g.ldc = ldo; g.M = M; g.N = N; g.K = K;
-    g.act = act; g.res = d.R; g.ldr = ldo; g.glu = glu; g.glu_cols = gc == N ? 0 : gc;
-    debug_force_gemm_cfg(cfg);
+    g.A = A; g.lda = K; g.W = W; g.ldw = K; g.bias = b; g.C = C; g.ldc = ldo; g.M = M; g.N = N; g.K = K;
+    g.act = act; g.res = R; g.ldr = ldo; g.glu = glu; g.glu_cols = gc == N ? 0 : gc;
+    GemmForceGuard force(cfg);
     gemm(c, g);
     K2_HIP(hipStreamSynchronize(stream_));
-    K2_HIP(copy_blocking(hC, d.C, sizeof(float) * (size_t)M * ldo, hipMemcpyDeviceToHost));
+    K2_HIP(copy_blocking(hC, C, sizeof(float) * (size_t)M * ldo, hipMemcpyDeviceToHost));
 }
 
 // test hook: ONE launch of a launcher of kernels.h on the caller's host operands (tests/test_kernels_gpu.py).  Buffer k of the call is
@@ -1746,19 +1742,28 @@ void Engine::debug_op_host(const char* op, const int64_t* iargs, int n_iargs, vo
         if (dev[k] && (out_mask >> k & 1u)) K2_HIP(copy_blocking(bufs[k], dev[k], (size_t)buf_bytes[k], hipMemcpyDeviceToHost));
 }
 
-// tuning hook: ONE launch of the ring kernel `cfg` (>= 100) with in-kernel s_memtime stamps; out [n_wg][n_waves][64]
+// tuning hook: ONE launch of the LDS-DMA, ring or pipelined kernel that cfg forces, with in-kernel s_memtime stamps; out [n_wg][n_waves][64]
 void Engine::debug_gemm_trace(int M, int N, int K, int act, bool with_res, int cfg, unsigned long long* out, int64_t cap, int* n_wg, int* n_waves) {
     K2_HIP(hipSetDevice(device_));
+    GemmForceGuard force(cfg);
+    GemmArgs g;
+    g.lda = K; g.ldw = K; g.ldc = N; g.M = M; g.N = N; g.K = K; g.act = act; g.ldr = N;
+    const GemmPlan p = plan_gemm(g, gemm_force());
+    K2_REQUIRE(p.family == GemmFamily::DMA || p.family == GemmFamily::RING || p.family == GemmFamily::PIPE,
+               "trace: LDS-DMA (0, 5, 7, 9, 10, 11), ring (100+) and pipelined (2000+) configurations only");
+    *n_wg = cdiv(M, p.BM) * cdiv(N, p.BN);
+    *n_waves = p.waves;
+    const int64_t words = (int64_t)*n_wg * p.waves * 64;
+    K2_REQUIRE(words <= cap, "trace buffer too small: need %lld words", (long long)words);
     std::vector<float> h((size_t)std::max((int64_t)M * K, std::max((int64_t)N * K, (int64_t)M * N)));
     uint32_t s = 12345u;
     for (auto& v : h) { s = s * 1664525u + 1013904223u; v = ((s >> 8) * (1.0f / 8388608.0f)) - 1.0f; }
-    float *A, *W, *C, *b;
-    unsigned long long* dbg;
-    K2_HIP(hipMalloc(&A, sizeof(float) * (size_t)M * K));
-    K2_HIP(hipMalloc(&W, sizeof(float) * (size_t)N * K));
-    K2_HIP(hipMalloc(&C, sizeof(float) * (size_t)M * N));
-    K2_HIP(hipMalloc(&b, sizeof(float) * (size_t)N));
-    K2_HIP(hipMalloc(&dbg, sizeof(unsigned long long) * (size_t)cap));
+    DevBufs dev;
+    float* A = dev.alloc<float>((size_t)M * K);
+    float* W = dev.alloc<float>((size_t)N * K);
+    float* C = dev.alloc<float>((size_t)M * N);
+    float* b = dev.alloc<float>((size_t)N);
+    unsigned long long* dbg = dev.alloc<unsigned long long>((size_t)cap);
     K2_HIP(fill_blocking(dbg, 0, sizeof(unsigned long long) * (size_t)cap));
     K2_HIP(copy_blocking(A, h.data(), sizeof(float) * (size_t)M * K, hipMemcpyHostToDevice));
     K2_HIP(copy_blocking(W, h.data(), sizeof(float) * (size_t)N * K, hipMemcpyHostToDevice));
@@ -1767,37 +1772,12 @@ void Engine::debug_gemm_trace(int M, int N, int K, int act, bool with_res, int c
     Ctx c = make_ctx(false);
     c.instrument = false;
     c.stats = nullptr;
-    try {
-        debug_force_gemm_cfg(cfg);
-        GemmArgs g;
-        g.A = A; g.lda = K; g.W = W; g.ldw = K; g.bias = b; g.C = C; g.ldc = N; g.M = M; g.N = N; g.K = K; g.act = act;
-        g.res = with_res ? C : nullptr; g.ldr = N;
-        for (int i = 0; i < 5; i++) gemm(c, g);   // steady state (caches, clocks)
-        int bm = 0, bn = 0, nw = 0;
-        if (cfg >= 2000) {
-            debug_pipe_shape(cfg, M, N, n_wg, &nw);
-        } else if (cfg < 100) {  // LDS-DMA kernel: 5 / 7 = 128x64 (8 waves), 9 = 64x64 (4 waves), 0 = 128x128 (8 waves), 11 = 64x96 (6 waves)
-            bm = cfg == 9 || cfg == 10 || cfg == 11 ? 64 : 128;
-            bn = cfg == 0 ? 128 : cfg == 11 ? 96 : 64;
-            nw = cfg == 9 || cfg == 10 ? 4 : cfg == 11 ? 6 : 8;
-            *n_wg = cdiv(M, bm) * cdiv(N, bn);
-        } else {
-            debug_ring_shape(cfg - 100, &bm, &bn, &nw);
-            *n_wg = cdiv(M, bm) * cdiv(N, bn);
-        }
-        *n_waves = nw;
-        K2_REQUIRE((int64_t)*n_wg * nw * 64 <= cap, "trace buffer too small: need %lld words", (long long)*n_wg * nw * 64);
-        g.dbg = dbg;
-        gemm(c, g);
-        K2_HIP(hipStreamSynchronize(stream_));
-        K2_HIP(copy_blocking(out, dbg, sizeof(unsigned long long) * (size_t)*n_wg * nw * 64, hipMemcpyDeviceToHost));
-    } catch (...) {
-        debug_force_gemm_cfg(-1);
-        (void)hipFree(A); (void)hipFree(W); (void)hipFree(C); (void)hipFree(b); (void)hipFree(dbg);
-        throw;
-    }
-    debug_force_gemm_cfg(-1);
-    (void)hipFree(A); (void)hipFree(W); (void)hipFree(C); (void)hipFree(b); (void)hipFree(dbg);
+    g.A = A; g.W = W; g.bias = b; g.C = C; g.res = with_res ? C : nullptr;
+    for (int i = 0; i < 5; i++) gemm(c, g);   // steady state (caches, clocks)
+    g.dbg = dbg;
+    gemm(c, g);
+    K2_HIP(hipStreamSynchronize(stream_));
+    K2_HIP(copy_blocking(out, dbg, sizeof(unsigned long long) * (size_t)words, hipMemcpyDeviceToHost));
 }
 
 void* Engine::dev_alloc(int64_t bytes) {

@@ -46,7 +46,6 @@ namespace {
 
 // K step BK (32 or 64) is a template parameter; LDS rows are padded to BK+4 floats (16-byte
 // aligned; 36- and 68-dword strides are both conflict-free for the ds_read_b128 fragment reads)
-enum { MODE_PLAIN = 0, MODE_CONV = 1, MODE_WKN = 2 };
 
 // Activations with the hardware transcendental units (v_exp_f32 / v_log_f32, ~1e-6
 // relative): the accurate libm forms cost ~100 VALU instructions per element, which
@@ -1673,24 +1672,6 @@ void launch_pipe(const Ctx& ctx, const GemmArgs& a) {
     K2_REQUIRE(a.K % 32 == 0 && a.K >= 32 * (NST - 1), "pipe: K %d too short for %d stages", a.K, NST);
     hipLaunchKernelGGL((gemm_f32_mfma_pipe<BM, BN, WM, WN, NST>), grid, dim3(64 * (BM / WM) * (BN / WN)), lds, ctx.stream, a);
 }
-// tuning table of the pipelined kernel: k2hip_debug_gemm cfg = 2000 + index
-struct PipeCfg { int BM, BN, WM, WN, NST; };
-#define K2_PIPE_TABLE(X)                                                                                                       \
-    X(0, 128, 64, 64, 32, 3) X(1, 128, 64, 32, 32, 3) X(2, 128, 128, 64, 64, 3) X(3, 128, 128, 64, 32, 3) X(4, 128, 64, 64, 32, 4)  \
-    X(5, 64, 64, 32, 32, 3) X(6, 128, 128, 64, 64, 4) X(7, 64, 128, 32, 64, 3) X(8, 128, 128, 32, 32, 3) X(9, 128, 64, 32, 32, 4) \
-    X(10, 64, 64, 64, 32, 3) X(11, 64, 64, 32, 64, 3) X(12, 256, 64, 64, 32, 3) X(13, 128, 32, 32, 32, 3) X(14, 128, 32, 64, 32, 3)
-#define X(i, bm, bn, wm, wn, nst) {bm, bn, wm, wn, nst},
-const PipeCfg kPipe[] = {K2_PIPE_TABLE(X)};
-#undef X
-bool launch_pipe_idx(const Ctx& ctx, const GemmArgs& a, int idx) {
-    switch (idx) {
-#define X(i, bm, bn, wm, wn, nst) case i: launch_pipe<bm, bn, wm, wn, nst>(ctx, a); break;
-        K2_PIPE_TABLE(X)
-#undef X
-        default: return false;
-    }
-    return true;
-}
 
 template <int BM, int BN, int WM, int WN, int NST>
 void launch_p16(const Ctx& ctx, const GemmArgs& a) {
@@ -1701,40 +1682,6 @@ void launch_p16(const Ctx& ctx, const GemmArgs& a) {
     K2_REQUIRE((long long)a.M * a.lda < (1ll << 29) && (long long)a.N * a.ldw < (1ll << 29), "p16: operand too large for 31-bit lane byte offsets");
     K2_REQUIRE(a.K % 32 == 0 && a.K >= 32 * (NST - 1) && !a.glu, "p16: K %d too short for %d stages, or a gated epilogue", a.K, NST);
     hipLaunchKernelGGL((gemm_f32_mfma_p16<BM, BN, WM, WN, NST>), grid, dim3(64 * (BM / WM) * (BN / WN)), lds, ctx.stream, a);
-}
-// tuning table of the 16x16x4 pipelined kernel: k2hip_debug_gemm cfg = 3000 + index
-bool launch_p16_idx(const Ctx& ctx, const GemmArgs& a, int idx) {
-    switch (idx) {
-        case 0: launch_p16<64, 96, 32, 48, 3>(ctx, a); break;     // 4 waves of 32 x 48
-        case 1: launch_p16<128, 96, 64, 48, 3>(ctx, a); break;    // 4 waves of 64 x 48
-        case 2: launch_p16<64, 192, 32, 96, 3>(ctx, a); break;    // 4 waves of 32 x 96
-        case 3: launch_p16<32, 96, 16, 48, 3>(ctx, a); break;     // 4 waves of 16 x 48
-        default: return false;
-    }
-    return true;
-}
-
-// tuning table of the ring kernel: k2hip_debug_gemm cfg = 100 + index
-struct RingCfg { int BM, BN, KS, NST, LW, PF; };
-#define K2_RING_TABLE(X)                                                                                        \
-    X(0, 128, 64, 1, 2, 0, 0) X(1, 128, 64, 1, 3, 0, 0) X(2, 128, 64, 1, 2, 0, 1) X(3, 128, 64, 1, 3, 0, 1) X(4, 128, 64, 1, 4, 0, 1)   \
-    X(5, 64, 64, 1, 3, 0, 0) X(6, 64, 64, 1, 3, 0, 1) X(7, 64, 64, 1, 4, 0, 1) X(8, 64, 64, 2, 3, 0, 0) X(9, 64, 64, 2, 3, 0, 1)      \
-    X(10, 64, 64, 4, 2, 0, 0) X(11, 64, 64, 4, 2, 0, 1) X(12, 32, 64, 2, 3, 0, 0) X(13, 32, 64, 4, 3, 0, 0) X(14, 32, 64, 4, 3, 0, 1)  \
-    X(15, 32, 32, 4, 3, 0, 0) X(16, 32, 32, 4, 4, 0, 1) X(17, 64, 32, 4, 3, 0, 0) X(18, 128, 128, 1, 2, 0, 0) X(19, 128, 128, 1, 2, 0, 1) \
-    X(20, 64, 128, 1, 3, 0, 0) X(21, 64, 128, 1, 3, 0, 1) X(22, 64, 96, 1, 3, 0, 0) X(23, 64, 96, 1, 3, 0, 1) X(24, 128, 96, 1, 2, 0, 1) \
-    X(25, 128, 64, 1, 3, 2, 0) X(26, 128, 64, 1, 3, 2, 1) X(27, 128, 64, 2, 2, 0, 1) X(28, 64, 96, 2, 3, 0, 0) X(29, 64, 96, 2, 2, 0, 0) \
-    X(30, 64, 96, 2, 2, 0, 1) X(31, 128, 96, 1, 3, 0, 0) X(32, 128, 96, 1, 3, 0, 1)
-#define X(i, bm, bn, ks, nst, lw, pf) {bm, bn, ks, nst, lw, pf},
-const RingCfg kRing[] = {K2_RING_TABLE(X)};
-#undef X
-bool launch_ring_idx(const Ctx& ctx, const GemmArgs& a, int idx) {
-    switch (idx) {
-#define X(i, bm, bn, ks, nst, lw, pf) case i: launch_ring<bm, bn, ks, nst, lw, pf>(ctx, a); break;
-        K2_RING_TABLE(X)
-#undef X
-        default: return false;
-    }
-    return true;
 }
 
 template <int BM, int BN, int WM, int WN, int BK, int MODE>
@@ -1748,106 +1695,22 @@ void launch_cfg(const Ctx& ctx, const GemmArgs& a) {
 }
 
 template <int MODE>
-void launch_mode(const Ctx& ctx, const GemmArgs& a, int cfg) {
-    switch (cfg) {
-        case 0: launch_cfg<128, 128, 64, 32, 32, MODE>(ctx, a); break;  // 8 waves
-        case 1: launch_cfg<128, 128, 64, 32, 64, MODE>(ctx, a); break;  // 8 waves, BK 64
-        case 3: launch_cfg<64, 64, 32, 32, 64, MODE>(ctx, a); break;    // 4 waves, BK 64
-        case 4: launch_cfg<128, 64, 32, 32, 64, MODE>(ctx, a); break;   // 8 waves, BK 64
-        case 5: case 7: case 8: case 11: launch_cfg<128, 64, 32, 32, 32, MODE>(ctx, a); break;   // 8 waves (and the fallback of the DMA-only configs)
-        case 12: launch_cfg<128, 32, 32, 32, 32, MODE>(ctx, a); break;  // 4 waves, 32 columns (the second embed convolution: N = 32, 600k rows)
-        default: launch_cfg<64, 64, 32, 32, 32, MODE>(ctx, a); break;   // 4 waves
+void launch_reg(const Ctx& ctx, const GemmArgs& a, int idx) {
+    switch (idx) {
+#define X(i, bm, bn, wm, wn, bk) case i: launch_cfg<bm, bn, wm, wn, bk, MODE>(ctx, a); break;
+        K2_REG_TABLE(X)
+#undef X
     }
 }
 
-int g_forced_cfg = -1;  // debug_force_gemm_cfg (tuning hook); K2HIP_GEMM_CFG comes through tunables()
-
-// Tile choice, from tools/gemm_tune.py on the benchmark's shapes (gpurun_out/gemm_tune_*.txt):
-// on this path K is short (192..2560), so a launch is dominated by how well the prologue /
-// epilogue of one workgroup overlaps the MFMA loop of its neighbours.  Small wave tiles
-// (32x32 per wave, 4-5 waves per SIMD) win almost everywhere; the 128x128 tile only pays
-// when the output is large enough to fill every CU several times over.
-//   cfg 0: 128x128, 8 waves (64x32 per wave)   cfg 5: 128x64, 8 waves (32x32 per wave)
-//   cfg 2:  64x64,  4 waves (32x32 per wave)
-int choose_cfg(const GemmArgs& a) {
-    if (g_forced_cfg >= 0) return g_forced_cfg;
-    if (tunables().gemm_cfg >= 0) return tunables().gemm_cfg;
-    // N <= 32 with many rows (encoder_embed.conv.4 as an implicit GEMM: 632 736 x 32 x 72 at the headline shape): a 64-column tile
-    // multiplies 32 columns of padding
-    if (a.N <= 32 && a.M >= 4096) return 12;
-    // (the third embed convolution, 307 040 x 128 x 288, stays on 128x64 with K steps of 32: one 128-column tile that gathers each A row once is
-    // 301 against 284 us, K steps of 64 382)
-    if (a.N <= 64) return 2;    // 64x64 tiles, 4 waves
-    if (a.M <= 64) return 3;    // a handful of rows (per-frame recurrent products, batched over layers): 64x64 tiles, K step 64
-    // few output tiles (streaming chunks: 256..2048 rows): the launch is one latency-bound K sweep per
-    // workgroup; small tiles with a 64-deep K step are fastest (gpurun_out/gemm_tune_s1.txt)
-    if ((long long)cdiv(a.M, 128) * cdiv(a.N, 64) * a.nb0 * a.nb1 < 144) return 3;  // fewer 128x64 tiles than ~half the CUs
-    if (a.N <= 128 && a.M < 32768) return 3;   // 64x64 tiles, K step 64 (the ConvNeXt 1x1s have enough rows for 128x64)
-    {   // N a multiple of 96 and a multi-round 128x64 grid that leaves the last round mostly empty: 64x96 tiles balance it
-        // (measured -9 % on 4064x1152x512, -4 % on 2048x1536x768; no gain on single-round grids, which are bubble-bound)
-        const long long b5 = (long long)cdiv(a.M, 128) * cdiv(a.N, 64), b6 = (long long)cdiv(a.M, 64) * (a.N / 96);
-        const bool plain = a.cv_Fout == 0 && !a.w_kn && a.nb0 * a.nb1 == 1 && a.K % 32 == 0 && a.K >= 64;
-        if (plain && a.N % 96 == 0 && b5 > 256 && cdiv(b6, 256) * 6144 * 100 <= cdiv(b5, 256) * 8192 * 80) return 11;
-        // 128x64 tiles that fill the last round of the 256 CUs badly while 64x64 tiles fill it well (the 6.25 Hz stack: 2048 rows x
-        // 1536 / 2080 / 2560 columns -> 384 / 528 / 640 tiles): the smaller tile costs ~7 % per tile and wins 7-14 % on balance
-        // (tools/probes/m2048_probe.py)
-        const long long b9 = (long long)cdiv(a.M, 64) * cdiv(a.N, 64);
-        const double e5 = (double)b5 / (double)(cdiv(b5, 256) * 256), e9 = (double)b9 / (double)(cdiv(b9, 256) * 256);
-        if (plain && a.K >= 512 && b5 > 256 && e9 >= e5 + 0.12) return 9;
-    }
-    return 5;                   // 128x64 tiles, 8 waves (LDS-DMA pipeline when K % 32 == 0)
+// ring entry E with the fused GLU + chunk-causal conv tail (gemm_glu_causal_conv)
+template <int E>
+void launch_ring_conv_entry(const Ctx& ctx, const GemmArgs& a) {
+    static_assert(kRing[E].LW == 0, "conv tail: no loader waves");
+    launch_ring_conv<kRing[E].BM, kRing[E].BN, kRing[E].KS, kRing[E].NST, kRing[E].PF>(ctx, a);
 }
 
 }  // namespace
-
-int g_ablate = 0;
-int g_use_dma = 1;
-void debug_ring_shape(int idx, int* bm, int* bn, int* waves) {
-    K2_REQUIRE(idx >= 0 && idx < (int)(sizeof(kRing) / sizeof(kRing[0])), "no ring cfg %d", idx);
-    *bm = kRing[idx].BM;
-    *bn = kRing[idx].BN;
-    *waves = (kRing[idx].BM / 32) * (kRing[idx].BN / 32) * kRing[idx].KS + kRing[idx].LW + kRing[idx].PF;
-}
-int g_forced_ring = -1;
-int g_forced_pipe = -1;
-int g_forced_p16 = -1;
-void debug_pipe_shape(int cfg, int M, int N, int* n_wg, int* waves) {
-    const int idx = (cfg - 2000) % 100;
-    K2_REQUIRE(idx >= 0 && idx < (int)(sizeof(kPipe) / sizeof(kPipe[0])), "no pipe cfg %d", idx);
-    *n_wg = cdiv(M, kPipe[idx].BM) * cdiv(N, kPipe[idx].BN);
-    *waves = (kPipe[idx].BM / kPipe[idx].WM) * (kPipe[idx].BN / kPipe[idx].WN);
-}
-void debug_force_gemm_cfg(int cfg) {
-    const int dma_default = 1;
-    g_forced_pipe = -1;
-    g_forced_p16 = -1;
-    if (cfg >= 3000) {  // 16x16x4 pipelined kernel table
-        g_forced_p16 = cfg - 3000;
-        g_forced_ring = -1;
-        g_forced_cfg = -1;
-        g_ablate = 0;
-        g_use_dma = dma_default;
-        return;
-    }
-    if (cfg >= 2000) {  // pipelined kernel table
-        g_forced_pipe = cfg - 2000;
-        g_forced_ring = -1;
-        g_forced_cfg = -1;
-        g_ablate = 0;
-        g_use_dma = dma_default;
-        return;
-    }
-    g_forced_ring = cfg >= 100 ? ((cfg - 100) & 0xff) : -1;
-    if (cfg >= 100) {
-        g_ablate = (cfg - 100) >> 8;
-        g_forced_cfg = -1;
-        g_use_dma = dma_default;
-        return;
-    }
-    g_forced_cfg = cfg < 0 ? -1 : (cfg & 0x3f);
-    g_ablate = cfg < 0 ? 0 : (cfg >> 8);
-    g_use_dma = (cfg >= 0 && (cfg & 0x40)) ? 0 : dma_default;  // +64: classic (register-staged) kernel
-}
 
 void gemm(const Ctx& ctx, const GemmArgs& a) {
     K2_REQUIRE(a.M > 0 && a.N > 0 && a.K > 0, "gemm: empty shape %dx%dx%d", a.M, a.N, a.K);
@@ -1867,167 +1730,57 @@ void gemm(const Ctx& ctx, const GemmArgs& a) {
     ctx.add_flops(fl, 0.0, 1);
     if (ctx.dry) return;
     if (ctx.instrument) K2_HIP(hipEventRecord(ctx.next_event(), ctx.stream));
-    int cfg = choose_cfg(a);
+    const GemmPlan p = plan_gemm(a, gemm_force());
     GemmArgs b = a;
-    b.ablate = g_ablate;
+    b.ablate = p.ablate;
     b.xcd_panels = tunables().xcd_panels;
-    if (ctx.instrument && ctx.gemm_log)
-        ctx.gemm_log->push_back({a.M, a.N, a.K, a.nb0 * a.nb1, a.act, a.res != nullptr, a.cv_Fout > 0 ? 1 : (a.w_kn ? 2 : 0), 0.f});
-    // (a) N <= 96: few columns; (b) small problems (streaming chunks, beam search: a 128x64 grid would leave most CUs idle and
-    // every workgroup would walk K serially): the same kernel over column chunks of 96
-    if (g_forced_p16 >= 0) {  // tuning hook
-        K2_REQUIRE(a.cv_Fout == 0 && !a.w_kn && !a.mul && a.res_div == 1 && !a.act_after_res && !a.glu && a.K % 32 == 0 && a.K >= 64 && a.nb0 * a.nb1 == 1,
-                   "p16 cfg %d does not fit this GEMM", g_forced_p16);
-        K2_REQUIRE(launch_p16_idx(ctx, b, g_forced_p16), "no p16 cfg %d", g_forced_p16);
-        K2_HIP(hipGetLastError());
-        if (ctx.instrument) K2_HIP(hipEventRecord(ctx.next_event(), ctx.stream));
-        return;
-    }
-    if (g_forced_pipe >= 0) {  // tuning hook
-        K2_REQUIRE(a.cv_Fout == 0 && !a.w_kn && !a.mul && a.res_div == 1 && !a.act_after_res && a.K % 32 == 0 && a.K >= 64 && a.nb0 * a.nb1 == 1,
-                   "pipe cfg %d does not fit this GEMM", g_forced_pipe);
-        K2_REQUIRE(launch_pipe_idx(ctx, b, g_forced_pipe), "no pipe cfg %d", g_forced_pipe);
-        K2_HIP(hipGetLastError());
-        if (ctx.instrument) K2_HIP(hipEventRecord(ctx.next_event(), ctx.stream));
-        return;
-    }
-    if (g_forced_ring >= 0) {  // tuning hook
-        const RingCfg& rc = kRing[g_forced_ring];
-        K2_REQUIRE(a.cv_Fout == 0 && !a.w_kn && !a.mul && a.res_div == 1 && !a.act_after_res && a.K % (32 * rc.KS) == 0 && a.K >= 32 * rc.KS,
-                   "ring cfg %d does not fit this GEMM", g_forced_ring);
-        K2_REQUIRE(launch_ring_idx(ctx, b, g_forced_ring), "no ring cfg %d", g_forced_ring);
-        K2_HIP(hipGetLastError());
-        if (ctx.instrument) K2_HIP(hipEventRecord(ctx.next_event(), ctx.stream));
-        return;
-    }
-    const Tunables& tn = tunables();
-    const bool forced = g_forced_cfg >= 0 || tn.gemm_cfg >= 0, use_dma = g_use_dma != 0;
-    const bool plain = a.cv_Fout == 0 && !a.w_kn && a.nb0 * a.nb1 == 1 && a.K % 64 == 0 && a.K >= 64;
-    // (16-row workgroups re-read the weight chunk M/16 times: with many rows and a short K the 64x64 tiles are better)
-    const bool few_tiles = (long long)cdiv(a.M, 128) * cdiv(a.N, 64) < 144 && a.M <= 4096 && !(a.M >= 2048 && a.K <= 256 && a.N > 272);
-    const bool skinny_ok = !forced && plain && !a.mul && ((a.N <= 96 && a.M >= 512) || few_tiles);
-    const bool skinny16_ok = skinny_ok && !a.glu;  // the 16-column C/D layout of gemm_f32_mfma_skinny has no lane pair 16 apart
-    // Small problems with more than a handful of columns (the streaming chunk step: 256 .. 2048 rows): small ring tiles with the
-    // K step split over four (two) wave groups of the workgroup put 4 - 8 waves on ~200 CUs and walk K in K / 128 (K / 64) steps
-    // through coalesced LDS-DMA tiles, where the 16-row skinny kernel re-reads the weight chunk M / 16 times straight into
-    // fragment layout (half-used cache lines; it is bound by the texture-address path, not by latency).  Choice by grid size,
-    // from tools/gemm_lab.py streaming (gpurun_out/lab_str1.txt): 17 % less GEMM time over the chunk step's shapes.
-    if (skinny_ok && few_tiles && a.N > 96 && a.res_div == 1 && !a.act_after_res) {
-        const long long g32 = (long long)cdiv(a.M, 32) * cdiv(a.N, 32), g6432 = (long long)cdiv(a.M, 64) * cdiv(a.N, 32);
-        int ring = -1;
-        if (a.K % 128 == 0 && g32 <= 256) ring = 16;          // 32x32 tiles, KS 4, 4 stages + L2 prefetch wave
-        else if (a.K % 128 == 0 && g6432 <= 256) ring = 17;   // 64x32 tiles, KS 4, 3 stages
-        // K a multiple of 64 but not of 128 (the 256-wide stacks' feed-forward outputs: K = 576 / 960, and K = 192): 32x64 tiles, KS 2 --
-        // round 4, tools/gemm_lab.py streaming-real (gpurun_out/r4c/lab_stream.txt): 1024 x 256 x 960 14.7 against 17.3 us (skinny),
-        // x 576 10.4 against 12.2, 2048 x 192 x 192 6.2 against 7.9 (64x64 tiles)
-        else if (a.K % 64 == 0 && a.K % 128 != 0 && (long long)cdiv(a.M, 32) * cdiv(a.N, 64) <= 256) ring = 12;
-        else if (a.K % 64 == 0 && (long long)cdiv(a.M, 64) * cdiv(a.N, 64) >= 96) ring = 8;  // 64x64 tiles, KS 2, 3 stages
-        if (ring >= 0) {
-            launch_ring_idx(ctx, b, ring);
-            K2_HIP(hipGetLastError());
-            if (ctx.instrument && ctx.gemm_log) ctx.gemm_log->back().kind += 64;
-            if (ctx.instrument) K2_HIP(hipEventRecord(ctx.next_event(), ctx.stream));
-            return;
-        }
-    }
-    // a few hundred rows x <= 96 columns with a long enough K (the streaming value projections of the downsampled stacks: 256 x 96 x 512,
-    // 512 x 48 x 384): 32x32 ring tiles with the K step split four ways, 6.4 / 5.7 against 9.3 / 6.5 us (same lab run)
-    if (skinny16_ok && a.N <= 96 && a.M <= 512 && a.K % 128 == 0 && a.K >= 384 && a.res_div == 1 && !a.act_after_res) {
-        launch_ring_idx(ctx, b, 15);
-        K2_HIP(hipGetLastError());
-        if (ctx.instrument && ctx.gemm_log) ctx.gemm_log->back().kind += 64;
-        if (ctx.instrument) K2_HIP(hipEventRecord(ctx.next_event(), ctx.stream));
-        return;
-    }
-    if (skinny16_ok) {
-        if (a.N <= 48) hipLaunchKernelGGL(gemm_f32_mfma_skinny<3>, dim3(cdiv(a.M, 16), 1), dim3(256), 0, ctx.stream, b);
-        else if (a.K % 128 == 0 && ((a.K >= 1024 && (long long)cdiv(a.M, 16) * cdiv(a.N, 96) <= 384) ||
-                                    (a.K >= 512 && (long long)cdiv(a.M, 16) * cdiv(a.N, 96) <= 128)))
+    switch (p.family) {
+        case GemmFamily::REG:
+            if (p.mode == MODE_CONV) launch_reg<MODE_CONV>(ctx, b, p.idx);
+            else if (p.mode == MODE_WKN) launch_reg<MODE_WKN>(ctx, b, p.idx);
+            else launch_reg<MODE_PLAIN>(ctx, b, p.idx);
+            break;
+        case GemmFamily::DMA:
+            switch (p.idx) {
+#define X(i, bm, bn, wm, wn, nst) case i: launch_dma<bm, bn, wm, wn, nst>(ctx, b); break;
+                K2_DMA_TABLE(X)
+#undef X
+            }
+            break;
+        case GemmFamily::PIPE:
+            switch (p.idx) {
+#define X(i, bm, bn, wm, wn, nst) case i: launch_pipe<bm, bn, wm, wn, nst>(ctx, b); break;
+                K2_PIPE_TABLE(X)
+#undef X
+            }
+            break;
+        case GemmFamily::P16:
+            switch (p.idx) {
+#define X(i, bm, bn, wm, wn, nst) case i: launch_p16<bm, bn, wm, wn, nst>(ctx, b); break;
+                K2_P16_TABLE(X)
+#undef X
+            }
+            break;
+        case GemmFamily::RING:
+            switch (p.idx) {
+#define X(i, bm, bn, ks, nst, lw, pf) case i: launch_ring<bm, bn, ks, nst, lw, pf>(ctx, b); break;
+                K2_RING_TABLE(X)
+#undef X
+            }
+            break;
+        case GemmFamily::SKINNY3:
+            hipLaunchKernelGGL(gemm_f32_mfma_skinny<3>, dim3(cdiv(a.M, 16), 1), dim3(256), 0, ctx.stream, b);
+            break;
+        case GemmFamily::SKINNY6:
+            hipLaunchKernelGGL(gemm_f32_mfma_skinny<6>, dim3(cdiv(a.M, 16), cdiv(a.N, 96)), dim3(256), 0, ctx.stream, b);
+            break;
+        case GemmFamily::SKINNY6_8:
             hipLaunchKernelGGL((gemm_f32_mfma_skinny<6, 8>), dim3(cdiv(a.M, 16), cdiv(a.N, 96)), dim3(512), 0, ctx.stream, b);
-        else hipLaunchKernelGGL(gemm_f32_mfma_skinny<6>, dim3(cdiv(a.M, 16), cdiv(a.N, 96)), dim3(256), 0, ctx.stream, b);
-        K2_HIP(hipGetLastError());
-        if (ctx.instrument && ctx.gemm_log) ctx.gemm_log->back().kind += 32;
-        if (ctx.instrument) K2_HIP(hipEventRecord(ctx.next_event(), ctx.stream));
-        return;
+            break;
     }
-    const bool dma_ok = a.cv_Fout == 0 && !a.w_kn && a.K % 32 == 0 && a.K >= 64 && a.lda % 4 == 0 && !a.mul && a.res_div == 1 && !a.act_after_res;
-    if (dma_ok && use_dma && !forced && a.nb0 * a.nb1 > 1 && a.M <= 64) {
-        // a handful of rows against many layers' weight matrices (LSTM wavefront): a weight-streaming problem -- 64x64 tiles, three
-        // 16 KB stages in flight per workgroup
-        // enough workgroups to keep ~3 per CU streaming (bytes in flight are what sets the rate): 32-column tiles when 64-column
-        // tiles would give fewer than ~600
-        if ((long long)cdiv(a.N, 64) * a.nb0 * a.nb1 < 600) launch_dma<32, 32, 32, 32, 4>(ctx, b);
-        else launch_dma<32, 64, 32, 32, 4>(ctx, b);
-        K2_HIP(hipGetLastError());
-        if (ctx.instrument && ctx.gemm_log) ctx.gemm_log->back().kind += 16;
-        if (ctx.instrument) K2_HIP(hipEventRecord(ctx.next_event(), ctx.stream));
-        return;
-    }
-    // One problem per launch, K % 32 == 0: the pipelined kernel, tile by a small cost model fitted to tools/gemm_lab.py offline
-    // (gpurun_out/lab_pipe3.txt).  The busiest CU runs ceil(tiles / 256) tiles; a tile costs its K steps plus a fixed part (prologue,
-    // last steps, epilogue -- less of it is exposed when several small workgroups share the CU), small tiles pay a few percent
-    // for their extra operand traffic.  Examples it reproduces: 4064 x 512 -> 128x64 (256 tiles, one round); 4064 x 1152,
-    // 2048 x 2560 / 2080 -> 64x64 (1152 / 1280 / 1056 tiles: 4.5 / 5 / 4.1 rounds of 4096 instead of 2.25 / 2.5 / 2.1 -> 3 of 8192);
-    // 4064 x 1024 / 1920, 2048 x 2048 -> 128x128; 16160 x 192 -> 64x64 or 128x32 (3 rounds of 4096 instead of 2 of 8192).
-    if (dma_ok && use_dma && !forced && a.nb0 * a.nb1 == 1 && a.K >= 64 && a.M >= 256 &&
-        (long long)a.M * a.lda < (1ll << 29) && (long long)a.N * a.ldw < (1ll << 29)) {
-        struct Cand { int idx, bm, bn; double fixed_steps, penalty; };
-        static const Cand cands[] = {{8, 128, 128, 3.5, 0.0}, {1, 128, 64, 3.3, 0.02}, {5, 64, 64, 4.0, 0.12}, {13, 128, 32, 5.5, 0.08}};
-        const double nk = a.K / 32.0;
-        int best = -1;
-        double best_cost = 0;
-        for (const Cand& c : cands) {
-            const long long tiles = (long long)cdiv(a.M, c.bm) * cdiv(a.N, c.bn);
-            const double cost = (double)cdiv(tiles, 256) * c.bm * c.bn * (nk + c.fixed_steps) * (1.0 + c.penalty);
-            if (best < 0 || cost < best_cost) {
-                best = c.idx;
-                best_cost = cost;
-            }
-        }
-        // The 16x16x4 form's 64 x 96 tile (gemm_f32_mfma_p16, round 5) where N is a multiple of 96 and the same model prefers it: the
-        // launches that quantise badly in 32 x 32 blocks -- 2048 x 768 is 256 tiles of 64 x 96 against 192 of 128 x 64 (tools/gemm_lab.py,
-        // gpurun_out/r5j/lab_p16.txt: 69.3 against 83.5 us at K = 2560, 57.2 / 67.8 at 2048, 44.7 / 52.5 at 1536, 25.7 / 29.0 at 768;
-        // 4064 x 1152 x 512 47.4 / 48.3; it loses where 128 x 64 already divides the output: 8096 x 768 x 256 40.7 / 36.3, which the model
-        // reproduces).  One wave per SIMD on a single-round grid, so its prologue and tail are fully exposed: six fixed steps.
-        if (a.N % 96 == 0 && !a.glu && a.M >= 1024) {
-            const long long tiles = (long long)cdiv(a.M, 64) * (a.N / 96);
-            // (a long K loop amortises the form's extra operand traffic: 16160 x 192 x 2432 is 126.8 us on it against 134.8 on 128 x 32,
-            // gpurun_out/r5q/lab_p16_all.txt -- 6 % over the other tiles from 64 K steps, 10 % below)
-            const double cost = (double)cdiv(tiles, 256) * 64 * 96 * (nk + 6.0) * (nk >= 64 ? 1.06 : 1.10);
-            if (tiles >= 128 && cost < best_cost) {
-                launch_p16_idx(ctx, b, 0);
-                K2_HIP(hipGetLastError());
-                // (+128 + 2048: the pipelined kernel on 16x16x4 tiles; BM / 32 = 2 in bits 8-11, BN / 32 = 3 in bits 12-15)
-                if (ctx.instrument && ctx.gemm_log) ctx.gemm_log->back().kind += 128 + 256 * 2 + 4096 * 3 + (1 << 20);
-                if (ctx.instrument) K2_HIP(hipEventRecord(ctx.next_event(), ctx.stream));
-                return;
-            }
-        }
-        launch_pipe_idx(ctx, b, best);
-        K2_HIP(hipGetLastError());
-        // (+128: the pipelined kernel; its tile in bits 8.. so that a profile can be grouped by instantiation: BM / 32, BN / 32)
-        if (ctx.instrument && ctx.gemm_log) ctx.gemm_log->back().kind += 128 + 256 * (kPipe[best].BM / 32) + 4096 * (kPipe[best].BN / 32);
-        if (ctx.instrument) K2_HIP(hipEventRecord(ctx.next_event(), ctx.stream));
-        return;
-    }
-    // (batched launches too -- the Conformer's per-(head, stream) score products -- as long as the tile choice is one of the DMA kernel's)
-    if (dma_ok && use_dma && (cfg == 5 || cfg == 0 || (cfg >= 7 && cfg <= 11))) {
-        if (cfg == 11) launch_dma<64, 96, 32, 32, 2>(ctx, b);        // 64x96 tiles (6 waves): N % 96 == 0 outputs that 128x64 quantises badly
-        else if (cfg == 9) launch_dma<64, 64, 32, 32, 2>(ctx, b);    // tuning: 64x64 tiles, 2 stages
-        else if (cfg == 10) launch_dma<64, 64, 32, 32, 3>(ctx, b);   // tuning: 64x64 tiles, 3 stages
-        else if (cfg == 7) launch_dma<128, 64, 32, 32, 2>(ctx, b);  // tuning: 2 stages, 3 workgroups per CU
-        else if (cfg == 8) launch_dma<128, 64, 32, 32, 4>(ctx, b);  // tuning: 4 stages, 1 workgroup per CU
-        else if (cfg == 5) launch_dma<128, 64, 32, 32, 2>(ctx, b);  // 2 stages: 3 workgroups per CU
-        else launch_dma<128, 128, 64, 32>(ctx, b);
-        K2_HIP(hipGetLastError());
-        if (ctx.instrument && ctx.gemm_log) ctx.gemm_log->back().kind += 16;
-        if (ctx.instrument) K2_HIP(hipEventRecord(ctx.next_event(), ctx.stream));
-        return;
-    }
-    if (a.cv_Fout > 0) launch_mode<MODE_CONV>(ctx, b, cfg);
-    else if (a.w_kn) launch_mode<MODE_WKN>(ctx, b, cfg);
-    else launch_mode<MODE_PLAIN>(ctx, b, cfg);
     K2_HIP(hipGetLastError());
+    if (ctx.instrument && ctx.gemm_log)
+        ctx.gemm_log->push_back({a.M, a.N, a.K, a.nb0 * a.nb1, a.act, a.res != nullptr, gemm_kind(a, p), 0.f});
     if (ctx.instrument) K2_HIP(hipEventRecord(ctx.next_event(), ctx.stream));
 }
 
@@ -2035,20 +1788,8 @@ bool gemm_glu_causal_conv(const Ctx& ctx, const float* x, const float* wg, const
                           const int* slots, const float* wc, const float* bc, const float* ww, const float* bw, const float* sc, float* y, int B,
                           int Tc, int D, int K) {
     const int M = B * Tc, N = 2 * D;
-    // tiles: 32 / 64 rows of whole streams (Tc | 32), 32 / 64 GEMM columns of whole (value | gate) blocks; the K step split over the
-    // workgroup's wave groups as the dispatcher of gemm() does for these shapes (streaming chunk steps: a few hundred tiles at most)
-    if (Tc < 2 || 32 % Tc != 0 || D % 64 != 0 || (K != 31 && K != 15 && K != 7)) return false;
-    const long long g32 = (long long)cdiv(M, 32) * (N / 32), g6432 = (long long)cdiv(M, 64) * (N / 32);
-    int form = -1;   // 0: 32x32 KS 4 (4 stages), 1: 64x32 KS 4, 2: 32x64 KS 2, 3: 64x64 KS 2
-    if (D % 128 == 0 && g32 <= 256) form = 0;
-    else if (D % 128 == 0 && g6432 <= 256) form = 1;
-    else if (D % 128 == 0) form = 3;
-    else if ((long long)cdiv(M, 32) * (N / 64) <= 256) form = 2;
-    else form = 3;
-    {   // the tail's cache staging holds at most 8 elements per thread (conv_tail): tile's streams x channels x cached frames
-        const int bm = (form == 1 || form == 3) ? 64 : 32, ch = (form >= 2) ? 32 : 16, nthr = (bm / 32) * (ch / 16) * (form >= 2 ? 2 : 4) * 64;
-        if ((long long)(bm / Tc) * ch * (K >> 1) > 8ll * nthr) return false;
-    }
+    const int entry = glu_conv_ring_entry(B, Tc, D, K);
+    if (entry < 0) return false;
     const double fl = 2.0 * M * (double)N * D;
     ctx.add_flops(fl, 2.0 * M * (double)D * (K + (K + 1) / 2), 1);
     if (ctx.dry) return true;
@@ -2059,11 +1800,11 @@ bool gemm_glu_causal_conv(const Ctx& ctx, const float* x, const float* wg, const
     g.xcd_panels = tunables().xcd_panels;
     if (ctx.instrument) K2_HIP(hipEventRecord(ctx.next_event(), ctx.stream));
     if (ctx.instrument && ctx.gemm_log) ctx.gemm_log->push_back({M, N, D, 1, 0, 0, 64, 0.f});
-    switch (form) {
-        case 0: launch_ring_conv<32, 32, 4, 4, 1>(ctx, g); break;   // (+ the L2-prefetch wave, as gemm()'s choice for this grid has it)
-        case 1: launch_ring_conv<64, 32, 4, 3>(ctx, g); break;
-        case 2: launch_ring_conv<32, 64, 2, 3>(ctx, g); break;
-        default: launch_ring_conv<64, 64, 2, 3>(ctx, g); break;
+    switch (entry) {
+        case 16: launch_ring_conv_entry<16>(ctx, g); break;
+        case 17: launch_ring_conv_entry<17>(ctx, g); break;
+        case 12: launch_ring_conv_entry<12>(ctx, g); break;
+        default: launch_ring_conv_entry<8>(ctx, g); break;
     }
     K2_HIP(hipGetLastError());
     if (ctx.instrument) K2_HIP(hipEventRecord(ctx.next_event(), ctx.stream));

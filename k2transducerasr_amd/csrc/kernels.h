@@ -45,7 +45,7 @@ struct Tunables {
                                   // (greedy.hip screen_round: exact tokens, ~2.5x fewer bytes per round); 0 = never
     int max_streams = 0;          // K2HIP_MAX_STREAMS: slots of the streaming state pool (0 = 256)
     // ---- tuning probes (-DK2HIP_DEV builds only)
-    K2HIP_DEV_SWITCH(gemm_cfg, -1);         // K2HIP_GEMM_CFG: force one tile configuration
+    K2HIP_DEV_SWITCH(gemm_cfg, -1);         // K2HIP_GEMM_CFG: force one tile configuration (a k2hip_debug_gemm cfg code: GemmForce)
     K2HIP_DEV_SWITCH(xcd_panels, 0);        // K2HIP_XCD_PANELS: 1 = every GEMM's tiles as bands of M per XCD (rounds 1 - 3)
     K2HIP_DEV_SWITCH(greedy_stamps, 0);     // K2HIP_GREEDY_STAMPS: the persistent search reports where a round's time goes (stderr, synchronous)
     K2HIP_DEV_SWITCH(conformer_stamps, 0);  // K2HIP_CONFORMER_STAMPS: the Conformer scores kernel reports its phases (stderr, synchronous)
@@ -62,7 +62,7 @@ struct GemmStats {
 };
 
 struct GemmLaunchRec {  // one row per GEMM launch of an instrumented call
-    int M, N, K, batch, act, res, kind;  // kind: 0 plain, 1 conv gather, 2 [K,N] operand; +16 = LDS-DMA kernel
+    int M, N, K, batch, act, res, kind;  // kind: 0 plain, 1 conv gather, 2 [K,N] operand; + the kernel family (gemm_kind)
     float us;
 };
 
@@ -168,9 +168,75 @@ void gemm(const Ctx& ctx, const GemmArgs& a);
 bool gemm_glu_causal_conv(const Ctx& ctx, const float* x, const float* wg, const float* bg, float* pool, long long slot_stride, long long off,
                           const int* slots, const float* wc, const float* bc, const float* ww, const float* bw, const float* sc, float* y, int B,
                           int Tc, int D, int K);
-void debug_force_gemm_cfg(int cfg);  // tuning hook: -1 = automatic
-void debug_pipe_shape(int cfg, int M, int N, int* n_wg, int* waves);  // grid and waves of pipe cfg (>= 2000) on a shape
-void debug_ring_shape(int idx, int* bm, int* bn, int* waves);  // tile and waves of ring table entry idx
+
+// ---- GEMM tile plan (gemm_plan.cpp, host only): which kernel instantiation gemm() launches for a GemmArgs, decided without
+// launching.  The tile tables of the kernel families; a table index is the k2hip_debug_gemm cfg code that forces the entry, less the
+// family's base (pipe 2000, p16 3000, ring 100, LDS-DMA and register-staged 0).
+// pipelined kernel on 32x32x2 MFMAs (gemm_f32_mfma_pipe): BM, BN, WM, WN, stages
+#define K2_PIPE_TABLE(X)                                                                                                       \
+    X(0, 128, 64, 64, 32, 3) X(1, 128, 64, 32, 32, 3) X(2, 128, 128, 64, 64, 3) X(3, 128, 128, 64, 32, 3) X(4, 128, 64, 64, 32, 4)  \
+    X(5, 64, 64, 32, 32, 3) X(6, 128, 128, 64, 64, 4) X(7, 64, 128, 32, 64, 3) X(8, 128, 128, 32, 32, 3) X(9, 128, 64, 32, 32, 4) \
+    X(10, 64, 64, 64, 32, 3) X(11, 64, 64, 32, 64, 3) X(12, 256, 64, 64, 32, 3) X(13, 128, 32, 32, 32, 3) X(14, 128, 32, 64, 32, 3)
+// pipelined kernel on 16x16x4 MFMAs (gemm_f32_mfma_p16): 4 waves of 32 x 48, 64 x 48, 32 x 96, 16 x 48
+#define K2_P16_TABLE(X) X(0, 64, 96, 32, 48, 3) X(1, 128, 96, 64, 48, 3) X(2, 64, 192, 32, 96, 3) X(3, 32, 96, 16, 48, 3)
+// ring kernel (gemm_f32_mfma_ring): BM, BN, K groups, stages, loader waves, L2-prefetch wave
+#define K2_RING_TABLE(X)                                                                                        \
+    X(0, 128, 64, 1, 2, 0, 0) X(1, 128, 64, 1, 3, 0, 0) X(2, 128, 64, 1, 2, 0, 1) X(3, 128, 64, 1, 3, 0, 1) X(4, 128, 64, 1, 4, 0, 1)   \
+    X(5, 64, 64, 1, 3, 0, 0) X(6, 64, 64, 1, 3, 0, 1) X(7, 64, 64, 1, 4, 0, 1) X(8, 64, 64, 2, 3, 0, 0) X(9, 64, 64, 2, 3, 0, 1)      \
+    X(10, 64, 64, 4, 2, 0, 0) X(11, 64, 64, 4, 2, 0, 1) X(12, 32, 64, 2, 3, 0, 0) X(13, 32, 64, 4, 3, 0, 0) X(14, 32, 64, 4, 3, 0, 1)  \
+    X(15, 32, 32, 4, 3, 0, 0) X(16, 32, 32, 4, 4, 0, 1) X(17, 64, 32, 4, 3, 0, 0) X(18, 128, 128, 1, 2, 0, 0) X(19, 128, 128, 1, 2, 0, 1) \
+    X(20, 64, 128, 1, 3, 0, 0) X(21, 64, 128, 1, 3, 0, 1) X(22, 64, 96, 1, 3, 0, 0) X(23, 64, 96, 1, 3, 0, 1) X(24, 128, 96, 1, 2, 0, 1) \
+    X(25, 128, 64, 1, 3, 2, 0) X(26, 128, 64, 1, 3, 2, 1) X(27, 128, 64, 2, 2, 0, 1) X(28, 64, 96, 2, 3, 0, 0) X(29, 64, 96, 2, 2, 0, 0) \
+    X(30, 64, 96, 2, 2, 0, 1) X(31, 128, 96, 1, 3, 0, 0) X(32, 128, 96, 1, 3, 0, 1)
+struct RingCfg { int BM, BN, KS, NST, LW, PF; };
+#define X(i, bm, bn, ks, nst, lw, pf) {bm, bn, ks, nst, lw, pf},
+constexpr RingCfg kRing[] = {K2_RING_TABLE(X)};
+#undef X
+// LDS-DMA kernel (gemm_f32_mfma_dma): BM, BN, WM, WN, stages.  cfg 7 forces 5's tile; 20 and 21 are the batched few-row tiles, which
+// no cfg forces.
+#define K2_DMA_TABLE(X)                                                                                                          \
+    X(0, 128, 128, 64, 32, 3) X(5, 128, 64, 32, 32, 2) X(8, 128, 64, 32, 32, 4) X(9, 64, 64, 32, 32, 2) X(10, 64, 64, 32, 32, 3) \
+    X(11, 64, 96, 32, 32, 2) X(20, 32, 32, 32, 32, 4) X(21, 32, 64, 32, 32, 4)
+// register-staged kernel (gemm_f32_mfma): BM, BN, WM, WN, BK.  cfg 7, 8, 11 force 5's tile, every other cfg below 64 2's.
+#define K2_REG_TABLE(X)                                                                                                           \
+    X(0, 128, 128, 64, 32, 32) X(1, 128, 128, 64, 32, 64) X(2, 64, 64, 32, 32, 32) X(3, 64, 64, 32, 32, 64) X(4, 128, 64, 32, 32, 64) \
+    X(5, 128, 64, 32, 32, 32) X(12, 128, 32, 32, 32, 32)
+enum GemmMode { MODE_PLAIN = 0, MODE_CONV = 1, MODE_WKN = 2 };  // the register-staged kernel's A / W addressing
+
+// skinny: gemm_f32_mfma_skinny<3>, <6>, <6, 8> (16 rows x 48 / 96 columns per workgroup, 4 / 4 / 8 waves)
+enum class GemmFamily { REG, DMA, PIPE, P16, RING, SKINNY3, SKINNY6, SKINNY6_8 };
+struct GemmPlan {
+    GemmFamily family = GemmFamily::REG;
+    int idx = 0;                    // entry of the family's table (skinny: 0)
+    int mode = MODE_PLAIN;          // REG only
+    int ablate = 0;                 // GemmArgs.ablate (tuning only)
+    int BM = 0, BN = 0, waves = 0;  // the entry's workgroup tile and waves per workgroup
+};
+// A forced tile choice (tuning hooks), decoded from a k2hip_debug_gemm cfg code by decode_gemm_force:
+//   < 0: automatic
+//   0 .. 63: the LDS-DMA tile of cfg (0, 5, 7 .. 11) where the GEMM suits that kernel, else the register-staged tile of cfg;
+//            +64: register-staged only; +256 n: ablate n
+//   100 + i (+256 n): ring entry i (ablate n);  2000 + i: pipe entry i;  3000 + i: p16 entry i
+struct GemmForce {
+    enum Kind { AUTO, CFG, RING, PIPE, P16 } kind = AUTO;
+    int idx = -1;
+    int ablate = 0;
+    bool dma = true;  // CFG: the LDS-DMA kernel where the cfg names one of its tiles
+};
+GemmForce decode_gemm_force(int code);
+// gemm()'s choice of kernel for a GEMM under a force; throws (K2HIP_ERR_INVALID) when a forced entry does not exist or does not fit
+GemmPlan plan_gemm(const GemmArgs& a, const GemmForce& f);
+int gemm_kind(const GemmArgs& a, const GemmPlan& p);  // GemmLaunchRec.kind of the launch
+// the ring entry of gemm_glu_causal_conv's fused form for B streams of Tc rows and D channels, conv kernel size K; -1 = no fused form
+int glu_conv_ring_entry(int B, int Tc, int D, int K);
+void debug_force_gemm_cfg(int code);  // tuning hook: -1 = automatic
+GemmForce gemm_force();  // what gemm() plans under: the tuning hook's force, else K2HIP_GEMM_CFG (DEV builds)
+struct GemmForceGuard {  // forces cfg code `code` for its lifetime, automatic again on scope exit
+    explicit GemmForceGuard(int code) { debug_force_gemm_cfg(code); }
+    ~GemmForceGuard() { debug_force_gemm_cfg(-1); }
+    GemmForceGuard(const GemmForceGuard&) = delete;
+    GemmForceGuard& operator=(const GemmForceGuard&) = delete;
+};
 // convenience: plain Linear  C = act(A W^T + b) (+res)
 void linear(const Ctx& ctx, const float* A, int lda, const float* W, const float* bias, float* C, int ldc, int M, int K,
             int N, int act = ACT_NONE, const float* res = nullptr, int ldr = 0);

@@ -6,6 +6,7 @@
 //   san_api_driver offline <offline.k2w> <seed> <rounds>     OfflineStream AddSamples in pieces, GetResults / GetResult, pipelined
 //                                                            submit / wait, operator-level calls with tight output buffers
 //   san_api_driver errors  <streaming.k2w>                   null arguments, wrong model, duplicates, poisoned streams
+//   san_api_driver plans   <gemm_plans.txt>                  csrc/gemm_plan.cpp's tile plan for each line's inputs (see plans below)
 // Any sanitizer report, crash or model mismatch fails the process; prints one summary line.
 #include <cstdio>
 #include <cstdlib>
@@ -15,6 +16,7 @@
 #include <vector>
 
 #include "../../include/k2hip.h"
+#include "../../k2transducerasr_amd/csrc/kernels.h"
 
 extern "C" void k2hip_stub_fail_next_step(int n);
 extern "C" void k2hip_stub_fail_next_gather_finish(int n);
@@ -335,6 +337,53 @@ int meta(const char* path, const char* key) {
     return 0;
 }
 
+// The GEMM tile plan of csrc/gemm_plan.cpp for each input line of `path` (tests/golden/gemm_plans.txt; text from " -> " on and lines
+// starting with '#' are ignored), printed as "<inputs> -> <plan>":
+//   gemm M N K batch conv w_kn mul res_div act_after_res glu lda ldw cfg -> family index BMxBN w<waves> a<ablate> k<kind> | error
+//     (cfg: the k2hip_debug_gemm code; kind "-" under a forced ring / pipe / p16 entry, which runs with instrumentation off)
+//   conv B Tc D K -> ring <entry> | none                                 (gemm_glu_causal_conv's fused form)
+int plans(const char* path) {
+    using namespace k2hip;
+    FILE* f = fopen(path, "r");
+    if (!f) { fprintf(stderr, "cannot open %s\n", path); return 2; }
+    static const char* kFamily[] = {"reg", "dma", "pipe", "p16", "ring", "skinny3", "skinny6", "skinny6_8"};
+    static const char* kMode[] = {"reg.plain", "reg.conv", "reg.wkn"};
+    char line[512];
+    while (fgets(line, sizeof line, f)) {
+        if (char* e = strstr(line, " -> ")) *e = 0;
+        line[strcspn(line, "\r\n")] = 0;
+        if (!line[0] || line[0] == '#') continue;
+        int v[13];
+        if (sscanf(line, "conv %d %d %d %d", &v[0], &v[1], &v[2], &v[3]) == 4) {
+            const int e = glu_conv_ring_entry(v[0], v[1], v[2], v[3]);
+            if (e < 0) printf("%s -> none\n", line);
+            else printf("%s -> ring %d\n", line, e);
+            continue;
+        }
+        CHECK(sscanf(line, "gemm %d %d %d %d %d %d %d %d %d %d %d %d %d", &v[0], &v[1], &v[2], &v[3], &v[4], &v[5], &v[6], &v[7], &v[8],
+                     &v[9], &v[10], &v[11], &v[12]) == 13);
+        GemmArgs a;
+        a.M = v[0]; a.N = v[1]; a.K = v[2]; a.nb0 = v[3]; a.cv_Fout = v[4]; a.w_kn = v[5];
+        static const float kMul = 1.f;  // (the plan looks at the presence of the operand only)
+        a.mul = v[6] ? &kMul : nullptr;
+        a.res_div = v[7]; a.act_after_res = v[8]; a.glu = v[9]; a.lda = v[10]; a.ldw = v[11];
+        const int cfg = v[12];
+        GemmPlan p;
+        try {
+            p = plan_gemm(a, decode_gemm_force(cfg));
+        } catch (const Error&) {
+            printf("%s -> error\n", line);
+            continue;
+        }
+        const char* fam = p.family == GemmFamily::REG ? kMode[p.mode] : kFamily[(int)p.family];
+        char kind[16] = "-";
+        if (cfg < 100) snprintf(kind, sizeof kind, "%d", gemm_kind(a, p));
+        printf("%s -> %s %d %dx%d w%d a%d k%s\n", line, fam, p.idx, p.BM, p.BN, p.waves, p.ablate, kind);
+    }
+    fclose(f);
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -342,6 +391,7 @@ int main(int argc, char** argv) {
     if (argc >= 5 && !strcmp(argv[1], "online")) return online(argv[2], strtoull(argv[3], nullptr, 10), atoi(argv[4]));
     if (argc >= 5 && !strcmp(argv[1], "offline")) return offline(argv[2], strtoull(argv[3], nullptr, 10), atoi(argv[4]));
     if (argc >= 3 && !strcmp(argv[1], "errors")) return errors(argv[2]);
-    fprintf(stderr, "usage: san_api_driver online|offline <model.k2w> <seed> <rounds> | errors <streaming.k2w> | meta <model.k2w> <key>\n");
+    if (argc >= 3 && !strcmp(argv[1], "plans")) return plans(argv[2]);
+    fprintf(stderr, "usage: san_api_driver online|offline <model.k2w> <seed> <rounds> | errors <streaming.k2w> | meta <model.k2w> <key> | plans <gemm_plans.txt>\n");
     return 2;
 }

@@ -211,6 +211,20 @@ def test_large_vocabulary_repack_under_sanitizers(api_driver, tmp_path):
     assert run(api_driver, "meta", p2, "model_type") == "zipformer2"
 
 
+def test_gemm_plans_match_the_golden_table(api_driver):
+    """csrc/gemm_plan.cpp, gemm()'s choice of kernel instantiation (family, table entry, tile, waves, ablate flag, profile kind), and
+    gemm_glu_causal_conv's ring entry, under the sanitizers, line by line against tests/golden/gemm_plans.txt: a grid across every
+    threshold of the selection rules, each flag, operands at and over 2^29 elements, each forced cfg code of tests/test_gemm_gpu.py
+    and tools/, and the GEMMs of the presets' offline and streaming passes.  A changed rule shows here as the rows it moves."""
+    golden = os.path.join(ROOT, "tests", "golden", "gemm_plans.txt")
+    with open(golden) as f:
+        want = [line.rstrip("\n") for line in f if line.strip() and not line.startswith("#")]
+    got = run(api_driver, "plans", golden).splitlines()
+    assert len(got) == len(want) > 800
+    moved = [(w, g) for w, g in zip(want, got) if w != g]
+    assert not moved, f"{len(moved)} plans differ from the table, first ones (want, got): {moved[:8]}"
+
+
 def test_host_layer_from_several_threads_under_thread_sanitizer(streaming_tiny_path, tiny_model_path):
     """INTEGRATION.md's threading contract -- calls on one handle serialise on its mutex, different handles run concurrently, any
     thread may call -- checked by ThreadSanitizer (`make tsan`: csrc/api.cpp + model.cpp + tunables.cpp over the CPU stand-in of the

@@ -19,7 +19,7 @@ L = pkg.load_library()
 L.k2hip_debug_gemm_check.argtypes = [C.c_void_p] + [C.c_int32] * 7 + [C.POINTER(C.c_float), C.POINTER(C.c_float)]
 
 import re
-_src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "k2transducerasr_amd", "csrc", "gemm.hip")).read()
+_src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "k2transducerasr_amd", "csrc", "kernels.h")).read()
 _tab = _src[_src.index("#define K2_RING_TABLE(X)") : _src.index("#define X(i, bm, bn, ks, nst, lw, pf) {bm")]
 RING = [tuple(int(v) for v in m[1:]) for m in sorted((tuple(int(x) for x in t) for t in re.findall(r"X\((\d+), (\d+), (\d+), (\d+), (\d+), (\d+), (\d+)\)", _tab)))]
 
@@ -97,11 +97,10 @@ if len(sys.argv) > 3:  # "MxN,MxN": only these output shapes
 
 
 
-_tab3 = _src[_src.index("#define K2_PIPE_TABLE(X)") : _src.index("const PipeCfg kPipe[]")]
+_tab3 = _src[_src.index("#define K2_PIPE_TABLE(X)") : _src.index("#define K2_P16_TABLE(X)")]
 PIPE = [tuple(int(v) for v in t[1:]) for t in sorted((tuple(int(x) for x in t) for t in re.findall(r"X\((\d+), (\d+), (\d+), (\d+), (\d+), (\d+)\)", _tab3)))]
-
-
-P16 = [(64, 96, 32, 48), (128, 96, 64, 48), (64, 192, 32, 96), (32, 96, 16, 48)]   # gemm.hip launch_p16_idx
+_tab4 = _src[_src.index("#define K2_P16_TABLE(X)") : _src.index("#define K2_RING_TABLE(X)")]
+P16 = [tuple(int(v) for v in t[1:5]) for t in sorted((tuple(int(x) for x in t) for t in re.findall(r"X\((\d+), (\d+), (\d+), (\d+), (\d+), (\d+)\)", _tab4)))]
 
 
 def name(c):
