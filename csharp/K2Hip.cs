@@ -75,6 +75,15 @@ namespace K2TransducerAsr.Hip
 
         [DllImport(Lib)] internal static extern int k2hip_model_meta(IntPtr model, string key, byte[] buf, int cap);
         [DllImport(Lib)] internal static extern int k2hip_set_decoding_method(IntPtr model, string method, int beam);
+        // hotword biasing of the offline modified beam search (k2hip.h "hotword biasing"; INTEGRATION.md "Hotwords").  ids: the phrases'
+        // token ids back to back, lens: tokens per phrase.  The model copies the tables: destroy the graph after k2hip_set_hotwords.
+        [DllImport(Lib)] internal static extern int k2hip_hotwords_create(long[] ids, int[] lens, int nPhrases, float scorePerToken, int vocabSize, out IntPtr hotwords);
+        [DllImport(Lib)] internal static extern int k2hip_hotwords_load(IntPtr tokens, string path, float scorePerToken, out IntPtr hotwords);
+        [DllImport(Lib)] internal static extern int k2hip_hotwords_destroy(IntPtr hotwords);
+        [DllImport(Lib)] internal static extern int k2hip_hotwords_num_states(IntPtr hotwords);
+        [DllImport(Lib)] internal static extern int k2hip_hotwords_step(IntPtr hotwords, int state, long token, out int nextState, out float bonus);
+        [DllImport(Lib)] internal static extern int k2hip_hotwords_pending(IntPtr hotwords, int state, out float pending);
+        [DllImport(Lib)] internal static extern int k2hip_set_hotwords(IntPtr model, IntPtr hotwords /* IntPtr.Zero clears */);
 
         // Which GPU?  The reference's constructors (OfflineRecognizer.cs:27-28, OnlineRecognizer.cs:18-19) take file paths and nothing
         // else, and they stay as they are: the device rides on the paths.

@@ -54,6 +54,7 @@ typedef struct k2hip_offline_stream k2hip_offline_stream_t;
 typedef struct k2hip_online_stream k2hip_online_stream_t;
 typedef struct k2hip_beam_stream k2hip_beam_stream_t;
 typedef struct k2hip_tokens k2hip_tokens_t;
+typedef struct k2hip_hotwords k2hip_hotwords_t;
 
 /* Fixed ids of the reference: OfflineModel.cs:18-20. */
 #define K2HIP_BLANK_ID 0
@@ -312,6 +313,47 @@ int32_t k2hip_beam_stream_num_tokens(const k2hip_beam_stream_t* s);
 int32_t k2hip_beam_stream_get_tokens(const k2hip_beam_stream_t* s, int64_t* tokens, int32_t cap);
 int32_t k2hip_beam_stream_get_timestamps(const k2hip_beam_stream_t* s, int32_t* timestamps, int32_t cap);
 int32_t k2hip_beam_stream_get_score(const k2hip_beam_stream_t* s, float* score);
+
+/* ---- hotword (contextual) biasing of the OFFLINE modified beam search ------------------------------------------------------
+ * The reference never got this far (Utils/HotwordsHelper.cs is a helper without a call site: it has no beam search); the
+ * semantics are the project's own, after icefall's ContextGraph, and are defined here and in DESIGN.md "Hotword biasing".
+ *
+ * Graph: P phrases, each a non-empty sequence of token ids in [0, vocab_size) without blank (0) and unk (2), and one
+ * score_per_token c (finite, >= 0).  The trie of the phrases with Aho-Corasick failure links; state 0 is the root,
+ * pending(s) = c * depth(s).  Creation fails with K2HIP_ERR_INVALID, the message naming the phrase, for: an empty phrase, an id
+ * out of range, blank / unk inside a phrase, a phrase that is a proper prefix of another one, duplicate phrases, and a graph
+ * over the size cap: the device form is dense (next state and bonus per (state, token)), so states * vocab_size may not exceed
+ * K2HIP_HOTWORDS_MAX_ENTRIES.
+ * Step: a hypothesis in state s that appends the real token v (blank and unk append nothing and leave s alone) moves to
+ * n = delta(s, v) (goto; on a miss the failure links; the root loops on a miss) and its log-prob gets pending(n) - pending(s)
+ * (negative when a partial match breaks).  If n ends a phrase the match is committed: the bonus stays, the new state is the root.
+ * A phrase end reachable only through a failure link from n is NOT reported (no output links) -- limitation of this version.
+ * Search: a frame's top-`beam` selection uses the unbiased sums as before; the bonus of a selected candidate is added before the
+ * candidates that spell the same sequence are merged (logaddexp of the biased scores; the merged hypothesis keeps the
+ * first-inserted one's state).  After the last frame every hypothesis loses pending(state) (an unfinished match earns nothing),
+ * then the usual length-normalised pick; scores report the finalized log-prob.
+ * A k2hip_hotwords_t belongs to no model and needs no GPU. */
+#define K2HIP_HOTWORDS_MAX_ENTRIES (1 << 23)
+/* ids: the phrases' tokens back to back, lens [n_phrases] */
+int32_t k2hip_hotwords_create(const int64_t* ids, const int32_t* lens, int32_t n_phrases, float score_per_token, int32_t vocab_size,
+                              k2hip_hotwords_t** out);
+/* a text file, one phrase per line, written as the token strings of tokens.txt separated by blanks ("▁HE LL O"; the
+ * pre-tokenised form -- no BPE encoder here); lines without a token are skipped; an unknown token string fails with the line
+ * number, and so does everything k2hip_hotwords_create refuses (vocab_size = the number of lines of tokens.txt) */
+int32_t k2hip_hotwords_load(const k2hip_tokens_t* tokens, const char* path, float score_per_token, k2hip_hotwords_t** out);
+int32_t k2hip_hotwords_destroy(k2hip_hotwords_t* hw);
+int32_t k2hip_hotwords_num_states(const k2hip_hotwords_t* hw);   /* -1 for NULL */
+/* the host walk of the definition above (for tests and for hosts that score a transcript) */
+int32_t k2hip_hotwords_step(const k2hip_hotwords_t* hw, int32_t state, int64_t token, int32_t* next_state, float* bonus);
+int32_t k2hip_hotwords_pending(const k2hip_hotwords_t* hw, int32_t state, float* pending);
+/* hw = NULL clears.  Checks vocab_size against the model, uploads the tables (the model keeps its own copy: hw may be destroyed
+ * afterwards) and keeps them until replaced or the model is destroyed; not while submitted batches are in flight.  Applies wherever
+ * the offline modified beam search runs: k2hip_beam_search and the batch entry points under
+ * k2hip_set_decoding_method("modified_beam_search") (k2hip_offline_greedy*, k2hip_offline_recognizer_get_results, submit / wait).
+ * Greedy search, the CTC search and the single-stream path ignore it.  No hotwords, or an empty list: bit for bit the unbiased
+ * results.  STREAMING is not covered: with hotwords set, k2hip_beam_search_chunk and k2hip_online_step under
+ * modified_beam_search fail with K2HIP_ERR_INVALID (streaming greedy is untouched). */
+int32_t k2hip_set_hotwords(k2hip_model_t* model, const k2hip_hotwords_t* hw);
 
 /* OfflineRecognizer.GetResults (:85-91) minus DecodeMulti: runs the fused batch
  * path on the streams' feature buffers, stores Tokens/Timestamps in each stream

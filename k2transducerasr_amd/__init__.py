@@ -12,6 +12,7 @@ from __future__ import annotations
 from . import config, k2w, synth  # noqa: F401
 from .binding import (  # noqa: F401
     BeamStream,
+    Hotwords,
     K2HipError,
     Model,
     OfflineRecognizer,
@@ -29,6 +30,7 @@ from .binding import (  # noqa: F401
 
 __all__ = [
     "BeamStream",
+    "Hotwords",
     "K2HipError",
     "Model",
     "OfflineRecognizer",

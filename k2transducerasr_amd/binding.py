@@ -192,6 +192,76 @@ class TokenTable:
             pass
 
 
+class Hotwords:
+    """The hotword graph of the offline modified beam search (k2hip_hotwords_t; include/k2hip.h "hotword biasing"): a trie of
+    token-id phrases with Aho-Corasick failure links.  Host only: built and walked without a GPU.  `phrases`: sequences of token
+    ids; `score` = the bonus per matched token.  Hotwords.load reads a pre-tokenised text file through a TokenTable."""
+
+    def _bind(self):
+        self._h = None
+        self._L = L = load_library()
+        L.k2hip_hotwords_create.argtypes = [lp, ip, C.c_int32, C.c_float, C.c_int32, C.POINTER(C.c_void_p)]
+        L.k2hip_hotwords_load.argtypes = [C.c_void_p, C.c_char_p, C.c_float, C.POINTER(C.c_void_p)]
+        L.k2hip_hotwords_destroy.argtypes = [C.c_void_p]
+        L.k2hip_hotwords_num_states.argtypes = [C.c_void_p]
+        L.k2hip_hotwords_step.argtypes = [C.c_void_p, C.c_int32, C.c_int64, ip, fp]
+        L.k2hip_hotwords_pending.argtypes = [C.c_void_p, C.c_int32, fp]
+        return L
+
+    def __init__(self, phrases, score: float, vocab_size: int):
+        L = self._bind()
+        phrases = [list(p) for p in phrases]
+        ids = np.ascontiguousarray([t for p in phrases for t in p] or [0], dtype=np.int64)
+        lens = np.ascontiguousarray([len(p) for p in phrases] or [0], dtype=np.int32)
+        h = C.c_void_p()
+        rc = L.k2hip_hotwords_create(_l(ids), _i(lens), len(phrases), float(score), int(vocab_size), C.byref(h))
+        if rc != 0:
+            raise K2HipError(rc, L.k2hip_last_error().decode())
+        self._h = h
+
+    @classmethod
+    def load(cls, tokens: "TokenTable", path: str, score: float) -> "Hotwords":
+        hw = cls.__new__(cls)
+        L = hw._bind()
+        h = C.c_void_p()
+        rc = L.k2hip_hotwords_load(tokens._h, path.encode(), float(score), C.byref(h))
+        if rc != 0:
+            raise K2HipError(rc, L.k2hip_last_error().decode())
+        hw._h = h
+        return hw
+
+    @property
+    def num_states(self) -> int:
+        return self._L.k2hip_hotwords_num_states(self._h)
+
+    def step(self, state: int, token: int):
+        """(next state, bonus) of a hypothesis in `state` that appends `token`"""
+        n, b = C.c_int32(), C.c_float()
+        rc = self._L.k2hip_hotwords_step(self._h, state, token, C.byref(n), C.byref(b))
+        if rc != 0:
+            raise K2HipError(rc, self._L.k2hip_last_error().decode())
+        return n.value, np.float32(b.value)
+
+    def pending(self, state: int):
+        """the bonus an unfinished match in `state` holds (taken back when the search ends)"""
+        b = C.c_float()
+        rc = self._L.k2hip_hotwords_pending(self._h, state, C.byref(b))
+        if rc != 0:
+            raise K2HipError(rc, self._L.k2hip_last_error().decode())
+        return np.float32(b.value)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.k2hip_hotwords_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Model:
     """One model replica on one GPU (k2hip_model_t): the IOfflineProj operators."""
 
@@ -363,6 +433,12 @@ class Model:
     def set_decoding_method(self, method: str = "greedy_search", beam: int = 4):
         """decodingMethod of the batch entry points (OfflineRecognizer.cs:54-68): greedy_search | modified_beam_search"""
         self._chk(self._L.k2hip_set_decoding_method(self._h, method.encode(), beam))
+
+    def set_hotwords(self, hotwords: Optional["Hotwords"] = None):
+        """k2hip_set_hotwords: bias the offline modified beam search towards the graph's phrases; None clears.  The model keeps its own
+        copy of the tables."""
+        self._L.k2hip_set_hotwords.argtypes = [C.c_void_p, C.c_void_p]
+        self._chk(self._L.k2hip_set_hotwords(self._h, hotwords._h if hotwords is not None else None))
 
     def gemm_profile(self) -> np.ndarray:
         """[n, 8] rows (M, N, K, batch, act, has_residual, kind, us) of the last instrumented call"""
@@ -539,11 +615,17 @@ class OfflineStream:
 
 class OfflineRecognizer:
     """OfflineRecognizer.cs:12-91 on the HIP backend; decoding_method "greedy_search" (the reference's only method) or
-    "modified_beam_search" (BASELINE.json configs[2])."""
+    "modified_beam_search" (BASELINE.json configs[2]).  hotwords: a Hotwords graph, or a list of token-id phrases scored
+    hotwords_score per matched token (sherpa's hotwords_file / hotwords_score); it biases modified_beam_search only."""
 
-    def __init__(self, weights_path: str, device: int = 0, decoding_method: str = "greedy_search", beam: int = 4):
+    def __init__(self, weights_path: str, device: int = 0, decoding_method: str = "greedy_search", beam: int = 4, hotwords=None,
+                 hotwords_score: float = 1.5):
         self.model = Model(weights_path, device)
         self.model.set_decoding_method(decoding_method, beam)
+        if hotwords is not None:
+            if not isinstance(hotwords, Hotwords):
+                hotwords = Hotwords(hotwords, hotwords_score, self.model.vocab_size)
+            self.model.set_hotwords(hotwords)
 
     def create_offline_stream(self) -> OfflineStream:  # CreateOfflineStream :71-75
         return OfflineStream(self.model)

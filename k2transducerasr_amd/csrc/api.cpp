@@ -2,6 +2,7 @@
 // OfflineStream / OfflineRecognizer bookkeeping (K2TransducerAsr/OfflineStream.cs,
 // OfflineRecognizer.cs:77-91,289-296).
 #include <algorithm>
+#include <fstream>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -10,6 +11,7 @@
 #include "text.h"
 #include "engine.h"
 #include "beam_hist.h"
+#include "hotwords.h"
 #include "../../include/k2hip_debug.h"
 
 using namespace k2hip;
@@ -75,7 +77,18 @@ struct k2hip_model {
     static constexpr size_t kPoolMax = 128;
     std::mutex wav_mu;
     std::vector<PinVec> wav_pool;   // (declared behind `engine`: released first)
+    // the hotword tables on the device (k2hip_set_hotwords): one allocation [next | bonus | pending], or null
+    void* hw_dev = nullptr;
     k2hip_model(const char* path, const char* ov, int dev) : engine(path, ov, dev) {}
+    ~k2hip_model() {
+        if (hw_dev) {
+            try {
+                engine.synchronize();
+                engine.dev_free(hw_dev);
+            } catch (...) {
+            }
+        }
+    }
 };
 
 // OfflineStream.cs:7-99
@@ -410,6 +423,119 @@ int32_t k2hip_decode_text(const k2hip_tokens_t* t, const int64_t* ids, int32_t n
         if (!out) return;
         if ((int32_t)s.size() + 1 > cap) failf(K2HIP_ERR_CAPACITY, "decode_text: text needs %zu bytes", s.size() + 1);
         memcpy(out, s.c_str(), s.size() + 1);
+    });
+}
+// ---- hotword biasing (hotwords.cpp) ----------------------------------------------------------------
+struct k2hip_hotwords {
+    k2hip::HotwordGraph graph;
+};
+int32_t k2hip_hotwords_create(const int64_t* ids, const int32_t* lens, int32_t n_phrases, float score_per_token, int32_t vocab_size,
+                              k2hip_hotwords_t** out) {
+    return guard([&] {
+        NEED(out);
+        *out = nullptr;
+        *out = new k2hip_hotwords{HotwordGraph(ids, lens, n_phrases, score_per_token, vocab_size)};
+    });
+}
+int32_t k2hip_hotwords_load(const k2hip_tokens_t* tokens, const char* path, float score_per_token, k2hip_hotwords_t** out) {
+    return guard([&] {
+        NEED(tokens); NEED(path); NEED(out);
+        *out = nullptr;
+        const int V = token_table_size(tokens->tab);
+        std::map<std::string, int> id_of;
+        for (int i = V - 1; i >= 0; i--) id_of[token_table_symbol(*tokens->tab, i)] = i;   // (a repeated symbol: its first line)
+        std::ifstream f(path, std::ios::binary);
+        if (!f) failf(K2HIP_ERR_IO, "cannot open hotwords file %s", path);
+        std::vector<int64_t> ids;
+        std::vector<int32_t> lens;
+        std::vector<int> line_of;
+        std::string line;
+        for (int ln = 1; std::getline(f, line); ln++) {
+            int n = 0;
+            size_t i = 0;
+            while (i < line.size()) {
+                while (i < line.size() && (line[i] == ' ' || line[i] == '\t' || line[i] == '\r')) i++;
+                size_t j = i;
+                while (j < line.size() && line[j] != ' ' && line[j] != '\t' && line[j] != '\r') j++;
+                if (j == i) break;
+                const std::string sym = line.substr(i, j - i);
+                auto it = id_of.find(sym);
+                if (it == id_of.end()) failf(K2HIP_ERR_INVALID, "hotwords file %s line %d: token '%s' is not in the token table", path, ln, sym.c_str());
+                ids.push_back(it->second);
+                n++;
+                i = j;
+            }
+            if (n == 0) continue;
+            lens.push_back(n);
+            line_of.push_back(ln);
+        }
+        *out = new k2hip_hotwords{HotwordGraph(ids.data(), lens.data(), (int)lens.size(), score_per_token, V, "line", line_of.data())};
+    });
+}
+int32_t k2hip_hotwords_destroy(k2hip_hotwords_t* hw) {
+    return guard([&] { delete hw; });
+}
+int32_t k2hip_hotwords_num_states(const k2hip_hotwords_t* hw) { return hw ? hw->graph.num_states() : -1; }
+int32_t k2hip_hotwords_step(const k2hip_hotwords_t* hw, int32_t state, int64_t token, int32_t* next_state, float* bonus) {
+    return guard([&] {
+        NEED(hw); NEED(next_state); NEED(bonus);
+        int n = 0;
+        hw->graph.step(state, token, &n, bonus);
+        *next_state = n;
+    });
+}
+int32_t k2hip_hotwords_pending(const k2hip_hotwords_t* hw, int32_t state, float* pending) {
+    return guard([&] {
+        NEED(hw); NEED(pending);
+        K2_REQUIRE(state >= 0 && state < hw->graph.num_states(), "hotwords: state %d outside [0, %d)", state, hw->graph.num_states());
+        *pending = hw->graph.pending(state);
+    });
+}
+int32_t k2hip_set_hotwords(k2hip_model_t* model, const k2hip_hotwords_t* hw) {
+    return guard([&] {
+        NEED(model);
+        Engine& e = model->engine;
+        const int V = e.model().cfg().V;
+        if (hw) K2_REQUIRE(hw->graph.vocab_size() == V, "set_hotwords: the graph was built for vocab_size %d, the model has %d", hw->graph.vocab_size(), V);
+        EngineLock lk(e);
+        K2_REQUIRE(e.batches_in_flight() == 0, "set_hotwords: %d submitted batches are in flight; wait for them first", e.batches_in_flight());
+        void* fresh = nullptr;
+        const int32_t* d_next = nullptr;
+        const float *d_bonus = nullptr, *d_pending = nullptr;
+        if (hw) {
+            std::vector<int32_t> next;
+            std::vector<float> bonus, pending;
+            hw->graph.dense(&next, &bonus, &pending);
+            const int64_t nb_t = (int64_t)sizeof(int32_t) * (int64_t)next.size(), nb_p = (int64_t)sizeof(float) * (int64_t)pending.size();
+            fresh = e.dev_alloc(2 * nb_t + nb_p);
+            try {
+                char* d = static_cast<char*>(fresh);
+                e.dev_upload(d, next.data(), nb_t);
+                e.dev_upload(d + nb_t, bonus.data(), nb_t);
+                e.dev_upload(d + 2 * nb_t, pending.data(), nb_p);
+                d_next = reinterpret_cast<const int32_t*>(d);
+                d_bonus = reinterpret_cast<const float*>(d + nb_t);
+                d_pending = reinterpret_cast<const float*>(d + 2 * nb_t);
+            } catch (...) {
+                try { e.dev_free(fresh); } catch (...) {}
+                throw;
+            }
+        }
+        // searches already enqueued read the old tables: let them finish before the memory goes
+        if (model->hw_dev) {
+            try {
+                e.synchronize();
+            } catch (...) {
+                if (fresh) {
+                    try { e.dev_free(fresh); } catch (...) {}
+                }
+                throw;
+            }
+        }
+        e.set_hotword_tables(d_next, d_bonus, d_pending);
+        void* old = model->hw_dev;
+        model->hw_dev = fresh;
+        if (old) e.dev_free(old);
     });
 }
 int32_t k2hip_ctc_greedy(k2hip_model_t* model, const float* log_probs, int32_t B, int32_t Tprime, const int32_t* frame_offsets,
@@ -788,6 +914,9 @@ int32_t k2hip_online_step(k2hip_model_t* model, k2hip_online_stream_t* const* st
         if (!c.ctc) {
             EngineLock lk(e);
             K = e.beam();
+            K2_REQUIRE(!(K > 0 && e.has_hotwords()),
+                       "online step: hotword biasing covers the offline modified beam search only, not the streaming one -- clear the "
+                       "hotwords (k2hip_set_hotwords(model, NULL)) or decode with greedy_search");
         }
         std::vector<int> idx;
         for (int i = 0; i < B; i++) {
@@ -1061,6 +1190,11 @@ int32_t k2hip_beam_search_chunk(k2hip_model_t* model, k2hip_beam_stream_t* const
     return guard([&] {
         NEED(model); NEED(streams); NEED(enc_out);
         K2_REQUIRE(B > 0 && Tc >= 1, "beam search chunk: bad shape B=%d Tc=%d", B, Tc);
+        {
+            EngineLock lk(model->engine);
+            K2_REQUIRE(!model->engine.has_hotwords(), "beam search chunk: hotword biasing covers the offline modified beam search only, not the "
+                                                      "streaming one -- clear the hotwords (k2hip_set_hotwords(model, NULL)) first");
+        }
         std::vector<const k2hip_beam_stream*> seen(streams, streams + B);
         for (int b = 0; b < B; b++) {
             NEED(streams[b]);

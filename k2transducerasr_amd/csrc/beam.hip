@@ -14,6 +14,10 @@
 // [blank, blank]; a hypothesis is then (saved index org, suffix ys of this chunk), its decoder context falls back to the saved
 // context while the suffix is shorter than 2, and the merge test of two candidates from different saved hypotheses goes through the
 // host's relation table.  With rin == null every one of these is the offline search's own behaviour.
+// Hotword biasing (BeamArgs::hw_*, offline only): every hypothesis carries the state of the hotword graph; the bonus of a selected
+// candidate is looked up after the frame's selection and added before the merges, the new state is written with the hypothesis, and
+// the final pick takes back the pending bonus of an unfinished match.  The kernels are templates on HW: HW = false is the unbiased
+// search, with nothing added to its code.
 #include <type_traits>
 
 #include "kernels.h"
@@ -33,6 +37,10 @@ __global__ void k_beam_init(BeamState s, int B) {
     s.n[B * s.K + i] = 0;
     s.ctx[2 * i] = K2HIP_BLANK_ID;
     s.ctx[2 * i + 1] = K2HIP_BLANK_ID;
+    if (s.st) {
+        s.st[i] = 0;
+        s.st[B * s.K + i] = 0;
+    }
     if (k == 0) s.nhyp[i / s.K] = 1;
 }
 // the saved hypotheses of every stream (resume): hypothesis k = saved hypothesis k with an empty suffix
@@ -134,10 +142,15 @@ struct HypView {
     int* org_n = nullptr;
     const int* rin = nullptr;
     int Tp = 0;
+    // hotword biasing (HW instantiations only): graph state of each hypothesis at frame t / t + 1, the tables [S][V]
+    const int* st_c = nullptr;
+    int* st_n = nullptr;
+    const int* hw_next = nullptr;
+    const float* hw_bonus = nullptr;
 };
 constexpr int kStepScratchInts = 4 * kMaxBeam + 4 + 2 * kMaxBeam * kMaxBeam;
 // one workgroup of NT threads per stream; lg: the hypotheses' logits, ldl floats per row; scratch: kStepScratchInts ints of LDS
-template <int NT>
+template <int NT, bool HW>
 __device__ void beam_step_body(const HypView& hv, const float* lg, int ldl, int V, int t, int* scratch) {
     constexpr int BT = NT;
     int* taken = scratch;
@@ -301,6 +314,13 @@ __device__ void beam_step_body(const HypView& hv, const float* lg, int ldl, int 
 #pragma unroll
         for (int r = 0; r < kMaxBeam; r++) {
             tv[r] = r < want ? topv[r] : -INFINITY;
+            if constexpr (HW) {
+                // the selected candidate's bonus (the selection itself and the tap's `val` stay unbiased): independent loads
+                if (r < want) {
+                    const int hr = topi[r] / V, tr = topi[r] % V;
+                    if (tr != K2HIP_BLANK_ID && tr != K2HIP_UNK_ID) tv[r] += hv.hw_bonus[(long long)hv.st_c[hr] * V + tr];
+                }
+            }
             lpn[r] = -INFINITY;
             eqm[r] = 0;
 #pragma unroll
@@ -352,6 +372,7 @@ __device__ void beam_step_body(const HypView& hv, const float* lg, int ldl, int 
             hv.ctx[2 * k + 1] = K2HIP_BLANK_ID;
             n_n[k] = 0;
             if (hv.org_n) hv.org_n[k] = 0;
+            if constexpr (HW) hv.st_n[k] = 0;
         }
         *hv.nhyp = nN;
         if (hv.trace) hv.trace[2 * K] = nN;
@@ -381,6 +402,7 @@ __device__ void beam_step_body(const HypView& hv, const float* lg, int ldl, int 
                 nn++;
             }
             n_n[slot] = nn;
+            if constexpr (HW) hv.st_n[slot] = realr ? hv.hw_next[(long long)hv.st_c[hr] * V + tr] : hv.st_c[hr];
             // decoder context of the new hypothesis: last two of [c0, c1] + ys, [c0, c1] = the saved hypothesis' context (resume) or
             // [blank, blank]
             long long c0 = K2HIP_BLANK_ID, c1 = K2HIP_BLANK_ID;
@@ -400,6 +422,7 @@ __device__ void beam_step_body(const HypView& hv, const float* lg, int ldl, int 
 }
 
 // one workgroup per stream; `cur` = buffer holding frame t's input hypotheses
+template <bool HW>
 __global__ __launch_bounds__(BT) void k_beam_step(BeamState s, const float* __restrict__ logits, int V, int t, int cur, int B, int* trace, int Tp) {
     __shared__ int scratch[kStepScratchInts];
     const int b = blockIdx.x, K = s.K, nxt = cur ^ 1;
@@ -422,7 +445,13 @@ __global__ __launch_bounds__(BT) void k_beam_step(BeamState s, const float* __re
         hv.rin = s.rin + (long long)b * BeamResumeLayout{K, s.Tp}.in_ints();
         hv.Tp = s.Tp;
     }
-    beam_step_body<BT>(hv, logits + (long long)b * K * V, V, V, t, scratch);
+    if constexpr (HW) {
+        hv.st_c = s.st + cur * BK + b * K;
+        hv.st_n = s.st + nxt * BK + b * K;
+        hv.hw_next = s.hw_next;
+        hv.hw_bonus = s.hw_bonus;
+    }
+    beam_step_body<BT, HW>(hv, logits + (long long)b * K * V, V, V, t, scratch);
 }
 
 // resume: every surviving hypothesis of the stream into its out block, and the best one (get_most_probable over the WHOLE
@@ -484,12 +513,13 @@ __device__ __forceinline__ void bstore_granule(unsigned long long* g, unsigned e
 __device__ __forceinline__ unsigned long long bload_granule(const unsigned long long* g) {
     return __hip_atomic_load((bgu64*)g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-// LDS (floats): actT[J GF] | psum | lg[GF][Vp] | ctx[2 GF] (long long) | lp[GF] | n[2][GF] | org[2][GF] | nhyp, pad | scratch |
-// ys[2][K][cap] | ts[2][K][cap]
-__host__ __device__ inline size_t beam_loop_lds_floats(int J, int Vp, int K, int cap, bool hyp_in_lds) {
-    return (size_t)J * GF + kPsumFloats + (size_t)GF * Vp + 4 * GF + GF + 2 * GF + 2 * GF + 4 + kStepScratchInts + 4 + (hyp_in_lds ? 4 * (size_t)K * cap : 0);
+// LDS (floats): actT[J GF] | psum | lg[GF][Vp] | ctx[2 GF] (long long) | lp[GF] | n[2][GF] | org[2][GF] | st[2][GF] (hotwords only) |
+// nhyp, pad | scratch | ys[2][K][cap] | ts[2][K][cap]
+__host__ __device__ inline size_t beam_loop_lds_floats(int J, int Vp, int K, int cap, bool hyp_in_lds, bool hw) {
+    return (size_t)J * GF + kPsumFloats + (size_t)GF * Vp + 4 * GF + GF + 2 * GF + 2 * GF + (hw ? 2 * GF : 0) + 4 + kStepScratchInts + 4 +
+           (hyp_in_lds ? 4 * (size_t)K * cap : 0);
 }
-template <int NH>   // NH = 1: beam <= 4, the sweep forms only rows 0..3
+template <int NH, bool HW>   // NH = 1: beam <= 4, the sweep forms only rows 0..3; HW: hotword biasing
 __global__ __launch_bounds__(GT) void k_beam_loop(DecJoinW w, BeamLoopArgs a) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     float* actT = sm;
@@ -499,7 +529,8 @@ __global__ __launch_bounds__(GT) void k_beam_loop(DecJoinW w, BeamLoopArgs a) {
     float* lp = reinterpret_cast<float*>(ctx + 2 * GF);
     int* nbuf = reinterpret_cast<int*>(lp + GF);       // [2][GF]
     int* orgb = nbuf + 2 * GF;                          // [2][GF] (resume)
-    int* nhyp = orgb + 2 * GF;
+    int* stb = orgb + 2 * GF;                           // [2][GF] (hotwords)
+    int* nhyp = stb + (HW ? 2 * GF : 0);
     int* scratch = nhyp + 4;
     int* ys = a.ys_g ? a.ys_g + (size_t)blockIdx.x * 2 * a.K * a.cap : scratch + kStepScratchInts + 4;
     int* ts = a.ys_g ? a.ts_g + (size_t)blockIdx.x * 2 * a.K * a.cap : ys + 2 * a.K * a.cap;
@@ -515,6 +546,10 @@ __global__ __launch_bounds__(GT) void k_beam_loop(DecJoinW w, BeamLoopArgs a) {
         nbuf[GF + tid] = 0;
         orgb[tid] = tid;
         orgb[GF + tid] = 0;
+        if constexpr (HW) {
+            stb[tid] = 0;
+            stb[GF + tid] = 0;
+        }
         if (rin) {
             const int nh = rin[0];
             const bool live = tid < nh && tid < K;
@@ -665,7 +700,13 @@ __global__ __launch_bounds__(GT) void k_beam_loop(DecJoinW w, BeamLoopArgs a) {
             hv.rin = rin;
             hv.Tp = a.Tp;
         }
-        beam_step_body<GT>(hv, lg, w.Vp, w.V, t, scratch);
+        if constexpr (HW) {
+            hv.st_c = stb + cur * GF;
+            hv.st_n = stb + (cur ^ 1) * GF;
+            hv.hw_next = a.hw_next;
+            hv.hw_bonus = a.hw_bonus;
+        }
+        beam_step_body<GT, HW>(hv, lg, w.Vp, w.V, t, scratch);
         __syncthreads();
     }
     // k_beam_final: max of log_prob / len(ys) (len counts the 2 ctx blanks), first maximum
@@ -676,10 +717,16 @@ __global__ __launch_bounds__(GT) void k_beam_loop(DecJoinW w, BeamLoopArgs a) {
                           ys + (size_t)fin * K * a.cap, ts + (size_t)fin * K * a.cap);
         return;
     }
+    // (hotwords: an unfinished match earns nothing -- every hypothesis' log-prob loses its state's pending bonus first)
+    const int* st_f = stb + fin * GF;
+    auto final_lp = [&](int k) {
+        if constexpr (HW) return lp[k] - a.hw_pending[st_f[k]];
+        else return lp[k];
+    };
     int best = 0;
-    float bs = lp[0] / (float)(n_f[0] + 2);
+    float bs = final_lp(0) / (float)(n_f[0] + 2);
     for (int k = 1; k < *nhyp; k++) {
-        const float v = lp[k] / (float)(n_f[k] + 2);
+        const float v = final_lp(k) / (float)(n_f[k] + 2);
         if (v > bs) { bs = v; best = k; }
     }
     const int n = n_f[best];
@@ -696,20 +743,26 @@ __global__ __launch_bounds__(GT) void k_beam_loop(DecJoinW w, BeamLoopArgs a) {
     }
     if (tid == 0) {
         a.n_tokens[b] = n;
-        if (a.scores) a.scores[b] = lp[best];
+        if (a.scores) a.scores[b] = final_lp(best);
     }
 }
 
 // get_most_probable(length_norm=True): max of log_prob / len(ys) (len counts the 2 ctx blanks), first maximum
+template <bool HW>
 __global__ void k_beam_final(BeamState s, int fin, int B, long long* __restrict__ tokens, int* __restrict__ timestamps,
                              int* __restrict__ n_tokens, float* __restrict__ scores, int max_tokens, int* __restrict__ overflow) {
     const int b = blockIdx.x, K = s.K;
     const long long BK = (long long)B * K;
     const int* n_f = s.n + fin * BK + b * K;
+    // (hotwords: every hypothesis' log-prob loses its state's pending bonus first)
+    auto final_lp = [&](int k) {
+        if constexpr (HW) return s.lp[b * K + k] - s.hw_pending[s.st[fin * BK + b * K + k]];
+        else return s.lp[b * K + k];
+    };
     int best = 0;
-    float bs = s.lp[b * K] / (float)(n_f[0] + 2);
+    float bs = final_lp(0) / (float)(n_f[0] + 2);
     for (int k = 1; k < s.nhyp[b]; k++) {
-        float v = s.lp[b * K + k] / (float)(n_f[k] + 2);
+        float v = final_lp(k) / (float)(n_f[k] + 2);
         if (v > bs) { bs = v; best = k; }
     }
     const int n = n_f[best];
@@ -725,7 +778,7 @@ __global__ void k_beam_final(BeamState s, int fin, int B, long long* __restrict_
     }
     if (threadIdx.x == 0) {
         n_tokens[b] = n;
-        if (scores) scores[b] = s.lp[b * K + best];
+        if (scores) scores[b] = final_lp(best);
     }
 }
 
@@ -734,13 +787,16 @@ __global__ void k_beam_final(BeamState s, int fin, int B, long long* __restrict_
 void beam_search(const Ctx& ctx, const DecJoinW& w, const BeamArgs& a) {
     K2_REQUIRE(a.beam >= 1 && a.beam <= kMaxBeam, "beam search: beam %d out of range [1,%d]", a.beam, kMaxBeam);
     K2_REQUIRE(a.B > 0 && a.Tp > 0, "beam search: bad shape");
+    const bool hw = a.hw_next != nullptr;
+    K2_REQUIRE(!hw || (a.hw_bonus && a.hw_pending), "beam search: incomplete hotword tables");
+    K2_REQUIRE(!(hw && a.rin), "beam search: hotword biasing does not cover the streaming (resumed) search");
     Arena& ar = *ctx.arena;
     const int B = a.B, K = a.beam, M = B * K, cap = a.Tp + 1;
     {
         // the one-kernel form: needs the decoder table (small vocabulary) and the stream's logits and hypotheses in LDS
         // hypotheses in LDS when they fit beside the logits (T' <= ~600 at beam 4 with the large-en shapes), else in device memory
-        const bool hyp_in_lds = sizeof(float) * beam_loop_lds_floats(w.J, w.Vp, K, cap, true) <= 150 * 1024 && !tunables().beam_hyp_global;
-        const size_t lds = sizeof(float) * beam_loop_lds_floats(w.J, w.Vp, K, cap, hyp_in_lds);
+        const bool hyp_in_lds = sizeof(float) * beam_loop_lds_floats(w.J, w.Vp, K, cap, true, hw) <= 150 * 1024 && !tunables().beam_hyp_global;
+        const size_t lds = sizeof(float) * beam_loop_lds_floats(w.J, w.Vp, K, cap, hyp_in_lds, hw);
         if (w.dec_table && !tunables().beam_launches && lds <= 150 * 1024 && w.J % 8 == 0 && w.Vp % 4 == 0 && K <= GF) {
             // Two column slabs per stream where one workgroup would sweep two chunks (beam <= 4, 256 < V <= 512) and 2 B workgroups fit
             // the offline co-residency budget: the frame's sweep is bound by ONE CU's fetch of the 1 MB matrix, two CUs halve it, and the
@@ -760,14 +816,22 @@ void beam_search(const Ctx& ctx, const DecJoinW& w, const BeamArgs& a) {
             la.xg = xg;
             la.trace = a.trace;
             la.rin = a.rin; la.rout = a.rout;
+            la.hw_next = a.hw_next; la.hw_bonus = a.hw_bonus; la.hw_pending = a.hw_pending;
             K2_HIP(hipMemsetAsync(a.overflow, 0, sizeof(int), ctx.stream));
-            static LdsAttrOnce lds_attr;
-            static LdsAttrOnce lds_attr1;
-            lds_attr.ensure(k_beam_loop<2>, 150 * 1024);
-            lds_attr1.ensure(k_beam_loop<1>, 150 * 1024);
+            static LdsAttrOnce lds_attr, lds_attr1, lds_attr_hw, lds_attr1_hw;
+            if (hw) {
+                lds_attr_hw.ensure(k_beam_loop<2, true>, 150 * 1024);
+                lds_attr1_hw.ensure(k_beam_loop<1, true>, 150 * 1024);
+            } else {
+                lds_attr.ensure(k_beam_loop<2, false>, 150 * 1024);
+                lds_attr1.ensure(k_beam_loop<1, false>, 150 * 1024);
+            }
             if (two) K2_HIP(hipMemsetAsync(xg, 0, sizeof(unsigned long long) * (size_t)B * 2 * 2 * 4 * 256, ctx.stream));
-            if (K <= 4) hipLaunchKernelGGL(k_beam_loop<1>, dim3(two ? 2 * B : B), dim3(GT), lds, ctx.stream, w, la);
-            else hipLaunchKernelGGL(k_beam_loop<2>, dim3(B), dim3(GT), lds, ctx.stream, w, la);
+            const dim3 grid1(two ? 2 * B : B);
+            if (K <= 4 && hw) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_beam_loop<1, true>), grid1, dim3(GT), lds, ctx.stream, w, la);
+            else if (K <= 4) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_beam_loop<1, false>), grid1, dim3(GT), lds, ctx.stream, w, la);
+            else if (hw) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_beam_loop<2, true>), dim3(B), dim3(GT), lds, ctx.stream, w, la);
+            else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_beam_loop<2, false>), dim3(B), dim3(GT), lds, ctx.stream, w, la);
             K2_HIP(hipGetLastError());
             if (ctx.greedy_rec) {
                 ctx.greedy_rec->valid = two;
@@ -800,6 +864,10 @@ void beam_search(const Ctx& ctx, const DecJoinW& w, const BeamArgs& a) {
         s.rin = a.rin;
         s.Tp = a.Tp;
     }
+    if (hw) {
+        s.st = ar.take<int>((int64_t)2 * M);
+        s.hw_next = a.hw_next; s.hw_bonus = a.hw_bonus; s.hw_pending = a.hw_pending;
+    }
     float* hbuf = ar.take<float>((int64_t)M * w.DD);
     float* act = ar.take<float>((int64_t)M * w.J);
     float* logits = ar.take<float>((int64_t)M * w.V);
@@ -823,13 +891,16 @@ void beam_search(const Ctx& ctx, const DecJoinW& w, const BeamArgs& a) {
         }
         linear(ctx, act, w.J, a.out_w, w.out_b, logits, w.V, M, w.J, w.V);
         if (!ctx.dry) {
-            hipLaunchKernelGGL(k_beam_step, dim3(B), dim3(BT), 0, ctx.stream, s, logits, w.V, t, t & 1, B, a.trace, a.Tp);
+            if (hw) hipLaunchKernelGGL(k_beam_step<true>, dim3(B), dim3(BT), 0, ctx.stream, s, logits, w.V, t, t & 1, B, a.trace, a.Tp);
+            else hipLaunchKernelGGL(k_beam_step<false>, dim3(B), dim3(BT), 0, ctx.stream, s, logits, w.V, t, t & 1, B, a.trace, a.Tp);
             K2_HIP(hipGetLastError());
         }
     }
     if (!ctx.dry) {
         if (a.rin) hipLaunchKernelGGL(k_beam_resume_final, dim3(B), dim3(256), 0, ctx.stream, s, a.Tp & 1, B, a.rout);
-        else hipLaunchKernelGGL(k_beam_final, dim3(B), dim3(256), 0, ctx.stream, s, a.Tp & 1, B, a.tokens, a.timestamps, a.n_tokens, a.scores,
+        else if (hw) hipLaunchKernelGGL(k_beam_final<true>, dim3(B), dim3(256), 0, ctx.stream, s, a.Tp & 1, B, a.tokens, a.timestamps, a.n_tokens,
+                                        a.scores, a.max_tokens, a.overflow);
+        else hipLaunchKernelGGL(k_beam_final<false>, dim3(B), dim3(256), 0, ctx.stream, s, a.Tp & 1, B, a.tokens, a.timestamps, a.n_tokens, a.scores,
                                 a.max_tokens, a.overflow);
         K2_HIP(hipGetLastError());
     }
@@ -846,7 +917,9 @@ void beam_relaunch_one_slab(hipStream_t stream, const GreedyLaunch& rec) {
         K2_HIP(hipMemsetAsync(la.n_tokens, 0xEE, sizeof(int) * (size_t)rec.a.B, stream));
         if (la.scores) K2_HIP(hipMemsetAsync(la.scores, 0xEE, sizeof(float) * (size_t)rec.a.B, stream));
     }
-    hipLaunchKernelGGL(k_beam_loop<1>, dim3(rec.a.B), dim3(GT), rec.beam_lds, stream, rec.w, la);
+    // (la carries the hotword tables of the first launch; its LDS size was computed with them)
+    if (la.hw_next) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_beam_loop<1, true>), dim3(rec.a.B), dim3(GT), rec.beam_lds, stream, rec.w, la);
+    else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_beam_loop<1, false>), dim3(rec.a.B), dim3(GT), rec.beam_lds, stream, rec.w, la);
     K2_HIP(hipGetLastError());
 }
 

@@ -706,6 +706,7 @@ void Engine::beam_device(const Ctx& c, const float* enc, int B, int Tp, long lon
     a.tokens = d_tok; a.timestamps = d_ts; a.n_tokens = d_n; a.max_tokens = max_tokens; a.overflow = d_overflow;
     d_scores_ = c.arena->take<float>(B);
     a.scores = d_scores_;
+    a.hw_next = hw_next_; a.hw_bonus = hw_bonus_; a.hw_pending = hw_pending_;
     if (tunables().beam_trace) {
         d_beam_trace_ = c.arena->take<int>((int64_t)B * Tp * (2 * beam_ + 1));
         a.trace = d_beam_trace_;

@@ -132,6 +132,17 @@ class Engine {
         return last_beam_trace_;
     }
     const k2hip_timing& timing() const { return timing_; }
+    // hotword tables of the offline modified beam search (BeamArgs::hw_*): device memory owned by the caller (api.cpp
+    // k2hip_set_hotwords, which allocates, uploads and frees it through dev_alloc / dev_upload / dev_free); null = none
+    void set_hotword_tables(const int* next, const float* bonus, const float* pending) {
+        hw_next_ = next; hw_bonus_ = bonus; hw_pending_ = pending;
+    }
+    bool has_hotwords() const { return hw_next_ != nullptr; }
+    int batches_in_flight() const {
+        int n = 0;
+        for (const auto& sl : slots_) n += sl.busy;
+        return n;
+    }
 
     float debug_gemm(int M, int N, int K, int act, bool with_res, int iters, int cfg, float* max_err);
     // test hook: ONE launch of configuration `cfg` (-1 = the dispatcher's own choice) on the caller's operands, result back to the host --
@@ -258,6 +269,8 @@ class Engine {
     std::map<int, float*> pe_cache_;
     bool instrument_ = false;
     int beam_ = 0;
+    const int* hw_next_ = nullptr;
+    const float *hw_bonus_ = nullptr, *hw_pending_ = nullptr;
     // CTC search by-products of the last synchronous call (NumTrailingBlank bookkeeping, OfflineRecognizer.cs:392-397)
     int *d_trail_ = nullptr, *d_any_ = nullptr;
     std::vector<int> last_trail_, last_any_;

@@ -493,6 +493,10 @@ struct BeamLoopArgs {
     // streaming resume (BeamResume below): per-stream in / out blocks, or null for the offline search
     const int* rin = nullptr;
     int* rout = nullptr;
+    // hotword biasing (HotwordTables below; offline search only) or null pointers
+    const int* hw_next = nullptr;
+    const float* hw_bonus = nullptr;
+    const float* hw_pending = nullptr;
 };
 struct GreedyLaunch {
     bool valid = false;  // a launch with inter-workgroup waits (parts > 1 / two beam slabs) that can be repeated without them
@@ -547,6 +551,11 @@ struct BeamState {       // device arrays; hypotheses double-buffered by frame p
     float *lp, *lp_next; // [B][K] hypothesis log-probs (-inf = empty slot)
     long long *ctx, *ctx_next;  // [B][K][2] decoder inputs
     int *nhyp, *nhyp_next;      // [B]
+    // hotword biasing (offline search only): the hypotheses' graph states [2][B][K] and the tables, or null
+    int* st = nullptr;
+    const int* hw_next = nullptr;
+    const float* hw_bonus = nullptr;
+    const float* hw_pending = nullptr;
 };
 struct BeamArgs {
     const float* enc;    // [B, Tp, J]
@@ -564,6 +573,14 @@ struct BeamArgs {
     // every surviving hypothesis to rout [B][out_ints] instead of the best one to tokens / timestamps / n_tokens / scores
     const int* rin = nullptr;
     int* rout = nullptr;
+    // Hotword biasing (hotwords.h; semantics in include/k2hip.h), offline search only: the dense tables of the graph on the device --
+    // hw_next [S][V] the state after appending a token (the root after a committed match), hw_bonus [S][V] what the step adds to the
+    // hypothesis' log-prob, hw_pending [S] what the final pick takes back from an unfinished match.  Every hypothesis carries its
+    // state; the bonus of a selected candidate is added after the frame's selection and before the merges.  Null: the unbiased search
+    // (its own template instantiations of the kernels: today's arithmetic, nothing added).
+    const int* hw_next = nullptr;
+    const float* hw_bonus = nullptr;
+    const float* hw_pending = nullptr;
 };
 void beam_search(const Ctx& ctx, const DecJoinW& w, const BeamArgs& a);
 

@@ -260,6 +260,10 @@ TokenTable* token_table_load(const char* path) {
 }
 void token_table_free(TokenTable* t) { delete t; }
 int token_table_size(const TokenTable* t) { return (int)t->lines.size(); }
+std::string token_table_symbol(const TokenTable& t, int id) {
+    const std::string& line = t.lines[(size_t)id];
+    return line.substr(0, line.find(' '));
+}
 
 // DecodeMulti for one stream; online = OnlineRecognizer's variant (no special case for id -1)
 std::string decode_tokens(const TokenTable& tab, const int64_t* ids, int n, bool online) {
