@@ -56,7 +56,7 @@ int32_t k2hip_debug_gemm_run(k2hip_model_t* model, const float* A, const float* 
 /* ONE launch of the launcher named `op` (csrc/kernels.h: attn_scores_softmax, attn_av_out, attn_av_out_ring, attn_proj_av_out_ring,
  * nonlin_av_out_ring, attn_stream_ring, attn_stream, glu_causal_conv, biasnorm, bypass, biasnorm_bypass, biasnorm_bypass_downsample,
  * downsample, downsample_full, upsample_combine, upsample_combine_downsample, glu_dwconv1d_swoosh, glu_dwconv1d_dswish, dwconv1d_swoosh,
- * dwconv7x7) on host operands, on the engine's stream.  iargs: the launcher's integer arguments in its own order (a RingRef counts as
+ * dwconv7x7; gemm and gemm_glu_causal_conv: see below) on host operands, on the engine's stream.  iargs: the launcher's integer arguments in its own order (a RingRef counts as
  * slot_stride, off; downsample_full's segments put n, ld[n], col1[n], lz_Td, lz_ds, lz_Do in front).  bufs / buf_bytes: its pointer
  * arguments in order (a RingRef as pool, slots, chunks; the segments as src[n], lz_orig, lz_xd, lz_scale), each uploaded whole -- in
  * place operands (x of attn_av_out, the state pool, int arrays) work as they are; NULL or 0 bytes passes a null pointer.  Every buffer
@@ -64,7 +64,22 @@ int32_t k2hip_debug_gemm_run(k2hip_model_t* model, const float* A, const float* 
  * changed fails the call (K2HIP_ERR_INVALID, naming the buffer).  After the launch the buffers flagged in out_mask (bit k = bufs[k]) are
  * downloaded.  A shape the launcher refuses returns K2HIP_ERR_UNSUPPORTED with nothing launched and nothing downloaded.  Branch
  * switches (K2HIP_ATTN_LONG, K2HIP_DW1D_TT, K2HIP_DW7_TILED) go through k2hip_debug_set_switch.  tests/test_kernels_gpu.py compares each
- * kernel with a float64 reference computed on the host. */
+ * kernel with a float64 reference computed on the host.
+ * Two more ops launch the GEMM in every form GemmArgs (csrc/kernels.h) can say (tests/test_gemm_forms_gpu.py):
+ *   "gemm": ONE gemm() call.  iargs: GemmArgs' integer and stride fields in their declared order -- M, N, K, lda, ldw, ldc, ldr, act,
+ *     act_cols, w_kn, nb0, nb1, sA0, sA1, sW0, sW1, sC0, sC1, sR0, sR1, sBias0, cv_Fout, cv_Tout, cv_Tin, cv_Fin, cv_C, cv_st, cv_sf,
+ *     seg_len, seg_stride, res_div, act_after_res, glu, glu_cols, ldm, sM0, sM1, ld_orig (not the tuning fields xcd_panels, dbg, ablate,
+ *     and not cf_*: the next op) -- then the cfg force code as k2hip_debug_gemm_run takes it (-1: the dispatcher's choice), res_is_C
+ *     (1: the residual is C's own device buffer, the in-place form; no res buffer then), and the offsets in floats of the A, W, res,
+ *     C, mul and byp_orig pointers inside their buffers.  bufs: A, W, bias, res, C, skip_if_zero (one int32), mul, byp_orig,
+ *     byp_scale, each optional but A, W and C, then a buffer of 5 int32 the hook itself fills with plan_gemm()'s choice for the call:
+ *     family (0 register-staged, 1 LDS-DMA, 2 pipe, 3 p16, 4 ring, 5 / 6 / 7 skinny<3> / <6> / <6, 8>), table index, BM, BN, and the
+ *     register-staged kernel's addressing mode (0 plain, 1 conv gather, 2 [K,N]).  The hook checks no extent: the caller sizes the
+ *     buffers for the addresses its arguments describe.  A K2_REQUIRE of gemm() or a forced plan that does not fit the call is
+ *     K2HIP_ERR_UNSUPPORTED.
+ *   "gemm_glu_causal_conv": the launcher's arguments in its own order (x, wg, bg, pool, slot_stride, off, slots, wc, bc, ww, bw, sc,
+ *     y, B, Tc, D, K), then a buffer of 1 int32 that the hook fills with glu_conv_ring_entry(B, Tc, D, K) (-1: no fused form, and the
+ *     call is K2HIP_ERR_UNSUPPORTED with nothing launched). */
 int32_t k2hip_debug_op_run(k2hip_model_t* model, const char* op, const int64_t* iargs, int32_t n_iargs, void* const* bufs,
                            const int64_t* buf_bytes, int32_t n_bufs, uint32_t out_mask);
 

@@ -1665,6 +1665,52 @@ void Engine::debug_op_host(const char* op, const int64_t* iargs, int n_iargs, vo
             float *wc = P(), *bc = P(), *ww = P(), *bw = P(), *sc = P(), *y = P();
             const int B = I(), Tc = I(), D = I(), K = I();
             glu_causal_conv(c, x2, pool, ss, off, slots, wc, bc, ww, bw, sc, y, B, Tc, D, K);
+        } else if (name == "gemm") {
+            // every int / stride field of GemmArgs in its declared order (no tuning fields, no cf_*: that form is the next op), the cfg
+            // force code, res_is_C, then the float offsets of A, W, res, C, mul, byp_orig inside their buffers
+            GemmArgs g;
+            g.M = I(); g.N = I(); g.K = I();
+            g.lda = I(); g.ldw = I(); g.ldc = I(); g.ldr = I();
+            g.act = I(); g.act_cols = I(); g.w_kn = I();
+            g.nb0 = I(); g.nb1 = I();
+            g.sA0 = L(); g.sA1 = L(); g.sW0 = L(); g.sW1 = L(); g.sC0 = L(); g.sC1 = L(); g.sR0 = L(); g.sR1 = L();
+            g.sBias0 = L();
+            g.cv_Fout = I(); g.cv_Tout = I(); g.cv_Tin = I(); g.cv_Fin = I(); g.cv_C = I(); g.cv_st = I(); g.cv_sf = I();
+            g.seg_len = I(); g.seg_stride = I();
+            g.res_div = I(); g.act_after_res = I();
+            g.glu = I(); g.glu_cols = I();
+            g.ldm = I(); g.sM0 = L(); g.sM1 = L();
+            g.ld_orig = I();
+            const int cfg = I(), res_is_C = I();
+            const long long oA = L(), oW = L(), oR = L(), oC = L(), oM = L(), oO = L();
+            float *A = P(), *W = P(), *bias = P(), *res = P(), *C = P();
+            const int* skip = reinterpret_cast<const int*>(P());
+            float *mul = P(), *orig = P(), *scale = P();
+            int* plan_out = reinterpret_cast<int*>(P());
+            K2_REQUIRE(A && W && C && plan_out && buf_bytes[n_bufs - 1] >= 20, "debug_op_run gemm: A, W, C and a plan buffer of 5 ints are needed");
+            K2_REQUIRE(!(res_is_C && res), "debug_op_run gemm: res_is_C takes no res buffer");
+            K2_REQUIRE(oA >= 0 && oW >= 0 && oR >= 0 && oC >= 0 && oM >= 0 && oO >= 0, "debug_op_run gemm: negative offset");
+            if (res_is_C) res = C;
+            g.A = A + oA; g.W = W + oW; g.bias = bias; g.res = res ? res + oR : nullptr; g.C = C + oC;
+            g.skip_if_zero = skip;
+            g.mul = mul ? mul + oM : nullptr;
+            g.byp_orig = orig ? orig + oO : nullptr; g.byp_scale = scale;
+            GemmForceGuard force(cfg);
+            const GemmPlan pl = plan_gemm(g, gemm_force());
+            const int rep[5] = {(int)pl.family, pl.idx, pl.BM, pl.BN, pl.mode};
+            K2_HIP(copy_blocking(plan_out, rep, sizeof rep, hipMemcpyHostToDevice));
+            gemm(c, g);
+        } else if (name == "gemm_glu_causal_conv") {
+            float *x = P(), *wg = P(), *bg = P(), *pool = P();
+            const long long ss = L(), off = L();
+            const int* slots = reinterpret_cast<const int*>(P());
+            float *wc = P(), *bc = P(), *ww = P(), *bw = P(), *sc = P(), *y = P();
+            const int B = I(), Tc = I(), D = I(), K = I();
+            int* entry_out = reinterpret_cast<int*>(P());
+            K2_REQUIRE(entry_out && buf_bytes[n_bufs - 1] >= 4, "debug_op_run gemm_glu_causal_conv: an entry buffer of 1 int is needed");
+            const int entry = glu_conv_ring_entry(B, Tc, D, K);
+            K2_HIP(copy_blocking(entry_out, &entry, sizeof entry, hipMemcpyHostToDevice));
+            took = gemm_glu_causal_conv(c, x, wg, bg, pool, ss, off, slots, wc, bc, ww, bw, sc, y, B, Tc, D, K);
         } else if (name == "biasnorm") {
             float *x = P(), *bias = P(), *ls = P(), *y = P();
             const int M = I(), D = I();

@@ -267,7 +267,7 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN)) void gemm_f32_mfma(Gemm
     const int z = blockIdx.z;
     const int z0 = z % g.nb0, z1 = z / g.nb0;
     const float* __restrict__ A = g.A + z0 * g.sA0 + z1 * g.sA1;
-    const float* __restrict__ W = g.W + (MODE == MODE_WKN && g.wz_map ? (long long)g.wz_map[z0] : (long long)z0) * g.sW0 + z1 * g.sW1;
+    const float* __restrict__ W = g.W + z0 * g.sW0 + z1 * g.sW1;
     float* __restrict__ C = g.C + z0 * g.sC0 + z1 * g.sC1;
     const float* __restrict__ R = g.res ? g.res + z0 * g.sR0 + z1 * g.sR1 : nullptr;
 
@@ -1714,7 +1714,6 @@ void launch_ring_conv_entry(const Ctx& ctx, const GemmArgs& a) {
 
 void gemm(const Ctx& ctx, const GemmArgs& a) {
     K2_REQUIRE(a.M > 0 && a.N > 0 && a.K > 0, "gemm: empty shape %dx%dx%d", a.M, a.N, a.K);
-    K2_REQUIRE(!a.wz_map || a.w_kn, "gemm: wz_map is for the [K,N] operand form");
     K2_REQUIRE(!a.glu || ((a.glu_cols > 0 ? a.glu_cols : a.N) % 32 == 0 && a.glu_cols <= a.N && a.N > 96 && !a.res && !a.mul && !a.byp_orig &&
                           a.act == ACT_NONE && a.nb0 * a.nb1 == 1),
                "gemm: the gated epilogue needs its paired columns in whole blocks of 32, N > 96 and no other epilogue term");

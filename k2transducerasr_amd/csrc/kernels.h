@@ -121,7 +121,6 @@ struct GemmArgs {
     int nb0 = 1, nb1 = 1;
     // device flag: the launch does nothing when *skip_if_zero == 0 (rounds of the batched search after every stream has finished)
     const int* skip_if_zero = nullptr;
-    const int* wz_map = nullptr;  // [K,N] form only: batch z0 reads W + wz_map[z0] * sW0 (stream slots of the state pool)
     long long sA0 = 0, sA1 = 0, sW0 = 0, sW1 = 0, sC0 = 0, sC1 = 0, sR0 = 0, sR1 = 0;
     long long sBias0 = 0;  // bias + z0 * sBias0 (batched launches over layers, each with its own bias)
     // implicit-conv gather of A over an NHWC tensor [B, Tin, Fin, C]:

@@ -505,21 +505,17 @@ def test_nonlin_av_out_ring(op):
     assert ran == 24
 
 
-def glu_causal_conv_case(op, rng, K, Tc, D=100, B=3):
-    """online.hip:253-312 (k_glu_causal_conv, k_glu_causal_conv_reg); oracle: k2_oracle_online.c:349-396 (online_conv_module)"""
+def glu_causal_conv_ref(x2, cache0, wc, bc, ww, bw, sc, B, Tc, D, K, x2tol=0.0):
+    """online.hip:253-312 (k_glu_causal_conv, k_glu_causal_conv_reg); oracle: k2_oracle_online.c:349-396 (online_conv_module).
+    x2 [B Tc, 2 D] = (value | gate) halves (x2tol: the bound of their own error, 0 when they are operands), cache0 [B, D, K / 2]:
+    y = SwooshR(chunk-causal depthwise conv(GLU(x2))) as float64 with its tolerance, and the advanced caches [B, D, K / 2]"""
     pad, Kc = K // 2, (K + 1) // 2
-    rg = Ring(rng, B, 1, 1, D * pad, [0] * B)    # one "row": the stream's [D][pad] cache, replaced whole
-    x2 = uni(rng, B * Tc, 2 * D, scale=2.0)
-    wc, bc, ww, bw = uni(rng, D, Kc, scale=0.4), uni(rng, D), uni(rng, D, K, scale=0.3), uni(rng, D)
-    sc = uni(rng, 2, D, K, scale=0.5)
-    y = nan(B * Tc, D)
-    cache0 = np.stack([f64(rg.ring(rg.pool, b)).reshape(D, pad) for b in range(B)])  # [B, D, pad]
-    op("glu_causal_conv", [*rg.ints(), B, Tc, D, K], [x2, rg.pool, rg.slots, wc, bc, ww, bw, sc, y], {1, 8})
     a = f64(x2).reshape(B, Tc, 2 * D)
+    atol = np.broadcast_to(f64(x2tol), (B * Tc, 2 * D)).reshape(B, Tc, 2 * D)
     gate = a[..., D:]
     g = a[..., :D] * sigmoid64(gate)                                      # [B, Tc, D]
-    gtol = np.abs(g) * (np.abs(gate) + 8) * U
-    cat = np.concatenate([cache0.transpose(0, 2, 1), g], axis=1)          # [B, pad + Tc, D]
+    gtol = np.abs(g) * (np.abs(gate) + 8) * U + atol[..., :D] + 0.25 * np.abs(a[..., :D]) * atol[..., D:]
+    cat = np.concatenate([f64(cache0).transpose(0, 2, 1), g], axis=1)     # [B, pad + Tc, D]
     cmag = np.abs(cat)
     xc = np.broadcast_to(f64(bc), (B, Tc, D)).copy()
     xcm = np.abs(xc)
@@ -545,10 +541,24 @@ def glu_causal_conv_case(op, rng, K, Tc, D=100, B=3):
     z = xw * scale + xc
     ztol = (sum_tol(xwm * np.abs(scale) + xcm, K + Kc + 2)
             + gtol.max() * np.sqrt((f64(ww) ** 2).sum(1) * scale ** 2 + (f64(wc) ** 2).sum(1)))
-    what = f"glu_causal_conv K={K} Tc={Tc} D={D}"
-    check(y, swoosh_r64(z).reshape(B * Tc, D), act_tol(z, ztol).reshape(B * Tc, D), what)
     # the cache advances to the last pad frames of [cache ; chunk]
-    newcache = cat[:, Tc:Tc + pad].transpose(0, 2, 1).reshape(B, 1, D * pad)
+    newcache = cat[:, Tc:Tc + pad].transpose(0, 2, 1)
+    return swoosh_r64(z).reshape(B * Tc, D), act_tol(z, ztol).reshape(B * Tc, D), newcache
+
+
+def glu_causal_conv_case(op, rng, K, Tc, D=100, B=3):
+    pad, Kc = K // 2, (K + 1) // 2
+    rg = Ring(rng, B, 1, 1, D * pad, [0] * B)    # one "row": the stream's [D][pad] cache, replaced whole
+    x2 = uni(rng, B * Tc, 2 * D, scale=2.0)
+    wc, bc, ww, bw = uni(rng, D, Kc, scale=0.4), uni(rng, D), uni(rng, D, K, scale=0.3), uni(rng, D)
+    sc = uni(rng, 2, D, K, scale=0.5)
+    y = nan(B * Tc, D)
+    cache0 = np.stack([f64(rg.ring(rg.pool, b)).reshape(D, pad) for b in range(B)])  # [B, D, pad]
+    op("glu_causal_conv", [*rg.ints(), B, Tc, D, K], [x2, rg.pool, rg.slots, wc, bc, ww, bw, sc, y], {1, 8})
+    want, tol, newcache = glu_causal_conv_ref(x2, cache0, wc, bc, ww, bw, sc, B, Tc, D, K)
+    what = f"glu_causal_conv K={K} Tc={Tc} D={D}"
+    check(y, want, tol, what)
+    newcache = newcache.reshape(B, 1, D * pad)
     want_pool, _ = rg.after(newcache)
     rg.check_pool(rg.pool, want_pool, np.abs(newcache).max() * 16 * U + 1e-7, "cache " + what)
 
