@@ -84,6 +84,9 @@ namespace K2TransducerAsr.Hip
         [DllImport(Lib)] internal static extern int k2hip_hotwords_step(IntPtr hotwords, int state, long token, out int nextState, out float bonus);
         [DllImport(Lib)] internal static extern int k2hip_hotwords_pending(IntPtr hotwords, int state, out float pending);
         [DllImport(Lib)] internal static extern int k2hip_set_hotwords(IntPtr model, IntPtr hotwords /* IntPtr.Zero clears */);
+        // streaming: the graph belongs to the stream (IntPtr.Zero detaches; only before the stream's first chunk or after a reset)
+        [DllImport(Lib)] internal static extern int k2hip_online_stream_set_hotwords(IntPtr stream, IntPtr hotwords);
+        [DllImport(Lib)] internal static extern int k2hip_beam_stream_set_hotwords(IntPtr stream, IntPtr hotwords);
 
         // Which GPU?  The reference's constructors (OfflineRecognizer.cs:27-28, OnlineRecognizer.cs:18-19) take file paths and nothing
         // else, and they stay as they are: the device rides on the paths.

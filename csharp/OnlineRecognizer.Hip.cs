@@ -79,6 +79,22 @@ namespace K2TransducerAsr
             return fin != 0;
         }
 
+        // This stream's hotword list under modified_beam_search (k2hip.h "hotword biasing", STREAMING): token-id phrases, back to
+        // back in `ids` with `lens` tokens each; null detaches.  Only before the stream's first decoded chunk.  The native stream
+        // keeps its own reference to the uploaded tables, so the graph is destroyed here at once.
+        public void SetHotwords(long[] ids, int[] lens, float scorePerToken, int vocabSize)
+        {
+            if (HipStream == IntPtr.Zero) throw new InvalidOperationException("SetHotwords: not a libk2hip stream");
+            if (ids == null || lens == null)
+            {
+                K2Hip.Check(K2Hip.k2hip_online_stream_set_hotwords(HipStream, IntPtr.Zero), "SetHotwords failed");
+                return;
+            }
+            K2Hip.Check(K2Hip.k2hip_hotwords_create(ids, lens, lens.Length, scorePerToken, vocabSize, out IntPtr graph), "SetHotwords: bad phrase list");
+            try { K2Hip.Check(K2Hip.k2hip_online_stream_set_hotwords(HipStream, graph), "SetHotwords failed"); }
+            finally { K2Hip.k2hip_hotwords_destroy(graph); }
+        }
+
         // Dispose(bool) (:162-190) calls this first
         internal void DisposeHip()
         {

@@ -290,7 +290,9 @@ int32_t k2hip_offline_stream_get_ctc_state(const k2hip_offline_stream_t* s, int3
  * The best hypothesis can revise earlier tokens: n_new_tokens is the SIGNED change of its length, and a host re-reads Tokens
  * after every step instead of appending.  A stream keeps the method and beam it decoded its first chunk with: after a change of
  * the setting, k2hip_online_step fails with K2HIP_ERR_INVALID for it until k2hip_online_stream_reset (which clears the
- * hypotheses). */
+ * hypotheses).  With a hotword graph attached to the stream (k2hip_online_stream_set_hotwords, below) the same rule holds against
+ * the BIASED offline search, and Tokens are revised from step to step more often (an unfinished match that led drops back): the
+ * re-read contract above covers it. */
 int32_t k2hip_set_decoding_method(k2hip_model_t* model, const char* method /* "greedy_search" | "modified_beam_search" */,
                                   int32_t beam /* 1..8, ignored for greedy_search */);
 /* operator level: modified beam search over a host encoder_out [B,T',J]; scores [B] (optional) = log-prob of the
@@ -307,14 +309,14 @@ int32_t k2hip_last_scores(k2hip_model_t* model, float* scores, int32_t B);
  * changes no stream.  The fused step (k2hip_online_step) runs the same kernel. */
 int32_t k2hip_beam_stream_create(k2hip_model_t* model, int32_t beam /* 1..8 */, k2hip_beam_stream_t** out);
 int32_t k2hip_beam_stream_destroy(k2hip_beam_stream_t* s);
-int32_t k2hip_beam_stream_reset(k2hip_beam_stream_t* s);   /* back to the start state */
+int32_t k2hip_beam_stream_reset(k2hip_beam_stream_t* s);   /* back to the start state (an attached hotword graph stays) */
 int32_t k2hip_beam_search_chunk(k2hip_model_t* model, k2hip_beam_stream_t* const* streams, int32_t B, const float* enc_out, int32_t Tc);
 int32_t k2hip_beam_stream_num_tokens(const k2hip_beam_stream_t* s);
 int32_t k2hip_beam_stream_get_tokens(const k2hip_beam_stream_t* s, int64_t* tokens, int32_t cap);
 int32_t k2hip_beam_stream_get_timestamps(const k2hip_beam_stream_t* s, int32_t* timestamps, int32_t cap);
 int32_t k2hip_beam_stream_get_score(const k2hip_beam_stream_t* s, float* score);
 
-/* ---- hotword (contextual) biasing of the OFFLINE modified beam search ------------------------------------------------------
+/* ---- hotword (contextual) biasing of the modified beam search, offline (per model) and streaming (per stream) ----------------
  * The reference never got this far (Utils/HotwordsHelper.cs is a helper without a call site: it has no beam search); the
  * semantics are the project's own, after icefall's ContextGraph, and are defined here and in DESIGN.md "Hotword biasing".
  *
@@ -351,9 +353,29 @@ int32_t k2hip_hotwords_pending(const k2hip_hotwords_t* hw, int32_t state, float*
  * the offline modified beam search runs: k2hip_beam_search and the batch entry points under
  * k2hip_set_decoding_method("modified_beam_search") (k2hip_offline_greedy*, k2hip_offline_recognizer_get_results, submit / wait).
  * Greedy search, the CTC search and the single-stream path ignore it.  No hotwords, or an empty list: bit for bit the unbiased
- * results.  STREAMING is not covered: with hotwords set, k2hip_beam_search_chunk and k2hip_online_step under
- * modified_beam_search fail with K2HIP_ERR_INVALID (streaming greedy is untouched). */
+ * results.  This list is the OFFLINE batch's: with it set, k2hip_beam_search_chunk and k2hip_online_step under
+ * modified_beam_search fail with K2HIP_ERR_INVALID, graphs attached to the streams or not (streaming greedy is untouched).
+ * STREAMING takes its graph per stream, below. */
 int32_t k2hip_set_hotwords(k2hip_model_t* model, const k2hip_hotwords_t* hw);
+/* STREAMING: the graph belongs to the stream (each connection brings its own list).  hw = NULL detaches.  Checks vocab_size against
+ * the stream's model; the stream keeps its own reference to the uploaded tables, so hw may be destroyed afterwards.  Streams that
+ * attach the same k2hip_hotwords_t to the same model share one upload; the tables are freed when the last such stream is detached
+ * or destroyed, or with the model (a stream may be destroyed before or after its model as far as the graph is concerned).
+ * Allowed only while the stream holds the start state -- before its first decoded chunk or after k2hip_online_stream_reset /
+ * k2hip_beam_stream_reset -- else K2HIP_ERR_INVALID ("... reset the stream first"): saved hypotheses carry states of the graph they
+ * started with.  A reset keeps the graph and returns every hypothesis to the root.
+ * Semantics: after every step (k2hip_online_step under modified_beam_search, k2hip_beam_search_chunk) the stream holds exactly
+ * what the offline biased search (k2hip_beam_search with the same graph set by k2hip_set_hotwords) gives over ALL encoder frames
+ * produced so far.  Every saved hypothesis carries its graph state across the chunk boundary, and its carried log-prob KEEPS the
+ * pending bonus (the match may complete in the next chunk).  Per step the best hypothesis is picked on
+ * (log-prob - pending(state)) / (length + 2), first maximum, and k2hip_online_stream_get_score / k2hip_beam_stream_get_score
+ * report log-prob - pending(state) of that pick; nothing is subtracted from what is carried.  Tokens can therefore be revised from
+ * step to step more often than without a graph: re-read them after every step (n_new_tokens is a signed change).
+ * One call may mix streams with different graphs and streams with none; a call in which no stream has a graph is exactly the
+ * unbiased call.  An empty graph or score_per_token = 0: bit for bit the unbiased results.  Streaming greedy search and a CTC model's
+ * search ignore an attached graph. */
+int32_t k2hip_online_stream_set_hotwords(k2hip_online_stream_t* s, const k2hip_hotwords_t* hw);
+int32_t k2hip_beam_stream_set_hotwords(k2hip_beam_stream_t* s, const k2hip_hotwords_t* hw);
 
 /* OfflineRecognizer.GetResults (:85-91) minus DecodeMulti: runs the fused batch
  * path on the streams' feature buffers, stores Tokens/Timestamps in each stream

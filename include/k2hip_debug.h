@@ -37,6 +37,13 @@ int32_t k2hip_debug_decoder_table_check(k2hip_model_t* model, int32_t n_samples,
  * (oracle/k2_oracle_beam.c) to find the first frame at which the two searches part. */
 int32_t k2hip_debug_beam_trace(k2hip_model_t* model, int32_t* trace, int64_t cap_words, int32_t* B, int32_t* Tprime, int32_t* beam);
 
+/* Hotword graphs of the streaming search (k2hip_online_stream_set_hotwords, k2hip_beam_stream_set_hotwords): uploads = tables
+ * uploaded for this model's streams since it was created, resident = graphs on the device now */
+int32_t k2hip_debug_stream_hotword_uploads(k2hip_model_t* model, int32_t* uploads, int32_t* resident);
+/* modified beam searches enqueued by this process so far, by kernel instantiation: plain = the unbiased kernels, hotwords = the
+ * biased ones (a call in which no stream has a graph must count as plain) */
+int32_t k2hip_debug_beam_launch_counts(int64_t* plain, int64_t* hotwords);
+
 /* ---- streaming --------------------------------------------------------------------------------- */
 /* mark a stream as if a chunk step over it had failed on the device (k2hip_online_step's poisoning rule, k2hip.h) */
 int32_t k2hip_debug_poison_stream(k2hip_online_stream_t* s);

@@ -193,8 +193,8 @@ class TokenTable:
 
 
 class Hotwords:
-    """The hotword graph of the offline modified beam search (k2hip_hotwords_t; include/k2hip.h "hotword biasing"): a trie of
-    token-id phrases with Aho-Corasick failure links.  Host only: built and walked without a GPU.  `phrases`: sequences of token
+    """The hotword graph of the modified beam search, set per model for the offline search or per stream for the streaming one
+    (k2hip_hotwords_t; include/k2hip.h "hotword biasing"): a trie of token-id phrases with Aho-Corasick failure links.  Host only: built and walked without a GPU.  `phrases`: sequences of token
     ids; `score` = the bonus per matched token.  Hotwords.load reads a pre-tokenised text file through a TokenTable."""
 
     def _bind(self):
@@ -683,6 +683,8 @@ def _bind_online(L):
     L.k2hip_beam_stream_get_tokens.argtypes = [vp, lp, C.c_int32]
     L.k2hip_beam_stream_get_timestamps.argtypes = [vp, ip, C.c_int32]
     L.k2hip_beam_stream_get_score.argtypes = [vp, fp]
+    L.k2hip_online_stream_set_hotwords.argtypes = [vp, vp]
+    L.k2hip_beam_stream_set_hotwords.argtypes = [vp, vp]
     L._online_bound = True
 
 
@@ -700,6 +702,11 @@ class OnlineStream:
     def reset(self):
         """back to a freshly created stream (same slot): for the next utterance on the same object"""
         self._m._chk(self._L.k2hip_online_stream_reset(self._h))
+
+    def set_hotwords(self, hotwords: Optional["Hotwords"] = None):
+        """k2hip_online_stream_set_hotwords: this stream's hotword graph under modified_beam_search; None detaches.  Only before the
+        stream's first decoded chunk or after reset(); the stream keeps its own reference (hotwords.close() afterwards is fine)."""
+        self._m._chk(self._L.k2hip_online_stream_set_hotwords(self._h, hotwords._h if hotwords is not None else None))
 
     def close(self):
         if getattr(self, "_h", None):
@@ -852,6 +859,10 @@ class BeamStream:
     def reset(self):
         self._m._chk(self._L.k2hip_beam_stream_reset(self._h))
 
+    def set_hotwords(self, hotwords: Optional["Hotwords"] = None):
+        """k2hip_beam_stream_set_hotwords: this stream's hotword graph; None detaches.  Only in the start state (new or reset)."""
+        self._m._chk(self._L.k2hip_beam_stream_set_hotwords(self._h, hotwords._h if hotwords is not None else None))
+
     @staticmethod
     def search_chunk(streams: Sequence["BeamStream"], enc_out):
         """continue every stream's search over enc_out [B, Tc, J] (k2hip_beam_search_chunk)"""
@@ -903,8 +914,20 @@ class OnlineRecognizer:
                             "lstm": ["lstm_h", "lstm_c"]}.get(mt, [])
         self.embed_state_floats = 128 * 3 * 19 if mt in ("zipformer2", "zipformer2ctc") else 0
 
-    def create_online_stream(self) -> OnlineStream:  # CreateOnlineStream :60-64
-        return OnlineStream(self.model)
+    def create_online_stream(self, hotwords=None, hotwords_score: float = 1.5) -> OnlineStream:  # CreateOnlineStream :60-64
+        """hotwords: a Hotwords graph, or a list of token-id phrases scored hotwords_score per matched token -- the stream's own list
+        (sherpa-onnx's CreateStream(hotwords)); it biases modified_beam_search only."""
+        s = OnlineStream(self.model)
+        if hotwords is not None:
+            if isinstance(hotwords, Hotwords):
+                s.set_hotwords(hotwords)
+            else:
+                hw = Hotwords(hotwords, hotwords_score, self.model.vocab_size)
+                try:
+                    s.set_hotwords(hw)
+                finally:
+                    hw.close()   # (the stream keeps its own reference to the uploaded tables)
+        return s
 
     def add_samples_batch(self, streams: Sequence[OnlineStream], samples: Sequence[np.ndarray]):
         """B AddSamples calls in one (one fbank launch when all streams are at the same position)."""

@@ -2,6 +2,7 @@
 // OfflineStream / OfflineRecognizer bookkeeping (K2TransducerAsr/OfflineStream.cs,
 // OfflineRecognizer.cs:77-91,289-296).
 #include <algorithm>
+#include <atomic>
 #include <fstream>
 #include <map>
 #include <memory>
@@ -69,6 +70,22 @@ struct PinVec {
     }
 };
 
+// A hotword graph resident on a model's device for the streams that attached it (k2hip_online_stream_set_hotwords,
+// k2hip_beam_stream_set_hotwords): the dense tables in ONE allocation [next | bonus | pending] and a host copy of pending.  Streams
+// hold it through a shared_ptr; the model's cache (k2hip_model::hw_cache, keyed by the graph's serial number) holds a weak one, so
+// the tables are freed when the last stream lets go -- or with the model, which then clears `owner` and `dev`: a stream that outlives
+// its model drops its reference without touching the model.  g_hw_mu guards the caches, `owner` and `dev` of every model; it is taken
+// before an engine lock, never inside one.
+struct HwResident {
+    uint64_t serial = 0;
+    k2hip_model* owner = nullptr;
+    void* dev = nullptr;
+    BeamHwStream tables;
+    std::shared_ptr<const std::vector<float>> pending;
+};
+static std::mutex g_hw_mu;
+static std::atomic<uint64_t> g_hw_serial{0};
+
 struct k2hip_model {
     Engine engine;
     // Sample buffers of destroyed OfflineStreams, handed to the next streams (a GetResults batch is B x create / AddSamples / destroy
@@ -79,8 +96,26 @@ struct k2hip_model {
     std::vector<PinVec> wav_pool;   // (declared behind `engine`: released first)
     // the hotword tables on the device (k2hip_set_hotwords): one allocation [next | bonus | pending], or null
     void* hw_dev = nullptr;
+    // the graphs attached to this model's streams (HwResident), by serial number; hw_uploads counts the uploads (k2hip_debug.h)
+    std::map<uint64_t, std::weak_ptr<HwResident>> hw_cache;
+    int hw_uploads = 0;
     k2hip_model(const char* path, const char* ov, int dev) : engine(path, ov, dev) {}
     ~k2hip_model() {
+        {
+            std::lock_guard<std::mutex> g(g_hw_mu);
+            for (auto& kv : hw_cache)
+                if (auto r = kv.second.lock()) {   // streams still hold it: the tables go with the model, the host part stays theirs
+                    try {
+                        engine.synchronize();
+                        engine.dev_free(r->dev);
+                    } catch (...) {
+                    }
+                    r->dev = nullptr;
+                    r->owner = nullptr;
+                    r->tables = BeamHwStream{};
+                }
+            hw_cache.clear();
+        }
         if (hw_dev) {
             try {
                 engine.synchronize();
@@ -138,12 +173,15 @@ struct k2hip_online_stream {
     int method = -1;
     // modified_beam_search: the hypotheses carried between chunks; Tokens / Timestamps / Hyp are its best hypothesis
     std::unique_ptr<BeamHistory> beam;
+    // the stream's hotword graph (k2hip_online_stream_set_hotwords) or null; kept by a reset
+    std::shared_ptr<HwResident> hw;
 };
 
 // operator level of the streaming beam search: one stream's hypotheses, fed encoder frames by the caller (k2hip_beam_search_chunk)
 struct k2hip_beam_stream {
     k2hip_model* model;
     BeamHistory hist;
+    std::shared_ptr<HwResident> hw;   // the stream's hotword graph (k2hip_beam_stream_set_hotwords) or null
 };
 
 // one stream's encoder caches as the operator-level API sees them (IOnlineProj's List<List<float[]>>): a slot of the device pool
@@ -428,7 +466,65 @@ int32_t k2hip_decode_text(const k2hip_tokens_t* t, const int64_t* ids, int32_t n
 // ---- hotword biasing (hotwords.cpp) ----------------------------------------------------------------
 struct k2hip_hotwords {
     k2hip::HotwordGraph graph;
+    uint64_t serial = ++g_hw_serial;   // the graph's identity for the models' caches (a handle's address can be reused)
 };
+// last reference gone (a stream detached, was reset to none or destroyed): free the tables unless the model already did
+static void hw_resident_release(HwResident* r) {
+    {
+        std::lock_guard<std::mutex> g(g_hw_mu);
+        if (r->owner) {
+            auto it = r->owner->hw_cache.find(r->serial);
+            if (it != r->owner->hw_cache.end() && it->second.expired()) r->owner->hw_cache.erase(it);
+            try {
+                Engine& e = r->owner->engine;
+                EngineLock lk(e);
+                e.synchronize();
+                e.dev_free(r->dev);
+            } catch (...) {
+            }
+        }
+    }
+    delete r;
+}
+// the model's resident copy of `hw`: the cached one, or a fresh upload
+static std::shared_ptr<HwResident> hw_resident_get(k2hip_model* model, const k2hip_hotwords* hw, const char* who) {
+    Engine& e = model->engine;
+    const int V = e.model().cfg().V;
+    K2_REQUIRE(hw->graph.vocab_size() == V, "%s: the graph was built for vocab_size %d, the model has %d", who, hw->graph.vocab_size(), V);
+    std::lock_guard<std::mutex> g(g_hw_mu);
+    auto it = model->hw_cache.find(hw->serial);
+    if (it != model->hw_cache.end())
+        if (auto r = it->second.lock()) return r;
+    std::vector<int32_t> next;
+    std::vector<float> bonus;
+    auto pending = std::make_shared<std::vector<float>>();
+    hw->graph.dense(&next, &bonus, pending.get());
+    const int64_t nb_t = (int64_t)sizeof(int32_t) * (int64_t)next.size(), nb_p = (int64_t)sizeof(float) * (int64_t)pending->size();
+    std::unique_ptr<HwResident> fresh(new HwResident());
+    fresh->serial = hw->serial;
+    fresh->pending = pending;
+    {
+        EngineLock lk(e);
+        void* d = e.dev_alloc(2 * nb_t + nb_p);
+        try {
+            char* c = static_cast<char*>(d);
+            e.dev_upload(c, next.data(), nb_t);
+            e.dev_upload(c + nb_t, bonus.data(), nb_t);
+            e.dev_upload(c + 2 * nb_t, pending->data(), nb_p);
+            fresh->tables = BeamHwStream{reinterpret_cast<const int*>(c), reinterpret_cast<const float*>(c + nb_t),
+                                         reinterpret_cast<const float*>(c + 2 * nb_t)};
+        } catch (...) {
+            try { e.dev_free(d); } catch (...) {}
+            throw;
+        }
+        fresh->dev = d;
+    }
+    fresh->owner = model;
+    std::shared_ptr<HwResident> r(fresh.release(), hw_resident_release);
+    model->hw_cache[hw->serial] = r;
+    model->hw_uploads++;
+    return r;
+}
 int32_t k2hip_hotwords_create(const int64_t* ids, const int32_t* lens, int32_t n_phrases, float score_per_token, int32_t vocab_size,
                               k2hip_hotwords_t** out) {
     return guard([&] {
@@ -730,8 +826,19 @@ int32_t k2hip_online_stream_reset(k2hip_online_stream_t* s) {
             s->slot = -1;
             s->slot = model->engine.online_alloc_slot();  // (the slot just freed: re-zeroed like GetEncoderInitStates)
         }
+        std::shared_ptr<HwResident> hw = std::move(s->hw);   // (the attached hotword graph stays; every hypothesis is back at its root)
         *s = k2hip_online_stream{model, s->slot};
+        s->hw = std::move(hw);
         if (model->engine.model().cfg().conformer) s->processed_len = 2;
+    });
+}
+int32_t k2hip_online_stream_set_hotwords(k2hip_online_stream_t* s, const k2hip_hotwords_t* hw) {
+    return guard([&] {
+        NEED(s);
+        K2_REQUIRE(s->chunks_done == 0 && s->method < 0, "online stream set_hotwords: the stream has decoded %lld chunks and its hypotheses carry "
+                   "states of the graph it started with -- reset the stream first", s->chunks_done);
+        s->hw = hw ? hw_resident_get(s->model, hw, "online stream set_hotwords") : nullptr;
+        if (s->beam) s->beam->set_pending(s->hw ? s->hw->pending : nullptr);
     });
 }
 int32_t k2hip_online_stream_destroy(k2hip_online_stream_t* s) {
@@ -986,14 +1093,31 @@ int32_t k2hip_online_step(k2hip_model_t* model, k2hip_online_stream_t* const* st
         std::vector<int64_t> tok;
         std::vector<int32_t> ts, n;
         std::vector<int> bin, bout;   // modified beam search: the streams' saved hypotheses in, the surviving ones out
+        bool any_hw = false;
+        std::vector<BeamHwStream> graphs;
+        std::vector<int> st_in, st_out;
         const BeamResumeLayout RL{std::max(K, 1), Tp};
         if (K > 0) {
             bin.resize((size_t)R * RL.in_ints());
             bout.resize((size_t)R * RL.out_ints());
             for (int r = 0; r < R; r++) {
                 k2hip_online_stream* s = streams[idx[r]];
-                if (!s->beam) s->beam.reset(new BeamHistory(K, K2HIP_BLANK_ID));
+                if (!s->beam) {
+                    s->beam.reset(new BeamHistory(K, K2HIP_BLANK_ID));
+                    if (s->hw) s->beam->set_pending(s->hw->pending);
+                }
                 s->beam->fill_in(bin.data() + (size_t)r * RL.in_ints(), Tp);
+                any_hw = any_hw || s->hw;
+            }
+            if (any_hw) {   // hotword graphs: the side blocks of the tick (none attached anywhere: the unbiased call, unchanged)
+                graphs.resize((size_t)R);
+                st_in.resize((size_t)R * K);
+                st_out.resize((size_t)R * K);
+                for (int r = 0; r < R; r++) {
+                    k2hip_online_stream* s = streams[idx[r]];
+                    if (s->hw) graphs[(size_t)r] = s->hw->tables;
+                    s->beam->fill_states(st_in.data() + (size_t)r * K);
+                }
             }
         } else {
             tok.resize((size_t)R * Tp);
@@ -1003,7 +1127,10 @@ int32_t k2hip_online_step(k2hip_model_t* model, k2hip_online_stream_t* const* st
         if (!all_mirrored) fb.finish();   // the step reads some stream's chunk from host memory: the frames must be there
         try {
             EngineLock lk(e);
-            if (K > 0)
+            if (K > 0 && any_hw)
+                e.online_step_beam_hw(slots.data(), chunks.data(), plens.data(), nch.data(), R, K, bin.data(), bout.data(),
+                                      Engine::BeamHwIO{graphs.data(), st_in.data(), st_out.data()}, all_mirrored ? heads.data() : nullptr);
+            else if (K > 0)
                 e.online_step_beam(slots.data(), chunks.data(), plens.data(), nch.data(), R, K, bin.data(), bout.data(),
                                    all_mirrored ? heads.data() : nullptr);
             else
@@ -1034,7 +1161,8 @@ int32_t k2hip_online_step(k2hip_model_t* model, k2hip_online_stream_t* const* st
             if (K > 0) {
                 // the best hypothesis replaces the result (it may revise earlier tokens): n_new_tokens = change of its length
                 const int64_t before = (int64_t)s->beam->tokens().size();
-                s->beam->apply_out(bout.data() + (size_t)r * RL.out_ints(), Tp);
+                if (any_hw) s->beam->apply_out_states(bout.data() + (size_t)r * RL.out_ints(), Tp, st_out.data() + (size_t)r * K);
+                else s->beam->apply_out(bout.data() + (size_t)r * RL.out_ints(), Tp);
                 s->hyp[0] = s->beam->hyp_last(0);
                 s->hyp[1] = s->beam->hyp_last(1);
                 n_new_tokens[idx[r]] = (int32_t)((int64_t)s->beam->tokens().size() - before);
@@ -1174,7 +1302,7 @@ int32_t k2hip_beam_stream_create(k2hip_model_t* model, int32_t beam, k2hip_beam_
         *out = nullptr;
         K2_REQUIRE(beam >= 1 && beam <= kMaxBeam, "beam stream: beam %d out of range [1,%d]", beam, kMaxBeam);
         K2_REQUIRE(!model->engine.model().cfg().ctc, "beam stream: a CTC model has no transducer search");
-        *out = new k2hip_beam_stream{model, BeamHistory(beam, K2HIP_BLANK_ID)};
+        *out = new k2hip_beam_stream{model, BeamHistory(beam, K2HIP_BLANK_ID), nullptr};
     });
 }
 int32_t k2hip_beam_stream_destroy(k2hip_beam_stream_t* s) {
@@ -1183,7 +1311,16 @@ int32_t k2hip_beam_stream_destroy(k2hip_beam_stream_t* s) {
 int32_t k2hip_beam_stream_reset(k2hip_beam_stream_t* s) {
     return guard([&] {
         NEED(s);
-        s->hist.reset();
+        s->hist.reset();   // (an attached hotword graph stays; every hypothesis is back at its root)
+    });
+}
+int32_t k2hip_beam_stream_set_hotwords(k2hip_beam_stream_t* s, const k2hip_hotwords_t* hw) {
+    return guard([&] {
+        NEED(s);
+        K2_REQUIRE(s->hist.frames() == 0, "beam stream set_hotwords: the stream has searched %lld frames and its hypotheses carry states of the "
+                   "graph it started with -- reset the stream first", s->hist.frames());
+        s->hw = hw ? hw_resident_get(s->model, hw, "beam stream set_hotwords") : nullptr;
+        s->hist.set_pending(s->hw ? s->hw->pending : nullptr);
     });
 }
 int32_t k2hip_beam_search_chunk(k2hip_model_t* model, k2hip_beam_stream_t* const* streams, int32_t B, const float* enc_out, int32_t Tc) {
@@ -1208,12 +1345,30 @@ int32_t k2hip_beam_search_chunk(k2hip_model_t* model, k2hip_beam_stream_t* const
         const BeamResumeLayout L{K, Tc};
         std::vector<int> bin((size_t)B * L.in_ints()), bout((size_t)B * L.out_ints());
         for (int b = 0; b < B; b++) streams[b]->hist.fill_in(bin.data() + (size_t)b * L.in_ints(), Tc);
+        // hotword graphs: with none attached anywhere this is the unbiased call, unchanged; else the side blocks go along
+        bool any_hw = false;
+        for (int b = 0; b < B; b++) any_hw = any_hw || streams[b]->hw;
+        std::vector<BeamHwStream> graphs;
+        std::vector<int> st_in, st_out;
+        if (any_hw) {
+            graphs.resize((size_t)B);
+            st_in.resize((size_t)B * K);
+            st_out.resize((size_t)B * K);
+            for (int b = 0; b < B; b++) {
+                if (streams[b]->hw) graphs[(size_t)b] = streams[b]->hw->tables;
+                streams[b]->hist.fill_states(st_in.data() + (size_t)b * K);
+            }
+        }
         {
             EngineLock lk(model->engine);
-            model->engine.beam_chunk_host(enc_out, B, Tc, K, bin.data(), bout.data());
+            if (any_hw) model->engine.beam_chunk_host_hw(enc_out, B, Tc, K, bin.data(), bout.data(), Engine::BeamHwIO{graphs.data(), st_in.data(), st_out.data()});
+            else model->engine.beam_chunk_host(enc_out, B, Tc, K, bin.data(), bout.data());
         }
         // (only after success: a failed call leaves every stream as it was)
-        for (int b = 0; b < B; b++) streams[b]->hist.apply_out(bout.data() + (size_t)b * L.out_ints(), Tc);
+        for (int b = 0; b < B; b++) {
+            if (any_hw) streams[b]->hist.apply_out_states(bout.data() + (size_t)b * L.out_ints(), Tc, st_out.data() + (size_t)b * K);
+            else streams[b]->hist.apply_out(bout.data() + (size_t)b * L.out_ints(), Tc);
+        }
     });
 }
 int32_t k2hip_beam_stream_num_tokens(const k2hip_beam_stream_t* s) { return s ? (int32_t)s->hist.tokens().size() - 2 : -1; }
@@ -1254,6 +1409,26 @@ int32_t k2hip_online_stream_state(k2hip_online_stream_t* s, int32_t layer, int32
     });
 }
 
+// hotword graphs uploaded for this model's streams so far, and how many are resident now (k2hip_debug.h)
+int32_t k2hip_debug_stream_hotword_uploads(k2hip_model_t* model, int32_t* uploads, int32_t* resident) {
+    return guard([&] {
+        NEED(model); NEED(uploads); NEED(resident);
+        std::lock_guard<std::mutex> g(g_hw_mu);
+        *uploads = model->hw_uploads;
+        int n = 0;
+        for (auto& kv : model->hw_cache) n += !kv.second.expired();
+        *resident = n;
+    });
+}
+int32_t k2hip_debug_beam_launch_counts(int64_t* plain, int64_t* hotwords) {
+    return guard([&] {
+        NEED(plain); NEED(hotwords);
+        long long p = 0, h = 0;
+        beam_launch_counts(&p, &h);
+        *plain = p;
+        *hotwords = h;
+    });
+}
 // one-part repeats of the vocabulary-parallel search since the model was created (test / monitoring hook: include/k2hip_debug.h)
 int32_t k2hip_debug_search_retries(k2hip_model_t* model, int32_t* n) {
     return guard([&] {

@@ -14,17 +14,23 @@
 // [blank, blank]; a hypothesis is then (saved index org, suffix ys of this chunk), its decoder context falls back to the saved
 // context while the suffix is shorter than 2, and the merge test of two candidates from different saved hypotheses goes through the
 // host's relation table.  With rin == null every one of these is the offline search's own behaviour.
-// Hotword biasing (BeamArgs::hw_*, offline only): every hypothesis carries the state of the hotword graph; the bonus of a selected
+// Hotword biasing (BeamArgs::hw_*): every hypothesis carries the state of the hotword graph; the bonus of a selected
 // candidate is looked up after the frame's selection and added before the merges, the new state is written with the hypothesis, and
 // the final pick takes back the pending bonus of an unfinished match.  The kernels are templates on HW: HW = false is the unbiased
-// search, with nothing added to its code.
+// search, with nothing added to its code.  Streaming with hotwords (HW and resume): every stream of the call brings its own tables
+// (BeamArgs::hw_streams; none = no bonus, state 0), the saved hypotheses' states come in with st_in and the survivors' go out with
+// st_out, and the out block's `best` follows the same final pick while the log-probs written keep the pending bonus.
 #include <type_traits>
+
+#include <atomic>
 
 #include "kernels.h"
 #include "sweep.h"
 
 namespace k2hip {
 namespace {
+
+std::atomic<long long> g_launches[2];   // searches enqueued with HW = false / true (beam_launch_counts)
 
 constexpr int BT = 256;  // threads per stream workgroup
 
@@ -58,6 +64,10 @@ __global__ void k_beam_resume_init(BeamState s, int B) {
     s.org[B * K + i] = 0;
     s.ctx[2 * i] = k < nh ? in[L.in_ctx() + 2 * k] : K2HIP_BLANK_ID;
     s.ctx[2 * i + 1] = k < nh ? in[L.in_ctx() + 2 * k + 1] : K2HIP_BLANK_ID;
+    if (s.st) {
+        s.st[i] = (s.st_in && k < nh) ? s.st_in[i] : 0;
+        s.st[B * K + i] = 0;
+    }
     if (k == 0) s.nhyp[b] = nh;
 }
 
@@ -142,7 +152,8 @@ struct HypView {
     int* org_n = nullptr;
     const int* rin = nullptr;
     int Tp = 0;
-    // hotword biasing (HW instantiations only): graph state of each hypothesis at frame t / t + 1, the tables [S][V]
+    // hotword biasing (HW instantiations only): graph state of each hypothesis at frame t / t + 1, the stream's tables [S][V] (null:
+    // a stream without a graph in a call that has one -- no bonus, the states stay 0)
     const int* st_c = nullptr;
     int* st_n = nullptr;
     const int* hw_next = nullptr;
@@ -318,7 +329,7 @@ __device__ void beam_step_body(const HypView& hv, const float* lg, int ldl, int 
                 // the selected candidate's bonus (the selection itself and the tap's `val` stay unbiased): independent loads
                 if (r < want) {
                     const int hr = topi[r] / V, tr = topi[r] % V;
-                    if (tr != K2HIP_BLANK_ID && tr != K2HIP_UNK_ID) tv[r] += hv.hw_bonus[(long long)hv.st_c[hr] * V + tr];
+                    if (hv.hw_bonus && tr != K2HIP_BLANK_ID && tr != K2HIP_UNK_ID) tv[r] += hv.hw_bonus[(long long)hv.st_c[hr] * V + tr];
                 }
             }
             lpn[r] = -INFINITY;
@@ -402,7 +413,7 @@ __device__ void beam_step_body(const HypView& hv, const float* lg, int ldl, int 
                 nn++;
             }
             n_n[slot] = nn;
-            if constexpr (HW) hv.st_n[slot] = realr ? hv.hw_next[(long long)hv.st_c[hr] * V + tr] : hv.st_c[hr];
+            if constexpr (HW) hv.st_n[slot] = (realr && hv.hw_next) ? hv.hw_next[(long long)hv.st_c[hr] * V + tr] : hv.st_c[hr];
             // decoder context of the new hypothesis: last two of [c0, c1] + ys, [c0, c1] = the saved hypothesis' context (resume) or
             // [blank, blank]
             long long c0 = K2HIP_BLANK_ID, c1 = K2HIP_BLANK_ID;
@@ -448,8 +459,8 @@ __global__ __launch_bounds__(BT) void k_beam_step(BeamState s, const float* __re
     if constexpr (HW) {
         hv.st_c = s.st + cur * BK + b * K;
         hv.st_n = s.st + nxt * BK + b * K;
-        hv.hw_next = s.hw_next;
-        hv.hw_bonus = s.hw_bonus;
+        hv.hw_next = s.hw_streams ? s.hw_streams[b].next : s.hw_next;
+        hv.hw_bonus = s.hw_streams ? s.hw_streams[b].bonus : s.hw_bonus;
     }
     beam_step_body<BT, HW>(hv, logits + (long long)b * K * V, V, V, t, scratch);
 }
@@ -457,15 +468,23 @@ __global__ __launch_bounds__(BT) void k_beam_step(BeamState s, const float* __re
 // resume: every surviving hypothesis of the stream into its out block, and the best one (get_most_probable over the WHOLE
 // sequences: length = |saved| + |suffix| + the 2 ctx blanks, first maximum).  ys / ts / n / org: the final parity's [K][cap] / [K]
 // arrays of the stream.  Called by all threads of a workgroup.
+// HW: st = the hypotheses' graph states, pending = the stream's table or null; the pick is made on lp - pending(state) (an unfinished
+// match earns nothing), the log-probs go out as they are, the states to st_out [K].
+template <bool HW>
 __device__ void beam_resume_write(const int* in, int* out, int K, int Tp, int cap, int nh, const float* lp, const long long* ctx,
-                                  const int* n, const int* org, const int* ys, const int* ts) {
+                                  const int* n, const int* org, const int* ys, const int* ts, const int* st = nullptr,
+                                  const float* pending = nullptr, int* st_out = nullptr) {
     const BeamResumeLayout L{K, Tp};
     const int tid = threadIdx.x;
     if (tid == 0) {
         int best = 0;
         float bs = -INFINITY;
         for (int k = 0; k < nh; k++) {
-            const float v = lp[k] / (float)(in[L.in_len() + org[k]] + n[k] + 2);
+            float l = lp[k];
+            if constexpr (HW) {
+                if (pending) l -= pending[st[k]];
+            }
+            const float v = l / (float)(in[L.in_len() + org[k]] + n[k] + 2);
             if (k == 0 || v > bs) { bs = v; best = k; }
         }
         out[0] = nh;
@@ -478,6 +497,9 @@ __device__ void beam_resume_write(const int* in, int* out, int K, int Tp, int ca
         out[L.out_lp() + k] = __float_as_int(live ? lp[k] : -INFINITY);
         out[L.out_ctx() + 2 * k] = live ? (int)ctx[2 * k] : K2HIP_BLANK_ID;
         out[L.out_ctx() + 2 * k + 1] = live ? (int)ctx[2 * k + 1] : K2HIP_BLANK_ID;
+        if constexpr (HW) {
+            if (st_out) st_out[k] = live ? st[k] : 0;
+        }
     }
     for (int i = tid; i < nh * Tp; i += blockDim.x) {
         const int k = i / Tp, j = i - k * Tp;
@@ -487,13 +509,21 @@ __device__ void beam_resume_write(const int* in, int* out, int K, int Tp, int ca
         }
     }
 }
+template <bool HW>
 __global__ void k_beam_resume_final(BeamState s, int fin, int B, int* __restrict__ rout) {
     const int b = blockIdx.x, K = s.K;
     const long long BK = (long long)B * K;
     const BeamResumeLayout L{K, s.Tp};
-    beam_resume_write(s.rin + (long long)b * L.in_ints(), rout + (long long)b * L.out_ints(), K, s.Tp, s.cap, s.nhyp[b], s.lp + b * K,
-                      s.ctx + 2 * (long long)b * K, s.n + fin * BK + b * K, s.org + fin * BK + b * K,
-                      s.ys + (fin * BK + (long long)b * K) * s.cap, s.ts + (fin * BK + (long long)b * K) * s.cap);
+    if constexpr (HW)
+        beam_resume_write<true>(s.rin + (long long)b * L.in_ints(), rout + (long long)b * L.out_ints(), K, s.Tp, s.cap, s.nhyp[b], s.lp + b * K,
+                                s.ctx + 2 * (long long)b * K, s.n + fin * BK + b * K, s.org + fin * BK + b * K,
+                                s.ys + (fin * BK + (long long)b * K) * s.cap, s.ts + (fin * BK + (long long)b * K) * s.cap,
+                                s.st + fin * BK + b * K, s.hw_streams ? s.hw_streams[b].pending : s.hw_pending,
+                                s.st_out ? s.st_out + b * K : nullptr);
+    else
+        beam_resume_write<false>(s.rin + (long long)b * L.in_ints(), rout + (long long)b * L.out_ints(), K, s.Tp, s.cap, s.nhyp[b], s.lp + b * K,
+                                 s.ctx + 2 * (long long)b * K, s.n + fin * BK + b * K, s.org + fin * BK + b * K,
+                                 s.ys + (fin * BK + (long long)b * K) * s.cap, s.ts + (fin * BK + (long long)b * K) * s.cap);
 }
 
 // ---- the whole search of a stream in one kernel (small vocabularies: the model's all-contexts decoder table) -----------------
@@ -541,6 +571,12 @@ __global__ __launch_bounds__(GT) void k_beam_loop(DecJoinW w, BeamLoopArgs a) {
     const float* enc = a.enc + (long long)b * a.Tp * w.J;
     const BeamResumeLayout RL{K, a.Tp};
     const int* rin = a.rin ? a.rin + (long long)b * RL.in_ints() : nullptr;
+    // this stream's hotword tables: its own (streaming) or the call's one graph
+    BeamHwStream hws;
+    if constexpr (HW) {
+        if (a.hw_streams) hws = a.hw_streams[b];
+        else hws = BeamHwStream{a.hw_next, a.hw_bonus, a.hw_pending};
+    }
     if (tid < GF) {   // k_beam_init / k_beam_resume_init
         nbuf[tid] = 0;
         nbuf[GF + tid] = 0;
@@ -556,6 +592,9 @@ __global__ __launch_bounds__(GT) void k_beam_loop(DecJoinW w, BeamLoopArgs a) {
             lp[tid] = live ? __int_as_float(rin[RL.in_lp() + tid]) : -INFINITY;
             ctx[2 * tid] = live ? rin[RL.in_ctx() + 2 * tid] : K2HIP_BLANK_ID;
             ctx[2 * tid + 1] = live ? rin[RL.in_ctx() + 2 * tid + 1] : K2HIP_BLANK_ID;
+            if constexpr (HW) {
+                if (a.st_in && live) stb[tid] = a.st_in[b * K + tid];   // the saved hypotheses' graph states
+            }
             if (tid == 0) *nhyp = nh;
         } else {
             lp[tid] = tid == 0 ? 0.f : -INFINITY;
@@ -703,8 +742,8 @@ __global__ __launch_bounds__(GT) void k_beam_loop(DecJoinW w, BeamLoopArgs a) {
         if constexpr (HW) {
             hv.st_c = stb + cur * GF;
             hv.st_n = stb + (cur ^ 1) * GF;
-            hv.hw_next = a.hw_next;
-            hv.hw_bonus = a.hw_bonus;
+            hv.hw_next = hws.next;
+            hv.hw_bonus = hws.bonus;
         }
         beam_step_body<GT, HW>(hv, lg, w.Vp, w.V, t, scratch);
         __syncthreads();
@@ -713,14 +752,19 @@ __global__ __launch_bounds__(GT) void k_beam_loop(DecJoinW w, BeamLoopArgs a) {
     const int fin = a.Tp & 1;
     const int* n_f = nbuf + fin * GF;
     if (rin) {   // (resume runs one workgroup per stream: no slabs)
-        beam_resume_write(rin, a.rout + (long long)b * RL.out_ints(), K, a.Tp, a.cap, *nhyp, lp, ctx, n_f, orgb + fin * GF,
-                          ys + (size_t)fin * K * a.cap, ts + (size_t)fin * K * a.cap);
+        if constexpr (HW)
+            beam_resume_write<true>(rin, a.rout + (long long)b * RL.out_ints(), K, a.Tp, a.cap, *nhyp, lp, ctx, n_f, orgb + fin * GF,
+                                    ys + (size_t)fin * K * a.cap, ts + (size_t)fin * K * a.cap, stb + fin * GF, hws.pending,
+                                    a.st_out ? a.st_out + b * K : nullptr);
+        else
+            beam_resume_write<false>(rin, a.rout + (long long)b * RL.out_ints(), K, a.Tp, a.cap, *nhyp, lp, ctx, n_f, orgb + fin * GF,
+                                     ys + (size_t)fin * K * a.cap, ts + (size_t)fin * K * a.cap);
         return;
     }
     // (hotwords: an unfinished match earns nothing -- every hypothesis' log-prob loses its state's pending bonus first)
     const int* st_f = stb + fin * GF;
     auto final_lp = [&](int k) {
-        if constexpr (HW) return lp[k] - a.hw_pending[st_f[k]];
+        if constexpr (HW) return lp[k] - hws.pending[st_f[k]];
         else return lp[k];
     };
     int best = 0;
@@ -787,9 +831,12 @@ __global__ void k_beam_final(BeamState s, int fin, int B, long long* __restrict_
 void beam_search(const Ctx& ctx, const DecJoinW& w, const BeamArgs& a) {
     K2_REQUIRE(a.beam >= 1 && a.beam <= kMaxBeam, "beam search: beam %d out of range [1,%d]", a.beam, kMaxBeam);
     K2_REQUIRE(a.B > 0 && a.Tp > 0, "beam search: bad shape");
-    const bool hw = a.hw_next != nullptr;
-    K2_REQUIRE(!hw || (a.hw_bonus && a.hw_pending), "beam search: incomplete hotword tables");
-    K2_REQUIRE(!(hw && a.rin), "beam search: hotword biasing does not cover the streaming (resumed) search");
+    const bool hw = a.hw_next != nullptr || a.hw_streams != nullptr;
+    K2_REQUIRE(!a.hw_next || (a.hw_bonus && a.hw_pending), "beam search: incomplete hotword tables");
+    K2_REQUIRE(!(a.hw_next && a.hw_streams), "beam search: one hotword graph or one per stream, not both");
+    K2_REQUIRE(!a.hw_streams || (a.rin && a.st_in && a.st_out), "beam search: per-stream hotword graphs belong to the resumed search and need its state blocks");
+    K2_REQUIRE(!(a.hw_next && a.rin), "beam search: the resumed search takes its hotword graphs per stream");
+    if (!ctx.dry) g_launches[hw ? 1 : 0]++;
     Arena& ar = *ctx.arena;
     const int B = a.B, K = a.beam, M = B * K, cap = a.Tp + 1;
     {
@@ -817,6 +864,7 @@ void beam_search(const Ctx& ctx, const DecJoinW& w, const BeamArgs& a) {
             la.trace = a.trace;
             la.rin = a.rin; la.rout = a.rout;
             la.hw_next = a.hw_next; la.hw_bonus = a.hw_bonus; la.hw_pending = a.hw_pending;
+            la.hw_streams = a.hw_streams; la.st_in = a.st_in; la.st_out = a.st_out;
             K2_HIP(hipMemsetAsync(a.overflow, 0, sizeof(int), ctx.stream));
             static LdsAttrOnce lds_attr, lds_attr1, lds_attr_hw, lds_attr1_hw;
             if (hw) {
@@ -867,6 +915,7 @@ void beam_search(const Ctx& ctx, const DecJoinW& w, const BeamArgs& a) {
     if (hw) {
         s.st = ar.take<int>((int64_t)2 * M);
         s.hw_next = a.hw_next; s.hw_bonus = a.hw_bonus; s.hw_pending = a.hw_pending;
+        s.hw_streams = a.hw_streams; s.st_in = a.st_in; s.st_out = a.st_out;
     }
     float* hbuf = ar.take<float>((int64_t)M * w.DD);
     float* act = ar.take<float>((int64_t)M * w.J);
@@ -897,13 +946,19 @@ void beam_search(const Ctx& ctx, const DecJoinW& w, const BeamArgs& a) {
         }
     }
     if (!ctx.dry) {
-        if (a.rin) hipLaunchKernelGGL(k_beam_resume_final, dim3(B), dim3(256), 0, ctx.stream, s, a.Tp & 1, B, a.rout);
+        if (a.rin && hw) hipLaunchKernelGGL(k_beam_resume_final<true>, dim3(B), dim3(256), 0, ctx.stream, s, a.Tp & 1, B, a.rout);
+        else if (a.rin) hipLaunchKernelGGL(k_beam_resume_final<false>, dim3(B), dim3(256), 0, ctx.stream, s, a.Tp & 1, B, a.rout);
         else if (hw) hipLaunchKernelGGL(k_beam_final<true>, dim3(B), dim3(256), 0, ctx.stream, s, a.Tp & 1, B, a.tokens, a.timestamps, a.n_tokens,
                                         a.scores, a.max_tokens, a.overflow);
         else hipLaunchKernelGGL(k_beam_final<false>, dim3(B), dim3(256), 0, ctx.stream, s, a.Tp & 1, B, a.tokens, a.timestamps, a.n_tokens, a.scores,
                                 a.max_tokens, a.overflow);
         K2_HIP(hipGetLastError());
     }
+}
+
+void beam_launch_counts(long long* plain, long long* hw) {
+    *plain = g_launches[0].load();
+    *hw = g_launches[1].load();
 }
 
 void beam_relaunch_one_slab(hipStream_t stream, const GreedyLaunch& rec) {
@@ -918,7 +973,7 @@ void beam_relaunch_one_slab(hipStream_t stream, const GreedyLaunch& rec) {
         if (la.scores) K2_HIP(hipMemsetAsync(la.scores, 0xEE, sizeof(float) * (size_t)rec.a.B, stream));
     }
     // (la carries the hotword tables of the first launch; its LDS size was computed with them)
-    if (la.hw_next) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_beam_loop<1, true>), dim3(rec.a.B), dim3(GT), rec.beam_lds, stream, rec.w, la);
+    if (la.hw_next || la.hw_streams) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_beam_loop<1, true>), dim3(rec.a.B), dim3(GT), rec.beam_lds, stream, rec.w, la);
     else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_beam_loop<1, false>), dim3(rec.a.B), dim3(GT), rec.beam_lds, stream, rec.w, la);
     K2_HIP(hipGetLastError());
 }

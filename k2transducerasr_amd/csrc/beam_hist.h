@@ -14,6 +14,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <memory>
 #include <unordered_map>
 #include <vector>
 
@@ -114,6 +115,7 @@ class BeamHistory {
         int seq, path;     // SeqTree / PathTree nodes
         float lp;
         int ctx[2];        // decoder context: the last two tokens of [blank, blank] + ys
+        int st = 0;        // state of the stream's hotword graph (0 = the root; always 0 without a graph)
     };
     explicit BeamHistory(int K = 1, int blank = 0) : K_(K), blank_(blank) { reset(); }
     int beam() const { return K_; }
@@ -131,7 +133,13 @@ class BeamHistory {
     const std::vector<Hyp>& hyps() const { return hyps_; }
     int best() const { return best_; }
     long long frames() const { return frames_; }
-    float score() const { return hyps_[(size_t)best_].lp; }
+    // Hotword biasing: pending[s] of the stream's graph (host copy), or null.  The carried log-probs keep the pending bonus of an
+    // unfinished match; the result's score is reported without it (the finalize rule of the offline search, applied per step).
+    void set_pending(std::shared_ptr<const std::vector<float>> pending) { pending_ = std::move(pending); }
+    float score() const {
+        const Hyp& h = hyps_[(size_t)best_];
+        return pending_ ? h.lp - (*pending_)[(size_t)h.st] : h.lp;
+    }
     // Tokens = [blank, blank] + ys of the best hypothesis; Timestamps = its absolute frame indexes
     const std::vector<int64_t>& tokens() const { return tokens_; }
     const std::vector<int32_t>& timestamps() const { return timestamps_; }
@@ -157,6 +165,15 @@ class BeamHistory {
                 else r = seq_.extension(hyps_[(size_t)k].seq, hyps_[(size_t)j].seq, Tp, &in[o_relx + (k * K + j) * Tp]);
             }
         }
+    }
+    // hotword side block in: the saved hypotheses' graph states [K]
+    void fill_states(int* st_in) const {
+        for (int k = 0; k < K_; k++) st_in[k] = k < (int)hyps_.size() ? hyps_[(size_t)k].st : 0;
+    }
+    // apply_out + the hotword side block out: the survivors' graph states [K]
+    void apply_out_states(const int* out, int Tp, const int* st_out) {
+        apply_out(out, Tp);
+        for (size_t k = 0; k < hyps_.size(); k++) hyps_[k].st = st_out[k];
     }
     // the device search's out block of that chunk: the new hypotheses, the best one, the result
     void apply_out(const int* out, int Tp) {
@@ -216,6 +233,7 @@ class BeamHistory {
     }
 
     int K_, blank_;
+    std::shared_ptr<const std::vector<float>> pending_;   // (kept across reset(): the graph stays attached)
     SeqTree seq_;
     PathTree path_;
     std::vector<Hyp> hyps_;

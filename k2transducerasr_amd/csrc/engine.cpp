@@ -716,7 +716,8 @@ void Engine::beam_device(const Ctx& c, const float* enc, int B, int Tp, long lon
 }
 
 // modified beam search resumed from saved hypotheses (streaming chunk; BeamResumeLayout{K, Tp} blocks on the device)
-void Engine::beam_resume_device(const Ctx& c, const float* enc, int B, int Tp, int K, const int* d_in, int* d_out, int* d_overflow) {
+void Engine::beam_resume_device(const Ctx& c, const float* enc, int B, int Tp, int K, const int* d_in, int* d_out, int* d_overflow,
+                                const BeamHwIO* hw) {
     BeamArgs a;
     a.enc = enc; a.out_w = model_->w("joiner.output_linear.weight");
     a.dproj_w = model_->w("joiner.decoder_proj.weight");
@@ -724,37 +725,55 @@ void Engine::beam_resume_device(const Ctx& c, const float* enc, int B, int Tp, i
     a.tokens = nullptr; a.timestamps = nullptr; a.n_tokens = nullptr; a.scores = nullptr; a.max_tokens = 0;
     a.overflow = d_overflow;
     a.rin = d_in; a.rout = d_out;
+    if (hw) {
+        a.hw_streams = hw->graphs; a.st_in = hw->st_in; a.st_out = hw->st_out;
+    }
     beam_search(c, decjoin(), a);
 }
 
 void Engine::beam_chunk_host(const float* enc, int B, int Tp, int K, const int* beam_in, int* beam_out) {
+    beam_chunk_impl(enc, B, Tp, K, beam_in, beam_out, nullptr);
+}
+void Engine::beam_chunk_host_hw(const float* enc, int B, int Tp, int K, const int* beam_in, int* beam_out, const BeamHwIO& hw) {
+    beam_chunk_impl(enc, B, Tp, K, beam_in, beam_out, &hw);
+}
+void Engine::beam_chunk_impl(const float* enc, int B, int Tp, int K, const int* beam_in, int* beam_out, const BeamHwIO* hw) {
     K2_REQUIRE(B > 0 && Tp > 0, "beam chunk: bad shape B=%d T'=%d", B, Tp);
     K2_REQUIRE(K >= 1 && K <= kMaxBeam, "beam chunk: beam %d out of range [1,%d]", K, kMaxBeam);
     const Config& cf = model_->cfg();
     K2_REQUIRE(!cf.ctc, "beam chunk: a CTC model has no transducer search");
     const BeamResumeLayout L{K, Tp};
-    // ONE upload [enc | in blocks] and ONE download [flag | out blocks]
+    // ONE upload [enc | in blocks | hotwords: states in, graphs] and ONE download [flag | out blocks | hotwords: states out]
     const int64_t nb_enc = (int64_t)sizeof(float) * B * Tp * cf.J, nb_in = (int64_t)sizeof(int) * B * L.in_ints(),
                   nb_out = (int64_t)sizeof(int) * B * L.out_ints();
-    const int64_t o_in = align_up(nb_enc, 16), o_ovf = align_up(o_in + nb_in, 16), in_bytes = o_ovf + 16;
+    const int64_t nb_st = hw ? (int64_t)sizeof(int) * B * K : 0, nb_g = hw ? (int64_t)sizeof(BeamHwStream) * B : 0;
+    const int64_t o_in = align_up(nb_enc, 16), o_st = align_up(o_in + nb_in, 16), o_g = align_up(o_st + nb_st, 16),
+                  o_ovf = align_up(o_g + nb_g, 16), in_bytes = o_ovf + 16;
     K2_HIP(hipSetDevice(device_));
     char* stage = static_cast<char*>(pinned_in(in_bytes));
     memcpy(stage, enc, (size_t)nb_enc);
     memcpy(stage + o_in, beam_in, (size_t)nb_in);
+    if (hw) {
+        memcpy(stage + o_st, hw->st_in, (size_t)nb_st);
+        memcpy(stage + o_g, hw->graphs, (size_t)nb_g);
+    }
     memset(stage + o_ovf, 0, 16);
     int* d_ovf = nullptr;
     run_sized([&](const Ctx& c) {
-        char* d = c.arena->take<char>(in_bytes + nb_out);
+        char* d = c.arena->take<char>(in_bytes + nb_out + nb_st);
         d_ovf = reinterpret_cast<int*>(d + o_ovf);
         if (!c.dry) K2_HIP(hipMemcpyAsync(d, stage, (size_t)in_bytes, hipMemcpyHostToDevice, c.stream));
+        const BeamHwIO dhw{reinterpret_cast<const BeamHwStream*>(d + o_g), reinterpret_cast<const int*>(d + o_st),
+                           reinterpret_cast<int*>(d + in_bytes + nb_out)};
         beam_resume_device(c, reinterpret_cast<const float*>(d), B, Tp, K, reinterpret_cast<const int*>(d + o_in),
-                           reinterpret_cast<int*>(d + in_bytes), d_ovf);
+                           reinterpret_cast<int*>(d + in_bytes), d_ovf, hw ? &dhw : nullptr);
     });
-    char* pin = static_cast<char*>(pinned(16 + nb_out));
-    K2_HIP(hipMemcpyAsync(pin, d_ovf, (size_t)(16 + nb_out), hipMemcpyDeviceToHost, stream_));
+    char* pin = static_cast<char*>(pinned(16 + nb_out + nb_st));
+    K2_HIP(hipMemcpyAsync(pin, d_ovf, (size_t)(16 + nb_out + nb_st), hipMemcpyDeviceToHost, stream_));
     K2_HIP(hipStreamSynchronize(stream_));
     if (*reinterpret_cast<int*>(pin)) failf(K2HIP_ERR_HIP, "beam chunk: a hypothesis outgrew its buffer");
     memcpy(beam_out, pin + 16, (size_t)nb_out);
+    if (hw) memcpy(hw->st_out, pin + 16 + nb_out, (size_t)nb_st);
 }
 
 // Back-off of the parted searches.  A search whose column slabs are not co-resident (other handles or processes on the GPU hold the

@@ -116,6 +116,17 @@ class Engine {
                           const int* beam_in, int* beam_out, const int* fifo_heads = nullptr);
     // operator level of the resumed search: enc [B, Tp, J] host, in / out blocks of BeamResumeLayout{K, Tp} (host)
     void beam_chunk_host(const float* enc, int B, int Tp, int K, const int* beam_in, int* beam_out);
+    // The two entry points above with per-stream hotword graphs (BeamArgs::hw_streams): side blocks of their own beside the
+    // BeamResumeLayout blocks, all host memory -- graphs [B] (device tables; all null = that stream is unbiased), st_in [B][K] the
+    // graph states of the saved hypotheses, st_out [B][K] those of the survivors.  They ride in the same upload / download.
+    struct BeamHwIO {
+        const BeamHwStream* graphs;
+        const int* st_in;
+        int* st_out;
+    };
+    void online_step_beam_hw(const int* slots, const float* const* chunks, const long long* plens, const int* nchunks, int B, int K,
+                             const int* beam_in, int* beam_out, const BeamHwIO& hw, const int* fifo_heads = nullptr);
+    void beam_chunk_host_hw(const float* enc, int B, int Tp, int K, const int* beam_in, int* beam_out, const BeamHwIO& hw);
 
     void set_instrument(bool on) { instrument_ = on; }
     const std::vector<GemmLaunchRec>& gemm_log() const { return gemm_log_; }
@@ -185,8 +196,11 @@ class Engine {
                     int* d_overflow);
     void beam_device(const Ctx& c, const float* enc, int B, int Tp, long long* d_tok, int* d_ts, int* d_n, int max_tokens,
                      int* d_overflow);
-    void beam_resume_device(const Ctx& c, const float* enc, int B, int Tp, int K, const int* d_in, int* d_out, int* d_overflow);
-    struct OnlineBeamIO { int K; const int* in; int* out; };
+    // hw (device pointers) or null: the unbiased search, today's launch
+    void beam_resume_device(const Ctx& c, const float* enc, int B, int Tp, int K, const int* d_in, int* d_out, int* d_overflow,
+                            const BeamHwIO* hw = nullptr);
+    void beam_chunk_impl(const float* enc, int B, int Tp, int K, const int* beam_in, int* beam_out, const BeamHwIO* hw);
+    struct OnlineBeamIO { int K; const int* in; int* out; const BeamHwIO* hw; };
     void online_step_impl(const int* slots, const float* const* chunks, const long long* hyps, const long long* plens, const int* nchunks,
                           int B, int64_t* tokens, int32_t* ts, int32_t* n_tokens, const int* fifo_heads, const OnlineBeamIO* beam);
     // LSTM transducer (lstm_engine.cpp)

@@ -472,6 +472,13 @@ bool greedy_loop_screens(const DecJoinW& w, int B, bool streaming, bool one_part
 // therefore keeps the launch (inputs are read-only, outputs are rewritten from scratch) and, on a timeout, runs it again with ONE
 // workgroup per stream -- no inter-workgroup wait, same tokens -- instead of failing the call.
 // arguments of the one-kernel modified beam search (beam.hip k_beam_loop); here because a repeatable launch is kept in GreedyLaunch
+// One stream's hotword graph as the search reads it: the dense tables on the device (BeamArgs::hw_*).  All null: this stream is
+// unbiased -- no bonus, its hypotheses stay in state 0.
+struct BeamHwStream {
+    const int* next = nullptr;
+    const float* bonus = nullptr;
+    const float* pending = nullptr;
+};
 struct BeamLoopArgs {
     const float* enc;   // [B, Tp, J]
     int Tp, K, cap;
@@ -492,10 +499,14 @@ struct BeamLoopArgs {
     // streaming resume (BeamResume below): per-stream in / out blocks, or null for the offline search
     const int* rin = nullptr;
     int* rout = nullptr;
-    // hotword biasing (HotwordTables below; offline search only) or null pointers
+    // hotword biasing (BeamArgs below) or null pointers: one graph for every stream (hw_*), or one per stream (hw_streams) with
+    // the saved hypotheses' states in / the survivors' states out (resume only)
     const int* hw_next = nullptr;
     const float* hw_bonus = nullptr;
     const float* hw_pending = nullptr;
+    const BeamHwStream* hw_streams = nullptr;
+    const int* st_in = nullptr;
+    int* st_out = nullptr;
 };
 struct GreedyLaunch {
     bool valid = false;  // a launch with inter-workgroup waits (parts > 1 / two beam slabs) that can be repeated without them
@@ -550,11 +561,15 @@ struct BeamState {       // device arrays; hypotheses double-buffered by frame p
     float *lp, *lp_next; // [B][K] hypothesis log-probs (-inf = empty slot)
     long long *ctx, *ctx_next;  // [B][K][2] decoder inputs
     int *nhyp, *nhyp_next;      // [B]
-    // hotword biasing (offline search only): the hypotheses' graph states [2][B][K] and the tables, or null
+    // hotword biasing: the hypotheses' graph states [2][B][K] and the tables (one graph, or hw_streams [B]: one per stream), or null;
+    // resume: the saved hypotheses' states st_in [B][K], the survivors' st_out [B][K]
     int* st = nullptr;
     const int* hw_next = nullptr;
     const float* hw_bonus = nullptr;
     const float* hw_pending = nullptr;
+    const BeamHwStream* hw_streams = nullptr;
+    const int* st_in = nullptr;
+    int* st_out = nullptr;
 };
 struct BeamArgs {
     const float* enc;    // [B, Tp, J]
@@ -572,7 +587,7 @@ struct BeamArgs {
     // every surviving hypothesis to rout [B][out_ints] instead of the best one to tokens / timestamps / n_tokens / scores
     const int* rin = nullptr;
     int* rout = nullptr;
-    // Hotword biasing (hotwords.h; semantics in include/k2hip.h), offline search only: the dense tables of the graph on the device --
+    // Hotword biasing (hotwords.h; semantics in include/k2hip.h): the dense tables of the graph on the device --
     // hw_next [S][V] the state after appending a token (the root after a committed match), hw_bonus [S][V] what the step adds to the
     // hypothesis' log-prob, hw_pending [S] what the final pick takes back from an unfinished match.  Every hypothesis carries its
     // state; the bonus of a selected candidate is added after the frame's selection and before the merges.  Null: the unbiased search
@@ -580,7 +595,16 @@ struct BeamArgs {
     const int* hw_next = nullptr;
     const float* hw_bonus = nullptr;
     const float* hw_pending = nullptr;
+    // The streaming form (with rin / rout): one graph PER STREAM, hw_streams [B] on the device (a stream without a graph: null
+    // tables), instead of hw_*; st_in [B][K] the graph states of the saved hypotheses, st_out [B][K] those of the survivors (0 for
+    // empty slots).  `best` of the out block is then picked on (lp - pending(state)) / length; the log-probs written keep the
+    // pending bonus (the match may complete in the next chunk).
+    const BeamHwStream* hw_streams = nullptr;
+    const int* st_in = nullptr;
+    int* st_out = nullptr;
 };
+// launches of the search since the process started, by instantiation: [0] HW = false, [1] HW = true (k2hip_debug.h)
+void beam_launch_counts(long long* plain, long long* hw);
 void beam_search(const Ctx& ctx, const DecJoinW& w, const BeamArgs& a);
 
 // ---- streaming (online.hip): device-resident per-stream caches indexed by slot ------------------

@@ -498,7 +498,15 @@ void Engine::online_step_beam(const int* slots, const float* const* chunks, cons
     K2_REQUIRE(K >= 1 && K <= kMaxBeam, "online beam search: beam %d out of range [1,%d]", K, kMaxBeam);
     K2_REQUIRE(!model_->cfg().ctc, "online beam search: a CTC model runs its own search");
     std::vector<long long> hyps(2 * (size_t)B, K2HIP_BLANK_ID);   // (the greedy search's context input; unused by the beam search)
-    OnlineBeamIO io{K, beam_in, beam_out};
+    OnlineBeamIO io{K, beam_in, beam_out, nullptr};
+    online_step_impl(slots, chunks, hyps.data(), plens, nchunks, B, nullptr, nullptr, nullptr, fifo_heads, &io);
+}
+void Engine::online_step_beam_hw(const int* slots, const float* const* chunks, const long long* plens, const int* nchunks, int B, int K,
+                                 const int* beam_in, int* beam_out, const BeamHwIO& hw, const int* fifo_heads) {
+    K2_REQUIRE(K >= 1 && K <= kMaxBeam, "online beam search: beam %d out of range [1,%d]", K, kMaxBeam);
+    K2_REQUIRE(!model_->cfg().ctc, "online beam search: a CTC model runs its own search");
+    std::vector<long long> hyps(2 * (size_t)B, K2HIP_BLANK_ID);
+    OnlineBeamIO io{K, beam_in, beam_out, &hw};
     online_step_impl(slots, chunks, hyps.data(), plens, nchunks, B, nullptr, nullptr, nullptr, fifo_heads, &io);
 }
 void Engine::online_step_impl(const int* slots, const float* const* chunks, const long long* hyps, const long long* plens, const int* nchunks,
@@ -518,13 +526,17 @@ void Engine::online_step_impl(const int* slots, const float* const* chunks, cons
     // overflow flag = 0], packed in pinned staging in the device block's layout (five small copies from pageable memory + a memset were
     // six blit launches of ~4 us each at the head of the step); ONE download: [tokens | timestamps | counts | overflow flag]
     // Under beam search the upload carries the streams' saved hypotheses and relation tables too (in front of the flag), and the
-    // download is [flag | the surviving hypotheses' out blocks] instead of the greedy tokens.
+    // download is [flag | the surviving hypotheses' out blocks] instead of the greedy tokens.  With hotword graphs attached the saved
+    // hypotheses' graph states and the streams' table pointers follow the in blocks, the survivors' states the out blocks.
     const BeamResumeLayout RL{beam ? beam->K : 1, Tp};
-    const int64_t nb_bin = beam ? (int64_t)sizeof(int) * RL.in_ints() * B : 0, nb_bout = beam ? (int64_t)sizeof(int) * RL.out_ints() * B : 0;
+    const BeamHwIO* bhw = beam ? beam->hw : nullptr;
+    const int64_t nb_bin = beam ? (int64_t)sizeof(int) * RL.in_ints() * B : 0;
+    const int64_t nb_hst = bhw ? (int64_t)sizeof(int) * beam->K * B : 0, nb_hg = bhw ? (int64_t)sizeof(BeamHwStream) * B : 0;
+    const int64_t nb_bout = beam ? (int64_t)sizeof(int) * RL.out_ints() * B + nb_hst : 0, o_hout = nb_bout - nb_hst;
     const int64_t nb_x = from_fifo ? 0 : (int64_t)sizeof(float) * chunk_floats * B;
     const int64_t o_plen = align_up(nb_x, 16), o_hyp = o_plen + 8 * (int64_t)B, o_slots = o_hyp + 16 * (int64_t)B, o_chunks = o_slots + 4 * (int64_t)B,
-                  o_heads = o_chunks + 4 * (int64_t)B, o_bin = align_up(o_heads + 4 * (int64_t)B, 16), o_ovf = align_up(o_bin + nb_bin, 16),
-                  in_bytes = o_ovf + 16;
+                  o_heads = o_chunks + 4 * (int64_t)B, o_bin = align_up(o_heads + 4 * (int64_t)B, 16), o_hst = align_up(o_bin + nb_bin, 16),
+                  o_hg = align_up(o_hst + nb_hst, 16), o_ovf = align_up(o_hg + nb_hg, 16), in_bytes = o_ovf + 16;
     char* stage = static_cast<char*>(pinned_in(in_bytes));
     if (!from_fifo)
         for (int b = 0; b < B; b++) memcpy(stage + (size_t)b * chunk_floats * sizeof(float), chunks[b], sizeof(float) * chunk_floats);
@@ -535,6 +547,10 @@ void Engine::online_step_impl(const int* slots, const float* const* chunks, cons
     if (from_fifo) memcpy(stage + o_heads, fifo_heads, sizeof(int) * B);
     else memset(stage + o_heads, 0, sizeof(int) * B);
     if (beam) memcpy(stage + o_bin, beam->in, (size_t)nb_bin);
+    if (bhw) {
+        memcpy(stage + o_hst, bhw->st_in, (size_t)nb_hst);
+        memcpy(stage + o_hg, bhw->graphs, (size_t)nb_hg);
+    }
     memset(stage + o_ovf, 0, 16);
     const int64_t nb_tok = beam ? nb_bout : (int64_t)B * Tp * 8, nb_ts = beam ? 0 : (int64_t)B * Tp * 4, nb_n = beam ? 0 : (int64_t)B * 4;
     run_sized([&](const Ctx& c) {
@@ -555,6 +571,9 @@ void Engine::online_step_impl(const int* slots, const float* const* chunks, cons
         int* d_heads = reinterpret_cast<int*>(d_in + o_heads);
         const int* d_bin = reinterpret_cast<const int*>(d_in + o_bin);
         int* d_bout = reinterpret_cast<int*>(d_out);
+        const BeamHwIO dhw{reinterpret_cast<const BeamHwStream*>(d_in + o_hg), reinterpret_cast<const int*>(d_in + o_hst),
+                           reinterpret_cast<int*>(d_out + o_hout)};
+        const BeamHwIO* d_hw = bhw ? &dhw : nullptr;
         if (!c.dry) {
             K2_HIP(hipEventRecord(ev_[0], c.stream));
             K2_HIP(hipMemcpyAsync(d_in, stage, (size_t)in_bytes, hipMemcpyHostToDevice, c.stream));
@@ -572,7 +591,7 @@ void Engine::online_step_impl(const int* slots, const float* const* chunks, cons
             K2_REQUIRE(tc == Tp, "internal: chunk yields %d frames, expected %d", tc, Tp);
             if (ev_ok) K2_HIP(hipEventRecord(ev_[3], c.stream));
             if (beam) {
-                beam_resume_device(c, enc, B, Tp, beam->K, d_bin, d_bout, d_ovf);
+                beam_resume_device(c, enc, B, Tp, beam->K, d_bin, d_bout, d_ovf, d_hw);
                 if (ev_ok) K2_HIP(hipEventRecord(ev_[4], c.stream));
                 return;
             }
@@ -593,7 +612,7 @@ void Engine::online_step_impl(const int* slots, const float* const* chunks, cons
             return;
         }
         if (beam) {   // modified beam search resumed from the streams' saved hypotheses, on the tick's encoder buffer
-            beam_resume_device(c, enc, B, Tp, beam->K, d_bin, d_bout, d_ovf);
+            beam_resume_device(c, enc, B, Tp, beam->K, d_bin, d_bout, d_ovf, d_hw);
             if (ev_ok) K2_HIP(hipEventRecord(ev_[4], c.stream));
             return;
         }
@@ -611,7 +630,8 @@ void Engine::online_step_impl(const int* slots, const float* const* chunks, cons
         K2_HIP(hipEventRecord(ev_[5], stream_));
         K2_HIP(hipStreamSynchronize(stream_));
         if (*reinterpret_cast<int*>(pin)) failf(K2HIP_ERR_HIP, "online beam search: a hypothesis outgrew its buffer");
-        memcpy(beam->out, pin + 16, (size_t)nb_bout);
+        memcpy(beam->out, pin + 16, (size_t)o_hout);
+        if (bhw) memcpy(bhw->st_out, pin + 16 + o_hout, (size_t)nb_hst);
     } else {
         finish_tokens(d_tok, d_ts, d_n, d_ovf, B, Tp, tokens, ts, n_tokens);
     }

@@ -1,12 +1,14 @@
 """Streaming tick under modified beam search next to greedy, on the same audio.
 
-    python tools/stream_beam_bench.py [preset] [streams] [seconds] [beam]      (defaults: zipformer2-streaming-zh 128 20 4)
+    python tools/stream_beam_bench.py [preset] [streams] [seconds] [beam] [--hotwords N]   (defaults: zipformer2-streaming-zh 128 20 4)
 
 N streams of the synthetic `preset` model each buffer an utterance of `seconds` s; the tool decodes all of them chunk by chunk
 (one k2hip_online_step per tick over the whole group) once with greedy_search and once with modified_beam_search, reports the
 median ms per tick of each, and holds the first few streams' beam results to the CPU oracle (k2o_modified_beam_search over the
 oracle's own concatenated chunks; a difference is excused only where the oracle's margin at the first differing frame is below
-LOGIT_TOL).  One JSON line on stdout."""
+LOGIT_TOL).  --hotwords N: two more beam runs with a hotword graph attached to EVERY stream -- an empty one (the biased kernels with
+every bonus 0) and N phrases of 2 - 5 tokens drawn from the unbiased beam run's output (as tools/hotword_bench.py draws them) -- and a
+second unbiased run behind them, their tick times printed beside the unbiased and the greedy one.  One JSON line on stdout."""
 import json
 import os
 import sys
@@ -21,17 +23,23 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 from k2transducerasr_amd import OnlineRecognizer  # noqa: E402
 from k2transducerasr_amd.synth import synth_utterance, write_synthetic_model  # noqa: E402
 
-preset = sys.argv[1] if len(sys.argv) > 1 else "zipformer2-streaming-zh"
-N = int(sys.argv[2]) if len(sys.argv) > 2 else 128
-secs = float(sys.argv[3]) if len(sys.argv) > 3 else 20.0
-beam = int(sys.argv[4]) if len(sys.argv) > 4 else 4
+argv = sys.argv[1:]
+n_hotwords = None
+if "--hotwords" in argv:
+    i = argv.index("--hotwords")
+    n_hotwords = int(argv[i + 1])
+    del argv[i: i + 2]
+preset = argv[0] if len(argv) > 0 else "zipformer2-streaming-zh"
+N = int(argv[1]) if len(argv) > 1 else 128
+secs = float(argv[2]) if len(argv) > 2 else 20.0
+beam = int(argv[3]) if len(argv) > 3 else 4
 CHECK = 3
 DISTINCT = 8
 
 
-def run(rec, feats, method, k):
+def run(rec, feats, method, k, hotwords=None):
     rec.model.set_decoding_method(method, k)
-    hs = [rec.create_online_stream() for _ in feats]
+    hs = [rec.create_online_stream(hotwords=hotwords) for _ in feats]
     for h, f in zip(hs, feats):
         h.add_features(f)
     group = rec.batch(hs)
@@ -61,6 +69,23 @@ def main():
         run(rec, feats[: min(N, 8)], "greedy_search", 0)          # warm-up: arenas, decoder tables
         g_ms, _ = run(rec, feats, "greedy_search", 0)
         b_ms, b_res = run(rec, feats, "modified_beam_search", beam)
+        hw_out = {}
+        if n_hotwords is not None:
+            from hotword_twin import SCORE, draw_phrases
+            from k2transducerasr_amd import Hotwords
+            V = rec.model.vocab_size
+            phrases = draw_phrases(b_res[:DISTINCT], n_hotwords, np.random.default_rng(100), min_len=2, max_len=5)
+            empty, full = Hotwords([], SCORE, V), Hotwords(phrases, SCORE, V)
+            e_ms, e_res = run(rec, feats, "modified_beam_search", beam, empty)
+            h_ms, h_res = run(rec, feats, "modified_beam_search", beam, full)
+            b2_ms, _ = run(rec, feats, "modified_beam_search", beam)
+            if e_res != b_res:
+                raise SystemExit("an empty hotword graph changed the results")
+            hw_out = {"hotword_phrases": len(phrases), "hotword_states": full.num_states,
+                      "beam_empty_graph_ms_per_tick": round(float(np.median(e_ms)), 3),
+                      "beam_hotwords_ms_per_tick": round(float(np.median(h_ms)), 3),
+                      "beam_again_ms_per_tick": round(float(np.median(b2_ms)), 3),
+                      "streams_moved_by_the_bias": int(sum(a != b for a, b in zip(h_res, b_res)))}
         import parity
         from test_online_beam_gpu import oracle_frames
         exact = excused = 0
@@ -80,7 +105,7 @@ def main():
         print(json.dumps({"preset": preset, "streams": N, "seconds": secs, "beam": beam, "ticks": len(b_ms),
                           "greedy_ms_per_tick": round(float(np.median(g_ms)), 3), "beam_ms_per_tick": round(float(np.median(b_ms)), 3),
                           "beam_over_greedy": round(float(np.median(b_ms) / np.median(g_ms)), 3),
-                          "oracle_checked": min(CHECK, N), "oracle_exact": exact, "oracle_excused": excused}))
+                          "oracle_checked": min(CHECK, N), "oracle_exact": exact, "oracle_excused": excused, **hw_out}))
 
 
 if __name__ == "__main__":
