@@ -72,6 +72,19 @@ namespace K2TransducerAsr.Hip
         [DllImport(Lib)] internal static extern int k2hip_beam_stream_get_tokens(IntPtr stream, long[] tokens, int cap);
         [DllImport(Lib)] internal static extern int k2hip_beam_stream_get_timestamps(IntPtr stream, int[] timestamps, int cap);
         [DllImport(Lib)] internal static extern int k2hip_beam_stream_get_score(IntPtr stream, out float score);
+        // N-best hypotheses and token log-probs of the modified beam search (k2hip.h "N-best hypotheses and token log-probs"; INTEGRATION.md)
+        [DllImport(Lib)] internal static extern int k2hip_set_nbest(IntPtr model, int n);
+        [DllImport(Lib)] internal static extern int k2hip_beam_search_nbest(IntPtr model, float[] encOut, int B, int Tprime, int beam, int nbest, long[] tokens,
+                                                                            int[] timestamps, float[] tokenLogProbs, int[] nTokens, int[] nHyps, float[] scores, int maxTokens);
+        [DllImport(Lib)] internal static extern int k2hip_offline_stream_num_alternatives(IntPtr stream);
+        [DllImport(Lib)] internal static extern int k2hip_offline_stream_get_alternative(IntPtr stream, int i, long[] tokens, int[] timestamps, float[] tokenLogProbs, int cap, out int n, out float score);
+        [DllImport(Lib)] internal static extern int k2hip_offline_stream_get_token_log_probs(IntPtr stream, float[] dst, int cap);
+        [DllImport(Lib)] internal static extern int k2hip_online_stream_num_alternatives(IntPtr stream);
+        [DllImport(Lib)] internal static extern int k2hip_online_stream_get_alternative(IntPtr stream, int i, long[] tokens, int[] timestamps, float[] tokenLogProbs, int cap, out int n, out float score);
+        [DllImport(Lib)] internal static extern int k2hip_online_stream_get_token_log_probs(IntPtr stream, float[] dst, int cap);
+        [DllImport(Lib)] internal static extern int k2hip_beam_stream_num_alternatives(IntPtr stream);
+        [DllImport(Lib)] internal static extern int k2hip_beam_stream_get_alternative(IntPtr stream, int i, long[] tokens, int[] timestamps, float[] tokenLogProbs, int cap, out int n, out float score);
+        [DllImport(Lib)] internal static extern int k2hip_beam_stream_get_token_log_probs(IntPtr stream, float[] dst, int cap);
 
         [DllImport(Lib)] internal static extern int k2hip_model_meta(IntPtr model, string key, byte[] buf, int cap);
         [DllImport(Lib)] internal static extern int k2hip_set_decoding_method(IntPtr model, string method, int beam);

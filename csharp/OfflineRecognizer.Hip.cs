@@ -93,11 +93,64 @@ namespace K2TransducerAsr
             _offlineInputEntity.SpeechLength = (int)K2Hip.k2hip_offline_stream_speech_length(HipStream);
             if (_offlineInputEntity.SpeechLength == 0) _offlineInputEntity.Speech = null;
         }
+
+        // N-best and token confidences (k2hip.h "N-best hypotheses and token log-probs"; on after the recognizer's SetNbest(n > 1)):
+        // the stream's alternatives in pick order -- entry 0 is the result Tokens / Timestamps report -- each with its tokens (no blank
+        // prefix), frame indexes, token log-probs (unbiased by hotwords, <= 0) and finalized log-prob.
+        public sealed class Alternative
+        {
+            public long[] Tokens;
+            public int[] Timestamps;
+            public float[] TokenLogProbs;
+            public float Score;
+        }
+        public int NumAlternatives
+        {
+            get
+            {
+                if (HipStream == IntPtr.Zero) throw new InvalidOperationException("NumAlternatives: not a libk2hip stream");
+                int n = K2Hip.k2hip_offline_stream_num_alternatives(HipStream);
+                if (n < 0) K2Hip.Check(n, "num_alternatives failed");
+                return n;
+            }
+        }
+        public Alternative GetAlternative(int i)
+        {
+            if (HipStream == IntPtr.Zero) throw new InvalidOperationException("GetAlternative: not a libk2hip stream");
+            // the length first (no buffer is written with cap = 0 unless the alternative is empty), then the copy
+            int rc = K2Hip.k2hip_offline_stream_get_alternative(HipStream, i, null, null, null, int.MaxValue, out int n, out float score);
+            K2Hip.Check(rc, "get_alternative failed");
+            var a = new Alternative { Tokens = new long[n], Timestamps = new int[n], TokenLogProbs = new float[n], Score = score };
+            if (n > 0)
+                K2Hip.Check(K2Hip.k2hip_offline_stream_get_alternative(HipStream, i, a.Tokens, a.Timestamps, a.TokenLogProbs, n, out n, out score), "get_alternative failed");
+            return a;
+        }
+        public List<Alternative> Alternatives
+        {
+            get
+            {
+                var list = new List<Alternative>();
+                for (int i = 0, n = NumAlternatives; i < n; i++) list.Add(GetAlternative(i));
+                return list;
+            }
+        }
+        // token log-probs of the best result, parallel to its emitted tokens
+        public float[] TokenLogProbs => GetAlternative(0).TokenLogProbs;
     }
 
     public partial class OfflineRecognizer
     {
         private bool _hipSamples;   // the fused route: streams own native handles, the fbank runs on the GPU inside GetResults
+
+        // N-best: n > 1 makes GetResults under "modified_beam_search" leave up to n alternatives, each with its token log-probs, on
+        // every stream (OfflineStream.Alternatives / TokenLogProbs); 1 = off.  GetResult (the single-stream greedy path) is refused
+        // natively while n > 1.
+        public void SetNbest(int n)
+        {
+            if (!(_offlineProj is OfflineProjOfHip proj)) throw new InvalidOperationException("SetNbest: not a libk2hip recognizer");
+            K2Hip.Check(K2Hip.k2hip_set_nbest(proj.Handle, n), "SetNbest failed");
+        }
+        public List<OfflineStream.Alternative> GetAlternatives(OfflineStream stream) { return stream.Alternatives; }
 
         // the constructor's early branch (see the header): everything :30-68 does, for a .k2w container
         private void InitHip(string encoderFilePath, string decoderFilePath, string tokensFilePath, string decodingMethod, int sampleRate, int featureDim)

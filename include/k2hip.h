@@ -377,6 +377,56 @@ int32_t k2hip_set_hotwords(k2hip_model_t* model, const k2hip_hotwords_t* hw);
 int32_t k2hip_online_stream_set_hotwords(k2hip_online_stream_t* s, const k2hip_hotwords_t* hw);
 int32_t k2hip_beam_stream_set_hotwords(k2hip_beam_stream_t* s, const k2hip_hotwords_t* hw);
 
+/* ---- N-best hypotheses and token log-probs of the modified beam search ---------------------------------------------------------
+ * Token log-prob: when a selected candidate (hypothesis k, token v), v outside {blank, unk}, is appended at frame t, its token
+ * log-prob is the float32 term (logit[k][v] - max_k) - lse_k the step forms before it adds the hypothesis' log-prob -- that term
+ * itself, not a difference of scores.  It is UNBIASED (a hotword bonus is never part of it) and <= 0.  It travels with the
+ * timestamp: when candidates that spell the same sequence merge, the first-inserted hypothesis keeps its token log-probs exactly as
+ * it keeps its timestamps.
+ * N-best: after the last frame the surviving hypotheses (at most `beam`, pairwise distinct sequences) are ordered by the quantity of
+ * the final pick, (log-prob - pending(state)) / (length + 2) (pending only with hotwords attached), descending, ties in insertion
+ * order.  Entry 0 is therefore the result the search returns anyway: same tokens, timestamps and score.  Every entry carries its
+ * tokens (no [blank, blank] prefix), timestamps, token log-probs and its FINALIZED log-prob (not the normalised value).  nbest is
+ * in 1..8; asking for more than survive returns what survives.
+ * Streaming: after every step a stream's alternatives are what the offline search gives over all frames so far (the contract of the
+ * best result); they may be revised from step to step.  Their scores use the pending table attached when they are read.
+ * What a stream holds before its first result, after a reset and after a failed call (offline streams: a failed GetResults; the
+ * streaming calls change no stream when they fail) is the start state: ONE empty alternative with score 0.
+ *
+ * k2hip_set_nbest(model, n): n = 1 (the default) is off -- nothing is computed or kept beyond the best hypothesis.  With n > 1 the
+ * synchronous entries k2hip_offline_recognizer_get_results, k2hip_online_step and k2hip_beam_search_chunk keep up to n alternatives
+ * per stream, each with its token log-probs (token log-probs are recorded for the frames searched while n > 1; 0 for frames
+ * searched before).  Needs modified_beam_search (K2HIP_ERR_INVALID under greedy_search, K2HIP_ERR_UNSUPPORTED for a CTC model), and
+ * no submitted batch in flight.  While n > 1: the pipelined k2hip_offline_submit_* / k2hip_offline_wait return K2HIP_ERR_INVALID (they
+ * have one result per stream), and so does k2hip_offline_recognizer_get_result (the single-stream path is greedy search). */
+int32_t k2hip_set_nbest(k2hip_model_t* model, int32_t n /* 1..8 */);
+/* operator level: k2hip_beam_search that returns the list.  tokens / timestamps / token_log_probs [B][nbest][max_tokens],
+ * n_tokens / scores [B][nbest], n_hyps [B] = entries written for the stream (<= min(beam, nbest)); what lies behind them is not
+ * touched.  K2HIP_ERR_CAPACITY if any returned entry is longer than max_tokens -- also where the best one alone would fit: the
+ * overflow rule of the single result holds per entry, and one over-long entry fails the whole call (the same holds for the
+ * synchronous entries under k2hip_set_nbest(n > 1)).  Independent of k2hip_set_nbest. */
+int32_t k2hip_beam_search_nbest(k2hip_model_t* model, const float* enc_out, int32_t B, int32_t Tprime, int32_t beam, int32_t nbest,
+                                int64_t* tokens, int32_t* timestamps, float* token_log_probs, int32_t* n_tokens, int32_t* n_hyps,
+                                float* scores, int32_t max_tokens);
+/* Per stream.  num_alternatives: the count (>= 1; -1 for NULL, for online streams a negative error code under greedy_search).
+ * get_alternative(i): tokens / timestamps / token_log_probs [cap] (each may be NULL), *n = its length, *score = its finalized
+ * log-prob; K2HIP_ERR_CAPACITY if cap is too small (nothing is written), K2HIP_ERR_INVALID for i outside the list.
+ * get_token_log_probs: those of the best result, parallel to its timestamps; returns the count, or a negative error code
+ * (K2HIP_ERR_CAPACITY: nothing written).  Offline streams: alternatives' timestamps are frame indexes of the utterance, tokens carry
+ * no seed prefix. */
+int32_t k2hip_offline_stream_num_alternatives(const k2hip_offline_stream_t* s);
+int32_t k2hip_offline_stream_get_alternative(const k2hip_offline_stream_t* s, int32_t i, int64_t* tokens, int32_t* timestamps,
+                                             float* token_log_probs, int32_t cap, int32_t* n, float* score);
+int32_t k2hip_offline_stream_get_token_log_probs(const k2hip_offline_stream_t* s, float* out, int32_t cap);
+int32_t k2hip_online_stream_num_alternatives(const k2hip_online_stream_t* s);
+int32_t k2hip_online_stream_get_alternative(const k2hip_online_stream_t* s, int32_t i, int64_t* tokens, int32_t* timestamps,
+                                            float* token_log_probs, int32_t cap, int32_t* n, float* score);
+int32_t k2hip_online_stream_get_token_log_probs(const k2hip_online_stream_t* s, float* out, int32_t cap);
+int32_t k2hip_beam_stream_num_alternatives(const k2hip_beam_stream_t* s);
+int32_t k2hip_beam_stream_get_alternative(const k2hip_beam_stream_t* s, int32_t i, int64_t* tokens, int32_t* timestamps,
+                                          float* token_log_probs, int32_t cap, int32_t* n, float* score);
+int32_t k2hip_beam_stream_get_token_log_probs(const k2hip_beam_stream_t* s, float* out, int32_t cap);
+
 /* OfflineRecognizer.GetResults (:85-91) minus DecodeMulti: runs the fused batch
  * path on the streams' feature buffers, stores Tokens/Timestamps in each stream
  * (including the reference's 2*B-blank prefix) and calls RemoveSamples (:294). */

@@ -406,10 +406,32 @@ class Model:
         self._chk(self._L.k2hip_ctc_greedy(self._h, _f(e), B, Tp, _i(fo), _l(tok), _i(ts), _i(n), Tp, _i(tb)))
         return self._unpack(tok, ts, n), tb
 
-    def beam_search(self, enc_out, beam: int = 4, want_scores: bool = False):
-        """modified beam search over a host encoder_out [B,T',J] (k2hip_beam_search)"""
+    def set_nbest(self, n: int = 1):
+        """k2hip_set_nbest: n > 1 makes the synchronous modified-beam-search entries keep up to n alternatives per stream, each with
+        its token log-probs (streams' .alternatives() / .token_log_probs()); 1 = off"""
+        self._L.k2hip_set_nbest.argtypes = [C.c_void_p, C.c_int32]
+        self._chk(self._L.k2hip_set_nbest(self._h, n))
+
+    def beam_search(self, enc_out, beam: int = 4, want_scores: bool = False, nbest: Optional[int] = None, want_token_log_probs: bool = False):
+        """modified beam search over a host encoder_out [B,T',J] (k2hip_beam_search).  With nbest = N and / or want_token_log_probs
+        (k2hip_beam_search_nbest): per stream a list of up to N alternatives in pick order (entry 0 = the plain call's result), each a
+        dict(tokens, timestamps, token_log_probs, score); without nbest only the best one's dict is returned per stream."""
         e = _f32(enc_out)
         B, Tp, _ = e.shape
+        if nbest is not None or want_token_log_probs:
+            N = 1 if nbest is None else nbest
+            M = max(N, 1)
+            tok = np.zeros((B, M, Tp), np.int64)
+            ts = np.zeros((B, M, Tp), np.int32)
+            yp = np.zeros((B, M, Tp), np.float32)
+            n = np.zeros((B, M), np.int32)
+            nh = np.zeros(B, np.int32)
+            sc = np.zeros((B, M), np.float32)
+            self._L.k2hip_beam_search_nbest.argtypes = [C.c_void_p, fp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, lp, ip, fp, ip, ip, fp, C.c_int32]
+            self._chk(self._L.k2hip_beam_search_nbest(self._h, _f(e), B, Tp, beam, N, _l(tok), _i(ts), _f(yp), _i(n), _i(nh), _f(sc), Tp))
+            out = [[dict(tokens=tok[b, i, : n[b, i]].tolist(), timestamps=ts[b, i, : n[b, i]].tolist(), token_log_probs=yp[b, i, : n[b, i]].copy(),
+                         score=float(sc[b, i])) for i in range(nh[b])] for b in range(B)]
+            return out if nbest is not None else [alts[0] for alts in out]
         tok = np.zeros((B, Tp), np.int64)
         ts = np.zeros((B, Tp), np.int32)
         n = np.zeros(B, np.int32)
@@ -562,6 +584,45 @@ class Model:
         return self._unpack(tok, ts, n)
 
 
+def _alternatives(model, L, prefix, h):
+    """a stream's alternatives in pick order: [dict(tokens, timestamps, token_log_probs, score)] (entry 0 = the best result)"""
+    num, get = getattr(L, prefix + "_num_alternatives"), getattr(L, prefix + "_get_alternative")
+    num.argtypes = [C.c_void_p]
+    get.argtypes = [C.c_void_p, C.c_int32, lp, ip, fp, C.c_int32, ip, fp]
+    count = num(h)
+    if count < 0:
+        model._chk(count)
+    out = []
+    for i in range(count):
+        n, sc = C.c_int32(0), C.c_float(0)
+        cap = 64
+        while True:
+            tok, ts, yp = np.zeros(cap, np.int64), np.zeros(cap, np.int32), np.zeros(cap, np.float32)
+            rc = get(h, i, _l(tok), _i(ts), _f(yp), cap, C.byref(n), C.byref(sc))
+            if rc == -5 and cap < (1 << 24):   # K2HIP_ERR_CAPACITY: nothing was written
+                cap *= 8
+                continue
+            model._chk(rc)
+            break
+        out.append(dict(tokens=tok[: n.value].tolist(), timestamps=ts[: n.value].tolist(), token_log_probs=yp[: n.value].copy(), score=float(sc.value)))
+    return out
+
+
+def _token_log_probs(model, L, prefix, h) -> np.ndarray:
+    get = getattr(L, prefix + "_get_token_log_probs")
+    get.argtypes = [C.c_void_p, fp, C.c_int32]
+    cap = 64
+    while True:
+        out = np.zeros(cap, np.float32)
+        rc = get(h, _f(out), cap)
+        if rc == -5 and cap < (1 << 24):
+            cap *= 8
+            continue
+        if rc < 0:
+            model._chk(rc)
+        return out[:rc].copy()
+
+
 class OfflineStream:
     """OfflineStream.cs:7-99."""
 
@@ -612,6 +673,13 @@ class OfflineStream:
         self._m._chk(self._L.k2hip_offline_stream_get_timestamps(self._h, _i(out), n))
         return out[:n].tolist()
 
+    def alternatives(self):
+        """the N-best list of the last get_results made with Model.set_nbest(n > 1) (k2hip_offline_stream_*_alternative*)"""
+        return _alternatives(self._m, self._L, "k2hip_offline_stream", self._h)
+
+    def token_log_probs(self) -> np.ndarray:
+        return _token_log_probs(self._m, self._L, "k2hip_offline_stream", self._h)
+
 
 class OfflineRecognizer:
     """OfflineRecognizer.cs:12-91 on the HIP backend; decoding_method "greedy_search" (the reference's only method) or
@@ -619,9 +687,11 @@ class OfflineRecognizer:
     hotwords_score per matched token (sherpa's hotwords_file / hotwords_score); it biases modified_beam_search only."""
 
     def __init__(self, weights_path: str, device: int = 0, decoding_method: str = "greedy_search", beam: int = 4, hotwords=None,
-                 hotwords_score: float = 1.5):
+                 hotwords_score: float = 1.5, nbest: int = 1):
         self.model = Model(weights_path, device)
         self.model.set_decoding_method(decoding_method, beam)
+        if nbest != 1:   # (streams then carry .alternatives() / .token_log_probs() after get_results)
+            self.model.set_nbest(nbest)
         if hotwords is not None:
             if not isinstance(hotwords, Hotwords):
                 hotwords = Hotwords(hotwords, hotwords_score, self.model.vocab_size)
@@ -763,6 +833,13 @@ class OnlineStream:
         self._m._chk(self._L.k2hip_online_stream_get_score(self._h, C.byref(out)))
         return out.value
 
+    def alternatives(self):
+        """the stream's current hypotheses under modified_beam_search, up to Model.set_nbest's n, in pick order"""
+        return _alternatives(self._m, self._L, "k2hip_online_stream", self._h)
+
+    def token_log_probs(self) -> np.ndarray:
+        return _token_log_probs(self._m, self._L, "k2hip_online_stream", self._h)
+
     @property
     def processed_len(self) -> int:
         self._L.k2hip_online_stream_processed_len.restype = C.c_int64
@@ -892,6 +969,13 @@ class BeamStream:
         out = C.c_float()
         self._m._chk(self._L.k2hip_beam_stream_get_score(self._h, C.byref(out)))
         return out.value
+
+    def alternatives(self):
+        """the stream's current hypotheses, up to Model.set_nbest's n, in pick order (k2hip_beam_stream_*_alternative*)"""
+        return _alternatives(self._m, self._L, "k2hip_beam_stream", self._h)
+
+    def token_log_probs(self) -> np.ndarray:
+        return _token_log_probs(self._m, self._L, "k2hip_beam_stream", self._h)
 
 
 class OnlineRecognizer:

@@ -96,6 +96,8 @@ struct k2hip_model {
     std::vector<PinVec> wav_pool;   // (declared behind `engine`: released first)
     // the hotword tables on the device (k2hip_set_hotwords): one allocation [next | bonus | pending], or null
     void* hw_dev = nullptr;
+    // k2hip_set_nbest: 1 = off (the engine keeps nothing beyond the best hypothesis), n > 1 = alternatives and token log-probs are kept
+    std::atomic<int> nbest{1};
     // the graphs attached to this model's streams (HwResident), by serial number; hw_uploads counts the uploads (k2hip_debug.h)
     std::map<uint64_t, std::weak_ptr<HwResident>> hw_cache;
     int hw_uploads = 0;
@@ -138,6 +140,9 @@ struct k2hip_offline_stream {
     PinVec wav;
     std::vector<int64_t> tokens;   // Tokens, initialised to [blank, blank] (:34)
     std::vector<int32_t> timestamps;
+    // N-best of the last k2hip_offline_recognizer_get_results made with k2hip_set_nbest(n > 1); otherwise the start state: one empty
+    // alternative with score 0
+    std::vector<BeamAlt> alts = std::vector<BeamAlt>(1);
     int32_t frame_offset = 0;        // FrameOffset (:39), read by the CTC search (OfflineRecognizer.cs:376,402)
     int32_t num_trailing_blank = 0;  // NumTrailingBlank (:40)
 };
@@ -695,6 +700,92 @@ int32_t k2hip_last_scores(k2hip_model_t* model, float* scores, int32_t B) {
         memcpy(scores, model->engine.last_scores().data(), sizeof(float) * B);
     });
 }
+int32_t k2hip_set_nbest(k2hip_model_t* model, int32_t n) {
+    return guard([&] {
+        NEED(model);
+        K2_REQUIRE(n >= 1 && n <= kMaxBeam, "set_nbest: n = %d out of range [1,%d]", n, kMaxBeam);
+        Engine& e = model->engine;
+        if (n > 1 && e.model().cfg().ctc) failf(K2HIP_ERR_UNSUPPORTED, "set_nbest: a CTC model has no beam search to take alternatives from");
+        EngineLock lk(e);
+        K2_REQUIRE(n == 1 || e.beam() > 0, "set_nbest: alternatives come from modified_beam_search; the model decodes with greedy_search "
+                                           "(k2hip_set_decoding_method first)");
+        K2_REQUIRE(e.batches_in_flight() == 0, "set_nbest: %d submitted batches are in flight; wait for them first", e.batches_in_flight());
+        e.set_nbest(n > 1 ? n : 0);
+        model->nbest = n;
+    });
+}
+// the alternatives of a stream (empty list: the start state) through the getters' common rules
+static void alt_get(const std::vector<BeamAlt>& alts, int32_t i, int64_t* tokens, int32_t* timestamps, float* token_log_probs, int32_t cap,
+                    int32_t* n, float* score) {
+    K2_REQUIRE(i >= 0 && i < (int32_t)alts.size(), "alternative %d of %zu", i, alts.size());
+    const BeamAlt& a = alts[(size_t)i];
+    if ((int64_t)a.tokens.size() > cap) failf(K2HIP_ERR_CAPACITY, "alternative %d holds %zu tokens", i, a.tokens.size());
+    if (!a.tokens.empty()) {
+        if (tokens) memcpy(tokens, a.tokens.data(), sizeof(int64_t) * a.tokens.size());
+        if (timestamps) memcpy(timestamps, a.timestamps.data(), sizeof(int32_t) * a.timestamps.size());
+        if (token_log_probs) memcpy(token_log_probs, a.token_log_probs.data(), sizeof(float) * a.token_log_probs.size());
+    }
+    if (n) *n = (int32_t)a.tokens.size();
+    if (score) *score = a.score;
+}
+static int32_t yp_get(const std::vector<float>& yp, float* out, int32_t cap) {
+    int32_t count = 0;
+    const int32_t rc = guard([&] {
+        if ((int64_t)yp.size() > cap) failf(K2HIP_ERR_CAPACITY, "the result holds %zu token log-probs", yp.size());
+        if (!yp.empty()) {
+            NEED(out);
+            memcpy(out, yp.data(), sizeof(float) * yp.size());
+        }
+        count = (int32_t)yp.size();
+    });
+    return rc < 0 ? rc : count;
+}
+// entry (b, i) of the engine's last N-best as a BeamAlt
+static BeamAlt alt_of(const Engine::NbestHost& h, int b, int i) {
+    BeamAlt a;
+    const size_t e = (size_t)b * h.N + i, o = e * h.max_tokens, len = (size_t)h.n_tokens[e];
+    a.tokens.assign(h.tokens.begin() + o, h.tokens.begin() + o + len);
+    a.timestamps.assign(h.timestamps.begin() + o, h.timestamps.begin() + o + len);
+    a.token_log_probs.assign(h.token_log_probs.begin() + o, h.token_log_probs.begin() + o + len);
+    a.score = h.scores[e];
+    return a;
+}
+int32_t k2hip_beam_search_nbest(k2hip_model_t* model, const float* enc_out, int32_t B, int32_t Tprime, int32_t beam, int32_t nbest,
+                                int64_t* tokens, int32_t* timestamps, float* token_log_probs, int32_t* n_tokens, int32_t* n_hyps, float* scores,
+                                int32_t max_tokens) {
+    return guard([&] {
+        NEED(model); NEED(enc_out); NEED(tokens); NEED(timestamps); NEED(token_log_probs); NEED(n_tokens); NEED(n_hyps); NEED(scores);
+        K2_REQUIRE(beam >= 1 && beam <= kMaxBeam, "beam search: beam %d out of range [1,%d]", beam, kMaxBeam);
+        K2_REQUIRE(nbest >= 1 && nbest <= kMaxBeam, "beam search: nbest %d out of range [1,%d]", nbest, kMaxBeam);
+        K2_REQUIRE(B > 0 && Tprime > 0 && max_tokens > 0, "beam search: bad shape B=%d T'=%d max_tokens=%d", B, Tprime, max_tokens);
+        Engine& e = model->engine;
+        if (e.model().cfg().ctc) failf(K2HIP_ERR_UNSUPPORTED, "beam search: a CTC model has no transducer search");
+        EngineLock lk(e);
+        struct Restore {
+            Engine& e; int beam, nbest;
+            ~Restore() { e.set_beam(beam); e.set_nbest(nbest); }
+        } restore{e, e.beam(), e.nbest()};
+        e.set_beam(beam);
+        e.set_nbest(nbest);
+        // (the single result goes to scratch: entry 0 of the list is that result)
+        std::vector<int64_t> tok1((size_t)B * max_tokens);
+        std::vector<int32_t> ts1((size_t)B * max_tokens), n1((size_t)B);
+        e.greedy_host(enc_out, B, Tprime, false, tok1.data(), ts1.data(), n1.data(), max_tokens);
+        const Engine::NbestHost& h = e.last_nbest();
+        K2_REQUIRE(h.B == B && h.N == nbest && h.max_tokens == max_tokens, "internal: the search kept no N-best");
+        for (int b = 0; b < B; b++) {
+            n_hyps[b] = h.n_hyps[(size_t)b];
+            for (int i = 0; i < h.n_hyps[(size_t)b]; i++) {
+                const size_t en = (size_t)b * nbest + i, o = en * max_tokens, len = (size_t)h.n_tokens[en];
+                memcpy(tokens + o, h.tokens.data() + o, sizeof(int64_t) * len);
+                memcpy(timestamps + o, h.timestamps.data() + o, sizeof(int32_t) * len);
+                memcpy(token_log_probs + o, h.token_log_probs.data() + o, sizeof(float) * len);
+                n_tokens[en] = (int32_t)len;
+                scores[en] = h.scores[en];
+            }
+        }
+    });
+}
 int32_t k2hip_offline_greedy(k2hip_model_t* model, const float* const* feats, const int64_t* n_floats, int32_t B,
                              int64_t* tokens, int32_t* timestamps, int32_t* n_tokens, int32_t max_tokens) {
     return guard([&] {
@@ -737,6 +828,8 @@ int32_t k2hip_offline_submit_samples_dev(k2hip_model_t* model, const float* samp
     return guard([&] {
         NEED(model); NEED(samples_dev); NEED(ticket);
         EngineLock lk(model->engine);
+        K2_REQUIRE(model->engine.nbest() == 0, "offline submit: the pipelined route returns one result per stream and the model keeps %d "
+                   "alternatives (k2hip_set_nbest) -- use the synchronous entries, or set_nbest(model, 1)", model->engine.nbest());
         *ticket = model->engine.submit_samples_dev(samples_dev, n_samples_each, B, max_tokens);
     });
 }
@@ -745,6 +838,8 @@ int32_t k2hip_offline_submit_samples(k2hip_model_t* model, const float* samples_
     return guard([&] {
         NEED(model); NEED(samples_host); NEED(ticket);
         EngineLock lk(model->engine);
+        K2_REQUIRE(model->engine.nbest() == 0, "offline submit: the pipelined route returns one result per stream and the model keeps %d "
+                   "alternatives (k2hip_set_nbest) -- use the synchronous entries, or set_nbest(model, 1)", model->engine.nbest());
         *ticket = model->engine.submit_samples_host(samples_host, n_samples_each, B, max_tokens);
     });
 }
@@ -765,6 +860,8 @@ int32_t k2hip_offline_wait(k2hip_model_t* model, int32_t ticket, int64_t* tokens
     return guard([&] {
         NEED(model); NEED(tokens); NEED(timestamps); NEED(n_tokens);
         EngineLock lk(model->engine);
+        K2_REQUIRE(model->engine.nbest() == 0, "offline wait: the pipelined route returns one result per stream and the model keeps %d "
+                   "alternatives (k2hip_set_nbest)", model->engine.nbest());
         model->engine.wait_ticket(ticket, tokens, timestamps, n_tokens);
     });
 }
@@ -1021,6 +1118,8 @@ int32_t k2hip_online_step(k2hip_model_t* model, k2hip_online_stream_t* const* st
         if (!c.ctc) {
             EngineLock lk(e);
             K = e.beam();
+            K2_REQUIRE(K > 0 || e.nbest() == 0, "online step: the model keeps %d alternatives (k2hip_set_nbest) but decodes with greedy_search, "
+                       "which has none", e.nbest());
             K2_REQUIRE(!(K > 0 && e.has_hotwords()),
                        "online step: hotword biasing covers the offline modified beam search only, not the streaming one -- clear the "
                        "hotwords (k2hip_set_hotwords(model, NULL)) or decode with greedy_search");
@@ -1125,8 +1224,17 @@ int32_t k2hip_online_step(k2hip_model_t* model, k2hip_online_stream_t* const* st
             n.resize(R);
         }
         if (!all_mirrored) fb.finish();   // the step reads some stream's chunk from host memory: the frames must be there
+        std::vector<float> ypb;   // N-best on: the token log-probs of the survivors' suffixes come back beside the out blocks
         try {
             EngineLock lk(e);
+            struct YpOut {
+                Engine& e;
+                ~YpOut() { e.set_beam_yp_out(nullptr); }
+            } yp_guard{e};
+            if (K > 0 && e.nbest() > 0) {
+                ypb.resize((size_t)R * K * Tp);
+                e.set_beam_yp_out(ypb.data());
+            }
             if (K > 0 && any_hw)
                 e.online_step_beam_hw(slots.data(), chunks.data(), plens.data(), nch.data(), R, K, bin.data(), bout.data(),
                                       Engine::BeamHwIO{graphs.data(), st_in.data(), st_out.data()}, all_mirrored ? heads.data() : nullptr);
@@ -1161,8 +1269,9 @@ int32_t k2hip_online_step(k2hip_model_t* model, k2hip_online_stream_t* const* st
             if (K > 0) {
                 // the best hypothesis replaces the result (it may revise earlier tokens): n_new_tokens = change of its length
                 const int64_t before = (int64_t)s->beam->tokens().size();
-                if (any_hw) s->beam->apply_out_states(bout.data() + (size_t)r * RL.out_ints(), Tp, st_out.data() + (size_t)r * K);
-                else s->beam->apply_out(bout.data() + (size_t)r * RL.out_ints(), Tp);
+                const float* yp = ypb.empty() ? nullptr : ypb.data() + (size_t)r * K * Tp;
+                if (any_hw) s->beam->apply_out_states(bout.data() + (size_t)r * RL.out_ints(), Tp, st_out.data() + (size_t)r * K, yp);
+                else s->beam->apply_out(bout.data() + (size_t)r * RL.out_ints(), Tp, yp);
                 s->hyp[0] = s->beam->hyp_last(0);
                 s->hyp[1] = s->beam->hyp_last(1);
                 n_new_tokens[idx[r]] = (int32_t)((int64_t)s->beam->tokens().size() - before);
@@ -1359,15 +1468,25 @@ int32_t k2hip_beam_search_chunk(k2hip_model_t* model, k2hip_beam_stream_t* const
                 streams[b]->hist.fill_states(st_in.data() + (size_t)b * K);
             }
         }
+        std::vector<float> ypb;
         {
             EngineLock lk(model->engine);
+            struct YpOut {
+                Engine& e;
+                ~YpOut() { e.set_beam_yp_out(nullptr); }
+            } yp_guard{model->engine};
+            if (model->engine.nbest() > 0) {
+                ypb.resize((size_t)B * K * Tc);
+                model->engine.set_beam_yp_out(ypb.data());
+            }
             if (any_hw) model->engine.beam_chunk_host_hw(enc_out, B, Tc, K, bin.data(), bout.data(), Engine::BeamHwIO{graphs.data(), st_in.data(), st_out.data()});
             else model->engine.beam_chunk_host(enc_out, B, Tc, K, bin.data(), bout.data());
         }
         // (only after success: a failed call leaves every stream as it was)
         for (int b = 0; b < B; b++) {
-            if (any_hw) streams[b]->hist.apply_out_states(bout.data() + (size_t)b * L.out_ints(), Tc, st_out.data() + (size_t)b * K);
-            else streams[b]->hist.apply_out(bout.data() + (size_t)b * L.out_ints(), Tc);
+            const float* yp = ypb.empty() ? nullptr : ypb.data() + (size_t)b * K * Tc;
+            if (any_hw) streams[b]->hist.apply_out_states(bout.data() + (size_t)b * L.out_ints(), Tc, st_out.data() + (size_t)b * K, yp);
+            else streams[b]->hist.apply_out(bout.data() + (size_t)b * L.out_ints(), Tc, yp);
         }
     });
 }
@@ -1393,6 +1512,46 @@ int32_t k2hip_beam_stream_get_score(const k2hip_beam_stream_t* s, float* score) 
         NEED(s); NEED(score);
         *score = s->hist.score();
     });
+}
+int32_t k2hip_beam_stream_num_alternatives(const k2hip_beam_stream_t* s) {
+    return s ? (int32_t)s->hist.nbest(s->model->nbest.load()).size() : -1;
+}
+int32_t k2hip_beam_stream_get_alternative(const k2hip_beam_stream_t* s, int32_t i, int64_t* tokens, int32_t* timestamps, float* token_log_probs,
+                                          int32_t cap, int32_t* n, float* score) {
+    return guard([&] {
+        NEED(s);
+        alt_get(s->hist.nbest(s->model->nbest.load()), i, tokens, timestamps, token_log_probs, cap, n, score);
+    });
+}
+int32_t k2hip_beam_stream_get_token_log_probs(const k2hip_beam_stream_t* s, float* out, int32_t cap) {
+    if (!s) return guard([&] { NEED(s); });
+    return yp_get(s->hist.token_log_probs(), out, cap);
+}
+// (a stream that has not decoded a chunk yet is in the start state: one empty alternative, score 0)
+static std::vector<BeamAlt> online_alts(const k2hip_online_stream* s) {
+    K2_REQUIRE(s->method != 0, "the stream decodes with greedy_search: it has no alternatives");
+    return s->method > 0 ? s->beam->nbest(s->model->nbest.load()) : std::vector<BeamAlt>(1);
+}
+int32_t k2hip_online_stream_num_alternatives(const k2hip_online_stream_t* s) {
+    int32_t count = 0;
+    const int32_t rc = guard([&] {
+        NEED(s);
+        count = (int32_t)online_alts(s).size();
+    });
+    return rc < 0 ? rc : count;
+}
+int32_t k2hip_online_stream_get_alternative(const k2hip_online_stream_t* s, int32_t i, int64_t* tokens, int32_t* timestamps,
+                                            float* token_log_probs, int32_t cap, int32_t* n, float* score) {
+    return guard([&] {
+        NEED(s);
+        alt_get(online_alts(s), i, tokens, timestamps, token_log_probs, cap, n, score);
+    });
+}
+int32_t k2hip_online_stream_get_token_log_probs(const k2hip_online_stream_t* s, float* out, int32_t cap) {
+    if (!s) return guard([&] { NEED(s); });
+    if (s->method == 0) return guard([&] { K2_REQUIRE(false, "the stream decodes with greedy_search: it keeps no token log-probs"); });
+    static const std::vector<float> none;
+    return yp_get(s->method > 0 ? s->beam->token_log_probs() : none, out, cap);
 }
 int32_t k2hip_online_stream_get_hyp(const k2hip_online_stream_t* s, int64_t* hyp2) {
     return guard([&] {
@@ -1662,10 +1821,22 @@ int32_t k2hip_offline_recognizer_get_results(k2hip_model_t* model, k2hip_offline
         int max_tokens = std::max(1, e.encoder_out_frames(T));
         std::vector<int64_t> tok((size_t)B * max_tokens);
         std::vector<int32_t> ts((size_t)B * max_tokens), n(B);
+        for (int b = 0; b < B; b++) streams[b]->alts.assign(1, BeamAlt{});   // (a failed call leaves the start state)
         {
             EngineLock lk(e);
+            K2_REQUIRE(e.nbest() == 0 || e.beam() > 0, "GetResults: the model keeps %d alternatives (k2hip_set_nbest) but decodes with "
+                       "greedy_search, which has none", e.nbest());
             if (from_samples) e.offline_greedy_samples(ptrs.data(), nfl.data(), B, tok.data(), ts.data(), n.data(), max_tokens, false, /*pinned_src=*/true);
             else e.offline_greedy_feats(ptrs.data(), nfl.data(), B, false, tok.data(), ts.data(), n.data(), max_tokens);
+            const Engine::NbestHost& h = e.last_nbest();
+            // (never one silent result where a list was asked for)
+            K2_REQUIRE(e.nbest() == 0 || (h.B == B && h.N == e.nbest()), "internal: GetResults ran with %d alternatives asked for and the search kept no list",
+                       e.nbest());
+            if (e.nbest() > 0)
+                for (int b = 0; b < B; b++) {
+                    streams[b]->alts.clear();
+                    for (int i = 0; i < h.n_hyps[(size_t)b]; i++) streams[b]->alts.push_back(alt_of(h, b, i));
+                }
         }
         auto remove_samples = [&](k2hip_offline_stream* s) {   // RemoveSamples (:294 / :418, OfflineStream.cs:58-68)
             if (from_samples) {
@@ -1717,8 +1888,12 @@ int32_t k2hip_offline_recognizer_get_result(k2hip_model_t* model, k2hip_offline_
         int32_t n = 0;
         const float* p[1] = {from_samples ? s->wav.data() : s->speech.data()};
         int64_t nfl[1] = {from_samples ? (int64_t)s->wav.size() : (int64_t)s->speech.size()};
+        s->alts.assign(1, BeamAlt{});
         {
             EngineLock lk(e);
+            // (the single-stream path is the reference's greedy loop whatever the decoding method: it has no alternatives)
+            K2_REQUIRE(e.nbest() == 0, "GetResult: the single-stream path is greedy search and the model keeps %d alternatives "
+                       "(k2hip_set_nbest) -- use GetResults", e.nbest());
             if (from_samples) e.offline_greedy_samples(p, nfl, 1, tok.data(), ts.data(), &n, max_tokens, true, /*pinned_src=*/true);
             else e.offline_greedy_feats(p, nfl, 1, true, tok.data(), ts.data(), &n, max_tokens);
         }
@@ -1729,6 +1904,18 @@ int32_t k2hip_offline_recognizer_get_result(k2hip_model_t* model, k2hip_offline_
         // (the single paths never call RemoveSamples, :93-187 / :305-364: Speech stays -- materialised now if the search took the samples)
         if (from_samples) offline_materialize(s);
     });
+}
+int32_t k2hip_offline_stream_num_alternatives(const k2hip_offline_stream_t* s) { return s ? (int32_t)s->alts.size() : -1; }
+int32_t k2hip_offline_stream_get_alternative(const k2hip_offline_stream_t* s, int32_t i, int64_t* tokens, int32_t* timestamps,
+                                             float* token_log_probs, int32_t cap, int32_t* n, float* score) {
+    return guard([&] {
+        NEED(s);
+        alt_get(s->alts, i, tokens, timestamps, token_log_probs, cap, n, score);
+    });
+}
+int32_t k2hip_offline_stream_get_token_log_probs(const k2hip_offline_stream_t* s, float* out, int32_t cap) {
+    if (!s) return guard([&] { NEED(s); });
+    return yp_get(s->alts[0].token_log_probs, out, cap);
 }
 int32_t k2hip_offline_stream_num_tokens(const k2hip_offline_stream_t* s) { return s ? (int32_t)s->tokens.size() : -1; }
 int32_t k2hip_offline_stream_num_timestamps(const k2hip_offline_stream_t* s) { return s ? (int32_t)s->timestamps.size() : -1; }

@@ -158,12 +158,20 @@ struct HypView {
     int* st_n = nullptr;
     const int* hw_next = nullptr;
     const float* hw_bonus = nullptr;
+    // token log-probs (null: not kept, the search does what it does without them): parallel to ts, the unbiased log-softmax term
+    // of each emitted token at the frame it was emitted
+    const float* yp_c = nullptr;
+    float* yp_n = nullptr;
 };
 constexpr int kStepScratchInts = 4 * kMaxBeam + 4 + 2 * kMaxBeam * kMaxBeam;
+constexpr int kYpScratchFloats = kMaxBeam * kMaxBeam + kMaxBeam;
 // one workgroup of NT threads per stream; lg: the hypotheses' logits, ldl floats per row; scratch: kStepScratchInts ints of LDS
+// pscratch: kYpScratchFloats floats of LDS when hv.yp_n is set (the candidates' unbiased terms beside candv / candi, the top K's)
 template <int NT, bool HW>
-__device__ void beam_step_body(const HypView& hv, const float* lg, int ldl, int V, int t, int* scratch) {
+__device__ void beam_step_body(const HypView& hv, const float* lg, int ldl, int V, int t, int* scratch, float* pscratch = nullptr) {
     constexpr int BT = NT;
+    float* candp = hv.yp_n ? pscratch : nullptr;
+    float* topp = candp ? pscratch + kMaxBeam * kMaxBeam : nullptr;
     int* taken = scratch;
     float* topv = reinterpret_cast<float*>(scratch + kMaxBeam);
     int* topi = scratch + 2 * kMaxBeam;
@@ -212,6 +220,8 @@ __device__ void beam_step_body(const HypView& hv, const float* lg, int ldl, int 
                     wave_best(bv, bi);
                     if (bi >= 0 && (bi & 63) == lane) used |= 1u << (bi >> 6);
                     if (lane == 0) { candv[k * kMaxBeam + r] = bv; candi[k * kMaxBeam + r] = bi < 0 ? -1 : k * V + bi; }
+                    // the unbiased term of the winner, formed from its logit exactly as the score's first two operations were
+                    if (candp && lane == 0 && bi >= 0) candp[k * kMaxBeam + r] = (l[bi] - mx) - lse;
                 }
             }
         };
@@ -242,6 +252,7 @@ __device__ void beam_step_body(const HypView& hv, const float* lg, int ldl, int 
             wave_best(bv, bi);
             excl[r] = bi;
             if (lane == 0) { candv[k * kMaxBeam + r] = bv; candi[k * kMaxBeam + r] = bi < 0 ? -1 : k * V + bi; }
+            if (candp && lane == 0 && bi >= 0) candp[k * kMaxBeam + r] = (l[bi] - mx) - lse;
         }
     }
     __syncthreads();
@@ -260,7 +271,10 @@ __device__ void beam_step_body(const HypView& hv, const float* lg, int ldl, int 
                 const int oi = __builtin_amdgcn_readlane(myi, src);
                 if (oi >= 0 && (ov > myv || (ov == myv && oi < myi))) rank++;
             }
-        if (myi >= 0 && rank < want) { topv[rank] = myv; topi[rank] = myi; taken[rank] = myi; }
+        if (myi >= 0 && rank < want) {
+            topv[rank] = myv; topi[rank] = myi; taken[rank] = myi;
+            if (candp) topp[rank] = candp[lane];
+        }
     }
     __syncthreads();
     // ---- expand + merge (HypothesisList.add) into the other buffer
@@ -403,12 +417,15 @@ __device__ void beam_step_body(const HypView& hv, const float* lg, int ldl, int 
             ys_n[(long long)slot * hv.cap + i] = ys_c[(long long)hr * hv.cap + i];
             ts_n[(long long)slot * hv.cap + i] = ts_c[(long long)hr * hv.cap + i];
         }
+        if (hv.yp_n)
+            for (int i = lane; i < n0; i += 64) hv.yp_n[(long long)slot * hv.cap + i] = hv.yp_c[(long long)hr * hv.cap + i];
         if (lane == 0) {
             int nn = n0;
             if (realr) {
                 if (nn < hv.cap) {
                     ys_n[(long long)slot * hv.cap + nn] = tr;
                     ts_n[(long long)slot * hv.cap + nn] = t;
+                    if (hv.yp_n) hv.yp_n[(long long)slot * hv.cap + nn] = topp[r];
                 }
                 nn++;
             }
@@ -436,6 +453,7 @@ __device__ void beam_step_body(const HypView& hv, const float* lg, int ldl, int 
 template <bool HW>
 __global__ __launch_bounds__(BT) void k_beam_step(BeamState s, const float* __restrict__ logits, int V, int t, int cur, int B, int* trace, int Tp) {
     __shared__ int scratch[kStepScratchInts];
+    __shared__ float pscratch[kYpScratchFloats];
     const int b = blockIdx.x, K = s.K, nxt = cur ^ 1;
     const long long BK = (long long)B * K;
     HypView hv;
@@ -462,7 +480,11 @@ __global__ __launch_bounds__(BT) void k_beam_step(BeamState s, const float* __re
         hv.hw_next = s.hw_streams ? s.hw_streams[b].next : s.hw_next;
         hv.hw_bonus = s.hw_streams ? s.hw_streams[b].bonus : s.hw_bonus;
     }
-    beam_step_body<BT, HW>(hv, logits + (long long)b * K * V, V, V, t, scratch);
+    if (s.yp) {
+        hv.yp_c = s.yp + ((long long)cur * BK + (long long)b * K) * s.cap;
+        hv.yp_n = s.yp + ((long long)nxt * BK + (long long)b * K) * s.cap;
+    }
+    beam_step_body<BT, HW>(hv, logits + (long long)b * K * V, V, V, t, scratch, pscratch);
 }
 
 // resume: every surviving hypothesis of the stream into its out block, and the best one (get_most_probable over the WHOLE
@@ -473,7 +495,7 @@ __global__ __launch_bounds__(BT) void k_beam_step(BeamState s, const float* __re
 template <bool HW>
 __device__ void beam_resume_write(const int* in, int* out, int K, int Tp, int cap, int nh, const float* lp, const long long* ctx,
                                   const int* n, const int* org, const int* ys, const int* ts, const int* st = nullptr,
-                                  const float* pending = nullptr, int* st_out = nullptr) {
+                                  const float* pending = nullptr, int* st_out = nullptr, const float* yp = nullptr, float* yp_out = nullptr) {
     const BeamResumeLayout L{K, Tp};
     const int tid = threadIdx.x;
     if (tid == 0) {
@@ -506,6 +528,7 @@ __device__ void beam_resume_write(const int* in, int* out, int K, int Tp, int ca
         if (j < n[k] && j < cap) {
             out[L.out_ys() + i] = ys[(long long)k * cap + j];
             out[L.out_ts() + i] = ts[(long long)k * cap + j];
+            if (yp_out) yp_out[i] = yp[(long long)k * cap + j];   // side block [K][Tp]: the suffixes' token log-probs
         }
     }
 }
@@ -519,11 +542,48 @@ __global__ void k_beam_resume_final(BeamState s, int fin, int B, int* __restrict
                                 s.ctx + 2 * (long long)b * K, s.n + fin * BK + b * K, s.org + fin * BK + b * K,
                                 s.ys + (fin * BK + (long long)b * K) * s.cap, s.ts + (fin * BK + (long long)b * K) * s.cap,
                                 s.st + fin * BK + b * K, s.hw_streams ? s.hw_streams[b].pending : s.hw_pending,
-                                s.st_out ? s.st_out + b * K : nullptr);
+                                s.st_out ? s.st_out + b * K : nullptr, s.yp ? s.yp + (fin * BK + (long long)b * K) * s.cap : nullptr,
+                                s.yp_out ? s.yp_out + (long long)b * K * s.Tp : nullptr);
     else
         beam_resume_write<false>(s.rin + (long long)b * L.in_ints(), rout + (long long)b * L.out_ints(), K, s.Tp, s.cap, s.nhyp[b], s.lp + b * K,
                                  s.ctx + 2 * (long long)b * K, s.n + fin * BK + b * K, s.org + fin * BK + b * K,
-                                 s.ys + (fin * BK + (long long)b * K) * s.cap, s.ts + (fin * BK + (long long)b * K) * s.cap);
+                                 s.ys + (fin * BK + (long long)b * K) * s.cap, s.ts + (fin * BK + (long long)b * K) * s.cap, nullptr, nullptr,
+                                 nullptr, s.yp ? s.yp + (fin * BK + (long long)b * K) * s.cap : nullptr,
+                                 s.yp_out ? s.yp_out + (long long)b * K * s.Tp : nullptr);
+}
+
+// N-best: up to nb.nbest of the stream's nh final hypotheses in the order of the final pick -- (final log-prob) / (length + 2)
+// descending, ties in insertion order, so entry 0 is the hypothesis the single-result code picks.  Called by all threads of a
+// workgroup; n / ys / ts / yp: the final parity's [K] / [K][cap] arrays of the stream, final_lp(k): the finalized log-prob.
+template <typename FinalLp>
+__device__ void beam_nbest_write(const BeamNbest& nb, int b, int nh, int cap, int max_tokens, const int* n, const int* ys, const int* ts,
+                                 const float* yp, FinalLp final_lp, int* overflow) {
+    float v[kMaxBeam];
+#pragma unroll
+    for (int k = 0; k < kMaxBeam; k++) v[k] = k < nh ? final_lp(k) / (float)(n[k] + 2) : -INFINITY;
+    for (int k = 0; k < nh; k++) {
+        int rank = 0;
+#pragma unroll
+        for (int j = 0; j < kMaxBeam; j++)
+            if (j < nh && (v[j] > v[k] || (v[j] == v[k] && j < k))) rank++;
+        if (rank >= nb.nbest) continue;
+        const int len = n[k];
+        if (len > max_tokens || len > cap) {   // (the single result's rule, per entry)
+            if (threadIdx.x == 0) *overflow = 1;
+            continue;
+        }
+        const long long o = ((long long)b * nb.nbest + rank) * max_tokens;
+        for (int i = threadIdx.x; i < len; i += blockDim.x) {
+            nb.tokens[o + i] = ys[(long long)k * cap + i];
+            nb.timestamps[o + i] = ts[(long long)k * cap + i];
+            nb.token_log_probs[o + i] = yp[(long long)k * cap + i];
+        }
+        if (threadIdx.x == 0) {
+            nb.n_tokens[b * nb.nbest + rank] = len;
+            nb.scores[b * nb.nbest + rank] = final_lp(k);
+        }
+    }
+    if (threadIdx.x == 0) nb.n_hyps[b] = min(nh, nb.nbest);
 }
 
 // ---- the whole search of a stream in one kernel (small vocabularies: the model's all-contexts decoder table) -----------------
@@ -545,9 +605,10 @@ __device__ __forceinline__ unsigned long long bload_granule(const unsigned long 
 }
 // LDS (floats): actT[J GF] | psum | lg[GF][Vp] | ctx[2 GF] (long long) | lp[GF] | n[2][GF] | org[2][GF] | st[2][GF] (hotwords only) |
 // nhyp, pad | scratch | ys[2][K][cap] | ts[2][K][cap]
-__host__ __device__ inline size_t beam_loop_lds_floats(int J, int Vp, int K, int cap, bool hyp_in_lds, bool hw) {
+// with token log-probs (yp): ... | scratch | yp scratch | ys | ts | yp[2][K][cap]
+__host__ __device__ inline size_t beam_loop_lds_floats(int J, int Vp, int K, int cap, bool hyp_in_lds, bool hw, bool yp) {
     return (size_t)J * GF + kPsumFloats + (size_t)GF * Vp + 4 * GF + GF + 2 * GF + 2 * GF + (hw ? 2 * GF : 0) + 4 + kStepScratchInts + 4 +
-           (hyp_in_lds ? 4 * (size_t)K * cap : 0);
+           (yp ? kYpScratchFloats : 0) + (hyp_in_lds ? (yp ? 6 : 4) * (size_t)K * cap : 0);
 }
 template <int NH, bool HW>   // NH = 1: beam <= 4, the sweep forms only rows 0..3; HW: hotword biasing
 __global__ __launch_bounds__(GT) void k_beam_loop(DecJoinW w, BeamLoopArgs a) {
@@ -562,8 +623,11 @@ __global__ __launch_bounds__(GT) void k_beam_loop(DecJoinW w, BeamLoopArgs a) {
     int* stb = orgb + 2 * GF;                           // [2][GF] (hotwords)
     int* nhyp = stb + (HW ? 2 * GF : 0);
     int* scratch = nhyp + 4;
-    int* ys = a.ys_g ? a.ys_g + (size_t)blockIdx.x * 2 * a.K * a.cap : scratch + kStepScratchInts + 4;
+    // token log-probs (a.want_yp; the whole launch takes one side of this branch): the step's extra scratch, and yp beside ys / ts
+    float* pscratch = a.want_yp ? reinterpret_cast<float*>(scratch + kStepScratchInts + 4) : nullptr;
+    int* ys = a.ys_g ? a.ys_g + (size_t)blockIdx.x * 2 * a.K * a.cap : scratch + kStepScratchInts + 4 + (a.want_yp ? kYpScratchFloats : 0);
     int* ts = a.ys_g ? a.ts_g + (size_t)blockIdx.x * 2 * a.K * a.cap : ys + 2 * a.K * a.cap;
+    float* yp = !a.want_yp ? nullptr : a.ys_g ? a.yp_g + (size_t)blockIdx.x * 2 * a.K * a.cap : reinterpret_cast<float*>(ts + 2 * a.K * a.cap);
     __shared__ int xfail;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, K = a.K;
     if (tid == 0) xfail = 0;
@@ -745,7 +809,11 @@ __global__ __launch_bounds__(GT) void k_beam_loop(DecJoinW w, BeamLoopArgs a) {
             hv.hw_next = hws.next;
             hv.hw_bonus = hws.bonus;
         }
-        beam_step_body<GT, HW>(hv, lg, w.Vp, w.V, t, scratch);
+        if (yp) {
+            hv.yp_c = yp + (size_t)cur * K * a.cap;
+            hv.yp_n = yp + (size_t)(cur ^ 1) * K * a.cap;
+        }
+        beam_step_body<GT, HW>(hv, lg, w.Vp, w.V, t, scratch, pscratch);
         __syncthreads();
     }
     // k_beam_final: max of log_prob / len(ys) (len counts the 2 ctx blanks), first maximum
@@ -755,10 +823,12 @@ __global__ __launch_bounds__(GT) void k_beam_loop(DecJoinW w, BeamLoopArgs a) {
         if constexpr (HW)
             beam_resume_write<true>(rin, a.rout + (long long)b * RL.out_ints(), K, a.Tp, a.cap, *nhyp, lp, ctx, n_f, orgb + fin * GF,
                                     ys + (size_t)fin * K * a.cap, ts + (size_t)fin * K * a.cap, stb + fin * GF, hws.pending,
-                                    a.st_out ? a.st_out + b * K : nullptr);
+                                    a.st_out ? a.st_out + b * K : nullptr, yp ? yp + (size_t)fin * K * a.cap : nullptr,
+                                    a.yp_out ? a.yp_out + (long long)b * K * a.Tp : nullptr);
         else
             beam_resume_write<false>(rin, a.rout + (long long)b * RL.out_ints(), K, a.Tp, a.cap, *nhyp, lp, ctx, n_f, orgb + fin * GF,
-                                     ys + (size_t)fin * K * a.cap, ts + (size_t)fin * K * a.cap);
+                                     ys + (size_t)fin * K * a.cap, ts + (size_t)fin * K * a.cap, nullptr, nullptr, nullptr,
+                                     yp ? yp + (size_t)fin * K * a.cap : nullptr, a.yp_out ? a.yp_out + (long long)b * K * a.Tp : nullptr);
         return;
     }
     // (hotwords: an unfinished match earns nothing -- every hypothesis' log-prob loses its state's pending bonus first)
@@ -767,6 +837,9 @@ __global__ __launch_bounds__(GT) void k_beam_loop(DecJoinW w, BeamLoopArgs a) {
         if constexpr (HW) return lp[k] - hws.pending[st_f[k]];
         else return lp[k];
     };
+    if (a.nb.tokens && slab == 0)
+        beam_nbest_write(a.nb, b, *nhyp, a.cap, a.max_tokens, n_f, ys + (size_t)fin * K * a.cap, ts + (size_t)fin * K * a.cap,
+                         yp + (size_t)fin * K * a.cap, final_lp, a.overflow);
     int best = 0;
     float bs = final_lp(0) / (float)(n_f[0] + 2);
     for (int k = 1; k < *nhyp; k++) {
@@ -794,7 +867,7 @@ __global__ __launch_bounds__(GT) void k_beam_loop(DecJoinW w, BeamLoopArgs a) {
 // get_most_probable(length_norm=True): max of log_prob / len(ys) (len counts the 2 ctx blanks), first maximum
 template <bool HW>
 __global__ void k_beam_final(BeamState s, int fin, int B, long long* __restrict__ tokens, int* __restrict__ timestamps,
-                             int* __restrict__ n_tokens, float* __restrict__ scores, int max_tokens, int* __restrict__ overflow) {
+                             int* __restrict__ n_tokens, float* __restrict__ scores, int max_tokens, int* __restrict__ overflow, BeamNbest nb) {
     const int b = blockIdx.x, K = s.K;
     const long long BK = (long long)B * K;
     const int* n_f = s.n + fin * BK + b * K;
@@ -803,6 +876,9 @@ __global__ void k_beam_final(BeamState s, int fin, int B, long long* __restrict_
         if constexpr (HW) return s.lp[b * K + k] - s.hw_pending[s.st[fin * BK + b * K + k]];
         else return s.lp[b * K + k];
     };
+    if (nb.tokens)
+        beam_nbest_write(nb, b, s.nhyp[b], s.cap, max_tokens, n_f, s.ys + (fin * BK + (long long)b * K) * s.cap,
+                         s.ts + (fin * BK + (long long)b * K) * s.cap, s.yp + (fin * BK + (long long)b * K) * s.cap, final_lp, overflow);
     int best = 0;
     float bs = final_lp(0) / (float)(n_f[0] + 2);
     for (int k = 1; k < s.nhyp[b]; k++) {
@@ -836,14 +912,20 @@ void beam_search(const Ctx& ctx, const DecJoinW& w, const BeamArgs& a) {
     K2_REQUIRE(!(a.hw_next && a.hw_streams), "beam search: one hotword graph or one per stream, not both");
     K2_REQUIRE(!a.hw_streams || (a.rin && a.st_in && a.st_out), "beam search: per-stream hotword graphs belong to the resumed search and need its state blocks");
     K2_REQUIRE(!(a.hw_next && a.rin), "beam search: the resumed search takes its hotword graphs per stream");
+    // token log-probs / N-best: the offline search writes nb (which needs them), the resumed one the side block yp_out
+    const bool yp = a.nb.tokens != nullptr || a.yp_out != nullptr;
+    K2_REQUIRE(!a.nb.tokens || (!a.rin && a.nb.nbest >= 1 && a.nb.nbest <= kMaxBeam && a.nb.timestamps && a.nb.token_log_probs && a.nb.n_tokens &&
+                                a.nb.scores && a.nb.n_hyps),
+               "beam search: incomplete N-best outputs (nbest %d, range [1,%d])", a.nb.nbest, kMaxBeam);
+    K2_REQUIRE(!a.yp_out || a.rin, "beam search: the token log-prob side block belongs to the resumed search");
     if (!ctx.dry) g_launches[hw ? 1 : 0]++;
     Arena& ar = *ctx.arena;
     const int B = a.B, K = a.beam, M = B * K, cap = a.Tp + 1;
     {
         // the one-kernel form: needs the decoder table (small vocabulary) and the stream's logits and hypotheses in LDS
         // hypotheses in LDS when they fit beside the logits (T' <= ~600 at beam 4 with the large-en shapes), else in device memory
-        const bool hyp_in_lds = sizeof(float) * beam_loop_lds_floats(w.J, w.Vp, K, cap, true, hw) <= 150 * 1024 && !tunables().beam_hyp_global;
-        const size_t lds = sizeof(float) * beam_loop_lds_floats(w.J, w.Vp, K, cap, hyp_in_lds, hw);
+        const bool hyp_in_lds = sizeof(float) * beam_loop_lds_floats(w.J, w.Vp, K, cap, true, hw, yp) <= 150 * 1024 && !tunables().beam_hyp_global;
+        const size_t lds = sizeof(float) * beam_loop_lds_floats(w.J, w.Vp, K, cap, hyp_in_lds, hw, yp);
         if (w.dec_table && !tunables().beam_launches && lds <= 150 * 1024 && w.J % 8 == 0 && w.Vp % 4 == 0 && K <= GF) {
             // Two column slabs per stream where one workgroup would sweep two chunks (beam <= 4, 256 < V <= 512) and 2 B workgroups fit
             // the offline co-residency budget: the frame's sweep is bound by ONE CU's fetch of the 1 MB matrix, two CUs halve it, and the
@@ -854,12 +936,14 @@ void beam_search(const Ctx& ctx, const DecJoinW& w, const BeamArgs& a) {
             // (hypotheses in device memory: every workgroup keeps its own copy, so two slabs need twice the space)
             int* ys_g = hyp_in_lds ? nullptr : ar.take<int>((int64_t)(two ? 2 : 1) * 2 * M * cap);
             int* ts_g = hyp_in_lds ? nullptr : ar.take<int>((int64_t)(two ? 2 : 1) * 2 * M * cap);
+            float* yp_g = (hyp_in_lds || !yp) ? nullptr : ar.take<float>((int64_t)(two ? 2 : 1) * 2 * M * cap);
             if (ctx.dry) return;
             BeamLoopArgs la;
             la.enc = a.enc; la.Tp = a.Tp; la.K = K; la.cap = cap;
             la.tokens = a.tokens; la.timestamps = a.timestamps; la.n_tokens = a.n_tokens; la.scores = a.scores;
             la.max_tokens = a.max_tokens; la.overflow = a.overflow;
             la.ys_g = ys_g; la.ts_g = ts_g;
+            la.want_yp = yp; la.yp_g = yp_g; la.nb = a.nb; la.yp_out = a.yp_out;
             la.xg = xg;
             la.trace = a.trace;
             la.rin = a.rin; la.rout = a.rout;
@@ -900,6 +984,10 @@ void beam_search(const Ctx& ctx, const DecJoinW& w, const BeamArgs& a) {
     s.cap = cap;
     s.ys = ar.take<int>((int64_t)2 * M * cap);
     s.ts = ar.take<int>((int64_t)2 * M * cap);
+    if (yp) {
+        s.yp = ar.take<float>((int64_t)2 * M * cap);
+        s.yp_out = a.yp_out;
+    }
     s.n = ar.take<int>((int64_t)2 * M);
     s.lp = ar.take<float>(M);
     s.lp_next = s.lp;  // in place: within k_beam_step every read of a stream's lp / nhyp precedes (barrier-separated) tid 0's write
@@ -949,9 +1037,9 @@ void beam_search(const Ctx& ctx, const DecJoinW& w, const BeamArgs& a) {
         if (a.rin && hw) hipLaunchKernelGGL(k_beam_resume_final<true>, dim3(B), dim3(256), 0, ctx.stream, s, a.Tp & 1, B, a.rout);
         else if (a.rin) hipLaunchKernelGGL(k_beam_resume_final<false>, dim3(B), dim3(256), 0, ctx.stream, s, a.Tp & 1, B, a.rout);
         else if (hw) hipLaunchKernelGGL(k_beam_final<true>, dim3(B), dim3(256), 0, ctx.stream, s, a.Tp & 1, B, a.tokens, a.timestamps, a.n_tokens,
-                                        a.scores, a.max_tokens, a.overflow);
+                                        a.scores, a.max_tokens, a.overflow, a.nb);
         else hipLaunchKernelGGL(k_beam_final<false>, dim3(B), dim3(256), 0, ctx.stream, s, a.Tp & 1, B, a.tokens, a.timestamps, a.n_tokens, a.scores,
-                                a.max_tokens, a.overflow);
+                                a.max_tokens, a.overflow, a.nb);
         K2_HIP(hipGetLastError());
     }
 }

@@ -6,7 +6,7 @@
 //   - SeqTree, hash-consed: one node per distinct token sequence ((parent, token) -> node), so node identity IS sequence identity
 //     and the relation of a pair costs at most T' parent steps, whatever the length of the transcript.  (Without hash-consing a
 //     prefix that was pruned and later spelled again would get a second node: a false "different".)
-//   - PathTree, plain: (parent, token, timestamp) per hypothesis -- two hypotheses with the same tokens may carry different
+//   - PathTree, plain: (parent, token, timestamp, token log-prob) per hypothesis -- two hypotheses with the same tokens may carry different
 //     timestamps (the first-inserted one's are kept at a merge, but an equal sequence can be spelled again later).
 // Nodes no hypothesis reaches any more are freed (and their slot reused), so memory follows the live beam, not the stream's age.
 // Plain C++ (no HIP): tests/native builds it on the CPU.
@@ -25,10 +25,11 @@ class RefTree {
   public:
     struct Node {
         int parent, tok, ts, depth, refs;
+        float yp;   // PathTree: the token's log-prob at the frame it was emitted (0 where it was not asked for)
     };
     RefTree() { clear(); }
     void clear() {
-        nodes_.assign(1, Node{-1, -1, -1, 0, 1});
+        nodes_.assign(1, Node{-1, -1, -1, 0, 1, 0.f});
         free_.clear();
     }
     const Node& operator[](int i) const { return nodes_[(size_t)i]; }
@@ -48,9 +49,9 @@ class RefTree {
     size_t live() const { return nodes_.size() - free_.size(); }
 
   protected:
-    int make(int parent, int tok, int ts) {
+    int make(int parent, int tok, int ts, float yp = 0.f) {
         int id;
-        const Node n{parent, tok, ts, nodes_[(size_t)parent].depth + 1, 0};
+        const Node n{parent, tok, ts, nodes_[(size_t)parent].depth + 1, 0, yp};
         if (!free_.empty()) {
             id = free_.back();
             free_.pop_back();
@@ -102,10 +103,18 @@ class SeqTree : public RefTree {
 
 class PathTree : public RefTree {
   public:
-    int child(int parent, int tok, int ts) { return make(parent, tok, ts); }
+    int child(int parent, int tok, int ts, float yp = 0.f) { return make(parent, tok, ts, yp); }
     void unref(int i) {
         RefTree::unref(i, [](int) {});
     }
+};
+
+// One entry of an N-best list: the emitted tokens (no context prefix), their frames and log-probs, the finalized log-prob
+struct BeamAlt {
+    std::vector<int64_t> tokens;
+    std::vector<int32_t> timestamps;
+    std::vector<float> token_log_probs;
+    float score = 0.f;
 };
 
 // One stream's hypotheses between chunks and its result (the best hypothesis, materialised incrementally).
@@ -129,6 +138,7 @@ class BeamHistory {
         mat_ids_.clear();
         tokens_.assign(2, blank_);
         timestamps_.clear();
+        token_log_probs_.clear();
     }
     const std::vector<Hyp>& hyps() const { return hyps_; }
     int best() const { return best_; }
@@ -143,6 +153,40 @@ class BeamHistory {
     // Tokens = [blank, blank] + ys of the best hypothesis; Timestamps = its absolute frame indexes
     const std::vector<int64_t>& tokens() const { return tokens_; }
     const std::vector<int32_t>& timestamps() const { return timestamps_; }
+    // token log-probs of the best hypothesis, parallel to timestamps() (zeros for chunks applied without the yp block)
+    const std::vector<float>& token_log_probs() const { return token_log_probs_; }
+    // The current hypotheses, at most n of them, in the order of the final pick: (lp - pending(state)) / (length + 2) descending, ties
+    // in insertion order -- entry 0 is the best hypothesis (tokens() / timestamps() / score()).  Each is read off its path node.
+    std::vector<BeamAlt> nbest(int n) const {
+        const int nh = (int)hyps_.size();
+        std::vector<float> fin((size_t)nh), v((size_t)nh);
+        for (int k = 0; k < nh; k++) {
+            const Hyp& h = hyps_[(size_t)k];
+            fin[(size_t)k] = pending_ ? h.lp - (*pending_)[(size_t)h.st] : h.lp;
+            v[(size_t)k] = fin[(size_t)k] / (float)(seq_.depth(h.seq) + 2);
+        }
+        std::vector<BeamAlt> out((size_t)(n < nh ? (n < 0 ? 0 : n) : nh));
+        for (int k = 0; k < nh; k++) {
+            int rank = 0;
+            for (int j = 0; j < nh; j++)
+                if (v[(size_t)j] > v[(size_t)k] || (v[(size_t)j] == v[(size_t)k] && j < k)) rank++;
+            if (rank >= (int)out.size()) continue;
+            BeamAlt& a = out[(size_t)rank];
+            const int d = path_.depth(hyps_[(size_t)k].path);
+            a.tokens.resize((size_t)d);
+            a.timestamps.resize((size_t)d);
+            a.token_log_probs.resize((size_t)d);
+            int p = hyps_[(size_t)k].path;
+            for (int i = d - 1; i >= 0; i--) {
+                a.tokens[(size_t)i] = path_[p].tok;
+                a.timestamps[(size_t)i] = path_[p].ts;
+                a.token_log_probs[(size_t)i] = path_[p].yp;
+                p = path_.parent(p);
+            }
+            a.score = fin[(size_t)k];
+        }
+        return out;
+    }
     const SeqTree& seq_tree() const { return seq_; }
 
     // the device search's in block (kernels.h BeamResumeLayout{K, Tp}) for the next chunk of Tp frames
@@ -171,12 +215,13 @@ class BeamHistory {
         for (int k = 0; k < K_; k++) st_in[k] = k < (int)hyps_.size() ? hyps_[(size_t)k].st : 0;
     }
     // apply_out + the hotword side block out: the survivors' graph states [K]
-    void apply_out_states(const int* out, int Tp, const int* st_out) {
-        apply_out(out, Tp);
+    void apply_out_states(const int* out, int Tp, const int* st_out, const float* yp = nullptr) {
+        apply_out(out, Tp, yp);
         for (size_t k = 0; k < hyps_.size(); k++) hyps_[k].st = st_out[k];
     }
-    // the device search's out block of that chunk: the new hypotheses, the best one, the result
-    void apply_out(const int* out, int Tp) {
+    // the device search's out block of that chunk: the new hypotheses, the best one, the result; yp: the side block [K][Tp] with the
+    // token log-probs of each survivor's suffix, or null (they are then kept as 0)
+    void apply_out(const int* out, int Tp, const float* yp = nullptr) {
         const int K = K_, nh = out[0];
         const int o_org = 2, o_n = 2 + K, o_lp = 2 + 2 * K, o_ctx = 2 + 3 * K, o_ys = 2 + 5 * K, o_ts = 2 + 5 * K + K * Tp;
         std::vector<Hyp> nx((size_t)nh);
@@ -186,7 +231,7 @@ class BeamHistory {
             for (int i = 0; i < out[o_n + k]; i++) {
                 const int tok = out[o_ys + k * Tp + i];
                 sq = seq_.child(sq, tok);
-                ph = path_.child(ph, tok, (int)(frames_ + out[o_ts + k * Tp + i]));
+                ph = path_.child(ph, tok, (int)(frames_ + out[o_ts + k * Tp + i]), yp ? yp[k * Tp + i] : 0.f);
             }
             Hyp& h = nx[(size_t)k];
             h.seq = sq;
@@ -222,10 +267,12 @@ class BeamHistory {
         mat_ids_.resize(keep);
         tokens_.resize(2 + keep);
         timestamps_.resize(keep);
+        token_log_probs_.resize(keep);
         for (size_t i = tail.size(); i-- > 0;) {
             mat_ids_.push_back(tail[i]);
             tokens_.push_back(path_[tail[i]].tok);
             timestamps_.push_back(path_[tail[i]].ts);
+            token_log_probs_.push_back(path_[tail[i]].yp);
         }
         path_.ref(to);
         path_.unref(mat_path_);
@@ -243,6 +290,7 @@ class BeamHistory {
     std::vector<int> mat_ids_;
     std::vector<int64_t> tokens_;
     std::vector<int32_t> timestamps_;
+    std::vector<float> token_log_probs_;
 };
 
 }  // namespace k2hip

@@ -640,6 +640,7 @@ void Engine::greedy_device(const Ctx& c, const float* enc, int B, int Tp, bool s
                            int max_tokens, int* d_overflow) {
     // by-products of the search this call runs, and of no earlier one (their arena may have been rebuilt since)
     d_scores_ = nullptr;
+    d_nb_ = BeamNbest{};
     d_beam_trace_ = nullptr;
     d_trail_ = nullptr;
     d_any_ = nullptr;
@@ -707,6 +708,18 @@ void Engine::beam_device(const Ctx& c, const float* enc, int B, int Tp, long lon
     d_scores_ = c.arena->take<float>(B);
     a.scores = d_scores_;
     a.hw_next = hw_next_; a.hw_bonus = hw_bonus_; a.hw_pending = hw_pending_;
+    if (nbest_ > 0 && c.arena == &arena_) {   // (the synchronous entries only: the pipelined route has no place to keep them)
+        const int64_t NB = (int64_t)B * nbest_;
+        d_nb_.nbest = nbest_;
+        d_nb_.tokens = c.arena->take<long long>(NB * max_tokens);
+        d_nb_.timestamps = c.arena->take<int>(NB * max_tokens);
+        d_nb_.token_log_probs = c.arena->take<float>(NB * max_tokens);
+        d_nb_.n_tokens = c.arena->take<int>(NB);
+        d_nb_.scores = c.arena->take<float>(NB);
+        d_nb_.n_hyps = c.arena->take<int>(B);
+        nb_B_ = B; nb_max_tokens_ = max_tokens;
+        a.nb = d_nb_;
+    }
     if (tunables().beam_trace) {
         d_beam_trace_ = c.arena->take<int>((int64_t)B * Tp * (2 * beam_ + 1));
         a.trace = d_beam_trace_;
@@ -728,7 +741,17 @@ void Engine::beam_resume_device(const Ctx& c, const float* enc, int B, int Tp, i
     if (hw) {
         a.hw_streams = hw->graphs; a.st_in = hw->st_in; a.st_out = hw->st_out;
     }
+    d_yp_ = nullptr;
+    if (yp_host_) {
+        yp_floats_ = (size_t)B * K * Tp;
+        d_yp_ = c.arena->take<float>((int64_t)yp_floats_);
+        a.yp_out = d_yp_;
+    }
     beam_search(c, decjoin(), a);
+}
+void Engine::fetch_beam_yp() {
+    if (yp_host_ && d_yp_) K2_HIP(copy_blocking(yp_host_, d_yp_, sizeof(float) * yp_floats_, hipMemcpyDeviceToHost));
+    d_yp_ = nullptr;
 }
 
 void Engine::beam_chunk_host(const float* enc, int B, int Tp, int K, const int* beam_in, int* beam_out) {
@@ -774,6 +797,7 @@ void Engine::beam_chunk_impl(const float* enc, int B, int Tp, int K, const int* 
     if (*reinterpret_cast<int*>(pin)) failf(K2HIP_ERR_HIP, "beam chunk: a hypothesis outgrew its buffer");
     memcpy(beam_out, pin + 16, (size_t)nb_out);
     if (hw) memcpy(hw->st_out, pin + 16 + nb_out, (size_t)nb_st);
+    fetch_beam_yp();
 }
 
 // Back-off of the parted searches.  A search whose column slabs are not co-resident (other handles or processes on the GPU hold the
@@ -841,6 +865,21 @@ void Engine::finish_tokens(const long long* d_tok, const int* d_ts, const int* d
     if (beam_ > 0 && d_scores_) {
         last_scores_.resize(B);
         K2_HIP(copy_blocking(last_scores_.data(), d_scores_, sizeof(float) * B, hipMemcpyDeviceToHost));
+    }
+    if (beam_ > 0 && d_nb_.tokens && B == nb_B_ && max_tokens == nb_max_tokens_) {
+        NbestHost& h = last_nbest_;
+        const size_t NB = (size_t)B * d_nb_.nbest;
+        h.B = B; h.N = d_nb_.nbest; h.max_tokens = max_tokens;
+        h.tokens.resize(NB * max_tokens); h.timestamps.resize(NB * max_tokens); h.token_log_probs.resize(NB * max_tokens);
+        h.n_tokens.resize(NB); h.scores.resize(NB); h.n_hyps.resize((size_t)B);
+        K2_HIP(copy_blocking(h.tokens.data(), d_nb_.tokens, sizeof(int64_t) * h.tokens.size(), hipMemcpyDeviceToHost));
+        K2_HIP(copy_blocking(h.timestamps.data(), d_nb_.timestamps, sizeof(int32_t) * h.timestamps.size(), hipMemcpyDeviceToHost));
+        K2_HIP(copy_blocking(h.token_log_probs.data(), d_nb_.token_log_probs, sizeof(float) * h.token_log_probs.size(), hipMemcpyDeviceToHost));
+        K2_HIP(copy_blocking(h.n_tokens.data(), d_nb_.n_tokens, sizeof(int32_t) * NB, hipMemcpyDeviceToHost));
+        K2_HIP(copy_blocking(h.scores.data(), d_nb_.scores, sizeof(float) * NB, hipMemcpyDeviceToHost));
+        K2_HIP(copy_blocking(h.n_hyps.data(), d_nb_.n_hyps, sizeof(int32_t) * (size_t)B, hipMemcpyDeviceToHost));
+    } else {
+        last_nbest_.B = 0;
     }
     if (beam_ > 0 && d_beam_trace_ && B == trace_B_) {
         last_beam_trace_.resize((size_t)trace_B_ * trace_Tp_ * (2 * trace_K_ + 1));

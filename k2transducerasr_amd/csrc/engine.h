@@ -149,6 +149,27 @@ class Engine {
         hw_next_ = next; hw_bonus_ = bonus; hw_pending_ = pending;
     }
     bool has_hotwords() const { return hw_next_ != nullptr; }
+    // N-best and token log-probs of the synchronous modified beam search (semantics in include/k2hip.h): 0 = off, nothing is computed
+    // or kept beyond the best hypothesis; n >= 1 = every search keeps its first n final hypotheses in pick order, each with its token
+    // log-probs, and last_nbest() holds them after the call (entry 0 = the result the call returned)
+    struct NbestHost {
+        int B = 0, N = 0, max_tokens = 0;
+        std::vector<int64_t> tokens;      // [B][N][max_tokens]
+        std::vector<int32_t> timestamps;  // [B][N][max_tokens]
+        std::vector<float> token_log_probs;
+        std::vector<int32_t> n_tokens;    // [B][N]
+        std::vector<float> scores;        // [B][N]
+        std::vector<int32_t> n_hyps;      // [B]
+    };
+    // The resumed (streaming) search: while a host buffer is named here, every resumed search also returns the token log-probs of its
+    // survivors' suffixes, [B][K][Tp] floats (BeamArgs::yp_out), into it.  The caller names it for one call and clears it.
+    void set_beam_yp_out(float* host) { yp_host_ = host; }
+    void set_nbest(int n) {
+        nbest_ = n;
+        d_nb_ = BeamNbest{};
+    }
+    int nbest() const { return nbest_; }
+    const NbestHost& last_nbest() const { return last_nbest_; }
     int batches_in_flight() const {
         int n = 0;
         for (const auto& sl : slots_) n += sl.busy;
@@ -283,6 +304,13 @@ class Engine {
     std::map<int, float*> pe_cache_;
     bool instrument_ = false;
     int beam_ = 0;
+    int nbest_ = 0;
+    float *yp_host_ = nullptr, *d_yp_ = nullptr;
+    size_t yp_floats_ = 0;
+    void fetch_beam_yp();   // after the resumed search's download: d_yp_ -> yp_host_
+    BeamNbest d_nb_;            // device outputs of the search this call runs (tokens == null: none)
+    int nb_B_ = 0, nb_max_tokens_ = 0;
+    NbestHost last_nbest_;
     const int* hw_next_ = nullptr;
     const float *hw_bonus_ = nullptr, *hw_pending_ = nullptr;
     // CTC search by-products of the last synchronous call (NumTrailingBlank bookkeeping, OfflineRecognizer.cs:392-397)

@@ -479,6 +479,17 @@ struct BeamHwStream {
     const float* bonus = nullptr;
     const float* pending = nullptr;
 };
+// N-best outputs of the offline search (device; tokens == null: off): up to `nbest` final hypotheses per stream in the order of the
+// final pick, (finalized log-prob) / (length + 2) descending with ties in insertion order -- entry 0 is the single result
+struct BeamNbest {
+    int nbest = 0;
+    long long* tokens = nullptr;        // [B][nbest][max_tokens]
+    int* timestamps = nullptr;          // [B][nbest][max_tokens]
+    float* token_log_probs = nullptr;   // [B][nbest][max_tokens]
+    int* n_tokens = nullptr;            // [B][nbest]
+    float* scores = nullptr;            // [B][nbest] finalized log-probs (not normalised)
+    int* n_hyps = nullptr;              // [B] entries written: min(survivors, nbest)
+};
 struct BeamLoopArgs {
     const float* enc;   // [B, Tp, J]
     int Tp, K, cap;
@@ -507,6 +518,12 @@ struct BeamLoopArgs {
     const BeamHwStream* hw_streams = nullptr;
     const int* st_in = nullptr;
     int* st_out = nullptr;
+    // token log-probs (false: not kept): yp beside ys / ts -- in LDS, or yp_g [B][2][K][cap] where ys_g / ts_g are used; nb: the
+    // offline N-best outputs; yp_out: the resumed search's side block [B][K][Tp], the token log-probs of each survivor's suffix
+    bool want_yp = false;
+    float* yp_g = nullptr;
+    BeamNbest nb;
+    float* yp_out = nullptr;
 };
 struct GreedyLaunch {
     bool valid = false;  // a launch with inter-workgroup waits (parts > 1 / two beam slabs) that can be repeated without them
@@ -557,6 +574,8 @@ struct BeamState {       // device arrays; hypotheses double-buffered by frame p
     int Tp = 0;
     int* ys;             // [2][B][K][cap] tokens without the ctx-blank prefix
     int* ts;             // [2][B][K][cap]
+    float* yp = nullptr; // [2][B][K][cap] token log-probs, parallel to ts (null: not kept)
+    float* yp_out = nullptr;   // resume: side block [B][K][Tp] (null: not asked for)
     int* n;              // [2][B][K]
     float *lp, *lp_next; // [B][K] hypothesis log-probs (-inf = empty slot)
     long long *ctx, *ctx_next;  // [B][K][2] decoder inputs
@@ -602,6 +621,11 @@ struct BeamArgs {
     const BeamHwStream* hw_streams = nullptr;
     const int* st_in = nullptr;
     int* st_out = nullptr;
+    // Token log-probs and N-best (semantics in include/k2hip.h).  Both null: nothing is kept beyond the best hypothesis.  nb: the
+    // offline search also writes its final hypotheses in pick order; yp_out [B][K][Tp] (resume): the token log-probs of each
+    // survivor's suffix, a side block beside rout as st_out is.
+    BeamNbest nb;
+    float* yp_out = nullptr;
 };
 // launches of the search since the process started, by instantiation: [0] HW = false, [1] HW = true (k2hip_debug.h)
 void beam_launch_counts(long long* plain, long long* hw);

@@ -632,6 +632,7 @@ void Engine::online_step_impl(const int* slots, const float* const* chunks, cons
         if (*reinterpret_cast<int*>(pin)) failf(K2HIP_ERR_HIP, "online beam search: a hypothesis outgrew its buffer");
         memcpy(beam->out, pin + 16, (size_t)o_hout);
         if (bhw) memcpy(bhw->st_out, pin + 16 + o_hout, (size_t)nb_hst);
+        fetch_beam_yp();
     } else {
         finish_tokens(d_tok, d_ts, d_n, d_ovf, B, Tp, tokens, ts, n_tokens);
     }

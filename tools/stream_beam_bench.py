@@ -1,6 +1,6 @@
 """Streaming tick under modified beam search next to greedy, on the same audio.
 
-    python tools/stream_beam_bench.py [preset] [streams] [seconds] [beam] [--hotwords N]   (defaults: zipformer2-streaming-zh 128 20 4)
+    python tools/stream_beam_bench.py [preset] [streams] [seconds] [beam] [--hotwords N] [--nbest N]   (defaults: zipformer2-streaming-zh 128 20 4)
 
 N streams of the synthetic `preset` model each buffer an utterance of `seconds` s; the tool decodes all of them chunk by chunk
 (one k2hip_online_step per tick over the whole group) once with greedy_search and once with modified_beam_search, reports the
@@ -8,7 +8,9 @@ median ms per tick of each, and holds the first few streams' beam results to the
 oracle's own concatenated chunks; a difference is excused only where the oracle's margin at the first differing frame is below
 LOGIT_TOL).  --hotwords N: two more beam runs with a hotword graph attached to EVERY stream -- an empty one (the biased kernels with
 every bonus 0) and N phrases of 2 - 5 tokens drawn from the unbiased beam run's output (as tools/hotword_bench.py draws them) -- and a
-second unbiased run behind them, their tick times printed beside the unbiased and the greedy one.  One JSON line on stdout."""
+second unbiased run behind them, their tick times printed beside the unbiased and the greedy one.  --nbest N: one more beam run with
+Model.set_nbest(N) (alternatives and token log-probs kept per stream), its tick time beside the others and the results held equal to
+the plain beam run's.  One JSON line on stdout."""
 import json
 import os
 import sys
@@ -28,6 +30,11 @@ n_hotwords = None
 if "--hotwords" in argv:
     i = argv.index("--hotwords")
     n_hotwords = int(argv[i + 1])
+    del argv[i: i + 2]
+n_best = None
+if "--nbest" in argv:
+    i = argv.index("--nbest")
+    n_best = int(argv[i + 1])
     del argv[i: i + 2]
 preset = argv[0] if len(argv) > 0 else "zipformer2-streaming-zh"
 N = int(argv[1]) if len(argv) > 1 else 128
@@ -86,6 +93,17 @@ def main():
                       "beam_hotwords_ms_per_tick": round(float(np.median(h_ms)), 3),
                       "beam_again_ms_per_tick": round(float(np.median(b2_ms)), 3),
                       "streams_moved_by_the_bias": int(sum(a != b for a, b in zip(h_res, b_res)))}
+        if n_best is not None:
+            rec.model.set_decoding_method("modified_beam_search", beam)
+            rec.model.set_nbest(n_best)
+            try:
+                n_ms, n_res = run(rec, feats, "modified_beam_search", beam)
+            finally:
+                rec.model.set_nbest(1)
+            if n_res != b_res:
+                raise SystemExit("keeping the alternatives changed the results")
+            hw_out["nbest"] = n_best
+            hw_out["beam_nbest_ms_per_tick"] = round(float(np.median(n_ms)), 3)
         import parity
         from test_online_beam_gpu import oracle_frames
         exact = excused = 0
