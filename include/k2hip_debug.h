@@ -63,15 +63,23 @@ int32_t k2hip_debug_gemm_run(k2hip_model_t* model, const float* A, const float* 
 /* ONE launch of the launcher named `op` (csrc/kernels.h: attn_scores_softmax, attn_av_out, attn_av_out_ring, attn_proj_av_out_ring,
  * nonlin_av_out_ring, attn_stream_ring, attn_stream, glu_causal_conv, biasnorm, bypass, biasnorm_bypass, biasnorm_bypass_downsample,
  * downsample, downsample_full, upsample_combine, upsample_combine_downsample, glu_dwconv1d_swoosh, glu_dwconv1d_dswish, dwconv1d_swoosh,
- * dwconv7x7; gemm and gemm_glu_causal_conv: see below) on host operands, on the engine's stream.  iargs: the launcher's integer arguments in its own order (a RingRef counts as
- * slot_stride, off; downsample_full's segments put n, ld[n], col1[n], lz_Td, lz_ds, lz_Do in front).  bufs / buf_bytes: its pointer
+ * dwconv7x7; the Conformer's conformer_qprep, conformer_scores_softmax, conformer_softmax_shift, conformer_softmax_shift_stream,
+ * slice_rows, dwconv_valid_dswish; Zipformer v1's z1_pool, z1_attn, z1_glu_conv, z1_norm_bypass, z1_attn_downsample, z1_combine, z1_mean,
+ * z1_add_bcast, z1_group_rows; the LSTM's lstm_cell, lstm_cell_rows, lstm_add_frame, lstm_norm_frame, add_inplace, gather_rows,
+ * scatter_rows; basicnorm, conv0_pad1_dswish, conv0_nopad_dswish; gemm and gemm_glu_causal_conv: see below) on host operands, on the
+ * engine's stream.  iargs: the launcher's integer arguments in its own order (a RingRef counts as slot_stride, off; downsample_full's
+ * segments put n, ld[n], col1[n], lz_Td, lz_ds, lz_Do in front; long long strides and offsets -- slot_stride, off, avg_off, len_off,
+ * ldgx, SY, pstride, lstride, add_inplace's n -- are integer arguments like the ints).  A float argument (`scaling` of conformer_qprep
+ * and conformer_scores_softmax) travels in its place among the integer arguments as its IEEE-754 bit pattern, zero-extended: 1.0f is
+ * 0x3f800000.  Default arguments are passed explicitly (ldq = 0: rows of 3 D floats / of D floats).  bufs / buf_bytes: its pointer
  * arguments in order (a RingRef as pool, slots, chunks; the segments as src[n], lz_orig, lz_xd, lz_scale), each uploaded whole -- in
  * place operands (x of attn_av_out, the state pool, int arrays) work as they are; NULL or 0 bytes passes a null pointer.  Every buffer
  * sits between two 16 KB guards of 0xff bytes (NaN): a read past either end that reaches the result shows as NaN, and a guard that
  * changed fails the call (K2HIP_ERR_INVALID, naming the buffer).  After the launch the buffers flagged in out_mask (bit k = bufs[k]) are
  * downloaded.  A shape the launcher refuses returns K2HIP_ERR_UNSUPPORTED with nothing launched and nothing downloaded.  Branch
- * switches (K2HIP_ATTN_LONG, K2HIP_DW1D_TT, K2HIP_DW7_TILED) go through k2hip_debug_set_switch.  tests/test_kernels_gpu.py compares each
- * kernel with a float64 reference computed on the host.
+ * switches (K2HIP_ATTN_LONG, K2HIP_DW1D_TT, K2HIP_DW7_TILED, K2HIP_CONFORMER_GEMM_SCORES) go through k2hip_debug_set_switch.
+ * tests/test_kernels_gpu.py (Zipformer2) and tests/test_family_kernels_gpu.py (Conformer, Zipformer v1, LSTM) compare each kernel with
+ * a float64 reference computed on the host.
  * Two more ops launch the GEMM in every form GemmArgs (csrc/kernels.h) can say (tests/test_gemm_forms_gpu.py):
  *   "gemm": ONE gemm() call.  iargs: GemmArgs' integer and stride fields in their declared order -- M, N, K, lda, ldw, ldc, ldr, act,
  *     act_cols, w_kn, nb0, nb1, sA0, sA1, sW0, sW1, sC0, sC1, sR0, sR1, sBias0, cv_Fout, cv_Tout, cv_Tin, cv_Fin, cv_C, cv_st, cv_sf,

@@ -1616,13 +1616,14 @@ void Engine::debug_gemm_host(const float* hA, const float* hW, const float* hb, 
     K2_HIP(copy_blocking(hC, C, sizeof(float) * (size_t)M * ldo, hipMemcpyDeviceToHost));
 }
 
-// test hook: ONE launch of a launcher of kernels.h on the caller's host operands (tests/test_kernels_gpu.py).  Buffer k of the call is
+// test hook: ONE launch of a launcher of kernels.h on the caller's host operands (tests/test_kernels_gpu.py, test_family_kernels_gpu.py).  Buffer k of the call is
 // uploaded into an allocation with kGuard bytes of 0xff (NaN) on either side, so a read past either end whose value reaches the result
 // shows as NaN; after the launch the guards must still hold 0xff, else a write went past the buffer and the call fails naming it.
 // A launcher that refuses the shape (a false return, a K2_REQUIRE) fails as K2HIP_ERR_UNSUPPORTED before anything is launched or
 // downloaded.  iargs: the launcher's int arguments in its own order, a RingRef counting as (slot_stride, off); bufs: its pointer
 // arguments in order, a RingRef as (pool, slots, chunks), a FullDimSegs as (src[0 .. n), lz_orig, lz_xd, lz_scale) with its ints
-// (n, ld[0 .. n), col1[0 .. n), lz_Td, lz_ds, lz_Do) in front of the launcher's.  A null buffer (or 0 bytes) passes nullptr.
+// (n, ld[0 .. n), col1[0 .. n), lz_Td, lz_ds, lz_Do) in front of the launcher's.  A null buffer (or 0 bytes) passes nullptr.  A float
+// argument (conformer_qprep's and conformer_scores_softmax's scaling) sits among the ints as its IEEE-754 bits.
 static const bool kDebugOpSet = (Engine::debug_op = &Engine::debug_op_host, true);
 void Engine::debug_op_host(const char* op, const int64_t* iargs, int n_iargs, void* const* bufs, const int64_t* buf_bytes, int n_bufs,
                            uint32_t out_mask) {
@@ -1658,6 +1659,12 @@ void Engine::debug_op_host(const char* op, const int64_t* iargs, int n_iargs, vo
     auto L = [&]() -> long long {
         K2_REQUIRE(ni < n_iargs, "debug_op_run %s: too few int arguments (%d)", op, n_iargs);
         return (long long)iargs[ni++];
+    };
+    auto F = [&]() -> float {   // a float argument: its IEEE-754 bit pattern in the int slot
+        const uint32_t u = (uint32_t)L();
+        float f;
+        memcpy(&f, &u, sizeof f);
+        return f;
     };
     auto P = [&]() -> float* {
         K2_REQUIRE(nbuf < n_bufs, "debug_op_run %s: too few buffers (%d)", op, n_bufs);
@@ -1819,6 +1826,145 @@ void Engine::debug_op_host(const char* op, const int64_t* iargs, int n_iargs, vo
             float *x = P(), *w = P(), *b = P(), *y = P();
             const int B = I(), Tin = I(), Tout = I(), tpad = I(), F = I(), C = I();
             dwconv7x7(c, x, w, b, y, B, Tin, Tout, tpad, F, C);
+        // ---- offline / streaming Conformer (conformer.hip); a float argument travels in the int slot as its IEEE-754 bits
+        } else if (name == "conformer_qprep") {
+            float *qkv = P(), *bu = P(), *bv = P(), *qu = P(), *qv = P();
+            const int M = I(), D = I();
+            const float scaling = F();
+            const int ldq = I();
+            conformer_qprep(c, qkv, bu, bv, qu, qv, M, D, scaling, ldq);
+        } else if (name == "conformer_scores_softmax") {
+            float *qu = P(), *qv = P(), *kmat = P();
+            const int ldk = I();
+            float *pp = P(), *aw = P();
+            const int B = I(), H = I(), T = I(), Tp = I(), D = I(), ldq = I();
+            float *bu = P(), *bv = P();
+            const float scaling = F();
+            took = conformer_scores_softmax(c, qu, qv, kmat, ldk, pp, aw, B, H, T, Tp, D, ldq, bu, bv, scaling);
+        } else if (name == "conformer_softmax_shift") {
+            float *ac = P(), *bd = P();
+            const int Z = I(), T = I(), Tp = I(), NPp = I();
+            conformer_softmax_shift(c, ac, bd, Z, T, Tp, NPp);
+        } else if (name == "conformer_softmax_shift_stream") {
+            float *ac = P(), *bd = P();
+            const long long* plen = reinterpret_cast<const long long*>(P());
+            const int B = I(), H = I(), Tc = I(), left = I(), KLp = I(), NPp = I();
+            conformer_softmax_shift_stream(c, ac, bd, plen, B, H, Tc, left, KLp, NPp);
+        } else if (name == "slice_rows") {
+            float *in = P(), *out = P();
+            const int B = I(), Tin = I(), row0 = I(), Tout = I(), D = I();
+            slice_rows(c, in, out, B, Tin, row0, Tout, D);
+        } else if (name == "dwconv_valid_dswish") {
+            float *cat = P(), *w = P(), *bias = P(), *y = P();
+            const int B = I(), Tc = I(), D = I(), K = I();
+            dwconv_valid_dswish(c, cat, w, bias, y, B, Tc, D, K);
+        // ---- Zipformer v1 (zipformer1.hip)
+        } else if (name == "z1_pool") {
+            float *x = P(), *pool = P();
+            const long long ss = L(), avg_off = L(), len_off = L();
+            const int* slots = reinterpret_cast<const int*>(P());
+            float* out = P();
+            const int B = I(), Tc = I(), D = I();
+            z1_pool(c, x, pool, ss, avg_off, len_off, slots, out, B, Tc, D);
+        } else if (name == "z1_attn") {
+            float* qkvp = P();
+            const int ld = I();
+            float *kcat = P(), *pp = P(), *aw = P();
+            const int B = I(), Tc = I(), Lc = I(), KLp = I(), H = I(), A = I();
+            z1_attn(c, qkvp, ld, kcat, pp, aw, B, Tc, Lc, KLp, H, A);
+        } else if (name == "z1_glu_conv") {
+            float *x2 = P(), *pool = P();
+            const long long ss = L(), off = L();
+            const int* slots = reinterpret_cast<const int*>(P());
+            float *w = P(), *bias = P(), *y = P();
+            const int B = I(), Tc = I(), D = I(), K = I();
+            z1_glu_conv(c, x2, pool, ss, off, slots, w, bias, y, B, Tc, D, K);
+        } else if (name == "z1_norm_bypass") {
+            float *x = P(), *orig = P(), *le = P(), *bs = P(), *y = P();
+            const int M = I(), D = I();
+            z1_norm_bypass(c, x, orig, le, bs, y, M, D);
+        } else if (name == "z1_attn_downsample") {
+            float *x = P(), *query = P(), *y = P();
+            const int B = I(), T = I(), Din = I(), ldy = I(), ds = I();
+            z1_attn_downsample(c, x, query, y, B, T, Din, ldy, ds);
+        } else if (name == "z1_mean") {
+            float *x = P(), *mean = P();
+            const int B = I(), T = I(), D = I();
+            z1_mean(c, x, mean, B, T, D);
+        } else if (name == "z1_add_bcast") {
+            float *x = P(), *v = P();
+            const int B = I(), T = I(), D = I();
+            z1_add_bcast(c, x, v, B, T, D);
+        } else if (name == "z1_group_rows") {
+            float *x = P(), *grp = P();
+            const int B = I(), T = I(), Din = I(), ds = I();
+            z1_group_rows(c, x, grp, B, T, Din, ds);
+        } else if (name == "z1_combine") {
+            float* s1 = P();
+            const int d1 = I();
+            float* s2 = P();
+            const int d2 = I();
+            float *w1 = P(), *ub = P();
+            const int ds = I(), B = I(), T = I(), Td = I();
+            float* y = P();
+            z1_combine(c, s1, d1, s2, d2, w1, ub, ds, B, T, Td, y);
+        // ---- LSTM transducer (lstm.hip) and the elementwise.hip kernels only these families use
+        } else if (name == "lstm_cell") {
+            float* gx = P();
+            const long long ldgx = L();
+            float* gh = P();
+            const int ldgh = I();
+            float *cc = P(), *hf = P();
+            const int B = I(), Hh = I();
+            lstm_cell(c, gx, ldgx, gh, ldgh, cc, hf, B, Hh);
+        } else if (name == "lstm_cell_rows") {
+            float *gates = P(), *cc = P(), *hf = P();
+            const int rows = I(), Hh = I();
+            lstm_cell_rows(c, gates, cc, hf, rows, Hh);
+        } else if (name == "lstm_add_frame") {
+            float* Y = P();
+            const long long SY = L();
+            float* hp = P();
+            const long long pstride = L();
+            const int S = I();
+            float *h = P(), *x1 = P();
+            const int n = I(), B = I(), T = I(), D = I(), lo = I(), s = I();
+            lstm_add_frame(c, Y, SY, hp, pstride, S, h, x1, n, B, T, D, lo, s);
+        } else if (name == "lstm_norm_frame") {
+            float *x1 = P(), *fp = P();
+            const long long pstride = L();
+            const int S = I();
+            float *b2 = P(), *eps = P();
+            const long long lstride = L();
+            float* Y = P();
+            const long long SY = L();
+            const int n = I(), B = I(), T = I(), D = I(), lo = I(), s = I();
+            lstm_norm_frame(c, x1, fp, pstride, S, b2, eps, lstride, Y, SY, n, B, T, D, lo, s);
+        } else if (name == "add_inplace") {
+            float *a = P(), *b = P();
+            const long long n = L();
+            add_inplace(c, a, b, n);
+        } else if (name == "gather_rows" || name == "scatter_rows") {
+            float* pool = P();
+            const long long ss = L(), off = L();
+            const int* slots = reinterpret_cast<const int*>(P());
+            float* io = P();
+            if (name == "gather_rows") {
+                const int B = I(), width = I();
+                gather_rows(c, pool, ss, off, slots, io, B, width);
+            } else {
+                const int ldin = I(), B = I(), width = I();
+                scatter_rows(c, pool, ss, off, slots, io, ldin, B, width);
+            }
+        } else if (name == "basicnorm") {
+            float *x = P(), *le = P(), *y = P();
+            const int M = I(), D = I();
+            basicnorm(c, x, le, y, M, D);
+        } else if (name == "conv0_pad1_dswish" || name == "conv0_nopad_dswish") {
+            float *x = P(), *w = P(), *b = P(), *y = P();
+            const int B = I(), T = I(), Fq = I();
+            if (name == "conv0_pad1_dswish") conv0_pad1_dswish(c, x, w, b, y, B, T, Fq);
+            else conv0_nopad_dswish(c, x, w, b, y, B, T, Fq);
         } else {
             failf(K2HIP_ERR_INVALID, "debug_op_run: unknown op '%s'", op);
         }
