@@ -97,6 +97,20 @@ namespace K2TransducerAsr.Hip
         [DllImport(Lib)] internal static extern int k2hip_hotwords_step(IntPtr hotwords, int state, long token, out int nextState, out float bonus);
         [DllImport(Lib)] internal static extern int k2hip_hotwords_pending(IntPtr hotwords, int state, out float pending);
         [DllImport(Lib)] internal static extern int k2hip_set_hotwords(IntPtr model, IntPtr hotwords /* IntPtr.Zero clears */);
+        // n-gram LM shallow fusion in the offline modified beam search (k2hip.h "n-gram LM shallow fusion"; INTEGRATION.md "N-gram LM").
+        // ids: the entries' token ids back to back (-1 <s>, -2 </s>, -3 the LM's <unk>), orders: tokens per entry, natural-log weights.
+        // The model copies the scaled tables: destroy the LM after k2hip_set_ngram_lm.
+        [DllImport(Lib)] internal static extern int k2hip_ngram_lm_create(long[] ids, int[] orders, float[] logProbs, float[] backoffs, long nEntries, int vocabSize, out IntPtr lm);
+        [DllImport(Lib)] internal static extern int k2hip_tokens_load(string tokensPath, out IntPtr tokens);
+        [DllImport(Lib)] internal static extern int k2hip_tokens_destroy(IntPtr tokens);
+        [DllImport(Lib)] internal static extern int k2hip_ngram_lm_load(IntPtr tokens, string path, out IntPtr lm);
+        [DllImport(Lib)] internal static extern int k2hip_ngram_lm_destroy(IntPtr lm);
+        [DllImport(Lib)] internal static extern int k2hip_ngram_lm_order(IntPtr lm);
+        [DllImport(Lib)] internal static extern int k2hip_ngram_lm_num_states(IntPtr lm);
+        [DllImport(Lib)] internal static extern long k2hip_ngram_lm_num_arcs(IntPtr lm);
+        [DllImport(Lib)] internal static extern int k2hip_ngram_lm_start_state(IntPtr lm);
+        [DllImport(Lib)] internal static extern int k2hip_ngram_lm_step(IntPtr lm, int state, long token, out int nextState, out float logProb);
+        [DllImport(Lib)] internal static extern int k2hip_set_ngram_lm(IntPtr model, IntPtr lm /* IntPtr.Zero clears */, float scale);
         // streaming: the graph belongs to the stream (IntPtr.Zero detaches; only before the stream's first chunk or after a reset)
         [DllImport(Lib)] internal static extern int k2hip_online_stream_set_hotwords(IntPtr stream, IntPtr hotwords);
         [DllImport(Lib)] internal static extern int k2hip_beam_stream_set_hotwords(IntPtr stream, IntPtr hotwords);

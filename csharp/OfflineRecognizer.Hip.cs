@@ -152,7 +152,28 @@ namespace K2TransducerAsr
         }
         public List<OfflineStream.Alternative> GetAlternatives(OfflineStream stream) { return stream.Alternatives; }
 
+        // sherpa's lm / lm_scale for an n-gram: a text ARPA file over the token strings of tokens.txt, fused into modified_beam_search
+        // (k2hip.h "n-gram LM shallow fusion"); arpaPath = null clears.  The model keeps its own copy of the scaled tables.
+        public void SetNgramLm(string arpaPath, float scale)
+        {
+            if (!(_offlineProj is OfflineProjOfHip proj)) throw new InvalidOperationException("SetNgramLm: not a libk2hip recognizer");
+            if (arpaPath == null)
+            {
+                K2Hip.Check(K2Hip.k2hip_set_ngram_lm(proj.Handle, IntPtr.Zero, 0f), "SetNgramLm failed");
+                return;
+            }
+            K2Hip.Check(K2Hip.k2hip_tokens_load(_tokensFilePath, out IntPtr tokens), "SetNgramLm: tokens");
+            try
+            {
+                K2Hip.Check(K2Hip.k2hip_ngram_lm_load(tokens, arpaPath, out IntPtr lm), "SetNgramLm: load failed");
+                try { K2Hip.Check(K2Hip.k2hip_set_ngram_lm(proj.Handle, lm, scale), "SetNgramLm failed"); }
+                finally { K2Hip.k2hip_ngram_lm_destroy(lm); }
+            }
+            finally { K2Hip.k2hip_tokens_destroy(tokens); }
+        }
+
         // the constructor's early branch (see the header): everything :30-68 does, for a .k2w container
+        private string _tokensFilePath;   // (SetNgramLm reads the ARPA words through the same token table)
         private void InitHip(string encoderFilePath, string decoderFilePath, string tokensFilePath, string decodingMethod, int sampleRate, int featureDim)
         {
             K2Hip.SplitSpec(encoderFilePath, decoderFilePath, out string k2wPath, out int device);
@@ -162,6 +183,7 @@ namespace K2TransducerAsr
             _offlineModel.CustomMetadata = proj.CustomMetadata;       // what :73, :95, :191, :307, :367 read
             _offlineModel.FeatureDim = featureDim;                    // :31
             _tokens = File.ReadAllLines(tokensFilePath);              // :32
+            _tokensFilePath = tokensFilePath;
             _frontendConfEntity = new FrontendConfEntity();           // :34-37
             _frontendConfEntity.fs = sampleRate;
             _frontendConfEntity.n_mels = featureDim;

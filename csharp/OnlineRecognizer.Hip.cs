@@ -172,12 +172,35 @@ namespace K2TransducerAsr
         }
         public List<OnlineStream.Alternative> GetAlternatives(OnlineStream stream) { return stream.Alternatives; }
 
+        // sherpa's lm / lm_scale for an n-gram: a text ARPA file over the token strings of tokens.txt, fused into modified_beam_search
+        // (k2hip.h "n-gram LM shallow fusion"); arpaPath = null clears.  A stream keeps the LM it decoded its first chunk with: set it
+        // before the streams start, or reset them afterwards.
+        public void SetNgramLm(string arpaPath, float scale)
+        {
+            if (_hipModel == null) throw new InvalidOperationException("SetNgramLm: not a libk2hip recognizer");
+            if (arpaPath == null)
+            {
+                K2Hip.Check(K2Hip.k2hip_set_ngram_lm(_hipModel.Handle, IntPtr.Zero, 0f), "SetNgramLm failed");
+                return;
+            }
+            K2Hip.Check(K2Hip.k2hip_tokens_load(_tokensFilePath, out IntPtr tokens), "SetNgramLm: tokens");
+            try
+            {
+                K2Hip.Check(K2Hip.k2hip_ngram_lm_load(tokens, arpaPath, out IntPtr lm), "SetNgramLm: load failed");
+                try { K2Hip.Check(K2Hip.k2hip_set_ngram_lm(_hipModel.Handle, lm, scale), "SetNgramLm failed"); }
+                finally { K2Hip.k2hip_ngram_lm_destroy(lm); }
+            }
+            finally { K2Hip.k2hip_tokens_destroy(tokens); }
+        }
+        private string _tokensFilePath;   // (SetNgramLm reads the ARPA words through the same token table)
+
         // the constructor's early branch (see the header): everything :21-57 does, for a .k2w container
         private void InitHip(string encoderFilePath, string decoderFilePath, string tokensFilePath, string decodingMethod, int sampleRate, int featureDim)
         {
             K2Hip.SplitSpec(encoderFilePath, decoderFilePath, out string k2wPath, out int device);
             _hipModel = new HipOnlineModel(k2wPath, device);
             _tokens = File.ReadAllLines(tokensFilePath);                                // :24
+            _tokensFilePath = tokensFilePath;
             _hipFused = decodingMethod != "greedy_search_operators";
             if (decodingMethod == "modified_beam_search")
                 K2Hip.Check(K2Hip.k2hip_set_decoding_method(_hipModel.Handle, "modified_beam_search", 4), "OnlineRecognizer: decoding method");

@@ -55,6 +55,7 @@ typedef struct k2hip_online_stream k2hip_online_stream_t;
 typedef struct k2hip_beam_stream k2hip_beam_stream_t;
 typedef struct k2hip_tokens k2hip_tokens_t;
 typedef struct k2hip_hotwords k2hip_hotwords_t;
+typedef struct k2hip_ngram_lm k2hip_ngram_lm_t;
 
 /* Fixed ids of the reference: OfflineModel.cs:18-20. */
 #define K2HIP_BLANK_ID 0
@@ -376,6 +377,70 @@ int32_t k2hip_set_hotwords(k2hip_model_t* model, const k2hip_hotwords_t* hw);
  * search ignore an attached graph. */
 int32_t k2hip_online_stream_set_hotwords(k2hip_online_stream_t* s, const k2hip_hotwords_t* hw);
 int32_t k2hip_beam_stream_set_hotwords(k2hip_beam_stream_t* s, const k2hip_hotwords_t* hw);
+
+/* ---- n-gram LM shallow fusion in the modified beam search, offline and streaming ----------------------------------------------------------------
+ * The reference has no beam search and no LM; the semantics are the project's own, defined here and in DESIGN.md "N-gram LM
+ * shallow fusion".
+ *
+ * LM: a back-off n-gram of order N, 1 <= N <= 5, over the model's own token ids.  An entry is (ids[1..n], log_prob, backoff), natural
+ * log, float32, backoff 0 where absent.  Blank (0) and unk (2) may not occur in an entry; the sentence marks and the LM's own unknown
+ * word are the pseudo ids below.  Automaton: state 0 is the empty history; one state per history of length 1 .. N-1 that is the
+ * history of some kept entry, numbered by (length, then ids lexicographically, <s> = -1 first).  A state has its explicit arcs
+ * (token -> log_prob, next state), a back-off weight (the backoff of the history's own entry) and a back-off state (the longest
+ * proper suffix of its history that is a state).  The next state of (h, w) is the longest suffix of h.w, of length <= N-1, that is
+ * a state.
+ * Step(s, w), w a real token: acc = 0; while w has no arc in s and s != 0: acc = acc + bow(s), s = backoff(s); the result is
+ * acc + log_prob(arc), in float32 in exactly that order.  At state 0 a token without a unigram scores the LM's <unk> unigram and
+ * moves to state 0; if such a token exists and the LM has no <unk> unigram, creation fails and names the first such token.  Blank and
+ * unk append nothing: state unchanged, 0.
+ * Start state: the state of history <s> if the LM has kept entries with that history, else 0.  </s> and <s> as PREDICTED words are
+ * ignored (the <s> unigram still gives the back-off weight of history <s>); n-grams of order >= 2 that contain <unk> are dropped (a
+ * token without a unigram returns to state 0, so they are never reached).  No end-of-sentence cost is ever applied.
+ * Creation fails with K2HIP_ERR_INVALID, naming the entry (or the line), for: an order outside [1, 5], an id out of range, blank / unk
+ * in an entry, a sentence mark inside a history, a non-finite number, a duplicate entry, an n-gram whose history has no entry of its
+ * own, and a model of more than K2HIP_NGRAM_MAX_ARCS entries.
+ * A k2hip_ngram_lm_t belongs to no model and needs no GPU. */
+#define K2HIP_NGRAM_MAX_ARCS (1 << 24)
+#define K2HIP_NGRAM_MAX_ORDER 5
+#define K2HIP_NGRAM_BOS (-1) /* <s> */
+#define K2HIP_NGRAM_EOS (-2) /* </s> */
+#define K2HIP_NGRAM_UNK (-3) /* the LM's <unk>: the fallback for tokens without a unigram, never the acoustic unk id */
+/* ids: the entries' tokens back to back; orders / log_probs / backoffs [n_entries] */
+int32_t k2hip_ngram_lm_create(const int64_t* ids, const int32_t* orders, const float* log_probs, const float* backoffs, int64_t n_entries,
+                              int32_t vocab_size, k2hip_ngram_lm_t** out);
+/* a text ARPA file whose words are the token strings of tokens.txt.  <unk> is always the LM's fallback; <s> and </s> are the
+ * sentence marks unless they are themselves lines of tokens.txt.  log10 values are parsed as double, multiplied by ln 10 in double,
+ * then rounded to float32.  Refused with K2HIP_ERR_INVALID and the line number: a missing \data\ or \end\, counts that disagree with
+ * the sections, an order above 5, an unknown word, a non-finite number, and everything k2hip_ngram_lm_create refuses. */
+int32_t k2hip_ngram_lm_load(const k2hip_tokens_t* tokens, const char* path, k2hip_ngram_lm_t** out);
+int32_t k2hip_ngram_lm_destroy(k2hip_ngram_lm_t* lm);
+int32_t k2hip_ngram_lm_order(const k2hip_ngram_lm_t* lm);        /* -1 for NULL, as the next three */
+int32_t k2hip_ngram_lm_num_states(const k2hip_ngram_lm_t* lm);
+int64_t k2hip_ngram_lm_num_arcs(const k2hip_ngram_lm_t* lm);
+int32_t k2hip_ngram_lm_start_state(const k2hip_ngram_lm_t* lm);
+/* the host walk of Step above, unscaled */
+int32_t k2hip_ngram_lm_step(const k2hip_ngram_lm_t* lm, int32_t state, int64_t token, int32_t* next_state, float* log_prob);
+/* lm = NULL clears; scale finite and >= 0.  Checks vocab_size against the model and uploads the sparse tables, every weight
+ * multiplied by scale once on the host in float32 (the device only adds); the model keeps its own copy, so lm may be destroyed
+ * afterwards.  Not while submitted batches are in flight.
+ * Search: every hypothesis carries an LM state, the start hypothesis the start state.  A frame's top-`beam` selection uses the same
+ * sums as without an LM; a selected candidate that appends a real token v then gets (sum + hotword bonus) + Step(state, v), and
+ * the merge of candidates that spell the same sequence follows.  Blank and unk leave the state alone and earn nothing.  Nothing is
+ * pending or taken back at the end: the final pick and every reported score (N-best scores included) use the log-prob with the LM
+ * terms.  Token log-probs and the beam trace stay the unbiased acoustic terms.  Works together with k2hip_set_hotwords and
+ * k2hip_set_nbest.
+ * One setting per model.  Unlike the model-level hotword list it applies to BOTH searches: wherever the offline modified beam search
+ * runs (as k2hip_set_hotwords), and in the streaming one (k2hip_online_step under modified_beam_search, k2hip_beam_search_chunk),
+ * together with the streams' own hotword graphs.  Greedy search, the CTC search and the single-stream path ignore it.  No LM, a
+ * cleared LM and scale = 0: bit for bit the plain results, from the plain kernels.
+ * STREAMING: after every step a stream holds exactly what the offline search with the same LM gives over all frames so far; the LM
+ * state of every saved hypothesis crosses the chunk boundary.  A stream keeps the LM setting it decoded its first chunk with: after
+ * k2hip_set_ngram_lm changes or clears it (every call that leaves an LM set is a new setting; scale = 0 is "none"), k2hip_online_step
+ * and k2hip_beam_search_chunk fail with K2HIP_ERR_INVALID ("... reset the stream first") for a call that names such a stream, and the
+ * failed call changes no stream.  A reset returns every hypothesis to the start state of the LM then set.  A k2hip_set_ngram_lm that
+ * lands between a streaming call's checks and its launch is caught under the lock that covers the launch (K2HIP_ERR_INVALID,
+ * "... call again"; no stream changes): saved LM states never meet another LM's tables. */
+int32_t k2hip_set_ngram_lm(k2hip_model_t* model, const k2hip_ngram_lm_t* lm, float scale);
 
 /* ---- N-best hypotheses and token log-probs of the modified beam search ---------------------------------------------------------
  * Token log-prob: when a selected candidate (hypothesis k, token v), v outside {blank, unk}, is appended at frame t, its token

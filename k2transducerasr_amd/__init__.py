@@ -13,6 +13,7 @@ from . import config, k2w, synth  # noqa: F401
 from .binding import (  # noqa: F401
     BeamStream,
     Hotwords,
+    NgramLm,
     K2HipError,
     Model,
     OfflineRecognizer,
@@ -31,6 +32,7 @@ from .binding import (  # noqa: F401
 __all__ = [
     "BeamStream",
     "Hotwords",
+    "NgramLm",
     "K2HipError",
     "Model",
     "OfflineRecognizer",

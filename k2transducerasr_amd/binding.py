@@ -192,6 +192,85 @@ class TokenTable:
             pass
 
 
+class NgramLm:
+    """A back-off n-gram LM over the model's own tokens for shallow fusion in the offline modified beam search (k2hip_ngram_lm_t;
+    include/k2hip.h "n-gram LM shallow fusion").  Host only: built, parsed and walked without a GPU.  `entries`: (ids, log_prob,
+    backoff) with natural-log float32 weights; NgramLm.BOS / EOS / UNK stand for <s>, </s> and the LM's own <unk>.  NgramLm.load
+    reads a text ARPA file whose words are the token strings of a TokenTable."""
+    BOS, EOS, UNK = -1, -2, -3
+
+    def _bind(self):
+        self._h = None
+        self._L = L = load_library()
+        L.k2hip_ngram_lm_create.argtypes = [lp, ip, fp, fp, C.c_int64, C.c_int32, C.POINTER(C.c_void_p)]
+        L.k2hip_ngram_lm_load.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_void_p)]
+        L.k2hip_ngram_lm_destroy.argtypes = [C.c_void_p]
+        for f in ("order", "num_states", "num_arcs", "start_state"):
+            getattr(L, "k2hip_ngram_lm_" + f).argtypes = [C.c_void_p]
+        L.k2hip_ngram_lm_num_arcs.restype = C.c_int64
+        L.k2hip_ngram_lm_step.argtypes = [C.c_void_p, C.c_int32, C.c_int64, ip, fp]
+        return L
+
+    def __init__(self, entries, vocab_size: int):
+        L = self._bind()
+        entries = [(list(e[0]), e[1], e[2] if len(e) > 2 else 0.0) for e in entries]
+        ids = np.ascontiguousarray([t for e in entries for t in e[0]] or [0], dtype=np.int64)
+        orders = np.ascontiguousarray([len(e[0]) for e in entries] or [0], dtype=np.int32)
+        lps = np.ascontiguousarray([e[1] for e in entries] or [0], dtype=np.float32)
+        bos = np.ascontiguousarray([e[2] for e in entries] or [0], dtype=np.float32)
+        h = C.c_void_p()
+        rc = L.k2hip_ngram_lm_create(_l(ids), _i(orders), _f(lps), _f(bos), len(entries), int(vocab_size), C.byref(h))
+        if rc != 0:
+            raise K2HipError(rc, L.k2hip_last_error().decode())
+        self._h = h
+
+    @classmethod
+    def load(cls, tokens: "TokenTable", path: str) -> "NgramLm":
+        lm = cls.__new__(cls)
+        L = lm._bind()
+        h = C.c_void_p()
+        rc = L.k2hip_ngram_lm_load(tokens._h, path.encode(), C.byref(h))
+        if rc != 0:
+            raise K2HipError(rc, L.k2hip_last_error().decode())
+        lm._h = h
+        return lm
+
+    @property
+    def order(self) -> int:
+        return self._L.k2hip_ngram_lm_order(self._h)
+
+    @property
+    def num_states(self) -> int:
+        return self._L.k2hip_ngram_lm_num_states(self._h)
+
+    @property
+    def num_arcs(self) -> int:
+        return self._L.k2hip_ngram_lm_num_arcs(self._h)
+
+    @property
+    def start_state(self) -> int:
+        return self._L.k2hip_ngram_lm_start_state(self._h)
+
+    def step(self, state: int, token: int):
+        """(next state, unscaled log-prob) of a hypothesis in `state` that appends `token`"""
+        n, b = C.c_int32(), C.c_float()
+        rc = self._L.k2hip_ngram_lm_step(self._h, state, token, C.byref(n), C.byref(b))
+        if rc != 0:
+            raise K2HipError(rc, self._L.k2hip_last_error().decode())
+        return n.value, np.float32(b.value)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.k2hip_ngram_lm_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Hotwords:
     """The hotword graph of the modified beam search, set per model for the offline search or per stream for the streaming one
     (k2hip_hotwords_t; include/k2hip.h "hotword biasing"): a trie of token-id phrases with Aho-Corasick failure links.  Host only: built and walked without a GPU.  `phrases`: sequences of token
@@ -462,6 +541,12 @@ class Model:
         self._L.k2hip_set_hotwords.argtypes = [C.c_void_p, C.c_void_p]
         self._chk(self._L.k2hip_set_hotwords(self._h, hotwords._h if hotwords is not None else None))
 
+    def set_ngram_lm(self, lm: Optional["NgramLm"] = None, scale: float = 0.0):
+        """k2hip_set_ngram_lm: shallow fusion of the n-gram LM, weighted by `scale`, in the modified beam search, offline and
+        streaming; None clears.  The model keeps its own copy of the scaled tables: lm.close() afterwards is fine."""
+        self._L.k2hip_set_ngram_lm.argtypes = [C.c_void_p, C.c_void_p, C.c_float]
+        self._chk(self._L.k2hip_set_ngram_lm(self._h, lm._h if lm is not None else None, float(scale)))
+
     def gemm_profile(self) -> np.ndarray:
         """[n, 8] rows (M, N, K, batch, act, has_residual, kind, us) of the last instrumented call"""
         n = C.c_int32(0)
@@ -684,10 +769,11 @@ class OfflineStream:
 class OfflineRecognizer:
     """OfflineRecognizer.cs:12-91 on the HIP backend; decoding_method "greedy_search" (the reference's only method) or
     "modified_beam_search" (BASELINE.json configs[2]).  hotwords: a Hotwords graph, or a list of token-id phrases scored
-    hotwords_score per matched token (sherpa's hotwords_file / hotwords_score); it biases modified_beam_search only."""
+    hotwords_score per matched token (sherpa's hotwords_file / hotwords_score); it biases modified_beam_search only.  ngram_lm: an
+    NgramLm fused with weight ngram_lm_scale (sherpa's lm / lm_scale), modified_beam_search only."""
 
     def __init__(self, weights_path: str, device: int = 0, decoding_method: str = "greedy_search", beam: int = 4, hotwords=None,
-                 hotwords_score: float = 1.5, nbest: int = 1):
+                 hotwords_score: float = 1.5, nbest: int = 1, ngram_lm: Optional["NgramLm"] = None, ngram_lm_scale: float = 0.3):
         self.model = Model(weights_path, device)
         self.model.set_decoding_method(decoding_method, beam)
         if nbest != 1:   # (streams then carry .alternatives() / .token_log_probs() after get_results)
@@ -696,6 +782,8 @@ class OfflineRecognizer:
             if not isinstance(hotwords, Hotwords):
                 hotwords = Hotwords(hotwords, hotwords_score, self.model.vocab_size)
             self.model.set_hotwords(hotwords)
+        if ngram_lm is not None:
+            self.model.set_ngram_lm(ngram_lm, ngram_lm_scale)
 
     def create_offline_stream(self) -> OfflineStream:  # CreateOfflineStream :71-75
         return OfflineStream(self.model)
@@ -980,12 +1068,16 @@ class BeamStream:
 
 class OnlineRecognizer:
     """OnlineRecognizer.cs:11-84 on the HIP backend; decoding_method "greedy_search" (the reference's) or "modified_beam_search"
-    (hypotheses carried from chunk to chunk: include/k2hip.h)."""
+    (hypotheses carried from chunk to chunk: include/k2hip.h).  ngram_lm: an NgramLm fused with weight ngram_lm_scale
+    under modified_beam_search (every hypothesis carries its LM state across the chunk boundary)."""
 
-    def __init__(self, weights_path: str, device: int = 0, decoding_method: str = "greedy_search", beam: int = 4):
+    def __init__(self, weights_path: str, device: int = 0, decoding_method: str = "greedy_search", beam: int = 4,
+                 ngram_lm: Optional["NgramLm"] = None, ngram_lm_scale: float = 0.3):
         self.model = Model(weights_path, device)
         _bind_online(self.model._L)
         self.model.set_decoding_method(decoding_method, beam)
+        if ngram_lm is not None:
+            self.model.set_ngram_lm(ngram_lm, ngram_lm_scale)
         a, b, c = C.c_int32(), C.c_int32(), C.c_int32()
         self.model._chk(self.model._L.k2hip_online_chunk_info(self.model.handle, C.byref(a), C.byref(b), C.byref(c)))
         self.chunk_length, self.shift_length, self.frames_per_chunk = a.value, b.value, c.value

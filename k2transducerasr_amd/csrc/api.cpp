@@ -3,7 +3,9 @@
 // OfflineRecognizer.cs:77-91,289-296).
 #include <algorithm>
 #include <atomic>
+#include <cmath>
 #include <fstream>
+#include <iterator>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -13,6 +15,7 @@
 #include "engine.h"
 #include "beam_hist.h"
 #include "hotwords.h"
+#include "ngram_lm.h"
 #include "../../include/k2hip_debug.h"
 
 using namespace k2hip;
@@ -96,6 +99,12 @@ struct k2hip_model {
     std::vector<PinVec> wav_pool;   // (declared behind `engine`: released first)
     // the hotword tables on the device (k2hip_set_hotwords): one allocation [next | bonus | pending], or null
     void* hw_dev = nullptr;
+    // the scaled n-gram LM tables on the device (k2hip_set_ngram_lm): one allocation, or null
+    void* lm_dev = nullptr;
+    // identity of the LM that is set (0 = none; a fresh number for every k2hip_set_ngram_lm that leaves one set) and its start state:
+    // what a stream notes with its first chunk (BeamHistory::begin_lm).  Written and read under the engine's lock.
+    uint64_t lm_serial = 0;
+    int lm_start = 0;
     // k2hip_set_nbest: 1 = off (the engine keeps nothing beyond the best hypothesis), n > 1 = alternatives and token log-probs are kept
     std::atomic<int> nbest{1};
     // the graphs attached to this model's streams (HwResident), by serial number; hw_uploads counts the uploads (k2hip_debug.h)
@@ -122,6 +131,13 @@ struct k2hip_model {
             try {
                 engine.synchronize();
                 engine.dev_free(hw_dev);
+            } catch (...) {
+            }
+        }
+        if (lm_dev) {
+            try {
+                engine.synchronize();
+                engine.dev_free(lm_dev);
             } catch (...) {
             }
         }
@@ -639,6 +655,109 @@ int32_t k2hip_set_hotwords(k2hip_model_t* model, const k2hip_hotwords_t* hw) {
         if (old) e.dev_free(old);
     });
 }
+// ---- n-gram LM shallow fusion (ngram_lm.cpp) -----------------------------------------------------------
+struct k2hip_ngram_lm {
+    std::unique_ptr<k2hip::NgramLm> lm;
+};
+int32_t k2hip_ngram_lm_create(const int64_t* ids, const int32_t* orders, const float* log_probs, const float* backoffs, int64_t n_entries,
+                              int32_t vocab_size, k2hip_ngram_lm_t** out) {
+    return guard([&] {
+        NEED(out);
+        *out = nullptr;
+        std::unique_ptr<NgramLm> lm(new NgramLm(ids, orders, log_probs, backoffs, n_entries, vocab_size));
+        *out = new k2hip_ngram_lm{std::move(lm)};
+    });
+}
+int32_t k2hip_ngram_lm_load(const k2hip_tokens_t* tokens, const char* path, k2hip_ngram_lm_t** out) {
+    return guard([&] {
+        NEED(tokens); NEED(path); NEED(out);
+        *out = nullptr;
+        const int V = token_table_size(tokens->tab);
+        std::map<std::string, int> id_of;
+        for (int i = V - 1; i >= 0; i--) id_of[token_table_symbol(*tokens->tab, i)] = i;   // (a repeated symbol: its first line)
+        std::ifstream f(path, std::ios::binary);
+        if (!f) failf(K2HIP_ERR_IO, "cannot open ngram lm file %s", path);
+        std::string text((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+        std::unique_ptr<NgramLm> lm(ngram_parse_arpa(text.data(), text.size(), id_of, V, path));
+        *out = new k2hip_ngram_lm{std::move(lm)};
+    });
+}
+int32_t k2hip_ngram_lm_destroy(k2hip_ngram_lm_t* lm) {
+    return guard([&] { delete lm; });
+}
+int32_t k2hip_ngram_lm_order(const k2hip_ngram_lm_t* lm) { return lm ? lm->lm->order() : -1; }
+int32_t k2hip_ngram_lm_num_states(const k2hip_ngram_lm_t* lm) { return lm ? lm->lm->num_states() : -1; }
+int64_t k2hip_ngram_lm_num_arcs(const k2hip_ngram_lm_t* lm) { return lm ? lm->lm->num_arcs() : -1; }
+int32_t k2hip_ngram_lm_start_state(const k2hip_ngram_lm_t* lm) { return lm ? lm->lm->start_state() : -1; }
+int32_t k2hip_ngram_lm_step(const k2hip_ngram_lm_t* lm, int32_t state, int64_t token, int32_t* next_state, float* log_prob) {
+    return guard([&] {
+        NEED(lm); NEED(next_state); NEED(log_prob);
+        int n = 0;
+        lm->lm->step(state, token, &n, log_prob);
+        *next_state = n;
+    });
+}
+int32_t k2hip_set_ngram_lm(k2hip_model_t* model, const k2hip_ngram_lm_t* lm, float scale) {
+    return guard([&] {
+        NEED(model);
+        Engine& e = model->engine;
+        const int V = e.model().cfg().V;
+        if (lm) {
+            K2_REQUIRE(std::isfinite(scale) && scale >= 0.f, "set_ngram_lm: scale %g must be finite and >= 0", (double)scale);
+            K2_REQUIRE(lm->lm->vocab_size() == V, "set_ngram_lm: the LM was built for vocab_size %d, the model has %d", lm->lm->vocab_size(), V);
+        }
+        EngineLock lk(e);
+        K2_REQUIRE(e.batches_in_flight() == 0, "set_ngram_lm: %d submitted batches are in flight; wait for them first", e.batches_in_flight());
+        void* fresh = nullptr;
+        BeamLm tables;
+        if (lm && scale > 0.f) {   // (scale = 0 adds nothing anywhere: the plain search, as with no LM)
+            NgramDeviceForm d;
+            lm->lm->device_form(scale, &d);
+            const int64_t nb_s = align_up((int64_t)sizeof(int32_t) * (int64_t)d.states.size(), 16);
+            const int64_t nb_a = align_up((int64_t)sizeof(int32_t) * std::max<int64_t>((int64_t)d.arc_tok.size(), 1), 16);
+            const int64_t nb_v = align_up((int64_t)sizeof(int32_t) * V, 16);
+            fresh = e.dev_alloc(nb_s + 3 * nb_a + 2 * nb_v);
+            try {
+                char* c = static_cast<char*>(fresh);
+                e.dev_upload(c, d.states.data(), (int64_t)sizeof(int32_t) * (int64_t)d.states.size());
+                if (!d.arc_tok.empty()) {
+                    e.dev_upload(c + nb_s, d.arc_tok.data(), (int64_t)sizeof(int32_t) * (int64_t)d.arc_tok.size());
+                    e.dev_upload(c + nb_s + nb_a, d.arc_lp.data(), (int64_t)sizeof(float) * (int64_t)d.arc_lp.size());
+                    e.dev_upload(c + nb_s + 2 * nb_a, d.arc_next.data(), (int64_t)sizeof(int32_t) * (int64_t)d.arc_next.size());
+                }
+                e.dev_upload(c + nb_s + 3 * nb_a, d.uni_lp.data(), (int64_t)sizeof(float) * V);
+                e.dev_upload(c + nb_s + 3 * nb_a + nb_v, d.uni_next.data(), (int64_t)sizeof(int32_t) * V);
+                tables.states = reinterpret_cast<const int4*>(c);
+                tables.arc_tok = reinterpret_cast<const int*>(c + nb_s);
+                tables.arc_lp = reinterpret_cast<const float*>(c + nb_s + nb_a);
+                tables.arc_next = reinterpret_cast<const int*>(c + nb_s + 2 * nb_a);
+                tables.uni_lp = reinterpret_cast<const float*>(c + nb_s + 3 * nb_a);
+                tables.uni_next = reinterpret_cast<const int*>(c + nb_s + 3 * nb_a + nb_v);
+                tables.start = lm->lm->start_state();
+            } catch (...) {
+                try { e.dev_free(fresh); } catch (...) {}
+                throw;
+            }
+        }
+        // searches already enqueued read the old tables: let them finish before the memory goes
+        if (model->lm_dev) {
+            try {
+                e.synchronize();
+            } catch (...) {
+                if (fresh) {
+                    try { e.dev_free(fresh); } catch (...) {}
+                }
+                throw;
+            }
+        }
+        e.set_ngram_tables(tables);
+        model->lm_serial = fresh ? ++g_hw_serial : 0;
+        model->lm_start = tables.start;
+        void* old = model->lm_dev;
+        model->lm_dev = fresh;
+        if (old) e.dev_free(old);
+    });
+}
 int32_t k2hip_ctc_greedy(k2hip_model_t* model, const float* log_probs, int32_t B, int32_t Tprime, const int32_t* frame_offsets,
                          int64_t* tokens, int32_t* timestamps, int32_t* n_tokens, int32_t max_tokens, int32_t* num_trailing_blank) {
     return guard([&] {
@@ -1114,6 +1233,8 @@ int32_t k2hip_online_step(k2hip_model_t* model, k2hip_online_stream_t* const* st
         const Config& c = e.model().cfg();
         K2_REQUIRE(c.streaming || c.lstm, "this model is not a streaming export");
         const size_t chunk_floats = (size_t)c.chunk_T * c.feat, shift_floats = (size_t)c.shift * c.feat;
+        uint64_t lm_serial = 0;   // the n-gram LM this tick's beam search runs with (0 = none) and its start state
+        int lm_start = 0;
         int K = 0;   // the search of this tick: 0 = greedy (and a CTC model's own search), K = modified beam search with beam K
         if (!c.ctc) {
             EngineLock lk(e);
@@ -1123,6 +1244,8 @@ int32_t k2hip_online_step(k2hip_model_t* model, k2hip_online_stream_t* const* st
             K2_REQUIRE(!(K > 0 && e.has_hotwords()),
                        "online step: hotword biasing covers the offline modified beam search only, not the streaming one -- clear the "
                        "hotwords (k2hip_set_hotwords(model, NULL)) or decode with greedy_search");
+            lm_serial = K > 0 ? model->lm_serial : 0;
+            lm_start = model->lm_start;
         }
         std::vector<int> idx;
         for (int i = 0; i < B; i++) {
@@ -1142,6 +1265,13 @@ int32_t k2hip_online_step(k2hip_model_t* model, k2hip_online_stream_t* const* st
             K2_REQUIRE(std::adjacent_find(seen.begin(), seen.end()) == seen.end(), "GetResults: the same stream appears twice in the list");
         }
         if (idx.empty()) return;   // :113-116
+        // a stream keeps the LM it decoded its first chunk with (decided for all streams before anything of any of them moves)
+        for (size_t r = 0; K > 0 && r < idx.size(); r++) {
+            const k2hip_online_stream* s = streams[idx[r]];
+            K2_REQUIRE(!s->beam || s->beam->frames() == 0 || s->beam->lm_serial() == lm_serial,
+                       "online step: stream %d has decoded %lld frames with another n-gram LM setting (k2hip_set_ngram_lm changed or cleared "
+                       "it) and its hypotheses carry that LM's states -- reset the stream first", idx[r], s->beam->frames());
+        }
         // the new frames' host copy is collected after the step (one wait for the device per tick); whatever way this call ends -- an
         // allocation failure below included -- the outstanding download is collected before the streams' Speech can move
         // If the collection itself fails (the device work behind the download did), the streams whose Speech was extended with
@@ -1193,6 +1323,7 @@ int32_t k2hip_online_step(k2hip_model_t* model, k2hip_online_stream_t* const* st
         std::vector<int32_t> ts, n;
         std::vector<int> bin, bout;   // modified beam search: the streams' saved hypotheses in, the surviving ones out
         bool any_hw = false;
+        const bool with_lm = lm_serial != 0;
         std::vector<BeamHwStream> graphs;
         std::vector<int> st_in, st_out;
         const BeamResumeLayout RL{std::max(K, 1), Tp};
@@ -1205,17 +1336,20 @@ int32_t k2hip_online_step(k2hip_model_t* model, k2hip_online_stream_t* const* st
                     s->beam.reset(new BeamHistory(K, K2HIP_BLANK_ID));
                     if (s->hw) s->beam->set_pending(s->hw->pending);
                 }
+                if (s->beam->frames() == 0) s->beam->begin_lm(lm_serial, with_lm ? lm_start : 0);
                 s->beam->fill_in(bin.data() + (size_t)r * RL.in_ints(), Tp);
                 any_hw = any_hw || s->hw;
             }
-            if (any_hw) {   // hotword graphs: the side blocks of the tick (none attached anywhere: the unbiased call, unchanged)
+            any_hw = any_hw || with_lm;   // (the LM states ride in the same side blocks, behind the graph states)
+            if (any_hw) {   // hotword graphs / LM: the side blocks of the tick (neither anywhere: the unbiased call, unchanged)
                 graphs.resize((size_t)R);
-                st_in.resize((size_t)R * K);
-                st_out.resize((size_t)R * K);
+                st_in.resize((size_t)R * K * (with_lm ? 2 : 1));
+                st_out.resize((size_t)R * K * (with_lm ? 2 : 1));
                 for (int r = 0; r < R; r++) {
                     k2hip_online_stream* s = streams[idx[r]];
                     if (s->hw) graphs[(size_t)r] = s->hw->tables;
                     s->beam->fill_states(st_in.data() + (size_t)r * K);
+                    if (with_lm) s->beam->fill_lm_states(st_in.data() + (size_t)(R + r) * K);
                 }
             }
         } else {
@@ -1225,8 +1359,15 @@ int32_t k2hip_online_step(k2hip_model_t* model, k2hip_online_stream_t* const* st
         }
         if (!all_mirrored) fb.finish();   // the step reads some stream's chunk from host memory: the frames must be there
         std::vector<float> ypb;   // N-best on: the token log-probs of the survivors' suffixes come back beside the out blocks
+        bool lm_raced = false;
         try {
             EngineLock lk(e);
+            // the LM states staged above index the tables of setting lm_serial: this lock covers the launch, and k2hip_set_ngram_lm
+            // takes it too, so a setting that changed since it was read is caught here, before any device work
+            if (K > 0 && model->lm_serial != lm_serial) {
+                lm_raced = true;
+                failf(K2HIP_ERR_INVALID, "online step: k2hip_set_ngram_lm changed the n-gram LM while this step was being prepared; call again");
+            }
             struct YpOut {
                 Engine& e;
                 ~YpOut() { e.set_beam_yp_out(nullptr); }
@@ -1237,7 +1378,7 @@ int32_t k2hip_online_step(k2hip_model_t* model, k2hip_online_stream_t* const* st
             }
             if (K > 0 && any_hw)
                 e.online_step_beam_hw(slots.data(), chunks.data(), plens.data(), nch.data(), R, K, bin.data(), bout.data(),
-                                      Engine::BeamHwIO{graphs.data(), st_in.data(), st_out.data()}, all_mirrored ? heads.data() : nullptr);
+                                      Engine::BeamHwIO{graphs.data(), st_in.data(), st_out.data(), with_lm}, all_mirrored ? heads.data() : nullptr);
             else if (K > 0)
                 e.online_step_beam(slots.data(), chunks.data(), plens.data(), nch.data(), R, K, bin.data(), bout.data(),
                                    all_mirrored ? heads.data() : nullptr);
@@ -1248,7 +1389,7 @@ int32_t k2hip_online_step(k2hip_model_t* model, k2hip_online_stream_t* const* st
             // Host-side nothing has moved (RemoveChunk happens below), but the device caches of these streams may have: the step
             // updates the conv / embed caches in place.  A search exchange timeout is retried inside the engine and does not come
             // here; what does is a HIP failure.  The streams are unusable until reset.
-            for (int r = 0; r < R; r++) streams[idx[r]]->poisoned = true;
+            for (int r = 0; r < R && !lm_raced; r++) streams[idx[r]]->poisoned = true;   // (the LM race is decided before any device work)
             throw;   // (fb's destructor collects the frames; the streams are poisoned either way)
         }
         fb.finish();   // the step's token download has synchronised the stream: copies only
@@ -1270,7 +1411,8 @@ int32_t k2hip_online_step(k2hip_model_t* model, k2hip_online_stream_t* const* st
                 // the best hypothesis replaces the result (it may revise earlier tokens): n_new_tokens = change of its length
                 const int64_t before = (int64_t)s->beam->tokens().size();
                 const float* yp = ypb.empty() ? nullptr : ypb.data() + (size_t)r * K * Tp;
-                if (any_hw) s->beam->apply_out_states(bout.data() + (size_t)r * RL.out_ints(), Tp, st_out.data() + (size_t)r * K, yp);
+                if (any_hw) s->beam->apply_out_states(bout.data() + (size_t)r * RL.out_ints(), Tp, st_out.data() + (size_t)r * K, yp,
+                                                      with_lm ? st_out.data() + (size_t)(R + r) * K : nullptr);
                 else s->beam->apply_out(bout.data() + (size_t)r * RL.out_ints(), Tp, yp);
                 s->hyp[0] = s->beam->hyp_last(0);
                 s->hyp[1] = s->beam->hyp_last(1);
@@ -1436,10 +1578,14 @@ int32_t k2hip_beam_search_chunk(k2hip_model_t* model, k2hip_beam_stream_t* const
     return guard([&] {
         NEED(model); NEED(streams); NEED(enc_out);
         K2_REQUIRE(B > 0 && Tc >= 1, "beam search chunk: bad shape B=%d Tc=%d", B, Tc);
+        uint64_t lm_serial = 0;   // the n-gram LM this call runs with (0 = none) and its start state
+        int lm_start = 0;
         {
             EngineLock lk(model->engine);
             K2_REQUIRE(!model->engine.has_hotwords(), "beam search chunk: hotword biasing covers the offline modified beam search only, not the "
                                                       "streaming one -- clear the hotwords (k2hip_set_hotwords(model, NULL)) first");
+            lm_serial = model->lm_serial;
+            lm_start = model->lm_start;
         }
         std::vector<const k2hip_beam_stream*> seen(streams, streams + B);
         for (int b = 0; b < B; b++) {
@@ -1451,21 +1597,31 @@ int32_t k2hip_beam_search_chunk(k2hip_model_t* model, k2hip_beam_stream_t* const
         std::sort(seen.begin(), seen.end());
         K2_REQUIRE(std::adjacent_find(seen.begin(), seen.end()) == seen.end(), "beam search chunk: the same stream appears twice");
         const int K = streams[0]->hist.beam();
+        const bool with_lm = lm_serial != 0;
+        // a stream keeps the LM it searched its first chunk with (decided for all streams before any of them changes)
+        for (int b = 0; b < B; b++)
+            K2_REQUIRE(streams[b]->hist.frames() == 0 || streams[b]->hist.lm_serial() == lm_serial,
+                       "beam search chunk: stream %d has searched %lld frames with another n-gram LM setting (k2hip_set_ngram_lm changed or "
+                       "cleared it) and its hypotheses carry that LM's states -- reset the stream first", b, streams[b]->hist.frames());
+        for (int b = 0; b < B; b++)
+            if (streams[b]->hist.frames() == 0) streams[b]->hist.begin_lm(lm_serial, with_lm ? lm_start : 0);
         const BeamResumeLayout L{K, Tc};
         std::vector<int> bin((size_t)B * L.in_ints()), bout((size_t)B * L.out_ints());
         for (int b = 0; b < B; b++) streams[b]->hist.fill_in(bin.data() + (size_t)b * L.in_ints(), Tc);
-        // hotword graphs: with none attached anywhere this is the unbiased call, unchanged; else the side blocks go along
-        bool any_hw = false;
+        // hotword graphs / LM: with neither anywhere this is the unbiased call, unchanged; else the side blocks go along (the LM states
+        // behind the graph states)
+        bool any_hw = with_lm;
         for (int b = 0; b < B; b++) any_hw = any_hw || streams[b]->hw;
         std::vector<BeamHwStream> graphs;
         std::vector<int> st_in, st_out;
         if (any_hw) {
             graphs.resize((size_t)B);
-            st_in.resize((size_t)B * K);
-            st_out.resize((size_t)B * K);
+            st_in.resize((size_t)B * K * (with_lm ? 2 : 1));
+            st_out.resize((size_t)B * K * (with_lm ? 2 : 1));
             for (int b = 0; b < B; b++) {
                 if (streams[b]->hw) graphs[(size_t)b] = streams[b]->hw->tables;
                 streams[b]->hist.fill_states(st_in.data() + (size_t)b * K);
+                if (with_lm) streams[b]->hist.fill_lm_states(st_in.data() + (size_t)(B + b) * K);
             }
         }
         std::vector<float> ypb;
@@ -1475,17 +1631,21 @@ int32_t k2hip_beam_search_chunk(k2hip_model_t* model, k2hip_beam_stream_t* const
                 Engine& e;
                 ~YpOut() { e.set_beam_yp_out(nullptr); }
             } yp_guard{model->engine};
+            // (this lock covers the launch and k2hip_set_ngram_lm takes it too: the staged LM states still index the tables that are set)
+            K2_REQUIRE(model->lm_serial == lm_serial, "beam search chunk: k2hip_set_ngram_lm changed the n-gram LM while this call was being "
+                                                      "prepared; call again");
             if (model->engine.nbest() > 0) {
                 ypb.resize((size_t)B * K * Tc);
                 model->engine.set_beam_yp_out(ypb.data());
             }
-            if (any_hw) model->engine.beam_chunk_host_hw(enc_out, B, Tc, K, bin.data(), bout.data(), Engine::BeamHwIO{graphs.data(), st_in.data(), st_out.data()});
+            if (any_hw) model->engine.beam_chunk_host_hw(enc_out, B, Tc, K, bin.data(), bout.data(), Engine::BeamHwIO{graphs.data(), st_in.data(), st_out.data(), with_lm});
             else model->engine.beam_chunk_host(enc_out, B, Tc, K, bin.data(), bout.data());
         }
         // (only after success: a failed call leaves every stream as it was)
         for (int b = 0; b < B; b++) {
             const float* yp = ypb.empty() ? nullptr : ypb.data() + (size_t)b * K * Tc;
-            if (any_hw) streams[b]->hist.apply_out_states(bout.data() + (size_t)b * L.out_ints(), Tc, st_out.data() + (size_t)b * K, yp);
+            if (any_hw) streams[b]->hist.apply_out_states(bout.data() + (size_t)b * L.out_ints(), Tc, st_out.data() + (size_t)b * K, yp,
+                                                          with_lm ? st_out.data() + (size_t)(B + b) * K : nullptr);
             else streams[b]->hist.apply_out(bout.data() + (size_t)b * L.out_ints(), Tc, yp);
         }
     });

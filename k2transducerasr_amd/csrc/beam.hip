@@ -20,6 +20,9 @@
 // search, with nothing added to its code.  Streaming with hotwords (HW and resume): every stream of the call brings its own tables
 // (BeamArgs::hw_streams; none = no bonus, state 0), the saved hypotheses' states come in with st_in and the survivors' go out with
 // st_out, and the out block's `best` follows the same final pick while the log-probs written keep the pending bonus.
+// N-gram LM shallow fusion (BeamArgs::lm; resumed: lst_in / lst_out beside st_in / st_out): every hypothesis also carries the state of the LM's back-off automaton; the
+// selected candidates' walks (beam_lm_walk, a wave per candidate) run beside the pair comparisons, before the barrier in front of the
+// merge section, which reads term and next state from LDS.  It lives in the HW instantiations behind a null check, as hw_bonus does.
 #include <type_traits>
 
 #include <atomic>
@@ -47,6 +50,10 @@ __global__ void k_beam_init(BeamState s, int B) {
         s.st[i] = 0;
         s.st[B * s.K + i] = 0;
     }
+    if (s.lst) {
+        s.lst[i] = s.lm.start;
+        s.lst[B * s.K + i] = s.lm.start;
+    }
     if (k == 0) s.nhyp[i / s.K] = 1;
 }
 // the saved hypotheses of every stream (resume): hypothesis k = saved hypothesis k with an empty suffix
@@ -67,6 +74,10 @@ __global__ void k_beam_resume_init(BeamState s, int B) {
     if (s.st) {
         s.st[i] = (s.st_in && k < nh) ? s.st_in[i] : 0;
         s.st[B * K + i] = 0;
+    }
+    if (s.lst) {
+        s.lst[i] = (s.lst_in && k < nh) ? s.lst_in[i] : 0;
+        s.lst[B * K + i] = 0;
     }
     if (k == 0) s.nhyp[b] = nh;
 }
@@ -158,11 +169,49 @@ struct HypView {
     int* st_n = nullptr;
     const int* hw_next = nullptr;
     const float* hw_bonus = nullptr;
+    // n-gram LM (HW instantiations only; lm.states null: none): LM state of each hypothesis at frame t / t + 1
+    const int* lst_c = nullptr;
+    int* lst_n = nullptr;
+    BeamLm lm;
     // token log-probs (null: not kept, the search does what it does without them): parallel to ts, the unbiased log-softmax term
     // of each emitted token at the frame it was emitted
     const float* yp_c = nullptr;
     float* yp_n = nullptr;
 };
+// Step(state, tok) of the n-gram LM (ngram_lm.h) over the scaled device tables, by one whole wave: per level ONE 16-byte load of the
+// state, then the 64 lanes search its sorted arcs together -- a 64-ary narrowing while the range is longer than a wave, then one
+// compare per lane with the arc's weight and next state loaded beside the token (no load depends on the vote), and a wave vote.  A
+// miss adds the back-off weight and moves on; state 0 is a dense row, so every walk ends in one direct load.  At most order - 1 levels.
+__device__ __forceinline__ void beam_lm_walk(const BeamLm& lm, int s, int tok, int lane, float* term, int* next) {
+    float acc = 0.f;
+    for (int lvl = 0; lvl < K2HIP_NGRAM_MAX_ORDER - 1 && s != 0; lvl++) {   // (a state's history is at most order - 1 tokens long)
+        const int4 st = lm.states[s];
+        int lo = st.x, n = st.y - st.x;
+        while (n > 64) {
+            const int stride = (n + 63) >> 6, i = lo + lane * stride;
+            const unsigned long long le = __ballot(lane * stride < n && lm.arc_tok[i] <= tok);   // (sorted: a prefix of the lanes)
+            if (!le) { n = 0; break; }
+            const int j = 63 - __clzll(le);
+            n = min(stride, n - j * stride);
+            lo += j * stride;
+        }
+        const bool in = lane < n;
+        const int tk = in ? lm.arc_tok[lo + lane] : -1;
+        const float lpv = in ? lm.arc_lp[lo + lane] : 0.f;
+        const int nxv = in ? lm.arc_next[lo + lane] : 0;
+        const unsigned long long hit = __ballot(in && tk == tok);
+        if (hit) {
+            const int src = __ffsll(hit) - 1;
+            *term = acc + __shfl(lpv, src);
+            *next = __shfl(nxv, src);
+            return;
+        }
+        acc = acc + __int_as_float(st.w);
+        s = st.z;
+    }
+    *term = acc + lm.uni_lp[tok];
+    *next = lm.uni_next[tok];
+}
 constexpr int kStepScratchInts = 4 * kMaxBeam + 4 + 2 * kMaxBeam * kMaxBeam;
 constexpr int kYpScratchFloats = kMaxBeam * kMaxBeam + kMaxBeam;
 // one workgroup of NT threads per stream; lg: the hypotheses' logits, ldl floats per row; scratch: kStepScratchInts ints of LDS
@@ -284,6 +333,19 @@ __device__ void beam_step_body(const HypView& hv, const float* lg, int ldl, int 
     // compared by a wave of its own (one barrier for all pairs; a loop over the pairs with three block barriers each was a third of
     // the step), then tid 0 resolves the merges in insertion order
     int* eq = candi;   // [r][q] (the per-hypothesis candidates are used up)
+    // n-gram LM: term and next state of every selected candidate, a wave each, into LDS for the merge section (candv is used up too)
+    float* lmterm = candv;
+    int* lmnext = reinterpret_cast<int*>(candv) + kMaxBeam;
+    if constexpr (HW) {
+        if (hv.lm.states)
+            for (int r = wave; r < want; r += BT / 64) {
+                const int hr = topi[r] / V, tr = topi[r] % V;
+                float term = 0.f;
+                int nx = hv.lst_c[hr];
+                if (tr != K2HIP_BLANK_ID && tr != K2HIP_UNK_ID) beam_lm_walk(hv.lm, nx, tr, lane, &term, &nx);
+                if (lane == 0) { lmterm[r] = term; lmnext[r] = nx; }
+            }
+    }
     {
         const int npairs = want * (want - 1) / 2;
         for (int pi = wave; pi < npairs; pi += BT / 64) {
@@ -344,6 +406,7 @@ __device__ void beam_step_body(const HypView& hv, const float* lg, int ldl, int 
                 if (r < want) {
                     const int hr = topi[r] / V, tr = topi[r] % V;
                     if (hv.hw_bonus && tr != K2HIP_BLANK_ID && tr != K2HIP_UNK_ID) tv[r] += hv.hw_bonus[(long long)hv.st_c[hr] * V + tr];
+                    if (hv.lm.states) tv[r] += lmterm[r];   // (sum + hotword bonus) + LM term
                 }
             }
             lpn[r] = -INFINITY;
@@ -397,7 +460,10 @@ __device__ void beam_step_body(const HypView& hv, const float* lg, int ldl, int 
             hv.ctx[2 * k + 1] = K2HIP_BLANK_ID;
             n_n[k] = 0;
             if (hv.org_n) hv.org_n[k] = 0;
-            if constexpr (HW) hv.st_n[k] = 0;
+            if constexpr (HW) {
+                hv.st_n[k] = 0;
+                if (hv.lst_n) hv.lst_n[k] = 0;
+            }
         }
         *hv.nhyp = nN;
         if (hv.trace) hv.trace[2 * K] = nN;
@@ -430,7 +496,10 @@ __device__ void beam_step_body(const HypView& hv, const float* lg, int ldl, int 
                 nn++;
             }
             n_n[slot] = nn;
-            if constexpr (HW) hv.st_n[slot] = (realr && hv.hw_next) ? hv.hw_next[(long long)hv.st_c[hr] * V + tr] : hv.st_c[hr];
+            if constexpr (HW) {
+                hv.st_n[slot] = (realr && hv.hw_next) ? hv.hw_next[(long long)hv.st_c[hr] * V + tr] : hv.st_c[hr];
+                if (hv.lst_n) hv.lst_n[slot] = lmnext[r];
+            }
             // decoder context of the new hypothesis: last two of [c0, c1] + ys, [c0, c1] = the saved hypothesis' context (resume) or
             // [blank, blank]
             long long c0 = K2HIP_BLANK_ID, c1 = K2HIP_BLANK_ID;
@@ -479,6 +548,11 @@ __global__ __launch_bounds__(BT) void k_beam_step(BeamState s, const float* __re
         hv.st_n = s.st + nxt * BK + b * K;
         hv.hw_next = s.hw_streams ? s.hw_streams[b].next : s.hw_next;
         hv.hw_bonus = s.hw_streams ? s.hw_streams[b].bonus : s.hw_bonus;
+        if (s.lst) {
+            hv.lst_c = s.lst + cur * BK + b * K;
+            hv.lst_n = s.lst + nxt * BK + b * K;
+            hv.lm = s.lm;
+        }
     }
     if (s.yp) {
         hv.yp_c = s.yp + ((long long)cur * BK + (long long)b * K) * s.cap;
@@ -495,7 +569,8 @@ __global__ __launch_bounds__(BT) void k_beam_step(BeamState s, const float* __re
 template <bool HW>
 __device__ void beam_resume_write(const int* in, int* out, int K, int Tp, int cap, int nh, const float* lp, const long long* ctx,
                                   const int* n, const int* org, const int* ys, const int* ts, const int* st = nullptr,
-                                  const float* pending = nullptr, int* st_out = nullptr, const float* yp = nullptr, float* yp_out = nullptr) {
+                                  const float* pending = nullptr, int* st_out = nullptr, const float* yp = nullptr, float* yp_out = nullptr,
+                                  const int* lst = nullptr, int* lst_out = nullptr) {
     const BeamResumeLayout L{K, Tp};
     const int tid = threadIdx.x;
     if (tid == 0) {
@@ -521,6 +596,7 @@ __device__ void beam_resume_write(const int* in, int* out, int K, int Tp, int ca
         out[L.out_ctx() + 2 * k + 1] = live ? (int)ctx[2 * k + 1] : K2HIP_BLANK_ID;
         if constexpr (HW) {
             if (st_out) st_out[k] = live ? st[k] : 0;
+            if (lst_out) lst_out[k] = live ? lst[k] : 0;
         }
     }
     for (int i = tid; i < nh * Tp; i += blockDim.x) {
@@ -543,7 +619,8 @@ __global__ void k_beam_resume_final(BeamState s, int fin, int B, int* __restrict
                                 s.ys + (fin * BK + (long long)b * K) * s.cap, s.ts + (fin * BK + (long long)b * K) * s.cap,
                                 s.st + fin * BK + b * K, s.hw_streams ? s.hw_streams[b].pending : s.hw_pending,
                                 s.st_out ? s.st_out + b * K : nullptr, s.yp ? s.yp + (fin * BK + (long long)b * K) * s.cap : nullptr,
-                                s.yp_out ? s.yp_out + (long long)b * K * s.Tp : nullptr);
+                                s.yp_out ? s.yp_out + (long long)b * K * s.Tp : nullptr, s.lst ? s.lst + fin * BK + b * K : nullptr,
+                                s.lst_out ? s.lst_out + b * K : nullptr);
     else
         beam_resume_write<false>(s.rin + (long long)b * L.in_ints(), rout + (long long)b * L.out_ints(), K, s.Tp, s.cap, s.nhyp[b], s.lp + b * K,
                                  s.ctx + 2 * (long long)b * K, s.n + fin * BK + b * K, s.org + fin * BK + b * K,
@@ -603,11 +680,11 @@ __device__ __forceinline__ void bstore_granule(unsigned long long* g, unsigned e
 __device__ __forceinline__ unsigned long long bload_granule(const unsigned long long* g) {
     return __hip_atomic_load((bgu64*)g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-// LDS (floats): actT[J GF] | psum | lg[GF][Vp] | ctx[2 GF] (long long) | lp[GF] | n[2][GF] | org[2][GF] | st[2][GF] (hotwords only) |
+// LDS (floats): actT[J GF] | psum | lg[GF][Vp] | ctx[2 GF] (long long) | lp[GF] | n[2][GF] | org[2][GF] | st[2][GF], lst[2][GF] (biased only) |
 // nhyp, pad | scratch | ys[2][K][cap] | ts[2][K][cap]
 // with token log-probs (yp): ... | scratch | yp scratch | ys | ts | yp[2][K][cap]
 __host__ __device__ inline size_t beam_loop_lds_floats(int J, int Vp, int K, int cap, bool hyp_in_lds, bool hw, bool yp) {
-    return (size_t)J * GF + kPsumFloats + (size_t)GF * Vp + 4 * GF + GF + 2 * GF + 2 * GF + (hw ? 2 * GF : 0) + 4 + kStepScratchInts + 4 +
+    return (size_t)J * GF + kPsumFloats + (size_t)GF * Vp + 4 * GF + GF + 2 * GF + 2 * GF + (hw ? 4 * GF : 0) + 4 + kStepScratchInts + 4 +
            (yp ? kYpScratchFloats : 0) + (hyp_in_lds ? (yp ? 6 : 4) * (size_t)K * cap : 0);
 }
 template <int NH, bool HW>   // NH = 1: beam <= 4, the sweep forms only rows 0..3; HW: hotword biasing
@@ -621,7 +698,8 @@ __global__ __launch_bounds__(GT) void k_beam_loop(DecJoinW w, BeamLoopArgs a) {
     int* nbuf = reinterpret_cast<int*>(lp + GF);       // [2][GF]
     int* orgb = nbuf + 2 * GF;                          // [2][GF] (resume)
     int* stb = orgb + 2 * GF;                           // [2][GF] (hotwords)
-    int* nhyp = stb + (HW ? 2 * GF : 0);
+    int* lstb = stb + 2 * GF;                           // [2][GF] (n-gram LM)
+    int* nhyp = stb + (HW ? 4 * GF : 0);
     int* scratch = nhyp + 4;
     // token log-probs (a.want_yp; the whole launch takes one side of this branch): the step's extra scratch, and yp beside ys / ts
     float* pscratch = a.want_yp ? reinterpret_cast<float*>(scratch + kStepScratchInts + 4) : nullptr;
@@ -649,6 +727,8 @@ __global__ __launch_bounds__(GT) void k_beam_loop(DecJoinW w, BeamLoopArgs a) {
         if constexpr (HW) {
             stb[tid] = 0;
             stb[GF + tid] = 0;
+            lstb[tid] = a.lm.start;
+            lstb[GF + tid] = a.lm.start;
         }
         if (rin) {
             const int nh = rin[0];
@@ -658,6 +738,8 @@ __global__ __launch_bounds__(GT) void k_beam_loop(DecJoinW w, BeamLoopArgs a) {
             ctx[2 * tid + 1] = live ? rin[RL.in_ctx() + 2 * tid + 1] : K2HIP_BLANK_ID;
             if constexpr (HW) {
                 if (a.st_in && live) stb[tid] = a.st_in[b * K + tid];   // the saved hypotheses' graph states
+                lstb[tid] = (a.lst_in && live) ? a.lst_in[b * K + tid] : 0;     // ... and LM states
+                lstb[GF + tid] = 0;
             }
             if (tid == 0) *nhyp = nh;
         } else {
@@ -808,6 +890,11 @@ __global__ __launch_bounds__(GT) void k_beam_loop(DecJoinW w, BeamLoopArgs a) {
             hv.st_n = stb + (cur ^ 1) * GF;
             hv.hw_next = hws.next;
             hv.hw_bonus = hws.bonus;
+            if (a.lm.states) {
+                hv.lst_c = lstb + cur * GF;
+                hv.lst_n = lstb + (cur ^ 1) * GF;
+                hv.lm = a.lm;
+            }
         }
         if (yp) {
             hv.yp_c = yp + (size_t)cur * K * a.cap;
@@ -824,7 +911,8 @@ __global__ __launch_bounds__(GT) void k_beam_loop(DecJoinW w, BeamLoopArgs a) {
             beam_resume_write<true>(rin, a.rout + (long long)b * RL.out_ints(), K, a.Tp, a.cap, *nhyp, lp, ctx, n_f, orgb + fin * GF,
                                     ys + (size_t)fin * K * a.cap, ts + (size_t)fin * K * a.cap, stb + fin * GF, hws.pending,
                                     a.st_out ? a.st_out + b * K : nullptr, yp ? yp + (size_t)fin * K * a.cap : nullptr,
-                                    a.yp_out ? a.yp_out + (long long)b * K * a.Tp : nullptr);
+                                    a.yp_out ? a.yp_out + (long long)b * K * a.Tp : nullptr, lstb + fin * GF,
+                                    a.lst_out ? a.lst_out + b * K : nullptr);
         else
             beam_resume_write<false>(rin, a.rout + (long long)b * RL.out_ints(), K, a.Tp, a.cap, *nhyp, lp, ctx, n_f, orgb + fin * GF,
                                      ys + (size_t)fin * K * a.cap, ts + (size_t)fin * K * a.cap, nullptr, nullptr, nullptr,
@@ -834,7 +922,7 @@ __global__ __launch_bounds__(GT) void k_beam_loop(DecJoinW w, BeamLoopArgs a) {
     // (hotwords: an unfinished match earns nothing -- every hypothesis' log-prob loses its state's pending bonus first)
     const int* st_f = stb + fin * GF;
     auto final_lp = [&](int k) {
-        if constexpr (HW) return lp[k] - hws.pending[st_f[k]];
+        if constexpr (HW) return hws.pending ? lp[k] - hws.pending[st_f[k]] : lp[k];   // (an LM alone: nothing is pending)
         else return lp[k];
     };
     if (a.nb.tokens && slab == 0)
@@ -873,7 +961,7 @@ __global__ void k_beam_final(BeamState s, int fin, int B, long long* __restrict_
     const int* n_f = s.n + fin * BK + b * K;
     // (hotwords: every hypothesis' log-prob loses its state's pending bonus first)
     auto final_lp = [&](int k) {
-        if constexpr (HW) return s.lp[b * K + k] - s.hw_pending[s.st[fin * BK + b * K + k]];
+        if constexpr (HW) return s.hw_pending ? s.lp[b * K + k] - s.hw_pending[s.st[fin * BK + b * K + k]] : s.lp[b * K + k];
         else return s.lp[b * K + k];
     };
     if (nb.tokens)
@@ -907,7 +995,9 @@ __global__ void k_beam_final(BeamState s, int fin, int B, long long* __restrict_
 void beam_search(const Ctx& ctx, const DecJoinW& w, const BeamArgs& a) {
     K2_REQUIRE(a.beam >= 1 && a.beam <= kMaxBeam, "beam search: beam %d out of range [1,%d]", a.beam, kMaxBeam);
     K2_REQUIRE(a.B > 0 && a.Tp > 0, "beam search: bad shape");
-    const bool hw = a.hw_next != nullptr || a.hw_streams != nullptr;
+    const bool hw = a.hw_next != nullptr || a.hw_streams != nullptr || a.lm.states != nullptr;
+    K2_REQUIRE(!a.lm.states || (a.lm.arc_tok && a.lm.arc_lp && a.lm.arc_next && a.lm.uni_lp && a.lm.uni_next), "beam search: incomplete n-gram LM tables");
+    K2_REQUIRE(!(a.lm.states && a.rin) || (a.lst_in && a.lst_out), "beam search: the resumed search with an n-gram LM needs its LM state blocks");
     K2_REQUIRE(!a.hw_next || (a.hw_bonus && a.hw_pending), "beam search: incomplete hotword tables");
     K2_REQUIRE(!(a.hw_next && a.hw_streams), "beam search: one hotword graph or one per stream, not both");
     K2_REQUIRE(!a.hw_streams || (a.rin && a.st_in && a.st_out), "beam search: per-stream hotword graphs belong to the resumed search and need its state blocks");
@@ -949,6 +1039,7 @@ void beam_search(const Ctx& ctx, const DecJoinW& w, const BeamArgs& a) {
             la.rin = a.rin; la.rout = a.rout;
             la.hw_next = a.hw_next; la.hw_bonus = a.hw_bonus; la.hw_pending = a.hw_pending;
             la.hw_streams = a.hw_streams; la.st_in = a.st_in; la.st_out = a.st_out;
+            la.lm = a.lm; la.lst_in = a.lst_in; la.lst_out = a.lst_out;
             K2_HIP(hipMemsetAsync(a.overflow, 0, sizeof(int), ctx.stream));
             static LdsAttrOnce lds_attr, lds_attr1, lds_attr_hw, lds_attr1_hw;
             if (hw) {
@@ -1004,6 +1095,10 @@ void beam_search(const Ctx& ctx, const DecJoinW& w, const BeamArgs& a) {
         s.st = ar.take<int>((int64_t)2 * M);
         s.hw_next = a.hw_next; s.hw_bonus = a.hw_bonus; s.hw_pending = a.hw_pending;
         s.hw_streams = a.hw_streams; s.st_in = a.st_in; s.st_out = a.st_out;
+        if (a.lm.states) {
+            s.lst = ar.take<int>((int64_t)2 * M);
+            s.lm = a.lm; s.lst_in = a.lst_in; s.lst_out = a.lst_out;
+        }
     }
     float* hbuf = ar.take<float>((int64_t)M * w.DD);
     float* act = ar.take<float>((int64_t)M * w.J);
@@ -1060,8 +1155,8 @@ void beam_relaunch_one_slab(hipStream_t stream, const GreedyLaunch& rec) {
         K2_HIP(hipMemsetAsync(la.n_tokens, 0xEE, sizeof(int) * (size_t)rec.a.B, stream));
         if (la.scores) K2_HIP(hipMemsetAsync(la.scores, 0xEE, sizeof(float) * (size_t)rec.a.B, stream));
     }
-    // (la carries the hotword tables of the first launch; its LDS size was computed with them)
-    if (la.hw_next || la.hw_streams) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_beam_loop<1, true>), dim3(rec.a.B), dim3(GT), rec.beam_lds, stream, rec.w, la);
+    // (la carries the hotword and LM tables of the first launch; its LDS size was computed with them)
+    if (la.hw_next || la.hw_streams || la.lm.states) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_beam_loop<1, true>), dim3(rec.a.B), dim3(GT), rec.beam_lds, stream, rec.w, la);
     else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_beam_loop<1, false>), dim3(rec.a.B), dim3(GT), rec.beam_lds, stream, rec.w, la);
     K2_HIP(hipGetLastError());
 }

@@ -125,6 +125,7 @@ class BeamHistory {
         float lp;
         int ctx[2];        // decoder context: the last two tokens of [blank, blank] + ys
         int st = 0;        // state of the stream's hotword graph (0 = the root; always 0 without a graph)
+        int lst = 0;       // state of the model's n-gram LM (always 0 without an LM)
     };
     explicit BeamHistory(int K = 1, int blank = 0) : K_(K), blank_(blank) { reset(); }
     int beam() const { return K_; }
@@ -210,14 +211,28 @@ class BeamHistory {
             }
         }
     }
+    // N-gram LM: a stream keeps the LM it decoded its first chunk with.  begin_lm (only while no frame has been searched) notes that
+    // LM's serial number (0 = none) and puts the start hypothesis into its start state; lm_serial() is what later chunks compare.
+    void begin_lm(uint64_t serial, int start_state) {
+        lm_serial_ = serial;
+        hyps_[0].lst = start_state;
+    }
+    uint64_t lm_serial() const { return lm_serial_; }
+    void fill_lm_states(int* lst_in) const {
+        for (int k = 0; k < K_; k++) lst_in[k] = k < (int)hyps_.size() ? hyps_[(size_t)k].lst : 0;
+    }
     // hotword side block in: the saved hypotheses' graph states [K]
     void fill_states(int* st_in) const {
         for (int k = 0; k < K_; k++) st_in[k] = k < (int)hyps_.size() ? hyps_[(size_t)k].st : 0;
     }
     // apply_out + the hotword side block out: the survivors' graph states [K]
-    void apply_out_states(const int* out, int Tp, const int* st_out, const float* yp = nullptr) {
+    // (lst_out: the survivors' LM states [K], or null)
+    void apply_out_states(const int* out, int Tp, const int* st_out, const float* yp = nullptr, const int* lst_out = nullptr) {
         apply_out(out, Tp, yp);
-        for (size_t k = 0; k < hyps_.size(); k++) hyps_[k].st = st_out[k];
+        for (size_t k = 0; k < hyps_.size(); k++) {
+            hyps_[k].st = st_out[k];
+            if (lst_out) hyps_[k].lst = lst_out[k];
+        }
     }
     // the device search's out block of that chunk: the new hypotheses, the best one, the result; yp: the side block [K][Tp] with the
     // token log-probs of each survivor's suffix, or null (they are then kept as 0)
@@ -280,6 +295,7 @@ class BeamHistory {
     }
 
     int K_, blank_;
+    uint64_t lm_serial_ = 0;
     std::shared_ptr<const std::vector<float>> pending_;   // (kept across reset(): the graph stays attached)
     SeqTree seq_;
     PathTree path_;

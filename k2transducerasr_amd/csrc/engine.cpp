@@ -708,6 +708,7 @@ void Engine::beam_device(const Ctx& c, const float* enc, int B, int Tp, long lon
     d_scores_ = c.arena->take<float>(B);
     a.scores = d_scores_;
     a.hw_next = hw_next_; a.hw_bonus = hw_bonus_; a.hw_pending = hw_pending_;
+    a.lm = lm_;
     if (nbest_ > 0 && c.arena == &arena_) {   // (the synchronous entries only: the pipelined route has no place to keep them)
         const int64_t NB = (int64_t)B * nbest_;
         d_nb_.nbest = nbest_;
@@ -740,6 +741,11 @@ void Engine::beam_resume_device(const Ctx& c, const float* enc, int B, int Tp, i
     a.rin = d_in; a.rout = d_out;
     if (hw) {
         a.hw_streams = hw->graphs; a.st_in = hw->st_in; a.st_out = hw->st_out;
+        if (hw->lm) {
+            a.lm = lm_;
+            a.lst_in = hw->st_in + (size_t)B * K;
+            a.lst_out = hw->st_out + (size_t)B * K;
+        }
     }
     d_yp_ = nullptr;
     if (yp_host_) {
@@ -769,7 +775,7 @@ void Engine::beam_chunk_impl(const float* enc, int B, int Tp, int K, const int* 
     // ONE upload [enc | in blocks | hotwords: states in, graphs] and ONE download [flag | out blocks | hotwords: states out]
     const int64_t nb_enc = (int64_t)sizeof(float) * B * Tp * cf.J, nb_in = (int64_t)sizeof(int) * B * L.in_ints(),
                   nb_out = (int64_t)sizeof(int) * B * L.out_ints();
-    const int64_t nb_st = hw ? (int64_t)sizeof(int) * B * K : 0, nb_g = hw ? (int64_t)sizeof(BeamHwStream) * B : 0;
+    const int64_t nb_st = hw ? (int64_t)sizeof(int) * B * K * (hw->lm ? 2 : 1) : 0, nb_g = hw ? (int64_t)sizeof(BeamHwStream) * B : 0;
     const int64_t o_in = align_up(nb_enc, 16), o_st = align_up(o_in + nb_in, 16), o_g = align_up(o_st + nb_st, 16),
                   o_ovf = align_up(o_g + nb_g, 16), in_bytes = o_ovf + 16;
     K2_HIP(hipSetDevice(device_));
@@ -787,7 +793,7 @@ void Engine::beam_chunk_impl(const float* enc, int B, int Tp, int K, const int* 
         d_ovf = reinterpret_cast<int*>(d + o_ovf);
         if (!c.dry) K2_HIP(hipMemcpyAsync(d, stage, (size_t)in_bytes, hipMemcpyHostToDevice, c.stream));
         const BeamHwIO dhw{reinterpret_cast<const BeamHwStream*>(d + o_g), reinterpret_cast<const int*>(d + o_st),
-                           reinterpret_cast<int*>(d + in_bytes + nb_out)};
+                           reinterpret_cast<int*>(d + in_bytes + nb_out), hw && hw->lm};
         beam_resume_device(c, reinterpret_cast<const float*>(d), B, Tp, K, reinterpret_cast<const int*>(d + o_in),
                            reinterpret_cast<int*>(d + in_bytes), d_ovf, hw ? &dhw : nullptr);
     });

@@ -123,6 +123,8 @@ class Engine {
         const BeamHwStream* graphs;
         const int* st_in;
         int* st_out;
+        // the model's n-gram LM runs in this call: st_in / st_out are [2][B][K], the hypotheses' LM states behind their graph states
+        bool lm = false;
     };
     void online_step_beam_hw(const int* slots, const float* const* chunks, const long long* plens, const int* nchunks, int B, int K,
                              const int* beam_in, int* beam_out, const BeamHwIO& hw, const int* fifo_heads = nullptr);
@@ -149,6 +151,10 @@ class Engine {
         hw_next_ = next; hw_bonus_ = bonus; hw_pending_ = pending;
     }
     bool has_hotwords() const { return hw_next_ != nullptr; }
+    // n-gram LM of the offline modified beam search (BeamArgs::lm): the scaled tables in device memory owned by the caller (api.cpp
+    // k2hip_set_ngram_lm, as for the hotword tables); null tables = none
+    void set_ngram_tables(const BeamLm& lm) { lm_ = lm; }
+    bool has_ngram_lm() const { return lm_.states != nullptr; }
     // N-best and token log-probs of the synchronous modified beam search (semantics in include/k2hip.h): 0 = off, nothing is computed
     // or kept beyond the best hypothesis; n >= 1 = every search keeps its first n final hypotheses in pick order, each with its token
     // log-probs, and last_nbest() holds them after the call (entry 0 = the result the call returned)
@@ -313,6 +319,7 @@ class Engine {
     NbestHost last_nbest_;
     const int* hw_next_ = nullptr;
     const float *hw_bonus_ = nullptr, *hw_pending_ = nullptr;
+    BeamLm lm_;
     // CTC search by-products of the last synchronous call (NumTrailingBlank bookkeeping, OfflineRecognizer.cs:392-397)
     int *d_trail_ = nullptr, *d_any_ = nullptr;
     std::vector<int> last_trail_, last_any_;

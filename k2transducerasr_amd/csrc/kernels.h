@@ -479,6 +479,19 @@ struct BeamHwStream {
     const float* bonus = nullptr;
     const float* pending = nullptr;
 };
+// The n-gram LM of the search (shallow fusion) as the kernels read it: the sparse form of ngram_lm.h on the device, every weight already
+// multiplied by the scale (the device only adds).  states == null: no LM.  states [S] = (arc begin, arc end, back-off state, back-off
+// weight bits) -- one 16-byte load per level of a walk; the arcs of a state sorted by token; uni_* [V]: state 0 as a dense row with
+// the <unk> rule resolved, so every walk ends in one direct load.
+struct BeamLm {
+    const int4* states = nullptr;
+    const int* arc_tok = nullptr;
+    const float* arc_lp = nullptr;
+    const int* arc_next = nullptr;
+    const float* uni_lp = nullptr;
+    const int* uni_next = nullptr;
+    int start = 0;   // the start hypothesis' state
+};
 // N-best outputs of the offline search (device; tokens == null: off): up to `nbest` final hypotheses per stream in the order of the
 // final pick, (finalized log-prob) / (length + 2) descending with ties in insertion order -- entry 0 is the single result
 struct BeamNbest {
@@ -518,6 +531,9 @@ struct BeamLoopArgs {
     const BeamHwStream* hw_streams = nullptr;
     const int* st_in = nullptr;
     int* st_out = nullptr;
+    BeamLm lm;   // n-gram LM or null tables; resume: the saved hypotheses' LM states in / the survivors' out [B][K]
+    const int* lst_in = nullptr;
+    int* lst_out = nullptr;
     // token log-probs (false: not kept): yp beside ys / ts -- in LDS, or yp_g [B][2][K][cap] where ys_g / ts_g are used; nb: the
     // offline N-best outputs; yp_out: the resumed search's side block [B][K][Tp], the token log-probs of each survivor's suffix
     bool want_yp = false;
@@ -589,6 +605,11 @@ struct BeamState {       // device arrays; hypotheses double-buffered by frame p
     const BeamHwStream* hw_streams = nullptr;
     const int* st_in = nullptr;
     int* st_out = nullptr;
+    // n-gram LM: the hypotheses' LM states [2][B][K] beside st, and the tables (null: none)
+    int* lst = nullptr;
+    BeamLm lm;
+    const int* lst_in = nullptr;
+    int* lst_out = nullptr;
 };
 struct BeamArgs {
     const float* enc;    // [B, Tp, J]
@@ -621,6 +642,13 @@ struct BeamArgs {
     const BeamHwStream* hw_streams = nullptr;
     const int* st_in = nullptr;
     int* st_out = nullptr;
+    // N-gram LM shallow fusion (ngram_lm.h; semantics in include/k2hip.h): every hypothesis carries an LM state beside its hotword
+    // state; a selected candidate that appends a real token gets (sum + hotword bonus) + Step(state, token) before the merges, nothing
+    // is taken back at the end.  Runs in the biased instantiations (a null check there, as for hw_bonus).  The resumed search takes
+    // the saved hypotheses' LM states in lst_in [B][K] and writes the survivors' to lst_out [B][K], side blocks as st_in / st_out are.
+    BeamLm lm;
+    const int* lst_in = nullptr;
+    int* lst_out = nullptr;
     // Token log-probs and N-best (semantics in include/k2hip.h).  Both null: nothing is kept beyond the best hypothesis.  nb: the
     // offline search also writes its final hypotheses in pick order; yp_out [B][K][Tp] (resume): the token log-probs of each
     // survivor's suffix, a side block beside rout as st_out is.

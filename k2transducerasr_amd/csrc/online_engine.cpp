@@ -531,7 +531,7 @@ void Engine::online_step_impl(const int* slots, const float* const* chunks, cons
     const BeamResumeLayout RL{beam ? beam->K : 1, Tp};
     const BeamHwIO* bhw = beam ? beam->hw : nullptr;
     const int64_t nb_bin = beam ? (int64_t)sizeof(int) * RL.in_ints() * B : 0;
-    const int64_t nb_hst = bhw ? (int64_t)sizeof(int) * beam->K * B : 0, nb_hg = bhw ? (int64_t)sizeof(BeamHwStream) * B : 0;
+    const int64_t nb_hst = bhw ? (int64_t)sizeof(int) * beam->K * B * (bhw->lm ? 2 : 1) : 0, nb_hg = bhw ? (int64_t)sizeof(BeamHwStream) * B : 0;
     const int64_t nb_bout = beam ? (int64_t)sizeof(int) * RL.out_ints() * B + nb_hst : 0, o_hout = nb_bout - nb_hst;
     const int64_t nb_x = from_fifo ? 0 : (int64_t)sizeof(float) * chunk_floats * B;
     const int64_t o_plen = align_up(nb_x, 16), o_hyp = o_plen + 8 * (int64_t)B, o_slots = o_hyp + 16 * (int64_t)B, o_chunks = o_slots + 4 * (int64_t)B,
@@ -572,7 +572,7 @@ void Engine::online_step_impl(const int* slots, const float* const* chunks, cons
         const int* d_bin = reinterpret_cast<const int*>(d_in + o_bin);
         int* d_bout = reinterpret_cast<int*>(d_out);
         const BeamHwIO dhw{reinterpret_cast<const BeamHwStream*>(d_in + o_hg), reinterpret_cast<const int*>(d_in + o_hst),
-                           reinterpret_cast<int*>(d_out + o_hout)};
+                           reinterpret_cast<int*>(d_out + o_hout), bhw && bhw->lm};
         const BeamHwIO* d_hw = bhw ? &dhw : nullptr;
         if (!c.dry) {
             K2_HIP(hipEventRecord(ev_[0], c.stream));

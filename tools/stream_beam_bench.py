@@ -36,6 +36,9 @@ if "--nbest" in argv:
     i = argv.index("--nbest")
     n_best = int(argv[i + 1])
     del argv[i: i + 2]
+ngram_lm = "--ngram-lm" in argv      # also time the tick with a seeded trigram fused (tests/ngram_twin.draw_lm, scale 0.5)
+if ngram_lm:
+    argv.remove("--ngram-lm")
 preset = argv[0] if len(argv) > 0 else "zipformer2-streaming-zh"
 N = int(argv[1]) if len(argv) > 1 else 128
 secs = float(argv[2]) if len(argv) > 2 else 20.0
@@ -104,6 +107,23 @@ def main():
                 raise SystemExit("keeping the alternatives changed the results")
             hw_out["nbest"] = n_best
             hw_out["beam_nbest_ms_per_tick"] = round(float(np.median(n_ms)), 3)
+        if ngram_lm:
+            from k2transducerasr_amd import NgramLm
+            from ngram_twin import draw_lm
+            V = rec.model.vocab_size
+            lm = NgramLm(draw_lm(b_res[:DISTINCT], V, np.random.default_rng(100), n_cut=300, n_random=2000, n_no_unigram=5), V)
+            rec.model.set_ngram_lm(lm, 0.5)
+            try:
+                l_ms, l_res = run(rec, feats, "modified_beam_search", beam)
+            finally:
+                rec.model.set_ngram_lm(None)
+            l2_ms, l2_res = run(rec, feats, "modified_beam_search", beam)
+            if l2_res != b_res:
+                raise SystemExit("a cleared LM changed the results")
+            hw_out.update({"ngram_order": lm.order, "ngram_states": lm.num_states, "ngram_arcs": lm.num_arcs,
+                           "beam_ngram_lm_ms_per_tick": round(float(np.median(l_ms)), 3),
+                           "beam_no_lm_again_ms_per_tick": round(float(np.median(l2_ms)), 3),
+                           "streams_moved_by_the_lm": int(sum(a != b for a, b in zip(l_res, b_res)))})
         import parity
         from test_online_beam_gpu import oracle_frames
         exact = excused = 0
