@@ -94,7 +94,14 @@ int32_t k2hip_debug_gemm_run(k2hip_model_t* model, const float* A, const float* 
  *     K2HIP_ERR_UNSUPPORTED.
  *   "gemm_glu_causal_conv": the launcher's arguments in its own order (x, wg, bg, pool, slot_stride, off, slots, wc, bc, ww, bw, sc,
  *     y, B, Tc, D, K), then a buffer of 1 int32 that the hook fills with glu_conv_ring_entry(B, Tc, D, K) (-1: no fused form, and the
- *     call is K2HIP_ERR_UNSUPPORTED with nothing launched). */
+ *     call is K2HIP_ERR_UNSUPPORTED with nothing launched).
+ * One op launches nothing (tests/test_search_ties_gpu.py):
+ *   "greedy_screen_counts": no int arguments, one buffer of 2 int64 that the hook fills (whatever out_mask says) with the model's
+ *     counters since it was created: [0] rounds of the persistent large-vocabulary greedy search (csrc/greedy.hip k_greedy) that its
+ *     f16 screen decided, [1] rounds that ran the f32 passes instead (non-finite screen values, more than 64 candidates, or a slab
+ *     too wide for the screen) -- one count per round and column slab of a stream.  They only move while the switch
+ *     K2HIP_SCREEN_COUNT is on; a model loaded with K2HIP_SCREEN_MIN_V=0, a small vocabulary and the K2HIP_SEARCH_ROUNDS=1 form
+ *     never count.  Call it with no pipelined search in flight. */
 int32_t k2hip_debug_op_run(k2hip_model_t* model, const char* op, const int64_t* iargs, int32_t n_iargs, void* const* bufs,
                            const int64_t* buf_bytes, int32_t n_bufs, uint32_t out_mask);
 

@@ -37,6 +37,8 @@ Engine::Engine(const std::string& weights, const char* overrides, int device) : 
         K2_HIP(hipEventCreateWithFlags(&sl.h2d_done, hipEventDisableTiming));
     }
     for (auto& e : ev_) K2_HIP(hipEventCreate(&e));
+    K2_HIP(hipMalloc(&d_screen_counts_, 2 * sizeof(unsigned long long)));
+    K2_HIP(fill_blocking(d_screen_counts_, 0, 2 * sizeof(unsigned long long)));
     // The search tables (groups = 1 decoders: the per-token conv contributions; small vocabularies: the all-contexts decoder table,
     // 0.5 GB at V = 500 -- k2hip.h "memory") are built HERE, not inside the first search call: their hipMalloc + build + stream
     // synchronisation would otherwise sit under the engine lock in the first decode or the first pipelined submit.
@@ -66,6 +68,7 @@ Engine::~Engine() {
         if (e) (void)hipEventDestroy(e);
     for (auto& e : evpool_) (void)hipEventDestroy(e);
     if (d_dec_start_) (void)hipFree(d_dec_start_);
+    if (d_screen_counts_) (void)hipFree(d_screen_counts_);
     if (pin_) (void)hipHostFree(pin_);
     if (pin_in_) (void)hipHostFree(pin_in_);
     if (pin_fb_) (void)hipHostFree(pin_fb_);
@@ -677,6 +680,7 @@ void Engine::greedy_device(const Ctx& c, const float* enc, int B, int Tp, bool s
     a.max_sym = single ? 1000 : INT_MAX;  // OfflineRecognizer.cs:122
     a.tokens = d_tok; a.timestamps = d_ts; a.n_tokens = d_n; a.max_tokens = max_tokens; a.overflow = d_overflow;
     a.dec_init = dec_start;
+    a.screen_counts = screen_counts();
     // batch path: rounds of whole-chip GEMMs (they interleave with the next batch's encoder instead of pinning CUs for the whole
     // search); the single-stream path (1000-symbol cap, B = 1) keeps the persistent kernel
     if (!single && tunables().search_rounds == 1) greedy_rounds(c, w, model_->w("joiner.output_linear.weight"), a);
@@ -1962,6 +1966,13 @@ void Engine::debug_op_host(const char* op, const int64_t* iargs, int n_iargs, vo
                 const int ldin = I(), B = I(), width = I();
                 scatter_rows(c, pool, ss, off, slots, io, ldin, B, width);
             }
+        } else if (name == "greedy_screen_counts") {
+            // no launch: the model's two counters (rounds the f16 screen decided, rounds that ran the f32 passes) into bufs[0]
+            float* out = P();
+            K2_REQUIRE(out && buf_bytes[0] >= 16, "debug_op_run greedy_screen_counts: a buffer of 2 int64 is needed");
+            K2_HIP(hipStreamSynchronize(stream_));
+            K2_HIP(copy_blocking(out, d_screen_counts_, 2 * sizeof(unsigned long long), hipMemcpyDeviceToDevice));
+            out_mask |= 1u;
         } else if (name == "basicnorm") {
             float *x = P(), *le = P(), *y = P();
             const int M = I(), D = I();

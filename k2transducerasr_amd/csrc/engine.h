@@ -295,6 +295,10 @@ class Engine {
     GreedyLaunch last_greedy_;          // the same for the synchronous entries (searches on stream_)
     void note_search(bool parted, bool timed_out);
     int one_part_left_ = 0, one_part_span_ = 0;   // searches still to run with one workgroup per stream / the current back-off span
+    // [2] rounds of the large-vocabulary search decided by the f16 screen / run by the f32 passes since the model was created, counted
+    // only while K2HIP_SCREEN_COUNT is on (k2hip_debug_op_run "greedy_screen_counts")
+    unsigned long long* d_screen_counts_ = nullptr;
+    unsigned long long* screen_counts() const { return tunables().screen_count ? d_screen_counts_ : nullptr; }
     int search_retries_ = 0;            // one-part retries since the model was created (k2hip_debug_search_retries)
     int next_slot_ = 0;
     hipStream_t stream2_ = nullptr;

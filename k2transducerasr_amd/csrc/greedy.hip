@@ -432,6 +432,11 @@ __device__ __forceinline__ unsigned long long load_granule(const unsigned long l
 // the f32 logit l the passes would compute.  A column can only hold frame f's maximum if l~ + eps >= max_u (l~_u - eps_u); those
 // candidates -- a handful -- are recomputed EXACTLY as the passes compute them (the k slices' fma chains in k order, the slices
 // summed in the passes' tree, + bias: bit-identical values), and the later-wins argmax over them is the argmax over the slab.
+// ("Bit-identical" is held to account by tests/test_search_ties_gpu.py: on twin columns whose true margin is about one f32 ulp --
+// the bias, the first or the last weight one ulp apart, a row against its own reversal in k -- the entries that run this kernel
+// give the same token on every frame: the screen on and off (K2HIP_SCREEN_MIN_V=0), 1 / 2 / 4 / the default number of parts, one
+// part, greedy_batch and greedy_single, at J = 64 .. 512.  The claim stands.  greedy_rounds does NOT share this arithmetic: its
+// logits come from the GEMM kernels' summation orders, and on such twins it is only held to naming one of the two.)
 // Non-finite screen values (a NaN sample upstream, a NaN / Inf / f16-overflowing weight: the reference's NaN rule needs every column)
 // or more than kScreenCand candidates send the round to the f32 passes.  Per round and part: 708 KB of L2 traffic instead of 1.4 MB
 // x the three passes' MFMA-issue time.
@@ -613,7 +618,10 @@ __device__ __noinline__ bool screen_round(const DecJoinW& w, const float* actT, 
 // actH (large vocabularies: the activations as f16 MFMA fragments, J x 32 bytes)
 // SCREEN: the instantiation for large vocabularies (w.out_h16 set) -- kept apart so that the screen's 128 fragment registers do
 // not weigh on the small-vocabulary kernel's allocation (172 VGPRs, no scratch)
-template <bool SCREEN>
+// COUNT: the K2HIP_SCREEN_COUNT build of the SCREEN instantiation (a.screen_counts set) -- an instantiation of its own, so that the
+// kernel that runs with the switch off is compiled from exactly the code it had before the counter (in the same kernel, behind a
+// null test, the counter's address pair cost two more VGPRs)
+template <bool SCREEN, bool COUNT = false>
 __global__ __launch_bounds__(GT) void k_greedy(DecJoinW w, GreedyArgs a) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     float* actT = sm;
@@ -903,6 +911,8 @@ __global__ __launch_bounds__(GT) void k_greedy(DecJoinW w, GreedyArgs a) {
         } else {
             __syncthreads();  // actT / fin are rewritten by the next round
         }
+        // K2HIP_SCREEN_COUNT: which way this part's round went, one atomic per part and round
+        if constexpr (COUNT) if (tid == 0) atomicAdd(a.screen_counts + (screened ? 0 : 1), 1ull);
         stamp(7);
     }
     if (tid == 0 && part == 0) a.n_tokens[b] = n_tok < a.max_tokens ? n_tok : a.max_tokens;
@@ -1292,6 +1302,10 @@ void greedy_loop(const Ctx& ctx, const DecJoinW& w, const GreedyArgs& a0) {
     static LdsAttrOnce lds_attr_s;
     lds_attr.ensure(k_greedy<false>, 150 * 1024);
     lds_attr_s.ensure(k_greedy<true>, 150 * 1024);
+    if (w.out_h16 && a.screen_counts) {
+        static LdsAttrOnce lds_attr_c;
+        lds_attr_c.ensure(k_greedy<true, true>, 150 * 1024);
+    }
     if (parts > 1) {
         K2_HIP(hipMemsetAsync(a.gran, 0, sizeof(unsigned long long) * (gran_words + gran2_words), ctx.stream));
     }
@@ -1301,7 +1315,8 @@ void greedy_loop(const Ctx& ctx, const DecJoinW& w, const GreedyArgs& a0) {
         K2_HIP(hipMemsetAsync(d_stamps, 0, 8 * sizeof(unsigned long long), ctx.stream));
         a.stamps = d_stamps;
     }
-    if (w.out_h16) hipLaunchKernelGGL(k_greedy<true>, dim3(a.B * parts), dim3(GT), lds, ctx.stream, w, a);
+    if (w.out_h16 && a.screen_counts) hipLaunchKernelGGL((k_greedy<true, true>), dim3(a.B * parts), dim3(GT), lds, ctx.stream, w, a);
+    else if (w.out_h16) hipLaunchKernelGGL(k_greedy<true>, dim3(a.B * parts), dim3(GT), lds, ctx.stream, w, a);
     else hipLaunchKernelGGL(k_greedy<false>, dim3(a.B * parts), dim3(GT), lds, ctx.stream, w, a);
     if (a.stamps) {   // tuning: synchronous report of workgroup 0's round
         unsigned long long h[8];
@@ -1337,7 +1352,8 @@ void greedy_relaunch_one_part(hipStream_t stream, const GreedyLaunch& rec) {
         K2_HIP(hipMemsetAsync(a.timestamps, 0xEE, sizeof(int) * (size_t)a.B * a.max_tokens, stream));
         K2_HIP(hipMemsetAsync(a.n_tokens, 0xEE, sizeof(int) * (size_t)a.B, stream));
     }
-    if (w.out_h16) hipLaunchKernelGGL(k_greedy<true>, dim3(a.B), dim3(GT), lds, stream, w, a);
+    if (w.out_h16 && a.screen_counts) hipLaunchKernelGGL((k_greedy<true, true>), dim3(a.B), dim3(GT), lds, stream, w, a);   // (its attribute: set by the first launch)
+    else if (w.out_h16) hipLaunchKernelGGL(k_greedy<true>, dim3(a.B), dim3(GT), lds, stream, w, a);
     else hipLaunchKernelGGL(k_greedy<false>, dim3(a.B), dim3(GT), lds, stream, w, a);
     K2_HIP(hipGetLastError());
 }

@@ -43,6 +43,8 @@ struct Tunables {
     int decoder_table_mb = 1024;  // K2HIP_DECODER_TABLE_MB: build the all-contexts decoder table when it fits this many MiB (0 = never)
     int screen_min_v = 1024;      // K2HIP_SCREEN_MIN_V: vocabularies of at least this size get the f16 screening pass in the greedy search
                                   // (greedy.hip screen_round: exact tokens, ~2.5x fewer bytes per round); 0 = never
+    int screen_count = 0;         // K2HIP_SCREEN_COUNT: the persistent search counts, per round and part, whether the f16 screen decided the round or it
+                                  // went to the f32 passes (k2hip_debug.h: k2hip_debug_op_run "greedy_screen_counts"); 0 = the kernel gets no counter
     int max_streams = 0;          // K2HIP_MAX_STREAMS: slots of the streaming state pool (0 = 256)
     // ---- tuning probes (-DK2HIP_DEV builds only)
     K2HIP_DEV_SWITCH(gemm_cfg, -1);         // K2HIP_GEMM_CFG: force one tile configuration (a k2hip_debug_gemm cfg code: GemmForce)
@@ -464,6 +466,10 @@ struct GreedyArgs {
     // [0] rounds, [1] activations, [2] screen tiles, [3] candidate scan, [4] re-check, [5] sweep passes, [6] publish + exchange,
     // [7] decision + decoder update
     unsigned long long* stamps = nullptr;
+    // K2HIP_SCREEN_COUNT: [2] device counters, or nullptr (no atomics in the kernel).  Thread 0 of every part adds one per round of the
+    // large-vocabulary instantiation: [0] the f16 screen decided the round, [1] the round ran the f32 passes (the screen gave up, or
+    // the part's slab does not fit it)
+    unsigned long long* screen_counts = nullptr;
 };
 void greedy_loop(const Ctx& ctx, const DecJoinW& w, const GreedyArgs& a);
 bool greedy_loop_screens(const DecJoinW& w, int B, bool streaming, bool one_part);  // would its rounds use the f16 screen (large vocabulary, slab fits)?

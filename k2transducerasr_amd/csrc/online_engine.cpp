@@ -597,7 +597,7 @@ void Engine::online_step_impl(const int* slots, const float* const* chunks, cons
             }
             GreedyArgs a;
             a.enc = enc; a.B = B; a.Tp = Tp; a.t0 = nullptr; a.skip1 = 1; a.max_sym = INT_MAX;
-            a.tokens = d_tok; a.timestamps = d_ts; a.n_tokens = d_n; a.max_tokens = Tp; a.overflow = d_ovf; a.init_ctx = d_hyp;
+            a.tokens = d_tok; a.timestamps = d_ts; a.n_tokens = d_n; a.max_tokens = Tp; a.overflow = d_ovf; a.init_ctx = d_hyp; a.screen_counts = screen_counts();
             if (persistent_search) greedy_loop(c, decjoin(), a);
             else greedy_rounds(c, decjoin(), model_->w("joiner.output_linear.weight"), a);
             if (ev_ok) K2_HIP(hipEventRecord(ev_[4], c.stream));
@@ -619,7 +619,7 @@ void Engine::online_step_impl(const int* slots, const float* const* chunks, cons
         // OnlineRecognizer.cs:135-202: decoder on the streams' hyps, T' joiner steps, skip {blank, unk, 1}
         GreedyArgs a;
         a.enc = enc; a.B = B; a.Tp = Tp; a.t0 = nullptr; a.skip1 = 1; a.max_sym = INT_MAX;
-        a.tokens = d_tok; a.timestamps = d_ts; a.n_tokens = d_n; a.max_tokens = Tp; a.overflow = d_ovf; a.init_ctx = d_hyp;
+        a.tokens = d_tok; a.timestamps = d_ts; a.n_tokens = d_n; a.max_tokens = Tp; a.overflow = d_ovf; a.init_ctx = d_hyp; a.screen_counts = screen_counts();
         if (persistent_search) greedy_loop(c, decjoin(), a);
         else greedy_rounds(c, decjoin(), model_->w("joiner.output_linear.weight"), a);
         if (ev_ok) K2_HIP(hipEventRecord(ev_[4], c.stream));

@@ -85,6 +85,7 @@ const Entry kEntries[] = {
     {"K2HIP_BEAM_PARTS", &Tunables::beam_parts, false},
     {"K2HIP_BEAM_TRACE", &Tunables::beam_trace, true},
     {"K2HIP_SCREEN_MIN_V", &Tunables::screen_min_v, false},
+    {"K2HIP_SCREEN_COUNT", &Tunables::screen_count, false},
     {"K2HIP_TEST_GREEDY_TIMEOUT", &Tunables::test_greedy_timeout, true},
     {"K2HIP_SEARCH_ROUNDS", &Tunables::search_rounds, false},
     {"K2HIP_MAX_STREAMS", &Tunables::max_streams, false},

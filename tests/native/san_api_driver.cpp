@@ -7,6 +7,9 @@
 //                                                            submit / wait, operator-level calls with tight output buffers
 //   san_api_driver errors  <streaming.k2w>                   null arguments, wrong model, duplicates, poisoned streams
 //   san_api_driver plans   <gemm_plans.txt>                  csrc/gemm_plan.cpp's tile plan for each line's inputs (see plans below)
+//   san_api_driver tensor  <model.k2w> <name>                csrc/model.cpp's loader on the container, then the named tensor -- a repack the
+//                                                            loader derives, such as joiner.output_linear.weight#h16 / #eps, or one of
+//                                                            the file's own -- as raw bytes on stdout (tests/test_search_screen_ref.py)
 // Any sanitizer report, crash or model mismatch fails the process; prints one summary line.
 #include <cstdio>
 #include <cstdlib>
@@ -17,6 +20,7 @@
 
 #include "../../include/k2hip.h"
 #include "../../k2transducerasr_amd/csrc/kernels.h"
+#include "../../k2transducerasr_amd/csrc/model.h"
 
 extern "C" void k2hip_stub_fail_next_step(int n);
 extern "C" void k2hip_stub_fail_next_gather_finish(int n);
@@ -384,6 +388,31 @@ int plans(const char* path) {
     return 0;
 }
 
+// The real loader (Model's constructor: parse, validate, repack; upload(): the repacks become named tensors, "device" memory being
+// the stand-in's host allocations) and one of its tensors as raw bytes: 4 bytes per element of the tensor's dims, whatever the repack
+// keeps in them (#h16: two halfs per float slot).  Nothing else is printed to stdout; a failure is "ERR <code> <message>" on stderr.
+int tensor_bytes(const char* path, const char* name) {
+    using namespace k2hip;
+    try {
+        tunables_init_from_env();
+        Model m(path, nullptr);
+        m.upload(0);
+        if (!m.has(name)) {
+            fprintf(stderr, "ERR %d no tensor '%s'\n", K2HIP_ERR_INVALID, name);
+            return 4;
+        }
+        const Tensor& t = m.tensor(name);
+        const size_t n = (size_t)t.numel();
+        CHECK(t.host != nullptr);
+        CHECK(fwrite(t.host, sizeof(float), n, stdout) == n);
+        CHECK(fflush(stdout) == 0);
+    } catch (const Error& e) {
+        fprintf(stderr, "ERR %d %s\n", e.code, e.what());
+        return 4;
+    }
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -392,6 +421,8 @@ int main(int argc, char** argv) {
     if (argc >= 5 && !strcmp(argv[1], "offline")) return offline(argv[2], strtoull(argv[3], nullptr, 10), atoi(argv[4]));
     if (argc >= 3 && !strcmp(argv[1], "errors")) return errors(argv[2]);
     if (argc >= 3 && !strcmp(argv[1], "plans")) return plans(argv[2]);
-    fprintf(stderr, "usage: san_api_driver online|offline <model.k2w> <seed> <rounds> | errors <streaming.k2w> | meta <model.k2w> <key> | plans <gemm_plans.txt>\n");
+    if (argc >= 4 && !strcmp(argv[1], "tensor")) return tensor_bytes(argv[2], argv[3]);
+    fprintf(stderr, "usage: san_api_driver online|offline <model.k2w> <seed> <rounds> | errors <streaming.k2w> | meta <model.k2w> <key> | plans <gemm_plans.txt> | "
+                    "tensor <model.k2w> <name>\n");
     return 2;
 }
