@@ -639,27 +639,14 @@ const float* Engine::decoder_start(const Ctx& c) {
 // ---------------------------------------------------------------------------
 // greedy search on device
 // ---------------------------------------------------------------------------
-void Engine::greedy_device(const Ctx& c, const float* enc, int B, int Tp, bool single, long long* d_tok, int* d_ts, int* d_n,
-                           int max_tokens, int* d_overflow) {
-    // by-products of the search this call runs, and of no earlier one (their arena may have been rebuilt since)
-    d_scores_ = nullptr;
-    d_nb_ = BeamNbest{};
-    d_beam_trace_ = nullptr;
-    d_trail_ = nullptr;
-    d_any_ = nullptr;
-    if (model_->cfg().ctc) {
-        ctc_device(c, enc, B, Tp, d_tok, d_ts, d_n, max_tokens, d_overflow);
-        return;
-    }
-    if (beam_ > 0 && !single) {
-        beam_device(c, enc, B, Tp, d_tok, d_ts, d_n, max_tokens, d_overflow);
-        return;
-    }
+Engine::SearchExtras Engine::greedy_device(const Ctx& c, const float* enc, int B, int Tp, bool single, const SearchOut& out, bool keep_nbest) {
+    if (model_->cfg().ctc) return ctc_device(c, enc, B, Tp, out);
+    if (beam_ > 0 && !single) return beam_device(c, enc, B, Tp, out, keep_nbest);
     const Config& cf = model_->cfg();
     Arena& ar = *c.arena;
     DecJoinW w = decjoin();
     int* d_t0 = nullptr;
-    if (!c.dry) K2_HIP(hipMemsetAsync(d_overflow, 0, sizeof(int), c.stream));
+    if (!c.dry) K2_HIP(hipMemsetAsync(out.flag(), 0, sizeof(int), c.stream));
     const float* dec_start = decoder_start(c);
     if (!single && B > 1) {
         // parallel pass under the initial context [-1, blank]: which frame is the batch's first emission?
@@ -678,59 +665,61 @@ void Engine::greedy_device(const Ctx& c, const float* enc, int B, int Tp, bool s
     GreedyArgs a;
     a.enc = enc; a.B = B; a.Tp = Tp; a.t0 = d_t0; a.skip1 = 0;
     a.max_sym = single ? 1000 : INT_MAX;  // OfflineRecognizer.cs:122
-    a.tokens = d_tok; a.timestamps = d_ts; a.n_tokens = d_n; a.max_tokens = max_tokens; a.overflow = d_overflow;
+    a.tokens = out.tokens(); a.timestamps = out.timestamps(); a.n_tokens = out.counts(); a.max_tokens = out.max_tokens; a.overflow = out.flag();
     a.dec_init = dec_start;
     a.screen_counts = screen_counts();
     // batch path: rounds of whole-chip GEMMs (they interleave with the next batch's encoder instead of pinning CUs for the whole
     // search); the single-stream path (1000-symbol cap, B = 1) keeps the persistent kernel
     if (!single && tunables().search_rounds == 1) greedy_rounds(c, w, model_->w("joiner.output_linear.weight"), a);
     else greedy_loop(c, w, a);
+    return {};
 }
 
 // ForwardBatchGreedySearchCTC (OfflineRecognizer.cs:366-424): first-index argmax per frame (parallel), then per stream drop
 // blanks and repeats.  logp: [B, Tp, V]
-void Engine::ctc_device(const Ctx& c, const float* logp, int B, int Tp, long long* d_tok, int* d_ts, int* d_n, int max_tokens,
-                        int* d_overflow) {
+Engine::SearchExtras Engine::ctc_device(const Ctx& c, const float* logp, int B, int Tp, const SearchOut& out) {
     const Config& cf = model_->cfg();
     Arena& ar = *c.arena;
     int* tok = ar.take<int>((int64_t)B * Tp);
-    d_trail_ = ar.take<int>(B);
-    d_any_ = ar.take<int>(B);
-    if (!c.dry) K2_HIP(hipMemsetAsync(d_overflow, 0, sizeof(int), c.stream));
+    SearchExtras ex;
+    ex.trail = ar.take<int>(B);
+    ex.any = ar.take<int>(B);
+    if (!c.dry) K2_HIP(hipMemsetAsync(out.flag(), 0, sizeof(int), c.stream));
     argmax_first_rows(c, logp, cf.V, B * Tp, cf.V, tok);
-    ctc_collapse(c, tok, B, Tp, nullptr, d_tok, d_ts, d_n, max_tokens, d_trail_, d_any_, d_overflow);
+    ctc_collapse(c, tok, B, Tp, nullptr, out.tokens(), out.timestamps(), out.counts(), out.max_tokens, ex.trail, ex.any, out.flag());
+    return ex;
 }
 
 // modified beam search instead of the greedy loop (set_beam(K) selects it for the fused / operator entry points)
-void Engine::beam_device(const Ctx& c, const float* enc, int B, int Tp, long long* d_tok, int* d_ts, int* d_n, int max_tokens,
-                         int* d_overflow) {
+Engine::SearchExtras Engine::beam_device(const Ctx& c, const float* enc, int B, int Tp, const SearchOut& out, bool keep_nbest) {
     BeamArgs a;
     a.enc = enc; a.out_w = model_->w("joiner.output_linear.weight");
     a.dproj_w = model_->w("joiner.decoder_proj.weight");
     a.B = B; a.Tp = Tp; a.beam = beam_;
-    a.tokens = d_tok; a.timestamps = d_ts; a.n_tokens = d_n; a.max_tokens = max_tokens; a.overflow = d_overflow;
-    d_scores_ = c.arena->take<float>(B);
-    a.scores = d_scores_;
+    a.tokens = out.tokens(); a.timestamps = out.timestamps(); a.n_tokens = out.counts(); a.max_tokens = out.max_tokens; a.overflow = out.flag();
+    SearchExtras ex;
+    ex.scores = c.arena->take<float>(B);
+    a.scores = ex.scores;
     a.hw_next = hw_next_; a.hw_bonus = hw_bonus_; a.hw_pending = hw_pending_;
     a.lm = lm_;
-    if (nbest_ > 0 && c.arena == &arena_) {   // (the synchronous entries only: the pipelined route has no place to keep them)
+    if (nbest_ > 0 && keep_nbest) {
         const int64_t NB = (int64_t)B * nbest_;
-        d_nb_.nbest = nbest_;
-        d_nb_.tokens = c.arena->take<long long>(NB * max_tokens);
-        d_nb_.timestamps = c.arena->take<int>(NB * max_tokens);
-        d_nb_.token_log_probs = c.arena->take<float>(NB * max_tokens);
-        d_nb_.n_tokens = c.arena->take<int>(NB);
-        d_nb_.scores = c.arena->take<float>(NB);
-        d_nb_.n_hyps = c.arena->take<int>(B);
-        nb_B_ = B; nb_max_tokens_ = max_tokens;
-        a.nb = d_nb_;
+        ex.nb.nbest = nbest_;
+        ex.nb.tokens = c.arena->take<long long>(NB * out.max_tokens);
+        ex.nb.timestamps = c.arena->take<int>(NB * out.max_tokens);
+        ex.nb.token_log_probs = c.arena->take<float>(NB * out.max_tokens);
+        ex.nb.n_tokens = c.arena->take<int>(NB);
+        ex.nb.scores = c.arena->take<float>(NB);
+        ex.nb.n_hyps = c.arena->take<int>(B);
+        a.nb = ex.nb;
     }
     if (tunables().beam_trace) {
-        d_beam_trace_ = c.arena->take<int>((int64_t)B * Tp * (2 * beam_ + 1));
-        a.trace = d_beam_trace_;
-        trace_B_ = B; trace_Tp_ = Tp; trace_K_ = beam_;
+        ex.trace = c.arena->take<int>((int64_t)B * Tp * (2 * beam_ + 1));
+        a.trace = ex.trace;
+        ex.trace_B = B; ex.trace_Tp = Tp; ex.trace_K = beam_;
     }
     beam_search(c, decjoin(), a);
+    return ex;
 }
 
 // modified beam search resumed from saved hypotheses (streaming chunk; BeamResumeLayout{K, Tp} blocks on the device)
@@ -831,70 +820,80 @@ void Engine::note_search(bool parted, bool timed_out) {
     }
 }
 
-void Engine::finish_tokens(const long long* d_tok, const int* d_ts, const int* d_n, const int* d_ovf, int B, int max_tokens,
-                           int64_t* tokens, int32_t* ts, int32_t* n_tokens) {
-    int64_t nb_tok = (int64_t)B * max_tokens * 8, nb_ts = (int64_t)B * max_tokens * 4, nb_n = (int64_t)B * 4;
-    char* pin0 = static_cast<char*>(pinned(nb_tok + nb_ts + nb_n + 64));
-    char* pin = pin0 + 16;  // [flag (16 B) | tokens | timestamps | counts]
-    const char* t8 = reinterpret_cast<const char*>(d_tok);
-    int ovf = 0;
-    for (int attempt = 0; attempt < 2; attempt++) {
-        if (reinterpret_cast<const char*>(d_ovf) + 16 == t8 && reinterpret_cast<const char*>(d_ts) == t8 + nb_tok &&
-            reinterpret_cast<const char*>(d_n) == t8 + nb_tok + nb_ts) {
-            // the caller laid the four out as one block (the streaming chunk step): one copy
-            K2_HIP(hipMemcpyAsync(pin0, d_ovf, (size_t)(16 + nb_tok + nb_ts + nb_n), hipMemcpyDeviceToHost, stream_));
-        } else {
-            K2_HIP(hipMemcpyAsync(pin, d_tok, nb_tok, hipMemcpyDeviceToHost, stream_));
-            K2_HIP(hipMemcpyAsync(pin + nb_tok, d_ts, nb_ts, hipMemcpyDeviceToHost, stream_));
-            K2_HIP(hipMemcpyAsync(pin + nb_tok + nb_ts, d_n, nb_n, hipMemcpyDeviceToHost, stream_));
-            K2_HIP(hipMemcpyAsync(pin0, d_ovf, 4, hipMemcpyDeviceToHost, stream_));
-        }
-        if (attempt == 0) K2_HIP(hipEventRecord(ev_[5], stream_));
-        K2_HIP(hipStreamSynchronize(stream_));
-        ovf = *reinterpret_cast<int*>(pin0);
-        // exchange timeout of the vocabulary-parallel search (its workgroups were not co-resident: a shared GPU): the same search
-        // once more with one workgroup per stream, which waits for nobody
-        const bool mine = last_greedy_.valid && last_greedy_.a.overflow == d_ovf;
-        if (attempt == 0) note_search(mine, ovf == 2 && mine);
-        if (ovf != 2 || attempt == 1 || !mine) break;
-        greedy_relaunch_one_part(stream_, last_greedy_);
+void Engine::download_search(const SearchOut& out, hipStream_t s, void* pin) {
+    K2_HIP(hipMemcpyAsync(pin, out.base, (size_t)out.bytes(), hipMemcpyDeviceToHost, s));
+}
+
+void Engine::settle_search(const SearchOut& out, hipStream_t s, GreedyLaunch& rec, void* pin) {
+    const int* flag = SearchOut(pin, out.B, out.max_tokens).flag();
+    // exchange timeout of a parted search (its workgroups were not co-resident: a shared GPU): the same search once more with one
+    // workgroup per stream, which waits for nobody.  Its arena still holds the encoder output and the search's inputs.
+    const bool mine = rec.valid && rec.a.overflow == out.flag();
+    note_search(mine, *flag == 2 && mine);
+    if (*flag == 2 && mine) {
+        greedy_relaunch_one_part(s, rec);
         search_retries_++;
+        download_search(out, s, pin);
+        K2_HIP(hipStreamSynchronize(s));
     }
-    last_greedy_.valid = false;
-    if (ovf == 2) failf(K2HIP_ERR_HIP, "greedy search: the vocabulary-parallel exchange timed out (a workgroup never arrived)");
-    if (ovf) failf(K2HIP_ERR_CAPACITY, "a stream emitted more than max_tokens=%d symbols", max_tokens);
-    memcpy(tokens, pin, nb_tok);
-    memcpy(ts, pin + nb_tok, nb_ts);
-    memcpy(n_tokens, pin + nb_tok + nb_ts, nb_n);
-    if (model_->cfg().ctc && d_trail_) {
-        last_trail_.resize(B);
-        last_any_.resize(B);
-        K2_HIP(copy_blocking(last_trail_.data(), d_trail_, sizeof(int) * B, hipMemcpyDeviceToHost));
-        K2_HIP(copy_blocking(last_any_.data(), d_any_, sizeof(int) * B, hipMemcpyDeviceToHost));
+    rec.valid = false;
+    if (*flag == 2) failf(K2HIP_ERR_HIP, "greedy search: the vocabulary-parallel exchange timed out (a workgroup never arrived)");
+    if (*flag) failf(K2HIP_ERR_CAPACITY, "a stream emitted more than max_tokens=%d symbols", out.max_tokens);
+}
+
+void Engine::finish_tokens(const SearchOut& out, const SearchExtras& ex, int64_t* tokens, int32_t* ts, int32_t* n_tokens) {
+    const int B = out.B, max_tokens = out.max_tokens;
+    const SearchOut host(pinned(out.bytes()), B, max_tokens);
+    download_search(out, stream_, host.base);
+    K2_HIP(hipEventRecord(ev_[5], stream_));
+    K2_HIP(hipStreamSynchronize(stream_));
+    settle_search(out, stream_, last_greedy_, host.base);
+    host.copy_out(tokens, ts, n_tokens);
+    auto fetch = [](auto& dst, const auto* src, size_t n) {
+        dst.resize(n);
+        K2_HIP(copy_blocking(dst.data(), src, sizeof(*src) * n, hipMemcpyDeviceToHost));
+    };
+    if (ex.trail) {
+        fetch(last_trail_, ex.trail, (size_t)B);
+        fetch(last_any_, ex.any, (size_t)B);
     }
-    if (beam_ > 0 && d_scores_) {
-        last_scores_.resize(B);
-        K2_HIP(copy_blocking(last_scores_.data(), d_scores_, sizeof(float) * B, hipMemcpyDeviceToHost));
+    if (ex.scores) fetch(last_scores_, ex.scores, (size_t)B);
+    NbestHost& h = last_nbest_;
+    h.B = 0;
+    if (ex.nb.tokens) {
+        const size_t NB = (size_t)B * ex.nb.nbest;
+        h.B = B; h.N = ex.nb.nbest; h.max_tokens = max_tokens;
+        fetch(h.tokens, reinterpret_cast<const int64_t*>(ex.nb.tokens), NB * max_tokens);
+        fetch(h.timestamps, ex.nb.timestamps, NB * max_tokens);
+        fetch(h.token_log_probs, ex.nb.token_log_probs, NB * max_tokens);
+        fetch(h.n_tokens, ex.nb.n_tokens, NB);
+        fetch(h.scores, ex.nb.scores, NB);
+        fetch(h.n_hyps, ex.nb.n_hyps, (size_t)B);
     }
-    if (beam_ > 0 && d_nb_.tokens && B == nb_B_ && max_tokens == nb_max_tokens_) {
-        NbestHost& h = last_nbest_;
-        const size_t NB = (size_t)B * d_nb_.nbest;
-        h.B = B; h.N = d_nb_.nbest; h.max_tokens = max_tokens;
-        h.tokens.resize(NB * max_tokens); h.timestamps.resize(NB * max_tokens); h.token_log_probs.resize(NB * max_tokens);
-        h.n_tokens.resize(NB); h.scores.resize(NB); h.n_hyps.resize((size_t)B);
-        K2_HIP(copy_blocking(h.tokens.data(), d_nb_.tokens, sizeof(int64_t) * h.tokens.size(), hipMemcpyDeviceToHost));
-        K2_HIP(copy_blocking(h.timestamps.data(), d_nb_.timestamps, sizeof(int32_t) * h.timestamps.size(), hipMemcpyDeviceToHost));
-        K2_HIP(copy_blocking(h.token_log_probs.data(), d_nb_.token_log_probs, sizeof(float) * h.token_log_probs.size(), hipMemcpyDeviceToHost));
-        K2_HIP(copy_blocking(h.n_tokens.data(), d_nb_.n_tokens, sizeof(int32_t) * NB, hipMemcpyDeviceToHost));
-        K2_HIP(copy_blocking(h.scores.data(), d_nb_.scores, sizeof(float) * NB, hipMemcpyDeviceToHost));
-        K2_HIP(copy_blocking(h.n_hyps.data(), d_nb_.n_hyps, sizeof(int32_t) * (size_t)B, hipMemcpyDeviceToHost));
-    } else {
-        last_nbest_.B = 0;
+    if (ex.trace) {
+        last_trace_shape_[0] = ex.trace_B; last_trace_shape_[1] = ex.trace_Tp; last_trace_shape_[2] = ex.trace_K;
+        fetch(last_beam_trace_, ex.trace, (size_t)ex.trace_B * ex.trace_Tp * (2 * ex.trace_K + 1));
     }
-    if (beam_ > 0 && d_beam_trace_ && B == trace_B_) {
-        last_beam_trace_.resize((size_t)trace_B_ * trace_Tp_ * (2 * trace_K_ + 1));
-        K2_HIP(copy_blocking(last_beam_trace_.data(), d_beam_trace_, sizeof(int) * last_beam_trace_.size(), hipMemcpyDeviceToHost));
-    }
+}
+
+Engine::SearchExtras Engine::encode_and_search(const Ctx& c, const float* d_x, int B, int T, bool single, const SearchOut& out) {
+    if (!c.dry) K2_HIP(hipEventRecord(ev_[2], c.stream));
+    int Tp = 0;
+    float* enc = encoder_forward(c, d_x, B, T, &Tp, -1, nullptr, nullptr, nullptr);
+    if (!c.dry) K2_HIP(hipEventRecord(ev_[3], c.stream));
+    SearchExtras ex = greedy_device(c, enc, B, Tp, single, out, true);
+    if (!c.dry) K2_HIP(hipEventRecord(ev_[4], c.stream));
+    return ex;
+}
+
+void Engine::fill_timing(bool fbank_leg, bool pad_leg) {
+    auto el = [&](int a, int b) { float ms = 0; (void)hipEventElapsedTime(&ms, ev_[a], ev_[b]); return ms; };
+    timing_.fbank_ms = fbank_leg ? el(0, 1) : 0;   // (from host samples it includes their H2D copy)
+    timing_.pad_ms = pad_leg ? el(1, 2) : 0;
+    timing_.encoder_ms = el(pad_leg ? 2 : 0, 3);
+    timing_.greedy_ms = el(3, 4);
+    timing_.d2h_ms = el(4, 5);
+    timing_.total_ms = el(0, 5);
 }
 
 // ---------------------------------------------------------------------------
@@ -1121,18 +1120,15 @@ void Engine::greedy_host(const float* enc_out, int B, int Tp, bool single, int64
     K2_REQUIRE(B > 0 && Tp > 0 && max_tokens > 0, "greedy: bad shape B=%d T'=%d max_tokens=%d", B, Tp, max_tokens);
     K2_REQUIRE(!single || B == 1, "greedy_single: B must be 1");
     const Config& cf = model_->cfg();
-    long long* d_tok = nullptr;
-    int *d_ts = nullptr, *d_n = nullptr, *d_ovf = nullptr;
+    SearchOut out;
+    SearchExtras ex;
     run_sized([&](const Ctx& c) {
         float* d_e = c.arena->take<float>((int64_t)B * Tp * cf.enc_dim());
-        d_tok = c.arena->take<long long>((int64_t)B * max_tokens);
-        d_ts = c.arena->take<int>((int64_t)B * max_tokens);
-        d_n = c.arena->take<int>(B);
-        d_ovf = c.arena->take<int>(1);
+        out = SearchOut(*c.arena, B, max_tokens);
         if (!c.dry) K2_HIP(hipMemcpyAsync(d_e, enc_out, sizeof(float) * (size_t)B * Tp * cf.enc_dim(), hipMemcpyHostToDevice, c.stream));
-        greedy_device(c, d_e, B, Tp, single, d_tok, d_ts, d_n, max_tokens, d_ovf);
+        ex = greedy_device(c, d_e, B, Tp, single, out, true);
     });
-    finish_tokens(d_tok, d_ts, d_n, d_ovf, B, max_tokens, tokens, ts, n_tokens);
+    finish_tokens(out, ex, tokens, ts, n_tokens);
 }
 
 // ---------------------------------------------------------------------------
@@ -1164,14 +1160,11 @@ void Engine::offline_greedy_feats(const float* const* feats, const int64_t* n_fl
             o += n_floats[b];
         }
     }
-    long long* d_tok = nullptr;
-    int *d_ts = nullptr, *d_n = nullptr, *d_ovf = nullptr;
+    SearchOut out;
+    SearchExtras ex;
     run_sized([&](const Ctx& c) {
         Arena& ar = *c.arena;
-        d_tok = ar.take<long long>((int64_t)B * max_tokens);
-        d_ts = ar.take<int>((int64_t)B * max_tokens);
-        d_n = ar.take<int>(B);
-        d_ovf = ar.take<int>(1);
+        out = SearchOut(ar, B, max_tokens);
         float* d_packed = ar.take<float>(total);
         long long* d_off = ar.take<long long>(B);
         long long* d_len = ar.take<long long>(B);
@@ -1184,21 +1177,10 @@ void Engine::offline_greedy_feats(const float* const* feats, const int64_t* n_fl
             K2_HIP(hipEventRecord(ev_[1], c.stream));
         }
         pad_logfloor(c, d_packed, d_off, d_len, d_x, B, L);
-        if (!c.dry) K2_HIP(hipEventRecord(ev_[2], c.stream));
-        int Tp = 0;
-        float* enc = encoder_forward(c, d_x, B, T, &Tp, -1, nullptr, nullptr, nullptr);
-        if (!c.dry) K2_HIP(hipEventRecord(ev_[3], c.stream));
-        greedy_device(c, enc, B, Tp, single, d_tok, d_ts, d_n, max_tokens, d_ovf);
-        if (!c.dry) K2_HIP(hipEventRecord(ev_[4], c.stream));
+        ex = encode_and_search(c, d_x, B, T, single, out);
     });
-    finish_tokens(d_tok, d_ts, d_n, d_ovf, B, max_tokens, tokens, ts, n_tokens);
-    auto el = [&](int a, int b) { float ms = 0; (void)hipEventElapsedTime(&ms, ev_[a], ev_[b]); return ms; };
-    timing_.fbank_ms = 0;
-    timing_.pad_ms = el(1, 2);
-    timing_.encoder_ms = el(2, 3);
-    timing_.greedy_ms = el(3, 4);
-    timing_.d2h_ms = el(4, 5);
-    timing_.total_ms = el(0, 5);
+    finish_tokens(out, ex, tokens, ts, n_tokens);
+    fill_timing(false, true);
 }
 
 void Engine::offline_greedy_samples_dev(const float* samples_dev, int64_t n_each, int B, int64_t* tokens, int32_t* ts,
@@ -1211,14 +1193,11 @@ void Engine::offline_greedy_samples_dev(const float* samples_dev, int64_t n_each
     K2_REQUIRE(nf > 0, "offline_greedy_from_samples: %lld samples give no frame", (long long)n_each);
     const int64_t n_fl = nf * cf.feat, L = n_fl + 80 * kTailFrames;
     const int T = (int)(L / cf.feat);
-    long long* d_tok = nullptr;
-    int *d_ts = nullptr, *d_n = nullptr, *d_ovf = nullptr;
+    SearchOut out;
+    SearchExtras ex;
     run_sized([&](const Ctx& c) {
         Arena& ar = *c.arena;
-        d_tok = ar.take<long long>((int64_t)B * max_tokens);
-        d_ts = ar.take<int>((int64_t)B * max_tokens);
-        d_n = ar.take<int>(B);
-        d_ovf = ar.take<int>(1);
+        out = SearchOut(ar, B, max_tokens);
         float* d_feats = ar.take<float>((int64_t)B * n_fl);
         float* d_x = ar.take<float>((int64_t)B * L);
         if (!c.dry) K2_HIP(hipEventRecord(ev_[0], c.stream));
@@ -1228,21 +1207,10 @@ void Engine::offline_greedy_samples_dev(const float* samples_dev, int64_t n_each
         fbank(c, a);
         if (!c.dry) K2_HIP(hipEventRecord(ev_[1], c.stream));
         pad_logfloor_dense(c, d_feats, n_fl, d_x, B, L);
-        if (!c.dry) K2_HIP(hipEventRecord(ev_[2], c.stream));
-        int Tp = 0;
-        float* enc = encoder_forward(c, d_x, B, T, &Tp, -1, nullptr, nullptr, nullptr);
-        if (!c.dry) K2_HIP(hipEventRecord(ev_[3], c.stream));
-        greedy_device(c, enc, B, Tp, false, d_tok, d_ts, d_n, max_tokens, d_ovf);
-        if (!c.dry) K2_HIP(hipEventRecord(ev_[4], c.stream));
+        ex = encode_and_search(c, d_x, B, T, false, out);
     });
-    finish_tokens(d_tok, d_ts, d_n, d_ovf, B, max_tokens, tokens, ts, n_tokens);
-    auto el = [&](int a, int b) { float ms = 0; (void)hipEventElapsedTime(&ms, ev_[a], ev_[b]); return ms; };
-    timing_.fbank_ms = el(0, 1);
-    timing_.pad_ms = el(1, 2);
-    timing_.encoder_ms = el(2, 3);
-    timing_.greedy_ms = el(3, 4);
-    timing_.d2h_ms = el(4, 5);
-    timing_.total_ms = el(0, 5);
+    finish_tokens(out, ex, tokens, ts, n_tokens);
+    fill_timing(true, true);
 }
 
 void Engine::offline_greedy_samples(const float* const* samples, const int64_t* n_samples, int B, int64_t* tokens, int32_t* ts,
@@ -1275,7 +1243,7 @@ void Engine::offline_greedy_samples(const float* const* samples, const int64_t* 
     // the host block: [samples (not with pinned_src)] | feature offsets | feature lengths | [sample pointers | sample counts]
     const int64_t hb_s = pinned_src ? 0 : nb_s, hb_in = hb_s + 32 * (int64_t)B;
     // (sized for the token download as well: finish_tokens takes the same buffer and must not re-allocate it under the upload)
-    char* pin = static_cast<char*>(pinned(std::max<int64_t>(hb_in, (int64_t)B * max_tokens * 12 + 4 * (int64_t)B + 64) + 64));
+    char* pin = static_cast<char*>(pinned(std::max<int64_t>(hb_in, SearchOut::bytes_for(B, max_tokens)) + 64));
     long long* h_off = reinterpret_cast<long long*>(pin + hb_s);
     long long* h_len = h_off + B;
     const float** h_ptr = reinterpret_cast<const float**>(h_len + B);
@@ -1312,14 +1280,11 @@ void Engine::offline_greedy_samples(const float* const* samples, const int64_t* 
         h_off[b] = (long long)b * n_fl;
         h_len[b] = fbank_num_frames(n_samples[b]) * cf.feat;
     }
-    long long* d_tok = nullptr;
-    int *d_ts = nullptr, *d_n = nullptr, *d_ovf = nullptr;
+    SearchOut out;
+    SearchExtras ex;
     run_sized([&](const Ctx& c) {
         Arena& ar = *c.arena;
-        d_tok = ar.take<long long>((int64_t)B * max_tokens);
-        d_ts = ar.take<int>((int64_t)B * max_tokens);
-        d_n = ar.take<int>(B);
-        d_ovf = ar.take<int>(1);
+        out = SearchOut(ar, B, max_tokens);
         char* d_in = ar.take<char>(nb_s + 32 * (int64_t)B);
         float* d_s = reinterpret_cast<float*>(d_in);
         long long* d_off = reinterpret_cast<long long*>(d_in + nb_s);
@@ -1340,21 +1305,10 @@ void Engine::offline_greedy_samples(const float* const* samples, const int64_t* 
         fbank(c, a);
         if (!c.dry) K2_HIP(hipEventRecord(ev_[1], c.stream));
         pad_logfloor(c, d_feats, d_off, d_len, d_x, B, L);
-        if (!c.dry) K2_HIP(hipEventRecord(ev_[2], c.stream));
-        int Tp = 0;
-        float* enc = encoder_forward(c, d_x, B, T, &Tp, -1, nullptr, nullptr, nullptr);
-        if (!c.dry) K2_HIP(hipEventRecord(ev_[3], c.stream));
-        greedy_device(c, enc, B, Tp, single, d_tok, d_ts, d_n, max_tokens, d_ovf);
-        if (!c.dry) K2_HIP(hipEventRecord(ev_[4], c.stream));
+        ex = encode_and_search(c, d_x, B, T, single, out);
     });
-    finish_tokens(d_tok, d_ts, d_n, d_ovf, B, max_tokens, tokens, ts, n_tokens);
-    auto el = [&](int a, int b) { float ms = 0; (void)hipEventElapsedTime(&ms, ev_[a], ev_[b]); return ms; };
-    timing_.fbank_ms = el(0, 1);   // (includes the samples' H2D copy)
-    timing_.pad_ms = el(1, 2);
-    timing_.encoder_ms = el(2, 3);
-    timing_.greedy_ms = el(3, 4);
-    timing_.d2h_ms = el(4, 5);
-    timing_.total_ms = el(0, 5);
+    finish_tokens(out, ex, tokens, ts, n_tokens);
+    fill_timing(true, true);
 }
 
 int Engine::submit_samples_dev(const float* samples_dev, int64_t n_each, int B, int max_tokens) {
@@ -1392,7 +1346,7 @@ int Engine::submit_impl(const float* samples_dev, const float* samples_host, int
     if (!sl.stream) K2_HIP(hipStreamCreateWithFlags(&sl.stream, hipStreamNonBlocking));
     const int64_t n_fl = nf * cf.feat, L = n_fl + 80 * kTailFrames;
     const int T = (int)(L / cf.feat);
-    const int64_t nb = (int64_t)B * max_tokens * 12 + (int64_t)B * 4 + 64;
+    const int64_t nb = SearchOut::bytes_for(B, max_tokens);
     if (nb > sl.pin_cap) {
         if (sl.pin) K2_HIP(hipHostFree(sl.pin));
         sl.pin = nullptr;
@@ -1405,10 +1359,7 @@ int Engine::submit_impl(const float* samples_dev, const float* samples_host, int
     try {
         run_sized([&](const Ctx& c) {
             Arena& ar = *c.arena;
-            sl.d_tok = ar.take<long long>((int64_t)B * max_tokens);
-            sl.d_ts = ar.take<int>((int64_t)B * max_tokens);
-            sl.d_n = ar.take<int>(B);
-            sl.d_ovf = ar.take<int>(1);
+            sl.out = SearchOut(ar, B, max_tokens);
             float* d_feats = ar.take<float>((int64_t)B * n_fl);
             float* d_x = ar.take<float>((int64_t)B * L);
             const float* src = samples_dev;
@@ -1438,19 +1389,14 @@ int Engine::submit_impl(const float* samples_dev, const float* samples_host, int
                 K2_HIP(hipEventRecord(sl.enc_done, c.stream));
                 K2_HIP(hipStreamWaitEvent(s2, sl.enc_done, 0));
             }
-            greedy_device(cd, enc, B, Tp, false, sl.d_tok, sl.d_ts, sl.d_n, max_tokens, sl.d_ovf);
+            greedy_device(cd, enc, B, Tp, false, sl.out, false);
         });
     } catch (...) {
         cur_arena_ = &arena_;
         throw;
     }
     cur_arena_ = &arena_;
-    const int64_t nb_tok = (int64_t)B * max_tokens * 8, nb_ts = (int64_t)B * max_tokens * 4, nb_n = (int64_t)B * 4;
-    char* pin = static_cast<char*>(sl.pin);
-    K2_HIP(hipMemcpyAsync(pin, sl.d_tok, nb_tok, hipMemcpyDeviceToHost, s2));
-    K2_HIP(hipMemcpyAsync(pin + nb_tok, sl.d_ts, nb_ts, hipMemcpyDeviceToHost, s2));
-    K2_HIP(hipMemcpyAsync(pin + nb_tok + nb_ts, sl.d_n, nb_n, hipMemcpyDeviceToHost, s2));
-    K2_HIP(hipMemcpyAsync(pin + nb_tok + nb_ts + nb_n, sl.d_ovf, 4, hipMemcpyDeviceToHost, s2));
+    download_search(sl.out, s2, sl.pin);
     K2_HIP(hipEventRecord(sl.done, s2));
     sl.B = B;
     sl.max_tokens = max_tokens;
@@ -1466,29 +1412,8 @@ void Engine::wait_ticket(int ticket, int64_t* tokens, int32_t* ts, int32_t* n_to
     Slot& sl = slots_[ticket];
     K2_HIP(hipEventSynchronize(sl.done));
     sl.busy = false;
-    const int64_t nb_tok = (int64_t)sl.B * sl.max_tokens * 8, nb_ts = (int64_t)sl.B * sl.max_tokens * 4, nb_n = (int64_t)sl.B * 4;
-    char* pin = static_cast<char*>(sl.pin);
-    int ovf = *reinterpret_cast<const int*>(pin + nb_tok + nb_ts + nb_n);
-    note_search(sl.greedy.valid && sl.greedy.a.overflow == sl.d_ovf, ovf == 2 && sl.greedy.valid && sl.greedy.a.overflow == sl.d_ovf);
-    if (ovf == 2 && sl.greedy.valid && sl.greedy.a.overflow == sl.d_ovf) {
-        // exchange timeout (the search's workgroups were not co-resident): once more with one workgroup per stream.  The slot's
-        // arena still holds the encoder output and the search's inputs (it is only rebuilt by the slot's next submit).
-        hipStream_t s2 = sl.search_stream;
-        greedy_relaunch_one_part(s2, sl.greedy);
-        search_retries_++;
-        K2_HIP(hipMemcpyAsync(pin, sl.d_tok, nb_tok, hipMemcpyDeviceToHost, s2));
-        K2_HIP(hipMemcpyAsync(pin + nb_tok, sl.d_ts, nb_ts, hipMemcpyDeviceToHost, s2));
-        K2_HIP(hipMemcpyAsync(pin + nb_tok + nb_ts, sl.d_n, nb_n, hipMemcpyDeviceToHost, s2));
-        K2_HIP(hipMemcpyAsync(pin + nb_tok + nb_ts + nb_n, sl.d_ovf, 4, hipMemcpyDeviceToHost, s2));
-        K2_HIP(hipStreamSynchronize(s2));
-        ovf = *reinterpret_cast<const int*>(pin + nb_tok + nb_ts + nb_n);
-    }
-    sl.greedy.valid = false;
-    if (ovf == 2) failf(K2HIP_ERR_HIP, "greedy search: the vocabulary-parallel exchange timed out (a workgroup never arrived)");
-    if (ovf) failf(K2HIP_ERR_CAPACITY, "a stream emitted more than max_tokens=%d symbols", sl.max_tokens);
-    memcpy(tokens, pin, nb_tok);
-    memcpy(ts, pin + nb_tok, nb_ts);
-    memcpy(n_tokens, pin + nb_tok + nb_ts, nb_n);
+    settle_search(sl.out, sl.search_stream, sl.greedy, sl.pin);
+    SearchOut(sl.pin, sl.B, sl.max_tokens).copy_out(tokens, ts, n_tokens);
 }
 
 namespace {

@@ -12,6 +12,7 @@
 
 #include "kernels.h"
 #include "model.h"
+#include "search_out.h"
 
 namespace k2hip {
 
@@ -141,7 +142,7 @@ class Engine {
     const std::vector<float>& last_scores() const { return last_scores_; }
     // K2HIP_BEAM_TRACE: [B][Tp][2 beam + 1] words of the last synchronous beam search (BeamArgs::trace), and its B / Tp / beam
     const std::vector<int>& last_beam_trace(int* B, int* Tp, int* K) const {
-        *B = trace_B_; *Tp = trace_Tp_; *K = trace_K_;
+        *B = last_trace_shape_[0]; *Tp = last_trace_shape_[1]; *K = last_trace_shape_[2];
         return last_beam_trace_;
     }
     const k2hip_timing& timing() const { return timing_; }
@@ -170,10 +171,7 @@ class Engine {
     // The resumed (streaming) search: while a host buffer is named here, every resumed search also returns the token log-probs of its
     // survivors' suffixes, [B][K][Tp] floats (BeamArgs::yp_out), into it.  The caller names it for one call and clears it.
     void set_beam_yp_out(float* host) { yp_host_ = host; }
-    void set_nbest(int n) {
-        nbest_ = n;
-        d_nb_ = BeamNbest{};
-    }
+    void set_nbest(int n) { nbest_ = n; }
     int nbest() const { return nbest_; }
     const NbestHost& last_nbest() const { return last_nbest_; }
     int batches_in_flight() const {
@@ -211,18 +209,29 @@ class Engine {
     float* encoder_stacks(const Ctx& c, float* x0, int B, int T50, int tap, float** tap_ptr, int* tap_dim, bool* tapped, FullDimSegs* segs_out = nullptr);
     float* encoder_forward(const Ctx& c, const float* x, int B, int T, int* Tp, int tap, float** tap_ptr, int* tap_rows,
                            int* tap_dim);
-    void greedy_device(const Ctx& c, const float* enc, int B, int Tp, bool single, long long* d_tok, int* d_ts, int* d_n,
-                       int max_tokens, int* d_overflow);
+    // device by-products of ONE search, in the arena that search ran in: they travel from the search to the finish_tokens of the same
+    // call and are kept nowhere else (null = that search has none)
+    struct SearchExtras {
+        float* scores = nullptr;              // beam: [B] final scores
+        BeamNbest nb;                         // beam with N-best kept
+        int* trace = nullptr;                 // K2HIP_BEAM_TRACE: [B][Tp][2 K + 1]
+        int trace_B = 0, trace_Tp = 0, trace_K = 0;
+        int *trail = nullptr, *any = nullptr; // CTC: [B] each
+    };
+    // keep_nbest: the caller fetches the beam search's N-best (the synchronous entries; the pipelined route has no place to keep them)
+    SearchExtras greedy_device(const Ctx& c, const float* enc, int B, int Tp, bool single, const SearchOut& out, bool keep_nbest);
+    // the fused offline entries' tail on c.stream: event 2, encoder, event 3, search, event 4
+    SearchExtras encode_and_search(const Ctx& c, const float* d_x, int B, int T, bool single, const SearchOut& out);
+    // timing_ from ev_[0..5]; which of the legs in front of the encoder the call has
+    void fill_timing(bool fbank_leg, bool pad_leg);
     const float* pos_emb(int T);  // cached CompactRelPositionalEncoding table on device
     // linear_pos(pos_emb) of one layer: [rows, ncols] = pe [rows, pe_dim] . W^T.  It does not depend on the audio, so it is computed
     // once per (layer, rows) and kept on the device (a handful of utterance lengths in flight; the cache is dropped when it grows)
     const float* pos_proj_cached(const Ctx& c, int layer, const float* pe, int pe_dim, const float* W, int rows, int ncols);
     std::map<std::pair<int, int>, float*> pp_cache_;
     size_t pp_cache_bytes_ = 0;
-    void ctc_device(const Ctx& c, const float* logp, int B, int Tp, long long* d_tok, int* d_ts, int* d_n, int max_tokens,
-                    int* d_overflow);
-    void beam_device(const Ctx& c, const float* enc, int B, int Tp, long long* d_tok, int* d_ts, int* d_n, int max_tokens,
-                     int* d_overflow);
+    SearchExtras ctc_device(const Ctx& c, const float* logp, int B, int Tp, const SearchOut& out);
+    SearchExtras beam_device(const Ctx& c, const float* enc, int B, int Tp, const SearchOut& out, bool keep_nbest);
     // hw (device pointers) or null: the unbiased search, today's launch
     void beam_resume_device(const Ctx& c, const float* enc, int B, int Tp, int K, const int* d_in, int* d_out, int* d_overflow,
                             const BeamHwIO* hw = nullptr);
@@ -270,8 +279,12 @@ class Engine {
     template <typename F>
     void run_sized(F&& body);
     int submit_impl(const float* samples_dev, const float* samples_host, int64_t n_each, int B, int max_tokens);
-    void finish_tokens(const long long* d_tok, const int* d_ts, const int* d_n, const int* d_ovf, int B, int max_tokens,
-                       int64_t* tokens, int32_t* ts, int32_t* n_tokens);
+    // The end of every search.  download_search enqueues the block's ONE copy into `pin` on the search's stream; once that copy has
+    // landed, settle_search reads the flag, feeds the back-off, repeats a timed-out parted search (`rec`, if it is this block's) with one
+    // part per stream and downloads again, and turns what the flag then says into the call's error.
+    void download_search(const SearchOut& out, hipStream_t s, void* pin);
+    void settle_search(const SearchOut& out, hipStream_t s, GreedyLaunch& rec, void* pin);
+    void finish_tokens(const SearchOut& out, const SearchExtras& ex, int64_t* tokens, int32_t* ts, int32_t* n_tokens);
     Ctx make_ctx(bool dry);
 
     std::unique_ptr<Model> model_;
@@ -285,9 +298,8 @@ class Engine {
         hipStream_t stream = nullptr;  // pipe mode 1: the slot's whole pipeline (fbank .. search .. D2H) runs here
         void* pin = nullptr;
         int64_t pin_cap = 0;
-        long long* d_tok = nullptr;
-        int *d_ts = nullptr, *d_n = nullptr, *d_ovf = nullptr;
-        int B = 0, max_tokens = 0;
+        SearchOut out;                  // the batch's token block in `arena`
+        int B = 0, max_tokens = 0;      // the batch's shape (all that the CPU stand-ins of the engine under tests/native keep of it)
         bool busy = false;
         GreedyLaunch greedy;            // the slot's search launch, kept for the one-part retry
         hipStream_t search_stream = nullptr;
@@ -318,19 +330,14 @@ class Engine {
     float *yp_host_ = nullptr, *d_yp_ = nullptr;
     size_t yp_floats_ = 0;
     void fetch_beam_yp();   // after the resumed search's download: d_yp_ -> yp_host_
-    BeamNbest d_nb_;            // device outputs of the search this call runs (tokens == null: none)
-    int nb_B_ = 0, nb_max_tokens_ = 0;
     NbestHost last_nbest_;
     const int* hw_next_ = nullptr;
     const float *hw_bonus_ = nullptr, *hw_pending_ = nullptr;
     BeamLm lm_;
     // CTC search by-products of the last synchronous call (NumTrailingBlank bookkeeping, OfflineRecognizer.cs:392-397)
-    int *d_trail_ = nullptr, *d_any_ = nullptr;
     std::vector<int> last_trail_, last_any_;
-    float* d_scores_ = nullptr;
-    int* d_beam_trace_ = nullptr;
-    int trace_B_ = 0, trace_Tp_ = 0, trace_K_ = 0;
     std::vector<int> last_beam_trace_;
+    int last_trace_shape_[3] = {0, 0, 0};   // its B / Tp / beam
     float* d_dec_start_ = nullptr;  // [2][J]: decoder outputs of the start contexts [-1, blank], [blank, blank] (model constants)
     const float* decoder_start(const Ctx& c);
     std::vector<float> last_scores_;

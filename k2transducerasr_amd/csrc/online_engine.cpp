@@ -516,15 +516,15 @@ void Engine::online_step_impl(const int* slots, const float* const* chunks, cons
     const Model& m = *model_;
     const Config& cf = m.cfg();
     const int T = cf.chunk_T, Tp = online_frames_per_chunk();
-    long long* d_tok = nullptr;
-    int *d_ts = nullptr, *d_n = nullptr, *d_ovf = nullptr;
+    SearchOut out;
+    SearchExtras ex;
     // the streams' chunks, gathered once into pinned staging (one host copy; the H2D below is then a real asynchronous DMA)
     const size_t chunk_floats = (size_t)T * cf.feat;
     K2_HIP(hipSetDevice(device_));
     const bool from_fifo = fifo_heads != nullptr && online_fifo_ != nullptr;  // the chunks are already on the device (FIFO mirror)
     // ONE upload per tick: [chunks' frames (only when they are not on the device yet) | plens | hyps | slots | chunk counts | FIFO heads |
     // overflow flag = 0], packed in pinned staging in the device block's layout (five small copies from pageable memory + a memset were
-    // six blit launches of ~4 us each at the head of the step); ONE download: [tokens | timestamps | counts | overflow flag]
+    // six blit launches of ~4 us each at the head of the step); ONE download: the SearchOut block, whose flag is the upload's last 16 bytes
     // Under beam search the upload carries the streams' saved hypotheses and relation tables too (in front of the flag), and the
     // download is [flag | the surviving hypotheses' out blocks] instead of the greedy tokens.  With hotword graphs attached the saved
     // hypotheses' graph states and the streams' table pointers follow the in blocks, the survivors' states the out blocks.
@@ -552,81 +552,61 @@ void Engine::online_step_impl(const int* slots, const float* const* chunks, cons
         memcpy(stage + o_hg, bhw->graphs, (size_t)nb_hg);
     }
     memset(stage + o_ovf, 0, 16);
-    const int64_t nb_tok = beam ? nb_bout : (int64_t)B * Tp * 8, nb_ts = beam ? 0 : (int64_t)B * Tp * 4, nb_n = beam ? 0 : (int64_t)B * 4;
+    const int64_t nb_out = beam ? nb_bout : SearchOut::bytes_for(B, Tp) - 16;   // what follows the flag
     run_sized([&](const Ctx& c) {
         Arena& ar = *c.arena;
         // one device block: the inputs, the overflow flag (uploaded as zero: the last 16 bytes of the input part), the outputs right
-        // behind it -- [flag | tokens | timestamps | counts] is the layout finish_tokens downloads in one copy
-        char* d_in = ar.take<char>(in_bytes + nb_tok + nb_ts + nb_n);
+        // behind it -- a SearchOut placed on the flag, or under beam search [flag | out blocks]
+        char* d_in = ar.take<char>(in_bytes + nb_out);
         char* d_out = d_in + in_bytes;
-        d_tok = reinterpret_cast<long long*>(d_out);
-        d_ts = reinterpret_cast<int*>(d_out + nb_tok);
-        d_n = reinterpret_cast<int*>(d_out + nb_tok + nb_ts);
-        d_ovf = reinterpret_cast<int*>(d_in + o_ovf);
+        out = SearchOut(d_in + o_ovf, B, Tp);
         float* d_x = from_fifo ? ar.take<float>((int64_t)B * T * cf.feat) : reinterpret_cast<float*>(d_in);
         long long* d_plen = reinterpret_cast<long long*>(d_in + o_plen);
         long long* d_hyp = reinterpret_cast<long long*>(d_in + o_hyp);
         int* d_slots = reinterpret_cast<int*>(d_in + o_slots);
         int* d_chunks = reinterpret_cast<int*>(d_in + o_chunks);
         int* d_heads = reinterpret_cast<int*>(d_in + o_heads);
-        const int* d_bin = reinterpret_cast<const int*>(d_in + o_bin);
-        int* d_bout = reinterpret_cast<int*>(d_out);
         const BeamHwIO dhw{reinterpret_cast<const BeamHwStream*>(d_in + o_hg), reinterpret_cast<const int*>(d_in + o_hst),
                            reinterpret_cast<int*>(d_out + o_hout), bhw && bhw->lm};
-        const BeamHwIO* d_hw = bhw ? &dhw : nullptr;
         if (!c.dry) {
             K2_HIP(hipEventRecord(ev_[0], c.stream));
             K2_HIP(hipMemcpyAsync(d_in, stage, (size_t)in_bytes, hipMemcpyHostToDevice, c.stream));
         }
-        // the tick's search: rounds of joiner GEMMs + a per-stream step kernel, or the persistent kernel where its rounds go through
-        // the f16 screen (measured per model: greedy_loop_screens)
-        const bool persistent_search = tunables().search_rounds == 0 || (tunables().search_rounds < 0 && !cf.ctc && greedy_loop_screens(decjoin(), B, true, c.one_part));
-        const bool ev_ok = !c.dry;
         // online PadSequence (PadHelper.cs:9-13,58): the floor of genuine zeros runs inside the gather when the chunks come from the FIFO
         if (from_fifo) fifo_gather(c, online_fifo_, kFifoFrames, cf.feat, d_slots, d_heads, d_x, B, T);
         else logfloor_inplace(c, d_x, (long long)B * T * cf.feat);
+        float* enc = nullptr;
         if (cf.lstm || cf.conformer || cf.zip1) {
             int tc = Tp;
-            float* enc = cf.lstm ? lstm_chunk(c, d_x, d_slots, B) : cf.zip1 ? zip1_chunk(c, d_x, d_slots, B, &tc) : conformer_chunk(c, d_x, d_slots, d_plen, B, &tc);
+            enc = cf.lstm ? lstm_chunk(c, d_x, d_slots, B) : cf.zip1 ? zip1_chunk(c, d_x, d_slots, B, &tc) : conformer_chunk(c, d_x, d_slots, d_plen, B, &tc);
             K2_REQUIRE(tc == Tp, "internal: chunk yields %d frames, expected %d", tc, Tp);
-            if (ev_ok) K2_HIP(hipEventRecord(ev_[3], c.stream));
-            if (beam) {
-                beam_resume_device(c, enc, B, Tp, beam->K, d_bin, d_bout, d_ovf, d_hw);
-                if (ev_ok) K2_HIP(hipEventRecord(ev_[4], c.stream));
-                return;
-            }
-            GreedyArgs a;
-            a.enc = enc; a.B = B; a.Tp = Tp; a.t0 = nullptr; a.skip1 = 1; a.max_sym = INT_MAX;
-            a.tokens = d_tok; a.timestamps = d_ts; a.n_tokens = d_n; a.max_tokens = Tp; a.overflow = d_ovf; a.init_ctx = d_hyp; a.screen_counts = screen_counts();
-            if (persistent_search) greedy_loop(c, decjoin(), a);
-            else greedy_rounds(c, decjoin(), model_->w("joiner.output_linear.weight"), a);
-            if (ev_ok) K2_HIP(hipEventRecord(ev_[4], c.stream));
-            return;
+        } else {
+            enc = online_encoder_zip2(c, d_x, d_slots, d_plen, d_chunks, B);
         }
-        float* enc = online_encoder_zip2(c, d_x, d_slots, d_plen, d_chunks, B);
-        if (ev_ok) K2_HIP(hipEventRecord(ev_[3], c.stream));
+        if (!c.dry) K2_HIP(hipEventRecord(ev_[3], c.stream));
         if (cf.ctc) {
             // OnlineRecognizer.ForwardBatchGreedySearchCTC (:220-313): per-chunk CTC collapse, prev_id reset per chunk
-            ctc_device(c, enc, B, Tp, d_tok, d_ts, d_n, Tp, d_ovf);
-            if (ev_ok) K2_HIP(hipEventRecord(ev_[4], c.stream));
-            return;
+            ex = ctc_device(c, enc, B, Tp, out);
+        } else if (beam) {   // modified beam search resumed from the streams' saved hypotheses, on the tick's encoder buffer
+            beam_resume_device(c, enc, B, Tp, beam->K, reinterpret_cast<const int*>(d_in + o_bin), reinterpret_cast<int*>(d_out), out.flag(),
+                               bhw ? &dhw : nullptr);
+        } else {
+            // OnlineRecognizer.cs:135-202: decoder on the streams' hyps, T' joiner steps, skip {blank, unk, 1}
+            GreedyArgs a;
+            a.enc = enc; a.B = B; a.Tp = Tp; a.t0 = nullptr; a.skip1 = 1; a.max_sym = INT_MAX;
+            a.tokens = out.tokens(); a.timestamps = out.timestamps(); a.n_tokens = out.counts(); a.max_tokens = Tp; a.overflow = out.flag();
+            a.init_ctx = d_hyp; a.screen_counts = screen_counts();
+            // rounds of joiner GEMMs + a per-stream step kernel, or the persistent kernel where its rounds go through the f16 screen
+            // (measured per model: greedy_loop_screens)
+            const bool persistent_search = tunables().search_rounds == 0 || (tunables().search_rounds < 0 && greedy_loop_screens(decjoin(), B, true, c.one_part));
+            if (persistent_search) greedy_loop(c, decjoin(), a);
+            else greedy_rounds(c, decjoin(), model_->w("joiner.output_linear.weight"), a);
         }
-        if (beam) {   // modified beam search resumed from the streams' saved hypotheses, on the tick's encoder buffer
-            beam_resume_device(c, enc, B, Tp, beam->K, d_bin, d_bout, d_ovf, d_hw);
-            if (ev_ok) K2_HIP(hipEventRecord(ev_[4], c.stream));
-            return;
-        }
-        // OnlineRecognizer.cs:135-202: decoder on the streams' hyps, T' joiner steps, skip {blank, unk, 1}
-        GreedyArgs a;
-        a.enc = enc; a.B = B; a.Tp = Tp; a.t0 = nullptr; a.skip1 = 1; a.max_sym = INT_MAX;
-        a.tokens = d_tok; a.timestamps = d_ts; a.n_tokens = d_n; a.max_tokens = Tp; a.overflow = d_ovf; a.init_ctx = d_hyp; a.screen_counts = screen_counts();
-        if (persistent_search) greedy_loop(c, decjoin(), a);
-        else greedy_rounds(c, decjoin(), model_->w("joiner.output_linear.weight"), a);
-        if (ev_ok) K2_HIP(hipEventRecord(ev_[4], c.stream));
+        if (!c.dry) K2_HIP(hipEventRecord(ev_[4], c.stream));
     });
     if (beam) {   // ONE download: [flag | out blocks]
         char* pin = static_cast<char*>(pinned(16 + nb_bout));
-        K2_HIP(hipMemcpyAsync(pin, d_ovf, (size_t)(16 + nb_bout), hipMemcpyDeviceToHost, stream_));
+        K2_HIP(hipMemcpyAsync(pin, out.flag(), (size_t)(16 + nb_bout), hipMemcpyDeviceToHost, stream_));
         K2_HIP(hipEventRecord(ev_[5], stream_));
         K2_HIP(hipStreamSynchronize(stream_));
         if (*reinterpret_cast<int*>(pin)) failf(K2HIP_ERR_HIP, "online beam search: a hypothesis outgrew its buffer");
@@ -634,15 +614,9 @@ void Engine::online_step_impl(const int* slots, const float* const* chunks, cons
         if (bhw) memcpy(bhw->st_out, pin + 16 + o_hout, (size_t)nb_hst);
         fetch_beam_yp();
     } else {
-        finish_tokens(d_tok, d_ts, d_n, d_ovf, B, Tp, tokens, ts, n_tokens);
+        finish_tokens(out, ex, tokens, ts, n_tokens);
     }
-    auto el = [&](int a, int b) { float ms = 0; (void)hipEventElapsedTime(&ms, ev_[a], ev_[b]); return ms; };
-    timing_.fbank_ms = 0;
-    timing_.pad_ms = 0;
-    timing_.encoder_ms = el(0, 3);
-    timing_.greedy_ms = el(3, 4);
-    timing_.d2h_ms = el(4, 5);
-    timing_.total_ms = el(0, 5);
+    fill_timing(false, false);
 }
 
 // IOnlineProj.EncoderProj (OnlineProjOfZipformer2.cs:491-618) as an operator: feats [B, chunk_T, feat] host, the B slots' caches

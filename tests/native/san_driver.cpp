@@ -4,6 +4,7 @@
 //   san_driver fuzz <file> <seed> <iters>  parse <iters> mutated copies (truncations, byte flips, field overwrites in the header);
 //                                          prints the OK / ERR counts.  Any crash or sanitizer report fails the process.
 //   san_driver text <tokens.txt> <online 0|1> <id> ...   decode ids to text
+//   san_driver searchout                   the arithmetic of SearchOut (csrc/search_out.h), the one layout of a search's token outputs
 #include <unistd.h>
 
 #include <cstdio>
@@ -16,6 +17,7 @@
 
 #include "../../k2transducerasr_amd/csrc/errors.h"
 #include "../../k2transducerasr_amd/csrc/k2w_file.h"
+#include "../../k2transducerasr_amd/csrc/search_out.h"
 #include "../../k2transducerasr_amd/csrc/text.h"
 
 using namespace k2hip;
@@ -35,7 +37,57 @@ static int parse(const std::string& path, bool verbose) {
     }
 }
 
+struct OneBlockArena {   // hands out one 256-aligned block of exactly the bytes asked for, as the engine's arena would
+    char* p = nullptr;
+    int64_t n = 0;
+    template <typename T>
+    T* take(int64_t count) {
+        n = count * (int64_t)sizeof(T);
+        p = static_cast<char*>(aligned_alloc(256, (size_t)((n + 255) / 256 * 256)));
+        return reinterpret_cast<T*>(p);
+    }
+    ~OneBlockArena() { free(p); }
+};
+
+// SearchOut: the four parts in order, without overlap, aligned to 16 / 8 / 4 / 4 bytes from a 256-aligned base, summing to bytes();
+// the form taken from an arena equal to the form placed at the same address; every byte of the block writable through the accessors
+// and none beyond (the allocation is exactly bytes() long, AddressSanitizer watches its end).
+static int check_search_out() {
+    static const int shapes[][2] = {{1, 1}, {3, 7}, {32, 250}, {128, 16}};
+    for (const auto& sh : shapes) {
+        const int B = sh[0], mt = sh[1];
+        OneBlockArena ar;
+        const SearchOut o(ar, B, mt);
+        const char *f = reinterpret_cast<const char*>(o.flag()), *t = reinterpret_cast<const char*>(o.tokens()),
+                   *s = reinterpret_cast<const char*>(o.timestamps()), *c = reinterpret_cast<const char*>(o.counts());
+        const int64_t want = 16 + (int64_t)B * mt * 8 + (int64_t)B * mt * 4 + (int64_t)B * 4;
+        bool ok = o.base == ar.p && ar.n == o.bytes() && o.bytes() == want && o.bytes() == SearchOut::bytes_for(B, mt);
+        ok = ok && ((uintptr_t)ar.p % 256) == 0 && f == ar.p;
+        ok = ok && t == f + 16 && s == t + (int64_t)B * mt * 8 && c == s + (int64_t)B * mt * 4 && c + (int64_t)B * 4 == f + o.bytes();   // in order, gapless
+        ok = ok && o.tokens_bytes() == s - t && o.timestamps_bytes() == c - s && o.counts_bytes() == (int64_t)B * 4;
+        ok = ok && (uintptr_t)f % 16 == 0 && (uintptr_t)t % 8 == 0 && (uintptr_t)s % 4 == 0 && (uintptr_t)c % 4 == 0;
+        const SearchOut q(static_cast<void*>(ar.p), B, mt);
+        ok = ok && q.B == o.B && q.max_tokens == o.max_tokens && q.base == o.base && q.flag() == o.flag() && q.tokens() == o.tokens() &&
+             q.timestamps() == o.timestamps() && q.counts() == o.counts() && q.bytes() == o.bytes();
+        if (!ok) { printf("searchout FAILED at B=%d max_tokens=%d\n", B, mt); return 6; }
+        // write every element through the accessors, read it back through copy_out
+        *o.flag() = 0;
+        for (int64_t i = 0; i < (int64_t)B * mt; i++) { o.tokens()[i] = 1000 + i; o.timestamps()[i] = (int)(7 * i); }
+        for (int b = 0; b < B; b++) o.counts()[b] = b % (mt + 1);
+        std::vector<int64_t> ht((size_t)B * mt);
+        std::vector<int32_t> hs((size_t)B * mt), hn((size_t)B);
+        q.copy_out(ht.data(), hs.data(), hn.data());
+        for (int64_t i = 0; i < (int64_t)B * mt; i++)
+            if (ht[(size_t)i] != 1000 + i || hs[(size_t)i] != (int)(7 * i)) return 7;
+        for (int b = 0; b < B; b++)
+            if (hn[(size_t)b] != b % (mt + 1)) return 7;
+    }
+    printf("searchout OK\n");
+    return 0;
+}
+
 int main(int argc, char** argv) {
+    if (argc >= 2 && !strcmp(argv[1], "searchout")) return check_search_out();
     if (argc >= 3 && !strcmp(argv[1], "k2w")) {
         int r = parse(argv[2], true);
         return r == 2 ? 3 : 0;  // a wrong error class is a failure; OK and K2HIP_ERR_IO are both valid outcomes
@@ -95,6 +147,6 @@ int main(int argc, char** argv) {
         }
         return 0;
     }
-    fprintf(stderr, "usage: san_driver k2w|fuzz|text ...\n");
+    fprintf(stderr, "usage: san_driver k2w|fuzz|text|searchout ...\n");
     return 64;
 }

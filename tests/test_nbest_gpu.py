@@ -196,6 +196,93 @@ def test_offline_recognizer_streams_carry_the_alternatives(tiny_model_path, orac
     assert excused == 0
 
 
+def same_alternatives(got, want):
+    """two N-best lists of a batch ([stream][alternative] dicts), bit for bit"""
+    assert [len(a) for a in got] == [len(a) for a in want]
+    for ga, wa in zip(got, want):
+        for g, w in zip(ga, wa):
+            assert (g["tokens"], g["timestamps"]) == (w["tokens"], w["timestamps"])
+            assert np.float32(g["score"]) == np.float32(w["score"])
+            assert np.array_equal(g["token_log_probs"], w["token_log_probs"])
+
+
+def test_by_products_do_not_outlive_their_call(tiny_model_path, utts):
+    """One handle, three synchronous calls in a row: beam 4 with nbest = 3 on B = 3, the same on B = 2 with another max_tokens (a shorter
+    longest utterance), then greedy search.  Each call's N-best is what a fresh handle returns for that batch alone -- nothing of an
+    earlier search's device by-products (another batch size, another max_tokens, an arena since rebuilt) is fetched -- and the greedy
+    call leaves the streams with no alternatives; a beam call after it has its own again."""
+    from k2transducerasr_amd import OfflineRecognizer
+    batches = [utts[:3], [utts[4], utts[1]]]
+
+    def decode(rec, batch):
+        ss = [rec.create_offline_stream() for _ in batch]
+        for s, u in zip(ss, batch):
+            s.add_samples(u)
+        res = rec.get_results(ss)
+        return res, [s.alternatives() for s in ss], [s.token_log_probs() for s in ss]
+
+    fresh = []
+    for batch in batches:
+        rec = OfflineRecognizer(tiny_model_path, 0, "modified_beam_search", 4, nbest=3)
+        fresh.append(decode(rec, batch))
+        rec.model.close()
+    assert max(len(a) for a in fresh[0][1]) > 1 and max(len(a) for a in fresh[1][1]) > 1   # there are alternatives to mix up
+    rec = OfflineRecognizer(tiny_model_path, 0, "modified_beam_search", 4, nbest=3)
+    for batch, (wres, walts, _) in zip(batches, fresh):
+        res, alts, _ = decode(rec, batch)
+        assert res == wres
+        same_alternatives(alts, walts)
+    rec.model.set_nbest(1)
+    rec.model.set_decoding_method("greedy_search")
+    res, alts, yps = decode(rec, batches[0])
+    assert all(len(a) == 1 and a[0]["tokens"] == [] and a[0]["score"] == 0.0 for a in alts) and all(len(y) == 0 for y in yps)
+    greedy = OfflineRecognizer(tiny_model_path, 0)
+    assert res == decode(greedy, batches[0])[0]
+    greedy.model.close()
+    rec.model.set_decoding_method("modified_beam_search", 4)
+    rec.model.set_nbest(3)
+    res, alts, _ = decode(rec, batches[0])
+    assert res == fresh[0][0]
+    same_alternatives(alts, fresh[0][1])
+    rec.model.close()
+
+
+def test_slab_timeout_repeat_returns_its_own_by_products(tmp_path):
+    """Beam 4, nbest = 2, B = 2 on the V = 400 model (Vp / 4 = 100 column groups: in (64, 128], beam <= 4, 2 B <= a quarter of the CUs --
+    beam_search's two-slab form).  The simulated slab timeout makes the engine repeat the search with one slab: tokens, scores and the
+    N-best the call returns are the REPEAT's, equal to the run without the switch -- and the retry counter shows that the repeat ran."""
+    import ctypes as C
+    from hotword_twin import WIDE_VOCAB, wide_enc
+    from kat_model import write_wide_model
+    from k2transducerasr_amd import Model, load_library, set_switch
+    p = str(tmp_path / "wide.k2w")
+    write_wide_model(p, WIDE_VOCAB)
+    m = Model(p, 0)
+    L = load_library()
+    L.k2hip_debug_search_retries.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
+
+    def retries():
+        n = C.c_int32(-1)
+        assert L.k2hip_debug_search_retries(m.handle, C.byref(n)) == 0
+        return n.value
+
+    enc = wide_enc()[:2]
+    want, wsc = m.beam_search(enc, 4, want_scores=True)
+    want_alts = m.beam_search(enc, 4, nbest=2)
+    assert max(len(a) for a in want_alts) == 2
+    r0 = retries()
+    set_switch("K2HIP_TEST_GREEDY_TIMEOUT", 1)
+    try:
+        got, gsc = m.beam_search(enc, 4, want_scores=True)
+        got_alts = m.beam_search(enc, 4, nbest=2)
+    finally:
+        set_switch("K2HIP_TEST_GREEDY_TIMEOUT", 0)
+    assert retries() == r0 + 2, "the two-slab form did not run: the case shows nothing"
+    assert got == want and gsc.tobytes() == wsc.tobytes()
+    same_alternatives(got_alts, want_alts)
+    m.close()
+
+
 @pytest.mark.parametrize("hotwords", [False, True])
 @pytest.mark.parametrize("beam", [2, 4])
 def test_beam_stream_alternatives_after_every_step(hip_tiny, oracle_tiny, enc_tiny, beam, hotwords):

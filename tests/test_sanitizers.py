@@ -97,6 +97,13 @@ def test_text_stage_under_sanitizers(driver, tmp_path):
     assert run(driver, "text", str(tmp_path / "none.txt"), "0", "1").startswith("ERR -2")
 
 
+def test_search_output_layout_arithmetic(driver):
+    """SearchOut (csrc/search_out.h), the one block [flag | tokens | timestamps | counts] every search writes and every entry point
+    downloads with one copy: for (B, max_tokens) in {(1,1), (3,7), (32,250), (128,16)} the parts are in order, do not overlap, are
+    aligned to 16 / 8 / 4 / 4 bytes from a 256-aligned base and sum to bytes(); the placed form equals the arena form."""
+    assert run(driver, "searchout") == "searchout OK"
+
+
 # ---- the host layer (csrc/api.cpp) under the sanitizers, over tests/native/engine_stub.cpp ---------------------------------------
 API_DRIVER = os.path.join(ROOT, "tests", "native", "k2hip_san_api_driver")
 
