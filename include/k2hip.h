@@ -473,6 +473,39 @@ int32_t k2hip_set_nbest(k2hip_model_t* model, int32_t n /* 1..8 */);
 int32_t k2hip_beam_search_nbest(k2hip_model_t* model, const float* enc_out, int32_t B, int32_t Tprime, int32_t beam, int32_t nbest,
                                 int64_t* tokens, int32_t* timestamps, float* token_log_probs, int32_t* n_tokens, int32_t* n_hyps,
                                 float* scores, int32_t max_tokens);
+/* ---- Forced alignment and full-sum scoring of a given transcript on the RNN-T lattice ------------------------------------------
+ * No reference counterpart: the reference only searches.  The semantics are the project's own, defined here and in DESIGN.md "Forced
+ * alignment and full-sum scoring"; they follow the modified beam search, so the scores are comparable with k2hip_beam_search when
+ * no hotwords and no LM are set.
+ * Per stream: frames t = 0 .. T-1; the target y_1 .. y_U, ids in [0, V), neither blank (0) nor unk (2).  The context of position u
+ * is the last context_size ids of [blank, blank, y_1 .. y_u] (the offline beam search's start state), and
+ * lp(t,u,.) = log_softmax(output_linear(tanh(enc[t] + decoder(ctx_u)))).  Arcs (modified topology, at most one symbol per frame):
+ *   stay(t,u) = logaddexp(lp(t,u,blank), lp(t,u,unk)): (t,u) -> (t+1,u)   (the search's skip set is {blank, unk}, and two candidates
+ *                                                                         that append nothing spell the same sequence and merge)
+ *   emit(t,u) = lp(t,u,y_{u+1}):                       (t,u) -> (t+1,u+1), u < U
+ * total_logp = logsumexp over all paths (0,0) -> (T,U) = log P(transcript | audio); best_logp = their maximum (Viterbi);
+ * timestamps[u] = the frame t of the best path's emit arc of y_{u+1} (the search's convention; strictly increasing);
+ * token_log_probs[u] = that arc's emit value (<= 0, as with k2hip_*_get_token_log_probs).
+ * Tie rule of the Viterbi step: on equal float32 values the emit predecessor (t-1,u-1) wins over the stay predecessor (t-1,u).
+ * All arithmetic is float32; logaddexp(a,b) = m + log1p(exp(min - m)), -inf operands give no NaN.
+ * Hotwords and the n-gram LM set on the model are IGNORED: the lattice scores the acoustic model alone.  The model's decoding
+ * method, N-best setting and later searches are not affected.
+ * Errors: U > T has no path: K2HIP_ERR_INVALID, checked on the host before any device work, the message names the stream; so are a
+ * blank, unk or out-of-vocabulary target id and n_frames outside [1, Tprime].  A CTC model: K2HIP_ERR_UNSUPPORTED.  U = 0 is legal:
+ * total = best = the sum of stay(t,0).  K2HIP_ERR_CAPACITY if any lens[b] > max_tokens; nothing is written then.
+ *
+ * k2hip_transducer_align: operator level, enc_out [B][Tprime][joiner_dim] on the host.  n_frames [B] or NULL (= Tprime for every
+ * stream); ids: the B targets back to back; lens [B].  Outputs, each may be NULL: timestamps / token_log_probs [B][max_tokens] (the
+ * first lens[b] entries of row b are written), total_logp / best_logp [B].
+ * k2hip_offline_align_from_samples: samples -> fbank -> pad -> encoder as k2hip_offline_greedy_from_samples, encoder_out stays on
+ * the device; every stream is aligned over ALL Tprime frames of the padded batch, exactly the frames the searches decode.
+ * *Tprime_out (may be NULL) = that frame count. */
+int32_t k2hip_transducer_align(k2hip_model_t* model, const float* enc_out, int32_t B, int32_t Tprime, const int32_t* n_frames,
+                               const int64_t* ids, const int32_t* lens, int32_t* timestamps, float* token_log_probs, float* total_logp,
+                               float* best_logp, int32_t max_tokens);
+int32_t k2hip_offline_align_from_samples(k2hip_model_t* model, const float* const* samples, const int64_t* n_samples, int32_t B,
+                                         const int64_t* ids, const int32_t* lens, int32_t* timestamps, float* token_log_probs,
+                                         float* total_logp, float* best_logp, int32_t max_tokens, int32_t* Tprime_out);
 /* Per stream.  num_alternatives: the count (>= 1; -1 for NULL, for online streams a negative error code under greedy_search).
  * get_alternative(i): tokens / timestamps / token_log_probs [cap] (each may be NULL), *n = its length, *score = its finalized
  * log-prob; K2HIP_ERR_CAPACITY if cap is too small (nothing is written), K2HIP_ERR_INVALID for i outside the list.

@@ -95,6 +95,12 @@ int32_t k2hip_debug_gemm_run(k2hip_model_t* model, const float* A, const float* 
  *   "gemm_glu_causal_conv": the launcher's arguments in its own order (x, wg, bg, pool, slot_stride, off, slots, wc, bc, ww, bw, sc,
  *     y, B, Tc, D, K), then a buffer of 1 int32 that the hook fills with glu_conv_ring_entry(B, Tc, D, K) (-1: no fused form, and the
  *     call is K2HIP_ERR_UNSUPPORTED with nothing launched).
+ * The two kernels of the forced alignment (csrc/align.hip, tests/test_align_gpu.py); every stream's plane [T_b][U_b + 1] lies back to
+ * back in stream order, T_b = n_frames[b] (a null buffer: Tp), U_b = lens[b]; cells outside the reachable band keep what they held:
+ *   "lattice_logprobs": buffers enc [B][Tp][J], n_frames [B] int32, ids (int64, the targets back to back), lens [B] int32, stay, emit
+ *     (out); ints B, Tp.  The targets pass the checks of k2hip_transducer_align.
+ *   "lattice_dp": buffers n_frames, lens, stay, emit (in), timestamps [B][max_tokens] int32, token_log_probs [B][max_tokens],
+ *     scores [B][2] = (total, best) (out); ints B, Tp, max_tokens.  What lies behind a row's first lens[b] entries is unspecified.
  * One op launches nothing (tests/test_search_ties_gpu.py):
  *   "greedy_screen_counts": no int arguments, one buffer of 2 int64 that the hook fills (whatever out_mask says) with the model's
  *     counters since it was created: [0] rounds of the persistent large-vocabulary greedy search (csrc/greedy.hip k_greedy) that its

@@ -603,6 +603,60 @@ class Model:
         self._chk(self._L.k2hip_offline_greedy_from_samples(self._h, ptrs, _l(ns), B, _l(tok), _i(ts), _i(n), mt))
         return self._unpack(tok, ts, n)
 
+    # ---- forced alignment and full-sum scoring (k2hip.h "Forced alignment and full-sum scoring ...")
+    @staticmethod
+    def _align_targets(targets):
+        tg = [np.ascontiguousarray(t, dtype=np.int64).reshape(-1) for t in targets]
+        lens = np.array([t.size for t in tg], np.int32)
+        ids = np.concatenate(tg) if tg and int(lens.sum()) else np.zeros(0, np.int64)
+        return np.ascontiguousarray(ids, dtype=np.int64), lens
+
+    @staticmethod
+    def _align_result(lens, ts, yp, tot, best):
+        return [dict(timestamps=ts[b, : lens[b]].tolist(), token_log_probs=yp[b, : lens[b]].copy(), total_logp=float(tot[b]),
+                     best_logp=float(best[b])) for b in range(len(lens))]
+
+    def align(self, enc_out, targets, n_frames=None, max_tokens: Optional[int] = None):
+        """k2hip_transducer_align over a host encoder_out [B,T',J]: per stream the forced alignment of targets[b] (token ids, neither
+        blank nor unk) and its full-sum score -> a list of dict(timestamps, token_log_probs, total_logp, best_logp).  n_frames [B]: the
+        frames of each stream that count (default: all T')."""
+        e = _f32(enc_out)
+        B, Tp, _ = e.shape
+        if len(targets) != B:
+            raise ValueError(f"align: {len(targets)} targets for {B} streams")
+        ids, lens = self._align_targets(targets)
+        mt = max(1, int(lens.max())) if max_tokens is None else max_tokens
+        nf = None if n_frames is None else np.ascontiguousarray(n_frames, dtype=np.int32)
+        ts = np.zeros((B, max(mt, 1)), np.int32)
+        yp = np.zeros((B, max(mt, 1)), np.float32)
+        tot = np.zeros(B, np.float32)
+        best = np.zeros(B, np.float32)
+        self._L.k2hip_transducer_align.argtypes = [C.c_void_p, fp, C.c_int32, C.c_int32, ip, lp, ip, ip, fp, fp, fp, C.c_int32]
+        self._chk(self._L.k2hip_transducer_align(self._h, _f(e), B, Tp, None if nf is None else _i(nf), _l(ids), _i(lens), _i(ts), _f(yp),
+                                                 _f(tot), _f(best), mt))
+        return self._align_result(lens, ts, yp, tot, best)
+
+    def align_samples(self, samples: Sequence[np.ndarray], targets, max_tokens: Optional[int] = None):
+        """k2hip_offline_align_from_samples: samples -> fbank -> pad -> encoder on the device, then align() over all T' frames of the
+        padded batch (the frames the searches decode)"""
+        ss = [_f32(s).reshape(-1) for s in samples]
+        B = len(ss)
+        if len(targets) != B:
+            raise ValueError(f"align_samples: {len(targets)} targets for {B} streams")
+        ptrs = (fp * B)(*[_f(s) for s in ss])
+        ns = np.array([s.size for s in ss], np.int64)
+        ids, lens = self._align_targets(targets)
+        mt = max(1, int(lens.max())) if max_tokens is None else max_tokens
+        ts = np.zeros((B, max(mt, 1)), np.int32)
+        yp = np.zeros((B, max(mt, 1)), np.float32)
+        tot = np.zeros(B, np.float32)
+        best = np.zeros(B, np.float32)
+        tp = C.c_int32(0)
+        self._L.k2hip_offline_align_from_samples.argtypes = [C.c_void_p, C.POINTER(fp), lp, C.c_int32, lp, ip, ip, fp, fp, fp, C.c_int32, ip]
+        self._chk(self._L.k2hip_offline_align_from_samples(self._h, ptrs, _l(ns), B, _l(ids), _i(lens), _i(ts), _f(yp), _f(tot), _f(best), mt,
+                                                           C.byref(tp)))
+        return self._align_result(lens, ts, yp, tot, best)
+
     # ---- device-resident benchmark path
     def device_alloc(self, nbytes: int) -> int:
         p = C.c_void_p()
@@ -797,6 +851,10 @@ class OfflineRecognizer:
     def get_result(self, stream: OfflineStream):  # GetResult :77-83
         self.model._chk(self.model._L.k2hip_offline_recognizer_get_result(self.model.handle, stream._h))
         return stream.tokens, stream.timestamps
+
+    def align(self, samples: Sequence[np.ndarray], targets):
+        """forced alignment and full-sum score of targets[b] (token ids) on samples[b] (Model.align_samples; no reference counterpart)"""
+        return self.model.align_samples(samples, targets)
 
 
 # ============================== streaming: OnlineStream / OnlineRecognizer ===============================

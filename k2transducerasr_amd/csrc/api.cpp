@@ -905,6 +905,31 @@ int32_t k2hip_beam_search_nbest(k2hip_model_t* model, const float* enc_out, int3
         }
     });
 }
+// forced alignment / full-sum scoring: the engine checks the targets on the host before any device work (lattice_ref.h)
+int32_t k2hip_transducer_align(k2hip_model_t* model, const float* enc_out, int32_t B, int32_t Tprime, const int32_t* n_frames,
+                               const int64_t* ids, const int32_t* lens, int32_t* timestamps, float* token_log_probs, float* total_logp,
+                               float* best_logp, int32_t max_tokens) {
+    return guard([&] {
+        NEED(model); NEED(enc_out); NEED(lens);
+        K2_REQUIRE(B > 0 && Tprime > 0 && max_tokens >= 0, "align: bad shape B=%d T'=%d max_tokens=%d", B, Tprime, max_tokens);
+        Engine& e = model->engine;
+        if (e.model().cfg().ctc) failf(K2HIP_ERR_UNSUPPORTED, "align: a CTC model has no transducer lattice");
+        EngineLock lk(e);
+        e.align_host(enc_out, B, Tprime, n_frames, ids, lens, timestamps, token_log_probs, total_logp, best_logp, max_tokens);
+    });
+}
+int32_t k2hip_offline_align_from_samples(k2hip_model_t* model, const float* const* samples, const int64_t* n_samples, int32_t B,
+                                         const int64_t* ids, const int32_t* lens, int32_t* timestamps, float* token_log_probs,
+                                         float* total_logp, float* best_logp, int32_t max_tokens, int32_t* Tprime_out) {
+    return guard([&] {
+        NEED(model); NEED(samples); NEED(n_samples); NEED(lens);
+        K2_REQUIRE(B > 0 && max_tokens >= 0, "align_from_samples: bad shape B=%d max_tokens=%d", B, max_tokens);
+        Engine& e = model->engine;
+        if (e.model().cfg().ctc) failf(K2HIP_ERR_UNSUPPORTED, "align: a CTC model has no transducer lattice");
+        EngineLock lk(e);
+        e.align_samples(samples, n_samples, B, ids, lens, timestamps, token_log_probs, total_logp, best_logp, max_tokens, Tprime_out);
+    });
+}
 int32_t k2hip_offline_greedy(k2hip_model_t* model, const float* const* feats, const int64_t* n_floats, int32_t B,
                              int64_t* tokens, int32_t* timestamps, int32_t* n_tokens, int32_t max_tokens) {
     return guard([&] {

@@ -2,6 +2,7 @@
 #include <thread>
 
 #include "engine.h"
+#include "lattice_ref.h"
 
 #include <climits>
 #include <cmath>
@@ -640,6 +641,7 @@ const float* Engine::decoder_start(const Ctx& c) {
 // greedy search on device
 // ---------------------------------------------------------------------------
 Engine::SearchExtras Engine::greedy_device(const Ctx& c, const float* enc, int B, int Tp, bool single, const SearchOut& out, bool keep_nbest) {
+    if (align_plan_) return align_device(c, enc, Tp, *align_plan_, out);
     if (model_->cfg().ctc) return ctc_device(c, enc, B, Tp, out);
     if (beam_ > 0 && !single) return beam_device(c, enc, B, Tp, out, keep_nbest);
     const Config& cf = model_->cfg();
@@ -858,6 +860,10 @@ void Engine::finish_tokens(const SearchOut& out, const SearchExtras& ex, int64_t
         fetch(last_any_, ex.any, (size_t)B);
     }
     if (ex.scores) fetch(last_scores_, ex.scores, (size_t)B);
+    if (ex.align_lp) {
+        fetch(last_align_lp_, ex.align_lp, (size_t)B * max_tokens);
+        fetch(last_align_scores_, ex.align_scores, (size_t)B * 2);
+    }
     NbestHost& h = last_nbest_;
     h.B = 0;
     if (ex.nb.tokens) {
@@ -1129,6 +1135,148 @@ void Engine::greedy_host(const float* enc_out, int B, int Tp, bool single, int64
         ex = greedy_device(c, d_e, B, Tp, single, out, true);
     });
     finish_tokens(out, ex, tokens, ts, n_tokens);
+}
+
+// ---------------------------------------------------------------------------
+// forced alignment and full-sum scoring (align.hip)
+// ---------------------------------------------------------------------------
+Engine::AlignPlan Engine::align_plan(int B, int Tp, const int32_t* n_frames, const int64_t* ids, const int32_t* lens, int max_tokens) const {
+    const Config& cf = model_->cfg();
+    if (cf.ctc) failf(K2HIP_ERR_UNSUPPORTED, "align: a CTC model has no transducer lattice");
+    K2_REQUIRE(cf.ctx == 2, "align: decoder context size %d (2 is built)", cf.ctx);
+    lattice_check_targets(cf.V, B, Tp, n_frames, ids, lens);
+    AlignPlan p;
+    p.B = B; p.Tp = Tp;
+    for (int b = 0; b < B; b++) {
+        if (lens[b] > max_tokens) failf(K2HIP_ERR_CAPACITY, "align: stream %d has %d target tokens, max_tokens is %d", b, lens[b], max_tokens);
+        K2_REQUIRE(lens[b] <= kAlignMaxU, "align: stream %d has %d target tokens (at most %d)", b, lens[b], kAlignMaxU);
+        p.n_ids += lens[b];
+        p.n_ctx += lens[b] + 1;
+    }
+    p.o_ids = align_up((int64_t)sizeof(AlignStream) * B, 16);
+    p.o_ctx = align_up(p.o_ids + (int64_t)sizeof(int) * p.n_ids, 16);
+    p.blob.assign((size_t)(p.o_ctx + (int64_t)sizeof(long long) * 2 * p.n_ctx), 0);
+    AlignStream* st = reinterpret_cast<AlignStream*>(p.blob.data());
+    int* h_ids = reinterpret_cast<int*>(p.blob.data() + p.o_ids);
+    long long* h_ctx = reinterpret_cast<long long*>(p.blob.data() + p.o_ctx);
+    int io = 0, co = 0;
+    for (int b = 0; b < B; b++) {
+        const int T = n_frames ? n_frames[b] : Tp, U = lens[b];
+        st[b] = AlignStream{p.plane_floats, p.bp_words, co, io, U, T};
+        p.plane_floats += (long long)T * (U + 1);
+        p.bp_words += (long long)T * ((U + 1 + 63) / 64);
+        p.max_T = std::max(p.max_T, T);
+        p.max_U = std::max(p.max_U, U);
+        // the context of position u: the last two ids of [blank, blank, y_1 .. y_u] (the offline beam search's start state)
+        long long y0 = K2HIP_BLANK_ID, y1 = K2HIP_BLANK_ID;
+        for (int u = 0; u <= U; u++) {
+            h_ctx[2 * (co + u)] = y0;
+            h_ctx[2 * (co + u) + 1] = y1;
+            if (u < U) {
+                h_ids[io + u] = (int)ids[io + u];
+                y0 = y1;
+                y1 = ids[io + u];
+            }
+        }
+        io += U;
+        co += U + 1;
+    }
+    return p;
+}
+
+Engine::SearchExtras Engine::align_device(const Ctx& c, const float* enc, int Tp, const AlignPlan& p, const SearchOut& out, float* stay,
+                                          float* emit, bool cells, bool dp) {
+    K2_REQUIRE(Tp == p.Tp && out.B == p.B, "internal: the align plan was laid out for T'=%d B=%d, the encoder gave T'=%d B=%d", p.Tp, p.B, Tp, out.B);
+    const Config& cf = model_->cfg();
+    Arena& ar = *c.arena;
+    char* d_blob = ar.take<char>((int64_t)p.blob.size());
+    AlignArgs a;
+    a.enc = enc; a.B = p.B; a.Tp = Tp; a.max_T = p.max_T; a.max_U = p.max_U;
+    a.streams = reinterpret_cast<const AlignStream*>(d_blob);
+    a.ids = reinterpret_cast<const int*>(d_blob + p.o_ids);
+    const long long* d_ctx = reinterpret_cast<const long long*>(d_blob + p.o_ctx);
+    float* d_dec = cells ? ar.take<float>((int64_t)p.n_ctx * cf.J) : nullptr;
+    a.dec = d_dec;
+    a.stay = stay ? stay : ar.take<float>(p.plane_floats);
+    a.emit = emit ? emit : ar.take<float>(p.plane_floats);
+    if (!c.dry) K2_HIP(hipMemcpyAsync(d_blob, p.blob.data(), p.blob.size(), hipMemcpyHostToDevice, c.stream));
+    if (cells) {
+        // the decoder table is not consulted: decoder() runs the U + 1 contexts of every stream in one launch
+        const DecJoinW w = decjoin();
+        decoder(c, w, d_ctx, p.n_ctx, d_dec);
+        lattice_logprobs(c, w, a);
+    }
+    SearchExtras ex;
+    if (!dp) return ex;
+    a.bp = ar.take<unsigned long long>(p.bp_words);
+    ex.align_lp = ar.take<float>((int64_t)p.B * out.max_tokens);
+    ex.align_scores = ar.take<float>((int64_t)p.B * 2);
+    a.tokens = cells ? out.tokens() : nullptr;
+    a.timestamps = out.timestamps(); a.n_tokens = out.counts(); a.max_tokens = out.max_tokens;
+    a.token_log_probs = ex.align_lp; a.scores = ex.align_scores;
+    if (!c.dry) K2_HIP(hipMemsetAsync(out.flag(), 0, sizeof(int), c.stream));
+    lattice_dp(c, a);
+    return ex;
+}
+
+void Engine::align_copy_out(const AlignPlan& p, const int32_t* ts_all, int max_tokens, int32_t* timestamps, float* token_log_probs, float* total,
+                            float* best) const {
+    const AlignStream* st = p.streams();
+    for (int b = 0; b < p.B; b++) {
+        const size_t o = (size_t)b * max_tokens, n = (size_t)st[b].U;
+        if (timestamps && n) memcpy(timestamps + o, ts_all + o, sizeof(int32_t) * n);
+        if (token_log_probs && n) memcpy(token_log_probs + o, last_align_lp_.data() + o, sizeof(float) * n);
+        if (total) total[b] = last_align_scores_[2 * (size_t)b];
+        if (best) best[b] = last_align_scores_[2 * (size_t)b + 1];
+    }
+}
+
+void Engine::align_host(const float* enc_out, int B, int Tp, const int32_t* n_frames, const int64_t* ids, const int32_t* lens, int32_t* timestamps,
+                        float* token_log_probs, float* total, float* best, int max_tokens) {
+    K2_REQUIRE(enc_out != nullptr && max_tokens >= 0, "align: bad arguments");
+    const AlignPlan p = align_plan(B, Tp, n_frames, ids, lens, max_tokens);
+    const Config& cf = model_->cfg();
+    const int mt = std::max(max_tokens, 1);
+    SearchOut out;
+    SearchExtras ex;
+    run_sized([&](const Ctx& c) {
+        float* d_e = c.arena->take<float>((int64_t)B * Tp * cf.J);
+        out = SearchOut(*c.arena, B, mt);
+        if (!c.dry) K2_HIP(hipMemcpyAsync(d_e, enc_out, sizeof(float) * (size_t)B * Tp * cf.J, hipMemcpyHostToDevice, c.stream));
+        ex = align_device(c, d_e, Tp, p, out);
+    });
+    std::vector<int64_t> tok((size_t)B * mt);
+    std::vector<int32_t> ts((size_t)B * mt), n((size_t)B);
+    finish_tokens(out, ex, tok.data(), ts.data(), n.data());
+    align_copy_out(p, ts.data(), mt, timestamps, token_log_probs, total, best);
+}
+
+void Engine::align_samples(const float* const* samples, const int64_t* n_samples, int B, const int64_t* ids, const int32_t* lens,
+                           int32_t* timestamps, float* token_log_probs, float* total, float* best, int max_tokens, int32_t* Tp_out) {
+    K2_REQUIRE(samples != nullptr && n_samples != nullptr && B > 0 && max_tokens >= 0, "align_from_samples: bad arguments");
+    const Config& cf = model_->cfg();
+    if (cf.ctc) failf(K2HIP_ERR_UNSUPPORTED, "align: a CTC model has no transducer lattice");
+    // T' of the padded batch, as offline_greedy_samples derives it: every stream is aligned over all of it, the frames the searches decode
+    int64_t nmax = 0;
+    for (int b = 0; b < B; b++) {
+        K2_REQUIRE(samples[b] != nullptr && fbank_num_frames(n_samples[b]) > 0, "stream %d: %lld samples give no frame", b, (long long)n_samples[b]);
+        nmax = std::max(nmax, n_samples[b]);
+    }
+    const int T = (int)((fbank_num_frames(nmax) * cf.feat + 80 * kTailFrames) / cf.feat);
+    const int Tp = encoder_out_frames(T);
+    K2_REQUIRE(Tp > 0, "align_from_samples: %lld samples give no encoder frame", (long long)nmax);
+    const AlignPlan p = align_plan(B, Tp, nullptr, ids, lens, max_tokens);
+    const int mt = std::max(max_tokens, 1);
+    std::vector<int64_t> tok((size_t)B * mt);
+    std::vector<int32_t> ts((size_t)B * mt), n((size_t)B);
+    struct Scope {
+        const AlignPlan*& slot;
+        ~Scope() { slot = nullptr; }
+    } scope{align_plan_};
+    align_plan_ = &p;
+    offline_greedy_samples(samples, n_samples, B, tok.data(), ts.data(), n.data(), mt);
+    align_copy_out(p, ts.data(), mt, timestamps, token_log_probs, total, best);
+    if (Tp_out) *Tp_out = Tp;
 }
 
 // ---------------------------------------------------------------------------
@@ -1898,6 +2046,54 @@ void Engine::debug_op_host(const char* op, const int64_t* iargs, int n_iargs, vo
             K2_HIP(hipStreamSynchronize(stream_));
             K2_HIP(copy_blocking(out, d_screen_counts_, 2 * sizeof(unsigned long long), hipMemcpyDeviceToDevice));
             out_mask |= 1u;
+        } else if (name == "lattice_logprobs" || name == "lattice_dp") {
+            // lattice_logprobs: bufs enc [B][Tp][J], n_frames [B] int32 (or null), ids int64 back to back, lens [B] int32, stay, emit (out:
+            //   every stream's plane [T_b][U_b + 1], back to back); ints B, Tp
+            // lattice_dp: bufs n_frames, lens, stay, emit (in), timestamps [B][max_tokens] int32, token_log_probs [B][max_tokens],
+            //   scores [B][2] = (total, best) (out); ints B, Tp, max_tokens
+            const bool cells = name == "lattice_logprobs";
+            K2_REQUIRE(n_bufs == (cells ? 6 : 7), "debug_op_run %s: %d buffers", op, n_bufs);
+            const int k_enc = cells ? 0 : -1, k_nf = cells ? 1 : 0, k_ids = cells ? 2 : -1, k_lens = cells ? 3 : 1, k_stay = cells ? 4 : 2,
+                      k_emit = k_stay + 1, k_ts = 4, k_lp = 5, k_sc = 6;
+            for (int k = 0; k < n_bufs; k++) P();
+            const int B = I(), Tp = I(), max_tokens = cells ? INT_MAX : I();
+            K2_REQUIRE(B > 0 && Tp > 0 && max_tokens > 0, "debug_op_run %s: bad shape", op);
+            K2_REQUIRE(bufs[k_lens] && buf_bytes[k_lens] >= 4 * (int64_t)B && (!bufs[k_nf] || buf_bytes[k_nf] >= 4 * (int64_t)B),
+                       "debug_op_run %s: lens / n_frames are too short", op);
+            const int32_t* lens = static_cast<const int32_t*>(bufs[k_lens]);
+            const int32_t* nf = static_cast<const int32_t*>(bufs[k_nf]);
+            int64_t n_ids = 0;
+            for (int b = 0; b < B; b++) n_ids += std::max(lens[b], 0);
+            std::vector<int64_t> fill;   // (lattice_dp reads no targets: any id the check accepts)
+            const int64_t* ids = nullptr;
+            if (cells) {
+                K2_REQUIRE(n_ids == 0 || (bufs[k_ids] && buf_bytes[k_ids] >= 8 * n_ids), "debug_op_run %s: ids are too short", op);
+                ids = static_cast<const int64_t*>(bufs[k_ids]);
+            } else {
+                fill.assign((size_t)n_ids + 1, std::min(3, model_->cfg().V - 1));
+                ids = fill.data();
+            }
+            const AlignPlan p = align_plan(B, Tp, nf, ids, lens, max_tokens);
+            K2_REQUIRE(dev[k_stay] && dev[k_emit] && buf_bytes[k_stay] >= 4 * p.plane_floats && buf_bytes[k_emit] >= 4 * p.plane_floats,
+                       "debug_op_run %s: the planes need %lld floats each", op, p.plane_floats);
+            if (cells) K2_REQUIRE(dev[k_enc] && buf_bytes[k_enc] >= 4 * (int64_t)B * Tp * model_->cfg().J, "debug_op_run %s: enc is too short", op);
+            else
+                K2_REQUIRE(dev[k_ts] && dev[k_lp] && dev[k_sc] && buf_bytes[k_ts] >= 4 * (int64_t)B * max_tokens &&
+                               buf_bytes[k_lp] >= 4 * (int64_t)B * max_tokens && buf_bytes[k_sc] >= 8 * (int64_t)B,
+                           "debug_op_run %s: the result buffers are too short", op);
+            SearchOut out;
+            SearchExtras ex;
+            run_sized([&](const Ctx& cc) {
+                out = SearchOut(*cc.arena, B, cells ? 1 : max_tokens);
+                ex = align_device(cc, cells ? static_cast<const float*>(dev[k_enc]) : nullptr, Tp, p, out, static_cast<float*>(dev[k_stay]),
+                                  static_cast<float*>(dev[k_emit]), cells, !cells);
+            });
+            K2_HIP(hipStreamSynchronize(stream_));
+            if (!cells) {
+                K2_HIP(copy_blocking(dev[k_ts], out.timestamps(), 4 * (size_t)B * max_tokens, hipMemcpyDeviceToDevice));
+                K2_HIP(copy_blocking(dev[k_lp], ex.align_lp, 4 * (size_t)B * max_tokens, hipMemcpyDeviceToDevice));
+                K2_HIP(copy_blocking(dev[k_sc], ex.align_scores, 8 * (size_t)B, hipMemcpyDeviceToDevice));
+            }
         } else if (name == "basicnorm") {
             float *x = P(), *le = P(), *y = P();
             const int M = I(), D = I();

@@ -74,6 +74,14 @@ class Engine {
     void joiner_host(const float* enc, const float* dec, int N, float* logits);
     void greedy_host(const float* enc_out, int B, int Tp, bool single, int64_t* tokens, int32_t* ts, int32_t* n_tokens,
                      int max_tokens);
+    // ---- forced alignment and full-sum scoring of given transcripts (align.hip; semantics in include/k2hip.h) ----
+    // ids: the B targets back to back, lens [B]; n_frames [B] or null (= Tp for every stream).  Outputs (each may be null): timestamps /
+    // token_log_probs [B][max_tokens], total / best [B].  The arguments are checked on the host before any device work (lattice_ref.h).
+    void align_host(const float* enc_out, int B, int Tp, const int32_t* n_frames, const int64_t* ids, const int32_t* lens, int32_t* timestamps,
+                    float* token_log_probs, float* total, float* best, int max_tokens);
+    // fbank + pad + encoder as offline_greedy_samples, encoder_out left on the device, every stream aligned over all T' frames
+    void align_samples(const float* const* samples, const int64_t* n_samples, int B, const int64_t* ids, const int32_t* lens, int32_t* timestamps,
+                       float* token_log_probs, float* total, float* best, int max_tokens, int32_t* Tp_out);
     // ---- fused paths ----
     void offline_greedy_feats(const float* const* feats, const int64_t* n_floats, int B, bool single, int64_t* tokens,
                               int32_t* ts, int32_t* n_tokens, int max_tokens);
@@ -217,7 +225,26 @@ class Engine {
         int* trace = nullptr;                 // K2HIP_BEAM_TRACE: [B][Tp][2 K + 1]
         int trace_B = 0, trace_Tp = 0, trace_K = 0;
         int *trail = nullptr, *any = nullptr; // CTC: [B] each
+        float* align_lp = nullptr;            // align: [B][max_tokens] token log-probs of the best path
+        float* align_scores = nullptr;        // align: [B][2] = (total, best)
     };
+    // One align call as the host lays it out before any device work: the streams' descriptors, targets and contexts in ONE upload block
+    struct AlignPlan {
+        int B = 0, Tp = 0, max_T = 0, max_U = 0, n_ctx = 0, n_ids = 0;
+        long long plane_floats = 0, bp_words = 0;
+        int64_t o_ids = 0, o_ctx = 0;     // byte offsets of the targets (int) and the contexts (long long [n_ctx][2]) behind the descriptors
+        std::vector<char> blob;
+        const AlignStream* streams() const { return reinterpret_cast<const AlignStream*>(blob.data()); }
+    };
+    AlignPlan align_plan(int B, int Tp, const int32_t* n_frames, const int64_t* ids, const int32_t* lens, int max_tokens) const;
+    // decoder over every context, lattice_logprobs, lattice_dp into `out` (tokens = the targets, counts = their lengths).  The test hooks
+    // pass planes of their own (stay / emit) and stop after the first kernel (dp = false) or run only the second (cells = false).
+    SearchExtras align_device(const Ctx& c, const float* enc, int Tp, const AlignPlan& p, const SearchOut& out, float* stay = nullptr,
+                              float* emit = nullptr, bool cells = true, bool dp = true);
+    const AlignPlan* align_plan_ = nullptr;   // while set (the span of align_samples), the fused entries' search is align_device
+    std::vector<float> last_align_lp_, last_align_scores_;
+    void align_copy_out(const AlignPlan& p, const int32_t* ts_all, int max_tokens, int32_t* timestamps, float* token_log_probs, float* total,
+                        float* best) const;
     // keep_nbest: the caller fetches the beam search's N-best (the synchronous entries; the pipelined route has no place to keep them)
     SearchExtras greedy_device(const Ctx& c, const float* enc, int B, int Tp, bool single, const SearchOut& out, bool keep_nbest);
     // the fused offline entries' tail on c.stream: event 2, encoder, event 3, search, event 4

@@ -665,6 +665,39 @@ struct BeamArgs {
 void beam_launch_counts(long long* plain, long long* hw);
 void beam_search(const Ctx& ctx, const DecJoinW& w, const BeamArgs& a);
 
+// ---- forced alignment and full-sum scoring on the RNN-T lattice (align.hip; semantics in include/k2hip.h and lattice_ref.h) ----
+// One stream of an align call: T frames (the first T of its Tp encoder rows), U target tokens, its U + 1 contexts at rows ctx_off ..
+// of the call's decoder outputs, its targets at ids[id_off ..], its two planes [T][U + 1] at plane_off floats into stay / emit, and
+// its back-pointer bits [T][ceil((U + 1) / 64)] 64-bit words at bp_off words into bp.
+struct AlignStream {
+    long long plane_off, bp_off;
+    int ctx_off, id_off, U, T;
+};
+struct AlignArgs {
+    const float* enc = nullptr;          // [B, Tp, J]
+    int B = 0, Tp = 0;
+    int max_T = 0, max_U = 0;            // over the call's streams (the launch grid)
+    const AlignStream* streams = nullptr;   // [B] (device)
+    const int* ids = nullptr;            // the targets back to back (device); lattice_dp: may be null
+    const float* dec = nullptr;          // [sum(U_b + 1)][J]: decoder() of every position's context
+    float *stay = nullptr, *emit = nullptr;
+    unsigned long long* bp = nullptr;
+    // lattice_dp's results: tokens / timestamps / token_log_probs [B][max_tokens] (tokens: the targets back, may be null), n_tokens [B]
+    // (= U, may be null), scores [B][2] = (total, best)
+    long long* tokens = nullptr;
+    int* timestamps = nullptr;
+    float* token_log_probs = nullptr;
+    int* n_tokens = nullptr;
+    float* scores = nullptr;
+    int max_tokens = 0;
+};
+// stay(t,u) = logaddexp(lp(t,u,blank), lp(t,u,unk)) and emit(t,u) = lp(t,u,y_{u+1}) of every cell of the reachable band, with
+// lp = log_softmax(output_linear(tanh(enc[t] + dec[u]))) swept on the f32 matrix pipe -- no logits are stored.  emit(t,U) = -inf.
+void lattice_logprobs(const Ctx& ctx, const DecJoinW& w, const AlignArgs& a);
+// forward (logaddexp) and Viterbi (max, emit wins ties) recursions over the two planes, one workgroup per stream, then the backtrace
+constexpr int kAlignMaxU = 4095;   // U + 1 positions of both recursions' two rows live in LDS
+void lattice_dp(const Ctx& ctx, const AlignArgs& a);
+
 // ---- streaming (online.hip): device-resident per-stream caches indexed by slot ------------------
 // ConvNeXt.streaming_forward's data movement in one launch: cat[b] = [cached_left_pad ; x], the cache advanced to x's frames Tc-3 .. Tc-1,
 // byp[b] = x[b, :Tc] (the bypass operand)
