@@ -506,6 +506,44 @@ int32_t k2hip_transducer_align(k2hip_model_t* model, const float* enc_out, int32
 int32_t k2hip_offline_align_from_samples(k2hip_model_t* model, const float* const* samples, const int64_t* n_samples, int32_t B,
                                          const int64_t* ids, const int32_t* lens, int32_t* timestamps, float* token_log_probs,
                                          float* total_logp, float* best_logp, int32_t max_tokens, int32_t* Tprime_out);
+/* ---- CTC forced alignment and full-sum scoring of given transcripts (zipformer2ctc models) -------------------------------------
+ * No reference counterpart: the reference's CTC path only searches (ForwardBatchGreedySearchCTC).  The semantics are the project's
+ * own, defined here and in DESIGN.md "CTC forced alignment and full-sum scoring".
+ * log_probs [R][Tprime][V] is what the encoder entries of a CTC model return, already log-softmaxed; lp(t, v) is row r's entry.  A
+ * target y_1 .. y_U is scored against row r over that row's first T = n_frames[r] frames.
+ * Target ids lie in [1, V): only blank (0) is illegal; unk is legal, because the CTC search does not filter it either.
+ * Topology (standard CTC): the extended sequence z = [blank, y_1, blank, y_2, .., y_U, blank] with S = 2U + 1 states.  State s at
+ * frame t is reached from s, from s-1, and from s-2; the s-2 predecessor is allowed only when z_s is not blank and z_s != z_{s-2}.
+ * Every arrival pays lp(t, z_s).  Frame 0 starts in state 0 or state 1.  The path ends after frame T-1 in state S-1 or S-2.
+ * total_logp = the log-sum-exp over all such paths = log P(transcript | audio); best_logp = their maximum (Viterbi);
+ * timestamps[u] = the first frame the best path spends in y_{u+1}'s state (the frame at which the CTC greedy collapse would emit the
+ * token); end_frames[u] = the last frame it spends there (timestamps[u] <= end_frames[u] < timestamps[u+1]);
+ * token_log_probs[u] = lp(timestamps[u], y_{u+1}).
+ * All arithmetic is float32; logaddexp(a,b) = m + log1p(exp(min - m)), -inf operands give no NaN.  If every path crosses a -inf
+ * cell, best_logp = total_logp = -inf and the three per-token outputs are unspecified (inside [0, T) and finite or -inf).
+ * Tie rule of the Viterbi step: on equal float32 values the predecessor with the lowest state index wins -- s-2 over s-1 over s; at
+ * the end S-2 wins over S-1.
+ * U = 0 is legal: total = best = the sum of lp(t, blank).  A target needs T >= U + (the number of adjacent equal pairs in y), else it
+ * has no path: K2HIP_ERR_INVALID, decided on the host before any device work, the message names the target ("target h"); so are a
+ * blank or out-of-range id, n_frames outside [1, Tprime] and a stream_of entry outside [0, R).  At most 4095 tokens per target and
+ * 65535 targets per call (K2HIP_ERR_INVALID beyond).  K2HIP_ERR_CAPACITY if any lens[h] > max_tokens; nothing is written then.  A
+ * transducer model has no CTC head: K2HIP_ERR_UNSUPPORTED.  (k2hip_transducer_align / k2hip_offline_align_from_samples keep refusing a
+ * CTC model.)
+ *
+ * k2hip_ctc_align: operator level, log_probs [R][Tprime][V] on the host.  n_frames [R] or NULL (= Tprime for every row).  H targets:
+ * ids = the targets back to back, lens [H]; stream_of [H] names the row each target is scored against, NULL = H == R and the identity
+ * (rescoring a candidate list against one utterance is one call with no duplicated activations).  Outputs, each may be NULL:
+ * timestamps / end_frames / token_log_probs [H][max_tokens] (the first lens[h] entries of row h are written), total_logp / best_logp [H].
+ * k2hip_offline_ctc_align_from_samples: samples -> fbank -> pad -> encoder as k2hip_offline_greedy_from_samples, log_probs stay on
+ * the device (R = B); every target is aligned over ALL Tprime frames of the padded batch, exactly the frames the CTC search decodes.
+ * *Tprime_out (may be NULL) = that frame count. */
+int32_t k2hip_ctc_align(k2hip_model_t* model, const float* log_probs, int32_t R, int32_t Tprime, const int32_t* n_frames, int32_t H,
+                        const int32_t* stream_of, const int64_t* ids, const int32_t* lens, int32_t* timestamps, int32_t* end_frames,
+                        float* token_log_probs, float* total_logp, float* best_logp, int32_t max_tokens);
+int32_t k2hip_offline_ctc_align_from_samples(k2hip_model_t* model, const float* const* samples, const int64_t* n_samples, int32_t B, int32_t H,
+                                             const int32_t* stream_of, const int64_t* ids, const int32_t* lens, int32_t* timestamps,
+                                             int32_t* end_frames, float* token_log_probs, float* total_logp, float* best_logp,
+                                             int32_t max_tokens, int32_t* Tprime_out);
 /* Per stream.  num_alternatives: the count (>= 1; -1 for NULL, for online streams a negative error code under greedy_search).
  * get_alternative(i): tokens / timestamps / token_log_probs [cap] (each may be NULL), *n = its length, *score = its finalized
  * log-prob; K2HIP_ERR_CAPACITY if cap is too small (nothing is written), K2HIP_ERR_INVALID for i outside the list.

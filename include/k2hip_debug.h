@@ -101,6 +101,11 @@ int32_t k2hip_debug_gemm_run(k2hip_model_t* model, const float* A, const float* 
  *     (out); ints B, Tp.  The targets pass the checks of k2hip_transducer_align.
  *   "lattice_dp": buffers n_frames, lens, stay, emit (in), timestamps [B][max_tokens] int32, token_log_probs [B][max_tokens],
  *     scores [B][2] = (total, best) (out); ints B, Tp, max_tokens.  What lies behind a row's first lens[b] entries is unspecified.
+ * The CTC forced alignment's device path alone (csrc/ctc_align.hip: gather + lattice; tests/test_ctc_align_gpu.py):
+ *   "ctc_lattice": buffers log_probs [R][Tp][V], n_frames [R] int32 (or null), stream_of [H] int32 (or null), ids (int64, the targets
+ *     back to back), lens [H] int32, timestamps, end_frames [H][max_tokens] int32, token_log_probs [H][max_tokens], scores [H][2] =
+ *     (total, best) (out); ints R, Tp, H, max_tokens.  The arguments pass the checks of k2hip_ctc_align; what lies behind a row's first
+ *     lens[h] entries is unspecified.
  * One op launches nothing (tests/test_search_ties_gpu.py):
  *   "greedy_screen_counts": no int arguments, one buffer of 2 int64 that the hook fills (whatever out_mask says) with the model's
  *     counters since it was created: [0] rounds of the persistent large-vocabulary greedy search (csrc/greedy.hip k_greedy) that its

@@ -657,6 +657,54 @@ class Model:
                                                            C.byref(tp)))
         return self._align_result(lens, ts, yp, tot, best)
 
+    # ---- CTC forced alignment and full-sum scoring (k2hip.h "CTC forced alignment and full-sum scoring ...")
+    @staticmethod
+    def _ctc_align_result(lens, ts, en, yp, tot, best):
+        return [dict(timestamps=ts[h, : lens[h]].tolist(), end_frames=en[h, : lens[h]].tolist(), token_log_probs=yp[h, : lens[h]].copy(),
+                     total_logp=float(tot[h]), best_logp=float(best[h])) for h in range(len(lens))]
+
+    def _ctc_align_buffers(self, what, targets, R, stream_of, max_tokens):
+        H = len(targets)
+        if stream_of is None and H != R:
+            raise ValueError(f"{what}: {H} targets for {R} rows and no stream_of")
+        so = None if stream_of is None else np.ascontiguousarray(stream_of, dtype=np.int32).reshape(-1)
+        if so is not None and so.size != H:
+            raise ValueError(f"{what}: stream_of has {so.size} entries for {H} targets")
+        ids, lens = self._align_targets(targets)
+        mt = max(1, int(lens.max()) if H else 1) if max_tokens is None else max_tokens
+        shape = (max(H, 1), max(mt, 1))
+        return H, so, ids, lens, mt, np.zeros(shape, np.int32), np.zeros(shape, np.int32), np.zeros(shape, np.float32), \
+            np.zeros(max(H, 1), np.float32), np.zeros(max(H, 1), np.float32)
+
+    def ctc_align(self, log_probs, targets, n_frames=None, stream_of=None, max_tokens: Optional[int] = None):
+        """k2hip_ctc_align over host log_probs [R,T',V] (what the encoder entries of a CTC model return): the forced alignment of every
+        target (token ids in [1, V)) and its full-sum score -> a list of dict(timestamps, end_frames, token_log_probs, total_logp,
+        best_logp).  n_frames [R]: the frames of each row that count (default: all T'); stream_of [H]: the row each target is scored
+        against (default: target h against row h)."""
+        x = _f32(log_probs)
+        R, Tp, _ = x.shape
+        H, so, ids, lens, mt, ts, en, yp, tot, best = self._ctc_align_buffers("ctc_align", targets, R, stream_of, max_tokens)
+        nf = None if n_frames is None else np.ascontiguousarray(n_frames, dtype=np.int32)
+        self._L.k2hip_ctc_align.argtypes = [C.c_void_p, fp, C.c_int32, C.c_int32, ip, C.c_int32, ip, lp, ip, ip, ip, fp, fp, fp, C.c_int32]
+        self._chk(self._L.k2hip_ctc_align(self._h, _f(x), R, Tp, None if nf is None else _i(nf), H, None if so is None else _i(so), _l(ids),
+                                          _i(lens), _i(ts), _i(en), _f(yp), _f(tot), _f(best), mt))
+        return self._ctc_align_result(lens, ts, en, yp, tot, best)
+
+    def ctc_align_samples(self, samples: Sequence[np.ndarray], targets, stream_of=None, max_tokens: Optional[int] = None):
+        """k2hip_offline_ctc_align_from_samples: samples -> fbank -> pad -> encoder on the device, then ctc_align() over all T' frames of
+        the padded batch (the frames the CTC search decodes)"""
+        ss = [_f32(s).reshape(-1) for s in samples]
+        B = len(ss)
+        H, so, ids, lens, mt, ts, en, yp, tot, best = self._ctc_align_buffers("ctc_align_samples", targets, B, stream_of, max_tokens)
+        ptrs = (fp * B)(*[_f(s) for s in ss])
+        ns = np.array([s.size for s in ss], np.int64)
+        tp = C.c_int32(0)
+        self._L.k2hip_offline_ctc_align_from_samples.argtypes = [C.c_void_p, C.POINTER(fp), lp, C.c_int32, C.c_int32, ip, lp, ip, ip, ip, fp, fp,
+                                                                 fp, C.c_int32, ip]
+        self._chk(self._L.k2hip_offline_ctc_align_from_samples(self._h, ptrs, _l(ns), B, H, None if so is None else _i(so), _l(ids), _i(lens),
+                                                               _i(ts), _i(en), _f(yp), _f(tot), _f(best), mt, C.byref(tp)))
+        return self._ctc_align_result(lens, ts, en, yp, tot, best)
+
     # ---- device-resident benchmark path
     def device_alloc(self, nbytes: int) -> int:
         p = C.c_void_p()
@@ -853,7 +901,10 @@ class OfflineRecognizer:
         return stream.tokens, stream.timestamps
 
     def align(self, samples: Sequence[np.ndarray], targets):
-        """forced alignment and full-sum score of targets[b] (token ids) on samples[b] (Model.align_samples; no reference counterpart)"""
+        """forced alignment and full-sum score of targets[b] (token ids) on samples[b] (Model.align_samples, or Model.ctc_align_samples
+        when the model is a CTC model; no reference counterpart)"""
+        if self.model.meta("model_type") == "zipformer2ctc":
+            return self.model.ctc_align_samples(samples, targets)
         return self.model.align_samples(samples, targets)
 
 

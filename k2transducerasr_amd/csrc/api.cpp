@@ -930,6 +930,34 @@ int32_t k2hip_offline_align_from_samples(k2hip_model_t* model, const float* cons
         e.align_samples(samples, n_samples, B, ids, lens, timestamps, token_log_probs, total_logp, best_logp, max_tokens, Tprime_out);
     });
 }
+// CTC forced alignment / full-sum scoring: the engine checks the targets on the host before any device work (ctc_lattice_ref.h)
+int32_t k2hip_ctc_align(k2hip_model_t* model, const float* log_probs, int32_t R, int32_t Tprime, const int32_t* n_frames, int32_t H,
+                        const int32_t* stream_of, const int64_t* ids, const int32_t* lens, int32_t* timestamps, int32_t* end_frames,
+                        float* token_log_probs, float* total_logp, float* best_logp, int32_t max_tokens) {
+    return guard([&] {
+        NEED(model); NEED(log_probs); NEED(lens);
+        K2_REQUIRE(R > 0 && Tprime > 0 && H > 0 && max_tokens >= 0, "ctc_align: bad shape R=%d T'=%d H=%d max_tokens=%d", R, Tprime, H, max_tokens);
+        Engine& e = model->engine;
+        if (!e.model().cfg().ctc) failf(K2HIP_ERR_UNSUPPORTED, "ctc_align: model_type '%s' has no CTC head", e.model().cfg().model_type.c_str());
+        EngineLock lk(e);
+        e.ctc_align_host(log_probs, R, Tprime, n_frames, H, stream_of, ids, lens, timestamps, end_frames, token_log_probs, total_logp, best_logp,
+                         max_tokens);
+    });
+}
+int32_t k2hip_offline_ctc_align_from_samples(k2hip_model_t* model, const float* const* samples, const int64_t* n_samples, int32_t B, int32_t H,
+                                             const int32_t* stream_of, const int64_t* ids, const int32_t* lens, int32_t* timestamps,
+                                             int32_t* end_frames, float* token_log_probs, float* total_logp, float* best_logp,
+                                             int32_t max_tokens, int32_t* Tprime_out) {
+    return guard([&] {
+        NEED(model); NEED(samples); NEED(n_samples); NEED(lens);
+        K2_REQUIRE(B > 0 && H > 0 && max_tokens >= 0, "ctc_align_from_samples: bad shape B=%d H=%d max_tokens=%d", B, H, max_tokens);
+        Engine& e = model->engine;
+        if (!e.model().cfg().ctc) failf(K2HIP_ERR_UNSUPPORTED, "ctc_align: model_type '%s' has no CTC head", e.model().cfg().model_type.c_str());
+        EngineLock lk(e);
+        e.ctc_align_samples(samples, n_samples, B, H, stream_of, ids, lens, timestamps, end_frames, token_log_probs, total_logp, best_logp,
+                            max_tokens, Tprime_out);
+    });
+}
 int32_t k2hip_offline_greedy(k2hip_model_t* model, const float* const* feats, const int64_t* n_floats, int32_t B,
                              int64_t* tokens, int32_t* timestamps, int32_t* n_tokens, int32_t max_tokens) {
     return guard([&] {

@@ -3,6 +3,7 @@
 
 #include "engine.h"
 #include "lattice_ref.h"
+#include "ctc_lattice_ref.h"
 
 #include <climits>
 #include <cmath>
@@ -642,6 +643,7 @@ const float* Engine::decoder_start(const Ctx& c) {
 // ---------------------------------------------------------------------------
 Engine::SearchExtras Engine::greedy_device(const Ctx& c, const float* enc, int B, int Tp, bool single, const SearchOut& out, bool keep_nbest) {
     if (align_plan_) return align_device(c, enc, Tp, *align_plan_, out);
+    if (ctc_align_plan_) return ctc_align_device(c, enc, B, Tp, *ctc_align_plan_, out);
     if (model_->cfg().ctc) return ctc_device(c, enc, B, Tp, out);
     if (beam_ > 0 && !single) return beam_device(c, enc, B, Tp, out, keep_nbest);
     const Config& cf = model_->cfg();
@@ -864,6 +866,7 @@ void Engine::finish_tokens(const SearchOut& out, const SearchExtras& ex, int64_t
         fetch(last_align_lp_, ex.align_lp, (size_t)B * max_tokens);
         fetch(last_align_scores_, ex.align_scores, (size_t)B * 2);
     }
+    if (ex.align_end) fetch(last_align_end_, ex.align_end, (size_t)B * max_tokens);
     NbestHost& h = last_nbest_;
     h.B = 0;
     if (ex.nb.tokens) {
@@ -1280,6 +1283,130 @@ void Engine::align_samples(const float* const* samples, const int64_t* n_samples
 }
 
 // ---------------------------------------------------------------------------
+// CTC forced alignment and full-sum scoring (ctc_align.hip)
+// ---------------------------------------------------------------------------
+static_assert(kCtcAlignMaxTokens == kCtcAlignMaxU, "the kernel's and the host reference's target limit are one number");
+
+Engine::CtcAlignPlan Engine::ctc_align_plan(int R, int Tp, const int32_t* n_frames, int H, const int32_t* stream_of, const int64_t* ids,
+                                            const int32_t* lens, int max_tokens) const {
+    const Config& cf = model_->cfg();
+    if (!cf.ctc) failf(K2HIP_ERR_UNSUPPORTED, "ctc_align: model_type '%s' has no CTC head", cf.model_type.c_str());
+    ctc_check_targets(cf.V, R, Tp, n_frames, H, stream_of, ids, lens);
+    K2_REQUIRE(H <= 65535, "ctc_align: %d targets in one call (at most 65535)", H);
+    CtcAlignPlan p;
+    p.R = R; p.Tp = Tp; p.H = H;
+    for (int h = 0; h < H; h++) {
+        if (lens[h] > max_tokens) failf(K2HIP_ERR_CAPACITY, "ctc_align: target %d has %d tokens, max_tokens is %d", h, lens[h], max_tokens);
+        K2_REQUIRE(lens[h] <= kCtcAlignMaxU, "ctc_align: target %d has %d tokens (at most %d)", h, lens[h], kCtcAlignMaxU);
+        p.n_ids += lens[h];
+    }
+    p.o_ids = align_up((int64_t)sizeof(CtcAlignTarget) * H, 16);
+    p.blob.assign((size_t)(p.o_ids + (int64_t)sizeof(int) * std::max(p.n_ids, 1)), 0);
+    CtcAlignTarget* tg = reinterpret_cast<CtcAlignTarget*>(p.blob.data());
+    int* h_ids = reinterpret_cast<int*>(p.blob.data() + p.o_ids);
+    int io = 0;
+    for (int h = 0; h < H; h++) {
+        const int r = stream_of ? stream_of[h] : h, T = n_frames ? n_frames[r] : Tp, U = lens[h];
+        tg[h] = CtcAlignTarget{p.plane_floats, p.bp_words, r, io, U, T};
+        p.plane_floats += (long long)T * (U + 1);
+        p.bp_words += (long long)T * ((2 * U + 1 + 63) / 64) * 2;
+        p.max_T = std::max(p.max_T, T);
+        p.max_U = std::max(p.max_U, U);
+        for (int u = 0; u < U; u++) h_ids[io + u] = (int)ids[io + u];
+        io += U;
+    }
+    return p;
+}
+
+Engine::SearchExtras Engine::ctc_align_device(const Ctx& c, const float* logp, int R, int Tp, const CtcAlignPlan& p, const SearchOut& out) {
+    K2_REQUIRE(Tp == p.Tp && R == p.R && out.B == p.H, "internal: the CTC align plan was laid out for T'=%d R=%d H=%d, the encoder gave T'=%d R=%d H=%d",
+               p.Tp, p.R, p.H, Tp, R, out.B);
+    Arena& ar = *c.arena;
+    char* d_blob = ar.take<char>((int64_t)p.blob.size());
+    CtcAlignArgs a;
+    a.log_probs = logp; a.Tp = Tp; a.V = model_->cfg().V; a.H = p.H; a.max_T = p.max_T; a.max_U = p.max_U;
+    a.targets = reinterpret_cast<const CtcAlignTarget*>(d_blob);
+    a.ids = reinterpret_cast<const int*>(d_blob + p.o_ids);
+    a.plane = ar.take<float>(p.plane_floats);
+    a.bp = ar.take<unsigned long long>(p.bp_words);
+    SearchExtras ex;
+    ex.align_lp = ar.take<float>((int64_t)p.H * out.max_tokens);
+    ex.align_end = ar.take<int>((int64_t)p.H * out.max_tokens);
+    ex.align_scores = ar.take<float>((int64_t)p.H * 2);
+    a.tokens = out.tokens(); a.timestamps = out.timestamps(); a.n_tokens = out.counts(); a.max_tokens = out.max_tokens;
+    a.end_frames = ex.align_end; a.token_log_probs = ex.align_lp; a.scores = ex.align_scores;
+    if (!c.dry) {
+        K2_HIP(hipMemcpyAsync(d_blob, p.blob.data(), p.blob.size(), hipMemcpyHostToDevice, c.stream));
+        K2_HIP(hipMemsetAsync(out.flag(), 0, sizeof(int), c.stream));
+    }
+    ctc_lattice(c, a);
+    return ex;
+}
+
+void Engine::ctc_align_copy_out(const CtcAlignPlan& p, const int32_t* ts_all, int max_tokens, int32_t* timestamps, int32_t* end_frames,
+                                float* token_log_probs, float* total, float* best) const {
+    const CtcAlignTarget* tg = p.targets();
+    for (int h = 0; h < p.H; h++) {
+        const size_t o = (size_t)h * max_tokens, n = (size_t)tg[h].U;
+        if (timestamps && n) memcpy(timestamps + o, ts_all + o, sizeof(int32_t) * n);
+        if (end_frames && n) memcpy(end_frames + o, last_align_end_.data() + o, sizeof(int32_t) * n);
+        if (token_log_probs && n) memcpy(token_log_probs + o, last_align_lp_.data() + o, sizeof(float) * n);
+        if (total) total[h] = last_align_scores_[2 * (size_t)h];
+        if (best) best[h] = last_align_scores_[2 * (size_t)h + 1];
+    }
+}
+
+void Engine::ctc_align_host(const float* log_probs, int R, int Tp, const int32_t* n_frames, int H, const int32_t* stream_of, const int64_t* ids,
+                            const int32_t* lens, int32_t* timestamps, int32_t* end_frames, float* token_log_probs, float* total, float* best,
+                            int max_tokens) {
+    K2_REQUIRE(log_probs != nullptr && max_tokens >= 0, "ctc_align: bad arguments");
+    const CtcAlignPlan p = ctc_align_plan(R, Tp, n_frames, H, stream_of, ids, lens, max_tokens);
+    const Config& cf = model_->cfg();
+    const int mt = std::max(max_tokens, 1);
+    SearchOut out;
+    SearchExtras ex;
+    run_sized([&](const Ctx& c) {
+        float* d_lp = c.arena->take<float>((int64_t)R * Tp * cf.V);
+        out = SearchOut(*c.arena, H, mt);
+        if (!c.dry) K2_HIP(hipMemcpyAsync(d_lp, log_probs, sizeof(float) * (size_t)R * Tp * cf.V, hipMemcpyHostToDevice, c.stream));
+        ex = ctc_align_device(c, d_lp, R, Tp, p, out);
+    });
+    std::vector<int64_t> tok((size_t)H * mt);
+    std::vector<int32_t> ts((size_t)H * mt), n((size_t)H);
+    finish_tokens(out, ex, tok.data(), ts.data(), n.data());
+    ctc_align_copy_out(p, ts.data(), mt, timestamps, end_frames, token_log_probs, total, best);
+}
+
+void Engine::ctc_align_samples(const float* const* samples, const int64_t* n_samples, int B, int H, const int32_t* stream_of, const int64_t* ids,
+                               const int32_t* lens, int32_t* timestamps, int32_t* end_frames, float* token_log_probs, float* total, float* best,
+                               int max_tokens, int32_t* Tp_out) {
+    K2_REQUIRE(samples != nullptr && n_samples != nullptr && B > 0 && max_tokens >= 0, "ctc_align_from_samples: bad arguments");
+    const Config& cf = model_->cfg();
+    if (!cf.ctc) failf(K2HIP_ERR_UNSUPPORTED, "ctc_align: model_type '%s' has no CTC head", cf.model_type.c_str());
+    // T' of the padded batch, as offline_greedy_samples derives it: every target is aligned over all of it, the frames the search decodes
+    int64_t nmax = 0;
+    for (int b = 0; b < B; b++) {
+        K2_REQUIRE(samples[b] != nullptr && fbank_num_frames(n_samples[b]) > 0, "stream %d: %lld samples give no frame", b, (long long)n_samples[b]);
+        nmax = std::max(nmax, n_samples[b]);
+    }
+    const int T = (int)((fbank_num_frames(nmax) * cf.feat + 80 * kTailFrames) / cf.feat);
+    const int Tp = encoder_out_frames(T);
+    K2_REQUIRE(Tp > 0, "ctc_align_from_samples: %lld samples give no encoder frame", (long long)nmax);
+    const CtcAlignPlan p = ctc_align_plan(B, Tp, nullptr, H, stream_of, ids, lens, max_tokens);
+    const int mt = std::max(max_tokens, 1);
+    std::vector<int64_t> tok((size_t)H * mt);
+    std::vector<int32_t> ts((size_t)H * mt), n((size_t)H);
+    struct Scope {
+        const CtcAlignPlan*& slot;
+        ~Scope() { slot = nullptr; }
+    } scope{ctc_align_plan_};
+    ctc_align_plan_ = &p;
+    offline_greedy_samples(samples, n_samples, B, tok.data(), ts.data(), n.data(), mt);
+    ctc_align_copy_out(p, ts.data(), mt, timestamps, end_frames, token_log_probs, total, best);
+    if (Tp_out) *Tp_out = Tp;
+}
+
+// ---------------------------------------------------------------------------
 // fused paths
 // ---------------------------------------------------------------------------
 void Engine::offline_greedy_feats(const float* const* feats, const int64_t* n_floats, int B, bool single, int64_t* tokens,
@@ -1384,6 +1511,8 @@ void Engine::offline_greedy_samples(const float* const* samples, const int64_t* 
     }
     const int64_t nfmax = fbank_num_frames(nmax), n_fl = nfmax * cf.feat, L = n_fl + 80 * kTailFrames;
     const int T = (int)(L / cf.feat);  // OfflineProjOfTransducer.cs:59 over PadHelper.cs:17,22
+    // rows of the search-output block: one per stream, or one per target while a CTC align call (several targets may share a stream) runs here
+    const int rows = ctc_align_plan_ ? ctc_align_plan_->H : B;
     // rows of the dense sample block are `ns` floats apart: nmax rounded up to 4, so that every row starts on 16 bytes for any lengths (the
     // gather moves float4; a row that did not would take its scalar path -- four 4-byte reads per lane over PCIe)
     const int64_t ns = (nmax + 3) & ~(int64_t)3;
@@ -1391,7 +1520,7 @@ void Engine::offline_greedy_samples(const float* const* samples, const int64_t* 
     // the host block: [samples (not with pinned_src)] | feature offsets | feature lengths | [sample pointers | sample counts]
     const int64_t hb_s = pinned_src ? 0 : nb_s, hb_in = hb_s + 32 * (int64_t)B;
     // (sized for the token download as well: finish_tokens takes the same buffer and must not re-allocate it under the upload)
-    char* pin = static_cast<char*>(pinned(std::max<int64_t>(hb_in, SearchOut::bytes_for(B, max_tokens)) + 64));
+    char* pin = static_cast<char*>(pinned(std::max<int64_t>(hb_in, SearchOut::bytes_for(rows, max_tokens)) + 64));
     long long* h_off = reinterpret_cast<long long*>(pin + hb_s);
     long long* h_len = h_off + B;
     const float** h_ptr = reinterpret_cast<const float**>(h_len + B);
@@ -1432,7 +1561,7 @@ void Engine::offline_greedy_samples(const float* const* samples, const int64_t* 
     SearchExtras ex;
     run_sized([&](const Ctx& c) {
         Arena& ar = *c.arena;
-        out = SearchOut(ar, B, max_tokens);
+        out = SearchOut(ar, rows, max_tokens);
         char* d_in = ar.take<char>(nb_s + 32 * (int64_t)B);
         float* d_s = reinterpret_cast<float*>(d_in);
         long long* d_off = reinterpret_cast<long long*>(d_in + nb_s);
@@ -2094,6 +2223,37 @@ void Engine::debug_op_host(const char* op, const int64_t* iargs, int n_iargs, vo
                 K2_HIP(copy_blocking(dev[k_lp], ex.align_lp, 4 * (size_t)B * max_tokens, hipMemcpyDeviceToDevice));
                 K2_HIP(copy_blocking(dev[k_sc], ex.align_scores, 8 * (size_t)B, hipMemcpyDeviceToDevice));
             }
+        } else if (name == "ctc_lattice") {
+            // bufs log_probs [R][Tp][V], n_frames [R] int32 (or null), stream_of [H] int32 (or null), ids int64 back to back, lens [H] int32,
+            //   timestamps, end_frames [H][max_tokens] int32, token_log_probs [H][max_tokens], scores [H][2] = (total, best) (out);
+            //   ints R, Tp, H, max_tokens
+            K2_REQUIRE(n_bufs == 9, "debug_op_run %s: %d buffers", op, n_bufs);
+            for (int k = 0; k < n_bufs; k++) P();
+            const int R = I(), Tp = I(), H = I(), max_tokens = I();
+            K2_REQUIRE(R > 0 && Tp > 0 && H > 0 && max_tokens > 0, "debug_op_run %s: bad shape", op);
+            K2_REQUIRE(bufs[4] && buf_bytes[4] >= 4 * (int64_t)H && (!bufs[1] || buf_bytes[1] >= 4 * (int64_t)R) && (!bufs[2] || buf_bytes[2] >= 4 * (int64_t)H),
+                       "debug_op_run %s: lens / n_frames / stream_of are too short", op);
+            const int32_t* lens = static_cast<const int32_t*>(bufs[4]);
+            int64_t n_ids = 0;
+            for (int h = 0; h < H; h++) n_ids += std::max(lens[h], 0);
+            K2_REQUIRE(n_ids == 0 || (bufs[3] && buf_bytes[3] >= 8 * n_ids), "debug_op_run %s: ids are too short", op);
+            const CtcAlignPlan p = ctc_align_plan(R, Tp, static_cast<const int32_t*>(bufs[1]), H, static_cast<const int32_t*>(bufs[2]),
+                                                  static_cast<const int64_t*>(bufs[3]), lens, max_tokens);
+            K2_REQUIRE(dev[0] && buf_bytes[0] >= 4 * (int64_t)R * Tp * model_->cfg().V, "debug_op_run %s: log_probs is too short", op);
+            K2_REQUIRE(dev[5] && dev[6] && dev[7] && dev[8] && buf_bytes[5] >= 4 * (int64_t)H * max_tokens && buf_bytes[6] >= 4 * (int64_t)H * max_tokens &&
+                           buf_bytes[7] >= 4 * (int64_t)H * max_tokens && buf_bytes[8] >= 8 * (int64_t)H,
+                       "debug_op_run %s: the result buffers are too short", op);
+            SearchOut out;
+            SearchExtras ex;
+            run_sized([&](const Ctx& cc) {
+                out = SearchOut(*cc.arena, H, max_tokens);
+                ex = ctc_align_device(cc, static_cast<const float*>(dev[0]), R, Tp, p, out);
+            });
+            K2_HIP(hipStreamSynchronize(stream_));
+            K2_HIP(copy_blocking(dev[5], out.timestamps(), 4 * (size_t)H * max_tokens, hipMemcpyDeviceToDevice));
+            K2_HIP(copy_blocking(dev[6], ex.align_end, 4 * (size_t)H * max_tokens, hipMemcpyDeviceToDevice));
+            K2_HIP(copy_blocking(dev[7], ex.align_lp, 4 * (size_t)H * max_tokens, hipMemcpyDeviceToDevice));
+            K2_HIP(copy_blocking(dev[8], ex.align_scores, 8 * (size_t)H, hipMemcpyDeviceToDevice));
         } else if (name == "basicnorm") {
             float *x = P(), *le = P(), *y = P();
             const int M = I(), D = I();

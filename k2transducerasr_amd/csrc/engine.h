@@ -82,6 +82,17 @@ class Engine {
     // fbank + pad + encoder as offline_greedy_samples, encoder_out left on the device, every stream aligned over all T' frames
     void align_samples(const float* const* samples, const int64_t* n_samples, int B, const int64_t* ids, const int32_t* lens, int32_t* timestamps,
                        float* token_log_probs, float* total, float* best, int max_tokens, int32_t* Tp_out);
+    // ---- CTC forced alignment and full-sum scoring (ctc_align.hip; semantics in include/k2hip.h) ----
+    // log_probs [R][Tp][V] on the host; n_frames [R] or null (= Tp); H targets back to back in ids, lens [H]; stream_of [H] names the row a
+    // target is scored against, or null (H == R, the identity).  Outputs (each may be null): timestamps / end_frames / token_log_probs
+    // [H][max_tokens], total / best [H].  The arguments are checked on the host before any device work (ctc_lattice_ref.h).
+    void ctc_align_host(const float* log_probs, int R, int Tp, const int32_t* n_frames, int H, const int32_t* stream_of, const int64_t* ids,
+                        const int32_t* lens, int32_t* timestamps, int32_t* end_frames, float* token_log_probs, float* total, float* best,
+                        int max_tokens);
+    // fbank + pad + encoder as offline_greedy_samples, log_probs left on the device, every target aligned over all T' frames
+    void ctc_align_samples(const float* const* samples, const int64_t* n_samples, int B, int H, const int32_t* stream_of, const int64_t* ids,
+                           const int32_t* lens, int32_t* timestamps, int32_t* end_frames, float* token_log_probs, float* total, float* best,
+                           int max_tokens, int32_t* Tp_out);
     // ---- fused paths ----
     void offline_greedy_feats(const float* const* feats, const int64_t* n_floats, int B, bool single, int64_t* tokens,
                               int32_t* ts, int32_t* n_tokens, int max_tokens);
@@ -227,6 +238,7 @@ class Engine {
         int *trail = nullptr, *any = nullptr; // CTC: [B] each
         float* align_lp = nullptr;            // align: [B][max_tokens] token log-probs of the best path
         float* align_scores = nullptr;        // align: [B][2] = (total, best)
+        int* align_end = nullptr;             // CTC align: [H][max_tokens] last frame of every token on the best path
     };
     // One align call as the host lays it out before any device work: the streams' descriptors, targets and contexts in ONE upload block
     struct AlignPlan {
@@ -245,6 +257,24 @@ class Engine {
     std::vector<float> last_align_lp_, last_align_scores_;
     void align_copy_out(const AlignPlan& p, const int32_t* ts_all, int max_tokens, int32_t* timestamps, float* token_log_probs, float* total,
                         float* best) const;
+    // One CTC align call as the host lays it out before any device work: the targets' descriptors and ids (stream_of resolved into
+    // CtcAlignTarget::row) in ONE upload block
+    struct CtcAlignPlan {
+        int R = 0, Tp = 0, H = 0, max_T = 0, max_U = 0, n_ids = 0;
+        long long plane_floats = 0, bp_words = 0;
+        int64_t o_ids = 0;                // byte offset of the targets (int) behind the descriptors
+        std::vector<char> blob;
+        const CtcAlignTarget* targets() const { return reinterpret_cast<const CtcAlignTarget*>(blob.data()); }
+    };
+    CtcAlignPlan ctc_align_plan(int R, int Tp, const int32_t* n_frames, int H, const int32_t* stream_of, const int64_t* ids, const int32_t* lens,
+                                int max_tokens) const;
+    // gather + lattice into `out` (H rows: tokens = the targets, counts = their lengths, timestamps); end frames, token log-probs and
+    // (total, best) are SearchExtras
+    SearchExtras ctc_align_device(const Ctx& c, const float* logp, int R, int Tp, const CtcAlignPlan& p, const SearchOut& out);
+    const CtcAlignPlan* ctc_align_plan_ = nullptr;   // while set (the span of ctc_align_samples), the fused entries' search is ctc_align_device
+    std::vector<int32_t> last_align_end_;
+    void ctc_align_copy_out(const CtcAlignPlan& p, const int32_t* ts_all, int max_tokens, int32_t* timestamps, int32_t* end_frames,
+                            float* token_log_probs, float* total, float* best) const;
     // keep_nbest: the caller fetches the beam search's N-best (the synchronous entries; the pipelined route has no place to keep them)
     SearchExtras greedy_device(const Ctx& c, const float* enc, int B, int Tp, bool single, const SearchOut& out, bool keep_nbest);
     // the fused offline entries' tail on c.stream: event 2, encoder, event 3, search, event 4

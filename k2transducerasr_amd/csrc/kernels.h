@@ -698,6 +698,36 @@ void lattice_logprobs(const Ctx& ctx, const DecJoinW& w, const AlignArgs& a);
 constexpr int kAlignMaxU = 4095;   // U + 1 positions of both recursions' two rows live in LDS
 void lattice_dp(const Ctx& ctx, const AlignArgs& a);
 
+// ---- CTC forced alignment and full-sum scoring (ctc_align.hip; semantics in include/k2hip.h and ctc_lattice_ref.h) ----
+// One target of a CTC align call: U tokens at ids[id_off ..], scored against row `row` of log_probs over its first T frames; its compact
+// plane [T][U + 1] (column 0: lp(t, blank), column k: lp(t, y_k)) at plane_off floats into `plane`, and its back-pointers
+// [T][ceil(S / 64)][2] 64-bit words (S = 2U + 1; the low and the high bit of every state's two-bit pointer) at bp_off words into bp.
+struct CtcAlignTarget {
+    long long plane_off, bp_off;
+    int row, id_off, U, T;
+};
+struct CtcAlignArgs {
+    const float* log_probs = nullptr;    // [R, Tp, V], log-softmaxed
+    int Tp = 0, V = 0, H = 0;
+    int max_T = 0, max_U = 0;            // over the call's targets (the launch grid, the LDS rows)
+    const CtcAlignTarget* targets = nullptr;   // [H] (device)
+    const int* ids = nullptr;            // the targets back to back (device)
+    float* plane = nullptr;
+    unsigned long long* bp = nullptr;
+    // results: tokens / timestamps / end_frames / token_log_probs [H][max_tokens] (tokens: the targets back, may be null), n_tokens [H]
+    // (= U, may be null), scores [H][2] = (total, best)
+    long long* tokens = nullptr;
+    int *timestamps = nullptr, *end_frames = nullptr;
+    float* token_log_probs = nullptr;
+    int* n_tokens = nullptr;
+    float* scores = nullptr;
+    int max_tokens = 0;
+};
+constexpr int kCtcAlignMaxTokens = 4095;   // = kCtcAlignMaxU of ctc_lattice_ref.h: four rows of 2U + 1 floats live in LDS (131 KB)
+// gather pass (the U + 1 columns every target needs, out of [Tp][V] into its compact plane), then one workgroup per target: forward
+// (logaddexp) and Viterbi (max, the lowest state index wins ties) over the reachable band, two back-pointer bits per cell, backtrace
+void ctc_lattice(const Ctx& ctx, const CtcAlignArgs& a);
+
 // ---- streaming (online.hip): device-resident per-stream caches indexed by slot ------------------
 // ConvNeXt.streaming_forward's data movement in one launch: cat[b] = [cached_left_pad ; x], the cache advanced to x's frames Tc-3 .. Tc-1,
 // byp[b] = x[b, :Tc] (the bypass operand)
