@@ -641,9 +641,13 @@ const float* Engine::decoder_start(const Ctx& c) {
 // ---------------------------------------------------------------------------
 // greedy search on device
 // ---------------------------------------------------------------------------
+Engine::SearchExtras Engine::search_device(const Ctx& c, const float* enc, int B, int Tp, const SearchStage& stage, const SearchOut& out) {
+    if (stage.align) return align_device(c, enc, Tp, *stage.align, out);
+    if (stage.ctc_align) return ctc_align_device(c, enc, B, Tp, *stage.ctc_align, out);
+    return greedy_device(c, enc, B, Tp, stage.single, out, stage.keep_nbest);
+}
+
 Engine::SearchExtras Engine::greedy_device(const Ctx& c, const float* enc, int B, int Tp, bool single, const SearchOut& out, bool keep_nbest) {
-    if (align_plan_) return align_device(c, enc, Tp, *align_plan_, out);
-    if (ctc_align_plan_) return ctc_align_device(c, enc, B, Tp, *ctc_align_plan_, out);
     if (model_->cfg().ctc) return ctc_device(c, enc, B, Tp, out);
     if (beam_ > 0 && !single) return beam_device(c, enc, B, Tp, out, keep_nbest);
     const Config& cf = model_->cfg();
@@ -885,12 +889,12 @@ void Engine::finish_tokens(const SearchOut& out, const SearchExtras& ex, int64_t
     }
 }
 
-Engine::SearchExtras Engine::encode_and_search(const Ctx& c, const float* d_x, int B, int T, bool single, const SearchOut& out) {
+Engine::SearchExtras Engine::encode_and_search(const Ctx& c, const float* d_x, int B, int T, const SearchStage& stage, const SearchOut& out) {
     if (!c.dry) K2_HIP(hipEventRecord(ev_[2], c.stream));
     int Tp = 0;
     float* enc = encoder_forward(c, d_x, B, T, &Tp, -1, nullptr, nullptr, nullptr);
     if (!c.dry) K2_HIP(hipEventRecord(ev_[3], c.stream));
-    SearchExtras ex = greedy_device(c, enc, B, Tp, single, out, true);
+    SearchExtras ex = search_device(c, enc, B, Tp, stage, out);
     if (!c.dry) K2_HIP(hipEventRecord(ev_[4], c.stream));
     return ex;
 }
@@ -908,6 +912,13 @@ void Engine::fill_timing(bool fbank_leg, bool pad_leg) {
 // ---------------------------------------------------------------------------
 // operator-level entry points
 // ---------------------------------------------------------------------------
+FbankArgs Engine::fbank_args(const float* src, int64_t n, int64_t stride, int n_utts, int64_t nf, float* dst) const {
+    const FbankOpts& f = model_->cfg().fbank;
+    FbankArgs a{src, n, stride, n_utts, nf, dst, model_->d_window, model_->d_melw, f.frame_len, f.frame_shift, f.preemph, f.input_scale, f.remove_dc};
+    a.melrange = model_->d_melrange;
+    return a;
+}
+
 void Engine::fbank_host(const float* samples, int64_t n, float* feats, int64_t cap_frames, int64_t* n_frames) {
     const FbankOpts& f = model_->cfg().fbank;
     int64_t nf = fbank_num_frames(n);
@@ -919,9 +930,7 @@ void Engine::fbank_host(const float* samples, int64_t n, float* feats, int64_t c
         float* d_s = c.arena->take<float>(n);
         d_out = c.arena->take<float>(nf * f.num_bins);
         if (!c.dry) K2_HIP(hipMemcpyAsync(d_s, samples, sizeof(float) * n, hipMemcpyHostToDevice, c.stream));
-        FbankArgs a{d_s, n, n, 1, nf, d_out, model_->d_window, model_->d_melw, f.frame_len, f.frame_shift, f.preemph, f.input_scale, f.remove_dc};
-        a.melrange = model_->d_melrange;
-        fbank(c, a);
+        fbank(c, fbank_args(d_s, n, n, 1, nf, d_out));
     });
     K2_HIP(hipMemcpyAsync(feats, d_out, sizeof(float) * nf * f.num_bins, hipMemcpyDeviceToHost, stream_));
     K2_HIP(hipStreamSynchronize(stream_));
@@ -940,9 +949,7 @@ void Engine::fbank_host_batch(const float* samples, int64_t n, int n_utts, float
         float* d_s = c.arena->take<float>(n * n_utts);
         d_out = c.arena->take<float>(nf * f.num_bins * n_utts);
         if (!c.dry) K2_HIP(hipMemcpyAsync(d_s, pin, nb_in, hipMemcpyHostToDevice, c.stream));
-        FbankArgs a{d_s, n, n, n_utts, nf, d_out, model_->d_window, model_->d_melw, f.frame_len, f.frame_shift, f.preemph, f.input_scale, f.remove_dc};
-        a.melrange = model_->d_melrange;
-        fbank(c, a);
+        fbank(c, fbank_args(d_s, n, n, n_utts, nf, d_out));
     });
     K2_HIP(hipMemcpyAsync(pin + nb_in, d_out, nb_out, hipMemcpyDeviceToHost, stream_));
     K2_HIP(hipStreamSynchronize(stream_));
@@ -975,9 +982,7 @@ void Engine::fbank_host_gather(const float* const* head, const int64_t* n_head, 
         float* d_s = c.arena->take<float>(n * G);
         d_out = c.arena->take<float>(nf * f.num_bins * G);
         if (!c.dry) K2_HIP(hipMemcpyAsync(d_s, pin, nb_in, hipMemcpyHostToDevice, c.stream));
-        FbankArgs a{d_s, n, n, G, nf, d_out, model_->d_window, model_->d_melw, f.frame_len, f.frame_shift, f.preemph, f.input_scale, f.remove_dc};
-        a.melrange = model_->d_melrange;
-        fbank(c, a);
+        fbank(c, fbank_args(d_s, n, n, G, nf, d_out));
         if (mirror) {  // the same frames into the streams' device FIFOs: the chunk step then needs no host copy of them
             int* d_idx = c.arena->take<int>(2 * G);
             if (!c.dry) K2_HIP(hipMemcpyAsync(d_idx, h_idx, nb_idx, hipMemcpyHostToDevice, c.stream));
@@ -1128,14 +1133,19 @@ void Engine::greedy_host(const float* enc_out, int B, int Tp, bool single, int64
                          int max_tokens) {
     K2_REQUIRE(B > 0 && Tp > 0 && max_tokens > 0, "greedy: bad shape B=%d T'=%d max_tokens=%d", B, Tp, max_tokens);
     K2_REQUIRE(!single || B == 1, "greedy_single: B must be 1");
-    const Config& cf = model_->cfg();
+    search_host(enc_out, B, Tp, SearchStage{single}, tokens, ts, n_tokens, max_tokens);
+}
+
+void Engine::search_host(const float* enc_out, int B, int Tp, const SearchStage& stage, int64_t* tokens, int32_t* ts, int32_t* n_tokens,
+                         int max_tokens) {
+    const int64_t n = (int64_t)B * Tp * model_->cfg().enc_dim();
     SearchOut out;
     SearchExtras ex;
     run_sized([&](const Ctx& c) {
-        float* d_e = c.arena->take<float>((int64_t)B * Tp * cf.enc_dim());
-        out = SearchOut(*c.arena, B, max_tokens);
-        if (!c.dry) K2_HIP(hipMemcpyAsync(d_e, enc_out, sizeof(float) * (size_t)B * Tp * cf.enc_dim(), hipMemcpyHostToDevice, c.stream));
-        ex = greedy_device(c, d_e, B, Tp, single, out, true);
+        float* d_e = c.arena->take<float>(n);
+        out = SearchOut(*c.arena, stage.rows(B), max_tokens);
+        if (!c.dry) K2_HIP(hipMemcpyAsync(d_e, enc_out, sizeof(float) * (size_t)n, hipMemcpyHostToDevice, c.stream));
+        ex = search_device(c, d_e, B, Tp, stage, out);
     });
     finish_tokens(out, ex, tokens, ts, n_tokens);
 }
@@ -1222,15 +1232,15 @@ Engine::SearchExtras Engine::align_device(const Ctx& c, const float* enc, int Tp
     return ex;
 }
 
-void Engine::align_copy_out(const AlignPlan& p, const int32_t* ts_all, int max_tokens, int32_t* timestamps, float* token_log_probs, float* total,
-                            float* best) const {
-    const AlignStream* st = p.streams();
-    for (int b = 0; b < p.B; b++) {
-        const size_t o = (size_t)b * max_tokens, n = (size_t)st[b].U;
-        if (timestamps && n) memcpy(timestamps + o, ts_all + o, sizeof(int32_t) * n);
+void Engine::align_copy_out(int rows, const int32_t* lens, const AlignScratch& s, int32_t* timestamps, int32_t* end_frames, float* token_log_probs,
+                            float* total, float* best) const {
+    for (int r = 0; r < rows; r++) {
+        const size_t o = (size_t)r * s.mt, n = (size_t)lens[r];
+        if (timestamps && n) memcpy(timestamps + o, s.ts.data() + o, sizeof(int32_t) * n);
+        if (end_frames && n) memcpy(end_frames + o, last_align_end_.data() + o, sizeof(int32_t) * n);
         if (token_log_probs && n) memcpy(token_log_probs + o, last_align_lp_.data() + o, sizeof(float) * n);
-        if (total) total[b] = last_align_scores_[2 * (size_t)b];
-        if (best) best[b] = last_align_scores_[2 * (size_t)b + 1];
+        if (total) total[r] = last_align_scores_[2 * (size_t)r];
+        if (best) best[r] = last_align_scores_[2 * (size_t)r + 1];
     }
 }
 
@@ -1238,20 +1248,11 @@ void Engine::align_host(const float* enc_out, int B, int Tp, const int32_t* n_fr
                         float* token_log_probs, float* total, float* best, int max_tokens) {
     K2_REQUIRE(enc_out != nullptr && max_tokens >= 0, "align: bad arguments");
     const AlignPlan p = align_plan(B, Tp, n_frames, ids, lens, max_tokens);
-    const Config& cf = model_->cfg();
-    const int mt = std::max(max_tokens, 1);
-    SearchOut out;
-    SearchExtras ex;
-    run_sized([&](const Ctx& c) {
-        float* d_e = c.arena->take<float>((int64_t)B * Tp * cf.J);
-        out = SearchOut(*c.arena, B, mt);
-        if (!c.dry) K2_HIP(hipMemcpyAsync(d_e, enc_out, sizeof(float) * (size_t)B * Tp * cf.J, hipMemcpyHostToDevice, c.stream));
-        ex = align_device(c, d_e, Tp, p, out);
-    });
-    std::vector<int64_t> tok((size_t)B * mt);
-    std::vector<int32_t> ts((size_t)B * mt), n((size_t)B);
-    finish_tokens(out, ex, tok.data(), ts.data(), n.data());
-    align_copy_out(p, ts.data(), mt, timestamps, token_log_probs, total, best);
+    AlignScratch s(B, max_tokens);
+    SearchStage stage;
+    stage.align = &p;
+    search_host(enc_out, B, Tp, stage, s.tok.data(), s.ts.data(), s.n.data(), s.mt);
+    align_copy_out(B, lens, s, timestamps, nullptr, token_log_probs, total, best);
 }
 
 void Engine::align_samples(const float* const* samples, const int64_t* n_samples, int B, const int64_t* ids, const int32_t* lens,
@@ -1259,26 +1260,16 @@ void Engine::align_samples(const float* const* samples, const int64_t* n_samples
     K2_REQUIRE(samples != nullptr && n_samples != nullptr && B > 0 && max_tokens >= 0, "align_from_samples: bad arguments");
     const Config& cf = model_->cfg();
     if (cf.ctc) failf(K2HIP_ERR_UNSUPPORTED, "align: a CTC model has no transducer lattice");
-    // T' of the padded batch, as offline_greedy_samples derives it: every stream is aligned over all of it, the frames the searches decode
-    int64_t nmax = 0;
-    for (int b = 0; b < B; b++) {
-        K2_REQUIRE(samples[b] != nullptr && fbank_num_frames(n_samples[b]) > 0, "stream %d: %lld samples give no frame", b, (long long)n_samples[b]);
-        nmax = std::max(nmax, n_samples[b]);
-    }
-    const int T = (int)((fbank_num_frames(nmax) * cf.feat + 80 * kTailFrames) / cf.feat);
-    const int Tp = encoder_out_frames(T);
-    K2_REQUIRE(Tp > 0, "align_from_samples: %lld samples give no encoder frame", (long long)nmax);
+    // T' of the padded batch: every stream is aligned over all of it, the frames the searches decode
+    const OfflineShape sh = samples_shape(samples, n_samples, B);
+    const int Tp = sh.Tp;
+    K2_REQUIRE(Tp > 0, "align_from_samples: %lld samples give no encoder frame", (long long)sh.longest);
     const AlignPlan p = align_plan(B, Tp, nullptr, ids, lens, max_tokens);
-    const int mt = std::max(max_tokens, 1);
-    std::vector<int64_t> tok((size_t)B * mt);
-    std::vector<int32_t> ts((size_t)B * mt), n((size_t)B);
-    struct Scope {
-        const AlignPlan*& slot;
-        ~Scope() { slot = nullptr; }
-    } scope{align_plan_};
-    align_plan_ = &p;
-    offline_greedy_samples(samples, n_samples, B, tok.data(), ts.data(), n.data(), mt);
-    align_copy_out(p, ts.data(), mt, timestamps, token_log_probs, total, best);
+    AlignScratch s(B, max_tokens);
+    SearchStage stage;
+    stage.align = &p;
+    offline_samples(samples, n_samples, B, stage, s.tok.data(), s.ts.data(), s.n.data(), s.mt, false);
+    align_copy_out(B, lens, s, timestamps, nullptr, token_log_probs, total, best);
     if (Tp_out) *Tp_out = Tp;
 }
 
@@ -1343,38 +1334,16 @@ Engine::SearchExtras Engine::ctc_align_device(const Ctx& c, const float* logp, i
     return ex;
 }
 
-void Engine::ctc_align_copy_out(const CtcAlignPlan& p, const int32_t* ts_all, int max_tokens, int32_t* timestamps, int32_t* end_frames,
-                                float* token_log_probs, float* total, float* best) const {
-    const CtcAlignTarget* tg = p.targets();
-    for (int h = 0; h < p.H; h++) {
-        const size_t o = (size_t)h * max_tokens, n = (size_t)tg[h].U;
-        if (timestamps && n) memcpy(timestamps + o, ts_all + o, sizeof(int32_t) * n);
-        if (end_frames && n) memcpy(end_frames + o, last_align_end_.data() + o, sizeof(int32_t) * n);
-        if (token_log_probs && n) memcpy(token_log_probs + o, last_align_lp_.data() + o, sizeof(float) * n);
-        if (total) total[h] = last_align_scores_[2 * (size_t)h];
-        if (best) best[h] = last_align_scores_[2 * (size_t)h + 1];
-    }
-}
-
 void Engine::ctc_align_host(const float* log_probs, int R, int Tp, const int32_t* n_frames, int H, const int32_t* stream_of, const int64_t* ids,
                             const int32_t* lens, int32_t* timestamps, int32_t* end_frames, float* token_log_probs, float* total, float* best,
                             int max_tokens) {
     K2_REQUIRE(log_probs != nullptr && max_tokens >= 0, "ctc_align: bad arguments");
     const CtcAlignPlan p = ctc_align_plan(R, Tp, n_frames, H, stream_of, ids, lens, max_tokens);
-    const Config& cf = model_->cfg();
-    const int mt = std::max(max_tokens, 1);
-    SearchOut out;
-    SearchExtras ex;
-    run_sized([&](const Ctx& c) {
-        float* d_lp = c.arena->take<float>((int64_t)R * Tp * cf.V);
-        out = SearchOut(*c.arena, H, mt);
-        if (!c.dry) K2_HIP(hipMemcpyAsync(d_lp, log_probs, sizeof(float) * (size_t)R * Tp * cf.V, hipMemcpyHostToDevice, c.stream));
-        ex = ctc_align_device(c, d_lp, R, Tp, p, out);
-    });
-    std::vector<int64_t> tok((size_t)H * mt);
-    std::vector<int32_t> ts((size_t)H * mt), n((size_t)H);
-    finish_tokens(out, ex, tok.data(), ts.data(), n.data());
-    ctc_align_copy_out(p, ts.data(), mt, timestamps, end_frames, token_log_probs, total, best);
+    AlignScratch s(H, max_tokens);
+    SearchStage stage;
+    stage.ctc_align = &p;
+    search_host(log_probs, R, Tp, stage, s.tok.data(), s.ts.data(), s.n.data(), s.mt);
+    align_copy_out(H, lens, s, timestamps, end_frames, token_log_probs, total, best);
 }
 
 void Engine::ctc_align_samples(const float* const* samples, const int64_t* n_samples, int B, int H, const int32_t* stream_of, const int64_t* ids,
@@ -1383,47 +1352,57 @@ void Engine::ctc_align_samples(const float* const* samples, const int64_t* n_sam
     K2_REQUIRE(samples != nullptr && n_samples != nullptr && B > 0 && max_tokens >= 0, "ctc_align_from_samples: bad arguments");
     const Config& cf = model_->cfg();
     if (!cf.ctc) failf(K2HIP_ERR_UNSUPPORTED, "ctc_align: model_type '%s' has no CTC head", cf.model_type.c_str());
-    // T' of the padded batch, as offline_greedy_samples derives it: every target is aligned over all of it, the frames the search decodes
-    int64_t nmax = 0;
-    for (int b = 0; b < B; b++) {
-        K2_REQUIRE(samples[b] != nullptr && fbank_num_frames(n_samples[b]) > 0, "stream %d: %lld samples give no frame", b, (long long)n_samples[b]);
-        nmax = std::max(nmax, n_samples[b]);
-    }
-    const int T = (int)((fbank_num_frames(nmax) * cf.feat + 80 * kTailFrames) / cf.feat);
-    const int Tp = encoder_out_frames(T);
-    K2_REQUIRE(Tp > 0, "ctc_align_from_samples: %lld samples give no encoder frame", (long long)nmax);
+    // T' of the padded batch: every target is aligned over all of it, the frames the search decodes
+    const OfflineShape sh = samples_shape(samples, n_samples, B);
+    const int Tp = sh.Tp;
+    K2_REQUIRE(Tp > 0, "ctc_align_from_samples: %lld samples give no encoder frame", (long long)sh.longest);
     const CtcAlignPlan p = ctc_align_plan(B, Tp, nullptr, H, stream_of, ids, lens, max_tokens);
-    const int mt = std::max(max_tokens, 1);
-    std::vector<int64_t> tok((size_t)H * mt);
-    std::vector<int32_t> ts((size_t)H * mt), n((size_t)H);
-    struct Scope {
-        const CtcAlignPlan*& slot;
-        ~Scope() { slot = nullptr; }
-    } scope{ctc_align_plan_};
-    ctc_align_plan_ = &p;
-    offline_greedy_samples(samples, n_samples, B, tok.data(), ts.data(), n.data(), mt);
-    ctc_align_copy_out(p, ts.data(), mt, timestamps, end_frames, token_log_probs, total, best);
+    AlignScratch s(H, max_tokens);
+    SearchStage stage;
+    stage.ctc_align = &p;
+    offline_samples(samples, n_samples, B, stage, s.tok.data(), s.ts.data(), s.n.data(), s.mt, false);
+    align_copy_out(H, lens, s, timestamps, end_frames, token_log_probs, total, best);
     if (Tp_out) *Tp_out = Tp;
 }
 
 // ---------------------------------------------------------------------------
 // fused paths
 // ---------------------------------------------------------------------------
+Engine::OfflineShape Engine::offline_shape(const char* who, int64_t longest, bool from_feats) const {
+    const Config& cf = model_->cfg();
+    K2_REQUIRE(cf.ctc || cf.J == 512, "offline loops hard-code a 512-wide encoder_out (OfflineRecognizer.cs:103,201); joiner_dim is %d", cf.J);
+    OfflineShape s;
+    s.longest = longest;
+    s.frames = from_feats ? longest / cf.feat : fbank_num_frames(longest);
+    K2_REQUIRE(from_feats || s.frames > 0, "%s: %lld samples give no frame", who, (long long)longest);
+    s.n_fl = from_feats ? longest : s.frames * cf.feat;
+    s.L = s.n_fl + 80 * kTailFrames;  // PadHelper.cs:17,22
+    s.T = (int)(s.L / cf.feat);       // OfflineProjOfTransducer.cs:59
+    s.Tp = encoder_out_frames(s.T);
+    return s;
+}
+
+Engine::OfflineShape Engine::samples_shape(const float* const* samples, const int64_t* n_samples, int B) const {
+    int64_t nmax = 0;
+    for (int b = 0; b < B; b++) {
+        K2_REQUIRE(samples[b] != nullptr && fbank_num_frames(n_samples[b]) > 0, "stream %d: %lld samples give no frame", b, (long long)n_samples[b]);
+        nmax = std::max(nmax, n_samples[b]);
+    }
+    return offline_shape("offline_greedy_from_samples", nmax);
+}
+
 void Engine::offline_greedy_feats(const float* const* feats, const int64_t* n_floats, int B, bool single, int64_t* tokens,
                                   int32_t* ts, int32_t* n_tokens, int max_tokens) {
     K2_REQUIRE(B > 0 && max_tokens > 0, "offline_greedy: bad B=%d / max_tokens=%d", B, max_tokens);
     K2_REQUIRE(!single || B == 1, "offline_greedy_single: B must be 1");
-    const Config& cf = model_->cfg();
-    K2_REQUIRE(cf.ctc || cf.J == 512, "offline loops hard-code a 512-wide encoder_out (OfflineRecognizer.cs:103,201); joiner_dim is %d", cf.J);
     int64_t mx = 0, total = 0;
     for (int b = 0; b < B; b++) {
         K2_REQUIRE(feats[b] != nullptr && n_floats[b] > 0, "offline_greedy: stream %d has no features", b);
         mx = std::max(mx, n_floats[b]);
         total += n_floats[b];
     }
-    const int64_t L = mx + 80 * kTailFrames;
-    const int T = (int)(L / cf.feat);  // OfflineProjOfTransducer.cs:59
-    K2_REQUIRE(L % cf.feat == 0, "offline_greedy: padded length %lld is not a multiple of feature_dim", (long long)L);
+    const OfflineShape sh = offline_shape("offline_greedy", mx, true);
+    K2_REQUIRE(sh.L % model_->cfg().feat == 0, "offline_greedy: padded length %lld is not a multiple of feature_dim", (long long)sh.L);
     // stage all features in one pinned buffer -> one H2D
     float* pin = static_cast<float*>(pinned(sizeof(float) * total + 16 * B + 64));
     std::vector<long long> off(B), len(B);
@@ -1443,7 +1422,7 @@ void Engine::offline_greedy_feats(const float* const* feats, const int64_t* n_fl
         float* d_packed = ar.take<float>(total);
         long long* d_off = ar.take<long long>(B);
         long long* d_len = ar.take<long long>(B);
-        float* d_x = ar.take<float>((int64_t)B * L);
+        float* d_x = ar.take<float>((int64_t)B * sh.L);
         if (!c.dry) {
             K2_HIP(hipEventRecord(ev_[0], c.stream));
             K2_HIP(hipMemcpyAsync(d_packed, pin, sizeof(float) * total, hipMemcpyHostToDevice, c.stream));
@@ -1451,8 +1430,8 @@ void Engine::offline_greedy_feats(const float* const* feats, const int64_t* n_fl
             K2_HIP(hipMemcpyAsync(d_len, len.data(), sizeof(long long) * B, hipMemcpyHostToDevice, c.stream));
             K2_HIP(hipEventRecord(ev_[1], c.stream));
         }
-        pad_logfloor(c, d_packed, d_off, d_len, d_x, B, L);
-        ex = encode_and_search(c, d_x, B, T, single, out);
+        pad_logfloor(c, d_packed, d_off, d_len, d_x, B, sh.L);
+        ex = encode_and_search(c, d_x, B, sh.T, SearchStage{single}, out);
     });
     finish_tokens(out, ex, tokens, ts, n_tokens);
     fill_timing(false, true);
@@ -1461,28 +1440,19 @@ void Engine::offline_greedy_feats(const float* const* feats, const int64_t* n_fl
 void Engine::offline_greedy_samples_dev(const float* samples_dev, int64_t n_each, int B, int64_t* tokens, int32_t* ts,
                                         int32_t* n_tokens, int max_tokens) {
     K2_REQUIRE(B > 0 && max_tokens > 0 && samples_dev != nullptr, "offline_greedy_from_samples: bad arguments");
-    const Config& cf = model_->cfg();
-    const FbankOpts& f = cf.fbank;
-    K2_REQUIRE(cf.ctc || cf.J == 512, "offline loops hard-code a 512-wide encoder_out; joiner_dim is %d", cf.J);
-    const int64_t nf = fbank_num_frames(n_each);
-    K2_REQUIRE(nf > 0, "offline_greedy_from_samples: %lld samples give no frame", (long long)n_each);
-    const int64_t n_fl = nf * cf.feat, L = n_fl + 80 * kTailFrames;
-    const int T = (int)(L / cf.feat);
+    const OfflineShape sh = offline_shape("offline_greedy_from_samples", n_each);
     SearchOut out;
     SearchExtras ex;
     run_sized([&](const Ctx& c) {
         Arena& ar = *c.arena;
         out = SearchOut(ar, B, max_tokens);
-        float* d_feats = ar.take<float>((int64_t)B * n_fl);
-        float* d_x = ar.take<float>((int64_t)B * L);
+        float* d_feats = ar.take<float>((int64_t)B * sh.n_fl);
+        float* d_x = ar.take<float>((int64_t)B * sh.L);
         if (!c.dry) K2_HIP(hipEventRecord(ev_[0], c.stream));
-        FbankArgs a{samples_dev, n_each, n_each, B, nf, d_feats, model_->d_window, model_->d_melw, f.frame_len, f.frame_shift,
-                    f.preemph, f.input_scale, f.remove_dc};
-        a.melrange = model_->d_melrange;
-        fbank(c, a);
+        fbank(c, fbank_args(samples_dev, n_each, n_each, B, sh.frames, d_feats));
         if (!c.dry) K2_HIP(hipEventRecord(ev_[1], c.stream));
-        pad_logfloor_dense(c, d_feats, n_fl, d_x, B, L);
-        ex = encode_and_search(c, d_x, B, T, false, out);
+        pad_logfloor_dense(c, d_feats, sh.n_fl, d_x, B, sh.L);
+        ex = encode_and_search(c, d_x, B, sh.T, SearchStage{}, out);
     });
     finish_tokens(out, ex, tokens, ts, n_tokens);
     fill_timing(true, true);
@@ -1490,6 +1460,11 @@ void Engine::offline_greedy_samples_dev(const float* samples_dev, int64_t n_each
 
 void Engine::offline_greedy_samples(const float* const* samples, const int64_t* n_samples, int B, int64_t* tokens, int32_t* ts,
                                     int32_t* n_tokens, int max_tokens, bool single, bool pinned_src) {
+    offline_samples(samples, n_samples, B, SearchStage{single}, tokens, ts, n_tokens, max_tokens, pinned_src);
+}
+
+void Engine::offline_samples(const float* const* samples, const int64_t* n_samples, int B, const SearchStage& stage, int64_t* tokens, int32_t* ts,
+                             int32_t* n_tokens, int max_tokens, bool pinned_src) {
     // Host samples, any lengths: ONE pinned staging block [B, nmax] (tails zeroed) + the streams' feature offsets / lengths, one H2D,
     // ONE batched fbank launch over nmax samples per stream, then the fused feature path on the device.  A frame i < frames(n_b) of
     // stream b only reads samples below n_b, so the zero tail never reaches a frame that is kept; pad_logfloor takes each stream's
@@ -1499,20 +1474,11 @@ void Engine::offline_greedy_samples(const float* const* samples, const int64_t* 
     // only the table of pointers and lengths is uploaded, and a gather kernel reads the samples in place over PCIe into the dense [B, nmax]
     // device block (tails zeroed there): the host's 20 MB staging copy and the separate upload of a 32 x 10 s batch become one pass.
     K2_REQUIRE(B > 0 && max_tokens > 0, "offline_greedy_from_samples: bad B=%d / max_tokens=%d", B, max_tokens);
-    K2_REQUIRE(!single || B == 1, "offline_greedy_from_samples: the single-stream loop takes one stream");
+    K2_REQUIRE(!stage.single || B == 1, "offline_greedy_from_samples: the single-stream loop takes one stream");
     K2_HIP(hipSetDevice(device_));   // (the pinned queues' device addresses are asked for below, before run_sized sets it)
-    const Config& cf = model_->cfg();
-    const FbankOpts& f = cf.fbank;
-    K2_REQUIRE(cf.ctc || cf.J == 512, "offline loops hard-code a 512-wide encoder_out (OfflineRecognizer.cs:103,201); joiner_dim is %d", cf.J);
-    int64_t nmax = 0;
-    for (int b = 0; b < B; b++) {
-        K2_REQUIRE(samples[b] != nullptr && fbank_num_frames(n_samples[b]) > 0, "stream %d: %lld samples give no frame", b, (long long)n_samples[b]);
-        nmax = std::max(nmax, n_samples[b]);
-    }
-    const int64_t nfmax = fbank_num_frames(nmax), n_fl = nfmax * cf.feat, L = n_fl + 80 * kTailFrames;
-    const int T = (int)(L / cf.feat);  // OfflineProjOfTransducer.cs:59 over PadHelper.cs:17,22
-    // rows of the search-output block: one per stream, or one per target while a CTC align call (several targets may share a stream) runs here
-    const int rows = ctc_align_plan_ ? ctc_align_plan_->H : B;
+    const OfflineShape sh = samples_shape(samples, n_samples, B);
+    const int64_t nmax = sh.longest, n_fl = sh.n_fl, L = sh.L;
+    const int rows = stage.rows(B);
     // rows of the dense sample block are `ns` floats apart: nmax rounded up to 4, so that every row starts on 16 bytes for any lengths (the
     // gather moves float4; a row that did not would take its scalar path -- four 4-byte reads per lane over PCIe)
     const int64_t ns = (nmax + 3) & ~(int64_t)3;
@@ -1555,7 +1521,7 @@ void Engine::offline_greedy_samples(const float* const* samples, const int64_t* 
     }
     for (int b = 0; b < B; b++) {
         h_off[b] = (long long)b * n_fl;
-        h_len[b] = fbank_num_frames(n_samples[b]) * cf.feat;
+        h_len[b] = fbank_num_frames(n_samples[b]) * model_->cfg().feat;
     }
     SearchOut out;
     SearchExtras ex;
@@ -1576,13 +1542,10 @@ void Engine::offline_greedy_samples(const float* const* samples, const int64_t* 
             else K2_HIP(hipMemcpyAsync(d_in, pin, (size_t)(nb_s + 16 * (int64_t)B), hipMemcpyHostToDevice, c.stream));
         }
         if (pinned_src) gather_samples(c, d_ptr, d_cnt, d_s, B, ns);
-        FbankArgs a{d_s, nmax, ns, B, nfmax, d_feats, model_->d_window, model_->d_melw, f.frame_len, f.frame_shift,
-                    f.preemph, f.input_scale, f.remove_dc};
-        a.melrange = model_->d_melrange;
-        fbank(c, a);
+        fbank(c, fbank_args(d_s, nmax, ns, B, sh.frames, d_feats));
         if (!c.dry) K2_HIP(hipEventRecord(ev_[1], c.stream));
         pad_logfloor(c, d_feats, d_off, d_len, d_x, B, L);
-        ex = encode_and_search(c, d_x, B, T, single, out);
+        ex = encode_and_search(c, d_x, B, sh.T, stage, out);
     });
     finish_tokens(out, ex, tokens, ts, n_tokens);
     fill_timing(true, true);
@@ -1602,14 +1565,10 @@ int Engine::submit_samples_host(const float* samples_host, int64_t n_each, int B
 // for it through an event -- PCIe is inside the pipeline, not in front of it.
 int Engine::submit_impl(const float* samples_dev, const float* samples_host, int64_t n_each, int B, int max_tokens) {
     K2_REQUIRE(B > 0 && max_tokens > 0, "offline_submit: bad arguments");
-    const Config& cf = model_->cfg();
-    const FbankOpts& f = cf.fbank;
-    K2_REQUIRE(cf.ctc || cf.J == 512, "offline loops hard-code a 512-wide encoder_out; joiner_dim is %d", cf.J);
-    const int64_t nf = fbank_num_frames(n_each);
-    K2_REQUIRE(nf > 0, "offline_submit: %lld samples give no frame", (long long)n_each);
+    const OfflineShape sh = offline_shape("offline_submit", n_each);
     // slots in use: all three when every slot's search runs on the slot's own stream (the beam search), else two.  (Rounds 1 - 4 kept a
     // third form behind a switch, two whole batches concurrently on two streams: 15.15 against 13.76 ms per headline batch; removed.)
-    const bool deep = beam_ > 0 && !cf.ctc;
+    const bool deep = beam_ > 0 && !model_->cfg().ctc;
     const int nslots = deep ? kSlots : 2;
     int ticket = -1, in_flight = 0;
     for (const auto& x : slots_) in_flight += x.busy;
@@ -1621,8 +1580,6 @@ int Engine::submit_impl(const float* samples_dev, const float* samples_host, int
         failf(K2HIP_ERR_INVALID, "offline_submit: %d batches already in flight; wait for one first", in_flight);
     Slot& sl = slots_[ticket];
     if (!sl.stream) K2_HIP(hipStreamCreateWithFlags(&sl.stream, hipStreamNonBlocking));
-    const int64_t n_fl = nf * cf.feat, L = n_fl + 80 * kTailFrames;
-    const int T = (int)(L / cf.feat);
     const int64_t nb = SearchOut::bytes_for(B, max_tokens);
     if (nb > sl.pin_cap) {
         if (sl.pin) K2_HIP(hipHostFree(sl.pin));
@@ -1637,8 +1594,8 @@ int Engine::submit_impl(const float* samples_dev, const float* samples_host, int
         run_sized([&](const Ctx& c) {
             Arena& ar = *c.arena;
             sl.out = SearchOut(ar, B, max_tokens);
-            float* d_feats = ar.take<float>((int64_t)B * n_fl);
-            float* d_x = ar.take<float>((int64_t)B * L);
+            float* d_feats = ar.take<float>((int64_t)B * sh.n_fl);
+            float* d_x = ar.take<float>((int64_t)B * sh.L);
             const float* src = samples_dev;
             if (samples_host) {
                 float* d_s = ar.take<float>((int64_t)B * n_each);
@@ -1650,13 +1607,10 @@ int Engine::submit_impl(const float* samples_dev, const float* samples_host, int
                     K2_HIP(hipStreamWaitEvent(c.stream, sl.h2d_done, 0));
                 }
             }
-            FbankArgs a{src, n_each, n_each, B, nf, d_feats, model_->d_window, model_->d_melw, f.frame_len, f.frame_shift,
-                        f.preemph, f.input_scale, f.remove_dc};
-            a.melrange = model_->d_melrange;
-            fbank(c, a);
-            pad_logfloor_dense(c, d_feats, n_fl, d_x, B, L);
+            fbank(c, fbank_args(src, n_each, n_each, B, sh.frames, d_feats));
+            pad_logfloor_dense(c, d_feats, sh.n_fl, d_x, B, sh.L);
             int Tp = 0;
-            float* enc = encoder_forward(c, d_x, B, T, &Tp, -1, nullptr, nullptr, nullptr);
+            float* enc = encoder_forward(c, d_x, B, sh.T, &Tp, -1, nullptr, nullptr, nullptr);
             Ctx cd = c;
             cd.stream = s2;
             cd.instrument = false;
@@ -1666,7 +1620,7 @@ int Engine::submit_impl(const float* samples_dev, const float* samples_host, int
                 K2_HIP(hipEventRecord(sl.enc_done, c.stream));
                 K2_HIP(hipStreamWaitEvent(s2, sl.enc_done, 0));
             }
-            greedy_device(cd, enc, B, Tp, false, sl.out, false);
+            search_device(cd, enc, B, Tp, SearchStage{false, false}, sl.out);
         });
     } catch (...) {
         cur_arena_ = &arena_;

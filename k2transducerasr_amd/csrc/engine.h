@@ -1,6 +1,7 @@
 // Engine = one model replica on one GPU: weights, HIP stream, device arena and the
 // host-side orchestration of the offline path (pad -> Zipformer2 -> greedy).
 #pragma once
+#include <algorithm>
 #include <array>
 #include <condition_variable>
 #include <functional>
@@ -79,7 +80,8 @@ class Engine {
     // token_log_probs [B][max_tokens], total / best [B].  The arguments are checked on the host before any device work (lattice_ref.h).
     void align_host(const float* enc_out, int B, int Tp, const int32_t* n_frames, const int64_t* ids, const int32_t* lens, int32_t* timestamps,
                     float* token_log_probs, float* total, float* best, int max_tokens);
-    // fbank + pad + encoder as offline_greedy_samples, encoder_out left on the device, every stream aligned over all T' frames
+    // offline_greedy_samples' fbank + pad + encoder with the plan's alignment as the stage behind them: encoder_out stays on the device,
+    // every stream is aligned over all T' frames
     void align_samples(const float* const* samples, const int64_t* n_samples, int B, const int64_t* ids, const int32_t* lens, int32_t* timestamps,
                        float* token_log_probs, float* total, float* best, int max_tokens, int32_t* Tp_out);
     // ---- CTC forced alignment and full-sum scoring (ctc_align.hip; semantics in include/k2hip.h) ----
@@ -89,7 +91,7 @@ class Engine {
     void ctc_align_host(const float* log_probs, int R, int Tp, const int32_t* n_frames, int H, const int32_t* stream_of, const int64_t* ids,
                         const int32_t* lens, int32_t* timestamps, int32_t* end_frames, float* token_log_probs, float* total, float* best,
                         int max_tokens);
-    // fbank + pad + encoder as offline_greedy_samples, log_probs left on the device, every target aligned over all T' frames
+    // the same with the CTC plan as the stage: log_probs stay on the device, every target is aligned over all T' frames
     void ctc_align_samples(const float* const* samples, const int64_t* n_samples, int B, int H, const int32_t* stream_of, const int64_t* ids,
                            const int32_t* lens, int32_t* timestamps, int32_t* end_frames, float* token_log_probs, float* total, float* best,
                            int max_tokens, int32_t* Tp_out);
@@ -253,10 +255,7 @@ class Engine {
     // pass planes of their own (stay / emit) and stop after the first kernel (dp = false) or run only the second (cells = false).
     SearchExtras align_device(const Ctx& c, const float* enc, int Tp, const AlignPlan& p, const SearchOut& out, float* stay = nullptr,
                               float* emit = nullptr, bool cells = true, bool dp = true);
-    const AlignPlan* align_plan_ = nullptr;   // while set (the span of align_samples), the fused entries' search is align_device
     std::vector<float> last_align_lp_, last_align_scores_;
-    void align_copy_out(const AlignPlan& p, const int32_t* ts_all, int max_tokens, int32_t* timestamps, float* token_log_probs, float* total,
-                        float* best) const;
     // One CTC align call as the host lays it out before any device work: the targets' descriptors and ids (stream_of resolved into
     // CtcAlignTarget::row) in ONE upload block
     struct CtcAlignPlan {
@@ -271,14 +270,47 @@ class Engine {
     // gather + lattice into `out` (H rows: tokens = the targets, counts = their lengths, timestamps); end frames, token log-probs and
     // (total, best) are SearchExtras
     SearchExtras ctc_align_device(const Ctx& c, const float* logp, int R, int Tp, const CtcAlignPlan& p, const SearchOut& out);
-    const CtcAlignPlan* ctc_align_plan_ = nullptr;   // while set (the span of ctc_align_samples), the fused entries' search is ctc_align_device
     std::vector<int32_t> last_align_end_;
-    void ctc_align_copy_out(const CtcAlignPlan& p, const int32_t* ts_all, int max_tokens, int32_t* timestamps, int32_t* end_frames,
-                            float* token_log_probs, float* total, float* best) const;
+    // what an align call has finish_tokens fill (only the timestamps are read back): rows of mt = max(max_tokens, 1) entries
+    struct AlignScratch {
+        int mt;
+        std::vector<int64_t> tok;
+        std::vector<int32_t> ts, n;
+        AlignScratch(int rows, int max_tokens) : mt(std::max(max_tokens, 1)), tok((size_t)rows * mt), ts((size_t)rows * mt), n((size_t)rows) {}
+    };
+    // lens[r] entries of row r from the scratch and the last_align_* vectors into the caller's outputs (each may be null)
+    void align_copy_out(int rows, const int32_t* lens, const AlignScratch& s, int32_t* timestamps, int32_t* end_frames, float* token_log_probs,
+                        float* total, float* best) const;
+    // What a call runs on the encoder output, named by the caller: one plan's alignment, or (both null) the model's search.
     // keep_nbest: the caller fetches the beam search's N-best (the synchronous entries; the pipelined route has no place to keep them)
+    struct SearchStage {
+        bool single = false, keep_nbest = true;
+        const AlignPlan* align = nullptr;
+        const CtcAlignPlan* ctc_align = nullptr;
+        // rows of its search-output block for B streams: one per stream, or one per target (several CTC targets may share a stream)
+        int rows(int B) const { return ctc_align ? ctc_align->H : B; }
+    };
+    SearchExtras search_device(const Ctx& c, const float* enc, int B, int Tp, const SearchStage& stage, const SearchOut& out);
+    // the model's search alone: CTC collapse, modified beam search or greedy
     SearchExtras greedy_device(const Ctx& c, const float* enc, int B, int Tp, bool single, const SearchOut& out, bool keep_nbest);
-    // the fused offline entries' tail on c.stream: event 2, encoder, event 3, search, event 4
-    SearchExtras encode_and_search(const Ctx& c, const float* d_x, int B, int T, bool single, const SearchOut& out);
+    // the operator entries' route: host encoder_out (a CTC model's log_probs) uploaded, the stage run on it, the results fetched
+    void search_host(const float* enc_out, int B, int Tp, const SearchStage& stage, int64_t* tokens, int32_t* ts, int32_t* n_tokens, int max_tokens);
+    // the fused offline entries' tail on c.stream: event 2, encoder, event 3, the stage, event 4
+    SearchExtras encode_and_search(const Ctx& c, const float* d_x, int B, int T, const SearchStage& stage, const SearchOut& out);
+    // One offline batch's shape from its longest stream (samples, or feature floats with from_feats): its feature frames and floats, the
+    // padded length L in floats, the encoder's input frames T and output frames Tp
+    struct OfflineShape {
+        int64_t longest, frames, n_fl, L;
+        int T, Tp;
+    };
+    OfflineShape offline_shape(const char* who, int64_t longest, bool from_feats = false) const;
+    // ... of host sample arrays of any lengths, each of which must give a frame
+    OfflineShape samples_shape(const float* const* samples, const int64_t* n_samples, int B) const;
+    // fbank's arguments, the model's constants filled in
+    FbankArgs fbank_args(const float* src, int64_t n, int64_t stride, int n_utts, int64_t nf, float* dst) const;
+    // offline_greedy_samples with the stage named: what the public entry and the two align entries run
+    void offline_samples(const float* const* samples, const int64_t* n_samples, int B, const SearchStage& stage, int64_t* tokens, int32_t* ts,
+                         int32_t* n_tokens, int max_tokens, bool pinned_src);
     // timing_ from ev_[0..5]; which of the legs in front of the encoder the call has
     void fill_timing(bool fbank_leg, bool pad_leg);
     const float* pos_emb(int T);  // cached CompactRelPositionalEncoding table on device

@@ -292,3 +292,30 @@ def test_align_changes_no_search(hip_tiny, enc_tiny):
     assert hip_tiny.greedy_batch(enc_tiny) == greedy0
     beam1, sc1 = hip_tiny.beam_search(enc_tiny, 4, want_scores=True)
     assert beam1 == beam0 and np.array_equal(sc0, sc1)
+
+
+def test_fused_align_changes_no_fused_search(hip_tiny, utts):
+    """the fused greedy and beam-4 results (tokens, timestamps, scores) are identical before and after fused align calls on the same handle,
+    one that runs and one that is refused: what the fused route runs behind the encoder is named by the call, not left behind by one"""
+    from k2transducerasr_amd import K2HipError
+
+    def fused():
+        greedy = hip_tiny.offline_greedy_from_samples(utts)
+        hip_tiny.set_decoding_method("modified_beam_search", 4)
+        try:
+            beam = hip_tiny.offline_greedy_from_samples(utts)
+            sc = hip_tiny.last_scores(len(utts)).copy()
+        finally:
+            hip_tiny.set_decoding_method("greedy_search")
+        return greedy, beam, sc
+
+    greedy0, beam0, sc0 = fused()
+    assert sum(len(t) for t, _ in greedy0) > 0 and sum(len(t) for t, _ in beam0) > 0
+    tg = targets_for(hip_tiny.vocab_size, [7, 4, 0, 11, 2][: len(utts)], 71)
+    got = hip_tiny.align_samples(utts, tg)
+    assert [len(g["timestamps"]) for g in got] == [len(t) for t in tg]
+    with pytest.raises(K2HipError) as e:
+        hip_tiny.align_samples(utts, tg, max_tokens=2)
+    assert e.value.code == -5 and "max_tokens" in str(e.value), (e.value.code, str(e.value))
+    greedy1, beam1, sc1 = fused()
+    assert greedy1 == greedy0 and beam1 == beam0 and np.array_equal(sc0, sc1)

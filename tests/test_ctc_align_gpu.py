@@ -251,3 +251,25 @@ def test_errors_on_the_device_build(hip_ctc, hip_tiny, utts, device_log_probs):
         assert e.value.code == -1 and "target 1" in str(e.value), (e.value.code, str(e.value))
     again = hip_ctc.ctc_align(device_log_probs, good)
     assert [(a["timestamps"], a["total_logp"], a["best_logp"]) for a in again] == [(a["timestamps"], a["total_logp"], a["best_logp"]) for a in ref]
+
+
+def test_fused_align_changes_no_fused_search(hip_ctc, utts, greedy, untied):
+    """offline_greedy_from_samples gives identical results before and after fused CTC align calls with more targets than streams (H = 7
+    rows in the output block against B = 5) and with fewer (H = 1)"""
+    before = hip_ctc.offline_greedy_from_samples(utts)
+    assert len(utts) == 5
+    b = next(b for b in untied if len(greedy[b][0]) >= 2)
+    V = hip_ctc.vocab_size
+    g = np.array(greedy[b][0], np.int64)
+    cands = []
+    for k in range(6):                                            # six substitutions of the greedy result, then the result itself
+        sub = g.copy()
+        sub[k % len(g)] = 1 + ((int(g[k % len(g)]) + k) % (V - 1))
+        cands.append(sub)
+    cands.append(g)
+    many = hip_ctc.ctc_align_samples(utts, cands, stream_of=[b] * 7)
+    assert [len(x["timestamps"]) for x in many] == [len(y) for y in cands]
+    assert hip_ctc.offline_greedy_from_samples(utts) == before
+    one = hip_ctc.ctc_align_samples(utts, [g], stream_of=[b])
+    assert one[0]["timestamps"] == many[6]["timestamps"] and one[0]["best_logp"] == many[6]["best_logp"]
+    assert hip_ctc.offline_greedy_from_samples(utts) == before
