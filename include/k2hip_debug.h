@@ -106,6 +106,10 @@ int32_t k2hip_debug_gemm_run(k2hip_model_t* model, const float* A, const float* 
  *     back to back), lens [H] int32, timestamps, end_frames [H][max_tokens] int32, token_log_probs [H][max_tokens], scores [H][2] =
  *     (total, best) (out); ints R, Tp, H, max_tokens.  The arguments pass the checks of k2hip_ctc_align; what lies behind a row's first
  *     lens[h] entries is unspecified.
+ * The two forms of Swoosh's softplus (csrc/act.h; tests/test_act_forms_gpu.py):
+ *   "act_forms": ints act (1 SwooshL, 2 SwooshR), n; buffers x [n] (in), y_lean [n], y_libm [n] (out).  One plain elementwise
+ *     kernel: y_lean = the activation as the GEMM epilogues and the elementwise kernels compute it (softplus_ge1), y_libm = the same
+ *     with the library's general log (softplus_libm).  The two must agree bit for bit.
  * One op launches nothing (tests/test_search_ties_gpu.py):
  *   "greedy_screen_counts": no int arguments, one buffer of 2 int64 that the hook fills (whatever out_mask says) with the model's
  *     counters since it was created: [0] rounds of the persistent large-vocabulary greedy search (csrc/greedy.hip k_greedy) that its

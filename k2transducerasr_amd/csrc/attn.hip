@@ -6,8 +6,8 @@
 //
 // One workgroup (8 waves) owns 32 query rows of one (head, batch) pair and ALL T
 // keys: q.k^T runs on the f32 MFMA (32x32x2, exact f32 products; K = 32), the
-// 4-wide positional term is added on the VALU in the accumulator layout, the
-// 32 x T score strip lives in LDS, and the row softmax is done in place before a
+// 4-wide positional term is a second, skewed f32 MFMA product that seeds the
+// accumulators through the 32 x T score strip in LDS, and the row softmax is done in place before a
 // single coalesced write of the weights.  The strip never touches HBM; the
 // weights are written once and read three times (non-linear attention and the
 // two value paths).
@@ -48,7 +48,7 @@ __global__ __launch_bounds__(512, 4) void k_attn_scores_softmax(const float* __r
         }
     }
     const int njt = (T + 31) / 32;
-    // the next key tile's fragments are requested before this tile's MFMAs and positional adds
+    // the next key tile's fragments are requested before this tile's strip reads and MFMAs
     float4 fkn[NG];
     auto load_keys = [&](int jt) {
         if (jt >= njt) return;                 // (wave-uniform)
@@ -56,15 +56,51 @@ __global__ __launch_bounds__(512, 4) void k_attn_scores_softmax(const float* __r
 #pragma unroll
         for (int g = 0; g < NG; g++) fkn[g] = *reinterpret_cast<const float4*>(base + (long long)j * ld + koff + 8 * g + 4 * lh);
     };
-    load_keys(wave);   // (requested in front of the window staging: one memory latency for both)
-    // the positional rows this workgroup can touch, n = T-1-i+j for its rows i and every key j: one window of <= T+R-1
-    // consecutive rows of pp (16 B each for this head) -> LDS, so the per-element gather below is an LDS read
-    float4* PW = reinterpret_cast<float4*>(S + R * lds_stride);
-    const int nlo = T - 1 - min(i0 + R - 1, T - 1), nwin = (2 * T - 2 - i0) - nlo + 1;
-    for (int wdx = tid; wdx < nwin; wdx += 512) PW[wdx] = *reinterpret_cast<const float4*>(pp + (long long)(nlo + wdx) * ppld + h * PH);
-    // the positional queries p_i of the 32 rows (read back as LDS broadcasts: all lanes of a half-wave share the row)
-    float4* PR = PW + (T + R);
-    if (tid < R) PR[tid] = i0 + tid < T ? *reinterpret_cast<const float4*>(base + (long long)(i0 + tid) * ld + poff) : make_float4(0.f, 0.f, 0.f, 0.f);
+    load_keys(wave);   // (requested in front of the positional phase: one memory latency for both)
+
+    // Positional term on the matrix pipe, rel-shift in scatter form.  The relative index of (row i, key j) is n = T-1-i+j in
+    // [0, 2T-2]; this workgroup's rows and every key touch one window of <= T+R-1 consecutive rows of pp, [nlo, nlo + nwin).
+    // P [32 x 4] . pos[window]^T [4 x nwin] in 32-column tiles dealt over the waves, two MFMAs per tile (k = 0, 2 then 1, 3: lane
+    // half lh supplies components 2 lh and 2 lh + 1 of both operands, straight from global memory); accumulator element (row rl,
+    // window row n) is the positional term of exactly one score, (rl, j = n - (T-1-(i0+rl))), and goes to S[rl][j] when that key
+    // exists.  A row past T has p = 0 (its cells are never read back for a result), a window row past 2T-2 reads row 2T-2 and
+    // lands on no key: j >= T for every row.
+    {
+        const int nlo = T - 1 - min(i0 + R - 1, T - 1), nwin = (2 * T - 2 - i0) - nlo + 1;
+        float2 fp = make_float2(0.f, 0.f);
+        if (i0 + li < T) fp = *reinterpret_cast<const float2*>(base + (long long)(i0 + li) * ld + poff + 2 * lh);
+        const float* pw = pp + h * PH + 2 * lh;
+        auto load_window = [&](int t) {   // (always in bounds: the row is clamped, so the tile after the last may be requested too)
+            return *reinterpret_cast<const float2*>(pw + (long long)min(nlo + t * 32 + li, 2 * T - 2) * ppld);
+        };
+        float2 fw = load_window(wave);
+        for (int t = wave; t * 32 < nwin; t += 8) {
+            const float2 fwn = load_window(t + 8);   // in flight during this tile's MFMAs and stores
+            f32x16 acc;
+#pragma unroll
+            for (int r = 0; r < 16; r++) acc[r] = 0.f;
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fp.x, fw.x, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fp.y, fw.y, acc, 0, 0, 0);
+            fw = fwn;
+            // j of (lane 0, register 0) of this tile; the tile's j span [j00, j00 + 62] over its 32 rows and 32 window rows
+            const int j00 = nlo + t * 32 + i0 - (T - 1);
+            const int j0 = j00 + li + 4 * lh;     // this lane's j for register r: j0 + Rows32 offset of r
+            float* sp = S + 4 * lh * lds_stride + j0;
+            if (j00 >= 0 && j00 + 62 < T) {       // (wave-uniform) an inner tile: every element has its key
+#pragma unroll
+                for (int r = 0; r < 16; r++) {
+                    const int ro = (r & 3) + 8 * (r >> 2);
+                    sp[ro * lds_stride + ro] = acc[r];
+                }
+            } else {
+#pragma unroll
+                for (int r = 0; r < 16; r++) {
+                    const int ro = (r & 3) + 8 * (r >> 2);
+                    if ((unsigned)(j0 + ro) < (unsigned)T) sp[ro * lds_stride + ro] = acc[r];
+                }
+            }
+        }
+    }
     __syncthreads();
 
     for (int jt = wave; jt < njt; jt += 8) {
@@ -73,9 +109,11 @@ __global__ __launch_bounds__(512, 4) void k_attn_scores_softmax(const float* __r
 #pragma unroll
         for (int g = 0; g < NG; g++) fk[g] = fkn[g];
         load_keys(jt + 8);
+        // the accumulator starts from the positional term of its score (no vector add behind the MFMAs)
+        float* sp = S + 4 * lh * lds_stride + min(j, T - 1);   // (a key past T reads column T-1 and is never written)
         f32x16 acc;
 #pragma unroll
-        for (int r = 0; r < 16; r++) acc[r] = 0.f;
+        for (int r = 0; r < 16; r++) acc[r] = sp[((r & 3) + 8 * (r >> 2)) * lds_stride];
 #pragma unroll
         for (int g = 0; g < NG; g++) {
             acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fq[g].x, fk[g].x, acc, 0, 0, 0);
@@ -84,25 +122,8 @@ __global__ __launch_bounds__(512, 4) void k_attn_scores_softmax(const float* __r
             acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fq[g].w, fk[g].w, acc, 0, 0, 0);
         }
         if (j < T) {
-            // rel-shift in gather form: relative index n = T-1-i+j in [0, 2T-2].  No condition on the row (a row past T reads the window
-            // entry of row T-1 and is never used): under `if (i < T)` every one of the 16 window reads sat in its own block behind its
-            // own LDS wait.  Eight reads per wait now (round 5: 75.5 -> 73.6 us per launch at T = 505 -- the phase is bound by MFMA +
-            // vector issue at two workgroups per CU, not by these round trips; DESIGN "Round 5")
 #pragma unroll
-            for (int r0 = 0; r0 < 16; r0 += 8) {
-                float4 e[8];
-#pragma unroll
-                for (int r = 0; r < 8; r++) {
-                    const int rl = ((r0 + r) & 3) + 8 * ((r0 + r) >> 2) + 4 * lh;
-                    e[r] = PW[T - 1 - min(i0 + rl, T - 1) + j - nlo];
-                }
-#pragma unroll
-                for (int r = 0; r < 8; r++) {
-                    const int rl = ((r0 + r) & 3) + 8 * ((r0 + r) >> 2) + 4 * lh;
-                    const float4 pq = PR[rl];
-                    S[rl * lds_stride + j] = acc[r0 + r] + (pq.x * e[r].x + pq.y * e[r].y + pq.z * e[r].z + pq.w * e[r].w);
-                }
-            }
+            for (int r = 0; r < 16; r++) sp[((r & 3) + 8 * (r >> 2)) * lds_stride] = acc[r];
         }
     }
     __syncthreads();
@@ -670,7 +691,7 @@ template <int NG>
 static void attn_scores_launch(const Ctx& ctx, const float* qkp, int ld, const float* pp, float* aw, int B, int T, int Tp, int H, int koff0,
                                int poff0) {
     int lds_stride = Tp + 4;  // rows 16 B aligned; +4 floats de-phases the 4-row-apart writers of one MFMA register
-    size_t lds = sizeof(float) * (R * lds_stride + 4 * (T + R) + 4 * R);  // score strip + the positional window + the rows' p
+    size_t lds = sizeof(float) * R * lds_stride;  // the score strip
     const bool force_long = tunables().attn_long != 0;
     if (lds > 160 * 1024 || force_long) {  // > ~1120 frames: two-pass form without the LDS strip
         hipLaunchKernelGGL(k_attn_scores_softmax_long<NG>, dim3(cdiv(T, R), B, H), dim3(256), 0, ctx.stream, qkp, ld, pp, aw, B, T, Tp, H, koff0,

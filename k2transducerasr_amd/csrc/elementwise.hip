@@ -2,6 +2,7 @@
 // first conv and depthwise 7x7, BiasNorm / bypass, GLU / tanh gates, depthwise
 // Conv1d, learned down/up-sampling.  All activations are [rows, channels] with
 // channels contiguous, so every kernel moves float4 per lane along channels.
+#include "act.h"
 #include "kernels.h"
 
 namespace k2hip {
@@ -9,9 +10,7 @@ namespace {
 
 constexpr float kLogFloor = -23.025850929940457F;  // PadHelper.cs:58
 
-// hardware exp/log (v_exp_f32 / v_log_f32), ~1e-6 relative -- see gemm.hip apply_act
-__device__ __forceinline__ float fast_softplus(float z) { return z > 15.f ? z : __logf(1.0f + __expf(z)); }
-__device__ __forceinline__ float swoosh_r(float v) { return fast_softplus(v - 1.0f) - 0.08f * v - 0.313261687f; }
+// hardware exp/log (v_exp_f32 / v_log_f32), ~1e-6 relative -- see gemm.hip apply_act; swoosh_r is act.h's
 __device__ __forceinline__ float fast_tanh(float v) {
     float e = __expf(-2.0f * fabsf(v));
     float t = (1.0f - e) / (1.0f + e);
@@ -22,6 +21,15 @@ __device__ __forceinline__ float sigm(float s) { return 1.0f / (1.0f + __expf(-s
 __device__ __forceinline__ float dswish(float v) { return v / (1.0f + __expf(1.0f - v)); }  // v * sigmoid(v - 1)
 
 inline int nblocks(long long n, int per) { return (int)((n + per - 1) / per); }
+
+// ---- the two forms of Swoosh's softplus side by side (act.h; the test hook's "act_forms", tests/test_act_forms_gpu.py)
+__global__ void k_act_forms(const float* __restrict__ x, float* __restrict__ y_lean, float* __restrict__ y_libm, int act, long long n) {
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        const float v = x[i];
+        y_lean[i] = act == ACT_SWOOSH_L ? swoosh_l(v) : swoosh_r(v);
+        y_libm[i] = act == ACT_SWOOSH_L ? softplus_libm(v - 4.0f) - 0.08f * v - 0.035f : softplus_libm(v - 1.0f) - 0.08f * v - 0.313261687f;
+    }
+}
 
 // ---- F3: PadHelper.PadSequence (PadHelper.cs:20-60) on device ------------------
 //  out[b, j] = j < len[b] ? src[b][j] : 0 ; then x == 0 -> log floor (Q1, Q2)
@@ -694,6 +702,11 @@ void pad_logfloor(const Ctx& ctx, const float* packed, const long long* d_off, c
 void pad_logfloor_dense(const Ctx& ctx, const float* feats, long long n_each, float* out, int B, long long L) {
     dim3 grid(std::min(nblocks(L, 256), 512), B);
     LAUNCH(k_pad_logfloor_dense, grid, dim3(256), feats, n_each, out, L);
+}
+void act_forms(const Ctx& ctx, const float* x, float* y_lean, float* y_libm, int act, long long n) {
+    K2_REQUIRE(act == ACT_SWOOSH_L || act == ACT_SWOOSH_R, "act_forms: act %d is neither SwooshL (1) nor SwooshR (2)", act);
+    if (n <= 0) return;
+    LAUNCH(k_act_forms, dim3(std::min(nblocks(n, 256), 4096)), dim3(256), x, y_lean, y_libm, act, n);
 }
 void conv0_swoosh(const Ctx& ctx, const float* x, const float* w, const float* b, float* y, int B, int T, int F) {
     long long n = (long long)B * (T - 2) * F;

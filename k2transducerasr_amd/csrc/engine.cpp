@@ -2208,6 +2208,13 @@ void Engine::debug_op_host(const char* op, const int64_t* iargs, int n_iargs, vo
             K2_HIP(copy_blocking(dev[6], ex.align_end, 4 * (size_t)H * max_tokens, hipMemcpyDeviceToDevice));
             K2_HIP(copy_blocking(dev[7], ex.align_lp, 4 * (size_t)H * max_tokens, hipMemcpyDeviceToDevice));
             K2_HIP(copy_blocking(dev[8], ex.align_scores, 8 * (size_t)H, hipMemcpyDeviceToDevice));
+        } else if (name == "act_forms") {
+            const int act = I();
+            const long long n = L();
+            float *x = P(), *y_lean = P(), *y_libm = P();
+            K2_REQUIRE(n >= 0 && x && y_lean && y_libm && buf_bytes[0] >= 4 * n && buf_bytes[1] >= 4 * n && buf_bytes[2] >= 4 * n,
+                       "debug_op_run act_forms: three buffers of n = %lld floats are needed", n);
+            act_forms(c, x, y_lean, y_libm, act, n);
         } else if (name == "basicnorm") {
             float *x = P(), *le = P(), *y = P();
             const int M = I(), D = I();

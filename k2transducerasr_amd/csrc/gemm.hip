@@ -30,6 +30,7 @@
 #include <mutex>
 #include <type_traits>
 
+#include "act.h"
 #include "kernels.h"
 
 // The LDS-DMA inline asm of the pipelined kernels writes M0 (the LDS destination) and SCC (s_add_u32) and says so in its clobber
@@ -49,14 +50,11 @@ namespace {
 
 // Activations with the hardware transcendental units (v_exp_f32 / v_log_f32, ~1e-6
 // relative): the accurate libm forms cost ~100 VALU instructions per element, which
-// for K <= 256 made the epilogue longer than the MFMA loop.
-__device__ __forceinline__ float fast_softplus(float z) {  // log(1 + e^z)
-    return z > 15.f ? z : __logf(1.0f + __expf(z));
-}
+// for K <= 256 made the epilogue longer than the MFMA loop.  Swoosh's softplus is act.h's lean form.
 __device__ __forceinline__ float apply_act(float v, int act) {
     switch (act) {
-        case ACT_SWOOSH_L: return fast_softplus(v - 4.0f) - 0.08f * v - 0.035f;
-        case ACT_SWOOSH_R: return fast_softplus(v - 1.0f) - 0.08f * v - 0.313261687f;
+        case ACT_SWOOSH_L: return swoosh_l(v);
+        case ACT_SWOOSH_R: return swoosh_r(v);
         case ACT_TANH: {
             float e = __expf(-2.0f * fabsf(v));
             float t = (1.0f - e) / (1.0f + e);
@@ -1217,7 +1215,7 @@ __device__ __forceinline__ void conv_outputs(const GemmArgs& g, const PRE& pre, 
 #pragma unroll
             for (int k = 0; k < Kc; k++) xc += wc[k] * col[i + k];
             const float z = xw[i] * (1.0f + (le[i] + re[i])) + xc;
-            yp[(long long)i * g.ldc] = fast_softplus(z - 1.0f) - 0.08f * z - 0.313261687f;   // SwooshR (online.hip swoosh_r)
+            yp[(long long)i * g.ldc] = swoosh_r(z);   // SwooshR (online.hip swoosh_r)
         }
     }
 }

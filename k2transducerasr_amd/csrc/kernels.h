@@ -287,6 +287,9 @@ void pad_logfloor(const Ctx& ctx, const float* packed, const long long* d_off, c
                   long long L);
 void pad_logfloor_dense(const Ctx& ctx, const float* feats, long long n_each, float* out, int B, long long L);
 void conv0_swoosh(const Ctx& ctx, const float* x, const float* w, const float* b, float* y, int B, int T, int F);
+// SwooshL (act 1) / SwooshR (act 2) of x[0 .. n) in the epilogues' lean form and in the library-log form it replaced (act.h), for
+// the bit comparison of the two
+void act_forms(const Ctx& ctx, const float* x, float* y_lean, float* y_libm, int act, long long n);
 // Conformer Conv2dSubsampling conv.0: 1->8 ch, 3x3, padding 1 in time and frequency, DoubleSwish; y: NHWC [B,T,F,8]
 void conv0_pad1_dswish(const Ctx& ctx, const float* x, const float* w, const float* b, float* y, int B, int T, int F);
 // depthwise 7x7 over [B,Tin,F,C] -> [B,Tout,F,C]; time taps read in[t + kt - tpad] (zero outside [0,Tin)).

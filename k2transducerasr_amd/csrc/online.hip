@@ -9,13 +9,12 @@
 //   per layer: cached_key [L, 32H] | cached_nonlin_attn [L, 3D/4] | cached_val1 [L, 12H] |
 //              cached_val2 [L, 12H] | cached_conv1 [D, K/2] | cached_conv2 [D, K/2]
 //   then embed_states [128, 3, 19].  processed_lens lives on the host (it is 16 x chunks).
+#include "act.h"
 #include "kernels.h"
 
 namespace k2hip {
 namespace {
 
-__device__ __forceinline__ float fast_softplus(float z) { return z > 15.f ? z : __logf(1.0f + __expf(z)); }
-__device__ __forceinline__ float swoosh_r(float v) { return fast_softplus(v - 1.0f) - 0.08f * v - 0.313261687f; }
 __device__ __forceinline__ float sigm(float s) { return 1.0f / (1.0f + __expf(-s)); }
 
 // ConvNeXt.streaming_forward in one pass over x (round 5; three launches before: this one, the cache update, a 2-D copy):
