@@ -279,6 +279,9 @@ int32_t k2hip_offline_stream_get_ctc_state(const k2hip_offline_stream_t* s, int3
  * The setting is per model handle and applies to every BATCH entry point (k2hip_offline_greedy*,
  * k2hip_offline_recognizer_get_results, submit/wait) and to the streaming step (k2hip_online_step); the single-stream
  * offline path stays greedy, and a CTC model (zipformer2ctc) keeps its own CTC search under either setting.
+ * "ctc_prefix_beam_search" (CTC models only; K2HIP_ERR_UNSUPPORTED for a transducer model): the batch entry points run the CTC prefix
+ * beam search with beam `beam` ("CTC prefix beam search with N-best" below) and k2hip_last_scores returns the scores; the single-stream
+ * path stays the collapse, and k2hip_online_step fails with K2HIP_ERR_INVALID while it is set (no stream changes).
  *
  * Streaming under modified_beam_search: after every k2hip_online_step a stream holds exactly what the offline search
  * (k2hip_beam_search, same tie-breaks) gives over ALL encoder frames the stream has produced so far -- its hypotheses live on
@@ -294,7 +297,7 @@ int32_t k2hip_offline_stream_get_ctc_state(const k2hip_offline_stream_t* s, int3
  * hypotheses).  With a hotword graph attached to the stream (k2hip_online_stream_set_hotwords, below) the same rule holds against
  * the BIASED offline search, and Tokens are revised from step to step more often (an unfinished match that led drops back): the
  * re-read contract above covers it. */
-int32_t k2hip_set_decoding_method(k2hip_model_t* model, const char* method /* "greedy_search" | "modified_beam_search" */,
+int32_t k2hip_set_decoding_method(k2hip_model_t* model, const char* method /* "greedy_search" | "modified_beam_search" | "ctc_prefix_beam_search" */,
                                   int32_t beam /* 1..8, ignored for greedy_search */);
 /* operator level: modified beam search over a host encoder_out [B,T',J]; scores [B] (optional) = log-prob of the
  * returned hypothesis */
@@ -462,7 +465,9 @@ int32_t k2hip_set_ngram_lm(k2hip_model_t* model, const k2hip_ngram_lm_t* lm, flo
  * synchronous entries k2hip_offline_recognizer_get_results, k2hip_online_step and k2hip_beam_search_chunk keep up to n alternatives
  * per stream, each with its token log-probs (token log-probs are recorded for the frames searched while n > 1; 0 for frames
  * searched before).  Needs modified_beam_search (K2HIP_ERR_INVALID under greedy_search, K2HIP_ERR_UNSUPPORTED for a CTC model), and
- * no submitted batch in flight.  While n > 1: the pipelined k2hip_offline_submit_* / k2hip_offline_wait return K2HIP_ERR_INVALID (they
+ * no submitted batch in flight.  A CTC model has alternatives under ctc_prefix_beam_search only (n <= its beam; UNSUPPORTED under its
+ * other two methods): k2hip_offline_recognizer_get_results then fills the offline streams' alternatives, and leaving that method sets n
+ * back to 1.  While n > 1: the pipelined k2hip_offline_submit_* / k2hip_offline_wait return K2HIP_ERR_INVALID (they
  * have one result per stream), and so does k2hip_offline_recognizer_get_result (the single-stream path is greedy search). */
 int32_t k2hip_set_nbest(k2hip_model_t* model, int32_t n /* 1..8 */);
 /* operator level: k2hip_beam_search that returns the list.  tokens / timestamps / token_log_probs [B][nbest][max_tokens],
@@ -544,6 +549,40 @@ int32_t k2hip_offline_ctc_align_from_samples(k2hip_model_t* model, const float* 
                                              const int32_t* stream_of, const int64_t* ids, const int32_t* lens, int32_t* timestamps,
                                              int32_t* end_frames, float* token_log_probs, float* total_logp, float* best_logp,
                                              int32_t max_tokens, int32_t* Tprime_out);
+/* ---- CTC prefix beam search with N-best (zipformer2ctc models) -------------------------------------------------------------------
+ * No reference counterpart: the reference's CTC path only does ForwardBatchGreedySearchCTC.  The semantics are the project's own,
+ * defined here, in DESIGN.md "CTC prefix beam search" and, as code, in csrc/ctc_prefix_ref.h.
+ * log_probs [R][Tprime][V] is what the encoder entries of a CTC model return; lp(t, v) is row r's entry.  Row r is searched over its
+ * first T = n_frames[r] frames (NULL = Tprime).  Blank is id 0; every other id, unk included, is an ordinary token, as in the CTC
+ * collapse and k2hip_ctc_align.
+ * A live hypothesis is a prefix y (a token sequence) with two float32 log-probs: pb (paths ending in blank) and pnb (paths ending in
+ * y's last token); tot = logaddexp(pb, pnb).  Start: the empty prefix with pb = 0, pnb = -inf.  At most `beam` (1..8) hypotheses are
+ * live, in slots 0 .. n-1; live prefixes are pairwise distinct AS TOKEN SEQUENCES.
+ * Frame t, live slots k with last token e_k (none for the empty prefix):
+ *   1. the stay candidate of slot k (flat index k V + 0): spb = tot_k + lp(t, 0); spnb = pnb_k + lp(t, e_k), -inf for the empty prefix.
+ *   2. the extension of slot k by v in 1 .. V-1: x = (v == e_k ? pb_k : tot_k) + lp(t, v).  If a live slot j spells y_k + [v], the
+ *      extension is folded into j's stay candidate, spnb_j = logaddexp(spnb_j, x), and is no candidate of its own (a slot receives at
+ *      most one fold per frame).  Otherwise it is the candidate k V + v with pb = -inf, pnb = x.
+ *   3. candidates whose total is -inf are dropped; the rest are ordered by total descending, exact float32 ties to the LOWER flat
+ *      index; the first `beam` become the new slots in rank order.  With no finite candidate, slot 0's stay candidate alone survives
+ *      and its scores stay -inf from then on.
+ *   4. a selected extension appends v: timestamp t, token log-prob lp(t, v) -- the input value itself, the convention of
+ *      k2hip_ctc_align.  A hypothesis that receives a fold keeps its own timestamps and token log-probs (the first-inserted rule).
+ * After the last frame the score of a hypothesis is its tot (no length normalisation); the slots are ordered by it; entry 0 is the
+ * result, the N-best the first min(nbest, live) slots.  All arithmetic is float32, logaddexp(a,b) = m + log1p(exp(min - m)); -inf
+ * operands give no NaN.
+ * PREFIX IDENTITY IS SEQUENCE IDENTITY.  "Slot j spells y_k + [v]" speaks of token sequences, not of history nodes: when a prefix P
+ * leaves the beam while its descendant P+w stays, P is later spelled again from its parent and that new P is extended by w, the
+ * extension folds into the old P+w -- two equal prefixes are never live together.
+ * Not covered: hotwords and the n-gram LM (ignored by this search), streaming, vocabulary pruning, length normalisation.
+ *
+ * k2hip_ctc_prefix_beam_search: operator level.  Output shapes and the K2HIP_ERR_CAPACITY rule are those of k2hip_beam_search_nbest
+ * (B = R).  K2HIP_ERR_UNSUPPORTED for a transducer model; K2HIP_ERR_INVALID for beam outside 1..8, nbest outside 1..beam, n_frames
+ * outside [1, Tprime] or R outside [1, 65535], decided on the host before any device work.  Independent of the model's decoding
+ * method and k2hip_set_nbest. */
+int32_t k2hip_ctc_prefix_beam_search(k2hip_model_t* model, const float* log_probs, int32_t R, int32_t Tprime, const int32_t* n_frames,
+                                     int32_t beam, int32_t nbest, int64_t* tokens, int32_t* timestamps, float* token_log_probs,
+                                     int32_t* n_tokens, int32_t* n_hyps, float* scores, int32_t max_tokens);
 /* Per stream.  num_alternatives: the count (>= 1; -1 for NULL, for online streams a negative error code under greedy_search).
  * get_alternative(i): tokens / timestamps / token_log_probs [cap] (each may be NULL), *n = its length, *score = its finalized
  * log-prob; K2HIP_ERR_CAPACITY if cap is too small (nothing is written), K2HIP_ERR_INVALID for i outside the list.

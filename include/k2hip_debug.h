@@ -110,6 +110,12 @@ int32_t k2hip_debug_gemm_run(k2hip_model_t* model, const float* A, const float* 
  *   "act_forms": ints act (1 SwooshL, 2 SwooshR), n; buffers x [n] (in), y_lean [n], y_libm [n] (out).  One plain elementwise
  *     kernel: y_lean = the activation as the GEMM epilogues and the elementwise kernels compute it (softplus_ge1), y_libm = the same
  *     with the library's general log (softplus_libm).  The two must agree bit for bit.
+ * The CTC prefix beam search's kernel alone (csrc/ctc_prefix.hip; tests/test_ctc_prefix_gpu.py):
+ *   "ctc_prefix_beam": buffers log_probs [R][Tp][V], n_frames [R] int32 (or null), then the outputs of k2hip_ctc_prefix_beam_search --
+ *     tokens [R][nbest][max_tokens] int64, timestamps (int32) and token_log_probs of the same shape, n_tokens [R][nbest] int32, n_hyps [R]
+ *     int32, scores [R][nbest] -- and flag [1] int32, the search-output block's status word (1: an entry outgrew max_tokens and was not
+ *     written); ints R, Tp, V, beam, nbest, max_tokens.  V here is free, not the model's.  The kernel stores straight into the guarded
+ *     buffers, so what it does not write keeps the caller's fill.
  * One op launches nothing (tests/test_search_ties_gpu.py):
  *   "greedy_screen_counts": no int arguments, one buffer of 2 int64 that the hook fills (whatever out_mask says) with the model's
  *     counters since it was created: [0] rounds of the persistent large-vocabulary greedy search (csrc/greedy.hip k_greedy) that its

@@ -485,6 +485,36 @@ class Model:
         self._chk(self._L.k2hip_ctc_greedy(self._h, _f(e), B, Tp, _i(fo), _l(tok), _i(ts), _i(n), Tp, _i(tb)))
         return self._unpack(tok, ts, n), tb
 
+    def ctc_prefix_beam_search(self, log_probs, beam: int = 4, n_frames=None, nbest: Optional[int] = None, want_scores: bool = False,
+                               want_token_log_probs: bool = False, max_tokens: Optional[int] = None):
+        """k2hip_ctc_prefix_beam_search over host log_probs [R,T',V] (what the encoder entries of a CTC model return); n_frames [R]: the
+        frames of each row that count (default: all T').  With nbest = N: per row a list of up to N alternatives in rank order, each a
+        dict(tokens, timestamps, token_log_probs, score); with want_token_log_probs alone the best one's dict per row; otherwise the
+        (tokens, timestamps) pairs of ctc_greedy, and the scores [R] behind them with want_scores."""
+        x = _f32(log_probs)
+        R, Tp, _ = x.shape
+        N = 1 if nbest is None else nbest
+        M, mt = max(N, 1), Tp if max_tokens is None else max_tokens
+        tok = np.zeros((R, M, max(mt, 1)), np.int64)
+        ts = np.zeros((R, M, max(mt, 1)), np.int32)
+        yp = np.zeros((R, M, max(mt, 1)), np.float32)
+        n = np.zeros((R, M), np.int32)
+        nh = np.zeros(R, np.int32)
+        sc = np.zeros((R, M), np.float32)
+        nf = None if n_frames is None else np.ascontiguousarray(n_frames, dtype=np.int32)
+        self._L.k2hip_ctc_prefix_beam_search.argtypes = [C.c_void_p, fp, C.c_int32, C.c_int32, ip, C.c_int32, C.c_int32, lp, ip, fp, ip, ip, fp,
+                                                         C.c_int32]
+        self._chk(self._L.k2hip_ctc_prefix_beam_search(self._h, _f(x), R, Tp, None if nf is None else _i(nf), beam, N, _l(tok), _i(ts), _f(yp),
+                                                       _i(n), _i(nh), _f(sc), mt))
+        out = [[dict(tokens=tok[r, i, : n[r, i]].tolist(), timestamps=ts[r, i, : n[r, i]].tolist(), token_log_probs=yp[r, i, : n[r, i]].copy(),
+                     score=float(sc[r, i])) for i in range(nh[r])] for r in range(R)]
+        if nbest is not None:
+            return out
+        if want_token_log_probs:
+            return [alts[0] for alts in out]
+        res = [(alts[0]["tokens"], alts[0]["timestamps"]) for alts in out]
+        return (res, sc[:, 0].copy()) if want_scores else res
+
     def set_nbest(self, n: int = 1):
         """k2hip_set_nbest: n > 1 makes the synchronous modified-beam-search entries keep up to n alternatives per stream, each with
         its token log-probs (streams' .alternatives() / .token_log_probs()); 1 = off"""
@@ -532,7 +562,8 @@ class Model:
         return dict(idx=tr[:, :, :k].copy(), val=tr[:, :, k: 2 * k].copy().view(np.float32), n=tr[:, :, 2 * k].copy(), beam=k)
 
     def set_decoding_method(self, method: str = "greedy_search", beam: int = 4):
-        """decodingMethod of the batch entry points (OfflineRecognizer.cs:54-68): greedy_search | modified_beam_search"""
+        """decodingMethod of the batch entry points (OfflineRecognizer.cs:54-68): greedy_search | modified_beam_search, and for a CTC
+        model ctc_prefix_beam_search (no reference counterpart; k2hip.h "CTC prefix beam search with N-best")"""
         self._chk(self._L.k2hip_set_decoding_method(self._h, method.encode(), beam))
 
     def set_hotwords(self, hotwords: Optional["Hotwords"] = None):
@@ -870,7 +901,8 @@ class OfflineStream:
 
 class OfflineRecognizer:
     """OfflineRecognizer.cs:12-91 on the HIP backend; decoding_method "greedy_search" (the reference's only method) or
-    "modified_beam_search" (BASELINE.json configs[2]).  hotwords: a Hotwords graph, or a list of token-id phrases scored
+    "modified_beam_search" (BASELINE.json configs[2]), or for a CTC model "ctc_prefix_beam_search" with beam / nbest (the streams then carry
+    .alternatives()).  hotwords: a Hotwords graph, or a list of token-id phrases scored
     hotwords_score per matched token (sherpa's hotwords_file / hotwords_score); it biases modified_beam_search only.  ngram_lm: an
     NgramLm fused with weight ngram_lm_scale (sherpa's lm / lm_scale), modified_beam_search only."""
 

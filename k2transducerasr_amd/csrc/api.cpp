@@ -783,14 +783,31 @@ int32_t k2hip_offline_stream_get_ctc_state(const k2hip_offline_stream_t* s, int3
 int32_t k2hip_set_decoding_method(k2hip_model_t* model, const char* method, int32_t beam) {
     return guard([&] {
         NEED(model); NEED(method);
-        EngineLock lk(model->engine);
+        Engine& e = model->engine;
+        EngineLock lk(e);
+        // leaving ctc_prefix_beam_search: a CTC model's other searches have no alternatives, so the N-best setting goes back to 1
+        auto leave_prefix = [&] {
+            if (e.ctc_prefix() == 0) return;
+            K2_REQUIRE(e.batches_in_flight() == 0, "set_decoding_method: %d submitted batches are in flight; wait for them first", e.batches_in_flight());
+            e.set_ctc_prefix(0);
+            e.set_nbest(0);
+            model->nbest = 1;
+        };
         if (!strcmp(method, "greedy_search")) {
-            model->engine.set_beam(0);
+            leave_prefix();
+            e.set_beam(0);
         } else if (!strcmp(method, "modified_beam_search")) {
             K2_REQUIRE(beam >= 1 && beam <= kMaxBeam, "modified_beam_search: beam %d out of range [1,%d]", beam, kMaxBeam);
-            model->engine.set_beam(beam);
+            leave_prefix();
+            e.set_beam(beam);
+        } else if (!strcmp(method, "ctc_prefix_beam_search")) {
+            if (!e.model().cfg().ctc)
+                failf(K2HIP_ERR_UNSUPPORTED, "ctc_prefix_beam_search: model_type '%s' has no CTC head", e.model().cfg().model_type.c_str());
+            K2_REQUIRE(beam >= 1 && beam <= kMaxBeam, "ctc_prefix_beam_search: beam %d out of range [1,%d]", beam, kMaxBeam);
+            K2_REQUIRE(e.nbest() <= beam, "ctc_prefix_beam_search: the model keeps %d alternatives (k2hip_set_nbest), more than beam %d", e.nbest(), beam);
+            e.set_ctc_prefix(beam);
         } else {
-            failf(K2HIP_ERR_UNSUPPORTED, "decoding method '%s' (have: greedy_search, modified_beam_search)", method);
+            failf(K2HIP_ERR_UNSUPPORTED, "decoding method '%s' (have: greedy_search, modified_beam_search, ctc_prefix_beam_search)", method);
         }
     });
 }
@@ -824,9 +841,12 @@ int32_t k2hip_set_nbest(k2hip_model_t* model, int32_t n) {
         NEED(model);
         K2_REQUIRE(n >= 1 && n <= kMaxBeam, "set_nbest: n = %d out of range [1,%d]", n, kMaxBeam);
         Engine& e = model->engine;
-        if (n > 1 && e.model().cfg().ctc) failf(K2HIP_ERR_UNSUPPORTED, "set_nbest: a CTC model has no beam search to take alternatives from");
         EngineLock lk(e);
-        K2_REQUIRE(n == 1 || e.beam() > 0, "set_nbest: alternatives come from modified_beam_search; the model decodes with greedy_search "
+        if (n > 1 && e.model().cfg().ctc && e.ctc_prefix() == 0)
+            failf(K2HIP_ERR_UNSUPPORTED, "set_nbest: a CTC model has no beam search to take alternatives from (ctc_prefix_beam_search has: "
+                                         "k2hip_set_decoding_method first)");
+        K2_REQUIRE(e.ctc_prefix() == 0 || n <= e.ctc_prefix(), "set_nbest: n = %d above the prefix search's beam %d", n, e.ctc_prefix());
+        K2_REQUIRE(n == 1 || e.beam() > 0 || e.ctc_prefix() > 0, "set_nbest: alternatives come from modified_beam_search; the model decodes with greedy_search "
                                            "(k2hip_set_decoding_method first)");
         K2_REQUIRE(e.batches_in_flight() == 0, "set_nbest: %d submitted batches are in flight; wait for them first", e.batches_in_flight());
         e.set_nbest(n > 1 ? n : 0);
@@ -903,6 +923,19 @@ int32_t k2hip_beam_search_nbest(k2hip_model_t* model, const float* enc_out, int3
                 scores[en] = h.scores[en];
             }
         }
+    });
+}
+// CTC prefix beam search, operator level: the engine checks the arguments on the host before any device work (ctc_prefix_ref.h)
+int32_t k2hip_ctc_prefix_beam_search(k2hip_model_t* model, const float* log_probs, int32_t R, int32_t Tprime, const int32_t* n_frames, int32_t beam,
+                                     int32_t nbest, int64_t* tokens, int32_t* timestamps, float* token_log_probs, int32_t* n_tokens,
+                                     int32_t* n_hyps, float* scores, int32_t max_tokens) {
+    return guard([&] {
+        NEED(model); NEED(log_probs); NEED(tokens); NEED(timestamps); NEED(token_log_probs); NEED(n_tokens); NEED(n_hyps); NEED(scores);
+        Engine& e = model->engine;
+        if (!e.model().cfg().ctc)
+            failf(K2HIP_ERR_UNSUPPORTED, "ctc_prefix_beam_search: model_type '%s' has no CTC head", e.model().cfg().model_type.c_str());
+        EngineLock lk(e);
+        e.ctc_prefix_host(log_probs, R, Tprime, n_frames, beam, nbest, tokens, timestamps, token_log_probs, n_tokens, n_hyps, scores, max_tokens);
     });
 }
 // forced alignment / full-sum scoring: the engine checks the targets on the host before any device work (lattice_ref.h)
@@ -1285,6 +1318,11 @@ int32_t k2hip_online_step(k2hip_model_t* model, k2hip_online_stream_t* const* st
         Engine& e = model->engine;
         const Config& c = e.model().cfg();
         K2_REQUIRE(c.streaming || c.lstm, "this model is not a streaming export");
+        if (c.ctc) {   // (before any stream is looked at: nothing changes)
+            EngineLock lk(e);
+            K2_REQUIRE(e.ctc_prefix() == 0, "online step: the decoding method is ctc_prefix_beam_search (beam %d), which covers the offline "
+                       "entries only -- set greedy_search for streaming", e.ctc_prefix());
+        }
         const size_t chunk_floats = (size_t)c.chunk_T * c.feat, shift_floats = (size_t)c.shift * c.feat;
         uint64_t lm_serial = 0;   // the n-gram LM this tick's beam search runs with (0 = none) and its start state
         int lm_start = 0;
@@ -2037,7 +2075,7 @@ int32_t k2hip_offline_recognizer_get_results(k2hip_model_t* model, k2hip_offline
         for (int b = 0; b < B; b++) streams[b]->alts.assign(1, BeamAlt{});   // (a failed call leaves the start state)
         {
             EngineLock lk(e);
-            K2_REQUIRE(e.nbest() == 0 || e.beam() > 0, "GetResults: the model keeps %d alternatives (k2hip_set_nbest) but decodes with "
+            K2_REQUIRE(e.nbest() == 0 || e.beam() > 0 || e.ctc_prefix() > 0, "GetResults: the model keeps %d alternatives (k2hip_set_nbest) but decodes with "
                        "greedy_search, which has none", e.nbest());
             if (from_samples) e.offline_greedy_samples(ptrs.data(), nfl.data(), B, tok.data(), ts.data(), n.data(), max_tokens, false, /*pinned_src=*/true);
             else e.offline_greedy_feats(ptrs.data(), nfl.data(), B, false, tok.data(), ts.data(), n.data(), max_tokens);

@@ -1,0 +1,263 @@
+// CTC prefix beam search with N-best (semantics: include/k2hip.h, DESIGN.md "CTC prefix beam search"; host reference, THE fold rule
+// and THE tie rule: ctc_prefix_ref.h).
+//
+//   k_ctc_prefix   one workgroup of 256 per row, frames sequential.  The live hypotheses (at most 8 slots: pb, pnb, tot, last token,
+//                  length, history node, rolling hashes) ping-pong in LDS.  Per frame:
+//                    candidates   the threads stride over the columns v; a thread forms the candidates of its columns for every slot
+//                                 from the slots' (pb, tot, e) held in registers and keeps its best `beam` in a sorted register list;
+//                                 thread k < n also forms slot k's stay candidate (with the fold it receives).  Columns named by the
+//                                 frame's fold table (slot j spells slot k + [e_j]: at most `beam` pairs) are skipped for slot k.
+//                    selection    `beam` rounds of wave_best take every wave's winners in rank order (no barrier), one barrier, then
+//                                 every wave repeats the rounds over the 4 x beam wave winners -- the workgroup's winners in rank
+//                                 order, known to every lane.  The order is (total desc, flat index k V + v asc) throughout.
+//                    update       thread r builds slot r of the other parity; an extension appends a node (parent, token, frame,
+//                                 lp(t, v)) to the row's pool at t * beam + r.
+//                    fold table   for the next frame, 64 threads, one per (j, k): length, rolling hash of the prefix without its last
+//                                 token as the filter, then the confirmation: the two parent chains are walked until the node ids
+//                                 coincide (zero steps when j was extended from k's node), comparing tokens.  Sequence identity, not
+//                                 node identity: a prefix that left the beam and was spelled again has another node.
+//                  The first 256 columns of frame t + 1 are requested before frame t's work.  After the last frame every surviving
+//                  slot's chain is walked back into its output row from index len - 1 down.
+// No workgroup waits for another; every loop is bounded by T, beam or a hypothesis length; all stores are ordinary vector stores.
+#include <climits>
+
+#include "kernels.h"
+#include "wave_best.h"
+
+namespace k2hip {
+namespace {
+
+constexpr int PT = 256, PW = PT / 64;   // threads / waves of the workgroup
+constexpr int KB = kMaxBeam;
+
+__device__ __forceinline__ float ninf() { return -__builtin_inff(); }
+
+// logaddexp(a, b) = m + log1p(exp(min - m)); -inf operands never make a NaN
+__device__ __forceinline__ float logaddexp_f(float a, float b) {
+    const float m = fmaxf(a, b), n = fminf(a, b);
+    if (n == ninf()) return m;
+    return m + log1pf(expf(n - m));
+}
+
+// the live hypotheses of one frame parity
+struct Slots {
+    float pb[KB], pnb[KB], tot[KB];
+    int e[KB], len[KB], node[KB], pnode[KB];   // last token (-1: the empty prefix), length, history node and its parent (-1: none)
+    unsigned long long hash[KB], phash[KB];    // rolling hash of the prefix / of the prefix without its last token
+    int n;
+};
+constexpr unsigned long long kHashSeed = 0x243F6A8885A308D3ull, kHashMul = 0x9E3779B97F4A7C15ull;
+
+__global__ __launch_bounds__(PT) void k_ctc_prefix(CtcPrefixArgs a) {
+    __shared__ Slots sl[2];
+    __shared__ float stay_pb[KB], stay_pnb[KB];
+    __shared__ int fold_par[KB];   // slot j -> the slot k whose extension by e_j spells j, or -1
+    __shared__ float wl_v[PW][KB];
+    __shared__ int wl_i[PW][KB];
+    const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int V = a.V, beam = a.beam;
+    const int T = min(max(a.n_frames ? a.n_frames[r] : a.Tp, 0), a.Tp);
+    const float* lp = a.log_probs + (long long)r * a.Tp * V;
+    int4* nodes = a.nodes + (long long)r * a.Tp * beam;
+    if (tid == 0) {
+        Slots& s = sl[0];
+        s.pb[0] = 0.f; s.pnb[0] = ninf(); s.tot[0] = 0.f;
+        s.e[0] = -1; s.len[0] = 0; s.node[0] = -1; s.pnode[0] = -1;
+        s.hash[0] = kHashSeed; s.phash[0] = 0;
+        s.n = 1;
+        fold_par[0] = -1;
+    }
+    float px = T > 0 && tid < V ? lp[tid] : ninf();
+    __syncthreads();
+    for (int t = 0; t < T; t++) {
+        const Slots& c = sl[t & 1];
+        Slots& nx = sl[(t + 1) & 1];
+        const float* row = lp + (long long)t * V;
+        const float cx = px;
+        if (t + 1 < T && tid < V) px = row[V + tid];   // the next frame's first chunk, before this frame's barriers
+        const int n = c.n;
+        float s_pb[KB], s_tot[KB];
+        int s_e[KB], s_fp[KB];
+#pragma unroll
+        for (int k = 0; k < KB; k++) {
+            const bool live = k < n;
+            s_pb[k] = live ? c.pb[k] : ninf();
+            s_tot[k] = live ? c.tot[k] : ninf();
+            s_e[k] = live ? c.e[k] : -1;
+            s_fp[k] = live ? fold_par[k] : -1;
+        }
+        // the thread's best `beam` candidates, sorted by (total desc, flat index asc); index < 0 = none
+        float lv[KB];
+        int li[KB];
+#pragma unroll
+        for (int s = 0; s < KB; s++) { lv[s] = ninf(); li[s] = -1; }
+        auto insert = [&](float v, int i) {
+#pragma unroll
+            for (int s = 0; s < KB; s++)
+                if (s < beam && i >= 0 && (li[s] < 0 || v > lv[s] || (v == lv[s] && i < li[s]))) {
+                    const float tv = lv[s]; const int ti = li[s];
+                    lv[s] = v; li[s] = i;
+                    v = tv; i = ti;
+                }
+        };
+        if (tid < n) {   // the stay candidate of slot tid, with the fold it receives
+            const int k = tid, e = c.e[k];
+            const float lpe = e >= 0 ? row[e] : ninf();
+            const float spb = c.tot[k] + row[0];
+            float spnb = e >= 0 ? c.pnb[k] + lpe : ninf();
+            const int p = fold_par[k];
+            if (p >= 0) spnb = logaddexp_f(spnb, (e == c.e[p] ? c.pb[p] : c.tot[p]) + lpe);
+            const float st = logaddexp_f(spb, spnb);
+            stay_pb[k] = spb;
+            stay_pnb[k] = spnb;
+            if (st > ninf()) insert(st, k * V);
+        }
+        for (int v0 = 0; v0 < V; v0 += PT) {
+            const int v = v0 + tid;
+            if (v >= 1 && v < V) {
+                const float xl = v0 == 0 ? cx : row[v];
+                unsigned kill = 0;   // bit k: slot k + [v] is a live slot, the extension joined that slot's stay candidate
+#pragma unroll
+                for (int j = 0; j < KB; j++)
+                    if (s_fp[j] >= 0 && s_e[j] == v) kill |= 1u << s_fp[j];
+#pragma unroll
+                for (int k = 0; k < KB; k++) {
+                    const float x = (v == s_e[k] ? s_pb[k] : s_tot[k]) + xl;
+                    if (k < n && !(kill >> k & 1u) && x > ninf()) insert(x, k * V + v);
+                }
+            }
+        }
+        // every wave's winners in rank order
+#pragma unroll
+        for (int q = 0; q < KB; q++)
+            if (q < beam) {
+                float bv = lv[0];
+                int bi = li[0];
+                wave_best(bv, bi);
+                if (bi >= 0 && li[0] == bi) {
+#pragma unroll
+                    for (int s = 0; s + 1 < KB; s++) { lv[s] = lv[s + 1]; li[s] = li[s + 1]; }
+                    li[KB - 1] = -1;
+                }
+                if (lane == 0) { wl_v[wave][q] = bv; wl_i[wave][q] = bi; }
+            }
+        __syncthreads();
+        // the workgroup's winners in rank order, in every lane of every wave
+        float mv = ninf();
+        int mi = -1;
+        if (lane < PW * KB && (lane & (KB - 1)) < beam) {
+            mv = wl_v[lane / KB][lane & (KB - 1)];
+            mi = wl_i[lane / KB][lane & (KB - 1)];
+        }
+        float win_v = ninf();
+        int win_i = -1, m = 0;
+#pragma unroll
+        for (int q = 0; q < KB; q++)
+            if (q < beam) {
+                float bv = mv;
+                int bi = mi;
+                wave_best(bv, bi);
+                if (bi >= 0) {
+                    if (mi == bi) mi = -1;
+                    if (tid == q) { win_v = bv; win_i = bi; }
+                    m++;
+                }
+            }
+        // thread q builds slot q of the other parity (no finite candidate: slot 0 stays, its scores -inf from then on)
+        if (tid < max(m, 1)) {
+            int k = 0, v = 0;
+            float pb = ninf(), pnb = ninf(), tot = ninf();
+            if (m > 0) {
+                k = win_i / V;
+                v = win_i - k * V;
+                tot = win_v;
+                pb = v ? ninf() : stay_pb[k];
+                pnb = v ? win_v : stay_pnb[k];
+            }
+            nx.pb[tid] = pb; nx.pnb[tid] = pnb; nx.tot[tid] = tot;
+            if (v == 0) {
+                nx.e[tid] = c.e[k]; nx.len[tid] = c.len[k]; nx.node[tid] = c.node[k]; nx.pnode[tid] = c.pnode[k];
+                nx.hash[tid] = c.hash[k]; nx.phash[tid] = c.phash[k];
+            } else {
+                const int id = t * beam + tid;   // < T * beam <= Tp * beam: inside the row's pool
+                nodes[id] = make_int4(c.node[k], v, t, __float_as_int(row[v]));
+                nx.e[tid] = v; nx.len[tid] = c.len[k] + 1; nx.node[tid] = id; nx.pnode[tid] = c.node[k];
+                nx.phash[tid] = c.hash[k];
+                nx.hash[tid] = c.hash[k] * kHashMul + (unsigned long long)(v + 1);
+            }
+            fold_par[tid] = -1;
+        }
+        if (tid == 0) nx.n = max(m, 1);
+        __syncthreads();
+        // the next frame's fold table: does slot j spell slot k + [e_j]?  (live prefixes are distinct: at most one k per j)
+        if (tid < KB * KB) {
+            const int j = tid / KB, k = tid & (KB - 1), n2 = nx.n;
+            if (j < n2 && k < n2 && j != k && nx.len[j] == nx.len[k] + 1 && nx.phash[j] == nx.hash[k]) {
+                int p = nx.pnode[j], q = nx.node[k];
+                bool same = true;
+                while (p != q) {   // equal lengths: both chains end at -1 together; every step shortens both
+                    if (p < 0 || q < 0) { same = false; break; }
+                    const int4 np = nodes[p], nq = nodes[q];
+                    if (np.y != nq.y) { same = false; break; }
+                    p = np.x;
+                    q = nq.x;
+                }
+                if (same) fold_par[j] = k;
+            }
+        }
+        __syncthreads();
+    }
+    const Slots& f = sl[T & 1];
+    const int n = f.n;
+    // a slot's chain walked back into a row, from index len - 1 down
+    auto write_chain = [&](int q, long long* tok, int* ts, float* yp, long long o) {
+        int node = f.node[q];
+        for (int i = f.len[q] - 1; i >= 0 && node >= 0; i--) {
+            const int4 nd = nodes[node];
+            tok[o + i] = nd.y;
+            ts[o + i] = nd.z;
+            if (yp) yp[o + i] = __int_as_float(nd.w);
+            node = nd.x;
+        }
+    };
+    if (tid == 64) {   // the single result: slot 0
+        const int len = f.len[0];
+        if (len > a.max_tokens) {
+            *a.overflow = 1;
+            a.n_tokens[r] = 0;
+        } else {
+            write_chain(0, a.tokens, a.timestamps, nullptr, (long long)r * a.max_tokens);
+            a.n_tokens[r] = len;
+        }
+        if (a.scores) a.scores[r] = f.tot[0];
+    }
+    if (a.nb.tokens && tid < KB) {
+        const int nh = min(n, a.nb.nbest), q = tid;
+        if (q < nh) {
+            const long long en = (long long)r * a.nb.nbest + q;
+            const int len = f.len[q];
+            if (len > a.max_tokens) {   // (the single result's rule, per entry)
+                *a.overflow = 1;
+                a.nb.n_tokens[en] = 0;
+            } else {
+                write_chain(q, a.nb.tokens, a.nb.timestamps, a.nb.token_log_probs, en * a.max_tokens);
+                a.nb.n_tokens[en] = len;
+            }
+            a.nb.scores[en] = f.tot[q];
+        }
+        if (tid == 0) a.nb.n_hyps[r] = nh;
+    }
+}
+
+}  // namespace
+
+void ctc_prefix_search(const Ctx& ctx, const CtcPrefixArgs& a) {
+    if (ctx.dry) return;
+    K2_REQUIRE(a.R >= 1 && a.R <= 65535 && a.Tp >= 1 && a.V >= 1 && (long long)kMaxBeam * a.V <= INT_MAX && a.beam >= 1 && a.beam <= kMaxBeam &&
+                   a.max_tokens >= 1 && (!a.nb.tokens || (a.nb.nbest >= 1 && a.nb.nbest <= a.beam)),
+               "ctc_prefix_search: bad shape R=%d T'=%d V=%d beam=%d nbest=%d max_tokens=%d", a.R, a.Tp, a.V, a.beam, a.nb.nbest, a.max_tokens);
+    hipLaunchKernelGGL(k_ctc_prefix, dim3(a.R), dim3(PT), 0, ctx.stream, a);
+    K2_HIP(hipGetLastError());
+}
+
+}  // namespace k2hip

@@ -4,6 +4,7 @@
 #include "engine.h"
 #include "lattice_ref.h"
 #include "ctc_lattice_ref.h"
+#include "ctc_prefix_ref.h"
 
 #include <climits>
 #include <cmath>
@@ -648,7 +649,15 @@ Engine::SearchExtras Engine::search_device(const Ctx& c, const float* enc, int B
 }
 
 Engine::SearchExtras Engine::greedy_device(const Ctx& c, const float* enc, int B, int Tp, bool single, const SearchOut& out, bool keep_nbest) {
-    if (model_->cfg().ctc) return ctc_device(c, enc, B, Tp, out);
+    if (model_->cfg().ctc) {
+        if (ctc_prefix_ == 0 || single) return ctc_device(c, enc, B, Tp, out);
+        SearchExtras ex = ctc_prefix_device(c, enc, B, Tp, model_->cfg().V, nullptr, ctc_prefix_, out, keep_nbest);
+        // the collapse's by-products (NumTrailingBlank bookkeeping) stay the first-argmax rule's: the collapse runs into a block of its own
+        const SearchExtras gx = ctc_device(c, enc, B, Tp, SearchOut(*c.arena, B, out.max_tokens));
+        ex.trail = gx.trail;
+        ex.any = gx.any;
+        return ex;
+    }
     if (beam_ > 0 && !single) return beam_device(c, enc, B, Tp, out, keep_nbest);
     const Config& cf = model_->cfg();
     Arena& ar = *c.arena;
@@ -696,6 +705,79 @@ Engine::SearchExtras Engine::ctc_device(const Ctx& c, const float* logp, int B, 
     argmax_first_rows(c, logp, cf.V, B * Tp, cf.V, tok);
     ctc_collapse(c, tok, B, Tp, nullptr, out.tokens(), out.timestamps(), out.counts(), out.max_tokens, ex.trail, ex.any, out.flag());
     return ex;
+}
+
+// CTC prefix beam search instead of the collapse (set_ctc_prefix(K) selects it for the batch entries; ctc_prefix.hip)
+static_assert(kCtcPrefixMaxBeam == kMaxBeam, "the kernel's and the host reference's beam limit are one number");
+Engine::SearchExtras Engine::ctc_prefix_device(const Ctx& c, const float* logp, int R, int Tp, int V, const int32_t* n_frames, int beam,
+                                               const SearchOut& out, bool keep_nbest) {
+    Arena& ar = *c.arena;
+    CtcPrefixArgs a;
+    a.log_probs = logp; a.R = R; a.Tp = Tp; a.V = V; a.beam = beam;
+    a.nodes = ar.take<int4>((int64_t)R * Tp * beam);
+    a.tokens = out.tokens(); a.timestamps = out.timestamps(); a.n_tokens = out.counts(); a.max_tokens = out.max_tokens; a.overflow = out.flag();
+    SearchExtras ex;
+    ex.scores = ar.take<float>(R);
+    a.scores = ex.scores;
+    if (n_frames) {
+        int* d_nf = ar.take<int>(R);
+        if (!c.dry) K2_HIP(hipMemcpyAsync(d_nf, n_frames, sizeof(int) * (size_t)R, hipMemcpyHostToDevice, c.stream));
+        a.n_frames = d_nf;
+    }
+    if (nbest_ > 0 && keep_nbest) {
+        const int64_t NB = (int64_t)R * nbest_;
+        ex.nb.nbest = nbest_;
+        ex.nb.tokens = ar.take<long long>(NB * out.max_tokens);
+        ex.nb.timestamps = ar.take<int>(NB * out.max_tokens);
+        ex.nb.token_log_probs = ar.take<float>(NB * out.max_tokens);
+        ex.nb.n_tokens = ar.take<int>(NB);
+        ex.nb.scores = ar.take<float>(NB);
+        ex.nb.n_hyps = ar.take<int>(R);
+        a.nb = ex.nb;
+    }
+    if (!c.dry) K2_HIP(hipMemsetAsync(out.flag(), 0, sizeof(int), c.stream));
+    ctc_prefix_search(c, a);
+    return ex;
+}
+
+void Engine::ctc_prefix_host(const float* log_probs, int R, int Tp, const int32_t* n_frames, int beam, int nbest, int64_t* tokens, int32_t* timestamps,
+                             float* token_log_probs, int32_t* n_tokens, int32_t* n_hyps, float* scores, int max_tokens) {
+    const Config& cf = model_->cfg();
+    if (!cf.ctc) failf(K2HIP_ERR_UNSUPPORTED, "ctc_prefix_beam_search: model_type '%s' has no CTC head", cf.model_type.c_str());
+    K2_REQUIRE(log_probs && tokens && timestamps && token_log_probs && n_tokens && n_hyps && scores, "ctc_prefix_beam_search: null argument");
+    ctc_prefix_check_args(R, Tp, cf.V, n_frames, beam, nbest, max_tokens);
+    struct Restore {
+        int& slot; int old;
+        ~Restore() { slot = old; }
+    } restore{nbest_, nbest_};
+    nbest_ = nbest;
+    SearchOut out;
+    SearchExtras ex;
+    run_sized([&](const Ctx& c) {
+        float* d_lp = c.arena->take<float>((int64_t)R * Tp * cf.V);
+        out = SearchOut(*c.arena, R, max_tokens);
+        if (!c.dry) K2_HIP(hipMemcpyAsync(d_lp, log_probs, sizeof(float) * (size_t)R * Tp * cf.V, hipMemcpyHostToDevice, c.stream));
+        ex = ctc_prefix_device(c, d_lp, R, Tp, cf.V, n_frames, beam, out, true);
+    });
+    // (the single result goes to scratch: entry 0 of the list is that result)
+    std::vector<int64_t> tok1((size_t)R * max_tokens);
+    std::vector<int32_t> ts1((size_t)R * max_tokens), n1((size_t)R);
+    finish_tokens(out, ex, tok1.data(), ts1.data(), n1.data());
+    const NbestHost& h = last_nbest_;
+    K2_REQUIRE(h.B == R && h.N == nbest && h.max_tokens == max_tokens, "internal: the prefix search kept no N-best");
+    for (int r = 0; r < R; r++) {
+        n_hyps[r] = h.n_hyps[(size_t)r];
+        for (int i = 0; i < h.n_hyps[(size_t)r]; i++) {
+            const size_t en = (size_t)r * nbest + i, o = en * max_tokens, len = (size_t)h.n_tokens[en];
+            if (len) {
+                memcpy(tokens + o, h.tokens.data() + o, sizeof(int64_t) * len);
+                memcpy(timestamps + o, h.timestamps.data() + o, sizeof(int32_t) * len);
+                memcpy(token_log_probs + o, h.token_log_probs.data() + o, sizeof(float) * len);
+            }
+            n_tokens[en] = (int32_t)len;
+            scores[en] = h.scores[en];
+        }
+    }
 }
 
 // modified beam search instead of the greedy loop (set_beam(K) selects it for the fused / operator entry points)
@@ -2215,6 +2297,39 @@ void Engine::debug_op_host(const char* op, const int64_t* iargs, int n_iargs, vo
             K2_REQUIRE(n >= 0 && x && y_lean && y_libm && buf_bytes[0] >= 4 * n && buf_bytes[1] >= 4 * n && buf_bytes[2] >= 4 * n,
                        "debug_op_run act_forms: three buffers of n = %lld floats are needed", n);
             act_forms(c, x, y_lean, y_libm, act, n);
+        } else if (name == "ctc_prefix_beam") {
+            // bufs log_probs [R][Tp][V], n_frames [R] int32 (or null), tokens [R][nbest][max_tokens] int64, timestamps (int32), token_log_probs
+            //   [R][nbest][max_tokens], n_tokens [R][nbest] int32, n_hyps [R] int32, scores [R][nbest], flag [1] int32 (out); ints R, Tp, V, beam,
+            //   nbest, max_tokens.  The kernel stores straight into the guarded buffers.
+            K2_REQUIRE(n_bufs == 9, "debug_op_run %s: %d buffers", op, n_bufs);
+            for (int k = 0; k < n_bufs; k++) P();
+            const int R = I(), Tp = I(), V = I(), beam = I(), nbest = I(), max_tokens = I();
+            K2_REQUIRE(!bufs[1] || buf_bytes[1] >= 4 * (int64_t)R, "debug_op_run %s: n_frames is too short", op);
+            ctc_prefix_check_args(R, Tp, V, static_cast<const int32_t*>(bufs[1]), beam, nbest, max_tokens);
+            const int64_t NB = (int64_t)R * nbest;
+            K2_REQUIRE(dev[0] && buf_bytes[0] >= 4 * (int64_t)R * Tp * V, "debug_op_run %s: log_probs is too short", op);
+            K2_REQUIRE(dev[2] && dev[3] && dev[4] && dev[5] && dev[6] && dev[7] && dev[8] && buf_bytes[2] >= 8 * NB * max_tokens &&
+                           buf_bytes[3] >= 4 * NB * max_tokens && buf_bytes[4] >= 4 * NB * max_tokens && buf_bytes[5] >= 4 * NB && buf_bytes[6] >= 4 * (int64_t)R &&
+                           buf_bytes[7] >= 4 * NB && buf_bytes[8] >= 4,
+                       "debug_op_run %s: the result buffers are too short", op);
+            CtcPrefixArgs a;
+            a.log_probs = static_cast<const float*>(dev[0]); a.R = R; a.Tp = Tp; a.V = V; a.beam = beam;
+            a.n_frames = static_cast<const int*>(dev[1]);
+            a.nb.nbest = nbest;
+            a.nb.tokens = static_cast<long long*>(dev[2]); a.nb.timestamps = static_cast<int*>(dev[3]);
+            a.nb.token_log_probs = static_cast<float*>(dev[4]); a.nb.n_tokens = static_cast<int*>(dev[5]);
+            a.nb.n_hyps = static_cast<int*>(dev[6]); a.nb.scores = static_cast<float*>(dev[7]);
+            SearchOut out;
+            run_sized([&](const Ctx& cc) {
+                out = SearchOut(*cc.arena, R, max_tokens);
+                a.nodes = cc.arena->take<int4>((int64_t)R * Tp * beam);
+                a.scores = cc.arena->take<float>(R);
+                a.tokens = out.tokens(); a.timestamps = out.timestamps(); a.n_tokens = out.counts(); a.max_tokens = max_tokens; a.overflow = out.flag();
+                if (!cc.dry) K2_HIP(hipMemsetAsync(out.flag(), 0, sizeof(int), cc.stream));
+                ctc_prefix_search(cc, a);
+            });
+            K2_HIP(hipStreamSynchronize(stream_));
+            K2_HIP(copy_blocking(dev[8], out.flag(), 4, hipMemcpyDeviceToDevice));
         } else if (name == "basicnorm") {
             float *x = P(), *le = P(), *y = P();
             const int M = I(), D = I();

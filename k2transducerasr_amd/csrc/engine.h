@@ -95,6 +95,16 @@ class Engine {
     void ctc_align_samples(const float* const* samples, const int64_t* n_samples, int B, int H, const int32_t* stream_of, const int64_t* ids,
                            const int32_t* lens, int32_t* timestamps, int32_t* end_frames, float* token_log_probs, float* total, float* best,
                            int max_tokens, int32_t* Tp_out);
+    // ---- CTC prefix beam search with N-best (ctc_prefix.hip; semantics in include/k2hip.h) ----
+    // log_probs [R][Tp][V] on the host; n_frames [R] or null (= Tp).  tokens / timestamps / token_log_probs [R][nbest][max_tokens],
+    // n_tokens / scores [R][nbest], n_hyps [R]: the shapes of k2hip_beam_search_nbest.  The arguments are checked on the host before
+    // any device work (ctc_prefix_ref.h); the engine's decoding method and N-best setting are not affected.
+    void ctc_prefix_host(const float* log_probs, int R, int Tp, const int32_t* n_frames, int beam, int nbest, int64_t* tokens, int32_t* timestamps,
+                         float* token_log_probs, int32_t* n_tokens, int32_t* n_hyps, float* scores, int max_tokens);
+    // decoding method of a CTC model's batch entries: 0 = the reference's argmax-and-collapse, K >= 1 = the prefix beam search with beam K
+    // (the single-stream path always collapses)
+    void set_ctc_prefix(int k) { ctc_prefix_ = k; }
+    int ctc_prefix() const { return ctc_prefix_; }
     // ---- fused paths ----
     void offline_greedy_feats(const float* const* feats, const int64_t* n_floats, int B, bool single, int64_t* tokens,
                               int32_t* ts, int32_t* n_tokens, int max_tokens);
@@ -321,6 +331,10 @@ class Engine {
     size_t pp_cache_bytes_ = 0;
     SearchExtras ctc_device(const Ctx& c, const float* logp, int B, int Tp, const SearchOut& out);
     SearchExtras beam_device(const Ctx& c, const float* enc, int B, int Tp, const SearchOut& out, bool keep_nbest);
+    // the prefix beam search over logp [R][Tp][V] (device; V is the call's): the best hypothesis into `out`, scores in ex.scores, and --
+    // with keep_nbest and set_nbest(n > 0) -- the first n slots in ex.nb.  n_frames: host [R] or null.
+    SearchExtras ctc_prefix_device(const Ctx& c, const float* logp, int R, int Tp, int V, const int32_t* n_frames, int beam, const SearchOut& out,
+                                   bool keep_nbest);
     // hw (device pointers) or null: the unbiased search, today's launch
     void beam_resume_device(const Ctx& c, const float* enc, int B, int Tp, int K, const int* d_in, int* d_out, int* d_overflow,
                             const BeamHwIO* hw = nullptr);
@@ -415,6 +429,7 @@ class Engine {
     std::map<int, float*> pe_cache_;
     bool instrument_ = false;
     int beam_ = 0;
+    int ctc_prefix_ = 0;
     int nbest_ = 0;
     float *yp_host_ = nullptr, *d_yp_ = nullptr;
     size_t yp_floats_ = 0;

@@ -731,6 +731,25 @@ constexpr int kCtcAlignMaxTokens = 4095;   // = kCtcAlignMaxU of ctc_lattice_ref
 // (logaddexp) and Viterbi (max, the lowest state index wins ties) over the reachable band, two back-pointer bits per cell, backtrace
 void ctc_lattice(const Ctx& ctx, const CtcAlignArgs& a);
 
+// ---- CTC prefix beam search with N-best (ctc_prefix.hip; semantics in include/k2hip.h and ctc_prefix_ref.h) ----
+struct CtcPrefixArgs {
+    const float* log_probs = nullptr;   // [R, Tp, V], log-softmaxed
+    int R = 0, Tp = 0, V = 0;           // V is the call's (the debug op runs other vocabularies than the model's)
+    const int* n_frames = nullptr;      // [R] (device) or null = Tp for every row
+    int beam = 0;                       // 1 .. kMaxBeam
+    int4* nodes = nullptr;              // history pool [R][Tp * beam]: (parent, token, frame, token log-prob bits); parent -1 = the empty prefix
+    // the best hypothesis of every row (the search-output block) and its score
+    long long* tokens = nullptr;        // [R][max_tokens]
+    int* timestamps = nullptr;          // [R][max_tokens]
+    int* n_tokens = nullptr;            // [R]
+    float* scores = nullptr;            // [R]
+    int max_tokens = 0;
+    int* overflow = nullptr;            // set to 1 when a written entry is longer than max_tokens (that entry is not written)
+    BeamNbest nb;                       // tokens == null: off; else the first min(nb.nbest, live) slots in rank order
+};
+// One workgroup of 256 per row, frames sequential, no workgroup waits for another; every store is an ordinary vector store
+void ctc_prefix_search(const Ctx& ctx, const CtcPrefixArgs& a);
+
 // ---- streaming (online.hip): device-resident per-stream caches indexed by slot ------------------
 // ConvNeXt.streaming_forward's data movement in one launch: cat[b] = [cached_left_pad ; x], the cache advanced to x's frames Tc-3 .. Tc-1,
 // byp[b] = x[b, :Tc] (the bypass operand)
