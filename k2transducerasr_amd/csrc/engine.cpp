@@ -337,18 +337,34 @@ const float* Engine::pos_proj_cached(const Ctx& c, int layer, const float* pe, i
 }
 
 // ---------------------------------------------------------------------------
-// Zipformer2EncoderLayer.forward (inference), in place on x [B*T, D]
+// Zipformer2EncoderLayer.forward / .streaming_forward (inference), in place on x [B*T, D]; gl = global layer index.
+// site == null: T frames of whole utterances.  Otherwise the streams' chunk of T frames behind cf.left[si] frames of left context: the
+// attention weights run over the key ring, NonlinAttention and the self-attention modules over their value rings, the depthwise
+// convolution is the chunk-causal one over the conv cache (slot layout: lay_, indexed by gl).  The launch skeleton is the same.
 // ---------------------------------------------------------------------------
-void Engine::encoder_layer(const Ctx& c, int si, int li, float* x, const float* pe, int B, int T, const LayerTail* tail) {
+void Engine::encoder_layer(const Ctx& c, int si, int li, int gl, float* x, const float* pe, int B, int T, const StreamSite* site,
+                           const LayerTail* tail) {
     const Model& m = *model_;
     const Config& cf = m.cfg();
-    const int D = cf.dim[si], F = cf.ff[si], H = cf.heads[si], vh = cf.vhd[si], K = cf.kern[si];
-    const int M = B * T, Tp = (T + 3) & ~3, inproj = (2 * cf.qhd[si] + cf.phd[si]) * H, Hc = 3 * D / 4, HV = H * vh;
+    const int D = cf.dim[si], F = cf.ff[si], H = cf.heads[si], vh = cf.vhd[si], K = cf.kern[si], qh = cf.qhd[si], ph = cf.phd[si];
+    // the keys are the T frames, behind L frames of left context when streaming; KLp = their count rounded up to 4 (a row of aw)
+    const int L = site ? cf.left[si] : 0, M = B * T, KL = L + T, KLp = (KL + 3) & ~3, inproj = (2 * qh + ph) * H, Hc = 3 * D / 4, HV = H * vh;
     char p[96];
     snprintf(p, sizeof p, "encoder.encoders.%d.layers.%d.", si, li);
     auto w = [&](const char* suffix) { return m.w(std::string(p) + suffix); };
+    auto wk = [&](const char* fmt, int k) {   // a weight of the k-th module of its kind: wk("self_attn%d.in_proj.weight", 2)
+        char name[96];
+        snprintf(name, sizeof name, fmt, k);
+        return w(name);
+    };
     Arena& ar = *c.arena;
     int64_t mark = ar.mark();
+    const long long SS = lay_.floats_per_stream;
+    auto ring = [&](long long off) {   // (streaming) a ring of the site's streams in the state pool
+        RingRef r;
+        r.pool = online_pool_; r.slot_stride = SS; r.off = off; r.slots = site->d_slots; r.chunks = site->d_chunks;
+        return r;
+    };
 
     // [ff1.in_proj | attention-weights in_proj] of the layer input in one GEMM (model.cpp stacks the two weight matrices);
     // the attention weights are shared by nonlin_attention / self_attn1 / self_attn2
@@ -361,91 +377,112 @@ void Engine::encoder_layer(const Ctx& c, int si, int li, float* x, const float* 
         gemm(c, g);
     }
     const float* qkp = cat + F1;
-    int gl = li;  // global layer index: the cache key of the layer's positional projection
-    for (int i = 0; i < si; i++) gl += cf.nlayer[i];
-    const float* pp = pos_proj_cached(c, gl, pe, cf.pos_dim, w("self_attn_weights.linear_pos.weight"), 2 * T - 1, cf.phd[si] * H);
-    float* aw = ar.take<float>((int64_t)H * B * T * Tp);
-    attn_scores_softmax(c, qkp, ldcat, pp, aw, B, T, Tp, H);
+    // the layer's positional projection does not depend on the audio: cached per (layer, rows), streaming tables under 1000 + gl
+    const float* pp = pos_proj_cached(c, site ? 1000 + gl : gl, pe, cf.pos_dim, w("self_attn_weights.linear_pos.weight"), 2 * T - 1 + L, ph * H);
+    float* aw = ar.take<float>((int64_t)H * B * T * KLp);  // (streaming: columns in ring order)
+    if (site) attn_stream_ring(c, qkp, ldcat, ring(lay_.key[gl]), pp, site->d_plen, aw, B, T, L, KLp, H, cf.ds[si], cf.left[0] * cf.ds[0]);
+    else attn_scores_softmax(c, qkp, ldcat, pp, aw, B, T, KLp, H);
 
     float* src = ar.take<float>((int64_t)M * D);
+    // the streaming self-attention modules with their value projection inside (attn_proj_av_out_ring) read one buffer and write the other
+    const bool vproj_fused = site && !tunables().no_fused_vproj && T >= tunables().fused_vproj_min_t && D % 32 == 0 && vh <= 16 && HV % 4 == 0 && HV <= 128;
+    float* src_alt = vproj_fused ? ar.take<float>((int64_t)M * D) : nullptr;
     float* hid = ar.take<float>((int64_t)M * std::max({F * 5 / 4, 3 * Hc, 2 * D}));
-    float* tmp = ar.take<float>((int64_t)M * std::max(D, Hc));
+    float* tmp = site ? nullptr : ar.take<float>((int64_t)M * std::max(D, Hc));
     float* tmp2 = ar.take<float>((int64_t)M * std::max(D, Hc));
 
     auto feed_forward = [&](int k, int Fk, const float* in, float* out) {
-        char a[48], b[48], cc[48], d[48];
-        snprintf(a, sizeof a, "feed_forward%d.in_proj.weight", k);
-        snprintf(b, sizeof b, "feed_forward%d.in_proj.bias", k);
-        snprintf(cc, sizeof cc, "feed_forward%d.out_proj.weight", k);
-        snprintf(d, sizeof d, "feed_forward%d.out_proj.bias", k);
-        linear(c, in, D, w(a), w(b), hid, Fk, M, D, Fk, ACT_SWOOSH_L);
-        linear(c, hid, Fk, w(cc), w(d), out, D, M, Fk, D, ACT_NONE, in, D);
+        linear(c, in, D, wk("feed_forward%d.in_proj.weight", k), wk("feed_forward%d.in_proj.bias", k), hid, Fk, M, D, Fk, ACT_SWOOSH_L);
+        linear(c, hid, Fk, wk("feed_forward%d.out_proj.weight", k), wk("feed_forward%d.out_proj.bias", k), out, D, M, Fk, D, ACT_NONE, in, D);
+    };
+    auto nonlin_attention = [&]() {   // src += NonlinAttention(src, aw[0])
+        if (site) {
+            linear(c, src, D, w("nonlin_attention.in_proj.weight"), w("nonlin_attention.in_proj.bias"), hid, 3 * Hc, M, D, 3 * Hc);
+            // x * tanh(s) into the ring rows of this chunk and ctx = (aw_head0 . ring) * y in one per-stream launch
+            nonlin_av_out_ring(c, aw, ring(lay_.nonlin[gl]), hid, 3 * Hc, nullptr, nullptr, tmp2, B, T, KL, KLp, Hc, D);
+        } else {
+            GemmArgs g;
+            g.A = aw; g.lda = KLp; g.sA0 = (long long)T * KLp;
+            g.w_kn = 1;
+            g.C = tmp2; g.ldc = Hc; g.sC0 = (long long)T * Hc;
+            g.M = T; g.N = Hc; g.K = T; g.nb0 = B; g.nb1 = 1;
+            if (M >= 256 && Hc % 16 == 0 && !tunables().no_glu_epilogue) {
+                // in_proj with x * tanh(s) in its epilogue (weights interleaved at load): hid = [M, 2 Hc] = (gated | y)
+                GemmArgs p;
+                p.A = src; p.lda = D; p.W = w("nonlin_attention.in_proj.weight#glu"); p.ldw = D; p.bias = w("nonlin_attention.in_proj.bias#glu");
+                p.C = hid; p.ldc = 2 * Hc; p.M = M; p.N = 3 * Hc; p.K = D; p.glu = 2; p.glu_cols = 2 * Hc;
+                gemm(c, p);
+                g.W = hid; g.ldw = 2 * Hc; g.sW0 = (long long)T * 2 * Hc;
+                g.mul = hid + Hc; g.ldm = 2 * Hc; g.sM0 = (long long)T * 2 * Hc;  // x * y (the third chunk of in_proj) in the epilogue
+            } else {
+                linear(c, src, D, w("nonlin_attention.in_proj.weight"), w("nonlin_attention.in_proj.bias"), hid, 3 * Hc, M, D, 3 * Hc);
+                tanh_gate(c, hid, tmp, M, Hc);
+                g.W = tmp; g.ldw = Hc; g.sW0 = (long long)T * Hc;
+                g.mul = hid + 2 * Hc; g.ldm = 3 * Hc; g.sM0 = (long long)T * 3 * Hc;  // x * y (the third chunk of in_proj) in the epilogue
+            }
+            gemm(c, g);
+        }
+        linear(c, tmp2, Hc, w("nonlin_attention.out_proj.weight"), w("nonlin_attention.out_proj.bias"), src, D, M, Hc, D, ACT_NONE, src, D);
     };
     auto self_attn = [&](int k) {
-        char a[48], b[48], cc[48], d[48];
-        snprintf(a, sizeof a, "self_attn%d.in_proj.weight", k);
-        snprintf(b, sizeof b, "self_attn%d.in_proj.bias", k);
-        snprintf(cc, sizeof cc, "self_attn%d.out_proj.weight", k);
-        snprintf(d, sizeof d, "self_attn%d.out_proj.bias", k);
-        linear(c, src, D, w(a), w(b), hid, HV, M, D, HV);
-        if (attn_av_out(c, aw, hid, w(cc), w(d), src, B, T, T, Tp, H, vh, D)) return;  // fused attention-apply + out_proj + residual
+        const float *wi = wk("self_attn%d.in_proj.weight", k), *bi = wk("self_attn%d.in_proj.bias", k);
+        const float *wo = wk("self_attn%d.out_proj.weight", k), *bo = wk("self_attn%d.out_proj.bias", k);
+        if (vproj_fused) {   // one launch: value projection of the chunk's rows, ring update, attention apply, out_proj, residual
+            attn_proj_av_out_ring(c, aw, ring(k == 1 ? lay_.val1[gl] : lay_.val2[gl]), src, wi, bi, wo, bo, src_alt, B, T, KL, KLp, H, vh, D);
+            std::swap(src, src_alt);
+            return;
+        }
+        linear(c, src, D, wi, bi, hid, HV, M, D, HV);
+        if (site) {   // fused: chunk rows into the value ring, attention apply over the ring, out_proj, residual
+            attn_av_out_ring(c, aw, ring(k == 1 ? lay_.val1[gl] : lay_.val2[gl]), hid, wo, bo, src, B, T, KL, KLp, H, vh, D);
+            return;
+        }
+        if (attn_av_out(c, aw, hid, wo, bo, src, B, T, T, KLp, H, vh, D)) return;  // fused attention-apply + out_proj + residual
         GemmArgs g;  // tmp[b, :, h*vh : (h+1)*vh] = aw[h][b] . hid[b, :, h*vh : ...]
-        g.A = aw; g.lda = Tp; g.sA0 = (long long)T * Tp; g.sA1 = (long long)B * T * Tp;
+        g.A = aw; g.lda = KLp; g.sA0 = (long long)T * KLp; g.sA1 = (long long)B * T * KLp;
         g.W = hid; g.w_kn = 1; g.ldw = HV; g.sW0 = (long long)T * HV; g.sW1 = vh;
         g.C = tmp; g.ldc = HV; g.sC0 = (long long)T * HV; g.sC1 = vh;
         g.M = T; g.N = vh; g.K = T; g.nb0 = B; g.nb1 = H;
         gemm(c, g);
-        linear(c, tmp, HV, w(cc), w(d), src, D, M, HV, D, ACT_NONE, src, D);
+        linear(c, tmp, HV, wo, bo, src, D, M, HV, D, ACT_NONE, src, D);
     };
-    auto conv_module = [&](int k) {
-        char a[64], b[64], cc[64], d[64], e[64], f[64];
-        snprintf(a, sizeof a, "conv_module%d.in_proj.weight", k);
-        snprintf(b, sizeof b, "conv_module%d.in_proj.bias", k);
-        snprintf(cc, sizeof cc, "conv_module%d.depthwise_conv.weight#kd", k);
-        snprintf(d, sizeof d, "conv_module%d.depthwise_conv.bias", k);
-        snprintf(e, sizeof e, "conv_module%d.out_proj.weight", k);
-        snprintf(f, sizeof f, "conv_module%d.out_proj.bias", k);
-        if (M >= 256 && !tunables().no_glu_epilogue) {
-            // in_proj with the GLU in its epilogue (weights interleaved at load): hid is [M, D], not [M, 2D]
-            GemmArgs g;
-            std::string wa = std::string(a) + "#glu", wb = std::string(b) + "#glu";
-            g.A = src; g.lda = D; g.W = w(wa.c_str()); g.ldw = D; g.bias = w(wb.c_str()); g.C = hid; g.ldc = D;
-            g.M = M; g.N = 2 * D; g.K = D; g.glu = 1;
-            gemm(c, g);
-            dwconv1d_swoosh(c, hid, w(cc), w(d), tmp2, B, T, D, K);
+    auto conv_module = [&](int k) {   // src += out_proj(SwooshR(depthwise_conv(GLU(in_proj(src)))))
+        if (site) {
+            const long long cache_off = k == 1 ? lay_.conv1[gl] : lay_.conv2[gl];
+            const float *wc = wk("conv_module%d.depthwise_conv.causal_conv.weight", k), *bc = wk("conv_module%d.depthwise_conv.causal_conv.bias", k);
+            const float *ww = wk("conv_module%d.depthwise_conv.chunkwise_conv.weight", k), *bw = wk("conv_module%d.depthwise_conv.chunkwise_conv.bias", k);
+            const float* sc = wk("conv_module%d.depthwise_conv.chunkwise_conv_scale", k);
+            // in_proj + GLU + chunk-causal depthwise conv + SwooshR in ONE launch where the shape has the fused form (round 5): the T rows
+            // of a stream and a 16-channel (value | gate) block sit in one tile of the in_proj GEMM, so its epilogue has everything the
+            // convolution needs (conv_module 3 -> 2 launches, 32 per tick; K2HIP_NO_FUSED_CONV keeps the two launches for the cross-check)
+            bool fused = false;
+            if (!tunables().no_fused_conv)
+                fused = gemm_glu_causal_conv(c, src, wk("conv_module%d.in_proj.weight#glu", k), wk("conv_module%d.in_proj.bias#glu", k), online_pool_, SS,
+                                             cache_off, site->d_slots, wc, bc, ww, bw, sc, tmp2, B, T, D, K);
+            if (!fused) {
+                linear(c, src, D, wk("conv_module%d.in_proj.weight", k), wk("conv_module%d.in_proj.bias", k), hid, 2 * D, M, D, 2 * D);
+                glu_causal_conv(c, hid, online_pool_, SS, cache_off, site->d_slots, wc, bc, ww, bw, sc, tmp2, B, T, D, K);
+            }
         } else {
-            linear(c, src, D, w(a), w(b), hid, 2 * D, M, D, 2 * D);
-            glu_dwconv1d_swoosh(c, hid, w(cc), w(d), tmp2, B, T, D, K);
+            const float *wd = wk("conv_module%d.depthwise_conv.weight#kd", k), *bd = wk("conv_module%d.depthwise_conv.bias", k);
+            if (M >= 256 && !tunables().no_glu_epilogue) {
+                // in_proj with the GLU in its epilogue (weights interleaved at load): hid is [M, D], not [M, 2D]
+                GemmArgs g;
+                g.A = src; g.lda = D; g.W = wk("conv_module%d.in_proj.weight#glu", k); g.ldw = D; g.bias = wk("conv_module%d.in_proj.bias#glu", k);
+                g.C = hid; g.ldc = D; g.M = M; g.N = 2 * D; g.K = D; g.glu = 1;
+                gemm(c, g);
+                dwconv1d_swoosh(c, hid, wd, bd, tmp2, B, T, D, K);
+            } else {
+                linear(c, src, D, wk("conv_module%d.in_proj.weight", k), wk("conv_module%d.in_proj.bias", k), hid, 2 * D, M, D, 2 * D);
+                glu_dwconv1d_swoosh(c, hid, wd, bd, tmp2, B, T, D, K);
+            }
         }
-        linear(c, tmp2, D, w(e), w(f), src, D, M, D, D, ACT_NONE, src, D);
+        linear(c, tmp2, D, wk("conv_module%d.out_proj.weight", k), wk("conv_module%d.out_proj.bias", k), src, D, M, D, D, ACT_NONE, src, D);
     };
 
     // src = x + ff1(x): the hidden activations are the first F1 columns of `cat`
     linear(c, cat, ldcat, w("feed_forward1.out_proj.weight"), w("feed_forward1.out_proj.bias"), src, D, M, F1, D, ACT_NONE, x, D);
-    {   // src += NonlinAttention(src, aw[0])
-        GemmArgs g;
-        g.A = aw; g.lda = Tp; g.sA0 = (long long)T * Tp;
-        g.w_kn = 1;
-        g.C = tmp2; g.ldc = Hc; g.sC0 = (long long)T * Hc;
-        g.M = T; g.N = Hc; g.K = T; g.nb0 = B; g.nb1 = 1;
-        if (M >= 256 && Hc % 16 == 0 && !tunables().no_glu_epilogue) {
-            // in_proj with x * tanh(s) in its epilogue (weights interleaved at load): hid = [M, 2 Hc] = (gated | y)
-            GemmArgs p;
-            p.A = src; p.lda = D; p.W = w("nonlin_attention.in_proj.weight#glu"); p.ldw = D; p.bias = w("nonlin_attention.in_proj.bias#glu");
-            p.C = hid; p.ldc = 2 * Hc; p.M = M; p.N = 3 * Hc; p.K = D; p.glu = 2; p.glu_cols = 2 * Hc;
-            gemm(c, p);
-            g.W = hid; g.ldw = 2 * Hc; g.sW0 = (long long)T * 2 * Hc;
-            g.mul = hid + Hc; g.ldm = 2 * Hc; g.sM0 = (long long)T * 2 * Hc;  // x * y (the third chunk of in_proj) in the epilogue
-        } else {
-            linear(c, src, D, w("nonlin_attention.in_proj.weight"), w("nonlin_attention.in_proj.bias"), hid, 3 * Hc, M, D, 3 * Hc);
-            tanh_gate(c, hid, tmp, M, Hc);
-            g.W = tmp; g.ldw = Hc; g.sW0 = (long long)T * Hc;
-            g.mul = hid + 2 * Hc; g.ldm = 3 * Hc; g.sM0 = (long long)T * 3 * Hc;  // x * y (the third chunk of in_proj) in the epilogue
-        }
-        gemm(c, g);
-        linear(c, tmp2, Hc, w("nonlin_attention.out_proj.weight"), w("nonlin_attention.out_proj.bias"), src, D, M, Hc, D,
-               ACT_NONE, src, D);
-    }
+    nonlin_attention();
     self_attn(1);
     conv_module(1);
     {   // src = bypass_mid(x, src + ff2(src)): the bypass mix runs in the out_proj GEMM's epilogue
@@ -467,8 +504,6 @@ void Engine::encoder_layer(const Ctx& c, int si, int li, float* x, const float* 
     ar.rewind(mark);
 }
 
-// Zipformer2.forward stacks; returns full-dim output [B*T50, Dmax]
-
 // which stack output supplies which columns of the full-width row (Zipformer2._get_full_dim_output): the last stack's output, then,
 // walking back, every stack that is wider than what is covered so far contributes its extra columns
 static FullDimSegs full_dim_segments(const Config& cf, float* const* outputs) {
@@ -486,43 +521,47 @@ static FullDimSegs full_dim_segments(const Config& cf, float* const* outputs) {
     return s;
 }
 
-float* Engine::encoder_stacks(const Ctx& c, float* x0, int B, int T50, int tap, float** tap_ptr, int* tap_dim, bool* tapped, FullDimSegs* segs_out) {
+// Zipformer2.forward / .streaming_forward: the stacks over x0 [B*T50, dim[0]], whole utterances (site == null) or the site's chunk.
+// Returns false with *segs = the pieces of the full-width output [B*T50, Dmax], which the caller's downsample_full gathers itself (no
+// concatenated tensor); true when the walk ended in an offline tap (1 + i: the output of stack i; 100: the concatenated tensor) -- then
+// *tap_ptr / *tap_dim name it and *segs is not set.  Streaming passes tap = -1.
+bool Engine::encoder_stacks(const Ctx& c, float* x0, int B, int T50, const StreamSite* site, int tap, float** tap_ptr, int* tap_dim, FullDimSegs* segs) {
     const Model& m = *model_;
     const Config& cf = m.cfg();
     Arena& ar = *c.arena;
     const int M = B * T50;
     float* outputs[kMaxStacks] = {nullptr};
     float* x = x0;
-    int Dcur = cf.dim[0];
+    int Dcur = cf.dim[0], gl = 0;
     float *pre_y = nullptr, *pre_xd = nullptr;
     FullDimSegs lz;   // (only its lz_* fields are used)
     for (int si = 0; si < cf.ns; si++) {
-        const int D = cf.dim[si], ds = cf.ds[si];
+        const int D = cf.dim[si], ds = cf.ds[si], nl = cf.nlayer[si];
         // the stack's input is the previous output zero-extended / truncated to D channels (convert_channels): a stack that runs at
         // the input rate works in place on a converted copy (or on x itself when the width does not change); a downsampled stack
         // never materialises it -- its downsample and its out_combiner read x at its own width
         const int Din = Dcur;
         Dcur = D;
+        const int Td = (T50 + ds - 1) / ds;   // the stack's own frames
+        const float* pe = c.dry ? nullptr : site ? pos_emb_stream(Td, cf.left[si]) : pos_emb(Td);
         if (ds == 1) {
             float* xi = x;
             if (D != Din) {
                 xi = ar.take<float>((int64_t)M * D);
                 convert_channels(c, x, xi, M, Din, D);
             }
-            const float* pe = c.dry ? nullptr : pos_emb(T50);
             // in front of a downsampled stack the last layer's BiasNorm launch forms that stack's input as well (LayerTail)
             LayerTail tail;
-            if (si + 1 < cf.ns && cf.ds[si + 1] > 1 && cf.nlayer[si] > 0) {
+            if (si + 1 < cf.ns && cf.ds[si + 1] > 1 && nl > 0) {
                 tail.D2 = cf.dim[si + 1]; tail.ds2 = cf.ds[si + 1];
                 pre_y = ar.take<float>((int64_t)M * tail.D2);
                 pre_xd = ar.take<float>((int64_t)B * ((T50 + tail.ds2 - 1) / tail.ds2) * tail.D2);
                 tail.xd2 = pre_xd;
                 tail.bias2 = m.wf("encoder.encoders.%d.downsample.bias", si + 1);
             }
-            for (int li = 0; li < cf.nlayer[si]; li++) encoder_layer(c, si, li, xi, pe, B, T50, li == cf.nlayer[si] - 1 ? &tail : nullptr);
+            for (int li = 0; li < nl; li++, gl++) encoder_layer(c, si, li, gl, xi, pe, B, T50, site, li == nl - 1 ? &tail : nullptr);
             x = xi;
         } else {
-            const int Td = (T50 + ds - 1) / ds;
             // Round 5: where the NEXT stack is downsampled too, this stack's out_combiner and that stack's SimpleDownsample are one
             // launch (upsample_combine_downsample): its two outputs -- the next stack's `y` is not one of them, only reserved here -- are
             // taken in front of this stack's mark, so that they outlive the rewind.
@@ -538,15 +577,15 @@ float* Engine::encoder_stacks(const Ctx& c, float* x0, int B, int T50, int tap, 
             int64_t mark = ar.mark();
             float* xd = xd_ready ? xd_ready : ar.take<float>((int64_t)B * Td * D);
             if (!xd_ready) downsample(c, x, m.wf("encoder.encoders.%d.downsample.bias", si), xd, B, T50, D, ds, Din);
-            const float* pe = c.dry ? nullptr : pos_emb(Td);
-            for (int li = 0; li < cf.nlayer[si]; li++) encoder_layer(c, si, li, xd, pe, B, Td);
-            // the LAST stack's out_combiner runs inside the final downsample (FullDimSegs::lz_*): its output tensor is never written
-            const bool lazy = segs_out != nullptr && si == cf.ns - 1 && tap != 1 + si;
+            for (int li = 0; li < nl; li++, gl++) encoder_layer(c, si, li, gl, xd, pe, B, Td, site);
+            // the LAST stack's out_combiner runs inside the final downsample (FullDimSegs::lz_*): its output tensor is never written,
+            // unless a tap asks for it
+            const bool lazy = si == cf.ns - 1 && tap != 1 + si && tap != 100;
             if (fuse_next)
                 upsample_combine_downsample(c, x, xd, m.wf("encoder.encoders.%d.out_combiner.bypass_scale", si), y,
                                             m.wf("encoder.encoders.%d.downsample.bias", si + 1), pre_xd, B, T50, Td, D, ds, Din, D2, ds2);
             else if (lazy) {
-                lz.lz_orig = x; lz.lz_xd = xd; lz.lz_scale = c.dry ? nullptr : m.wf("encoder.encoders.%d.out_combiner.bypass_scale", si);
+                lz.lz_orig = c.dry ? nullptr : x; lz.lz_xd = xd; lz.lz_scale = c.dry ? nullptr : m.wf("encoder.encoders.%d.out_combiner.bypass_scale", si);
                 lz.lz_Td = Td; lz.lz_ds = ds; lz.lz_Do = Din;
             } else
                 upsample_combine(c, x, xd, m.wf("encoder.encoders.%d.out_combiner.bypass_scale", si), y, B, T50, Td, D, ds, Din);
@@ -557,35 +596,47 @@ float* Engine::encoder_stacks(const Ctx& c, float* x0, int B, int T50, int tap, 
         if (tap == 1 + si) {
             *tap_ptr = x;
             *tap_dim = D;
-            *tapped = true;
-            return nullptr;
+            return true;
         }
     }
-    if (segs_out) {  // the caller gathers the columns itself (downsample_full): no concatenated tensor
-        *segs_out = full_dim_segments(cf, outputs);
-        segs_out->lz_orig = c.dry ? nullptr : lz.lz_orig; segs_out->lz_xd = lz.lz_xd; segs_out->lz_scale = lz.lz_scale;
-        segs_out->lz_Td = lz.lz_Td; segs_out->lz_ds = lz.lz_ds; segs_out->lz_Do = lz.lz_Do;
-        return nullptr;
-    }
-    // _get_full_dim_output
-    const int Dmax = cf.dmax;
-    float* full = ar.take<float>((int64_t)M * Dmax);
-    int cur = cf.dim[cf.ns - 1];
-    copy_cols(c, outputs[cf.ns - 1], cur, 0, full, Dmax, 0, M, cur);
-    for (int i = cf.ns - 2; i >= 0; i--) {
-        int d = cf.dim[i];
-        if (d > cur) {
-            copy_cols(c, outputs[i], d, cur, full, Dmax, cur, M, d - cur);
-            cur = d;
+    if (tap == 100) {   // _get_full_dim_output as a tensor
+        float* full = ar.take<float>((int64_t)M * cf.dmax);
+        const FullDimSegs s = full_dim_segments(cf, outputs);
+        for (int i = 0, col0 = 0; i < s.n; i++) {
+            copy_cols(c, s.src[i], s.ld[i], col0, full, cf.dmax, col0, M, s.col1[i] - col0);
+            col0 = s.col1[i];
         }
+        *tap_ptr = full;
+        *tap_dim = cf.dmax;
+        return true;
     }
-    return full;
+    *segs = full_dim_segments(cf, outputs);
+    segs->lz_orig = lz.lz_orig; segs->lz_xd = lz.lz_xd; segs->lz_scale = lz.lz_scale;
+    segs->lz_Td = lz.lz_Td; segs->lz_ds = lz.lz_ds; segs->lz_Do = lz.lz_Do;
+    return false;
+}
+
+// encoder.downsample_output over the stacks' full-width output, then the model's head: joiner.encoder_proj, or a CTC model's
+// Linear(Dmax -> V) + log_softmax (its "log_probs" output).  Returns [B * T', enc_dim] in enc_out, or (null) taken here, last.
+float* Engine::encoder_head(const Ctx& c, const FullDimSegs& segs, int B, int T50, float* enc_out) {
+    const Model& m = *model_;
+    const Config& cf = m.cfg();
+    const int Tp = (T50 + 1) / 2, Dmax = cf.dmax;
+    float* dsd = c.arena->take<float>((int64_t)B * Tp * Dmax);
+    downsample_full(c, segs, m.w("encoder.downsample_output.bias"), dsd, B, T50, Dmax, 2);
+    if (!enc_out) enc_out = c.arena->take<float>((int64_t)B * Tp * cf.enc_dim());
+    if (cf.ctc) {
+        linear(c, dsd, Dmax, m.w("ctc_output.1.weight"), m.w("ctc_output.1.bias"), enc_out, cf.V, B * Tp, Dmax, cf.V);
+        log_softmax_rows(c, enc_out, B * Tp, cf.V);
+    } else {
+        linear(c, dsd, Dmax, m.w("joiner.encoder_proj.weight"), m.w("joiner.encoder_proj.bias"), enc_out, cf.J, B * Tp, Dmax, cf.J);
+    }
+    return enc_out;
 }
 
 float* Engine::encoder_forward(const Ctx& c, const float* x, int B, int T, int* Tp, int tap, float** tap_ptr, int* tap_rows,
                                int* tap_dim) {
-    const Model& m = *model_;
-    const Config& cf = m.cfg();
+    const Config& cf = model_->cfg();
     if (cf.conformer) return conformer_forward(c, x, B, T, Tp, tap, tap_ptr, tap_rows, tap_dim);
     if (cf.lstm) return lstm_forward(c, x, B, T, Tp, tap, tap_ptr, tap_rows, tap_dim);
     if (cf.zip1) return zip1_forward(c, x, B, T, Tp, tap, tap_ptr, tap_rows, tap_dim);
@@ -603,25 +654,10 @@ float* Engine::encoder_forward(const Ctx& c, const float* x, int B, int T, int* 
         *tap_dim = cf.dim[0];
         return nullptr;
     }
-    bool tapped = false;  // NB: pointers are all null in a dry run, so never test them
     FullDimSegs segs;
-    float* full = encoder_stacks(c, x0, B, T50, tap, tap_ptr, tap_dim, &tapped, tap == 100 ? nullptr : &segs);
-    if (tapped) return nullptr;
-    if (tap == 100) {
-        *tap_ptr = full;
-        *tap_dim = cf.dmax;
-        return nullptr;
-    }
-    float* dsd = ar.take<float>((int64_t)B * Tpp * cf.dmax);
-    downsample_full(c, segs, m.w("encoder.downsample_output.bias"), dsd, B, T50, cf.dmax, 2);
-    if (cf.ctc) {  // CTC head: Linear(Dmax -> V) + log_softmax = the model's "log_probs" output
-        linear(c, dsd, cf.dmax, m.w("ctc_output.1.weight"), m.w("ctc_output.1.bias"), enc_out, cf.V, B * Tpp, cf.dmax, cf.V);
-        log_softmax_rows(c, enc_out, B * Tpp, cf.V);
-    } else {
-        linear(c, dsd, cf.dmax, m.w("joiner.encoder_proj.weight"), m.w("joiner.encoder_proj.bias"), enc_out, cf.J, B * Tpp, cf.dmax, cf.J);
-    }
+    if (encoder_stacks(c, x0, B, T50, nullptr, tap, tap_ptr, tap_dim, &segs)) return nullptr;
     *Tp = Tpp;
-    return enc_out;
+    return encoder_head(c, segs, B, T50, enc_out);
 }
 
 // The decoder outputs of the two contexts every offline greedy search starts from are constants of the model: computed once (by the

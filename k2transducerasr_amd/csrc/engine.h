@@ -236,8 +236,20 @@ class Engine {
   private:
     // device-side building blocks; all take a Ctx (dry run = sizing only)
     float* encoder_embed(const Ctx& c, const float* x, int B, int T, int* T50);
-    void encoder_layer(const Ctx& c, int si, int li, float* x, const float* pe, int B, int T, const LayerTail* tail = nullptr);
-    float* encoder_stacks(const Ctx& c, float* x0, int B, int T50, int tap, float** tap_ptr, int* tap_dim, bool* tapped, FullDimSegs* segs_out = nullptr);
+    // Where a Zipformer2 / Zipformer v1 stack walk and its layers run.  A null site is offline: whole utterances.  Otherwise one chunk of
+    // the streams in these state slots (device arrays of B entries each), behind the config's per-stack left context.
+    struct StreamSite {
+        const int* d_slots;
+        const long long* d_plen = nullptr;   // frames each stream has processed (Zipformer2)
+        const int* d_chunks = nullptr;       // chunks each stream has decoded: the position of its rings (Zipformer2)
+    };
+    // Zipformer2: one layer, the walk over the stacks and the head behind it, offline and streaming (engine.cpp).  gl = global layer index
+    void encoder_layer(const Ctx& c, int si, int li, int gl, float* x, const float* pe, int B, int T, const StreamSite* site,
+                       const LayerTail* tail = nullptr);
+    // true: ended in an offline tap (*tap_ptr, *tap_dim); false: *segs = the pieces of the full-width output
+    bool encoder_stacks(const Ctx& c, float* x0, int B, int T50, const StreamSite* site, int tap, float** tap_ptr, int* tap_dim, FullDimSegs* segs);
+    // downsample_output + joiner.encoder_proj (CTC: the log_probs head) into enc_out; null: taken from the arena here, last
+    float* encoder_head(const Ctx& c, const FullDimSegs& segs, int B, int T50, float* enc_out);
     float* encoder_forward(const Ctx& c, const float* x, int B, int T, int* Tp, int tap, float** tap_ptr, int* tap_rows,
                            int* tap_dim);
     // device by-products of ONE search, in the arena that search ran in: they travel from the search to the finish_tokens of the same
@@ -349,13 +361,14 @@ class Engine {
     float* lstm_forward_seq(const Ctx& c, float* xe, int B, int T3, float* enc_out, int tap, float** tap_ptr, int* tap_dim);
     float* lstm_forward(const Ctx& c, const float* x, int B, int T, int* Tp, int tap, float** tap_ptr, int* tap_rows, int* tap_dim);
     float* lstm_chunk(const Ctx& c, const float* x, const int* d_slots, int B);
-    // streaming Zipformer v1 (zipformer1_engine.cpp)
+    // Zipformer v1 (zipformer1_engine.cpp)
     const float* sinus_pos_emb(int Tc, int left, int D);
     std::map<std::tuple<int, int, int>, float*> sinus_cache_;  // (frames, left context, width) -> device table
     float* zip1_embed(const Ctx& c, const float* x, int B, int T, int* Tc_out);
-    void zip1_layer(const Ctx& c, int si, const std::string& pfx, int l, float* x, const float* pp, const int* d_slots, int B, int Tc, int L);
+    // one layer and the walk over the stacks (through joiner.encoder_proj), offline (null site) and streaming
+    void zip1_layer(const Ctx& c, int si, const std::string& pfx, int l, float* x, const float* pe, int B, int T, const StreamSite* site);
+    float* zip1_stacks(const Ctx& c, float* x0, int B, int Tc, const StreamSite* site, float* enc, int tap, float** tap_ptr, int* tap_dim);
     float* zip1_chunk(const Ctx& c, const float* x, const int* d_slots, int B, int* Tp_out);
-    void zip1_layer_offline(const Ctx& c, int si, const std::string& pfx, int l, float* x, const float* pe, int B, int T);
     float* zip1_forward(const Ctx& c, const float* x, int B, int T, int* Tp, int tap, float** tap_ptr, int* tap_rows, int* tap_dim);
     // offline Conformer (conformer_engine.cpp)
     const float* conformer_pos_emb_left(int Tc, int left);
@@ -369,8 +382,6 @@ class Engine {
     const float* pos_emb_stream(int Tc, int L);
     void online_ensure_pool();
     float* encoder_embed_stream(const Ctx& c, const float* x, const int* d_slots, int B, int T, int* Tc);
-    void encoder_layer_stream(const Ctx& c, int si, int li, int l, float* x, const float* pe, const int* d_slots,
-                              const long long* d_plen, const int* d_chunks, int B, int Tc, int L, const LayerTail* tail = nullptr);
     std::mutex cache_mu_;  // pos_proj / pos_emb / decjoin tables are built lazily
     float* online_encoder_zip2(const Ctx& c, const float* d_x, const int* d_slots, const long long* d_plen, const int* d_chunks, int B);
     DecJoinW decjoin();

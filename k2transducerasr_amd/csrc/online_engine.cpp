@@ -265,228 +265,17 @@ float* Engine::encoder_embed_stream(const Ctx& c, const float* x, const int* d_s
     return out;
 }
 
-// Zipformer2EncoderLayer.streaming_forward, in place on x [B*Tc, D]; l = global layer index
-void Engine::encoder_layer_stream(const Ctx& c, int si, int li, int l, float* x, const float* pe, const int* d_slots,
-                                  const long long* d_plen, const int* d_chunks, int B, int Tc, int L, const LayerTail* tail) {
-    const Model& m = *model_;
-    const Config& cf = m.cfg();
-    const int D = cf.dim[si], F = cf.ff[si], H = cf.heads[si], vh = cf.vhd[si], K = cf.kern[si], qh = cf.qhd[si], ph = cf.phd[si];
-    const int M = B * Tc, KL = L + Tc, KLp = (KL + 3) & ~3, inproj = (2 * qh + ph) * H, Hc = 3 * D / 4, HV = H * vh;
-    const int n2 = 2 * Tc - 1 + L, left50 = cf.left[0] * cf.ds[0];
-    char p[96];
-    snprintf(p, sizeof p, "encoder.encoders.%d.layers.%d.", si, li);
-    auto w = [&](const char* suffix) { return m.w(std::string(p) + suffix); };
-    Arena& ar = *c.arena;
-    int64_t mark = ar.mark();
-    const long long SS = lay_.floats_per_stream;
-
-    // [ff1.in_proj | attention-weights in_proj] of the layer input in one GEMM, as in the offline layer (model.cpp stacks the
-    // two weight matrices): one launch fewer per layer
-    const int F1 = F * 3 / 4, ldcat = F1 + inproj;
-    float* cat = ar.take<float>((int64_t)M * ldcat);
-    {
-        GemmArgs g;
-        g.A = x; g.lda = D; g.W = w("#ff1_attn_in.weight"); g.ldw = D; g.bias = w("#ff1_attn_in.bias");
-        g.C = cat; g.ldc = ldcat; g.M = M; g.N = ldcat; g.K = D; g.act = ACT_SWOOSH_L; g.act_cols = F1;
-        gemm(c, g);
-    }
-    const float* qkp = cat + F1;
-    auto ring = [&](long long off) {
-        RingRef r;
-        r.pool = online_pool_; r.slot_stride = SS; r.off = off; r.slots = d_slots; r.chunks = d_chunks;
-        return r;
-    };
-    const float* pp = pos_proj_cached(c, 1000 + l, pe, cf.pos_dim, w("self_attn_weights.linear_pos.weight"), n2, ph * H);
-    float* aw = ar.take<float>((int64_t)H * B * Tc * KLp);  // columns in ring order
-    attn_stream_ring(c, qkp, ldcat, ring(lay_.key[l]), pp, d_plen, aw, B, Tc, L, KLp, H, cf.ds[si], left50);
-
-    float* src = ar.take<float>((int64_t)M * D);
-    // the self-attention modules with their value projection inside (attn_proj_av_out_ring) read one buffer and write the other
-    const bool vproj_fused = !tunables().no_fused_vproj && Tc >= tunables().fused_vproj_min_t && D % 32 == 0 && vh <= 16 && HV % 4 == 0 && HV <= 128;
-    float* src_alt = vproj_fused ? ar.take<float>((int64_t)M * D) : nullptr;
-    float* hid = ar.take<float>((int64_t)M * std::max({F * 5 / 4, 3 * Hc, 2 * D}));
-    float* tmp2 = ar.take<float>((int64_t)M * std::max(D, Hc));
-
-    auto feed_forward = [&](int k, int Fk, const float* in, float* out) {
-        char a[48], b[48], cc[48], d[48];
-        snprintf(a, sizeof a, "feed_forward%d.in_proj.weight", k);
-        snprintf(b, sizeof b, "feed_forward%d.in_proj.bias", k);
-        snprintf(cc, sizeof cc, "feed_forward%d.out_proj.weight", k);
-        snprintf(d, sizeof d, "feed_forward%d.out_proj.bias", k);
-        linear(c, in, D, w(a), w(b), hid, Fk, M, D, Fk, ACT_SWOOSH_L);
-        linear(c, hid, Fk, w(cc), w(d), out, D, M, Fk, D, ACT_NONE, in, D);
-    };
-    auto self_attn = [&](int k, long long cache_off) {
-        char a[48], b[48], cc[48], d[48];
-        snprintf(a, sizeof a, "self_attn%d.in_proj.weight", k);
-        snprintf(b, sizeof b, "self_attn%d.in_proj.bias", k);
-        snprintf(cc, sizeof cc, "self_attn%d.out_proj.weight", k);
-        snprintf(d, sizeof d, "self_attn%d.out_proj.bias", k);
-        if (vproj_fused) {   // one launch: value projection of the chunk's rows, ring update, attention apply, out_proj, residual
-            attn_proj_av_out_ring(c, aw, ring(cache_off), src, w(a), w(b), w(cc), w(d), src_alt, B, Tc, KL, KLp, H, vh, D);
-            std::swap(src, src_alt);
-            return;
-        }
-        linear(c, src, D, w(a), w(b), hid, HV, M, D, HV);
-        // fused: chunk rows into the value ring, attention apply over the ring, out_proj, residual
-        attn_av_out_ring(c, aw, ring(cache_off), hid, w(cc), w(d), src, B, Tc, KL, KLp, H, vh, D);
-    };
-    auto conv_module = [&](int k, long long cache_off) {
-        char a[80], b[80], e[80], f[80], n1[96], n2_[96], n3[96], n4[96], n5[96];
-        snprintf(a, sizeof a, "conv_module%d.in_proj.weight", k);
-        snprintf(b, sizeof b, "conv_module%d.in_proj.bias", k);
-        snprintf(e, sizeof e, "conv_module%d.out_proj.weight", k);
-        snprintf(f, sizeof f, "conv_module%d.out_proj.bias", k);
-        snprintf(n1, sizeof n1, "conv_module%d.depthwise_conv.causal_conv.weight", k);
-        snprintf(n2_, sizeof n2_, "conv_module%d.depthwise_conv.causal_conv.bias", k);
-        snprintf(n3, sizeof n3, "conv_module%d.depthwise_conv.chunkwise_conv.weight", k);
-        snprintf(n4, sizeof n4, "conv_module%d.depthwise_conv.chunkwise_conv.bias", k);
-        snprintf(n5, sizeof n5, "conv_module%d.depthwise_conv.chunkwise_conv_scale", k);
-        // in_proj + GLU + chunk-causal depthwise conv + SwooshR in ONE launch where the shape has the fused form (round 5): the Tc rows
-        // of a stream and a 16-channel (value | gate) block sit in one tile of the in_proj GEMM, so its epilogue has everything the
-        // convolution needs (conv_module 3 -> 2 launches, 32 per tick; K2HIP_NO_FUSED_CONV keeps the two launches for the cross-check)
-        bool fused = false;
-        if (!tunables().no_fused_conv) {
-            const std::string wa = std::string(a) + "#glu", wb = std::string(b) + "#glu";
-            fused = gemm_glu_causal_conv(c, src, w(wa.c_str()), w(wb.c_str()), online_pool_, SS, cache_off, d_slots, w(n1), w(n2_), w(n3), w(n4), w(n5),
-                                         tmp2, B, Tc, D, K);
-        }
-        if (!fused) {
-            linear(c, src, D, w(a), w(b), hid, 2 * D, M, D, 2 * D);
-            glu_causal_conv(c, hid, online_pool_, SS, cache_off, d_slots, w(n1), w(n2_), w(n3), w(n4), w(n5), tmp2, B, Tc, D, K);
-        }
-        linear(c, tmp2, D, w(e), w(f), src, D, M, D, D, ACT_NONE, src, D);
-    };
-
-    // src = x + ff1(x): the hidden activations are the first F1 columns of `cat`
-    linear(c, cat, ldcat, w("feed_forward1.out_proj.weight"), w("feed_forward1.out_proj.bias"), src, D, M, F1, D, ACT_NONE, x, D);
-    {   // NonlinAttention.streaming_forward
-        linear(c, src, D, w("nonlin_attention.in_proj.weight"), w("nonlin_attention.in_proj.bias"), hid, 3 * Hc, M, D, 3 * Hc);
-        // x * tanh(s) into the ring rows of this chunk and ctx = (aw_head0 . ring) * y in one per-stream launch (k_ring_put + a batched
-        // GEMM before), then out_proj over all rows
-        nonlin_av_out_ring(c, aw, ring(lay_.nonlin[l]), hid, 3 * Hc, nullptr, nullptr, tmp2, B, Tc, KL, KLp, Hc, D);
-        linear(c, tmp2, Hc, w("nonlin_attention.out_proj.weight"), w("nonlin_attention.out_proj.bias"), src, D, M, Hc, D, ACT_NONE, src, D);
-    }
-    self_attn(1, lay_.val1[l]);
-    conv_module(1, lay_.conv1[l]);
-    {   // src = bypass_mid(x, src + ff2(src)): the bypass mix runs in the out_proj GEMM's epilogue
-        linear(c, src, D, w("feed_forward2.in_proj.weight"), w("feed_forward2.in_proj.bias"), hid, F, M, D, F, ACT_SWOOSH_L);
-        GemmArgs g;
-        g.A = hid; g.lda = F; g.W = w("feed_forward2.out_proj.weight"); g.ldw = F; g.bias = w("feed_forward2.out_proj.bias");
-        g.C = src; g.ldc = D; g.M = M; g.N = D; g.K = F; g.res = src; g.ldr = D;
-        g.byp_orig = x; g.ld_orig = D; g.byp_scale = w("bypass_mid.bypass_scale");
-        gemm(c, g);
-    }
-    self_attn(2, lay_.val2[l]);
-    conv_module(2, lay_.conv2[l]);
-    feed_forward(3, F * 5 / 4, src, src);
-    if (tail && tail->bias2)   // the stack's last layer in front of a downsampled stack: that stack's downsample in the same launch
-        biasnorm_bypass_downsample(c, src, x, w("norm.bias"), w("norm.log_scale"), w("bypass.bypass_scale"), x, tail->bias2, tail->xd2, B, Tc, D,
-                                   tail->ds2, tail->D2);
-    else
-        biasnorm_bypass(c, src, x, w("norm.bias"), w("norm.log_scale"), w("bypass.bypass_scale"), x, M, D);
-    ar.rewind(mark);
-}
-
 // The streaming Zipformer2 encoder of one (sub-)batch: x [B, T, feat] (log-floored) -> encoder_out [B*Tp, enc_dim]; caches of
 // the B slots advanced in place (OnlineProjOfZipformer2.EncoderProj :491-618 without stack / unstack)
 float* Engine::online_encoder_zip2(const Ctx& c, const float* d_x, const int* d_slots, const long long* d_plen, const int* d_chunks, int B) {
-    const Model& m = *model_;
-    const Config& cf = m.cfg();
-    Arena& ar = *c.arena;
-    const int T = cf.chunk_T, Tp = online_frames_per_chunk();
+    const int Tp = online_frames_per_chunk();
     int Tc = 0;
-    float* x = encoder_embed_stream(c, d_x, d_slots, B, T, &Tc);
-    const int M = B * Tc;
-    float* outputs[kMaxStacks] = {nullptr};
-    int Dcur = cf.dim[0], l = 0;
-    float *pre_y = nullptr, *pre_xd = nullptr;
-    FullDimSegs lz;   // (only its lz_* fields are used)
-    for (int si = 0; si < cf.ns; si++) {
-        const int D = cf.dim[si], ds = cf.ds[si], L = cf.left[si];
-        // the stack's input is the previous output zero-extended / truncated to D channels (convert_channels): a stack that runs at
-        // the input rate works in place on a converted copy (or on x itself when the width does not change); a downsampled stack
-        // never materialises it -- its downsample and its out_combiner read x at its own width
-        const int Din = Dcur;
-        Dcur = D;
-        if (ds == 1) {
-            float* xi = x;
-            if (D != Din) {
-                xi = ar.take<float>((int64_t)M * D);
-                convert_channels(c, x, xi, M, Din, D);
-            }
-            const float* pe = c.dry ? nullptr : pos_emb_stream(Tc, L);
-            // in front of a downsampled stack the last layer's BiasNorm launch forms that stack's input as well (LayerTail)
-            LayerTail tail;
-            if (si + 1 < cf.ns && cf.ds[si + 1] > 1 && cf.nlayer[si] > 0) {
-                tail.D2 = cf.dim[si + 1]; tail.ds2 = cf.ds[si + 1];
-                pre_y = ar.take<float>((int64_t)M * tail.D2);
-                pre_xd = ar.take<float>((int64_t)B * ((Tc + tail.ds2 - 1) / tail.ds2) * tail.D2);
-                tail.xd2 = pre_xd;
-                tail.bias2 = m.wf("encoder.encoders.%d.downsample.bias", si + 1);
-            }
-            for (int li = 0; li < cf.nlayer[si]; li++, l++)
-                encoder_layer_stream(c, si, li, l, xi, pe, d_slots, d_plen, d_chunks, B, Tc, L, li == cf.nlayer[si] - 1 ? &tail : nullptr);
-            x = xi;
-        } else {
-            const int Td = (Tc + ds - 1) / ds;
-            // (as in the offline stacks: this stack's out_combiner + the next stack's downsample in one launch where both are downsampled)
-            float* y = pre_y ? pre_y : ar.take<float>((int64_t)M * D);
-            float* xd_ready = pre_xd;
-            pre_y = pre_xd = nullptr;
-            const bool fuse_next = si + 1 < cf.ns && cf.ds[si + 1] > 1;
-            const int D2 = fuse_next ? cf.dim[si + 1] : 0, ds2 = fuse_next ? cf.ds[si + 1] : 1;
-            if (fuse_next) {
-                pre_y = ar.take<float>((int64_t)M * D2);
-                pre_xd = ar.take<float>((int64_t)B * ((Tc + ds2 - 1) / ds2) * D2);
-            }
-            int64_t mark = ar.mark();
-            float* xd = xd_ready ? xd_ready : ar.take<float>((int64_t)B * Td * D);
-            if (!xd_ready) downsample(c, x, m.wf("encoder.encoders.%d.downsample.bias", si), xd, B, Tc, D, ds, Din);
-            const float* pe = c.dry ? nullptr : pos_emb_stream(Td, L);
-            for (int li = 0; li < cf.nlayer[si]; li++, l++) encoder_layer_stream(c, si, li, l, xd, pe, d_slots, d_plen, d_chunks, B, Td, L);
-            const bool lazy = si == cf.ns - 1;   // the last stack's out_combiner runs inside the final downsample (FullDimSegs::lz_*)
-            if (fuse_next)
-                upsample_combine_downsample(c, x, xd, m.wf("encoder.encoders.%d.out_combiner.bypass_scale", si), y,
-                                            m.wf("encoder.encoders.%d.downsample.bias", si + 1), pre_xd, B, Tc, Td, D, ds, Din, D2, ds2);
-            else if (lazy) {
-                lz.lz_orig = x; lz.lz_xd = xd; lz.lz_scale = m.wf("encoder.encoders.%d.out_combiner.bypass_scale", si);
-                lz.lz_Td = Td; lz.lz_ds = ds; lz.lz_Do = Din;
-            } else
-                upsample_combine(c, x, xd, m.wf("encoder.encoders.%d.out_combiner.bypass_scale", si), y, B, Tc, Td, D, ds, Din);
-            if (!lazy) ar.rewind(mark);   // (lazy: xd is read by the final downsample -- it stays allocated)
-            x = y;
-        }
-        outputs[si] = x;
-    }
-    const int Dmax = cf.dmax;
-    const int Tpp = (Tc + 1) / 2;
-    K2_REQUIRE(Tpp == Tp, "internal: chunk yields %d frames, expected %d", Tpp, Tp);
-    float* dsd = ar.take<float>((int64_t)B * Tp * Dmax);
-    {   // _get_full_dim_output + downsample_output in one launch (no concatenated tensor)
-        FullDimSegs segs;
-        int cur = cf.dim[cf.ns - 1];
-        segs.src[0] = outputs[cf.ns - 1]; segs.ld[0] = cur; segs.col1[0] = cur; segs.n = 1;
-        for (int i = cf.ns - 2; i >= 0; i--) {
-            const int d = cf.dim[i];
-            if (d > cur) {
-                K2_REQUIRE(segs.n < 8, "too many stack widths");
-                segs.src[segs.n] = outputs[i]; segs.ld[segs.n] = d; segs.col1[segs.n] = d; segs.n++;
-                cur = d;
-            }
-        }
-        segs.lz_orig = c.dry ? nullptr : lz.lz_orig; segs.lz_xd = lz.lz_xd; segs.lz_scale = lz.lz_scale;
-        segs.lz_Td = lz.lz_Td; segs.lz_ds = lz.lz_ds; segs.lz_Do = lz.lz_Do;
-        downsample_full(c, segs, m.w("encoder.downsample_output.bias"), dsd, B, Tc, Dmax, 2);
-    }
-    float* enc = ar.take<float>((int64_t)B * Tp * cf.enc_dim());
-    if (cf.ctc) {
-        linear(c, dsd, Dmax, m.w("ctc_output.1.weight"), m.w("ctc_output.1.bias"), enc, cf.V, B * Tp, Dmax, cf.V);
-        log_softmax_rows(c, enc, B * Tp, cf.V);
-    } else {
-        linear(c, dsd, Dmax, m.w("joiner.encoder_proj.weight"), m.w("joiner.encoder_proj.bias"), enc, cf.J, B * Tp, Dmax, cf.J);
-    }
-    return enc;
+    float* x = encoder_embed_stream(c, d_x, d_slots, B, model_->cfg().chunk_T, &Tc);
+    K2_REQUIRE((Tc + 1) / 2 == Tp, "internal: chunk yields %d frames, expected %d", (Tc + 1) / 2, Tp);
+    const StreamSite site{d_slots, d_plen, d_chunks};
+    FullDimSegs segs;
+    encoder_stacks(c, x, B, Tc, &site, -1, nullptr, nullptr, &segs);
+    return encoder_head(c, segs, B, Tc, nullptr);
 }
 
 void Engine::online_step(const int* slots, const float* const* chunks, const long long* hyps, const long long* plens, const int* nchunks, int B,

@@ -8,6 +8,7 @@
 // Conv2dSubsampling ((T-7)//2 frames); per stack [skip SimpleCombiner] -> layers, behind AttentionDownsample / SimpleUpsample /
 // out_combiner when the stack runs at a lower rate; AttentionDownsample by 2; joiner.encoder_proj (applied by the ONNX encoder
 // wrapper).  Every Linear / pointwise conv is the fp32 MFMA GEMM with its bias, DoubleSwish and residual fused in the epilogue.
+// The offline encoder (Zipformer.forward over whole utterances) is the same stack walk and the same layer function with a null site.
 #include <cmath>
 
 #include "engine.h"
@@ -78,13 +79,16 @@ float* Engine::zip1_embed(const Ctx& c, const float* x, int B, int T, int* Tc_ou
     return out;
 }
 
-// ZipformerEncoderLayer.streaming_forward, in place on x [B*Tc, D]; l = global layer index (slot layout), pp = linear_pos(pos_emb)
-void Engine::zip1_layer(const Ctx& c, int si, const std::string& pfx, int l, float* x, const float* pp, const int* d_slots, int B, int Tc,
-                        int L) {
+// ZipformerEncoderLayer.forward / .streaming_forward, in place on x [B*T, D]; l = global layer index, pe = the stack's positional table.
+// site == null: whole utterances -- mean pooling over the utterance, attention over its T frames, centred depthwise convolutions, i.e. the
+// offline Zipformer2 kernels (32-row attention strips on the MFMA, fused attention-apply + out_proj, LDS-tiled GLU + depthwise conv) with
+// v1's row layout (q | k | v | p, head size attention_dim / heads).  Otherwise the streams' chunk of T frames: running-mean pooling, keys
+// and values behind their caches of cf.left[si] frames, causal convolutions over the conv caches (slot layout: lay_, indexed by l).
+void Engine::zip1_layer(const Ctx& c, int si, const std::string& pfx, int l, float* x, const float* pe, int B, int T, const StreamSite* site) {
     const Model& m = *model_;
     const Config& cf = m.cfg();
     const int D = cf.dim[si], A = cf.att[si], H = cf.heads[si], F = cf.ff[si], K = cf.kern[si];
-    const int M = B * Tc, KL = L + Tc, KLp = (KL + 3) & ~3, A2 = A / 2, vd = A2 / H, inproj = 2 * A + A2 + 4 * H;
+    const int L = site ? cf.left[si] : 0, M = B * T, KL = L + T, KLp = (KL + 3) & ~3, A2 = A / 2, vd = A2 / H, inproj = 2 * A + A2 + 4 * H;
     auto w = [&](const char* suffix) { return m.w(pfx + suffix); };
     Arena& ar = *c.arena;
     int64_t mark = ar.mark();
@@ -92,68 +96,86 @@ void Engine::zip1_layer(const Ctx& c, int si, const std::string& pfx, int l, flo
     float* src = ar.take<float>((int64_t)M * D);
     float* hid = ar.take<float>((int64_t)M * std::max({F, 2 * D, inproj}));
     float* tmp = ar.take<float>((int64_t)M * std::max(D, A2));
-    float* kcat = ar.take<float>((int64_t)B * KL * A);
-    float* vcat = ar.take<float>((int64_t)B * KL * A2);
-    float* aw = ar.take<float>((int64_t)H * B * Tc * KLp);
+    float* kcat = site ? ar.take<float>((int64_t)B * KL * A) : nullptr;
+    float* vcat = site ? ar.take<float>((int64_t)B * KL * A2) : nullptr;
+    float* aw = ar.take<float>((int64_t)H * B * T * KLp);
+    float* pool = site ? nullptr : ar.take<float>((int64_t)2 * B * D);
 
     auto feed_forward = [&](int k, const float* in, float* out) {
         const std::string n = "feed_forward" + std::to_string(k);
         linear(c, in, D, w((n + ".in_proj.weight").c_str()), w((n + ".in_proj.bias").c_str()), hid, F, M, D, F, ACT_DOUBLE_SWISH);
         linear(c, hid, F, w((n + ".out_proj.weight").c_str()), w((n + ".out_proj.bias").c_str()), out, D, M, F, D, ACT_NONE, in, D);
     };
-    // tmp[b, :, h*vd : (h+1)*vd] = aw[h][b] (Tc x KL) . vcat[b] (KL x A/2)[:, h*vd : (h+1)*vd]
-    auto attn_apply = [&]() {
-        GemmArgs g;
-        g.A = aw; g.lda = KLp; g.sA0 = (long long)Tc * KLp; g.sA1 = (long long)B * Tc * KLp;
-        g.W = vcat; g.w_kn = 1; g.ldw = A2; g.sW0 = (long long)KL * A2; g.sW1 = vd;
-        g.C = tmp; g.ldc = A2; g.sC0 = (long long)Tc * A2; g.sC1 = vd;
-        g.M = Tc; g.N = vd; g.K = KL; g.nb0 = B; g.nb1 = H;
+    auto attn_apply = [&](const float* v, const char* ow, const char* ob) {  // src += out_proj(concat_h(aw_h . v_h)) + b; v [B, KL, A/2]
+        if (attn_av_out(c, aw, v, w(ow), w(ob), src, B, T, KL, KLp, H, vd, D)) return;
+        GemmArgs g;  // tmp[b, :, h*vd : (h+1)*vd] = aw[h][b] (T x KL) . v[b] (KL x A/2)[:, h*vd : (h+1)*vd]
+        g.A = aw; g.lda = KLp; g.sA0 = (long long)T * KLp; g.sA1 = (long long)B * T * KLp;
+        g.W = v; g.w_kn = 1; g.ldw = A2; g.sW0 = (long long)KL * A2; g.sW1 = vd;
+        g.C = tmp; g.ldc = A2; g.sC0 = (long long)T * A2; g.sC1 = vd;
+        g.M = T; g.N = vd; g.K = KL; g.nb0 = B; g.nb1 = H;
         gemm(c, g);
+        linear(c, tmp, A2, w(ow), w(ob), src, D, M, A2, D, ACT_NONE, src, D);
     };
-    auto conv_module = [&](int k, long long cache_off) {
+    auto conv_module = [&](int k) {
         const std::string n = "conv_module" + std::to_string(k);
         linear(c, src, D, w((n + ".pointwise_conv1.weight").c_str()), w((n + ".pointwise_conv1.bias").c_str()), hid, 2 * D, M, D, 2 * D);
-        z1_glu_conv(c, hid, online_pool_, SS, cache_off, d_slots, w((n + ".depthwise_conv.weight").c_str()),
-                    w((n + ".depthwise_conv.bias").c_str()), tmp, B, Tc, D, K);
+        if (site)
+            z1_glu_conv(c, hid, online_pool_, SS, k == 1 ? lay_.conv1[l] : lay_.conv2[l], site->d_slots, w((n + ".depthwise_conv.weight").c_str()),
+                        w((n + ".depthwise_conv.bias").c_str()), tmp, B, T, D, K);
+        else
+            glu_dwconv1d_dswish(c, hid, w((n + ".depthwise_conv.weight#kd").c_str()), w((n + ".depthwise_conv.bias").c_str()), tmp, B, T, D, K);
         linear(c, tmp, D, w((n + ".pointwise_conv2.weight").c_str()), w((n + ".pointwise_conv2.bias").c_str()), src, D, M, D, D, ACT_NONE, src, D);
     };
 
     feed_forward(1, x, src);
-    z1_pool(c, src, online_pool_, SS, lay_.nonlin[l], lay_.clen[l], d_slots, tmp, B, Tc, D);
-    linear(c, tmp, D, w("pooling.proj.weight"), nullptr, src, D, M, D, D, ACT_NONE, src, D);
-    // self_attn.streaming_forward: in_proj -> q | k | v | p; keys and values behind their caches; weights kept for the second use
+    if (site) {   // pooling: the running mean of the stream so far ...
+        z1_pool(c, src, online_pool_, SS, lay_.nonlin[l], lay_.clen[l], site->d_slots, tmp, B, T, D);
+        linear(c, tmp, D, w("pooling.proj.weight"), nullptr, src, D, M, D, D, ACT_NONE, src, D);
+    } else {      // ... or the utterance mean, projected, added to every frame
+        z1_mean(c, src, pool, B, T, D);
+        linear(c, pool, D, w("pooling.proj.weight"), nullptr, pool + (long long)B * D, D, B, D, D);
+        z1_add_bcast(c, src, pool + (long long)B * D, B, T, D);
+    }
+    // self_attn: in_proj -> q | k | v | p; the weights are kept for the second use
     linear(c, src, D, w("self_attn.in_proj.weight"), w("self_attn.in_proj.bias"), hid, inproj, M, D, inproj);
-    cat_shift(c, online_pool_, SS, lay_.key[l], d_slots, hid + A, inproj, kcat, B, L, Tc, A);
-    cat_shift(c, online_pool_, SS, lay_.val1[l], d_slots, hid + 2 * A, inproj, vcat, B, L, Tc, A2);
-    z1_attn(c, hid, inproj, kcat, pp, aw, B, Tc, L, KLp, H, A);
-    if (!attn_av_out(c, aw, vcat, w("self_attn.out_proj.weight"), w("self_attn.out_proj.bias"), src, B, Tc, KL, KLp, H, vd, D)) {
-        attn_apply();
-        linear(c, tmp, A2, w("self_attn.out_proj.weight"), w("self_attn.out_proj.bias"), src, D, M, A2, D, ACT_NONE, src, D);
+    const float* pp = pos_proj_cached(c, (site ? 2000 : 5000) + l, pe, D, w("self_attn.linear_pos.weight"), 2 * T - 1 + L, H * 4);
+    float* v = vcat;   // the values the weights apply to, [B, KL, A/2] dense
+    if (site) {        // keys and values behind their caches
+        cat_shift(c, online_pool_, SS, lay_.key[l], site->d_slots, hid + A, inproj, kcat, B, L, T, A);
+        cat_shift(c, online_pool_, SS, lay_.val1[l], site->d_slots, hid + 2 * A, inproj, vcat, B, L, T, A2);
+        z1_attn(c, hid, inproj, kcat, pp, aw, B, T, L, KLp, H, A);
+    } else {           // columns [2A, 2A + A/2) of the projected rows
+        attn_scores_softmax(c, hid, inproj, pp, aw, B, T, KLp, H, A / H, A, 2 * A + A2);
+        v = ar.take<float>((int64_t)M * A2);
+        copy_cols(c, hid, inproj, 2 * A, v, A2, 0, M, A2);
     }
-    conv_module(1, lay_.conv1[l]);
+    attn_apply(v, "self_attn.out_proj.weight", "self_attn.out_proj.bias");
+    conv_module(1);
     feed_forward(2, src, src);
-    // self_attn.streaming_forward2
-    linear(c, src, D, w("self_attn.in_proj2.weight"), nullptr, hid, A2, M, D, A2);
-    cat_shift(c, online_pool_, SS, lay_.val2[l], d_slots, hid, A2, vcat, B, L, Tc, A2);
-    if (!attn_av_out(c, aw, vcat, w("self_attn.out_proj2.weight"), w("self_attn.out_proj2.bias"), src, B, Tc, KL, KLp, H, vd, D)) {
-        attn_apply();
-        linear(c, tmp, A2, w("self_attn.out_proj2.weight"), w("self_attn.out_proj2.bias"), src, D, M, A2, D, ACT_NONE, src, D);
+    if (site) {   // self_attn.streaming_forward2
+        linear(c, src, D, w("self_attn.in_proj2.weight"), nullptr, hid, A2, M, D, A2);
+        cat_shift(c, online_pool_, SS, lay_.val2[l], site->d_slots, hid, A2, vcat, B, L, T, A2);
+    } else {
+        v = ar.take<float>((int64_t)M * A2);
+        linear(c, src, D, w("self_attn.in_proj2.weight"), nullptr, v, A2, M, D, A2);
     }
-    conv_module(2, lay_.conv2[l]);
+    attn_apply(v, "self_attn.out_proj2.weight", "self_attn.out_proj2.bias");
+    conv_module(2);
     feed_forward(3, src, src);
     z1_norm_bypass(c, src, x, w("norm_final.eps"), w("bypass_scale"), x, M, D);
     ar.rewind(mark);
 }
 
-// one chunk for B streams: x [B, T, 80] (log-floored) -> enc [B, T', J]
-float* Engine::zip1_chunk(const Ctx& c, const float* x, const int* d_slots, int B, int* Tp_out) {
+// Zipformer.forward / .streaming_forward behind the embed: the stacks over x0 [B*Tc, dim[0]] (site as for zip1_layer), AttentionDownsample
+// by 2 and joiner.encoder_proj (applied by the ONNX encoder wrapper) -> enc [B, T', J]; a null enc is taken from the arena here, last.
+// Offline taps: 1 + i = the output of stack i into *tap_ptr / *tap_dim, and null is returned (streaming passes tap = -1).
+float* Engine::zip1_stacks(const Ctx& c, float* x0, int B, int Tc, const StreamSite* site, float* enc, int tap, float** tap_ptr, int* tap_dim) {
     const Model& m = *model_;
     const Config& cf = m.cfg();
     Arena& ar = *c.arena;
-    int Tc = 0;
-    float* cur = zip1_embed(c, x, B, cf.chunk_T, &Tc);
     const int M = B * Tc;
     float* outputs[kMaxStacks] = {nullptr};
+    float* cur = x0;
     int Dcur = cf.dim[0], l = 0;
     auto skip_layer = [&](int i) {  // Zipformer._init_skip_modules
         if (i <= 1 || cf.ds[i - 1] <= cf.ds[i]) return -1;
@@ -162,178 +184,38 @@ float* Engine::zip1_chunk(const Ctx& c, const float* x, const int* d_slots, int 
         return -1;
     };
     for (int si = 0; si < cf.ns; si++) {
-        const int D = cf.dim[si], ds = cf.ds[si], L = cf.left[si], H = cf.heads[si];
+        const int D = cf.dim[si], ds = cf.ds[si], L = site ? cf.left[si] : 0, Td = (Tc + ds - 1) / ds;
         const int k = skip_layer(si);
         if (k >= 0) {
             float* y = ar.take<float>((int64_t)M * Dcur);
             z1_combine(c, outputs[k], cf.dim[k], cur, Dcur, m.wf("encoder.skip_modules.%d.weight1", si), nullptr, 1, B, Tc, Tc, y);
             cur = y;
         }
-        char pfx[96];
+        // the stack's layers, in place on xs [B*Td, D]
+        auto layers = [&](const char* fmt, float* xs) {
+            const float* pe = c.dry ? nullptr : sinus_pos_emb(Td, L, D);
+            for (int li = 0; li < cf.nlayer[si]; li++, l++) {
+                char pfx[96];
+                snprintf(pfx, sizeof pfx, fmt, si, li);
+                zip1_layer(c, si, pfx, l, xs, pe, B, Td, site);
+            }
+        };
         if (ds == 1) {
             K2_REQUIRE(D == Dcur, "zipformer: stack %d has downsampling 1 but changes width %d -> %d", si, Dcur, D);
             float* xi = ar.take<float>((int64_t)M * D);  // the layers run in place; earlier outputs stay intact for skip connections
             if (!c.dry) K2_HIP(hipMemcpyAsync(xi, cur, sizeof(float) * (size_t)M * D, hipMemcpyDeviceToDevice, c.stream));
-            for (int li = 0; li < cf.nlayer[si]; li++, l++) {
-                snprintf(pfx, sizeof pfx, "encoder.encoders.%d.layers.%d.", si, li);
-                const float* pp = c.dry ? nullptr : pos_proj_cached(c, 2000 + l, sinus_pos_emb(Tc, L, D), D, m.w(std::string(pfx) + "self_attn.linear_pos.weight"), 2 * Tc - 1 + L, H * 4);
-                zip1_layer(c, si, pfx, l, xi, pp, d_slots, B, Tc, L);
-            }
+            layers("encoder.encoders.%d.layers.%d.", xi);
             cur = xi;
         } else {
             K2_REQUIRE(D >= Dcur, "zipformer: stack %d narrows %d -> %d (unsupported)", si, Dcur, D);
-            const int Td = (Tc + ds - 1) / ds;
             float* y = ar.take<float>((int64_t)M * D);
             int64_t mark = ar.mark();
             float* xd = ar.take<float>((int64_t)B * Td * D);
             z1_attn_downsample(c, cur, m.wf("encoder.encoders.%d.downsample.query", si), xd, B, Tc, Dcur, D, ds);
             if (D > Dcur) {  // extra channels: extra_proj over the ds frames of a group side by side (= a reshape when ds | Tc)
-                K2_REQUIRE(Tc % ds == 0, "zipformer: %d frames per chunk not divisible by downsampling %d with widening stacks", Tc, ds);
-                linear(c, cur, ds * Dcur, m.wf("encoder.encoders.%d.downsample.extra_proj.weight", si), nullptr, xd + Dcur, D, B * Td,
-                       ds * Dcur, D - Dcur);
-            }
-            for (int li = 0; li < cf.nlayer[si]; li++, l++) {
-                snprintf(pfx, sizeof pfx, "encoder.encoders.%d.encoder.layers.%d.", si, li);
-                const float* pp = c.dry ? nullptr : pos_proj_cached(c, 2000 + l, sinus_pos_emb(Td, L, D), D, m.w(std::string(pfx) + "self_attn.linear_pos.weight"), 2 * Td - 1 + L, H * 4);
-                zip1_layer(c, si, pfx, l, xd, pp, d_slots, B, Td, L);
-            }
-            z1_combine(c, cur, Dcur, xd, D, m.wf("encoder.encoders.%d.out_combiner.weight1", si), m.wf("encoder.encoders.%d.upsample.bias", si),
-                       ds, B, Tc, Td, y);
-            ar.rewind(mark);
-            cur = y;
-            Dcur = D;
-        }
-        outputs[si] = cur;
-    }
-    const int Tp = (Tc + 1) / 2;
-    float* dsd = ar.take<float>((int64_t)B * Tp * Dcur);
-    z1_attn_downsample(c, cur, m.w("encoder.downsample_output.query"), dsd, B, Tc, Dcur, Dcur, 2);
-    float* enc = ar.take<float>((int64_t)B * Tp * cf.J);
-    linear(c, dsd, Dcur, m.w("joiner.encoder_proj.weight"), m.w("joiner.encoder_proj.bias"), enc, cf.J, B * Tp, Dcur, cf.J);
-    *Tp_out = Tp;
-    return enc;
-}
-
-// ------------------------------------------------------------------------------------------------------------------------
-// Offline Zipformer v1: Model_type "zipformer" in OfflineRecognizer's switch (OfflineRecognizer.cs:40-44 -> OfflineProjOfTransducer,
-// x [B,T,80] with x_lens = T, :48-92).  icefall's pruned_transducer_stateless7 Zipformer.forward: the modules of the streaming path
-// with mean pooling over the utterance, attention over the whole utterance and centred depthwise convolutions -- i.e. the offline
-// Zipformer2 kernels (32-row attention strips on the MFMA, fused attention-apply + out_proj, LDS-tiled GLU + depthwise conv) with
-// v1's row layout (q | k | v | p, head size attention_dim / heads).
-// ------------------------------------------------------------------------------------------------------------------------
-void Engine::zip1_layer_offline(const Ctx& c, int si, const std::string& pfx, int l, float* x, const float* pe, int B, int T) {
-    const Model& m = *model_;
-    const Config& cf = m.cfg();
-    const int D = cf.dim[si], A = cf.att[si], H = cf.heads[si], F = cf.ff[si], K = cf.kern[si];
-    const int M = B * T, Tp = (T + 3) & ~3, A2 = A / 2, vd = A2 / H, hd = A / H, inproj = 2 * A + A2 + 4 * H;
-    auto w = [&](const char* suffix) { return m.w(pfx + suffix); };
-    Arena& ar = *c.arena;
-    int64_t mark = ar.mark();
-    float* src = ar.take<float>((int64_t)M * D);
-    float* hid = ar.take<float>((int64_t)M * std::max({F, 2 * D, inproj}));
-    float* tmp = ar.take<float>((int64_t)M * std::max(D, A2));
-    float* aw = ar.take<float>((int64_t)H * B * T * Tp);
-    float* pool = ar.take<float>((int64_t)2 * B * D);
-
-    auto feed_forward = [&](int k, const float* in, float* out) {
-        const std::string n = "feed_forward" + std::to_string(k);
-        linear(c, in, D, w((n + ".in_proj.weight").c_str()), w((n + ".in_proj.bias").c_str()), hid, F, M, D, F, ACT_DOUBLE_SWISH);
-        linear(c, hid, F, w((n + ".out_proj.weight").c_str()), w((n + ".out_proj.bias").c_str()), out, D, M, F, D, ACT_NONE, in, D);
-    };
-    auto attn_apply = [&](const float* v, int ldv, const char* ow, const char* ob) {  // src += out_proj(concat_h(aw_h . v_h)) + b
-        if (ldv == A2 && attn_av_out(c, aw, v, w(ow), w(ob), src, B, T, T, Tp, H, vd, D)) return;
-        GemmArgs g;
-        g.A = aw; g.lda = Tp; g.sA0 = (long long)T * Tp; g.sA1 = (long long)B * T * Tp;
-        g.W = v; g.w_kn = 1; g.ldw = ldv; g.sW0 = (long long)T * ldv; g.sW1 = vd;
-        g.C = tmp; g.ldc = A2; g.sC0 = (long long)T * A2; g.sC1 = vd;
-        g.M = T; g.N = vd; g.K = T; g.nb0 = B; g.nb1 = H;
-        gemm(c, g);
-        linear(c, tmp, A2, w(ow), w(ob), src, D, M, A2, D, ACT_NONE, src, D);
-    };
-    auto conv_module = [&](int k) {
-        const std::string n = "conv_module" + std::to_string(k);
-        linear(c, src, D, w((n + ".pointwise_conv1.weight").c_str()), w((n + ".pointwise_conv1.bias").c_str()), hid, 2 * D, M, D, 2 * D);
-        glu_dwconv1d_dswish(c, hid, w((n + ".depthwise_conv.weight#kd").c_str()), w((n + ".depthwise_conv.bias").c_str()), tmp, B, T, D, K);
-        linear(c, tmp, D, w((n + ".pointwise_conv2.weight").c_str()), w((n + ".pointwise_conv2.bias").c_str()), src, D, M, D, D, ACT_NONE, src, D);
-    };
-
-    feed_forward(1, x, src);
-    z1_mean(c, src, pool, B, T, D);                                               // pooling: the utterance mean, projected, added to every frame
-    linear(c, pool, D, w("pooling.proj.weight"), nullptr, pool + (long long)B * D, D, B, D, D);
-    z1_add_bcast(c, src, pool + (long long)B * D, B, T, D);
-    linear(c, src, D, w("self_attn.in_proj.weight"), w("self_attn.in_proj.bias"), hid, inproj, M, D, inproj);
-    const float* pp = pos_proj_cached(c, 5000 + l, pe, D, w("self_attn.linear_pos.weight"), 2 * T - 1, H * 4);
-    attn_scores_softmax(c, hid, inproj, pp, aw, B, T, Tp, H, hd, A, 2 * A + A2);
-    {   // values: columns [2A, 2A + A/2) of the projected rows -> contiguous [M, A/2] (the fused kernel wants them dense)
-        float* v = ar.take<float>((int64_t)M * A2);
-        copy_cols(c, hid, inproj, 2 * A, v, A2, 0, M, A2);
-        attn_apply(v, A2, "self_attn.out_proj.weight", "self_attn.out_proj.bias");
-    }
-    conv_module(1);
-    feed_forward(2, src, src);
-    {
-        float* v2 = ar.take<float>((int64_t)M * A2);
-        linear(c, src, D, w("self_attn.in_proj2.weight"), nullptr, v2, A2, M, D, A2);
-        attn_apply(v2, A2, "self_attn.out_proj2.weight", "self_attn.out_proj2.bias");
-    }
-    conv_module(2);
-    feed_forward(3, src, src);
-    z1_norm_bypass(c, src, x, w("norm_final.eps"), w("bypass_scale"), x, M, D);
-    ar.rewind(mark);
-}
-
-// taps: 0 = embed output; 1+i = output of stack i
-float* Engine::zip1_forward(const Ctx& c, const float* x, int B, int T, int* Tp_out, int tap, float** tap_ptr, int* tap_rows, int* tap_dim) {
-    const Model& m = *model_;
-    const Config& cf = m.cfg();
-    Arena& ar = *c.arena;
-    const int Tc0 = (T - 7) / 2;
-    K2_REQUIRE(T >= 9 && Tc0 > 0, "encoder: %d input frames are too few", T);
-    const int Tp = (Tc0 + 1) / 2;
-    float* enc = ar.take<float>((int64_t)B * Tp * cf.J);
-    int Tc = 0;
-    float* cur = zip1_embed(c, x, B, T, &Tc);
-    if (tap_rows) *tap_rows = B * Tc;
-    *Tp_out = Tp;
-    if (tap == 0) { *tap_ptr = cur; *tap_dim = cf.dim[0]; return nullptr; }
-    const int M = B * Tc;
-    float* outputs[kMaxStacks] = {nullptr};
-    int Dcur = cf.dim[0], l = 0;
-    auto skip_layer = [&](int i) {
-        if (i <= 1 || cf.ds[i - 1] <= cf.ds[i]) return -1;
-        for (int j = i - 2; j >= 0; j--)
-            if (cf.ds[j] <= cf.ds[i] || j == 0) return j;
-        return -1;
-    };
-    for (int si = 0; si < cf.ns; si++) {
-        const int D = cf.dim[si], ds = cf.ds[si];
-        const int k = skip_layer(si);
-        if (k >= 0) {
-            float* y = ar.take<float>((int64_t)M * Dcur);
-            z1_combine(c, outputs[k], cf.dim[k], cur, Dcur, m.wf("encoder.skip_modules.%d.weight1", si), nullptr, 1, B, Tc, Tc, y);
-            cur = y;
-        }
-        char pfx[96];
-        if (ds == 1) {
-            K2_REQUIRE(D == Dcur, "zipformer: stack %d has downsampling 1 but changes width %d -> %d", si, Dcur, D);
-            float* xi = ar.take<float>((int64_t)M * D);
-            if (!c.dry) K2_HIP(hipMemcpyAsync(xi, cur, sizeof(float) * (size_t)M * D, hipMemcpyDeviceToDevice, c.stream));
-            const float* pe = c.dry ? nullptr : sinus_pos_emb(Tc, 0, D);
-            for (int li = 0; li < cf.nlayer[si]; li++, l++) {
-                snprintf(pfx, sizeof pfx, "encoder.encoders.%d.layers.%d.", si, li);
-                zip1_layer_offline(c, si, pfx, l, xi, pe, B, Tc);
-            }
-            cur = xi;
-        } else {
-            K2_REQUIRE(D >= Dcur, "zipformer: stack %d narrows %d -> %d (unsupported)", si, Dcur, D);
-            const int Td = (Tc + ds - 1) / ds;
-            float* y = ar.take<float>((int64_t)M * D);
-            int64_t mark = ar.mark();
-            float* xd = ar.take<float>((int64_t)B * Td * D);
-            z1_attn_downsample(c, cur, m.wf("encoder.encoders.%d.downsample.query", si), xd, B, Tc, Dcur, D, ds);
-            if (D > Dcur) {  // extra channels: extra_proj over the group's ds frames side by side
                 const float* grp = cur;
-                if (Tc % ds != 0) {
+                if (Tc % ds != 0) {   // whole utterances only: the last group padded in a copy
+                    K2_REQUIRE(!site, "zipformer: %d frames per chunk not divisible by downsampling %d with widening stacks", Tc, ds);
                     float* gb = ar.take<float>((int64_t)B * Td * ds * Dcur);
                     z1_group_rows(c, cur, gb, B, Tc, Dcur, ds);
                     grp = gb;
@@ -341,11 +223,7 @@ float* Engine::zip1_forward(const Ctx& c, const float* x, int B, int T, int* Tp_
                 linear(c, grp, ds * Dcur, m.wf("encoder.encoders.%d.downsample.extra_proj.weight", si), nullptr, xd + Dcur, D, B * Td, ds * Dcur,
                        D - Dcur);
             }
-            const float* pe = c.dry ? nullptr : sinus_pos_emb(Td, 0, D);
-            for (int li = 0; li < cf.nlayer[si]; li++, l++) {
-                snprintf(pfx, sizeof pfx, "encoder.encoders.%d.encoder.layers.%d.", si, li);
-                zip1_layer_offline(c, si, pfx, l, xd, pe, B, Td);
-            }
+            layers("encoder.encoders.%d.encoder.layers.%d.", xd);
             z1_combine(c, cur, Dcur, xd, D, m.wf("encoder.encoders.%d.out_combiner.weight1", si), m.wf("encoder.encoders.%d.upsample.bias", si),
                        ds, B, Tc, Td, y);
             ar.rewind(mark);
@@ -355,10 +233,37 @@ float* Engine::zip1_forward(const Ctx& c, const float* x, int B, int T, int* Tp_
         outputs[si] = cur;
         if (tap == si + 1) { *tap_ptr = cur; *tap_dim = Dcur; return nullptr; }
     }
+    const int Tp = (Tc + 1) / 2;
     float* dsd = ar.take<float>((int64_t)B * Tp * Dcur);
     z1_attn_downsample(c, cur, m.w("encoder.downsample_output.query"), dsd, B, Tc, Dcur, Dcur, 2);
+    if (!enc) enc = ar.take<float>((int64_t)B * Tp * cf.J);
     linear(c, dsd, Dcur, m.w("joiner.encoder_proj.weight"), m.w("joiner.encoder_proj.bias"), enc, cf.J, B * Tp, Dcur, cf.J);
     return enc;
+}
+
+// one chunk for B streams: x [B, T, 80] (log-floored) -> enc [B, T', J]
+float* Engine::zip1_chunk(const Ctx& c, const float* x, const int* d_slots, int B, int* Tp_out) {
+    int Tc = 0;
+    float* x0 = zip1_embed(c, x, B, model_->cfg().chunk_T, &Tc);
+    const StreamSite site{d_slots};
+    *Tp_out = (Tc + 1) / 2;
+    return zip1_stacks(c, x0, B, Tc, &site, nullptr, -1, nullptr, nullptr);
+}
+
+// Offline Zipformer v1: Model_type "zipformer" in OfflineRecognizer's switch (OfflineRecognizer.cs:40-44 -> OfflineProjOfTransducer,
+// x [B,T,80] with x_lens = T, :48-92); icefall's pruned_transducer_stateless7 Zipformer.forward.  taps: 0 = embed output; 1+i = stack i
+float* Engine::zip1_forward(const Ctx& c, const float* x, int B, int T, int* Tp_out, int tap, float** tap_ptr, int* tap_rows, int* tap_dim) {
+    const Config& cf = model_->cfg();
+    const int Tc0 = (T - 7) / 2;
+    K2_REQUIRE(T >= 9 && Tc0 > 0, "encoder: %d input frames are too few", T);
+    const int Tp = (Tc0 + 1) / 2;
+    float* enc = c.arena->take<float>((int64_t)B * Tp * cf.J);   // output first so that everything after it can be rewound
+    int Tc = 0;
+    float* x0 = zip1_embed(c, x, B, T, &Tc);
+    if (tap_rows) *tap_rows = B * Tc;
+    *Tp_out = Tp;
+    if (tap == 0) { *tap_ptr = x0; *tap_dim = cf.dim[0]; return nullptr; }
+    return zip1_stacks(c, x0, B, Tc, nullptr, enc, tap, tap_ptr, tap_dim);
 }
 
 }  // namespace k2hip
