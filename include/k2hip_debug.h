@@ -66,7 +66,8 @@ int32_t k2hip_debug_gemm_run(k2hip_model_t* model, const float* A, const float* 
  * dwconv7x7; the Conformer's conformer_qprep, conformer_scores_softmax, conformer_softmax_shift, conformer_softmax_shift_stream,
  * slice_rows, dwconv_valid_dswish; Zipformer v1's z1_pool, z1_attn, z1_glu_conv, z1_norm_bypass, z1_attn_downsample, z1_combine, z1_mean,
  * z1_add_bcast, z1_group_rows; the LSTM's lstm_cell, lstm_cell_rows, lstm_add_frame, lstm_norm_frame, add_inplace, gather_rows,
- * scatter_rows; basicnorm, conv0_pad1_dswish, conv0_nopad_dswish; gemm and gemm_glu_causal_conv: see below) on host operands, on the
+ * scatter_rows; basicnorm, conv0_pad1_dswish, conv0_nopad_dswish; the kernels around the layers, gemm and gemm_glu_causal_conv: see below)
+ * on host operands, on the
  * engine's stream.  iargs: the launcher's integer arguments in its own order (a RingRef counts as slot_stride, off; downsample_full's
  * segments put n, ld[n], col1[n], lz_Td, lz_ds, lz_Do in front; long long strides and offsets -- slot_stride, off, avg_off, len_off,
  * ldgx, SY, pstride, lstride, add_inplace's n -- are integer arguments like the ints).  A float argument (`scaling` of conformer_qprep
@@ -116,6 +117,23 @@ int32_t k2hip_debug_gemm_run(k2hip_model_t* model, const float* A, const float* 
  *     int32, scores [R][nbest] -- and flag [1] int32, the search-output block's status word (1: an entry outgrew max_tokens and was not
  *     written); ints R, Tp, V, beam, nbest, max_tokens.  V here is free, not the model's.  The kernel stores straight into the guarded
  *     buffers, so what it does not write keeps the caller's fill.
+ * The kernels around the encoder layers (tests/test_outer_kernels_gpu.py; cases and references in tests/outer_kernels.py), arguments in
+ * the launcher's own order as above, a bool as an int:
+ *   offline front end: "pad_logfloor" (bufs packed, d_off int64 [B], d_len int64 [B], out; ints B, L), "pad_logfloor_dense" (bufs feats,
+ *     out; ints n_each, B, L), "conv0_swoosh" (as conv0_nopad_dswish), and "gather_samples": the launcher takes a device table of source
+ *     pointers, which the hook builds from float offsets into ONE uploaded samples buffer -- ints B, nmax, off[0 .. B); bufs samples,
+ *     n (int64 [B]), dst [B][nmax].  The samples buffer starts on a 256-byte boundary, so an offset that is a multiple of 4 puts a
+ *     source on a 16-byte boundary and any other offset off it.
+ *   streaming state movers (csrc/online.hip): "convnext_cat" (bufs a3, pool, slots, cat, byp; ints slot_stride, embed_off, B, T3, Tc, F,
+ *     C), "cat_shift" (bufs pool, slots, newrows, cat; ints slot_stride, off, ldn, B, L, Tc, width, tanh_gated), "cat_keep" (the same
+ *     with keep_back last), "fifo_append" (bufs fifo, src, slots, pos; ints cap, feat, G, nf), "fifo_gather" (bufs fifo, slots, head, x;
+ *     ints cap, feat, B, T), "zero_floats" and "logfloor_inplace" (one buffer; int n).
+ *   small elementwise kernels: "glu_sigmoid" (bufs x, y; ints M, D), "tanh_gate" (bufs x, y; ints M, Hc), "convert_channels" (bufs x, y;
+ *     ints M, Din, Dout), "copy_cols" (bufs x, y; ints ldx, xcol0, ldy, ycol0, M, n), "tanh_add" (bufs enc, dec, y; ints dec_stride, N, J).
+ *   search tail (csrc/greedy.hip): "argmax_rows" and "argmax_first_rows" (bufs logits, tok int32 [N]; ints ld, N, V), "log_softmax_rows"
+ *     (one buffer, in place; ints M, V), "ctc_collapse" (bufs tok int32 [B][Tp], frame_off int32 [B] or null, tokens int64
+ *     [B][max_tokens], timestamps, n_tokens, trail, any, overflow (int32; the kernel only ever raises overflow: pass it as 0); ints B, Tp,
+ *     max_tokens), "first_emit_frame" (bufs tok int32 [B][Tp], t0 int32 [1]; ints B, Tp, skip1).
  * One op launches nothing (tests/test_search_ties_gpu.py):
  *   "greedy_screen_counts": no int arguments, one buffer of 2 int64 that the hook fills (whatever out_mask says) with the model's
  *     counters since it was created: [0] rounds of the persistent large-vocabulary greedy search (csrc/greedy.hip k_greedy) that its

@@ -445,16 +445,6 @@ __global__ void k_tanh_gate(const float* __restrict__ x, float* __restrict__ y, 
     float4 s = xr[q], a = xr[H4 + q];
     reinterpret_cast<float4*>(y)[i] = make_float4(a.x * fast_tanh(s.x), a.y * fast_tanh(s.y), a.z * fast_tanh(s.z), a.w * fast_tanh(s.w));
 }
-// a[m, n] *= x[m*ldx + col0 + n]
-__global__ void k_mul_cols(float* __restrict__ a, const float* __restrict__ x, int ldx, int col0, long long n4, int N4) {
-    long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n4) return;
-    long long m = i / N4;
-    int q = (int)(i % N4);
-    float4 v = reinterpret_cast<float4*>(a)[i];
-    float4 s = *reinterpret_cast<const float4*>(x + m * ldx + col0 + 4 * q);
-    reinterpret_cast<float4*>(a)[i] = make_float4(v.x * s.x, v.y * s.y, v.z * s.z, v.w * s.w);
-}
 
 // ---- ConvolutionModule: GLU + depthwise Conv1d over time (zero pad K/2) + bias + SwooshR
 //  x2: [B,T,2D] (in_proj output: value | gate), y: [B,T,D], w: [K][D].
@@ -776,10 +766,6 @@ void glu_sigmoid(const Ctx& ctx, const float* x, float* y, int M, int D) {
 void tanh_gate(const Ctx& ctx, const float* x, float* y, int M, int Hc) {
     long long n4 = (long long)M * Hc / 4;
     LAUNCH(k_tanh_gate, dim3(nblocks(n4, 256)), dim3(256), x, y, n4, Hc / 4);
-}
-void mul_cols(const Ctx& ctx, float* a, const float* x, int ldx, int col0, int M, int N) {
-    long long n4 = (long long)M * N / 4;
-    LAUNCH(k_mul_cols, dim3(nblocks(n4, 256)), dim3(256), a, x, ldx, col0, n4, N / 4);
 }
 // outputs per thread by grid size: 32-frame workgroups unless they would number fewer than ~2 per CU
 static int dw1d_tt(int B, int T, int D) {

@@ -1900,7 +1900,8 @@ void Engine::debug_gemm_host(const float* hA, const float* hW, const float* hb, 
     K2_HIP(copy_blocking(hC, C, sizeof(float) * (size_t)M * ldo, hipMemcpyDeviceToHost));
 }
 
-// test hook: ONE launch of a launcher of kernels.h on the caller's host operands (tests/test_kernels_gpu.py, test_family_kernels_gpu.py).  Buffer k of the call is
+// test hook: ONE launch of a launcher of kernels.h on the caller's host operands (tests/test_kernels_gpu.py, test_family_kernels_gpu.py,
+// test_outer_kernels_gpu.py).  Buffer k of the call is
 // uploaded into an allocation with kGuard bytes of 0xff (NaN) on either side, so a read past either end whose value reaches the result
 // shows as NaN; after the launch the guards must still hold 0xff, else a write went past the buffer and the call fails naming it.
 // A launcher that refuses the shape (a false return, a K2_REQUIRE) fails as K2HIP_ERR_UNSUPPORTED before anything is launched or
@@ -2370,11 +2371,129 @@ void Engine::debug_op_host(const char* op, const int64_t* iargs, int n_iargs, vo
             float *x = P(), *le = P(), *y = P();
             const int M = I(), D = I();
             basicnorm(c, x, le, y, M, D);
-        } else if (name == "conv0_pad1_dswish" || name == "conv0_nopad_dswish") {
+        } else if (name == "conv0_pad1_dswish" || name == "conv0_nopad_dswish" || name == "conv0_swoosh") {
             float *x = P(), *w = P(), *b = P(), *y = P();
             const int B = I(), T = I(), Fq = I();
             if (name == "conv0_pad1_dswish") conv0_pad1_dswish(c, x, w, b, y, B, T, Fq);
-            else conv0_nopad_dswish(c, x, w, b, y, B, T, Fq);
+            else if (name == "conv0_nopad_dswish") conv0_nopad_dswish(c, x, w, b, y, B, T, Fq);
+            else conv0_swoosh(c, x, w, b, y, B, T, Fq);
+        } else if (name == "pad_logfloor") {
+            float* packed = P();
+            const long long *off = reinterpret_cast<const long long*>(P()), *len = reinterpret_cast<const long long*>(P());
+            float* out = P();
+            const int B = I();
+            const long long Lf = L();
+            pad_logfloor(c, packed, off, len, out, B, Lf);
+        } else if (name == "pad_logfloor_dense") {
+            float* feats = P();
+            const long long n_each = L();
+            float* out = P();
+            const int B = I();
+            const long long Lf = L();
+            pad_logfloor_dense(c, feats, n_each, out, B, Lf);
+        } else if (name == "gather_samples") {
+            // ints B, nmax, off[0 .. B): the float offset of every stream's source inside the samples buffer (the device table of
+            // source pointers is built here); bufs samples, n (int64 [B]), dst
+            const int B = I();
+            const long long nmax = L();
+            K2_REQUIRE(B > 0 && B <= 64, "debug_op_run gather_samples: B = %d", B);
+            std::vector<long long> off((size_t)B);
+            for (auto& o : off) o = L();
+            float* samples = P();
+            const long long* n = reinterpret_cast<const long long*>(P());
+            float* dst = P();
+            K2_REQUIRE(samples && n && dst && buf_bytes[1] >= 8 * (int64_t)B, "debug_op_run gather_samples: three buffers are needed");
+            std::vector<const float*> h((size_t)B);
+            for (int b = 0; b < B; b++) {
+                K2_REQUIRE(off[(size_t)b] >= 0 && 4 * off[(size_t)b] <= buf_bytes[0], "debug_op_run gather_samples: offset %lld", off[(size_t)b]);
+                h[(size_t)b] = samples + off[(size_t)b];
+            }
+            const float** table = nullptr;
+            K2_HIP(hipMalloc(&table, sizeof(float*) * (size_t)B));
+            d.base.push_back(reinterpret_cast<char*>(table));
+            K2_HIP(copy_blocking(table, h.data(), sizeof(float*) * (size_t)B, hipMemcpyHostToDevice));
+            gather_samples(c, table, n, dst, B, nmax);
+        } else if (name == "convnext_cat") {
+            float *a3 = P(), *pool = P();
+            const long long ss = L(), off = L();
+            const int* slots = reinterpret_cast<const int*>(P());
+            float *cat = P(), *byp = P();
+            const int B = I(), T3 = I(), Tc = I(), Fq = I(), Cc = I();
+            convnext_cat(c, a3, pool, ss, off, slots, cat, byp, B, T3, Tc, Fq, Cc);
+        } else if (name == "cat_shift" || name == "cat_keep") {
+            float* pool = P();
+            const long long ss = L(), off = L();
+            const int* slots = reinterpret_cast<const int*>(P());
+            float* newrows = P();
+            const int ldn = I();
+            float* cat = P();
+            const int B = I(), Lc = I(), Tc = I(), width = I(), last = I();   // last: tanh_gated (a bool as an int) / keep_back
+            if (name == "cat_shift") cat_shift(c, pool, ss, off, slots, newrows, ldn, cat, B, Lc, Tc, width, last != 0);
+            else cat_keep(c, pool, ss, off, slots, newrows, ldn, cat, B, Lc, Tc, width, last);
+        } else if (name == "fifo_append") {
+            float* fifo = P();
+            const int cap = I(), feat = I();
+            float* src = P();
+            const int *slots = reinterpret_cast<const int*>(P()), *pos = reinterpret_cast<const int*>(P());
+            const int G = I(), nf = I();
+            fifo_append(c, fifo, cap, feat, src, slots, pos, G, nf);
+        } else if (name == "fifo_gather") {
+            float* fifo = P();
+            const int cap = I(), feat = I();
+            const int *slots = reinterpret_cast<const int*>(P()), *head = reinterpret_cast<const int*>(P());
+            float* x = P();
+            const int B = I(), T = I();
+            fifo_gather(c, fifo, cap, feat, slots, head, x, B, T);
+        } else if (name == "zero_floats" || name == "logfloor_inplace") {
+            float* p = P();
+            const long long n = L();
+            if (name == "zero_floats") zero_floats(c, p, n);
+            else logfloor_inplace(c, p, n);
+        } else if (name == "glu_sigmoid" || name == "tanh_gate") {
+            float *x = P(), *y = P();
+            const int M = I(), D = I();
+            if (name == "glu_sigmoid") glu_sigmoid(c, x, y, M, D);
+            else tanh_gate(c, x, y, M, D);
+        } else if (name == "convert_channels") {
+            float *x = P(), *y = P();
+            const int M = I(), Din = I(), Dout = I();
+            convert_channels(c, x, y, M, Din, Dout);
+        } else if (name == "copy_cols") {
+            float* x = P();
+            const int ldx = I(), xcol0 = I();
+            float* y = P();
+            const int ldy = I(), ycol0 = I(), M = I(), n = I();
+            copy_cols(c, x, ldx, xcol0, y, ldy, ycol0, M, n);
+        } else if (name == "tanh_add") {
+            float *enc = P(), *dec = P();
+            const int dec_stride = I();
+            float* y = P();
+            const int N = I(), J = I();
+            tanh_add(c, enc, dec, dec_stride, y, N, J);
+        } else if (name == "argmax_rows" || name == "argmax_first_rows") {
+            float* logits = P();
+            const int ld = I(), N = I(), V = I();
+            int* tok = reinterpret_cast<int*>(P());
+            if (name == "argmax_rows") argmax_rows(c, logits, ld, N, V, tok);
+            else argmax_first_rows(c, logits, ld, N, V, tok);
+        } else if (name == "log_softmax_rows") {
+            float* x = P();
+            const int M = I(), V = I();
+            log_softmax_rows(c, x, M, V);
+        } else if (name == "ctc_collapse") {
+            const int* tok = reinterpret_cast<const int*>(P());
+            const int B = I(), Tp = I();
+            const int* frame_off = reinterpret_cast<const int*>(P());
+            long long* tokens = reinterpret_cast<long long*>(P());
+            int *timestamps = reinterpret_cast<int*>(P()), *n_tokens = reinterpret_cast<int*>(P());
+            const int max_tokens = I();
+            int *trail = reinterpret_cast<int*>(P()), *any = reinterpret_cast<int*>(P()), *overflow = reinterpret_cast<int*>(P());
+            ctc_collapse(c, tok, B, Tp, frame_off, tokens, timestamps, n_tokens, max_tokens, trail, any, overflow);
+        } else if (name == "first_emit_frame") {
+            const int* tok = reinterpret_cast<const int*>(P());
+            const int B = I(), Tp = I(), skip1 = I();
+            int* t0 = reinterpret_cast<int*>(P());
+            first_emit_frame(c, tok, B, Tp, skip1, t0);
         } else {
             failf(K2HIP_ERR_INVALID, "debug_op_run: unknown op '%s'", op);
         }

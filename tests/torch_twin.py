@@ -22,21 +22,24 @@ def _ints(meta, key):
 
 
 # ----------------------------------------------------------------------------- fbank
-def fbank_np(samples: np.ndarray, meta: dict) -> np.ndarray:
+def fbank_parts(samples: np.ndarray, meta: dict, f32_tables: bool = False):
+    """The front end up to the mel energies, in float64: the windowed frames [nf, N], the mel weights [nb, P / 2] and the frames as
+    cut (scaled, before DC removal) [nf, N].  f32_tables: the window, the mel weights, preemph_coeff and input_scale rounded to
+    float32 first, as the model's tables and FbankArgs hold them."""
     sr = int(meta["sample_rate"])
     N = sr * int(meta["frame_length_ms"]) // 1000
     S = sr * int(meta["frame_shift_ms"]) // 1000
     P = 1 << (N - 1).bit_length()
     nb = int(meta["feature_dim"])
-    x = samples.astype(np.float64) * float(meta["input_scale"])
-    if x.size < N:
-        return np.zeros((0, nb), np.float32)
-    nf = 1 + (x.size - N) // S
+    r32 = (lambda v: np.asarray(v, np.float32).astype(np.float64)) if f32_tables else (lambda v: v)
+    x = samples.astype(np.float64) * float(r32(float(meta["input_scale"])))
+    nf = 1 + (x.size - N) // S if x.size >= N else 0
     idx = np.arange(N)[None, :] + S * np.arange(nf)[:, None]
-    fr = x[idx]
+    raw = x[idx]
+    fr = raw
     if int(meta["remove_dc_offset"]):
         fr = fr - fr.mean(axis=1, keepdims=True)
-    c = float(meta["preemph_coeff"])
+    c = float(r32(float(meta["preemph_coeff"])))
     if c != 0.0:
         prev = np.concatenate([fr[:, :1], fr[:, :-1]], axis=1)
         fr = fr - c * prev
@@ -51,9 +54,7 @@ def fbank_np(samples: np.ndarray, meta: dict) -> np.ndarray:
         w = (0.5 - 0.5 * np.cos(a * i)) ** 0.85
     else:
         w = np.ones(N)
-    fr = fr * w
-    spec = np.fft.rfft(fr, n=P, axis=1)
-    pw = (spec.real**2 + spec.imag**2)[:, : P // 2]
+    fr = fr * r32(w)
 
     def mel(f):
         return 1127.0 * np.log(1.0 + f / 700.0)
@@ -62,7 +63,7 @@ def fbank_np(samples: np.ndarray, meta: dict) -> np.ndarray:
     if hi <= 0:
         hi += sr / 2
     ml, mh = mel(lo), mel(hi)
-    d = (ml_d := (mh - ml) / (nb + 1))
+    d = (mh - ml) / (nb + 1)
     fm = mel(np.arange(P // 2) * (sr / P))
     W = np.zeros((nb, P // 2))
     for b in range(nb):
@@ -71,8 +72,22 @@ def fbank_np(samples: np.ndarray, meta: dict) -> np.ndarray:
         dn = (r - fm) / (r - c_)
         sel = (fm > l) & (fm < r)
         W[b, sel] = np.where(fm[sel] <= c_, up[sel], dn[sel])
-    e = pw @ W.T
-    e = np.maximum(e, np.finfo(np.float32).eps)
+    return fr, r32(W), raw
+
+
+def fbank_energies(fr: np.ndarray, W: np.ndarray) -> np.ndarray:
+    """mel energies [nf, nb] of windowed frames, before the floor: numpy's float64 FFT"""
+    P = 2 * W.shape[1]
+    spec = np.fft.rfft(fr, n=P, axis=1)
+    pw = (spec.real**2 + spec.imag**2)[:, : P // 2]
+    return pw @ W.T
+
+
+def fbank_np(samples: np.ndarray, meta: dict, f32_tables: bool = False) -> np.ndarray:
+    fr, W, _ = fbank_parts(samples, meta, f32_tables)
+    if fr.shape[0] == 0:
+        return np.zeros((0, W.shape[0]), np.float32)
+    e = np.maximum(fbank_energies(fr, W), np.finfo(np.float32).eps)
     return np.log(e).astype(np.float32)
 
 
