@@ -574,7 +574,8 @@ int32_t k2hip_offline_ctc_align_from_samples(k2hip_model_t* model, const float* 
  * PREFIX IDENTITY IS SEQUENCE IDENTITY.  "Slot j spells y_k + [v]" speaks of token sequences, not of history nodes: when a prefix P
  * leaves the beam while its descendant P+w stays, P is later spelled again from its parent and that new P is extended by w, the
  * extension folds into the old P+w -- two equal prefixes are never live together.
- * Not covered: hotwords and the n-gram LM (ignored by this search), streaming, vocabulary pruning, length normalisation.
+ * Not covered: hotwords and the n-gram LM (ignored by this search), vocabulary pruning, length normalisation.  Streaming: the carried
+ * form below (k2hip_ctc_prefix_beam_search_chunk).
  *
  * k2hip_ctc_prefix_beam_search: operator level.  Output shapes and the K2HIP_ERR_CAPACITY rule are those of k2hip_beam_search_nbest
  * (B = R).  K2HIP_ERR_UNSUPPORTED for a transducer model; K2HIP_ERR_INVALID for beam outside 1..8, nbest outside 1..beam, n_frames
@@ -583,6 +584,50 @@ int32_t k2hip_offline_ctc_align_from_samples(k2hip_model_t* model, const float* 
 int32_t k2hip_ctc_prefix_beam_search(k2hip_model_t* model, const float* log_probs, int32_t R, int32_t Tprime, const int32_t* n_frames,
                                      int32_t beam, int32_t nbest, int64_t* tokens, int32_t* timestamps, float* token_log_probs,
                                      int32_t* n_tokens, int32_t* n_hyps, float* scores, int32_t max_tokens);
+/* ---- streaming CTC prefix beam search: prefixes carried across chunks (operator level) ------------------------------------------
+ * A k2hip_ctc_prefix_stream_t is one stream's live prefixes (host memory; no device slot), shaped like k2hip_beam_stream_t.
+ * k2hip_ctc_prefix_beam_search_chunk continues every listed stream over its next n_frames[b] (NULL = Tc) rows of log_probs
+ * [B][Tc][V] -- what k2hip_online_encoder-style producers of a CTC model's log-probs deliver per chunk.  Nothing new is defined: after
+ * any sequence of calls, whatever the chunk lengths and the batch composition per call, a stream's live prefixes are EXACTLY those of
+ * the search above run once over the concatenation of all frames it has been given -- in rank order, each with its tokens, ABSOLUTE
+ * frame timestamps, token log-probs and (pb, pnb, tot), bit for bit, the float32 scores included (both forms run the same float32
+ * operations in the same order; the score has no length normalisation).  Prefix identity, the fold rule, the tie rule, the
+ * first-inserted rule and the all -inf rule cross a chunk boundary unchanged.
+ * create: beam 1..8, nbest 1..beam (the alternatives the stream serves), else K2HIP_ERR_INVALID; K2HIP_ERR_UNSUPPORTED for a
+ * transducer model.  The chunk call fails with K2HIP_ERR_UNSUPPORTED for a transducer model and with K2HIP_ERR_INVALID for streams
+ * of different beams in one call, a stream listed twice, a stream of another model, or n_frames[b] outside [1, Tc] -- all decided on
+ * the host before any device work; a failed call leaves every stream as it was.  Independent of the model's decoding method and
+ * k2hip_set_nbest.  num_frames: the frames searched so far.  The getters are those of k2hip_beam_stream_*: the best prefix (entry
+ * 0), its score (0 before the first chunk), and the first min(nbest, live) prefixes in rank order. */
+typedef struct k2hip_ctc_prefix_stream k2hip_ctc_prefix_stream_t;
+int32_t k2hip_ctc_prefix_stream_create(k2hip_model_t* model, int32_t beam /* 1..8 */, int32_t nbest /* 1..beam */, k2hip_ctc_prefix_stream_t** out);
+int32_t k2hip_ctc_prefix_stream_destroy(k2hip_ctc_prefix_stream_t* s);
+int32_t k2hip_ctc_prefix_stream_reset(k2hip_ctc_prefix_stream_t* s);
+int64_t k2hip_ctc_prefix_stream_num_frames(const k2hip_ctc_prefix_stream_t* s);
+int32_t k2hip_ctc_prefix_beam_search_chunk(k2hip_model_t* model, k2hip_ctc_prefix_stream_t* const* streams, int32_t B, const float* log_probs /* [B,Tc,V] */,
+                                           int32_t Tc, const int32_t* n_frames /* [B] in 1..Tc, or NULL */);
+int32_t k2hip_ctc_prefix_stream_num_tokens(const k2hip_ctc_prefix_stream_t* s);
+int32_t k2hip_ctc_prefix_stream_get_tokens(const k2hip_ctc_prefix_stream_t* s, int64_t* tokens, int32_t cap);
+int32_t k2hip_ctc_prefix_stream_get_timestamps(const k2hip_ctc_prefix_stream_t* s, int32_t* timestamps, int32_t cap);
+int32_t k2hip_ctc_prefix_stream_get_token_log_probs(const k2hip_ctc_prefix_stream_t* s, float* out, int32_t cap);
+int32_t k2hip_ctc_prefix_stream_get_score(const k2hip_ctc_prefix_stream_t* s, float* score);
+int32_t k2hip_ctc_prefix_stream_num_alternatives(const k2hip_ctc_prefix_stream_t* s);
+int32_t k2hip_ctc_prefix_stream_get_alternative(const k2hip_ctc_prefix_stream_t* s, int32_t i, int64_t* tokens, int32_t* timestamps,
+                                                float* token_log_probs, int32_t cap, int32_t* n, float* score);
+/* Recognizer level: k2hip_online_stream_set_ctc_prefix_beam(s, beam, nbest) opts ONE stream of a streaming CTC model into the carried
+ * prefix search (beam 1..8, nbest 1..beam the alternatives it serves; beam 0 = off, the reference's per-chunk collapse).  Per stream
+ * because k2hip_set_decoding_method(model, "ctc_prefix_beam_search") covers the offline entries only -- k2hip_online_step under it
+ * keeps failing with K2HIP_ERR_INVALID -- and k2hip_set_nbest on a CTC model keeps its rules.  K2HIP_ERR_UNSUPPORTED on a model without
+ * a CTC head; K2HIP_ERR_INVALID for beam / nbest out of range, or once the stream has searched a chunk (legal again after
+ * k2hip_online_stream_reset, which keeps the setting and drops the prefixes).
+ * k2hip_online_step with such streams: every stream of the list must carry the same beam setting (0 included), else K2HIP_ERR_INVALID
+ * before anything moves.  The chunk's log-probs continue the stream's prefixes in the tick's own launch sequence (the in blocks ride
+ * the tick's one upload, the out blocks its one download); Tokens become [blank, blank] + the best prefix over all frames so far,
+ * Timestamps its ABSOLUTE frames (as under the streaming modified beam search), n_new_tokens[i] the signed change of its length --
+ * re-read Tokens, earlier ones can change.  k2hip_online_stream_get_score / _num_alternatives / _get_alternative /
+ * _get_token_log_probs serve it (score 0 and one empty alternative before the first chunk).  Streams without the setting decode
+ * exactly as before. */
+int32_t k2hip_online_stream_set_ctc_prefix_beam(k2hip_online_stream_t* s, int32_t beam /* 0 = off, 1..8 */, int32_t nbest /* 1..beam */);
 /* Per stream.  num_alternatives: the count (>= 1; -1 for NULL, for online streams a negative error code under greedy_search).
  * get_alternative(i): tokens / timestamps / token_log_probs [cap] (each may be NULL), *n = its length, *score = its finalized
  * log-prob; K2HIP_ERR_CAPACITY if cap is too small (nothing is written), K2HIP_ERR_INVALID for i outside the list.
@@ -670,7 +715,9 @@ int32_t k2hip_online_step(k2hip_model_t* model, k2hip_online_stream_t* const* st
  * For a host that keeps the reference's OnlineRecognizer loop unchanged and swaps only the operator (csharp/OnlineProjOfHip.cs).
  * A k2hip_online_state_t is ONE stream's encoder caches: a slot of the device state pool plus processed_lens.  It replaces the
  * List<List<float[]>> of GetEncoderInitStates (OnlineProjOfZipformer2.cs:144-238); stack_states / unstack_states (:240-489)
- * are the identity on handles because EncoderProj advances the caches in place.  Streaming Zipformer2 transducer models only. */
+ * are the identity on handles because EncoderProj advances the caches in place.  Streaming Zipformer2 models: transducer, and
+ * zipformer2ctc, whose EncoderProj output is [B, T', V] log-probs (the CTC head and the row log-softmax are part of the encoder entry;
+ * k2hip_model_info.reserved reports the width) -- the producer of k2hip_ctc_prefix_beam_search_chunk. */
 typedef struct k2hip_online_state k2hip_online_state_t;
 int32_t k2hip_online_state_create(k2hip_model_t* model, k2hip_online_state_t** out);
 int32_t k2hip_online_state_destroy(k2hip_online_state_t* state);

@@ -117,6 +117,11 @@ int32_t k2hip_debug_gemm_run(k2hip_model_t* model, const float* A, const float* 
  *     int32, scores [R][nbest] -- and flag [1] int32, the search-output block's status word (1: an entry outgrew max_tokens and was not
  *     written); ints R, Tp, V, beam, nbest, max_tokens.  V here is free, not the model's.  The kernel stores straight into the guarded
  *     buffers, so what it does not write keeps the caller's fill.
+ *   "ctc_prefix_resume" (tests/test_ctc_prefix_stream_gpu.py): the same kernel's resume form alone.  Buffers log_probs [B][Tc][V],
+ *     n_frames [B] int32 in 1..Tc (or null), in [B][in_ints] -- the caller's in blocks, laid out as kernels.h describes beside
+ *     CtcPrefixResumeArgs (csrc/ctc_prefix_layout.h has the offsets) --, out [B][out_ints] and status [1] int32 (1: an in block
+ *     contradicts itself); ints B, Tc, V, beam.  V is free.  The in blocks are checked on the host first (n, last tokens, relation
+ *     lengths: everything the kernel indexes with); the kernel stores straight into the guarded out buffer.
  * The kernels around the encoder layers (tests/test_outer_kernels_gpu.py; cases and references in tests/outer_kernels.py), arguments in
  * the launcher's own order as above, a bool as an int:
  *   offline front end: "pad_logfloor" (bufs packed, d_off int64 [B], d_len int64 [B], out; ints B, L), "pad_logfloor_dense" (bufs feats,

@@ -12,6 +12,7 @@ from __future__ import annotations
 from . import config, k2w, synth  # noqa: F401
 from .binding import (  # noqa: F401
     BeamStream,
+    CtcPrefixStream,
     Hotwords,
     NgramLm,
     K2HipError,
@@ -31,6 +32,7 @@ from .binding import (  # noqa: F401
 
 __all__ = [
     "BeamStream",
+    "CtcPrefixStream",
     "Hotwords",
     "NgramLm",
     "K2HipError",

@@ -20,6 +20,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import subprocess
+import weakref
 from typing import List, Optional, Sequence
 
 import numpy as np
@@ -351,6 +352,9 @@ class Model:
         if rc != 0:
             raise K2HipError(rc, self._L.k2hip_last_error().decode())
         self._h = h
+        # the live stream objects of this model: their native destroy calls reach into the model (the slot pool, the engine's lock), so
+        # close() closes them first -- a stream that outlives its model's handle is then a closed stream, not a dangling pointer
+        self._children = weakref.WeakSet()
         info = InfoStruct()
         self._chk(self._L.k2hip_model_get_info(self._h, C.byref(info)))
         self.vocab_size = info.vocab_size
@@ -368,6 +372,8 @@ class Model:
 
     def close(self):
         if getattr(self, "_h", None):
+            for child in list(getattr(self, "_children", ())):
+                child.close()
             self._L.k2hip_model_destroy(self._h)
             self._h = None
 
@@ -565,6 +571,22 @@ class Model:
         """decodingMethod of the batch entry points (OfflineRecognizer.cs:54-68): greedy_search | modified_beam_search, and for a CTC
         model ctc_prefix_beam_search (no reference counterpart; k2hip.h "CTC prefix beam search with N-best")"""
         self._chk(self._L.k2hip_set_decoding_method(self._h, method.encode(), beam))
+
+    def create_ctc_prefix_stream(self, beam: int, nbest: int = 1) -> "CtcPrefixStream":
+        """k2hip_ctc_prefix_stream_create: one stream of the CTC prefix beam search carried across chunks (beam 1..8, nbest 1..beam)"""
+        return CtcPrefixStream(self, beam, nbest)
+
+    def ctc_prefix_beam_search_chunk(self, streams, log_probs, n_frames=None):
+        """k2hip_ctc_prefix_beam_search_chunk: continue every stream over its next n_frames[b] (None = all Tc) rows of log_probs
+        [B, Tc, V].  A failed call leaves every stream as it was."""
+        _bind_online(self._L)
+        x = _f32(log_probs)
+        B = len(streams)
+        assert x.ndim == 3 and x.shape[0] == B and x.shape[2] == self.vocab_size, x.shape
+        nf = None if n_frames is None else np.ascontiguousarray(n_frames, np.int32)
+        assert nf is None or nf.shape == (B,), nf.shape
+        arr = (C.c_void_p * B)(*[s._h.value for s in streams])
+        self._chk(self._L.k2hip_ctc_prefix_beam_search_chunk(self._h, arr, B, _f(x), x.shape[1], _i(nf) if nf is not None else None))
 
     def set_hotwords(self, hotwords: Optional["Hotwords"] = None):
         """k2hip_set_hotwords: bias the offline modified beam search towards the graph's phrases; None clears.  The model keeps its own
@@ -850,6 +872,7 @@ class OfflineStream:
         h = C.c_void_p()
         model._chk(self._L.k2hip_offline_stream_create(model.handle, C.byref(h)))
         self._h = h
+        model._children.add(self)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -984,6 +1007,17 @@ def _bind_online(L):
     L.k2hip_beam_stream_get_score.argtypes = [vp, fp]
     L.k2hip_online_stream_set_hotwords.argtypes = [vp, vp]
     L.k2hip_beam_stream_set_hotwords.argtypes = [vp, vp]
+    L.k2hip_ctc_prefix_stream_create.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(vp)]
+    L.k2hip_ctc_prefix_stream_destroy.argtypes = [vp]
+    L.k2hip_ctc_prefix_stream_reset.argtypes = [vp]
+    L.k2hip_ctc_prefix_stream_num_frames.restype = C.c_int64
+    L.k2hip_ctc_prefix_stream_num_frames.argtypes = [vp]
+    L.k2hip_ctc_prefix_beam_search_chunk.argtypes = [vp, C.POINTER(vp), C.c_int32, fp, C.c_int32, ip]
+    L.k2hip_ctc_prefix_stream_num_tokens.argtypes = [vp]
+    L.k2hip_ctc_prefix_stream_get_tokens.argtypes = [vp, lp, C.c_int32]
+    L.k2hip_ctc_prefix_stream_get_timestamps.argtypes = [vp, ip, C.c_int32]
+    L.k2hip_ctc_prefix_stream_get_score.argtypes = [vp, fp]
+    L.k2hip_online_stream_set_ctc_prefix_beam.argtypes = [vp, C.c_int32, C.c_int32]
     L._online_bound = True
 
 
@@ -997,6 +1031,7 @@ class OnlineStream:
         h = C.c_void_p()
         model._chk(self._L.k2hip_online_stream_create(model.handle, C.byref(h)))
         self._h = h
+        model._children.add(self)
 
     def reset(self):
         """back to a freshly created stream (same slot): for the next utterance on the same object"""
@@ -1006,6 +1041,13 @@ class OnlineStream:
         """k2hip_online_stream_set_hotwords: this stream's hotword graph under modified_beam_search; None detaches.  Only before the
         stream's first decoded chunk or after reset(); the stream keeps its own reference (hotwords.close() afterwards is fine)."""
         self._m._chk(self._L.k2hip_online_stream_set_hotwords(self._h, hotwords._h if hotwords is not None else None))
+
+    def set_ctc_prefix_beam(self, beam: int, nbest: int = 1):
+        """k2hip_online_stream_set_ctc_prefix_beam: a streaming CTC model's stream decodes with the prefix beam search carried across
+        chunks (beam 1..8, nbest alternatives kept; 0 = off, the per-chunk collapse).  Only before the stream's first decoded chunk or
+        after reset().  tokens then are [blank, blank] + the best prefix, timestamps absolute frames; score, alternatives() and
+        token_log_probs() serve it."""
+        self._m._chk(self._L.k2hip_online_stream_set_ctc_prefix_beam(self._h, beam, nbest))
 
     def close(self):
         if getattr(self, "_h", None):
@@ -1125,7 +1167,8 @@ class OnlineProj:
     def encoder_proj(self, feats, states) -> np.ndarray:  # EncoderProj: the states advance in place
         B = len(states)
         x = _f32(feats).reshape(B, self.chunk_length, -1)
-        out = np.empty((B, self.frames_per_chunk, self.model.joiner_dim), np.float32)
+        # (a streaming CTC model's encoder entry ends in its CTC head: [B, T', V] log-probs)
+        out = np.empty((B, self.frames_per_chunk, self.model.encoder_out_dim), np.float32)
         arr = (C.c_void_p * B)(*[s.value for s in states])
         self.model._chk(self.model._L.k2hip_online_encoder(self.model.handle, arr, B, _f(x), _f(out), out.size))
         return out
@@ -1149,6 +1192,7 @@ class BeamStream:
         h = C.c_void_p()
         model._chk(self._L.k2hip_beam_stream_create(model.handle, beam, C.byref(h)))
         self._h = h
+        model._children.add(self)
         self.beam = beam
 
     def close(self):
@@ -1207,6 +1251,67 @@ class BeamStream:
         return _token_log_probs(self._m, self._L, "k2hip_beam_stream", self._h)
 
 
+class CtcPrefixStream:
+    """Operator level of the streaming CTC prefix beam search (k2hip_ctc_prefix_stream_*): one stream's live prefixes, continued over
+    chunks of log-probs the caller computed (Model.ctc_prefix_beam_search_chunk).  After any chunking the prefixes are those of
+    Model.ctc_prefix_beam_search over all frames so far, bit for bit; timestamps are absolute frame indexes."""
+
+    def __init__(self, model: Model, beam: int = 4, nbest: int = 1):
+        self._m = model
+        self._L = model._L
+        _bind_online(self._L)
+        h = C.c_void_p()
+        model._chk(self._L.k2hip_ctc_prefix_stream_create(model.handle, beam, nbest, C.byref(h)))
+        self._h = h
+        model._children.add(self)
+        self.beam, self.nbest = beam, nbest
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.k2hip_ctc_prefix_stream_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self):
+        self._m._chk(self._L.k2hip_ctc_prefix_stream_reset(self._h))
+
+    @property
+    def num_frames(self) -> int:
+        return int(self._L.k2hip_ctc_prefix_stream_num_frames(self._h))
+
+    @property
+    def tokens(self) -> List[int]:
+        n = self._L.k2hip_ctc_prefix_stream_num_tokens(self._h)
+        out = np.zeros(max(n, 1), np.int64)
+        self._m._chk(self._L.k2hip_ctc_prefix_stream_get_tokens(self._h, _l(out), n))
+        return out[:n].tolist()
+
+    @property
+    def timestamps(self) -> List[int]:
+        n = self._L.k2hip_ctc_prefix_stream_num_tokens(self._h)
+        out = np.zeros(max(n, 1), np.int32)
+        self._m._chk(self._L.k2hip_ctc_prefix_stream_get_timestamps(self._h, _i(out), n))
+        return out[:n].tolist()
+
+    @property
+    def score(self) -> float:
+        out = C.c_float()
+        self._m._chk(self._L.k2hip_ctc_prefix_stream_get_score(self._h, C.byref(out)))
+        return out.value
+
+    def alternatives(self):
+        """the first min(nbest, live) prefixes in rank order: [dict(tokens, timestamps, token_log_probs, score)]"""
+        return _alternatives(self._m, self._L, "k2hip_ctc_prefix_stream", self._h)
+
+    def token_log_probs(self) -> np.ndarray:
+        return _token_log_probs(self._m, self._L, "k2hip_ctc_prefix_stream", self._h)
+
+
 class OnlineRecognizer:
     """OnlineRecognizer.cs:11-84 on the HIP backend; decoding_method "greedy_search" (the reference's) or "modified_beam_search"
     (hypotheses carried from chunk to chunk: include/k2hip.h).  ngram_lm: an NgramLm fused with weight ngram_lm_scale
@@ -1231,10 +1336,13 @@ class OnlineRecognizer:
                             "lstm": ["lstm_h", "lstm_c"]}.get(mt, [])
         self.embed_state_floats = 128 * 3 * 19 if mt in ("zipformer2", "zipformer2ctc") else 0
 
-    def create_online_stream(self, hotwords=None, hotwords_score: float = 1.5) -> OnlineStream:  # CreateOnlineStream :60-64
+    def create_online_stream(self, hotwords=None, hotwords_score: float = 1.5, ctc_prefix_beam: int = 0, nbest: int = 1) -> OnlineStream:  # CreateOnlineStream :60-64
         """hotwords: a Hotwords graph, or a list of token-id phrases scored hotwords_score per matched token -- the stream's own list
-        (sherpa-onnx's CreateStream(hotwords)); it biases modified_beam_search only."""
+        (sherpa-onnx's CreateStream(hotwords)); it biases modified_beam_search only.  ctc_prefix_beam > 0 (a streaming CTC model):
+        the stream decodes with the carried prefix beam search, keeping nbest alternatives (OnlineStream.set_ctc_prefix_beam)."""
         s = OnlineStream(self.model)
+        if ctc_prefix_beam:
+            s.set_ctc_prefix_beam(ctc_prefix_beam, nbest)
         if hotwords is not None:
             if isinstance(hotwords, Hotwords):
                 s.set_hotwords(hotwords)

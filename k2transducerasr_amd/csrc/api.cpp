@@ -14,6 +14,7 @@
 #include "text.h"
 #include "engine.h"
 #include "beam_hist.h"
+#include "ctc_prefix_hist.h"
 #include "hotwords.h"
 #include "ngram_lm.h"
 #include "../../include/k2hip_debug.h"
@@ -196,6 +197,10 @@ struct k2hip_online_stream {
     std::unique_ptr<BeamHistory> beam;
     // the stream's hotword graph (k2hip_online_stream_set_hotwords) or null; kept by a reset
     std::shared_ptr<HwResident> hw;
+    // a CTC model's stream under the carried prefix search (k2hip_online_stream_set_ctc_prefix_beam; 0 = off: the per-chunk collapse);
+    // the setting is kept by a reset, the prefixes are not.  Tokens / Timestamps are [blank, blank] + the best prefix
+    int cp_beam = 0, cp_nbest = 1;
+    std::unique_ptr<CtcPrefixHistory> cprefix;
 };
 
 // operator level of the streaming beam search: one stream's hypotheses, fed encoder frames by the caller (k2hip_beam_search_chunk)
@@ -203,6 +208,12 @@ struct k2hip_beam_stream {
     k2hip_model* model;
     BeamHistory hist;
     std::shared_ptr<HwResident> hw;   // the stream's hotword graph (k2hip_beam_stream_set_hotwords) or null
+};
+
+// operator level of the streaming CTC prefix beam search: one stream's live prefixes (k2hip_ctc_prefix_beam_search_chunk)
+struct k2hip_ctc_prefix_stream {
+    k2hip_model* model;
+    CtcPrefixHistory hist;
 };
 
 // one stream's encoder caches as the operator-level API sees them (IOnlineProj's List<List<float[]>>): a slot of the device pool
@@ -1129,8 +1140,11 @@ int32_t k2hip_online_stream_reset(k2hip_online_stream_t* s) {
             s->slot = model->engine.online_alloc_slot();  // (the slot just freed: re-zeroed like GetEncoderInitStates)
         }
         std::shared_ptr<HwResident> hw = std::move(s->hw);   // (the attached hotword graph stays; every hypothesis is back at its root)
+        const int cp_beam = s->cp_beam, cp_nbest = s->cp_nbest;   // (so does the prefix-search setting; its prefixes go)
         *s = k2hip_online_stream{model, s->slot};
         s->hw = std::move(hw);
+        s->cp_beam = cp_beam;
+        s->cp_nbest = cp_nbest;
         if (model->engine.model().cfg().conformer) s->processed_len = 2;
     });
 }
@@ -1141,6 +1155,20 @@ int32_t k2hip_online_stream_set_hotwords(k2hip_online_stream_t* s, const k2hip_h
                    "states of the graph it started with -- reset the stream first", s->chunks_done);
         s->hw = hw ? hw_resident_get(s->model, hw, "online stream set_hotwords") : nullptr;
         if (s->beam) s->beam->set_pending(s->hw ? s->hw->pending : nullptr);
+    });
+}
+int32_t k2hip_online_stream_set_ctc_prefix_beam(k2hip_online_stream_t* s, int32_t beam, int32_t nbest) {
+    return guard([&] {
+        NEED(s);
+        const Config& c = s->model->engine.model().cfg();
+        if (!c.ctc) failf(K2HIP_ERR_UNSUPPORTED, "online stream set_ctc_prefix_beam: model_type '%s' has no CTC head", c.model_type.c_str());
+        K2_REQUIRE(beam >= 0 && beam <= kMaxBeam, "online stream set_ctc_prefix_beam: beam %d out of range [0 = off, 1..%d]", beam, kMaxBeam);
+        K2_REQUIRE(beam == 0 || (nbest >= 1 && nbest <= beam), "online stream set_ctc_prefix_beam: nbest %d out of range [1, beam = %d]", nbest, beam);
+        K2_REQUIRE(s->chunks_done == 0 && s->method < 0, "online stream set_ctc_prefix_beam: the stream has searched %lld chunks and its result "
+                   "belongs to the search it started with -- reset the stream first", s->chunks_done);
+        s->cp_beam = beam;
+        s->cp_nbest = beam ? nbest : 1;
+        s->cprefix.reset();
     });
 }
 int32_t k2hip_online_stream_destroy(k2hip_online_stream_t* s) {
@@ -1339,9 +1367,12 @@ int32_t k2hip_online_step(k2hip_model_t* model, k2hip_online_stream_t* const* st
             lm_start = model->lm_start;
         }
         std::vector<int> idx;
+        int CK = 0;   // a CTC model's streams under the carried prefix search: their beam (every stream of the list carries the same setting)
         for (int i = 0; i < B; i++) {
             NEED(streams[i]);
             K2_REQUIRE(streams[i]->model == model, "stream %d belongs to another model", i);
+            K2_REQUIRE(streams[i]->cp_beam == streams[0]->cp_beam, "online step: stream %d has ctc_prefix_beam %d, stream 0 has %d -- every stream "
+                       "of one call carries the same setting (k2hip_online_stream_set_ctc_prefix_beam)", i, streams[i]->cp_beam, streams[0]->cp_beam);
             K2_REQUIRE(!streams[i]->poisoned, "stream %d took part in a chunk step that failed: its caches are undefined, reset it first", i);
             K2_REQUIRE(streams[i]->method < 0 || streams[i]->method == K,
                        "stream %d started decoding with %s (beam %d); the decoding method changed since -- reset the stream first", i,
@@ -1356,6 +1387,7 @@ int32_t k2hip_online_step(k2hip_model_t* model, k2hip_online_stream_t* const* st
             K2_REQUIRE(std::adjacent_find(seen.begin(), seen.end()) == seen.end(), "GetResults: the same stream appears twice in the list");
         }
         if (idx.empty()) return;   // :113-116
+        CK = streams[0]->cp_beam;
         // a stream keeps the LM it decoded its first chunk with (decided for all streams before anything of any of them moves)
         for (size_t r = 0; K > 0 && r < idx.size(); r++) {
             const k2hip_online_stream* s = streams[idx[r]];
@@ -1443,6 +1475,15 @@ int32_t k2hip_online_step(k2hip_model_t* model, k2hip_online_stream_t* const* st
                     if (with_lm) s->beam->fill_lm_states(st_in.data() + (size_t)(R + r) * K);
                 }
             }
+        } else if (CK > 0) {   // the carried prefixes in, the survivors out
+            const CtcPrefixResumeLayout CL{CK, Tp};
+            bin.resize((size_t)R * CL.in_ints());
+            bout.resize((size_t)R * CL.out_ints());
+            for (int r = 0; r < R; r++) {
+                k2hip_online_stream* s = streams[idx[r]];
+                if (!s->cprefix) s->cprefix.reset(new CtcPrefixHistory(CK, s->cp_nbest));   // (the start state: as good as none)
+                s->cprefix->fill_in(bin.data() + (size_t)r * CL.in_ints(), Tp);
+            }
         } else {
             tok.resize((size_t)R * Tp);
             ts.resize((size_t)R * Tp);
@@ -1473,7 +1514,12 @@ int32_t k2hip_online_step(k2hip_model_t* model, k2hip_online_stream_t* const* st
             else if (K > 0)
                 e.online_step_beam(slots.data(), chunks.data(), plens.data(), nch.data(), R, K, bin.data(), bout.data(),
                                    all_mirrored ? heads.data() : nullptr);
-            else
+            else if (CK > 0) {
+                e.online_step_ctc_prefix(slots.data(), chunks.data(), plens.data(), nch.data(), R, CK, bin.data(), bout.data(),
+                                         all_mirrored ? heads.data() : nullptr);
+                const CtcPrefixResumeLayout CL{CK, Tp};   // (the device work is done: an out block that fails its check poisons the streams)
+                for (int r = 0; r < R; r++) streams[idx[r]]->cprefix->check_out(bout.data() + (size_t)r * CL.out_ints(), Tp, Tp);
+            } else
                 e.online_step(slots.data(), chunks.data(), hyps.data(), plens.data(), nch.data(), R, tok.data(), ts.data(), n.data(),
                               all_mirrored ? heads.data() : nullptr);
         } catch (...) {
@@ -1509,7 +1555,16 @@ int32_t k2hip_online_step(k2hip_model_t* model, k2hip_online_stream_t* const* st
                 s->hyp[1] = s->beam->hyp_last(1);
                 n_new_tokens[idx[r]] = (int32_t)((int64_t)s->beam->tokens().size() - before);
             }
-            for (int k = 0; K == 0 && k < n[r]; k++) {
+            if (CK > 0) {   // the best prefix replaces the result (it may revise earlier tokens): n_new_tokens = change of its length
+                const CtcPrefixResumeLayout CL{CK, Tp};
+                const int64_t before = (int64_t)s->cprefix->tokens().size();
+                s->cprefix->apply_out(bout.data() + (size_t)r * CL.out_ints(), Tp, Tp);
+                s->tokens.assign(2, K2HIP_BLANK_ID);
+                s->tokens.insert(s->tokens.end(), s->cprefix->tokens().begin(), s->cprefix->tokens().end());
+                s->timestamps = s->cprefix->timestamps();
+                n_new_tokens[idx[r]] = (int32_t)((int64_t)s->cprefix->tokens().size() - before);
+            }
+            for (int k = 0; K == 0 && CK == 0 && k < n[r]; k++) {
                 s->tokens.push_back(tok[(size_t)r * Tp + k]);          // :183
                 s->timestamps.push_back(ts[(size_t)r * Tp + k]);       // :184 (chunk-relative frame index)
             }
@@ -1521,7 +1576,7 @@ int32_t k2hip_online_step(k2hip_model_t* model, k2hip_online_stream_t* const* st
             else if (c.zip1) s->processed_len += (c.chunk_T - 7) / 2;  // no processed_lens state in v1; kept as a frame counter
             else s->processed_len += (c.chunk_T - 7) / 2 - 3;      // new_processed_lens = processed_lens + x_lens
             decoded[idx[r]] = 1;
-            if (K == 0) n_new_tokens[idx[r]] = n[r];
+            if (K == 0 && CK == 0) n_new_tokens[idx[r]] = n[r];
         }
         if (!remirror.empty()) {
             EngineLock lk(e);
@@ -1540,7 +1595,7 @@ int32_t k2hip_online_state_create(k2hip_model_t* model, k2hip_online_state_t** o
     return guard([&] {
         NEED(model); NEED(out);
         const Config& c = model->engine.model().cfg();
-        K2_REQUIRE(c.streaming && !c.lstm && !c.conformer && !c.zip1 && !c.ctc, "online states: streaming Zipformer2 transducer models only");
+        K2_REQUIRE(c.streaming && !c.lstm && !c.conformer && !c.zip1, "online states: streaming Zipformer2 models only");
         auto* st = new k2hip_online_state();
         st->model = model;
         try {
@@ -1632,6 +1687,10 @@ int32_t k2hip_online_stream_get_timestamps(const k2hip_online_stream_t* s, int32
 int32_t k2hip_online_stream_get_score(const k2hip_online_stream_t* s, float* score) {
     return guard([&] {
         NEED(s); NEED(score);
+        if (s->cp_beam > 0) {   // a CTC stream under the carried prefix search: the best prefix' total (0 before its first chunk)
+            *score = s->cprefix ? s->cprefix->score() : 0.f;
+            return;
+        }
         K2_REQUIRE(s->method != 0, "the stream decodes with greedy_search: it has no hypothesis score");
         *score = s->method > 0 ? s->beam->score() : 0.f;   // (no chunk yet: the start hypothesis, log-prob 0)
     });
@@ -1778,8 +1837,99 @@ int32_t k2hip_beam_stream_get_token_log_probs(const k2hip_beam_stream_t* s, floa
     if (!s) return guard([&] { NEED(s); });
     return yp_get(s->hist.token_log_probs(), out, cap);
 }
+// ---- operator level of the streaming CTC prefix beam search -------------------------------------------------------------------------
+int32_t k2hip_ctc_prefix_stream_create(k2hip_model_t* model, int32_t beam, int32_t nbest, k2hip_ctc_prefix_stream_t** out) {
+    return guard([&] {
+        NEED(model); NEED(out);
+        *out = nullptr;
+        if (!model->engine.model().cfg().ctc)
+            failf(K2HIP_ERR_UNSUPPORTED, "ctc prefix stream: model_type '%s' has no CTC head", model->engine.model().cfg().model_type.c_str());
+        K2_REQUIRE(beam >= 1 && beam <= kMaxBeam, "ctc prefix stream: beam %d out of range [1,%d]", beam, kMaxBeam);
+        K2_REQUIRE(nbest >= 1 && nbest <= beam, "ctc prefix stream: nbest %d out of range [1, beam = %d]", nbest, beam);
+        *out = new k2hip_ctc_prefix_stream{model, CtcPrefixHistory(beam, nbest)};
+    });
+}
+int32_t k2hip_ctc_prefix_stream_destroy(k2hip_ctc_prefix_stream_t* s) {
+    return guard([&] { delete s; });
+}
+int32_t k2hip_ctc_prefix_stream_reset(k2hip_ctc_prefix_stream_t* s) {
+    return guard([&] {
+        NEED(s);
+        s->hist.reset();
+    });
+}
+int64_t k2hip_ctc_prefix_stream_num_frames(const k2hip_ctc_prefix_stream_t* s) { return s ? (int64_t)s->hist.frames() : -1; }
+int32_t k2hip_ctc_prefix_beam_search_chunk(k2hip_model_t* model, k2hip_ctc_prefix_stream_t* const* streams, int32_t B, const float* log_probs, int32_t Tc,
+                                           const int32_t* n_frames) {
+    return guard([&] {
+        NEED(model); NEED(streams); NEED(log_probs);
+        if (!model->engine.model().cfg().ctc)
+            failf(K2HIP_ERR_UNSUPPORTED, "ctc_prefix_beam_search_chunk: model_type '%s' has no CTC head", model->engine.model().cfg().model_type.c_str());
+        K2_REQUIRE(B > 0 && B <= 65535 && Tc >= 1, "ctc_prefix_beam_search_chunk: bad shape B=%d Tc=%d", B, Tc);
+        std::vector<const k2hip_ctc_prefix_stream*> seen(streams, streams + B);
+        for (int b = 0; b < B; b++) {
+            NEED(streams[b]);
+            K2_REQUIRE(streams[b]->model == model, "ctc prefix stream %d belongs to another model", b);
+            K2_REQUIRE(streams[b]->hist.beam() == streams[0]->hist.beam(), "ctc prefix stream %d has beam %d, stream 0 has %d: one beam per call", b,
+                       streams[b]->hist.beam(), streams[0]->hist.beam());
+            K2_REQUIRE(!n_frames || (n_frames[b] >= 1 && n_frames[b] <= Tc), "ctc_prefix_beam_search_chunk: stream %d has n_frames = %d outside [1, Tc = %d]", b,
+                       n_frames[b], Tc);
+        }
+        std::sort(seen.begin(), seen.end());
+        K2_REQUIRE(std::adjacent_find(seen.begin(), seen.end()) == seen.end(), "ctc_prefix_beam_search_chunk: the same stream appears twice");
+        const int K = streams[0]->hist.beam();
+        const CtcPrefixResumeLayout L{K, Tc};
+        std::vector<int> bin((size_t)B * L.in_ints()), bout((size_t)B * L.out_ints());
+        for (int b = 0; b < B; b++) streams[b]->hist.fill_in(bin.data() + (size_t)b * L.in_ints(), Tc);
+        {
+            EngineLock lk(model->engine);
+            model->engine.ctc_prefix_chunk_host(log_probs, B, Tc, n_frames, K, bin.data(), bout.data());
+        }
+        // (only after success, and after every out block has passed its check: a failed call leaves every stream as it was)
+        for (int b = 0; b < B; b++) streams[b]->hist.check_out(bout.data() + (size_t)b * L.out_ints(), Tc, n_frames ? n_frames[b] : Tc);
+        for (int b = 0; b < B; b++) streams[b]->hist.apply_out(bout.data() + (size_t)b * L.out_ints(), Tc, n_frames ? n_frames[b] : Tc);
+    });
+}
+int32_t k2hip_ctc_prefix_stream_num_tokens(const k2hip_ctc_prefix_stream_t* s) { return s ? (int32_t)s->hist.tokens().size() : -1; }
+int32_t k2hip_ctc_prefix_stream_get_tokens(const k2hip_ctc_prefix_stream_t* s, int64_t* tokens, int32_t cap) {
+    return guard([&] {
+        NEED(s);
+        const std::vector<int64_t>& t = s->hist.tokens();
+        if ((int)t.size() > cap) failf(K2HIP_ERR_CAPACITY, "ctc prefix stream holds %zu tokens", t.size());
+        if (!t.empty()) { NEED(tokens); memcpy(tokens, t.data(), sizeof(int64_t) * t.size()); }
+    });
+}
+int32_t k2hip_ctc_prefix_stream_get_timestamps(const k2hip_ctc_prefix_stream_t* s, int32_t* timestamps, int32_t cap) {
+    return guard([&] {
+        NEED(s);
+        const std::vector<int32_t>& t = s->hist.timestamps();
+        if ((int)t.size() > cap) failf(K2HIP_ERR_CAPACITY, "ctc prefix stream holds %zu timestamps", t.size());
+        if (!t.empty()) { NEED(timestamps); memcpy(timestamps, t.data(), sizeof(int32_t) * t.size()); }
+    });
+}
+int32_t k2hip_ctc_prefix_stream_get_token_log_probs(const k2hip_ctc_prefix_stream_t* s, float* out, int32_t cap) {
+    if (!s) return guard([&] { NEED(s); });
+    return yp_get(s->hist.token_log_probs(), out, cap);
+}
+int32_t k2hip_ctc_prefix_stream_get_score(const k2hip_ctc_prefix_stream_t* s, float* score) {
+    return guard([&] {
+        NEED(s); NEED(score);
+        *score = s->hist.score();
+    });
+}
+int32_t k2hip_ctc_prefix_stream_num_alternatives(const k2hip_ctc_prefix_stream_t* s) {
+    return s ? (int32_t)s->hist.nbest(s->hist.nbest_limit()).size() : -1;
+}
+int32_t k2hip_ctc_prefix_stream_get_alternative(const k2hip_ctc_prefix_stream_t* s, int32_t i, int64_t* tokens, int32_t* timestamps, float* token_log_probs,
+                                                int32_t cap, int32_t* n, float* score) {
+    return guard([&] {
+        NEED(s);
+        alt_get(s->hist.nbest(s->hist.nbest_limit()), i, tokens, timestamps, token_log_probs, cap, n, score);
+    });
+}
 // (a stream that has not decoded a chunk yet is in the start state: one empty alternative, score 0)
 static std::vector<BeamAlt> online_alts(const k2hip_online_stream* s) {
+    if (s->cp_beam > 0) return s->cprefix ? s->cprefix->nbest(s->cp_nbest) : std::vector<BeamAlt>(1);
     K2_REQUIRE(s->method != 0, "the stream decodes with greedy_search: it has no alternatives");
     return s->method > 0 ? s->beam->nbest(s->model->nbest.load()) : std::vector<BeamAlt>(1);
 }
@@ -1800,8 +1950,9 @@ int32_t k2hip_online_stream_get_alternative(const k2hip_online_stream_t* s, int3
 }
 int32_t k2hip_online_stream_get_token_log_probs(const k2hip_online_stream_t* s, float* out, int32_t cap) {
     if (!s) return guard([&] { NEED(s); });
-    if (s->method == 0) return guard([&] { K2_REQUIRE(false, "the stream decodes with greedy_search: it keeps no token log-probs"); });
     static const std::vector<float> none;
+    if (s->cp_beam > 0) return yp_get(s->cprefix ? s->cprefix->token_log_probs() : none, out, cap);
+    if (s->method == 0) return guard([&] { K2_REQUIRE(false, "the stream decodes with greedy_search: it keeps no token log-probs"); });
     return yp_get(s->method > 0 ? s->beam->token_log_probs() : none, out, cap);
 }
 int32_t k2hip_online_stream_get_hyp(const k2hip_online_stream_t* s, int64_t* hyp2) {

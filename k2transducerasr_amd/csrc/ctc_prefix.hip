@@ -18,6 +18,14 @@
 //                                 node identity: a prefix that left the beam and was spelled again has another node.
 //                  The first 256 columns of frame t + 1 are requested before frame t's work.  After the last frame every surviving
 //                  slot's chain is walked back into its output row from index len - 1 down.
+//   k_ctc_prefix<true>  the same frames resumed from the live prefixes of the chunks before (streaming; CtcPrefixResumeLayout).  The
+//                  per-frame body is the one above -- one piece of source, the same float32 operations in the same order, so a stream's
+//                  prefixes after any chunking are bit for bit those of the search over all its frames.  What differs is outside the
+//                  arithmetic: the slots start from the in block (carried slot a is the pool's root -1 - a, its parent kNoParent), the
+//                  fold table is also built before the first frame, its confirmation walks through the boundary (both chains in lock
+//                  step; where one reaches its root a while the other is d tokens above its root b, the answer is rel[a][b] == d with
+//                  relx equal to those tokens; a carried slot with nothing appended is the case S_a = S_b + s_k + [e_a]), and the
+//                  survivors go to the out block as (origin, appended tokens / frames / log-probs, pb, pnb, hashes).
 // No workgroup waits for another; every loop is bounded by T, beam or a hypothesis length; all stores are ordinary vector stores.
 #include <climits>
 
@@ -46,9 +54,34 @@ struct Slots {
     unsigned long long hash[KB], phash[KB];    // rolling hash of the prefix / of the prefix without its last token
     int n;
 };
-constexpr unsigned long long kHashSeed = 0x243F6A8885A308D3ull, kHashMul = 0x9E3779B97F4A7C15ull;
+constexpr unsigned long long kHashSeed = kCtcPrefixHashSeed, kHashMul = kCtcPrefixHashMul;
 
-__global__ __launch_bounds__(PT) void k_ctc_prefix(CtcPrefixArgs a) {
+constexpr int kNoParent = INT_MIN;   // resume: the parent of a carried slot's last token lies outside the chunk
+
+// Resume: the confirmation of slot j = slot k + [e_j] once a chain has left the chunk.  p (from j's parent) and q (from k's node) have
+// spelled equal tokens so far and differ, and at least one is no in-chunk node.  jn: slot j's node.
+__device__ __forceinline__ bool fold_through_boundary(int p, int q, int jn, const int4* nodes, const int* in, CtcPrefixResumeLayout L, int* status) {
+    int a, o, skip = 0;   // a: the carried slot a chain ended in; o: where the other chain stands; skip: e_a itself is not walked
+    if (p == kNoParent) { a = -1 - jn; o = q; skip = 1; }
+    else if (p < 0 && q < 0) return false;   // two different carried slots: different sequences
+    else if (p < 0) { a = -1 - p; o = q; }
+    else { a = -1 - q; o = p; }
+    int d = 0, b = o;
+    while (b >= 0 && d < L.Tc) { b = nodes[b].x; d++; }
+    if (b >= 0 || b == kNoParent || a < 0 || a >= L.K || -1 - b >= L.K) { *status = 1; return false; }
+    const int ab = a * L.K + (-1 - b);
+    if (in[L.in_rel() + ab] != d + skip) return false;
+    const int* x = in + L.in_relx() + ab * L.Tc;
+    for (int i = d - 1; i >= 0; i--) {   // (d + skip <= Tc by the table's cap)
+        const int4 nd = nodes[o];
+        if (nd.y != x[i]) return false;
+        o = nd.x;
+    }
+    return true;
+}
+
+template <bool RESUME, typename Args>
+__global__ __launch_bounds__(PT) void k_ctc_prefix(Args a) {
     __shared__ Slots sl[2];
     __shared__ float stay_pb[KB], stay_pnb[KB];
     __shared__ int fold_par[KB];   // slot j -> the slot k whose extension by e_j spells j, or -1
@@ -56,10 +89,53 @@ __global__ __launch_bounds__(PT) void k_ctc_prefix(CtcPrefixArgs a) {
     __shared__ int wl_i[PW][KB];
     const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int V = a.V, beam = a.beam;
-    const int T = min(max(a.n_frames ? a.n_frames[r] : a.Tp, 0), a.Tp);
-    const float* lp = a.log_probs + (long long)r * a.Tp * V;
-    int4* nodes = a.nodes + (long long)r * a.Tp * beam;
-    if (tid == 0) {
+    int Tp;
+    if constexpr (RESUME) Tp = a.Tc;
+    else Tp = a.Tp;
+    const int T = min(max(a.n_frames ? a.n_frames[r] : Tp, 0), Tp);
+    const float* lp = a.log_probs + (long long)r * Tp * V;
+    int4* nodes = a.nodes + (long long)r * Tp * beam;
+    // the next frame's fold table: does slot j spell slot k + [e_j]?  (live prefixes are distinct: at most one k per j)
+    auto fold_table = [&](const Slots& nx) {
+        if (tid < KB * KB) {
+            const int j = tid / KB, k = tid & (KB - 1), n2 = nx.n;
+            if (j < n2 && k < n2 && j != k && nx.len[j] == nx.len[k] + 1 && nx.phash[j] == nx.hash[k]) {
+                int p = nx.pnode[j], q = nx.node[k];
+                bool same = true;
+                while (p != q) {   // equal lengths: both chains end at their roots together; every step shortens both
+                    if (p < 0 || q < 0) {
+                        if constexpr (RESUME) same = fold_through_boundary(p, q, nx.node[j], nodes, a.in + (long long)r * CtcPrefixResumeLayout{beam, Tp}.in_ints(),
+                                                                           CtcPrefixResumeLayout{beam, Tp}, a.status);
+                        else same = false;
+                        break;
+                    }
+                    const int4 np = nodes[p], nq = nodes[q];
+                    if (np.y != nq.y) { same = false; break; }
+                    p = np.x;
+                    q = nq.x;
+                }
+                if (same) fold_par[j] = k;
+            }
+        }
+    };
+    if constexpr (RESUME) {
+        const CtcPrefixResumeLayout L{beam, Tp};
+        const int* in = a.in + (long long)r * L.in_ints();
+        if (tid < KB) fold_par[tid] = -1;
+        if (tid == 0) sl[0].n = min(max(in[0], 1), beam);
+        if (tid < beam) {
+            Slots& s = sl[0];
+            const int k = tid, e = in[L.in_e() + k];
+            s.pb[k] = __int_as_float(in[L.in_pb() + k]);
+            s.pnb[k] = __int_as_float(in[L.in_pnb() + k]);
+            s.tot[k] = logaddexp_f(s.pb[k], s.pnb[k]);   // (the value the frame before formed from the same two operands)
+            s.e[k] = e >= 1 && e < V ? e : -1;
+            s.len[k] = in[L.in_len() + k];
+            s.node[k] = -1 - k; s.pnode[k] = kNoParent;
+            s.hash[k] = (unsigned long long)(unsigned)in[L.in_hash() + 2 * k] | (unsigned long long)(unsigned)in[L.in_hash() + 2 * k + 1] << 32;
+            s.phash[k] = (unsigned long long)(unsigned)in[L.in_phash() + 2 * k] | (unsigned long long)(unsigned)in[L.in_phash() + 2 * k + 1] << 32;
+        }
+    } else if (tid == 0) {
         Slots& s = sl[0];
         s.pb[0] = 0.f; s.pnb[0] = ninf(); s.tot[0] = 0.f;
         s.e[0] = -1; s.len[0] = 0; s.node[0] = -1; s.pnode[0] = -1;
@@ -69,6 +145,10 @@ __global__ __launch_bounds__(PT) void k_ctc_prefix(CtcPrefixArgs a) {
     }
     float px = T > 0 && tid < V ? lp[tid] : ninf();
     __syncthreads();
+    if constexpr (RESUME) {   // the first frame's fold table: the relations among the carried slots
+        fold_table(sl[0]);
+        __syncthreads();
+    }
     for (int t = 0; t < T; t++) {
         const Slots& c = sl[t & 1];
         Slots& nx = sl[(t + 1) & 1];
@@ -189,63 +269,75 @@ __global__ __launch_bounds__(PT) void k_ctc_prefix(CtcPrefixArgs a) {
         }
         if (tid == 0) nx.n = max(m, 1);
         __syncthreads();
-        // the next frame's fold table: does slot j spell slot k + [e_j]?  (live prefixes are distinct: at most one k per j)
-        if (tid < KB * KB) {
-            const int j = tid / KB, k = tid & (KB - 1), n2 = nx.n;
-            if (j < n2 && k < n2 && j != k && nx.len[j] == nx.len[k] + 1 && nx.phash[j] == nx.hash[k]) {
-                int p = nx.pnode[j], q = nx.node[k];
-                bool same = true;
-                while (p != q) {   // equal lengths: both chains end at -1 together; every step shortens both
-                    if (p < 0 || q < 0) { same = false; break; }
-                    const int4 np = nodes[p], nq = nodes[q];
-                    if (np.y != nq.y) { same = false; break; }
-                    p = np.x;
-                    q = nq.x;
-                }
-                if (same) fold_par[j] = k;
-            }
-        }
+        fold_table(nx);
         __syncthreads();
     }
     const Slots& f = sl[T & 1];
     const int n = f.n;
-    // a slot's chain walked back into a row, from index len - 1 down
-    auto write_chain = [&](int q, long long* tok, int* ts, float* yp, long long o) {
-        int node = f.node[q];
-        for (int i = f.len[q] - 1; i >= 0 && node >= 0; i--) {
-            const int4 nd = nodes[node];
-            tok[o + i] = nd.y;
-            ts[o + i] = nd.z;
-            if (yp) yp[o + i] = __int_as_float(nd.w);
-            node = nd.x;
-        }
-    };
-    if (tid == 64) {   // the single result: slot 0
-        const int len = f.len[0];
-        if (len > a.max_tokens) {
-            *a.overflow = 1;
-            a.n_tokens[r] = 0;
-        } else {
-            write_chain(0, a.tokens, a.timestamps, nullptr, (long long)r * a.max_tokens);
-            a.n_tokens[r] = len;
-        }
-        if (a.scores) a.scores[r] = f.tot[0];
-    }
-    if (a.nb.tokens && tid < KB) {
-        const int nh = min(n, a.nb.nbest), q = tid;
-        if (q < nh) {
-            const long long en = (long long)r * a.nb.nbest + q;
-            const int len = f.len[q];
-            if (len > a.max_tokens) {   // (the single result's rule, per entry)
-                *a.overflow = 1;
-                a.nb.n_tokens[en] = 0;
-            } else {
-                write_chain(q, a.nb.tokens, a.nb.timestamps, a.nb.token_log_probs, en * a.max_tokens);
-                a.nb.n_tokens[en] = len;
+    if constexpr (RESUME) {
+        const CtcPrefixResumeLayout L{beam, Tp};
+        int* out = a.out + (long long)r * L.out_ints();
+        if (tid == 0) out[0] = n;
+        if (tid < n) {   // survivor tid: back to its root for (origin, appended), then the appended part from its end down
+            const int q = tid;
+            int napp = 0, root = f.node[q];
+            while (root >= 0 && napp < Tp) { root = nodes[root].x; napp++; }
+            if (root >= 0 || root == kNoParent || -1 - root >= beam) { *a.status = 1; root = -1; napp = 0; }
+            out[L.out_org() + q] = -1 - root;
+            out[L.out_napp() + q] = napp;
+            out[L.out_pb() + q] = __float_as_int(f.pb[q]);
+            out[L.out_pnb() + q] = __float_as_int(f.pnb[q]);
+            out[L.out_tot() + q] = __float_as_int(f.tot[q]);
+            out[L.out_hash() + 2 * q] = (int)(unsigned)f.hash[q]; out[L.out_hash() + 2 * q + 1] = (int)(unsigned)(f.hash[q] >> 32);
+            out[L.out_phash() + 2 * q] = (int)(unsigned)f.phash[q]; out[L.out_phash() + 2 * q + 1] = (int)(unsigned)(f.phash[q] >> 32);
+            int node = f.node[q];
+            for (int i = napp - 1; i >= 0; i--) {
+                const int4 nd = nodes[node];
+                out[L.out_ys() + q * Tp + i] = nd.y;
+                out[L.out_ts() + q * Tp + i] = nd.z;
+                out[L.out_yp() + q * Tp + i] = nd.w;
+                node = nd.x;
             }
-            a.nb.scores[en] = f.tot[q];
         }
-        if (tid == 0) a.nb.n_hyps[r] = nh;
+    } else {
+        // a slot's chain walked back into a row, from index len - 1 down
+        auto write_chain = [&](int q, long long* tok, int* ts, float* yp, long long o) {
+            int node = f.node[q];
+            for (int i = f.len[q] - 1; i >= 0 && node >= 0; i--) {
+                const int4 nd = nodes[node];
+                tok[o + i] = nd.y;
+                ts[o + i] = nd.z;
+                if (yp) yp[o + i] = __int_as_float(nd.w);
+                node = nd.x;
+            }
+        };
+        if (tid == 64) {   // the single result: slot 0
+            const int len = f.len[0];
+            if (len > a.max_tokens) {
+                *a.overflow = 1;
+                a.n_tokens[r] = 0;
+            } else {
+                write_chain(0, a.tokens, a.timestamps, nullptr, (long long)r * a.max_tokens);
+                a.n_tokens[r] = len;
+            }
+            if (a.scores) a.scores[r] = f.tot[0];
+        }
+        if (a.nb.tokens && tid < KB) {
+            const int nh = min(n, a.nb.nbest), q = tid;
+            if (q < nh) {
+                const long long en = (long long)r * a.nb.nbest + q;
+                const int len = f.len[q];
+                if (len > a.max_tokens) {   // (the single result's rule, per entry)
+                    *a.overflow = 1;
+                    a.nb.n_tokens[en] = 0;
+                } else {
+                    write_chain(q, a.nb.tokens, a.nb.timestamps, a.nb.token_log_probs, en * a.max_tokens);
+                    a.nb.n_tokens[en] = len;
+                }
+                a.nb.scores[en] = f.tot[q];
+            }
+            if (tid == 0) a.nb.n_hyps[r] = nh;
+        }
     }
 }
 
@@ -256,7 +348,16 @@ void ctc_prefix_search(const Ctx& ctx, const CtcPrefixArgs& a) {
     K2_REQUIRE(a.R >= 1 && a.R <= 65535 && a.Tp >= 1 && a.V >= 1 && (long long)kMaxBeam * a.V <= INT_MAX && a.beam >= 1 && a.beam <= kMaxBeam &&
                    a.max_tokens >= 1 && (!a.nb.tokens || (a.nb.nbest >= 1 && a.nb.nbest <= a.beam)),
                "ctc_prefix_search: bad shape R=%d T'=%d V=%d beam=%d nbest=%d max_tokens=%d", a.R, a.Tp, a.V, a.beam, a.nb.nbest, a.max_tokens);
-    hipLaunchKernelGGL(k_ctc_prefix, dim3(a.R), dim3(PT), 0, ctx.stream, a);
+    hipLaunchKernelGGL((k_ctc_prefix<false, CtcPrefixArgs>), dim3(a.R), dim3(PT), 0, ctx.stream, a);
+    K2_HIP(hipGetLastError());
+}
+
+void ctc_prefix_resume(const Ctx& ctx, const CtcPrefixResumeArgs& a) {
+    if (ctx.dry) return;
+    K2_REQUIRE(a.B >= 1 && a.B <= 65535 && a.Tc >= 1 && a.V >= 1 && (long long)kMaxBeam * a.V <= INT_MAX && a.beam >= 1 && a.beam <= kMaxBeam &&
+                   (long long)a.Tc * a.beam <= INT_MAX / 2 && a.in && a.out && a.nodes && a.status,
+               "ctc_prefix_resume: bad shape B=%d Tc=%d V=%d beam=%d", a.B, a.Tc, a.V, a.beam);
+    hipLaunchKernelGGL((k_ctc_prefix<true, CtcPrefixResumeArgs>), dim3(a.B), dim3(PT), 0, ctx.stream, a);
     K2_HIP(hipGetLastError());
 }
 

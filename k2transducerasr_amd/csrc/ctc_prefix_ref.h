@@ -48,76 +48,90 @@ struct CtcPrefixRefResult {
     long long respelled_folds = 0;       // folds into a slot whose history parent is not the folded slot's node (the trap)
 };
 
-// lp: [T][ld] (ld >= V)
-inline CtcPrefixRefResult ctc_prefix_ref(const float* lp, int64_t ld, int T, int V, int beam) {
-    K2_REQUIRE(T >= 1 && V >= 1 && beam >= 1, "ctc_prefix_ref: T=%d V=%d beam=%d", T, V, beam);
+// THE FRAME STEP: the live slots `cur` over one frame's row, given the frame's fold table (fold_par[j] = the slot k with y_j = y_k +
+// [e_j] as token sequences, or -1).  How the table is decided is the caller's: the whole-row search below compares token lists, the
+// resumed search (tests/native/engine_stub_ctc_prefix_stream.cpp) goes through its relation tables.  A hypothesis' last token is
+// `last` (-1 for the empty prefix): the resumed form does not hold the carried tokens.
+struct CtcPrefixRefSlot {
+    CtcPrefixRefHyp h;
+    int64_t last = -1;
+    int origin = 0;   // the carried slot a resumed search started this hypothesis from (h then holds the chunk's part only)
+};
+inline std::vector<CtcPrefixRefSlot> ctc_prefix_ref_frame(const std::vector<CtcPrefixRefSlot>& cur, const std::vector<int>& fold_par, const float* row,
+                                                          int t, int V, int beam, long long* next_node) {
     const float ninf = -std::numeric_limits<float>::infinity();
     struct Cand {
         float tot, pb, pnb;
         long long idx;
     };
+    const int n = (int)cur.size();
+    std::vector<Cand> cands;
+    for (int k = 0; k < n; k++) {
+        const CtcPrefixRefHyp& h = cur[(size_t)k].h;
+        const int64_t e = cur[(size_t)k].last;
+        Cand s;
+        s.idx = (long long)k * V;
+        s.pb = h.tot + row[0];
+        s.pnb = e >= 0 ? h.pnb + row[e] : ninf;
+        if (fold_par[(size_t)k] >= 0) {
+            const CtcPrefixRefSlot& p = cur[(size_t)fold_par[(size_t)k]];
+            s.pnb = ctc_prefix_logaddexp(s.pnb, (e == p.last ? p.h.pb : p.h.tot) + row[e]);
+        }
+        s.tot = ctc_prefix_logaddexp(s.pb, s.pnb);
+        cands.push_back(s);
+        for (int v = 1; v < V; v++) {
+            bool folded = false;
+            for (int j = 0; j < n; j++) folded = folded || (fold_par[(size_t)j] == k && cur[(size_t)j].last == v);
+            if (folded) continue;
+            const float x = (v == e ? h.pb : h.tot) + row[v];
+            cands.push_back(Cand{x, ninf, x, (long long)k * V + v});
+        }
+    }
+    const Cand stay0 = cands[0];
+    cands.erase(std::remove_if(cands.begin(), cands.end(), [&](const Cand& c) { return !(c.tot > ninf); }), cands.end());
+    std::sort(cands.begin(), cands.end(), [](const Cand& a, const Cand& b) { return a.tot > b.tot || (a.tot == b.tot && a.idx < b.idx); });
+    if (cands.empty()) cands.push_back(stay0);
+    if ((int)cands.size() > beam) cands.resize((size_t)beam);
+    std::vector<CtcPrefixRefSlot> nxt;
+    for (const Cand& c : cands) {
+        const int k = (int)(c.idx / V), v = (int)(c.idx % V);
+        CtcPrefixRefSlot s = cur[(size_t)k];
+        s.h.pb = c.pb; s.h.pnb = c.pnb; s.h.tot = c.tot;
+        if (v) {
+            s.h.tokens.push_back(v);
+            s.h.timestamps.push_back(t);
+            s.h.token_log_probs.push_back(row[v]);
+            s.h.parent_node = s.h.node;
+            s.h.node = (*next_node)++;
+            s.last = v;
+        }
+        nxt.push_back(std::move(s));
+    }
+    return nxt;
+}
+
+// lp: [T][ld] (ld >= V)
+inline CtcPrefixRefResult ctc_prefix_ref(const float* lp, int64_t ld, int T, int V, int beam) {
+    K2_REQUIRE(T >= 1 && V >= 1 && beam >= 1, "ctc_prefix_ref: T=%d V=%d beam=%d", T, V, beam);
     CtcPrefixRefResult res;
-    std::vector<CtcPrefixRefHyp> cur(1), nxt;
-    cur[0].pb = 0.f; cur[0].pnb = ninf; cur[0].tot = 0.f;
+    std::vector<CtcPrefixRefSlot> cur(1);
+    cur[0].h.pb = 0.f; cur[0].h.pnb = -std::numeric_limits<float>::infinity(); cur[0].h.tot = 0.f;
     long long next_node = 0;
     for (int t = 0; t < T; t++) {
-        const float* row = lp + (size_t)t * (size_t)ld;
         const int n = (int)cur.size();
-        // fold_into[k V + v] as a short list: (k, v) -> j
         std::vector<int> fold_par((size_t)n, -1);   // j -> the slot k whose extension by e_j spells j
         for (int j = 0; j < n; j++)
             for (int k = 0; k < n; k++) {
-                if (j == k || cur[(size_t)j].tokens.size() != cur[(size_t)k].tokens.size() + 1) continue;
-                if (std::equal(cur[(size_t)k].tokens.begin(), cur[(size_t)k].tokens.end(), cur[(size_t)j].tokens.begin())) {
+                const CtcPrefixRefHyp &hj = cur[(size_t)j].h, &hk = cur[(size_t)k].h;
+                if (j == k || hj.tokens.size() != hk.tokens.size() + 1) continue;
+                if (std::equal(hk.tokens.begin(), hk.tokens.end(), hj.tokens.begin())) {
                     fold_par[(size_t)j] = k;
-                    if (cur[(size_t)j].parent_node != cur[(size_t)k].node) res.respelled_folds++;
+                    if (hj.parent_node != hk.node) res.respelled_folds++;
                 }
             }
-        std::vector<Cand> cands;
-        for (int k = 0; k < n; k++) {
-            const CtcPrefixRefHyp& h = cur[(size_t)k];
-            const int64_t e = h.tokens.empty() ? -1 : h.tokens.back();
-            Cand s;
-            s.idx = (long long)k * V;
-            s.pb = h.tot + row[0];
-            s.pnb = e >= 0 ? h.pnb + row[e] : ninf;
-            if (fold_par[(size_t)k] >= 0) {
-                const CtcPrefixRefHyp& p = cur[(size_t)fold_par[(size_t)k]];
-                const int64_t ep = p.tokens.empty() ? -1 : p.tokens.back();
-                s.pnb = ctc_prefix_logaddexp(s.pnb, (e == ep ? p.pb : p.tot) + row[e]);
-            }
-            s.tot = ctc_prefix_logaddexp(s.pb, s.pnb);
-            cands.push_back(s);
-            for (int v = 1; v < V; v++) {
-                bool folded = false;
-                for (int j = 0; j < n; j++) folded = folded || (fold_par[(size_t)j] == k && cur[(size_t)j].tokens.back() == v);
-                if (folded) continue;
-                const float x = (v == e ? h.pb : h.tot) + row[v];
-                cands.push_back(Cand{x, ninf, x, (long long)k * V + v});
-            }
-        }
-        const Cand stay0 = cands[0];
-        cands.erase(std::remove_if(cands.begin(), cands.end(), [&](const Cand& c) { return !(c.tot > ninf); }), cands.end());
-        std::sort(cands.begin(), cands.end(), [](const Cand& a, const Cand& b) { return a.tot > b.tot || (a.tot == b.tot && a.idx < b.idx); });
-        if (cands.empty()) cands.push_back(stay0);
-        if ((int)cands.size() > beam) cands.resize((size_t)beam);
-        nxt.clear();
-        for (const Cand& c : cands) {
-            const int k = (int)(c.idx / V), v = (int)(c.idx % V);
-            CtcPrefixRefHyp h = cur[(size_t)k];
-            h.pb = c.pb; h.pnb = c.pnb; h.tot = c.tot;
-            if (v) {
-                h.tokens.push_back(v);
-                h.timestamps.push_back(t);
-                h.token_log_probs.push_back(row[v]);
-                h.parent_node = h.node;
-                h.node = next_node++;
-            }
-            nxt.push_back(std::move(h));
-        }
-        cur.swap(nxt);
+        cur = ctc_prefix_ref_frame(cur, fold_par, lp + (size_t)t * (size_t)ld, t, V, beam, &next_node);
     }
-    res.hyps = std::move(cur);
+    for (CtcPrefixRefSlot& s : cur) res.hyps.push_back(std::move(s.h));
     return res;
 }
 
@@ -130,6 +144,28 @@ inline void ctc_prefix_check_args(int R, int Tp, int V, const int32_t* n_frames,
     if (n_frames)
         for (int r = 0; r < R; r++)
             K2_REQUIRE(n_frames[r] >= 1 && n_frames[r] <= Tp, "ctc_prefix_beam_search: row %d has n_frames = %d outside [1, T' = %d]", r, n_frames[r], Tp);
+}
+
+// The argument rules of the resumed search's chunk (k2hip_ctc_prefix_beam_search_chunk / Engine::ctc_prefix_chunk_host / the debug op),
+// checked before any device work; in: [B] blocks of `in_ints` ints laid out as CtcPrefixResumeLayout{K, Tc} (the offsets are passed in:
+// this header knows no layout), of which the kernel indexes with n, the last tokens and the relation lengths
+inline void ctc_prefix_chunk_check_args(int B, int Tc, int V, const int32_t* n_frames, int K, const int* in, int in_ints, int o_e, int o_rel) {
+    K2_REQUIRE(B >= 1 && B <= 65535, "ctc_prefix_beam_search_chunk: B = %d streams outside [1, 65535]", B);
+    K2_REQUIRE(Tc >= 1 && V >= 1 && (long long)Tc * kCtcPrefixMaxBeam <= (1 << 30), "ctc_prefix_beam_search_chunk: bad shape Tc=%d V=%d", Tc, V);
+    K2_REQUIRE(K >= 1 && K <= kCtcPrefixMaxBeam, "ctc_prefix_beam_search_chunk: beam %d out of range [1,%d]", K, kCtcPrefixMaxBeam);
+    if (n_frames)
+        for (int b = 0; b < B; b++)
+            K2_REQUIRE(n_frames[b] >= 1 && n_frames[b] <= Tc, "ctc_prefix_beam_search_chunk: stream %d has n_frames = %d outside [1, Tc = %d]", b, n_frames[b], Tc);
+    K2_REQUIRE(in, "ctc_prefix_beam_search_chunk: null in blocks");
+    for (int b = 0; b < B; b++) {
+        const int* blk = in + (size_t)b * (size_t)in_ints;
+        K2_REQUIRE(blk[0] >= 1 && blk[0] <= K, "ctc_prefix_beam_search_chunk: stream %d carries %d prefixes (beam %d)", b, blk[0], K);
+        for (int k = 0; k < K; k++) {
+            K2_REQUIRE(blk[o_e + k] >= -1 && blk[o_e + k] < V && blk[o_e + k] != 0, "ctc_prefix_beam_search_chunk: stream %d slot %d ends in token %d", b, k, blk[o_e + k]);
+            for (int j = 0; j < K; j++)
+                K2_REQUIRE(blk[o_rel + k * K + j] >= -1 && blk[o_rel + k * K + j] <= Tc, "ctc_prefix_beam_search_chunk: stream %d: relation %d", b, blk[o_rel + k * K + j]);
+        }
+    }
 }
 
 }  // namespace k2hip

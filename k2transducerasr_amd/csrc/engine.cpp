@@ -816,6 +816,45 @@ void Engine::ctc_prefix_host(const float* log_probs, int R, int Tp, const int32_
     }
 }
 
+// the prefix search resumed from carried prefixes (streaming chunk; CtcPrefixResumeLayout{K, Tc} blocks)
+static_assert(kCtcPrefixHashSeed != 0, "the empty prefix's hash is the seed");
+void Engine::ctc_prefix_chunk_host(const float* log_probs, int B, int Tc, const int32_t* n_frames, int K, const int* in, int* out) {
+    const Config& cf = model_->cfg();
+    if (!cf.ctc) failf(K2HIP_ERR_UNSUPPORTED, "ctc_prefix_beam_search_chunk: model_type '%s' has no CTC head", cf.model_type.c_str());
+    K2_REQUIRE(log_probs && in && out, "ctc_prefix_beam_search_chunk: null argument");
+    const CtcPrefixResumeLayout L{K, Tc};
+    ctc_prefix_chunk_check_args(B, Tc, cf.V, n_frames, K, in, L.in_ints(), L.in_e(), L.in_rel());
+    // ONE upload [log_probs | in blocks | n_frames | status] and ONE download [status | out blocks]
+    const int64_t nb_lp = (int64_t)sizeof(float) * B * Tc * cf.V, nb_in = (int64_t)sizeof(int) * B * L.in_ints(), nb_nf = (int64_t)sizeof(int) * B,
+                  nb_out = (int64_t)sizeof(int) * B * L.out_ints();
+    const int64_t o_in = align_up(nb_lp, 16), o_nf = align_up(o_in + nb_in, 16), o_st = align_up(o_nf + nb_nf, 16), in_bytes = o_st + 16;
+    K2_HIP(hipSetDevice(device_));
+    char* stage = static_cast<char*>(pinned_in(in_bytes));
+    memcpy(stage, log_probs, (size_t)nb_lp);
+    memcpy(stage + o_in, in, (size_t)nb_in);
+    if (n_frames) memcpy(stage + o_nf, n_frames, (size_t)nb_nf);
+    memset(stage + o_st, 0, 16);
+    int* d_st = nullptr;
+    run_sized([&](const Ctx& c) {
+        char* d = c.arena->take<char>(in_bytes + nb_out);
+        d_st = reinterpret_cast<int*>(d + o_st);
+        if (!c.dry) K2_HIP(hipMemcpyAsync(d, stage, (size_t)in_bytes, hipMemcpyHostToDevice, c.stream));
+        CtcPrefixResumeArgs a;
+        a.log_probs = reinterpret_cast<const float*>(d); a.B = B; a.Tc = Tc; a.V = cf.V; a.beam = K;
+        a.n_frames = n_frames ? reinterpret_cast<const int*>(d + o_nf) : nullptr;
+        a.nodes = c.arena->take<int4>((int64_t)B * Tc * K);
+        a.in = reinterpret_cast<const int*>(d + o_in);
+        a.out = reinterpret_cast<int*>(d + in_bytes);
+        a.status = d_st;
+        ctc_prefix_resume(c, a);
+    });
+    char* pin = static_cast<char*>(pinned(16 + nb_out));
+    K2_HIP(hipMemcpyAsync(pin, d_st, (size_t)(16 + nb_out), hipMemcpyDeviceToHost, stream_));
+    K2_HIP(hipStreamSynchronize(stream_));
+    if (*reinterpret_cast<int*>(pin)) failf(K2HIP_ERR_INVALID, "ctc_prefix_beam_search_chunk: an in block contradicts itself (its relations name tokens the chunk cannot walk)");
+    memcpy(out, pin + 16, (size_t)nb_out);
+}
+
 // modified beam search instead of the greedy loop (set_beam(K) selects it for the fused / operator entry points)
 Engine::SearchExtras Engine::beam_device(const Ctx& c, const float* enc, int B, int Tp, const SearchOut& out, bool keep_nbest) {
     BeamArgs a;
@@ -2367,6 +2406,28 @@ void Engine::debug_op_host(const char* op, const int64_t* iargs, int n_iargs, vo
             });
             K2_HIP(hipStreamSynchronize(stream_));
             K2_HIP(copy_blocking(dev[8], out.flag(), 4, hipMemcpyDeviceToDevice));
+        } else if (name == "ctc_prefix_resume") {
+            // bufs log_probs [B][Tc][V], n_frames [B] int32 (or null), in [B][in_ints] (caller-supplied), out [B][out_ints], status [1] int32
+            //   (out); ints B, Tc, V, beam.  The kernel stores straight into the guarded buffers.
+            K2_REQUIRE(n_bufs == 5, "debug_op_run %s: %d buffers", op, n_bufs);
+            for (int k = 0; k < n_bufs; k++) P();
+            const int B = I(), Tc = I(), V = I(), beam = I();
+            K2_REQUIRE(B >= 1 && Tc >= 1 && V >= 1 && beam >= 1 && beam <= kMaxBeam, "debug_op_run %s: bad shape", op);
+            const CtcPrefixResumeLayout RL{beam, Tc};
+            K2_REQUIRE(!bufs[1] || buf_bytes[1] >= 4 * (int64_t)B, "debug_op_run %s: n_frames is too short", op);
+            K2_REQUIRE(bufs[2] && buf_bytes[2] >= 4 * (int64_t)B * RL.in_ints(), "debug_op_run %s: the in blocks are too short", op);
+            ctc_prefix_chunk_check_args(B, Tc, V, static_cast<const int32_t*>(bufs[1]), beam, static_cast<const int*>(bufs[2]), RL.in_ints(), RL.in_e(), RL.in_rel());
+            K2_REQUIRE(dev[0] && buf_bytes[0] >= 4 * (int64_t)B * Tc * V, "debug_op_run %s: log_probs is too short", op);
+            K2_REQUIRE(dev[3] && dev[4] && buf_bytes[3] >= 4 * (int64_t)B * RL.out_ints() && buf_bytes[4] >= 4, "debug_op_run %s: the result buffers are too short", op);
+            CtcPrefixResumeArgs a;
+            a.log_probs = static_cast<const float*>(dev[0]); a.B = B; a.Tc = Tc; a.V = V; a.beam = beam;
+            a.n_frames = static_cast<const int*>(dev[1]);
+            a.in = static_cast<const int*>(dev[2]); a.out = static_cast<int*>(dev[3]); a.status = static_cast<int*>(dev[4]);
+            K2_HIP(hipMemsetAsync(dev[4], 0, sizeof(int), stream_));
+            run_sized([&](const Ctx& cc) {
+                a.nodes = cc.arena->take<int4>((int64_t)B * Tc * beam);
+                ctc_prefix_resume(cc, a);
+            });
         } else if (name == "basicnorm") {
             float *x = P(), *le = P(), *y = P();
             const int M = I(), D = I();

@@ -103,6 +103,10 @@ class Engine {
                          float* token_log_probs, int32_t* n_tokens, int32_t* n_hyps, float* scores, int max_tokens);
     // decoding method of a CTC model's batch entries: 0 = the reference's argmax-and-collapse, K >= 1 = the prefix beam search with beam K
     // (the single-stream path always collapses)
+    // operator level of the resumed prefix search (streaming): log_probs [B, Tc, V] host, n_frames [B] in [1, Tc] or null, in / out
+    // blocks of CtcPrefixResumeLayout{K, Tc} (host; the stream histories of ctc_prefix_hist.h fill and apply them).  One upload, one
+    // launch, one download; the arguments are checked on the host before any device work.
+    void ctc_prefix_chunk_host(const float* log_probs, int B, int Tc, const int32_t* n_frames, int K, const int* in, int* out);
     void set_ctc_prefix(int k) { ctc_prefix_ = k; }
     int ctc_prefix() const { return ctc_prefix_; }
     // ---- fused paths ----
@@ -146,6 +150,11 @@ class Engine {
     // download).  Transducer models only.
     void online_step_beam(const int* slots, const float* const* chunks, const long long* plens, const int* nchunks, int B, int K,
                           const int* beam_in, int* beam_out, const int* fifo_heads = nullptr);
+    // the tick of a CTC model under the carried prefix search with beam K: cp_in [B] blocks of CtcPrefixResumeLayout{K, T'}.in_ints() ints
+    // (uploaded with the tick's inputs), cp_out [B] blocks of out_ints() (the tick's one download); the resumed kernel runs on the
+    // tick's log-probs.  CTC models only.
+    void online_step_ctc_prefix(const int* slots, const float* const* chunks, const long long* plens, const int* nchunks, int B, int K,
+                                const int* cp_in, int* cp_out, const int* fifo_heads = nullptr);
     // operator level of the resumed search: enc [B, Tp, J] host, in / out blocks of BeamResumeLayout{K, Tp} (host)
     void beam_chunk_host(const float* enc, int B, int Tp, int K, const int* beam_in, int* beam_out);
     // The two entry points above with per-stream hotword graphs (BeamArgs::hw_streams): side blocks of their own beside the
@@ -352,8 +361,10 @@ class Engine {
                             const BeamHwIO* hw = nullptr);
     void beam_chunk_impl(const float* enc, int B, int Tp, int K, const int* beam_in, int* beam_out, const BeamHwIO* hw);
     struct OnlineBeamIO { int K; const int* in; int* out; const BeamHwIO* hw; };
+    struct OnlineCtcPrefixIO { int K; const int* in; int* out; };
     void online_step_impl(const int* slots, const float* const* chunks, const long long* hyps, const long long* plens, const int* nchunks,
-                          int B, int64_t* tokens, int32_t* ts, int32_t* n_tokens, const int* fifo_heads, const OnlineBeamIO* beam);
+                          int B, int64_t* tokens, int32_t* ts, int32_t* n_tokens, const int* fifo_heads, const OnlineBeamIO* beam,
+                          const OnlineCtcPrefixIO* cpx = nullptr);
     // LSTM transducer (lstm_engine.cpp)
     int lstm_out_frames(int T) const;
     float* lstm_embed(const Ctx& c, const float* x, int B, int T, int* T_out);

@@ -2,6 +2,7 @@
 // returns immediately; in a dry run (ctx.dry) nothing is launched -- the dry
 // pass only sizes the arena.
 #pragma once
+#include "ctc_prefix_layout.h"
 #include "common.h"
 
 namespace k2hip {
@@ -748,6 +749,26 @@ struct CtcPrefixArgs {
 };
 // One workgroup of 256 per row, frames sequential, no workgroup waits for another; every store is an ordinary vector store
 void ctc_prefix_search(const Ctx& ctx, const CtcPrefixArgs& a);
+// The search resumed from the live prefixes of the chunks before (streaming: one chunk of <= Tc frames per call).  Carried slot a is
+// the prefix S_a, whose tokens only the host keeps (ctc_prefix_hist.h); inside the chunk a prefix is (carried slot, suffix of <= Tc
+// tokens).  rel[a][b] = |x| when S_a = S_b + x with 0 < |x| <= Tc (x = relx[a][b]), else -1 (0 on the diagonal), as BeamResumeLayout.
+// The hashes are the kernel's own rolling hashes of the prefix and of the prefix without its last token, passed back as they came out.
+// Per stream, `in` (ints):  [n | pb[K] | pnb[K] (float bits) | e[K] (last token, -1: empty) | len[K] | hash[K][2] | phash[K][2] (lo, hi) |
+//                            rel[K][K] | relx[K][K][Tc]]
+//             `out` (ints): [n | org[K] | napp[K] | pb[K] | pnb[K] (float bits) | hash[K][2] | phash[K][2] | tot[K] (float bits: the score) |
+//                            ys[K][Tc] | ts[K][Tc] (chunk-relative) | yp[K][Tc] (float bits)], the survivors in rank order
+// (CtcPrefixResumeLayout{K, Tc}: ctc_prefix_layout.h, shared with the host history ctc_prefix_hist.h)
+struct CtcPrefixResumeArgs {
+    const float* log_probs = nullptr;   // [B, Tc, V], log-softmaxed
+    int B = 0, Tc = 0, V = 0;
+    const int* n_frames = nullptr;      // [B] (device), each in [1, Tc], or null = Tc for every stream
+    int beam = 0;                       // 1 .. kMaxBeam: K of the layout
+    int4* nodes = nullptr;              // in-chunk history pool [B][Tc * beam]; a parent < 0 is the carried slot -1 - parent
+    const int* in = nullptr;            // [B][in_ints]
+    int* out = nullptr;                 // [B][out_ints]
+    int* status = nullptr;              // set to 1 when an in block contradicts itself (a bounded walk ran into its bound)
+};
+void ctc_prefix_resume(const Ctx& ctx, const CtcPrefixResumeArgs& a);
 
 // ---- streaming (online.hip): device-resident per-stream caches indexed by slot ------------------
 // ConvNeXt.streaming_forward's data movement in one launch: cat[b] = [cached_left_pad ; x], the cache advanced to x's frames Tc-3 .. Tc-1,

@@ -6,6 +6,7 @@
 #include <cmath>
 
 #include "engine.h"
+#include "ctc_prefix_ref.h"
 
 namespace k2hip {
 
@@ -298,8 +299,19 @@ void Engine::online_step_beam_hw(const int* slots, const float* const* chunks, c
     OnlineBeamIO io{K, beam_in, beam_out, &hw};
     online_step_impl(slots, chunks, hyps.data(), plens, nchunks, B, nullptr, nullptr, nullptr, fifo_heads, &io);
 }
+void Engine::online_step_ctc_prefix(const int* slots, const float* const* chunks, const long long* plens, const int* nchunks, int B, int K,
+                                    const int* cp_in, int* cp_out, const int* fifo_heads) {
+    K2_REQUIRE(K >= 1 && K <= kMaxBeam, "online ctc prefix search: beam %d out of range [1,%d]", K, kMaxBeam);
+    K2_REQUIRE(model_->cfg().ctc, "online ctc prefix search: the model has no CTC head");
+    const CtcPrefixResumeLayout L{K, online_frames_per_chunk()};
+    ctc_prefix_chunk_check_args(B, L.Tc, model_->cfg().V, nullptr, K, cp_in, L.in_ints(), L.in_e(), L.in_rel());
+    std::vector<long long> hyps(2 * (size_t)B, K2HIP_BLANK_ID);   // (the greedy search's context input; unused here)
+    OnlineCtcPrefixIO io{K, cp_in, cp_out};
+    online_step_impl(slots, chunks, hyps.data(), plens, nchunks, B, nullptr, nullptr, nullptr, fifo_heads, nullptr, &io);
+}
 void Engine::online_step_impl(const int* slots, const float* const* chunks, const long long* hyps, const long long* plens, const int* nchunks,
-                              int B, int64_t* tokens, int32_t* ts, int32_t* n_tokens, const int* fifo_heads, const OnlineBeamIO* beam) {
+                              int B, int64_t* tokens, int32_t* ts, int32_t* n_tokens, const int* fifo_heads, const OnlineBeamIO* beam,
+                              const OnlineCtcPrefixIO* cpx) {
     online_ensure_pool();
     K2_REQUIRE(B > 0, "online_step: no ready stream");
     const Model& m = *model_;
@@ -319,9 +331,14 @@ void Engine::online_step_impl(const int* slots, const float* const* chunks, cons
     // hypotheses' graph states and the streams' table pointers follow the in blocks, the survivors' states the out blocks.
     const BeamResumeLayout RL{beam ? beam->K : 1, Tp};
     const BeamHwIO* bhw = beam ? beam->hw : nullptr;
-    const int64_t nb_bin = beam ? (int64_t)sizeof(int) * RL.in_ints() * B : 0;
+    // A CTC model under the carried prefix search: its in blocks ride where the beam search's do, its out blocks come back the same way
+    // (the flag is the resumed kernel's status word)
+    const CtcPrefixResumeLayout CL{cpx ? cpx->K : 1, Tp};
+    K2_REQUIRE(!(beam && cpx), "internal: one search per tick");
+    const int64_t nb_bin = beam ? (int64_t)sizeof(int) * RL.in_ints() * B : cpx ? (int64_t)sizeof(int) * CL.in_ints() * B : 0;
     const int64_t nb_hst = bhw ? (int64_t)sizeof(int) * beam->K * B * (bhw->lm ? 2 : 1) : 0, nb_hg = bhw ? (int64_t)sizeof(BeamHwStream) * B : 0;
-    const int64_t nb_bout = beam ? (int64_t)sizeof(int) * RL.out_ints() * B + nb_hst : 0, o_hout = nb_bout - nb_hst;
+    const int64_t nb_bout = beam ? (int64_t)sizeof(int) * RL.out_ints() * B + nb_hst : cpx ? (int64_t)sizeof(int) * CL.out_ints() * B : 0,
+                  o_hout = nb_bout - nb_hst;
     const int64_t nb_x = from_fifo ? 0 : (int64_t)sizeof(float) * chunk_floats * B;
     const int64_t o_plen = align_up(nb_x, 16), o_hyp = o_plen + 8 * (int64_t)B, o_slots = o_hyp + 16 * (int64_t)B, o_chunks = o_slots + 4 * (int64_t)B,
                   o_heads = o_chunks + 4 * (int64_t)B, o_bin = align_up(o_heads + 4 * (int64_t)B, 16), o_hst = align_up(o_bin + nb_bin, 16),
@@ -336,12 +353,13 @@ void Engine::online_step_impl(const int* slots, const float* const* chunks, cons
     if (from_fifo) memcpy(stage + o_heads, fifo_heads, sizeof(int) * B);
     else memset(stage + o_heads, 0, sizeof(int) * B);
     if (beam) memcpy(stage + o_bin, beam->in, (size_t)nb_bin);
+    if (cpx) memcpy(stage + o_bin, cpx->in, (size_t)nb_bin);
     if (bhw) {
         memcpy(stage + o_hst, bhw->st_in, (size_t)nb_hst);
         memcpy(stage + o_hg, bhw->graphs, (size_t)nb_hg);
     }
     memset(stage + o_ovf, 0, 16);
-    const int64_t nb_out = beam ? nb_bout : SearchOut::bytes_for(B, Tp) - 16;   // what follows the flag
+    const int64_t nb_out = beam || cpx ? nb_bout : SearchOut::bytes_for(B, Tp) - 16;   // what follows the flag
     run_sized([&](const Ctx& c) {
         Arena& ar = *c.arena;
         // one device block: the inputs, the overflow flag (uploaded as zero: the last 16 bytes of the input part), the outputs right
@@ -375,7 +393,18 @@ void Engine::online_step_impl(const int* slots, const float* const* chunks, cons
         if (!c.dry) K2_HIP(hipEventRecord(ev_[3], c.stream));
         if (cf.ctc) {
             // OnlineRecognizer.ForwardBatchGreedySearchCTC (:220-313): per-chunk CTC collapse, prev_id reset per chunk
-            ex = ctc_device(c, enc, B, Tp, out);
+            // ... or, for streams that opted in, the prefix search resumed from their carried prefixes on the tick's log-probs
+            if (cpx) {
+                CtcPrefixResumeArgs a;
+                a.log_probs = enc; a.B = B; a.Tc = Tp; a.V = cf.V; a.beam = cpx->K;
+                a.nodes = ar.take<int4>((int64_t)B * Tp * cpx->K);
+                a.in = reinterpret_cast<const int*>(d_in + o_bin);
+                a.out = reinterpret_cast<int*>(d_out);
+                a.status = out.flag();
+                ctc_prefix_resume(c, a);
+            } else {
+                ex = ctc_device(c, enc, B, Tp, out);
+            }
         } else if (beam) {   // modified beam search resumed from the streams' saved hypotheses, on the tick's encoder buffer
             beam_resume_device(c, enc, B, Tp, beam->K, reinterpret_cast<const int*>(d_in + o_bin), reinterpret_cast<int*>(d_out), out.flag(),
                                bhw ? &dhw : nullptr);
@@ -393,7 +422,14 @@ void Engine::online_step_impl(const int* slots, const float* const* chunks, cons
         }
         if (!c.dry) K2_HIP(hipEventRecord(ev_[4], c.stream));
     });
-    if (beam) {   // ONE download: [flag | out blocks]
+    if (cpx) {   // ONE download: [status | out blocks]
+        char* pin = static_cast<char*>(pinned(16 + nb_bout));
+        K2_HIP(hipMemcpyAsync(pin, out.flag(), (size_t)(16 + nb_bout), hipMemcpyDeviceToHost, stream_));
+        K2_HIP(hipEventRecord(ev_[5], stream_));
+        K2_HIP(hipStreamSynchronize(stream_));
+        if (*reinterpret_cast<int*>(pin)) failf(K2HIP_ERR_HIP, "online ctc prefix search: an in block contradicts itself");
+        memcpy(cpx->out, pin + 16, (size_t)nb_bout);
+    } else if (beam) {   // ONE download: [flag | out blocks]
         char* pin = static_cast<char*>(pinned(16 + nb_bout));
         K2_HIP(hipMemcpyAsync(pin, out.flag(), (size_t)(16 + nb_bout), hipMemcpyDeviceToHost, stream_));
         K2_HIP(hipEventRecord(ev_[5], stream_));
@@ -409,12 +445,14 @@ void Engine::online_step_impl(const int* slots, const float* const* chunks, cons
 }
 
 // IOnlineProj.EncoderProj (OnlineProjOfZipformer2.cs:491-618) as an operator: feats [B, chunk_T, feat] host, the B slots' caches
-// advance in place, encoder_out [B, T', joiner_dim] to host.  The search is the caller's (DecoderProj / JoinerProj).
+// advance in place, encoder_out [B, T', joiner_dim] to host.  The search is the caller's (DecoderProj / JoinerProj).  A streaming
+// zipformer2ctc model delivers [B, T', V] log-probs instead (encoder_head ends in the CTC head and the row log-softmax): the producer of
+// k2hip_ctc_prefix_beam_search_chunk.
 void Engine::online_encoder(const int* slots, const float* feats, const long long* plens, const int* nchunks, int B, float* enc_out) {
     online_ensure_pool();
     K2_REQUIRE(B > 0, "online_encoder: empty batch");
     const Config& cf = model_->cfg();
-    K2_REQUIRE(cf.streaming && !cf.lstm && !cf.conformer && !cf.zip1 && !cf.ctc, "online_encoder: streaming Zipformer2 transducer models only");
+    K2_REQUIRE(cf.streaming && !cf.lstm && !cf.conformer && !cf.zip1, "online_encoder: streaming Zipformer2 models only");
     const int T = cf.chunk_T, Tp = online_frames_per_chunk();
     K2_HIP(hipSetDevice(device_));
     const size_t in_bytes = sizeof(float) * (size_t)B * T * cf.feat;
