@@ -356,7 +356,8 @@ int32_t k2hip_hotwords_pending(const k2hip_hotwords_t* hw, int32_t state, float*
  * afterwards) and keeps them until replaced or the model is destroyed; not while submitted batches are in flight.  Applies wherever
  * the offline modified beam search runs: k2hip_beam_search and the batch entry points under
  * k2hip_set_decoding_method("modified_beam_search") (k2hip_offline_greedy*, k2hip_offline_recognizer_get_results, submit / wait).
- * Greedy search, the CTC search and the single-stream path ignore it.  No hotwords, or an empty list: bit for bit the unbiased
+ * Greedy search, the CTC search and the single-stream path ignore it (the CTC prefix beam search uses it once
+ * k2hip_set_ctc_prefix_biasing is on).  No hotwords, or an empty list: bit for bit the unbiased
  * results.  This list is the OFFLINE batch's: with it set, k2hip_beam_search_chunk and k2hip_online_step under
  * modified_beam_search fail with K2HIP_ERR_INVALID, graphs attached to the streams or not (streaming greedy is untouched).
  * STREAMING takes its graph per stream, below. */
@@ -434,7 +435,8 @@ int32_t k2hip_ngram_lm_step(const k2hip_ngram_lm_t* lm, int32_t state, int64_t t
  * k2hip_set_nbest.
  * One setting per model.  Unlike the model-level hotword list it applies to BOTH searches: wherever the offline modified beam search
  * runs (as k2hip_set_hotwords), and in the streaming one (k2hip_online_step under modified_beam_search, k2hip_beam_search_chunk),
- * together with the streams' own hotword graphs.  Greedy search, the CTC search and the single-stream path ignore it.  No LM, a
+ * together with the streams' own hotword graphs.  Greedy search, the CTC search and the single-stream path ignore it (the CTC prefix
+ * beam search uses it once k2hip_set_ctc_prefix_biasing is on).  No LM, a
  * cleared LM and scale = 0: bit for bit the plain results, from the plain kernels.
  * STREAMING: after every step a stream holds exactly what the offline search with the same LM gives over all frames so far; the LM
  * state of every saved hypothesis crosses the chunk boundary.  A stream keeps the LM setting it decoded its first chunk with: after
@@ -574,8 +576,9 @@ int32_t k2hip_offline_ctc_align_from_samples(k2hip_model_t* model, const float* 
  * PREFIX IDENTITY IS SEQUENCE IDENTITY.  "Slot j spells y_k + [v]" speaks of token sequences, not of history nodes: when a prefix P
  * leaves the beam while its descendant P+w stays, P is later spelled again from its parent and that new P is extended by w, the
  * extension folds into the old P+w -- two equal prefixes are never live together.
- * Not covered: hotwords and the n-gram LM (ignored by this search), vocabulary pruning, length normalisation.  Streaming: the carried
- * form below (k2hip_ctc_prefix_beam_search_chunk).
+ * Not covered: vocabulary pruning, length normalisation.  Hotwords and the n-gram LM are ignored by this search unless the model opts
+ * in ("Hotword and n-gram LM biasing of the CTC prefix beam search" below).  Streaming: the carried form below
+ * (k2hip_ctc_prefix_beam_search_chunk).
  *
  * k2hip_ctc_prefix_beam_search: operator level.  Output shapes and the K2HIP_ERR_CAPACITY rule are those of k2hip_beam_search_nbest
  * (B = R).  K2HIP_ERR_UNSUPPORTED for a transducer model; K2HIP_ERR_INVALID for beam outside 1..8, nbest outside 1..beam, n_frames
@@ -584,6 +587,36 @@ int32_t k2hip_offline_ctc_align_from_samples(k2hip_model_t* model, const float* 
 int32_t k2hip_ctc_prefix_beam_search(k2hip_model_t* model, const float* log_probs, int32_t R, int32_t Tprime, const int32_t* n_frames,
                                      int32_t beam, int32_t nbest, int64_t* tokens, int32_t* timestamps, float* token_log_probs,
                                      int32_t* n_tokens, int32_t* n_hyps, float* scores, int32_t max_tokens);
+/* ---- Hotword and n-gram LM biasing of the CTC prefix beam search (offline; zipformer2ctc models) ---------------------------------
+ * The reference has no counterpart; the semantics are this project's own.  Everything not mentioned is the rule of "CTC prefix beam
+ * search with N-best" above, unchanged.  The tables are those of k2hip_set_hotwords (dense next / bonus [S][V], pending [S]) and
+ * k2hip_set_ngram_lm (the sparse automaton, every weight already multiplied by the scale).
+ * SLOT STATE.  Every live slot carries three more values: hs, the hotword graph state (start 0); ls, the LM state (start: the LM's
+ *   start state); ctx, the float32 accumulated context score (start 0.0f).  All three are functions of the slot's token sequence
+ *   alone, ctx bit for bit: a sequence is always built by the same float32 additions in the same order, also when it is re-spelled.
+ *   So the fold rule needs nothing new: a slot that receives a fold keeps its own hs, ls and ctx.  pb and pnb stay purely acoustic.
+ * CANDIDATE KEYS.  Stay candidate of slot k: key st_k + ctx_k, st_k = logaddexp(spb, spnb) as above.  Extension k V + v that is not
+ *   folded: cb = ctx_k + bonus[hs_k][v], key x + cb -- the hotword bonus takes part IN THE SELECTION (otherwise a biased token would
+ *   have to make a beam of at most 8 unaided).  A candidate is dropped when its ACOUSTIC total is -inf, as above.  Order: key
+ *   descending, exact ties to the lower flat index.  No finite candidate: slot 0's stay candidate survives alone, unchanged.
+ * A SELECTED EXTENSION takes hs' = next[hs_k][v], then the LM step (term, ls') = Step(ls_k, v) over the scaled tables, and
+ *   ctx' = cb + term, in that order.  The LM term is NOT in that frame's selection (as in the modified beam search); it is in every
+ *   later key.  Slots stay in selection rank order.
+ * UNK AND BLANK.  Unk (id 2) is an ordinary CTC token; for both automata it leaves the state alone and earns nothing (the dense
+ *   hotword tables say so; the LM walk is skipped).  Blank is never appended.
+ * AFTER THE LAST FRAME final_q = (tot_q + ctx_q) - pending[hs_q]: an unfinished match earns nothing; nothing is subtracted for the
+ *   LM.  Entries are ordered by final descending, ties to the lower slot; entry 0 is the result; scores and k2hip_last_scores report
+ *   final.  Token log-probs stay the input values lp(t, v).
+ * NULL AND TRIVIAL TABLES.  Hotwords without an LM, or an LM without hotwords: the missing half contributes exactly nothing.  An
+ *   empty graph, score_per_token = 0 or LM scale 0 adds +0.0f: the result is bit for bit the plain search.
+ *
+ * k2hip_set_ctc_prefix_biasing: the opt-in, OFF by default (then the search above ignores both tables and its results are bit for
+ * bit what they always were).  On: k2hip_ctc_prefix_beam_search and the batch entries under "ctc_prefix_beam_search"
+ * (k2hip_offline_greedy*, k2hip_offline_recognizer_get_results, submit / wait) use the model's hotword and LM tables; with neither
+ * set the plain search runs.  K2HIP_ERR_UNSUPPORTED for a transducer model; K2HIP_ERR_INVALID with batches in flight, as for
+ * k2hip_set_hotwords.  Unaffected either way: k2hip_online_step, k2hip_ctc_prefix_beam_search_chunk (the carried streaming search
+ * stays unbiased), the collapse, k2hip_ctc_align. */
+int32_t k2hip_set_ctc_prefix_biasing(k2hip_model_t* model, int32_t on);
 /* ---- streaming CTC prefix beam search: prefixes carried across chunks (operator level) ------------------------------------------
  * A k2hip_ctc_prefix_stream_t is one stream's live prefixes (host memory; no device slot), shaped like k2hip_beam_stream_t.
  * k2hip_ctc_prefix_beam_search_chunk continues every listed stream over its next n_frames[b] (NULL = Tc) rows of log_probs

@@ -117,6 +117,13 @@ int32_t k2hip_debug_gemm_run(k2hip_model_t* model, const float* A, const float* 
  *     int32, scores [R][nbest] -- and flag [1] int32, the search-output block's status word (1: an entry outgrew max_tokens and was not
  *     written); ints R, Tp, V, beam, nbest, max_tokens.  V here is free, not the model's.  The kernel stores straight into the guarded
  *     buffers, so what it does not write keeps the caller's fill.
+ *   "ctc_prefix_beam_bias" (tests/test_ctc_prefix_bias_gpu.py): the same kernel's biased instantiation alone.  The nine buffers of
+ *     "ctc_prefix_beam", then caller-supplied tables: next [S][V] int32, bonus [S][V], pending [S] (the dense hotword graph; all three or
+ *     all null), LM states [S_lm][4] int32 = (arc begin, arc end, back-off state, back-off weight bits), arc_tok / arc_lp / arc_next [A],
+ *     uni_lp / uni_next [V] (the scaled sparse LM; all or all null, the arc buffers null when A = 0); ints R, Tp, V, beam, nbest,
+ *     max_tokens, S, S_lm, A, start.  V is free.  Before the launch the host checks everything the kernel indexes with -- every next,
+ *     arc_next, uni_next and back-off state in range, arc ranges inside [0, A] and ordered, the start state in range -- and fails with
+ *     K2HIP_ERR_INVALID otherwise: a bad table cannot fault the device.
  *   "ctc_prefix_resume" (tests/test_ctc_prefix_stream_gpu.py): the same kernel's resume form alone.  Buffers log_probs [B][Tc][V],
  *     n_frames [B] int32 in 1..Tc (or null), in [B][in_ints] -- the caller's in blocks, laid out as kernels.h describes beside
  *     CtcPrefixResumeArgs (csrc/ctc_prefix_layout.h has the offsets) --, out [B][out_ints] and status [1] int32 (1: an in block

@@ -588,6 +588,12 @@ class Model:
         arr = (C.c_void_p * B)(*[s._h.value for s in streams])
         self._chk(self._L.k2hip_ctc_prefix_beam_search_chunk(self._h, arr, B, _f(x), x.shape[1], _i(nf) if nf is not None else None))
 
+    def set_ctc_prefix_biasing(self, on: bool = True):
+        """k2hip_set_ctc_prefix_biasing: the offline CTC prefix beam search (ctc_prefix_beam_search and the batch entries under that
+        decoding method) uses the hotwords and the n-gram LM set on the model; off (the default) it ignores both.  CTC models only."""
+        self._L.k2hip_set_ctc_prefix_biasing.argtypes = [C.c_void_p, C.c_int32]
+        self._chk(self._L.k2hip_set_ctc_prefix_biasing(self._h, 1 if on else 0))
+
     def set_hotwords(self, hotwords: Optional["Hotwords"] = None):
         """k2hip_set_hotwords: bias the offline modified beam search towards the graph's phrases; None clears.  The model keeps its own
         copy of the tables."""
@@ -927,10 +933,12 @@ class OfflineRecognizer:
     "modified_beam_search" (BASELINE.json configs[2]), or for a CTC model "ctc_prefix_beam_search" with beam / nbest (the streams then carry
     .alternatives()).  hotwords: a Hotwords graph, or a list of token-id phrases scored
     hotwords_score per matched token (sherpa's hotwords_file / hotwords_score); it biases modified_beam_search only.  ngram_lm: an
-    NgramLm fused with weight ngram_lm_scale (sherpa's lm / lm_scale), modified_beam_search only."""
+    NgramLm fused with weight ngram_lm_scale (sherpa's lm / lm_scale), modified_beam_search only.  ctc_prefix_biasing=True: a CTC model's
+    ctc_prefix_beam_search uses both as well (Model.set_ctc_prefix_biasing); without it the recognizer behaves as before."""
 
     def __init__(self, weights_path: str, device: int = 0, decoding_method: str = "greedy_search", beam: int = 4, hotwords=None,
-                 hotwords_score: float = 1.5, nbest: int = 1, ngram_lm: Optional["NgramLm"] = None, ngram_lm_scale: float = 0.3):
+                 hotwords_score: float = 1.5, nbest: int = 1, ngram_lm: Optional["NgramLm"] = None, ngram_lm_scale: float = 0.3,
+                 ctc_prefix_biasing: bool = False):
         self.model = Model(weights_path, device)
         self.model.set_decoding_method(decoding_method, beam)
         if nbest != 1:   # (streams then carry .alternatives() / .token_log_probs() after get_results)
@@ -941,6 +949,8 @@ class OfflineRecognizer:
             self.model.set_hotwords(hotwords)
         if ngram_lm is not None:
             self.model.set_ngram_lm(ngram_lm, ngram_lm_scale)
+        if ctc_prefix_biasing:
+            self.model.set_ctc_prefix_biasing(True)
 
     def create_offline_stream(self) -> OfflineStream:  # CreateOfflineStream :71-75
         return OfflineStream(self.model)

@@ -949,6 +949,18 @@ int32_t k2hip_ctc_prefix_beam_search(k2hip_model_t* model, const float* log_prob
         e.ctc_prefix_host(log_probs, R, Tprime, n_frames, beam, nbest, tokens, timestamps, token_log_probs, n_tokens, n_hyps, scores, max_tokens);
     });
 }
+// the opt-in of the offline prefix search's hotword / n-gram LM biasing (off: the tables on the model are ignored by that search)
+int32_t k2hip_set_ctc_prefix_biasing(k2hip_model_t* model, int32_t on) {
+    return guard([&] {
+        NEED(model);
+        Engine& e = model->engine;
+        if (!e.model().cfg().ctc)
+            failf(K2HIP_ERR_UNSUPPORTED, "set_ctc_prefix_biasing: model_type '%s' has no CTC head", e.model().cfg().model_type.c_str());
+        EngineLock lk(e);
+        K2_REQUIRE(e.batches_in_flight() == 0, "set_ctc_prefix_biasing: %d submitted batches are in flight; wait for them first", e.batches_in_flight());
+        e.set_ctc_prefix_biasing(on != 0);
+    });
+}
 // forced alignment / full-sum scoring: the engine checks the targets on the host before any device work (lattice_ref.h)
 int32_t k2hip_transducer_align(k2hip_model_t* model, const float* enc_out, int32_t B, int32_t Tprime, const int32_t* n_frames,
                                const int64_t* ids, const int32_t* lens, int32_t* timestamps, float* token_log_probs, float* total_logp,

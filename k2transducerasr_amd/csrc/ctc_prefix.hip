@@ -26,10 +26,22 @@
 //                  step; where one reaches its root a while the other is d tokens above its root b, the answer is rel[a][b] == d with
 //                  relx equal to those tokens; a carried slot with nothing appended is the case S_a = S_b + s_k + [e_a]), and the
 //                  survivors go to the out block as (origin, appended tokens / frames / log-probs, pb, pnb, hashes).
-// No workgroup waits for another; every loop is bounded by T, beam or a hypothesis length; all stores are ordinary vector stores.
+//   k_ctc_prefix<false, true>  the offline search with hotword and n-gram LM biasing (semantics: include/k2hip.h "Hotword and n-gram
+//                  LM biasing of the CTC prefix beam search"; host reference: ctc_prefix_bias_ref.h).  The same source again; what the
+//                  instantiation adds: three more words per slot and parity in LDS (hs, ls, ctx), the slots' hs / ctx in registers
+//                  beside pb / tot in the column loop and ONE coalesced bonus[hs_k V + v] load per live slot and column, so that a
+//                  candidate's KEY is its acoustic total plus ctx (plus the bonus of the extension); pb / pnb / tot stay acoustic, the
+//                  slot-building thread forms them again from the same operands.  Behind the second-level selection every wave knows
+//                  all winners: wave w takes the LM walks (lm_walk.h, a wave per walk) of winners 2 w and 2 w + 1, term and next state
+//                  go through LDS -- one more barrier per frame -- to the thread that builds the slot, which loads next[hs_k V + v]
+//                  itself.  After the last frame final = (tot + ctx) - pending[hs] and the entries' order are formed in LDS before the
+//                  chains are written.  Null hotword tables / null LM tables: that half adds nothing (a null check).
+// No workgroup waits for another; every loop is bounded by T, beam, a hypothesis length, K2HIP_NGRAM_MAX_ORDER - 1 levels or the walk's
+// 64-ary narrowing; all stores are ordinary vector stores.
 #include <climits>
 
 #include "kernels.h"
+#include "lm_walk.h"
 #include "wave_best.h"
 
 namespace k2hip {
@@ -53,6 +65,19 @@ struct Slots {
     int e[KB], len[KB], node[KB], pnode[KB];   // last token (-1: the empty prefix), length, history node and its parent (-1: none)
     unsigned long long hash[KB], phash[KB];    // rolling hash of the prefix / of the prefix without its last token
     int n;
+};
+// what the biased instantiation keeps beside them (empty otherwise: no LDS)
+template <bool BIAS>
+struct BiasLds {};
+template <>
+struct BiasLds<true> {
+    float ctx[2][KB];               // accumulated context score of the slots, per frame parity
+    int hs[2][KB], ls[2][KB];       // hotword graph state, LM state
+    float stay_tot[KB];             // the stay candidates' acoustic totals (the selection carries keys)
+    float term[KB];                 // the selected candidates' LM terms and next LM states, by rank
+    int lnext[KB];
+    float fin[KB];                  // after the last frame: final scores by slot, slots by final rank
+    int ord[KB];
 };
 constexpr unsigned long long kHashSeed = kCtcPrefixHashSeed, kHashMul = kCtcPrefixHashMul;
 
@@ -80,9 +105,11 @@ __device__ __forceinline__ bool fold_through_boundary(int p, int q, int jn, cons
     return true;
 }
 
-template <bool RESUME, typename Args>
+template <bool RESUME, bool BIAS, typename Args>
 __global__ __launch_bounds__(PT) void k_ctc_prefix(Args a) {
+    static_assert(!(RESUME && BIAS), "the carried search is unbiased");
     __shared__ Slots sl[2];
+    [[maybe_unused]] __shared__ BiasLds<BIAS> bl;
     __shared__ float stay_pb[KB], stay_pnb[KB];
     __shared__ int fold_par[KB];   // slot j -> the slot k whose extension by e_j spells j, or -1
     __shared__ float wl_v[PW][KB];
@@ -142,6 +169,7 @@ __global__ __launch_bounds__(PT) void k_ctc_prefix(Args a) {
         s.hash[0] = kHashSeed; s.phash[0] = 0;
         s.n = 1;
         fold_par[0] = -1;
+        if constexpr (BIAS) { bl.ctx[0][0] = 0.f; bl.hs[0][0] = 0; bl.ls[0][0] = a.lm.start; }
     }
     float px = T > 0 && tid < V ? lp[tid] : ninf();
     __syncthreads();
@@ -158,9 +186,15 @@ __global__ __launch_bounds__(PT) void k_ctc_prefix(Args a) {
         const int n = c.n;
         float s_pb[KB], s_tot[KB];
         int s_e[KB], s_fp[KB];
+        [[maybe_unused]] float s_ctx[KB];
+        [[maybe_unused]] int s_hs[KB];
 #pragma unroll
         for (int k = 0; k < KB; k++) {
             const bool live = k < n;
+            if constexpr (BIAS) {
+                s_ctx[k] = live ? bl.ctx[t & 1][k] : 0.f;
+                s_hs[k] = live ? bl.hs[t & 1][k] : 0;
+            }
             s_pb[k] = live ? c.pb[k] : ninf();
             s_tot[k] = live ? c.tot[k] : ninf();
             s_e[k] = live ? c.e[k] : -1;
@@ -190,7 +224,10 @@ __global__ __launch_bounds__(PT) void k_ctc_prefix(Args a) {
             const float st = logaddexp_f(spb, spnb);
             stay_pb[k] = spb;
             stay_pnb[k] = spnb;
-            if (st > ninf()) insert(st, k * V);
+            if constexpr (BIAS) {
+                bl.stay_tot[k] = st;
+                if (st > ninf()) insert(st + bl.ctx[t & 1][k], k * V);
+            } else if (st > ninf()) insert(st, k * V);
         }
         for (int v0 = 0; v0 < V; v0 += PT) {
             const int v = v0 + tid;
@@ -203,7 +240,13 @@ __global__ __launch_bounds__(PT) void k_ctc_prefix(Args a) {
 #pragma unroll
                 for (int k = 0; k < KB; k++) {
                     const float x = (v == s_e[k] ? s_pb[k] : s_tot[k]) + xl;
-                    if (k < n && !(kill >> k & 1u) && x > ninf()) insert(x, k * V + v);
+                    if constexpr (BIAS) {   // the key: acoustic total + (ctx + bonus); dropped on the acoustic total
+                        if (k < n && !(kill >> k & 1u) && x > ninf()) {
+                            float cb = s_ctx[k];
+                            if (a.hw.bonus) cb += a.hw.bonus[(long long)s_hs[k] * V + v];
+                            insert(x + cb, k * V + v);
+                        }
+                    } else if (k < n && !(kill >> k & 1u) && x > ninf()) insert(x, k * V + v);
                 }
             }
         }
@@ -231,6 +274,7 @@ __global__ __launch_bounds__(PT) void k_ctc_prefix(Args a) {
         }
         float win_v = ninf();
         int win_i = -1, m = 0;
+        [[maybe_unused]] int walk_i[2] = {-1, -1};   // BIAS: the winners 2 wave, 2 wave + 1, whose LM walks this wave takes
 #pragma unroll
         for (int q = 0; q < KB; q++)
             if (q < beam) {
@@ -240,9 +284,25 @@ __global__ __launch_bounds__(PT) void k_ctc_prefix(Args a) {
                 if (bi >= 0) {
                     if (mi == bi) mi = -1;
                     if (tid == q) { win_v = bv; win_i = bi; }
+                    if constexpr (BIAS)
+                        if ((q >> 1) == wave) walk_i[q & 1] = bi;
                     m++;
                 }
             }
+        if constexpr (BIAS) {   // (wave-uniform throughout: every lane holds the same winners)
+#pragma unroll
+            for (int j = 0; j < 2; j++) {
+                const int i = walk_i[j];
+                if (i >= 0) {
+                    const int k = i / V, v = i - k * V;
+                    float term = 0.f;
+                    int ls = bl.ls[t & 1][k];
+                    if (v != 0 && v != K2HIP_UNK_ID && a.lm.states) beam_lm_walk(a.lm, ls, v, lane, &term, &ls);
+                    if (lane == 0) { bl.term[2 * wave + j] = term; bl.lnext[2 * wave + j] = ls; }
+                }
+            }
+            __syncthreads();
+        }
         // thread q builds slot q of the other parity (no finite candidate: slot 0 stays, its scores -inf from then on)
         if (tid < max(m, 1)) {
             int k = 0, v = 0;
@@ -253,6 +313,24 @@ __global__ __launch_bounds__(PT) void k_ctc_prefix(Args a) {
                 tot = win_v;
                 pb = v ? ninf() : stay_pb[k];
                 pnb = v ? win_v : stay_pnb[k];
+                if constexpr (BIAS) {   // win_v is the key: the acoustic values again, from the same operands
+                    tot = v ? (v == c.e[k] ? c.pb[k] : c.tot[k]) + row[v] : bl.stay_tot[k];
+                    if (v) pnb = tot;
+                }
+            }
+            if constexpr (BIAS) {
+                const int par = t & 1;
+                float ctx = bl.ctx[par][k];
+                int hs = bl.hs[par][k], ls = bl.ls[par][k];
+                if (m > 0 && v) {
+                    if (a.hw.bonus) {
+                        ctx += a.hw.bonus[(long long)hs * V + v];
+                        hs = a.hw.next[(long long)hs * V + v];
+                    }
+                    ctx = ctx + bl.term[tid];
+                    ls = bl.lnext[tid];
+                }
+                bl.ctx[par ^ 1][tid] = ctx; bl.hs[par ^ 1][tid] = hs; bl.ls[par ^ 1][tid] = ls;
             }
             nx.pb[tid] = pb; nx.pnb[tid] = pnb; nx.tot[tid] = tot;
             if (v == 0) {
@@ -300,6 +378,27 @@ __global__ __launch_bounds__(PT) void k_ctc_prefix(Args a) {
             }
         }
     } else {
+        if constexpr (BIAS) {   // final = (tot + ctx) - pending[hs]; the entries by (final desc, slot asc)
+            if (tid < n) {
+                const float fv = f.tot[tid] + bl.ctx[T & 1][tid];
+                bl.fin[tid] = a.hw.pending ? fv - a.hw.pending[bl.hs[T & 1][tid]] : fv;
+            }
+            __syncthreads();
+            if (tid < n) {
+                int rank = 0;
+                for (int j = 0; j < n; j++) rank += bl.fin[j] > bl.fin[tid] || (bl.fin[j] == bl.fin[tid] && j < tid);
+                bl.ord[rank] = tid;
+            }
+            __syncthreads();
+        }
+        auto slot_of = [&](int i) {
+            if constexpr (BIAS) return bl.ord[i];
+            else return i;
+        };
+        auto score_of = [&](int q) {
+            if constexpr (BIAS) return bl.fin[q];
+            else return f.tot[q];
+        };
         // a slot's chain walked back into a row, from index len - 1 down
         auto write_chain = [&](int q, long long* tok, int* ts, float* yp, long long o) {
             int node = f.node[q];
@@ -311,21 +410,23 @@ __global__ __launch_bounds__(PT) void k_ctc_prefix(Args a) {
                 node = nd.x;
             }
         };
-        if (tid == 64) {   // the single result: slot 0
-            const int len = f.len[0];
+        if (tid == 64) {   // the single result: slot 0 (BIAS: the first in final order)
+            const int s0 = slot_of(0);
+            const int len = f.len[s0];
             if (len > a.max_tokens) {
                 *a.overflow = 1;
                 a.n_tokens[r] = 0;
             } else {
-                write_chain(0, a.tokens, a.timestamps, nullptr, (long long)r * a.max_tokens);
+                write_chain(s0, a.tokens, a.timestamps, nullptr, (long long)r * a.max_tokens);
                 a.n_tokens[r] = len;
             }
-            if (a.scores) a.scores[r] = f.tot[0];
+            if (a.scores) a.scores[r] = score_of(s0);
         }
         if (a.nb.tokens && tid < KB) {
-            const int nh = min(n, a.nb.nbest), q = tid;
-            if (q < nh) {
-                const long long en = (long long)r * a.nb.nbest + q;
+            const int nh = min(n, a.nb.nbest);
+            if (tid < nh) {
+                const int q = slot_of(tid);
+                const long long en = (long long)r * a.nb.nbest + tid;
                 const int len = f.len[q];
                 if (len > a.max_tokens) {   // (the single result's rule, per entry)
                     *a.overflow = 1;
@@ -334,7 +435,7 @@ __global__ __launch_bounds__(PT) void k_ctc_prefix(Args a) {
                     write_chain(q, a.nb.tokens, a.nb.timestamps, a.nb.token_log_probs, en * a.max_tokens);
                     a.nb.n_tokens[en] = len;
                 }
-                a.nb.scores[en] = f.tot[q];
+                a.nb.scores[en] = score_of(q);
             }
             if (tid == 0) a.nb.n_hyps[r] = nh;
         }
@@ -348,7 +449,18 @@ void ctc_prefix_search(const Ctx& ctx, const CtcPrefixArgs& a) {
     K2_REQUIRE(a.R >= 1 && a.R <= 65535 && a.Tp >= 1 && a.V >= 1 && (long long)kMaxBeam * a.V <= INT_MAX && a.beam >= 1 && a.beam <= kMaxBeam &&
                    a.max_tokens >= 1 && (!a.nb.tokens || (a.nb.nbest >= 1 && a.nb.nbest <= a.beam)),
                "ctc_prefix_search: bad shape R=%d T'=%d V=%d beam=%d nbest=%d max_tokens=%d", a.R, a.Tp, a.V, a.beam, a.nb.nbest, a.max_tokens);
-    hipLaunchKernelGGL((k_ctc_prefix<false, CtcPrefixArgs>), dim3(a.R), dim3(PT), 0, ctx.stream, a);
+    hipLaunchKernelGGL((k_ctc_prefix<false, false, CtcPrefixArgs>), dim3(a.R), dim3(PT), 0, ctx.stream, a);
+    K2_HIP(hipGetLastError());
+}
+
+void ctc_prefix_search_biased(const Ctx& ctx, const CtcPrefixBiasArgs& a) {
+    if (ctx.dry) return;
+    K2_REQUIRE(a.R >= 1 && a.R <= 65535 && a.Tp >= 1 && a.V >= 1 && (long long)kMaxBeam * a.V <= INT_MAX && a.beam >= 1 && a.beam <= kMaxBeam &&
+                   a.max_tokens >= 1 && (!a.nb.tokens || (a.nb.nbest >= 1 && a.nb.nbest <= a.beam)),
+               "ctc_prefix_search_biased: bad shape R=%d T'=%d V=%d beam=%d nbest=%d max_tokens=%d", a.R, a.Tp, a.V, a.beam, a.nb.nbest, a.max_tokens);
+    K2_REQUIRE(!a.hw.next == !a.hw.bonus && !a.hw.next == !a.hw.pending, "ctc_prefix_search_biased: incomplete hotword tables");
+    K2_REQUIRE(!a.lm.states || (a.lm.uni_lp && a.lm.uni_next && a.lm.start >= 0), "ctc_prefix_search_biased: incomplete LM tables");   // (no arcs at all: null arc arrays)
+    hipLaunchKernelGGL((k_ctc_prefix<false, true, CtcPrefixBiasArgs>), dim3(a.R), dim3(PT), 0, ctx.stream, a);
     K2_HIP(hipGetLastError());
 }
 
@@ -357,7 +469,7 @@ void ctc_prefix_resume(const Ctx& ctx, const CtcPrefixResumeArgs& a) {
     K2_REQUIRE(a.B >= 1 && a.B <= 65535 && a.Tc >= 1 && a.V >= 1 && (long long)kMaxBeam * a.V <= INT_MAX && a.beam >= 1 && a.beam <= kMaxBeam &&
                    (long long)a.Tc * a.beam <= INT_MAX / 2 && a.in && a.out && a.nodes && a.status,
                "ctc_prefix_resume: bad shape B=%d Tc=%d V=%d beam=%d", a.B, a.Tc, a.V, a.beam);
-    hipLaunchKernelGGL((k_ctc_prefix<true, CtcPrefixResumeArgs>), dim3(a.B), dim3(PT), 0, ctx.stream, a);
+    hipLaunchKernelGGL((k_ctc_prefix<true, false, CtcPrefixResumeArgs>), dim3(a.B), dim3(PT), 0, ctx.stream, a);
     K2_HIP(hipGetLastError());
 }
 

@@ -4,7 +4,10 @@
 #include "engine.h"
 #include "lattice_ref.h"
 #include "ctc_lattice_ref.h"
+#include "ctc_prefix_bias_ref.h"
 #include "ctc_prefix_ref.h"
+#include "hotwords.h"
+#include "ngram_lm.h"
 
 #include <climits>
 #include <cmath>
@@ -772,9 +775,20 @@ Engine::SearchExtras Engine::ctc_prefix_device(const Ctx& c, const float* logp, 
         a.nb = ex.nb;
     }
     if (!c.dry) K2_HIP(hipMemsetAsync(out.flag(), 0, sizeof(int), c.stream));
-    ctc_prefix_search(c, a);
+    if (ctc_prefix_biasing_ && (hw_next_ || lm_.states)) {   // (the tables were built for the model's V, which is every caller's V here)
+        K2_REQUIRE(V == model_->cfg().V, "internal: the biased prefix search runs over the model's vocabulary");
+        CtcPrefixBiasArgs b;
+        static_cast<CtcPrefixArgs&>(b) = a;
+        b.hw = BeamHwStream{hw_next_, hw_bonus_, hw_pending_};
+        b.lm = lm_;
+        ctc_prefix_search_biased(c, b);
+    } else {
+        ctc_prefix_search(c, a);
+    }
     return ex;
 }
+
+void Engine::set_ctc_prefix_biasing(bool on) { ctc_prefix_biasing_ = on; }
 
 void Engine::ctc_prefix_host(const float* log_probs, int R, int Tp, const int32_t* n_frames, int beam, int nbest, int64_t* tokens, int32_t* timestamps,
                              float* token_log_probs, int32_t* n_tokens, int32_t* n_hyps, float* scores, int max_tokens) {
@@ -2403,6 +2417,73 @@ void Engine::debug_op_host(const char* op, const int64_t* iargs, int n_iargs, vo
                 a.tokens = out.tokens(); a.timestamps = out.timestamps(); a.n_tokens = out.counts(); a.max_tokens = max_tokens; a.overflow = out.flag();
                 if (!cc.dry) K2_HIP(hipMemsetAsync(out.flag(), 0, sizeof(int), cc.stream));
                 ctc_prefix_search(cc, a);
+            });
+            K2_HIP(hipStreamSynchronize(stream_));
+            K2_HIP(copy_blocking(dev[8], out.flag(), 4, hipMemcpyDeviceToDevice));
+        } else if (name == "ctc_prefix_beam_bias") {
+            // the buffers of "ctc_prefix_beam" [0..8], then caller-supplied tables: next [S][V] int32, bonus [S][V], pending [S] (all three
+            //   or none), LM states [S_lm][4] int32, arc_tok / arc_lp / arc_next [A], uni_lp / uni_next [V] (all or none; the arc buffers may
+            //   be null when A = 0); ints R, Tp, V, beam, nbest, max_tokens, S, S_lm, A, start.  Everything the kernel indexes with is
+            //   checked on the host first (ctc_prefix_bias_ref.h).
+            K2_REQUIRE(n_bufs == 18, "debug_op_run %s: %d buffers", op, n_bufs);
+            for (int k = 0; k < n_bufs; k++) P();
+            const int R = I(), Tp = I(), V = I(), beam = I(), nbest = I(), max_tokens = I(), S = I(), S_lm = I();
+            const long long A = L();
+            const int start = I();
+            K2_REQUIRE(!bufs[1] || buf_bytes[1] >= 4 * (int64_t)R, "debug_op_run %s: n_frames is too short", op);
+            ctc_prefix_check_args(R, Tp, V, static_cast<const int32_t*>(bufs[1]), beam, nbest, max_tokens);
+            const int64_t NB = (int64_t)R * nbest;
+            K2_REQUIRE(dev[0] && buf_bytes[0] >= 4 * (int64_t)R * Tp * V, "debug_op_run %s: log_probs is too short", op);
+            K2_REQUIRE(dev[2] && dev[3] && dev[4] && dev[5] && dev[6] && dev[7] && dev[8] && buf_bytes[2] >= 8 * NB * max_tokens &&
+                           buf_bytes[3] >= 4 * NB * max_tokens && buf_bytes[4] >= 4 * NB * max_tokens && buf_bytes[5] >= 4 * NB && buf_bytes[6] >= 4 * (int64_t)R &&
+                           buf_bytes[7] >= 4 * NB && buf_bytes[8] >= 4,
+                       "debug_op_run %s: the result buffers are too short", op);
+            CtcPrefixBiasTables tb;
+            tb.V = V;
+            if (bufs[9] || bufs[10] || bufs[11]) {
+                K2_REQUIRE(S >= 1 && (int64_t)S * V <= kHotwordMaxEntries && bufs[9] && bufs[10] && bufs[11] && buf_bytes[9] >= 4 * (int64_t)S * V &&
+                               buf_bytes[10] >= 4 * (int64_t)S * V && buf_bytes[11] >= 4 * (int64_t)S,
+                           "debug_op_run %s: the hotword tables are incomplete or too short for S = %d", op, S);
+                tb.S = S;
+                tb.next = static_cast<const int32_t*>(bufs[9]); tb.bonus = static_cast<const float*>(bufs[10]); tb.pending = static_cast<const float*>(bufs[11]);
+            }
+            if (bufs[12] || bufs[16] || bufs[17]) {
+                K2_REQUIRE(S_lm >= 1 && A >= 0 && A <= kNgramMaxArcs && bufs[12] && bufs[16] && bufs[17] && buf_bytes[12] >= 16 * (int64_t)S_lm &&
+                               buf_bytes[16] >= 4 * (int64_t)V && buf_bytes[17] >= 4 * (int64_t)V &&
+                               (A == 0 || (bufs[13] && bufs[14] && bufs[15] && buf_bytes[13] >= 4 * A && buf_bytes[14] >= 4 * A && buf_bytes[15] >= 4 * A)),
+                           "debug_op_run %s: the LM tables are incomplete or too short for S = %d, A = %lld", op, S_lm, A);
+                tb.S_lm = S_lm; tb.A = A; tb.start = start;
+                tb.states = static_cast<const int32_t*>(bufs[12]);
+                tb.arc_tok = static_cast<const int32_t*>(bufs[13]); tb.arc_lp = static_cast<const float*>(bufs[14]); tb.arc_next = static_cast<const int32_t*>(bufs[15]);
+                tb.uni_lp = static_cast<const float*>(bufs[16]); tb.uni_next = static_cast<const int32_t*>(bufs[17]);
+            }
+            try {
+                ctc_prefix_bias_check_tables(tb);
+            } catch (const Error& e) {   // (the caller's tables, not a shape the launcher refuses: INVALID)
+                failf(K2HIP_ERR_INVALID, "debug_op_run %s: %s", op, e.what());
+            }
+            CtcPrefixBiasArgs a;
+            a.log_probs = static_cast<const float*>(dev[0]); a.R = R; a.Tp = Tp; a.V = V; a.beam = beam;
+            a.n_frames = static_cast<const int*>(dev[1]);
+            a.nb.nbest = nbest;
+            a.nb.tokens = static_cast<long long*>(dev[2]); a.nb.timestamps = static_cast<int*>(dev[3]);
+            a.nb.token_log_probs = static_cast<float*>(dev[4]); a.nb.n_tokens = static_cast<int*>(dev[5]);
+            a.nb.n_hyps = static_cast<int*>(dev[6]); a.nb.scores = static_cast<float*>(dev[7]);
+            if (tb.next) a.hw = BeamHwStream{static_cast<const int*>(dev[9]), static_cast<const float*>(dev[10]), static_cast<const float*>(dev[11])};
+            if (tb.states) {
+                a.lm.states = static_cast<const int4*>(dev[12]);
+                a.lm.arc_tok = static_cast<const int*>(dev[13]); a.lm.arc_lp = static_cast<const float*>(dev[14]); a.lm.arc_next = static_cast<const int*>(dev[15]);
+                a.lm.uni_lp = static_cast<const float*>(dev[16]); a.lm.uni_next = static_cast<const int*>(dev[17]);
+                a.lm.start = start;
+            }
+            SearchOut out;
+            run_sized([&](const Ctx& cc) {
+                out = SearchOut(*cc.arena, R, max_tokens);
+                a.nodes = cc.arena->take<int4>((int64_t)R * Tp * beam);
+                a.scores = cc.arena->take<float>(R);
+                a.tokens = out.tokens(); a.timestamps = out.timestamps(); a.n_tokens = out.counts(); a.max_tokens = max_tokens; a.overflow = out.flag();
+                if (!cc.dry) K2_HIP(hipMemsetAsync(out.flag(), 0, sizeof(int), cc.stream));
+                ctc_prefix_search_biased(cc, a);
             });
             K2_HIP(hipStreamSynchronize(stream_));
             K2_HIP(copy_blocking(dev[8], out.flag(), 4, hipMemcpyDeviceToDevice));

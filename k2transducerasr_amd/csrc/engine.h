@@ -108,6 +108,11 @@ class Engine {
     // launch, one download; the arguments are checked on the host before any device work.
     void ctc_prefix_chunk_host(const float* log_probs, int B, int Tc, const int32_t* n_frames, int K, const int* in, int* out);
     void set_ctc_prefix(int k) { ctc_prefix_ = k; }
+    // Hotword and n-gram LM biasing of the OFFLINE prefix search (k2hip_set_ctc_prefix_biasing; off by default).  On: ctc_prefix_device
+    // runs the biased instantiation over the tables of set_hotword_tables / set_ngram_tables when at least one is set; off, or with
+    // neither set: the plain instantiation, bit for bit what it always gave.  The carried streaming search never looks at it.
+    void set_ctc_prefix_biasing(bool on);
+    bool ctc_prefix_biasing() const { return ctc_prefix_biasing_; }
     int ctc_prefix() const { return ctc_prefix_; }
     // ---- fused paths ----
     void offline_greedy_feats(const float* const* feats, const int64_t* n_floats, int B, bool single, int64_t* tokens,
@@ -452,6 +457,7 @@ class Engine {
     bool instrument_ = false;
     int beam_ = 0;
     int ctc_prefix_ = 0;
+    bool ctc_prefix_biasing_ = false;
     int nbest_ = 0;
     float *yp_host_ = nullptr, *d_yp_ = nullptr;
     size_t yp_floats_ = 0;

@@ -749,6 +749,14 @@ struct CtcPrefixArgs {
 };
 // One workgroup of 256 per row, frames sequential, no workgroup waits for another; every store is an ordinary vector store
 void ctc_prefix_search(const Ctx& ctx, const CtcPrefixArgs& a);
+// The same search with hotword and n-gram LM biasing (include/k2hip.h "Hotword and n-gram LM biasing of the CTC prefix beam search"): the
+// dense hotword tables [S][V] / [S] and the scaled sparse LM as the modified beam search reads them.  All of hw null / lm.states null:
+// that half adds nothing.  The caller has checked that every state the tables name is inside them (ctc_prefix_bias_ref.h).
+struct CtcPrefixBiasArgs : CtcPrefixArgs {
+    BeamHwStream hw;
+    BeamLm lm;
+};
+void ctc_prefix_search_biased(const Ctx& ctx, const CtcPrefixBiasArgs& a);
 // The search resumed from the live prefixes of the chunks before (streaming: one chunk of <= Tc frames per call).  Carried slot a is
 // the prefix S_a, whose tokens only the host keeps (ctc_prefix_hist.h); inside the chunk a prefix is (carried slot, suffix of <= Tc
 // tokens).  rel[a][b] = |x| when S_a = S_b + x with 0 < |x| <= Tc (x = relx[a][b]), else -1 (0 on the diagonal), as BeamResumeLayout.
