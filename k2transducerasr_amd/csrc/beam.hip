@@ -942,7 +942,8 @@ void beam_search(const Ctx& ctx, const DecJoinW& w, const BeamArgs& a) {
     K2_REQUIRE(!a.hw_streams || (a.rin && a.st_in && a.st_out), "beam search: per-stream hotword graphs belong to the resumed search and need its state blocks");
     K2_REQUIRE(!(a.hw_next && a.rin), "beam search: the resumed search takes its hotword graphs per stream");
     // token log-probs / N-best: the offline search writes nb (which needs them), the resumed one the side block yp_out
-    const bool yp = a.nb.tokens != nullptr || a.yp_out != nullptr;
+    // (keep_yp: the sizing pass sees null pointers for both)
+    const bool yp = a.keep_yp || a.nb.tokens != nullptr || a.yp_out != nullptr;
     K2_REQUIRE(!a.nb.tokens || (!a.rin && a.nb.nbest >= 1 && a.nb.nbest <= kMaxBeam && a.nb.timestamps && a.nb.token_log_probs && a.nb.n_tokens &&
                                 a.nb.scores && a.nb.n_hyps),
                "beam search: incomplete N-best outputs (nbest %d, range [1,%d])", a.nb.nbest, kMaxBeam);

@@ -891,6 +891,7 @@ Engine::SearchExtras Engine::beam_device(const Ctx& c, const float* enc, int B, 
         ex.nb.scores = c.arena->take<float>(NB);
         ex.nb.n_hyps = c.arena->take<int>(B);
         a.nb = ex.nb;
+        a.keep_yp = true;
     }
     if (tunables().beam_trace) {
         ex.trace = c.arena->take<int>((int64_t)B * Tp * (2 * beam_ + 1));
@@ -924,6 +925,7 @@ void Engine::beam_resume_device(const Ctx& c, const float* enc, int B, int Tp, i
         yp_floats_ = (size_t)B * K * Tp;
         d_yp_ = c.arena->take<float>((int64_t)yp_floats_);
         a.yp_out = d_yp_;
+        a.keep_yp = true;
     }
     beam_search(c, decjoin(), a);
 }

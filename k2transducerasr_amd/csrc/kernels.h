@@ -663,6 +663,9 @@ struct BeamArgs {
     // survivor's suffix, a side block beside rout as st_out is.
     BeamNbest nb;
     float* yp_out = nullptr;
+    // Set with either of them.  The sizing pass (Ctx::dry) hands out null pointers, so nb.tokens / yp_out cannot tell it that the
+    // search will keep token log-probs: without this flag it sized the arena without the [2][B][K][cap] array beside ys / ts.
+    bool keep_yp = false;
 };
 // launches of the search since the process started, by instantiation: [0] HW = false, [1] HW = true (k2hip_debug.h)
 void beam_launch_counts(long long* plain, long long* hw);

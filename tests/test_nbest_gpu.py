@@ -7,7 +7,8 @@ the error of the log-sum-exp).  A stream may be excused from the ORDER check onl
 normalised scores is below parity.LOGIT_TOL (its alternatives must then still match as a set).  The committed cases DO have such gaps
 (with up to 8 alternatives over 35 frames nearly every list has two entries closer than 1e-3; the smallest is 1.0e-4, a hundred
 times float32's rounding of these sums), so the excuse is available to them -- and every test asserts that it was not used: zero
-excused streams.
+excused streams.  (The order on EXACT ties -- planted duplicates, tied hypotheses, tied final scores, with no excuse available -- is
+held by tests/test_beam_ties_gpu.py on the cases of tests/beam_cases.py.)
 
 The fused streaming step scores the DEVICE encoder's frames, not the oracle's: its token log-probs are held to the same 2e-4
 (measured 2.4e-6), its scores -- sums over every frame so far -- to the relative bound tests/test_online_beam_gpu.py already uses for
