@@ -8,6 +8,10 @@
 // through the ABI: beam, nbest, n_frames and R out of range, max_tokens too small (nothing written), NULL arguments, a transducer
 // model, the method / N-best rules of a CTC handle, and a valid call after every refused one.
 //   san_ctc_prefix_driver <ctc.k2w> <offline.k2w>
+//   san_ctc_prefix_driver row <file>      one row through ctc_prefix_ref.h, printed for tests/test_ctc_prefix_tie_cases_ref.py: the file
+//                                         holds the text line "V T beam" and then T x V raw float32 values.  Per frame a line
+//                                         "picks t i0 i1 ..." (the selected flat indexes in rank order), per surviving hypothesis a line
+//                                         "hyp i score-bits n tok0 .. | ts0 .. | token-log-prob-bits0 .." (bits as unsigned decimals)
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -258,9 +262,66 @@ void abi(const char* ctc_path, const char* transducer_path) {
     OK(k2hip_model_destroy(tr));
 }
 
+unsigned bits_of(float x) {
+    unsigned u;
+    memcpy(&u, &x, sizeof u);
+    return u;
+}
+
+// the whole-row search stepped frame by frame (the fold table of ctc_prefix_ref: token lists compared), so that every frame's picks show:
+// a new slot's flat index is (the slot it came from) V + (the token it appended, 0 for a stay); the result must be ctc_prefix_ref's
+int row_from_file(const char* path) {
+    FILE* f = fopen(path, "rb");
+    CHECK(f != nullptr);
+    int V = 0, T = 0, beam = 0;
+    CHECK(fscanf(f, "%d %d %d", &V, &T, &beam) == 3 && fgetc(f) == '\n');
+    CHECK(V >= 1 && V <= 100000 && T >= 1 && T <= 100000 && beam >= 1 && beam <= 64);
+    std::vector<float> lp((size_t)T * (size_t)V);
+    CHECK(fread(lp.data(), sizeof(float), lp.size(), f) == lp.size());
+    fclose(f);
+    std::vector<k2hip::CtcPrefixRefSlot> cur(1);
+    cur[0].h.pb = 0.f; cur[0].h.pnb = -INFINITY; cur[0].h.tot = 0.f;
+    long long next_node = 0;
+    for (int t = 0; t < T; t++) {
+        const int n = (int)cur.size();
+        std::vector<int> fold_par((size_t)n, -1);
+        for (int j = 0; j < n; j++) {
+            cur[(size_t)j].origin = j;
+            for (int k = 0; k < n; k++) {
+                const auto &tj = cur[(size_t)j].h.tokens, &tk = cur[(size_t)k].h.tokens;
+                if (j != k && tj.size() == tk.size() + 1 && std::equal(tk.begin(), tk.end(), tj.begin())) fold_par[(size_t)j] = k;
+            }
+        }
+        std::vector<k2hip::CtcPrefixRefSlot> nxt = k2hip::ctc_prefix_ref_frame(cur, fold_par, lp.data() + (size_t)t * (size_t)V, t, V, beam, &next_node);
+        printf("picks %d", t);
+        for (const auto& s : nxt) {
+            const bool grew = s.h.tokens.size() > cur[(size_t)s.origin].h.tokens.size();
+            printf(" %lld", (long long)s.origin * V + (grew ? (long long)s.h.tokens.back() : 0));
+        }
+        printf("\n");
+        cur = std::move(nxt);
+    }
+    const CtcPrefixRefResult r = ctc_prefix_ref(lp.data(), V, T, V, beam);
+    CHECK(r.hyps.size() == cur.size());
+    for (size_t i = 0; i < r.hyps.size(); i++) {
+        const auto& h = r.hyps[i];
+        CHECK(h.tokens == cur[i].h.tokens && h.timestamps == cur[i].h.timestamps && bits_of(h.tot) == bits_of(cur[i].h.tot));
+        printf("hyp %zu %u %zu", i, bits_of(h.tot), h.tokens.size());
+        for (int64_t v : h.tokens) printf(" %lld", (long long)v);
+        printf(" |");
+        for (int32_t x : h.timestamps) printf(" %d", x);
+        printf(" |");
+        for (float x : h.token_log_probs) printf(" %u", bits_of(x));
+        printf("\n");
+    }
+    printf("san_ctc_prefix_driver row ok\n");
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
+    if (argc == 3 && strcmp(argv[1], "row") == 0) return row_from_file(argv[2]);
     for (int T = 1; T <= 6; T++)
         for (int inf : {0, 0, 0, 2, 6, 16}) brute_case(T, inf);
     rules();
