@@ -378,7 +378,8 @@ int32_t k2hip_set_hotwords(k2hip_model_t* model, const k2hip_hotwords_t* hw);
  * step to step more often than without a graph: re-read them after every step (n_new_tokens is a signed change).
  * One call may mix streams with different graphs and streams with none; a call in which no stream has a graph is exactly the
  * unbiased call.  An empty graph or score_per_token = 0: bit for bit the unbiased results.  Streaming greedy search and a CTC model's
- * search ignore an attached graph. */
+ * search ignore an attached graph -- unless the CTC stream opts in with k2hip_online_stream_set_ctc_prefix_biasing (below, "Biasing of
+ * the streaming CTC prefix beam search"). */
 int32_t k2hip_online_stream_set_hotwords(k2hip_online_stream_t* s, const k2hip_hotwords_t* hw);
 int32_t k2hip_beam_stream_set_hotwords(k2hip_beam_stream_t* s, const k2hip_hotwords_t* hw);
 
@@ -615,7 +616,8 @@ int32_t k2hip_ctc_prefix_beam_search(k2hip_model_t* model, const float* log_prob
  * (k2hip_offline_greedy*, k2hip_offline_recognizer_get_results, submit / wait) use the model's hotword and LM tables; with neither
  * set the plain search runs.  K2HIP_ERR_UNSUPPORTED for a transducer model; K2HIP_ERR_INVALID with batches in flight, as for
  * k2hip_set_hotwords.  Unaffected either way: k2hip_online_step, k2hip_ctc_prefix_beam_search_chunk (the carried streaming search
- * stays unbiased), the collapse, k2hip_ctc_align. */
+ * never reads this switch nor the model-level hotword list; it has a per-stream switch of its own, below), the collapse,
+ * k2hip_ctc_align. */
 int32_t k2hip_set_ctc_prefix_biasing(k2hip_model_t* model, int32_t on);
 /* ---- streaming CTC prefix beam search: prefixes carried across chunks (operator level) ------------------------------------------
  * A k2hip_ctc_prefix_stream_t is one stream's live prefixes (host memory; no device slot), shaped like k2hip_beam_stream_t.
@@ -661,6 +663,44 @@ int32_t k2hip_ctc_prefix_stream_get_alternative(const k2hip_ctc_prefix_stream_t*
  * _get_token_log_probs serve it (score 0 and one empty alternative before the first chunk).  Streams without the setting decode
  * exactly as before. */
 int32_t k2hip_online_stream_set_ctc_prefix_beam(k2hip_online_stream_t* s, int32_t beam /* 0 = off, 1..8 */, int32_t nbest /* 1..beam */);
+/* ---- Biasing of the streaming CTC prefix beam search -----------------------------------------------------------------------------
+ * Nothing new is defined.  The semantics are those of "Hotword and n-gram LM biasing of the CTC prefix beam search" above, applied to
+ * all frames a stream has been given: after any sequence of chunk calls (any chunk lengths, any batch composition per call, ragged
+ * n_frames, other streams of the call biased differently or not at all) a biased stream holds EXACTLY what the offline biased search
+ * holds after one run over the concatenation of its frames with the same tables -- the slots in selection-rank order, each with tokens,
+ * absolute frame timestamps, token log-probs, pb, pnb, tot, ctx, hs, ls; the entries in (final desc, slot asc) order with
+ * final = (tot + ctx) - pending[hs]; all of it bit for bit, the float32 ctx and final included (one per-frame source; ctx is a
+ * function of the token sequence alone).
+ *   What is CARRIED keeps the pending bonus: the carried ctx of a slot whose match is under way still holds that bonus, because the
+ *   match may complete in the next chunk; nothing is subtracted from what is carried.
+ *   The slots are carried in SELECTION-RANK order, not in final order: the tie rule "lower flat index" of the next frame depends on it.
+ *   What a stream REPORTS after a step is entry 0 in final order (tokens, timestamps, token log-probs), its score final, and as
+ *   alternatives the first min(nbest, live) entries in final order.  Tokens can therefore be revised from step to step more often than
+ *   in the unbiased search; n_new_tokens stays a signed change: re-read Tokens after every step.
+ *   Example (the flip row of tests/ctc_prefix_bias_cases.py, phrase [a, b], one frame per chunk): after frame 0 the slots are [a]
+ *   (hs = 1, ctx = 1.5, pending) and [b], but the reported result is [b] with score -1.25; after frame 1 it is [a, b] with score 1.0,
+ *   after frame 2 [a, b] with score 0.75 exactly.
+ * The switch is PER STREAM and OFF by default: k2hip_online_stream_set_ctc_prefix_biasing (recognizer level) and
+ * k2hip_ctc_prefix_stream_set_biasing (operator level).  On: the stream's carried search reads the graph attached to THAT stream, if
+ * any (k2hip_online_stream_set_hotwords / k2hip_ctc_prefix_stream_set_hotwords; uploads are shared between streams of one model as
+ * for the beam streams), and the model's n-gram LM of k2hip_set_ngram_lm, if one is set when the stream searches its first chunk.
+ * Off: both are ignored, the results are bit for bit the unbiased search's; an attached graph stays ignored.  The model-level list of
+ * k2hip_set_hotwords and k2hip_set_ctc_prefix_biasing never apply to streaming.
+ * The three setters are legal only while the stream holds the start state -- before its first searched chunk, or after a reset --
+ * else K2HIP_ERR_INVALID ("... reset the stream first").  A reset keeps the switch and the graph and returns every prefix to hs = 0,
+ * ctx = 0, ls = the start state of the LM then set.  K2HIP_ERR_UNSUPPORTED on a model without a CTC head; the graph's vocab_size is
+ * checked against the model.
+ * The LM follows the rule of the streaming beam search: a biased stream keeps the setting it searched its first chunk with; after
+ * k2hip_set_ngram_lm changed or cleared it, a chunk call or k2hip_online_step naming that stream fails with K2HIP_ERR_INVALID and no
+ * stream changes; a change that lands between the checks and the launch is caught under the launch's lock ("... call again").
+ * Streams with the switch off are not subject to the rule.
+ * One call may mix biased and unbiased streams, different graphs, graph-only, LM-only and both.  A call in which no stream is biased
+ * issues the unbiased launch, unchanged.  Otherwise the biased kernel runs for the whole call: streams without a graph get null
+ * tables, streams that do not run the LM have it masked off, and their results are bit for bit the plain search's.  Every stream of
+ * one call still carries the same beam setting. */
+int32_t k2hip_online_stream_set_ctc_prefix_biasing(k2hip_online_stream_t* s, int32_t on);
+int32_t k2hip_ctc_prefix_stream_set_hotwords(k2hip_ctc_prefix_stream_t* s, const k2hip_hotwords_t* hw /* NULL: detach */);
+int32_t k2hip_ctc_prefix_stream_set_biasing(k2hip_ctc_prefix_stream_t* s, int32_t on);
 /* Per stream.  num_alternatives: the count (>= 1; -1 for NULL, for online streams a negative error code under greedy_search).
  * get_alternative(i): tokens / timestamps / token_log_probs [cap] (each may be NULL), *n = its length, *score = its finalized
  * log-prob; K2HIP_ERR_CAPACITY if cap is too small (nothing is written), K2HIP_ERR_INVALID for i outside the list.

@@ -129,6 +129,14 @@ int32_t k2hip_debug_gemm_run(k2hip_model_t* model, const float* A, const float* 
  *     CtcPrefixResumeArgs (csrc/ctc_prefix_layout.h has the offsets) --, out [B][out_ints] and status [1] int32 (1: an in block
  *     contradicts itself); ints B, Tc, V, beam.  V is free.  The in blocks are checked on the host first (n, last tokens, relation
  *     lengths: everything the kernel indexes with); the kernel stores straight into the guarded out buffer.
+ *   "ctc_prefix_resume_bias" (tests/test_ctc_prefix_stream_bias_gpu.py): the resume form's biased instantiation alone.  The five buffers
+ *     of "ctc_prefix_resume", then side in [B][1 + 3K] = [flags | ctx[K] (float bits) | hs[K] | ls[K]] (flags bit 0: the row runs the
+ *     LM; K = beam) and side out [B][5K] = [ctx[K] | hs[K] | ls[K] | fin[K] (float bits) | ord[K]] (csrc/ctc_prefix_layout.h,
+ *     CtcPrefixResumeBiasLayout), the nine table buffers of "ctc_prefix_beam_bias" (one set per call) and row_graph [B] int32: 1 = the
+ *     row reads the hotword tables, 0 = null tables for that row; ints B, Tc, V, beam, S, S_lm, A, start.  V is free.  The host runs
+ *     the table check of "ctc_prefix_beam_bias" and the range checks of the side in blocks (every hs inside the row's graph, every ls
+ *     inside the LM where the flag is set, no flag without LM tables, no row_graph without hotword tables) first and fails with
+ *     K2HIP_ERR_INVALID; the kernel stores straight into the guarded out and side out buffers.
  * The kernels around the encoder layers (tests/test_outer_kernels_gpu.py; cases and references in tests/outer_kernels.py), arguments in
  * the launcher's own order as above, a bool as an int:
  *   offline front end: "pad_logfloor" (bufs packed, d_off int64 [B], d_len int64 [B], out; ints B, L), "pad_logfloor_dense" (bufs feats,

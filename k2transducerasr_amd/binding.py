@@ -1059,6 +1059,13 @@ class OnlineStream:
         token_log_probs() serve it."""
         self._m._chk(self._L.k2hip_online_stream_set_ctc_prefix_beam(self._h, beam, nbest))
 
+    def set_ctc_prefix_biasing(self, on: bool = True):
+        """k2hip_online_stream_set_ctc_prefix_biasing: the stream's carried prefix search reads the stream's own hotword graph
+        (set_hotwords) and the model's n-gram LM; off by default.  Only before the stream's first decoded chunk or after reset().  The
+        stream then reports the first entry in final order, score = (tot + ctx) - pending: re-read tokens after every step."""
+        self._L.k2hip_online_stream_set_ctc_prefix_biasing.argtypes = [C.c_void_p, C.c_int32]
+        self._m._chk(self._L.k2hip_online_stream_set_ctc_prefix_biasing(self._h, 1 if on else 0))
+
     def close(self):
         if getattr(self, "_h", None):
             self._L.k2hip_online_stream_destroy(self._h)
@@ -1290,6 +1297,18 @@ class CtcPrefixStream:
     def reset(self):
         self._m._chk(self._L.k2hip_ctc_prefix_stream_reset(self._h))
 
+    def set_hotwords(self, hotwords: Optional["Hotwords"] = None):
+        """k2hip_ctc_prefix_stream_set_hotwords: this stream's hotword graph, read only with set_biasing(True); None detaches.  Only in
+        the start state (new or reset); a reset keeps it."""
+        self._L.k2hip_ctc_prefix_stream_set_hotwords.argtypes = [C.c_void_p, C.c_void_p]
+        self._m._chk(self._L.k2hip_ctc_prefix_stream_set_hotwords(self._h, hotwords._h if hotwords is not None else None))
+
+    def set_biasing(self, on: bool = True):
+        """k2hip_ctc_prefix_stream_set_biasing: the per-stream switch (off by default): the carried search reads this stream's graph and
+        the model's n-gram LM.  Only in the start state (new or reset); a reset keeps it."""
+        self._L.k2hip_ctc_prefix_stream_set_biasing.argtypes = [C.c_void_p, C.c_int32]
+        self._m._chk(self._L.k2hip_ctc_prefix_stream_set_biasing(self._h, 1 if on else 0))
+
     @property
     def num_frames(self) -> int:
         return int(self._L.k2hip_ctc_prefix_stream_num_frames(self._h))
@@ -1346,13 +1365,17 @@ class OnlineRecognizer:
                             "lstm": ["lstm_h", "lstm_c"]}.get(mt, [])
         self.embed_state_floats = 128 * 3 * 19 if mt in ("zipformer2", "zipformer2ctc") else 0
 
-    def create_online_stream(self, hotwords=None, hotwords_score: float = 1.5, ctc_prefix_beam: int = 0, nbest: int = 1) -> OnlineStream:  # CreateOnlineStream :60-64
+    def create_online_stream(self, hotwords=None, hotwords_score: float = 1.5, ctc_prefix_beam: int = 0, nbest: int = 1,
+                             ctc_prefix_biasing: bool = False) -> OnlineStream:  # CreateOnlineStream :60-64
         """hotwords: a Hotwords graph, or a list of token-id phrases scored hotwords_score per matched token -- the stream's own list
         (sherpa-onnx's CreateStream(hotwords)); it biases modified_beam_search only.  ctc_prefix_beam > 0 (a streaming CTC model):
-        the stream decodes with the carried prefix beam search, keeping nbest alternatives (OnlineStream.set_ctc_prefix_beam)."""
+        the stream decodes with the carried prefix beam search, keeping nbest alternatives (OnlineStream.set_ctc_prefix_beam);
+        ctc_prefix_biasing: that search reads the stream's hotwords and the model's n-gram LM (OnlineStream.set_ctc_prefix_biasing)."""
         s = OnlineStream(self.model)
         if ctc_prefix_beam:
             s.set_ctc_prefix_beam(ctc_prefix_beam, nbest)
+        if ctc_prefix_biasing:
+            s.set_ctc_prefix_biasing(True)
         if hotwords is not None:
             if isinstance(hotwords, Hotwords):
                 s.set_hotwords(hotwords)

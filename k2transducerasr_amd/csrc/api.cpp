@@ -106,6 +106,7 @@ struct k2hip_model {
     // what a stream notes with its first chunk (BeamHistory::begin_lm).  Written and read under the engine's lock.
     uint64_t lm_serial = 0;
     int lm_start = 0;
+    int lm_states = 0;   // its number of states (0 = none): what a carried LM state is checked against before a launch
     // k2hip_set_nbest: 1 = off (the engine keeps nothing beyond the best hypothesis), n > 1 = alternatives and token log-probs are kept
     std::atomic<int> nbest{1};
     // the graphs attached to this model's streams (HwResident), by serial number; hw_uploads counts the uploads (k2hip_debug.h)
@@ -201,6 +202,9 @@ struct k2hip_online_stream {
     // the setting is kept by a reset, the prefixes are not.  Tokens / Timestamps are [blank, blank] + the best prefix
     int cp_beam = 0, cp_nbest = 1;
     std::unique_ptr<CtcPrefixHistory> cprefix;
+    // k2hip_online_stream_set_ctc_prefix_biasing: the carried prefix search of this stream reads its own graph (`hw`) and the model's
+    // n-gram LM.  Off by default; kept by a reset
+    bool cp_biasing = false;
 };
 
 // operator level of the streaming beam search: one stream's hypotheses, fed encoder frames by the caller (k2hip_beam_search_chunk)
@@ -214,6 +218,38 @@ struct k2hip_beam_stream {
 struct k2hip_ctc_prefix_stream {
     k2hip_model* model;
     CtcPrefixHistory hist;
+    std::shared_ptr<HwResident> hw;   // the stream's hotword graph (k2hip_ctc_prefix_stream_set_hotwords) or null; read only with the switch on
+    bool biasing = false;             // k2hip_ctc_prefix_stream_set_biasing; both are kept by a reset
+};
+
+// What the biased carried prefix search of one call needs beside the in / out blocks (k2hip_ctc_prefix_beam_search_chunk and the cp_beam
+// branch of k2hip_online_step share it): the LM setting the call runs with, the streams' graphs and side blocks.  Unbiased streams of a
+// biased call get null tables and a clear LM flag: bit for bit the plain search.
+struct CtcPrefixBiasCall {
+    uint64_t lm_serial = 0;
+    int lm_start = 0, lm_states = 0;
+    std::vector<BeamHwStream> graphs;
+    std::vector<int> side_in, side_out;
+    bool with_lm() const { return lm_serial != 0; }
+    // before anything of any stream moves: a biased stream keeps the LM setting it searched its first chunk with
+    static void check_lm(const CtcPrefixHistory& h, uint64_t lm_serial, const char* who, int i) {
+        K2_REQUIRE(h.frames() == 0 || h.lm_serial() == lm_serial,
+                   "%s: stream %d has searched %lld frames with another n-gram LM setting (k2hip_set_ngram_lm changed or cleared it) and its "
+                   "prefixes carry that LM's states -- reset the stream first", who, i, h.frames());
+    }
+    void stage(int B, int K) {
+        const CtcPrefixResumeBiasLayout SL{K};
+        graphs.assign((size_t)B, BeamHwStream{});
+        side_in.assign((size_t)B * SL.in_ints(), 0);
+        side_out.assign((size_t)B * SL.out_ints(), 0);
+    }
+    static int graph_states(const HwResident* hw, bool biased) { return biased && hw && hw->pending ? (int)hw->pending->size() : 0; }
+    void fill(int b, int K, CtcPrefixHistory& h, const HwResident* hw, bool biased) {
+        const CtcPrefixResumeBiasLayout SL{K};
+        if (biased && h.frames() == 0) h.begin_lm(lm_serial, with_lm(), lm_start);
+        if (biased && hw) graphs[(size_t)b] = hw->tables;
+        h.fill_side_in(side_in.data() + (size_t)b * SL.in_ints(), graph_states(hw, biased), biased && with_lm() ? lm_states : 0);
+    }
 };
 
 // one stream's encoder caches as the operator-level API sees them (IOnlineProj's List<List<float[]>>): a slot of the device pool
@@ -721,9 +757,11 @@ int32_t k2hip_set_ngram_lm(k2hip_model_t* model, const k2hip_ngram_lm_t* lm, flo
         K2_REQUIRE(e.batches_in_flight() == 0, "set_ngram_lm: %d submitted batches are in flight; wait for them first", e.batches_in_flight());
         void* fresh = nullptr;
         BeamLm tables;
+        int n_states = 0;
         if (lm && scale > 0.f) {   // (scale = 0 adds nothing anywhere: the plain search, as with no LM)
             NgramDeviceForm d;
             lm->lm->device_form(scale, &d);
+            n_states = (int)(d.states.size() / 4);
             const int64_t nb_s = align_up((int64_t)sizeof(int32_t) * (int64_t)d.states.size(), 16);
             const int64_t nb_a = align_up((int64_t)sizeof(int32_t) * std::max<int64_t>((int64_t)d.arc_tok.size(), 1), 16);
             const int64_t nb_v = align_up((int64_t)sizeof(int32_t) * V, 16);
@@ -764,6 +802,7 @@ int32_t k2hip_set_ngram_lm(k2hip_model_t* model, const k2hip_ngram_lm_t* lm, flo
         e.set_ngram_tables(tables);
         model->lm_serial = fresh ? ++g_hw_serial : 0;
         model->lm_start = tables.start;
+        model->lm_states = fresh ? n_states : 0;
         void* old = model->lm_dev;
         model->lm_dev = fresh;
         if (old) e.dev_free(old);
@@ -1153,8 +1192,10 @@ int32_t k2hip_online_stream_reset(k2hip_online_stream_t* s) {
         }
         std::shared_ptr<HwResident> hw = std::move(s->hw);   // (the attached hotword graph stays; every hypothesis is back at its root)
         const int cp_beam = s->cp_beam, cp_nbest = s->cp_nbest;   // (so does the prefix-search setting; its prefixes go)
+        const bool cp_biasing = s->cp_biasing;
         *s = k2hip_online_stream{model, s->slot};
         s->hw = std::move(hw);
+        s->cp_biasing = cp_biasing;
         s->cp_beam = cp_beam;
         s->cp_nbest = cp_nbest;
         if (model->engine.model().cfg().conformer) s->processed_len = 2;
@@ -1181,6 +1222,16 @@ int32_t k2hip_online_stream_set_ctc_prefix_beam(k2hip_online_stream_t* s, int32_
         s->cp_beam = beam;
         s->cp_nbest = beam ? nbest : 1;
         s->cprefix.reset();
+    });
+}
+int32_t k2hip_online_stream_set_ctc_prefix_biasing(k2hip_online_stream_t* s, int32_t on) {
+    return guard([&] {
+        NEED(s);
+        const Config& c = s->model->engine.model().cfg();
+        if (!c.ctc) failf(K2HIP_ERR_UNSUPPORTED, "online stream set_ctc_prefix_biasing: model_type '%s' has no CTC head", c.model_type.c_str());
+        K2_REQUIRE(s->chunks_done == 0 && s->method < 0, "online stream set_ctc_prefix_biasing: the stream has searched %lld chunks and its prefixes "
+                   "carry the states of the search it started with -- reset the stream first", s->chunks_done);
+        s->cp_biasing = on != 0;
     });
 }
 int32_t k2hip_online_stream_destroy(k2hip_online_stream_t* s) {
@@ -1400,6 +1451,20 @@ int32_t k2hip_online_step(k2hip_model_t* model, k2hip_online_stream_t* const* st
         }
         if (idx.empty()) return;   // :113-116
         CK = streams[0]->cp_beam;
+        // the carried prefix search with biasing: per stream, opt-in; the LM rule of the beam search holds for the streams that opted in
+        bool cp_bias = false;
+        CtcPrefixBiasCall cpb;
+        for (size_t r = 0; CK > 0 && r < idx.size(); r++) cp_bias = cp_bias || streams[idx[r]]->cp_biasing;
+        if (cp_bias) {
+            {
+                EngineLock lk(e);
+                cpb.lm_serial = model->lm_serial; cpb.lm_start = model->lm_start; cpb.lm_states = model->lm_states;
+            }
+            for (size_t r = 0; r < idx.size(); r++) {
+                const k2hip_online_stream* s = streams[idx[r]];
+                if (s->cp_biasing && s->cprefix) CtcPrefixBiasCall::check_lm(*s->cprefix, cpb.lm_serial, "online step", idx[r]);
+            }
+        }
         // a stream keeps the LM it decoded its first chunk with (decided for all streams before anything of any of them moves)
         for (size_t r = 0; K > 0 && r < idx.size(); r++) {
             const k2hip_online_stream* s = streams[idx[r]];
@@ -1496,6 +1561,13 @@ int32_t k2hip_online_step(k2hip_model_t* model, k2hip_online_stream_t* const* st
                 if (!s->cprefix) s->cprefix.reset(new CtcPrefixHistory(CK, s->cp_nbest));   // (the start state: as good as none)
                 s->cprefix->fill_in(bin.data() + (size_t)r * CL.in_ints(), Tp);
             }
+            if (cp_bias) {   // some stream of the tick is biased: graphs and side blocks for the whole call
+                cpb.stage(R, CK);
+                for (int r = 0; r < R; r++) {
+                    k2hip_online_stream* s = streams[idx[r]];
+                    cpb.fill(r, CK, *s->cprefix, s->hw.get(), s->cp_biasing);
+                }
+            }
         } else {
             tok.resize((size_t)R * Tp);
             ts.resize((size_t)R * Tp);
@@ -1508,7 +1580,7 @@ int32_t k2hip_online_step(k2hip_model_t* model, k2hip_online_stream_t* const* st
             EngineLock lk(e);
             // the LM states staged above index the tables of setting lm_serial: this lock covers the launch, and k2hip_set_ngram_lm
             // takes it too, so a setting that changed since it was read is caught here, before any device work
-            if (K > 0 && model->lm_serial != lm_serial) {
+            if ((K > 0 && model->lm_serial != lm_serial) || (cp_bias && model->lm_serial != cpb.lm_serial)) {
                 lm_raced = true;
                 failf(K2HIP_ERR_INVALID, "online step: k2hip_set_ngram_lm changed the n-gram LM while this step was being prepared; call again");
             }
@@ -1527,10 +1599,22 @@ int32_t k2hip_online_step(k2hip_model_t* model, k2hip_online_stream_t* const* st
                 e.online_step_beam(slots.data(), chunks.data(), plens.data(), nch.data(), R, K, bin.data(), bout.data(),
                                    all_mirrored ? heads.data() : nullptr);
             else if (CK > 0) {
-                e.online_step_ctc_prefix(slots.data(), chunks.data(), plens.data(), nch.data(), R, CK, bin.data(), bout.data(),
-                                         all_mirrored ? heads.data() : nullptr);
+                if (cp_bias)
+                    e.online_step_ctc_prefix_bias(slots.data(), chunks.data(), plens.data(), nch.data(), R, CK, bin.data(), bout.data(),
+                                                  Engine::CtcPrefixBiasIO{cpb.graphs.data(), cpb.side_in.data(), cpb.side_out.data(), cpb.with_lm()},
+                                                  all_mirrored ? heads.data() : nullptr);
+                else
+                    e.online_step_ctc_prefix(slots.data(), chunks.data(), plens.data(), nch.data(), R, CK, bin.data(), bout.data(),
+                                             all_mirrored ? heads.data() : nullptr);
                 const CtcPrefixResumeLayout CL{CK, Tp};   // (the device work is done: an out block that fails its check poisons the streams)
-                for (int r = 0; r < R; r++) streams[idx[r]]->cprefix->check_out(bout.data() + (size_t)r * CL.out_ints(), Tp, Tp);
+                const CtcPrefixResumeBiasLayout SL{CK};
+                for (int r = 0; r < R; r++) {
+                    const k2hip_online_stream* s = streams[idx[r]];
+                    if (cp_bias && s->cp_biasing)
+                        s->cprefix->check_out(bout.data() + (size_t)r * CL.out_ints(), cpb.side_out.data() + (size_t)r * SL.out_ints(), Tp, Tp,
+                                              CtcPrefixBiasCall::graph_states(s->hw.get(), true), cpb.with_lm() ? cpb.lm_states : 0);
+                    else s->cprefix->check_out(bout.data() + (size_t)r * CL.out_ints(), Tp, Tp);
+                }
             } else
                 e.online_step(slots.data(), chunks.data(), hyps.data(), plens.data(), nch.data(), R, tok.data(), ts.data(), n.data(),
                               all_mirrored ? heads.data() : nullptr);
@@ -1570,7 +1654,10 @@ int32_t k2hip_online_step(k2hip_model_t* model, k2hip_online_stream_t* const* st
             if (CK > 0) {   // the best prefix replaces the result (it may revise earlier tokens): n_new_tokens = change of its length
                 const CtcPrefixResumeLayout CL{CK, Tp};
                 const int64_t before = (int64_t)s->cprefix->tokens().size();
-                s->cprefix->apply_out(bout.data() + (size_t)r * CL.out_ints(), Tp, Tp);
+                // (a biased stream reports the first entry in final order: its tokens are revised more often than the unbiased search's)
+                if (cp_bias && s->cp_biasing)
+                    s->cprefix->apply_out(bout.data() + (size_t)r * CL.out_ints(), cpb.side_out.data() + (size_t)r * CtcPrefixResumeBiasLayout{CK}.out_ints(), Tp, Tp);
+                else s->cprefix->apply_out(bout.data() + (size_t)r * CL.out_ints(), Tp, Tp);
                 s->tokens.assign(2, K2HIP_BLANK_ID);
                 s->tokens.insert(s->tokens.end(), s->cprefix->tokens().begin(), s->cprefix->tokens().end());
                 s->timestamps = s->cprefix->timestamps();
@@ -1870,6 +1957,22 @@ int32_t k2hip_ctc_prefix_stream_reset(k2hip_ctc_prefix_stream_t* s) {
         s->hist.reset();
     });
 }
+int32_t k2hip_ctc_prefix_stream_set_hotwords(k2hip_ctc_prefix_stream_t* s, const k2hip_hotwords_t* hw) {
+    return guard([&] {
+        NEED(s);
+        K2_REQUIRE(s->hist.frames() == 0, "ctc prefix stream set_hotwords: the stream has searched %lld frames and its prefixes carry states of the "
+                   "graph it started with -- reset the stream first", s->hist.frames());
+        s->hw = hw ? hw_resident_get(s->model, hw, "ctc prefix stream set_hotwords") : nullptr;
+    });
+}
+int32_t k2hip_ctc_prefix_stream_set_biasing(k2hip_ctc_prefix_stream_t* s, int32_t on) {
+    return guard([&] {
+        NEED(s);
+        K2_REQUIRE(s->hist.frames() == 0, "ctc prefix stream set_biasing: the stream has searched %lld frames and its prefixes carry the states of "
+                   "the search it started with -- reset the stream first", s->hist.frames());
+        s->biasing = on != 0;
+    });
+}
 int64_t k2hip_ctc_prefix_stream_num_frames(const k2hip_ctc_prefix_stream_t* s) { return s ? (int64_t)s->hist.frames() : -1; }
 int32_t k2hip_ctc_prefix_beam_search_chunk(k2hip_model_t* model, k2hip_ctc_prefix_stream_t* const* streams, int32_t B, const float* log_probs, int32_t Tc,
                                            const int32_t* n_frames) {
@@ -1892,14 +1995,45 @@ int32_t k2hip_ctc_prefix_beam_search_chunk(k2hip_model_t* model, k2hip_ctc_prefi
         const int K = streams[0]->hist.beam();
         const CtcPrefixResumeLayout L{K, Tc};
         std::vector<int> bin((size_t)B * L.in_ints()), bout((size_t)B * L.out_ints());
+        // biasing is per stream and opt-in: with no biased stream in the call this is the plain call, unchanged
+        bool any_bias = false;
+        for (int b = 0; b < B; b++) any_bias = any_bias || streams[b]->biasing;
+        CtcPrefixBiasCall cpb;
+        const CtcPrefixResumeBiasLayout SL{K};
+        if (any_bias) {
+            {
+                EngineLock lk(model->engine);
+                cpb.lm_serial = model->lm_serial; cpb.lm_start = model->lm_start; cpb.lm_states = model->lm_states;
+            }
+            for (int b = 0; b < B; b++)
+                if (streams[b]->biasing) CtcPrefixBiasCall::check_lm(streams[b]->hist, cpb.lm_serial, "ctc_prefix_beam_search_chunk", b);
+            cpb.stage(B, K);
+            for (int b = 0; b < B; b++) cpb.fill(b, K, streams[b]->hist, streams[b]->hw.get(), streams[b]->biasing);
+        }
         for (int b = 0; b < B; b++) streams[b]->hist.fill_in(bin.data() + (size_t)b * L.in_ints(), Tc);
         {
             EngineLock lk(model->engine);
-            model->engine.ctc_prefix_chunk_host(log_probs, B, Tc, n_frames, K, bin.data(), bout.data());
+            // (this lock covers the launch and k2hip_set_ngram_lm takes it too: the staged LM states still index the tables that are set)
+            K2_REQUIRE(!any_bias || model->lm_serial == cpb.lm_serial, "ctc_prefix_beam_search_chunk: k2hip_set_ngram_lm changed the n-gram LM while this "
+                                                                        "call was being prepared; call again");
+            if (any_bias)
+                model->engine.ctc_prefix_chunk_host_bias(log_probs, B, Tc, n_frames, K, bin.data(), bout.data(),
+                                                         Engine::CtcPrefixBiasIO{cpb.graphs.data(), cpb.side_in.data(), cpb.side_out.data(), cpb.with_lm()});
+            else model->engine.ctc_prefix_chunk_host(log_probs, B, Tc, n_frames, K, bin.data(), bout.data());
         }
         // (only after success, and after every out block has passed its check: a failed call leaves every stream as it was)
-        for (int b = 0; b < B; b++) streams[b]->hist.check_out(bout.data() + (size_t)b * L.out_ints(), Tc, n_frames ? n_frames[b] : Tc);
-        for (int b = 0; b < B; b++) streams[b]->hist.apply_out(bout.data() + (size_t)b * L.out_ints(), Tc, n_frames ? n_frames[b] : Tc);
+        for (int b = 0; b < B; b++) {
+            const int nf = n_frames ? n_frames[b] : Tc;
+            if (streams[b]->biasing)
+                streams[b]->hist.check_out(bout.data() + (size_t)b * L.out_ints(), cpb.side_out.data() + (size_t)b * SL.out_ints(), Tc, nf,
+                                           CtcPrefixBiasCall::graph_states(streams[b]->hw.get(), true), cpb.with_lm() ? cpb.lm_states : 0);
+            else streams[b]->hist.check_out(bout.data() + (size_t)b * L.out_ints(), Tc, nf);
+        }
+        for (int b = 0; b < B; b++) {
+            const int nf = n_frames ? n_frames[b] : Tc;
+            if (streams[b]->biasing) streams[b]->hist.apply_out(bout.data() + (size_t)b * L.out_ints(), cpb.side_out.data() + (size_t)b * SL.out_ints(), Tc, nf);
+            else streams[b]->hist.apply_out(bout.data() + (size_t)b * L.out_ints(), Tc, nf);
+        }
     });
 }
 int32_t k2hip_ctc_prefix_stream_num_tokens(const k2hip_ctc_prefix_stream_t* s) { return s ? (int32_t)s->hist.tokens().size() : -1; }

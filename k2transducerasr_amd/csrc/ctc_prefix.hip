@@ -36,6 +36,14 @@
 //                  go through LDS -- one more barrier per frame -- to the thread that builds the slot, which loads next[hs_k V + v]
 //                  itself.  After the last frame final = (tot + ctx) - pending[hs] and the entries' order are formed in LDS before the
 //                  chains are written.  Null hotword tables / null LM tables: that half adds nothing (a null check).
+//   k_ctc_prefix<true, true>  the resumed search with biasing (include/k2hip.h "Biasing of the streaming CTC prefix beam search").  The
+//                  same source a fourth time.  The tables are the row's own: row_hw / row_lm read the row's entry of hw_streams [B] and
+//                  the call's LM (null where the row's flag is clear) once, wave-uniformly; the offline form reads its single pair
+//                  through the same two accessors.  The slots' (ctx, hs, ls) start from the side in block -- ctx with the pending bonus
+//                  of a match under way, the slots in selection order --, a slot that receives a fold through the boundary keeps its
+//                  own three values as inside a chunk, and after the chunk's last frame final and the entries' order are formed by the
+//                  code the offline form runs there; the survivors' (ctx, hs, ls, fin, ord) go to the side out block beside the
+//                  unchanged out block, whose tot stays acoustic (CtcPrefixResumeBiasLayout).
 // No workgroup waits for another; every loop is bounded by T, beam, a hypothesis length, K2HIP_NGRAM_MAX_ORDER - 1 levels or the walk's
 // 64-ary narrowing; all stores are ordinary vector stores.
 #include <climits>
@@ -105,9 +113,23 @@ __device__ __forceinline__ bool fold_through_boundary(int p, int q, int jn, cons
     return true;
 }
 
+// The tables a row reads (BIAS): the call's single pair offline; resumed, the row's own graph out of hw_streams [B] (all null: none)
+// and the call's LM, masked off for a row whose side in block does not set flag bit 0.  Wave-uniform: r = blockIdx.x.
+__device__ __forceinline__ BeamHwStream row_hw(const CtcPrefixBiasArgs& a, int) { return a.hw; }
+__device__ __forceinline__ BeamLm row_lm(const CtcPrefixBiasArgs& a, int) { return a.lm; }
+__device__ __forceinline__ BeamHwStream row_hw(const CtcPrefixResumeBiasArgs& a, int r) { return a.hw_streams[r]; }
+__device__ __forceinline__ BeamLm row_lm(const CtcPrefixResumeBiasArgs& a, int r) {
+    BeamLm lm = a.lm;
+    if (!(a.side_in[(long long)r * CtcPrefixResumeBiasLayout{a.beam}.in_ints()] & 1)) lm.states = nullptr;
+    return lm;
+}
+template <typename Args>
+__device__ __forceinline__ BeamHwStream row_hw(const Args&, int) { return {}; }
+template <typename Args>
+__device__ __forceinline__ BeamLm row_lm(const Args&, int) { return {}; }
+
 template <bool RESUME, bool BIAS, typename Args>
 __global__ __launch_bounds__(PT) void k_ctc_prefix(Args a) {
-    static_assert(!(RESUME && BIAS), "the carried search is unbiased");
     __shared__ Slots sl[2];
     [[maybe_unused]] __shared__ BiasLds<BIAS> bl;
     __shared__ float stay_pb[KB], stay_pnb[KB];
@@ -116,6 +138,8 @@ __global__ __launch_bounds__(PT) void k_ctc_prefix(Args a) {
     __shared__ int wl_i[PW][KB];
     const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int V = a.V, beam = a.beam;
+    [[maybe_unused]] const BeamHwStream hw = row_hw(a, r);   // (BIAS; wave-uniform, read once)
+    [[maybe_unused]] const BeamLm lm = row_lm(a, r);
     int Tp;
     if constexpr (RESUME) Tp = a.Tc;
     else Tp = a.Tp;
@@ -161,6 +185,11 @@ __global__ __launch_bounds__(PT) void k_ctc_prefix(Args a) {
             s.node[k] = -1 - k; s.pnode[k] = kNoParent;
             s.hash[k] = (unsigned long long)(unsigned)in[L.in_hash() + 2 * k] | (unsigned long long)(unsigned)in[L.in_hash() + 2 * k + 1] << 32;
             s.phash[k] = (unsigned long long)(unsigned)in[L.in_phash() + 2 * k] | (unsigned long long)(unsigned)in[L.in_phash() + 2 * k + 1] << 32;
+            if constexpr (BIAS) {   // the carried (ctx, hs, ls): ctx with the pending bonus still in it
+                const CtcPrefixResumeBiasLayout SL{beam};
+                const int* sin = a.side_in + (long long)r * SL.in_ints();
+                bl.ctx[0][k] = __int_as_float(sin[SL.in_ctx() + k]); bl.hs[0][k] = sin[SL.in_hs() + k]; bl.ls[0][k] = sin[SL.in_ls() + k];
+            }
         }
     } else if (tid == 0) {
         Slots& s = sl[0];
@@ -169,7 +198,7 @@ __global__ __launch_bounds__(PT) void k_ctc_prefix(Args a) {
         s.hash[0] = kHashSeed; s.phash[0] = 0;
         s.n = 1;
         fold_par[0] = -1;
-        if constexpr (BIAS) { bl.ctx[0][0] = 0.f; bl.hs[0][0] = 0; bl.ls[0][0] = a.lm.start; }
+        if constexpr (BIAS) { bl.ctx[0][0] = 0.f; bl.hs[0][0] = 0; bl.ls[0][0] = lm.start; }
     }
     float px = T > 0 && tid < V ? lp[tid] : ninf();
     __syncthreads();
@@ -243,7 +272,7 @@ __global__ __launch_bounds__(PT) void k_ctc_prefix(Args a) {
                     if constexpr (BIAS) {   // the key: acoustic total + (ctx + bonus); dropped on the acoustic total
                         if (k < n && !(kill >> k & 1u) && x > ninf()) {
                             float cb = s_ctx[k];
-                            if (a.hw.bonus) cb += a.hw.bonus[(long long)s_hs[k] * V + v];
+                            if (hw.bonus) cb += hw.bonus[(long long)s_hs[k] * V + v];
                             insert(x + cb, k * V + v);
                         }
                     } else if (k < n && !(kill >> k & 1u) && x > ninf()) insert(x, k * V + v);
@@ -297,7 +326,7 @@ __global__ __launch_bounds__(PT) void k_ctc_prefix(Args a) {
                     const int k = i / V, v = i - k * V;
                     float term = 0.f;
                     int ls = bl.ls[t & 1][k];
-                    if (v != 0 && v != K2HIP_UNK_ID && a.lm.states) beam_lm_walk(a.lm, ls, v, lane, &term, &ls);
+                    if (v != 0 && v != K2HIP_UNK_ID && lm.states) beam_lm_walk(lm, ls, v, lane, &term, &ls);
                     if (lane == 0) { bl.term[2 * wave + j] = term; bl.lnext[2 * wave + j] = ls; }
                 }
             }
@@ -323,9 +352,9 @@ __global__ __launch_bounds__(PT) void k_ctc_prefix(Args a) {
                 float ctx = bl.ctx[par][k];
                 int hs = bl.hs[par][k], ls = bl.ls[par][k];
                 if (m > 0 && v) {
-                    if (a.hw.bonus) {
-                        ctx += a.hw.bonus[(long long)hs * V + v];
-                        hs = a.hw.next[(long long)hs * V + v];
+                    if (hw.bonus) {
+                        ctx += hw.bonus[(long long)hs * V + v];
+                        hs = hw.next[(long long)hs * V + v];
                     }
                     ctx = ctx + bl.term[tid];
                     ls = bl.lnext[tid];
@@ -352,6 +381,19 @@ __global__ __launch_bounds__(PT) void k_ctc_prefix(Args a) {
     }
     const Slots& f = sl[T & 1];
     const int n = f.n;
+    if constexpr (BIAS) {   // final = (tot + ctx) - pending[hs]; the entries by (final desc, slot asc)
+        if (tid < n) {
+            const float fv = f.tot[tid] + bl.ctx[T & 1][tid];
+            bl.fin[tid] = hw.pending ? fv - hw.pending[bl.hs[T & 1][tid]] : fv;
+        }
+        __syncthreads();
+        if (tid < n) {
+            int rank = 0;
+            for (int j = 0; j < n; j++) rank += bl.fin[j] > bl.fin[tid] || (bl.fin[j] == bl.fin[tid] && j < tid);
+            bl.ord[rank] = tid;
+        }
+        __syncthreads();
+    }
     if constexpr (RESUME) {
         const CtcPrefixResumeLayout L{beam, Tp};
         int* out = a.out + (long long)r * L.out_ints();
@@ -366,6 +408,12 @@ __global__ __launch_bounds__(PT) void k_ctc_prefix(Args a) {
             out[L.out_pb() + q] = __float_as_int(f.pb[q]);
             out[L.out_pnb() + q] = __float_as_int(f.pnb[q]);
             out[L.out_tot() + q] = __float_as_int(f.tot[q]);
+            if constexpr (BIAS) {   // beside the unchanged block: what the slot carries on, its final score, and the q-th slot in final order
+                const CtcPrefixResumeBiasLayout SL{beam};
+                int* so = a.side_out + (long long)r * SL.out_ints();
+                so[SL.out_ctx() + q] = __float_as_int(bl.ctx[T & 1][q]); so[SL.out_hs() + q] = bl.hs[T & 1][q]; so[SL.out_ls() + q] = bl.ls[T & 1][q];
+                so[SL.out_fin() + q] = __float_as_int(bl.fin[q]); so[SL.out_ord() + q] = bl.ord[q];
+            }
             out[L.out_hash() + 2 * q] = (int)(unsigned)f.hash[q]; out[L.out_hash() + 2 * q + 1] = (int)(unsigned)(f.hash[q] >> 32);
             out[L.out_phash() + 2 * q] = (int)(unsigned)f.phash[q]; out[L.out_phash() + 2 * q + 1] = (int)(unsigned)(f.phash[q] >> 32);
             int node = f.node[q];
@@ -378,19 +426,6 @@ __global__ __launch_bounds__(PT) void k_ctc_prefix(Args a) {
             }
         }
     } else {
-        if constexpr (BIAS) {   // final = (tot + ctx) - pending[hs]; the entries by (final desc, slot asc)
-            if (tid < n) {
-                const float fv = f.tot[tid] + bl.ctx[T & 1][tid];
-                bl.fin[tid] = a.hw.pending ? fv - a.hw.pending[bl.hs[T & 1][tid]] : fv;
-            }
-            __syncthreads();
-            if (tid < n) {
-                int rank = 0;
-                for (int j = 0; j < n; j++) rank += bl.fin[j] > bl.fin[tid] || (bl.fin[j] == bl.fin[tid] && j < tid);
-                bl.ord[rank] = tid;
-            }
-            __syncthreads();
-        }
         auto slot_of = [&](int i) {
             if constexpr (BIAS) return bl.ord[i];
             else return i;
@@ -461,6 +496,16 @@ void ctc_prefix_search_biased(const Ctx& ctx, const CtcPrefixBiasArgs& a) {
     K2_REQUIRE(!a.hw.next == !a.hw.bonus && !a.hw.next == !a.hw.pending, "ctc_prefix_search_biased: incomplete hotword tables");
     K2_REQUIRE(!a.lm.states || (a.lm.uni_lp && a.lm.uni_next && a.lm.start >= 0), "ctc_prefix_search_biased: incomplete LM tables");   // (no arcs at all: null arc arrays)
     hipLaunchKernelGGL((k_ctc_prefix<false, true, CtcPrefixBiasArgs>), dim3(a.R), dim3(PT), 0, ctx.stream, a);
+    K2_HIP(hipGetLastError());
+}
+
+void ctc_prefix_resume_biased(const Ctx& ctx, const CtcPrefixResumeBiasArgs& a) {
+    if (ctx.dry) return;
+    K2_REQUIRE(a.B >= 1 && a.B <= 65535 && a.Tc >= 1 && a.V >= 1 && (long long)kMaxBeam * a.V <= INT_MAX && a.beam >= 1 && a.beam <= kMaxBeam &&
+                   (long long)a.Tc * a.beam <= INT_MAX / 2 && a.in && a.out && a.nodes && a.status && a.hw_streams && a.side_in && a.side_out,
+               "ctc_prefix_resume_biased: bad shape B=%d Tc=%d V=%d beam=%d", a.B, a.Tc, a.V, a.beam);
+    K2_REQUIRE(!a.lm.states || (a.lm.uni_lp && a.lm.uni_next && a.lm.start >= 0), "ctc_prefix_resume_biased: incomplete LM tables");
+    hipLaunchKernelGGL((k_ctc_prefix<true, true, CtcPrefixResumeBiasArgs>), dim3(a.B), dim3(PT), 0, ctx.stream, a);
     K2_HIP(hipGetLastError());
 }
 

@@ -59,6 +59,18 @@ inline void ctc_prefix_bias_check_tables(const CtcPrefixBiasTables& t) {
     }
 }
 
+// The resumed biased search's side in block [flags | ctx[K] | hs[K] | ls[K]] of one stream, before any launch: every carried hs inside
+// that stream's graph (S states; S = 0: no graph, every hs must be 0), every carried ls inside the LM when the row runs it (flag bit 0;
+// S_lm = 0: the call has no LM, the flag must be clear)
+inline void ctc_prefix_bias_check_side_in(const int* side, int K, int S, int S_lm, int stream) {
+    K2_REQUIRE((side[0] & ~1) == 0 && (!(side[0] & 1) || S_lm >= 1), "ctc_prefix biasing: stream %d has the flags %d (LM states: %d)", stream, side[0], S_lm);
+    for (int k = 0; k < K; k++) {
+        const int hs = side[1 + K + k], ls = side[1 + 2 * K + k];
+        K2_REQUIRE(hs >= 0 && hs < (S >= 1 ? S : 1), "ctc_prefix biasing: stream %d slot %d carries the hotword state %d outside [0, %d)", stream, k, hs, S >= 1 ? S : 1);
+        K2_REQUIRE(!(side[0] & 1) || (ls >= 0 && ls < S_lm), "ctc_prefix biasing: stream %d slot %d carries the LM state %d outside [0, %d)", stream, k, ls, S_lm);
+    }
+}
+
 // Step(s, tok) over the sparse tables as beam_lm_walk (lm_walk.h) takes it: at most order - 1 levels, then state 0's dense row
 inline void ctc_prefix_bias_lm_step(const CtcPrefixBiasTables& t, int s, int tok, float* term, int* next) {
     float acc = 0.f;

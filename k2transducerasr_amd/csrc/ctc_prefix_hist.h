@@ -35,6 +35,13 @@ class CtcPrefixHistory {
         path_.clear();
         slots_.assign(1, Slot{0, 0, 0.f, -INFINITY, kCtcPrefixHashSeed, 0});
         tot_.clear();
+        ctx_.assign(1, 0.f);
+        hs_.assign(1, 0);
+        ls_.assign(1, 0);
+        fin_.clear();
+        ord_.clear();
+        lm_serial_ = 0;
+        lm_on_ = false;
         frames_ = 0;
         mat_path_ = 0;
         mat_ids_.clear();
@@ -49,19 +56,22 @@ class CtcPrefixHistory {
     const std::vector<int32_t>& timestamps() const { return timestamps_; }
     const std::vector<float>& token_log_probs() const { return token_log_probs_; }
     // (the total the device formed from (pb, pnb), kept as it came out: the host's log1pf / expf may round the sum differently)
-    float score() const { return tot_.empty() ? 0.f : tot_[0]; }
+    // (a biased stream: the first entry in final order and its final score; tokens() etc. are that entry's)
+    float score() const { return tot_.empty() ? 0.f : fin_.empty() ? tot_[0] : fin_[(size_t)ord_[0]]; }
     int longest() const {
         int d = 0;
         for (const Slot& s : slots_) d = seq_.depth(s.seq) > d ? seq_.depth(s.seq) : d;
         return d;
     }
     size_t live_nodes() const { return seq_.live() > path_.live() ? seq_.live() : path_.live(); }
-    // the live prefixes in slot (= rank) order, at most n of them, each read off its path node
+    // the live prefixes in slot (= rank) order -- a biased stream: in final order, read through ord --, at most n of them, each read off
+    // its path node
     std::vector<BeamAlt> nbest(int n) const {
         const int nh = (int)slots_.size();
         std::vector<BeamAlt> out((size_t)(n < nh ? (n < 0 ? 0 : n) : nh));
-        for (size_t k = 0; k < out.size(); k++) {
-            BeamAlt& a = out[k];
+        for (size_t i = 0; i < out.size(); i++) {
+            BeamAlt& a = out[i];
+            const size_t k = ord_.empty() ? i : (size_t)ord_[i];
             const int d = path_.depth(slots_[k].path);
             a.tokens.resize((size_t)d);
             a.timestamps.resize((size_t)d);
@@ -73,9 +83,75 @@ class CtcPrefixHistory {
                 a.token_log_probs[(size_t)i] = path_[p].yp;
                 p = path_.parent(p);
             }
-            a.score = k < tot_.size() ? tot_[k] : 0.f;
+            a.score = k >= tot_.size() ? 0.f : fin_.empty() ? tot_[k] : fin_[k];
         }
         return out;
+    }
+
+    // ---- biasing (include/k2hip.h "Biasing of the streaming CTC prefix beam search") ----
+    // Beside (pb, pnb) every slot carries ctx (the accumulated context score, WITH the pending bonus of a match under way), hs (state of
+    // the stream's hotword graph) and ls (LM state); the slots stay in selection-rank order.  fin / ord are the last step's final
+    // scores by slot and the slots by (final desc, slot asc): what the stream reports.  An unbiased stream has ctx = hs = ls = 0 and
+    // no fin / ord (identity, tot).
+    // A stream keeps the LM it searched its first chunk with: begin_lm (only while no frame has been searched) notes that LM's serial
+    // number (0 = none), whether this stream runs it, and puts the start prefix into its start state.
+    void begin_lm(uint64_t serial, bool on, int start_state) {
+        lm_serial_ = serial;
+        lm_on_ = on;
+        ls_[0] = on ? start_state : 0;
+    }
+    uint64_t lm_serial() const { return lm_serial_; }
+    bool lm_on() const { return lm_on_; }
+    const std::vector<float>& ctx() const { return ctx_; }
+    const std::vector<int>& hs() const { return hs_; }
+    const std::vector<int>& ls() const { return ls_; }
+    const std::vector<float>& fin() const { return fin_; }
+    const std::vector<int>& ord() const { return ord_; }
+    // the side in block (CtcPrefixResumeBiasLayout{K}) for the next chunk.  S: the states of the graph this stream reads (0: none),
+    // S_lm: the states of the LM (0: none): every carried state must lie inside its table before anything is launched
+    void fill_side_in(int* side, int S, int S_lm) const {
+        const CtcPrefixResumeBiasLayout L{K_};
+        memset(side, 0, sizeof(int) * (size_t)L.in_ints());
+        K2_REQUIRE(!lm_on_ || S_lm >= 1, "ctc prefix stream: the stream runs an n-gram LM and none is set");
+        side[0] = lm_on_ ? 1 : 0;
+        for (size_t k = 0; k < slots_.size(); k++) {
+            K2_REQUIRE(hs_[k] >= 0 && hs_[k] < (S >= 1 ? S : 1), "ctc prefix stream: slot %zu carries the hotword state %d outside [0, %d)", k, hs_[k], S >= 1 ? S : 1);
+            K2_REQUIRE(!lm_on_ || (ls_[k] >= 0 && ls_[k] < S_lm), "ctc prefix stream: slot %zu carries the LM state %d outside [0, %d)", k, ls_[k], S_lm);
+            memcpy(&side[L.in_ctx() + (int)k], &ctx_[k], sizeof(float));
+            side[L.in_hs() + (int)k] = hs_[k];
+            side[L.in_ls() + (int)k] = ls_[k];
+        }
+    }
+    // what a side out block must satisfy beside check_out: ord a permutation of the survivors, every state inside its table
+    void check_out(const int* out, const int* side, int Tc, int n_frames, int S, int S_lm) const {
+        check_out(out, Tc, n_frames);
+        const CtcPrefixResumeBiasLayout L{K_};
+        const int nh = out[0];
+        unsigned seen = 0;
+        for (int k = 0; k < nh; k++) {
+            const int q = side[L.out_ord() + k], hs = side[L.out_hs() + k], ls = side[L.out_ls() + k];
+            K2_REQUIRE(q >= 0 && q < nh && !(seen >> q & 1u), "ctc prefix stream: side out block: the final order is no permutation (entry %d = %d)", k, q);
+            seen |= 1u << q;
+            K2_REQUIRE(hs >= 0 && hs < (S >= 1 ? S : 1), "ctc prefix stream: side out block slot %d: hotword state %d outside [0, %d)", k, hs, S >= 1 ? S : 1);
+            K2_REQUIRE(!lm_on_ || (ls >= 0 && ls < S_lm), "ctc prefix stream: side out block slot %d: LM state %d outside [0, %d)", k, ls, S_lm);
+        }
+    }
+    // the out block and the side out block of a chunk (both checked by the caller)
+    void apply_out(const int* out, const int* side, int Tc, int n_frames) {
+        const CtcPrefixResumeBiasLayout L{K_};
+        const int nh = out[0];
+        std::vector<float> ctx((size_t)nh), fin((size_t)nh);
+        std::vector<int> hs((size_t)nh), ls((size_t)nh), ord((size_t)nh);
+        for (int k = 0; k < nh; k++) {
+            memcpy(&ctx[(size_t)k], &side[L.out_ctx() + k], sizeof(float));
+            memcpy(&fin[(size_t)k], &side[L.out_fin() + k], sizeof(float));
+            hs[(size_t)k] = side[L.out_hs() + k];
+            ls[(size_t)k] = side[L.out_ls() + k];
+            ord[(size_t)k] = side[L.out_ord() + k];
+        }
+        apply_slots(out, Tc, n_frames);
+        ctx_.swap(ctx); hs_.swap(hs); ls_.swap(ls); fin_.swap(fin); ord_.swap(ord);
+        materialise(slots_[(size_t)ord_[0]].path);
     }
 
     // the device search's in block (CtcPrefixResumeLayout{K, Tc}) for the next chunk of up to Tc frames
@@ -119,6 +195,15 @@ class CtcPrefixHistory {
     }
     // the device search's out block of that chunk of n_frames frames: the survivors in rank order
     void apply_out(const int* out, int Tc, int n_frames) {
+        apply_slots(out, Tc, n_frames);
+        ctx_.assign(slots_.size(), 0.f);
+        hs_.assign(slots_.size(), 0);
+        ls_.assign(slots_.size(), 0);
+        materialise(slots_[0].path);
+    }
+
+  private:
+    void apply_slots(const int* out, int Tc, int n_frames) {
         check_out(out, Tc, n_frames);
         const CtcPrefixResumeLayout L{K_, Tc};
         const int nh = out[0];
@@ -152,10 +237,8 @@ class CtcPrefixHistory {
         slots_.swap(nx);
         tot_.swap(tot);
         frames_ += n_frames;
-        materialise(slots_[0].path);
     }
 
-  private:
     // tokens_ / timestamps_ / token_log_probs_ := the path of node `to`; only the part past the longest prefix still shared with the
     // last result is rewritten (BeamHistory::materialise)
     void materialise(int to) {
@@ -186,6 +269,10 @@ class CtcPrefixHistory {
     PathTree path_;
     std::vector<Slot> slots_;
     std::vector<float> tot_;   // the slots' totals as the device formed them (empty before the first chunk: the start, 0)
+    std::vector<float> ctx_, fin_;   // biasing: per slot; fin_ / ord_ empty on an unbiased stream
+    std::vector<int> hs_, ls_, ord_;
+    uint64_t lm_serial_ = 0;
+    bool lm_on_ = false;
     long long frames_ = 0;
     int mat_path_ = 0;
     std::vector<int> mat_ids_;

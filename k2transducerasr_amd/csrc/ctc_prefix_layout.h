@@ -36,4 +36,23 @@ struct CtcPrefixResumeLayout {
     K2HIP_LAYOUT_HD int out_yp() const { return 1 + 9 * K + 2 * K * Tc; }
 };
 
+// The side blocks of the resumed BIASED search (k_ctc_prefix<true, true>), beside the blocks above, which keep every offset:
+//   in  (ints): [flags | ctx[K] (float bits) | hs[K] | ls[K]]   flags bit 0: this row runs the n-gram LM.  ctx is the accumulated
+//               context score WITH the pending bonus of a match under way (it may complete in the next chunk); slots in selection order
+//   out (ints): [ctx[K] | hs[K] | ls[K] | fin[K] (float bits) | ord[K]]   the survivors' values by slot; fin[q] = (tot + ctx) -
+//               pending[hs] of slot q; ord[i] = the slot that is i-th by (fin desc, slot asc)
+struct CtcPrefixResumeBiasLayout {
+    int K;
+    K2HIP_LAYOUT_HD int in_ints() const { return 1 + 3 * K; }
+    K2HIP_LAYOUT_HD int in_ctx() const { return 1; }
+    K2HIP_LAYOUT_HD int in_hs() const { return 1 + K; }
+    K2HIP_LAYOUT_HD int in_ls() const { return 1 + 2 * K; }
+    K2HIP_LAYOUT_HD int out_ints() const { return 5 * K; }
+    K2HIP_LAYOUT_HD int out_ctx() const { return 0; }
+    K2HIP_LAYOUT_HD int out_hs() const { return K; }
+    K2HIP_LAYOUT_HD int out_ls() const { return 2 * K; }
+    K2HIP_LAYOUT_HD int out_fin() const { return 3 * K; }
+    K2HIP_LAYOUT_HD int out_ord() const { return 4 * K; }
+};
+
 }  // namespace k2hip

@@ -833,40 +833,67 @@ void Engine::ctc_prefix_host(const float* log_probs, int R, int Tp, const int32_
 // the prefix search resumed from carried prefixes (streaming chunk; CtcPrefixResumeLayout{K, Tc} blocks)
 static_assert(kCtcPrefixHashSeed != 0, "the empty prefix's hash is the seed");
 void Engine::ctc_prefix_chunk_host(const float* log_probs, int B, int Tc, const int32_t* n_frames, int K, const int* in, int* out) {
+    ctc_prefix_chunk_impl(log_probs, B, Tc, n_frames, K, in, out, nullptr);
+}
+void Engine::ctc_prefix_chunk_host_bias(const float* log_probs, int B, int Tc, const int32_t* n_frames, int K, const int* in, int* out,
+                                        const CtcPrefixBiasIO& bias) {
+    K2_REQUIRE(bias.graphs && bias.side_in && bias.side_out, "ctc_prefix_beam_search_chunk: null side block");
+    ctc_prefix_chunk_impl(log_probs, B, Tc, n_frames, K, in, out, &bias);
+}
+void Engine::ctc_prefix_chunk_impl(const float* log_probs, int B, int Tc, const int32_t* n_frames, int K, const int* in, int* out,
+                                   const CtcPrefixBiasIO* bias) {
     const Config& cf = model_->cfg();
     if (!cf.ctc) failf(K2HIP_ERR_UNSUPPORTED, "ctc_prefix_beam_search_chunk: model_type '%s' has no CTC head", cf.model_type.c_str());
     K2_REQUIRE(log_probs && in && out, "ctc_prefix_beam_search_chunk: null argument");
     const CtcPrefixResumeLayout L{K, Tc};
     ctc_prefix_chunk_check_args(B, Tc, cf.V, n_frames, K, in, L.in_ints(), L.in_e(), L.in_rel());
-    // ONE upload [log_probs | in blocks | n_frames | status] and ONE download [status | out blocks]
+    // ONE upload [log_probs | in blocks | n_frames | biasing: side in blocks, graphs | status] and ONE download [status | out blocks |
+    // biasing: side out blocks]
+    const CtcPrefixResumeBiasLayout SL{K};
     const int64_t nb_lp = (int64_t)sizeof(float) * B * Tc * cf.V, nb_in = (int64_t)sizeof(int) * B * L.in_ints(), nb_nf = (int64_t)sizeof(int) * B,
                   nb_out = (int64_t)sizeof(int) * B * L.out_ints();
-    const int64_t o_in = align_up(nb_lp, 16), o_nf = align_up(o_in + nb_in, 16), o_st = align_up(o_nf + nb_nf, 16), in_bytes = o_st + 16;
+    const int64_t nb_si = bias ? (int64_t)sizeof(int) * B * SL.in_ints() : 0, nb_g = bias ? (int64_t)sizeof(BeamHwStream) * B : 0,
+                  nb_so = bias ? (int64_t)sizeof(int) * B * SL.out_ints() : 0;
+    const int64_t o_in = align_up(nb_lp, 16), o_nf = align_up(o_in + nb_in, 16), o_si = align_up(o_nf + nb_nf, 16), o_g = align_up(o_si + nb_si, 16),
+                  o_st = align_up(o_g + nb_g, 16), in_bytes = o_st + 16;
     K2_HIP(hipSetDevice(device_));
     char* stage = static_cast<char*>(pinned_in(in_bytes));
     memcpy(stage, log_probs, (size_t)nb_lp);
     memcpy(stage + o_in, in, (size_t)nb_in);
     if (n_frames) memcpy(stage + o_nf, n_frames, (size_t)nb_nf);
+    if (bias) {
+        memcpy(stage + o_si, bias->side_in, (size_t)nb_si);
+        memcpy(stage + o_g, bias->graphs, (size_t)nb_g);
+    }
     memset(stage + o_st, 0, 16);
     int* d_st = nullptr;
     run_sized([&](const Ctx& c) {
-        char* d = c.arena->take<char>(in_bytes + nb_out);
+        char* d = c.arena->take<char>(in_bytes + nb_out + nb_so);
         d_st = reinterpret_cast<int*>(d + o_st);
         if (!c.dry) K2_HIP(hipMemcpyAsync(d, stage, (size_t)in_bytes, hipMemcpyHostToDevice, c.stream));
-        CtcPrefixResumeArgs a;
+        CtcPrefixResumeBiasArgs a;
         a.log_probs = reinterpret_cast<const float*>(d); a.B = B; a.Tc = Tc; a.V = cf.V; a.beam = K;
         a.n_frames = n_frames ? reinterpret_cast<const int*>(d + o_nf) : nullptr;
         a.nodes = c.arena->take<int4>((int64_t)B * Tc * K);
         a.in = reinterpret_cast<const int*>(d + o_in);
         a.out = reinterpret_cast<int*>(d + in_bytes);
         a.status = d_st;
-        ctc_prefix_resume(c, a);
+        if (bias) {
+            a.hw_streams = reinterpret_cast<const BeamHwStream*>(d + o_g);
+            a.side_in = reinterpret_cast<const int*>(d + o_si);
+            a.side_out = reinterpret_cast<int*>(d + in_bytes + nb_out);
+            if (bias->lm) a.lm = lm_;
+            ctc_prefix_resume_biased(c, a);
+        } else {
+            ctc_prefix_resume(c, a);   // (no stream of the call is biased: the plain launch, unchanged)
+        }
     });
-    char* pin = static_cast<char*>(pinned(16 + nb_out));
-    K2_HIP(hipMemcpyAsync(pin, d_st, (size_t)(16 + nb_out), hipMemcpyDeviceToHost, stream_));
+    char* pin = static_cast<char*>(pinned(16 + nb_out + nb_so));
+    K2_HIP(hipMemcpyAsync(pin, d_st, (size_t)(16 + nb_out + nb_so), hipMemcpyDeviceToHost, stream_));
     K2_HIP(hipStreamSynchronize(stream_));
     if (*reinterpret_cast<int*>(pin)) failf(K2HIP_ERR_INVALID, "ctc_prefix_beam_search_chunk: an in block contradicts itself (its relations name tokens the chunk cannot walk)");
     memcpy(out, pin + 16, (size_t)nb_out);
+    if (bias) memcpy(bias->side_out, pin + 16 + nb_out, (size_t)nb_so);
 }
 
 // modified beam search instead of the greedy loop (set_beam(K) selects it for the fused / operator entry points)
@@ -2510,6 +2537,80 @@ void Engine::debug_op_host(const char* op, const int64_t* iargs, int n_iargs, vo
             run_sized([&](const Ctx& cc) {
                 a.nodes = cc.arena->take<int4>((int64_t)B * Tc * beam);
                 ctc_prefix_resume(cc, a);
+            });
+        } else if (name == "ctc_prefix_resume_bias") {
+            // the buffers of "ctc_prefix_resume" [0..4], side in [B][1 + 3K] (caller-supplied) [5], side out [B][5K] (out) [6], the nine table
+            //   buffers of "ctc_prefix_beam_bias" [7..15] (one set per call), row_graph [B] int32 [16]: 1 = the row reads the hotword tables,
+            //   0 = null tables for that row; ints B, Tc, V, beam, S, S_lm, A, start.  Tables and side in blocks are checked on the host first.
+            K2_REQUIRE(n_bufs == 17, "debug_op_run %s: %d buffers", op, n_bufs);
+            for (int k = 0; k < n_bufs; k++) P();
+            const int B = I(), Tc = I(), V = I(), beam = I(), S = I(), S_lm = I();
+            const long long A = L();
+            const int start = I();
+            K2_REQUIRE(B >= 1 && Tc >= 1 && V >= 1 && beam >= 1 && beam <= kMaxBeam, "debug_op_run %s: bad shape", op);
+            const CtcPrefixResumeLayout RL{beam, Tc};
+            const CtcPrefixResumeBiasLayout SL{beam};
+            K2_REQUIRE(!bufs[1] || buf_bytes[1] >= 4 * (int64_t)B, "debug_op_run %s: n_frames is too short", op);
+            K2_REQUIRE(bufs[2] && buf_bytes[2] >= 4 * (int64_t)B * RL.in_ints(), "debug_op_run %s: the in blocks are too short", op);
+            ctc_prefix_chunk_check_args(B, Tc, V, static_cast<const int32_t*>(bufs[1]), beam, static_cast<const int*>(bufs[2]), RL.in_ints(), RL.in_e(), RL.in_rel());
+            K2_REQUIRE(dev[0] && buf_bytes[0] >= 4 * (int64_t)B * Tc * V, "debug_op_run %s: log_probs is too short", op);
+            K2_REQUIRE(dev[3] && dev[4] && dev[6] && buf_bytes[3] >= 4 * (int64_t)B * RL.out_ints() && buf_bytes[4] >= 4 && buf_bytes[6] >= 4 * (int64_t)B * SL.out_ints(),
+                       "debug_op_run %s: the result buffers are too short", op);
+            K2_REQUIRE(bufs[5] && buf_bytes[5] >= 4 * (int64_t)B * SL.in_ints() && bufs[16] && buf_bytes[16] >= 4 * (int64_t)B,
+                       "debug_op_run %s: the side in blocks or row_graph are too short", op);
+            CtcPrefixBiasTables tb;
+            tb.V = V;
+            if (bufs[7] || bufs[8] || bufs[9]) {
+                K2_REQUIRE(S >= 1 && (int64_t)S * V <= kHotwordMaxEntries && bufs[7] && bufs[8] && bufs[9] && buf_bytes[7] >= 4 * (int64_t)S * V &&
+                               buf_bytes[8] >= 4 * (int64_t)S * V && buf_bytes[9] >= 4 * (int64_t)S,
+                           "debug_op_run %s: the hotword tables are incomplete or too short for S = %d", op, S);
+                tb.S = S;
+                tb.next = static_cast<const int32_t*>(bufs[7]); tb.bonus = static_cast<const float*>(bufs[8]); tb.pending = static_cast<const float*>(bufs[9]);
+            }
+            if (bufs[10] || bufs[14] || bufs[15]) {
+                K2_REQUIRE(S_lm >= 1 && A >= 0 && A <= kNgramMaxArcs && bufs[10] && bufs[14] && bufs[15] && buf_bytes[10] >= 16 * (int64_t)S_lm &&
+                               buf_bytes[14] >= 4 * (int64_t)V && buf_bytes[15] >= 4 * (int64_t)V &&
+                               (A == 0 || (bufs[11] && bufs[12] && bufs[13] && buf_bytes[11] >= 4 * A && buf_bytes[12] >= 4 * A && buf_bytes[13] >= 4 * A)),
+                           "debug_op_run %s: the LM tables are incomplete or too short for S = %d, A = %lld", op, S_lm, A);
+                tb.S_lm = S_lm; tb.A = A; tb.start = start;
+                tb.states = static_cast<const int32_t*>(bufs[10]);
+                tb.arc_tok = static_cast<const int32_t*>(bufs[11]); tb.arc_lp = static_cast<const float*>(bufs[12]); tb.arc_next = static_cast<const int32_t*>(bufs[13]);
+                tb.uni_lp = static_cast<const float*>(bufs[14]); tb.uni_next = static_cast<const int32_t*>(bufs[15]);
+            }
+            const int32_t* row_graph = static_cast<const int32_t*>(bufs[16]);
+            try {
+                ctc_prefix_bias_check_tables(tb);
+                for (int b = 0; b < B; b++) {
+                    K2_REQUIRE(row_graph[b] == 0 || (row_graph[b] == 1 && tb.next), "row_graph[%d] = %d (hotword tables: %s)", b, row_graph[b], tb.next ? "given" : "none");
+                    ctc_prefix_bias_check_side_in(static_cast<const int*>(bufs[5]) + (size_t)b * (size_t)SL.in_ints(), beam, row_graph[b] ? tb.S : 0,
+                                                  tb.states ? tb.S_lm : 0, b);
+                }
+            } catch (const Error& e) {   // (the caller's tables and blocks, not a shape the launcher refuses: INVALID)
+                failf(K2HIP_ERR_INVALID, "debug_op_run %s: %s", op, e.what());
+            }
+            std::vector<BeamHwStream> hws((size_t)B);
+            for (int b = 0; b < B; b++)
+                if (row_graph[b]) hws[(size_t)b] = BeamHwStream{static_cast<const int*>(dev[7]), static_cast<const float*>(dev[8]), static_cast<const float*>(dev[9])};
+            BeamHwStream* d_hws = nullptr;
+            K2_HIP(hipMalloc(&d_hws, sizeof(BeamHwStream) * (size_t)B));
+            d.base.push_back(reinterpret_cast<char*>(d_hws));
+            K2_HIP(copy_blocking(d_hws, hws.data(), sizeof(BeamHwStream) * (size_t)B, hipMemcpyHostToDevice));
+            CtcPrefixResumeBiasArgs a;
+            a.log_probs = static_cast<const float*>(dev[0]); a.B = B; a.Tc = Tc; a.V = V; a.beam = beam;
+            a.n_frames = static_cast<const int*>(dev[1]);
+            a.in = static_cast<const int*>(dev[2]); a.out = static_cast<int*>(dev[3]); a.status = static_cast<int*>(dev[4]);
+            a.side_in = static_cast<const int*>(dev[5]); a.side_out = static_cast<int*>(dev[6]);
+            a.hw_streams = d_hws;
+            if (tb.states) {
+                a.lm.states = static_cast<const int4*>(dev[10]);
+                a.lm.arc_tok = static_cast<const int*>(dev[11]); a.lm.arc_lp = static_cast<const float*>(dev[12]); a.lm.arc_next = static_cast<const int*>(dev[13]);
+                a.lm.uni_lp = static_cast<const float*>(dev[14]); a.lm.uni_next = static_cast<const int*>(dev[15]);
+                a.lm.start = start;
+            }
+            K2_HIP(hipMemsetAsync(dev[4], 0, sizeof(int), stream_));
+            run_sized([&](const Ctx& cc) {
+                a.nodes = cc.arena->take<int4>((int64_t)B * Tc * beam);
+                ctc_prefix_resume_biased(cc, a);
             });
         } else if (name == "basicnorm") {
             float *x = P(), *le = P(), *y = P();

@@ -175,6 +175,20 @@ class Engine {
     void online_step_beam_hw(const int* slots, const float* const* chunks, const long long* plens, const int* nchunks, int B, int K,
                              const int* beam_in, int* beam_out, const BeamHwIO& hw, const int* fifo_heads = nullptr);
     void beam_chunk_host_hw(const float* enc, int B, int Tp, int K, const int* beam_in, int* beam_out, const BeamHwIO& hw);
+    // The two entry points of the carried CTC prefix search with biasing (ctc_prefix_resume_biased): side blocks of their own beside the
+    // CtcPrefixResumeLayout blocks, all host memory -- graphs [B] (device tables; all null = that stream reads no graph), side_in [B]
+    // blocks of CtcPrefixResumeBiasLayout{K}.in_ints() ints (flag bit 0: the stream runs the LM), side_out [B] blocks of out_ints().
+    // lm: the tables of set_ngram_tables go along (false: null tables, whatever the flags say).  They ride in the same upload / download.
+    struct CtcPrefixBiasIO {
+        const BeamHwStream* graphs;
+        const int* side_in;
+        int* side_out;
+        bool lm = false;
+    };
+    void ctc_prefix_chunk_host_bias(const float* log_probs, int B, int Tc, const int32_t* n_frames, int K, const int* in, int* out,
+                                    const CtcPrefixBiasIO& bias);
+    void online_step_ctc_prefix_bias(const int* slots, const float* const* chunks, const long long* plens, const int* nchunks, int B, int K,
+                                     const int* cp_in, int* cp_out, const CtcPrefixBiasIO& bias, const int* fifo_heads = nullptr);
 
     void set_instrument(bool on) { instrument_ = on; }
     const std::vector<GemmLaunchRec>& gemm_log() const { return gemm_log_; }
@@ -366,7 +380,8 @@ class Engine {
                             const BeamHwIO* hw = nullptr);
     void beam_chunk_impl(const float* enc, int B, int Tp, int K, const int* beam_in, int* beam_out, const BeamHwIO* hw);
     struct OnlineBeamIO { int K; const int* in; int* out; const BeamHwIO* hw; };
-    struct OnlineCtcPrefixIO { int K; const int* in; int* out; };
+    struct OnlineCtcPrefixIO { int K; const int* in; int* out; const CtcPrefixBiasIO* bias = nullptr; };
+    void ctc_prefix_chunk_impl(const float* log_probs, int B, int Tc, const int32_t* n_frames, int K, const int* in, int* out, const CtcPrefixBiasIO* bias);
     void online_step_impl(const int* slots, const float* const* chunks, const long long* hyps, const long long* plens, const int* nchunks,
                           int B, int64_t* tokens, int32_t* ts, int32_t* n_tokens, const int* fifo_heads, const OnlineBeamIO* beam,
                           const OnlineCtcPrefixIO* cpx = nullptr);

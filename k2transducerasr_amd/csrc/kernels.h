@@ -780,6 +780,18 @@ struct CtcPrefixResumeArgs {
     int* status = nullptr;              // set to 1 when an in block contradicts itself (a bounded walk ran into its bound)
 };
 void ctc_prefix_resume(const Ctx& ctx, const CtcPrefixResumeArgs& a);
+// The resumed search with per-stream hotword graphs and the call's n-gram LM (include/k2hip.h "Biasing of the streaming CTC prefix beam
+// search").  The in / out blocks above are unchanged (tot there stays acoustic); the slots' (ctx, hs, ls) come in and the survivors'
+// (ctx, hs, ls, fin, ord) go out through side blocks of their own (CtcPrefixResumeBiasLayout{K}).  hw_streams [B] on the device: a row's
+// dense tables, all null = no graph for that row; a row runs the LM only if its side in block sets flag bit 0.  A row with neither is
+// bit for bit the plain resumed search.  The caller has checked every table and every carried hs / ls against its table.
+struct CtcPrefixResumeBiasArgs : CtcPrefixResumeArgs {
+    const BeamHwStream* hw_streams = nullptr;   // [B] (device)
+    BeamLm lm;
+    const int* side_in = nullptr;               // [B][in_ints]
+    int* side_out = nullptr;                    // [B][out_ints]
+};
+void ctc_prefix_resume_biased(const Ctx& ctx, const CtcPrefixResumeBiasArgs& a);
 
 // ---- streaming (online.hip): device-resident per-stream caches indexed by slot ------------------
 // ConvNeXt.streaming_forward's data movement in one launch: cat[b] = [cached_left_pad ; x], the cache advanced to x's frames Tc-3 .. Tc-1,

@@ -309,6 +309,17 @@ void Engine::online_step_ctc_prefix(const int* slots, const float* const* chunks
     OnlineCtcPrefixIO io{K, cp_in, cp_out};
     online_step_impl(slots, chunks, hyps.data(), plens, nchunks, B, nullptr, nullptr, nullptr, fifo_heads, nullptr, &io);
 }
+void Engine::online_step_ctc_prefix_bias(const int* slots, const float* const* chunks, const long long* plens, const int* nchunks, int B, int K,
+                                         const int* cp_in, int* cp_out, const CtcPrefixBiasIO& bias, const int* fifo_heads) {
+    K2_REQUIRE(K >= 1 && K <= kMaxBeam, "online ctc prefix search: beam %d out of range [1,%d]", K, kMaxBeam);
+    K2_REQUIRE(model_->cfg().ctc, "online ctc prefix search: the model has no CTC head");
+    K2_REQUIRE(bias.graphs && bias.side_in && bias.side_out, "online ctc prefix search: null side block");
+    const CtcPrefixResumeLayout L{K, online_frames_per_chunk()};
+    ctc_prefix_chunk_check_args(B, L.Tc, model_->cfg().V, nullptr, K, cp_in, L.in_ints(), L.in_e(), L.in_rel());
+    std::vector<long long> hyps(2 * (size_t)B, K2HIP_BLANK_ID);
+    OnlineCtcPrefixIO io{K, cp_in, cp_out, &bias};
+    online_step_impl(slots, chunks, hyps.data(), plens, nchunks, B, nullptr, nullptr, nullptr, fifo_heads, nullptr, &io);
+}
 void Engine::online_step_impl(const int* slots, const float* const* chunks, const long long* hyps, const long long* plens, const int* nchunks,
                               int B, int64_t* tokens, int32_t* ts, int32_t* n_tokens, const int* fifo_heads, const OnlineBeamIO* beam,
                               const OnlineCtcPrefixIO* cpx) {
@@ -336,9 +347,15 @@ void Engine::online_step_impl(const int* slots, const float* const* chunks, cons
     const CtcPrefixResumeLayout CL{cpx ? cpx->K : 1, Tp};
     K2_REQUIRE(!(beam && cpx), "internal: one search per tick");
     const int64_t nb_bin = beam ? (int64_t)sizeof(int) * RL.in_ints() * B : cpx ? (int64_t)sizeof(int) * CL.in_ints() * B : 0;
-    const int64_t nb_hst = bhw ? (int64_t)sizeof(int) * beam->K * B * (bhw->lm ? 2 : 1) : 0, nb_hg = bhw ? (int64_t)sizeof(BeamHwStream) * B : 0;
-    const int64_t nb_bout = beam ? (int64_t)sizeof(int) * RL.out_ints() * B + nb_hst : cpx ? (int64_t)sizeof(int) * CL.out_ints() * B : 0,
-                  o_hout = nb_bout - nb_hst;
+    // (a biased prefix search: its side in blocks and graph pointers ride where the beam search's states and graphs do, its side out
+    // blocks behind the out blocks)
+    const CtcPrefixBiasIO* cbias = cpx ? cpx->bias : nullptr;
+    const CtcPrefixResumeBiasLayout CSL{cpx ? cpx->K : 1};
+    const int64_t nb_cso = cbias ? (int64_t)sizeof(int) * CSL.out_ints() * B : 0;
+    const int64_t nb_hst = bhw ? (int64_t)sizeof(int) * beam->K * B * (bhw->lm ? 2 : 1) : cbias ? (int64_t)sizeof(int) * CSL.in_ints() * B : 0,
+                  nb_hg = bhw || cbias ? (int64_t)sizeof(BeamHwStream) * B : 0;
+    const int64_t nb_bout = beam ? (int64_t)sizeof(int) * RL.out_ints() * B + nb_hst : cpx ? (int64_t)sizeof(int) * CL.out_ints() * B + nb_cso : 0,
+                  o_hout = nb_bout - (beam ? nb_hst : nb_cso);
     const int64_t nb_x = from_fifo ? 0 : (int64_t)sizeof(float) * chunk_floats * B;
     const int64_t o_plen = align_up(nb_x, 16), o_hyp = o_plen + 8 * (int64_t)B, o_slots = o_hyp + 16 * (int64_t)B, o_chunks = o_slots + 4 * (int64_t)B,
                   o_heads = o_chunks + 4 * (int64_t)B, o_bin = align_up(o_heads + 4 * (int64_t)B, 16), o_hst = align_up(o_bin + nb_bin, 16),
@@ -357,6 +374,10 @@ void Engine::online_step_impl(const int* slots, const float* const* chunks, cons
     if (bhw) {
         memcpy(stage + o_hst, bhw->st_in, (size_t)nb_hst);
         memcpy(stage + o_hg, bhw->graphs, (size_t)nb_hg);
+    }
+    if (cbias) {
+        memcpy(stage + o_hst, cbias->side_in, (size_t)nb_hst);
+        memcpy(stage + o_hg, cbias->graphs, (size_t)nb_hg);
     }
     memset(stage + o_ovf, 0, 16);
     const int64_t nb_out = beam || cpx ? nb_bout : SearchOut::bytes_for(B, Tp) - 16;   // what follows the flag
@@ -395,13 +416,21 @@ void Engine::online_step_impl(const int* slots, const float* const* chunks, cons
             // OnlineRecognizer.ForwardBatchGreedySearchCTC (:220-313): per-chunk CTC collapse, prev_id reset per chunk
             // ... or, for streams that opted in, the prefix search resumed from their carried prefixes on the tick's log-probs
             if (cpx) {
-                CtcPrefixResumeArgs a;
+                CtcPrefixResumeBiasArgs a;
                 a.log_probs = enc; a.B = B; a.Tc = Tp; a.V = cf.V; a.beam = cpx->K;
                 a.nodes = ar.take<int4>((int64_t)B * Tp * cpx->K);
                 a.in = reinterpret_cast<const int*>(d_in + o_bin);
                 a.out = reinterpret_cast<int*>(d_out);
                 a.status = out.flag();
-                ctc_prefix_resume(c, a);
+                if (cbias) {
+                    a.hw_streams = reinterpret_cast<const BeamHwStream*>(d_in + o_hg);
+                    a.side_in = reinterpret_cast<const int*>(d_in + o_hst);
+                    a.side_out = reinterpret_cast<int*>(d_out + o_hout);
+                    if (cbias->lm) a.lm = lm_;
+                    ctc_prefix_resume_biased(c, a);
+                } else {
+                    ctc_prefix_resume(c, a);   // (no stream of the tick is biased: the plain launch, unchanged)
+                }
             } else {
                 ex = ctc_device(c, enc, B, Tp, out);
             }
@@ -428,7 +457,8 @@ void Engine::online_step_impl(const int* slots, const float* const* chunks, cons
         K2_HIP(hipEventRecord(ev_[5], stream_));
         K2_HIP(hipStreamSynchronize(stream_));
         if (*reinterpret_cast<int*>(pin)) failf(K2HIP_ERR_HIP, "online ctc prefix search: an in block contradicts itself");
-        memcpy(cpx->out, pin + 16, (size_t)nb_bout);
+        memcpy(cpx->out, pin + 16, (size_t)o_hout);
+        if (cbias) memcpy(cbias->side_out, pin + 16 + o_hout, (size_t)nb_cso);
     } else if (beam) {   // ONE download: [flag | out blocks]
         char* pin = static_cast<char*>(pinned(16 + nb_bout));
         K2_HIP(hipMemcpyAsync(pin, out.flag(), (size_t)(16 + nb_bout), hipMemcpyDeviceToHost, stream_));
