@@ -56,6 +56,8 @@ typedef struct k2hip_beam_stream k2hip_beam_stream_t;
 typedef struct k2hip_tokens k2hip_tokens_t;
 typedef struct k2hip_hotwords k2hip_hotwords_t;
 typedef struct k2hip_ngram_lm k2hip_ngram_lm_t;
+typedef struct k2hip_keywords k2hip_keywords_t;
+typedef struct k2hip_kws_stream k2hip_kws_stream_t;
 
 /* Fixed ids of the reference: OfflineModel.cs:18-20. */
 #define K2HIP_BLANK_ID 0
@@ -514,6 +516,74 @@ int32_t k2hip_transducer_align(k2hip_model_t* model, const float* enc_out, int32
 int32_t k2hip_offline_align_from_samples(k2hip_model_t* model, const float* const* samples, const int64_t* n_samples, int32_t B,
                                          const int64_t* ids, const int32_t* lens, int32_t* timestamps, float* token_log_probs,
                                          float* total_logp, float* best_logp, int32_t max_tokens, int32_t* Tprime_out);
+/* ---- Keyword spotting for transducer models: trie Viterbi on the lattice ---------------------------------------------------------
+ * No reference counterpart (its Utils/HotwordsHelper.cs has no call site): the semantics are the project's own, defined here and in
+ * DESIGN.md "Keyword spotting"; tests/kws_twin.py restates them in float64.
+ *
+ * Graph (k2hip_keywords_t): host only, needs no GPU and belongs to no model.  P >= 0 keywords, each a non-empty sequence of token ids
+ * in [0, vocab_size) without blank (0) and unk (2) (id 1 is allowed), each with a threshold in (0, 1].  Creation fails with
+ * K2HIP_ERR_INVALID, the message naming the keyword, for: an empty keyword, an id out of range, blank or unk inside a keyword, a
+ * duplicate, a threshold outside (0, 1] or not finite, more than K2HIP_KEYWORDS_MAX_STATES trie states.  A keyword may be a proper
+ * prefix of another: a terminal state may have children.  Trie states are numbered in insertion order, root = 0, parent(s) < s; state
+ * s has tok(s), depth(s), kw(s) = the keyword ending there or -1, and bar(s) = (float)depth(s) * logf(threshold): one float32 product,
+ * rounded once, on the host.  ctx(s) = the last context_size ids of [blank] * context_size + path(s).
+ *
+ * Arcs (the modified topology, at most one symbol per frame, exactly as in "Forced alignment and full-sum scoring"):
+ *   lp(t,s,.) = log_softmax(output_linear(tanh(enc[t] + decoder(ctx(s)))))
+ *   stay(t,s) = logaddexp(lp(t,s,blank), lp(t,s,unk));  for c != root: emit(t,c) = lp(t, parent(c), tok(c)).
+ *
+ * Token passing, per stream, all in float32.  Frames are numbered absolutely, t = 0, 1, .., since the stream's creation or reset.
+ * Every non-root state holds (a, start), initially a = -inf; the root always holds (0, t): a keyword may begin at any frame at no
+ * cost.  For every non-root c, from the values before frame t:
+ *   ve = a[parent(c)] + emit(t,c)   (a root parent contributes 0 and start = t),   vs = a[c] + stay(t,c),   a[c] <- max(ve, vs);
+ * the emit predecessor wins an exact float32 tie, `start` is inherited from the winner, and if both are -inf the state stays -inf.
+ *
+ * Detection, after the update of frame t: among the terminal states that were entered by their emit arc in this frame and have
+ * a[c] >= bar(c) (the average log-prob per keyword token reaches log threshold) the winner is the one of largest depth, then largest
+ * a, then smallest keyword index.  At most one event fires per frame: (keyword, start, end = t, sum_logp = a[c]).  After it every
+ * non-root state is set to -inf (overlapping matches are suppressed); the root restarts at t + 1.  The device compares and adds only;
+ * score = sum_logp / depth is computed by the host accessors.
+ *
+ * Streaming rule: after any chunking a stream's events and carried (a, start) are bit for bit those of one call over all frames so
+ * far.  n_frames[b] = 0 leaves stream b untouched.  Zero keywords (one state) is legal and never fires.
+ * Hotwords, the n-gram LM and the decoding method do not take part.  A CTC model: K2HIP_ERR_UNSUPPORTED.  Every transducer family is
+ * served: the search consumes encoder_out [B][T][joiner_dim] only.
+ *
+ * k2hip_keywords_create: keyword p = ids[off .. off + lens[p]), thresholds[p].  k2hip_keywords_load: a text file in the token-string
+ * form of k2hip_hotwords_load, one keyword per line (empty lines are skipped); an optional last field ":0.35" gives the line's threshold,
+ * default_threshold the others'; errors name the line.
+ * k2hip_kws_stream_create: a stream of `kw` on `model` (K2HIP_ERR_INVALID if the graph's vocab_size is not the model's).  The graph's
+ * decoder rows are computed once per (model, graph), kept on the device and shared by the streams of that pair; the stream keeps its own
+ * reference to the graph, so `kw` may be destroyed at once.  k2hip_kws_stream_reset: frame count 0, no tokens, no events.
+ * k2hip_kws_search_chunk: enc_out [B][Tc][joiner_dim] on the host, any Tc >= 1, n_frames [B] in [0, Tc] or NULL (= Tc); the streams
+ * (distinct, all of `model`) may walk different graphs.  New events are appended to each stream's list.  A failed call changes no
+ * stream.
+ * k2hip_kws_stream_get_events: the first min(cap, n) events into the arrays (each may be NULL), returns their number n or an error;
+ * score[i] = sum_logp[i] / (number of tokens of keyword[i]).
+ * k2hip_offline_spot_keywords_from_samples: samples -> fbank -> pad -> encoder as k2hip_offline_greedy_from_samples, encoder_out stays
+ * on the device; fresh streams of `kw`, every one searched over ALL Tprime frames of the padded batch.  Outputs [B][max_events] (each
+ * may be NULL), n_events [B]; K2HIP_ERR_CAPACITY if a stream has more events than max_events.  *Tprime_out (may be NULL) = the frame
+ * count. */
+#define K2HIP_KEYWORDS_MAX_STATES 1024
+int32_t k2hip_keywords_create(const int64_t* ids, const int32_t* lens, const float* thresholds, int32_t n_keywords, int32_t vocab_size,
+                              k2hip_keywords_t** out);
+int32_t k2hip_keywords_load(const k2hip_tokens_t* tokens, const char* path, float default_threshold, k2hip_keywords_t** out);
+int32_t k2hip_keywords_destroy(k2hip_keywords_t* kw);
+int32_t k2hip_keywords_num_states(const k2hip_keywords_t* kw);
+int32_t k2hip_keywords_num_keywords(const k2hip_keywords_t* kw);
+int32_t k2hip_kws_stream_create(k2hip_model_t* model, const k2hip_keywords_t* kw, k2hip_kws_stream_t** out);
+int32_t k2hip_kws_stream_destroy(k2hip_kws_stream_t* s);
+int32_t k2hip_kws_stream_reset(k2hip_kws_stream_t* s);
+int64_t k2hip_kws_stream_num_frames(const k2hip_kws_stream_t* s);
+int32_t k2hip_kws_search_chunk(k2hip_model_t* model, k2hip_kws_stream_t* const* streams, int32_t B, const float* enc_out, int32_t Tc,
+                               const int32_t* n_frames);
+int32_t k2hip_kws_stream_num_events(const k2hip_kws_stream_t* s);
+int32_t k2hip_kws_stream_get_events(const k2hip_kws_stream_t* s, int32_t* keyword, int32_t* start, int32_t* end, float* sum_logp, float* score,
+                                    int32_t cap);
+int32_t k2hip_kws_stream_clear_events(k2hip_kws_stream_t* s);
+int32_t k2hip_offline_spot_keywords_from_samples(k2hip_model_t* model, const k2hip_keywords_t* kw, const float* const* samples,
+                                                 const int64_t* n_samples, int32_t B, int32_t* keyword, int32_t* start, int32_t* end,
+                                                 float* sum_logp, float* score, int32_t* n_events, int32_t max_events, int32_t* Tprime_out);
 /* ---- CTC forced alignment and full-sum scoring of given transcripts (zipformer2ctc models) -------------------------------------
  * No reference counterpart: the reference's CTC path only searches (ForwardBatchGreedySearchCTC).  The semantics are the project's
  * own, defined here and in DESIGN.md "CTC forced alignment and full-sum scoring".

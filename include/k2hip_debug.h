@@ -163,6 +163,26 @@ int32_t k2hip_debug_gemm_run(k2hip_model_t* model, const float* A, const float* 
  *     never count.  Call it with no pipelined search in flight. */
 int32_t k2hip_debug_op_run(k2hip_model_t* model, const char* op, const int64_t* iargs, int32_t n_iargs, void* const* bufs,
                            const int64_t* buf_bytes, int32_t n_bufs, uint32_t out_mask);
+/* The two kernels of the keyword spotter (csrc/kws.hip; tests/test_kws_gpu.py) through k2hip_debug_op_run:
+ *   "trie_logprobs": bufs enc [B][Tp][J], n_frames [B] int32 (or null = Tp), the keywords' ids int64 back to back, lens [P] int32,
+ *     thresholds [P], stay, emit (out: every stream's plane [T_b][S], back to back; all streams walk the one graph, which the hook builds
+ *     and makes resident for the call); ints B, Tp, P.
+ *   "trie_dp": bufs n_frames [B] int32 (or null), parent, depth, kw [S] int32, bar [S] (taken as given), stay, emit (in, laid out as
+ *     above), a [B][S], start [B][S] int32 (in / out: the carried blocks of csrc/kws_ref.h), ev_keyword [B][Tp] int64, ev_start, ev_end
+ *     [B][Tp] int32, ev_sum [B][Tp], n_events [B] int32 (out; row b holds n_events[b] events); ints B, Tp, S. */
+
+/* ---- keyword spotting (k2hip.h "Keyword spotting") ---------------------------------------------- */
+/* the carried block of a keyword stream: a [S] and start [S] (S = k2hip_keywords_num_states of its graph).  State 0 is the root:
+ * a = 0, start = the stream's frame count.  A state without a token holds (-inf, -1). */
+int32_t k2hip_debug_kws_stream_get_state(const k2hip_kws_stream_t* s, float* a, int32_t* start, int32_t cap);
+/* the graph's tables, each [S] (any may be NULL): what tests/test_kws.py holds against its Python restatement */
+int32_t k2hip_debug_keywords_get_tables(const k2hip_keywords_t* kw, int32_t* parent, int32_t* tok, int32_t* depth, int32_t* keyword, float* bar,
+                                        int32_t cap);
+/* the float32 host reference of the token passing (csrc/kws_ref.h), no GPU: one stream, planes stay / emit [T][S], the carried block
+ * a / start [S] updated in place, events into ev_* [cap] (K2HIP_ERR_CAPACITY beyond), *n_events their number */
+int32_t k2hip_debug_kws_ref_dp(const int32_t* parent, const int32_t* depth, const int32_t* keyword, const float* bar, int32_t S, const float* stay,
+                               const float* emit, int32_t T, float* a, int32_t* start, int32_t* ev_keyword, int32_t* ev_start, int32_t* ev_end,
+                               float* ev_sum, int32_t cap, int32_t* n_events);
 
 /* ---- GEMM tuning ------------------------------------------------------------------------------- */
 /* time `iters` launches of a shape / configuration on pseudo-random operands (tools/gemm_lab.py, gemm_tune.py) */

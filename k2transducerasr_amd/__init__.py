@@ -14,6 +14,8 @@ from .binding import (  # noqa: F401
     BeamStream,
     CtcPrefixStream,
     Hotwords,
+    Keywords,
+    KeywordStream,
     NgramLm,
     K2HipError,
     Model,
@@ -34,6 +36,8 @@ __all__ = [
     "BeamStream",
     "CtcPrefixStream",
     "Hotwords",
+    "Keywords",
+    "KeywordStream",
     "NgramLm",
     "K2HipError",
     "Model",

@@ -342,6 +342,161 @@ class Hotwords:
             pass
 
 
+class Keywords:
+    """The keyword graph of the transducer keyword spotter (k2hip_keywords_t; include/k2hip.h "Keyword spotting"): a trie of token-id
+    keywords, each with a threshold in (0, 1] on the geometric mean of its tokens' probabilities.  Host only: built without a GPU and
+    without a model.  `thresholds`: one number for all keywords or one per keyword.  Keywords.load reads a pre-tokenised text file
+    through a TokenTable (an optional last field ":0.35" is the line's threshold)."""
+
+    def _bind(self):
+        self._h = None
+        self._L = L = load_library()
+        L.k2hip_keywords_create.argtypes = [lp, ip, fp, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
+        L.k2hip_keywords_load.argtypes = [C.c_void_p, C.c_char_p, C.c_float, C.POINTER(C.c_void_p)]
+        L.k2hip_keywords_destroy.argtypes = [C.c_void_p]
+        L.k2hip_keywords_num_states.argtypes = [C.c_void_p]
+        L.k2hip_keywords_num_keywords.argtypes = [C.c_void_p]
+        L.k2hip_debug_keywords_get_tables.argtypes = [C.c_void_p, ip, ip, ip, ip, fp, C.c_int32]
+        return L
+
+    def __init__(self, keywords, thresholds, vocab_size: int):
+        L = self._bind()
+        keywords = [list(k) for k in keywords]
+        thr = np.broadcast_to(np.asarray(thresholds, np.float32), (len(keywords),)) if keywords else np.zeros(0, np.float32)
+        ids = np.ascontiguousarray([t for k in keywords for t in k] or [0], dtype=np.int64)
+        lens = np.ascontiguousarray([len(k) for k in keywords] or [0], dtype=np.int32)
+        thr = np.ascontiguousarray(thr if thr.size else [1.0], dtype=np.float32)
+        h = C.c_void_p()
+        rc = L.k2hip_keywords_create(_l(ids), _i(lens), _f(thr), len(keywords), int(vocab_size), C.byref(h))
+        if rc != 0:
+            raise K2HipError(rc, L.k2hip_last_error().decode())
+        self._h = h
+
+    @classmethod
+    def load(cls, tokens: "TokenTable", path: str, threshold: float) -> "Keywords":
+        kw = cls.__new__(cls)
+        L = kw._bind()
+        h = C.c_void_p()
+        rc = L.k2hip_keywords_load(tokens._h, path.encode(), float(threshold), C.byref(h))
+        if rc != 0:
+            raise K2HipError(rc, L.k2hip_last_error().decode())
+        kw._h = h
+        return kw
+
+    @property
+    def num_states(self) -> int:
+        return self._L.k2hip_keywords_num_states(self._h)
+
+    @property
+    def num_keywords(self) -> int:
+        return self._L.k2hip_keywords_num_keywords(self._h)
+
+    def tables(self) -> dict:
+        """the trie as the library built it: parent, tok, depth, kw (int32 [S]) and bar (float32 [S])"""
+        S = self.num_states
+        out = dict(parent=np.zeros(S, np.int32), tok=np.zeros(S, np.int32), depth=np.zeros(S, np.int32), kw=np.zeros(S, np.int32),
+                   bar=np.zeros(S, np.float32))
+        rc = self._L.k2hip_debug_keywords_get_tables(self._h, _i(out["parent"]), _i(out["tok"]), _i(out["depth"]), _i(out["kw"]), _f(out["bar"]), S)
+        if rc != 0:
+            raise K2HipError(rc, self._L.k2hip_last_error().decode())
+        return out
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.k2hip_keywords_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _bind_kws(L):
+    if getattr(L, "_kws_bound", False):
+        return
+    L.k2hip_kws_stream_create.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
+    L.k2hip_kws_stream_destroy.argtypes = [C.c_void_p]
+    L.k2hip_kws_stream_reset.argtypes = [C.c_void_p]
+    L.k2hip_kws_stream_num_frames.argtypes = [C.c_void_p]
+    L.k2hip_kws_stream_num_frames.restype = C.c_int64
+    L.k2hip_kws_stream_num_events.argtypes = [C.c_void_p]
+    L.k2hip_kws_stream_get_events.argtypes = [C.c_void_p, ip, ip, ip, fp, fp, C.c_int32]
+    L.k2hip_kws_stream_clear_events.argtypes = [C.c_void_p]
+    L.k2hip_kws_search_chunk.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, fp, C.c_int32, ip]
+    L.k2hip_debug_kws_stream_get_state.argtypes = [C.c_void_p, fp, ip, C.c_int32]
+    L.k2hip_offline_spot_keywords_from_samples.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(fp), lp, C.c_int32, ip, ip, ip, fp, fp, ip, C.c_int32, ip]
+    L._kws_bound = True
+
+
+def _kws_events(k, st, en, sm, sc, n):
+    return [dict(keyword=int(k[i]), start=int(st[i]), end=int(en[i]), sum_logp=np.float32(sm[i]), score=np.float32(sc[i])) for i in range(n)]
+
+
+class KeywordStream:
+    """One audio stream watched for the keywords of a graph (k2hip_kws_stream_*; include/k2hip.h "Keyword spotting"): the tokens carried
+    across chunks and the events found so far.  The streaming recipe is OnlineProj.encoder_proj followed by
+    KeywordStream.search_chunk.  An event is dict(keyword, start, end, sum_logp, score): frames are absolute since creation or reset."""
+
+    def __init__(self, model: "Model", keywords: Keywords):
+        self._m = model
+        self._L = model._L
+        _bind_kws(self._L)
+        h = C.c_void_p()
+        model._chk(self._L.k2hip_kws_stream_create(model.handle, keywords._h, C.byref(h)))
+        self._h = h
+        self._S = keywords.num_states
+        model._children.add(self)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.k2hip_kws_stream_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self):
+        self._m._chk(self._L.k2hip_kws_stream_reset(self._h))
+
+    def num_frames(self) -> int:
+        return int(self._L.k2hip_kws_stream_num_frames(self._h))
+
+    @staticmethod
+    def search_chunk(streams: Sequence["KeywordStream"], enc_out, n_frames=None):
+        """continue every stream's search over enc_out [B, Tc, J] (k2hip_kws_search_chunk); n_frames [B]: the frames of each stream
+        that count (default all Tc; 0 leaves a stream untouched).  The streams may walk different graphs."""
+        m = streams[0]._m
+        e = _f32(enc_out)
+        B = len(streams)
+        if e.ndim != 3 or e.shape[0] != B:
+            raise ValueError(f"search_chunk: enc_out {e.shape} for {B} streams")
+        nf = None if n_frames is None else np.ascontiguousarray(n_frames, dtype=np.int32)
+        arr = (C.c_void_p * B)(*[s._h.value for s in streams])
+        m._chk(m._L.k2hip_kws_search_chunk(m.handle, arr, B, _f(e), e.shape[1], None if nf is None else _i(nf)))
+
+    def events(self, clear: bool = False):
+        n = self._L.k2hip_kws_stream_num_events(self._h)
+        k, st, en = (np.zeros(max(n, 1), np.int32) for _ in range(3))
+        sm, sc = (np.zeros(max(n, 1), np.float32) for _ in range(2))
+        got = self._L.k2hip_kws_stream_get_events(self._h, _i(k), _i(st), _i(en), _f(sm), _f(sc), n)
+        if got < 0:
+            raise K2HipError(got, self._L.k2hip_last_error().decode())
+        if clear:
+            self._m._chk(self._L.k2hip_kws_stream_clear_events(self._h))
+        return _kws_events(k, st, en, sm, sc, n)
+
+    def state(self):
+        """the carried block (a float32 [S], start int32 [S]) -- the debug header's view, for the chunking tests"""
+        a, st = np.zeros(self._S, np.float32), np.zeros(self._S, np.int32)
+        self._m._chk(self._L.k2hip_debug_kws_stream_get_state(self._h, _f(a), _i(st), self._S))
+        return a, st
+
+
 class Model:
     """One model replica on one GPU (k2hip_model_t): the IOfflineProj operators."""
 
@@ -716,6 +871,38 @@ class Model:
                                                            C.byref(tp)))
         return self._align_result(lens, ts, yp, tot, best)
 
+    # ---- keyword spotting (k2hip.h "Keyword spotting ...")
+    def spot_keywords(self, enc_out, keywords: "Keywords", n_frames=None):
+        """fresh keyword streams over a host encoder_out [B,T',J] in one chunk -> per stream the list of events
+        dict(keyword, start, end, sum_logp, score)"""
+        e = _f32(enc_out)
+        streams = [KeywordStream(self, keywords) for _ in range(e.shape[0])]
+        try:
+            KeywordStream.search_chunk(streams, e, n_frames)
+            return [s.events() for s in streams]
+        finally:
+            for s in streams:
+                s.close()
+
+    def spot_keywords_samples(self, samples: Sequence[np.ndarray], keywords: "Keywords", max_events: Optional[int] = None):
+        """k2hip_offline_spot_keywords_from_samples: samples -> fbank -> pad -> encoder on the device, then spot_keywords() over all T'
+        frames of the padded batch"""
+        _bind_kws(self._L)
+        ss = [_f32(s).reshape(-1) for s in samples]
+        B = len(ss)
+        ptrs = (fp * B)(*[_f(s) for s in ss])
+        ns = np.array([s.size for s in ss], np.int64)
+        if max_events is None:   # at most one event per frame
+            max_events = max(1, self.encoder_out_frames(int(self.fbank_num_frames(int(ns.max()))) + 19))
+        me = max(max_events, 1)
+        k, st, en = (np.zeros((B, me), np.int32) for _ in range(3))
+        sm, sc = (np.zeros((B, me), np.float32) for _ in range(2))
+        n = np.zeros(B, np.int32)
+        tp = C.c_int32(0)
+        self._chk(self._L.k2hip_offline_spot_keywords_from_samples(self._h, keywords._h, ptrs, _l(ns), B, _i(k), _i(st), _i(en), _f(sm), _f(sc),
+                                                                   _i(n), max_events, C.byref(tp)))
+        return [_kws_events(k[b], st[b], en[b], sm[b], sc[b], int(n[b])) for b in range(B)]
+
     # ---- CTC forced alignment and full-sum scoring (k2hip.h "CTC forced alignment and full-sum scoring ...")
     @staticmethod
     def _ctc_align_result(lens, ts, en, yp, tot, best):
@@ -971,6 +1158,10 @@ class OfflineRecognizer:
         if self.model.meta("model_type") == "zipformer2ctc":
             return self.model.ctc_align_samples(samples, targets)
         return self.model.align_samples(samples, targets)
+
+    def spot_keywords(self, samples: Sequence[np.ndarray], keywords: "Keywords"):
+        """the events of `keywords` in samples[b] (Model.spot_keywords_samples; transducer models; no reference counterpart)"""
+        return self.model.spot_keywords_samples(samples, keywords)
 
 
 # ============================== streaming: OnlineStream / OnlineRecognizer ===============================

@@ -16,6 +16,8 @@
 #include "beam_hist.h"
 #include "ctc_prefix_hist.h"
 #include "hotwords.h"
+#include "keywords.h"
+#include "kws_ref.h"
 #include "ngram_lm.h"
 #include "../../include/k2hip_debug.h"
 
@@ -87,6 +89,16 @@ struct HwResident {
     BeamHwStream tables;
     std::shared_ptr<const std::vector<float>> pending;
 };
+// A keyword graph resident on a model's device for the keyword streams created on it (k2hip_kws_stream_create): the decoder rows of
+// the trie's contexts and its tables in ONE allocation, shared by the streams of that (model, graph) and released the way HwResident is.
+// It also holds the graph itself: a stream outlives the handle it was created from.
+struct KwResident {
+    uint64_t serial = 0;
+    k2hip_model* owner = nullptr;
+    void* dev = nullptr;
+    KwsGraphDev tables;
+    std::shared_ptr<const KeywordGraph> graph;
+};
 static std::mutex g_hw_mu;
 static std::atomic<uint64_t> g_hw_serial{0};
 
@@ -112,6 +124,8 @@ struct k2hip_model {
     // the graphs attached to this model's streams (HwResident), by serial number; hw_uploads counts the uploads (k2hip_debug.h)
     std::map<uint64_t, std::weak_ptr<HwResident>> hw_cache;
     int hw_uploads = 0;
+    // the keyword graphs resident for this model's keyword streams (KwResident), by serial number
+    std::map<uint64_t, std::weak_ptr<KwResident>> kw_cache;
     k2hip_model(const char* path, const char* ov, int dev) : engine(path, ov, dev) {}
     ~k2hip_model() {
         {
@@ -128,6 +142,18 @@ struct k2hip_model {
                     r->tables = BeamHwStream{};
                 }
             hw_cache.clear();
+            for (auto& kv : kw_cache)
+                if (auto r = kv.second.lock()) {
+                    try {
+                        engine.synchronize();
+                        engine.dev_free(r->dev);
+                    } catch (...) {
+                    }
+                    r->dev = nullptr;
+                    r->owner = nullptr;
+                    r->tables = KwsGraphDev{};
+                }
+            kw_cache.clear();
         }
         if (hw_dev) {
             try {
@@ -700,6 +726,296 @@ int32_t k2hip_set_hotwords(k2hip_model_t* model, const k2hip_hotwords_t* hw) {
         void* old = model->hw_dev;
         model->hw_dev = fresh;
         if (old) e.dev_free(old);
+    });
+}
+// ---- keyword spotting (keywords.cpp, kws.hip) -----------------------------------------------------------
+struct k2hip_keywords {
+    std::shared_ptr<const KeywordGraph> graph;
+    uint64_t serial = ++g_hw_serial;   // the graph's identity for the models' caches (a handle's address can be reused)
+};
+struct k2hip_kws_stream {
+    k2hip_model* model;
+    std::shared_ptr<KwResident> res;
+    std::vector<float> a;            // the carried block (kws_ref.h)
+    std::vector<int32_t> start;
+    std::vector<KwsRefEvent> events;
+    void fresh() {
+        const int S = res->graph->num_states();
+        a.resize((size_t)S);
+        start.resize((size_t)S);
+        kws_fresh_state(S, a.data(), start.data());
+        events.clear();
+    }
+};
+// last reference gone: free the resident block unless the model already did
+static void kw_resident_release(KwResident* r) {
+    {
+        std::lock_guard<std::mutex> g(g_hw_mu);
+        if (r->owner) {
+            auto it = r->owner->kw_cache.find(r->serial);
+            if (it != r->owner->kw_cache.end() && it->second.expired()) r->owner->kw_cache.erase(it);
+            try {
+                Engine& e = r->owner->engine;
+                EngineLock lk(e);
+                e.synchronize();
+                e.dev_free(r->dev);
+            } catch (...) {
+            }
+        }
+    }
+    delete r;
+}
+// the model's resident copy of `kw`: the cached one, or a fresh upload (its decoder rows are computed here, once)
+static std::shared_ptr<KwResident> kw_resident_get(k2hip_model* model, const k2hip_keywords* kw, const char* who) {
+    Engine& e = model->engine;
+    const Config& cf = e.model().cfg();
+    if (cf.ctc) failf(K2HIP_ERR_UNSUPPORTED, "%s: a CTC model has no transducer lattice", who);
+    K2_REQUIRE(kw->graph->vocab_size() == cf.V, "%s: the graph was built for vocab_size %d, the model has %d", who, kw->graph->vocab_size(), cf.V);
+    std::lock_guard<std::mutex> g(g_hw_mu);
+    auto it = model->kw_cache.find(kw->serial);
+    if (it != model->kw_cache.end())
+        if (auto r = it->second.lock()) return r;
+    std::unique_ptr<KwResident> fresh(new KwResident());
+    fresh->serial = kw->serial;
+    fresh->graph = kw->graph;
+    {
+        EngineLock lk(e);
+        fresh->dev = e.kws_graph_upload(*kw->graph, &fresh->tables);
+    }
+    fresh->owner = model;
+    std::shared_ptr<KwResident> r(fresh.release(), kw_resident_release);
+    model->kw_cache[kw->serial] = r;
+    return r;
+}
+int32_t k2hip_keywords_create(const int64_t* ids, const int32_t* lens, const float* thresholds, int32_t n_keywords, int32_t vocab_size,
+                              k2hip_keywords_t** out) {
+    return guard([&] {
+        NEED(out);
+        *out = nullptr;
+        auto g = std::make_shared<const KeywordGraph>(ids, lens, thresholds, n_keywords, vocab_size);
+        *out = new k2hip_keywords{std::move(g)};
+    });
+}
+int32_t k2hip_keywords_load(const k2hip_tokens_t* tokens, const char* path, float default_threshold, k2hip_keywords_t** out) {
+    return guard([&] {
+        NEED(tokens); NEED(path); NEED(out);
+        *out = nullptr;
+        const int V = token_table_size(tokens->tab);
+        std::map<std::string, int> id_of;
+        for (int i = V - 1; i >= 0; i--) id_of[token_table_symbol(*tokens->tab, i)] = i;   // (a repeated symbol: its first line)
+        std::ifstream f(path, std::ios::binary);
+        if (!f) failf(K2HIP_ERR_IO, "cannot open keywords file %s", path);
+        std::vector<int64_t> ids;
+        std::vector<int32_t> lens;
+        std::vector<float> thr;
+        std::vector<int> line_of;
+        std::string line;
+        for (int ln = 1; std::getline(f, line); ln++) {
+            std::vector<std::string> fields;
+            size_t i = 0;
+            while (i < line.size()) {
+                while (i < line.size() && (line[i] == ' ' || line[i] == '\t' || line[i] == '\r')) i++;
+                size_t j = i;
+                while (j < line.size() && line[j] != ' ' && line[j] != '\t' && line[j] != '\r') j++;
+                if (j == i) break;
+                fields.push_back(line.substr(i, j - i));
+                i = j;
+            }
+            if (fields.empty()) continue;
+            float th = default_threshold;
+            // a last field ":<number>" that is no token of the table is the line's threshold
+            const std::string& last = fields.back();
+            if (last.size() > 1 && last[0] == ':' && id_of.find(last) == id_of.end()) {
+                char* endp = nullptr;
+                th = strtof(last.c_str() + 1, &endp);
+                if (endp == last.c_str() + 1 || *endp != '\0')
+                    failf(K2HIP_ERR_INVALID, "keywords file %s line %d: threshold '%s' is not a number", path, ln, last.c_str());
+                fields.pop_back();
+            }
+            for (const std::string& sym : fields) {
+                auto it = id_of.find(sym);
+                if (it == id_of.end()) failf(K2HIP_ERR_INVALID, "keywords file %s line %d: token '%s' is not in the token table", path, ln, sym.c_str());
+                ids.push_back(it->second);
+            }
+            lens.push_back((int32_t)fields.size());
+            thr.push_back(th);
+            line_of.push_back(ln);
+        }
+        auto g = std::make_shared<const KeywordGraph>(ids.data(), lens.data(), thr.data(), (int)lens.size(), V, "line", line_of.data());
+        *out = new k2hip_keywords{std::move(g)};
+    });
+}
+int32_t k2hip_keywords_destroy(k2hip_keywords_t* kw) {
+    return guard([&] { delete kw; });
+}
+int32_t k2hip_keywords_num_states(const k2hip_keywords_t* kw) { return kw ? kw->graph->num_states() : -1; }
+int32_t k2hip_keywords_num_keywords(const k2hip_keywords_t* kw) { return kw ? kw->graph->num_keywords() : -1; }
+int32_t k2hip_debug_keywords_get_tables(const k2hip_keywords_t* kw, int32_t* parent, int32_t* tok, int32_t* depth, int32_t* keyword, float* bar,
+                                        int32_t cap) {
+    return guard([&] {
+        NEED(kw);
+        const KeywordGraph& g = *kw->graph;
+        const size_t S = (size_t)g.num_states();
+        if ((int64_t)S > cap) failf(K2HIP_ERR_CAPACITY, "the graph has %zu states", S);
+        if (parent) memcpy(parent, g.parent().data(), 4 * S);
+        if (tok) memcpy(tok, g.tok().data(), 4 * S);
+        if (depth) memcpy(depth, g.depth().data(), 4 * S);
+        if (keyword) memcpy(keyword, g.kw().data(), 4 * S);
+        if (bar) memcpy(bar, g.bar().data(), 4 * S);
+    });
+}
+int32_t k2hip_debug_kws_ref_dp(const int32_t* parent, const int32_t* depth, const int32_t* keyword, const float* bar, int32_t S, const float* stay,
+                               const float* emit, int32_t T, float* a, int32_t* start, int32_t* ev_keyword, int32_t* ev_start, int32_t* ev_end,
+                               float* ev_sum, int32_t cap, int32_t* n_events) {
+    return guard([&] {
+        NEED(parent); NEED(depth); NEED(keyword); NEED(bar); NEED(a); NEED(start); NEED(n_events);
+        K2_REQUIRE(S >= 1 && T >= 0 && cap >= 0, "kws_ref_dp: bad shape S=%d T=%d", S, T);
+        K2_REQUIRE(T == 0 || S == 1 || (stay && emit), "kws_ref_dp: null planes");
+        for (int s = 1; s < S; s++) K2_REQUIRE(parent[s] >= 0 && parent[s] < s, "kws_ref_dp: parent(%d) = %d", s, parent[s]);
+        std::vector<KwsRefEvent> ev;
+        kws_dp_ref(parent, depth, keyword, bar, S, stay, emit, T, a, start, &ev);
+        *n_events = (int32_t)ev.size();
+        if ((int64_t)ev.size() > cap) failf(K2HIP_ERR_CAPACITY, "kws_ref_dp: %zu events", ev.size());
+        for (size_t i = 0; i < ev.size(); i++) {
+            if (ev_keyword) ev_keyword[i] = ev[i].keyword;
+            if (ev_start) ev_start[i] = ev[i].start;
+            if (ev_end) ev_end[i] = ev[i].end;
+            if (ev_sum) ev_sum[i] = ev[i].sum_logp;
+        }
+    });
+}
+int32_t k2hip_kws_stream_create(k2hip_model_t* model, const k2hip_keywords_t* kw, k2hip_kws_stream_t** out) {
+    return guard([&] {
+        NEED(model); NEED(kw); NEED(out);
+        *out = nullptr;
+        std::unique_ptr<k2hip_kws_stream> s(new k2hip_kws_stream{model, kw_resident_get(model, kw, "kws_stream_create"), {}, {}, {}});
+        s->fresh();
+        *out = s.release();
+    });
+}
+int32_t k2hip_kws_stream_destroy(k2hip_kws_stream_t* s) {
+    return guard([&] { delete s; });
+}
+int32_t k2hip_kws_stream_reset(k2hip_kws_stream_t* s) {
+    return guard([&] {
+        NEED(s);
+        s->fresh();
+    });
+}
+int64_t k2hip_kws_stream_num_frames(const k2hip_kws_stream_t* s) { return s ? (int64_t)s->start[0] : -1; }
+int32_t k2hip_kws_stream_num_events(const k2hip_kws_stream_t* s) { return s ? (int32_t)s->events.size() : -1; }
+// the events of a list through the getters' common rules; depth_of: the keyword's number of tokens
+static int32_t kws_events_out(const KeywordGraph& g, const KwsRefEvent* ev, size_t n, int32_t* keyword, int32_t* start, int32_t* end, float* sum_logp,
+                              float* score, size_t cap) {
+    const size_t m = std::min(n, cap);
+    for (size_t i = 0; i < m; i++) {
+        if (keyword) keyword[i] = ev[i].keyword;
+        if (start) start[i] = ev[i].start;
+        if (end) end[i] = ev[i].end;
+        if (sum_logp) sum_logp[i] = ev[i].sum_logp;
+        if (score) score[i] = ev[i].sum_logp / (float)g.depth()[(size_t)g.terminal()[(size_t)ev[i].keyword]];
+    }
+    return (int32_t)n;
+}
+int32_t k2hip_kws_stream_get_events(const k2hip_kws_stream_t* s, int32_t* keyword, int32_t* start, int32_t* end, float* sum_logp, float* score,
+                                    int32_t cap) {
+    int32_t count = 0;
+    const int32_t rc = guard([&] {
+        NEED(s);
+        K2_REQUIRE(cap >= 0, "kws_stream_get_events: cap %d", cap);
+        count = kws_events_out(*s->res->graph, s->events.data(), s->events.size(), keyword, start, end, sum_logp, score, (size_t)cap);
+    });
+    return rc < 0 ? rc : count;
+}
+int32_t k2hip_kws_stream_clear_events(k2hip_kws_stream_t* s) {
+    return guard([&] {
+        NEED(s);
+        s->events.clear();
+    });
+}
+int32_t k2hip_debug_kws_stream_get_state(const k2hip_kws_stream_t* s, float* a, int32_t* start, int32_t cap) {
+    return guard([&] {
+        NEED(s);
+        if ((int64_t)s->a.size() > cap) failf(K2HIP_ERR_CAPACITY, "the stream's graph has %zu states", s->a.size());
+        if (a) memcpy(a, s->a.data(), sizeof(float) * s->a.size());
+        if (start) memcpy(start, s->start.data(), sizeof(int32_t) * s->start.size());
+    });
+}
+// the events of row b of a chunk result behind `into`
+static void kws_take_events(const Engine::KwsResult& r, int b, std::vector<KwsRefEvent>* into) {
+    for (int i = 0; i < r.n[(size_t)b]; i++) {
+        const size_t o = (size_t)b * r.mt + i;
+        into->push_back(KwsRefEvent{(int32_t)r.keyword[o], r.start[o], r.end[o], r.sum[o]});
+    }
+}
+int32_t k2hip_kws_search_chunk(k2hip_model_t* model, k2hip_kws_stream_t* const* streams, int32_t B, const float* enc_out, int32_t Tc,
+                               const int32_t* n_frames) {
+    return guard([&] {
+        NEED(model); NEED(streams); NEED(enc_out);
+        K2_REQUIRE(B > 0 && Tc >= 1, "kws_search_chunk: bad shape B=%d Tc=%d", B, Tc);
+        Engine& e = model->engine;
+        if (e.model().cfg().ctc) failf(K2HIP_ERR_UNSUPPORTED, "kws_search_chunk: a CTC model has no transducer lattice");
+        std::vector<Engine::KwsIO> io((size_t)B);
+        for (int b = 0; b < B; b++) {
+            k2hip_kws_stream* s = streams[b];
+            K2_REQUIRE(s != nullptr, "kws_search_chunk: stream %d is null", b);
+            K2_REQUIRE(s->model == model, "kws_search_chunk: stream %d belongs to another model", b);
+            for (int c = 0; c < b; c++) K2_REQUIRE(streams[c] != s, "kws_search_chunk: streams %d and %d are the same stream", c, b);
+            const int T = n_frames ? n_frames[b] : Tc;
+            K2_REQUIRE(T >= 0 && T <= Tc, "kws_search_chunk: stream %d: n_frames %d outside [0, %d]", b, T, Tc);
+            K2_REQUIRE((int64_t)s->start[0] + T <= INT32_MAX, "kws_search_chunk: stream %d has run out of frame numbers; reset it", b);
+            io[(size_t)b] = Engine::KwsIO{&s->res->tables, T, s->a.data(), s->start.data()};
+        }
+        Engine::KwsResult r;
+        {
+            EngineLock lk(e);
+            e.kws_chunk_host(enc_out, B, Tc, io.data(), &r);
+        }
+        for (int b = 0; b < B; b++) K2_REQUIRE(r.n[(size_t)b] >= 0 && r.n[(size_t)b] <= r.mt, "internal: stream %d reports %d events", b, r.n[(size_t)b]);
+        // nothing below fails: the call is applied to every stream or to none
+        for (int b = 0; b < B; b++) {
+            k2hip_kws_stream* s = streams[b];
+            if (io[(size_t)b].T == 0) continue;
+            const size_t S = s->a.size(), o = (size_t)r.state_off[(size_t)b];
+            memcpy(s->a.data(), r.a.data() + o, sizeof(float) * S);
+            memcpy(s->start.data(), r.st.data() + o, sizeof(int32_t) * S);
+            kws_take_events(r, b, &s->events);
+        }
+    });
+}
+int32_t k2hip_offline_spot_keywords_from_samples(k2hip_model_t* model, const k2hip_keywords_t* kw, const float* const* samples,
+                                                 const int64_t* n_samples, int32_t B, int32_t* keyword, int32_t* start, int32_t* end,
+                                                 float* sum_logp, float* score, int32_t* n_events, int32_t max_events, int32_t* Tprime_out) {
+    return guard([&] {
+        NEED(model); NEED(kw); NEED(samples); NEED(n_samples); NEED(n_events);
+        K2_REQUIRE(B > 0 && max_events >= 0, "spot_keywords_from_samples: bad shape B=%d max_events=%d", B, max_events);
+        Engine& e = model->engine;
+        if (e.model().cfg().ctc) failf(K2HIP_ERR_UNSUPPORTED, "spot_keywords_from_samples: a CTC model has no transducer lattice");
+        const std::shared_ptr<KwResident> res = kw_resident_get(model, kw, "spot_keywords_from_samples");
+        const int S = res->graph->num_states();
+        std::vector<float> a0((size_t)S);
+        std::vector<int32_t> s0((size_t)S);
+        kws_fresh_state(S, a0.data(), s0.data());
+        std::vector<Engine::KwsIO> io((size_t)B, Engine::KwsIO{&res->tables, 0, a0.data(), s0.data()});
+        Engine::KwsResult r;
+        int32_t Tp = 0;
+        {
+            EngineLock lk(e);
+            e.kws_samples(samples, n_samples, B, io.data(), &r, &Tp);
+        }
+        for (int b = 0; b < B; b++) {
+            K2_REQUIRE(r.n[(size_t)b] >= 0 && r.n[(size_t)b] <= r.mt, "internal: stream %d reports %d events", b, r.n[(size_t)b]);
+            if (r.n[(size_t)b] > max_events) failf(K2HIP_ERR_CAPACITY, "spot_keywords_from_samples: stream %d has %d events, max_events is %d", b, r.n[(size_t)b], max_events);
+        }
+        for (int b = 0; b < B; b++) {
+            std::vector<KwsRefEvent> ev;
+            kws_take_events(r, b, &ev);
+            const size_t o = (size_t)b * (size_t)max_events;
+            kws_events_out(*res->graph, ev.data(), ev.size(), keyword ? keyword + o : nullptr, start ? start + o : nullptr, end ? end + o : nullptr,
+                           sum_logp ? sum_logp + o : nullptr, score ? score + o : nullptr, ev.size());
+            n_events[b] = (int32_t)ev.size();
+        }
+        if (Tprime_out) *Tprime_out = Tp;
     });
 }
 // ---- n-gram LM shallow fusion (ngram_lm.cpp) -----------------------------------------------------------

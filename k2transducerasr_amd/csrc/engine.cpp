@@ -4,6 +4,7 @@
 #include "engine.h"
 #include "lattice_ref.h"
 #include "ctc_lattice_ref.h"
+#include "kws_ref.h"
 #include "ctc_prefix_bias_ref.h"
 #include "ctc_prefix_ref.h"
 #include "hotwords.h"
@@ -684,6 +685,7 @@ const float* Engine::decoder_start(const Ctx& c) {
 Engine::SearchExtras Engine::search_device(const Ctx& c, const float* enc, int B, int Tp, const SearchStage& stage, const SearchOut& out) {
     if (stage.align) return align_device(c, enc, Tp, *stage.align, out);
     if (stage.ctc_align) return ctc_align_device(c, enc, B, Tp, *stage.ctc_align, out);
+    if (stage.kws) return kws_device(c, enc, Tp, *stage.kws, out);
     return greedy_device(c, enc, B, Tp, stage.single, out, stage.keep_nbest);
 }
 
@@ -1071,6 +1073,12 @@ void Engine::finish_tokens(const SearchOut& out, const SearchExtras& ex, int64_t
         fetch(last_align_scores_, ex.align_scores, (size_t)B * 2);
     }
     if (ex.align_end) fetch(last_align_end_, ex.align_end, (size_t)B * max_tokens);
+    if (ex.kws_a) {
+        fetch(last_kws_start_, ex.kws_start, (size_t)B * max_tokens);
+        fetch(last_kws_sum_, ex.kws_sum, (size_t)B * max_tokens);
+        fetch(last_kws_a_, ex.kws_a, (size_t)ex.kws_states);
+        fetch(last_kws_st_, ex.kws_st, (size_t)ex.kws_states);
+    }
     NbestHost& h = last_nbest_;
     h.B = 0;
     if (ex.nb.tokens) {
@@ -1470,6 +1478,157 @@ void Engine::align_samples(const float* const* samples, const int64_t* n_samples
     stage.align = &p;
     offline_samples(samples, n_samples, B, stage, s.tok.data(), s.ts.data(), s.n.data(), s.mt, false);
     align_copy_out(B, lens, s, timestamps, nullptr, token_log_probs, total, best);
+    if (Tp_out) *Tp_out = Tp;
+}
+
+// ---------------------------------------------------------------------------
+// keyword spotting: trie Viterbi on the lattice (kws.hip)
+// ---------------------------------------------------------------------------
+static_assert(kKwsMaxStates == kKeywordsMaxStates, "the kernel's and the graph builder's state limit are one number");
+
+void* Engine::kws_graph_upload(const KeywordGraph& g, KwsGraphDev* out) {
+    const Config& cf = model_->cfg();
+    if (cf.ctc) failf(K2HIP_ERR_UNSUPPORTED, "keyword spotting: a CTC model has no transducer lattice");
+    K2_REQUIRE(cf.ctx == 2, "keyword spotting: decoder context size %d (2 is built)", cf.ctx);
+    K2_REQUIRE(g.vocab_size() == cf.V, "keyword spotting: the graph was built for vocab_size %d, the model has %d", g.vocab_size(), cf.V);
+    const int S = g.num_states();
+    const std::vector<int64_t> ctx = g.contexts(2);
+    std::vector<long long> hy(ctx.begin(), ctx.end());
+    // [dec | parent | depth | kw | bar | child_off | child_tok | child_state], every piece on 16 bytes
+    const int64_t nb_dec = align_up((int64_t)sizeof(float) * S * cf.J, 16), nb_s = align_up((int64_t)sizeof(int32_t) * (S + 1), 16);
+    char* d = static_cast<char*>(dev_alloc(nb_dec + 7 * nb_s));
+    try {
+        char* t = d + nb_dec;
+        const void* src[7] = {g.parent().data(), g.depth().data(), g.kw().data(), g.bar().data(), g.child_off().data(), g.child_tok().data(),
+                              g.child_state().data()};
+        const int64_t cnt[7] = {S, S, S, S, S + 1, S - 1, S - 1};
+        for (int k = 0; k < 7; k++)
+            if (cnt[k] > 0) dev_upload(t + k * nb_s, src[k], 4 * cnt[k]);
+        run_sized([&](const Ctx& c) {
+            long long* d_y = c.arena->take<long long>((int64_t)S * 2);
+            if (!c.dry) K2_HIP(hipMemcpyAsync(d_y, hy.data(), sizeof(long long) * hy.size(), hipMemcpyHostToDevice, c.stream));
+            decoder(c, decjoin(), d_y, S, reinterpret_cast<float*>(d));
+        });
+        K2_HIP(hipStreamSynchronize(stream_));
+        out->dec = reinterpret_cast<const float*>(d);
+        out->parent = reinterpret_cast<const int*>(t);
+        out->depth = reinterpret_cast<const int*>(t + nb_s);
+        out->kw = reinterpret_cast<const int*>(t + 2 * nb_s);
+        out->bar = reinterpret_cast<const float*>(t + 3 * nb_s);
+        out->child_off = reinterpret_cast<const int*>(t + 4 * nb_s);
+        out->child_tok = reinterpret_cast<const int*>(t + 5 * nb_s);
+        out->child_state = reinterpret_cast<const int*>(t + 6 * nb_s);
+        out->S = S;
+    } catch (...) {
+        try { dev_free(d); } catch (...) {}
+        throw;
+    }
+    return d;
+}
+
+Engine::KwsPlan Engine::kws_plan(int B, int Tp, const KwsIO* io, bool all_frames) const {
+    const Config& cf = model_->cfg();
+    if (cf.ctc) failf(K2HIP_ERR_UNSUPPORTED, "keyword spotting: a CTC model has no transducer lattice");
+    K2_REQUIRE(B > 0 && B <= 65535 && Tp >= 1 && io != nullptr, "keyword spotting: bad shape B=%d T'=%d", B, Tp);
+    KwsPlan p;
+    p.B = B; p.Tp = Tp;
+    p.state_off.resize((size_t)B);
+    for (int b = 0; b < B; b++) {
+        const int T = all_frames ? Tp : io[b].T;
+        K2_REQUIRE(io[b].graph && io[b].graph->dec && io[b].a && io[b].start, "keyword spotting: stream %d has no resident graph", b);
+        K2_REQUIRE(T >= 0 && T <= Tp, "keyword spotting: stream %d: n_frames %d outside [0, %d]", b, T, Tp);
+        K2_REQUIRE(io[b].graph->S >= 1 && io[b].graph->S <= kKwsMaxStates, "keyword spotting: stream %d: %d trie states", b, io[b].graph->S);
+        p.state_off[(size_t)b] = p.n_states;
+        p.n_states += io[b].graph->S;
+    }
+    p.o_a = align_up((int64_t)sizeof(KwsStream) * B, 16);
+    p.o_st = align_up(p.o_a + (int64_t)sizeof(float) * p.n_states, 16);
+    p.blob.assign((size_t)(p.o_st + (int64_t)sizeof(int32_t) * p.n_states), 0);
+    KwsStream* st = reinterpret_cast<KwsStream*>(p.blob.data());
+    float* h_a = reinterpret_cast<float*>(p.blob.data() + p.o_a);
+    int32_t* h_st = reinterpret_cast<int32_t*>(p.blob.data() + p.o_st);
+    for (int b = 0; b < B; b++) {
+        const int T = all_frames ? Tp : io[b].T, S = io[b].graph->S, so = p.state_off[(size_t)b];
+        st[b] = KwsStream{*io[b].graph, p.plane_floats, so, T};
+        p.plane_floats += (long long)T * S;
+        p.max_T = std::max(p.max_T, T);
+        p.max_S = std::max(p.max_S, S);
+        memcpy(h_a + so, io[b].a, sizeof(float) * (size_t)S);
+        memcpy(h_st + so, io[b].start, sizeof(int32_t) * (size_t)S);
+    }
+    return p;
+}
+
+Engine::SearchExtras Engine::kws_device(const Ctx& c, const float* enc, int Tp, const KwsPlan& p, const SearchOut& out, float* stay, float* emit,
+                                        bool cells, bool dp) {
+    K2_REQUIRE(Tp == p.Tp && out.B == p.B && out.max_tokens >= std::max(p.max_T, 1),
+               "internal: the keyword plan was laid out for T'=%d B=%d, the encoder gave T'=%d B=%d", p.Tp, p.B, Tp, out.B);
+    Arena& ar = *c.arena;
+    char* d_blob = ar.take<char>((int64_t)p.blob.size());
+    KwsArgs a;
+    a.enc = enc; a.B = p.B; a.Tp = Tp; a.max_T = p.max_T; a.max_S = p.max_S;
+    a.streams = reinterpret_cast<const KwsStream*>(d_blob);
+    a.a_in = reinterpret_cast<const float*>(d_blob + p.o_a);
+    a.start_in = reinterpret_cast<const int*>(d_blob + p.o_st);
+    a.stay = stay ? stay : ar.take<float>(std::max<long long>(p.plane_floats, 1));
+    a.emit = emit ? emit : ar.take<float>(std::max<long long>(p.plane_floats, 1));
+    if (!c.dry) K2_HIP(hipMemcpyAsync(d_blob, p.blob.data(), p.blob.size(), hipMemcpyHostToDevice, c.stream));
+    if (cells) trie_logprobs(c, decjoin(), a);
+    SearchExtras ex;
+    if (!dp) return ex;
+    const int64_t ne = (int64_t)p.B * out.max_tokens;
+    ex.kws_start = ar.take<int>(ne);
+    ex.kws_sum = ar.take<float>(ne);
+    ex.kws_a = ar.take<float>(p.n_states);
+    ex.kws_st = ar.take<int>(p.n_states);
+    ex.kws_states = p.n_states;
+    a.a_out = ex.kws_a; a.start_out = ex.kws_st;
+    a.ev_keyword = out.tokens(); a.ev_end = out.timestamps(); a.n_events = out.counts(); a.max_events = out.max_tokens;
+    a.ev_start = ex.kws_start; a.ev_sum = ex.kws_sum;
+    if (!c.dry) K2_HIP(hipMemsetAsync(out.flag(), 0, sizeof(int), c.stream));
+    trie_dp(c, a);
+    return ex;
+}
+
+void Engine::kws_collect(const KwsPlan& p, int mt, std::vector<int64_t>&& tok, std::vector<int32_t>&& ts, std::vector<int32_t>&& n,
+                         KwsResult* res) const {
+    res->mt = mt;
+    res->keyword = std::move(tok);
+    res->end = std::move(ts);
+    res->n = std::move(n);
+    res->start = last_kws_start_;
+    res->sum = last_kws_sum_;
+    res->a = last_kws_a_;
+    res->st = last_kws_st_;
+    res->state_off = p.state_off;
+}
+
+void Engine::kws_chunk_host(const float* enc_out, int B, int Tc, const KwsIO* io, KwsResult* res) {
+    K2_REQUIRE(enc_out != nullptr && res != nullptr, "keyword spotting: bad arguments");
+    const KwsPlan p = kws_plan(B, Tc, io, false);
+    const int mt = std::max(p.max_T, 1);
+    std::vector<int64_t> tok((size_t)B * mt);
+    std::vector<int32_t> ts((size_t)B * mt), n((size_t)B);
+    SearchStage stage;
+    stage.kws = &p;
+    search_host(enc_out, B, Tc, stage, tok.data(), ts.data(), n.data(), mt);
+    kws_collect(p, mt, std::move(tok), std::move(ts), std::move(n), res);
+}
+
+void Engine::kws_samples(const float* const* samples, const int64_t* n_samples, int B, const KwsIO* io, KwsResult* res, int32_t* Tp_out) {
+    K2_REQUIRE(samples != nullptr && n_samples != nullptr && B > 0 && res != nullptr, "spot_keywords_from_samples: bad arguments");
+    if (model_->cfg().ctc) failf(K2HIP_ERR_UNSUPPORTED, "keyword spotting: a CTC model has no transducer lattice");
+    // T' of the padded batch: every stream is searched over all of it, the frames the searches decode
+    const OfflineShape sh = samples_shape(samples, n_samples, B);
+    const int Tp = sh.Tp;
+    K2_REQUIRE(Tp > 0, "spot_keywords_from_samples: %lld samples give no encoder frame", (long long)sh.longest);
+    const KwsPlan p = kws_plan(B, Tp, io, true);
+    std::vector<int64_t> tok((size_t)B * Tp);
+    std::vector<int32_t> ts((size_t)B * Tp), n((size_t)B);
+    SearchStage stage;
+    stage.kws = &p;
+    offline_samples(samples, n_samples, B, stage, tok.data(), ts.data(), n.data(), Tp, false);
+    kws_collect(p, Tp, std::move(tok), std::move(ts), std::move(n), res);
     if (Tp_out) *Tp_out = Tp;
 }
 
@@ -2378,6 +2537,84 @@ void Engine::debug_op_host(const char* op, const int64_t* iargs, int n_iargs, vo
                 K2_HIP(copy_blocking(dev[k_lp], ex.align_lp, 4 * (size_t)B * max_tokens, hipMemcpyDeviceToDevice));
                 K2_HIP(copy_blocking(dev[k_sc], ex.align_scores, 8 * (size_t)B, hipMemcpyDeviceToDevice));
             }
+        } else if (name == "trie_logprobs") {
+            // bufs enc [B][Tp][J], n_frames [B] int32 (or null), keyword ids int64 back to back, lens [P] int32, thresholds [P], stay, emit
+            //   (out: every stream's plane [T_b][S], back to back; all streams on the one graph); ints B, Tp, P
+            K2_REQUIRE(n_bufs == 7, "debug_op_run %s: %d buffers", op, n_bufs);
+            for (int k = 0; k < n_bufs; k++) P();
+            const int B = I(), Tp = I(), NP = I();
+            K2_REQUIRE(B > 0 && Tp > 0 && NP >= 0, "debug_op_run %s: bad shape", op);
+            K2_REQUIRE((!bufs[1] || buf_bytes[1] >= 4 * (int64_t)B) && (NP == 0 || (bufs[3] && buf_bytes[3] >= 4 * (int64_t)NP && bufs[4] &&
+                                                                                    buf_bytes[4] >= 4 * (int64_t)NP)),
+                       "debug_op_run %s: n_frames / lens / thresholds are too short", op);
+            const int32_t* lens = static_cast<const int32_t*>(bufs[3]);
+            int64_t n_ids = 0;
+            for (int k = 0; k < NP; k++) n_ids += std::max(lens[k], 0);
+            K2_REQUIRE(n_ids == 0 || (bufs[2] && buf_bytes[2] >= 8 * n_ids), "debug_op_run %s: ids are too short", op);
+            const KeywordGraph g(static_cast<const int64_t*>(bufs[2]), lens, static_cast<const float*>(bufs[4]), NP, model_->cfg().V);
+            const int S = g.num_states();
+            KwsGraphDev gd;
+            char* res = static_cast<char*>(kws_graph_upload(g, &gd));
+            d.base.push_back(res);
+            std::vector<float> a0((size_t)S);
+            std::vector<int32_t> s0((size_t)S);
+            kws_fresh_state(S, a0.data(), s0.data());
+            const int32_t* nf = static_cast<const int32_t*>(bufs[1]);
+            std::vector<KwsIO> io((size_t)B);
+            for (int b = 0; b < B; b++) io[(size_t)b] = KwsIO{&gd, nf ? nf[b] : Tp, a0.data(), s0.data()};
+            const KwsPlan p = kws_plan(B, Tp, io.data(), false);
+            K2_REQUIRE(dev[0] && buf_bytes[0] >= 4 * (int64_t)B * Tp * model_->cfg().J, "debug_op_run %s: enc is too short", op);
+            K2_REQUIRE(dev[5] && dev[6] && buf_bytes[5] >= 4 * p.plane_floats && buf_bytes[6] >= 4 * p.plane_floats,
+                       "debug_op_run %s: the planes need %lld floats each", op, p.plane_floats);
+            run_sized([&](const Ctx& cc) {
+                const SearchOut out(*cc.arena, B, std::max(p.max_T, 1));
+                kws_device(cc, static_cast<const float*>(dev[0]), Tp, p, out, static_cast<float*>(dev[5]), static_cast<float*>(dev[6]), true, false);
+            });
+            K2_HIP(hipStreamSynchronize(stream_));
+        } else if (name == "trie_dp") {
+            // bufs n_frames [B] int32 (or null), parent, depth, kw [S] int32, bar [S], stay, emit (in: every stream's plane [T_b][S], back to
+            //   back), a [B][S], start [B][S] int32 (in / out: the carried blocks), ev_keyword [B][Tp] int64, ev_start, ev_end [B][Tp] int32,
+            //   ev_sum [B][Tp], n_events [B] int32 (out); ints B, Tp, S.  All streams walk the one trie; bar is taken as given.
+            K2_REQUIRE(n_bufs == 14, "debug_op_run %s: %d buffers", op, n_bufs);
+            for (int k = 0; k < n_bufs; k++) P();
+            const int B = I(), Tp = I(), S = I();
+            K2_REQUIRE(B > 0 && Tp > 0 && S >= 1 && S <= kKwsMaxStates, "debug_op_run %s: bad shape", op);
+            K2_REQUIRE(!bufs[0] || buf_bytes[0] >= 4 * (int64_t)B, "debug_op_run %s: n_frames is too short", op);
+            for (int k = 1; k <= 4; k++) K2_REQUIRE(dev[k] && buf_bytes[k] >= 4 * (int64_t)S, "debug_op_run %s: the trie tables are too short", op);
+            const int32_t* par = static_cast<const int32_t*>(bufs[1]);
+            for (int s2 = 1; s2 < S; s2++) K2_REQUIRE(par[s2] >= 0 && par[s2] < s2, "debug_op_run %s: parent(%d) = %d", op, s2, par[s2]);
+            K2_REQUIRE(dev[7] && dev[8] && buf_bytes[7] >= 4 * (int64_t)B * S && buf_bytes[8] >= 4 * (int64_t)B * S,
+                       "debug_op_run %s: the carried blocks are too short", op);
+            KwsGraphDev gd;
+            gd.dec = static_cast<const float*>(dev[1]);   // (not read: the arcs are the caller's planes)
+            gd.parent = static_cast<const int*>(dev[1]); gd.depth = static_cast<const int*>(dev[2]); gd.kw = static_cast<const int*>(dev[3]);
+            gd.bar = static_cast<const float*>(dev[4]);
+            gd.S = S;
+            const int32_t* nf = static_cast<const int32_t*>(bufs[0]);
+            std::vector<KwsIO> io((size_t)B);
+            for (int b = 0; b < B; b++)
+                io[(size_t)b] = KwsIO{&gd, nf ? nf[b] : Tp, static_cast<const float*>(bufs[7]) + (size_t)b * S, static_cast<const int32_t*>(bufs[8]) + (size_t)b * S};
+            const KwsPlan p = kws_plan(B, Tp, io.data(), false);
+            K2_REQUIRE(dev[5] && dev[6] && buf_bytes[5] >= 4 * p.plane_floats && buf_bytes[6] >= 4 * p.plane_floats,
+                       "debug_op_run %s: the planes need %lld floats each", op, p.plane_floats);
+            const int64_t ne = (int64_t)B * Tp;
+            K2_REQUIRE(dev[9] && dev[10] && dev[11] && dev[12] && dev[13] && buf_bytes[9] >= 8 * ne && buf_bytes[10] >= 4 * ne && buf_bytes[11] >= 4 * ne &&
+                           buf_bytes[12] >= 4 * ne && buf_bytes[13] >= 4 * (int64_t)B,
+                       "debug_op_run %s: the event buffers are too short", op);
+            SearchOut out;
+            SearchExtras ex;
+            run_sized([&](const Ctx& cc) {
+                out = SearchOut(*cc.arena, B, Tp);
+                ex = kws_device(cc, nullptr, Tp, p, out, static_cast<float*>(dev[5]), static_cast<float*>(dev[6]), false, true);
+            });
+            K2_HIP(hipStreamSynchronize(stream_));
+            K2_HIP(copy_blocking(dev[7], ex.kws_a, 4 * (size_t)B * S, hipMemcpyDeviceToDevice));
+            K2_HIP(copy_blocking(dev[8], ex.kws_st, 4 * (size_t)B * S, hipMemcpyDeviceToDevice));
+            K2_HIP(copy_blocking(dev[9], out.tokens(), 8 * (size_t)ne, hipMemcpyDeviceToDevice));
+            K2_HIP(copy_blocking(dev[10], ex.kws_start, 4 * (size_t)ne, hipMemcpyDeviceToDevice));
+            K2_HIP(copy_blocking(dev[11], out.timestamps(), 4 * (size_t)ne, hipMemcpyDeviceToDevice));
+            K2_HIP(copy_blocking(dev[12], ex.kws_sum, 4 * (size_t)ne, hipMemcpyDeviceToDevice));
+            K2_HIP(copy_blocking(dev[13], out.counts(), 4 * (size_t)B, hipMemcpyDeviceToDevice));
         } else if (name == "ctc_lattice") {
             // bufs log_probs [R][Tp][V], n_frames [R] int32 (or null), stream_of [H] int32 (or null), ids int64 back to back, lens [H] int32,
             //   timestamps, end_frames [H][max_tokens] int32, token_log_probs [H][max_tokens], scores [H][2] = (total, best) (out);

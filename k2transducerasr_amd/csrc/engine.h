@@ -12,6 +12,7 @@
 #include <tuple>
 
 #include "kernels.h"
+#include "keywords.h"
 #include "model.h"
 #include "search_out.h"
 
@@ -95,6 +96,30 @@ class Engine {
     void ctc_align_samples(const float* const* samples, const int64_t* n_samples, int B, int H, const int32_t* stream_of, const int64_t* ids,
                            const int32_t* lens, int32_t* timestamps, int32_t* end_frames, float* token_log_probs, float* total, float* best,
                            int max_tokens, int32_t* Tp_out);
+    // ---- keyword spotting: trie Viterbi on the lattice (kws.hip; semantics in include/k2hip.h "Keyword spotting") ----
+    // A graph made resident: ONE device allocation [decoder rows [S][J] | the trie's tables], the rows from the decoder() launch on the
+    // S contexts.  The caller owns the allocation (dev_free) and shares it among the streams of the graph.
+    void* kws_graph_upload(const KeywordGraph& g, KwsGraphDev* out);
+    // One stream of a chunk call: its resident graph, the T frames it takes (0: untouched) and its carried block (kws_ref.h)
+    struct KwsIO {
+        const KwsGraphDev* graph;
+        int T;
+        const float* a;
+        const int32_t* start;
+    };
+    // What a chunk call gives back: row b of keyword / end / start / sum [B][mt] holds n[b] events, a / st the new carried blocks, stream
+    // b's at state_off[b]
+    struct KwsResult {
+        int mt = 0;
+        std::vector<int64_t> keyword;
+        std::vector<int32_t> end, start, n, st, state_off;
+        std::vector<float> sum, a;
+    };
+    // enc_out [B][Tc][J] on the host; the arguments are checked before any device work, and nothing of `io` is written
+    void kws_chunk_host(const float* enc_out, int B, int Tc, const KwsIO* io, KwsResult* res);
+    // offline_greedy_samples' fbank + pad + encoder with the spotter as the stage behind them: encoder_out stays on the device, every
+    // stream is searched over all T' frames (io[b].T is not read)
+    void kws_samples(const float* const* samples, const int64_t* n_samples, int B, const KwsIO* io, KwsResult* res, int32_t* Tp_out);
     // ---- CTC prefix beam search with N-best (ctc_prefix.hip; semantics in include/k2hip.h) ----
     // log_probs [R][Tp][V] on the host; n_frames [R] or null (= Tp).  tokens / timestamps / token_log_probs [R][nbest][max_tokens],
     // n_tokens / scores [R][nbest], n_hyps [R]: the shapes of k2hip_beam_search_nbest.  The arguments are checked on the host before
@@ -291,7 +316,29 @@ class Engine {
         float* align_lp = nullptr;            // align: [B][max_tokens] token log-probs of the best path
         float* align_scores = nullptr;        // align: [B][2] = (total, best)
         int* align_end = nullptr;             // CTC align: [H][max_tokens] last frame of every token on the best path
+        int* kws_start = nullptr;             // keyword spotting: [B][max_tokens] start frames, sum_logp, and the new carried blocks
+        float* kws_sum = nullptr;
+        float* kws_a = nullptr;
+        int* kws_st = nullptr;
+        int kws_states = 0;
     };
+    // One keyword-spotting call as the host lays it out before any device work: the streams' descriptors and carried blocks in ONE upload
+    struct KwsPlan {
+        int B = 0, Tp = 0, max_T = 0, max_S = 0, n_states = 0;
+        long long plane_floats = 0;
+        int64_t o_a = 0, o_st = 0;        // byte offsets of the carried values (float) and starts (int) behind the descriptors
+        std::vector<int32_t> state_off;
+        std::vector<char> blob;
+    };
+    KwsPlan kws_plan(int B, int Tp, const KwsIO* io, bool all_frames) const;
+    // trie_logprobs, trie_dp into `out` (tokens = keywords, timestamps = end frames, counts = events).  The test hooks pass planes of
+    // their own (stay / emit) and stop after the first kernel (dp = false) or run only the second (cells = false).
+    SearchExtras kws_device(const Ctx& c, const float* enc, int Tp, const KwsPlan& p, const SearchOut& out, float* stay = nullptr,
+                            float* emit = nullptr, bool cells = true, bool dp = true);
+    // a finished call's results (the SearchOut rows of mt entries and the last_kws_* vectors) into `res`
+    void kws_collect(const KwsPlan& p, int mt, std::vector<int64_t>&& tok, std::vector<int32_t>&& ts, std::vector<int32_t>&& n, KwsResult* res) const;
+    std::vector<int32_t> last_kws_start_, last_kws_st_;
+    std::vector<float> last_kws_sum_, last_kws_a_;
     // One align call as the host lays it out before any device work: the streams' descriptors, targets and contexts in ONE upload block
     struct AlignPlan {
         int B = 0, Tp = 0, max_T = 0, max_U = 0, n_ctx = 0, n_ids = 0;
@@ -337,6 +384,7 @@ class Engine {
         bool single = false, keep_nbest = true;
         const AlignPlan* align = nullptr;
         const CtcAlignPlan* ctc_align = nullptr;
+        const KwsPlan* kws = nullptr;
         // rows of its search-output block for B streams: one per stream, or one per target (several CTC targets may share a stream)
         int rows(int B) const { return ctc_align ? ctc_align->H : B; }
     };

@@ -704,6 +704,50 @@ void lattice_logprobs(const Ctx& ctx, const DecJoinW& w, const AlignArgs& a);
 constexpr int kAlignMaxU = 4095;   // U + 1 positions of both recursions' two rows live in LDS
 void lattice_dp(const Ctx& ctx, const AlignArgs& a);
 
+// ---- keyword spotting: trie Viterbi on the transducer lattice (kws.hip; semantics in include/k2hip.h and kws_ref.h) ----
+// A keyword graph resident on the device (keywords.h): the decoder row of every state's context and the trie's tables.
+struct KwsGraphDev {
+    const float* dec = nullptr;          // [S][J]: decoder() of ctx(s)
+    const int* parent = nullptr;         // [S]
+    const int* depth = nullptr;          // [S]
+    const int* kw = nullptr;             // [S], -1 = no keyword ends there
+    const float* bar = nullptr;          // [S]
+    const int* child_off = nullptr;      // [S + 1]
+    const int* child_tok = nullptr;      // [S - 1], sorted by token inside every state's range
+    const int* child_state = nullptr;    // [S - 1]
+    int S = 0;
+};
+// One stream of a chunk call: T frames (the first T of its Tp encoder rows; 0 = the stream is carried through unchanged), its two planes
+// [T][S] at plane_off floats into stay / emit, its carried block [S] at state_off into a_in / start_in / a_out / start_out.
+struct KwsStream {
+    KwsGraphDev g;
+    long long plane_off;
+    int state_off, T;
+};
+struct KwsArgs {
+    const float* enc = nullptr;          // [B, Tp, J]
+    int B = 0, Tp = 0;
+    int max_T = 0, max_S = 0;            // over the call's streams (the launch grid, the DP's LDS rows)
+    const KwsStream* streams = nullptr;  // [B] (device)
+    float *stay = nullptr, *emit = nullptr;
+    const float* a_in = nullptr;
+    const int* start_in = nullptr;
+    float* a_out = nullptr;
+    int* start_out = nullptr;
+    // trie_dp's events, row b of [B][max_events] each (max_events >= max_T: at most one per frame), n_events [B]
+    long long* ev_keyword = nullptr;
+    int *ev_end = nullptr, *ev_start = nullptr;
+    float* ev_sum = nullptr;
+    int* n_events = nullptr;
+    int max_events = 0;
+};
+constexpr int kKwsMaxStates = 1024;   // = K2HIP_KEYWORDS_MAX_STATES: four states per lane of trie_dp's workgroup
+// stay(t,s) = logaddexp(lp(t,s,blank), lp(t,s,unk)) of every state and emit(t,c) = lp(t,parent(c),tok(c)) of every non-root state (column
+// 0 of emit: -inf), lp = log_softmax(output_linear(tanh(enc[t] + dec[s]))) swept on the f32 matrix pipe -- no logits are stored
+void trie_logprobs(const Ctx& ctx, const DecJoinW& w, const KwsArgs& a);
+// token passing over the two planes, one workgroup per stream: the carried block in, events and the new carried block out
+void trie_dp(const Ctx& ctx, const KwsArgs& a);
+
 // ---- CTC forced alignment and full-sum scoring (ctc_align.hip; semantics in include/k2hip.h and ctc_lattice_ref.h) ----
 // One target of a CTC align call: U tokens at ids[id_off ..], scored against row `row` of log_probs over its first T frames; its compact
 // plane [T][U + 1] (column 0: lp(t, blank), column k: lp(t, y_k)) at plane_off floats into `plane`, and its back-pointers
