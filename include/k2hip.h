@@ -58,6 +58,7 @@ typedef struct k2hip_hotwords k2hip_hotwords_t;
 typedef struct k2hip_ngram_lm k2hip_ngram_lm_t;
 typedef struct k2hip_keywords k2hip_keywords_t;
 typedef struct k2hip_kws_stream k2hip_kws_stream_t;
+typedef struct k2hip_ctc_kws_stream k2hip_ctc_kws_stream_t;
 
 /* Fixed ids of the reference: OfflineModel.cs:18-20. */
 #define K2HIP_BLANK_ID 0
@@ -546,7 +547,8 @@ int32_t k2hip_offline_align_from_samples(k2hip_model_t* model, const float* cons
  *
  * Streaming rule: after any chunking a stream's events and carried (a, start) are bit for bit those of one call over all frames so
  * far.  n_frames[b] = 0 leaves stream b untouched.  Zero keywords (one state) is legal and never fires.
- * Hotwords, the n-gram LM and the decoding method do not take part.  A CTC model: K2HIP_ERR_UNSUPPORTED.  Every transducer family is
+ * Hotwords, the n-gram LM and the decoding method do not take part.  A CTC model: K2HIP_ERR_UNSUPPORTED (its spotter is
+ * k2hip_ctc_kws_* / k2hip_offline_ctc_spot_keywords_from_samples, "Keyword spotting for CTC models" below).  Every transducer family is
  * served: the search consumes encoder_out [B][T][joiner_dim] only.
  *
  * k2hip_keywords_create: keyword p = ids[off .. off + lens[p]), thresholds[p].  k2hip_keywords_load: a text file in the token-string
@@ -584,6 +586,67 @@ int32_t k2hip_kws_stream_clear_events(k2hip_kws_stream_t* s);
 int32_t k2hip_offline_spot_keywords_from_samples(k2hip_model_t* model, const k2hip_keywords_t* kw, const float* const* samples,
                                                  const int64_t* n_samples, int32_t B, int32_t* keyword, int32_t* start, int32_t* end,
                                                  float* sum_logp, float* score, int32_t* n_events, int32_t max_events, int32_t* Tprime_out);
+/* ---- Keyword spotting for CTC models: trie Viterbi on the CTC trellis (zipformer2ctc models) -------------------------------------
+ * No reference counterpart: the semantics are the project's own, defined here and in DESIGN.md "CTC keyword spotting"; they follow
+ * "Keyword spotting" and "CTC forced alignment" wherever those already decide a question.  tests/ctc_kws_twin.py restates them in
+ * float64, csrc/ctc_kws_ref.h in float32.
+ *
+ * Graph: a k2hip_keywords_t as it is, with all its refusals.  Limitation: it keeps refusing unk (id 2) inside a keyword although CTC
+ * treats unk as an ordinary token.  bar(s) = (float)depth(s) * logf(threshold) as before.  One derived host table: rc(s) = the root's
+ * child whose token equals tok(s), or -1.
+ *
+ * Input: lp(t, v), a row's log-probs [T][V], finite or -inf; blank is id 0.
+ *
+ * States: every non-root trie state c holds two cells, n[c] (the path's last frame carried tok(c)) and b[c] (tok(c) is finished and
+ * the path sits in blanks after it).  Each cell is (value, start), initially (-inf, -1).  The root is free: value 0, start t -- a
+ * keyword may begin at any frame at no cost.
+ *
+ * Frame t: all reads are of the values before the frame; all arithmetic is float32, adds and compares only.
+ *   n[c] <- max(pred, n[c]) + lp(t, tok(c)).  When parent(c) is the root, pred is the root (0, t).  Otherwise pred is the better of
+ *     n[parent(c)] and b[parent(c)], n[parent(c)] being allowed only when tok(parent(c)) != tok(c): a repeated token needs a blank
+ *     between, the CTC rule.  Exact float32 ties go in k2hip_ctc_align's order (lowest extended-state index first): n[parent], then
+ *     b[parent], then the self loop.  c is "entered" in this frame when the winner is not the self loop and the result is above -inf.
+ *   b[c] <- max(n[c], b[c]) + lp(t, 0); on a tie n[c] wins.
+ *   `start` is inherited from the winner; a cell at -inf carries start = -1.
+ *
+ * Hold, the one rule CTC needs beyond the transducer spotter: a CTC token may span several frames, so a keyword whose tokens are all
+ * the same -- in practice a one-token keyword -- would fire again on each of them.  Each stream carries `hold`, a state index or -1.
+ * At the top of frame t, if hold = r >= 0: when lp(t, tok(r)) >= lp(t, 0) the root arc into r is closed for this frame; otherwise
+ * hold <- -1 and the arc is open.  An event whose winner is c sets hold <- rc(c), effective from frame t + 1.
+ *
+ * Detection, after the update of frame t: among the terminal states entered in this frame with n[c] >= bar(c) the winner is the one of
+ * largest depth, then largest n[c], then smallest keyword index.  At most one event fires per frame: (keyword, start, end = t,
+ * sum_logp = n[c]).  After an event every non-root cell becomes (-inf, -1).  score = sum_logp / depth is computed by the host
+ * accessors.
+ *
+ * Carried block (canonical: one function of the frames seen, whatever the chunking): values [2][S] floats and starts [2][S] ints,
+ * plane 0 = n, plane 1 = b.  The root's n entry is (0, frame count); the root's b entry is (-inf, hold).
+ *
+ * Streaming rule: after any chunking a stream's events and carried block are bit for bit those of one call over all frames so far.
+ * n_frames[b] = 0 leaves stream b untouched.  Zero keywords is legal and never fires.  Streams in one call may walk different graphs.
+ * A failed call changes no stream.
+ *
+ * The entries follow the argument rules of their k2hip_kws_* siblings.  k2hip_ctc_kws_search_chunk: log_probs [B][Tc][V] on the host
+ * (as k2hip_online_encoder returns them for a streaming CTC model), any Tc >= 1, n_frames [B] in [0, Tc] or NULL (= Tc).  A stream
+ * keeps its own reference to the graph, so `kw` may be destroyed at once; the graph's tables are uploaded with every call (there are
+ * no decoder rows to keep resident).  k2hip_offline_ctc_spot_keywords_from_samples: samples -> fbank -> pad -> encoder, the log-probs
+ * stay on the device; fresh streams of `kw`, every one searched over ALL Tprime frames of the padded batch; K2HIP_ERR_CAPACITY if a
+ * stream has more events than max_events.
+ * Refusals, all decided on the host before any device work: K2HIP_ERR_UNSUPPORTED for a transducer model; K2HIP_ERR_INVALID for a
+ * graph of another vocabulary size, a stream listed twice, a stream of another model, n_frames[b] outside [0, Tc]. */
+int32_t k2hip_ctc_kws_stream_create(k2hip_model_t* model, const k2hip_keywords_t* kw, k2hip_ctc_kws_stream_t** out);
+int32_t k2hip_ctc_kws_stream_destroy(k2hip_ctc_kws_stream_t* s);
+int32_t k2hip_ctc_kws_stream_reset(k2hip_ctc_kws_stream_t* s);
+int64_t k2hip_ctc_kws_stream_num_frames(const k2hip_ctc_kws_stream_t* s);
+int32_t k2hip_ctc_kws_search_chunk(k2hip_model_t* model, k2hip_ctc_kws_stream_t* const* streams, int32_t B, const float* log_probs, int32_t Tc,
+                                   const int32_t* n_frames);
+int32_t k2hip_ctc_kws_stream_num_events(const k2hip_ctc_kws_stream_t* s);
+int32_t k2hip_ctc_kws_stream_get_events(const k2hip_ctc_kws_stream_t* s, int32_t* keyword, int32_t* start, int32_t* end, float* sum_logp,
+                                        float* score, int32_t cap);
+int32_t k2hip_ctc_kws_stream_clear_events(k2hip_ctc_kws_stream_t* s);
+int32_t k2hip_offline_ctc_spot_keywords_from_samples(k2hip_model_t* model, const k2hip_keywords_t* kw, const float* const* samples,
+                                                     const int64_t* n_samples, int32_t B, int32_t* keyword, int32_t* start, int32_t* end,
+                                                     float* sum_logp, float* score, int32_t* n_events, int32_t max_events, int32_t* Tprime_out);
 /* ---- CTC forced alignment and full-sum scoring of given transcripts (zipformer2ctc models) -------------------------------------
  * No reference counterpart: the reference's CTC path only searches (ForwardBatchGreedySearchCTC).  The semantics are the project's
  * own, defined here and in DESIGN.md "CTC forced alignment and full-sum scoring".

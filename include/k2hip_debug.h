@@ -184,6 +184,22 @@ int32_t k2hip_debug_kws_ref_dp(const int32_t* parent, const int32_t* depth, cons
                                const float* emit, int32_t T, float* a, int32_t* start, int32_t* ev_keyword, int32_t* ev_start, int32_t* ev_end,
                                float* ev_sum, int32_t cap, int32_t* n_events);
 
+/* ---- keyword spotting for CTC models (k2hip.h "Keyword spotting for CTC models") ----------------- */
+/* the carried block of a CTC keyword stream: v [2][S] and st [2][S] (plane 0 = n, plane 1 = b; S = k2hip_keywords_num_states of its
+ * graph; cap counts cells, 2 * S).  n of the root: (0, the stream's frame count); b of the root: (-inf, hold). */
+int32_t k2hip_debug_ctc_kws_stream_get_state(const k2hip_ctc_kws_stream_t* s, float* v, int32_t* st, int32_t cap);
+/* the float32 host reference of the token passing (csrc/ctc_kws_ref.h), no GPU: one stream, log_probs [T][V], the tables each [S] (bar
+ * as given; rc(s) = the root's child whose token is tok(s), or -1), the carried block v / st [2][S] updated in place, events into ev_*
+ * [cap] (K2HIP_ERR_CAPACITY beyond), *n_events their number */
+int32_t k2hip_debug_ctc_kws_ref_dp(const int32_t* parent, const int32_t* tok, const int32_t* depth, const int32_t* keyword, const float* bar,
+                                   const int32_t* rc, int32_t S, const float* log_probs, int32_t V, int32_t T, float* v, int32_t* st,
+                                   int32_t* ev_keyword, int32_t* ev_start, int32_t* ev_end, float* ev_sum, int32_t cap, int32_t* n_events);
+/* The spotter's kernel (csrc/ctc_kws.hip; tests/test_ctc_kws_gpu.py) through k2hip_debug_op_run on a CTC model:
+ *   "ctc_trie_dp": bufs log_probs [B][Tp][V], n_frames [B] int32 (or null = Tp), graph_of [B] int32 (or null = graph 0), the G graphs'
+ *     tables back to back, each [parent | tok | depth | kw | bar | rc] x [S_g] words (bar taken as given), n_states [G] int32, v, st (in /
+ *     out: every stream's carried block [2][S], back to back), ev_keyword [B][Tp] int64, ev_start, ev_end [B][Tp] int32, ev_sum [B][Tp],
+ *     n_events [B] int32 (out; row b holds n_events[b] events); ints B, Tp, G, V (the log-probs' width: any, not the model's). */
+
 /* ---- GEMM tuning ------------------------------------------------------------------------------- */
 /* time `iters` launches of a shape / configuration on pseudo-random operands (tools/gemm_lab.py, gemm_tune.py) */
 int32_t k2hip_debug_gemm(k2hip_model_t* model, int32_t M, int32_t N, int32_t K, int32_t act, int32_t with_res, int32_t cfg,

@@ -12,6 +12,7 @@ from __future__ import annotations
 from . import config, k2w, synth  # noqa: F401
 from .binding import (  # noqa: F401
     BeamStream,
+    CtcKeywordStream,
     CtcPrefixStream,
     Hotwords,
     Keywords,
@@ -34,6 +35,7 @@ from .binding import (  # noqa: F401
 
 __all__ = [
     "BeamStream",
+    "CtcKeywordStream",
     "CtcPrefixStream",
     "Hotwords",
     "Keywords",

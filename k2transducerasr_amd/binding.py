@@ -497,6 +497,91 @@ class KeywordStream:
         return a, st
 
 
+def _bind_ctc_kws(L):
+    if getattr(L, "_ctc_kws_bound", False):
+        return
+    L.k2hip_ctc_kws_stream_create.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
+    L.k2hip_ctc_kws_stream_destroy.argtypes = [C.c_void_p]
+    L.k2hip_ctc_kws_stream_reset.argtypes = [C.c_void_p]
+    L.k2hip_ctc_kws_stream_num_frames.argtypes = [C.c_void_p]
+    L.k2hip_ctc_kws_stream_num_frames.restype = C.c_int64
+    L.k2hip_ctc_kws_stream_num_events.argtypes = [C.c_void_p]
+    L.k2hip_ctc_kws_stream_get_events.argtypes = [C.c_void_p, ip, ip, ip, fp, fp, C.c_int32]
+    L.k2hip_ctc_kws_stream_clear_events.argtypes = [C.c_void_p]
+    L.k2hip_ctc_kws_search_chunk.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, fp, C.c_int32, ip]
+    L.k2hip_debug_ctc_kws_stream_get_state.argtypes = [C.c_void_p, fp, ip, C.c_int32]
+    L.k2hip_offline_ctc_spot_keywords_from_samples.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(fp), lp, C.c_int32, ip, ip, ip, fp, fp, ip, C.c_int32,
+                                                               ip]
+    L._ctc_kws_bound = True
+
+
+class CtcKeywordStream:
+    """One audio stream of a CTC model watched for the keywords of a graph (k2hip_ctc_kws_stream_*; include/k2hip.h "Keyword spotting for
+    CTC models"): the cells carried across chunks and the events found so far.  The streaming recipe is OnlineProj.encoder_proj (the
+    log-probs of a streaming CTC model) followed by CtcKeywordStream.search_chunk.  An event is dict(keyword, start, end, sum_logp,
+    score): frames are absolute since creation or reset."""
+
+    def __init__(self, model: "Model", keywords: Keywords):
+        self._m = model
+        self._L = model._L
+        _bind_ctc_kws(self._L)
+        h = C.c_void_p()
+        model._chk(self._L.k2hip_ctc_kws_stream_create(model.handle, keywords._h, C.byref(h)))
+        self._h = h
+        self._S = keywords.num_states
+        model._children.add(self)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.k2hip_ctc_kws_stream_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self):
+        self._m._chk(self._L.k2hip_ctc_kws_stream_reset(self._h))
+
+    def num_frames(self) -> int:
+        return int(self._L.k2hip_ctc_kws_stream_num_frames(self._h))
+
+    @staticmethod
+    def search_chunk(streams: Sequence["CtcKeywordStream"], log_probs, n_frames=None):
+        """continue every stream's search over log_probs [B, Tc, V] (k2hip_ctc_kws_search_chunk); n_frames [B]: the frames of each stream
+        that count (default all Tc; 0 leaves a stream untouched).  The streams may walk different graphs."""
+        m = streams[0]._m
+        e = _f32(log_probs)
+        B = len(streams)
+        if e.ndim != 3 or e.shape[0] != B or e.shape[2] != m.vocab_size:
+            raise ValueError(f"search_chunk: log_probs {e.shape} for {B} streams of vocab_size {m.vocab_size}")
+        nf = None if n_frames is None else np.ascontiguousarray(n_frames, dtype=np.int32)
+        if nf is not None and nf.shape != (B,):
+            raise ValueError(f"search_chunk: n_frames {nf.shape} for {B} streams")
+        arr = (C.c_void_p * B)(*[s._h.value for s in streams])
+        m._chk(m._L.k2hip_ctc_kws_search_chunk(m.handle, arr, B, _f(e), e.shape[1], None if nf is None else _i(nf)))
+
+    def events(self, clear: bool = False):
+        n = self._L.k2hip_ctc_kws_stream_num_events(self._h)
+        k, st, en = (np.zeros(max(n, 1), np.int32) for _ in range(3))
+        sm, sc = (np.zeros(max(n, 1), np.float32) for _ in range(2))
+        got = self._L.k2hip_ctc_kws_stream_get_events(self._h, _i(k), _i(st), _i(en), _f(sm), _f(sc), n)
+        if got < 0:
+            raise K2HipError(got, self._L.k2hip_last_error().decode())
+        if clear:
+            self._m._chk(self._L.k2hip_ctc_kws_stream_clear_events(self._h))
+        return _kws_events(k, st, en, sm, sc, n)
+
+    def state(self):
+        """the carried block (values float32 [2, S], starts int32 [2, S]; plane 0 = n, plane 1 = b) -- the debug header's view, for the
+        chunking tests"""
+        v, st = np.zeros((2, self._S), np.float32), np.zeros((2, self._S), np.int32)
+        self._m._chk(self._L.k2hip_debug_ctc_kws_stream_get_state(self._h, _f(v), _i(st), 2 * self._S))
+        return v, st
+
+
 class Model:
     """One model replica on one GPU (k2hip_model_t): the IOfflineProj operators."""
 
@@ -903,6 +988,38 @@ class Model:
                                                                    _i(n), max_events, C.byref(tp)))
         return [_kws_events(k[b], st[b], en[b], sm[b], sc[b], int(n[b])) for b in range(B)]
 
+    # ---- keyword spotting for CTC models (k2hip.h "Keyword spotting for CTC models ...")
+    def ctc_spot_keywords(self, log_probs, keywords: "Keywords", n_frames=None):
+        """fresh CTC keyword streams over host log_probs [B,T',V] in one chunk -> per stream the list of events
+        dict(keyword, start, end, sum_logp, score)"""
+        e = _f32(log_probs)
+        streams = [CtcKeywordStream(self, keywords) for _ in range(e.shape[0])]
+        try:
+            CtcKeywordStream.search_chunk(streams, e, n_frames)
+            return [s.events() for s in streams]
+        finally:
+            for s in streams:
+                s.close()
+
+    def ctc_spot_keywords_samples(self, samples: Sequence[np.ndarray], keywords: "Keywords", max_events: Optional[int] = None):
+        """k2hip_offline_ctc_spot_keywords_from_samples: samples -> fbank -> pad -> encoder on the device, then ctc_spot_keywords() over
+        all T' frames of the padded batch"""
+        _bind_ctc_kws(self._L)
+        ss = [_f32(s).reshape(-1) for s in samples]
+        B = len(ss)
+        ptrs = (fp * B)(*[_f(s) for s in ss])
+        ns = np.array([s.size for s in ss], np.int64)
+        if max_events is None:   # at most one event per frame
+            max_events = max(1, self.encoder_out_frames(int(self.fbank_num_frames(int(ns.max()))) + 19))
+        me = max(max_events, 1)
+        k, st, en = (np.zeros((B, me), np.int32) for _ in range(3))
+        sm, sc = (np.zeros((B, me), np.float32) for _ in range(2))
+        n = np.zeros(B, np.int32)
+        tp = C.c_int32(0)
+        self._chk(self._L.k2hip_offline_ctc_spot_keywords_from_samples(self._h, keywords._h, ptrs, _l(ns), B, _i(k), _i(st), _i(en), _f(sm), _f(sc),
+                                                                       _i(n), max_events, C.byref(tp)))
+        return [_kws_events(k[b], st[b], en[b], sm[b], sc[b], int(n[b])) for b in range(B)]
+
     # ---- CTC forced alignment and full-sum scoring (k2hip.h "CTC forced alignment and full-sum scoring ...")
     @staticmethod
     def _ctc_align_result(lens, ts, en, yp, tot, best):
@@ -1160,7 +1277,10 @@ class OfflineRecognizer:
         return self.model.align_samples(samples, targets)
 
     def spot_keywords(self, samples: Sequence[np.ndarray], keywords: "Keywords"):
-        """the events of `keywords` in samples[b] (Model.spot_keywords_samples; transducer models; no reference counterpart)"""
+        """the events of `keywords` in samples[b] (Model.spot_keywords_samples, or Model.ctc_spot_keywords_samples for a zipformer2ctc
+        model; no reference counterpart)"""
+        if self.model.meta("model_type") == "zipformer2ctc":
+            return self.model.ctc_spot_keywords_samples(samples, keywords)
         return self.model.spot_keywords_samples(samples, keywords)
 
 

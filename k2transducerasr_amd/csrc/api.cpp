@@ -18,6 +18,7 @@
 #include "hotwords.h"
 #include "keywords.h"
 #include "kws_ref.h"
+#include "ctc_kws_ref.h"
 #include "ngram_lm.h"
 #include "../../include/k2hip_debug.h"
 
@@ -729,9 +730,23 @@ int32_t k2hip_set_hotwords(k2hip_model_t* model, const k2hip_hotwords_t* hw) {
     });
 }
 // ---- keyword spotting (keywords.cpp, kws.hip) -----------------------------------------------------------
+// What the CTC spotter reads of a graph: the graph itself, rc(s) = the root's child whose token is tok(s) (or -1) and the table block
+// the engine uploads.  Built with the handle and shared by its CTC streams, which keep it alive after the handle is gone; streams of
+// one call that share it share one upload.
+struct CtcKwShared {
+    std::shared_ptr<const KeywordGraph> graph;
+    std::vector<int32_t> rc;
+    Engine::CtcKwsGraph tables;
+    explicit CtcKwShared(std::shared_ptr<const KeywordGraph> g) : graph(std::move(g)), rc((size_t)graph->num_states()) {
+        const KeywordGraph& k = *graph;
+        ctc_kws_root_children(k.parent().data(), k.tok().data(), k.num_states(), rc.data());
+        tables = Engine::CtcKwsGraph{k.parent().data(), k.tok().data(), k.depth().data(), k.kw().data(), k.bar().data(), rc.data(), k.num_states()};
+    }
+};
 struct k2hip_keywords {
     std::shared_ptr<const KeywordGraph> graph;
     uint64_t serial = ++g_hw_serial;   // the graph's identity for the models' caches (a handle's address can be reused)
+    std::shared_ptr<const CtcKwShared> ctc = std::make_shared<const CtcKwShared>(graph);
 };
 struct k2hip_kws_stream {
     k2hip_model* model;
@@ -1012,6 +1027,167 @@ int32_t k2hip_offline_spot_keywords_from_samples(k2hip_model_t* model, const k2h
             kws_take_events(r, b, &ev);
             const size_t o = (size_t)b * (size_t)max_events;
             kws_events_out(*res->graph, ev.data(), ev.size(), keyword ? keyword + o : nullptr, start ? start + o : nullptr, end ? end + o : nullptr,
+                           sum_logp ? sum_logp + o : nullptr, score ? score + o : nullptr, ev.size());
+            n_events[b] = (int32_t)ev.size();
+        }
+        if (Tprime_out) *Tprime_out = Tp;
+    });
+}
+// ---- keyword spotting for CTC models (ctc_kws.hip) -----------------------------------------------------------
+struct k2hip_ctc_kws_stream {
+    k2hip_model* model;
+    std::shared_ptr<const CtcKwShared> sh;
+    std::vector<float> v;            // the carried block (ctc_kws_ref.h): [2][S]
+    std::vector<int32_t> st;
+    std::vector<KwsRefEvent> events;
+    void fresh() {
+        const int S = sh->graph->num_states();
+        v.resize(2 * (size_t)S);
+        st.resize(2 * (size_t)S);
+        ctc_kws_fresh_state(S, v.data(), st.data());
+        events.clear();
+    }
+};
+// the refusals every CTC spotting entry shares, decided on the host
+static void ctc_kws_check(k2hip_model* model, const k2hip_keywords* kw, const char* who) {
+    const Config& cf = model->engine.model().cfg();
+    if (!cf.ctc) failf(K2HIP_ERR_UNSUPPORTED, "%s: model_type '%s' has no CTC head", who, cf.model_type.c_str());
+    if (kw) K2_REQUIRE(kw->graph->vocab_size() == cf.V, "%s: the graph was built for vocab_size %d, the model has %d", who, kw->graph->vocab_size(), cf.V);
+}
+int32_t k2hip_ctc_kws_stream_create(k2hip_model_t* model, const k2hip_keywords_t* kw, k2hip_ctc_kws_stream_t** out) {
+    return guard([&] {
+        NEED(model); NEED(kw); NEED(out);
+        *out = nullptr;
+        ctc_kws_check(model, kw, "ctc_kws_stream_create");
+        std::unique_ptr<k2hip_ctc_kws_stream> s(new k2hip_ctc_kws_stream{model, kw->ctc, {}, {}, {}});
+        s->fresh();
+        *out = s.release();
+    });
+}
+int32_t k2hip_ctc_kws_stream_destroy(k2hip_ctc_kws_stream_t* s) {
+    return guard([&] { delete s; });
+}
+int32_t k2hip_ctc_kws_stream_reset(k2hip_ctc_kws_stream_t* s) {
+    return guard([&] {
+        NEED(s);
+        s->fresh();
+    });
+}
+int64_t k2hip_ctc_kws_stream_num_frames(const k2hip_ctc_kws_stream_t* s) { return s ? (int64_t)s->st[0] : -1; }
+int32_t k2hip_ctc_kws_stream_num_events(const k2hip_ctc_kws_stream_t* s) { return s ? (int32_t)s->events.size() : -1; }
+int32_t k2hip_ctc_kws_stream_get_events(const k2hip_ctc_kws_stream_t* s, int32_t* keyword, int32_t* start, int32_t* end, float* sum_logp, float* score,
+                                        int32_t cap) {
+    int32_t count = 0;
+    const int32_t rc = guard([&] {
+        NEED(s);
+        K2_REQUIRE(cap >= 0, "ctc_kws_stream_get_events: cap %d", cap);
+        count = kws_events_out(*s->sh->graph, s->events.data(), s->events.size(), keyword, start, end, sum_logp, score, (size_t)cap);
+    });
+    return rc < 0 ? rc : count;
+}
+int32_t k2hip_ctc_kws_stream_clear_events(k2hip_ctc_kws_stream_t* s) {
+    return guard([&] {
+        NEED(s);
+        s->events.clear();
+    });
+}
+int32_t k2hip_debug_ctc_kws_stream_get_state(const k2hip_ctc_kws_stream_t* s, float* v, int32_t* st, int32_t cap) {
+    return guard([&] {
+        NEED(s);
+        if ((int64_t)s->v.size() > cap) failf(K2HIP_ERR_CAPACITY, "the stream's block has %zu cells", s->v.size());
+        if (v) memcpy(v, s->v.data(), sizeof(float) * s->v.size());
+        if (st) memcpy(st, s->st.data(), sizeof(int32_t) * s->st.size());
+    });
+}
+int32_t k2hip_debug_ctc_kws_ref_dp(const int32_t* parent, const int32_t* tok, const int32_t* depth, const int32_t* keyword, const float* bar,
+                                   const int32_t* rc, int32_t S, const float* log_probs, int32_t V, int32_t T, float* v, int32_t* st,
+                                   int32_t* ev_keyword, int32_t* ev_start, int32_t* ev_end, float* ev_sum, int32_t cap, int32_t* n_events) {
+    return guard([&] {
+        NEED(parent); NEED(tok); NEED(depth); NEED(keyword); NEED(bar); NEED(rc); NEED(v); NEED(st); NEED(n_events);
+        K2_REQUIRE(S >= 1 && T >= 0 && V >= 2 && cap >= 0, "ctc_kws_ref_dp: bad shape S=%d T=%d V=%d", S, T, V);
+        K2_REQUIRE(T == 0 || log_probs, "ctc_kws_ref_dp: null log_probs");
+        for (int s = 1; s < S; s++) {
+            K2_REQUIRE(parent[s] >= 0 && parent[s] < s, "ctc_kws_ref_dp: parent(%d) = %d", s, parent[s]);
+            K2_REQUIRE(tok[s] >= 1 && tok[s] < V, "ctc_kws_ref_dp: tok(%d) = %d", s, tok[s]);
+            K2_REQUIRE(rc[s] == -1 || (rc[s] >= 1 && rc[s] < S && parent[rc[s]] == 0), "ctc_kws_ref_dp: rc(%d) = %d", s, rc[s]);
+        }
+        K2_REQUIRE(st[S] == -1 || (st[S] >= 1 && st[S] < S && parent[st[S]] == 0), "ctc_kws_ref_dp: hold = %d", st[S]);
+        std::vector<KwsRefEvent> ev;
+        ctc_kws_dp_ref(parent, tok, depth, keyword, bar, rc, S, log_probs, V, T, v, st, &ev);
+        *n_events = (int32_t)ev.size();
+        if ((int64_t)ev.size() > cap) failf(K2HIP_ERR_CAPACITY, "ctc_kws_ref_dp: %zu events", ev.size());
+        for (size_t i = 0; i < ev.size(); i++) {
+            if (ev_keyword) ev_keyword[i] = ev[i].keyword;
+            if (ev_start) ev_start[i] = ev[i].start;
+            if (ev_end) ev_end[i] = ev[i].end;
+            if (ev_sum) ev_sum[i] = ev[i].sum_logp;
+        }
+    });
+}
+int32_t k2hip_ctc_kws_search_chunk(k2hip_model_t* model, k2hip_ctc_kws_stream_t* const* streams, int32_t B, const float* log_probs, int32_t Tc,
+                                   const int32_t* n_frames) {
+    return guard([&] {
+        NEED(model); NEED(streams); NEED(log_probs);
+        K2_REQUIRE(B > 0 && Tc >= 1, "ctc_kws_search_chunk: bad shape B=%d Tc=%d", B, Tc);
+        ctc_kws_check(model, nullptr, "ctc_kws_search_chunk");
+        Engine& e = model->engine;
+        std::vector<Engine::CtcKwsIO> io((size_t)B);
+        for (int b = 0; b < B; b++) {
+            k2hip_ctc_kws_stream* s = streams[b];
+            K2_REQUIRE(s != nullptr, "ctc_kws_search_chunk: stream %d is null", b);
+            K2_REQUIRE(s->model == model, "ctc_kws_search_chunk: stream %d belongs to another model", b);
+            for (int c = 0; c < b; c++) K2_REQUIRE(streams[c] != s, "ctc_kws_search_chunk: streams %d and %d are the same stream", c, b);
+            const int T = n_frames ? n_frames[b] : Tc;
+            K2_REQUIRE(T >= 0 && T <= Tc, "ctc_kws_search_chunk: stream %d: n_frames %d outside [0, %d]", b, T, Tc);
+            K2_REQUIRE((int64_t)s->st[0] + T <= INT32_MAX, "ctc_kws_search_chunk: stream %d has run out of frame numbers; reset it", b);
+            io[(size_t)b] = Engine::CtcKwsIO{&s->sh->tables, T, s->v.data(), s->st.data()};
+        }
+        Engine::KwsResult r;
+        {
+            EngineLock lk(e);
+            e.ctc_kws_chunk_host(log_probs, B, Tc, io.data(), &r);
+        }
+        for (int b = 0; b < B; b++) K2_REQUIRE(r.n[(size_t)b] >= 0 && r.n[(size_t)b] <= r.mt, "internal: stream %d reports %d events", b, r.n[(size_t)b]);
+        // nothing below fails: the call is applied to every stream or to none
+        for (int b = 0; b < B; b++) {
+            k2hip_ctc_kws_stream* s = streams[b];
+            if (io[(size_t)b].T == 0) continue;
+            const size_t n = s->v.size(), o = 2 * (size_t)r.state_off[(size_t)b];
+            memcpy(s->v.data(), r.a.data() + o, sizeof(float) * n);
+            memcpy(s->st.data(), r.st.data() + o, sizeof(int32_t) * n);
+            kws_take_events(r, b, &s->events);
+        }
+    });
+}
+int32_t k2hip_offline_ctc_spot_keywords_from_samples(k2hip_model_t* model, const k2hip_keywords_t* kw, const float* const* samples,
+                                                     const int64_t* n_samples, int32_t B, int32_t* keyword, int32_t* start, int32_t* end,
+                                                     float* sum_logp, float* score, int32_t* n_events, int32_t max_events, int32_t* Tprime_out) {
+    return guard([&] {
+        NEED(model); NEED(kw); NEED(samples); NEED(n_samples); NEED(n_events);
+        K2_REQUIRE(B > 0 && max_events >= 0, "ctc_spot_keywords_from_samples: bad shape B=%d max_events=%d", B, max_events);
+        ctc_kws_check(model, kw, "ctc_spot_keywords_from_samples");
+        Engine& e = model->engine;
+        const std::shared_ptr<const CtcKwShared> sh = kw->ctc;
+        const int S = sh->graph->num_states();
+        std::vector<float> v0(2 * (size_t)S);
+        std::vector<int32_t> s0(2 * (size_t)S);
+        ctc_kws_fresh_state(S, v0.data(), s0.data());
+        std::vector<Engine::CtcKwsIO> io((size_t)B, Engine::CtcKwsIO{&sh->tables, 0, v0.data(), s0.data()});
+        Engine::KwsResult r;
+        int32_t Tp = 0;
+        {
+            EngineLock lk(e);
+            e.ctc_kws_samples(samples, n_samples, B, io.data(), &r, &Tp);
+        }
+        for (int b = 0; b < B; b++) {
+            K2_REQUIRE(r.n[(size_t)b] >= 0 && r.n[(size_t)b] <= r.mt, "internal: stream %d reports %d events", b, r.n[(size_t)b]);
+            if (r.n[(size_t)b] > max_events) failf(K2HIP_ERR_CAPACITY, "ctc_spot_keywords_from_samples: stream %d has %d events, max_events is %d", b, r.n[(size_t)b], max_events);
+        }
+        for (int b = 0; b < B; b++) {
+            std::vector<KwsRefEvent> ev;
+            kws_take_events(r, b, &ev);
+            const size_t o = (size_t)b * (size_t)max_events;
+            kws_events_out(*sh->graph, ev.data(), ev.size(), keyword ? keyword + o : nullptr, start ? start + o : nullptr, end ? end + o : nullptr,
                            sum_logp ? sum_logp + o : nullptr, score ? score + o : nullptr, ev.size());
             n_events[b] = (int32_t)ev.size();
         }

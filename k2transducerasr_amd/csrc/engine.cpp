@@ -5,6 +5,7 @@
 #include "lattice_ref.h"
 #include "ctc_lattice_ref.h"
 #include "kws_ref.h"
+#include "ctc_kws_ref.h"
 #include "ctc_prefix_bias_ref.h"
 #include "ctc_prefix_ref.h"
 #include "hotwords.h"
@@ -686,6 +687,7 @@ Engine::SearchExtras Engine::search_device(const Ctx& c, const float* enc, int B
     if (stage.align) return align_device(c, enc, Tp, *stage.align, out);
     if (stage.ctc_align) return ctc_align_device(c, enc, B, Tp, *stage.ctc_align, out);
     if (stage.kws) return kws_device(c, enc, Tp, *stage.kws, out);
+    if (stage.ctc_kws) return ctc_kws_device(c, enc, Tp, *stage.ctc_kws, out);
     return greedy_device(c, enc, B, Tp, stage.single, out, stage.keep_nbest);
 }
 
@@ -1629,6 +1631,137 @@ void Engine::kws_samples(const float* const* samples, const int64_t* n_samples, 
     stage.kws = &p;
     offline_samples(samples, n_samples, B, stage, tok.data(), ts.data(), n.data(), Tp, false);
     kws_collect(p, Tp, std::move(tok), std::move(ts), std::move(n), res);
+    if (Tp_out) *Tp_out = Tp;
+}
+
+// ---------------------------------------------------------------------------
+// keyword spotting for CTC models: trie Viterbi on the CTC trellis (ctc_kws.hip)
+// ---------------------------------------------------------------------------
+Engine::CtcKwsPlan Engine::ctc_kws_plan(int B, int Tp, const CtcKwsIO* io, bool all_frames, int V) const {
+    const Config& cf = model_->cfg();
+    if (!cf.ctc) failf(K2HIP_ERR_UNSUPPORTED, "CTC keyword spotting: model_type '%s' has no CTC head", cf.model_type.c_str());
+    if (V == 0) V = cf.V;
+    K2_REQUIRE(B > 0 && B <= 65535 && Tp >= 1 && V >= 2 && io != nullptr, "CTC keyword spotting: bad shape B=%d T'=%d V=%d", B, Tp, V);
+    CtcKwsPlan p;
+    p.B = B; p.Tp = Tp; p.V = V;
+    p.state_off.resize((size_t)B);
+    // the call's distinct graphs (by table block) and where their tables go, in words
+    std::vector<const CtcKwsGraph*> graphs;
+    std::vector<int> tab_off, graph_of((size_t)B);
+    int tab_words = 0;
+    for (int b = 0; b < B; b++) {
+        const int T = all_frames ? Tp : io[b].T;
+        const CtcKwsGraph* g = io[b].graph;
+        K2_REQUIRE(g && g->parent && g->tok && g->depth && g->kw && g->bar && g->rc && io[b].v && io[b].st, "CTC keyword spotting: stream %d has no graph", b);
+        K2_REQUIRE(T >= 0 && T <= Tp, "CTC keyword spotting: stream %d: n_frames %d outside [0, %d]", b, T, Tp);
+        const int S = g->S;
+        K2_REQUIRE(S >= 1 && S <= kKwsMaxStates, "CTC keyword spotting: stream %d: %d trie states", b, S);
+        size_t k = 0;
+        while (k < graphs.size() && graphs[k] != g) k++;
+        if (k == graphs.size()) {
+            // everything the kernel turns into an address is checked here: parents, tokens, root children
+            for (int s = 1; s < S; s++) {
+                K2_REQUIRE(g->parent[s] >= 0 && g->parent[s] < s, "CTC keyword spotting: stream %d: parent(%d) = %d", b, s, g->parent[s]);
+                K2_REQUIRE(g->tok[s] >= 1 && g->tok[s] < V, "CTC keyword spotting: stream %d: tok(%d) = %d, the log-probs have %d columns", b, s, g->tok[s], V);
+                const int r = g->rc[s];
+                K2_REQUIRE(r == -1 || (r >= 1 && r < S && g->parent[r] == 0 && g->tok[r] == g->tok[s]), "CTC keyword spotting: stream %d: rc(%d) = %d", b, s, r);
+            }
+            graphs.push_back(g);
+            tab_off.push_back(tab_words);
+            tab_words += 6 * S;
+        }
+        graph_of[(size_t)b] = (int)k;
+        const int32_t hold = io[b].st[S], frames = io[b].st[0];
+        K2_REQUIRE(hold == -1 || (hold >= 1 && hold < S && g->parent[hold] == 0), "CTC keyword spotting: stream %d carries hold = %d", b, hold);
+        K2_REQUIRE(frames >= 0 && (int64_t)frames + T <= INT32_MAX, "CTC keyword spotting: stream %d has run out of frame numbers", b);
+        p.state_off[(size_t)b] = p.n_states;
+        p.n_states += S;
+    }
+    p.o_v = align_up((int64_t)sizeof(CtcKwsStream) * B, 16);
+    p.o_st = align_up(p.o_v + (int64_t)sizeof(float) * 2 * p.n_states, 16);
+    p.o_tab = align_up(p.o_st + (int64_t)sizeof(int32_t) * 2 * p.n_states, 16);
+    p.blob.assign((size_t)(p.o_tab + 4 * (int64_t)std::max(tab_words, 1)), 0);
+    CtcKwsStream* st = reinterpret_cast<CtcKwsStream*>(p.blob.data());
+    float* h_v = reinterpret_cast<float*>(p.blob.data() + p.o_v);
+    int32_t* h_st = reinterpret_cast<int32_t*>(p.blob.data() + p.o_st);
+    int32_t* h_tab = reinterpret_cast<int32_t*>(p.blob.data() + p.o_tab);
+    for (size_t k = 0; k < graphs.size(); k++) {
+        const CtcKwsGraph& g = *graphs[k];
+        const void* src[6] = {g.parent, g.tok, g.depth, g.kw, g.bar, g.rc};
+        for (int j = 0; j < 6; j++) memcpy(h_tab + tab_off[k] + (size_t)j * g.S, src[j], 4 * (size_t)g.S);
+    }
+    for (int b = 0; b < B; b++) {
+        const int T = all_frames ? Tp : io[b].T, S = io[b].graph->S, so = p.state_off[(size_t)b];
+        st[b] = CtcKwsStream{tab_off[(size_t)graph_of[(size_t)b]], S, b, so, T};
+        p.max_T = std::max(p.max_T, T);
+        p.max_S = std::max(p.max_S, S);
+        memcpy(h_v + 2 * (size_t)so, io[b].v, sizeof(float) * 2 * (size_t)S);
+        memcpy(h_st + 2 * (size_t)so, io[b].st, sizeof(int32_t) * 2 * (size_t)S);
+    }
+    return p;
+}
+
+Engine::SearchExtras Engine::ctc_kws_device(const Ctx& c, const float* logp, int Tp, const CtcKwsPlan& p, const SearchOut& out) {
+    K2_REQUIRE(Tp == p.Tp && out.B == p.B && out.max_tokens >= std::max(p.max_T, 1),
+               "internal: the CTC keyword plan was laid out for T'=%d B=%d, the encoder gave T'=%d B=%d", p.Tp, p.B, Tp, out.B);
+    Arena& ar = *c.arena;
+    char* d_blob = ar.take<char>((int64_t)p.blob.size());
+    CtcKwsArgs a;
+    a.log_probs = logp; a.B = p.B; a.Tp = Tp; a.V = p.V; a.max_T = p.max_T; a.max_S = p.max_S;
+    a.streams = reinterpret_cast<const CtcKwsStream*>(d_blob);
+    a.v_in = reinterpret_cast<const float*>(d_blob + p.o_v);
+    a.st_in = reinterpret_cast<const int*>(d_blob + p.o_st);
+    a.tables = reinterpret_cast<const int*>(d_blob + p.o_tab);
+    SearchExtras ex;
+    const int64_t ne = (int64_t)p.B * out.max_tokens;
+    ex.kws_start = ar.take<int>(ne);
+    ex.kws_sum = ar.take<float>(ne);
+    ex.kws_a = ar.take<float>(2 * (int64_t)p.n_states);
+    ex.kws_st = ar.take<int>(2 * (int64_t)p.n_states);
+    ex.kws_states = 2 * p.n_states;
+    a.v_out = ex.kws_a; a.st_out = ex.kws_st;
+    a.ev_keyword = out.tokens(); a.ev_end = out.timestamps(); a.n_events = out.counts(); a.max_events = out.max_tokens;
+    a.ev_start = ex.kws_start; a.ev_sum = ex.kws_sum;
+    if (!c.dry) {
+        K2_HIP(hipMemcpyAsync(d_blob, p.blob.data(), p.blob.size(), hipMemcpyHostToDevice, c.stream));
+        K2_HIP(hipMemsetAsync(out.flag(), 0, sizeof(int), c.stream));
+    }
+    ctc_trie_dp(c, a);
+    return ex;
+}
+
+void Engine::ctc_kws_chunk_host(const float* log_probs, int B, int Tc, const CtcKwsIO* io, KwsResult* res) {
+    K2_REQUIRE(log_probs != nullptr && res != nullptr, "CTC keyword spotting: bad arguments");
+    const CtcKwsPlan p = ctc_kws_plan(B, Tc, io, false);
+    const int mt = std::max(p.max_T, 1);
+    std::vector<int64_t> tok((size_t)B * mt);
+    std::vector<int32_t> ts((size_t)B * mt), n((size_t)B);
+    SearchStage stage;
+    stage.ctc_kws = &p;
+    search_host(log_probs, B, Tc, stage, tok.data(), ts.data(), n.data(), mt);
+    res->mt = mt;
+    res->keyword = std::move(tok); res->end = std::move(ts); res->n = std::move(n);
+    res->start = last_kws_start_; res->sum = last_kws_sum_; res->a = last_kws_a_; res->st = last_kws_st_;
+    res->state_off = p.state_off;
+}
+
+void Engine::ctc_kws_samples(const float* const* samples, const int64_t* n_samples, int B, const CtcKwsIO* io, KwsResult* res, int32_t* Tp_out) {
+    K2_REQUIRE(samples != nullptr && n_samples != nullptr && B > 0 && res != nullptr, "ctc_spot_keywords_from_samples: bad arguments");
+    if (!model_->cfg().ctc) failf(K2HIP_ERR_UNSUPPORTED, "CTC keyword spotting: model_type '%s' has no CTC head", model_->cfg().model_type.c_str());
+    // T' of the padded batch: every stream is searched over all of it, the frames the searches decode
+    const OfflineShape sh = samples_shape(samples, n_samples, B);
+    const int Tp = sh.Tp;
+    K2_REQUIRE(Tp > 0, "ctc_spot_keywords_from_samples: %lld samples give no encoder frame", (long long)sh.longest);
+    const CtcKwsPlan p = ctc_kws_plan(B, Tp, io, true);
+    std::vector<int64_t> tok((size_t)B * Tp);
+    std::vector<int32_t> ts((size_t)B * Tp), n((size_t)B);
+    SearchStage stage;
+    stage.ctc_kws = &p;
+    offline_samples(samples, n_samples, B, stage, tok.data(), ts.data(), n.data(), Tp, false);
+    res->mt = Tp;
+    res->keyword = std::move(tok); res->end = std::move(ts); res->n = std::move(n);
+    res->start = last_kws_start_; res->sum = last_kws_sum_; res->a = last_kws_a_; res->st = last_kws_st_;
+    res->state_off = p.state_off;
     if (Tp_out) *Tp_out = Tp;
 }
 
@@ -2615,6 +2748,65 @@ void Engine::debug_op_host(const char* op, const int64_t* iargs, int n_iargs, vo
             K2_HIP(copy_blocking(dev[11], out.timestamps(), 4 * (size_t)ne, hipMemcpyDeviceToDevice));
             K2_HIP(copy_blocking(dev[12], ex.kws_sum, 4 * (size_t)ne, hipMemcpyDeviceToDevice));
             K2_HIP(copy_blocking(dev[13], out.counts(), 4 * (size_t)B, hipMemcpyDeviceToDevice));
+        } else if (name == "ctc_trie_dp") {
+            // bufs log_probs [B][Tp][V], n_frames [B] int32 (or null), graph_of [B] int32 (or null = graph 0), the G graphs' tables back to
+            //   back, each [parent | tok | depth | kw | bar | rc] x [S_g] (bar as given), n_states [G] int32, v, st (in / out: the carried
+            //   blocks [2][S] of every stream, back to back), ev_keyword [B][Tp] int64, ev_start, ev_end [B][Tp] int32, ev_sum [B][Tp],
+            //   n_events [B] int32 (out); ints B, Tp, G, V (the log-probs' width: any, not the model's)
+            K2_REQUIRE(n_bufs == 12, "debug_op_run %s: %d buffers", op, n_bufs);
+            for (int k = 0; k < n_bufs; k++) P();
+            const int B = I(), Tp = I(), G = I(), V = I();
+            K2_REQUIRE(B > 0 && Tp > 0 && G > 0 && V >= 2, "debug_op_run %s: bad shape", op);
+            K2_REQUIRE((!bufs[1] || buf_bytes[1] >= 4 * (int64_t)B) && (!bufs[2] || buf_bytes[2] >= 4 * (int64_t)B) && bufs[4] && buf_bytes[4] >= 4 * (int64_t)G,
+                       "debug_op_run %s: n_frames / graph_of / n_states are too short", op);
+            K2_REQUIRE(dev[0] && buf_bytes[0] >= 4 * (int64_t)B * Tp * V, "debug_op_run %s: log_probs is too short", op);
+            const int32_t *nf = static_cast<const int32_t*>(bufs[1]), *gof = static_cast<const int32_t*>(bufs[2]), *ns = static_cast<const int32_t*>(bufs[4]);
+            std::vector<CtcKwsGraph> graphs((size_t)G);
+            int64_t words = 0;
+            for (int g = 0; g < G; g++) {
+                K2_REQUIRE(ns[g] >= 1 && ns[g] <= kKwsMaxStates, "debug_op_run %s: graph %d has %d states", op, g, ns[g]);
+                words += 6 * (int64_t)ns[g];
+            }
+            K2_REQUIRE(bufs[3] && buf_bytes[3] >= 4 * words, "debug_op_run %s: the tables are too short", op);
+            const int32_t* tab = static_cast<const int32_t*>(bufs[3]);
+            for (int g = 0; g < G; g++) {
+                const int S = ns[g];
+                graphs[(size_t)g] = CtcKwsGraph{tab, tab + S, tab + 2 * S, tab + 3 * S, reinterpret_cast<const float*>(tab + 4 * S), tab + 5 * S, S};
+                tab += 6 * S;
+            }
+            std::vector<CtcKwsIO> io((size_t)B);
+            int64_t cells = 0;
+            for (int b = 0; b < B; b++) {
+                const int g = gof ? gof[b] : 0;
+                K2_REQUIRE(g >= 0 && g < G, "debug_op_run %s: stream %d names graph %d", op, b, g);
+                cells += 2 * (int64_t)graphs[(size_t)g].S;
+            }
+            K2_REQUIRE(bufs[5] && bufs[6] && buf_bytes[5] >= 4 * cells && buf_bytes[6] >= 4 * cells, "debug_op_run %s: the carried blocks are too short", op);
+            cells = 0;
+            for (int b = 0; b < B; b++) {
+                const CtcKwsGraph* g = &graphs[(size_t)(gof ? gof[b] : 0)];
+                io[(size_t)b] = CtcKwsIO{g, nf ? nf[b] : Tp, static_cast<const float*>(bufs[5]) + cells, static_cast<const int32_t*>(bufs[6]) + cells};
+                cells += 2 * (int64_t)g->S;
+            }
+            const CtcKwsPlan p = ctc_kws_plan(B, Tp, io.data(), false, V);
+            const int64_t ne = (int64_t)B * Tp;
+            K2_REQUIRE(dev[7] && dev[8] && dev[9] && dev[10] && dev[11] && buf_bytes[7] >= 8 * ne && buf_bytes[8] >= 4 * ne && buf_bytes[9] >= 4 * ne &&
+                           buf_bytes[10] >= 4 * ne && buf_bytes[11] >= 4 * (int64_t)B,
+                       "debug_op_run %s: the event buffers are too short", op);
+            SearchOut out;
+            SearchExtras ex;
+            run_sized([&](const Ctx& cc) {
+                out = SearchOut(*cc.arena, B, Tp);
+                ex = ctc_kws_device(cc, static_cast<const float*>(dev[0]), Tp, p, out);
+            });
+            K2_HIP(hipStreamSynchronize(stream_));
+            K2_HIP(copy_blocking(dev[5], ex.kws_a, 4 * (size_t)cells, hipMemcpyDeviceToDevice));
+            K2_HIP(copy_blocking(dev[6], ex.kws_st, 4 * (size_t)cells, hipMemcpyDeviceToDevice));
+            K2_HIP(copy_blocking(dev[7], out.tokens(), 8 * (size_t)ne, hipMemcpyDeviceToDevice));
+            K2_HIP(copy_blocking(dev[8], ex.kws_start, 4 * (size_t)ne, hipMemcpyDeviceToDevice));
+            K2_HIP(copy_blocking(dev[9], out.timestamps(), 4 * (size_t)ne, hipMemcpyDeviceToDevice));
+            K2_HIP(copy_blocking(dev[10], ex.kws_sum, 4 * (size_t)ne, hipMemcpyDeviceToDevice));
+            K2_HIP(copy_blocking(dev[11], out.counts(), 4 * (size_t)B, hipMemcpyDeviceToDevice));
         } else if (name == "ctc_lattice") {
             // bufs log_probs [R][Tp][V], n_frames [R] int32 (or null), stream_of [H] int32 (or null), ids int64 back to back, lens [H] int32,
             //   timestamps, end_frames [H][max_tokens] int32, token_log_probs [H][max_tokens], scores [H][2] = (total, best) (out);

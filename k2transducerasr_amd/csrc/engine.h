@@ -120,6 +120,29 @@ class Engine {
     // offline_greedy_samples' fbank + pad + encoder with the spotter as the stage behind them: encoder_out stays on the device, every
     // stream is searched over all T' frames (io[b].T is not read)
     void kws_samples(const float* const* samples, const int64_t* n_samples, int B, const KwsIO* io, KwsResult* res, int32_t* Tp_out);
+    // ---- keyword spotting for CTC models: trie Viterbi on the CTC trellis (ctc_kws.hip; semantics in include/k2hip.h "Keyword spotting
+    // for CTC models") ----
+    // A graph's tables on the host, each [S]: uploaded with every call (six words per state; there are no decoder rows to keep), the
+    // streams of one call that name the same block sharing one copy.  A table block must outlive the call only.
+    struct CtcKwsGraph {
+        const int32_t *parent, *tok, *depth, *kw;
+        const float* bar;
+        const int32_t* rc;
+        int S;
+    };
+    // One stream of a chunk call: its graph, the T frames it takes (0: untouched) and its carried block (ctc_kws_ref.h): v / st [2][S]
+    struct CtcKwsIO {
+        const CtcKwsGraph* graph;
+        int T;
+        const float* v;
+        const int32_t* st;
+    };
+    // log_probs [B][Tc][V] on the host; the arguments are checked before any device work, and nothing of `io` is written.  The result is
+    // a KwsResult whose a / st hold the new blocks, stream b's 2 * S entries at 2 * state_off[b].
+    void ctc_kws_chunk_host(const float* log_probs, int B, int Tc, const CtcKwsIO* io, KwsResult* res);
+    // offline_greedy_samples' fbank + pad + encoder with the spotter as the stage behind them: the log-probs stay on the device, every
+    // stream is searched over all T' frames (io[b].T is not read)
+    void ctc_kws_samples(const float* const* samples, const int64_t* n_samples, int B, const CtcKwsIO* io, KwsResult* res, int32_t* Tp_out);
     // ---- CTC prefix beam search with N-best (ctc_prefix.hip; semantics in include/k2hip.h) ----
     // log_probs [R][Tp][V] on the host; n_frames [R] or null (= Tp).  tokens / timestamps / token_log_probs [R][nbest][max_tokens],
     // n_tokens / scores [R][nbest], n_hyps [R]: the shapes of k2hip_beam_search_nbest.  The arguments are checked on the host before
@@ -339,6 +362,19 @@ class Engine {
     void kws_collect(const KwsPlan& p, int mt, std::vector<int64_t>&& tok, std::vector<int32_t>&& ts, std::vector<int32_t>&& n, KwsResult* res) const;
     std::vector<int32_t> last_kws_start_, last_kws_st_;
     std::vector<float> last_kws_sum_, last_kws_a_;
+    // One CTC keyword-spotting call as the host lays it out before any device work: the streams' descriptors, carried blocks and the
+    // distinct graphs' tables in ONE upload
+    struct CtcKwsPlan {
+        int B = 0, Tp = 0, V = 0, max_T = 0, max_S = 0, n_states = 0;
+        int64_t o_v = 0, o_st = 0, o_tab = 0;   // byte offsets of the carried values, starts and the tables behind the descriptors
+        std::vector<int32_t> state_off;
+        std::vector<char> blob;
+    };
+    // V: the width of the log-probs, 0 = the model's vocabulary (the test hook passes planes of any width)
+    CtcKwsPlan ctc_kws_plan(int B, int Tp, const CtcKwsIO* io, bool all_frames, int V = 0) const;
+    // ctc_trie_dp into `out` (tokens = keywords, timestamps = end frames, counts = events); the new blocks and the events' starts and
+    // sums travel in the kws_* extras
+    SearchExtras ctc_kws_device(const Ctx& c, const float* logp, int Tp, const CtcKwsPlan& p, const SearchOut& out);
     // One align call as the host lays it out before any device work: the streams' descriptors, targets and contexts in ONE upload block
     struct AlignPlan {
         int B = 0, Tp = 0, max_T = 0, max_U = 0, n_ctx = 0, n_ids = 0;
@@ -385,6 +421,7 @@ class Engine {
         const AlignPlan* align = nullptr;
         const CtcAlignPlan* ctc_align = nullptr;
         const KwsPlan* kws = nullptr;
+        const CtcKwsPlan* ctc_kws = nullptr;
         // rows of its search-output block for B streams: one per stream, or one per target (several CTC targets may share a stream)
         int rows(int B) const { return ctc_align ? ctc_align->H : B; }
     };

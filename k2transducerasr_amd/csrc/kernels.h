@@ -748,6 +748,34 @@ void trie_logprobs(const Ctx& ctx, const DecJoinW& w, const KwsArgs& a);
 // token passing over the two planes, one workgroup per stream: the carried block in, events and the new carried block out
 void trie_dp(const Ctx& ctx, const KwsArgs& a);
 
+// ---- keyword spotting for CTC models: trie Viterbi on the CTC trellis (ctc_kws.hip; semantics in include/k2hip.h and ctc_kws_ref.h) ----
+// One stream of a chunk call: its graph's tables [parent | tok | depth | kw | bar | rc], each [S] words (rc(s) = the root's child whose
+// token is tok(s), or -1), at table_off words into `tables`; the first T frames of row `row` of log_probs (0 = the stream is carried
+// through unchanged); its carried block -- values [2][S] and starts [2][S], plane 0 = n, plane 1 = b -- at 2 * state_off into v_in /
+// st_in / v_out / st_out.
+struct CtcKwsStream {
+    int table_off, S, row, state_off, T;
+};
+struct CtcKwsArgs {
+    const float* log_probs = nullptr;    // [R, Tp, V]
+    int B = 0, Tp = 0, V = 0;
+    int max_T = 0, max_S = 0;            // over the call's streams
+    const CtcKwsStream* streams = nullptr;   // [B] (device)
+    const int* tables = nullptr;             // the call's distinct graphs, back to back (device)
+    const float* v_in = nullptr;
+    const int* st_in = nullptr;
+    float* v_out = nullptr;
+    int* st_out = nullptr;
+    // the events, row b of [B][max_events] each (max_events >= max_T: at most one per frame), n_events [B]
+    long long* ev_keyword = nullptr;
+    int *ev_end = nullptr, *ev_start = nullptr;
+    float* ev_sum = nullptr;
+    int* n_events = nullptr;
+    int max_events = 0;
+};
+// token passing over the log-probs, one workgroup per stream: the carried block in, events and the new carried block out
+void ctc_trie_dp(const Ctx& ctx, const CtcKwsArgs& a);
+
 // ---- CTC forced alignment and full-sum scoring (ctc_align.hip; semantics in include/k2hip.h and ctc_lattice_ref.h) ----
 // One target of a CTC align call: U tokens at ids[id_off ..], scored against row `row` of log_probs over its first T frames; its compact
 // plane [T][U + 1] (column 0: lp(t, blank), column k: lp(t, y_k)) at plane_off floats into `plane`, and its back-pointers
