@@ -59,6 +59,12 @@ int32_t k2hip_debug_stream_mirrored(const k2hip_online_stream_t* s, int32_t* ok)
  * kernel does not write shows.  tests/test_gemm_gpu.py compares the result with a float64 product computed on the host. */
 int32_t k2hip_debug_gemm_run(k2hip_model_t* model, const float* A, const float* W, const float* bias, const float* res, float* C,
                              int32_t M, int32_t N, int32_t K, int32_t act, int32_t glu, int32_t glu_cols, int32_t cfg);
+/* The fused form of an offline conv module's in_proj + GLU + depthwise conv for B streams of T frames, D channels and K taps (csrc/
+ * gemm_plan.cpp glu_dwconv_pipe_entry; host only, no model and no device): *entry = the pipe tile of the one launch (1: 128 x 64,
+ * 5: 64 x 64, 8: 128 x 128), or -1 where the two launches run -- a streaming site (streaming != 0), fewer than 256 rows, a GLU GEMM
+ * that does not run on one of these tiles or whose tile does not hold a stream, the switch K2HIP_NO_FUSED_CONV
+ * (tests/test_conv_fused_plan.py). */
+int32_t k2hip_debug_conv_fused_plan(int32_t B, int32_t T, int32_t D, int32_t K, int32_t streaming, int32_t* entry);
 /* ---- other encoder kernels ---------------------------------------------------------------------- */
 /* ONE launch of the launcher named `op` (csrc/kernels.h: attn_scores_softmax, attn_av_out, attn_av_out_ring, attn_proj_av_out_ring,
  * nonlin_av_out_ring, attn_stream_ring, attn_stream, glu_causal_conv, biasnorm, bypass, biasnorm_bypass, biasnorm_bypass_downsample,
@@ -66,7 +72,8 @@ int32_t k2hip_debug_gemm_run(k2hip_model_t* model, const float* A, const float* 
  * dwconv7x7; the Conformer's conformer_qprep, conformer_scores_softmax, conformer_softmax_shift, conformer_softmax_shift_stream,
  * slice_rows, dwconv_valid_dswish; Zipformer v1's z1_pool, z1_attn, z1_glu_conv, z1_norm_bypass, z1_attn_downsample, z1_combine, z1_mean,
  * z1_add_bcast, z1_group_rows; the LSTM's lstm_cell, lstm_cell_rows, lstm_add_frame, lstm_norm_frame, add_inplace, gather_rows,
- * scatter_rows; basicnorm, conv0_pad1_dswish, conv0_nopad_dswish; the kernels around the layers, gemm and gemm_glu_causal_conv: see below)
+ * scatter_rows; basicnorm, conv0_pad1_dswish, conv0_nopad_dswish; the kernels around the layers, gemm, gemm_glu_causal_conv and
+ * gemm_glu_dwconv1d: see below)
  * on host operands, on the
  * engine's stream.  iargs: the launcher's integer arguments in its own order (a RingRef counts as slot_stride, off; downsample_full's
  * segments put n, ld[n], col1[n], lz_Td, lz_ds, lz_Do in front; long long strides and offsets -- slot_stride, off, avg_off, len_off,
@@ -96,6 +103,12 @@ int32_t k2hip_debug_gemm_run(k2hip_model_t* model, const float* A, const float* 
  *   "gemm_glu_causal_conv": the launcher's arguments in its own order (x, wg, bg, pool, slot_stride, off, slots, wc, bc, ww, bw, sc,
  *     y, B, Tc, D, K), then a buffer of 1 int32 that the hook fills with glu_conv_ring_entry(B, Tc, D, K) (-1: no fused form, and the
  *     call is K2HIP_ERR_UNSUPPORTED with nothing launched).
+ *   "gemm_glu_dwconv1d" (tests/test_conv_fused_offline_gpu.py): the first two thirds of an OFFLINE conv module as the layer body runs
+ *     them for the shape.  bufs x [B T, D], wg [2 D, D] and bg [2 D] (the "#glu" row-interleaved in_proj: row 32 q + p = value of channel
+ *     16 q + p, row 32 q + 16 + p = its gate), wd [K][D], bd [D], y [B T, D] (out), then a buffer of 1 int32 that the hook fills with
+ *     k2hip_debug_conv_fused_plan's entry for the shape; ints B, T, D, K.  entry >= 0: ONE launch (gemm_glu_dwconv1d); -1: the two
+ *     launches -- the GLU GEMM + dwconv1d_swoosh from 256 rows on, else the plain in_proj (the hook puts the rows back in value | gate
+ *     order) + glu_dwconv1d_swoosh.  The switch K2HIP_NO_FUSED_CONV keeps the two launches.
  * The two kernels of the forced alignment (csrc/align.hip, tests/test_align_gpu.py); every stream's plane [T_b][U_b + 1] lies back to
  * back in stream order, T_b = n_frames[b] (a null buffer: Tp), U_b = lens[b]; cells outside the reachable band keep what they held:
  *   "lattice_logprobs": buffers enc [B][Tp][J], n_frames [B] int32, ids (int64, the targets back to back), lens [B] int32, stay, emit

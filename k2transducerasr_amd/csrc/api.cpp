@@ -2686,6 +2686,14 @@ int32_t k2hip_debug_set_switch(const char* env_name, int32_t value) {
         if (!tunables_set(env_name, value)) failf(K2HIP_ERR_INVALID, "unknown switch '%s'", env_name);
     });
 }
+// the offline conv module's fused form for a shape (gemm_plan.cpp glu_dwconv_pipe_entry): host only, no model, no device
+int32_t k2hip_debug_conv_fused_plan(int32_t B, int32_t T, int32_t D, int32_t K, int32_t streaming, int32_t* entry) {
+    return guard([&] {
+        NEED(entry);
+        tunables_init_from_env();
+        *entry = glu_dwconv_pipe_entry(B, T, D, K, streaming != 0);
+    });
+}
 int32_t k2hip_debug_gemm(k2hip_model_t* model, int32_t M, int32_t N, int32_t K,
                                                                  int32_t act, int32_t with_res, int32_t cfg, int32_t iters, float* ms) {
     return guard([&] {

@@ -470,7 +470,14 @@ void Engine::encoder_layer(const Ctx& c, int si, int li, int gl, float* x, const
             }
         } else {
             const float *wd = wk("conv_module%d.depthwise_conv.weight#kd", k), *bd = wk("conv_module%d.depthwise_conv.bias", k);
-            if (M >= 256 && !tunables().no_glu_epilogue) {
+            // in_proj + GLU + depthwise conv + SwooshR in ONE launch where all T rows of a stream fit the M tile of the in_proj GEMM (the
+            // low-rate stacks: T = 127 in a 128-row tile, 64 in a 64-row one): the tile that has just finished the GLU holds every frame
+            // the convolution of its channels needs, and hid is never written (conv_module 3 -> 2 launches; bit-identical to the two
+            // launches, which K2HIP_NO_FUSED_CONV keeps for the cross-check)
+            const bool fused = gemm_glu_dwconv1d(c, src, wk("conv_module%d.in_proj.weight#glu", k), wk("conv_module%d.in_proj.bias#glu", k), wd, bd, tmp2, B, T, D, K);
+            if (fused) {
+                // tmp2 holds SwooshR(depthwise_conv(GLU(in_proj(src))))
+            } else if (M >= 256 && !tunables().no_glu_epilogue) {
                 // in_proj with the GLU in its epilogue (weights interleaved at load): hid is [M, D], not [M, 2D]
                 GemmArgs g;
                 g.A = src; g.lda = D; g.W = wk("conv_module%d.in_proj.weight#glu", k); g.ldw = D; g.bias = wk("conv_module%d.in_proj.bias#glu", k);
@@ -2435,6 +2442,50 @@ void Engine::debug_op_host(const char* op, const int64_t* iargs, int n_iargs, vo
             const int entry = glu_conv_ring_entry(B, Tc, D, K);
             K2_HIP(copy_blocking(entry_out, &entry, sizeof entry, hipMemcpyHostToDevice));
             took = gemm_glu_causal_conv(c, x, wg, bg, pool, ss, off, slots, wc, bc, ww, bw, sc, y, B, Tc, D, K);
+        } else if (name == "gemm_glu_dwconv1d") {
+            // the offline conv module's in_proj + GLU + depthwise conv + SwooshR as the layer body runs it for the shape: the fused launch
+            // where glu_dwconv_pipe_entry has one, else the GLU GEMM + dwconv1d_swoosh (M >= 256), else linear + glu_dwconv1d_swoosh
+            const int wg_k = nbuf + 1, bg_k = nbuf + 2;   // (the host copies of wg and bg, for the plain in_proj below)
+            float *x = P(), *wg = P(), *bg = P(), *wd = P(), *bd = P(), *y = P();
+            const int B = I(), T = I(), D = I(), K = I();
+            int* entry_out = reinterpret_cast<int*>(P());
+            K2_REQUIRE(x && wg && bg && wd && bd && y && entry_out && buf_bytes[n_bufs - 1] >= 4, "debug_op_run gemm_glu_dwconv1d: six operands and an entry buffer of 1 int are needed");
+            K2_REQUIRE(B >= 1 && T >= 1 && D >= 16 && D % 16 == 0 && K >= 1, "debug_op_run gemm_glu_dwconv1d: B %d T %d D %d K %d", B, T, D, K);
+            const int M = B * T;
+            const int entry = glu_dwconv_pipe_entry(B, T, D, K, false);
+            K2_HIP(copy_blocking(entry_out, &entry, sizeof entry, hipMemcpyHostToDevice));
+            auto scratch = [&](size_t floats) {
+                char* p = nullptr;
+                K2_HIP(hipMalloc(&p, floats * sizeof(float)));
+                d.base.push_back(p);
+                return reinterpret_cast<float*>(p);
+            };
+            const bool fused = gemm_glu_dwconv1d(c, x, wg, bg, wd, bd, y, B, T, D, K);
+            if (fused) {
+                // (entry >= 0: the one launch has written y)
+            } else if (M >= 256 && !tunables().no_glu_epilogue) {
+                float* hid = scratch((size_t)M * D);
+                GemmArgs g;
+                g.A = x; g.lda = D; g.W = wg; g.ldw = D; g.bias = bg;
+                g.C = hid; g.ldc = D; g.M = M; g.N = 2 * D; g.K = D; g.glu = 1;
+                gemm(c, g);
+                dwconv1d_swoosh(c, hid, wd, bd, y, B, T, D, K);
+            } else {   // the plain in_proj: the "#glu" rows back in (value rows | gate rows) order (model.cpp interleaves them at load)
+                const float *hw = static_cast<const float*>(bufs[wg_k]), *hb = static_cast<const float*>(bufs[bg_k]);
+                std::vector<float> vw((size_t)2 * D * D), vb((size_t)2 * D);
+                for (int ch = 0; ch < D; ch++) {
+                    const int rv = 32 * (ch / 16) + ch % 16, rg = rv + 16;
+                    memcpy(&vw[(size_t)ch * D], &hw[(size_t)rv * D], sizeof(float) * D);
+                    memcpy(&vw[(size_t)(D + ch) * D], &hw[(size_t)rg * D], sizeof(float) * D);
+                    vb[ch] = hb[rv];
+                    vb[D + ch] = hb[rg];
+                }
+                float *wp = scratch(vw.size()), *bp = scratch(vb.size()), *hid = scratch((size_t)M * 2 * D);
+                K2_HIP(copy_blocking(wp, vw.data(), vw.size() * sizeof(float), hipMemcpyHostToDevice));
+                K2_HIP(copy_blocking(bp, vb.data(), vb.size() * sizeof(float), hipMemcpyHostToDevice));
+                linear(c, x, D, wp, bp, hid, 2 * D, M, D, 2 * D);
+                glu_dwconv1d_swoosh(c, hid, wd, bd, y, B, T, D, K);
+            }
         } else if (name == "biasnorm") {
             float *x = P(), *bias = P(), *ls = P(), *y = P();
             const int M = I(), D = I();

@@ -653,7 +653,19 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN)) void gemm_f32_mfma_dma(
 //     is issued behind that barrier, spread over group 3's MFMA slots.
 // Wave tiles of 32 MT x 32 NT; NINST % waves == 0 (every wave issues the same number of DMAs, so the counted waits are constants).
 // The per-lane byte offsets stay below 2^31: the launcher requires M * lda and N * ldw below 2^29 floats.
-template <int BM, int BN, int WM, int WN, int NST>
+//
+// DWK > 0 (15 or 31): the offline conv module's form (GemmArgs::dw_*, gemm_glu_dwconv1d).  One M tile per STREAM -- the tile of stream
+// b starts at row b dw_T (dw_T <= BM; rows >= dw_T of the tile are the next stream's, staged like any rows and never used; the A
+// staging's clamp to M - 1 keeps the last stream's inside the tensor) -- and after the K loop, instead of the shared epilogue:
+//   * bias + GLU exactly as epilogue_rows forms them, the value lanes writing xs [dw_T + DWK - 1][BN / 2] in the stage memory (free by
+//     then), frame t at row DWK / 2 + t; the DWK / 2 rows in front of and behind the stream are zeroed: the conv's padding;
+//   * thread (channel = tid % (BN / 2), frame group = tid / (BN / 2)) forms 8 consecutive frames of its channel: one LDS read per input
+//     row (a 32-lane half reads 32 consecutive channels of one row: conflict-free), each feeding the <= 8 outputs it touches from
+//     registers.  Every output's sum starts from the conv bias and takes its taps in ascending order with one fma each -- the order
+//     and the operations of k_glu_dwconv1d -- then SwooshR, and goes to C = y [M, N / 2]; `hid` does not exist.
+//   * the thread's DWK taps and its conv bias are requested in front of the K loop, beside the GEMM bias.
+// DWK == 0 compiles to what the kernel was before the form existed (every difference is an `if constexpr`).
+template <int BM, int BN, int WM, int WN, int NST, int DWK = 0>
 __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN)) void gemm_f32_mfma_pipe(GemmArgs g) {
     constexpr int BK = 32;
     constexpr int MT = WM / 32, NT = WN / 32;
@@ -678,7 +690,7 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN)) void gemm_f32_mfma_pipe
     const float* __restrict__ R = g.res;
     int mb_, nb_;
     xcd_tile(mb_, nb_, g.xcd_panels == 1 ? 0 : g.M, g.N);
-    const int m0 = mb_ * BM, n0 = nb_ * BN;
+    const int m0 = DWK > 0 ? mb_ * g.dw_T : mb_ * BM, n0 = nb_ * BN;
     const int nk = g.K / BK;
 
     unsigned long long* stamp = g.dbg ? g.dbg + ((size_t)(blockIdx.x + blockIdx.y * gridDim.x) * NW + wave) * 64 : nullptr;
@@ -828,6 +840,16 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN)) void gemm_f32_mfma_pipe
     float bias_pre[NT];
 #pragma unroll
     for (int j = 0; j < NT; j++) bias_pre[j] = g.bias ? g.bias[min(n0 + wc * WN + j * 32 + li, g.N - 1)] : 0.f;
+    // (DWK: the conv tail's taps and bias of this thread's channel, in flight under the K loop like the bias above)
+    constexpr int DW_CH = BN / 2, DW_TT = DWK > 0 ? BM * DW_CH / (64 * NW) : 1;
+    static_assert(DWK == 0 || (DW_TT == 8 && DWK % 2 == 1 && (BM + DWK - 1) * DW_CH <= NST * STAGE), "pipe: conv tail's tile form");
+    float dw_tap[DWK > 0 ? DWK : 1], dw_bias = 0.f;
+    if constexpr (DWK > 0) {
+        const float* wp = g.dw_w + (n0 >> 1) + (tid & (DW_CH - 1));   // (N % BN == 0: every channel of the tile exists)
+        dw_bias = g.dw_b[(n0 >> 1) + (tid & (DW_CH - 1))];
+#pragma unroll
+        for (int q = 0; q < DWK; q++) dw_tap[q] = wp[(long long)q * (g.N >> 1)];
+    }
 
     int kt = 0;
     const int nsteady = nk - (NST - 1);  // steps whose step kt+NST-1 exists
@@ -868,6 +890,57 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN)) void gemm_f32_mfma_pipe
 #undef K2_PIPE_READ
 #undef K2_PIPE_DMA
 
+    if constexpr (DWK > 0) {
+        constexpr int HALF = DWK / 2, lgCH = DW_CH == 64 ? 6 : DW_CH == 32 ? 5 : 4;
+        static_assert(DW_CH == 1 << lgCH, "pipe: conv tail's channel count");
+        const int T = g.dw_T;
+        float* xs = smem;      // [T + DWK - 1][DW_CH]; rows up to BM + DWK - 2 are read (their outputs are not stored), inside the stages
+        __syncthreads();       // every wave has left the stages (the last K step has no barrier behind it; its DMAs landed before it)
+        for (int e = tid; e < 2 * HALF * DW_CH; e += 64 * NW) {   // the time halo
+            const int r = e >> lgCH;
+            xs[((r < HALF ? r : T + r) << lgCH) + (e & (DW_CH - 1))] = 0.f;
+        }
+#pragma unroll
+        for (int j = 0; j < NT; j++)
+#pragma unroll
+            for (int i = 0; i < MT; i++) {
+                // (value | gate) blocks of 32 columns: the value lanes (li & 16) == 0 hold channel 16 (column / 32) + (li & 15)
+                const int ch = ((wc * WN + j * 32) >> 1) + (li & 15), lrow0 = wr * WM + i * 32 + 4 * lh;
+#pragma unroll
+                for (int r = 0; r < 16; r++) {
+                    const float v = acc[i][j][r] + bias_pre[j];
+                    const float other = __shfl_xor(v, 16, 64);
+                    const float gated = v * (1.0f / (1.0f + __expf(-other)));   // epilogue_rows' GLU, operation for operation
+                    const int lrow = lrow0 + Rows32::off(r);
+                    if ((li & 16) == 0 && lrow < T) xs[((HALF + lrow) << lgCH) + ch] = gated;
+                }
+            }
+        __syncthreads();
+        const int ch = tid & (DW_CH - 1), t0 = (tid >> lgCH) * DW_TT;
+        if (t0 < T) {
+            float o[DW_TT];
+#pragma unroll
+            for (int i = 0; i < DW_TT; i++) o[i] = dw_bias;
+            const float* xp = xs + (t0 << lgCH) + ch;
+#pragma unroll
+            for (int r = 0; r < DW_TT + DWK - 1; r++) {   // input row r of the group feeds output i through tap r - i: ascending taps per output
+                const float xv = xp[r << lgCH];
+#pragma unroll
+                for (int i = 0; i < DW_TT; i++)
+                    if (r - i >= 0 && r - i < DWK) o[i] = __builtin_fmaf(dw_tap[r - i], xv, o[i]);
+            }
+            float* yp = C + (long long)(m0 + t0) * g.ldc + (n0 >> 1) + ch;
+#pragma unroll
+            for (int i = 0; i < DW_TT; i++)
+                if (t0 + i < T) yp[(long long)i * g.ldc] = swoosh_r(o[i]);
+        }
+        K2_PIPE_STAMP()
+        if (stamp && lane == 0) {
+            stamp[62] = nstamp;
+            stamp[63] = __builtin_amdgcn_s_memrealtime();
+        }
+        return;
+    }
 #pragma unroll
     for (int j = 0; j < NT; j++)
 #pragma unroll
@@ -1671,6 +1744,28 @@ void launch_pipe(const Ctx& ctx, const GemmArgs& a) {
     hipLaunchKernelGGL((gemm_f32_mfma_pipe<BM, BN, WM, WN, NST>), grid, dim3(64 * (BM / WM) * (BN / WN)), lds, ctx.stream, a);
 }
 
+// the pipe kernel with the offline conv module's tail (gemm_glu_dwconv1d): one M tile per stream
+template <int BM, int BN, int WM, int WN, int NST, int DWK>
+void launch_pipe_dwconv(const Ctx& ctx, const GemmArgs& a) {
+    dim3 grid(a.N / BN, a.M / a.dw_T, 1);
+    size_t lds = sizeof(float) * NST * (BM + BN) * 32;
+    static LdsAttrOnce lds_attr;
+    lds_attr.ensure(gemm_f32_mfma_pipe<BM, BN, WM, WN, NST, DWK>, (int)lds);
+    K2_REQUIRE((long long)a.M * a.lda < (1ll << 29) && (long long)a.N * a.ldw < (1ll << 29), "pipe: operand too large for 31-bit lane byte offsets");
+    K2_REQUIRE(a.K % 32 == 0 && a.K >= 32 * (NST - 1), "pipe: K %d too short for %d stages", a.K, NST);
+    K2_REQUIRE(a.dw_K == DWK && a.dw_T >= 1 && a.dw_T <= BM && a.M % a.dw_T == 0 && a.N % BN == 0 && a.ldc >= a.N / 2 && a.dw_w && a.dw_b,
+               "pipe: conv tail needs whole streams of <= %d frames and whole column tiles (T %d, M %d, N %d)", BM, a.dw_T, a.M, a.N);
+    hipLaunchKernelGGL((gemm_f32_mfma_pipe<BM, BN, WM, WN, NST, DWK>), grid, dim3(64 * (BM / WM) * (BN / WN)), lds, ctx.stream, a);
+}
+template <int DWK>
+void launch_pipe_dwconv_entry(const Ctx& ctx, const GemmArgs& a, int idx) {
+    switch (idx) {   // the pipe table's entries 1, 5 and 8
+        case 1: launch_pipe_dwconv<128, 64, 32, 32, 3, DWK>(ctx, a); break;
+        case 5: launch_pipe_dwconv<64, 64, 32, 32, 3, DWK>(ctx, a); break;
+        default: launch_pipe_dwconv<128, 128, 32, 32, 3, DWK>(ctx, a); break;
+    }
+}
+
 template <int BM, int BN, int WM, int WN, int NST>
 void launch_p16(const Ctx& ctx, const GemmArgs& a) {
     dim3 grid(cdiv(a.N, BN), cdiv(a.M, BM), 1);
@@ -1803,6 +1898,33 @@ bool gemm_glu_causal_conv(const Ctx& ctx, const float* x, const float* wg, const
         case 12: launch_ring_conv_entry<12>(ctx, g); break;
         default: launch_ring_conv_entry<8>(ctx, g); break;
     }
+    K2_HIP(hipGetLastError());
+    if (ctx.instrument) K2_HIP(hipEventRecord(ctx.next_event(), ctx.stream));
+    return true;
+}
+
+bool gemm_glu_dwconv1d(const Ctx& ctx, const float* x, const float* wg, const float* bg, const float* wd, const float* bd, float* y, int B, int T,
+                       int D, int K) {
+    const int M = B * T, N = 2 * D;
+    const int entry = glu_dwconv_pipe_entry(B, T, D, K, false);
+    if (entry < 0) return false;
+    // (tallied as the two launches it replaces tally themselves, one launch fewer)
+    ctx.add_flops(2.0 * M * (double)N * D, 2.0 * M * (double)D * K, 1);
+    if (ctx.dry) return true;
+    GemmArgs g;
+    g.A = x; g.lda = D; g.W = wg; g.ldw = D; g.bias = bg; g.C = y; g.ldc = D; g.M = M; g.N = N; g.K = D;
+    g.dw_w = wd; g.dw_b = bd; g.dw_K = K; g.dw_T = T;
+    g.xcd_panels = tunables().xcd_panels;
+    if (ctx.instrument) K2_HIP(hipEventRecord(ctx.next_event(), ctx.stream));
+    if (ctx.instrument && ctx.gemm_log) {
+        GemmPlan p;
+        p.family = GemmFamily::PIPE;
+        p.BM = entry == 5 ? 64 : 128;
+        p.BN = entry == 8 ? 128 : 64;
+        ctx.gemm_log->push_back({M, N, D, 1, 0, 0, gemm_kind(g, p), 0.f});
+    }
+    if (K == 15) launch_pipe_dwconv_entry<15>(ctx, g, entry);
+    else launch_pipe_dwconv_entry<31>(ctx, g, entry);
     K2_HIP(hipGetLastError());
     if (ctx.instrument) K2_HIP(hipEventRecord(ctx.next_event(), ctx.stream));
     return true;

@@ -243,4 +243,26 @@ int glu_conv_ring_entry(int B, int Tc, int D, int K) {
     return e;
 }
 
+// Offline conv module: in_proj + GLU + depthwise conv in one launch (gemm_glu_dwconv1d) where the GLU GEMM it replaces runs on a pipe
+// tile that holds a whole stream.  The fused launch takes THAT tile -- so the in_proj sums, and with them the output, are those of the
+// two launches bit for bit -- with one M tile per stream instead of M / BM packed ones.
+int glu_dwconv_pipe_entry(int B, int T, int D, int K, bool streaming) {
+    if (streaming || tunables().no_fused_conv || tunables().no_glu_epilogue) return -1;
+    if (B < 1 || T < 1 || D < 1) return -1;
+    const long long M = (long long)B * T;
+    if (M < 256 || M * D >= (1ll << 29)) return -1;   // fewer rows: the engine runs the plain in_proj and the GLU in the conv kernel
+    if (K != 15 && K != 31) return -1;                // the tail's instantiated tap counts (odd; its LDS strip has K - 1 halo rows)
+    if (gemm_force().kind != GemmForce::AUTO) return -1;
+    GemmArgs a;
+    a.M = (int)M; a.N = 2 * D; a.K = D; a.lda = D; a.ldw = D; a.ldc = D; a.glu = 1;
+    if (a.N <= 96 || a.N % 32 != 0) return -1;        // gemm()'s own conditions for the gated epilogue
+    const GemmPlan p = plan_gemm(a, GemmForce());
+    if (p.family != GemmFamily::PIPE || (p.idx != 1 && p.idx != 5 && p.idx != 8)) return -1;   // 128x64, 64x64, 128x128
+    if (T > p.BM || a.N % p.BN != 0) return -1;       // a stream per tile; whole (value | gate) column tiles
+    // one tile per stream must not add a round of the 256 CUs to the launch (T well below BM: half-empty tiles)
+    const long long cols = a.N / p.BN;
+    if (cdiv((long long)B * cols, 256ll) > cdiv((long long)cdiv(M, (long long)p.BM) * cols, 256ll)) return -1;
+    return p.idx;
+}
+
 }  // namespace k2hip

@@ -26,6 +26,7 @@ struct Tunables {
     int no_fused_vproj = 0;       // K2HIP_NO_FUSED_VPROJ: ... as a GEMM launch of its own
     int no_fused_conv = 0;        // K2HIP_NO_FUSED_CONV: the streaming conv modules' GLU + chunk-causal depthwise conv as a launch of its own
                                   // instead of inside the in_proj GEMM's epilogue (round 5)
+                                  // (offline: the low-rate stacks' GLU GEMM + depthwise conv as two launches instead of gemm_glu_dwconv1d)
     int conformer_gemm_scores = 0;  // K2HIP_CONFORMER_GEMM_SCORES: two batched GEMMs + gather/softmax (the long-utterance form)
     int dw7_tiled = 0;            // K2HIP_DW7_TILED: the one-shot LDS-tiled 7x7 depthwise conv also for long inputs (default: the sliding LDS-DMA form)
     int dw1d_tt = 0;              // K2HIP_DW1D_TT: outputs per thread of the depthwise Conv1d (8 / 4 / 2; 0 = by grid size; tests/test_kernels_gpu.py forces each)
@@ -159,6 +160,14 @@ struct GemmArgs {
     int cf_Tc = 0, cf_K = 0;
     unsigned long long* dbg = nullptr;  // tuning only: in-kernel s_memtime stamps of the ring kernel, [workgroup][wave][64]
     int ablate = 0;  // tuning only: 1 = skip in-loop global loads, 2 = skip MFMAs, 4 = skip epilogue stores
+    // Offline conv module (gemm_glu_dwconv1d below): the in_proj GEMM over "#glu"-interleaved weights finishes with the GLU AND the
+    // depthwise Conv1d over time + bias + SwooshR of elementwise.hip's k_glu_dwconv1d<false, false> -- one M tile per stream (the tile of
+    // stream b starts at row b dw_T, its rows >= dw_T are dead), so the tile that has just finished the GLU holds every frame the
+    // convolution of its channels needs; zero rows in LDS are the time halo.  C = y [M, N / 2].  (Behind the tuning fields so that every
+    // other launch keeps its argument layout.)
+    const float* dw_w = nullptr;       // != nullptr: the fused form; taps [dw_K][N / 2] ("#kd")
+    const float* dw_b = nullptr;       // conv bias [N / 2]
+    int dw_K = 0, dw_T = 0;            // taps (15 or 31), frames per stream (<= the tile's BM)
 };
 void gemm(const Ctx& ctx, const GemmArgs& a);
 // Conv module of a streaming Zipformer2 layer, first two thirds in ONE launch: y [M, D] = SwooshR(chunk-causal depthwise conv(GLU(x Wg^T + bg)))
@@ -170,6 +179,13 @@ void gemm(const Ctx& ctx, const GemmArgs& a);
 bool gemm_glu_causal_conv(const Ctx& ctx, const float* x, const float* wg, const float* bg, float* pool, long long slot_stride, long long off,
                           const int* slots, const float* wc, const float* bc, const float* ww, const float* bw, const float* sc, float* y, int B,
                           int Tc, int D, int K);
+
+// Conv module of an offline Zipformer2 layer, first two thirds in ONE launch: y [B T, D] = SwooshR(depthwise conv_K(GLU(x Wg^T + bg)) + bd),
+// zero-padded in time per stream.  wg / bg: the "#glu" row-interleaved in_proj [2 D, D]; wd: taps [K][D] ("#kd"); bd [D].  Returns
+// false (nothing launched, nothing tallied) when glu_dwconv_pipe_entry has no fused form for the shape -- the caller then runs the GLU
+// GEMM + dwconv1d_swoosh.  Same pipe tile as that GEMM, same sums in k_glu_dwconv1d's order: bit-identical to the two launches.
+bool gemm_glu_dwconv1d(const Ctx& ctx, const float* x, const float* wg, const float* bg, const float* wd, const float* bd, float* y, int B, int T,
+                       int D, int K);
 
 // ---- GEMM tile plan (gemm_plan.cpp, host only): which kernel instantiation gemm() launches for a GemmArgs, decided without
 // launching.  The tile tables of the kernel families; a table index is the k2hip_debug_gemm cfg code that forces the entry, less the
@@ -231,6 +247,9 @@ GemmPlan plan_gemm(const GemmArgs& a, const GemmForce& f);
 int gemm_kind(const GemmArgs& a, const GemmPlan& p);  // GemmLaunchRec.kind of the launch
 // the ring entry of gemm_glu_causal_conv's fused form for B streams of Tc rows and D channels, conv kernel size K; -1 = no fused form
 int glu_conv_ring_entry(int B, int Tc, int D, int K);
+// the pipe table entry (1: 128x64, 5: 64x64, 8: 128x128) of gemm_glu_dwconv1d's fused form for B streams of T frames, D channels and K
+// taps; -1 = no fused form (streaming: the call comes from a streaming site, which has gemm_glu_causal_conv instead)
+int glu_dwconv_pipe_entry(int B, int T, int D, int K, bool streaming);
 void debug_force_gemm_cfg(int code);  // tuning hook: -1 = automatic
 GemmForce gemm_force();  // what gemm() plans under: the tuning hook's force, else K2HIP_GEMM_CFG (DEV builds)
 struct GemmForceGuard {  // forces cfg code `code` for its lifetime, automatic again on scope exit
