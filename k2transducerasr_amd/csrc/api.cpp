@@ -748,20 +748,6 @@ struct k2hip_keywords {
     uint64_t serial = ++g_hw_serial;   // the graph's identity for the models' caches (a handle's address can be reused)
     std::shared_ptr<const CtcKwShared> ctc = std::make_shared<const CtcKwShared>(graph);
 };
-struct k2hip_kws_stream {
-    k2hip_model* model;
-    std::shared_ptr<KwResident> res;
-    std::vector<float> a;            // the carried block (kws_ref.h)
-    std::vector<int32_t> start;
-    std::vector<KwsRefEvent> events;
-    void fresh() {
-        const int S = res->graph->num_states();
-        a.resize((size_t)S);
-        start.resize((size_t)S);
-        kws_fresh_state(S, a.data(), start.data());
-        events.clear();
-    }
-};
 // last reference gone: free the resident block unless the model already did
 static void kw_resident_release(KwResident* r) {
     {
@@ -879,6 +865,18 @@ int32_t k2hip_debug_keywords_get_tables(const k2hip_keywords_t* kw, int32_t* par
         if (bar) memcpy(bar, g.bar().data(), 4 * S);
     });
 }
+// the events of a k2hip_debug_*_ref_dp call into the caller's arrays
+static void kws_ref_events_out(const std::vector<KwsRefEvent>& ev, const char* who, int32_t* ev_keyword, int32_t* ev_start, int32_t* ev_end, float* ev_sum,
+                               int32_t cap, int32_t* n_events) {
+    *n_events = (int32_t)ev.size();
+    if ((int64_t)ev.size() > cap) failf(K2HIP_ERR_CAPACITY, "%s: %zu events", who, ev.size());
+    for (size_t i = 0; i < ev.size(); i++) {
+        if (ev_keyword) ev_keyword[i] = ev[i].keyword;
+        if (ev_start) ev_start[i] = ev[i].start;
+        if (ev_end) ev_end[i] = ev[i].end;
+        if (ev_sum) ev_sum[i] = ev[i].sum_logp;
+    }
+}
 int32_t k2hip_debug_kws_ref_dp(const int32_t* parent, const int32_t* depth, const int32_t* keyword, const float* bar, int32_t S, const float* stay,
                                const float* emit, int32_t T, float* a, int32_t* start, int32_t* ev_keyword, int32_t* ev_start, int32_t* ev_end,
                                float* ev_sum, int32_t cap, int32_t* n_events) {
@@ -889,214 +887,7 @@ int32_t k2hip_debug_kws_ref_dp(const int32_t* parent, const int32_t* depth, cons
         for (int s = 1; s < S; s++) K2_REQUIRE(parent[s] >= 0 && parent[s] < s, "kws_ref_dp: parent(%d) = %d", s, parent[s]);
         std::vector<KwsRefEvent> ev;
         kws_dp_ref(parent, depth, keyword, bar, S, stay, emit, T, a, start, &ev);
-        *n_events = (int32_t)ev.size();
-        if ((int64_t)ev.size() > cap) failf(K2HIP_ERR_CAPACITY, "kws_ref_dp: %zu events", ev.size());
-        for (size_t i = 0; i < ev.size(); i++) {
-            if (ev_keyword) ev_keyword[i] = ev[i].keyword;
-            if (ev_start) ev_start[i] = ev[i].start;
-            if (ev_end) ev_end[i] = ev[i].end;
-            if (ev_sum) ev_sum[i] = ev[i].sum_logp;
-        }
-    });
-}
-int32_t k2hip_kws_stream_create(k2hip_model_t* model, const k2hip_keywords_t* kw, k2hip_kws_stream_t** out) {
-    return guard([&] {
-        NEED(model); NEED(kw); NEED(out);
-        *out = nullptr;
-        std::unique_ptr<k2hip_kws_stream> s(new k2hip_kws_stream{model, kw_resident_get(model, kw, "kws_stream_create"), {}, {}, {}});
-        s->fresh();
-        *out = s.release();
-    });
-}
-int32_t k2hip_kws_stream_destroy(k2hip_kws_stream_t* s) {
-    return guard([&] { delete s; });
-}
-int32_t k2hip_kws_stream_reset(k2hip_kws_stream_t* s) {
-    return guard([&] {
-        NEED(s);
-        s->fresh();
-    });
-}
-int64_t k2hip_kws_stream_num_frames(const k2hip_kws_stream_t* s) { return s ? (int64_t)s->start[0] : -1; }
-int32_t k2hip_kws_stream_num_events(const k2hip_kws_stream_t* s) { return s ? (int32_t)s->events.size() : -1; }
-// the events of a list through the getters' common rules; depth_of: the keyword's number of tokens
-static int32_t kws_events_out(const KeywordGraph& g, const KwsRefEvent* ev, size_t n, int32_t* keyword, int32_t* start, int32_t* end, float* sum_logp,
-                              float* score, size_t cap) {
-    const size_t m = std::min(n, cap);
-    for (size_t i = 0; i < m; i++) {
-        if (keyword) keyword[i] = ev[i].keyword;
-        if (start) start[i] = ev[i].start;
-        if (end) end[i] = ev[i].end;
-        if (sum_logp) sum_logp[i] = ev[i].sum_logp;
-        if (score) score[i] = ev[i].sum_logp / (float)g.depth()[(size_t)g.terminal()[(size_t)ev[i].keyword]];
-    }
-    return (int32_t)n;
-}
-int32_t k2hip_kws_stream_get_events(const k2hip_kws_stream_t* s, int32_t* keyword, int32_t* start, int32_t* end, float* sum_logp, float* score,
-                                    int32_t cap) {
-    int32_t count = 0;
-    const int32_t rc = guard([&] {
-        NEED(s);
-        K2_REQUIRE(cap >= 0, "kws_stream_get_events: cap %d", cap);
-        count = kws_events_out(*s->res->graph, s->events.data(), s->events.size(), keyword, start, end, sum_logp, score, (size_t)cap);
-    });
-    return rc < 0 ? rc : count;
-}
-int32_t k2hip_kws_stream_clear_events(k2hip_kws_stream_t* s) {
-    return guard([&] {
-        NEED(s);
-        s->events.clear();
-    });
-}
-int32_t k2hip_debug_kws_stream_get_state(const k2hip_kws_stream_t* s, float* a, int32_t* start, int32_t cap) {
-    return guard([&] {
-        NEED(s);
-        if ((int64_t)s->a.size() > cap) failf(K2HIP_ERR_CAPACITY, "the stream's graph has %zu states", s->a.size());
-        if (a) memcpy(a, s->a.data(), sizeof(float) * s->a.size());
-        if (start) memcpy(start, s->start.data(), sizeof(int32_t) * s->start.size());
-    });
-}
-// the events of row b of a chunk result behind `into`
-static void kws_take_events(const Engine::KwsResult& r, int b, std::vector<KwsRefEvent>* into) {
-    for (int i = 0; i < r.n[(size_t)b]; i++) {
-        const size_t o = (size_t)b * r.mt + i;
-        into->push_back(KwsRefEvent{(int32_t)r.keyword[o], r.start[o], r.end[o], r.sum[o]});
-    }
-}
-int32_t k2hip_kws_search_chunk(k2hip_model_t* model, k2hip_kws_stream_t* const* streams, int32_t B, const float* enc_out, int32_t Tc,
-                               const int32_t* n_frames) {
-    return guard([&] {
-        NEED(model); NEED(streams); NEED(enc_out);
-        K2_REQUIRE(B > 0 && Tc >= 1, "kws_search_chunk: bad shape B=%d Tc=%d", B, Tc);
-        Engine& e = model->engine;
-        if (e.model().cfg().ctc) failf(K2HIP_ERR_UNSUPPORTED, "kws_search_chunk: a CTC model has no transducer lattice");
-        std::vector<Engine::KwsIO> io((size_t)B);
-        for (int b = 0; b < B; b++) {
-            k2hip_kws_stream* s = streams[b];
-            K2_REQUIRE(s != nullptr, "kws_search_chunk: stream %d is null", b);
-            K2_REQUIRE(s->model == model, "kws_search_chunk: stream %d belongs to another model", b);
-            for (int c = 0; c < b; c++) K2_REQUIRE(streams[c] != s, "kws_search_chunk: streams %d and %d are the same stream", c, b);
-            const int T = n_frames ? n_frames[b] : Tc;
-            K2_REQUIRE(T >= 0 && T <= Tc, "kws_search_chunk: stream %d: n_frames %d outside [0, %d]", b, T, Tc);
-            K2_REQUIRE((int64_t)s->start[0] + T <= INT32_MAX, "kws_search_chunk: stream %d has run out of frame numbers; reset it", b);
-            io[(size_t)b] = Engine::KwsIO{&s->res->tables, T, s->a.data(), s->start.data()};
-        }
-        Engine::KwsResult r;
-        {
-            EngineLock lk(e);
-            e.kws_chunk_host(enc_out, B, Tc, io.data(), &r);
-        }
-        for (int b = 0; b < B; b++) K2_REQUIRE(r.n[(size_t)b] >= 0 && r.n[(size_t)b] <= r.mt, "internal: stream %d reports %d events", b, r.n[(size_t)b]);
-        // nothing below fails: the call is applied to every stream or to none
-        for (int b = 0; b < B; b++) {
-            k2hip_kws_stream* s = streams[b];
-            if (io[(size_t)b].T == 0) continue;
-            const size_t S = s->a.size(), o = (size_t)r.state_off[(size_t)b];
-            memcpy(s->a.data(), r.a.data() + o, sizeof(float) * S);
-            memcpy(s->start.data(), r.st.data() + o, sizeof(int32_t) * S);
-            kws_take_events(r, b, &s->events);
-        }
-    });
-}
-int32_t k2hip_offline_spot_keywords_from_samples(k2hip_model_t* model, const k2hip_keywords_t* kw, const float* const* samples,
-                                                 const int64_t* n_samples, int32_t B, int32_t* keyword, int32_t* start, int32_t* end,
-                                                 float* sum_logp, float* score, int32_t* n_events, int32_t max_events, int32_t* Tprime_out) {
-    return guard([&] {
-        NEED(model); NEED(kw); NEED(samples); NEED(n_samples); NEED(n_events);
-        K2_REQUIRE(B > 0 && max_events >= 0, "spot_keywords_from_samples: bad shape B=%d max_events=%d", B, max_events);
-        Engine& e = model->engine;
-        if (e.model().cfg().ctc) failf(K2HIP_ERR_UNSUPPORTED, "spot_keywords_from_samples: a CTC model has no transducer lattice");
-        const std::shared_ptr<KwResident> res = kw_resident_get(model, kw, "spot_keywords_from_samples");
-        const int S = res->graph->num_states();
-        std::vector<float> a0((size_t)S);
-        std::vector<int32_t> s0((size_t)S);
-        kws_fresh_state(S, a0.data(), s0.data());
-        std::vector<Engine::KwsIO> io((size_t)B, Engine::KwsIO{&res->tables, 0, a0.data(), s0.data()});
-        Engine::KwsResult r;
-        int32_t Tp = 0;
-        {
-            EngineLock lk(e);
-            e.kws_samples(samples, n_samples, B, io.data(), &r, &Tp);
-        }
-        for (int b = 0; b < B; b++) {
-            K2_REQUIRE(r.n[(size_t)b] >= 0 && r.n[(size_t)b] <= r.mt, "internal: stream %d reports %d events", b, r.n[(size_t)b]);
-            if (r.n[(size_t)b] > max_events) failf(K2HIP_ERR_CAPACITY, "spot_keywords_from_samples: stream %d has %d events, max_events is %d", b, r.n[(size_t)b], max_events);
-        }
-        for (int b = 0; b < B; b++) {
-            std::vector<KwsRefEvent> ev;
-            kws_take_events(r, b, &ev);
-            const size_t o = (size_t)b * (size_t)max_events;
-            kws_events_out(*res->graph, ev.data(), ev.size(), keyword ? keyword + o : nullptr, start ? start + o : nullptr, end ? end + o : nullptr,
-                           sum_logp ? sum_logp + o : nullptr, score ? score + o : nullptr, ev.size());
-            n_events[b] = (int32_t)ev.size();
-        }
-        if (Tprime_out) *Tprime_out = Tp;
-    });
-}
-// ---- keyword spotting for CTC models (ctc_kws.hip) -----------------------------------------------------------
-struct k2hip_ctc_kws_stream {
-    k2hip_model* model;
-    std::shared_ptr<const CtcKwShared> sh;
-    std::vector<float> v;            // the carried block (ctc_kws_ref.h): [2][S]
-    std::vector<int32_t> st;
-    std::vector<KwsRefEvent> events;
-    void fresh() {
-        const int S = sh->graph->num_states();
-        v.resize(2 * (size_t)S);
-        st.resize(2 * (size_t)S);
-        ctc_kws_fresh_state(S, v.data(), st.data());
-        events.clear();
-    }
-};
-// the refusals every CTC spotting entry shares, decided on the host
-static void ctc_kws_check(k2hip_model* model, const k2hip_keywords* kw, const char* who) {
-    const Config& cf = model->engine.model().cfg();
-    if (!cf.ctc) failf(K2HIP_ERR_UNSUPPORTED, "%s: model_type '%s' has no CTC head", who, cf.model_type.c_str());
-    if (kw) K2_REQUIRE(kw->graph->vocab_size() == cf.V, "%s: the graph was built for vocab_size %d, the model has %d", who, kw->graph->vocab_size(), cf.V);
-}
-int32_t k2hip_ctc_kws_stream_create(k2hip_model_t* model, const k2hip_keywords_t* kw, k2hip_ctc_kws_stream_t** out) {
-    return guard([&] {
-        NEED(model); NEED(kw); NEED(out);
-        *out = nullptr;
-        ctc_kws_check(model, kw, "ctc_kws_stream_create");
-        std::unique_ptr<k2hip_ctc_kws_stream> s(new k2hip_ctc_kws_stream{model, kw->ctc, {}, {}, {}});
-        s->fresh();
-        *out = s.release();
-    });
-}
-int32_t k2hip_ctc_kws_stream_destroy(k2hip_ctc_kws_stream_t* s) {
-    return guard([&] { delete s; });
-}
-int32_t k2hip_ctc_kws_stream_reset(k2hip_ctc_kws_stream_t* s) {
-    return guard([&] {
-        NEED(s);
-        s->fresh();
-    });
-}
-int64_t k2hip_ctc_kws_stream_num_frames(const k2hip_ctc_kws_stream_t* s) { return s ? (int64_t)s->st[0] : -1; }
-int32_t k2hip_ctc_kws_stream_num_events(const k2hip_ctc_kws_stream_t* s) { return s ? (int32_t)s->events.size() : -1; }
-int32_t k2hip_ctc_kws_stream_get_events(const k2hip_ctc_kws_stream_t* s, int32_t* keyword, int32_t* start, int32_t* end, float* sum_logp, float* score,
-                                        int32_t cap) {
-    int32_t count = 0;
-    const int32_t rc = guard([&] {
-        NEED(s);
-        K2_REQUIRE(cap >= 0, "ctc_kws_stream_get_events: cap %d", cap);
-        count = kws_events_out(*s->sh->graph, s->events.data(), s->events.size(), keyword, start, end, sum_logp, score, (size_t)cap);
-    });
-    return rc < 0 ? rc : count;
-}
-int32_t k2hip_ctc_kws_stream_clear_events(k2hip_ctc_kws_stream_t* s) {
-    return guard([&] {
-        NEED(s);
-        s->events.clear();
-    });
-}
-int32_t k2hip_debug_ctc_kws_stream_get_state(const k2hip_ctc_kws_stream_t* s, float* v, int32_t* st, int32_t cap) {
-    return guard([&] {
-        NEED(s);
-        if ((int64_t)s->v.size() > cap) failf(K2HIP_ERR_CAPACITY, "the stream's block has %zu cells", s->v.size());
-        if (v) memcpy(v, s->v.data(), sizeof(float) * s->v.size());
-        if (st) memcpy(st, s->st.data(), sizeof(int32_t) * s->st.size());
+        kws_ref_events_out(ev, "kws_ref_dp", ev_keyword, ev_start, ev_end, ev_sum, cap, n_events);
     });
 }
 int32_t k2hip_debug_ctc_kws_ref_dp(const int32_t* parent, const int32_t* tok, const int32_t* depth, const int32_t* keyword, const float* bar,
@@ -1114,49 +905,232 @@ int32_t k2hip_debug_ctc_kws_ref_dp(const int32_t* parent, const int32_t* tok, co
         K2_REQUIRE(st[S] == -1 || (st[S] >= 1 && st[S] < S && parent[st[S]] == 0), "ctc_kws_ref_dp: hold = %d", st[S]);
         std::vector<KwsRefEvent> ev;
         ctc_kws_dp_ref(parent, tok, depth, keyword, bar, rc, S, log_probs, V, T, v, st, &ev);
-        *n_events = (int32_t)ev.size();
-        if ((int64_t)ev.size() > cap) failf(K2HIP_ERR_CAPACITY, "ctc_kws_ref_dp: %zu events", ev.size());
-        for (size_t i = 0; i < ev.size(); i++) {
-            if (ev_keyword) ev_keyword[i] = ev[i].keyword;
-            if (ev_start) ev_start[i] = ev[i].start;
-            if (ev_end) ev_end[i] = ev[i].end;
-            if (ev_sum) ev_sum[i] = ev[i].sum_logp;
-        }
+        kws_ref_events_out(ev, "ctc_kws_ref_dp", ev_keyword, ev_start, ev_end, ev_sum, cap, n_events);
     });
+}
+// the refusals every CTC spotting entry shares, decided on the host
+static void ctc_kws_check(k2hip_model* model, const k2hip_keywords* kw, const char* who) {
+    const Config& cf = model->engine.model().cfg();
+    if (!cf.ctc) failf(K2HIP_ERR_UNSUPPORTED, "%s: model_type '%s' has no CTC head", who, cf.model_type.c_str());
+    if (kw) K2_REQUIRE(kw->graph->vocab_size() == cf.V, "%s: the graph was built for vocab_size %d, the model has %d", who, kw->graph->vocab_size(), cf.V);
+}
+}  // extern "C"
+
+// ---- the keyword streams of both spotters (kws.hip, ctc_kws.hip): one implementation --------------------------------------------
+// What differs between the two is named by a spotter: the graph holder its streams keep alive, the carried block's width per trie state
+// and its fresh state, the refusals decided on the host and the engine's two calls.  The stream, its bookkeeping and the chunk and
+// fused entries' checks, write-back and copy-out are written once over it; the exported entries below check their pointers and pass
+// their own name `who` for the messages.
+struct LatticeSpotter {   // transducer models: the carried block is a / start [S] (kws_ref.h)
+    using Holder = KwResident;
+    using IO = Engine::KwsIO;
+    static constexpr int kWidth = 1;
+    static constexpr const char* kStateFull = "the stream's graph has %zu states";
+    static std::shared_ptr<Holder> holder(k2hip_model* model, const k2hip_keywords* kw, const char* who) { return kw_resident_get(model, kw, who); }
+    static void check_model(k2hip_model* model, const char* who) {
+        if (model->engine.model().cfg().ctc) failf(K2HIP_ERR_UNSUPPORTED, "%s: a CTC model has no transducer lattice", who);
+    }
+    static void fresh_state(int S, float* val, int32_t* st) { kws_fresh_state(S, val, st); }
+    static void chunk(Engine& e, const float* enc_out, int B, int Tc, const IO* io, Engine::KwsResult* r) { e.kws_chunk_host(enc_out, B, Tc, io, r); }
+    static void samples(Engine& e, const float* const* samples, const int64_t* n_samples, int B, const IO* io, Engine::KwsResult* r, int32_t* Tp) {
+        e.kws_samples(samples, n_samples, B, io, r, Tp);
+    }
+};
+struct CtcSpotter {       // CTC models: the carried block is v / st [2][S] (ctc_kws_ref.h)
+    using Holder = const CtcKwShared;
+    using IO = Engine::CtcKwsIO;
+    static constexpr int kWidth = 2;
+    static constexpr const char* kStateFull = "the stream's block has %zu cells";
+    static std::shared_ptr<Holder> holder(k2hip_model* model, const k2hip_keywords* kw, const char* who) {
+        ctc_kws_check(model, kw, who);
+        return kw->ctc;
+    }
+    static void check_model(k2hip_model* model, const char* who) { ctc_kws_check(model, nullptr, who); }
+    static void fresh_state(int S, float* val, int32_t* st) { ctc_kws_fresh_state(S, val, st); }
+    static void chunk(Engine& e, const float* log_probs, int B, int Tc, const IO* io, Engine::KwsResult* r) { e.ctc_kws_chunk_host(log_probs, B, Tc, io, r); }
+    static void samples(Engine& e, const float* const* samples, const int64_t* n_samples, int B, const IO* io, Engine::KwsResult* r, int32_t* Tp) {
+        e.ctc_kws_samples(samples, n_samples, B, io, r, Tp);
+    }
+};
+template <class K>
+struct KwStream {
+    using Spotter = K;
+    k2hip_model* model = nullptr;
+    std::shared_ptr<typename K::Holder> hold;
+    std::vector<float> val;          // the carried block: kWidth * S values and as many starts; st[0] counts the stream's frames
+    std::vector<int32_t> st;
+    std::vector<KwsRefEvent> events;
+    void fresh() {
+        const int S = hold->graph->num_states();
+        val.resize((size_t)K::kWidth * S);
+        st.resize((size_t)K::kWidth * S);
+        K::fresh_state(S, val.data(), st.data());
+        events.clear();
+    }
+};
+struct k2hip_kws_stream : KwStream<LatticeSpotter> {};
+struct k2hip_ctc_kws_stream : KwStream<CtcSpotter> {};
+
+namespace {
+template <class S>
+void kw_stream_create(k2hip_model* model, const k2hip_keywords* kw, S** out, const char* who) {
+    *out = nullptr;
+    std::unique_ptr<S> s(new S());
+    s->model = model;
+    s->hold = S::Spotter::holder(model, kw, who);
+    s->fresh();
+    *out = s.release();
+}
+// the events of a list through the getters' common rules; depth_of: the keyword's number of tokens
+int32_t kws_events_out(const KeywordGraph& g, const KwsRefEvent* ev, size_t n, int32_t* keyword, int32_t* start, int32_t* end, float* sum_logp, float* score,
+                       size_t cap) {
+    const size_t m = std::min(n, cap);
+    for (size_t i = 0; i < m; i++) {
+        if (keyword) keyword[i] = ev[i].keyword;
+        if (start) start[i] = ev[i].start;
+        if (end) end[i] = ev[i].end;
+        if (sum_logp) sum_logp[i] = ev[i].sum_logp;
+        if (score) score[i] = ev[i].sum_logp / (float)g.depth()[(size_t)g.terminal()[(size_t)ev[i].keyword]];
+    }
+    return (int32_t)n;
+}
+template <class S>
+int32_t kw_stream_get_events(const S* s, int32_t* keyword, int32_t* start, int32_t* end, float* sum_logp, float* score, int32_t cap, const char* who) {
+    K2_REQUIRE(cap >= 0, "%s: cap %d", who, cap);
+    return kws_events_out(*s->hold->graph, s->events.data(), s->events.size(), keyword, start, end, sum_logp, score, (size_t)cap);
+}
+template <class S>
+void kw_stream_get_state(const S* s, float* val, int32_t* st, int32_t cap) {
+    if ((int64_t)s->val.size() > cap) failf(K2HIP_ERR_CAPACITY, S::Spotter::kStateFull, s->val.size());
+    if (val) memcpy(val, s->val.data(), sizeof(float) * s->val.size());
+    if (st) memcpy(st, s->st.data(), sizeof(int32_t) * s->st.size());
+}
+// the events of row b of a chunk result behind `into`
+void kws_take_events(const Engine::KwsResult& r, int b, std::vector<KwsRefEvent>* into) {
+    for (int i = 0; i < r.n[(size_t)b]; i++) {
+        const size_t o = (size_t)b * r.mt + i;
+        into->push_back(KwsRefEvent{(int32_t)r.keyword[o], r.start[o], r.end[o], r.sum[o]});
+    }
+}
+// x: encoder_out (transducer) or log_probs (CTC), [B][Tc][.] on the host
+template <class S>
+void kw_search_chunk(k2hip_model* model, S* const* streams, int32_t B, const float* x, int32_t Tc, const int32_t* n_frames, const char* who) {
+    using K = typename S::Spotter;
+    K2_REQUIRE(B > 0 && Tc >= 1, "%s: bad shape B=%d Tc=%d", who, B, Tc);
+    K::check_model(model, who);
+    Engine& e = model->engine;
+    std::vector<typename K::IO> io((size_t)B);
+    for (int b = 0; b < B; b++) {
+        S* s = streams[b];
+        K2_REQUIRE(s != nullptr, "%s: stream %d is null", who, b);
+        K2_REQUIRE(s->model == model, "%s: stream %d belongs to another model", who, b);
+        for (int c = 0; c < b; c++) K2_REQUIRE(streams[c] != s, "%s: streams %d and %d are the same stream", who, c, b);
+        const int T = n_frames ? n_frames[b] : Tc;
+        K2_REQUIRE(T >= 0 && T <= Tc, "%s: stream %d: n_frames %d outside [0, %d]", who, b, T, Tc);
+        K2_REQUIRE((int64_t)s->st[0] + T <= INT32_MAX, "%s: stream %d has run out of frame numbers; reset it", who, b);
+        io[(size_t)b] = typename K::IO{&s->hold->tables, T, s->val.data(), s->st.data()};
+    }
+    Engine::KwsResult r;
+    {
+        EngineLock lk(e);
+        K::chunk(e, x, B, Tc, io.data(), &r);
+    }
+    for (int b = 0; b < B; b++) K2_REQUIRE(r.n[(size_t)b] >= 0 && r.n[(size_t)b] <= r.mt, "internal: stream %d reports %d events", b, r.n[(size_t)b]);
+    // nothing below fails: the call is applied to every stream or to none
+    for (int b = 0; b < B; b++) {
+        S* s = streams[b];
+        if (io[(size_t)b].T == 0) continue;
+        const size_t n = s->val.size(), o = (size_t)K::kWidth * (size_t)r.state_off[(size_t)b];
+        memcpy(s->val.data(), r.a.data() + o, sizeof(float) * n);
+        memcpy(s->st.data(), r.st.data() + o, sizeof(int32_t) * n);
+        kws_take_events(r, b, &s->events);
+    }
+}
+template <class K>
+void kw_spot_from_samples(k2hip_model* model, const k2hip_keywords* kw, const float* const* samples, const int64_t* n_samples, int32_t B, int32_t* keyword,
+                          int32_t* start, int32_t* end, float* sum_logp, float* score, int32_t* n_events, int32_t max_events, int32_t* Tprime_out,
+                          const char* who) {
+    K2_REQUIRE(B > 0 && max_events >= 0, "%s: bad shape B=%d max_events=%d", who, B, max_events);
+    const std::shared_ptr<typename K::Holder> hold = K::holder(model, kw, who);
+    Engine& e = model->engine;
+    const int S = hold->graph->num_states();
+    std::vector<float> v0((size_t)K::kWidth * S);
+    std::vector<int32_t> s0((size_t)K::kWidth * S);
+    K::fresh_state(S, v0.data(), s0.data());
+    std::vector<typename K::IO> io((size_t)B, typename K::IO{&hold->tables, 0, v0.data(), s0.data()});
+    Engine::KwsResult r;
+    int32_t Tp = 0;
+    {
+        EngineLock lk(e);
+        K::samples(e, samples, n_samples, B, io.data(), &r, &Tp);
+    }
+    for (int b = 0; b < B; b++) {
+        K2_REQUIRE(r.n[(size_t)b] >= 0 && r.n[(size_t)b] <= r.mt, "internal: stream %d reports %d events", b, r.n[(size_t)b]);
+        if (r.n[(size_t)b] > max_events) failf(K2HIP_ERR_CAPACITY, "%s: stream %d has %d events, max_events is %d", who, b, r.n[(size_t)b], max_events);
+    }
+    for (int b = 0; b < B; b++) {
+        std::vector<KwsRefEvent> ev;
+        kws_take_events(r, b, &ev);
+        const size_t o = (size_t)b * (size_t)max_events;
+        kws_events_out(*hold->graph, ev.data(), ev.size(), keyword ? keyword + o : nullptr, start ? start + o : nullptr, end ? end + o : nullptr,
+                       sum_logp ? sum_logp + o : nullptr, score ? score + o : nullptr, ev.size());
+        n_events[b] = (int32_t)ev.size();
+    }
+    if (Tprime_out) *Tprime_out = Tp;
+}
+}  // namespace
+
+extern "C" {
+// ---- keyword spotting (keywords.cpp, kws.hip) and keyword spotting for CTC models (ctc_kws.hip): the exported entries -------------
+int32_t k2hip_kws_stream_create(k2hip_model_t* model, const k2hip_keywords_t* kw, k2hip_kws_stream_t** out) {
+    return guard([&] { NEED(model); NEED(kw); NEED(out); kw_stream_create(model, kw, out, "kws_stream_create"); });
+}
+int32_t k2hip_ctc_kws_stream_create(k2hip_model_t* model, const k2hip_keywords_t* kw, k2hip_ctc_kws_stream_t** out) {
+    return guard([&] { NEED(model); NEED(kw); NEED(out); kw_stream_create(model, kw, out, "ctc_kws_stream_create"); });
+}
+int32_t k2hip_kws_stream_destroy(k2hip_kws_stream_t* s) { return guard([&] { delete s; }); }
+int32_t k2hip_ctc_kws_stream_destroy(k2hip_ctc_kws_stream_t* s) { return guard([&] { delete s; }); }
+int32_t k2hip_kws_stream_reset(k2hip_kws_stream_t* s) { return guard([&] { NEED(s); s->fresh(); }); }
+int32_t k2hip_ctc_kws_stream_reset(k2hip_ctc_kws_stream_t* s) { return guard([&] { NEED(s); s->fresh(); }); }
+int64_t k2hip_kws_stream_num_frames(const k2hip_kws_stream_t* s) { return s ? (int64_t)s->st[0] : -1; }
+int64_t k2hip_ctc_kws_stream_num_frames(const k2hip_ctc_kws_stream_t* s) { return s ? (int64_t)s->st[0] : -1; }
+int32_t k2hip_kws_stream_num_events(const k2hip_kws_stream_t* s) { return s ? (int32_t)s->events.size() : -1; }
+int32_t k2hip_ctc_kws_stream_num_events(const k2hip_ctc_kws_stream_t* s) { return s ? (int32_t)s->events.size() : -1; }
+int32_t k2hip_kws_stream_get_events(const k2hip_kws_stream_t* s, int32_t* keyword, int32_t* start, int32_t* end, float* sum_logp, float* score,
+                                    int32_t cap) {
+    int32_t count = 0;
+    const int32_t rc = guard([&] { NEED(s); count = kw_stream_get_events(s, keyword, start, end, sum_logp, score, cap, "kws_stream_get_events"); });
+    return rc < 0 ? rc : count;
+}
+int32_t k2hip_ctc_kws_stream_get_events(const k2hip_ctc_kws_stream_t* s, int32_t* keyword, int32_t* start, int32_t* end, float* sum_logp, float* score,
+                                        int32_t cap) {
+    int32_t count = 0;
+    const int32_t rc = guard([&] { NEED(s); count = kw_stream_get_events(s, keyword, start, end, sum_logp, score, cap, "ctc_kws_stream_get_events"); });
+    return rc < 0 ? rc : count;
+}
+int32_t k2hip_kws_stream_clear_events(k2hip_kws_stream_t* s) { return guard([&] { NEED(s); s->events.clear(); }); }
+int32_t k2hip_ctc_kws_stream_clear_events(k2hip_ctc_kws_stream_t* s) { return guard([&] { NEED(s); s->events.clear(); }); }
+int32_t k2hip_debug_kws_stream_get_state(const k2hip_kws_stream_t* s, float* a, int32_t* start, int32_t cap) {
+    return guard([&] { NEED(s); kw_stream_get_state(s, a, start, cap); });
+}
+int32_t k2hip_debug_ctc_kws_stream_get_state(const k2hip_ctc_kws_stream_t* s, float* v, int32_t* st, int32_t cap) {
+    return guard([&] { NEED(s); kw_stream_get_state(s, v, st, cap); });
+}
+int32_t k2hip_kws_search_chunk(k2hip_model_t* model, k2hip_kws_stream_t* const* streams, int32_t B, const float* enc_out, int32_t Tc,
+                               const int32_t* n_frames) {
+    return guard([&] { NEED(model); NEED(streams); NEED(enc_out); kw_search_chunk(model, streams, B, enc_out, Tc, n_frames, "kws_search_chunk"); });
 }
 int32_t k2hip_ctc_kws_search_chunk(k2hip_model_t* model, k2hip_ctc_kws_stream_t* const* streams, int32_t B, const float* log_probs, int32_t Tc,
                                    const int32_t* n_frames) {
+    return guard([&] { NEED(model); NEED(streams); NEED(log_probs); kw_search_chunk(model, streams, B, log_probs, Tc, n_frames, "ctc_kws_search_chunk"); });
+}
+int32_t k2hip_offline_spot_keywords_from_samples(k2hip_model_t* model, const k2hip_keywords_t* kw, const float* const* samples,
+                                                 const int64_t* n_samples, int32_t B, int32_t* keyword, int32_t* start, int32_t* end,
+                                                 float* sum_logp, float* score, int32_t* n_events, int32_t max_events, int32_t* Tprime_out) {
     return guard([&] {
-        NEED(model); NEED(streams); NEED(log_probs);
-        K2_REQUIRE(B > 0 && Tc >= 1, "ctc_kws_search_chunk: bad shape B=%d Tc=%d", B, Tc);
-        ctc_kws_check(model, nullptr, "ctc_kws_search_chunk");
-        Engine& e = model->engine;
-        std::vector<Engine::CtcKwsIO> io((size_t)B);
-        for (int b = 0; b < B; b++) {
-            k2hip_ctc_kws_stream* s = streams[b];
-            K2_REQUIRE(s != nullptr, "ctc_kws_search_chunk: stream %d is null", b);
-            K2_REQUIRE(s->model == model, "ctc_kws_search_chunk: stream %d belongs to another model", b);
-            for (int c = 0; c < b; c++) K2_REQUIRE(streams[c] != s, "ctc_kws_search_chunk: streams %d and %d are the same stream", c, b);
-            const int T = n_frames ? n_frames[b] : Tc;
-            K2_REQUIRE(T >= 0 && T <= Tc, "ctc_kws_search_chunk: stream %d: n_frames %d outside [0, %d]", b, T, Tc);
-            K2_REQUIRE((int64_t)s->st[0] + T <= INT32_MAX, "ctc_kws_search_chunk: stream %d has run out of frame numbers; reset it", b);
-            io[(size_t)b] = Engine::CtcKwsIO{&s->sh->tables, T, s->v.data(), s->st.data()};
-        }
-        Engine::KwsResult r;
-        {
-            EngineLock lk(e);
-            e.ctc_kws_chunk_host(log_probs, B, Tc, io.data(), &r);
-        }
-        for (int b = 0; b < B; b++) K2_REQUIRE(r.n[(size_t)b] >= 0 && r.n[(size_t)b] <= r.mt, "internal: stream %d reports %d events", b, r.n[(size_t)b]);
-        // nothing below fails: the call is applied to every stream or to none
-        for (int b = 0; b < B; b++) {
-            k2hip_ctc_kws_stream* s = streams[b];
-            if (io[(size_t)b].T == 0) continue;
-            const size_t n = s->v.size(), o = 2 * (size_t)r.state_off[(size_t)b];
-            memcpy(s->v.data(), r.a.data() + o, sizeof(float) * n);
-            memcpy(s->st.data(), r.st.data() + o, sizeof(int32_t) * n);
-            kws_take_events(r, b, &s->events);
-        }
+        NEED(model); NEED(kw); NEED(samples); NEED(n_samples); NEED(n_events);
+        kw_spot_from_samples<LatticeSpotter>(model, kw, samples, n_samples, B, keyword, start, end, sum_logp, score, n_events, max_events, Tprime_out,
+                                             "spot_keywords_from_samples");
     });
 }
 int32_t k2hip_offline_ctc_spot_keywords_from_samples(k2hip_model_t* model, const k2hip_keywords_t* kw, const float* const* samples,
@@ -1164,34 +1138,8 @@ int32_t k2hip_offline_ctc_spot_keywords_from_samples(k2hip_model_t* model, const
                                                      float* sum_logp, float* score, int32_t* n_events, int32_t max_events, int32_t* Tprime_out) {
     return guard([&] {
         NEED(model); NEED(kw); NEED(samples); NEED(n_samples); NEED(n_events);
-        K2_REQUIRE(B > 0 && max_events >= 0, "ctc_spot_keywords_from_samples: bad shape B=%d max_events=%d", B, max_events);
-        ctc_kws_check(model, kw, "ctc_spot_keywords_from_samples");
-        Engine& e = model->engine;
-        const std::shared_ptr<const CtcKwShared> sh = kw->ctc;
-        const int S = sh->graph->num_states();
-        std::vector<float> v0(2 * (size_t)S);
-        std::vector<int32_t> s0(2 * (size_t)S);
-        ctc_kws_fresh_state(S, v0.data(), s0.data());
-        std::vector<Engine::CtcKwsIO> io((size_t)B, Engine::CtcKwsIO{&sh->tables, 0, v0.data(), s0.data()});
-        Engine::KwsResult r;
-        int32_t Tp = 0;
-        {
-            EngineLock lk(e);
-            e.ctc_kws_samples(samples, n_samples, B, io.data(), &r, &Tp);
-        }
-        for (int b = 0; b < B; b++) {
-            K2_REQUIRE(r.n[(size_t)b] >= 0 && r.n[(size_t)b] <= r.mt, "internal: stream %d reports %d events", b, r.n[(size_t)b]);
-            if (r.n[(size_t)b] > max_events) failf(K2HIP_ERR_CAPACITY, "ctc_spot_keywords_from_samples: stream %d has %d events, max_events is %d", b, r.n[(size_t)b], max_events);
-        }
-        for (int b = 0; b < B; b++) {
-            std::vector<KwsRefEvent> ev;
-            kws_take_events(r, b, &ev);
-            const size_t o = (size_t)b * (size_t)max_events;
-            kws_events_out(*sh->graph, ev.data(), ev.size(), keyword ? keyword + o : nullptr, start ? start + o : nullptr, end ? end + o : nullptr,
-                           sum_logp ? sum_logp + o : nullptr, score ? score + o : nullptr, ev.size());
-            n_events[b] = (int32_t)ev.size();
-        }
-        if (Tprime_out) *Tprime_out = Tp;
+        kw_spot_from_samples<CtcSpotter>(model, kw, samples, n_samples, B, keyword, start, end, sum_logp, score, n_events, max_events, Tprime_out,
+                                         "ctc_spot_keywords_from_samples");
     });
 }
 // ---- n-gram LM shallow fusion (ngram_lm.cpp) -----------------------------------------------------------

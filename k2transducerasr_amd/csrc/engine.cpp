@@ -1370,50 +1370,6 @@ void Engine::search_host(const float* enc_out, int B, int Tp, const SearchStage&
 // ---------------------------------------------------------------------------
 // forced alignment and full-sum scoring (align.hip)
 // ---------------------------------------------------------------------------
-Engine::AlignPlan Engine::align_plan(int B, int Tp, const int32_t* n_frames, const int64_t* ids, const int32_t* lens, int max_tokens) const {
-    const Config& cf = model_->cfg();
-    if (cf.ctc) failf(K2HIP_ERR_UNSUPPORTED, "align: a CTC model has no transducer lattice");
-    K2_REQUIRE(cf.ctx == 2, "align: decoder context size %d (2 is built)", cf.ctx);
-    lattice_check_targets(cf.V, B, Tp, n_frames, ids, lens);
-    AlignPlan p;
-    p.B = B; p.Tp = Tp;
-    for (int b = 0; b < B; b++) {
-        if (lens[b] > max_tokens) failf(K2HIP_ERR_CAPACITY, "align: stream %d has %d target tokens, max_tokens is %d", b, lens[b], max_tokens);
-        K2_REQUIRE(lens[b] <= kAlignMaxU, "align: stream %d has %d target tokens (at most %d)", b, lens[b], kAlignMaxU);
-        p.n_ids += lens[b];
-        p.n_ctx += lens[b] + 1;
-    }
-    p.o_ids = align_up((int64_t)sizeof(AlignStream) * B, 16);
-    p.o_ctx = align_up(p.o_ids + (int64_t)sizeof(int) * p.n_ids, 16);
-    p.blob.assign((size_t)(p.o_ctx + (int64_t)sizeof(long long) * 2 * p.n_ctx), 0);
-    AlignStream* st = reinterpret_cast<AlignStream*>(p.blob.data());
-    int* h_ids = reinterpret_cast<int*>(p.blob.data() + p.o_ids);
-    long long* h_ctx = reinterpret_cast<long long*>(p.blob.data() + p.o_ctx);
-    int io = 0, co = 0;
-    for (int b = 0; b < B; b++) {
-        const int T = n_frames ? n_frames[b] : Tp, U = lens[b];
-        st[b] = AlignStream{p.plane_floats, p.bp_words, co, io, U, T};
-        p.plane_floats += (long long)T * (U + 1);
-        p.bp_words += (long long)T * ((U + 1 + 63) / 64);
-        p.max_T = std::max(p.max_T, T);
-        p.max_U = std::max(p.max_U, U);
-        // the context of position u: the last two ids of [blank, blank, y_1 .. y_u] (the offline beam search's start state)
-        long long y0 = K2HIP_BLANK_ID, y1 = K2HIP_BLANK_ID;
-        for (int u = 0; u <= U; u++) {
-            h_ctx[2 * (co + u)] = y0;
-            h_ctx[2 * (co + u) + 1] = y1;
-            if (u < U) {
-                h_ids[io + u] = (int)ids[io + u];
-                y0 = y1;
-                y1 = ids[io + u];
-            }
-        }
-        io += U;
-        co += U + 1;
-    }
-    return p;
-}
-
 Engine::SearchExtras Engine::align_device(const Ctx& c, const float* enc, int Tp, const AlignPlan& p, const SearchOut& out, float* stay,
                                           float* emit, bool cells, bool dp) {
     K2_REQUIRE(Tp == p.Tp && out.B == p.B, "internal: the align plan was laid out for T'=%d B=%d, the encoder gave T'=%d B=%d", p.Tp, p.B, Tp, out.B);
@@ -1477,10 +1433,7 @@ void Engine::align_samples(const float* const* samples, const int64_t* n_samples
     K2_REQUIRE(samples != nullptr && n_samples != nullptr && B > 0 && max_tokens >= 0, "align_from_samples: bad arguments");
     const Config& cf = model_->cfg();
     if (cf.ctc) failf(K2HIP_ERR_UNSUPPORTED, "align: a CTC model has no transducer lattice");
-    // T' of the padded batch: every stream is aligned over all of it, the frames the searches decode
-    const OfflineShape sh = samples_shape(samples, n_samples, B);
-    const int Tp = sh.Tp;
-    K2_REQUIRE(Tp > 0, "align_from_samples: %lld samples give no encoder frame", (long long)sh.longest);
+    const int Tp = samples_frames("align_from_samples", samples, n_samples, B);
     const AlignPlan p = align_plan(B, Tp, nullptr, ids, lens, max_tokens);
     AlignScratch s(B, max_tokens);
     SearchStage stage;
@@ -1493,8 +1446,6 @@ void Engine::align_samples(const float* const* samples, const int64_t* n_samples
 // ---------------------------------------------------------------------------
 // keyword spotting: trie Viterbi on the lattice (kws.hip)
 // ---------------------------------------------------------------------------
-static_assert(kKwsMaxStates == kKeywordsMaxStates, "the kernel's and the graph builder's state limit are one number");
-
 void* Engine::kws_graph_upload(const KeywordGraph& g, KwsGraphDev* out) {
     const Config& cf = model_->cfg();
     if (cf.ctc) failf(K2HIP_ERR_UNSUPPORTED, "keyword spotting: a CTC model has no transducer lattice");
@@ -1535,39 +1486,6 @@ void* Engine::kws_graph_upload(const KeywordGraph& g, KwsGraphDev* out) {
     return d;
 }
 
-Engine::KwsPlan Engine::kws_plan(int B, int Tp, const KwsIO* io, bool all_frames) const {
-    const Config& cf = model_->cfg();
-    if (cf.ctc) failf(K2HIP_ERR_UNSUPPORTED, "keyword spotting: a CTC model has no transducer lattice");
-    K2_REQUIRE(B > 0 && B <= 65535 && Tp >= 1 && io != nullptr, "keyword spotting: bad shape B=%d T'=%d", B, Tp);
-    KwsPlan p;
-    p.B = B; p.Tp = Tp;
-    p.state_off.resize((size_t)B);
-    for (int b = 0; b < B; b++) {
-        const int T = all_frames ? Tp : io[b].T;
-        K2_REQUIRE(io[b].graph && io[b].graph->dec && io[b].a && io[b].start, "keyword spotting: stream %d has no resident graph", b);
-        K2_REQUIRE(T >= 0 && T <= Tp, "keyword spotting: stream %d: n_frames %d outside [0, %d]", b, T, Tp);
-        K2_REQUIRE(io[b].graph->S >= 1 && io[b].graph->S <= kKwsMaxStates, "keyword spotting: stream %d: %d trie states", b, io[b].graph->S);
-        p.state_off[(size_t)b] = p.n_states;
-        p.n_states += io[b].graph->S;
-    }
-    p.o_a = align_up((int64_t)sizeof(KwsStream) * B, 16);
-    p.o_st = align_up(p.o_a + (int64_t)sizeof(float) * p.n_states, 16);
-    p.blob.assign((size_t)(p.o_st + (int64_t)sizeof(int32_t) * p.n_states), 0);
-    KwsStream* st = reinterpret_cast<KwsStream*>(p.blob.data());
-    float* h_a = reinterpret_cast<float*>(p.blob.data() + p.o_a);
-    int32_t* h_st = reinterpret_cast<int32_t*>(p.blob.data() + p.o_st);
-    for (int b = 0; b < B; b++) {
-        const int T = all_frames ? Tp : io[b].T, S = io[b].graph->S, so = p.state_off[(size_t)b];
-        st[b] = KwsStream{*io[b].graph, p.plane_floats, so, T};
-        p.plane_floats += (long long)T * S;
-        p.max_T = std::max(p.max_T, T);
-        p.max_S = std::max(p.max_S, S);
-        memcpy(h_a + so, io[b].a, sizeof(float) * (size_t)S);
-        memcpy(h_st + so, io[b].start, sizeof(int32_t) * (size_t)S);
-    }
-    return p;
-}
-
 Engine::SearchExtras Engine::kws_device(const Ctx& c, const float* enc, int Tp, const KwsPlan& p, const SearchOut& out, float* stay, float* emit,
                                         bool cells, bool dp) {
     K2_REQUIRE(Tp == p.Tp && out.B == p.B && out.max_tokens >= std::max(p.max_T, 1),
@@ -1599,7 +1517,7 @@ Engine::SearchExtras Engine::kws_device(const Ctx& c, const float* enc, int Tp, 
     return ex;
 }
 
-void Engine::kws_collect(const KwsPlan& p, int mt, std::vector<int64_t>&& tok, std::vector<int32_t>&& ts, std::vector<int32_t>&& n,
+void Engine::kws_collect(const std::vector<int32_t>& state_off, int mt, std::vector<int64_t>&& tok, std::vector<int32_t>&& ts, std::vector<int32_t>&& n,
                          KwsResult* res) const {
     res->mt = mt;
     res->keyword = std::move(tok);
@@ -1609,7 +1527,7 @@ void Engine::kws_collect(const KwsPlan& p, int mt, std::vector<int64_t>&& tok, s
     res->sum = last_kws_sum_;
     res->a = last_kws_a_;
     res->st = last_kws_st_;
-    res->state_off = p.state_off;
+    res->state_off = state_off;
 }
 
 void Engine::kws_chunk_host(const float* enc_out, int B, int Tc, const KwsIO* io, KwsResult* res) {
@@ -1621,93 +1539,26 @@ void Engine::kws_chunk_host(const float* enc_out, int B, int Tc, const KwsIO* io
     SearchStage stage;
     stage.kws = &p;
     search_host(enc_out, B, Tc, stage, tok.data(), ts.data(), n.data(), mt);
-    kws_collect(p, mt, std::move(tok), std::move(ts), std::move(n), res);
+    kws_collect(p.state_off, mt, std::move(tok), std::move(ts), std::move(n), res);
 }
 
 void Engine::kws_samples(const float* const* samples, const int64_t* n_samples, int B, const KwsIO* io, KwsResult* res, int32_t* Tp_out) {
     K2_REQUIRE(samples != nullptr && n_samples != nullptr && B > 0 && res != nullptr, "spot_keywords_from_samples: bad arguments");
     if (model_->cfg().ctc) failf(K2HIP_ERR_UNSUPPORTED, "keyword spotting: a CTC model has no transducer lattice");
-    // T' of the padded batch: every stream is searched over all of it, the frames the searches decode
-    const OfflineShape sh = samples_shape(samples, n_samples, B);
-    const int Tp = sh.Tp;
-    K2_REQUIRE(Tp > 0, "spot_keywords_from_samples: %lld samples give no encoder frame", (long long)sh.longest);
+    const int Tp = samples_frames("spot_keywords_from_samples", samples, n_samples, B);
     const KwsPlan p = kws_plan(B, Tp, io, true);
     std::vector<int64_t> tok((size_t)B * Tp);
     std::vector<int32_t> ts((size_t)B * Tp), n((size_t)B);
     SearchStage stage;
     stage.kws = &p;
     offline_samples(samples, n_samples, B, stage, tok.data(), ts.data(), n.data(), Tp, false);
-    kws_collect(p, Tp, std::move(tok), std::move(ts), std::move(n), res);
+    kws_collect(p.state_off, Tp, std::move(tok), std::move(ts), std::move(n), res);
     if (Tp_out) *Tp_out = Tp;
 }
 
 // ---------------------------------------------------------------------------
 // keyword spotting for CTC models: trie Viterbi on the CTC trellis (ctc_kws.hip)
 // ---------------------------------------------------------------------------
-Engine::CtcKwsPlan Engine::ctc_kws_plan(int B, int Tp, const CtcKwsIO* io, bool all_frames, int V) const {
-    const Config& cf = model_->cfg();
-    if (!cf.ctc) failf(K2HIP_ERR_UNSUPPORTED, "CTC keyword spotting: model_type '%s' has no CTC head", cf.model_type.c_str());
-    if (V == 0) V = cf.V;
-    K2_REQUIRE(B > 0 && B <= 65535 && Tp >= 1 && V >= 2 && io != nullptr, "CTC keyword spotting: bad shape B=%d T'=%d V=%d", B, Tp, V);
-    CtcKwsPlan p;
-    p.B = B; p.Tp = Tp; p.V = V;
-    p.state_off.resize((size_t)B);
-    // the call's distinct graphs (by table block) and where their tables go, in words
-    std::vector<const CtcKwsGraph*> graphs;
-    std::vector<int> tab_off, graph_of((size_t)B);
-    int tab_words = 0;
-    for (int b = 0; b < B; b++) {
-        const int T = all_frames ? Tp : io[b].T;
-        const CtcKwsGraph* g = io[b].graph;
-        K2_REQUIRE(g && g->parent && g->tok && g->depth && g->kw && g->bar && g->rc && io[b].v && io[b].st, "CTC keyword spotting: stream %d has no graph", b);
-        K2_REQUIRE(T >= 0 && T <= Tp, "CTC keyword spotting: stream %d: n_frames %d outside [0, %d]", b, T, Tp);
-        const int S = g->S;
-        K2_REQUIRE(S >= 1 && S <= kKwsMaxStates, "CTC keyword spotting: stream %d: %d trie states", b, S);
-        size_t k = 0;
-        while (k < graphs.size() && graphs[k] != g) k++;
-        if (k == graphs.size()) {
-            // everything the kernel turns into an address is checked here: parents, tokens, root children
-            for (int s = 1; s < S; s++) {
-                K2_REQUIRE(g->parent[s] >= 0 && g->parent[s] < s, "CTC keyword spotting: stream %d: parent(%d) = %d", b, s, g->parent[s]);
-                K2_REQUIRE(g->tok[s] >= 1 && g->tok[s] < V, "CTC keyword spotting: stream %d: tok(%d) = %d, the log-probs have %d columns", b, s, g->tok[s], V);
-                const int r = g->rc[s];
-                K2_REQUIRE(r == -1 || (r >= 1 && r < S && g->parent[r] == 0 && g->tok[r] == g->tok[s]), "CTC keyword spotting: stream %d: rc(%d) = %d", b, s, r);
-            }
-            graphs.push_back(g);
-            tab_off.push_back(tab_words);
-            tab_words += 6 * S;
-        }
-        graph_of[(size_t)b] = (int)k;
-        const int32_t hold = io[b].st[S], frames = io[b].st[0];
-        K2_REQUIRE(hold == -1 || (hold >= 1 && hold < S && g->parent[hold] == 0), "CTC keyword spotting: stream %d carries hold = %d", b, hold);
-        K2_REQUIRE(frames >= 0 && (int64_t)frames + T <= INT32_MAX, "CTC keyword spotting: stream %d has run out of frame numbers", b);
-        p.state_off[(size_t)b] = p.n_states;
-        p.n_states += S;
-    }
-    p.o_v = align_up((int64_t)sizeof(CtcKwsStream) * B, 16);
-    p.o_st = align_up(p.o_v + (int64_t)sizeof(float) * 2 * p.n_states, 16);
-    p.o_tab = align_up(p.o_st + (int64_t)sizeof(int32_t) * 2 * p.n_states, 16);
-    p.blob.assign((size_t)(p.o_tab + 4 * (int64_t)std::max(tab_words, 1)), 0);
-    CtcKwsStream* st = reinterpret_cast<CtcKwsStream*>(p.blob.data());
-    float* h_v = reinterpret_cast<float*>(p.blob.data() + p.o_v);
-    int32_t* h_st = reinterpret_cast<int32_t*>(p.blob.data() + p.o_st);
-    int32_t* h_tab = reinterpret_cast<int32_t*>(p.blob.data() + p.o_tab);
-    for (size_t k = 0; k < graphs.size(); k++) {
-        const CtcKwsGraph& g = *graphs[k];
-        const void* src[6] = {g.parent, g.tok, g.depth, g.kw, g.bar, g.rc};
-        for (int j = 0; j < 6; j++) memcpy(h_tab + tab_off[k] + (size_t)j * g.S, src[j], 4 * (size_t)g.S);
-    }
-    for (int b = 0; b < B; b++) {
-        const int T = all_frames ? Tp : io[b].T, S = io[b].graph->S, so = p.state_off[(size_t)b];
-        st[b] = CtcKwsStream{tab_off[(size_t)graph_of[(size_t)b]], S, b, so, T};
-        p.max_T = std::max(p.max_T, T);
-        p.max_S = std::max(p.max_S, S);
-        memcpy(h_v + 2 * (size_t)so, io[b].v, sizeof(float) * 2 * (size_t)S);
-        memcpy(h_st + 2 * (size_t)so, io[b].st, sizeof(int32_t) * 2 * (size_t)S);
-    }
-    return p;
-}
-
 Engine::SearchExtras Engine::ctc_kws_device(const Ctx& c, const float* logp, int Tp, const CtcKwsPlan& p, const SearchOut& out) {
     K2_REQUIRE(Tp == p.Tp && out.B == p.B && out.max_tokens >= std::max(p.max_T, 1),
                "internal: the CTC keyword plan was laid out for T'=%d B=%d, the encoder gave T'=%d B=%d", p.Tp, p.B, Tp, out.B);
@@ -1746,68 +1597,26 @@ void Engine::ctc_kws_chunk_host(const float* log_probs, int B, int Tc, const Ctc
     SearchStage stage;
     stage.ctc_kws = &p;
     search_host(log_probs, B, Tc, stage, tok.data(), ts.data(), n.data(), mt);
-    res->mt = mt;
-    res->keyword = std::move(tok); res->end = std::move(ts); res->n = std::move(n);
-    res->start = last_kws_start_; res->sum = last_kws_sum_; res->a = last_kws_a_; res->st = last_kws_st_;
-    res->state_off = p.state_off;
+    kws_collect(p.state_off, mt, std::move(tok), std::move(ts), std::move(n), res);
 }
 
 void Engine::ctc_kws_samples(const float* const* samples, const int64_t* n_samples, int B, const CtcKwsIO* io, KwsResult* res, int32_t* Tp_out) {
     K2_REQUIRE(samples != nullptr && n_samples != nullptr && B > 0 && res != nullptr, "ctc_spot_keywords_from_samples: bad arguments");
     if (!model_->cfg().ctc) failf(K2HIP_ERR_UNSUPPORTED, "CTC keyword spotting: model_type '%s' has no CTC head", model_->cfg().model_type.c_str());
-    // T' of the padded batch: every stream is searched over all of it, the frames the searches decode
-    const OfflineShape sh = samples_shape(samples, n_samples, B);
-    const int Tp = sh.Tp;
-    K2_REQUIRE(Tp > 0, "ctc_spot_keywords_from_samples: %lld samples give no encoder frame", (long long)sh.longest);
+    const int Tp = samples_frames("ctc_spot_keywords_from_samples", samples, n_samples, B);
     const CtcKwsPlan p = ctc_kws_plan(B, Tp, io, true);
     std::vector<int64_t> tok((size_t)B * Tp);
     std::vector<int32_t> ts((size_t)B * Tp), n((size_t)B);
     SearchStage stage;
     stage.ctc_kws = &p;
     offline_samples(samples, n_samples, B, stage, tok.data(), ts.data(), n.data(), Tp, false);
-    res->mt = Tp;
-    res->keyword = std::move(tok); res->end = std::move(ts); res->n = std::move(n);
-    res->start = last_kws_start_; res->sum = last_kws_sum_; res->a = last_kws_a_; res->st = last_kws_st_;
-    res->state_off = p.state_off;
+    kws_collect(p.state_off, Tp, std::move(tok), std::move(ts), std::move(n), res);
     if (Tp_out) *Tp_out = Tp;
 }
 
 // ---------------------------------------------------------------------------
 // CTC forced alignment and full-sum scoring (ctc_align.hip)
 // ---------------------------------------------------------------------------
-static_assert(kCtcAlignMaxTokens == kCtcAlignMaxU, "the kernel's and the host reference's target limit are one number");
-
-Engine::CtcAlignPlan Engine::ctc_align_plan(int R, int Tp, const int32_t* n_frames, int H, const int32_t* stream_of, const int64_t* ids,
-                                            const int32_t* lens, int max_tokens) const {
-    const Config& cf = model_->cfg();
-    if (!cf.ctc) failf(K2HIP_ERR_UNSUPPORTED, "ctc_align: model_type '%s' has no CTC head", cf.model_type.c_str());
-    ctc_check_targets(cf.V, R, Tp, n_frames, H, stream_of, ids, lens);
-    K2_REQUIRE(H <= 65535, "ctc_align: %d targets in one call (at most 65535)", H);
-    CtcAlignPlan p;
-    p.R = R; p.Tp = Tp; p.H = H;
-    for (int h = 0; h < H; h++) {
-        if (lens[h] > max_tokens) failf(K2HIP_ERR_CAPACITY, "ctc_align: target %d has %d tokens, max_tokens is %d", h, lens[h], max_tokens);
-        K2_REQUIRE(lens[h] <= kCtcAlignMaxU, "ctc_align: target %d has %d tokens (at most %d)", h, lens[h], kCtcAlignMaxU);
-        p.n_ids += lens[h];
-    }
-    p.o_ids = align_up((int64_t)sizeof(CtcAlignTarget) * H, 16);
-    p.blob.assign((size_t)(p.o_ids + (int64_t)sizeof(int) * std::max(p.n_ids, 1)), 0);
-    CtcAlignTarget* tg = reinterpret_cast<CtcAlignTarget*>(p.blob.data());
-    int* h_ids = reinterpret_cast<int*>(p.blob.data() + p.o_ids);
-    int io = 0;
-    for (int h = 0; h < H; h++) {
-        const int r = stream_of ? stream_of[h] : h, T = n_frames ? n_frames[r] : Tp, U = lens[h];
-        tg[h] = CtcAlignTarget{p.plane_floats, p.bp_words, r, io, U, T};
-        p.plane_floats += (long long)T * (U + 1);
-        p.bp_words += (long long)T * ((2 * U + 1 + 63) / 64) * 2;
-        p.max_T = std::max(p.max_T, T);
-        p.max_U = std::max(p.max_U, U);
-        for (int u = 0; u < U; u++) h_ids[io + u] = (int)ids[io + u];
-        io += U;
-    }
-    return p;
-}
-
 Engine::SearchExtras Engine::ctc_align_device(const Ctx& c, const float* logp, int R, int Tp, const CtcAlignPlan& p, const SearchOut& out) {
     K2_REQUIRE(Tp == p.Tp && R == p.R && out.B == p.H, "internal: the CTC align plan was laid out for T'=%d R=%d H=%d, the encoder gave T'=%d R=%d H=%d",
                p.Tp, p.R, p.H, Tp, R, out.B);
@@ -1851,10 +1660,7 @@ void Engine::ctc_align_samples(const float* const* samples, const int64_t* n_sam
     K2_REQUIRE(samples != nullptr && n_samples != nullptr && B > 0 && max_tokens >= 0, "ctc_align_from_samples: bad arguments");
     const Config& cf = model_->cfg();
     if (!cf.ctc) failf(K2HIP_ERR_UNSUPPORTED, "ctc_align: model_type '%s' has no CTC head", cf.model_type.c_str());
-    // T' of the padded batch: every target is aligned over all of it, the frames the search decodes
-    const OfflineShape sh = samples_shape(samples, n_samples, B);
-    const int Tp = sh.Tp;
-    K2_REQUIRE(Tp > 0, "ctc_align_from_samples: %lld samples give no encoder frame", (long long)sh.longest);
+    const int Tp = samples_frames("ctc_align_from_samples", samples, n_samples, B);
     const CtcAlignPlan p = ctc_align_plan(B, Tp, nullptr, H, stream_of, ids, lens, max_tokens);
     AlignScratch s(H, max_tokens);
     SearchStage stage;
@@ -1888,6 +1694,12 @@ Engine::OfflineShape Engine::samples_shape(const float* const* samples, const in
         nmax = std::max(nmax, n_samples[b]);
     }
     return offline_shape("offline_greedy_from_samples", nmax);
+}
+
+int Engine::samples_frames(const char* who, const float* const* samples, const int64_t* n_samples, int B) const {
+    const OfflineShape sh = samples_shape(samples, n_samples, B);
+    K2_REQUIRE(sh.Tp > 0, "%s: %lld samples give no encoder frame", who, (long long)sh.longest);
+    return sh.Tp;
 }
 
 void Engine::offline_greedy_feats(const float* const* feats, const int64_t* n_floats, int B, bool single, int64_t* tokens,

@@ -358,8 +358,8 @@ class Engine {
     // their own (stay / emit) and stop after the first kernel (dp = false) or run only the second (cells = false).
     SearchExtras kws_device(const Ctx& c, const float* enc, int Tp, const KwsPlan& p, const SearchOut& out, float* stay = nullptr,
                             float* emit = nullptr, bool cells = true, bool dp = true);
-    // a finished call's results (the SearchOut rows of mt entries and the last_kws_* vectors) into `res`
-    void kws_collect(const KwsPlan& p, int mt, std::vector<int64_t>&& tok, std::vector<int32_t>&& ts, std::vector<int32_t>&& n, KwsResult* res) const;
+    // a finished call's results (the SearchOut rows of mt entries and the last_kws_* vectors) into `res`; state_off is the plan's, either spotter's
+    void kws_collect(const std::vector<int32_t>& state_off, int mt, std::vector<int64_t>&& tok, std::vector<int32_t>&& ts, std::vector<int32_t>&& n, KwsResult* res) const;
     std::vector<int32_t> last_kws_start_, last_kws_st_;
     std::vector<float> last_kws_sum_, last_kws_a_;
     // One CTC keyword-spotting call as the host lays it out before any device work: the streams' descriptors, carried blocks and the
@@ -441,6 +441,8 @@ class Engine {
     OfflineShape offline_shape(const char* who, int64_t longest, bool from_feats = false) const;
     // ... of host sample arrays of any lengths, each of which must give a frame
     OfflineShape samples_shape(const float* const* samples, const int64_t* n_samples, int B) const;
+    // T' of that batch, over all of which the fused align / keyword entry `who` runs its search; a batch that gives no encoder frame is refused
+    int samples_frames(const char* who, const float* const* samples, const int64_t* n_samples, int B) const;
     // fbank's arguments, the model's constants filled in
     FbankArgs fbank_args(const float* src, int64_t n, int64_t stride, int n_utts, int64_t nf, float* dst) const;
     // offline_greedy_samples with the stage named: what the public entry and the two align entries run

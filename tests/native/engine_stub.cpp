@@ -58,6 +58,19 @@ int64_t Engine::fbank_num_frames(int64_t n) const {
     const FbankOpts& f = model_->cfg().fbank;
     return n < f.frame_len ? 0 : 1 + (n - f.frame_len) / f.frame_shift;
 }
+// what the four fused lattice-search stand-ins share: both ends of every stream's samples are read, T' comes from the longest stream
+int Engine::samples_frames(const char* who, const float* const* samples, const int64_t* n_samples, int B) const {
+    int64_t nmax = 0;
+    for (int b = 0; b < B; b++) {
+        K2_REQUIRE(samples[b] != nullptr && fbank_num_frames(n_samples[b]) > 0, "stream %d: %lld samples give no frame", b, (long long)n_samples[b]);
+        volatile float sink = samples[b][0] + samples[b][n_samples[b] - 1];
+        (void)sink;
+        nmax = std::max(nmax, n_samples[b]);
+    }
+    const int Tp = encoder_out_frames((int)fbank_num_frames(nmax) + 19);
+    K2_REQUIRE(Tp > 0, "%s: %lld samples give no encoder frame", who, (long long)nmax);
+    return Tp;
+}
 int Engine::online_frames_per_chunk() const { return (model_->cfg().shift / 2 + 1) / 2; }
 
 // frame values: a function of the frame's first sample, so that the driver can predict them

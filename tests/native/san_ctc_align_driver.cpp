@@ -226,6 +226,13 @@ void abi(const char* ctc_path, const char* transducer_path) {
     for (int t = 0; t < Tp; t++) blank_sum += lp[(size_t)t * Vm];
     CHECK(ts[0] == -7 && tot[0] == best[0] && tot[0] == blank_sum);
     wipe();
+    {   // the plan's own rule (the launch grid's limit): 65536 empty targets are one too many, and nothing is written
+        const int many = 65536;
+        std::vector<int32_t> lens_many((size_t)many, 0), so_many((size_t)many, 0);
+        CHECK(k2hip_ctc_align(m, lp.data(), R, Tp, nullptr, many, so_many.data(), nullptr, lens_many.data(), ts.data(), en.data(), yp.data(), tot.data(),
+                              best.data(), 0) == K2HIP_ERR_INVALID && strstr(k2hip_last_error(), "at most 65535") != nullptr && untouched());
+        valid();
+    }
     // the fused entry
     std::vector<float> wav(16000);
     for (size_t i = 0; i < wav.size(); i++) wav[i] = (float)((int)(i * 2654435761u % 2001) - 1000) / 1000.f;
