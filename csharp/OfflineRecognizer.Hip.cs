@@ -71,6 +71,18 @@ namespace K2TransducerAsr
             _offlineInputEntity.SpeechLength = (int)K2Hip.k2hip_offline_stream_speech_length(HipStream);
         }
 
+        // Samples at any rate (include/k2hip.h "Input at other sample rates"): the native stream queues them as they are and the device
+        // converts the whole batch inside GetResults.  The stream's rate is fixed by its first samples; sampleRate equal to the model's is
+        // AddSamples(samples).  Native streams only: the reference's CPU front end has no resampler, so a stream without one refuses.
+        [System.Runtime.InteropServices.DllImport("k2hip")]
+        private static extern int k2hip_offline_stream_accept_waveform(IntPtr stream, int sampleRate, float[] samples, long n);
+        public void AddSamples(float[] samples, int sampleRate)
+        {
+            if (HipStream == IntPtr.Zero) throw new NotSupportedException("AddSamples(samples, sampleRate) needs the HIP backend");
+            K2Hip.Check(k2hip_offline_stream_accept_waveform(HipStream, sampleRate, samples, samples.LongLength), "AddSamples failed");
+            _offlineInputEntity.SpeechLength = (int)K2Hip.k2hip_offline_stream_speech_length(HipStream);
+        }
+
         // Dispose(bool) (:70-91) calls this first
         internal void DisposeHip()
         {

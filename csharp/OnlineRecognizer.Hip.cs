@@ -73,6 +73,16 @@ namespace K2TransducerAsr
         internal void AddSamplesHip(float[] samples) =>
             K2Hip.Check(K2Hip.k2hip_online_stream_accept_samples(HipStream, samples, samples.LongLength), "AddSamples failed");
 
+        // Samples at any rate (include/k2hip.h "Input at other sample rates"): the native stream carries the resampler's state, so any
+        // chunking gives the same frames.  The rate is fixed by the stream's first samples until it is reset; native streams only.
+        [System.Runtime.InteropServices.DllImport("k2hip")]
+        private static extern int k2hip_online_stream_accept_waveform(IntPtr stream, int sampleRate, float[] samples, long n);
+        public void AddSamples(float[] samples, int sampleRate)
+        {
+            if (HipStream == IntPtr.Zero) throw new NotSupportedException("AddSamples(samples, sampleRate) needs the HIP backend");
+            K2Hip.Check(k2hip_online_stream_accept_waveform(HipStream, sampleRate, samples, samples.LongLength), "AddSamples failed");
+        }
+
         internal bool IsFinishedHip(bool isEndpoint)
         {
             K2Hip.Check(K2Hip.k2hip_online_stream_is_finished(HipStream, isEndpoint ? 1 : 0, out int fin), "IsFinished failed");

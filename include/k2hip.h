@@ -896,8 +896,37 @@ int32_t k2hip_online_accept_samples_batch(k2hip_model_t* model, k2hip_online_str
 int32_t k2hip_online_accept_samples_matrix(k2hip_model_t* model, k2hip_online_stream_t* const* streams, int32_t B, const float* samples,
                                            int64_t row_stride, int64_t n);
 int32_t k2hip_online_stream_accept_features(k2hip_online_stream_t* s, const float* feats, int64_t n_frames);
+
+/* ---- Input at other sample rates --------------------------------------------------------------------------------------------------
+ * The accept_samples entries take samples at the model's rate (k2hip_model_info.sample_rate).  The accept_waveform entries take
+ * (sample_rate, samples) and convert on the device: Kaldi's LinearResample written from its definition, a Hann-windowed sinc with 6
+ * zero crossings and cutoff 0.99 * 0.5 * min(in, out), without flush -- an output sample exists once its whole window has been
+ * accepted, so the last <= 6 / (0.99 min(in, out)) seconds of a stream (under 0.4 ms towards 16 kHz; less than a frame shift) stay
+ * withheld.  Output k = u * ou + p (iu : ou = in : out in lowest terms) is sum_j w[p][j] * x[first[p] + u * iu + j] in float32, taps
+ * ascending by fused multiply-add from +0; x is zero in front of the stream's first sample.  Any chunking of a stream gives the same
+ * bits.
+ * Rules: sample_rate equal to the model's is exactly accept_samples (no plan, no launch, same bits).  A stream's rate is fixed by
+ * its first samples -- an offline stream's for its lifetime, an online stream's until k2hip_online_stream_reset; samples at another
+ * rate later, or accept_samples on a stream that resamples, return K2HIP_ERR_INVALID with the two rates in the message.
+ * Refusals: sample_rate <= 0 is K2HIP_ERR_INVALID; a pair of rates whose filter table (out / gcd phases x taps) exceeds 65536 floats
+ * (16001 -> 16000) or has more than 256 taps per phase is K2HIP_ERR_UNSUPPORTED, the message names the two rates.
+ * An offline stream queues its raw samples in pinned memory as ever (no launch, no lock on the model); SpeechLength counts the
+ * frames of the samples the queue will give, and k2hip_offline_recognizer_get_results converts the whole batch, any mix of rates,
+ * in the one launch that gathers it.  An online stream converts when its frames are needed, all streams of a step in one launch.
+ * k2hip_resample_num_out: samples at the model's rate that n_in_total samples at in_rate give in all (-1 on error).
+ * k2hip_resample: one call over a whole signal (no flush, no state): *n_out = k2hip_resample_num_out(n) samples into out;
+ * K2HIP_ERR_CAPACITY when cap is short (*n_out is set, nothing is written). */
+int64_t k2hip_resample_num_out(k2hip_model_t* model, int32_t in_rate, int64_t n_in_total);
+int32_t k2hip_resample(k2hip_model_t* model, int32_t in_rate, const float* samples, int64_t n, float* out, int64_t cap, int64_t* n_out);
+int32_t k2hip_offline_stream_accept_waveform(k2hip_offline_stream_t* s, int32_t sample_rate, const float* samples, int64_t n);
+int32_t k2hip_online_stream_accept_waveform(k2hip_online_stream_t* s, int32_t sample_rate, const float* samples, int64_t n);
+/* B k2hip_online_stream_accept_waveform calls at one rate */
+int32_t k2hip_online_accept_waveform_batch(k2hip_model_t* model, k2hip_online_stream_t* const* streams, int32_t B, int32_t sample_rate,
+                                           const float* const* samples, const int64_t* n);
 /* OnlineInputEntity.SpeechLength (floats buffered) */
 int64_t k2hip_online_stream_speech_length(const k2hip_online_stream_t* s);
+/* copies the buffered frames to out (cap floats; K2HIP_ERR_CAPACITY if short); the frames of samples accepted earlier are computed first */
+int32_t k2hip_online_stream_get_speech(k2hip_online_stream_t* s, float* out, int64_t cap);
 /* OnlineStream.IsFinished(isEndpoint) (:124-161), including its side effect of feeding 400 zero
  * samples when less than a chunk is buffered */
 int32_t k2hip_online_stream_is_finished(k2hip_online_stream_t* s, int32_t is_endpoint, int32_t* finished);

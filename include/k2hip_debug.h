@@ -213,6 +213,29 @@ int32_t k2hip_debug_ctc_kws_ref_dp(const int32_t* parent, const int32_t* tok, co
  *     out: every stream's carried block [2][S], back to back), ev_keyword [B][Tp] int64, ev_start, ev_end [B][Tp] int32, ev_sum [B][Tp],
  *     n_events [B] int32 (out; row b holds n_events[b] events); ints B, Tp, G, V (the log-probs' width: any, not the model's). */
 
+/* ---- input at other sample rates (k2hip.h "Input at other sample rates"; tests/test_resample.py, test_resample_gpu.py) ---------- */
+/* the plan of csrc/resample_plan.h for in_rate -> out_rate, host only, no model: *iu, *ou, *max_taps, then (each may be NULL; all NULL =
+ * the sizes alone) first [ou], ntaps [ou] and the float32 weights w [ou][max_taps], rows zero-filled behind ntaps[p].  K2HIP_ERR_CAPACITY
+ * when cap_phases < ou or cap_w < ou * max_taps; the refusals of k2hip.h otherwise. */
+int32_t k2hip_debug_resample_plan(int32_t in_rate, int32_t out_rate, int32_t* iu, int32_t* ou, int32_t* max_taps, int32_t* first, int32_t* ntaps,
+                                  float* w, int32_t cap_phases, int64_t cap_w);
+/* outputs that exist after n_in_total input samples (-1 on error) */
+int64_t k2hip_debug_resample_num_out(int32_t in_rate, int32_t out_rate, int64_t n_in_total);
+/* the float32 host reference (csrc/resample_ref.h), no GPU: one push of n samples x into a stream whose carried block is tail
+ * [*n_tail] (the input samples [*n_in - *n_tail, *n_in)) and the counts *n_in / *n_out, all updated in place (a fresh stream: 0, 0, 0);
+ * the outputs the push completes go to out, *n_written their number.  K2HIP_ERR_CAPACITY beyond cap / tail_cap. */
+int32_t k2hip_debug_resample_ref(int32_t in_rate, int32_t out_rate, float* tail, int64_t* n_tail, int64_t tail_cap, int64_t* n_in, int64_t* n_out,
+                                 const float* x, int64_t n, float* out, int64_t cap, int64_t* n_written);
+/* how many plans the model has built: one per input rate other than its own that an entry has named */
+int32_t k2hip_debug_resample_plans(k2hip_model_t* model, int32_t* n);
+/* The kernel alone (csrc/resample.hip) through k2hip_debug_op_run:
+ *   "resample_gather": ints B, n_dst_rows, nmax, then per row (in_rate, out_rate, off_head, n_head, off_tail, n_tail, x0, k0, n_out,
+ *     dst_row); bufs samples, dst [n_dst_rows][nmax] (out).  Row b reads the two pieces samples[off_head .. + n_head) ;
+ *     samples[off_tail .. + n_tail), the first float being input sample x0 of its stream, and writes outputs k0 .. k0 + n_out of the plan
+ *     in_rate -> out_rate, then zeros up to nmax, into row dst_row.  in_rate = 0: a pass-through row, the pieces copied and zero-filled.
+ *     The samples buffer starts on a 256-byte boundary, so an offset that is no multiple of 4 puts a piece off the 16-byte boundary.
+ *     The launcher checks on the host that no row reads outside its pieces or writes outside its row: K2HIP_ERR_UNSUPPORTED. */
+
 /* ---- GEMM tuning ------------------------------------------------------------------------------- */
 /* time `iters` launches of a shape / configuration on pseudo-random operands (tools/gemm_lab.py, gemm_tune.py) */
 int32_t k2hip_debug_gemm(k2hip_model_t* model, int32_t M, int32_t N, int32_t K, int32_t act, int32_t with_res, int32_t cfg,

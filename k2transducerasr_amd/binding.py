@@ -125,6 +125,12 @@ def load_library():
     L.k2hip_offline_stream_num_timestamps.argtypes = [vp]
     L.k2hip_offline_stream_get_tokens.argtypes = [vp, lp, C.c_int32]
     L.k2hip_offline_stream_get_timestamps.argtypes = [vp, ip, C.c_int32]
+    L.k2hip_resample_num_out.restype = C.c_int64
+    L.k2hip_resample_num_out.argtypes = [vp, C.c_int32, C.c_int64]
+    L.k2hip_resample.argtypes = [vp, C.c_int32, fp, C.c_int64, fp, C.c_int64, lp]
+    L.k2hip_offline_stream_accept_waveform.argtypes = [vp, C.c_int32, fp, C.c_int64]
+    L.k2hip_online_stream_accept_waveform.argtypes = [vp, C.c_int32, fp, C.c_int64]
+    L.k2hip_online_accept_waveform_batch.argtypes = [vp, C.POINTER(vp), C.c_int32, C.c_int32, C.POINTER(fp), lp]
     _lib = L
     return L
 
@@ -650,6 +656,23 @@ class Model:
         out = np.empty((nf, self.feature_dim), np.float32)
         got = C.c_int64()
         self._chk(self._L.k2hip_fbank(self._h, _f(s), s.size, _f(out), nf, C.byref(got)))
+        return out[: got.value]
+
+    # ---- input at other sample rates (include/k2hip.h "Input at other sample rates")
+    def resample_num_out(self, in_rate: int, n_in_total: int) -> int:
+        """samples at the model's rate that n_in_total samples at in_rate give in all (no flush: the last fraction of a millisecond is
+        withheld)"""
+        n = self._L.k2hip_resample_num_out(self._h, int(in_rate), int(n_in_total))
+        if n < 0:
+            raise K2HipError(-1, self._L.k2hip_last_error().decode())
+        return int(n)
+
+    def resample(self, samples, in_rate: int) -> np.ndarray:
+        """one signal at in_rate converted to the model's rate on the device, in one call"""
+        s = _f32(samples).reshape(-1)
+        out = np.empty(self.resample_num_out(in_rate, s.size), np.float32)
+        got = C.c_int64()
+        self._chk(self._L.k2hip_resample(self._h, int(in_rate), _f(s), s.size, _f(out), out.size, C.byref(got)))
         return out[: got.value]
 
     # ---- F3
@@ -1199,6 +1222,12 @@ class OfflineStream:
         s = _f32(samples).reshape(-1)
         self._m._chk(self._L.k2hip_offline_stream_accept_samples(self._h, _f(s), s.size))
 
+    def accept_waveform(self, sample_rate: int, samples):
+        """samples at any rate: queued as they are, converted to the model's rate on the device when the frames are needed.  The
+        stream's rate is fixed by its first samples."""
+        s = _f32(samples).reshape(-1)
+        self._m._chk(self._L.k2hip_offline_stream_accept_waveform(self._h, int(sample_rate), _f(s), s.size))
+
     @property
     def speech_length(self) -> int:  # OfflineInputEntity.SpeechLength
         return self._L.k2hip_offline_stream_speech_length(self._h)
@@ -1392,6 +1421,12 @@ class OnlineStream:
         s = _f32(samples).reshape(-1)
         self._m._chk(self._L.k2hip_online_stream_accept_samples(self._h, _f(s), s.size))
 
+    def accept_waveform(self, sample_rate: int, samples):
+        """samples at any rate; the stream carries the resampler's state, so any chunking gives the same frames.  The stream's rate
+        is fixed by its first samples until reset()."""
+        s = _f32(samples).reshape(-1)
+        self._m._chk(self._L.k2hip_online_stream_accept_waveform(self._h, int(sample_rate), _f(s), s.size))
+
     def add_features(self, feats):
         f = _f32(feats).reshape(-1, self._m.feature_dim)
         self._m._chk(self._L.k2hip_online_stream_accept_features(self._h, _f(f), f.shape[0]))
@@ -1399,6 +1434,14 @@ class OnlineStream:
     @property
     def speech_length(self) -> int:
         return self._L.k2hip_online_stream_speech_length(self._h)
+
+    @property
+    def speech(self) -> np.ndarray:  # OnlineInputEntity.Speech: the buffered frames
+        self._L.k2hip_online_stream_get_speech.argtypes = [C.c_void_p, fp, C.c_int64]
+        n = self.speech_length
+        out = np.empty(n, np.float32)
+        self._m._chk(self._L.k2hip_online_stream_get_speech(self._h, _f(out), n))
+        return out
 
     def is_finished(self, is_endpoint: bool = False) -> bool:  # IsFinished :124-161
         out = C.c_int32()
@@ -1711,6 +1754,15 @@ class OnlineRecognizer:
         ptrs = (fp * B)(*[_f(x) for x in ss])
         n = np.array([x.size for x in ss], np.int64)
         self.model._chk(self.model._L.k2hip_online_accept_samples_batch(self.model.handle, arr, B, ptrs, _l(n)))
+
+    def accept_waveform_batch(self, streams: Sequence[OnlineStream], sample_rate: int, samples: Sequence[np.ndarray]):
+        """B accept_waveform calls at one rate in one."""
+        B = len(streams)
+        arr = self._handles(streams)
+        ss = [_f32(x).reshape(-1) for x in samples]
+        ptrs = (fp * B)(*[_f(x) for x in ss])
+        n = np.array([x.size for x in ss], np.int64)
+        self.model._chk(self.model._L.k2hip_online_accept_waveform_batch(self.model.handle, arr, B, int(sample_rate), ptrs, _l(n)))
 
     def get_results(self, streams: Sequence[OnlineStream]):
         """GetResults :76-84 (tokens, not text).  Returns (decoded flags, new-token counts)."""

@@ -18,6 +18,7 @@
 #include "hotwords.h"
 #include "keywords.h"
 #include "kws_ref.h"
+#include "resample_ref.h"
 #include "ctc_kws_ref.h"
 #include "ngram_lm.h"
 #include "../../include/k2hip_debug.h"
@@ -127,6 +128,10 @@ struct k2hip_model {
     int hw_uploads = 0;
     // the keyword graphs resident for this model's keyword streams (KwResident), by serial number
     std::map<uint64_t, std::weak_ptr<KwResident>> kw_cache;
+    // the resampler's plans by input rate (resample_plan.h), built on first use and kept for the model's life: streams and the engine's
+    // device tables name them by address
+    std::mutex rs_mu;
+    std::map<int, std::unique_ptr<ResamplePlan>> rs_plans;
     k2hip_model(const char* path, const char* ov, int dev) : engine(path, ov, dev) {}
     ~k2hip_model() {
         {
@@ -190,6 +195,12 @@ struct k2hip_offline_stream {
     std::vector<BeamAlt> alts = std::vector<BeamAlt>(1);
     int32_t frame_offset = 0;        // FrameOffset (:39), read by the CTC search (OfflineRecognizer.cs:376,402)
     int32_t num_trailing_blank = 0;  // NumTrailingBlank (:40)
+    // Input at another sample rate (k2hip_offline_stream_accept_waveform): `rate` is fixed by the stream's first samples (0: none yet),
+    // `rs` is its plan (null at the model's rate).  `wav` then queues INPUT samples, wav[0] being input sample rs_x0 of the stream, and
+    // rs_k0 counts the samples at the model's rate that the frames materialised or searched so far have consumed.
+    int rate = 0;
+    const ResamplePlan* rs = nullptr;
+    int64_t rs_x0 = 0, rs_k0 = 0;
 };
 
 // OnlineStream.cs:7-199
@@ -232,6 +243,14 @@ struct k2hip_online_stream {
     // k2hip_online_stream_set_ctc_prefix_biasing: the carried prefix search of this stream reads its own graph (`hw`) and the model's
     // n-gram LM.  Off by default; kept by a reset
     bool cp_biasing = false;
+    // Input at another sample rate (k2hip_online_stream_accept_waveform): `rate` is fixed by the stream's first samples until a reset
+    // (0: none yet), `rs` is its plan (null at the model's rate).  rs_in queues the input samples accepted since the last
+    // materialisation; rs_tail is the resampler's carried input [rs_n_in - size, rs_n_in) and rs_n_in / rs_n_out its running counts
+    // (resample_ref.h's state).  `pending` holds samples at the model's rate as ever: the resampler's output on its way to the fbank.
+    int rate = 0;
+    const ResamplePlan* rs = nullptr;
+    std::vector<float> rs_in, rs_tail;
+    int64_t rs_n_in = 0, rs_n_out = 0;
 };
 
 // operator level of the streaming beam search: one stream's hypotheses, fed encoder frames by the caller (k2hip_beam_search_chunk)
@@ -1694,12 +1713,82 @@ int32_t k2hip_online_chunk_info(const k2hip_model_t* model, int32_t* chunk_lengt
         if (frames_per_chunk) *frames_per_chunk = model->engine.online_frames_per_chunk();
     });
 }
+// the model's plan for input at `rate` (null: the model's own rate); built once per rate
+static const ResamplePlan* model_resample_plan(k2hip_model* m, int rate) {
+    const int out = m->engine.model().cfg().fbank.sample_rate;
+    K2_REQUIRE(rate > 0, "sample rate %d", rate);
+    if (rate == out) return nullptr;
+    std::lock_guard<std::mutex> lk(m->rs_mu);
+    auto it = m->rs_plans.find(rate);
+    if (it == m->rs_plans.end()) it = m->rs_plans.emplace(rate, std::make_unique<ResamplePlan>(resample_plan(rate, out))).first;
+    return it->second.get();
+}
+constexpr int64_t kResampleMaxInput = (int64_t)1 << 36;   // input samples of one stream: keeps the plan's tick arithmetic inside int64
+// the rule of the accept_waveform entries, offline and online: a stream's rate (*s_rate, 0 = none yet) and plan (*s_rs) are fixed by
+// its first samples; returns the plan
+static const ResamplePlan* take_rate(k2hip_model* m, int* s_rate, const ResamplePlan** s_rs, int rate, const char* who) {
+    if (*s_rate == 0) {
+        const ResamplePlan* p = model_resample_plan(m, rate);   // (a refused plan leaves the stream without a rate)
+        *s_rate = rate;
+        *s_rs = p;
+    }
+    K2_REQUIRE(*s_rate == rate, "%s: the stream takes samples at %d Hz, these are at %d Hz", who, *s_rate, rate);
+    return *s_rs;
+}
 static void online_add_samples(k2hip_online_stream* s, const float* samples, int64_t n) {
-    if (n > 0) s->pending.insert(s->pending.end(), samples, samples + n);  // OnlineStream.AddSamples (:57-79), fbank deferred
+    if (n <= 0) return;
+    const int own = s->model->engine.model().cfg().fbank.sample_rate;
+    K2_REQUIRE(!s->rs, "accept_samples: the stream resamples from %d Hz (accept_waveform), these samples are at the model's %d Hz", s->rate, own);
+    s->rate = own;
+    s->pending.insert(s->pending.end(), samples, samples + n);  // OnlineStream.AddSamples (:57-79), fbank deferred
+}
+static void online_add_waveform(k2hip_online_stream* s, int rate, const float* samples, int64_t n) {
+    if (!take_rate(s->model, &s->rate, &s->rs, rate, "accept_waveform")) return online_add_samples(s, samples, n);
+    if (n <= 0) return;
+    K2_REQUIRE(s->rs_n_in + (int64_t)s->rs_in.size() + n < kResampleMaxInput, "accept_waveform: more than 2^36 samples in one stream");
+    s->rs_in.insert(s->rs_in.end(), samples, samples + n);
+}
+// samples at the model's rate that the stream's queued input will give
+static int64_t online_resample_due(const k2hip_online_stream* s) {
+    return s->rs ? s->rs->num_out(s->rs_n_in + (int64_t)s->rs_in.size()) - s->rs_n_out : 0;
 }
 // frames the stream's pending samples will add to Speech
 static int64_t online_pending_frames(const k2hip_online_stream* s) {
-    return s->pending.empty() ? 0 : s->model->engine.fbank_num_frames((int64_t)(s->remainder.size() + s->pending.size()));
+    const int64_t due = online_resample_due(s);
+    return s->pending.empty() && due == 0 ? 0 : s->model->engine.fbank_num_frames((int64_t)(s->remainder.size() + s->pending.size()) + due);
+}
+// the queued input of every resampling stream among `streams` through the resampler, ONE launch across their rates; the outputs join
+// `pending`, the streams keep the input tail that later outputs read
+static void online_resample(k2hip_online_stream* const* streams, int n) {
+    std::vector<k2hip_online_stream*> g;
+    for (int i = 0; i < n; i++)
+        if (streams[i]->rs && !streams[i]->rs_in.empty()) g.push_back(streams[i]);
+    if (g.empty()) return;
+    std::vector<std::vector<float>> out(g.size());
+    std::vector<Engine::ResampleJob> jobs;
+    for (size_t i = 0; i < g.size(); i++) {
+        k2hip_online_stream* s = g[i];
+        out[i].resize((size_t)online_resample_due(s));
+        if (out[i].empty()) continue;   // (a push that completes no output: bookkeeping only)
+        jobs.push_back(Engine::ResampleJob{s->rs, s->rs_tail.data(), (int64_t)s->rs_tail.size(), s->rs_in.data(), (int64_t)s->rs_in.size(),
+                                           s->rs_n_in - (int64_t)s->rs_tail.size(), s->rs_n_out, (int64_t)out[i].size(), out[i].data()});
+    }
+    if (!jobs.empty()) {
+        Engine& e = g[0]->model->engine;
+        EngineLock lk(e);
+        e.resample_host(jobs.data(), (int)jobs.size());
+    }
+    for (size_t i = 0; i < g.size(); i++) {
+        k2hip_online_stream* s = g[i];
+        const int64_t x0 = s->rs_n_in - (int64_t)s->rs_tail.size();
+        s->rs_n_in += (int64_t)s->rs_in.size();
+        s->rs_n_out += (int64_t)out[i].size();
+        const int64_t keep = std::min(s->rs->keep_from(s->rs_n_out), s->rs_n_in);
+        s->rs_tail.insert(s->rs_tail.end(), s->rs_in.begin(), s->rs_in.end());
+        s->rs_tail.erase(s->rs_tail.begin(), s->rs_tail.begin() + (keep - x0));
+        s->rs_in.clear();
+        s->pending.insert(s->pending.end(), out[i].begin(), out[i].end());
+    }
 }
 static int64_t online_logical_floats(const k2hip_online_stream* s) {
     return (int64_t)s->speech.size() + online_pending_frames(s) * s->model->engine.model().cfg().feat;
@@ -1709,6 +1798,7 @@ static int64_t online_logical_floats(const k2hip_online_stream* s) {
 // taken only when ONE batched launch covers every stream with queued samples.  Returns whether a gather was left outstanding.
 static bool online_materialize(k2hip_online_stream* const* streams, int n, bool may_defer = false) {
     if (n <= 0) return false;
+    online_resample(streams, n);
     bool deferred = false;
     Engine& e = streams[0]->model->engine;
     const Config& c = e.model().cfg();
@@ -1787,6 +1877,124 @@ int32_t k2hip_online_accept_samples_batch(k2hip_model_t* model, k2hip_online_str
         }
     });
 }
+int32_t k2hip_online_stream_accept_waveform(k2hip_online_stream_t* s, int32_t sample_rate, const float* samples, int64_t n) {
+    return guard([&] {
+        NEED(s);
+        if (n > 0) NEED(samples);
+        online_add_waveform(s, sample_rate, samples, n);
+    });
+}
+int32_t k2hip_online_accept_waveform_batch(k2hip_model_t* model, k2hip_online_stream_t* const* streams, int32_t B, int32_t sample_rate,
+                                           const float* const* samples, const int64_t* n) {
+    return guard([&] {
+        NEED(model); NEED(streams); NEED(samples); NEED(n);
+        K2_REQUIRE(B > 0, "accept_waveform_batch: empty list");
+        const int own = model->engine.model().cfg().fbank.sample_rate;
+        model_resample_plan(model, sample_rate);   // (a rate that is refused is refused before any stream takes a sample)
+        for (int i = 0; i < B; i++) {
+            NEED(streams[i]);
+            if (n[i] > 0) NEED(samples[i]);
+            K2_REQUIRE(streams[i]->model == model, "accept_waveform_batch: stream %d belongs to another model", i);
+            K2_REQUIRE(streams[i]->rate == 0 || streams[i]->rate == sample_rate, "accept_waveform_batch: stream %d takes samples at %d Hz, these are at "
+                       "%d Hz (the model's: %d Hz)", i, streams[i]->rate, sample_rate, own);
+        }
+        for (int i = 0; i < B; i++) online_add_waveform(streams[i], sample_rate, samples[i], n[i]);
+    });
+}
+// ---- the resampler alone (include/k2hip.h "Input at other sample rates") ----
+int64_t k2hip_resample_num_out(k2hip_model_t* model, int32_t in_rate, int64_t n_in_total) {
+    int64_t r = -1;
+    guard([&] {
+        NEED(model);
+        K2_REQUIRE(n_in_total >= 0 && n_in_total < kResampleMaxInput, "resample_num_out: %lld samples", (long long)n_in_total);
+        const ResamplePlan* p = model_resample_plan(model, in_rate);
+        r = p ? p->num_out(n_in_total) : n_in_total;
+    });
+    return r;
+}
+int32_t k2hip_resample(k2hip_model_t* model, int32_t in_rate, const float* samples, int64_t n, float* out, int64_t cap, int64_t* n_out) {
+    return guard([&] {
+        NEED(model); NEED(n_out);
+        K2_REQUIRE(n >= 0 && n < kResampleMaxInput && cap >= 0, "resample: %lld samples into %lld", (long long)n, (long long)cap);
+        if (n > 0) NEED(samples);
+        const ResamplePlan* p = model_resample_plan(model, in_rate);
+        const int64_t no = p ? p->num_out(n) : n;
+        *n_out = no;
+        if (no > cap) failf(K2HIP_ERR_CAPACITY, "resample: %lld samples at %d Hz give %lld, capacity %lld", (long long)n, in_rate, (long long)no, (long long)cap);
+        if (no == 0) return;
+        NEED(out);
+        if (!p) {
+            memcpy(out, samples, sizeof(float) * (size_t)n);
+            return;
+        }
+        const Engine::ResampleJob job{p, samples, n, nullptr, 0, 0, 0, no, out};
+        EngineLock lk(model->engine);
+        model->engine.resample_host(&job, 1);
+    });
+}
+// test hooks (include/k2hip_debug.h): the plan and the float32 host reference, no model and no GPU
+int32_t k2hip_debug_resample_plan(int32_t in_rate, int32_t out_rate, int32_t* iu, int32_t* ou, int32_t* max_taps, int32_t* first, int32_t* ntaps,
+                                  float* w, int32_t cap_phases, int64_t cap_w) {
+    return guard([&] {
+        NEED(iu); NEED(ou); NEED(max_taps);
+        const ResamplePlan p = resample_plan(in_rate, out_rate);
+        *iu = p.iu; *ou = p.ou; *max_taps = p.max_taps;
+        if (!first && !ntaps && !w) return;   // (the sizes alone)
+        if (p.ou > cap_phases || (w && (int64_t)p.w.size() > cap_w))
+            failf(K2HIP_ERR_CAPACITY, "resample plan %d -> %d: %d phases x %d taps", in_rate, out_rate, p.ou, p.max_taps);
+        if (first) memcpy(first, p.first.data(), sizeof(int32_t) * (size_t)p.ou);
+        if (ntaps) memcpy(ntaps, p.ntaps.data(), sizeof(int32_t) * (size_t)p.ou);
+        if (w) memcpy(w, p.w.data(), sizeof(float) * p.w.size());
+    });
+}
+int64_t k2hip_debug_resample_num_out(int32_t in_rate, int32_t out_rate, int64_t n_in_total) {
+    int64_t r = -1;
+    guard([&] {
+        K2_REQUIRE(n_in_total >= 0 && n_in_total < kResampleMaxInput, "resample_num_out: %lld samples", (long long)n_in_total);
+        r = resample_plan(in_rate, out_rate).num_out(n_in_total);
+    });
+    return r;
+}
+int32_t k2hip_debug_resample_ref(int32_t in_rate, int32_t out_rate, float* tail, int64_t* n_tail, int64_t tail_cap, int64_t* n_in, int64_t* n_out,
+                                 const float* x, int64_t n, float* out, int64_t cap, int64_t* n_written) {
+    return guard([&] {
+        NEED(n_tail); NEED(n_in); NEED(n_out); NEED(n_written);
+        K2_REQUIRE(n >= 0 && *n_tail >= 0 && *n_tail <= *n_in && *n_out >= 0 && *n_in + n < kResampleMaxInput, "resample_ref: bad carried block");
+        if (n > 0) NEED(x);
+        if (*n_tail > 0) NEED(tail);
+        const ResamplePlan p = resample_plan(in_rate, out_rate);
+        K2_REQUIRE(*n_out == p.num_out(*n_in) && *n_in - *n_tail <= p.keep_from(*n_out), "resample_ref: the carried block does not belong to %lld "
+                   "samples in, %lld out", (long long)*n_in, (long long)*n_out);
+        ResampleRefState st;
+        st.tail.assign(tail, tail + *n_tail);
+        st.n_in = *n_in;
+        st.n_out = *n_out;
+        std::vector<float> y;
+        resample_ref_push(p, st, x, n, &y);
+        *n_written = (int64_t)y.size();
+        if ((int64_t)y.size() > cap || (int64_t)st.tail.size() > tail_cap)
+            failf(K2HIP_ERR_CAPACITY, "resample_ref: %zu outputs and a tail of %zu samples", y.size(), st.tail.size());
+        if (!y.empty()) {
+            NEED(out);
+            memcpy(out, y.data(), sizeof(float) * y.size());
+        }
+        if (!st.tail.empty()) {
+            NEED(tail);
+            memcpy(tail, st.tail.data(), sizeof(float) * st.tail.size());
+        }
+        *n_tail = (int64_t)st.tail.size();
+        *n_in = st.n_in;
+        *n_out = st.n_out;
+    });
+}
+// the plans a model has built so far (one per input rate that differed from its own)
+int32_t k2hip_debug_resample_plans(k2hip_model_t* model, int32_t* n) {
+    return guard([&] {
+        NEED(model); NEED(n);
+        std::lock_guard<std::mutex> lk(model->rs_mu);
+        *n = (int32_t)model->rs_plans.size();
+    });
+}
 // B AddSamples calls over the rows of one [B, n] matrix (row stride in floats): what a host that receives audio in lock step
 // holds anyway; saves building B pointers per 50 ms push
 int32_t k2hip_online_accept_samples_matrix(k2hip_model_t* model, k2hip_online_stream_t* const* streams, int32_t B, const float* samples,
@@ -1820,6 +2028,18 @@ int32_t k2hip_online_stream_accept_features(k2hip_online_stream_t* s, const floa
     });
 }
 int64_t k2hip_online_stream_speech_length(const k2hip_online_stream_t* s) { return s ? online_logical_floats(s) : -1; }
+// the feature FIFO itself: the frames of samples accepted earlier are materialised first
+int32_t k2hip_online_stream_get_speech(k2hip_online_stream_t* s, float* out, int64_t cap) {
+    return guard([&] {
+        NEED(s);
+        online_materialize(&s, 1);
+        if ((int64_t)s->speech.size() > cap) failf(K2HIP_ERR_CAPACITY, "speech has %zu floats", s->speech.size());
+        if (!s->speech.empty()) {
+            NEED(out);
+            memcpy(out, s->speech.data(), sizeof(float) * s->speech.size());
+        }
+    });
+}
 // OnlineStream.IsFinished (:124-161)
 int32_t k2hip_online_stream_is_finished(k2hip_online_stream_t* s, int32_t is_endpoint, int32_t* finished) {
     return guard([&] {
@@ -1837,8 +2057,11 @@ int32_t k2hip_online_stream_is_finished(k2hip_online_stream_t* s, int32_t is_end
         for (float v : s->speech) num += (v != avg);
         if (num == 0) { *finished = 1; return; }
         if ((long long)oLen <= (long long)c.chunk_T * c.feat) {
-            std::vector<float> z(400, 0.f);  // AddSamples(new float[400]) (:146)
-            online_add_samples(s, z.data(), 400);
+            // AddSamples(new float[400]) (:146); a resampling stream takes them at its own rate, ceil(400 iu / ou) zeros
+            const int64_t nz = s->rs ? (400 * (int64_t)s->rs->iu + s->rs->ou - 1) / s->rs->ou : 400;
+            std::vector<float> z((size_t)nz, 0.f);
+            if (s->rs) online_add_waveform(s, s->rate, z.data(), nz);
+            else online_add_samples(s, z.data(), nz);
         }
     });
 }
@@ -2713,9 +2936,40 @@ int32_t k2hip_offline_stream_destroy(k2hip_offline_stream_t* s) {
     });
 }
 // frames the stream's unmaterialised samples will add to Speech
-static int64_t offline_pending_frames(const k2hip_offline_stream* s) {
-    return s->wav.empty() ? 0 : s->model->engine.fbank_num_frames((int64_t)s->wav.size());
+// samples at the model's rate that the stream's queue gives: the queue itself, or what the resampler makes of it
+static int64_t offline_queued(const k2hip_offline_stream* s) {
+    return s->rs ? s->rs->num_out(s->rs_x0 + (int64_t)s->wav.size()) - s->rs_k0 : (int64_t)s->wav.size();
 }
+static int64_t offline_pending_frames(const k2hip_offline_stream* s) {
+    return s->wav.empty() ? 0 : s->model->engine.fbank_num_frames(offline_queued(s));
+}
+// nf frames of the queue are spoken for: the samples behind the last whole frame shift stay queued -- of a resampling stream, the
+// input behind it AND behind what the resampler still reads for the outputs to come
+static void offline_erase_frames(k2hip_offline_stream* s, int64_t nf) {
+    const int64_t used = nf * s->model->engine.model().cfg().fbank.frame_shift;
+    if (!s->rs) {
+        s->wav.erase_front((size_t)used);
+        return;
+    }
+    s->rs_k0 += used;
+    const int64_t keep = std::min(s->rs->keep_from(s->rs_k0), s->rs_x0 + (int64_t)s->wav.size());
+    s->wav.erase_front((size_t)(keep - s->rs_x0));
+    s->rs_x0 = keep;
+}
+// the batch's resampling streams named to the engine for one from-samples call (Engine::set_wave_srcs); made under the engine's lock
+struct WaveSrcScope {
+    Engine& e;
+    std::vector<Engine::WaveSrc> w;
+    WaveSrcScope(Engine& eng, k2hip_offline_stream* const* streams, int B) : e(eng), w((size_t)B) {
+        bool any = false;
+        for (int b = 0; b < B; b++) {
+            w[(size_t)b] = Engine::WaveSrc{streams[b]->rs, streams[b]->rs_x0, streams[b]->rs_k0};
+            any = any || streams[b]->rs;
+        }
+        if (any) e.set_wave_srcs(w.data());
+    }
+    ~WaveSrcScope() { e.set_wave_srcs(nullptr); }
+};
 // run the fbank of the stream's unmaterialised samples now and append the frames to Speech; the samples behind the last whole frame
 // shift stay queued (the streaming framing of an OnlineFbank)
 static void offline_materialize(k2hip_offline_stream* s) {
@@ -2728,32 +2982,57 @@ static void offline_materialize(k2hip_offline_stream* s) {
     try {
         int64_t got = 0;
         EngineLock lk(e);
-        e.fbank_host(s->wav.data(), (int64_t)s->wav.size(), s->speech.data() + old, nf, &got);
+        if (s->rs) {
+            std::vector<float> y((size_t)offline_queued(s));
+            const Engine::ResampleJob job{s->rs, s->wav.data(), (int64_t)s->wav.size(), nullptr, 0, s->rs_x0, s->rs_k0, (int64_t)y.size(), y.data()};
+            e.resample_host(&job, 1);
+            e.fbank_host(y.data(), (int64_t)y.size(), s->speech.data() + old, nf, &got);
+        } else {
+            e.fbank_host(s->wav.data(), (int64_t)s->wav.size(), s->speech.data() + old, nf, &got);
+        }
     } catch (...) {
         s->speech.resize(old);
         throw;
     }
-    s->wav.erase_front((size_t)nf * c.fbank.frame_shift);
+    offline_erase_frames(s, nf);
 }
 // OfflineStream.AddSamples (:43-57): the samples are queued; their frames count in SpeechLength at once and are computed when
 // somebody needs them (GetResults: on the device, for the whole batch in one launch)
+static void offline_add(k2hip_offline_stream* s, const float* samples, int64_t n);
 int32_t k2hip_offline_stream_accept_samples(k2hip_offline_stream_t* s, const float* samples, int64_t n) {
     return guard([&] {
         NEED(s);
         if (n > 0) NEED(samples);
         if (n <= 0) return;
-        if (s->wav.capacity() == 0) {   // first samples of the stream: a buffer of the model's pool that is large enough, if there is one
-            std::lock_guard<std::mutex> lk(s->model->wav_mu);
-            auto& pool = s->model->wav_pool;
-            for (size_t i = pool.size(); i-- > 0;)
-                if (pool[i].capacity() >= (size_t)n) {
-                    s->wav = std::move(pool[i]);
-                    pool.erase(pool.begin() + (long)i);
-                    break;
-                }
-        }
-        s->wav.append(s->model->engine, samples, (size_t)n);
+        const int own = s->model->engine.model().cfg().fbank.sample_rate;
+        K2_REQUIRE(!s->rs, "accept_samples: the stream resamples from %d Hz (accept_waveform), these samples are at the model's %d Hz", s->rate, own);
+        s->rate = own;
+        offline_add(s, samples, n);
     });
+}
+// a stream fed at another rate queues its raw samples as any other does: nothing is launched, no lock on the model is taken
+int32_t k2hip_offline_stream_accept_waveform(k2hip_offline_stream_t* s, int32_t sample_rate, const float* samples, int64_t n) {
+    return guard([&] {
+        NEED(s);
+        if (n > 0) NEED(samples);
+        const ResamplePlan* p = take_rate(s->model, &s->rate, &s->rs, sample_rate, "accept_waveform");
+        if (n <= 0) return;
+        K2_REQUIRE(!p || s->rs_x0 + (int64_t)s->wav.size() + n < kResampleMaxInput, "accept_waveform: more than 2^36 samples in one stream");
+        offline_add(s, samples, n);
+    });
+}
+static void offline_add(k2hip_offline_stream* s, const float* samples, int64_t n) {
+    if (s->wav.capacity() == 0) {   // first samples of the stream: a buffer of the model's pool that is large enough, if there is one
+        std::lock_guard<std::mutex> lk(s->model->wav_mu);
+        auto& pool = s->model->wav_pool;
+        for (size_t i = pool.size(); i-- > 0;)
+            if (pool[i].capacity() >= (size_t)n) {
+                s->wav = std::move(pool[i]);
+                pool.erase(pool.begin() + (long)i);
+                break;
+            }
+    }
+    s->wav.append(s->model->engine, samples, (size_t)n);
 }
 int64_t k2hip_offline_stream_speech_length(const k2hip_offline_stream_t* s) {
     return s ? (int64_t)s->speech.size() + offline_pending_frames(s) * s->model->engine.model().cfg().feat : -1;
@@ -2777,7 +3056,7 @@ int32_t k2hip_offline_stream_get_speech(const k2hip_offline_stream_t* s_, float*
 static void offline_consume(k2hip_offline_stream* s, int ctx) {
     if ((int)s->tokens.size() > ctx) {
         const int64_t nf = offline_pending_frames(s);
-        if (nf > 0) s->wav.erase_front((size_t)nf * s->model->engine.model().cfg().fbank.frame_shift);
+        if (nf > 0) offline_erase_frames(s, nf);
         s->speech.clear();
         s->speech.shrink_to_fit();
     } else {
@@ -2820,6 +3099,7 @@ int32_t k2hip_offline_recognizer_get_results(k2hip_model_t* model, k2hip_offline
         for (int b = 0; b < B; b++) streams[b]->alts.assign(1, BeamAlt{});   // (a failed call leaves the start state)
         {
             EngineLock lk(e);
+            WaveSrcScope ws(e, streams, B);
             K2_REQUIRE(e.nbest() == 0 || e.beam() > 0 || e.ctc_prefix() > 0, "GetResults: the model keeps %d alternatives (k2hip_set_nbest) but decodes with "
                        "greedy_search, which has none", e.nbest());
             if (from_samples) e.offline_greedy_samples(ptrs.data(), nfl.data(), B, tok.data(), ts.data(), n.data(), max_tokens, false, /*pinned_src=*/true);
@@ -2887,6 +3167,7 @@ int32_t k2hip_offline_recognizer_get_result(k2hip_model_t* model, k2hip_offline_
         s->alts.assign(1, BeamAlt{});
         {
             EngineLock lk(e);
+            WaveSrcScope ws(e, &s, 1);
             // (the single-stream path is the reference's greedy loop whatever the decoding method: it has no alternatives)
             K2_REQUIRE(e.nbest() == 0, "GetResult: the single-stream path is greedy search and the model keeps %d alternatives "
                        "(k2hip_set_nbest) -- use GetResults", e.nbest());

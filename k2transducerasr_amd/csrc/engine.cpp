@@ -69,6 +69,7 @@ Engine::~Engine() {
     for (auto& kv : pe_cache_) (void)hipFree(kv.second);
     for (auto& kv : pp_cache_) (void)hipFree(kv.second);
     for (auto& kv : sinus_cache_) (void)hipFree(kv.second);
+    for (auto& kv : rs_cache_) (void)hipFree(kv.second.base);
     if (online_pool_) (void)hipFree(online_pool_);
     if (d_ptab_) (void)hipFree(d_ptab_);
     if (d_dec_table_) (void)hipFree(d_dec_table_);
@@ -1232,6 +1233,84 @@ void Engine::fbank_gather_finish() {
 }
 
 
+// ---- input at another sample rate ----------------------------------------------------------------------------------------------------
+const Engine::ResampleDev& Engine::resample_dev(const ResamplePlan& p) {
+    K2_REQUIRE(p.out_rate == model_->cfg().fbank.sample_rate, "resample: a plan for %d -> %d on a model that takes %d Hz", p.in_rate, p.out_rate,
+               model_->cfg().fbank.sample_rate);
+    auto it = rs_cache_.find(p.in_rate);
+    if (it != rs_cache_.end()) return it->second;
+    const size_t nb_w = align_up((int64_t)sizeof(float) * (int64_t)p.w.size(), 16), nb_i = sizeof(int32_t) * (size_t)p.ou;
+    std::vector<char> h(nb_w + 2 * nb_i);
+    memcpy(h.data(), p.w.data(), sizeof(float) * p.w.size());
+    memcpy(h.data() + nb_w, p.first.data(), nb_i);
+    memcpy(h.data() + nb_w + nb_i, p.ntaps.data(), nb_i);
+    ResampleDev d;
+    K2_HIP(hipMalloc(&d.base, h.size()));
+    if (hipError_t e = copy_blocking(d.base, h.data(), h.size(), hipMemcpyHostToDevice); e != hipSuccess) {
+        (void)hipFree(d.base);
+        K2_HIP(e);
+    }
+    d.w = reinterpret_cast<const float*>(d.base);
+    d.first = reinterpret_cast<const int*>(d.base + nb_w);
+    d.ntaps = d.first + p.ou;
+    return rs_cache_.emplace(p.in_rate, d).first->second;
+}
+
+ResampleRow Engine::resample_row(const ResamplePlan* p, const float* head, int64_t n_head, const float* tail, int64_t n_tail, int64_t x0, int64_t k0,
+                                 int64_t n_out, int dst_row) {
+    ResampleRow r;
+    r.head = head; r.n_head = n_head; r.tail = tail; r.n_tail = n_tail;
+    r.dst_row = dst_row;
+    if (!p) return r;
+    const ResampleDev& d = resample_dev(*p);
+    r.x0 = x0; r.k0 = k0; r.n_out = n_out; r.wmax = p->wmax;
+    r.w = d.w; r.first = d.first; r.ntaps = d.ntaps;
+    r.iu = p->iu; r.ou = p->ou; r.max_taps = p->max_taps;
+    return r;
+}
+
+void Engine::resample_host(const ResampleJob* jobs, int G) {
+    K2_REQUIRE(jobs && G > 0, "resample: empty call");
+    K2_HIP(hipSetDevice(device_));
+    // the staged inputs back to back, every signal on a 16-byte boundary; the outputs as rows of the longest
+    std::vector<int64_t> in_off((size_t)G);
+    int64_t n_in = 0, nmax = 1;
+    for (int g = 0; g < G; g++) {
+        const ResampleJob& j = jobs[g];
+        K2_REQUIRE(j.plan && j.n_head >= 0 && j.n_tail >= 0 && j.n_out >= 0 && (j.n_out == 0 || j.out), "resample: signal %d: bad arguments", g);
+        in_off[(size_t)g] = n_in;
+        n_in += (j.n_head + j.n_tail + 3) & ~(int64_t)3;
+        nmax = std::max(nmax, j.n_out);
+    }
+    nmax = (nmax + 3) & ~(int64_t)3;
+    const int64_t nb_in = (int64_t)sizeof(float) * n_in, nb_rows = align_up((int64_t)sizeof(ResampleRow) * G, 16), nb_out = (int64_t)sizeof(float) * G * nmax;
+    char* pin = static_cast<char*>(pinned_in(nb_in + nb_rows + nb_out + 64));
+    float* h_in = reinterpret_cast<float*>(pin);
+    ResampleRow* h_rows = reinterpret_cast<ResampleRow*>(pin + nb_in);
+    for (int g = 0; g < G; g++) {
+        const ResampleJob& j = jobs[g];
+        float* x = h_in + in_off[(size_t)g];
+        if (j.n_head) memcpy(x, j.head, sizeof(float) * (size_t)j.n_head);
+        if (j.n_tail) memcpy(x + j.n_head, j.tail, sizeof(float) * (size_t)j.n_tail);
+    }
+    float* d_out = nullptr;
+    run_sized([&](const Ctx& c) {
+        char* d_in = c.arena->take<char>(nb_in + nb_rows);
+        d_out = c.arena->take<float>((int64_t)G * nmax);
+        for (int g = 0; g < G; g++) {   // (the rows name device addresses: the arena's, the same in both passes once it is sized)
+            const ResampleJob& j = jobs[g];
+            h_rows[g] = resample_row(j.plan, c.dry ? nullptr : reinterpret_cast<const float*>(d_in) + in_off[(size_t)g], j.n_head + j.n_tail, nullptr, 0, j.x0, j.k0,
+                                     j.n_out, g);
+        }
+        if (!c.dry) K2_HIP(hipMemcpyAsync(d_in, pin, (size_t)(nb_in + nb_rows), hipMemcpyHostToDevice, c.stream));
+        resample_gather(c, h_rows, reinterpret_cast<const ResampleRow*>(d_in + nb_in), G, d_out, G, nmax);
+    });
+    K2_HIP(hipMemcpyAsync(pin + nb_in + nb_rows, d_out, (size_t)nb_out, hipMemcpyDeviceToHost, stream_));
+    K2_HIP(hipStreamSynchronize(stream_));
+    for (int g = 0; g < G; g++)
+        if (jobs[g].n_out) memcpy(jobs[g].out, pin + nb_in + nb_rows + sizeof(float) * (size_t)g * (size_t)nmax, sizeof(float) * (size_t)jobs[g].n_out);
+}
+
 void Engine::pad_host(const float* const* speech, const int64_t* n_floats, int B, int tail, float* out, int64_t cap, int64_t* Lout) {
     K2_REQUIRE(B > 0, "pad: empty batch");
     int64_t mx = 0, total = 0;
@@ -1690,8 +1769,9 @@ Engine::OfflineShape Engine::offline_shape(const char* who, int64_t longest, boo
 Engine::OfflineShape Engine::samples_shape(const float* const* samples, const int64_t* n_samples, int B) const {
     int64_t nmax = 0;
     for (int b = 0; b < B; b++) {
-        K2_REQUIRE(samples[b] != nullptr && fbank_num_frames(n_samples[b]) > 0, "stream %d: %lld samples give no frame", b, (long long)n_samples[b]);
-        nmax = std::max(nmax, n_samples[b]);
+        const int64_t n = wave_count(b, n_samples[b]);
+        K2_REQUIRE(samples[b] != nullptr && fbank_num_frames(n) > 0, "stream %d: %lld samples give no frame", b, (long long)n);
+        nmax = std::max(nmax, n);
     }
     return offline_shape("offline_greedy_from_samples", nmax);
 }
@@ -1796,8 +1876,15 @@ void Engine::offline_samples(const float* const* samples, const int64_t* n_sampl
     const int64_t nb_s = align_up((int64_t)sizeof(float) * B * ns, 16);
     // the host block: [samples (not with pinned_src)] | feature offsets | feature lengths | [sample pointers | sample counts]
     const int64_t hb_s = pinned_src ? 0 : nb_s, hb_in = hb_s + 32 * (int64_t)B;
+    // streams that hold input at another rate (set_wave_srcs): the resampler's row descriptors ride behind the table, and
+    // resample_gather fills the dense block in place of gather_samples
+    bool rs = false;
+    for (int b = 0; b < B && wave_srcs_; b++) rs = rs || wave_srcs_[b].plan;
+    K2_REQUIRE(!rs || pinned_src, "offline_greedy_from_samples: input at another rate is read from the streams' pinned queues only");
+    const int64_t nb_rows = rs ? align_up((int64_t)sizeof(ResampleRow) * B, 16) : 0;
     // (sized for the token download as well: finish_tokens takes the same buffer and must not re-allocate it under the upload)
-    char* pin = static_cast<char*>(pinned(std::max<int64_t>(hb_in, SearchOut::bytes_for(rows, max_tokens)) + 64));
+    char* pin = static_cast<char*>(pinned(std::max<int64_t>(hb_in + nb_rows, SearchOut::bytes_for(rows, max_tokens)) + 64));
+    ResampleRow* h_rows = reinterpret_cast<ResampleRow*>(pin + hb_in);
     long long* h_off = reinterpret_cast<long long*>(pin + hb_s);
     long long* h_len = h_off + B;
     const float** h_ptr = reinterpret_cast<const float**>(h_len + B);
@@ -1808,6 +1895,9 @@ void Engine::offline_samples(const float* const* samples, const int64_t* n_sampl
             K2_HIP(hipHostGetDevicePointer(&dp, const_cast<float*>(samples[b]), 0));
             h_ptr[b] = static_cast<const float*>(dp);
             h_cnt[b] = n_samples[b];
+            if (rs)
+                h_rows[b] = resample_row(wave_srcs_[b].plan, h_ptr[b], n_samples[b], nullptr, 0, wave_srcs_[b].x0, wave_srcs_[b].k0,
+                                         wave_srcs_[b].plan ? wave_count(b, n_samples[b]) : 0, b);
         }
     } else {
         auto stage = [&](int b_lo, int b_hi) {
@@ -1832,14 +1922,14 @@ void Engine::offline_samples(const float* const* samples, const int64_t* n_sampl
     }
     for (int b = 0; b < B; b++) {
         h_off[b] = (long long)b * n_fl;
-        h_len[b] = fbank_num_frames(n_samples[b]) * model_->cfg().feat;
+        h_len[b] = fbank_num_frames(wave_count(b, n_samples[b])) * model_->cfg().feat;
     }
     SearchOut out;
     SearchExtras ex;
     run_sized([&](const Ctx& c) {
         Arena& ar = *c.arena;
         out = SearchOut(ar, rows, max_tokens);
-        char* d_in = ar.take<char>(nb_s + 32 * (int64_t)B);
+        char* d_in = ar.take<char>(nb_s + 32 * (int64_t)B + nb_rows);
         float* d_s = reinterpret_cast<float*>(d_in);
         long long* d_off = reinterpret_cast<long long*>(d_in + nb_s);
         long long* d_len = d_off + B;
@@ -1849,10 +1939,11 @@ void Engine::offline_samples(const float* const* samples, const int64_t* n_sampl
         float* d_x = ar.take<float>((int64_t)B * L);
         if (!c.dry) {
             K2_HIP(hipEventRecord(ev_[0], c.stream));
-            if (pinned_src) K2_HIP(hipMemcpyAsync(d_in + nb_s, pin, (size_t)(32 * (int64_t)B), hipMemcpyHostToDevice, c.stream));
+            if (pinned_src) K2_HIP(hipMemcpyAsync(d_in + nb_s, pin, (size_t)(32 * (int64_t)B + nb_rows), hipMemcpyHostToDevice, c.stream));
             else K2_HIP(hipMemcpyAsync(d_in, pin, (size_t)(nb_s + 16 * (int64_t)B), hipMemcpyHostToDevice, c.stream));
         }
-        if (pinned_src) gather_samples(c, d_ptr, d_cnt, d_s, B, ns);
+        if (rs) resample_gather(c, h_rows, reinterpret_cast<const ResampleRow*>(d_in + nb_s + 32 * (int64_t)B), B, d_s, B, ns);
+        else if (pinned_src) gather_samples(c, d_ptr, d_cnt, d_s, B, ns);
         fbank(c, fbank_args(d_s, nmax, ns, B, sh.frames, d_feats));
         if (!c.dry) K2_HIP(hipEventRecord(ev_[1], c.stream));
         pad_logfloor(c, d_feats, d_off, d_len, d_x, B, L);
@@ -2950,6 +3041,45 @@ void Engine::debug_op_host(const char* op, const int64_t* iargs, int n_iargs, vo
             d.base.push_back(reinterpret_cast<char*>(table));
             K2_HIP(copy_blocking(table, h.data(), sizeof(float*) * (size_t)B, hipMemcpyHostToDevice));
             gather_samples(c, table, n, dst, B, nmax);
+        } else if (name == "resample_gather") {
+            // ints B, n_dst_rows, nmax, then per row (in_rate, out_rate, off_head, n_head, off_tail, n_tail, x0, k0, n_out, dst_row) --
+            // in_rate = 0: a pass-through row; the offsets are floats into the samples buffer; bufs samples, dst [n_dst_rows][nmax].
+            // The plans are built and uploaded here (tables freed with the call); the launcher checks every row's extents.
+            const int B = I(), n_dst = I();
+            const long long nmax = L();
+            K2_REQUIRE(B > 0 && B <= 64 && n_dst > 0 && nmax > 0, "debug_op_run resample_gather: B = %d, rows = %d, nmax = %lld", B, n_dst, nmax);
+            std::vector<long long> ia((size_t)B * 10);
+            for (auto& v : ia) v = L();
+            float* samples = P();
+            float* dst = P();
+            K2_REQUIRE(samples && dst && buf_bytes[1] >= 4 * (int64_t)n_dst * nmax, "debug_op_run resample_gather: two buffers are needed, dst of %d x %lld floats",
+                       n_dst, nmax);
+            std::vector<ResampleRow> rows((size_t)B);
+            for (int b = 0; b < B; b++) {
+                const long long* a = ia.data() + (size_t)b * 10;
+                K2_REQUIRE(a[2] >= 0 && a[3] >= 0 && a[4] >= 0 && a[5] >= 0 && 4 * (a[2] + a[3]) <= buf_bytes[0] && 4 * (a[4] + a[5]) <= buf_bytes[0],
+                           "debug_op_run resample_gather: row %d: pieces %lld + %lld and %lld + %lld floats", b, a[2], a[3], a[4], a[5]);
+                ResampleRow& r = rows[(size_t)b];
+                r.head = samples + a[2]; r.n_head = a[3]; r.tail = samples + a[4]; r.n_tail = a[5];
+                r.dst_row = (int)a[9];
+                if (a[0] == 0) continue;
+                const ResamplePlan p = resample_plan((int)a[0], (int)a[1]);
+                const size_t nw = p.w.size(), no = (size_t)p.ou;
+                char* t = nullptr;
+                K2_HIP(hipMalloc(&t, 4 * (nw + 2 * no)));
+                d.base.push_back(t);
+                K2_HIP(copy_blocking(t, p.w.data(), 4 * nw, hipMemcpyHostToDevice));
+                K2_HIP(copy_blocking(t + 4 * nw, p.first.data(), 4 * no, hipMemcpyHostToDevice));
+                K2_HIP(copy_blocking(t + 4 * (nw + no), p.ntaps.data(), 4 * no, hipMemcpyHostToDevice));
+                r.w = reinterpret_cast<const float*>(t); r.first = reinterpret_cast<const int*>(t + 4 * nw); r.ntaps = r.first + no;
+                r.iu = p.iu; r.ou = p.ou; r.max_taps = p.max_taps; r.wmax = p.wmax;
+                r.x0 = a[6]; r.k0 = a[7]; r.n_out = a[8];
+            }
+            ResampleRow* d_rows = nullptr;
+            K2_HIP(hipMalloc(&d_rows, sizeof(ResampleRow) * (size_t)B));
+            d.base.push_back(reinterpret_cast<char*>(d_rows));
+            K2_HIP(copy_blocking(d_rows, rows.data(), sizeof(ResampleRow) * (size_t)B, hipMemcpyHostToDevice));
+            resample_gather(c, rows.data(), d_rows, B, dst, n_dst, nmax);
         } else if (name == "convnext_cat") {
             float *a3 = P(), *pool = P();
             const long long ss = L(), off = L();

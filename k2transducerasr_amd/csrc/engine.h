@@ -14,6 +14,7 @@
 #include "kernels.h"
 #include "keywords.h"
 #include "model.h"
+#include "resample_plan.h"
 #include "search_out.h"
 
 namespace k2hip {
@@ -169,6 +170,32 @@ class Engine {
                                 int32_t* ts, int32_t* n_tokens, int max_tokens, bool single = false, bool pinned_src = false);
     void offline_greedy_samples_dev(const float* samples_dev, int64_t n_each, int B, int64_t* tokens, int32_t* ts,
                                     int32_t* n_tokens, int max_tokens);
+
+    // ---- input at another sample rate (resample.hip; DESIGN.md "Input at other sample rates") ----
+    // One signal of a resample_host call: outputs k0 .. k0 + n_out of `plan` over the input [head ; tail], whose first float is input
+    // sample x0 of its stream, into out (host).  The plans are the caller's (api.cpp keeps them per model and input rate); their tables
+    // are uploaded once per input rate and stay resident.
+    struct ResampleJob {
+        const ResamplePlan* plan;
+        const float* head;
+        int64_t n_head;
+        const float* tail;
+        int64_t n_tail;
+        int64_t x0, k0, n_out;
+        float* out;
+    };
+    // G signals, any mix of plans, in ONE resample_gather launch: one upload of the staged inputs, one download of the outputs
+    void resample_host(const ResampleJob* jobs, int G);
+    // Streams of the next from-samples batch that hold input at another rate: entry b names stream b's plan (null: the stream holds
+    // samples at the model's rate), the input index x0 of its first queued sample and the outputs k0 it has consumed; its n_samples
+    // counts INPUT samples.  While set (the caller clears it after the call), offline_samples counts with the outputs the queued input
+    // gives and fills the dense sample block through resample_gather; with no plan in the batch it issues exactly the launches it
+    // always did.
+    struct WaveSrc {
+        const ResamplePlan* plan = nullptr;
+        int64_t x0 = 0, k0 = 0;
+    };
+    void set_wave_srcs(const WaveSrc* w) { wave_srcs_ = w; }
 
     // ---- pipelined (asynchronous) form of offline_greedy_samples_dev ----
     // submit() enqueues fbank + pad + encoder on the encoder stream and the greedy loop + D2H
@@ -448,6 +475,23 @@ class Engine {
     // offline_greedy_samples with the stage named: what the public entry and the two align entries run
     void offline_samples(const float* const* samples, const int64_t* n_samples, int B, const SearchStage& stage, int64_t* tokens, int32_t* ts,
                          int32_t* n_tokens, int max_tokens, bool pinned_src);
+    const WaveSrc* wave_srcs_ = nullptr;
+    // samples of the model's rate that stream b of a from-samples batch gives
+    int64_t wave_count(int b, int64_t n_samples) const {
+        const WaveSrc* w = wave_srcs_ ? wave_srcs_ + b : nullptr;
+        return w && w->plan ? w->plan->num_out(w->x0 + n_samples) - w->k0 : n_samples;
+    }
+    // a plan's tables on the device: one allocation [w | first | ntaps] per input rate, made on first use
+    struct ResampleDev {
+        char* base = nullptr;
+        const float* w = nullptr;
+        const int *first = nullptr, *ntaps = nullptr;
+    };
+    std::map<int, ResampleDev> rs_cache_;
+    const ResampleDev& resample_dev(const ResamplePlan& p);
+    // the launcher's row for outputs k0 .. k0 + n_out of `p` (null: pass-through) over [head ; tail]
+    ResampleRow resample_row(const ResamplePlan* p, const float* head, int64_t n_head, const float* tail, int64_t n_tail, int64_t x0, int64_t k0,
+                             int64_t n_out, int dst_row);
     // timing_ from ev_[0..5]; which of the legs in front of the encoder the call has
     void fill_timing(bool fbank_leg, bool pad_leg);
     const float* pos_emb(int T);  // cached CompactRelPositionalEncoding table on device

@@ -421,6 +421,28 @@ void fbank(const Ctx& ctx, const FbankArgs& a);
 // dst[b][0 .. nmax) = src[b][0 .. n[b]) followed by zeros; src[b] may be pinned host memory (read in place over PCIe), 16 B aligned
 void gather_samples(const Ctx& ctx, const float* const* src, const long long* n, float* dst, int B, long long nmax);
 
+// ---- sample-rate conversion (resample.hip; the plan: resample_plan.h, the host reference: resample_ref.h) -------------------------
+// One row of a resample_gather launch.  Its input is two pieces [head ; tail] (the carried tail of a stream and its new samples, or
+// either alone), device memory or pinned host memory read in place.  w == nullptr: a pass-through row, dst row = the n_head + n_tail
+// samples followed by zeros, as gather_samples moves them.  Otherwise outputs k0 .. k0 + n_out of the plan, followed by zeros;
+// head[0] is input sample x0 of the stream, and samples in front of input sample 0 read as zero.
+struct ResampleRow {
+    const float* head = nullptr;
+    const float* tail = nullptr;
+    long long n_head = 0, n_tail = 0;
+    long long x0 = 0, k0 = 0, n_out = 0;
+    long long wmax = 0;                 // the plan's window in ticks: the launcher checks every row's reads against its input with it
+    const float* w = nullptr;           // device: [ou][max_taps]
+    const int* first = nullptr;         // device: [ou]
+    const int* ntaps = nullptr;         // device: [ou]
+    int iu = 0, ou = 0, max_taps = 0;
+    int dst_row = 0;
+};
+constexpr int kResampleTile = 1024;     // outputs per workgroup trip at most (fewer when the ratio iu / ou is large: the span is staged in LDS)
+// rows: B descriptors in host memory (checked here: no row reads outside its two pieces or writes outside its dst row), d_rows: the
+// same B descriptors in device memory.  dst [n_dst_rows][nmax].
+void resample_gather(const Ctx& ctx, const ResampleRow* rows, const ResampleRow* d_rows, int B, float* dst, int n_dst_rows, long long nmax);
+
 // ---- decoder / joiner / greedy ----------------------------------------------------
 struct DecJoinW {
     const float* emb;      // [V, DD]
