@@ -106,10 +106,10 @@ def twin_beam_search(oracle, enc_out, beam=4, lm=None, scale=0.0, graph=None):
         log_probs.add_(ys_log_probs)
         V = log_probs.size(-1)
         log_probs = log_probs.reshape(-1)
-        # the 2 * beam best in (score desc, flat index asc) order: torch.topk, ties put into index order
-        tv, ti = log_probs.topk(min(2 * beam, log_probs.numel()))
-        order = np.lexsort((ti.numpy(), -tv.numpy()))
-        tv, ti = tv[order], ti[order]
+        # the 2 * beam best in (score desc, flat index asc) order.  (A full sort, not torch.topk: of a block of exactly tied scores that
+        # reaches past the 2 * beam-th place topk returns whichever members it likes, not the lowest flat indexes.)
+        ti = torch.from_numpy(np.lexsort((np.arange(log_probs.numel()), -log_probs.numpy()))[: 2 * beam].copy())
+        tv = log_probs[ti]
         idx[t, : len(ti)] = ti.numpy()
         val[t, : len(ti)] = tv.numpy()
         want = min(beam, log_probs.numel())
