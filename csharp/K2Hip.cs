@@ -115,6 +115,35 @@ namespace K2TransducerAsr.Hip
         [DllImport(Lib)] internal static extern int k2hip_online_stream_set_hotwords(IntPtr stream, IntPtr hotwords);
         [DllImport(Lib)] internal static extern int k2hip_beam_stream_set_hotwords(IntPtr stream, IntPtr hotwords);
 
+        // voice activity detection and long recordings (include/k2hip.h "Voice activity detection and long recordings"); everything in
+        // fbank frames.  Declared here, not compiled in this repository (like the rest of this folder).
+        [StructLayout(LayoutKind.Sequential)]
+        internal struct VadConfig
+        {
+            public int band_lo, band_hi, floor_window;
+            public float rise, margin, abs_floor;
+            public int min_silence, min_speech, speech_pad, max_speech;
+        }
+        [DllImport(Lib)] internal static extern int k2hip_vad_default_config(IntPtr model, out VadConfig cfg);
+        [DllImport(Lib)] internal static extern int k2hip_vad_stream_create(IntPtr model, ref VadConfig cfg, out IntPtr stream);
+        [DllImport(Lib)] internal static extern int k2hip_vad_stream_destroy(IntPtr stream);
+        [DllImport(Lib)] internal static extern int k2hip_vad_stream_reset(IntPtr stream);
+        [DllImport(Lib)] internal static extern int k2hip_vad_stream_flush(IntPtr stream);
+        [DllImport(Lib)] internal static extern int k2hip_vad_accept_features_batch(IntPtr model, IntPtr[] streams, IntPtr[] feats, long[] nFrames, int B);
+        [DllImport(Lib)] internal static extern int k2hip_vad_accept_samples_batch(IntPtr model, IntPtr[] streams, int sampleRate, IntPtr[] samples, long[] n, int B);
+        [DllImport(Lib)] internal static extern int k2hip_vad_stream_is_speech(IntPtr stream);
+        [DllImport(Lib)] internal static extern long k2hip_vad_stream_num_frames(IntPtr stream);
+        [DllImport(Lib)] internal static extern int k2hip_vad_stream_num_segments(IntPtr stream);
+        [DllImport(Lib)] internal static extern int k2hip_vad_stream_get_segments(IntPtr stream, long[] start, long[] end, int[] forced, int cap);
+        [DllImport(Lib)] internal static extern int k2hip_vad_stream_pop_segments(IntPtr stream, int n);
+        // cfg: IntPtr.Zero = the defaults (a pinned VadConfig otherwise)
+        [DllImport(Lib)] internal static extern int k2hip_offline_recognize_long(IntPtr model, int sampleRate, float[] samples, long n, IntPtr cfg, int maxBatch,
+                                                                               long maxBatchFrames, out IntPtr result);
+        [DllImport(Lib)] internal static extern int k2hip_long_result_num_segments(IntPtr result);
+        [DllImport(Lib)] internal static extern int k2hip_long_result_get_segment(IntPtr result, int i, out long start, out long end, out int forced, out int batch);
+        [DllImport(Lib)] internal static extern int k2hip_long_result_get_tokens(IntPtr result, int i, long[] tokens, int[] timestamps, int cap, out int n);
+        [DllImport(Lib)] internal static extern int k2hip_long_result_destroy(IntPtr result);
+
         // Which GPU?  The reference's constructors (OfflineRecognizer.cs:27-28, OnlineRecognizer.cs:18-19) take file paths and nothing
         // else, and they stay as they are: the device rides on the paths.
         //   encoderFilePath "model.k2w@3"                 -> container "model.k2w" on device 3 (the suffix is split off only when what

@@ -184,6 +184,44 @@ namespace K2TransducerAsr
             finally { K2Hip.k2hip_tokens_destroy(tokens); }
         }
 
+        // A long recording in one call (no reference counterpart; k2hip.h "Voice activity detection and long recordings"): the device cuts
+        // it into segments with its voice activity detector and decodes them in batches.  One entry per segment: its range in seconds,
+        // whether it was cut by force at max_speech, its token ids and their times in seconds of the recording.  The detector's level
+        // defaults are untuned.  Token -> text is the caller's (DecodeMulti works on streams; these are plain id lists).
+        public class LongSegment
+        {
+            public double StartSeconds, EndSeconds;
+            public bool Forced;
+            public long[] Tokens;
+            public double[] TokenSeconds;
+        }
+        public List<LongSegment> GetResultsLong(float[] samples, int sampleRate, int maxBatch = 32, long maxBatchFrames = 32000)
+        {
+            if (!(_offlineProj is OfflineProjOfHip proj)) throw new InvalidOperationException("GetResultsLong: not a libk2hip recognizer");
+            const double frameShift = 0.01, encoderFrame = 0.04;   // 10 ms fbank frames, subsampled by 4
+            K2Hip.Check(K2Hip.k2hip_offline_recognize_long(proj.Handle, sampleRate, samples, samples.LongLength, IntPtr.Zero, maxBatch, maxBatchFrames,
+                                                           out IntPtr result), "Offline recognition failed");
+            try
+            {
+                var list = new List<LongSegment>();
+                int count = K2Hip.k2hip_long_result_num_segments(result);
+                for (int i = 0; i < count; i++)
+                {
+                    K2Hip.Check(K2Hip.k2hip_long_result_get_segment(result, i, out long start, out long end, out int forced, out int _), "GetResultsLong failed");
+                    K2Hip.k2hip_long_result_get_tokens(result, i, null, null, 0, out int n);   // (the count; K2HIP_ERR_CAPACITY when n > 0)
+                    var tokens = new long[n];
+                    var ts = new int[n];
+                    K2Hip.Check(K2Hip.k2hip_long_result_get_tokens(result, i, tokens, ts, n, out n), "GetResultsLong failed");
+                    var seg = new LongSegment { StartSeconds = start * frameShift, EndSeconds = end * frameShift, Forced = forced != 0, Tokens = tokens,
+                                                TokenSeconds = new double[n] };
+                    for (int k = 0; k < n; k++) seg.TokenSeconds[k] = seg.StartSeconds + ts[k] * encoderFrame;
+                    list.Add(seg);
+                }
+                return list;
+            }
+            finally { K2Hip.k2hip_long_result_destroy(result); }
+        }
+
         // the constructor's early branch (see the header): everything :30-68 does, for a .k2w container
         private string _tokensFilePath;   // (SetNgramLm reads the ARPA words through the same token table)
         private void InitHip(string encoderFilePath, string decoderFilePath, string tokensFilePath, string decodingMethod, int sampleRate, int featureDim)

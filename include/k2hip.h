@@ -982,6 +982,75 @@ int32_t k2hip_online_stream_get_score(const k2hip_online_stream_t* s, float* sco
  * cached_conv of `layer` [K-1, D] */
 int32_t k2hip_online_stream_state(k2hip_online_stream_t* s, int32_t layer, int32_t kind, float* out, int64_t cap, int64_t* n);
 
+/* ---- Voice activity detection and long recordings ---------------------------------------------------------------------------------
+ * No reference counterpart: the reference has only IsFinished(isEndpoint) and is fed pre-cut files.  The detector works on what the
+ * engine computes anyway, the log-mel features, so a segment is a range of rows of a feature matrix and its transcript is exactly
+ * what the offline entries give for the same samples.  Everything is counted in fbank frames (the model's frame_shift_ms and
+ * frame_length_ms: 160 and 400 samples at 16 kHz in every preset); the normative text is csrc/vad_ref.h, DESIGN.md "Voice activity
+ * detection and long recordings" the prose.
+ * Per frame t of a stream, numbered from its start or its last reset:
+ *   s_t = float32 mean of x[t][band_lo .. band_hi) in vad_ref.h's fixed order, m_t = the mean of s_{t-4} .. s_t (s_u := s_0 for u < 0,
+ *   summed left to right, times 0.2f), n_t = min over the last floor_window frames u of m_u + rise * (float)(t - u) (product and sum
+ *   rounded separately), d_t = (m_t - n_t > margin) && (m_t > abs_floor).
+ * A segment opens at the first speech frame, closes after min_silence frames of silence (dropped if shorter than min_speech), and is
+ * cut by force once it holds max_speech frames: at the frame with the smallest m among the last max_speech / 2, the earliest on ties.
+ * Reported segments [start, end) carry speech_pad frames on each side, clipped by the previous segment's end, by frame 0 and -- at
+ * a flush -- by the stream's length; a forced cut gets no padding on either side.  Samples of a segment:
+ * [start * frame_shift, (end - 1) * frame_shift + frame_len).  Any chunking of a stream gives the same bits.
+ * The level defaults (rise 0.002, margin 2.0, abs_floor -12.0; natural-log power units, the unit of the features) are UNTUNED:
+ * nobody has measured them on real speech.  The other defaults: floor_window 1000, min_silence 50, min_speech 25, speech_pad 10,
+ * max_speech 2000, and the mel bins whose centre frequency lies in [300, 3500] Hz.
+ * Refused with K2HIP_ERR_INVALID, the field named: band_lo >= band_hi or outside the feature row, floor_window < 8,
+ * min_silence < 2 * speech_pad, max_speech < 2 * min_speech, max_speech / 2 > floor_window, a count <= 0, a level that is not
+ * finite; with K2HIP_ERR_UNSUPPORTED: floor_window > 1024. */
+typedef struct k2hip_vad_config {
+    int32_t band_lo, band_hi;   /* mel bins [lo, hi) */
+    int32_t floor_window;       /* W */
+    float rise, margin, abs_floor;
+    int32_t min_silence, min_speech, speech_pad, max_speech;
+} k2hip_vad_config;
+typedef struct k2hip_vad_stream k2hip_vad_stream_t;
+int32_t k2hip_vad_default_config(const k2hip_model_t* model, k2hip_vad_config* cfg);
+int32_t k2hip_vad_stream_create(k2hip_model_t* model, const k2hip_vad_config* cfg, k2hip_vad_stream_t** out);
+int32_t k2hip_vad_stream_destroy(k2hip_vad_stream_t* s);
+/* the stream as if freshly created: frames, carried state, queued samples, sample rate and unread segments are dropped */
+int32_t k2hip_vad_stream_reset(k2hip_vad_stream_t* s);
+/* end of audio: an open segment is closed and reported (its padded end clipped to the stream's length); samples short of a frame
+ * are dropped; then the stream is as after a reset, except that the reported segments stay until they are popped */
+int32_t k2hip_vad_stream_flush(k2hip_vad_stream_t* s);
+/* feats[b]: n_frames[b] rows of feature_dim floats for streams[b]; 0 leaves a stream untouched.  One batched call on the device. */
+int32_t k2hip_vad_accept_features_batch(k2hip_model_t* model, k2hip_vad_stream_t* const* streams, const float* const* feats,
+                                        const int64_t* n_frames, int32_t B);
+/* samples[b]: n[b] samples at sample_rate for streams[b].  fbank runs on the device and the features never leave it; a stream carries
+ * the samples behind its last whole frame shift, as an online stream does.  A sample_rate other than the model's goes through the
+ * resampler under the rules of "Input at other sample rates": a stream's rate is fixed by its first samples until a reset or flush. */
+int32_t k2hip_vad_accept_samples_batch(k2hip_model_t* model, k2hip_vad_stream_t* const* streams, int32_t sample_rate,
+                                       const float* const* samples, const int64_t* n, int32_t B);
+/* 1 while a segment is open (the machine's `trig`), 0 otherwise; -1 on a null stream */
+int32_t k2hip_vad_stream_is_speech(const k2hip_vad_stream_t* s);
+/* frames taken since the stream's start, reset or flush */
+int64_t k2hip_vad_stream_num_frames(const k2hip_vad_stream_t* s);
+/* reported segments not popped yet, oldest first */
+int32_t k2hip_vad_stream_num_segments(const k2hip_vad_stream_t* s);
+int32_t k2hip_vad_stream_get_segments(const k2hip_vad_stream_t* s, int64_t* start, int64_t* end, int32_t* forced, int32_t cap);
+int32_t k2hip_vad_stream_pop_segments(k2hip_vad_stream_t* s, int32_t n);
+/* A long recording in one call: fbank over all of it into a resident block on the device (32 KB per second of audio), the detector
+ * and its flush, the segments packed in order into batches -- a batch closes at max_batch segments, or when (count + 1) * longest
+ * frames would exceed max_batch_frames; a segment longer than that on its own is a batch of one --, each batch gathered device to
+ * device and decoded by the model's current offline search exactly as k2hip_offline_recognizer_get_results runs it, the best
+ * hypothesis kept.  Timestamps are segment-local encoder frames; the segment's frame range goes with them, and `batch` names the
+ * batch it was decoded in (the offline encoder does not mask padding: a segment's tokens are those of k2hip_offline_greedy_from_samples
+ * on the sample ranges of its batch).  cfg == NULL: the defaults.  A recording of more than 2^27 samples at the model's rate (2 h 19 min
+ * at 16 kHz) is refused with K2HIP_ERR_UNSUPPORTED.  A sample_rate other than the model's is resampled first. */
+typedef struct k2hip_long_result k2hip_long_result_t;
+int32_t k2hip_offline_recognize_long(k2hip_model_t* model, int32_t sample_rate, const float* samples, int64_t n, const k2hip_vad_config* cfg,
+                                     int32_t max_batch, int64_t max_batch_frames, k2hip_long_result_t** result);
+int32_t k2hip_long_result_num_segments(const k2hip_long_result_t* r);
+int32_t k2hip_long_result_get_segment(const k2hip_long_result_t* r, int32_t i, int64_t* start, int64_t* end, int32_t* forced, int32_t* batch);
+/* *n = the segment's token count; K2HIP_ERR_CAPACITY when cap is short (nothing is written) */
+int32_t k2hip_long_result_get_tokens(const k2hip_long_result_t* r, int32_t i, int64_t* tokens, int32_t* timestamps, int32_t cap, int32_t* n);
+int32_t k2hip_long_result_destroy(k2hip_long_result_t* r);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

@@ -236,6 +236,23 @@ int32_t k2hip_debug_resample_plans(k2hip_model_t* model, int32_t* n);
  *     The samples buffer starts on a 256-byte boundary, so an offset that is no multiple of 4 puts a piece off the 16-byte boundary.
  *     The launcher checks on the host that no row reads outside its pieces or writes outside its row: K2HIP_ERR_UNSUPPORTED. */
 
+/* ---- voice activity detection (k2hip.h "Voice activity detection and long recordings"; tests/test_vad.py, test_vad_gpu.py) ------- */
+/* host only, no model and no GPU: the config rules for feature rows of num_bins floats; the default band of a filterbank; the long
+ * entry's packing rule over n segment lengths in frames (batch_of [n]) */
+int32_t k2hip_debug_vad_check_config(const k2hip_vad_config* cfg, int32_t num_bins);
+int32_t k2hip_debug_vad_default_config(int32_t sample_rate, int32_t num_bins, float low_freq, float high_freq, k2hip_vad_config* cfg);
+int32_t k2hip_debug_vad_pack(const int64_t* len, int32_t n, int32_t max_batch, int64_t max_batch_frames, int32_t* batch_of);
+/* a stream without a model, for rows of num_bins floats: every k2hip_vad_stream_* entry works on it, the accept entries do not */
+int32_t k2hip_debug_vad_ref_stream_create(int32_t num_bins, const k2hip_vad_config* cfg, k2hip_vad_stream_t** out);
+/* the float32 host reference (csrc/vad_ref.h), no GPU: n rows (num_bins or the model's feature_dim floats each) pushed into the stream's
+ * carried state, on a stream of either kind; the taps m, n, d (each may be NULL) get n entries */
+int32_t k2hip_debug_vad_ref_push(k2hip_vad_stream_t* s, const float* feats, int64_t n, float* tap_m, float* tap_n, uint8_t* tap_d);
+/* the taps of the model's last accept call (or of its last k2hip_offline_recognize_long): stream b's frames of that call.  *n_frames is
+ * set; K2HIP_ERR_CAPACITY when cap is short */
+int32_t k2hip_debug_vad_taps(k2hip_model_t* model, int32_t b, float* m, float* n, uint8_t* d, int64_t cap, int64_t* n_frames);
+/* host milliseconds of the last k2hip_offline_recognize_long by leg: fbank (with the upload), the detector, the batches */
+int32_t k2hip_debug_long_timing(k2hip_model_t* model, double* ms3);
+
 /* ---- GEMM tuning ------------------------------------------------------------------------------- */
 /* time `iters` launches of a shape / configuration on pseudo-random operands (tools/gemm_lab.py, gemm_tune.py) */
 int32_t k2hip_debug_gemm(k2hip_model_t* model, int32_t M, int32_t N, int32_t K, int32_t act, int32_t with_res, int32_t cfg,

@@ -27,6 +27,8 @@ from .binding import (  # noqa: F401
     OnlineStream,
     StreamBatch,
     TokenTable,
+    VadConfig,
+    VadStream,
     build_library,
     library_path,
     load_library,
@@ -50,6 +52,8 @@ __all__ = [
     "OnlineStream",
     "StreamBatch",
     "TokenTable",
+    "VadConfig",
+    "VadStream",
     "build_library",
     "library_path",
     "load_library",

@@ -588,6 +588,135 @@ class CtcKeywordStream:
         return v, st
 
 
+class VadConfig(C.Structure):
+    """k2hip_vad_config (include/k2hip.h "Voice activity detection and long recordings"): everything in fbank frames; the level
+    defaults are in natural-log power units and untuned.  VadConfig.from_seconds converts durations."""
+    _fields_ = [("band_lo", C.c_int32), ("band_hi", C.c_int32), ("floor_window", C.c_int32), ("rise", C.c_float), ("margin", C.c_float),
+                ("abs_floor", C.c_float), ("min_silence", C.c_int32), ("min_speech", C.c_int32), ("speech_pad", C.c_int32),
+                ("max_speech", C.c_int32)]
+
+    def copy(self, **changes) -> "VadConfig":
+        c = VadConfig.from_buffer_copy(self)
+        for k, v in changes.items():
+            if k not in dict(self._fields_):
+                raise AttributeError(k)
+            setattr(c, k, v)
+        return c
+
+    def with_seconds(self, frame_shift_s: float = 0.01, **seconds) -> "VadConfig":
+        """a copy with the named durations (floor_window, min_silence, min_speech, speech_pad, max_speech) given in seconds"""
+        return self.copy(**{k: int(round(v / frame_shift_s)) for k, v in seconds.items()})
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+def _bind_vad(L):
+    if getattr(L, "_vad_bound", False):
+        return
+    vp, cp, bp = C.c_void_p, C.POINTER(VadConfig), C.POINTER(C.c_uint8)
+    L.k2hip_vad_default_config.argtypes = [vp, cp]
+    L.k2hip_vad_stream_create.argtypes = [vp, cp, C.POINTER(vp)]
+    for f in ("destroy", "reset", "flush", "is_speech", "num_segments"):
+        getattr(L, "k2hip_vad_stream_" + f).argtypes = [vp]
+    L.k2hip_vad_stream_num_frames.argtypes = [vp]
+    L.k2hip_vad_stream_num_frames.restype = C.c_int64
+    L.k2hip_vad_stream_get_segments.argtypes = [vp, lp, lp, ip, C.c_int32]
+    L.k2hip_vad_stream_pop_segments.argtypes = [vp, C.c_int32]
+    L.k2hip_vad_accept_features_batch.argtypes = [vp, C.POINTER(vp), C.POINTER(fp), lp, C.c_int32]
+    L.k2hip_vad_accept_samples_batch.argtypes = [vp, C.POINTER(vp), C.c_int32, C.POINTER(fp), lp, C.c_int32]
+    L.k2hip_offline_recognize_long.argtypes = [vp, C.c_int32, fp, C.c_int64, cp, C.c_int32, C.c_int64, C.POINTER(vp)]
+    L.k2hip_long_result_num_segments.argtypes = [vp]
+    L.k2hip_long_result_get_segment.argtypes = [vp, C.c_int32, lp, lp, ip, ip]
+    L.k2hip_long_result_get_tokens.argtypes = [vp, C.c_int32, lp, ip, C.c_int32, ip]
+    L.k2hip_long_result_destroy.argtypes = [vp]
+    L.k2hip_debug_vad_check_config.argtypes = [cp, C.c_int32]
+    L.k2hip_debug_vad_default_config.argtypes = [C.c_int32, C.c_int32, C.c_float, C.c_float, cp]
+    L.k2hip_debug_vad_pack.argtypes = [lp, C.c_int32, C.c_int32, C.c_int64, ip]
+    L.k2hip_debug_vad_ref_stream_create.argtypes = [C.c_int32, cp, C.POINTER(vp)]
+    L.k2hip_debug_vad_ref_push.argtypes = [vp, fp, C.c_int64, fp, fp, bp]
+    L.k2hip_debug_vad_taps.argtypes = [vp, C.c_int32, fp, fp, bp, C.c_int64, lp]
+    L.k2hip_debug_long_timing.argtypes = [vp, C.POINTER(C.c_double)]
+    L._vad_bound = True
+
+
+class VadStream:
+    """One audio stream of the voice activity detector (k2hip_vad_stream_*).  Segments are dict(start, end, forced) in fbank frames,
+    numbered from the stream's start, reset or flush; is_speech tells whether a segment is open.  VadStream(None, cfg, num_bins=n)
+    is a stream without a model: only ref_push (the float32 host reference, no GPU) feeds it."""
+
+    def __init__(self, model: Optional["Model"], config: Optional[VadConfig] = None, num_bins: Optional[int] = None):
+        self._m = model
+        self._L = model._L if model is not None else load_library()
+        _bind_vad(self._L)
+        self.config = (config if config is not None else model.vad_default_config()).copy()
+        h = C.c_void_p()
+        if model is None:
+            self.num_bins = int(num_bins)
+            rc = self._L.k2hip_debug_vad_ref_stream_create(self.num_bins, C.byref(self.config), C.byref(h))
+        else:
+            self.num_bins = model.feature_dim
+            rc = self._L.k2hip_vad_stream_create(model.handle, C.byref(self.config), C.byref(h))
+        self._chk(rc)
+        self._h = h
+        if model is not None:
+            model._children.add(self)
+
+    def _chk(self, rc):
+        if rc != 0:
+            raise K2HipError(rc, self._L.k2hip_last_error().decode())
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.k2hip_vad_stream_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self):
+        self._chk(self._L.k2hip_vad_stream_reset(self._h))
+
+    def flush(self):
+        """end of audio: an open segment is closed and reported; the stream then starts over at frame 0"""
+        self._chk(self._L.k2hip_vad_stream_flush(self._h))
+
+    @property
+    def is_speech(self) -> bool:
+        return bool(self._L.k2hip_vad_stream_is_speech(self._h))
+
+    @property
+    def num_frames(self) -> int:
+        return int(self._L.k2hip_vad_stream_num_frames(self._h))
+
+    def accept_features(self, feats):
+        self._m.vad_accept_features([self], [feats])
+
+    def accept_waveform(self, sample_rate: int, samples):
+        """samples at any rate (fbank, and the resampler where needed, run on the device; the stream carries what is short of a frame)"""
+        self._m.vad_accept_samples([self], sample_rate, [samples])
+
+    def segments(self, pop: bool = False):
+        n = self._L.k2hip_vad_stream_num_segments(self._h)
+        st, en = np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.int64)
+        fo = np.zeros(max(n, 1), np.int32)
+        self._chk(self._L.k2hip_vad_stream_get_segments(self._h, _l(st), _l(en), _i(fo), n))
+        if pop:
+            self._chk(self._L.k2hip_vad_stream_pop_segments(self._h, n))
+        return [dict(start=int(st[i]), end=int(en[i]), forced=int(fo[i])) for i in range(n)]
+
+    def ref_push(self, feats):
+        """the float32 host reference over these rows (k2hip_debug_vad_ref_push): returns the taps (m, n, d)"""
+        f = _f32(feats).reshape(-1, self.num_bins)
+        n = f.shape[0]
+        m, nn, d = np.zeros(n, np.float32), np.zeros(n, np.float32), np.zeros(n, np.uint8)
+        self._chk(self._L.k2hip_debug_vad_ref_push(self._h, _f(f), n, _f(m), _f(nn), d.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return m, nn, d
+
+
 class Model:
     """One model replica on one GPU (k2hip_model_t): the IOfflineProj operators."""
 
@@ -674,6 +803,84 @@ class Model:
         got = C.c_int64()
         self._chk(self._L.k2hip_resample(self._h, int(in_rate), _f(s), s.size, _f(out), out.size, C.byref(got)))
         return out[: got.value]
+
+    # ---- voice activity detection and long recordings (include/k2hip.h "Voice activity detection and long recordings")
+    def vad_default_config(self) -> VadConfig:
+        """the defaults for this model's filterbank: the mel bins centred in [300, 3500] Hz; the levels are untuned"""
+        _bind_vad(self._L)
+        cfg = VadConfig()
+        self._chk(self._L.k2hip_vad_default_config(self._h, C.byref(cfg)))
+        return cfg
+
+    def vad_accept_features(self, streams: Sequence["VadStream"], feats: Sequence[np.ndarray]):
+        """feats[b] [n_b, feature_dim] for streams[b], all streams in one batched call on the device (0 rows leave a stream untouched)"""
+        _bind_vad(self._L)
+        B = len(streams)
+        fs = [_f32(f).reshape(-1, self.feature_dim) for f in feats]
+        if len(fs) != B:
+            raise ValueError(f"vad_accept_features: {len(fs)} feature matrices for {B} streams")
+        arr = (C.c_void_p * B)(*[s._h.value for s in streams])
+        ptrs = (fp * B)(*[_f(f) for f in fs])
+        n = np.array([f.shape[0] for f in fs], np.int64)
+        self._chk(self._L.k2hip_vad_accept_features_batch(self._h, arr, ptrs, _l(n), B))
+
+    def vad_accept_samples(self, streams: Sequence["VadStream"], sample_rate: int, samples: Sequence[np.ndarray]):
+        """samples[b] at sample_rate for streams[b]; fbank runs on the device and the features stay there"""
+        _bind_vad(self._L)
+        B = len(streams)
+        ss = [_f32(s).reshape(-1) for s in samples]
+        if len(ss) != B:
+            raise ValueError(f"vad_accept_samples: {len(ss)} signals for {B} streams")
+        arr = (C.c_void_p * B)(*[s._h.value for s in streams])
+        ptrs = (fp * B)(*[_f(s) for s in ss])
+        n = np.array([s.size for s in ss], np.int64)
+        self._chk(self._L.k2hip_vad_accept_samples_batch(self._h, arr, int(sample_rate), ptrs, _l(n), B))
+
+    def vad_taps(self, b: int = 0):
+        """the taps (m, n, d) of stream b's frames in the model's last VAD call (the debug header's view)"""
+        _bind_vad(self._L)
+        cnt = C.c_int64()
+        rc = self._L.k2hip_debug_vad_taps(self._h, b, None, None, None, 0, C.byref(cnt))
+        if rc != 0 and cnt.value == 0:
+            self._chk(rc)
+        m, n, d = np.zeros(cnt.value, np.float32), np.zeros(cnt.value, np.float32), np.zeros(cnt.value, np.uint8)
+        if cnt.value:
+            self._chk(self._L.k2hip_debug_vad_taps(self._h, b, _f(m), _f(n), d.ctypes.data_as(C.POINTER(C.c_uint8)), cnt.value, C.byref(cnt)))
+        return m, n, d
+
+    def recognize_long(self, samples, sample_rate: Optional[int] = None, config: Optional[VadConfig] = None, max_batch: int = 32,
+                       max_batch_frames: int = 32000):
+        """one long recording: fbank over all of it on the device, the detector, the segments decoded in batches by the model's current
+        offline search (k2hip_offline_recognize_long).  Returns a list of dict(start, end, forced, batch, tokens, timestamps): start /
+        end in fbank frames of the recording, timestamps in encoder frames of the segment."""
+        _bind_vad(self._L)
+        s = _f32(samples).reshape(-1)
+        h = C.c_void_p()
+        self._chk(self._L.k2hip_offline_recognize_long(self._h, int(sample_rate or self.sample_rate), _f(s), s.size,
+                                                       C.byref(config) if config is not None else None, int(max_batch), int(max_batch_frames),
+                                                       C.byref(h)))
+        try:
+            out = []
+            for i in range(self._L.k2hip_long_result_num_segments(h)):
+                st, en, fo, ba, n = C.c_int64(), C.c_int64(), C.c_int32(), C.c_int32(), C.c_int32()
+                self._chk(self._L.k2hip_long_result_get_segment(h, i, C.byref(st), C.byref(en), C.byref(fo), C.byref(ba)))
+                rc = self._L.k2hip_long_result_get_tokens(h, i, None, None, 0, C.byref(n))
+                if rc != 0 and n.value == 0:
+                    self._chk(rc)
+                tok, ts = np.zeros(max(n.value, 1), np.int64), np.zeros(max(n.value, 1), np.int32)
+                self._chk(self._L.k2hip_long_result_get_tokens(h, i, _l(tok), _i(ts), n.value, C.byref(n)))
+                out.append(dict(start=st.value, end=en.value, forced=fo.value, batch=ba.value, tokens=tok[: n.value].tolist(),
+                                timestamps=ts[: n.value].tolist()))
+            return out
+        finally:
+            self._L.k2hip_long_result_destroy(h)
+
+    def long_timing(self) -> dict:
+        """host milliseconds of the last recognize_long by leg"""
+        _bind_vad(self._L)
+        ms = (C.c_double * 3)()
+        self._chk(self._L.k2hip_debug_long_timing(self._h, ms))
+        return dict(fbank_ms=ms[0], vad_ms=ms[1], batches_ms=ms[2])
 
     # ---- F3
     def pad_sequence(self, feats: Sequence[np.ndarray], tail_frames: int = 19) -> np.ndarray:
@@ -1297,6 +1504,25 @@ class OfflineRecognizer:
     def get_result(self, stream: OfflineStream):  # GetResult :77-83
         self.model._chk(self.model._L.k2hip_offline_recognizer_get_result(self.model.handle, stream._h))
         return stream.tokens, stream.timestamps
+
+    def decode_long(self, samples, sample_rate: Optional[int] = None, config: Optional[VadConfig] = None, max_batch: int = 32,
+                    max_batch_frames: int = 32000, tokens: Optional[TokenTable] = None):
+        """a long recording cut by the voice activity detector and decoded by segment (Model.recognize_long; no reference counterpart).
+        Returns per segment dict(start_s, end_s, forced, batch, tokens, timestamps_s, text): times in seconds of the recording (a token's:
+        its segment's start + its encoder frame), text from `tokens` (a TokenTable) or None."""
+        m = self.model
+        try:
+            shift_s = int(m.meta("frame_shift_ms")) / 1000.0
+        except K2HipError:
+            shift_s = 0.01   # (the container's default)
+        enc_s = shift_s * 4   # encoder frames per fbank frame: the offline models subsample by 4
+        out = []
+        for g in m.recognize_long(samples, sample_rate, config, max_batch, max_batch_frames):
+            t0 = g["start"] * shift_s
+            out.append(dict(start_s=t0, end_s=g["end"] * shift_s, forced=bool(g["forced"]), batch=g["batch"], tokens=g["tokens"],
+                            timestamps_s=[t0 + t * enc_s for t in g["timestamps"]],
+                            text=tokens.decode(g["tokens"]) if tokens is not None else None))
+        return out
 
     def align(self, samples: Sequence[np.ndarray], targets):
         """forced alignment and full-sum score of targets[b] (token ids) on samples[b] (Model.align_samples, or Model.ctc_align_samples

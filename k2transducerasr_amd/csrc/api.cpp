@@ -3218,3 +3218,312 @@ int32_t k2hip_offline_stream_get_timestamps(const k2hip_offline_stream_t* s, int
 }
 
 }  // extern "C"
+
+// ---- voice activity detection and long recordings (include/k2hip.h; vad_ref.h, vad.hip, vad_engine.cpp) ---------------------------
+// One stream of the detector.  `st` is vad_ref.h's carried state, held on the host and riding in every call's upload and download;
+// `segs` the reported segments not popped yet.  Samples: `remainder` holds those behind the last whole frame shift, as an online
+// stream's does; at another rate the resampler's carried input and counts (resample_ref.h's state) sit in front of it.
+struct k2hip_vad_stream {
+    k2hip_model* model = nullptr;   // null: a reference stream of the test hooks (k2hip_debug_vad_ref_stream_create)
+    int num_bins = 0;
+    k2hip_vad_config cfg{};
+    VadState st;
+    std::vector<VadSeg> segs;
+    std::vector<float> remainder;
+    int rate = 0;   // fixed by the stream's first samples until a reset or flush (0: none yet)
+    std::vector<float> rs_tail;
+    int64_t rs_n_in = 0, rs_n_out = 0;
+    void restart() {   // what a flush and a reset share
+        st = VadState();
+        remainder.clear();
+        rate = 0;
+        rs_tail.clear();
+        rs_n_in = rs_n_out = 0;
+    }
+};
+struct k2hip_long_result {
+    std::vector<Engine::LongSegment> segs;
+};
+
+extern "C" {
+
+int32_t k2hip_vad_default_config(const k2hip_model_t* model, k2hip_vad_config* cfg) {
+    return guard([&] {
+        NEED(model); NEED(cfg);
+        const Config& c = model->engine.model().cfg();
+        vad_default_config(c.fbank.sample_rate, c.feat, c.fbank.low_freq, c.fbank.high_freq, cfg);
+    });
+}
+int32_t k2hip_vad_stream_create(k2hip_model_t* model, const k2hip_vad_config* cfg, k2hip_vad_stream_t** out) {
+    return guard([&] {
+        NEED(model); NEED(cfg); NEED(out);
+        *out = nullptr;
+        vad_check_config(*cfg, model->engine.model().cfg().feat);
+        auto s = std::make_unique<k2hip_vad_stream>();
+        s->model = model;
+        s->num_bins = model->engine.model().cfg().feat;
+        s->cfg = *cfg;
+        *out = s.release();
+    });
+}
+int32_t k2hip_vad_stream_destroy(k2hip_vad_stream_t* s) {
+    return guard([&] { delete s; });
+}
+int32_t k2hip_vad_stream_reset(k2hip_vad_stream_t* s) {
+    return guard([&] {
+        NEED(s);
+        s->restart();
+        s->segs.clear();
+    });
+}
+int32_t k2hip_vad_stream_flush(k2hip_vad_stream_t* s) {
+    return guard([&] {
+        NEED(s);
+        vad_ref_flush(s->cfg, s->st, &s->segs);
+        s->restart();
+    });
+}
+int32_t k2hip_vad_accept_features_batch(k2hip_model_t* model, k2hip_vad_stream_t* const* streams, const float* const* feats, const int64_t* n_frames,
+                                        int32_t B) {
+    return guard([&] {
+        NEED(model); NEED(streams); NEED(feats); NEED(n_frames);
+        K2_REQUIRE(B > 0, "vad_accept_features_batch: empty list");
+        std::vector<Engine::VadJob> jobs((size_t)B);
+        for (int b = 0; b < B; b++) {
+            NEED(streams[b]);
+            K2_REQUIRE(streams[b]->model == model, "vad_accept_features_batch: stream %d belongs to another model", b);
+            K2_REQUIRE(n_frames[b] >= 0, "vad_accept_features_batch: stream %d: %lld frames", b, (long long)n_frames[b]);
+            if (n_frames[b] > 0) NEED(feats[b]);
+            K2_REQUIRE(streams[b]->remainder.empty() && !streams[b]->rs_n_in, "vad_accept_features_batch: stream %d holds samples short of a frame "
+                       "(accept_samples): features and samples do not mix between resets", b);
+            jobs[(size_t)b].cfg = &streams[b]->cfg;
+            jobs[(size_t)b].st = &streams[b]->st;
+            jobs[(size_t)b].segs = &streams[b]->segs;
+            jobs[(size_t)b].feats = feats[b];
+            jobs[(size_t)b].n = n_frames[b];
+        }
+        {
+            std::vector<const k2hip_vad_stream*> seen(streams, streams + B);
+            std::sort(seen.begin(), seen.end());
+            K2_REQUIRE(std::adjacent_find(seen.begin(), seen.end()) == seen.end(), "vad_accept_features_batch: the same stream appears twice in the list");
+        }
+        EngineLock lk(model->engine);
+        model->engine.vad_host(jobs.data(), B, false);
+    });
+}
+int32_t k2hip_vad_accept_samples_batch(k2hip_model_t* model, k2hip_vad_stream_t* const* streams, int32_t sample_rate, const float* const* samples,
+                                       const int64_t* n, int32_t B) {
+    return guard([&] {
+        NEED(model); NEED(streams); NEED(samples); NEED(n);
+        K2_REQUIRE(B > 0, "vad_accept_samples_batch: empty list");
+        Engine& e = model->engine;
+        const Config& c = e.model().cfg();
+        const ResamplePlan* plan = model_resample_plan(model, sample_rate);   // (a rate that is refused is refused before any stream moves)
+        for (int b = 0; b < B; b++) {
+            NEED(streams[b]);
+            K2_REQUIRE(streams[b]->model == model, "vad_accept_samples_batch: stream %d belongs to another model", b);
+            K2_REQUIRE(n[b] >= 0, "vad_accept_samples_batch: stream %d: %lld samples", b, (long long)n[b]);
+            if (n[b] > 0) NEED(samples[b]);
+            K2_REQUIRE(streams[b]->rate == 0 || streams[b]->rate == sample_rate, "vad_accept_samples_batch: stream %d takes samples at %d Hz, these are at "
+                       "%d Hz (the model's: %d Hz)", b, streams[b]->rate, sample_rate, c.fbank.sample_rate);
+            K2_REQUIRE(streams[b]->rs_n_in + n[b] < kResampleMaxInput, "vad_accept_samples_batch: more than 2^36 samples in stream %d", b);
+        }
+        {
+            std::vector<const k2hip_vad_stream*> seen(streams, streams + B);
+            std::sort(seen.begin(), seen.end());
+            K2_REQUIRE(std::adjacent_find(seen.begin(), seen.end()) == seen.end(), "vad_accept_samples_batch: the same stream appears twice in the list");
+        }
+        // at another rate: all streams through the resampler in one launch; the outputs are this call's samples at the model's rate
+        std::vector<std::vector<float>> conv((size_t)B);
+        EngineLock lk(e);
+        if (plan) {
+            std::vector<Engine::ResampleJob> rj;
+            for (int b = 0; b < B; b++) {
+                k2hip_vad_stream* s = streams[b];
+                conv[(size_t)b].resize((size_t)(plan->num_out(s->rs_n_in + n[b]) - s->rs_n_out));
+                if (!conv[(size_t)b].empty())
+                    rj.push_back(Engine::ResampleJob{plan, s->rs_tail.data(), (int64_t)s->rs_tail.size(), samples[b], n[b], s->rs_n_in - (int64_t)s->rs_tail.size(),
+                                                     s->rs_n_out, (int64_t)conv[(size_t)b].size(), conv[(size_t)b].data()});
+            }
+            if (!rj.empty()) e.resample_host(rj.data(), (int)rj.size());
+        }
+        std::vector<Engine::VadJob> jobs((size_t)B);
+        for (int b = 0; b < B; b++) {
+            k2hip_vad_stream* s = streams[b];
+            Engine::VadJob& j = jobs[(size_t)b];
+            j.cfg = &s->cfg; j.st = &s->st; j.segs = &s->segs;
+            j.head = s->remainder.data(); j.n_head = (int64_t)s->remainder.size();
+            j.tail = plan ? conv[(size_t)b].data() : samples[b];
+            j.n_tail = plan ? (int64_t)conv[(size_t)b].size() : n[b];
+        }
+        e.vad_host(jobs.data(), B, true);
+        // the call has succeeded: the streams' sample bookkeeping moves
+        for (int b = 0; b < B; b++) {
+            k2hip_vad_stream* s = streams[b];
+            const Engine::VadJob& j = jobs[(size_t)b];
+            if (n[b] > 0) s->rate = sample_rate;
+            if (plan && n[b] > 0) {
+                const int64_t x0 = s->rs_n_in - (int64_t)s->rs_tail.size();
+                s->rs_n_in += n[b];
+                s->rs_n_out += (int64_t)conv[(size_t)b].size();
+                const int64_t keep = std::min(plan->keep_from(s->rs_n_out), s->rs_n_in);
+                s->rs_tail.insert(s->rs_tail.end(), samples[b], samples[b] + n[b]);
+                s->rs_tail.erase(s->rs_tail.begin(), s->rs_tail.begin() + (keep - x0));
+            }
+            const int64_t used = j.n * c.fbank.frame_shift, len = j.n_head + j.n_tail;   // samples consumed by whole frame shifts
+            std::vector<float> rem((size_t)(len - used));
+            for (int64_t k = used; k < len; k++) rem[(size_t)(k - used)] = k < j.n_head ? j.head[k] : j.tail[k - j.n_head];
+            s->remainder.swap(rem);
+        }
+    });
+}
+int32_t k2hip_vad_stream_is_speech(const k2hip_vad_stream_t* s) { return s ? s->st.trig : -1; }
+int64_t k2hip_vad_stream_num_frames(const k2hip_vad_stream_t* s) { return s ? s->st.frames : -1; }
+int32_t k2hip_vad_stream_num_segments(const k2hip_vad_stream_t* s) { return s ? (int32_t)s->segs.size() : -1; }
+int32_t k2hip_vad_stream_get_segments(const k2hip_vad_stream_t* s, int64_t* start, int64_t* end, int32_t* forced, int32_t cap) {
+    return guard([&] {
+        NEED(s);
+        if ((int64_t)s->segs.size() > cap) failf(K2HIP_ERR_CAPACITY, "stream holds %zu segments", s->segs.size());
+        if (s->segs.empty()) return;
+        NEED(start); NEED(end); NEED(forced);
+        for (size_t i = 0; i < s->segs.size(); i++) {
+            start[i] = s->segs[i].start;
+            end[i] = s->segs[i].end;
+            forced[i] = s->segs[i].forced;
+        }
+    });
+}
+int32_t k2hip_vad_stream_pop_segments(k2hip_vad_stream_t* s, int32_t n) {
+    return guard([&] {
+        NEED(s);
+        K2_REQUIRE(n >= 0 && (size_t)n <= s->segs.size(), "vad_stream_pop_segments: %d of %zu segments", n, s->segs.size());
+        s->segs.erase(s->segs.begin(), s->segs.begin() + n);
+    });
+}
+
+int32_t k2hip_offline_recognize_long(k2hip_model_t* model, int32_t sample_rate, const float* samples, int64_t n, const k2hip_vad_config* cfg,
+                                     int32_t max_batch, int64_t max_batch_frames, k2hip_long_result_t** result) {
+    return guard([&] {
+        NEED(model); NEED(result);
+        *result = nullptr;
+        K2_REQUIRE(n >= 0 && n < kResampleMaxInput, "recognize_long: %lld samples", (long long)n);
+        if (n > 0) NEED(samples);
+        K2_REQUIRE(max_batch > 0 && max_batch_frames > 0, "recognize_long: max_batch = %d, max_batch_frames = %lld", max_batch, (long long)max_batch_frames);
+        Engine& e = model->engine;
+        const Config& c = e.model().cfg();
+        k2hip_vad_config use;
+        if (cfg) use = *cfg;
+        else vad_default_config(c.fbank.sample_rate, c.feat, c.fbank.low_freq, c.fbank.high_freq, &use);
+        vad_check_config(use, c.feat);
+        const ResamplePlan* plan = model_resample_plan(model, sample_rate);
+        const int64_t n_own = plan ? plan->num_out(n) : n;
+        if (n_own > Engine::kLongMaxSamples)
+            failf(K2HIP_ERR_UNSUPPORTED, "recognize_long: %lld samples at the model's rate exceed the limit of %lld (split the recording)", (long long)n_own,
+                  (long long)Engine::kLongMaxSamples);
+        auto r = std::make_unique<k2hip_long_result>();
+        EngineLock lk(e);
+        std::vector<float> conv;
+        if (plan && n_own > 0) {
+            conv.resize((size_t)n_own);
+            const Engine::ResampleJob job{plan, samples, n, nullptr, 0, 0, 0, n_own, conv.data()};
+            e.resample_host(&job, 1);
+        }
+        if (n_own > 0) e.recognize_long(plan ? conv.data() : samples, n_own, use, max_batch, max_batch_frames, &r->segs);
+        *result = r.release();
+    });
+}
+int32_t k2hip_long_result_num_segments(const k2hip_long_result_t* r) { return r ? (int32_t)r->segs.size() : -1; }
+int32_t k2hip_long_result_get_segment(const k2hip_long_result_t* r, int32_t i, int64_t* start, int64_t* end, int32_t* forced, int32_t* batch) {
+    return guard([&] {
+        NEED(r);
+        K2_REQUIRE(i >= 0 && (size_t)i < r->segs.size(), "long_result_get_segment: segment %d of %zu", i, r->segs.size());
+        const Engine::LongSegment& g = r->segs[(size_t)i];
+        if (start) *start = g.start;
+        if (end) *end = g.end;
+        if (forced) *forced = g.forced;
+        if (batch) *batch = g.batch;
+    });
+}
+int32_t k2hip_long_result_get_tokens(const k2hip_long_result_t* r, int32_t i, int64_t* tokens, int32_t* timestamps, int32_t cap, int32_t* n) {
+    return guard([&] {
+        NEED(r); NEED(n);
+        K2_REQUIRE(i >= 0 && (size_t)i < r->segs.size(), "long_result_get_tokens: segment %d of %zu", i, r->segs.size());
+        const Engine::LongSegment& g = r->segs[(size_t)i];
+        *n = (int32_t)g.tokens.size();
+        if ((int64_t)g.tokens.size() > cap) failf(K2HIP_ERR_CAPACITY, "segment %d holds %zu tokens, capacity %d", i, g.tokens.size(), cap);
+        if (g.tokens.empty()) return;
+        NEED(tokens); NEED(timestamps);
+        memcpy(tokens, g.tokens.data(), sizeof(int64_t) * g.tokens.size());
+        memcpy(timestamps, g.timestamps.data(), sizeof(int32_t) * g.timestamps.size());
+    });
+}
+int32_t k2hip_long_result_destroy(k2hip_long_result_t* r) {
+    return guard([&] { delete r; });
+}
+
+// test hooks (include/k2hip_debug.h)
+int32_t k2hip_debug_vad_check_config(const k2hip_vad_config* cfg, int32_t num_bins) {
+    return guard([&] {
+        NEED(cfg);
+        vad_check_config(*cfg, num_bins);
+    });
+}
+int32_t k2hip_debug_vad_default_config(int32_t sample_rate, int32_t num_bins, float low_freq, float high_freq, k2hip_vad_config* cfg) {
+    return guard([&] {
+        NEED(cfg);
+        K2_REQUIRE(sample_rate > 0 && num_bins > 0, "vad_default_config: %d Hz, %d bins", sample_rate, num_bins);
+        vad_default_config(sample_rate, num_bins, low_freq, high_freq, cfg);
+    });
+}
+int32_t k2hip_debug_vad_pack(const int64_t* len, int32_t n, int32_t max_batch, int64_t max_batch_frames, int32_t* batch_of) {
+    return guard([&] {
+        K2_REQUIRE(n >= 0, "vad_pack: %d segments", n);
+        if (n > 0) { NEED(len); NEED(batch_of); }
+        std::vector<int32_t> b;
+        vad_pack_batches(len, n, max_batch, max_batch_frames, &b);
+        if (n > 0) memcpy(batch_of, b.data(), sizeof(int32_t) * (size_t)n);
+    });
+}
+int32_t k2hip_debug_vad_ref_stream_create(int32_t num_bins, const k2hip_vad_config* cfg, k2hip_vad_stream_t** out) {
+    return guard([&] {
+        NEED(cfg); NEED(out);
+        *out = nullptr;
+        K2_REQUIRE(num_bins > 0, "vad_ref_stream_create: %d bins", num_bins);
+        vad_check_config(*cfg, num_bins);
+        auto s = std::make_unique<k2hip_vad_stream>();
+        s->num_bins = num_bins;
+        s->cfg = *cfg;
+        *out = s.release();
+    });
+}
+int32_t k2hip_debug_vad_ref_push(k2hip_vad_stream_t* s, const float* feats, int64_t n, float* tap_m, float* tap_n, uint8_t* tap_d) {
+    return guard([&] {
+        NEED(s);
+        K2_REQUIRE(n >= 0, "vad_ref_push: %lld frames", (long long)n);
+        if (n > 0) NEED(feats);
+        vad_ref_push(s->cfg, s->st, feats, n, s->num_bins, &s->segs, tap_m, tap_n, tap_d);
+    });
+}
+int32_t k2hip_debug_vad_taps(k2hip_model_t* model, int32_t b, float* m, float* n, uint8_t* d, int64_t cap, int64_t* n_frames) {
+    return guard([&] {
+        NEED(model); NEED(n_frames);
+        EngineLock lk(model->engine);
+        const Engine::VadTaps& t = model->engine.last_vad_taps();
+        K2_REQUIRE(b >= 0 && (size_t)b + 1 < t.off.size(), "vad_taps: stream %d of the last call's %zu", b, t.off.empty() ? (size_t)0 : t.off.size() - 1);
+        const int64_t o = t.off[(size_t)b], cnt = t.off[(size_t)b + 1] - o;
+        *n_frames = cnt;
+        if (cnt > cap) failf(K2HIP_ERR_CAPACITY, "vad_taps: %lld frames, capacity %lld", (long long)cnt, (long long)cap);
+        if (m && cnt) memcpy(m, t.m.data() + o, sizeof(float) * (size_t)cnt);
+        if (n && cnt) memcpy(n, t.n.data() + o, sizeof(float) * (size_t)cnt);
+        if (d && cnt) memcpy(d, t.d.data() + o, (size_t)cnt);
+    });
+}
+int32_t k2hip_debug_long_timing(k2hip_model_t* model, double* ms3) {
+    return guard([&] {
+        NEED(model); NEED(ms3);
+        EngineLock lk(model->engine);
+        for (int i = 0; i < 3; i++) ms3[i] = model->engine.last_long_ms()[(size_t)i];
+    });
+}
+
+}  // extern "C"

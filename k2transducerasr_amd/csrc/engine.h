@@ -16,6 +16,7 @@
 #include "model.h"
 #include "resample_plan.h"
 #include "search_out.h"
+#include "vad_ref.h"
 
 namespace k2hip {
 
@@ -196,6 +197,46 @@ class Engine {
         int64_t x0 = 0, k0 = 0;
     };
     void set_wave_srcs(const WaveSrc* w) { wave_srcs_ = w; }
+
+    // ---- voice activity detection and long recordings (vad.hip; the definition: vad_ref.h, DESIGN.md "Voice activity detection and
+    // long recordings") ----
+    // One stream of a VAD call: its config (checked by the caller: vad_check_config), its carried state (host; replaced by the call),
+    // and its input -- n feature rows in `feats` (host), or the samples [head ; tail] (host), whose whole frames are taken: the call
+    // sets n to their count.  n == 0 leaves the stream untouched.  The reported segments are appended to *segs.
+    struct VadJob {
+        const k2hip_vad_config* cfg = nullptr;
+        VadState* st = nullptr;
+        const float* feats = nullptr;
+        int64_t n = 0;
+        const float *head = nullptr, *tail = nullptr;
+        int64_t n_head = 0, n_tail = 0;
+        std::vector<VadSeg>* segs = nullptr;
+    };
+    // One upload (descriptors, carried blocks, input), the launches of vad_run (behind one batched fbank launch with from_samples: the
+    // features never leave the device), one download (new blocks, raw segments, taps).  Everything is checked on the host before any
+    // device work; a failed call leaves every state as it was.
+    void vad_host(VadJob* jobs, int B, bool from_samples);
+    // the taps of the last vad_host call: m, n, d of job b's frames at [off[b], off[b + 1])
+    struct VadTaps {
+        std::vector<float> m, n;
+        std::vector<uint8_t> d;
+        std::vector<int64_t> off;
+    };
+    const VadTaps& last_vad_taps() const { return vad_taps_; }
+    // A long recording at the model's rate: fbank over all of it into a resident [T][feat] block, the detector and its flush over the
+    // block, the segments packed into batches (vad_pack_batches), each batch gathered device to device into the pad stage and decoded by
+    // the model's current search, the best hypothesis kept.  At most kLongMaxSamples samples (K2HIP_ERR_UNSUPPORTED beyond).
+    struct LongSegment {
+        int64_t start = 0, end = 0;       // frames [start, end) of the recording
+        int32_t forced = 0, batch = 0;
+        std::vector<int64_t> tokens;
+        std::vector<int32_t> timestamps;  // segment-local encoder frames
+    };
+    static constexpr int64_t kLongMaxSamples = (int64_t)1 << 27;   // 2 h 19 min at 16 kHz: 512 MiB of samples, 256 MiB of features
+    void recognize_long(const float* samples, int64_t n, const k2hip_vad_config& cfg, int max_batch, int64_t max_batch_frames,
+                        std::vector<LongSegment>* out);
+    // legs of the last recognize_long in milliseconds of host time: fbank (with the upload), the detector, the batches
+    const std::array<double, 3>& last_long_ms() const { return long_ms_; }
 
     // ---- pipelined (asynchronous) form of offline_greedy_samples_dev ----
     // submit() enqueues fbank + pad + encoder on the encoder stream and the greedy loop + D2H
@@ -476,6 +517,11 @@ class Engine {
     void offline_samples(const float* const* samples, const int64_t* n_samples, int B, const SearchStage& stage, int64_t* tokens, int32_t* ts,
                          int32_t* n_tokens, int max_tokens, bool pinned_src);
     const WaveSrc* wave_srcs_ = nullptr;
+    // the core of vad_host / recognize_long: jobs whose feature rows are on the device (d_feats[b], rows `feat` floats apart; filled in by
+    // `prepare`, which runs inside the sized body in front of the detector and enqueues whatever produces the rows)
+    void vad_device_call(VadJob* jobs, int B, const std::function<void(const Ctx&, std::vector<const float*>&)>& prepare);
+    VadTaps vad_taps_;
+    std::array<double, 3> long_ms_{};
     // samples of the model's rate that stream b of a from-samples batch gives
     int64_t wave_count(int b, int64_t n_samples) const {
         const WaveSrc* w = wave_srcs_ ? wave_srcs_ + b : nullptr;

@@ -443,6 +443,38 @@ constexpr int kResampleTile = 1024;     // outputs per workgroup trip at most (f
 // same B descriptors in device memory.  dst [n_dst_rows][nmax].
 void resample_gather(const Ctx& ctx, const ResampleRow* rows, const ResampleRow* d_rows, int B, float* dst, int n_dst_rows, long long nmax);
 
+// ---- voice activity detection (vad.hip; the definition and the host reference: vad_ref.h) -------------------------------------------
+constexpr int kVadMaxW = 1024;   // floor_window at most (= vad_ref.h kVadMaxWindow)
+constexpr int kVadTile = 256;    // frames per workgroup of the floor pass
+// words of one stream's carried block: [W - 1 floats of m, right-aligned: the newest last | 4 floats of s | trig, start, te, segments
+// emitted by the call (ints)]
+inline long long vad_state_words(int W) { return (long long)W + 7; }
+// One stream of a vad_run call: n > 0 feature rows (device; `stride` floats apart), row 0 being frame t0 of the stream.
+struct VadRow {
+    const float* feats = nullptr;
+    long long stride = 0;
+    int n = 0, t0 = 0, n_hist = 0;       // n_hist = min(t0, W - 1) values of m are carried
+    int lo = 0, hi = 0, W = 0;
+    float inv_band = 0.f, rise = 0.f, margin = 0.f, abs_floor = 0.f;
+    int min_silence = 0, min_speech = 0, max_speech = 0;
+    int trig = 0, start = 0, te = -1;    // the machine as the call finds it
+    long long work_off = 0;              // the stream's first entry in s / m / n / d
+    long long state_off = 0;             // ... word in st_in / st_out
+    long long seg_off = 0;               // ... segment in segs [.][3] = (a, b, forced); at most seg_cap are written
+    int seg_cap = 0;
+};
+struct VadBuffers {
+    const float* st_in = nullptr;        // device: the carried blocks
+    float* st_out = nullptr;             // device: the new ones, same layout
+    float *s = nullptr, *m = nullptr, *n = nullptr;
+    unsigned char* d = nullptr;
+    int* segs = nullptr;
+    long long n_work = 0, n_state = 0, n_segs = 0;   // entries of s / m / n / d, words of st_in / st_out, segments of segs
+};
+// rows: B descriptors in host memory (checked here before anything is launched: no stream reads or writes outside its extents),
+// d_rows: the same in device memory
+void vad_run(const Ctx& ctx, const VadRow* rows, const VadRow* d_rows, int B, const VadBuffers& buf);
+
 // ---- decoder / joiner / greedy ----------------------------------------------------
 struct DecJoinW {
     const float* emb;      // [V, DD]
