@@ -111,6 +111,19 @@ namespace K2TransducerAsr.Hip
         [DllImport(Lib)] internal static extern int k2hip_ngram_lm_start_state(IntPtr lm);
         [DllImport(Lib)] internal static extern int k2hip_ngram_lm_step(IntPtr lm, int state, long token, out int nextState, out float logProb);
         [DllImport(Lib)] internal static extern int k2hip_set_ngram_lm(IntPtr model, IntPtr lm /* IntPtr.Zero clears */, float scale);
+        // Neural LM rescoring (include/k2hip.h "Neural LM rescoring").  The model keeps its own copy: destroy the LM after k2hip_set_rnn_lm.
+        [DllImport(Lib)] internal static extern int k2hip_rnn_lm_load(string path, out IntPtr lm);
+        [DllImport(Lib)] internal static extern int k2hip_rnn_lm_destroy(IntPtr lm);
+        [DllImport(Lib)] internal static extern int k2hip_rnn_lm_vocab_size(IntPtr lm);
+        [DllImport(Lib)] internal static extern int k2hip_rnn_lm_embedding_dim(IntPtr lm);
+        [DllImport(Lib)] internal static extern int k2hip_rnn_lm_hidden_dim(IntPtr lm);
+        [DllImport(Lib)] internal static extern int k2hip_rnn_lm_num_layers(IntPtr lm);
+        [DllImport(Lib)] internal static extern int k2hip_rnn_lm_sos_id(IntPtr lm);
+        [DllImport(Lib)] internal static extern int k2hip_rnn_lm_eos_id(IntPtr lm);
+        [DllImport(Lib)] internal static extern int k2hip_rnn_lm_score_host(IntPtr lm, long[] tokens, long[] offsets, int hn, int withEos, float[] tokenLogProbs /* may be null */, float[] totals);
+        [DllImport(Lib)] internal static extern int k2hip_set_rnn_lm(IntPtr model, IntPtr lm /* IntPtr.Zero clears */, float scale);
+        [DllImport(Lib)] internal static extern int k2hip_rnn_lm_score(IntPtr model, long[] tokens, long[] offsets, int hn, int withEos, float[] tokenLogProbs /* may be null */, float[] totals);
+        [DllImport(Lib)] internal static extern int k2hip_offline_stream_get_alternative_lm_score(IntPtr stream, int i, out float lmTotal);
         // streaming: the graph belongs to the stream (IntPtr.Zero detaches; only before the stream's first chunk or after a reset)
         [DllImport(Lib)] internal static extern int k2hip_online_stream_set_hotwords(IntPtr stream, IntPtr hotwords);
         [DllImport(Lib)] internal static extern int k2hip_beam_stream_set_hotwords(IntPtr stream, IntPtr hotwords);

@@ -1051,6 +1051,61 @@ int32_t k2hip_long_result_get_segment(const k2hip_long_result_t* r, int32_t i, i
 int32_t k2hip_long_result_get_tokens(const k2hip_long_result_t* r, int32_t i, int64_t* tokens, int32_t* timestamps, int32_t cap, int32_t* n);
 int32_t k2hip_long_result_destroy(k2hip_long_result_t* r);
 
+/* ---- Neural LM rescoring: LSTM language model scores for N-best lists ------------------------------------------------------------
+ * (no reference counterpart; the toolkit the searches follow rescores with an icefall RnnLmModel: embedding -> multi-layer LSTM ->
+ * linear -> log_softmax.  The normative text is csrc/rnn_lm_ref.h, DESIGN.md "Neural LM rescoring".)
+ * THE LM is a .k2w container: metadata model_type=rnn_lm, vocab_size (V), embedding_dim (E), hidden_dim (H), num_layers (L, 1..8),
+ * sos_id, eos_id (icefall: both 1), tie_weights (0/1); tensors under their icefall / torch state-dict names in torch layout:
+ * input_embedding.weight [V,E]; rnn.weight_ih_l{k} [4H,in] (in = E for k = 0, else H), rnn.weight_hh_l{k} [4H,H], rnn.bias_ih_l{k} and
+ * rnn.bias_hh_l{k} [4H]; output_linear.weight [V,H], output_linear.bias [V].  With tie_weights=1 output_linear.weight may be absent:
+ * it is then the embedding, which needs E == H.  Gate order is torch's (i, f, g, o); there is no projection.
+ * Load refuses with K2HIP_ERR_UNSUPPORTED when H % 32 != 0 or E % 4 != 0, and with K2HIP_ERR_INVALID, naming the tensor, for a missing
+ * tensor, a tensor of the wrong shape, a non-f32 tensor, a non-finite value, and sos_id / eos_id outside [0,V).
+ * SCORE of one hypothesis y_1 .. y_n (ids in [0,V), n >= 0): the inputs are x = [sos, y_1 .. y_n]; the targets are [y_1 .. y_n, eos]
+ * with_eos (n + 1 positions), otherwise the first n of those (n positions; n = 0: the total is 0 and no device work is issued).  The
+ * layers start from h = c = 0.  At position t, layer k: gates = (x_t . W_ih^T + (b_ih + b_hh)) + h_{t-1} . W_hh^T (the two biases
+ * summed once in float32 at load); c = sigmoid(f) c + sigmoid(i) tanh(g); h = sigmoid(o) tanh(c);
+ * lp_t = log_softmax(h^{L-1}_t . W_out^T + b_out)[target_t]; total = the float32 sum of lp_t in position order.  All arithmetic is
+ * float32.  The device is held to a float64 twin within a measured bound, not bit for bit: its expf / tanhf and the GEMM plan's
+ * summation order differ from the host's, so a hypothesis' last bits may depend on what else is in the call (the caveat the offline
+ * encoder carries).
+ * A k2hip_rnn_lm_t belongs to no model and needs no GPU. */
+typedef struct k2hip_rnn_lm k2hip_rnn_lm_t;
+#define K2HIP_RNN_LM_MAX_ROWS (1 << 22) /* positions of all hypotheses of one scoring call */
+int32_t k2hip_rnn_lm_load(const char* path, k2hip_rnn_lm_t** out);
+int32_t k2hip_rnn_lm_destroy(k2hip_rnn_lm_t* lm);
+int32_t k2hip_rnn_lm_vocab_size(const k2hip_rnn_lm_t* lm);      /* -1 for NULL, as the next five */
+int32_t k2hip_rnn_lm_embedding_dim(const k2hip_rnn_lm_t* lm);
+int32_t k2hip_rnn_lm_hidden_dim(const k2hip_rnn_lm_t* lm);
+int32_t k2hip_rnn_lm_num_layers(const k2hip_rnn_lm_t* lm);
+int32_t k2hip_rnn_lm_sos_id(const k2hip_rnn_lm_t* lm);
+int32_t k2hip_rnn_lm_eos_id(const k2hip_rnn_lm_t* lm);
+/* the host reference (csrc/rnn_lm_ref.h), no GPU: Hn hypotheses back to back in tokens, hypothesis i at [offsets[i], offsets[i + 1]);
+ * token_log_probs (may be NULL) packed per hypothesis with its positions back to back; totals [Hn].  K2HIP_ERR_INVALID, naming the
+ * hypothesis, for an id outside [0,V) and for decreasing offsets. */
+int32_t k2hip_rnn_lm_score_host(const k2hip_rnn_lm_t* lm, const int64_t* tokens, const int64_t* offsets, int32_t Hn, int32_t with_eos,
+                                float* token_log_probs, float* totals);
+/* lm = NULL clears; scale finite and >= 0.  Checks vocab_size against the model and uploads the weights in the layouts the kernels
+ * want; the model keeps its own copy, so lm may be destroyed afterwards.  Not while submitted batches are in flight.
+ * RESCORING: while an LM with scale > 0 is set and k2hip_set_nbest(n > 1) is on, k2hip_offline_recognizer_get_results rescores each
+ * stream's list -- under modified_beam_search on a transducer model and under ctc_prefix_beam_search on a CTC model.  All alternatives
+ * of all streams go through ONE scoring call with_eos = 1; the list is then stably re-ordered by the method's own ordering quantity
+ * with the score replaced by score + scale * lm_total (the float32 product rounded, then the sum): transducer
+ * (score_i + scale lm_i) / (n_i + 2), CTC prefix score_i + scale lm_i.  Entry 0 becomes the stream's result (tokens, timestamps, token
+ * log-probs); an alternative's reported score stays the search's own, and k2hip_offline_stream_get_alternative_lm_score gives its
+ * lm_total (0 when nothing was rescored).  With n = 1 there is nothing to rescore and the LM changes nothing.
+ * Everything else ignores the LM: greedy search, the plain CTC search, the single-stream k2hip_offline_recognizer_get_result, the
+ * pipelined submit / wait, every streaming entry and k2hip_offline_recognize_long.  No LM, a cleared LM and scale = 0: bit for bit the
+ * plain results from the plain launches.  Hotwords and the n-gram LM keep working as they do; the neural term is added on top of
+ * whatever score the search reports. */
+int32_t k2hip_set_rnn_lm(k2hip_model_t* model, const k2hip_rnn_lm_t* lm, float scale);
+/* the device operator on the attached LM (any scale): the arguments and results of k2hip_rnn_lm_score_host, results in the caller's
+ * order.  Checked on the host before any device work, K2HIP_ERR_INVALID naming the hypothesis: an id outside [0,V), decreasing
+ * offsets, no LM attached, more than K2HIP_RNN_LM_MAX_ROWS positions. */
+int32_t k2hip_rnn_lm_score(k2hip_model_t* model, const int64_t* tokens, const int64_t* offsets, int32_t Hn, int32_t with_eos,
+                           float* token_log_probs, float* totals);
+int32_t k2hip_offline_stream_get_alternative_lm_score(const k2hip_offline_stream_t* s, int32_t i, float* lm_total);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

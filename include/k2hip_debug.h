@@ -253,6 +253,26 @@ int32_t k2hip_debug_vad_taps(k2hip_model_t* model, int32_t b, float* m, float* n
 /* host milliseconds of the last k2hip_offline_recognize_long by leg: fbank (with the upload), the detector, the batches */
 int32_t k2hip_debug_long_timing(k2hip_model_t* model, double* ms3);
 
+/* ---- neural LM rescoring (k2hip.h "Neural LM rescoring"; tests/test_rnn_lm.py, test_rnn_lm_gpu.py, tools/rnn_lm_bench.py) ---------- */
+/* host only, no model and no GPU: the row plan of a scoring call (csrc/rnn_lm_plan.h) over Hn hypotheses, hidden width H and a cap of
+ * gx_cap_floats floats per time block (<= 0: the default).  order [Hn], active [cap_T], base [cap_T + 1], block [cap_T + 1]; *T and
+ * *n_blocks are set; K2HIP_ERR_CAPACITY when cap_T is short of T. */
+int32_t k2hip_debug_rnn_lm_plan(const int64_t* offsets, int32_t Hn, int32_t with_eos, int32_t H, int64_t gx_cap_floats, int32_t* order,
+                                int32_t* active, int64_t* base, int32_t* block, int32_t cap_T, int32_t* T, int32_t* n_blocks);
+/* scoring calls that reached the device since the model was created; the time blocks of the last one */
+int32_t k2hip_debug_rnn_lm_stats(k2hip_model_t* model, int64_t* device_calls, int32_t* last_blocks);
+/* on != 0: every scoring call brackets its legs with events and waits for them; ms4 (may be NULL) gets the last call's milliseconds by
+ * leg: embed, GX, steps, score */
+int32_t k2hip_debug_rnn_lm_timing(k2hip_model_t* model, int32_t on, double* ms4);
+/* milliseconds per recurrent step of `rows` rows at hidden width H on pseudo-random operands, `iters` launches between two events: the
+ * fused step kernel, and the step composed from the GEMM launcher and the cell kernel as the LSTM encoder's lstm_layer does */
+int32_t k2hip_debug_rnn_lm_step_bench(k2hip_model_t* model, int32_t rows, int32_t H, int32_t iters, float* fused_ms, float* composed_ms);
+/* k2hip_debug_op_run ops, each ONE launch on the caller's buffers:
+ *   "rnn_lm_embed"  ints R, E; bufs emb [V][E], ids [R] (int32, in [0,V): not checked), x0 [R][E] (out)
+ *   "rnn_lm_step"   ints a, H, first (1: h = 0, h_prev is not read); bufs h_prev [a][H], whh_kn [H][4H], gx [rows][4H], c [rows][H]
+ *                   (in / out), h_out [rows][H] (out): rows >= a of c and h_out stay as they were
+ *   "rnn_lm_score"  ints R, H, V, Vp; bufs y [R][H], out_kn [H][Vp], out_b [V], target [R] (int32), lp [R] (out) */
+
 /* ---- GEMM tuning ------------------------------------------------------------------------------- */
 /* time `iters` launches of a shape / configuration on pseudo-random operands (tools/gemm_lab.py, gemm_tune.py) */
 int32_t k2hip_debug_gemm(k2hip_model_t* model, int32_t M, int32_t N, int32_t K, int32_t act, int32_t with_res, int32_t cfg,

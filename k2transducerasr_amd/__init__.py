@@ -25,6 +25,7 @@ from .binding import (  # noqa: F401
     OnlineProj,
     OnlineRecognizer,
     OnlineStream,
+    RnnLm,
     StreamBatch,
     TokenTable,
     VadConfig,
@@ -50,6 +51,7 @@ __all__ = [
     "OnlineProj",
     "OnlineRecognizer",
     "OnlineStream",
+    "RnnLm",
     "StreamBatch",
     "TokenTable",
     "VadConfig",

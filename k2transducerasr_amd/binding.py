@@ -278,6 +278,106 @@ class NgramLm:
             pass
 
 
+def _bind_rnn_lm(L):
+    if getattr(L, "_rnn_lm_bound", False):
+        return
+    vp = C.c_void_p
+    L.k2hip_rnn_lm_load.argtypes = [C.c_char_p, C.POINTER(vp)]
+    L.k2hip_rnn_lm_destroy.argtypes = [vp]
+    for f in ("vocab_size", "embedding_dim", "hidden_dim", "num_layers", "sos_id", "eos_id"):
+        getattr(L, "k2hip_rnn_lm_" + f).argtypes = [vp]
+    L.k2hip_rnn_lm_score_host.argtypes = [vp, lp, lp, C.c_int32, C.c_int32, fp, fp]
+    L.k2hip_set_rnn_lm.argtypes = [vp, vp, C.c_float]
+    L.k2hip_rnn_lm_score.argtypes = [vp, lp, lp, C.c_int32, C.c_int32, fp, fp]
+    L.k2hip_offline_stream_get_alternative_lm_score.argtypes = [vp, C.c_int32, fp]
+    L.k2hip_debug_rnn_lm_plan.argtypes = [lp, C.c_int32, C.c_int32, C.c_int32, C.c_int64, ip, ip, lp, ip, C.c_int32, ip, ip]
+    L.k2hip_debug_rnn_lm_stats.argtypes = [vp, lp, ip]
+    L.k2hip_debug_rnn_lm_timing.argtypes = [vp, C.c_int32, C.POINTER(C.c_double)]
+    L.k2hip_debug_rnn_lm_step_bench.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, fp, fp]
+    L._rnn_lm_bound = True
+
+
+def _pack_hyps(hyps):
+    """token-id lists -> (tokens int64, offsets int64 [Hn + 1])"""
+    hyps = [np.ascontiguousarray(h, dtype=np.int64).reshape(-1) for h in hyps]
+    off = np.zeros(len(hyps) + 1, np.int64)
+    if hyps:
+        off[1:] = np.cumsum([h.size for h in hyps])
+    tok = np.concatenate(hyps + [np.zeros(0, np.int64)]) if hyps else np.zeros(0, np.int64)
+    return np.ascontiguousarray(tok if tok.size else np.zeros(1, np.int64)), off
+
+
+def _rnn_lm_scores(call, handle, hyps, with_eos):
+    """(totals [Hn], [token log-probs of hypothesis i]) through k2hip_rnn_lm_score_host / k2hip_rnn_lm_score"""
+    tok, off = _pack_hyps(hyps)
+    Hn = len(off) - 1
+    P = np.diff(off) + (1 if with_eos else 0)
+    tlp, tot = np.zeros(max(int(P.sum()), 1), np.float32), np.zeros(max(Hn, 1), np.float32)
+    rc = call(handle, _l(tok), _l(off), Hn, int(bool(with_eos)), _f(tlp), _f(tot))
+    ends = np.cumsum(P)
+    return rc, tot[:Hn].copy(), [tlp[e - n: e].copy() for e, n in zip(ends, P)]
+
+
+def rnn_lm_plan(lengths, with_eos: bool = True, hidden_dim: int = 32, gx_cap_floats: int = 0) -> dict:
+    """the host plan of a scoring call over hypotheses of these lengths (k2hip_debug_rnn_lm_plan; no GPU): dict(order, active, base,
+    block): csrc/rnn_lm_plan.h"""
+    L = load_library()
+    _bind_rnn_lm(L)
+    off = np.zeros(len(lengths) + 1, np.int64)
+    off[1:] = np.cumsum(np.asarray(lengths, np.int64))
+    Hn = len(lengths)
+    cap = int(max(list(lengths) + [0])) + 1
+    order, active = np.zeros(max(Hn, 1), np.int32), np.zeros(cap, np.int32)
+    base, block = np.zeros(cap + 1, np.int64), np.zeros(cap + 1, np.int32)
+    T, nb = C.c_int32(), C.c_int32()
+    rc = L.k2hip_debug_rnn_lm_plan(_l(off), Hn, int(bool(with_eos)), int(hidden_dim), int(gx_cap_floats), _i(order), _i(active), _l(base), _i(block),
+                                   cap, C.byref(T), C.byref(nb))
+    if rc != 0:
+        raise K2HipError(rc, L.k2hip_last_error().decode())
+    return dict(order=order[:Hn].tolist(), active=active[: T.value].tolist(), base=base[: T.value + 1].tolist(), block=block[: nb.value + 1].tolist())
+
+
+class RnnLm:
+    """A neural LM for rescoring N-best lists (k2hip_rnn_lm_t; include/k2hip.h "Neural LM rescoring"): icefall's RnnLmModel (embedding,
+    multi-layer LSTM, linear, log_softmax) in a .k2w container (synth.write_synthetic_rnn_lm, rnn_lm_import.py).  Host only: loaded,
+    checked and scored (score_host: the float32 reference) without a GPU."""
+
+    def __init__(self, path: str):
+        self._h = None
+        self._L = L = load_library()
+        _bind_rnn_lm(L)
+        h = C.c_void_p()
+        rc = L.k2hip_rnn_lm_load(path.encode(), C.byref(h))
+        if rc != 0:
+            raise K2HipError(rc, L.k2hip_last_error().decode())
+        self._h = h
+
+    vocab_size = property(lambda self: self._L.k2hip_rnn_lm_vocab_size(self._h))
+    embedding_dim = property(lambda self: self._L.k2hip_rnn_lm_embedding_dim(self._h))
+    hidden_dim = property(lambda self: self._L.k2hip_rnn_lm_hidden_dim(self._h))
+    num_layers = property(lambda self: self._L.k2hip_rnn_lm_num_layers(self._h))
+    sos_id = property(lambda self: self._L.k2hip_rnn_lm_sos_id(self._h))
+    eos_id = property(lambda self: self._L.k2hip_rnn_lm_eos_id(self._h))
+
+    def score_host(self, hyps, with_eos: bool = True):
+        """(totals [Hn] float32, [token log-probs of hypothesis i]) of token-id lists by the host reference"""
+        rc, tot, tlp = _rnn_lm_scores(self._L.k2hip_rnn_lm_score_host, self._h, hyps, with_eos)
+        if rc != 0:
+            raise K2HipError(rc, self._L.k2hip_last_error().decode())
+        return tot, tlp
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.k2hip_rnn_lm_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Hotwords:
     """The hotword graph of the modified beam search, set per model for the offline search or per stream for the streaming one
     (k2hip_hotwords_t; include/k2hip.h "hotword biasing"): a trie of token-id phrases with Aho-Corasick failure links.  Host only: built and walked without a GPU.  `phrases`: sequences of token
@@ -882,6 +982,42 @@ class Model:
         self._chk(self._L.k2hip_debug_long_timing(self._h, ms))
         return dict(fbank_ms=ms[0], vad_ms=ms[1], batches_ms=ms[2])
 
+    # ---- neural LM rescoring (include/k2hip.h "Neural LM rescoring")
+    def set_rnn_lm(self, lm: Optional["RnnLm"] = None, scale: float = 0.0):
+        """k2hip_set_rnn_lm: attach the neural LM (None clears).  With scale > 0 and set_nbest(n > 1), get_results rescores every
+        stream's N-best list and re-orders it; with n = 1 there is nothing to rescore and the LM changes nothing."""
+        _bind_rnn_lm(self._L)
+        self._chk(self._L.k2hip_set_rnn_lm(self._h, lm._h if lm is not None else None, float(scale)))
+
+    def rnn_lm_score(self, hyps, with_eos: bool = True):
+        """(totals [Hn] float32, [token log-probs of hypothesis i]) of token-id lists by the attached LM, on the device, in the
+        caller's order (k2hip_rnn_lm_score)"""
+        _bind_rnn_lm(self._L)
+        rc, tot, tlp = _rnn_lm_scores(self._L.k2hip_rnn_lm_score, self._h, hyps, with_eos)
+        self._chk(rc)
+        return tot, tlp
+
+    def rnn_lm_stats(self) -> dict:
+        """scoring calls that reached the device, and the time blocks of the last one (the debug header's view)"""
+        _bind_rnn_lm(self._L)
+        n, b = C.c_int64(), C.c_int32()
+        self._chk(self._L.k2hip_debug_rnn_lm_stats(self._h, C.byref(n), C.byref(b)))
+        return dict(device_calls=n.value, last_blocks=b.value)
+
+    def rnn_lm_timing(self, on: bool = True) -> dict:
+        """switch the leg timing of the scoring calls; returns the last call's milliseconds by leg"""
+        _bind_rnn_lm(self._L)
+        ms = (C.c_double * 4)()
+        self._chk(self._L.k2hip_debug_rnn_lm_timing(self._h, int(on), ms))
+        return dict(embed_ms=ms[0], gx_ms=ms[1], steps_ms=ms[2], score_ms=ms[3])
+
+    def rnn_lm_step_bench(self, rows: int, hidden_dim: int, iters: int = 200) -> dict:
+        """milliseconds per recurrent step: the fused kernel, and the step composed from the GEMM launcher and the cell kernel"""
+        _bind_rnn_lm(self._L)
+        a, b = C.c_float(), C.c_float()
+        self._chk(self._L.k2hip_debug_rnn_lm_step_bench(self._h, int(rows), int(hidden_dim), int(iters), C.byref(a), C.byref(b)))
+        return dict(fused_ms=a.value, composed_ms=b.value)
+
     # ---- F3
     def pad_sequence(self, feats: Sequence[np.ndarray], tail_frames: int = 19) -> np.ndarray:
         fs = [_f32(f).reshape(-1) for f in feats]
@@ -1462,7 +1598,13 @@ class OfflineStream:
 
     def alternatives(self):
         """the N-best list of the last get_results made with Model.set_nbest(n > 1) (k2hip_offline_stream_*_alternative*)"""
-        return _alternatives(self._m, self._L, "k2hip_offline_stream", self._h)
+        alts = _alternatives(self._m, self._L, "k2hip_offline_stream", self._h)
+        _bind_rnn_lm(self._L)
+        for i, a in enumerate(alts):   # the neural LM's total of the alternative (0.0 when nothing was rescored)
+            v = C.c_float(0)
+            self._m._chk(self._L.k2hip_offline_stream_get_alternative_lm_score(self._h, i, C.byref(v)))
+            a["lm_score"] = float(v.value)
+        return alts
 
     def token_log_probs(self) -> np.ndarray:
         return _token_log_probs(self._m, self._L, "k2hip_offline_stream", self._h)
@@ -1474,11 +1616,13 @@ class OfflineRecognizer:
     .alternatives()).  hotwords: a Hotwords graph, or a list of token-id phrases scored
     hotwords_score per matched token (sherpa's hotwords_file / hotwords_score); it biases modified_beam_search only.  ngram_lm: an
     NgramLm fused with weight ngram_lm_scale (sherpa's lm / lm_scale), modified_beam_search only.  ctc_prefix_biasing=True: a CTC model's
-    ctc_prefix_beam_search uses both as well (Model.set_ctc_prefix_biasing); without it the recognizer behaves as before."""
+    ctc_prefix_beam_search uses both as well (Model.set_ctc_prefix_biasing); without it the recognizer behaves as before.  rnn_lm: an
+    RnnLm that rescores the N-best lists of get_results with weight rnn_lm_scale (sherpa's RNN LM rescoring); needs nbest > 1, the
+    alternatives then carry lm_score."""
 
     def __init__(self, weights_path: str, device: int = 0, decoding_method: str = "greedy_search", beam: int = 4, hotwords=None,
                  hotwords_score: float = 1.5, nbest: int = 1, ngram_lm: Optional["NgramLm"] = None, ngram_lm_scale: float = 0.3,
-                 ctc_prefix_biasing: bool = False):
+                 ctc_prefix_biasing: bool = False, rnn_lm: Optional["RnnLm"] = None, rnn_lm_scale: float = 0.5):
         self.model = Model(weights_path, device)
         self.model.set_decoding_method(decoding_method, beam)
         if nbest != 1:   # (streams then carry .alternatives() / .token_log_probs() after get_results)
@@ -1491,6 +1635,8 @@ class OfflineRecognizer:
             self.model.set_ngram_lm(ngram_lm, ngram_lm_scale)
         if ctc_prefix_biasing:
             self.model.set_ctc_prefix_biasing(True)
+        if rnn_lm is not None:
+            self.model.set_rnn_lm(rnn_lm, rnn_lm_scale)
 
     def create_offline_stream(self) -> OfflineStream:  # CreateOfflineStream :71-75
         return OfflineStream(self.model)

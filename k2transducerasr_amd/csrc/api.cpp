@@ -121,6 +121,11 @@ struct k2hip_model {
     uint64_t lm_serial = 0;
     int lm_start = 0;
     int lm_states = 0;   // its number of states (0 = none): what a carried LM state is checked against before a launch
+    // the neural LM of k2hip_set_rnn_lm: the model's own host copy (shared with the handle it came from: it is immutable), its weights
+    // on the device in one allocation, and the scale of the rescoring (0 = the N-best lists are left alone)
+    std::shared_ptr<const RnnLm> rnn_lm;
+    void* rnn_dev = nullptr;
+    float rnn_scale = 0.f;
     // k2hip_set_nbest: 1 = off (the engine keeps nothing beyond the best hypothesis), n > 1 = alternatives and token log-probs are kept
     std::atomic<int> nbest{1};
     // the graphs attached to this model's streams (HwResident), by serial number; hw_uploads counts the uploads (k2hip_debug.h)
@@ -172,6 +177,13 @@ struct k2hip_model {
             try {
                 engine.synchronize();
                 engine.dev_free(lm_dev);
+            } catch (...) {
+            }
+        }
+        if (rnn_dev) {
+            try {
+                engine.synchronize();
+                engine.dev_free(rnn_dev);
             } catch (...) {
             }
         }
@@ -1389,6 +1401,52 @@ static int32_t yp_get(const std::vector<float>& yp, float* out, int32_t cap) {
     return rc < 0 ? rc : count;
 }
 // entry (b, i) of the engine's last N-best as a BeamAlt
+// Neural LM rescoring of the streams' N-best lists (k2hip.h "Neural LM rescoring"): all alternatives of all streams through ONE scoring
+// call with_eos, each list stably re-ordered by the method's own ordering quantity over score + scale * lm_total, entry 0 written
+// into the call's result rows.  Under the engine's lock.
+static void rnn_lm_rescore(k2hip_model* model, k2hip_offline_stream_t* const* streams, int B, int max_tokens, int64_t* tok, int32_t* ts, int32_t* n) {
+    Engine& e = model->engine;
+    const bool ctc = e.model().cfg().ctc;
+    std::vector<int64_t> ids, off(1, 0);
+    for (int b = 0; b < B; b++)
+        for (const BeamAlt& a : streams[b]->alts) {
+            ids.insert(ids.end(), a.tokens.begin(), a.tokens.end());
+            off.push_back((int64_t)ids.size());
+        }
+    const int Hn = (int)off.size() - 1;
+    if (Hn == 0) return;
+    std::vector<float> totals((size_t)Hn);
+    e.rnn_lm_score_host(ids.data(), off.data(), Hn, true, nullptr, totals.data());
+    const float scale = model->rnn_scale;
+    int at = 0;
+    for (int b = 0; b < B; b++) {
+        std::vector<BeamAlt>& alts = streams[b]->alts;
+        const size_t N = alts.size();
+        std::vector<float> key(N);
+        for (size_t i = 0; i < N; i++) {
+            alts[i].lm_score = totals[(size_t)at++];
+            volatile float term = scale * alts[i].lm_score;   // (the product rounded to float32, then the sum: no contraction)
+            volatile float sum = alts[i].score + term;
+            key[i] = ctc ? sum : sum / (float)(alts[i].tokens.size() + 2);
+        }
+        std::vector<size_t> ord(N);
+        for (size_t i = 0; i < N; i++) ord[i] = i;
+        std::stable_sort(ord.begin(), ord.end(), [&](size_t x, size_t y) { return key[x] > key[y]; });
+        std::vector<BeamAlt> sorted;
+        sorted.reserve(N);
+        for (size_t i = 0; i < N; i++) sorted.push_back(std::move(alts[ord[i]]));
+        alts.swap(sorted);
+        if (alts.empty()) continue;
+        const BeamAlt& best = alts[0];
+        K2_REQUIRE((int64_t)best.tokens.size() <= max_tokens, "internal: a rescored alternative of stream %d holds %zu tokens, the result row %d", b,
+                   best.tokens.size(), max_tokens);
+        n[b] = (int32_t)best.tokens.size();
+        for (size_t k = 0; k < best.tokens.size(); k++) {
+            tok[(size_t)b * max_tokens + k] = best.tokens[k];
+            ts[(size_t)b * max_tokens + k] = best.timestamps[k];
+        }
+    }
+}
 static BeamAlt alt_of(const Engine::NbestHost& h, int b, int i) {
     BeamAlt a;
     const size_t e = (size_t)b * h.N + i, o = e * h.max_tokens, len = (size_t)h.n_tokens[e];
@@ -3113,6 +3171,13 @@ int32_t k2hip_offline_recognizer_get_results(k2hip_model_t* model, k2hip_offline
                     streams[b]->alts.clear();
                     for (int i = 0; i < h.n_hyps[(size_t)b]; i++) streams[b]->alts.push_back(alt_of(h, b, i));
                 }
+            if (e.nbest() > 1 && model->rnn_lm && model->rnn_scale > 0.f && (c.ctc ? e.ctc_prefix() > 0 : e.beam() > 0))
+                try {
+                    rnn_lm_rescore(model, streams, B, max_tokens, tok.data(), ts.data(), n.data());
+                } catch (...) {   // (a failed call leaves the start state)
+                    for (int b = 0; b < B; b++) streams[b]->alts.assign(1, BeamAlt{});
+                    throw;
+                }
         }
         auto remove_samples = [&](k2hip_offline_stream* s) {   // RemoveSamples (:294 / :418, OfflineStream.cs:58-68)
             if (from_samples) {
@@ -3523,6 +3588,139 @@ int32_t k2hip_debug_long_timing(k2hip_model_t* model, double* ms3) {
         NEED(model); NEED(ms3);
         EngineLock lk(model->engine);
         for (int i = 0; i < 3; i++) ms3[i] = model->engine.last_long_ms()[(size_t)i];
+    });
+}
+
+}  // extern "C"
+
+// ---- neural LM rescoring (include/k2hip.h; rnn_lm_ref.h, rnn_lm_plan.h, rnn_lm.hip, rnn_lm_engine.cpp) ------------------------------
+// The handle shares the immutable LM with every model it was set on: destroying it never pulls the weights from under a model.
+struct k2hip_rnn_lm {
+    std::shared_ptr<const RnnLm> lm;
+};
+
+extern "C" {
+
+int32_t k2hip_rnn_lm_load(const char* path, k2hip_rnn_lm_t** out) {
+    return guard([&] {
+        NEED(path); NEED(out);
+        *out = nullptr;
+        std::shared_ptr<const RnnLm> lm(rnn_lm_load(path));
+        *out = new k2hip_rnn_lm{std::move(lm)};
+    });
+}
+int32_t k2hip_rnn_lm_destroy(k2hip_rnn_lm_t* lm) {
+    return guard([&] { delete lm; });
+}
+int32_t k2hip_rnn_lm_vocab_size(const k2hip_rnn_lm_t* lm) { return lm ? lm->lm->V : -1; }
+int32_t k2hip_rnn_lm_embedding_dim(const k2hip_rnn_lm_t* lm) { return lm ? lm->lm->E : -1; }
+int32_t k2hip_rnn_lm_hidden_dim(const k2hip_rnn_lm_t* lm) { return lm ? lm->lm->H : -1; }
+int32_t k2hip_rnn_lm_num_layers(const k2hip_rnn_lm_t* lm) { return lm ? lm->lm->L : -1; }
+int32_t k2hip_rnn_lm_sos_id(const k2hip_rnn_lm_t* lm) { return lm ? lm->lm->sos : -1; }
+int32_t k2hip_rnn_lm_eos_id(const k2hip_rnn_lm_t* lm) { return lm ? lm->lm->eos : -1; }
+int32_t k2hip_rnn_lm_score_host(const k2hip_rnn_lm_t* lm, const int64_t* tokens, const int64_t* offsets, int32_t Hn, int32_t with_eos,
+                                float* token_log_probs, float* totals) {
+    return guard([&] {
+        NEED(lm);
+        K2_REQUIRE(Hn >= 0, "rnn_lm_score_host: %d hypotheses", Hn);
+        if (Hn == 0) return;
+        NEED(offsets); NEED(totals);
+        rnn_lm_ref_score_all(*lm->lm, tokens, offsets, Hn, with_eos != 0, token_log_probs, totals);
+    });
+}
+int32_t k2hip_set_rnn_lm(k2hip_model_t* model, const k2hip_rnn_lm_t* lm, float scale) {
+    return guard([&] {
+        NEED(model);
+        Engine& e = model->engine;
+        if (lm) {
+            const int V = e.model().cfg().V;
+            K2_REQUIRE(std::isfinite(scale) && scale >= 0.f, "set_rnn_lm: scale %g must be finite and >= 0", (double)scale);
+            K2_REQUIRE(lm->lm->V == V, "set_rnn_lm: the LM was built for vocab_size %d, the model has %d", lm->lm->V, V);
+        }
+        EngineLock lk(e);
+        K2_REQUIRE(e.batches_in_flight() == 0, "set_rnn_lm: %d submitted batches are in flight; wait for them first", e.batches_in_flight());
+        void* dev = nullptr;
+        RnnLmDev tables;
+        if (lm) dev = e.rnn_lm_upload(*lm->lm, &tables);   // (a failed upload leaves the setting as it was)
+        void* old = model->rnn_dev;
+        model->rnn_dev = dev;
+        model->rnn_lm = lm ? lm->lm : nullptr;
+        model->rnn_scale = lm ? scale : 0.f;
+        e.set_rnn_lm(model->rnn_lm.get(), tables);
+        if (old) {
+            e.synchronize();
+            e.dev_free(old);
+        }
+    });
+}
+int32_t k2hip_rnn_lm_score(k2hip_model_t* model, const int64_t* tokens, const int64_t* offsets, int32_t Hn, int32_t with_eos,
+                           float* token_log_probs, float* totals) {
+    return guard([&] {
+        NEED(model);
+        K2_REQUIRE(Hn >= 0, "rnn_lm_score: %d hypotheses", Hn);
+        EngineLock lk(model->engine);
+        K2_REQUIRE(model->engine.has_rnn_lm(), "rnn_lm_score: no LM is attached to the model (k2hip_set_rnn_lm)");
+        if (Hn == 0) return;
+        NEED(offsets); NEED(totals);
+        model->engine.rnn_lm_score_host(tokens, offsets, Hn, with_eos != 0, token_log_probs, totals);
+    });
+}
+int32_t k2hip_offline_stream_get_alternative_lm_score(const k2hip_offline_stream_t* s, int32_t i, float* lm_total) {
+    return guard([&] {
+        NEED(s); NEED(lm_total);
+        K2_REQUIRE(i >= 0 && i < (int32_t)s->alts.size(), "alternative %d of %zu", i, s->alts.size());
+        *lm_total = s->alts[(size_t)i].lm_score;
+    });
+}
+
+// test and tuning hooks (include/k2hip_debug.h)
+int32_t k2hip_debug_rnn_lm_plan(const int64_t* offsets, int32_t Hn, int32_t with_eos, int32_t H, int64_t gx_cap_floats, int32_t* order,
+                                int32_t* active, int64_t* base, int32_t* block, int32_t cap_T, int32_t* T, int32_t* n_blocks) {
+    return guard([&] {
+        NEED(T); NEED(n_blocks);
+        K2_REQUIRE(Hn >= 0 && H > 0 && cap_T >= 0, "rnn_lm_plan: %d hypotheses, hidden_dim %d", Hn, H);
+        if (Hn > 0) NEED(offsets);
+        for (int i = 0; i < Hn; i++)
+            K2_REQUIRE(offsets[i + 1] >= offsets[i] && offsets[0] >= 0, "rnn_lm_plan: hypothesis %d: offsets decrease", i);
+        const RnnLmPlan p = rnn_lm_plan(offsets, Hn, with_eos != 0, H, gx_cap_floats > 0 ? gx_cap_floats : kRnnLmGxCapFloats);
+        *T = p.T;
+        *n_blocks = (int32_t)p.block.size() - 1;
+        if (p.T > cap_T) failf(K2HIP_ERR_CAPACITY, "rnn_lm_plan: %d positions, capacity %d", p.T, cap_T);
+        if (Hn > 0) {
+            NEED(order);
+            memcpy(order, p.order.data(), sizeof(int32_t) * (size_t)Hn);
+        }
+        NEED(base); NEED(block);
+        if (p.T > 0) {
+            NEED(active);
+            memcpy(active, p.active.data(), sizeof(int32_t) * (size_t)p.T);
+        }
+        memcpy(base, p.base.data(), sizeof(int64_t) * ((size_t)p.T + 1));
+        memcpy(block, p.block.data(), sizeof(int32_t) * p.block.size());
+    });
+}
+int32_t k2hip_debug_rnn_lm_stats(k2hip_model_t* model, int64_t* device_calls, int32_t* last_blocks) {
+    return guard([&] {
+        NEED(model);
+        EngineLock lk(model->engine);
+        if (device_calls) *device_calls = model->engine.rnn_lm_device_calls();
+        if (last_blocks) *last_blocks = model->engine.rnn_lm_last_blocks();
+    });
+}
+int32_t k2hip_debug_rnn_lm_timing(k2hip_model_t* model, int32_t on, double* ms4) {
+    return guard([&] {
+        NEED(model);
+        EngineLock lk(model->engine);
+        model->engine.set_rnn_lm_timing(on != 0);
+        if (ms4)
+            for (int i = 0; i < 4; i++) ms4[i] = model->engine.rnn_lm_last_ms()[(size_t)i];
+    });
+}
+int32_t k2hip_debug_rnn_lm_step_bench(k2hip_model_t* model, int32_t rows, int32_t H, int32_t iters, float* fused_ms, float* composed_ms) {
+    return guard([&] {
+        NEED(model);
+        EngineLock lk(model->engine);
+        model->engine.rnn_lm_step_bench(rows, H, iters, fused_ms, composed_ms);
     });
 }
 

@@ -115,6 +115,7 @@ struct BeamAlt {
     std::vector<int32_t> timestamps;
     std::vector<float> token_log_probs;
     float score = 0.f;
+    float lm_score = 0.f;   // the neural LM's total of the alternative (k2hip_set_rnn_lm rescoring of an offline list); 0: not rescored
 };
 
 // One stream's hypotheses between chunks and its result (the best hypothesis, materialised incrementally).

@@ -3080,6 +3080,37 @@ void Engine::debug_op_host(const char* op, const int64_t* iargs, int n_iargs, vo
             d.base.push_back(reinterpret_cast<char*>(d_rows));
             K2_HIP(copy_blocking(d_rows, rows.data(), sizeof(ResampleRow) * (size_t)B, hipMemcpyHostToDevice));
             resample_gather(c, rows.data(), d_rows, B, dst, n_dst, nmax);
+        } else if (name == "rnn_lm_embed") {
+            const long long R = L();
+            const int E = I();
+            float* emb = P();
+            const int* ids = reinterpret_cast<const int*>(P());
+            float* x0 = P();
+            K2_REQUIRE(emb && ids && x0 && R > 0 && buf_bytes[1] >= 4 * R && buf_bytes[2] >= 4 * R * E, "debug_op_run rnn_lm_embed: %lld rows need ids and x0", R);
+            for (long long i = 0; i < R; i++)   // (the launcher trusts its ids: checked here on the caller's copy)
+                K2_REQUIRE(E > 0 && static_cast<const int*>(bufs[1])[i] >= 0 && 4LL * E * (static_cast<const int*>(bufs[1])[i] + 1LL) <= buf_bytes[0],
+                           "debug_op_run rnn_lm_embed: id %d of row %lld is outside the embedding", static_cast<const int*>(bufs[1])[i], i);
+            rnn_lm_embed(c, emb, ids, x0, R, E);
+        } else if (name == "rnn_lm_step") {
+            const int a = I(), H = I(), first = I();
+            float *hp = P(), *w = P(), *gx = P(), *cc = P(), *ho = P();
+            K2_REQUIRE(hp && w && gx && cc && ho && a > 0 && H > 0 && buf_bytes[0] >= 4LL * a * H && buf_bytes[1] >= 16LL * H * H && buf_bytes[2] >= 16LL * a * H &&
+                           buf_bytes[3] >= 4LL * a * H && buf_bytes[4] >= 4LL * a * H,
+                       "debug_op_run rnn_lm_step: the buffers are short of %d rows of hidden_dim %d", a, H);
+            rnn_lm_step(c, first ? nullptr : hp, w, gx, cc, ho, a, H);
+        } else if (name == "rnn_lm_score") {
+            const long long R = L();
+            const int H = I(), V = I(), Vp = I();
+            float *y = P(), *okn = P(), *ob = P();
+            const int* tgt = reinterpret_cast<const int*>(P());
+            float* lp = P();
+            K2_REQUIRE(y && okn && ob && tgt && lp && R > 0 && H > 0 && V > 0 && Vp >= V && buf_bytes[0] >= 4 * R * H && buf_bytes[1] >= 4LL * H * Vp &&
+                           buf_bytes[2] >= 4LL * V && buf_bytes[3] >= 4 * R && buf_bytes[4] >= 4 * R,
+                       "debug_op_run rnn_lm_score: the buffers are short of %lld rows, hidden_dim %d, %d columns", R, H, Vp);
+            for (long long i = 0; i < R; i++)
+                K2_REQUIRE(static_cast<const int*>(bufs[3])[i] >= 0 && static_cast<const int*>(bufs[3])[i] < V, "debug_op_run rnn_lm_score: target %d of row %lld",
+                           static_cast<const int*>(bufs[3])[i], i);
+            rnn_lm_score_rows(c, y, okn, ob, tgt, lp, R, H, V, Vp);
         } else if (name == "convnext_cat") {
             float *a3 = P(), *pool = P();
             const long long ss = L(), off = L();

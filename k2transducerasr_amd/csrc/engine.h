@@ -15,6 +15,8 @@
 #include "keywords.h"
 #include "model.h"
 #include "resample_plan.h"
+#include "rnn_lm_plan.h"
+#include "rnn_lm_ref.h"
 #include "search_out.h"
 #include "vad_ref.h"
 
@@ -237,6 +239,29 @@ class Engine {
                         std::vector<LongSegment>* out);
     // legs of the last recognize_long in milliseconds of host time: fbank (with the upload), the detector, the batches
     const std::array<double, 3>& last_long_ms() const { return long_ms_; }
+
+    // ---- neural LM rescoring (rnn_lm.hip; the definition: rnn_lm_ref.h, DESIGN.md "Neural LM rescoring") ----
+    // The LM's weights in the layouts the kernels want, ONE device allocation that the caller owns (dev_free), as for the hotword and
+    // n-gram tables; *out names its parts.
+    void* rnn_lm_upload(const RnnLm& lm, RnnLmDev* out);
+    // the LM the scoring entry runs: the caller's host copy (dimensions, sos / eos) and its resident form; null = none
+    void set_rnn_lm(const RnnLm* host, const RnnLmDev& dev) { rnn_host_ = host; rnn_dev_ = host ? dev : RnnLmDev{}; }
+    bool has_rnn_lm() const { return rnn_host_ != nullptr; }
+    // Hn hypotheses back to back in `tokens` (hypothesis i at [offsets[i], offsets[i + 1])) scored by the attached LM: one upload (ids,
+    // targets, descriptors), the launches of the plan (rnn_lm_plan.h), one download.  token_log_probs (may be null) packed per hypothesis
+    // in the caller's order, totals [Hn].  Everything is checked on the host before any device work; a call without a position issues
+    // none.
+    void rnn_lm_score_host(const int64_t* tokens, const int64_t* offsets, int Hn, bool with_eos, float* token_log_probs, float* totals);
+    // scoring calls that reached the device since the model was created, and the time blocks of the last one (k2hip_debug.h)
+    int64_t rnn_lm_device_calls() const { return rnn_calls_; }
+    int rnn_lm_last_blocks() const { return rnn_last_blocks_; }
+    // While on, every scoring call brackets its legs with events and waits for them: milliseconds of the last call's embed, GX, steps and
+    // score legs (tools/rnn_lm_bench.py)
+    void set_rnn_lm_timing(bool on) { rnn_timing_ = on; }
+    const std::array<double, 4>& rnn_lm_last_ms() const { return rnn_ms_; }
+    // tuning record: milliseconds per recurrent step of `a` rows at hidden width H on pseudo-random operands, `iters` launches timed
+    // between two events: the fused step kernel, and the same step composed from the GEMM launcher and lstm_cell (as lstm_layer does)
+    void rnn_lm_step_bench(int a, int H, int iters, float* fused_ms, float* composed_ms);
 
     // ---- pipelined (asynchronous) form of offline_greedy_samples_dev ----
     // submit() enqueues fbank + pad + encoder on the encoder stream and the greedy loop + D2H
@@ -522,6 +547,12 @@ class Engine {
     void vad_device_call(VadJob* jobs, int B, const std::function<void(const Ctx&, std::vector<const float*>&)>& prepare);
     VadTaps vad_taps_;
     std::array<double, 3> long_ms_{};
+    const RnnLm* rnn_host_ = nullptr;
+    RnnLmDev rnn_dev_;
+    int64_t rnn_calls_ = 0;
+    int rnn_last_blocks_ = 0;
+    bool rnn_timing_ = false;
+    std::array<double, 4> rnn_ms_{};
     // samples of the model's rate that stream b of a from-samples batch gives
     int64_t wave_count(int b, int64_t n_samples) const {
         const WaveSrc* w = wave_srcs_ ? wave_srcs_ + b : nullptr;

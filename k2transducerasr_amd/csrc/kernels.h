@@ -48,6 +48,8 @@ struct Tunables {
     int screen_count = 0;         // K2HIP_SCREEN_COUNT: the persistent search counts, per round and part, whether the f16 screen decided the round or it
                                   // went to the f32 passes (k2hip_debug.h: k2hip_debug_op_run "greedy_screen_counts"); 0 = the kernel gets no counter
     int max_streams = 0;          // K2HIP_MAX_STREAMS: slots of the streaming state pool (0 = 256)
+    int rnn_lm_gx_cap = 0;        // K2HIP_RNN_LM_GX_CAP: floats of a neural-LM call's input products per time block (0 = rnn_lm_plan.h's 2^26;
+                                  // tests/test_rnn_lm_gpu.py forces a small one to take the time-blocked route)
     // ---- tuning probes (-DK2HIP_DEV builds only)
     K2HIP_DEV_SWITCH(gemm_cfg, -1);         // K2HIP_GEMM_CFG: force one tile configuration (a k2hip_debug_gemm cfg code: GemmForce)
     K2HIP_DEV_SWITCH(xcd_panels, 0);        // K2HIP_XCD_PANELS: 1 = every GEMM's tiles as bands of M per XCD (rounds 1 - 3)
@@ -474,6 +476,39 @@ struct VadBuffers {
 // rows: B descriptors in host memory (checked here before anything is launched: no stream reads or writes outside its extents),
 // d_rows: the same in device memory
 void vad_run(const Ctx& ctx, const VadRow* rows, const VadRow* d_rows, int B, const VadBuffers& buf);
+
+// ---- neural LM rescoring (rnn_lm.hip; the definition and the host reference: rnn_lm_ref.h; the row layout: rnn_lm_plan.h) -----------
+// The LM resident on the device, one allocation: the embedding [V][E]; per layer W_ih [4H][in] (torch layout: the GEMM launcher's), the
+// summed bias [4H] and W_hh re-laid k-major as [H][4H] (whh_kn[k][g H + j] = W_hh[g H + j][k]: a half-wave's B operand of one k row
+// is 128 contiguous bytes); the output matrix k-major [H][Vp], Vp = V rounded up to 32 with zero columns, and its bias [V].
+struct RnnLmDev {
+    int V = 0, Vp = 0, E = 0, H = 0, L = 0, sos = 0, eos = 0;
+    const float* emb = nullptr;
+    const float* w_ih[8] = {};
+    const float* bias[8] = {};
+    const float* whh_kn[8] = {};
+    const float* out_kn = nullptr;
+    const float* out_b = nullptr;
+};
+// x0 [R][E] = emb[ids[row]]; ids in [0, V) (the caller's check)
+void rnn_lm_embed(const Ctx& ctx, const float* emb, const int* ids, float* x0, long long R, int E);
+// One position of one layer for the a active rows (a contiguous prefix): gates = gx[row] + h_prev[row] . W_hh^T on the matrix pipe
+// (k ascending in one accumulator chain per output), the cell applied in the epilogue, c [a][H] updated in place, h stored into
+// h_out [a][H].  gx rows are 4 H floats.  h_prev == nullptr: the first position (h = 0, the product is skipped).  Rows >= a of c and
+// h_out are not touched; gates never reach memory.
+void rnn_lm_step(const Ctx& ctx, const float* h_prev, const float* whh_kn, const float* gx, float* c, float* h_out, int a, int H);
+// lp [R] = log_softmax(y[row] . W_out^T + b)[target[row]]: strips of 32 rows against out_kn with an online log-sum-exp, the logits never
+// stored; columns >= V never enter the sum
+void rnn_lm_score_rows(const Ctx& ctx, const float* y, const float* out_kn, const float* out_b, const int* target, float* lp, long long R, int H,
+                       int V, int Vp);
+// One hypothesis of rnn_lm_totals, in sorted order j: its positions, the caller's index and where its token log-probs go
+struct RnnLmHyp {
+    int npos = 0, orig = 0;
+    long long out_off = 0;
+};
+// one wave per hypothesis j: total = the float32 sum of lp[base[t] + j] over t < npos in position order -> totals[orig]; the same
+// values -> token_log_probs[out_off + t] when token_log_probs is not null
+void rnn_lm_totals(const Ctx& ctx, const float* lp, const RnnLmHyp* hyps, const long long* base, int Hn, float* token_log_probs, float* totals);
 
 // ---- decoder / joiner / greedy ----------------------------------------------------
 struct DecJoinW {

@@ -89,6 +89,7 @@ const Entry kEntries[] = {
     {"K2HIP_TEST_GREEDY_TIMEOUT", &Tunables::test_greedy_timeout, true},
     {"K2HIP_SEARCH_ROUNDS", &Tunables::search_rounds, false},
     {"K2HIP_MAX_STREAMS", &Tunables::max_streams, false},
+    {"K2HIP_RNN_LM_GX_CAP", &Tunables::rnn_lm_gx_cap, false},
 #ifdef K2HIP_DEV   // tuning probes: a -DK2HIP_DEV build only (make DEV=1)
     {"K2HIP_GEMM_CFG", &Tunables::gemm_cfg, false},
     {"K2HIP_XCD_PANELS", &Tunables::xcd_panels, false},

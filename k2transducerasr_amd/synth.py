@@ -412,3 +412,50 @@ def synth_utterance(u: int, seconds: float, sample_rate: int = 16000) -> np.ndar
     x = np.clip(x, -0.99, 0.99).astype(np.float32)
     x[x == 0.0] = np.float32(1e-7)
     return x
+
+
+def rnn_lm_state_dict(vocab_size: int, embedding_dim: int, hidden_dim: int, num_layers: int, seed: int, tie_weights: bool = False) -> Dict[str, np.ndarray]:
+    """the tensors of a synthetic icefall RnnLmModel under their state-dict names: torch's default LSTM / Linear init range
+    (uniform in +-1 / sqrt(hidden_dim)), a standard-normal embedding scaled by 0.5 and a random output bias, so that no two
+    tokens score alike"""
+    V, E, H = int(vocab_size), int(embedding_dim), int(hidden_dim)
+    k = 1.0 / np.sqrt(H)
+
+    def uni(name, shape):
+        return _rng(seed, name).uniform(-k, k, size=shape).astype(np.float32)
+
+    sd = {"input_embedding.weight": (_rng(seed, "input_embedding.weight").standard_normal((V, E)) * 0.5).astype(np.float32)}
+    for l in range(int(num_layers)):
+        sd[f"rnn.weight_ih_l{l}"] = uni(f"rnn.weight_ih_l{l}", (4 * H, E if l == 0 else H))
+        sd[f"rnn.weight_hh_l{l}"] = uni(f"rnn.weight_hh_l{l}", (4 * H, H))
+        sd[f"rnn.bias_ih_l{l}"] = uni(f"rnn.bias_ih_l{l}", (4 * H,))
+        sd[f"rnn.bias_hh_l{l}"] = uni(f"rnn.bias_hh_l{l}", (4 * H,))
+    if tie_weights:
+        if E != H:
+            raise ValueError(f"tie_weights needs embedding_dim == hidden_dim ({E}, {H})")
+        sd["output_linear.weight"] = sd["input_embedding.weight"]
+    else:
+        sd["output_linear.weight"] = uni("output_linear.weight", (V, H))
+    sd["output_linear.bias"] = _rng(seed, "output_linear.bias").uniform(-1.0, 1.0, size=(V,)).astype(np.float32)
+    return sd
+
+
+def write_rnn_lm(path: str, state_dict: Dict[str, np.ndarray], num_layers: int, sos_id: int = 1, eos_id: int = 1, tie_weights: bool = False,
+                 keep_tied_output: bool = False) -> None:
+    """a neural LM container (include/k2hip.h "Neural LM rescoring") from the state dict's arrays; with tie_weights the output
+    matrix is left out of the file unless keep_tied_output"""
+    emb = np.asarray(state_dict["input_embedding.weight"])
+    H = int(np.asarray(state_dict["rnn.weight_hh_l0"]).shape[1])
+    meta = {"model_type": "rnn_lm", "vocab_size": str(emb.shape[0]), "embedding_dim": str(emb.shape[1]), "hidden_dim": str(H),
+            "num_layers": str(int(num_layers)), "sos_id": str(int(sos_id)), "eos_id": str(int(eos_id)), "tie_weights": str(int(bool(tie_weights)))}
+    tensors = [(n, np.ascontiguousarray(a, dtype=np.float32)) for n, a in state_dict.items()
+               if not (tie_weights and not keep_tied_output and n == "output_linear.weight")]
+    write_k2w(path, meta, tensors)
+
+
+def write_synthetic_rnn_lm(path: str, vocab_size: int, embedding_dim: int, hidden_dim: int, num_layers: int, seed: int, tie_weights: bool = False,
+                           sos_id: int = 1, eos_id: int = 1) -> Dict[str, np.ndarray]:
+    """write a synthetic neural LM and return its state dict (what the tests' float64 twin loads)"""
+    sd = rnn_lm_state_dict(vocab_size, embedding_dim, hidden_dim, num_layers, seed, tie_weights)
+    write_rnn_lm(path, sd, num_layers, sos_id, eos_id, tie_weights)
+    return sd
