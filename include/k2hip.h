@@ -1106,6 +1106,31 @@ int32_t k2hip_rnn_lm_score(k2hip_model_t* model, const int64_t* tokens, const in
                            float* token_log_probs, float* totals);
 int32_t k2hip_offline_stream_get_alternative_lm_score(const k2hip_offline_stream_t* s, int32_t i, float* lm_total);
 
+/* ---- Neural LM shallow fusion in the offline modified beam search -------------------------------------------------------------------
+ * (no reference counterpart; the project's own semantics after icefall's modified_beam_search_lm_shallow_fusion.  DESIGN.md "Neural LM
+ * shallow fusion"; the LM is the one of k2hip_set_rnn_lm, defined in csrc/rnn_lm_ref.h.)
+ * on != 0 switches the mode on; off by default; K2HIP_ERR_INVALID while submitted batches are in flight.  With fusion off nothing
+ * changes anywhere: rescoring as above, the same launches, bit for bit the same results.
+ * Fusion is ACTIVE when it is on and an LM with scale > 0 is attached.  Then, wherever the offline modified beam search runs
+ * (k2hip_beam_search, k2hip_beam_search_nbest, and the batch entries under modified_beam_search that honour k2hip_set_ngram_lm):
+ * STATE AND START: every hypothesis carries an LM state -- (h, c) of all L layers for its token sequence without the [blank, blank]
+ * prefix -- and the LM's next-token log-probs q = log_softmax(h^{L-1} W_out^T + b_out) over V.  The start hypothesis has the state
+ * after sos from h = c = 0 (the first position of csrc/rnn_lm_ref.h).
+ * SELECTION AND THE LM TERM: a frame's top-`beam` selection uses the same sums as without the LM.  A selected candidate of parent p that
+ * appends a real token v then gets ((sum + hotword bonus) + n-gram term) + fl32(scale * q_p[v]); the merge of equal sequences follows,
+ * exactly where the n-gram term is added.  Blank and unk earn nothing and keep the parent's state; the child's state is the parent's
+ * advanced by v.
+ * FINAL PICK AND SCORES: no eos term is applied at the end.  The final pick and all reported scores include the LM terms; token
+ * log-probs and the beam trace stay acoustic.  So for a returned hypothesis y the sum of its LM terms is
+ * scale * k2hip_rnn_lm_score(y, with_eos = 0) up to rounding.
+ * RESCORING WHILE FUSION IS ACTIVE: k2hip_offline_recognizer_get_results does NOT also rescore (the LM would count twice), and
+ * k2hip_offline_stream_get_alternative_lm_score gives 0.
+ * Fusion works together with hotwords, the n-gram LM and N-best.  Greedy search, the CTC searches,
+ * k2hip_offline_recognizer_get_result, the pipelined submit / wait, every streaming entry and k2hip_offline_recognize_long ignore the
+ * switch: a streaming call on a model with fusion on runs the unfused search.
+ * The device is held to a float64 twin within a bound, not bit for bit: the caveat rescoring carries. */
+int32_t k2hip_set_rnn_lm_fusion(k2hip_model_t* model, int32_t on);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

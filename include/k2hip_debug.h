@@ -273,6 +273,22 @@ int32_t k2hip_debug_rnn_lm_step_bench(k2hip_model_t* model, int32_t rows, int32_
  *                   (in / out), h_out [rows][H] (out): rows >= a of c and h_out stay as they were
  *   "rnn_lm_score"  ints R, H, V, Vp; bufs y [R][H], out_kn [H][Vp], out_b [V], target [R] (int32), lp [R] (out) */
 
+/* ---- neural LM shallow fusion (k2hip.h "Neural LM shallow fusion"; tests/test_rnn_lm_fusion_gpu.py, tools/rnn_lm_fusion_bench.py) ---- */
+/* searches: fused searches enqueued since the process started (the third counter beside k2hip_debug_beam_launch_counts: a fused
+ * search moves neither of those); swept / idle: per-layer LM launches of this model's attached LM that read their weights / that only
+ * moved state because no slot of the batch appended a token on their frame (counted on the device; 0 without an LM).  Each may be NULL. */
+int32_t k2hip_debug_rnn_lm_fusion_stats(k2hip_model_t* model, int64_t* searches, int64_t* swept, int64_t* idle);
+/* milliseconds per k_nlm_advance launch of `rows` rows that all append, input and hidden width H (2 H products per gate; the rescoring
+ * step of k2hip_debug_rnn_lm_step_bench sums H), a scattered parent map, pseudo-random operands, `iters` launches between two events */
+int32_t k2hip_debug_nlm_advance_bench(k2hip_model_t* model, int32_t rows, int32_t H, int32_t iters, float* ms);
+/* k2hip_debug_op_run ops:
+ *   "nlm_advance"  ONE launch.  ints M, in, H, use_emb, V, live (-1: no flag; else the device flag is set to it first); bufs wcat (the
+ *                  layer's panels: kernels.h RnnLmDev::wcat), bias [4H], x (emb [V][in] when use_emb, else rows [M][in]), h_par [M][H],
+ *                  c_par [M][H], h_out [M][H] (out), c_out [M][H] (out), par [M] (int32), tok [M] (int32, -1: nothing appended),
+ *                  flag [1] (int32), work [2] (int64 counters, in / out)
+ *   "nlm_rows"     the GEMM launcher + one launch.  ints M, H, V, live; bufs h [M][H], w_out [V][H], out_b [V], q_par [M][V],
+ *                  q_out [M][V] (out), par [M], tok [M], flag [1] */
+
 /* ---- GEMM tuning ------------------------------------------------------------------------------- */
 /* time `iters` launches of a shape / configuration on pseudo-random operands (tools/gemm_lab.py, gemm_tune.py) */
 int32_t k2hip_debug_gemm(k2hip_model_t* model, int32_t M, int32_t N, int32_t K, int32_t act, int32_t with_res, int32_t cfg,

@@ -294,6 +294,9 @@ def _bind_rnn_lm(L):
     L.k2hip_debug_rnn_lm_stats.argtypes = [vp, lp, ip]
     L.k2hip_debug_rnn_lm_timing.argtypes = [vp, C.c_int32, C.POINTER(C.c_double)]
     L.k2hip_debug_rnn_lm_step_bench.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, fp, fp]
+    L.k2hip_set_rnn_lm_fusion.argtypes = [vp, C.c_int32]
+    L.k2hip_debug_rnn_lm_fusion_stats.argtypes = [vp, lp, lp, lp]
+    L.k2hip_debug_nlm_advance_bench.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, fp]
     L._rnn_lm_bound = True
 
 
@@ -1011,6 +1014,27 @@ class Model:
         self._chk(self._L.k2hip_debug_rnn_lm_timing(self._h, int(on), ms))
         return dict(embed_ms=ms[0], gx_ms=ms[1], steps_ms=ms[2], score_ms=ms[3])
 
+    def set_rnn_lm_fusion(self, on: bool = True):
+        """k2hip_set_rnn_lm_fusion: with an LM of scale > 0 attached, the offline modified beam search adds the LM's term to every
+        appended token DURING the search (shallow fusion) and get_results no longer rescores (include/k2hip.h "Neural LM shallow
+        fusion")."""
+        _bind_rnn_lm(self._L)
+        self._chk(self._L.k2hip_set_rnn_lm_fusion(self._h, int(bool(on))))
+
+    def rnn_lm_fusion_stats(self) -> dict:
+        """fused searches enqueued by the process; per-layer LM launches of this model's LM that swept their weights / only moved state"""
+        _bind_rnn_lm(self._L)
+        n, s, i = C.c_int64(), C.c_int64(), C.c_int64()
+        self._chk(self._L.k2hip_debug_rnn_lm_fusion_stats(self._h, C.byref(n), C.byref(s), C.byref(i)))
+        return dict(searches=n.value, swept=s.value, idle=i.value)
+
+    def nlm_advance_bench(self, rows: int, hidden_dim: int, iters: int = 200) -> float:
+        """milliseconds per k_nlm_advance launch (k2hip_debug_nlm_advance_bench)"""
+        _bind_rnn_lm(self._L)
+        ms = C.c_float()
+        self._chk(self._L.k2hip_debug_nlm_advance_bench(self._h, int(rows), int(hidden_dim), int(iters), C.byref(ms)))
+        return float(ms.value)
+
     def rnn_lm_step_bench(self, rows: int, hidden_dim: int, iters: int = 200) -> dict:
         """milliseconds per recurrent step: the fused kernel, and the step composed from the GEMM launcher and the cell kernel"""
         _bind_rnn_lm(self._L)
@@ -1618,11 +1642,12 @@ class OfflineRecognizer:
     NgramLm fused with weight ngram_lm_scale (sherpa's lm / lm_scale), modified_beam_search only.  ctc_prefix_biasing=True: a CTC model's
     ctc_prefix_beam_search uses both as well (Model.set_ctc_prefix_biasing); without it the recognizer behaves as before.  rnn_lm: an
     RnnLm that rescores the N-best lists of get_results with weight rnn_lm_scale (sherpa's RNN LM rescoring); needs nbest > 1, the
-    alternatives then carry lm_score."""
+    alternatives then carry lm_score.  rnn_lm_fusion=True: the LM is fused into modified_beam_search instead (Model.set_rnn_lm_fusion):
+    its term is added during the search, any nbest, and the lists are not rescored."""
 
     def __init__(self, weights_path: str, device: int = 0, decoding_method: str = "greedy_search", beam: int = 4, hotwords=None,
                  hotwords_score: float = 1.5, nbest: int = 1, ngram_lm: Optional["NgramLm"] = None, ngram_lm_scale: float = 0.3,
-                 ctc_prefix_biasing: bool = False, rnn_lm: Optional["RnnLm"] = None, rnn_lm_scale: float = 0.5):
+                 ctc_prefix_biasing: bool = False, rnn_lm: Optional["RnnLm"] = None, rnn_lm_scale: float = 0.5, rnn_lm_fusion: bool = False):
         self.model = Model(weights_path, device)
         self.model.set_decoding_method(decoding_method, beam)
         if nbest != 1:   # (streams then carry .alternatives() / .token_log_probs() after get_results)
@@ -1637,6 +1662,8 @@ class OfflineRecognizer:
             self.model.set_ctc_prefix_biasing(True)
         if rnn_lm is not None:
             self.model.set_rnn_lm(rnn_lm, rnn_lm_scale)
+        if rnn_lm_fusion:
+            self.model.set_rnn_lm_fusion(True)
 
     def create_offline_stream(self) -> OfflineStream:  # CreateOfflineStream :71-75
         return OfflineStream(self.model)

@@ -125,7 +125,9 @@ struct k2hip_model {
     // on the device in one allocation, and the scale of the rescoring (0 = the N-best lists are left alone)
     std::shared_ptr<const RnnLm> rnn_lm;
     void* rnn_dev = nullptr;
+    void* rnn_fuse_dev = nullptr;   // the fused search's layouts of the same LM: made when fusion is on, null otherwise
     float rnn_scale = 0.f;
+    bool rnn_fusion = false;   // k2hip_set_rnn_lm_fusion: the LM's term is added during the offline modified beam search instead
     // k2hip_set_nbest: 1 = off (the engine keeps nothing beyond the best hypothesis), n > 1 = alternatives and token log-probs are kept
     std::atomic<int> nbest{1};
     // the graphs attached to this model's streams (HwResident), by serial number; hw_uploads counts the uploads (k2hip_debug.h)
@@ -180,10 +182,11 @@ struct k2hip_model {
             } catch (...) {
             }
         }
-        if (rnn_dev) {
+        if (rnn_dev || rnn_fuse_dev) {
             try {
                 engine.synchronize();
-                engine.dev_free(rnn_dev);
+                if (rnn_dev) engine.dev_free(rnn_dev);
+                if (rnn_fuse_dev) engine.dev_free(rnn_fuse_dev);
             } catch (...) {
             }
         }
@@ -3171,7 +3174,9 @@ int32_t k2hip_offline_recognizer_get_results(k2hip_model_t* model, k2hip_offline
                     streams[b]->alts.clear();
                     for (int i = 0; i < h.n_hyps[(size_t)b]; i++) streams[b]->alts.push_back(alt_of(h, b, i));
                 }
-            if (e.nbest() > 1 && model->rnn_lm && model->rnn_scale > 0.f && (c.ctc ? e.ctc_prefix() > 0 : e.beam() > 0))
+            // (an active fusion has put the LM's terms into the transducer search's scores already: rescoring would count it twice)
+            const bool fused = !c.ctc && e.beam() > 0 && e.rnn_lm_fusion_active();
+            if (!fused && e.nbest() > 1 && model->rnn_lm && model->rnn_scale > 0.f && (c.ctc ? e.ctc_prefix() > 0 : e.beam() > 0))
                 try {
                     rnn_lm_rescore(model, streams, B, max_tokens, tok.data(), ts.data(), n.data());
                 } catch (...) {   // (a failed call leaves the start state)
@@ -3641,16 +3646,43 @@ int32_t k2hip_set_rnn_lm(k2hip_model_t* model, const k2hip_rnn_lm_t* lm, float s
         K2_REQUIRE(e.batches_in_flight() == 0, "set_rnn_lm: %d submitted batches are in flight; wait for them first", e.batches_in_flight());
         void* dev = nullptr;
         RnnLmDev tables;
+        void* fuse = nullptr;
         if (lm) dev = e.rnn_lm_upload(*lm->lm, &tables);   // (a failed upload leaves the setting as it was)
-        void* old = model->rnn_dev;
+        if (lm && model->rnn_fusion) {                     // (a model that only rescores never pays for the fused layouts)
+            try {
+                fuse = e.rnn_lm_fusion_upload(*lm->lm, &tables);
+            } catch (...) {
+                try { e.dev_free(dev); } catch (...) {}
+                throw;
+            }
+        }
+        void *old = model->rnn_dev, *old_fuse = model->rnn_fuse_dev;
         model->rnn_dev = dev;
+        model->rnn_fuse_dev = fuse;
         model->rnn_lm = lm ? lm->lm : nullptr;
         model->rnn_scale = lm ? scale : 0.f;
         e.set_rnn_lm(model->rnn_lm.get(), tables);
-        if (old) {
+        e.set_rnn_lm_fusion(model->rnn_fusion, model->rnn_scale);
+        if (old || old_fuse) {
             e.synchronize();
-            e.dev_free(old);
+            if (old) e.dev_free(old);
+            if (old_fuse) e.dev_free(old_fuse);
         }
+    });
+}
+int32_t k2hip_set_rnn_lm_fusion(k2hip_model_t* model, int32_t on) {
+    return guard([&] {
+        NEED(model);
+        Engine& e = model->engine;
+        EngineLock lk(e);
+        K2_REQUIRE(e.batches_in_flight() == 0, "set_rnn_lm_fusion: %d submitted batches are in flight; wait for them first", e.batches_in_flight());
+        if (on && model->rnn_lm && !model->rnn_fuse_dev) {   // the fused layouts of the attached LM, on first use
+            RnnLmDev tables = e.rnn_lm_dev();
+            model->rnn_fuse_dev = e.rnn_lm_fusion_upload(*model->rnn_lm, &tables);
+            e.set_rnn_lm(model->rnn_lm.get(), tables);
+        }
+        model->rnn_fusion = on != 0;
+        e.set_rnn_lm_fusion(model->rnn_fusion, model->rnn_scale);
     });
 }
 int32_t k2hip_rnn_lm_score(k2hip_model_t* model, const int64_t* tokens, const int64_t* offsets, int32_t Hn, int32_t with_eos,
@@ -3705,6 +3737,21 @@ int32_t k2hip_debug_rnn_lm_stats(k2hip_model_t* model, int64_t* device_calls, in
         EngineLock lk(model->engine);
         if (device_calls) *device_calls = model->engine.rnn_lm_device_calls();
         if (last_blocks) *last_blocks = model->engine.rnn_lm_last_blocks();
+    });
+}
+int32_t k2hip_debug_rnn_lm_fusion_stats(k2hip_model_t* model, int64_t* searches, int64_t* swept, int64_t* idle) {
+    return guard([&] {
+        NEED(model);
+        EngineLock lk(model->engine);
+        if (searches) *searches = beam_nlm_launch_count();
+        model->engine.rnn_lm_fusion_work(swept, idle);
+    });
+}
+int32_t k2hip_debug_nlm_advance_bench(k2hip_model_t* model, int32_t rows, int32_t H, int32_t iters, float* ms) {
+    return guard([&] {
+        NEED(model); NEED(ms);
+        EngineLock lk(model->engine);
+        model->engine.nlm_advance_bench(rows, H, iters, ms);
     });
 }
 int32_t k2hip_debug_rnn_lm_timing(k2hip_model_t* model, int32_t on, double* ms4) {

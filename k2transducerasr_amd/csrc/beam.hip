@@ -23,6 +23,9 @@
 // N-gram LM shallow fusion (BeamArgs::lm; resumed: lst_in / lst_out beside st_in / st_out): every hypothesis also carries the state of the LM's back-off automaton; the
 // selected candidates' walks (beam_lm_walk, a wave per candidate) run beside the pair comparisons, before the barrier in front of the
 // merge section, which reads term and next state from LDS.  It lives in the HW instantiations behind a null check, as hw_bonus does.
+// Neural LM shallow fusion (BeamArgs::nlm; rnn_lm_fuse.hip): offline and in the per-frame launch form only.  The NLM instantiation of the
+// step reads the parent's row of the LM's log-probs for a selected real token, adds the scaled term after the n-gram term, and leaves
+// for the LM launches behind it each new slot's parent slot and appended token and the frame's "something appended" flag.
 #include <type_traits>
 
 #include <atomic>
@@ -150,12 +153,27 @@ struct HypView {
     // of each emitted token at the frame it was emitted
     const float* yp_c = nullptr;
     float* yp_n = nullptr;
+    // neural LM shallow fusion (the NLM instantiation only): the stream's rows of the LM's next-token log-probs at frame t [K][V]; what
+    // the step leaves for the LM launches behind it -- for each new slot the GLOBAL slot (nbase + parent) it continues and the token
+    // it appended (-1: none) -- and the frame's "some slot appended" flag
+    const float* nq_c = nullptr;
+    int* npar = nullptr;
+    int* ntok = nullptr;
+    int* nflag = nullptr;
+    int nbase = 0;
+    float nscale = 0.f;
 };
+// a + fl32(s q): the product rounded on its own (no contraction into an fma)
+__device__ __forceinline__ float add_scaled(float a, float s, float q) {
+#pragma clang fp contract(off)
+    const float t = s * q;
+    return a + t;
+}
 constexpr int kStepScratchInts = 4 * kMaxBeam + 4 + 2 * kMaxBeam * kMaxBeam;
 constexpr int kYpScratchFloats = kMaxBeam * kMaxBeam + kMaxBeam;
 // one workgroup of NT threads per stream; lg: the hypotheses' logits, ldl floats per row; scratch: kStepScratchInts ints of LDS
 // pscratch: kYpScratchFloats floats of LDS when hv.yp_n is set (the candidates' unbiased terms beside candv / candi, the top K's)
-template <int NT, bool HW>
+template <int NT, bool HW, bool NLM = false>
 __device__ void beam_step_body(const HypView& hv, const float* lg, int ldl, int V, int t, int* scratch, float* pscratch = nullptr) {
     constexpr int BT = NT;
     float* candp = hv.yp_n ? pscratch : nullptr;
@@ -346,6 +364,9 @@ __device__ void beam_step_body(const HypView& hv, const float* lg, int ldl, int 
                     const int hr = topi[r] / V, tr = topi[r] % V;
                     if (hv.hw_bonus && tr != K2HIP_BLANK_ID && tr != K2HIP_UNK_ID) tv[r] += hv.hw_bonus[(long long)hv.st_c[hr] * V + tr];
                     if (hv.lm.states) tv[r] += lmterm[r];   // (sum + hotword bonus) + LM term
+                    if constexpr (NLM) {   // ... + fl32(scale q_parent[token])
+                        if (tr != K2HIP_BLANK_ID && tr != K2HIP_UNK_ID) tv[r] = add_scaled(tv[r], hv.nscale, hv.nq_c[(long long)hr * V + tr]);
+                    }
                 }
             }
             lpn[r] = -INFINITY;
@@ -403,6 +424,10 @@ __device__ void beam_step_body(const HypView& hv, const float* lg, int ldl, int 
                 hv.st_n[k] = 0;
                 if (hv.lst_n) hv.lst_n[k] = 0;
             }
+            if constexpr (NLM) {   // (empty slots still go through the LM launches: a valid parent, nothing appended)
+                hv.npar[k] = hv.nbase;
+                hv.ntok[k] = -1;
+            }
         }
         *hv.nhyp = nN;
         if (hv.trace) hv.trace[2 * K] = nN;
@@ -439,6 +464,11 @@ __device__ void beam_step_body(const HypView& hv, const float* lg, int ldl, int 
                 hv.st_n[slot] = (realr && hv.hw_next) ? hv.hw_next[(long long)hv.st_c[hr] * V + tr] : hv.st_c[hr];
                 if (hv.lst_n) hv.lst_n[slot] = lmnext[r];
             }
+            if constexpr (NLM) {
+                hv.npar[slot] = hv.nbase + hr;
+                hv.ntok[slot] = realr ? tr : -1;
+                if (realr) *hv.nflag = 1;
+            }
             // decoder context of the new hypothesis: last two of [c0, c1] + ys, [c0, c1] = the saved hypothesis' context (resume) or
             // [blank, blank]
             long long c0 = K2HIP_BLANK_ID, c1 = K2HIP_BLANK_ID;
@@ -458,7 +488,7 @@ __device__ void beam_step_body(const HypView& hv, const float* lg, int ldl, int 
 }
 
 // one workgroup per stream; `cur` = buffer holding frame t's input hypotheses
-template <bool HW>
+template <bool HW, bool NLM = false>
 __global__ __launch_bounds__(BT) void k_beam_step(BeamState s, const float* __restrict__ logits, int V, int t, int cur, int B, int* trace, int Tp) {
     __shared__ int scratch[kStepScratchInts];
     __shared__ float pscratch[kYpScratchFloats];
@@ -497,7 +527,15 @@ __global__ __launch_bounds__(BT) void k_beam_step(BeamState s, const float* __re
         hv.yp_c = s.yp + ((long long)cur * BK + (long long)b * K) * s.cap;
         hv.yp_n = s.yp + ((long long)nxt * BK + (long long)b * K) * s.cap;
     }
-    beam_step_body<BT, HW>(hv, logits + (long long)b * K * V, V, V, t, scratch, pscratch);
+    if constexpr (NLM) {
+        hv.nq_c = s.nq + ((long long)cur * BK + (long long)b * K) * V;
+        hv.npar = s.npar + b * K;
+        hv.ntok = s.ntok + b * K;
+        hv.nflag = s.nflag + t;
+        hv.nbase = b * K;
+        hv.nscale = s.nscale;
+    }
+    beam_step_body<BT, HW, NLM>(hv, logits + (long long)b * K * V, V, V, t, scratch, pscratch);
 }
 
 // resume: every surviving hypothesis of the stream into its out block, and the best one (get_most_probable over the WHOLE
@@ -934,7 +972,13 @@ __global__ void k_beam_final(BeamState s, int fin, int B, long long* __restrict_
 void beam_search(const Ctx& ctx, const DecJoinW& w, const BeamArgs& a) {
     K2_REQUIRE(a.beam >= 1 && a.beam <= kMaxBeam, "beam search: beam %d out of range [1,%d]", a.beam, kMaxBeam);
     K2_REQUIRE(a.B > 0 && a.Tp > 0, "beam search: bad shape");
-    const bool hw = a.hw_next != nullptr || a.hw_streams != nullptr || a.lm.states != nullptr;
+    // neural LM shallow fusion: the biased instantiation with the neural term, always in the per-frame launch form
+    const bool nlm = a.nlm.dev.emb != nullptr;
+    const bool hw = a.hw_next != nullptr || a.hw_streams != nullptr || a.lm.states != nullptr || nlm;
+    K2_REQUIRE(!nlm || (!a.rin && a.nlm.scale > 0.f && a.nlm.dev.V == w.V && a.nlm.dev.L >= 1 && a.nlm.dev.L <= 8 && a.nlm.dev.w_out && a.nlm.dev.out_b &&
+                        a.nlm.dev.h0 && a.nlm.dev.c0 && a.nlm.dev.q0),
+               "beam search: neural LM fusion belongs to the offline search and needs a complete LM over the model's %d tokens and a scale > 0", w.V);
+    for (int k = 0; nlm && k < a.nlm.dev.L; k++) K2_REQUIRE(a.nlm.dev.wcat[k] && a.nlm.dev.bias[k], "beam search: neural LM fusion: layer %d has no weights", k);
     K2_REQUIRE(!a.lm.states || (a.lm.arc_tok && a.lm.arc_lp && a.lm.arc_next && a.lm.uni_lp && a.lm.uni_next), "beam search: incomplete n-gram LM tables");
     K2_REQUIRE(!(a.lm.states && a.rin) || (a.lst_in && a.lst_out), "beam search: the resumed search with an n-gram LM needs its LM state blocks");
     K2_REQUIRE(!a.hw_next || (a.hw_bonus && a.hw_pending), "beam search: incomplete hotword tables");
@@ -948,10 +992,13 @@ void beam_search(const Ctx& ctx, const DecJoinW& w, const BeamArgs& a) {
                                 a.nb.scores && a.nb.n_hyps),
                "beam search: incomplete N-best outputs (nbest %d, range [1,%d])", a.nb.nbest, kMaxBeam);
     K2_REQUIRE(!a.yp_out || a.rin, "beam search: the token log-prob side block belongs to the resumed search");
-    if (!ctx.dry) g_launches[hw ? 1 : 0]++;
+    if (!ctx.dry) {
+        if (nlm) nlm_note_search();
+        else g_launches[hw ? 1 : 0]++;
+    }
     Arena& ar = *ctx.arena;
     const int B = a.B, K = a.beam, M = B * K, cap = a.Tp + 1;
-    {
+    if (!nlm) {
         // the one-kernel form: needs the decoder table (small vocabulary) and the stream's logits and hypotheses in LDS
         // hypotheses in LDS when they fit beside the logits (T' <= ~600 at beam 4 with the large-en shapes), else in device memory
         const bool hyp_in_lds = sizeof(float) * beam_loop_lds_floats(w.J, w.Vp, K, cap, true, hw, yp) <= 150 * 1024 && !tunables().beam_hyp_global;
@@ -1040,6 +1087,22 @@ void beam_search(const Ctx& ctx, const DecJoinW& w, const BeamArgs& a) {
             s.lm = a.lm; s.lst_in = a.lst_in; s.lst_out = a.lst_out;
         }
     }
+    // neural LM: the slots' LSTM states [2][L][M][H] and rows [2][M][V] by frame parity, the step's notes for the LM launches
+    const RnnLmDev& nd = a.nlm.dev;
+    float *nh = nullptr, *nc = nullptr, *nq = nullptr;
+    const int64_t nst = nlm ? (int64_t)nd.L * M * nd.H : 0;
+    if (nlm) {
+        nh = ar.take<float>(2 * nst);
+        nc = ar.take<float>(2 * nst);
+        nq = ar.take<float>((int64_t)2 * M * nd.V);
+        s.nq = nq;
+        s.npar = ar.take<int>(M);
+        s.ntok = ar.take<int>(M);
+        s.nflag = ar.take<int>(a.Tp);
+        s.nscale = a.nlm.scale;
+        if (!ctx.dry) K2_HIP(hipMemsetAsync(s.nflag, 0, sizeof(int) * (size_t)a.Tp, ctx.stream));
+        nlm_broadcast(ctx, nd, nh, nc, nq, M);
+    }
     float* hbuf = ar.take<float>((int64_t)M * w.DD);
     float* act = ar.take<float>((int64_t)M * w.J);
     float* logits = ar.take<float>((int64_t)M * w.V);
@@ -1063,9 +1126,28 @@ void beam_search(const Ctx& ctx, const DecJoinW& w, const BeamArgs& a) {
         }
         linear(ctx, act, w.J, a.out_w, w.out_b, logits, w.V, M, w.J, w.V);
         if (!ctx.dry) {
-            if (hw) hipLaunchKernelGGL(k_beam_step<true>, dim3(B), dim3(BT), 0, ctx.stream, s, logits, w.V, t, t & 1, B, a.trace, a.Tp);
+            if (nlm) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_beam_step<true, true>), dim3(B), dim3(BT), 0, ctx.stream, s, logits, w.V, t, t & 1, B, a.trace, a.Tp);
+            else if (hw) hipLaunchKernelGGL(k_beam_step<true>, dim3(B), dim3(BT), 0, ctx.stream, s, logits, w.V, t, t & 1, B, a.trace, a.Tp);
             else hipLaunchKernelGGL(k_beam_step<false>, dim3(B), dim3(BT), 0, ctx.stream, s, logits, w.V, t, t & 1, B, a.trace, a.Tp);
             K2_HIP(hipGetLastError());
+        }
+        if (nlm && t + 1 < a.Tp) {
+            // the LM behind the step: one launch per layer over all slots (state of parity t & 1 gathered through npar into the other
+            // parity), then the rows; on a frame in which no slot appended a token they only move state and rows
+            const int cur = t & 1, nxt = cur ^ 1;
+            for (int k = 0; k < nd.L; k++) {
+                NlmAdvance v;
+                v.wcat = nd.wcat[k]; v.bias = nd.bias[k];
+                v.emb = k == 0 ? nd.emb : nullptr;
+                v.x_rows = k == 0 ? nullptr : nh + nxt * nst + (int64_t)(k - 1) * M * nd.H;
+                v.h_par = nh + cur * nst + (int64_t)k * M * nd.H; v.c_par = nc + cur * nst + (int64_t)k * M * nd.H;
+                v.h_out = nh + nxt * nst + (int64_t)k * M * nd.H; v.c_out = nc + nxt * nst + (int64_t)k * M * nd.H;
+                v.par = s.npar; v.tok = s.ntok; v.live = s.nflag + t; v.work = nd.work;
+                v.M = M; v.in = k == 0 ? nd.E : nd.H; v.H = nd.H;
+                nlm_advance(ctx, v);
+            }
+            nlm_rows(ctx, nh + nxt * nst + (int64_t)(nd.L - 1) * M * nd.H, nd.w_out, nd.out_b, nq + (int64_t)cur * M * nd.V, nq + (int64_t)nxt * M * nd.V,
+                     s.npar, s.ntok, s.nflag + t, M, nd.H, nd.V);
         }
     }
     if (!ctx.dry) {

@@ -920,6 +920,10 @@ Engine::SearchExtras Engine::beam_device(const Ctx& c, const float* enc, int B, 
     a.scores = ex.scores;
     a.hw_next = hw_next_; a.hw_bonus = hw_bonus_; a.hw_pending = hw_pending_;
     a.lm = lm_;
+    if (keep_nbest && rnn_lm_fusion_active()) {   // (the pipelined route and recognize_long keep no list: they ignore the switch)
+        a.nlm.dev = rnn_dev_;
+        a.nlm.scale = rnn_fuse_scale_;
+    }
     if (nbest_ > 0 && keep_nbest) {
         const int64_t NB = (int64_t)B * nbest_;
         ex.nb.nbest = nbest_;
@@ -3111,6 +3115,48 @@ void Engine::debug_op_host(const char* op, const int64_t* iargs, int n_iargs, vo
                 K2_REQUIRE(static_cast<const int*>(bufs[3])[i] >= 0 && static_cast<const int*>(bufs[3])[i] < V, "debug_op_run rnn_lm_score: target %d of row %lld",
                            static_cast<const int*>(bufs[3])[i], i);
             rnn_lm_score_rows(c, y, okn, ob, tgt, lp, R, H, V, Vp);
+        } else if (name == "nlm_advance") {
+            // ints M, in, H, use_emb, V (rows of emb), live (-1: no flag, else the flag's value)
+            const int M = I(), in = I(), H = I(), use_emb = I(), V = I(), live = I();
+            float *wcat = P(), *bias = P(), *x = P(), *hp = P(), *cp = P(), *ho = P(), *co = P();
+            const int* par = reinterpret_cast<const int*>(P());
+            const int* tok = reinterpret_cast<const int*>(P());
+            int* flag = reinterpret_cast<int*>(P());
+            long long* work = reinterpret_cast<long long*>(P());
+            K2_REQUIRE(M > 0 && in > 0 && H > 0 && V > 0, "debug_op_run nlm_advance: bad shape");
+            const long long Kc = (in + 31) / 32 * 32 + H, xrows = use_emb ? V : M;
+            K2_REQUIRE(wcat && bias && x && hp && cp && ho && co && par && tok && flag && work && buf_bytes[0] >= 16LL * H * Kc && buf_bytes[1] >= 16LL * H &&
+                           buf_bytes[2] >= 4LL * xrows * in && buf_bytes[3] >= 4LL * M * H && buf_bytes[4] >= 4LL * M * H && buf_bytes[5] >= 4LL * M * H &&
+                           buf_bytes[6] >= 4LL * M * H && buf_bytes[7] >= 4LL * M && buf_bytes[8] >= 4LL * M && buf_bytes[9] >= 4 && buf_bytes[10] >= 16,
+                       "debug_op_run nlm_advance: the buffers are short of %d rows, input %d, hidden_dim %d", M, in, H);
+            for (int i = 0; i < M; i++) {   // (the launcher trusts its indexes: checked here on the caller's copy)
+                const int p = static_cast<const int*>(bufs[7])[i], t = static_cast<const int*>(bufs[8])[i];
+                K2_REQUIRE(p >= 0 && p < M && t >= -1 && (use_emb ? t < V : true), "debug_op_run nlm_advance: row %d continues slot %d with token %d", i, p, t);
+            }
+            if (live >= 0) K2_HIP(hipMemsetD32Async((hipDeviceptr_t)flag, live, 1, stream_));
+            NlmAdvance a;
+            a.wcat = wcat; a.bias = bias;
+            a.emb = use_emb ? x : nullptr; a.x_rows = use_emb ? nullptr : x;
+            a.h_par = hp; a.c_par = cp; a.h_out = ho; a.c_out = co;
+            a.par = par; a.tok = tok; a.live = live >= 0 ? flag : nullptr; a.work = work;
+            a.M = M; a.in = in; a.H = H;
+            nlm_advance(c, a);
+        } else if (name == "nlm_rows") {
+            // ints M, H, V, live (-1: no flag)
+            const int M = I(), H = I(), V = I(), live = I();
+            float *h = P(), *wout = P(), *ob = P(), *qp = P(), *qo = P();
+            const int* par = reinterpret_cast<const int*>(P());
+            const int* tok = reinterpret_cast<const int*>(P());
+            int* flag = reinterpret_cast<int*>(P());
+            K2_REQUIRE(M > 0 && H > 0 && V > 0 && h && wout && ob && qp && qo && par && tok && flag && buf_bytes[0] >= 4LL * M * H && buf_bytes[1] >= 4LL * V * H &&
+                           buf_bytes[2] >= 4LL * V && buf_bytes[3] >= 4LL * M * V && buf_bytes[4] >= 4LL * M * V && buf_bytes[5] >= 4LL * M &&
+                           buf_bytes[6] >= 4LL * M && buf_bytes[7] >= 4,
+                       "debug_op_run nlm_rows: the buffers are short of %d rows, hidden_dim %d, V = %d", M, H, V);
+            for (int i = 0; i < M; i++)
+                K2_REQUIRE(static_cast<const int*>(bufs[5])[i] >= 0 && static_cast<const int*>(bufs[5])[i] < M, "debug_op_run nlm_rows: row %d continues slot %d", i,
+                           static_cast<const int*>(bufs[5])[i]);
+            if (live >= 0) K2_HIP(hipMemsetD32Async((hipDeviceptr_t)flag, live, 1, stream_));
+            nlm_rows(c, h, wout, ob, qp, qo, par, tok, live >= 0 ? flag : nullptr, M, H, V);
         } else if (name == "convnext_cat") {
             float *a3 = P(), *pool = P();
             const long long ss = L(), off = L();

@@ -16,6 +16,7 @@
 #include "model.h"
 #include "resample_plan.h"
 #include "rnn_lm_plan.h"
+#include "rnn_lm_fuse_layout.h"
 #include "rnn_lm_ref.h"
 #include "search_out.h"
 #include "vad_ref.h"
@@ -247,6 +248,20 @@ class Engine {
     // the LM the scoring entry runs: the caller's host copy (dimensions, sos / eos) and its resident form; null = none
     void set_rnn_lm(const RnnLm* host, const RnnLmDev& dev) { rnn_host_ = host; rnn_dev_ = host ? dev : RnnLmDev{}; }
     bool has_rnn_lm() const { return rnn_host_ != nullptr; }
+    // Neural LM shallow fusion (k2hip_set_rnn_lm_fusion): with `on`, an attached LM and scale > 0 the offline modified beam search of
+    // the synchronous entries (the ones that keep an N-best list: not the pipelined route, not recognize_long) adds the LM's term
+    // during the search; every other path runs as before
+    void set_rnn_lm_fusion(bool on, float scale) { rnn_fusion_ = on; rnn_fuse_scale_ = scale; }
+    bool rnn_lm_fusion_active() const { return rnn_fusion_ && rnn_host_ && rnn_fuse_scale_ > 0.f && rnn_dev_.w_out; }
+    // the fused search's layouts of the attached LM (rnn_lm_fusion_upload): built when fusion is first switched on, never for a model
+    // that only rescores; ONE more device allocation that the caller owns, *io = the attached LM's tables, completed
+    void* rnn_lm_fusion_upload(const RnnLm& lm, RnnLmDev* io);
+    const RnnLmDev& rnn_lm_dev() const { return rnn_dev_; }
+    // k_nlm_advance launches of this model's LM that swept their weights / that only moved state (k2hip_debug.h)
+    void rnn_lm_fusion_work(int64_t* swept, int64_t* idle);
+    // tuning record: milliseconds per k_nlm_advance launch of `rows` rows that all append, input and hidden width H (a layer above the
+    // first: 2 H products per gate), a scattered parent map, pseudo-random operands, `iters` launches between two events
+    void nlm_advance_bench(int rows, int H, int iters, float* ms);
     // Hn hypotheses back to back in `tokens` (hypothesis i at [offsets[i], offsets[i + 1])) scored by the attached LM: one upload (ids,
     // targets, descriptors), the launches of the plan (rnn_lm_plan.h), one download.  token_log_probs (may be null) packed per hypothesis
     // in the caller's order, totals [Hn].  Everything is checked on the host before any device work; a call without a position issues
@@ -549,6 +564,8 @@ class Engine {
     std::array<double, 3> long_ms_{};
     const RnnLm* rnn_host_ = nullptr;
     RnnLmDev rnn_dev_;
+    bool rnn_fusion_ = false;
+    float rnn_fuse_scale_ = 0.f;
     int64_t rnn_calls_ = 0;
     int rnn_last_blocks_ = 0;
     bool rnn_timing_ = false;

@@ -489,6 +489,18 @@ struct RnnLmDev {
     const float* whh_kn[8] = {};
     const float* out_kn = nullptr;
     const float* out_b = nullptr;
+    // shallow fusion (rnn_lm_fuse.hip): per layer [W_ih ; W_hh] concatenated along k and re-laid in panels -- panel jb holds the four
+    // gates of the 8 hidden columns 8 jb .. (column c = gate c / 8 of hidden column 8 jb + c % 8) over all k as [Kc / 4][32][4], Kc =
+    // in rounded up to 32 (zero rows) + H, so a lane's B operand of
+    // four consecutive k is ONE 16-byte load and a wave's load is 1 KiB contiguous; the output matrix once more in torch layout [V][H]
+    // for the GEMM launcher; the start hypothesis' state after sos h0 / c0 [L][H] and its row q0 [V], computed on the device at upload;
+    // work [2]: debug counters of k_nlm_advance launches that swept their weights / that only moved state
+    const float* wcat[8] = {};
+    const float* w_out = nullptr;
+    float* h0 = nullptr;
+    float* c0 = nullptr;
+    float* q0 = nullptr;
+    long long* work = nullptr;
 };
 // x0 [R][E] = emb[ids[row]]; ids in [0, V) (the caller's check)
 void rnn_lm_embed(const Ctx& ctx, const float* emb, const int* ids, float* x0, long long R, int E);
@@ -501,6 +513,46 @@ void rnn_lm_step(const Ctx& ctx, const float* h_prev, const float* whh_kn, const
 // stored; columns >= V never enter the sum
 void rnn_lm_score_rows(const Ctx& ctx, const float* y, const float* out_kn, const float* out_b, const int* target, float* lp, long long R, int H,
                        int V, int Vp);
+// ---- neural LM shallow fusion in the modified beam search (rnn_lm_fuse.hip; semantics: include/k2hip.h "Neural LM shallow fusion") ----
+// One layer of one frame over all M hypothesis slots.  Slot m continues slot par[m] of the other parity and appended tok[m] (-1: nothing).
+// Rows that appended: gates = [x ; h_par[par[m]]] . wcat^T + bias on the matrix pipe (x = emb[tok[m]] when emb is set, else x_rows[m]),
+// the cell in the epilogue against c_par[par[m]], h_out[m] / c_out[m] written; gates never reach memory.  Rows that appended nothing:
+// h_out[m] = h_par[par[m]], c_out[m] = c_par[par[m]], bit for bit.  A workgroup owns 8 hidden columns x four gates and walks every
+// 32-row strip of up to 256 rows against each weight it loads ONCE; strips without an appended row issue no matrix work, and with
+// *live == 0 (null: live) the launch reads no weight at all.  in % 4 == 0, H % 32 == 0; par in [0, M), tok in [-1, V): the caller's.
+struct NlmAdvance {
+    const float* wcat = nullptr;    // the layer's panels (RnnLmDev::wcat)
+    const float* bias = nullptr;    // [4H]
+    const float* emb = nullptr;     // [V][in] (layer 0) or null
+    const float* x_rows = nullptr;  // [M][in] (the layer below's new h) when emb is null
+    const float* h_par = nullptr;   // [M][H] frame t's state of this layer
+    const float* c_par = nullptr;
+    float* h_out = nullptr;         // [M][H] frame t + 1's
+    float* c_out = nullptr;
+    const int* par = nullptr;       // [M]
+    const int* tok = nullptr;       // [M]
+    const int* live = nullptr;      // device flag or null
+    long long* work = nullptr;      // debug counters or null (RnnLmDev::work)
+    int M = 0, in = 0, H = 0;
+};
+void nlm_advance(const Ctx& ctx, const NlmAdvance& a);
+// The LM rows of frame t + 1: q_out[m] = log_softmax(h[m] . W_out^T + b_out) over V for the slots that appended (the GEMM launcher,
+// skipped on the device when *live == 0, then one workgroup per row), q_out[m] = q_par[par[m]] for the others.  Rows are V floats.
+void nlm_rows(const Ctx& ctx, const float* h, const float* w_out, const float* out_b, const float* q_par, float* q_out, const int* par,
+              const int* tok, const int* live, int M, int H, int V);
+// The fused search's view of the LM (BeamArgs::nlm): dev.emb == null: off
+struct BeamNlm {
+    RnnLmDev dev;
+    float scale = 0.f;
+};
+// the start state h0 / c0 and row q0 into every slot of parity 0: h, c [L][M][H], q [M][V]
+void nlm_broadcast(const Ctx& ctx, const RnnLmDev& d, float* h, float* c, float* q, int M);
+// h0 / c0 / q0 of d from h = c = 0 and sos, through the kernels above (once per upload)
+void nlm_start_state(const Ctx& ctx, const RnnLmDev& d);
+// launches of the fused search since the process started (the third counter beside beam_launch_counts)
+void nlm_note_search();
+long long beam_nlm_launch_count();
+
 // One hypothesis of rnn_lm_totals, in sorted order j: its positions, the caller's index and where its token log-probs go
 struct RnnLmHyp {
     int npos = 0, orig = 0;
@@ -727,6 +779,14 @@ struct BeamState {       // device arrays; hypotheses double-buffered by frame p
     BeamLm lm;
     const int* lst_in = nullptr;
     int* lst_out = nullptr;
+    // neural LM shallow fusion (null: none), slot-indexed over M = B K: the hypotheses' next-token log-probs nq [2][M][V] by frame
+    // parity, what the step writes for the LM launches behind it -- npar [M] the slot (of the other parity) each new slot continues,
+    // ntok [M] the token it appended or -1 -- and nflag [Tp]: frame t's "some slot appended" flag
+    const float* nq = nullptr;
+    int* npar = nullptr;
+    int* ntok = nullptr;
+    int* nflag = nullptr;
+    float nscale = 0.f;
 };
 struct BeamArgs {
     const float* enc;    // [B, Tp, J]
@@ -766,6 +826,11 @@ struct BeamArgs {
     BeamLm lm;
     const int* lst_in = nullptr;
     int* lst_out = nullptr;
+    // Neural LM shallow fusion (rnn_lm_fuse.hip; semantics in include/k2hip.h): every hypothesis carries the LSTM state of its token
+    // sequence and the LM's next-token log-probs; a selected candidate that appends a real token v gets
+    // ((sum + hotword bonus) + n-gram term) + fl32(scale q_parent[v]) before the merges.  Offline only, always in the per-frame launch
+    // form; nlm.dev.emb == null: off.
+    BeamNlm nlm;
     // Token log-probs and N-best (semantics in include/k2hip.h).  Both null: nothing is kept beyond the best hypothesis.  nb: the
     // offline search also writes its final hypotheses in pick order; yp_out [B][K][Tp] (resume): the token log-probs of each
     // survivor's suffix, a side block beside rout as st_out is.

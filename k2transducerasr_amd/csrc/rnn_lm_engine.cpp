@@ -52,6 +52,121 @@ void* Engine::rnn_lm_upload(const RnnLm& m, RnnLmDev* out) {
     return base;
 }
 
+// What the fused search needs beyond the rescoring layouts, built when fusion is first switched on for an attached LM: a second
+// allocation that the caller owns -- per layer the panels of rnn_lm_fuse_layout.h, the output matrix in torch layout for the GEMM
+// launcher, the start state h0 / c0 and row q0 (computed here on the device, once), the debug counters.  *io: the attached LM's tables,
+// completed.
+void* Engine::rnn_lm_fusion_upload(const RnnLm& m, RnnLmDev* io) {
+    K2_HIP(hipSetDevice(device_));
+    const int V = m.V, H = m.H, L = m.L;
+    K2_REQUIRE(io && io->emb && io->L == L && io->H == H && io->V == V, "rnn lm fusion: the tables are not those of the attached LM");
+    auto al = [](int64_t n) { return align_up(n, 64); };
+    int64_t total = al((int64_t)V * H) + 2 * al((int64_t)L * H) + al(V) + al(4);
+    for (int k = 0; k < L; k++) total += al(rnn_lm_panel_floats(m, k));
+    float* base = static_cast<float*>(dev_alloc((int64_t)sizeof(float) * total));
+    try {
+        RnnLmDev d = *io;
+        float* p = base;
+        auto room = [&](int64_t n) {
+            float* at = p;
+            p += al(n);
+            return at;
+        };
+        std::vector<float> kn;
+        for (int k = 0; k < L; k++) {
+            kn.resize((size_t)rnn_lm_panel_floats(m, k));
+            rnn_lm_panels(m, k, kn.data());
+            float* at = room((int64_t)kn.size());
+            dev_upload(at, kn.data(), (int64_t)sizeof(float) * (int64_t)kn.size());
+            d.wcat[k] = at;
+        }
+        float* wo = room((int64_t)V * H);
+        dev_upload(wo, m.w_out.data(), (int64_t)sizeof(float) * V * H);
+        d.w_out = wo;
+        d.h0 = room((int64_t)L * H);
+        d.c0 = room((int64_t)L * H);
+        d.q0 = room(V);
+        d.work = reinterpret_cast<long long*>(room(4));
+        K2_HIP(hipMemsetAsync(d.work, 0, 16, stream_));
+        run_sized([&](const Ctx& c) { nlm_start_state(c, d); });
+        K2_HIP(hipStreamSynchronize(stream_));
+        *io = d;
+    } catch (...) {
+        try { dev_free(base); } catch (...) {}
+        throw;
+    }
+    return base;
+}
+
+void Engine::rnn_lm_fusion_work(int64_t* swept, int64_t* idle) {
+    long long w[2] = {0, 0};
+    if (rnn_host_ && rnn_dev_.work) {
+        K2_HIP(hipSetDevice(device_));
+        K2_HIP(hipStreamSynchronize(stream_));
+        K2_HIP(copy_blocking(w, rnn_dev_.work, sizeof w, hipMemcpyDeviceToHost));
+    }
+    if (swept) *swept = w[0];
+    if (idle) *idle = w[1];
+}
+
+void Engine::nlm_advance_bench(int rows, int H, int iters, float* ms) {
+    K2_REQUIRE(rows > 0 && rows <= 4096 && H > 0 && H <= 8192 && H % 32 == 0 && iters > 0 && iters <= 10000 && ms, "nlm_advance_bench: %d rows, hidden_dim %d, %d launches",
+               rows, H, iters);
+    K2_HIP(hipSetDevice(device_));
+    struct Bufs {
+        hipStream_t s;
+        std::vector<void*> p;
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        ~Bufs() {
+            (void)hipStreamSynchronize(s);
+            for (void* q : p) (void)hipFree(q);
+            if (e0) (void)hipEventDestroy(e0);
+            if (e1) (void)hipEventDestroy(e1);
+        }
+        float* take(int64_t n, float scale) {
+            float* q = nullptr;
+            K2_HIP(hipMalloc(&q, sizeof(float) * (size_t)n));
+            p.push_back(q);
+            std::vector<float> h((size_t)n);
+            uint32_t st = 54321u + (uint32_t)p.size();
+            for (auto& v : h) { st = st * 1664525u + 1013904223u; v = (((st >> 8) * (1.0f / 8388608.0f)) - 1.0f) * scale; }
+            K2_HIP(copy_blocking(q, h.data(), sizeof(float) * (size_t)n, hipMemcpyHostToDevice));
+            return q;
+        }
+    } b{stream_, {}};
+    // a layer above the first: x = rows of width H, so the launch sums 2 H products per gate (the rescoring step sums H: its input
+    // products are one GEMM per time block)
+    const float ws = 1.f / sqrtf(2.f * (float)H);
+    float *w = b.take(8LL * H * H, ws), *bias = b.take(4LL * H, 1.f), *x = b.take((int64_t)rows * H, 1.f);
+    float *h0 = b.take((int64_t)rows * H, 1.f), *h1 = b.take((int64_t)rows * H, 1.f), *c0 = b.take((int64_t)rows * H, 1.f), *c1 = b.take((int64_t)rows * H, 1.f);
+    int* idx = reinterpret_cast<int*>(b.take(2LL * rows, 0.f));
+    std::vector<int> hi((size_t)2 * rows);
+    for (int i = 0; i < rows; i++) { hi[(size_t)i] = (i * 7 + 3) % rows; hi[(size_t)rows + i] = 1; }   // a scattered parent map; every row appends
+    K2_HIP(copy_blocking(idx, hi.data(), sizeof(int) * hi.size(), hipMemcpyHostToDevice));
+    K2_HIP(hipEventCreate(&b.e0));
+    K2_HIP(hipEventCreate(&b.e1));
+    Ctx c = make_ctx(false);
+    c.instrument = false;
+    c.stats = nullptr;
+    auto one = [&](int i) {
+        NlmAdvance a;
+        a.wcat = w; a.bias = bias; a.x_rows = x;
+        a.h_par = i & 1 ? h1 : h0; a.c_par = i & 1 ? c1 : c0;
+        a.h_out = i & 1 ? h0 : h1; a.c_out = i & 1 ? c0 : c1;
+        a.par = idx; a.tok = idx + rows;
+        a.M = rows; a.in = H; a.H = H;
+        nlm_advance(c, a);
+    };
+    for (int i = 0; i < 3; i++) one(i);
+    K2_HIP(hipEventRecord(b.e0, stream_));
+    for (int i = 0; i < iters; i++) one(i);
+    K2_HIP(hipEventRecord(b.e1, stream_));
+    K2_HIP(hipEventSynchronize(b.e1));
+    float t = 0.f;
+    K2_HIP(hipEventElapsedTime(&t, b.e0, b.e1));
+    *ms = t / iters;
+}
+
 void Engine::rnn_lm_score_host(const int64_t* tokens, const int64_t* offsets, int Hn, bool with_eos, float* token_log_probs, float* totals) {
     K2_REQUIRE(rnn_host_, "rnn_lm_score: no LM is attached to the model (k2hip_set_rnn_lm)");
     const RnnLmDev& d = rnn_dev_;
