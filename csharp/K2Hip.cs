@@ -122,6 +122,8 @@ namespace K2TransducerAsr.Hip
         [DllImport(Lib)] internal static extern int k2hip_rnn_lm_eos_id(IntPtr lm);
         [DllImport(Lib)] internal static extern int k2hip_rnn_lm_score_host(IntPtr lm, long[] tokens, long[] offsets, int hn, int withEos, float[] tokenLogProbs /* may be null */, float[] totals);
         [DllImport(Lib)] internal static extern int k2hip_set_rnn_lm(IntPtr model, IntPtr lm /* IntPtr.Zero clears */, float scale);
+        // Neural LM shallow fusion in the streaming modified beam search (include/k2hip.h): the LM's state is carried from chunk to chunk
+        [DllImport(Lib)] internal static extern int k2hip_set_rnn_lm_stream_fusion(IntPtr model, int on);
         [DllImport(Lib)] internal static extern int k2hip_rnn_lm_score(IntPtr model, long[] tokens, long[] offsets, int hn, int withEos, float[] tokenLogProbs /* may be null */, float[] totals);
         [DllImport(Lib)] internal static extern int k2hip_offline_stream_get_alternative_lm_score(IntPtr stream, int i, out float lmTotal);
         // streaming: the graph belongs to the stream (IntPtr.Zero detaches; only before the stream's first chunk or after a reset)

@@ -1127,9 +1127,30 @@ int32_t k2hip_offline_stream_get_alternative_lm_score(const k2hip_offline_stream
  * k2hip_offline_stream_get_alternative_lm_score gives 0.
  * Fusion works together with hotwords, the n-gram LM and N-best.  Greedy search, the CTC searches,
  * k2hip_offline_recognizer_get_result, the pipelined submit / wait, every streaming entry and k2hip_offline_recognize_long ignore the
- * switch: a streaming call on a model with fusion on runs the unfused search.
+ * switch: a streaming call on a model with fusion on runs the unfused search (the streaming search has a switch of its own,
+ * k2hip_set_rnn_lm_stream_fusion below).
  * The device is held to a float64 twin within a bound, not bit for bit: the caveat rescoring carries. */
 int32_t k2hip_set_rnn_lm_fusion(k2hip_model_t* model, int32_t on);
+
+/* ---- Neural LM shallow fusion in the streaming modified beam search ------------------------------------------------------------------
+ * (no reference counterpart; DESIGN.md "Neural LM shallow fusion in the streaming search".)
+ * on != 0 switches the mode on; per model, off by default, SEPARATE from k2hip_set_rnn_lm_fusion (which no streaming entry reads).
+ * Fusion is ACTIVE when this switch is on and an LM with scale > 0 is attached (k2hip_set_rnn_lm).  With it off, scale 0 or no LM every
+ * streaming call issues the launches and gives the results of before, bit for bit.
+ * WHERE: k2hip_beam_search_chunk, and k2hip_online_step on streams under modified_beam_search.  Every hypothesis of a stream carries the
+ * LM's state from chunk to chunk (device memory owned by the model, one block per fused stream, taken with the stream's first fused chunk).
+ * INVARIANT: after any chunking a stream holds what the offline fused search above gives over all frames so far -- tokens, timestamps,
+ * the number and order of alternatives, scores: ((sum + hotword bonus) + n-gram term) + fl32(scale * q_parent[token]), then the merges.
+ * No eos term.  Token log-probs stay acoustic.  It works together with per-stream hotwords, the n-gram LM and N-best.
+ * A STREAM KEEPS THE SETTING OF ITS FIRST CHUNK, as it does for the n-gram LM: whether fusion was active, and then the attached LM (each
+ * k2hip_set_rnn_lm call is a new setting, the same LM handle included) and the scale.  A later chunk under another setting is
+ * K2HIP_ERR_INVALID ("reset the stream first"), decided for all streams of the call before any of them changes; so all streams of one
+ * call are fused, or none is.  k2hip_beam_stream_reset / k2hip_online_stream_reset return the stream to the start state and give its
+ * block back.  A call that fails leaves every stream, and every block, as it was; a block that cannot be allocated is K2HIP_ERR_HIP (or
+ * the out-of-memory status) before any device work.
+ * ORDER OF DESTRUCTION: k2hip_beam_stream_destroy and k2hip_beam_stream_reset after k2hip_model_destroy are allowed -- the model's end
+ * frees every block, and a stream then only forgets its own.  (An online stream still has to go before its model, as before.) */
+int32_t k2hip_set_rnn_lm_stream_fusion(k2hip_model_t* model, int32_t on);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

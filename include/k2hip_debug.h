@@ -289,6 +289,18 @@ int32_t k2hip_debug_nlm_advance_bench(k2hip_model_t* model, int32_t rows, int32_
  *   "nlm_rows"     the GEMM launcher + one launch.  ints M, H, V, live; bufs h [M][H], w_out [V][H], out_b [V], q_par [M][V],
  *                  q_out [M][V] (out), par [M], tok [M], flag [1] */
 
+/* ---- neural LM shallow fusion in the streaming search (k2hip.h; tests/test_rnn_lm_stream_fusion_gpu.py) ---- */
+/* chunk_calls: fused chunk calls (k2hip_beam_search_chunk / k2hip_online_step ticks) enqueued since the process started -- they move
+ * neither k2hip_debug_beam_launch_counts nor the counters of k2hip_debug_rnn_lm_fusion_stats; live_blocks: state blocks this model's
+ * streams hold; pool_bytes: device memory of the model's block pool (held and spare blocks).  Each may be NULL. */
+int32_t k2hip_debug_rnn_lm_stream_fusion_stats(k2hip_model_t* model, int64_t* chunk_calls, int64_t* live_blocks, int64_t* pool_bytes);
+/* k2hip_debug_op_run ops (the block layout: csrc/rnn_lm_stream_pool.h NlmStreamLayout -- per half states [K][L][2][H], rows [K][V],
+ * rounded up to 4 floats; a block is two halves):
+ *   "nlm_load_streams"   ints B, K, L, H, V; bufs blocks [B][block], cur [B] (int32: the half that is read, -1: a stream without a state),
+ *                        nh [B] (int32: live slots), h0 [L][H], c0 [L][H], q0 [V], h [L][B K][H] (out), c (out), q [B K][V] (out),
+ *                        io [B] x 16 bytes (scratch: the block-pointer table)
+ *   "nlm_store_streams"  ints B, K, L, H, V; bufs blocks (in / out), cur [B] (the half NOT written; -1: half 0 is written), h, c, q, io */
+
 /* ---- GEMM tuning ------------------------------------------------------------------------------- */
 /* time `iters` launches of a shape / configuration on pseudo-random operands (tools/gemm_lab.py, gemm_tune.py) */
 int32_t k2hip_debug_gemm(k2hip_model_t* model, int32_t M, int32_t N, int32_t K, int32_t act, int32_t with_res, int32_t cfg,

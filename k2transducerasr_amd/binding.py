@@ -297,6 +297,8 @@ def _bind_rnn_lm(L):
     L.k2hip_set_rnn_lm_fusion.argtypes = [vp, C.c_int32]
     L.k2hip_debug_rnn_lm_fusion_stats.argtypes = [vp, lp, lp, lp]
     L.k2hip_debug_nlm_advance_bench.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, fp]
+    L.k2hip_set_rnn_lm_stream_fusion.argtypes = [vp, C.c_int32]
+    L.k2hip_debug_rnn_lm_stream_fusion_stats.argtypes = [vp, lp, lp, lp]
     L._rnn_lm_bound = True
 
 
@@ -1027,6 +1029,21 @@ class Model:
         n, s, i = C.c_int64(), C.c_int64(), C.c_int64()
         self._chk(self._L.k2hip_debug_rnn_lm_fusion_stats(self._h, C.byref(n), C.byref(s), C.byref(i)))
         return dict(searches=n.value, swept=s.value, idle=i.value)
+
+    def set_rnn_lm_stream_fusion(self, on: bool = True):
+        """k2hip_set_rnn_lm_stream_fusion: with an LM of scale > 0 attached, the STREAMING modified beam search (BeamStream chunks,
+        OnlineRecognizer under modified_beam_search) adds the LM's term during the search and carries every hypothesis' LM state from
+        chunk to chunk (include/k2hip.h "Neural LM shallow fusion in the streaming modified beam search").  A switch of its own: the
+        offline one (set_rnn_lm_fusion) does not reach streaming entries."""
+        _bind_rnn_lm(self._L)
+        self._chk(self._L.k2hip_set_rnn_lm_stream_fusion(self._h, int(bool(on))))
+
+    def rnn_lm_stream_fusion_stats(self) -> dict:
+        """fused chunk calls enqueued by the process; state blocks this model's streams hold; bytes of the model's block pool"""
+        _bind_rnn_lm(self._L)
+        n, b, p = C.c_int64(), C.c_int64(), C.c_int64()
+        self._chk(self._L.k2hip_debug_rnn_lm_stream_fusion_stats(self._h, C.byref(n), C.byref(b), C.byref(p)))
+        return dict(chunk_calls=n.value, live_blocks=b.value, pool_bytes=p.value)
 
     def nlm_advance_bench(self, rows: int, hidden_dim: int, iters: int = 200) -> float:
         """milliseconds per k_nlm_advance launch (k2hip_debug_nlm_advance_bench)"""
@@ -2097,15 +2114,25 @@ class CtcPrefixStream:
 class OnlineRecognizer:
     """OnlineRecognizer.cs:11-84 on the HIP backend; decoding_method "greedy_search" (the reference's) or "modified_beam_search"
     (hypotheses carried from chunk to chunk: include/k2hip.h).  ngram_lm: an NgramLm fused with weight ngram_lm_scale
-    under modified_beam_search (every hypothesis carries its LM state across the chunk boundary)."""
+    under modified_beam_search (every hypothesis carries its LM state across the chunk boundary).  rnn_lm with rnn_lm_fusion=True:
+    an RnnLm fused with weight rnn_lm_scale under modified_beam_search, its LSTM state carried from chunk to chunk
+    (Model.set_rnn_lm_stream_fusion); without rnn_lm_fusion the LM is attached and the streaming search ignores it.  nbest > 1: the
+    streams keep that many alternatives."""
 
     def __init__(self, weights_path: str, device: int = 0, decoding_method: str = "greedy_search", beam: int = 4,
-                 ngram_lm: Optional["NgramLm"] = None, ngram_lm_scale: float = 0.3):
+                 ngram_lm: Optional["NgramLm"] = None, ngram_lm_scale: float = 0.3, rnn_lm: Optional["RnnLm"] = None,
+                 rnn_lm_scale: float = 0.5, rnn_lm_fusion: bool = False, nbest: int = 1):
         self.model = Model(weights_path, device)
         _bind_online(self.model._L)
         self.model.set_decoding_method(decoding_method, beam)
+        if nbest != 1:
+            self.model.set_nbest(nbest)
         if ngram_lm is not None:
             self.model.set_ngram_lm(ngram_lm, ngram_lm_scale)
+        if rnn_lm is not None:
+            self.model.set_rnn_lm(rnn_lm, rnn_lm_scale)
+        if rnn_lm_fusion:
+            self.model.set_rnn_lm_stream_fusion(True)
         a, b, c = C.c_int32(), C.c_int32(), C.c_int32()
         self.model._chk(self.model._L.k2hip_online_chunk_info(self.model.handle, C.byref(a), C.byref(b), C.byref(c)))
         self.chunk_length, self.shift_length, self.frames_per_chunk = a.value, b.value, c.value

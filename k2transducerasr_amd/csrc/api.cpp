@@ -128,6 +128,12 @@ struct k2hip_model {
     void* rnn_fuse_dev = nullptr;   // the fused search's layouts of the same LM: made when fusion is on, null otherwise
     float rnn_scale = 0.f;
     bool rnn_fusion = false;   // k2hip_set_rnn_lm_fusion: the LM's term is added during the offline modified beam search instead
+    // k2hip_set_rnn_lm_stream_fusion: ... and during the streaming one, the hypotheses' LM state carried from chunk to chunk in device
+    // blocks of nlm_pool (rnn_lm_stream_pool.h; made on first use, shared with the streams that hold a block, emptied with the model).
+    // rnn_serial numbers the settings of k2hip_set_rnn_lm: what a fused stream notes with its first chunk.  Under the engine's lock.
+    bool rnn_stream_fusion = false;
+    uint64_t rnn_serial = 0;
+    std::shared_ptr<NlmStreamPool> nlm_pool;
     // k2hip_set_nbest: 1 = off (the engine keeps nothing beyond the best hypothesis), n > 1 = alternatives and token log-probs are kept
     std::atomic<int> nbest{1};
     // the graphs attached to this model's streams (HwResident), by serial number; hw_uploads counts the uploads (k2hip_debug.h)
@@ -182,6 +188,13 @@ struct k2hip_model {
             } catch (...) {
             }
         }
+        if (nlm_pool) {   // (streams that still hold a block only forget it from now on)
+            try {
+                engine.synchronize();
+            } catch (...) {
+            }
+            nlm_pool->shutdown();
+        }
         if (rnn_dev || rnn_fuse_dev) {
             try {
                 engine.synchronize();
@@ -190,6 +203,51 @@ struct k2hip_model {
             } catch (...) {
             }
         }
+    }
+};
+
+// Streaming neural LM shallow fusion: what a stream under the modified beam search notes with its first chunk (whether fusion was
+// active, and then the LM's serial and the scale) and the device block that carries its hypotheses' LM state between chunks
+struct NlmCarry {
+    bool active = false;
+    uint64_t serial = 0;
+    float scale = 0.f;
+    NlmStreamPool::Handle block;
+};
+// One chunk call's view of the setting (read under the engine's lock), the rule "a stream keeps the setting of its first chunk", the
+// block table of the call and the flip after success
+struct NlmStreamCall {
+    bool active = false;
+    uint64_t serial = 0;
+    float scale = 0.f;
+    int L = 0, H = 0, V = 0;
+    std::vector<NlmStreamIO> table;
+    std::vector<NlmCarry*> taken;   // blocks taken by this call: given back if it fails
+    bool done = false;
+    void read(const k2hip_model* m);
+    void check(const NlmCarry* c, long long frames, const char* who, int i) const {
+        const bool was = c && c->active;
+        K2_REQUIRE(frames == 0 || (was == active && (!active || (c->serial == serial && c->scale == scale && c->block.carries(serial)))),
+                   "%s: stream %d has searched %lld frames with another neural LM fusion setting (k2hip_set_rnn_lm_stream_fusion or "
+                   "k2hip_set_rnn_lm changed it) and its hypotheses carry that LM's state -- reset the stream first", who, i, frames);
+    }
+    // a stream's first chunk: the start state under this call's setting
+    void begin(std::unique_ptr<NlmCarry>& c) const {
+        if (!c) {
+            if (!active) return;
+            c.reset(new NlmCarry());
+        }
+        c->block.release();
+        c->active = active;
+        c->serial = active ? serial : 0;
+        c->scale = active ? scale : 0.f;
+    }
+    // under the engine's lock, before the launch: stream i of the call's B gets its block (first fused chunk) and its table entry
+    void stage(k2hip_model* m, int i, int B, int K, NlmCarry& c);
+    void flip(NlmCarry& c) const { c.block.flip(); }
+    ~NlmStreamCall() {
+        if (!done)
+            for (NlmCarry* c : taken) c->block.release();
     }
 };
 
@@ -249,6 +307,8 @@ struct k2hip_online_stream {
     int method = -1;
     // modified_beam_search: the hypotheses carried between chunks; Tokens / Timestamps / Hyp are its best hypothesis
     std::unique_ptr<BeamHistory> beam;
+    // ... and, under the streaming neural LM fusion, their LM state (a reset returns the block)
+    std::unique_ptr<NlmCarry> nlm;
     // the stream's hotword graph (k2hip_online_stream_set_hotwords) or null; kept by a reset
     std::shared_ptr<HwResident> hw;
     // a CTC model's stream under the carried prefix search (k2hip_online_stream_set_ctc_prefix_beam; 0 = off: the per-chunk collapse);
@@ -273,7 +333,30 @@ struct k2hip_beam_stream {
     k2hip_model* model;
     BeamHistory hist;
     std::shared_ptr<HwResident> hw;   // the stream's hotword graph (k2hip_beam_stream_set_hotwords) or null
+    std::unique_ptr<NlmCarry> nlm;    // streaming neural LM fusion: the noted setting and the state block, or null
 };
+
+void NlmStreamCall::read(const k2hip_model* m) {
+    active = m->engine.rnn_lm_stream_fusion_active();
+    serial = m->rnn_serial;
+    scale = m->rnn_scale;
+    if (active) {
+        L = m->rnn_lm->L; H = m->rnn_lm->H; V = m->rnn_lm->V;
+    }
+}
+void NlmStreamCall::stage(k2hip_model* m, int i, int B, int K, NlmCarry& c) {
+    if (table.empty()) table.resize((size_t)B);
+    if (!c.block.held()) {
+        if (!m->nlm_pool) {
+            Engine* e = &m->engine;
+            m->nlm_pool = std::make_shared<NlmStreamPool>([e](size_t n) { return e->dev_alloc((int64_t)n); }, [e](void* p) { e->dev_free(p); });
+        }
+        NlmStreamPool::take(m->nlm_pool, c.block, NlmStreamLayout{K, L, H, V}, serial);
+        taken.push_back(&c);
+    }
+    table[(size_t)i].rd = c.block.read_half();
+    table[(size_t)i].wr = c.block.write_half();
+}
 
 // operator level of the streaming CTC prefix beam search: one stream's live prefixes (k2hip_ctc_prefix_beam_search_chunk)
 struct k2hip_ctc_prefix_stream {
@@ -2142,6 +2225,7 @@ int32_t k2hip_online_step(k2hip_model_t* model, k2hip_online_stream_t* const* st
         uint64_t lm_serial = 0;   // the n-gram LM this tick's beam search runs with (0 = none) and its start state
         int lm_start = 0;
         int K = 0;   // the search of this tick: 0 = greedy (and a CTC model's own search), K = modified beam search with beam K
+        NlmStreamCall nlm;   // the neural LM fusion setting this tick's beam search runs with
         if (!c.ctc) {
             EngineLock lk(e);
             K = e.beam();
@@ -2152,6 +2236,7 @@ int32_t k2hip_online_step(k2hip_model_t* model, k2hip_online_stream_t* const* st
                        "hotwords (k2hip_set_hotwords(model, NULL)) or decode with greedy_search");
             lm_serial = K > 0 ? model->lm_serial : 0;
             lm_start = model->lm_start;
+            if (K > 0) nlm.read(model);
         }
         std::vector<int> idx;
         int CK = 0;   // a CTC model's streams under the carried prefix search: their beam (every stream of the list carries the same setting)
@@ -2195,6 +2280,7 @@ int32_t k2hip_online_step(k2hip_model_t* model, k2hip_online_stream_t* const* st
             K2_REQUIRE(!s->beam || s->beam->frames() == 0 || s->beam->lm_serial() == lm_serial,
                        "online step: stream %d has decoded %lld frames with another n-gram LM setting (k2hip_set_ngram_lm changed or cleared "
                        "it) and its hypotheses carry that LM's states -- reset the stream first", idx[r], s->beam->frames());
+            nlm.check(s->nlm.get(), s->beam ? s->beam->frames() : 0, "online step", idx[r]);
         }
         // the new frames' host copy is collected after the step (one wait for the device per tick); whatever way this call ends -- an
         // allocation failure below included -- the outstanding download is collected before the streams' Speech can move
@@ -2260,7 +2346,10 @@ int32_t k2hip_online_step(k2hip_model_t* model, k2hip_online_stream_t* const* st
                     s->beam.reset(new BeamHistory(K, K2HIP_BLANK_ID));
                     if (s->hw) s->beam->set_pending(s->hw->pending);
                 }
-                if (s->beam->frames() == 0) s->beam->begin_lm(lm_serial, with_lm ? lm_start : 0);
+                if (s->beam->frames() == 0) {
+                    s->beam->begin_lm(lm_serial, with_lm ? lm_start : 0);
+                    nlm.begin(s->nlm);
+                }
                 s->beam->fill_in(bin.data() + (size_t)r * RL.in_ints(), Tp);
                 any_hw = any_hw || s->hw;
             }
@@ -2316,6 +2405,23 @@ int32_t k2hip_online_step(k2hip_model_t* model, k2hip_online_stream_t* const* st
                 ypb.resize((size_t)R * K * Tp);
                 e.set_beam_yp_out(ypb.data());
             }
+            struct NlmOut {
+                Engine& e;
+                ~NlmOut() { e.set_beam_nlm_io(nullptr); }
+            } nlm_guard{e};
+            if (K > 0 && (model->rnn_serial != nlm.serial || e.rnn_lm_stream_fusion_active() != nlm.active)) {
+                lm_raced = true;
+                failf(K2HIP_ERR_INVALID, "online step: the neural LM fusion setting changed while this step was being prepared; call again");
+            }
+            if (nlm.active) {   // the streams' state blocks (taken at a stream's first fused chunk), staged with the in blocks
+                try {
+                    for (int r = 0; r < R; r++) nlm.stage(model, r, R, K, *streams[idx[r]]->nlm);
+                } catch (...) {
+                    lm_raced = true;   // (no device work has been enqueued: the streams are as they were)
+                    throw;
+                }
+                e.set_beam_nlm_io(nlm.table.data());
+            }
             if (K > 0 && any_hw)
                 e.online_step_beam_hw(slots.data(), chunks.data(), plens.data(), nch.data(), R, K, bin.data(), bout.data(),
                                       Engine::BeamHwIO{graphs.data(), st_in.data(), st_out.data(), with_lm}, all_mirrored ? heads.data() : nullptr);
@@ -2350,6 +2456,7 @@ int32_t k2hip_online_step(k2hip_model_t* model, k2hip_online_stream_t* const* st
             throw;   // (fb's destructor collects the frames; the streams are poisoned either way)
         }
         fb.finish();   // the step's token download has synchronised the stream: copies only
+        nlm.done = true;
         // RemoveChunk (:102-117) only after success
         std::vector<k2hip_online_stream*> remirror;
         for (int r = 0; r < R; r++) {
@@ -2368,6 +2475,7 @@ int32_t k2hip_online_step(k2hip_model_t* model, k2hip_online_stream_t* const* st
                 // the best hypothesis replaces the result (it may revise earlier tokens): n_new_tokens = change of its length
                 const int64_t before = (int64_t)s->beam->tokens().size();
                 const float* yp = ypb.empty() ? nullptr : ypb.data() + (size_t)r * K * Tp;
+                if (nlm.active) nlm.flip(*s->nlm);
                 if (any_hw) s->beam->apply_out_states(bout.data() + (size_t)r * RL.out_ints(), Tp, st_out.data() + (size_t)r * K, yp,
                                                       with_lm ? st_out.data() + (size_t)(R + r) * K : nullptr);
                 else s->beam->apply_out(bout.data() + (size_t)r * RL.out_ints(), Tp, yp);
@@ -2536,6 +2644,7 @@ int32_t k2hip_beam_stream_reset(k2hip_beam_stream_t* s) {
     return guard([&] {
         NEED(s);
         s->hist.reset();   // (an attached hotword graph stays; every hypothesis is back at its root)
+        s->nlm.reset();    // (the LM state block goes back to the model's pool, or is forgotten when the model is gone)
     });
 }
 int32_t k2hip_beam_stream_set_hotwords(k2hip_beam_stream_t* s, const k2hip_hotwords_t* hw) {
@@ -2553,12 +2662,14 @@ int32_t k2hip_beam_search_chunk(k2hip_model_t* model, k2hip_beam_stream_t* const
         K2_REQUIRE(B > 0 && Tc >= 1, "beam search chunk: bad shape B=%d Tc=%d", B, Tc);
         uint64_t lm_serial = 0;   // the n-gram LM this call runs with (0 = none) and its start state
         int lm_start = 0;
+        NlmStreamCall nlm;        // the neural LM fusion setting this call runs with
         {
             EngineLock lk(model->engine);
             K2_REQUIRE(!model->engine.has_hotwords(), "beam search chunk: hotword biasing covers the offline modified beam search only, not the "
                                                       "streaming one -- clear the hotwords (k2hip_set_hotwords(model, NULL)) first");
             lm_serial = model->lm_serial;
             lm_start = model->lm_start;
+            nlm.read(model);
         }
         std::vector<const k2hip_beam_stream*> seen(streams, streams + B);
         for (int b = 0; b < B; b++) {
@@ -2576,8 +2687,12 @@ int32_t k2hip_beam_search_chunk(k2hip_model_t* model, k2hip_beam_stream_t* const
             K2_REQUIRE(streams[b]->hist.frames() == 0 || streams[b]->hist.lm_serial() == lm_serial,
                        "beam search chunk: stream %d has searched %lld frames with another n-gram LM setting (k2hip_set_ngram_lm changed or "
                        "cleared it) and its hypotheses carry that LM's states -- reset the stream first", b, streams[b]->hist.frames());
+        for (int b = 0; b < B; b++) nlm.check(streams[b]->nlm.get(), streams[b]->hist.frames(), "beam search chunk", b);
         for (int b = 0; b < B; b++)
-            if (streams[b]->hist.frames() == 0) streams[b]->hist.begin_lm(lm_serial, with_lm ? lm_start : 0);
+            if (streams[b]->hist.frames() == 0) {
+                streams[b]->hist.begin_lm(lm_serial, with_lm ? lm_start : 0);
+                nlm.begin(streams[b]->nlm);
+            }
         const BeamResumeLayout L{K, Tc};
         std::vector<int> bin((size_t)B * L.in_ints()), bout((size_t)B * L.out_ints());
         for (int b = 0; b < B; b++) streams[b]->hist.fill_in(bin.data() + (size_t)b * L.in_ints(), Tc);
@@ -2611,11 +2726,23 @@ int32_t k2hip_beam_search_chunk(k2hip_model_t* model, k2hip_beam_stream_t* const
                 ypb.resize((size_t)B * K * Tc);
                 model->engine.set_beam_yp_out(ypb.data());
             }
+            struct NlmOut {
+                Engine& e;
+                ~NlmOut() { e.set_beam_nlm_io(nullptr); }
+            } nlm_guard{model->engine};
+            K2_REQUIRE(model->rnn_serial == nlm.serial && model->engine.rnn_lm_stream_fusion_active() == nlm.active,
+                       "beam search chunk: the neural LM fusion setting changed while this call was being prepared; call again");
+            if (nlm.active) {   // the streams' state blocks (taken at a stream's first fused chunk), staged with the in blocks
+                for (int b = 0; b < B; b++) nlm.stage(model, b, B, K, *streams[b]->nlm);
+                model->engine.set_beam_nlm_io(nlm.table.data());
+            }
             if (any_hw) model->engine.beam_chunk_host_hw(enc_out, B, Tc, K, bin.data(), bout.data(), Engine::BeamHwIO{graphs.data(), st_in.data(), st_out.data(), with_lm});
             else model->engine.beam_chunk_host(enc_out, B, Tc, K, bin.data(), bout.data());
         }
-        // (only after success: a failed call leaves every stream as it was)
+        // (only after success: a failed call leaves every stream as it was -- the LM state blocks' halves flip here too)
+        nlm.done = true;
         for (int b = 0; b < B; b++) {
+            if (nlm.active) nlm.flip(*streams[b]->nlm);
             const float* yp = ypb.empty() ? nullptr : ypb.data() + (size_t)b * K * Tc;
             if (any_hw) streams[b]->hist.apply_out_states(bout.data() + (size_t)b * L.out_ints(), Tc, st_out.data() + (size_t)b * K, yp,
                                                           with_lm ? st_out.data() + (size_t)(B + b) * K : nullptr);
@@ -3648,7 +3775,7 @@ int32_t k2hip_set_rnn_lm(k2hip_model_t* model, const k2hip_rnn_lm_t* lm, float s
         RnnLmDev tables;
         void* fuse = nullptr;
         if (lm) dev = e.rnn_lm_upload(*lm->lm, &tables);   // (a failed upload leaves the setting as it was)
-        if (lm && model->rnn_fusion) {                     // (a model that only rescores never pays for the fused layouts)
+        if (lm && (model->rnn_fusion || model->rnn_stream_fusion)) {   // (a model that only rescores never pays for the fused layouts)
             try {
                 fuse = e.rnn_lm_fusion_upload(*lm->lm, &tables);
             } catch (...) {
@@ -3661,8 +3788,10 @@ int32_t k2hip_set_rnn_lm(k2hip_model_t* model, const k2hip_rnn_lm_t* lm, float s
         model->rnn_fuse_dev = fuse;
         model->rnn_lm = lm ? lm->lm : nullptr;
         model->rnn_scale = lm ? scale : 0.f;
+        model->rnn_serial++;   // (streams that carry the replaced LM's state refuse their next chunk until they are reset)
         e.set_rnn_lm(model->rnn_lm.get(), tables);
         e.set_rnn_lm_fusion(model->rnn_fusion, model->rnn_scale);
+        e.set_rnn_lm_stream_fusion(model->rnn_stream_fusion);
         if (old || old_fuse) {
             e.synchronize();
             if (old) e.dev_free(old);
@@ -3683,6 +3812,30 @@ int32_t k2hip_set_rnn_lm_fusion(k2hip_model_t* model, int32_t on) {
         }
         model->rnn_fusion = on != 0;
         e.set_rnn_lm_fusion(model->rnn_fusion, model->rnn_scale);
+    });
+}
+int32_t k2hip_set_rnn_lm_stream_fusion(k2hip_model_t* model, int32_t on) {
+    return guard([&] {
+        NEED(model);
+        Engine& e = model->engine;
+        EngineLock lk(e);
+        if (on && model->rnn_lm && !model->rnn_fuse_dev) {   // the fused layouts of the attached LM, on first use
+            RnnLmDev tables = e.rnn_lm_dev();
+            model->rnn_fuse_dev = e.rnn_lm_fusion_upload(*model->rnn_lm, &tables);
+            e.set_rnn_lm(model->rnn_lm.get(), tables);
+        }
+        model->rnn_stream_fusion = on != 0;
+        e.set_rnn_lm_stream_fusion(model->rnn_stream_fusion);
+    });
+}
+int32_t k2hip_debug_rnn_lm_stream_fusion_stats(k2hip_model_t* model, int64_t* chunk_calls, int64_t* live_blocks, int64_t* pool_bytes) {
+    return guard([&] {
+        NEED(model);
+        EngineLock lk(model->engine);
+        const NlmStreamPool::Stats st = model->nlm_pool ? model->nlm_pool->stats() : NlmStreamPool::Stats{};
+        if (chunk_calls) *chunk_calls = beam_nlm_stream_launch_count();
+        if (live_blocks) *live_blocks = st.live;
+        if (pool_bytes) *pool_bytes = st.bytes;
     });
 }
 int32_t k2hip_rnn_lm_score(k2hip_model_t* model, const int64_t* tokens, const int64_t* offsets, int32_t Hn, int32_t with_eos,

@@ -23,7 +23,8 @@
 // N-gram LM shallow fusion (BeamArgs::lm; resumed: lst_in / lst_out beside st_in / st_out): every hypothesis also carries the state of the LM's back-off automaton; the
 // selected candidates' walks (beam_lm_walk, a wave per candidate) run beside the pair comparisons, before the barrier in front of the
 // merge section, which reads term and next state from LDS.  It lives in the HW instantiations behind a null check, as hw_bonus does.
-// Neural LM shallow fusion (BeamArgs::nlm; rnn_lm_fuse.hip): offline and in the per-frame launch form only.  The NLM instantiation of the
+// Neural LM shallow fusion (BeamArgs::nlm; rnn_lm_fuse.hip): in the per-frame launch form only, offline and resumed (the streams' LM
+// state then lives in device blocks between the calls: BeamArgs::nlm_io).  The NLM instantiation of the
 // step reads the parent's row of the LM's log-probs for a selected real token, adds the scaled term after the n-gram term, and leaves
 // for the LM launches behind it each new slot's parent slot and appended token and the frame's "something appended" flag.
 #include <type_traits>
@@ -975,9 +976,10 @@ void beam_search(const Ctx& ctx, const DecJoinW& w, const BeamArgs& a) {
     // neural LM shallow fusion: the biased instantiation with the neural term, always in the per-frame launch form
     const bool nlm = a.nlm.dev.emb != nullptr;
     const bool hw = a.hw_next != nullptr || a.hw_streams != nullptr || a.lm.states != nullptr || nlm;
-    K2_REQUIRE(!nlm || (!a.rin && a.nlm.scale > 0.f && a.nlm.dev.V == w.V && a.nlm.dev.L >= 1 && a.nlm.dev.L <= 8 && a.nlm.dev.w_out && a.nlm.dev.out_b &&
+    K2_REQUIRE(!nlm || (a.nlm.scale > 0.f && a.nlm.dev.V == w.V && a.nlm.dev.L >= 1 && a.nlm.dev.L <= 8 && a.nlm.dev.w_out && a.nlm.dev.out_b &&
                         a.nlm.dev.h0 && a.nlm.dev.c0 && a.nlm.dev.q0),
-               "beam search: neural LM fusion belongs to the offline search and needs a complete LM over the model's %d tokens and a scale > 0", w.V);
+               "beam search: neural LM fusion needs a complete LM over the model's %d tokens and a scale > 0", w.V);
+    K2_REQUIRE(!nlm || ctx.dry || (a.rin != nullptr) == (a.nlm_io != nullptr), "beam search: neural LM fusion: the resumed search, and only it, takes the streams' state blocks");
     for (int k = 0; nlm && k < a.nlm.dev.L; k++) K2_REQUIRE(a.nlm.dev.wcat[k] && a.nlm.dev.bias[k], "beam search: neural LM fusion: layer %d has no weights", k);
     K2_REQUIRE(!a.lm.states || (a.lm.arc_tok && a.lm.arc_lp && a.lm.arc_next && a.lm.uni_lp && a.lm.uni_next), "beam search: incomplete n-gram LM tables");
     K2_REQUIRE(!(a.lm.states && a.rin) || (a.lst_in && a.lst_out), "beam search: the resumed search with an n-gram LM needs its LM state blocks");
@@ -993,7 +995,8 @@ void beam_search(const Ctx& ctx, const DecJoinW& w, const BeamArgs& a) {
                "beam search: incomplete N-best outputs (nbest %d, range [1,%d])", a.nb.nbest, kMaxBeam);
     K2_REQUIRE(!a.yp_out || a.rin, "beam search: the token log-prob side block belongs to the resumed search");
     if (!ctx.dry) {
-        if (nlm) nlm_note_search();
+        if (nlm && a.rin) nlm_note_stream_search();
+        else if (nlm) nlm_note_search();
         else g_launches[hw ? 1 : 0]++;
     }
     Arena& ar = *ctx.arena;
@@ -1101,7 +1104,9 @@ void beam_search(const Ctx& ctx, const DecJoinW& w, const BeamArgs& a) {
         s.nflag = ar.take<int>(a.Tp);
         s.nscale = a.nlm.scale;
         if (!ctx.dry) K2_HIP(hipMemsetAsync(s.nflag, 0, sizeof(int) * (size_t)a.Tp, ctx.stream));
-        nlm_broadcast(ctx, nd, nh, nc, nq, M);
+        // (the resumed form: the streams' carried blocks, the in blocks' first int naming the live slots)
+        if (a.rin) nlm_load_streams(ctx, nd, a.nlm_io, a.rin, BeamResumeLayout{K, a.Tp}.in_ints(), nh, nc, nq, B, K);
+        else nlm_broadcast(ctx, nd, nh, nc, nq, M);
     }
     float* hbuf = ar.take<float>((int64_t)M * w.DD);
     float* act = ar.take<float>((int64_t)M * w.J);
@@ -1131,7 +1136,7 @@ void beam_search(const Ctx& ctx, const DecJoinW& w, const BeamArgs& a) {
             else hipLaunchKernelGGL(k_beam_step<false>, dim3(B), dim3(BT), 0, ctx.stream, s, logits, w.V, t, t & 1, B, a.trace, a.Tp);
             K2_HIP(hipGetLastError());
         }
-        if (nlm && t + 1 < a.Tp) {
+        if (nlm && (a.rin || t + 1 < a.Tp)) {   // (resumed: behind the last frame too -- the next chunk needs the survivors' state)
             // the LM behind the step: one launch per layer over all slots (state of parity t & 1 gathered through npar into the other
             // parity), then the rows; on a frame in which no slot appended a token they only move state and rows
             const int cur = t & 1, nxt = cur ^ 1;
@@ -1142,13 +1147,17 @@ void beam_search(const Ctx& ctx, const DecJoinW& w, const BeamArgs& a) {
                 v.x_rows = k == 0 ? nullptr : nh + nxt * nst + (int64_t)(k - 1) * M * nd.H;
                 v.h_par = nh + cur * nst + (int64_t)k * M * nd.H; v.c_par = nc + cur * nst + (int64_t)k * M * nd.H;
                 v.h_out = nh + nxt * nst + (int64_t)k * M * nd.H; v.c_out = nc + nxt * nst + (int64_t)k * M * nd.H;
-                v.par = s.npar; v.tok = s.ntok; v.live = s.nflag + t; v.work = nd.work;
+                v.par = s.npar; v.tok = s.ntok; v.live = s.nflag + t; v.work = a.rin ? nullptr : nd.work;   // (the counters are the offline search's)
                 v.M = M; v.in = k == 0 ? nd.E : nd.H; v.H = nd.H;
                 nlm_advance(ctx, v);
             }
             nlm_rows(ctx, nh + nxt * nst + (int64_t)(nd.L - 1) * M * nd.H, nd.w_out, nd.out_b, nq + (int64_t)cur * M * nd.V, nq + (int64_t)nxt * M * nd.V,
                      s.npar, s.ntok, s.nflag + t, M, nd.H, nd.V);
         }
+    }
+    if (nlm && a.rin) {   // slot k of the final parity into slot k of the stream's other half (beam_resume_write keeps the slots' order)
+        const int fin = a.Tp & 1;
+        nlm_store_streams(ctx, nd, a.nlm_io, nh + fin * nst, nc + fin * nst, nq + (int64_t)fin * M * nd.V, B, K);
     }
     if (!ctx.dry) {
         if (a.rin && hw) hipLaunchKernelGGL(k_beam_resume_final<true>, dim3(B), dim3(256), 0, ctx.stream, s, a.Tp & 1, B, a.rout);

@@ -947,7 +947,7 @@ Engine::SearchExtras Engine::beam_device(const Ctx& c, const float* enc, int B, 
 
 // modified beam search resumed from saved hypotheses (streaming chunk; BeamResumeLayout{K, Tp} blocks on the device)
 void Engine::beam_resume_device(const Ctx& c, const float* enc, int B, int Tp, int K, const int* d_in, int* d_out, int* d_overflow,
-                                const BeamHwIO* hw) {
+                                const BeamHwIO* hw, const NlmStreamIO* d_nlm) {
     BeamArgs a;
     a.enc = enc; a.out_w = model_->w("joiner.output_linear.weight");
     a.dproj_w = model_->w("joiner.decoder_proj.weight");
@@ -962,6 +962,11 @@ void Engine::beam_resume_device(const Ctx& c, const float* enc, int B, int Tp, i
             a.lst_in = hw->st_in + (size_t)B * K;
             a.lst_out = hw->st_out + (size_t)B * K;
         }
+    }
+    if (d_nlm) {   // neural LM shallow fusion carried across chunks: the streams' state blocks (staged with the in blocks)
+        a.nlm.dev = rnn_dev_;
+        a.nlm.scale = rnn_fuse_scale_;
+        a.nlm_io = d_nlm;
     }
     d_yp_ = nullptr;
     if (yp_host_) {
@@ -993,8 +998,12 @@ void Engine::beam_chunk_impl(const float* enc, int B, int Tp, int K, const int* 
     const int64_t nb_enc = (int64_t)sizeof(float) * B * Tp * cf.J, nb_in = (int64_t)sizeof(int) * B * L.in_ints(),
                   nb_out = (int64_t)sizeof(int) * B * L.out_ints();
     const int64_t nb_st = hw ? (int64_t)sizeof(int) * B * K * (hw->lm ? 2 : 1) : 0, nb_g = hw ? (int64_t)sizeof(BeamHwStream) * B : 0;
+    // (an active streaming neural LM fusion: the streams' block-pointer table rides behind the graphs)
+    const NlmStreamIO* nlm_io = nlm_io_host_;
+    K2_REQUIRE(!nlm_io || rnn_lm_stream_fusion_active(), "beam chunk: state blocks without an active streaming neural LM fusion");
+    const int64_t nb_nl = nlm_io ? (int64_t)sizeof(NlmStreamIO) * B : 0;
     const int64_t o_in = align_up(nb_enc, 16), o_st = align_up(o_in + nb_in, 16), o_g = align_up(o_st + nb_st, 16),
-                  o_ovf = align_up(o_g + nb_g, 16), in_bytes = o_ovf + 16;
+                  o_nl = align_up(o_g + nb_g, 16), o_ovf = align_up(o_nl + nb_nl, 16), in_bytes = o_ovf + 16;
     K2_HIP(hipSetDevice(device_));
     char* stage = static_cast<char*>(pinned_in(in_bytes));
     memcpy(stage, enc, (size_t)nb_enc);
@@ -1003,6 +1012,7 @@ void Engine::beam_chunk_impl(const float* enc, int B, int Tp, int K, const int* 
         memcpy(stage + o_st, hw->st_in, (size_t)nb_st);
         memcpy(stage + o_g, hw->graphs, (size_t)nb_g);
     }
+    if (nlm_io) memcpy(stage + o_nl, nlm_io, (size_t)nb_nl);
     memset(stage + o_ovf, 0, 16);
     int* d_ovf = nullptr;
     run_sized([&](const Ctx& c) {
@@ -1012,7 +1022,8 @@ void Engine::beam_chunk_impl(const float* enc, int B, int Tp, int K, const int* 
         const BeamHwIO dhw{reinterpret_cast<const BeamHwStream*>(d + o_g), reinterpret_cast<const int*>(d + o_st),
                            reinterpret_cast<int*>(d + in_bytes + nb_out), hw && hw->lm};
         beam_resume_device(c, reinterpret_cast<const float*>(d), B, Tp, K, reinterpret_cast<const int*>(d + o_in),
-                           reinterpret_cast<int*>(d + in_bytes), d_ovf, hw ? &dhw : nullptr);
+                           reinterpret_cast<int*>(d + in_bytes), d_ovf, hw ? &dhw : nullptr,
+                           nlm_io ? reinterpret_cast<const NlmStreamIO*>(d + o_nl) : nullptr);
     });
     char* pin = static_cast<char*>(pinned(16 + nb_out + nb_st));
     K2_HIP(hipMemcpyAsync(pin, d_ovf, (size_t)(16 + nb_out + nb_st), hipMemcpyDeviceToHost, stream_));
@@ -3157,6 +3168,43 @@ void Engine::debug_op_host(const char* op, const int64_t* iargs, int n_iargs, vo
                            static_cast<const int*>(bufs[5])[i]);
             if (live >= 0) K2_HIP(hipMemsetD32Async((hipDeviceptr_t)flag, live, 1, stream_));
             nlm_rows(c, h, wout, ob, qp, qo, par, tok, live >= 0 ? flag : nullptr, M, H, V);
+        } else if (name == "nlm_load_streams" || name == "nlm_store_streams") {
+            // ints B, K, L, H, V; bufs blocks [B][NlmStreamLayout::block_floats()], cur [B] (int32: the current half, -1: no state yet),
+            // then (load) nh [B] (int32), h0 [L][H], c0 [L][H], q0 [V], h [L][M][H] (out), c (out), q [M][V] (out), io [B] x 16 bytes (scratch)
+            //      (store) h, c, q, io: the call writes the OTHER half of every block (half 0 of a block without a state)
+            const bool load = name == "nlm_load_streams";
+            const int B = I(), K = I(), Ln = I(), H = I(), V = I();
+            K2_REQUIRE(B > 0 && B <= 4096 && K >= 1 && K <= kMaxBeam && Ln >= 1 && Ln <= 8 && H > 0 && H % 4 == 0 && V > 0, "debug_op_run %s: bad shape", op);
+            const NlmStreamLayout lay{K, Ln, H, V};
+            const long long M = (long long)B * K;
+            float* blocks = P();
+            const int* cur = reinterpret_cast<const int*>(P());
+            const int* nh = load ? reinterpret_cast<const int*>(P()) : nullptr;
+            float *h0 = load ? P() : nullptr, *c0 = load ? P() : nullptr, *q0 = load ? P() : nullptr;
+            float *h = P(), *cc = P(), *q = P();
+            NlmStreamIO* io = reinterpret_cast<NlmStreamIO*>(P());
+            const int o = load ? 6 : 2;   // index of h among the buffers
+            K2_REQUIRE(blocks && cur && h && cc && q && io && (!load || (nh && h0 && c0 && q0)) && buf_bytes[0] >= 4LL * B * lay.block_floats() && buf_bytes[1] >= 4LL * B &&
+                           buf_bytes[o] >= 4LL * Ln * M * H && buf_bytes[o + 1] >= 4LL * Ln * M * H && buf_bytes[o + 2] >= 4LL * M * V &&
+                           buf_bytes[o + 3] >= (long long)sizeof(NlmStreamIO) * B &&
+                           (!load || (buf_bytes[2] >= 4LL * B && buf_bytes[3] >= 4LL * Ln * H && buf_bytes[4] >= 4LL * Ln * H && buf_bytes[5] >= 4LL * V)),
+                       "debug_op_run %s: the buffers are short of %d streams, beam %d, %d layers of %d, V = %d", op, B, K, Ln, H, V);
+            std::vector<NlmStreamIO> tbl((size_t)B);
+            for (int b = 0; b < B; b++) {
+                const int cb = static_cast<const int*>(bufs[1])[b];
+                K2_REQUIRE(cb >= -1 && cb <= 1, "debug_op_run %s: stream %d names half %d", op, b, cb);
+                K2_REQUIRE(!load || (static_cast<const int*>(bufs[2])[b] >= 0 && static_cast<const int*>(bufs[2])[b] <= K), "debug_op_run %s: stream %d has %d hypotheses", op,
+                           b, load ? static_cast<const int*>(bufs[2])[b] : 0);
+                float* base = blocks + (long long)b * lay.block_floats();
+                tbl[(size_t)b].rd = cb < 0 ? nullptr : base + cb * lay.half_floats();
+                tbl[(size_t)b].wr = base + (cb < 0 ? 0 : (cb ^ 1)) * lay.half_floats();
+            }
+            K2_HIP(copy_blocking(io, tbl.data(), sizeof(NlmStreamIO) * (size_t)B, hipMemcpyHostToDevice));
+            RnnLmDev dv;
+            dv.L = Ln; dv.H = H; dv.V = V;
+            dv.h0 = h0; dv.c0 = c0; dv.q0 = q0;
+            if (load) nlm_load_streams(c, dv, io, nh, 1, h, cc, q, B, K);
+            else nlm_store_streams(c, dv, io, h, cc, q, B, K);
         } else if (name == "convnext_cat") {
             float *a3 = P(), *pool = P();
             const long long ss = L(), off = L();

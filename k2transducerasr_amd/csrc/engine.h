@@ -17,6 +17,7 @@
 #include "resample_plan.h"
 #include "rnn_lm_plan.h"
 #include "rnn_lm_fuse_layout.h"
+#include "rnn_lm_stream_pool.h"
 #include "rnn_lm_ref.h"
 #include "search_out.h"
 #include "vad_ref.h"
@@ -253,6 +254,15 @@ class Engine {
     // during the search; every other path runs as before
     void set_rnn_lm_fusion(bool on, float scale) { rnn_fusion_ = on; rnn_fuse_scale_ = scale; }
     bool rnn_lm_fusion_active() const { return rnn_fusion_ && rnn_host_ && rnn_fuse_scale_ > 0.f && rnn_dev_.w_out; }
+    // Neural LM shallow fusion in the STREAMING modified beam search (k2hip_set_rnn_lm_stream_fusion; a switch of its own: the offline
+    // one above never reaches a streaming entry).  Active with `on`, an attached LM with its fused layouts and scale > 0.  The caller
+    // of a chunk call (k2hip_beam_search_chunk, k2hip_online_step) then names the streams' state blocks (set_beam_nlm_io: a host table
+    // of B entries, one per stream of the call in its order; null again after the call): the table is staged with the in blocks, the
+    // resumed search takes the per-frame launch form with the LM launches behind every frame, and the blocks' other halves hold the
+    // survivors' state afterwards.  Flipping the halves is the caller's, after success.
+    void set_rnn_lm_stream_fusion(bool on) { rnn_stream_fusion_ = on; }
+    bool rnn_lm_stream_fusion_active() const { return rnn_stream_fusion_ && rnn_host_ && rnn_fuse_scale_ > 0.f && rnn_dev_.w_out; }
+    void set_beam_nlm_io(const NlmStreamIO* host) { nlm_io_host_ = host; }
     // the fused search's layouts of the attached LM (rnn_lm_fusion_upload): built when fusion is first switched on, never for a model
     // that only rescores; ONE more device allocation that the caller owns, *io = the attached LM's tables, completed
     void* rnn_lm_fusion_upload(const RnnLm& lm, RnnLmDev* io);
@@ -565,6 +575,8 @@ class Engine {
     const RnnLm* rnn_host_ = nullptr;
     RnnLmDev rnn_dev_;
     bool rnn_fusion_ = false;
+    bool rnn_stream_fusion_ = false;
+    const NlmStreamIO* nlm_io_host_ = nullptr;
     float rnn_fuse_scale_ = 0.f;
     int64_t rnn_calls_ = 0;
     int rnn_last_blocks_ = 0;
@@ -602,7 +614,7 @@ class Engine {
                                    bool keep_nbest);
     // hw (device pointers) or null: the unbiased search, today's launch
     void beam_resume_device(const Ctx& c, const float* enc, int B, int Tp, int K, const int* d_in, int* d_out, int* d_overflow,
-                            const BeamHwIO* hw = nullptr);
+                            const BeamHwIO* hw = nullptr, const NlmStreamIO* d_nlm = nullptr);
     void beam_chunk_impl(const float* enc, int B, int Tp, int K, const int* beam_in, int* beam_out, const BeamHwIO* hw);
     struct OnlineBeamIO { int K; const int* in; int* out; const BeamHwIO* hw; };
     struct OnlineCtcPrefixIO { int K; const int* in; int* out; const CtcPrefixBiasIO* bias = nullptr; };

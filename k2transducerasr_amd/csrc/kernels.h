@@ -547,11 +547,27 @@ struct BeamNlm {
 };
 // the start state h0 / c0 and row q0 into every slot of parity 0: h, c [L][M][H], q [M][V]
 void nlm_broadcast(const Ctx& ctx, const RnnLmDev& d, float* h, float* c, float* q, int M);
+// The streaming (resumed) form: every stream of the call owns a device block (rnn_lm_stream_pool.h NlmStreamLayout{K, L, H, V}) that
+// carries its slots' states and rows from chunk to chunk.  io [B] (device): per stream the half this call reads (null: a stream without
+// a state yet) and the half it writes.
+struct NlmStreamIO {
+    const float* rd = nullptr;
+    float* wr = nullptr;
+};
+// once per call, in place of nlm_broadcast: stream b's current half into slots b K .. b K + K - 1 of the parity-0 arrays h, c [L][M][H],
+// q [M][V] (M = B K).  A stream with rd == null and every dead slot (k >= nh[b * nh_stride], the in blocks' first int) get the start
+// state h0 / c0 / q0, so no LM launch reads undefined memory.  16 bytes per lane where both sides are aligned, floats elsewhere.
+void nlm_load_streams(const Ctx& ctx, const RnnLmDev& d, const NlmStreamIO* io, const int* nh, int nh_stride, float* h, float* c, float* q, int B, int K);
+// once per call, behind the last frame's LM launches: slots b K + k of the final-parity arrays into slot k of stream b's other half
+void nlm_store_streams(const Ctx& ctx, const RnnLmDev& d, const NlmStreamIO* io, const float* h, const float* c, const float* q, int B, int K);
 // h0 / c0 / q0 of d from h = c = 0 and sos, through the kernels above (once per upload)
 void nlm_start_state(const Ctx& ctx, const RnnLmDev& d);
 // launches of the fused search since the process started (the third counter beside beam_launch_counts)
 void nlm_note_search();
 long long beam_nlm_launch_count();
+// ... and of the fused RESUMED search (chunk calls; k2hip_debug_rnn_lm_stream_fusion_stats), a counter of its own
+void nlm_note_stream_search();
+long long beam_nlm_stream_launch_count();
 
 // One hypothesis of rnn_lm_totals, in sorted order j: its positions, the caller's index and where its token log-probs go
 struct RnnLmHyp {
@@ -829,8 +845,10 @@ struct BeamArgs {
     // Neural LM shallow fusion (rnn_lm_fuse.hip; semantics in include/k2hip.h): every hypothesis carries the LSTM state of its token
     // sequence and the LM's next-token log-probs; a selected candidate that appends a real token v gets
     // ((sum + hotword bonus) + n-gram term) + fl32(scale q_parent[v]) before the merges.  Offline only, always in the per-frame launch
-    // form; nlm.dev.emb == null: off.
+    // form; nlm.dev.emb == null: off.  Resumed (rin set): nlm_io [B] names the streams' state blocks (NlmStreamIO), the LM launches
+    // run behind EVERY frame and the movers of rnn_lm_fuse.hip frame the call.
     BeamNlm nlm;
+    const NlmStreamIO* nlm_io = nullptr;
     // Token log-probs and N-best (semantics in include/k2hip.h).  Both null: nothing is kept beyond the best hypothesis.  nb: the
     // offline search also writes its final hypotheses in pick order; yp_out [B][K][Tp] (resume): the token log-probs of each
     // survivor's suffix, a side block beside rout as st_out is.

@@ -356,10 +356,14 @@ void Engine::online_step_impl(const int* slots, const float* const* chunks, cons
                   nb_hg = bhw || cbias ? (int64_t)sizeof(BeamHwStream) * B : 0;
     const int64_t nb_bout = beam ? (int64_t)sizeof(int) * RL.out_ints() * B + nb_hst : cpx ? (int64_t)sizeof(int) * CL.out_ints() * B + nb_cso : 0,
                   o_hout = nb_bout - (beam ? nb_hst : nb_cso);
+    // (an active streaming neural LM fusion: the streams' block-pointer table rides behind the graphs, in the same upload)
+    const NlmStreamIO* nlm_io = beam ? nlm_io_host_ : nullptr;
+    K2_REQUIRE(!nlm_io || rnn_lm_stream_fusion_active(), "online beam search: state blocks without an active streaming neural LM fusion");
+    const int64_t nb_nl = nlm_io ? (int64_t)sizeof(NlmStreamIO) * B : 0;
     const int64_t nb_x = from_fifo ? 0 : (int64_t)sizeof(float) * chunk_floats * B;
     const int64_t o_plen = align_up(nb_x, 16), o_hyp = o_plen + 8 * (int64_t)B, o_slots = o_hyp + 16 * (int64_t)B, o_chunks = o_slots + 4 * (int64_t)B,
                   o_heads = o_chunks + 4 * (int64_t)B, o_bin = align_up(o_heads + 4 * (int64_t)B, 16), o_hst = align_up(o_bin + nb_bin, 16),
-                  o_hg = align_up(o_hst + nb_hst, 16), o_ovf = align_up(o_hg + nb_hg, 16), in_bytes = o_ovf + 16;
+                  o_hg = align_up(o_hst + nb_hst, 16), o_nl = align_up(o_hg + nb_hg, 16), o_ovf = align_up(o_nl + nb_nl, 16), in_bytes = o_ovf + 16;
     char* stage = static_cast<char*>(pinned_in(in_bytes));
     if (!from_fifo)
         for (int b = 0; b < B; b++) memcpy(stage + (size_t)b * chunk_floats * sizeof(float), chunks[b], sizeof(float) * chunk_floats);
@@ -379,6 +383,7 @@ void Engine::online_step_impl(const int* slots, const float* const* chunks, cons
         memcpy(stage + o_hst, cbias->side_in, (size_t)nb_hst);
         memcpy(stage + o_hg, cbias->graphs, (size_t)nb_hg);
     }
+    if (nlm_io) memcpy(stage + o_nl, nlm_io, (size_t)nb_nl);
     memset(stage + o_ovf, 0, 16);
     const int64_t nb_out = beam || cpx ? nb_bout : SearchOut::bytes_for(B, Tp) - 16;   // what follows the flag
     run_sized([&](const Ctx& c) {
@@ -436,7 +441,7 @@ void Engine::online_step_impl(const int* slots, const float* const* chunks, cons
             }
         } else if (beam) {   // modified beam search resumed from the streams' saved hypotheses, on the tick's encoder buffer
             beam_resume_device(c, enc, B, Tp, beam->K, reinterpret_cast<const int*>(d_in + o_bin), reinterpret_cast<int*>(d_out), out.flag(),
-                               bhw ? &dhw : nullptr);
+                               bhw ? &dhw : nullptr, nlm_io ? reinterpret_cast<const NlmStreamIO*>(d_in + o_nl) : nullptr);
         } else {
             // OnlineRecognizer.cs:135-202: decoder on the streams' hyps, T' joiner steps, skip {blank, unk, 1}
             GreedyArgs a;

@@ -24,15 +24,20 @@
 //                    operand, and the A image is single-buffered behind two barriers per 32 k.
 //   nlm_rows         q = log_softmax(h^{L-1} W_out^T + b) for the rows that appended (the GEMM launcher behind the same device flag,
 //                    then k_nlm_rows: one workgroup per row), the parent's row copied for the others.
+//   k_nlm_load_streams / k_nlm_store_streams   the STREAMING form (the resumed search): the streams' carried blocks
+//                    (rnn_lm_stream_pool.h) into the parity-0 slot arrays before the first frame, the final-parity arrays into the
+//                    blocks' other halves behind the last frame's LM launches.  One workgroup per slot, 16 bytes per lane where both
+//                    sides are aligned.
 // No workgroup waits for another; every store is an ordinary vector store.
 #include <atomic>
 
 #include "kernels.h"
+#include "rnn_lm_stream_pool.h"
 
 namespace k2hip {
 namespace {
 
-std::atomic<long long> g_nlm_searches;
+std::atomic<long long> g_nlm_searches, g_nlm_stream_searches;
 
 constexpr int NT = 256;    // threads per workgroup: four waves, each with its own row strips
 constexpr int NKC = 32;    // k staged in LDS at a time
@@ -192,7 +197,62 @@ __global__ void k_nlm_broadcast(const float* __restrict__ h0, const float* __res
     }
 }
 
+// ---- the streaming form's movers: one workgroup per slot m = b K + k ------------------------------------------------------------------
+// n floats from src to dst by the whole workgroup: 16 bytes per lane where both start on 16 bytes (every state row; a row of q only
+// when V and the slot allow it), the tail and the unaligned rows float by float
+__device__ __forceinline__ void nlm_move(float* __restrict__ dst, const float* __restrict__ src, int n) {
+    const int tid = threadIdx.x, nt = blockDim.x;
+    if ((((unsigned long long)dst | (unsigned long long)src) & 15ull) == 0) {
+        const int n4 = n >> 2;
+        for (int i = tid; i < n4; i += nt) reinterpret_cast<float4*>(dst)[i] = reinterpret_cast<const float4*>(src)[i];
+        for (int i = 4 * n4 + tid; i < n; i += nt) dst[i] = src[i];
+    } else {
+        for (int i = tid; i < n; i += nt) dst[i] = src[i];
+    }
+}
+__global__ __launch_bounds__(NT) void k_nlm_load_streams(const NlmStreamIO* __restrict__ io, const int* __restrict__ nh, int nh_stride,
+                                                         const float* __restrict__ h0, const float* __restrict__ c0, const float* __restrict__ q0,
+                                                         float* __restrict__ h, float* __restrict__ c, float* __restrict__ q, NlmStreamLayout lay, int M) {
+    const int m = blockIdx.x, b = m / lay.K, k = m - b * lay.K;
+    const float* half = io[b].rd;
+    const bool start = half == nullptr || k >= nh[(long long)b * nh_stride];
+    for (int l = 0; l < lay.L; l++) {
+        const long long dst = ((long long)l * M + m) * lay.H;
+        nlm_move(h + dst, start ? h0 + (long long)l * lay.H : half + lay.state_off(k, l, 0), lay.H);
+        nlm_move(c + dst, start ? c0 + (long long)l * lay.H : half + lay.state_off(k, l, 1), lay.H);
+    }
+    nlm_move(q + (long long)m * lay.V, start ? q0 : half + lay.row_off(k), lay.V);
+}
+__global__ __launch_bounds__(NT) void k_nlm_store_streams(const NlmStreamIO* __restrict__ io, const float* __restrict__ h, const float* __restrict__ c,
+                                                          const float* __restrict__ q, NlmStreamLayout lay, int M) {
+    const int m = blockIdx.x, b = m / lay.K, k = m - b * lay.K;
+    float* half = io[b].wr;
+    for (int l = 0; l < lay.L; l++) {
+        const long long src = ((long long)l * M + m) * lay.H;
+        nlm_move(half + lay.state_off(k, l, 0), h + src, lay.H);
+        nlm_move(half + lay.state_off(k, l, 1), c + src, lay.H);
+    }
+    nlm_move(half + lay.row_off(k), q + (long long)m * lay.V, lay.V);
+}
+
 }  // namespace
+
+void nlm_load_streams(const Ctx& ctx, const RnnLmDev& d, const NlmStreamIO* io, const int* nh, int nh_stride, float* h, float* c, float* q, int B, int K) {
+    K2_REQUIRE(B > 0 && K >= 1 && K <= kMaxBeam && d.L >= 1 && d.H > 0 && d.H % 4 == 0 && d.V > 0, "nlm_load_streams: %d streams, beam %d, %d layers of %d, V = %d", B,
+               K, d.L, d.H, d.V);
+    if (ctx.dry) return;
+    K2_REQUIRE(io && nh && h && c && q && d.h0 && d.c0 && d.q0, "nlm_load_streams: null argument");
+    hipLaunchKernelGGL(k_nlm_load_streams, dim3(B * K), dim3(NT), 0, ctx.stream, io, nh, nh_stride, d.h0, d.c0, d.q0, h, c, q, NlmStreamLayout{K, d.L, d.H, d.V}, B * K);
+    K2_HIP(hipGetLastError());
+}
+void nlm_store_streams(const Ctx& ctx, const RnnLmDev& d, const NlmStreamIO* io, const float* h, const float* c, const float* q, int B, int K) {
+    K2_REQUIRE(B > 0 && K >= 1 && K <= kMaxBeam && d.L >= 1 && d.H > 0 && d.H % 4 == 0 && d.V > 0, "nlm_store_streams: %d streams, beam %d, %d layers of %d, V = %d", B,
+               K, d.L, d.H, d.V);
+    if (ctx.dry) return;
+    K2_REQUIRE(io && h && c && q, "nlm_store_streams: null argument");
+    hipLaunchKernelGGL(k_nlm_store_streams, dim3(B * K), dim3(NT), 0, ctx.stream, io, h, c, q, NlmStreamLayout{K, d.L, d.H, d.V}, B * K);
+    K2_HIP(hipGetLastError());
+}
 
 void nlm_advance(const Ctx& ctx, const NlmAdvance& a) {
     K2_REQUIRE(a.M > 0 && a.H > 0 && a.H % 32 == 0 && a.in > 0 && a.in % 4 == 0, "nlm_advance: %d rows, input %d (a multiple of 4), hidden_dim %d (a multiple of 32)",
@@ -258,5 +318,7 @@ void nlm_start_state(const Ctx& ctx, const RnnLmDev& d) {
 
 void nlm_note_search() { g_nlm_searches++; }
 long long beam_nlm_launch_count() { return g_nlm_searches.load(); }
+void nlm_note_stream_search() { g_nlm_stream_searches++; }
+long long beam_nlm_stream_launch_count() { return g_nlm_stream_searches.load(); }
 
 }  // namespace k2hip
