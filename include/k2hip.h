@@ -1152,6 +1152,43 @@ int32_t k2hip_set_rnn_lm_fusion(k2hip_model_t* model, int32_t on);
  * frees every block, and a stream then only forgets its own.  (An online stream still has to go before its model, as before.) */
 int32_t k2hip_set_rnn_lm_stream_fusion(k2hip_model_t* model, int32_t on);
 
+/* ---- LODR: low-order density ratio beside the neural LM ------------------------------------------------------------------------------
+ * (no reference counterpart; the project's own semantics after icefall's modified_beam_search_LODR / modified_beam_search_lm_rescore_LODR
+ * and sherpa's lodr_fst / lodr_scale.  DESIGN.md "LODR".)  A low-order n-gram LM, usually a bi-gram trained on the acoustic model's own
+ * training text, stands in for the transducer's internal LM: its score is SUBTRACTED wherever the neural LM's is added.  It is a second
+ * automaton slot with a state of its own per hypothesis, beside the one of k2hip_set_ngram_lm (whose behaviour is unchanged), so a
+ * positive-weight n-gram LM and a LODR LM can be set at once.
+ * lm = NULL clears the setting.  scale is finite and <= 0 (icefall's convention: the weight is given as a negative number); a positive
+ * value is K2HIP_ERR_INVALID -- an added n-gram weight is k2hip_set_ngram_lm's job; scale = 0 means "none".  Checks vocab_size against
+ * the model and uploads the sparse automaton with every weight multiplied by scale ONCE on the host in float32 (the device only adds);
+ * the model keeps its own copy, so lm may be destroyed afterwards.  K2HIP_ERR_INVALID while submitted batches are in flight.
+ * LODR IS ACTIVE ONLY WHERE THE NEURAL LM ACTS: in a fused offline search (k2hip_set_rnn_lm_fusion on and an LM with scale > 0
+ * attached), in a fused streaming search (k2hip_set_rnn_lm_stream_fusion), and in the rescoring k2hip_offline_recognizer_get_results
+ * does.  Everywhere else the setting is ignored: the plain modified beam search, greedy search, the CTC searches' own scoring,
+ * k2hip_offline_recognizer_get_result, the pipelined submit / wait and k2hip_offline_recognize_long.  With the setting ignored, with no
+ * LODR LM, a cleared one and scale = 0 every call issues the launches of before and gives the same bits.
+ * FUSION: every hypothesis carries a LODR state beside its n-gram state; the start hypothesis has the LODR LM's start state.  A frame's
+ * top-`beam` selection uses the same sums as before.  A selected candidate of parent p that appends a real token v gets
+ *   (((sum + hotword bonus) + n-gram term) + fl32(scale_nlm * q_p[v])) + Step_lodr(state_p, v)
+ * where Step is the n-gram step of k2hip_set_ngram_lm over the LODR LM's scaled tables -- float32, back-off weights first and then the
+ * arc, in exactly the order stated there; the merge of equal sequences follows.  Blank and unk earn nothing and keep the state.  No
+ * end-of-sentence term is applied.  The final pick and all reported scores include the LODR terms; token log-probs and the beam trace
+ * stay acoustic.
+ * STREAMING: after any chunking a stream holds what the offline fused search with the same LODR setting gives over all frames so far;
+ * the LODR state of every saved hypothesis crosses the chunk boundary.  A STREAM KEEPS THE LODR SETTING OF ITS FIRST CHUNK -- the
+ * k2hip_set_lodr_lm call (every call that leaves an LM set is a new setting) and with it the scale, as for the n-gram LM; "none" where
+ * the fusion is not active.  A chunk under another setting is K2HIP_ERR_INVALID ("... reset the stream first"), decided for all
+ * streams of a call before anything changes; a k2hip_set_lodr_lm that lands between a call's checks and its launch is caught under the
+ * lock that covers the launch.  A reset returns the hypotheses to the start state of the LODR LM then set.
+ * RESCORING (transducer modified_beam_search and ctc_prefix_beam_search, wherever the neural rescoring runs): the ordering quantity
+ * uses (score_i + fl32(scale_nlm * lm_i)) + lodr_i, where lodr_i is the float32 sum, in token order from the start state, of the scaled
+ * steps of alternative i's tokens, computed on the host over the model's copy of the scaled automaton.  lodr_i has NO eos term (the
+ * n-gram LM never has one) while the neural total keeps its with_eos = 1: the asymmetry is intended.
+ * k2hip_offline_stream_get_alternative_lodr_score gives lodr_i: 0 when nothing was rescored or no LODR LM was set, and 0 while fusion
+ * is active, as k2hip_offline_stream_get_alternative_lm_score does.  Reported alternative scores stay the search's own. */
+int32_t k2hip_set_lodr_lm(k2hip_model_t* model, const k2hip_ngram_lm_t* lm, float scale);
+int32_t k2hip_offline_stream_get_alternative_lodr_score(const k2hip_offline_stream_t* s, int32_t i, float* lodr_total);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

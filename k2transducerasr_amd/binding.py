@@ -1253,6 +1253,15 @@ class Model:
         self._L.k2hip_set_ngram_lm.argtypes = [C.c_void_p, C.c_void_p, C.c_float]
         self._chk(self._L.k2hip_set_ngram_lm(self._h, lm._h if lm is not None else None, float(scale)))
 
+    def set_lodr_lm(self, lm: Optional["NgramLm"] = None, scale: float = 0.0):
+        """k2hip_set_lodr_lm: LODR, a low-order n-gram LM (usually a bi-gram over the acoustic model's training text) whose score is
+        SUBTRACTED wherever the neural LM acts -- the fused offline and streaming modified beam search, and the N-best rescoring of
+        get_results.  scale <= 0 (icefall's convention); None or 0 clears.  A slot of its own beside set_ngram_lm's; ignored everywhere
+        else (include/k2hip.h "LODR")."""
+        self._L.k2hip_set_lodr_lm.argtypes = [C.c_void_p, C.c_void_p, C.c_float]
+        self._L.k2hip_set_lodr_lm.restype = C.c_int32
+        self._chk(self._L.k2hip_set_lodr_lm(self._h, lm._h if lm is not None else None, float(scale)))
+
     def gemm_profile(self) -> np.ndarray:
         """[n, 8] rows (M, N, K, batch, act, has_residual, kind, us) of the last instrumented call"""
         n = C.c_int32(0)
@@ -1645,7 +1654,17 @@ class OfflineStream:
             v = C.c_float(0)
             self._m._chk(self._L.k2hip_offline_stream_get_alternative_lm_score(self._h, i, C.byref(v)))
             a["lm_score"] = float(v.value)
+            a["lodr_score"] = self.alternative_lodr_score(i)
         return alts
+
+    def alternative_lodr_score(self, i: int) -> float:
+        """k2hip_offline_stream_get_alternative_lodr_score: the LODR total of alternative i that the rescoring added (0.0 when nothing was
+        rescored, without a LODR LM, and while fusion is active)"""
+        self._L.k2hip_offline_stream_get_alternative_lodr_score.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_float)]
+        self._L.k2hip_offline_stream_get_alternative_lodr_score.restype = C.c_int32
+        v = C.c_float(0)
+        self._m._chk(self._L.k2hip_offline_stream_get_alternative_lodr_score(self._h, int(i), C.byref(v)))
+        return float(v.value)
 
     def token_log_probs(self) -> np.ndarray:
         return _token_log_probs(self._m, self._L, "k2hip_offline_stream", self._h)
@@ -1660,11 +1679,13 @@ class OfflineRecognizer:
     ctc_prefix_beam_search uses both as well (Model.set_ctc_prefix_biasing); without it the recognizer behaves as before.  rnn_lm: an
     RnnLm that rescores the N-best lists of get_results with weight rnn_lm_scale (sherpa's RNN LM rescoring); needs nbest > 1, the
     alternatives then carry lm_score.  rnn_lm_fusion=True: the LM is fused into modified_beam_search instead (Model.set_rnn_lm_fusion):
-    its term is added during the search, any nbest, and the lists are not rescored."""
+    its term is added during the search, any nbest, and the lists are not rescored.  lodr_lm: an NgramLm (usually a bi-gram) subtracted
+    with weight lodr_scale <= 0 wherever rnn_lm acts, in the rescoring or in the fused search (Model.set_lodr_lm)."""
 
     def __init__(self, weights_path: str, device: int = 0, decoding_method: str = "greedy_search", beam: int = 4, hotwords=None,
                  hotwords_score: float = 1.5, nbest: int = 1, ngram_lm: Optional["NgramLm"] = None, ngram_lm_scale: float = 0.3,
-                 ctc_prefix_biasing: bool = False, rnn_lm: Optional["RnnLm"] = None, rnn_lm_scale: float = 0.5, rnn_lm_fusion: bool = False):
+                 ctc_prefix_biasing: bool = False, rnn_lm: Optional["RnnLm"] = None, rnn_lm_scale: float = 0.5, rnn_lm_fusion: bool = False,
+                 lodr_lm: Optional["NgramLm"] = None, lodr_scale: float = -0.1):
         self.model = Model(weights_path, device)
         self.model.set_decoding_method(decoding_method, beam)
         if nbest != 1:   # (streams then carry .alternatives() / .token_log_probs() after get_results)
@@ -1681,6 +1702,8 @@ class OfflineRecognizer:
             self.model.set_rnn_lm(rnn_lm, rnn_lm_scale)
         if rnn_lm_fusion:
             self.model.set_rnn_lm_fusion(True)
+        if lodr_lm is not None:
+            self.model.set_lodr_lm(lodr_lm, lodr_scale)
 
     def create_offline_stream(self) -> OfflineStream:  # CreateOfflineStream :71-75
         return OfflineStream(self.model)
@@ -2116,12 +2139,14 @@ class OnlineRecognizer:
     (hypotheses carried from chunk to chunk: include/k2hip.h).  ngram_lm: an NgramLm fused with weight ngram_lm_scale
     under modified_beam_search (every hypothesis carries its LM state across the chunk boundary).  rnn_lm with rnn_lm_fusion=True:
     an RnnLm fused with weight rnn_lm_scale under modified_beam_search, its LSTM state carried from chunk to chunk
-    (Model.set_rnn_lm_stream_fusion); without rnn_lm_fusion the LM is attached and the streaming search ignores it.  nbest > 1: the
-    streams keep that many alternatives."""
+    (Model.set_rnn_lm_stream_fusion); without rnn_lm_fusion the LM is attached and the streaming search ignores it.  lodr_lm: an
+    NgramLm subtracted with weight lodr_scale <= 0 beside the fused rnn_lm, its state carried as well (Model.set_lodr_lm); ignored
+    without an active fusion.  nbest > 1: the streams keep that many alternatives."""
 
     def __init__(self, weights_path: str, device: int = 0, decoding_method: str = "greedy_search", beam: int = 4,
                  ngram_lm: Optional["NgramLm"] = None, ngram_lm_scale: float = 0.3, rnn_lm: Optional["RnnLm"] = None,
-                 rnn_lm_scale: float = 0.5, rnn_lm_fusion: bool = False, nbest: int = 1):
+                 rnn_lm_scale: float = 0.5, rnn_lm_fusion: bool = False, nbest: int = 1, lodr_lm: Optional["NgramLm"] = None,
+                 lodr_scale: float = -0.1):
         self.model = Model(weights_path, device)
         _bind_online(self.model._L)
         self.model.set_decoding_method(decoding_method, beam)
@@ -2133,6 +2158,8 @@ class OnlineRecognizer:
             self.model.set_rnn_lm(rnn_lm, rnn_lm_scale)
         if rnn_lm_fusion:
             self.model.set_rnn_lm_stream_fusion(True)
+        if lodr_lm is not None:
+            self.model.set_lodr_lm(lodr_lm, lodr_scale)
         a, b, c = C.c_int32(), C.c_int32(), C.c_int32()
         self.model._chk(self.model._L.k2hip_online_chunk_info(self.model.handle, C.byref(a), C.byref(b), C.byref(c)))
         self.chunk_length, self.shift_length, self.frames_per_chunk = a.value, b.value, c.value

@@ -21,6 +21,7 @@
 #include "resample_ref.h"
 #include "ctc_kws_ref.h"
 #include "ngram_lm.h"
+#include "lodr_host.h"
 #include "../../include/k2hip_debug.h"
 
 using namespace k2hip;
@@ -121,6 +122,13 @@ struct k2hip_model {
     uint64_t lm_serial = 0;
     int lm_start = 0;
     int lm_states = 0;   // its number of states (0 = none): what a carried LM state is checked against before a launch
+    // LODR (k2hip_set_lodr_lm): the model's own copy of the low-order LM, its scaled automaton on the host (the rescoring walks it) and
+    // on the device (the fused searches walk it), and the setting's serial number (0 = none; fresh for every call that leaves one set).
+    // Under the engine's lock.
+    std::unique_ptr<NgramLm> lodr_lm;
+    std::shared_ptr<const LodrHost> lodr_host;
+    void* lodr_dev = nullptr;
+    uint64_t lodr_serial = 0;
     // the neural LM of k2hip_set_rnn_lm: the model's own host copy (shared with the handle it came from: it is immutable), its weights
     // on the device in one allocation, and the scale of the rescoring (0 = the N-best lists are left alone)
     std::shared_ptr<const RnnLm> rnn_lm;
@@ -185,6 +193,13 @@ struct k2hip_model {
             try {
                 engine.synchronize();
                 engine.dev_free(lm_dev);
+            } catch (...) {
+            }
+        }
+        if (lodr_dev) {
+            try {
+                engine.synchronize();
+                engine.dev_free(lodr_dev);
             } catch (...) {
             }
         }
@@ -1301,6 +1316,35 @@ int32_t k2hip_ngram_lm_step(const k2hip_ngram_lm_t* lm, int32_t state, int64_t t
         *next_state = n;
     });
 }
+// the scaled sparse form of an n-gram LM into ONE device allocation (returned; the caller owns it) and the kernels' view of it
+static void* ngram_tables_upload(Engine& e, const NgramDeviceForm& d, int V, int start, BeamLm* out) {
+    const int64_t nb_s = align_up((int64_t)sizeof(int32_t) * (int64_t)d.states.size(), 16);
+    const int64_t nb_a = align_up((int64_t)sizeof(int32_t) * std::max<int64_t>((int64_t)d.arc_tok.size(), 1), 16);
+    const int64_t nb_v = align_up((int64_t)sizeof(int32_t) * V, 16);
+    void* fresh = e.dev_alloc(nb_s + 3 * nb_a + 2 * nb_v);
+    try {
+        char* c = static_cast<char*>(fresh);
+        e.dev_upload(c, d.states.data(), (int64_t)sizeof(int32_t) * (int64_t)d.states.size());
+        if (!d.arc_tok.empty()) {
+            e.dev_upload(c + nb_s, d.arc_tok.data(), (int64_t)sizeof(int32_t) * (int64_t)d.arc_tok.size());
+            e.dev_upload(c + nb_s + nb_a, d.arc_lp.data(), (int64_t)sizeof(float) * (int64_t)d.arc_lp.size());
+            e.dev_upload(c + nb_s + 2 * nb_a, d.arc_next.data(), (int64_t)sizeof(int32_t) * (int64_t)d.arc_next.size());
+        }
+        e.dev_upload(c + nb_s + 3 * nb_a, d.uni_lp.data(), (int64_t)sizeof(float) * V);
+        e.dev_upload(c + nb_s + 3 * nb_a + nb_v, d.uni_next.data(), (int64_t)sizeof(int32_t) * V);
+        out->states = reinterpret_cast<const int4*>(c);
+        out->arc_tok = reinterpret_cast<const int*>(c + nb_s);
+        out->arc_lp = reinterpret_cast<const float*>(c + nb_s + nb_a);
+        out->arc_next = reinterpret_cast<const int*>(c + nb_s + 2 * nb_a);
+        out->uni_lp = reinterpret_cast<const float*>(c + nb_s + 3 * nb_a);
+        out->uni_next = reinterpret_cast<const int*>(c + nb_s + 3 * nb_a + nb_v);
+        out->start = start;
+    } catch (...) {
+        try { e.dev_free(fresh); } catch (...) {}
+        throw;
+    }
+    return fresh;
+}
 int32_t k2hip_set_ngram_lm(k2hip_model_t* model, const k2hip_ngram_lm_t* lm, float scale) {
     return guard([&] {
         NEED(model);
@@ -1319,31 +1363,7 @@ int32_t k2hip_set_ngram_lm(k2hip_model_t* model, const k2hip_ngram_lm_t* lm, flo
             NgramDeviceForm d;
             lm->lm->device_form(scale, &d);
             n_states = (int)(d.states.size() / 4);
-            const int64_t nb_s = align_up((int64_t)sizeof(int32_t) * (int64_t)d.states.size(), 16);
-            const int64_t nb_a = align_up((int64_t)sizeof(int32_t) * std::max<int64_t>((int64_t)d.arc_tok.size(), 1), 16);
-            const int64_t nb_v = align_up((int64_t)sizeof(int32_t) * V, 16);
-            fresh = e.dev_alloc(nb_s + 3 * nb_a + 2 * nb_v);
-            try {
-                char* c = static_cast<char*>(fresh);
-                e.dev_upload(c, d.states.data(), (int64_t)sizeof(int32_t) * (int64_t)d.states.size());
-                if (!d.arc_tok.empty()) {
-                    e.dev_upload(c + nb_s, d.arc_tok.data(), (int64_t)sizeof(int32_t) * (int64_t)d.arc_tok.size());
-                    e.dev_upload(c + nb_s + nb_a, d.arc_lp.data(), (int64_t)sizeof(float) * (int64_t)d.arc_lp.size());
-                    e.dev_upload(c + nb_s + 2 * nb_a, d.arc_next.data(), (int64_t)sizeof(int32_t) * (int64_t)d.arc_next.size());
-                }
-                e.dev_upload(c + nb_s + 3 * nb_a, d.uni_lp.data(), (int64_t)sizeof(float) * V);
-                e.dev_upload(c + nb_s + 3 * nb_a + nb_v, d.uni_next.data(), (int64_t)sizeof(int32_t) * V);
-                tables.states = reinterpret_cast<const int4*>(c);
-                tables.arc_tok = reinterpret_cast<const int*>(c + nb_s);
-                tables.arc_lp = reinterpret_cast<const float*>(c + nb_s + nb_a);
-                tables.arc_next = reinterpret_cast<const int*>(c + nb_s + 2 * nb_a);
-                tables.uni_lp = reinterpret_cast<const float*>(c + nb_s + 3 * nb_a);
-                tables.uni_next = reinterpret_cast<const int*>(c + nb_s + 3 * nb_a + nb_v);
-                tables.start = lm->lm->start_state();
-            } catch (...) {
-                try { e.dev_free(fresh); } catch (...) {}
-                throw;
-            }
+            fresh = ngram_tables_upload(e, d, V, lm->lm->start_state(), &tables);
         }
         // searches already enqueued read the old tables: let them finish before the memory goes
         if (model->lm_dev) {
@@ -1362,6 +1382,52 @@ int32_t k2hip_set_ngram_lm(k2hip_model_t* model, const k2hip_ngram_lm_t* lm, flo
         model->lm_states = fresh ? n_states : 0;
         void* old = model->lm_dev;
         model->lm_dev = fresh;
+        if (old) e.dev_free(old);
+    });
+}
+// LODR: a second automaton slot beside k2hip_set_ngram_lm's, subtracted (scale <= 0) where the neural LM is added
+int32_t k2hip_set_lodr_lm(k2hip_model_t* model, const k2hip_ngram_lm_t* lm, float scale) {
+    return guard([&] {
+        NEED(model);
+        Engine& e = model->engine;
+        const int V = e.model().cfg().V;
+        if (lm) {
+            K2_REQUIRE(std::isfinite(scale), "set_lodr_lm: scale %g must be finite", (double)scale);
+            K2_REQUIRE(scale <= 0.f, "set_lodr_lm: scale %g must be <= 0 -- the LODR weight is given as a negative number; an added n-gram "
+                       "weight is k2hip_set_ngram_lm's job", (double)scale);
+            K2_REQUIRE(lm->lm->vocab_size() == V, "set_lodr_lm: the LM was built for vocab_size %d, the model has %d", lm->lm->vocab_size(), V);
+        }
+        EngineLock lk(e);
+        K2_REQUIRE(e.batches_in_flight() == 0, "set_lodr_lm: %d submitted batches are in flight; wait for them first", e.batches_in_flight());
+        void* fresh = nullptr;
+        BeamLm tables;
+        std::unique_ptr<NgramLm> copy;
+        std::shared_ptr<LodrHost> host;
+        if (lm && scale < 0.f) {   // (scale = 0 subtracts nothing anywhere: as with no LODR LM)
+            copy.reset(new NgramLm(*lm->lm));   // (the handle may be destroyed after this call)
+            host = std::make_shared<LodrHost>();
+            copy->device_form(scale, &host->d);
+            host->start = copy->start_state();
+            host->V = V;
+            fresh = ngram_tables_upload(e, host->d, V, host->start, &tables);
+        }
+        // searches already enqueued read the old tables: let them finish before the memory goes
+        if (model->lodr_dev) {
+            try {
+                e.synchronize();
+            } catch (...) {
+                if (fresh) {
+                    try { e.dev_free(fresh); } catch (...) {}
+                }
+                throw;
+            }
+        }
+        e.set_lodr_tables(tables);
+        model->lodr_serial = fresh ? ++g_hw_serial : 0;
+        model->lodr_lm = std::move(copy);
+        model->lodr_host = std::move(host);
+        void* old = model->lodr_dev;
+        model->lodr_dev = fresh;
         if (old) e.dev_free(old);
     });
 }
@@ -1504,6 +1570,8 @@ static void rnn_lm_rescore(k2hip_model* model, k2hip_offline_stream_t* const* st
     std::vector<float> totals((size_t)Hn);
     e.rnn_lm_score_host(ids.data(), off.data(), Hn, true, nullptr, totals.data());
     const float scale = model->rnn_scale;
+    // LODR: lodr_i on the host, the model's scaled automaton walked over the alternative's tokens (a list is at most 8 short hypotheses)
+    const LodrHost* lodr = model->lodr_host.get();
     int at = 0;
     for (int b = 0; b < B; b++) {
         std::vector<BeamAlt>& alts = streams[b]->alts;
@@ -1513,6 +1581,10 @@ static void rnn_lm_rescore(k2hip_model* model, k2hip_offline_stream_t* const* st
             alts[i].lm_score = totals[(size_t)at++];
             volatile float term = scale * alts[i].lm_score;   // (the product rounded to float32, then the sum: no contraction)
             volatile float sum = alts[i].score + term;
+            if (lodr) {   // (score_i + fl32(scale lm_i)) + lodr_i
+                alts[i].lodr_score = lodr->total(alts[i].tokens.data(), alts[i].tokens.size());
+                sum = sum + alts[i].lodr_score;
+            }
             key[i] = ctc ? sum : sum / (float)(alts[i].tokens.size() + 2);
         }
         std::vector<size_t> ord(N);
@@ -2226,6 +2298,8 @@ int32_t k2hip_online_step(k2hip_model_t* model, k2hip_online_stream_t* const* st
         int lm_start = 0;
         int K = 0;   // the search of this tick: 0 = greedy (and a CTC model's own search), K = modified beam search with beam K
         NlmStreamCall nlm;   // the neural LM fusion setting this tick's beam search runs with
+        uint64_t lodr_serial = 0;   // the LODR setting this tick's beam search runs with (0 = none, or no active fusion), its start state
+        int lodr_start = 0;
         if (!c.ctc) {
             EngineLock lk(e);
             K = e.beam();
@@ -2237,6 +2311,8 @@ int32_t k2hip_online_step(k2hip_model_t* model, k2hip_online_stream_t* const* st
             lm_serial = K > 0 ? model->lm_serial : 0;
             lm_start = model->lm_start;
             if (K > 0) nlm.read(model);
+            lodr_serial = nlm.active ? model->lodr_serial : 0;   // (LODR acts only beside the neural LM)
+            lodr_start = lodr_serial ? model->lodr_host->start : 0;
         }
         std::vector<int> idx;
         int CK = 0;   // a CTC model's streams under the carried prefix search: their beam (every stream of the list carries the same setting)
@@ -2281,6 +2357,9 @@ int32_t k2hip_online_step(k2hip_model_t* model, k2hip_online_stream_t* const* st
                        "online step: stream %d has decoded %lld frames with another n-gram LM setting (k2hip_set_ngram_lm changed or cleared "
                        "it) and its hypotheses carry that LM's states -- reset the stream first", idx[r], s->beam->frames());
             nlm.check(s->nlm.get(), s->beam ? s->beam->frames() : 0, "online step", idx[r]);
+            K2_REQUIRE(!s->beam || s->beam->frames() == 0 || s->beam->lodr_serial() == lodr_serial,
+                       "online step: stream %d has decoded %lld frames with another LODR setting (k2hip_set_lodr_lm changed or cleared it) and "
+                       "its hypotheses carry that LM's states -- reset the stream first", idx[r], s->beam->frames());
         }
         // the new frames' host copy is collected after the step (one wait for the device per tick); whatever way this call ends -- an
         // allocation failure below included -- the outstanding download is collected before the streams' Speech can move
@@ -2333,7 +2412,8 @@ int32_t k2hip_online_step(k2hip_model_t* model, k2hip_online_stream_t* const* st
         std::vector<int32_t> ts, n;
         std::vector<int> bin, bout;   // modified beam search: the streams' saved hypotheses in, the surviving ones out
         bool any_hw = false;
-        const bool with_lm = lm_serial != 0;
+        const bool with_lm = lm_serial != 0, with_lodr = lodr_serial != 0;
+        const int planes = 1 + (with_lm ? 1 : 0) + (with_lodr ? 1 : 0);   // graph states | LM states | LODR states
         std::vector<BeamHwStream> graphs;
         std::vector<int> st_in, st_out;
         const BeamResumeLayout RL{std::max(K, 1), Tp};
@@ -2348,21 +2428,23 @@ int32_t k2hip_online_step(k2hip_model_t* model, k2hip_online_stream_t* const* st
                 }
                 if (s->beam->frames() == 0) {
                     s->beam->begin_lm(lm_serial, with_lm ? lm_start : 0);
+                    s->beam->begin_lodr(lodr_serial, lodr_start);
                     nlm.begin(s->nlm);
                 }
                 s->beam->fill_in(bin.data() + (size_t)r * RL.in_ints(), Tp);
                 any_hw = any_hw || s->hw;
             }
-            any_hw = any_hw || with_lm;   // (the LM states ride in the same side blocks, behind the graph states)
+            any_hw = any_hw || with_lm || with_lodr;   // (the LM and LODR states ride in the same side blocks, behind the graph states)
             if (any_hw) {   // hotword graphs / LM: the side blocks of the tick (neither anywhere: the unbiased call, unchanged)
                 graphs.resize((size_t)R);
-                st_in.resize((size_t)R * K * (with_lm ? 2 : 1));
-                st_out.resize((size_t)R * K * (with_lm ? 2 : 1));
+                st_in.resize((size_t)R * K * planes);
+                st_out.resize((size_t)R * K * planes);
                 for (int r = 0; r < R; r++) {
                     k2hip_online_stream* s = streams[idx[r]];
                     if (s->hw) graphs[(size_t)r] = s->hw->tables;
                     s->beam->fill_states(st_in.data() + (size_t)r * K);
                     if (with_lm) s->beam->fill_lm_states(st_in.data() + (size_t)(R + r) * K);
+                    if (with_lodr) s->beam->fill_lodr_states(st_in.data() + ((size_t)(planes - 1) * R + r) * K);
                 }
             }
         } else if (CK > 0) {   // the carried prefixes in, the survivors out
@@ -2413,6 +2495,10 @@ int32_t k2hip_online_step(k2hip_model_t* model, k2hip_online_stream_t* const* st
                 lm_raced = true;
                 failf(K2HIP_ERR_INVALID, "online step: the neural LM fusion setting changed while this step was being prepared; call again");
             }
+            if (K > 0 && (nlm.active ? model->lodr_serial : 0) != lodr_serial) {   // (k2hip_set_lodr_lm takes this lock too)
+                lm_raced = true;
+                failf(K2HIP_ERR_INVALID, "online step: k2hip_set_lodr_lm changed the LODR LM while this step was being prepared; call again");
+            }
             if (nlm.active) {   // the streams' state blocks (taken at a stream's first fused chunk), staged with the in blocks
                 try {
                     for (int r = 0; r < R; r++) nlm.stage(model, r, R, K, *streams[idx[r]]->nlm);
@@ -2424,7 +2510,7 @@ int32_t k2hip_online_step(k2hip_model_t* model, k2hip_online_stream_t* const* st
             }
             if (K > 0 && any_hw)
                 e.online_step_beam_hw(slots.data(), chunks.data(), plens.data(), nch.data(), R, K, bin.data(), bout.data(),
-                                      Engine::BeamHwIO{graphs.data(), st_in.data(), st_out.data(), with_lm}, all_mirrored ? heads.data() : nullptr);
+                                      Engine::BeamHwIO{graphs.data(), st_in.data(), st_out.data(), with_lm, with_lodr}, all_mirrored ? heads.data() : nullptr);
             else if (K > 0)
                 e.online_step_beam(slots.data(), chunks.data(), plens.data(), nch.data(), R, K, bin.data(), bout.data(),
                                    all_mirrored ? heads.data() : nullptr);
@@ -2477,7 +2563,8 @@ int32_t k2hip_online_step(k2hip_model_t* model, k2hip_online_stream_t* const* st
                 const float* yp = ypb.empty() ? nullptr : ypb.data() + (size_t)r * K * Tp;
                 if (nlm.active) nlm.flip(*s->nlm);
                 if (any_hw) s->beam->apply_out_states(bout.data() + (size_t)r * RL.out_ints(), Tp, st_out.data() + (size_t)r * K, yp,
-                                                      with_lm ? st_out.data() + (size_t)(R + r) * K : nullptr);
+                                                      with_lm ? st_out.data() + (size_t)(R + r) * K : nullptr,
+                                                      with_lodr ? st_out.data() + ((size_t)(planes - 1) * R + r) * K : nullptr);
                 else s->beam->apply_out(bout.data() + (size_t)r * RL.out_ints(), Tp, yp);
                 s->hyp[0] = s->beam->hyp_last(0);
                 s->hyp[1] = s->beam->hyp_last(1);
@@ -2663,6 +2750,8 @@ int32_t k2hip_beam_search_chunk(k2hip_model_t* model, k2hip_beam_stream_t* const
         uint64_t lm_serial = 0;   // the n-gram LM this call runs with (0 = none) and its start state
         int lm_start = 0;
         NlmStreamCall nlm;        // the neural LM fusion setting this call runs with
+        uint64_t lodr_serial = 0; // the LODR setting this call runs with (0 = none, or no active fusion) and its start state
+        int lodr_start = 0;
         {
             EngineLock lk(model->engine);
             K2_REQUIRE(!model->engine.has_hotwords(), "beam search chunk: hotword biasing covers the offline modified beam search only, not the "
@@ -2670,6 +2759,9 @@ int32_t k2hip_beam_search_chunk(k2hip_model_t* model, k2hip_beam_stream_t* const
             lm_serial = model->lm_serial;
             lm_start = model->lm_start;
             nlm.read(model);
+            // (LODR acts only beside the neural LM: without an active streaming fusion the setting is ignored, as if none were set)
+            lodr_serial = nlm.active ? model->lodr_serial : 0;
+            lodr_start = lodr_serial ? model->lodr_host->start : 0;
         }
         std::vector<const k2hip_beam_stream*> seen(streams, streams + B);
         for (int b = 0; b < B; b++) {
@@ -2688,9 +2780,15 @@ int32_t k2hip_beam_search_chunk(k2hip_model_t* model, k2hip_beam_stream_t* const
                        "beam search chunk: stream %d has searched %lld frames with another n-gram LM setting (k2hip_set_ngram_lm changed or "
                        "cleared it) and its hypotheses carry that LM's states -- reset the stream first", b, streams[b]->hist.frames());
         for (int b = 0; b < B; b++) nlm.check(streams[b]->nlm.get(), streams[b]->hist.frames(), "beam search chunk", b);
+        const bool with_lodr = lodr_serial != 0;
+        for (int b = 0; b < B; b++)
+            K2_REQUIRE(streams[b]->hist.frames() == 0 || streams[b]->hist.lodr_serial() == lodr_serial,
+                       "beam search chunk: stream %d has searched %lld frames with another LODR setting (k2hip_set_lodr_lm changed or cleared "
+                       "it) and its hypotheses carry that LM's states -- reset the stream first", b, streams[b]->hist.frames());
         for (int b = 0; b < B; b++)
             if (streams[b]->hist.frames() == 0) {
                 streams[b]->hist.begin_lm(lm_serial, with_lm ? lm_start : 0);
+                streams[b]->hist.begin_lodr(lodr_serial, lodr_start);
                 nlm.begin(streams[b]->nlm);
             }
         const BeamResumeLayout L{K, Tc};
@@ -2698,18 +2796,20 @@ int32_t k2hip_beam_search_chunk(k2hip_model_t* model, k2hip_beam_stream_t* const
         for (int b = 0; b < B; b++) streams[b]->hist.fill_in(bin.data() + (size_t)b * L.in_ints(), Tc);
         // hotword graphs / LM: with neither anywhere this is the unbiased call, unchanged; else the side blocks go along (the LM states
         // behind the graph states)
-        bool any_hw = with_lm;
+        bool any_hw = with_lm || with_lodr;
         for (int b = 0; b < B; b++) any_hw = any_hw || streams[b]->hw;
         std::vector<BeamHwStream> graphs;
         std::vector<int> st_in, st_out;
+        const int planes = 1 + (with_lm ? 1 : 0) + (with_lodr ? 1 : 0);   // graph states | LM states | LODR states
         if (any_hw) {
             graphs.resize((size_t)B);
-            st_in.resize((size_t)B * K * (with_lm ? 2 : 1));
-            st_out.resize((size_t)B * K * (with_lm ? 2 : 1));
+            st_in.resize((size_t)B * K * planes);
+            st_out.resize((size_t)B * K * planes);
             for (int b = 0; b < B; b++) {
                 if (streams[b]->hw) graphs[(size_t)b] = streams[b]->hw->tables;
                 streams[b]->hist.fill_states(st_in.data() + (size_t)b * K);
                 if (with_lm) streams[b]->hist.fill_lm_states(st_in.data() + (size_t)(B + b) * K);
+                if (with_lodr) streams[b]->hist.fill_lodr_states(st_in.data() + ((size_t)(planes - 1) * B + b) * K);
             }
         }
         std::vector<float> ypb;
@@ -2732,11 +2832,14 @@ int32_t k2hip_beam_search_chunk(k2hip_model_t* model, k2hip_beam_stream_t* const
             } nlm_guard{model->engine};
             K2_REQUIRE(model->rnn_serial == nlm.serial && model->engine.rnn_lm_stream_fusion_active() == nlm.active,
                        "beam search chunk: the neural LM fusion setting changed while this call was being prepared; call again");
+            // (... and k2hip_set_lodr_lm takes this lock too: the staged LODR states still index the tables that are set)
+            K2_REQUIRE((nlm.active ? model->lodr_serial : 0) == lodr_serial, "beam search chunk: k2hip_set_lodr_lm changed the LODR LM while "
+                                                                             "this call was being prepared; call again");
             if (nlm.active) {   // the streams' state blocks (taken at a stream's first fused chunk), staged with the in blocks
                 for (int b = 0; b < B; b++) nlm.stage(model, b, B, K, *streams[b]->nlm);
                 model->engine.set_beam_nlm_io(nlm.table.data());
             }
-            if (any_hw) model->engine.beam_chunk_host_hw(enc_out, B, Tc, K, bin.data(), bout.data(), Engine::BeamHwIO{graphs.data(), st_in.data(), st_out.data(), with_lm});
+            if (any_hw) model->engine.beam_chunk_host_hw(enc_out, B, Tc, K, bin.data(), bout.data(), Engine::BeamHwIO{graphs.data(), st_in.data(), st_out.data(), with_lm, with_lodr});
             else model->engine.beam_chunk_host(enc_out, B, Tc, K, bin.data(), bout.data());
         }
         // (only after success: a failed call leaves every stream as it was -- the LM state blocks' halves flip here too)
@@ -2745,7 +2848,8 @@ int32_t k2hip_beam_search_chunk(k2hip_model_t* model, k2hip_beam_stream_t* const
             if (nlm.active) nlm.flip(*streams[b]->nlm);
             const float* yp = ypb.empty() ? nullptr : ypb.data() + (size_t)b * K * Tc;
             if (any_hw) streams[b]->hist.apply_out_states(bout.data() + (size_t)b * L.out_ints(), Tc, st_out.data() + (size_t)b * K, yp,
-                                                          with_lm ? st_out.data() + (size_t)(B + b) * K : nullptr);
+                                                          with_lm ? st_out.data() + (size_t)(B + b) * K : nullptr,
+                                                          with_lodr ? st_out.data() + ((size_t)(planes - 1) * B + b) * K : nullptr);
             else streams[b]->hist.apply_out(bout.data() + (size_t)b * L.out_ints(), Tc, yp);
         }
     });
@@ -3848,6 +3952,13 @@ int32_t k2hip_rnn_lm_score(k2hip_model_t* model, const int64_t* tokens, const in
         if (Hn == 0) return;
         NEED(offsets); NEED(totals);
         model->engine.rnn_lm_score_host(tokens, offsets, Hn, with_eos != 0, token_log_probs, totals);
+    });
+}
+int32_t k2hip_offline_stream_get_alternative_lodr_score(const k2hip_offline_stream_t* s, int32_t i, float* lodr_total) {
+    return guard([&] {
+        NEED(s); NEED(lodr_total);
+        K2_REQUIRE(i >= 0 && i < (int32_t)s->alts.size(), "alternative %d of %zu", i, s->alts.size());
+        *lodr_total = s->alts[(size_t)i].lodr_score;
     });
 }
 int32_t k2hip_offline_stream_get_alternative_lm_score(const k2hip_offline_stream_t* s, int32_t i, float* lm_total) {

@@ -27,6 +27,8 @@
 // state then lives in device blocks between the calls: BeamArgs::nlm_io).  The NLM instantiation of the
 // step reads the parent's row of the LM's log-probs for a selected real token, adds the scaled term after the n-gram term, and leaves
 // for the LM launches behind it each new slot's parent slot and appended token and the frame's "something appended" flag.
+// LODR (BeamArgs::lodr; dst_in / dst_out resumed): a second automaton with a state of its own per hypothesis, in the NLM instantiation
+// only and behind a null check there: a second pass of beam_lm_walk beside the first, its term added last in the merge section.
 #include <type_traits>
 
 #include <atomic>
@@ -60,6 +62,10 @@ __global__ void k_beam_init(BeamState s, int B) {
         s.lst[i] = s.lm.start;
         s.lst[B * s.K + i] = s.lm.start;
     }
+    if (s.dst) {
+        s.dst[i] = s.lodr.start;
+        s.dst[B * s.K + i] = s.lodr.start;
+    }
     if (k == 0) s.nhyp[i / s.K] = 1;
 }
 // the saved hypotheses of every stream (resume): hypothesis k = saved hypothesis k with an empty suffix
@@ -84,6 +90,10 @@ __global__ void k_beam_resume_init(BeamState s, int B) {
     if (s.lst) {
         s.lst[i] = (s.lst_in && k < nh) ? s.lst_in[i] : 0;
         s.lst[B * K + i] = 0;
+    }
+    if (s.dst) {
+        s.dst[i] = (s.dst_in && k < nh) ? s.dst_in[i] : 0;
+        s.dst[B * K + i] = 0;
     }
     if (k == 0) s.nhyp[b] = nh;
 }
@@ -163,6 +173,10 @@ struct HypView {
     int* nflag = nullptr;
     int nbase = 0;
     float nscale = 0.f;
+    // LODR (the NLM instantiation only; lodr.states null: none): the state of each hypothesis in the second automaton at frame t / t + 1
+    const int* dst_c = nullptr;
+    int* dst_n = nullptr;
+    BeamLm lodr;
 };
 // a + fl32(s q): the product rounded on its own (no contraction into an fma)
 __device__ __forceinline__ float add_scaled(float a, float s, float q) {
@@ -294,6 +308,10 @@ __device__ void beam_step_body(const HypView& hv, const float* lg, int ldl, int 
     // n-gram LM: term and next state of every selected candidate, a wave each, into LDS for the merge section (candv is used up too)
     float* lmterm = candv;
     int* lmnext = reinterpret_cast<int*>(candv) + kMaxBeam;
+    // LODR: the same of the second automaton, behind them
+    static_assert(4 * kMaxBeam <= kMaxBeam * kMaxBeam, "the LM and LODR terms and next states live in candv");
+    [[maybe_unused]] float* dterm = candv + 2 * kMaxBeam;
+    [[maybe_unused]] int* dnext = reinterpret_cast<int*>(candv) + 3 * kMaxBeam;
     if constexpr (HW) {
         if (hv.lm.states)
             for (int r = wave; r < want; r += BT / 64) {
@@ -302,6 +320,16 @@ __device__ void beam_step_body(const HypView& hv, const float* lg, int ldl, int 
                 int nx = hv.lst_c[hr];
                 if (tr != K2HIP_BLANK_ID && tr != K2HIP_UNK_ID) beam_lm_walk(hv.lm, nx, tr, lane, &term, &nx);
                 if (lane == 0) { lmterm[r] = term; lmnext[r] = nx; }
+            }
+    }
+    if constexpr (NLM) {
+        if (hv.lodr.states)
+            for (int r = wave; r < want; r += BT / 64) {
+                const int hr = topi[r] / V, tr = topi[r] % V;
+                float term = 0.f;
+                int nx = hv.dst_c[hr];
+                if (tr != K2HIP_BLANK_ID && tr != K2HIP_UNK_ID) beam_lm_walk(hv.lodr, nx, tr, lane, &term, &nx);
+                if (lane == 0) { dterm[r] = term; dnext[r] = nx; }
             }
     }
     {
@@ -367,6 +395,7 @@ __device__ void beam_step_body(const HypView& hv, const float* lg, int ldl, int 
                     if (hv.lm.states) tv[r] += lmterm[r];   // (sum + hotword bonus) + LM term
                     if constexpr (NLM) {   // ... + fl32(scale q_parent[token])
                         if (tr != K2HIP_BLANK_ID && tr != K2HIP_UNK_ID) tv[r] = add_scaled(tv[r], hv.nscale, hv.nq_c[(long long)hr * V + tr]);
+                        if (hv.lodr.states) tv[r] += dterm[r];   // ... + Step_lodr(state, token), last
                     }
                 }
             }
@@ -428,6 +457,7 @@ __device__ void beam_step_body(const HypView& hv, const float* lg, int ldl, int 
             if constexpr (NLM) {   // (empty slots still go through the LM launches: a valid parent, nothing appended)
                 hv.npar[k] = hv.nbase;
                 hv.ntok[k] = -1;
+                if (hv.dst_n) hv.dst_n[k] = 0;
             }
         }
         *hv.nhyp = nN;
@@ -469,6 +499,7 @@ __device__ void beam_step_body(const HypView& hv, const float* lg, int ldl, int 
                 hv.npar[slot] = hv.nbase + hr;
                 hv.ntok[slot] = realr ? tr : -1;
                 if (realr) *hv.nflag = 1;
+                if (hv.dst_n) hv.dst_n[slot] = dnext[r];
             }
             // decoder context of the new hypothesis: last two of [c0, c1] + ys, [c0, c1] = the saved hypothesis' context (resume) or
             // [blank, blank]
@@ -535,6 +566,11 @@ __global__ __launch_bounds__(BT) void k_beam_step(BeamState s, const float* __re
         hv.nflag = s.nflag + t;
         hv.nbase = b * K;
         hv.nscale = s.nscale;
+        if (s.dst) {
+            hv.dst_c = s.dst + cur * BK + b * K;
+            hv.dst_n = s.dst + nxt * BK + b * K;
+            hv.lodr = s.lodr;
+        }
     }
     beam_step_body<BT, HW, NLM>(hv, logits + (long long)b * K * V, V, V, t, scratch, pscratch);
 }
@@ -548,7 +584,7 @@ template <bool HW>
 __device__ void beam_resume_write(const int* in, int* out, int K, int Tp, int cap, int nh, const float* lp, const long long* ctx,
                                   const int* n, const int* org, const int* ys, const int* ts, const int* st = nullptr,
                                   const float* pending = nullptr, int* st_out = nullptr, const float* yp = nullptr, float* yp_out = nullptr,
-                                  const int* lst = nullptr, int* lst_out = nullptr) {
+                                  const int* lst = nullptr, int* lst_out = nullptr, const int* dst = nullptr, int* dst_out = nullptr) {
     const BeamResumeLayout L{K, Tp};
     const int tid = threadIdx.x;
     if (tid == 0) {
@@ -575,6 +611,7 @@ __device__ void beam_resume_write(const int* in, int* out, int K, int Tp, int ca
         if constexpr (HW) {
             if (st_out) st_out[k] = live ? st[k] : 0;
             if (lst_out) lst_out[k] = live ? lst[k] : 0;
+            if (dst_out) dst_out[k] = live ? dst[k] : 0;
         }
     }
     for (int i = tid; i < nh * Tp; i += blockDim.x) {
@@ -598,7 +635,8 @@ __global__ void k_beam_resume_final(BeamState s, int fin, int B, int* __restrict
                                 s.st + fin * BK + b * K, s.hw_streams ? s.hw_streams[b].pending : s.hw_pending,
                                 s.st_out ? s.st_out + b * K : nullptr, s.yp ? s.yp + (fin * BK + (long long)b * K) * s.cap : nullptr,
                                 s.yp_out ? s.yp_out + (long long)b * K * s.Tp : nullptr, s.lst ? s.lst + fin * BK + b * K : nullptr,
-                                s.lst_out ? s.lst_out + b * K : nullptr);
+                                s.lst_out ? s.lst_out + b * K : nullptr, s.dst ? s.dst + fin * BK + b * K : nullptr,
+                                (s.dst && s.dst_out) ? s.dst_out + b * K : nullptr);
     else
         beam_resume_write<false>(s.rin + (long long)b * L.in_ints(), rout + (long long)b * L.out_ints(), K, s.Tp, s.cap, s.nhyp[b], s.lp + b * K,
                                  s.ctx + 2 * (long long)b * K, s.n + fin * BK + b * K, s.org + fin * BK + b * K,
@@ -983,6 +1021,9 @@ void beam_search(const Ctx& ctx, const DecJoinW& w, const BeamArgs& a) {
     for (int k = 0; nlm && k < a.nlm.dev.L; k++) K2_REQUIRE(a.nlm.dev.wcat[k] && a.nlm.dev.bias[k], "beam search: neural LM fusion: layer %d has no weights", k);
     K2_REQUIRE(!a.lm.states || (a.lm.arc_tok && a.lm.arc_lp && a.lm.arc_next && a.lm.uni_lp && a.lm.uni_next), "beam search: incomplete n-gram LM tables");
     K2_REQUIRE(!(a.lm.states && a.rin) || (a.lst_in && a.lst_out), "beam search: the resumed search with an n-gram LM needs its LM state blocks");
+    K2_REQUIRE(!a.lodr.states || nlm, "beam search: LODR runs only beside the neural LM fusion");
+    K2_REQUIRE(!a.lodr.states || (a.lodr.arc_tok && a.lodr.arc_lp && a.lodr.arc_next && a.lodr.uni_lp && a.lodr.uni_next), "beam search: incomplete LODR tables");
+    K2_REQUIRE(!(a.lodr.states && a.rin) || ctx.dry || (a.dst_in && a.dst_out), "beam search: the resumed search with LODR needs its LODR state blocks");
     K2_REQUIRE(!a.hw_next || (a.hw_bonus && a.hw_pending), "beam search: incomplete hotword tables");
     K2_REQUIRE(!(a.hw_next && a.hw_streams), "beam search: one hotword graph or one per stream, not both");
     K2_REQUIRE(!a.hw_streams || (a.rin && a.st_in && a.st_out), "beam search: per-stream hotword graphs belong to the resumed search and need its state blocks");
@@ -1103,6 +1144,10 @@ void beam_search(const Ctx& ctx, const DecJoinW& w, const BeamArgs& a) {
         s.ntok = ar.take<int>(M);
         s.nflag = ar.take<int>(a.Tp);
         s.nscale = a.nlm.scale;
+        if (a.lodr.states) {
+            s.dst = ar.take<int>((int64_t)2 * M);
+            s.lodr = a.lodr; s.dst_in = a.dst_in; s.dst_out = a.dst_out;
+        }
         if (!ctx.dry) K2_HIP(hipMemsetAsync(s.nflag, 0, sizeof(int) * (size_t)a.Tp, ctx.stream));
         // (the resumed form: the streams' carried blocks, the in blocks' first int naming the live slots)
         if (a.rin) nlm_load_streams(ctx, nd, a.nlm_io, a.rin, BeamResumeLayout{K, a.Tp}.in_ints(), nh, nc, nq, B, K);

@@ -116,6 +116,7 @@ struct BeamAlt {
     std::vector<float> token_log_probs;
     float score = 0.f;
     float lm_score = 0.f;   // the neural LM's total of the alternative (k2hip_set_rnn_lm rescoring of an offline list); 0: not rescored
+    float lodr_score = 0.f; // the LODR total of the alternative (k2hip_set_lodr_lm, added in that rescoring); 0: not rescored or no LODR LM
 };
 
 // One stream's hypotheses between chunks and its result (the best hypothesis, materialised incrementally).
@@ -127,6 +128,7 @@ class BeamHistory {
         int ctx[2];        // decoder context: the last two tokens of [blank, blank] + ys
         int st = 0;        // state of the stream's hotword graph (0 = the root; always 0 without a graph)
         int lst = 0;       // state of the model's n-gram LM (always 0 without an LM)
+        int dst = 0;       // state of the model's LODR LM (always 0 without one, and outside a fused search)
     };
     explicit BeamHistory(int K = 1, int blank = 0) : K_(K), blank_(blank) { reset(); }
     int beam() const { return K_; }
@@ -222,17 +224,29 @@ class BeamHistory {
     void fill_lm_states(int* lst_in) const {
         for (int k = 0; k < K_; k++) lst_in[k] = k < (int)hyps_.size() ? hyps_[(size_t)k].lst : 0;
     }
+    // LODR: the same rule for the second automaton, which runs only in a fused search.  begin_lodr (only while no frame has been
+    // searched) notes the setting's serial number (0 = none or not active) and puts the start hypothesis into that LM's start state.
+    void begin_lodr(uint64_t serial, int start_state) {
+        lodr_serial_ = serial;
+        hyps_[0].dst = start_state;
+    }
+    uint64_t lodr_serial() const { return lodr_serial_; }
+    void fill_lodr_states(int* dst_in) const {
+        for (int k = 0; k < K_; k++) dst_in[k] = k < (int)hyps_.size() ? hyps_[(size_t)k].dst : 0;
+    }
     // hotword side block in: the saved hypotheses' graph states [K]
     void fill_states(int* st_in) const {
         for (int k = 0; k < K_; k++) st_in[k] = k < (int)hyps_.size() ? hyps_[(size_t)k].st : 0;
     }
     // apply_out + the hotword side block out: the survivors' graph states [K]
-    // (lst_out: the survivors' LM states [K], or null)
-    void apply_out_states(const int* out, int Tp, const int* st_out, const float* yp = nullptr, const int* lst_out = nullptr) {
+    // (lst_out: the survivors' LM states [K], or null; dst_out: their LODR states [K], or null)
+    void apply_out_states(const int* out, int Tp, const int* st_out, const float* yp = nullptr, const int* lst_out = nullptr,
+                          const int* dst_out = nullptr) {
         apply_out(out, Tp, yp);
         for (size_t k = 0; k < hyps_.size(); k++) {
             hyps_[k].st = st_out[k];
             if (lst_out) hyps_[k].lst = lst_out[k];
+            if (dst_out) hyps_[k].dst = dst_out[k];
         }
     }
     // the device search's out block of that chunk: the new hypotheses, the best one, the result; yp: the side block [K][Tp] with the
@@ -297,6 +311,7 @@ class BeamHistory {
 
     int K_, blank_;
     uint64_t lm_serial_ = 0;
+    uint64_t lodr_serial_ = 0;
     std::shared_ptr<const std::vector<float>> pending_;   // (kept across reset(): the graph stays attached)
     SeqTree seq_;
     PathTree path_;

@@ -923,6 +923,7 @@ Engine::SearchExtras Engine::beam_device(const Ctx& c, const float* enc, int B, 
     if (keep_nbest && rnn_lm_fusion_active()) {   // (the pipelined route and recognize_long keep no list: they ignore the switch)
         a.nlm.dev = rnn_dev_;
         a.nlm.scale = rnn_fuse_scale_;
+        a.lodr = lodr_;   // (LODR acts only where the neural LM does)
     }
     if (nbest_ > 0 && keep_nbest) {
         const int64_t NB = (int64_t)B * nbest_;
@@ -962,6 +963,11 @@ void Engine::beam_resume_device(const Ctx& c, const float* enc, int B, int Tp, i
             a.lst_in = hw->st_in + (size_t)B * K;
             a.lst_out = hw->st_out + (size_t)B * K;
         }
+        if (hw->lodr && d_nlm) {   // (the last plane of the side blocks)
+            a.lodr = lodr_;
+            a.dst_in = hw->st_in + (size_t)B * K * (hw->planes() - 1);
+            a.dst_out = hw->st_out + (size_t)B * K * (hw->planes() - 1);
+        }
     }
     if (d_nlm) {   // neural LM shallow fusion carried across chunks: the streams' state blocks (staged with the in blocks)
         a.nlm.dev = rnn_dev_;
@@ -997,7 +1003,7 @@ void Engine::beam_chunk_impl(const float* enc, int B, int Tp, int K, const int* 
     // ONE upload [enc | in blocks | hotwords: states in, graphs] and ONE download [flag | out blocks | hotwords: states out]
     const int64_t nb_enc = (int64_t)sizeof(float) * B * Tp * cf.J, nb_in = (int64_t)sizeof(int) * B * L.in_ints(),
                   nb_out = (int64_t)sizeof(int) * B * L.out_ints();
-    const int64_t nb_st = hw ? (int64_t)sizeof(int) * B * K * (hw->lm ? 2 : 1) : 0, nb_g = hw ? (int64_t)sizeof(BeamHwStream) * B : 0;
+    const int64_t nb_st = hw ? (int64_t)sizeof(int) * B * K * hw->planes() : 0, nb_g = hw ? (int64_t)sizeof(BeamHwStream) * B : 0;
     // (an active streaming neural LM fusion: the streams' block-pointer table rides behind the graphs)
     const NlmStreamIO* nlm_io = nlm_io_host_;
     K2_REQUIRE(!nlm_io || rnn_lm_stream_fusion_active(), "beam chunk: state blocks without an active streaming neural LM fusion");
@@ -1020,7 +1026,7 @@ void Engine::beam_chunk_impl(const float* enc, int B, int Tp, int K, const int* 
         d_ovf = reinterpret_cast<int*>(d + o_ovf);
         if (!c.dry) K2_HIP(hipMemcpyAsync(d, stage, (size_t)in_bytes, hipMemcpyHostToDevice, c.stream));
         const BeamHwIO dhw{reinterpret_cast<const BeamHwStream*>(d + o_g), reinterpret_cast<const int*>(d + o_st),
-                           reinterpret_cast<int*>(d + in_bytes + nb_out), hw && hw->lm};
+                           reinterpret_cast<int*>(d + in_bytes + nb_out), hw && hw->lm, hw && hw->lodr};
         beam_resume_device(c, reinterpret_cast<const float*>(d), B, Tp, K, reinterpret_cast<const int*>(d + o_in),
                            reinterpret_cast<int*>(d + in_bytes), d_ovf, hw ? &dhw : nullptr,
                            nlm_io ? reinterpret_cast<const NlmStreamIO*>(d + o_nl) : nullptr);

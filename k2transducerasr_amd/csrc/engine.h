@@ -337,6 +337,10 @@ class Engine {
         int* st_out;
         // the model's n-gram LM runs in this call: st_in / st_out are [2][B][K], the hypotheses' LM states behind their graph states
         bool lm = false;
+        // the model's LODR LM runs in this call (only beside an active streaming neural LM fusion): one more [B][K] plane behind those,
+        // the hypotheses' LODR states
+        bool lodr = false;
+        int planes() const { return 1 + (lm ? 1 : 0) + (lodr ? 1 : 0); }
     };
     void online_step_beam_hw(const int* slots, const float* const* chunks, const long long* plens, const int* nchunks, int B, int K,
                              const int* beam_in, int* beam_out, const BeamHwIO& hw, const int* fifo_heads = nullptr);
@@ -381,6 +385,10 @@ class Engine {
     // k2hip_set_ngram_lm, as for the hotword tables); null tables = none
     void set_ngram_tables(const BeamLm& lm) { lm_ = lm; }
     bool has_ngram_lm() const { return lm_.states != nullptr; }
+    // LODR LM (BeamArgs::lodr): the tables scaled by the weight <= 0, device memory owned by the caller (api.cpp k2hip_set_lodr_lm); null
+    // tables = none.  Read only by a search the neural LM is fused into; every other search ignores them.
+    void set_lodr_tables(const BeamLm& lm) { lodr_ = lm; }
+    bool has_lodr_lm() const { return lodr_.states != nullptr; }
     // N-best and token log-probs of the synchronous modified beam search (semantics in include/k2hip.h): 0 = off, nothing is computed
     // or kept beyond the best hypothesis; n >= 1 = every search keeps its first n final hypotheses in pick order, each with its token
     // log-probs, and last_nbest() holds them after the call (entry 0 = the result the call returned)
@@ -718,6 +726,7 @@ class Engine {
     const int* hw_next_ = nullptr;
     const float *hw_bonus_ = nullptr, *hw_pending_ = nullptr;
     BeamLm lm_;
+    BeamLm lodr_;
     // CTC search by-products of the last synchronous call (NumTrailingBlank bookkeeping, OfflineRecognizer.cs:392-397)
     std::vector<int> last_trail_, last_any_;
     std::vector<int> last_beam_trace_;

@@ -803,6 +803,13 @@ struct BeamState {       // device arrays; hypotheses double-buffered by frame p
     int* ntok = nullptr;
     int* nflag = nullptr;
     float nscale = 0.f;
+    // LODR (the neural instantiation only): the hypotheses' states of the second automaton [2][B][K] beside lst, its tables (every
+    // weight times the scale <= 0; null: none) and the resumed search's side blocks.  (Behind everything else: the members the other
+    // instantiations read keep their place in the kernels' argument block.)
+    int* dst = nullptr;
+    BeamLm lodr;
+    const int* dst_in = nullptr;
+    int* dst_out = nullptr;
 };
 struct BeamArgs {
     const float* enc;    // [B, Tp, J]
@@ -849,6 +856,13 @@ struct BeamArgs {
     // run behind EVERY frame and the movers of rnn_lm_fuse.hip frame the call.
     BeamNlm nlm;
     const NlmStreamIO* nlm_io = nullptr;
+    // LODR (semantics in include/k2hip.h): a second automaton, the low-order LM with every weight multiplied by its scale <= 0, walked
+    // beside the n-gram LM's with a state of its own per hypothesis; its term is added last, ((.. + n-gram term) + neural term) +
+    // Step_lodr(state, token).  Only beside the neural LM (nlm on); lodr.states == null: none.  Resumed: the saved hypotheses' states
+    // in dst_in [B][K], the survivors' out dst_out [B][K], side blocks as lst_in / lst_out are.
+    BeamLm lodr;
+    const int* dst_in = nullptr;
+    int* dst_out = nullptr;
     // Token log-probs and N-best (semantics in include/k2hip.h).  Both null: nothing is kept beyond the best hypothesis.  nb: the
     // offline search also writes its final hypotheses in pick order; yp_out [B][K][Tp] (resume): the token log-probs of each
     // survivor's suffix, a side block beside rout as st_out is.

@@ -352,7 +352,7 @@ void Engine::online_step_impl(const int* slots, const float* const* chunks, cons
     const CtcPrefixBiasIO* cbias = cpx ? cpx->bias : nullptr;
     const CtcPrefixResumeBiasLayout CSL{cpx ? cpx->K : 1};
     const int64_t nb_cso = cbias ? (int64_t)sizeof(int) * CSL.out_ints() * B : 0;
-    const int64_t nb_hst = bhw ? (int64_t)sizeof(int) * beam->K * B * (bhw->lm ? 2 : 1) : cbias ? (int64_t)sizeof(int) * CSL.in_ints() * B : 0,
+    const int64_t nb_hst = bhw ? (int64_t)sizeof(int) * beam->K * B * bhw->planes() : cbias ? (int64_t)sizeof(int) * CSL.in_ints() * B : 0,
                   nb_hg = bhw || cbias ? (int64_t)sizeof(BeamHwStream) * B : 0;
     const int64_t nb_bout = beam ? (int64_t)sizeof(int) * RL.out_ints() * B + nb_hst : cpx ? (int64_t)sizeof(int) * CL.out_ints() * B + nb_cso : 0,
                   o_hout = nb_bout - (beam ? nb_hst : nb_cso);
@@ -400,7 +400,7 @@ void Engine::online_step_impl(const int* slots, const float* const* chunks, cons
         int* d_chunks = reinterpret_cast<int*>(d_in + o_chunks);
         int* d_heads = reinterpret_cast<int*>(d_in + o_heads);
         const BeamHwIO dhw{reinterpret_cast<const BeamHwStream*>(d_in + o_hg), reinterpret_cast<const int*>(d_in + o_hst),
-                           reinterpret_cast<int*>(d_out + o_hout), bhw && bhw->lm};
+                           reinterpret_cast<int*>(d_out + o_hout), bhw && bhw->lm, bhw && bhw->lodr};
         if (!c.dry) {
             K2_HIP(hipEventRecord(ev_[0], c.stream));
             K2_HIP(hipMemcpyAsync(d_in, stage, (size_t)in_bytes, hipMemcpyHostToDevice, c.stream));
