@@ -1152,6 +1152,21 @@ int32_t k2hip_set_rnn_lm_fusion(k2hip_model_t* model, int32_t on);
  * frees every block, and a stream then only forgets its own.  (An online stream still has to go before its model, as before.) */
 int32_t k2hip_set_rnn_lm_stream_fusion(k2hip_model_t* model, int32_t on);
 
+/* ---- Half-precision LM weights in the fused searches ---------------------------------------------------------------------------------
+ * (no reference counterpart; DESIGN.md "Half-precision LM weights in the fused search".)
+ * half != 0: the LSTM step of BOTH fused searches above (offline and streaming) reads W_ih and W_hh rounded to f16 and rounds its input
+ * [x ; h] to f16 on the way into the matrix pipe (nearest even, subnormals kept); the products are summed in float32, and bias, cell,
+ * the carried states, the output layer, the embedding table and the LM rows stay float32.  Per model, 0 (float32) by default;
+ * K2HIP_ERR_INVALID while submitted batches are in flight.  It is a different arithmetic, hence opt-in: results are held to a twin that
+ * rounds the same operands, not to the float32 search.  With the value 0 every call issues the launches and gives the bits of before.
+ * ONLY THE FUSED SEARCHES: rescoring (k2hip_rnn_lm_score, the re-ordering in k2hip_offline_recognizer_get_results) stays float32.
+ * A CALL THAT CHANGES THE VALUE IS A NEW LM SETTING, exactly as a k2hip_set_rnn_lm call is: the fused layouts are dropped and the next
+ * fused search builds them in the new precision, the start state after sos included; a fused stream that started under the other
+ * precision gets K2HIP_ERR_INVALID ("reset the stream first") on its next chunk.  A call with the current value does nothing.
+ * AN LM THAT DOES NOT FIT: a weight of W_ih / W_hh that is not finite in f16 (|w| >= 65520, or not finite to begin with) is
+ * K2HIP_ERR_INVALID from the first fused search under half precision, before any device work; the model still decodes under float32. */
+int32_t k2hip_set_rnn_lm_fusion_precision(k2hip_model_t* model, int32_t half);
+
 /* ---- LODR: low-order density ratio beside the neural LM ------------------------------------------------------------------------------
  * (no reference counterpart; the project's own semantics after icefall's modified_beam_search_LODR / modified_beam_search_lm_rescore_LODR
  * and sherpa's lodr_fst / lodr_scale.  DESIGN.md "LODR".)  A low-order n-gram LM, usually a bi-gram trained on the acoustic model's own

@@ -281,7 +281,11 @@ int32_t k2hip_debug_rnn_lm_fusion_stats(k2hip_model_t* model, int64_t* searches,
 /* milliseconds per k_nlm_advance launch of `rows` rows that all append, input and hidden width H (2 H products per gate; the rescoring
  * step of k2hip_debug_rnn_lm_step_bench sums H), a scattered parent map, pseudo-random operands, `iters` launches between two events */
 int32_t k2hip_debug_nlm_advance_bench(k2hip_model_t* model, int32_t rows, int32_t H, int32_t iters, float* ms);
+/* the same launches through k_nlm_advance_f16 (k2hip_set_rnn_lm_fusion_precision): the same draw of weights rounded to f16 */
+int32_t k2hip_debug_nlm_advance_f16_bench(k2hip_model_t* model, int32_t rows, int32_t H, int32_t iters, float* ms);
 /* k2hip_debug_op_run ops:
+ *   "nlm_advance_f16"  the ints and buffers of "nlm_advance" below, the panel buffer holding the f16 layout (kernels.h
+ *                  RnnLmDev::wcat_h: 2 bytes per weight); ONE launch of k_nlm_advance_f16
  *   "nlm_advance"  ONE launch.  ints M, in, H, use_emb, V, live (-1: no flag; else the device flag is set to it first); bufs wcat (the
  *                  layer's panels: kernels.h RnnLmDev::wcat), bias [4H], x (emb [V][in] when use_emb, else rows [M][in]), h_par [M][H],
  *                  c_par [M][H], h_out [M][H] (out), c_out [M][H] (out), par [M] (int32), tok [M] (int32, -1: nothing appended),

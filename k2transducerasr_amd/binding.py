@@ -297,6 +297,8 @@ def _bind_rnn_lm(L):
     L.k2hip_set_rnn_lm_fusion.argtypes = [vp, C.c_int32]
     L.k2hip_debug_rnn_lm_fusion_stats.argtypes = [vp, lp, lp, lp]
     L.k2hip_debug_nlm_advance_bench.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, fp]
+    L.k2hip_debug_nlm_advance_f16_bench.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, fp]
+    L.k2hip_set_rnn_lm_fusion_precision.argtypes = [vp, C.c_int32]
     L.k2hip_set_rnn_lm_stream_fusion.argtypes = [vp, C.c_int32]
     L.k2hip_debug_rnn_lm_stream_fusion_stats.argtypes = [vp, lp, lp, lp]
     L._rnn_lm_bound = True
@@ -1038,6 +1040,13 @@ class Model:
         _bind_rnn_lm(self._L)
         self._chk(self._L.k2hip_set_rnn_lm_stream_fusion(self._h, int(bool(on))))
 
+    def set_rnn_lm_fusion_precision(self, half: bool):
+        """k2hip_set_rnn_lm_fusion_precision: the fused searches (offline and streaming) read the LSTM weights, and round [x ; h], in
+        f16 with float32 sums; state, cell, output layer and rescoring stay float32.  A change is a new LM setting: the fused layouts
+        are rebuilt by the next fused search, and fused streams of the other precision must be reset."""
+        _bind_rnn_lm(self._L)
+        self._chk(self._L.k2hip_set_rnn_lm_fusion_precision(self._h, int(bool(half))))
+
     def rnn_lm_stream_fusion_stats(self) -> dict:
         """fused chunk calls enqueued by the process; state blocks this model's streams hold; bytes of the model's block pool"""
         _bind_rnn_lm(self._L)
@@ -1050,6 +1059,13 @@ class Model:
         _bind_rnn_lm(self._L)
         ms = C.c_float()
         self._chk(self._L.k2hip_debug_nlm_advance_bench(self._h, int(rows), int(hidden_dim), int(iters), C.byref(ms)))
+        return float(ms.value)
+
+    def nlm_advance_f16_bench(self, rows: int, hidden_dim: int, iters: int = 200) -> float:
+        """milliseconds per k_nlm_advance_f16 launch (k2hip_debug_nlm_advance_f16_bench)"""
+        _bind_rnn_lm(self._L)
+        ms = C.c_float()
+        self._chk(self._L.k2hip_debug_nlm_advance_f16_bench(self._h, int(rows), int(hidden_dim), int(iters), C.byref(ms)))
         return float(ms.value)
 
     def rnn_lm_step_bench(self, rows: int, hidden_dim: int, iters: int = 200) -> dict:
@@ -1679,13 +1695,14 @@ class OfflineRecognizer:
     ctc_prefix_beam_search uses both as well (Model.set_ctc_prefix_biasing); without it the recognizer behaves as before.  rnn_lm: an
     RnnLm that rescores the N-best lists of get_results with weight rnn_lm_scale (sherpa's RNN LM rescoring); needs nbest > 1, the
     alternatives then carry lm_score.  rnn_lm_fusion=True: the LM is fused into modified_beam_search instead (Model.set_rnn_lm_fusion):
-    its term is added during the search, any nbest, and the lists are not rescored.  lodr_lm: an NgramLm (usually a bi-gram) subtracted
+    its term is added during the search, any nbest, and the lists are not rescored; rnn_lm_half=True: the fused search reads the LSTM weights in
+    f16 (Model.set_rnn_lm_fusion_precision).  lodr_lm: an NgramLm (usually a bi-gram) subtracted
     with weight lodr_scale <= 0 wherever rnn_lm acts, in the rescoring or in the fused search (Model.set_lodr_lm)."""
 
     def __init__(self, weights_path: str, device: int = 0, decoding_method: str = "greedy_search", beam: int = 4, hotwords=None,
                  hotwords_score: float = 1.5, nbest: int = 1, ngram_lm: Optional["NgramLm"] = None, ngram_lm_scale: float = 0.3,
                  ctc_prefix_biasing: bool = False, rnn_lm: Optional["RnnLm"] = None, rnn_lm_scale: float = 0.5, rnn_lm_fusion: bool = False,
-                 lodr_lm: Optional["NgramLm"] = None, lodr_scale: float = -0.1):
+                 lodr_lm: Optional["NgramLm"] = None, lodr_scale: float = -0.1, rnn_lm_half: bool = False):
         self.model = Model(weights_path, device)
         self.model.set_decoding_method(decoding_method, beam)
         if nbest != 1:   # (streams then carry .alternatives() / .token_log_probs() after get_results)
@@ -1698,6 +1715,8 @@ class OfflineRecognizer:
             self.model.set_ngram_lm(ngram_lm, ngram_lm_scale)
         if ctc_prefix_biasing:
             self.model.set_ctc_prefix_biasing(True)
+        if rnn_lm_half:
+            self.model.set_rnn_lm_fusion_precision(True)
         if rnn_lm is not None:
             self.model.set_rnn_lm(rnn_lm, rnn_lm_scale)
         if rnn_lm_fusion:
@@ -2139,14 +2158,15 @@ class OnlineRecognizer:
     (hypotheses carried from chunk to chunk: include/k2hip.h).  ngram_lm: an NgramLm fused with weight ngram_lm_scale
     under modified_beam_search (every hypothesis carries its LM state across the chunk boundary).  rnn_lm with rnn_lm_fusion=True:
     an RnnLm fused with weight rnn_lm_scale under modified_beam_search, its LSTM state carried from chunk to chunk
-    (Model.set_rnn_lm_stream_fusion); without rnn_lm_fusion the LM is attached and the streaming search ignores it.  lodr_lm: an
+    (Model.set_rnn_lm_stream_fusion); without rnn_lm_fusion the LM is attached and the streaming search ignores it; rnn_lm_half=True: the fused search reads the
+    LSTM weights in f16 (Model.set_rnn_lm_fusion_precision).  lodr_lm: an
     NgramLm subtracted with weight lodr_scale <= 0 beside the fused rnn_lm, its state carried as well (Model.set_lodr_lm); ignored
     without an active fusion.  nbest > 1: the streams keep that many alternatives."""
 
     def __init__(self, weights_path: str, device: int = 0, decoding_method: str = "greedy_search", beam: int = 4,
                  ngram_lm: Optional["NgramLm"] = None, ngram_lm_scale: float = 0.3, rnn_lm: Optional["RnnLm"] = None,
                  rnn_lm_scale: float = 0.5, rnn_lm_fusion: bool = False, nbest: int = 1, lodr_lm: Optional["NgramLm"] = None,
-                 lodr_scale: float = -0.1):
+                 lodr_scale: float = -0.1, rnn_lm_half: bool = False):
         self.model = Model(weights_path, device)
         _bind_online(self.model._L)
         self.model.set_decoding_method(decoding_method, beam)
@@ -2154,6 +2174,8 @@ class OnlineRecognizer:
             self.model.set_nbest(nbest)
         if ngram_lm is not None:
             self.model.set_ngram_lm(ngram_lm, ngram_lm_scale)
+        if rnn_lm_half:
+            self.model.set_rnn_lm_fusion_precision(True)
         if rnn_lm is not None:
             self.model.set_rnn_lm(rnn_lm, rnn_lm_scale)
         if rnn_lm_fusion:

@@ -142,6 +142,15 @@ struct k2hip_model {
     bool rnn_stream_fusion = false;
     uint64_t rnn_serial = 0;
     std::shared_ptr<NlmStreamPool> nlm_pool;
+    // k2hip_set_rnn_lm_fusion_precision: the fused searches' weights in f16.  A change drops rnn_fuse_dev; the next fused search builds
+    // it again in the new precision (rnn_fusion_ensure, called with the engine's lock held by every entry that can run a fused search).
+    bool rnn_half = false;
+    void rnn_fusion_ensure() {
+        if (!rnn_lm || rnn_fuse_dev || !(rnn_fusion || rnn_stream_fusion)) return;
+        RnnLmDev tables = engine.rnn_lm_dev();
+        rnn_fuse_dev = engine.rnn_lm_fusion_upload(*rnn_lm, &tables);
+        engine.set_rnn_lm(rnn_lm.get(), tables);
+    }
     // k2hip_set_nbest: 1 = off (the engine keeps nothing beyond the best hypothesis), n > 1 = alternatives and token log-probs are kept
     std::atomic<int> nbest{1};
     // the graphs attached to this model's streams (HwResident), by serial number; hw_uploads counts the uploads (k2hip_debug.h)
@@ -239,7 +248,7 @@ struct NlmStreamCall {
     std::vector<NlmStreamIO> table;
     std::vector<NlmCarry*> taken;   // blocks taken by this call: given back if it fails
     bool done = false;
-    void read(const k2hip_model* m);
+    void read(k2hip_model* m);
     void check(const NlmCarry* c, long long frames, const char* who, int i) const {
         const bool was = c && c->active;
         K2_REQUIRE(frames == 0 || (was == active && (!active || (c->serial == serial && c->scale == scale && c->block.carries(serial)))),
@@ -351,7 +360,8 @@ struct k2hip_beam_stream {
     std::unique_ptr<NlmCarry> nlm;    // streaming neural LM fusion: the noted setting and the state block, or null
 };
 
-void NlmStreamCall::read(const k2hip_model* m) {
+void NlmStreamCall::read(k2hip_model* m) {
+    m->rnn_fusion_ensure();   // (the fused layouts, if a precision change dropped them)
     active = m->engine.rnn_lm_stream_fusion_active();
     serial = m->rnn_serial;
     scale = m->rnn_scale;
@@ -645,6 +655,7 @@ int32_t k2hip_greedy_batch(k2hip_model_t* model, const float* enc_out, int32_t B
     return guard([&] {
         NEED(model); NEED(enc_out); NEED(tokens); NEED(timestamps); NEED(n_tokens);
         EngineLock lk(model->engine);
+        model->rnn_fusion_ensure();
         model->engine.greedy_host(enc_out, B, Tprime, false, tokens, timestamps, n_tokens, max_tokens);
     });
 }
@@ -1496,6 +1507,7 @@ int32_t k2hip_beam_search(k2hip_model_t* model, const float* enc_out, int32_t B,
             ~Restore() { e.set_beam(old); }
         } restore{e, e.beam()};
         e.set_beam(beam);
+        model->rnn_fusion_ensure();
         e.greedy_host(enc_out, B, Tprime, false, tokens, timestamps, n_tokens, max_tokens);
         if (scores) memcpy(scores, e.last_scores().data(), sizeof(float) * B);
     });
@@ -1634,6 +1646,7 @@ int32_t k2hip_beam_search_nbest(k2hip_model_t* model, const float* enc_out, int3
         // (the single result goes to scratch: entry 0 of the list is that result)
         std::vector<int64_t> tok1((size_t)B * max_tokens);
         std::vector<int32_t> ts1((size_t)B * max_tokens), n1((size_t)B);
+        model->rnn_fusion_ensure();
         e.greedy_host(enc_out, B, Tprime, false, tok1.data(), ts1.data(), n1.data(), max_tokens);
         const Engine::NbestHost& h = e.last_nbest();
         K2_REQUIRE(h.B == B && h.N == nbest && h.max_tokens == max_tokens, "internal: the search kept no N-best");
@@ -1733,6 +1746,7 @@ int32_t k2hip_offline_greedy(k2hip_model_t* model, const float* const* feats, co
     return guard([&] {
         NEED(model); NEED(feats); NEED(n_floats); NEED(tokens); NEED(timestamps); NEED(n_tokens);
         EngineLock lk(model->engine);
+        model->rnn_fusion_ensure();
         model->engine.offline_greedy_feats(feats, n_floats, B, false, tokens, timestamps, n_tokens, max_tokens);
     });
 }
@@ -1752,6 +1766,7 @@ int32_t k2hip_offline_greedy_from_samples(k2hip_model_t* model, const float* con
     return guard([&] {
         NEED(model); NEED(samples); NEED(n_samples); NEED(tokens); NEED(timestamps); NEED(n_tokens);
         EngineLock lk(model->engine);
+        model->rnn_fusion_ensure();
         model->engine.offline_greedy_samples(samples, n_samples, B, tokens, timestamps, n_tokens, max_tokens);
     });
 }
@@ -1761,6 +1776,7 @@ int32_t k2hip_offline_greedy_from_samples_dev(k2hip_model_t* model, const float*
     return guard([&] {
         NEED(model); NEED(samples_dev); NEED(tokens); NEED(timestamps); NEED(n_tokens);
         EngineLock lk(model->engine);
+        model->rnn_fusion_ensure();
         model->engine.offline_greedy_samples_dev(samples_dev, n_samples_each, B, tokens, timestamps, n_tokens, max_tokens);
     });
 }
@@ -3392,6 +3408,7 @@ int32_t k2hip_offline_recognizer_get_results(k2hip_model_t* model, k2hip_offline
         {
             EngineLock lk(e);
             WaveSrcScope ws(e, streams, B);
+            model->rnn_fusion_ensure();
             K2_REQUIRE(e.nbest() == 0 || e.beam() > 0 || e.ctc_prefix() > 0, "GetResults: the model keeps %d alternatives (k2hip_set_nbest) but decodes with "
                        "greedy_search, which has none", e.nbest());
             if (from_samples) e.offline_greedy_samples(ptrs.data(), nfl.data(), B, tok.data(), ts.data(), n.data(), max_tokens, false, /*pinned_src=*/true);
@@ -3879,7 +3896,9 @@ int32_t k2hip_set_rnn_lm(k2hip_model_t* model, const k2hip_rnn_lm_t* lm, float s
         RnnLmDev tables;
         void* fuse = nullptr;
         if (lm) dev = e.rnn_lm_upload(*lm->lm, &tables);   // (a failed upload leaves the setting as it was)
-        if (lm && (model->rnn_fusion || model->rnn_stream_fusion)) {   // (a model that only rescores never pays for the fused layouts)
+        // (a model that only rescores never pays for the fused layouts; in half precision they are left to the first fused search, which
+        // is where an LM that does not fit f16 is refused)
+        if (lm && (model->rnn_fusion || model->rnn_stream_fusion) && !model->rnn_half) {
             try {
                 fuse = e.rnn_lm_fusion_upload(*lm->lm, &tables);
             } catch (...) {
@@ -3909,7 +3928,7 @@ int32_t k2hip_set_rnn_lm_fusion(k2hip_model_t* model, int32_t on) {
         Engine& e = model->engine;
         EngineLock lk(e);
         K2_REQUIRE(e.batches_in_flight() == 0, "set_rnn_lm_fusion: %d submitted batches are in flight; wait for them first", e.batches_in_flight());
-        if (on && model->rnn_lm && !model->rnn_fuse_dev) {   // the fused layouts of the attached LM, on first use
+        if (on && model->rnn_lm && !model->rnn_fuse_dev && !model->rnn_half) {   // the fused layouts of the attached LM, on first use
             RnnLmDev tables = e.rnn_lm_dev();
             model->rnn_fuse_dev = e.rnn_lm_fusion_upload(*model->rnn_lm, &tables);
             e.set_rnn_lm(model->rnn_lm.get(), tables);
@@ -3923,13 +3942,37 @@ int32_t k2hip_set_rnn_lm_stream_fusion(k2hip_model_t* model, int32_t on) {
         NEED(model);
         Engine& e = model->engine;
         EngineLock lk(e);
-        if (on && model->rnn_lm && !model->rnn_fuse_dev) {   // the fused layouts of the attached LM, on first use
+        if (on && model->rnn_lm && !model->rnn_fuse_dev && !model->rnn_half) {   // the fused layouts of the attached LM, on first use
             RnnLmDev tables = e.rnn_lm_dev();
             model->rnn_fuse_dev = e.rnn_lm_fusion_upload(*model->rnn_lm, &tables);
             e.set_rnn_lm(model->rnn_lm.get(), tables);
         }
         model->rnn_stream_fusion = on != 0;
         e.set_rnn_lm_stream_fusion(model->rnn_stream_fusion);
+    });
+}
+int32_t k2hip_set_rnn_lm_fusion_precision(k2hip_model_t* model, int32_t half) {
+    return guard([&] {
+        NEED(model);
+        Engine& e = model->engine;
+        EngineLock lk(e);
+        K2_REQUIRE(e.batches_in_flight() == 0, "set_rnn_lm_fusion_precision: %d submitted batches are in flight; wait for them first", e.batches_in_flight());
+        if (model->rnn_half == (half != 0)) return;
+        // a new LM setting, as k2hip_set_rnn_lm makes one: the fused layouts go (the next fused search builds them in the new precision,
+        // start state included) and fused streams of the other precision refuse their next chunk until they are reset
+        model->rnn_half = half != 0;
+        e.set_rnn_lm_fusion_half(model->rnn_half);
+        model->rnn_serial++;
+        if (model->rnn_fuse_dev) {
+            RnnLmDev tables = e.rnn_lm_dev();
+            for (int k = 0; k < 8; k++) { tables.wcat[k] = nullptr; tables.wcat_h[k] = nullptr; }
+            tables.w_out = nullptr; tables.h0 = nullptr; tables.c0 = nullptr; tables.q0 = nullptr; tables.work = nullptr;
+            e.set_rnn_lm(model->rnn_lm.get(), tables);
+            void* old = model->rnn_fuse_dev;
+            model->rnn_fuse_dev = nullptr;
+            e.synchronize();
+            e.dev_free(old);
+        }
     });
 }
 int32_t k2hip_debug_rnn_lm_stream_fusion_stats(k2hip_model_t* model, int64_t* chunk_calls, int64_t* live_blocks, int64_t* pool_bytes) {
@@ -4016,6 +4059,13 @@ int32_t k2hip_debug_nlm_advance_bench(k2hip_model_t* model, int32_t rows, int32_
         NEED(model); NEED(ms);
         EngineLock lk(model->engine);
         model->engine.nlm_advance_bench(rows, H, iters, ms);
+    });
+}
+int32_t k2hip_debug_nlm_advance_f16_bench(k2hip_model_t* model, int32_t rows, int32_t H, int32_t iters, float* ms) {
+    return guard([&] {
+        NEED(model); NEED(ms);
+        EngineLock lk(model->engine);
+        model->engine.nlm_advance_bench_f16(rows, H, iters, ms);
     });
 }
 int32_t k2hip_debug_rnn_lm_timing(k2hip_model_t* model, int32_t on, double* ms4) {

@@ -1018,7 +1018,7 @@ void beam_search(const Ctx& ctx, const DecJoinW& w, const BeamArgs& a) {
                         a.nlm.dev.h0 && a.nlm.dev.c0 && a.nlm.dev.q0),
                "beam search: neural LM fusion needs a complete LM over the model's %d tokens and a scale > 0", w.V);
     K2_REQUIRE(!nlm || ctx.dry || (a.rin != nullptr) == (a.nlm_io != nullptr), "beam search: neural LM fusion: the resumed search, and only it, takes the streams' state blocks");
-    for (int k = 0; nlm && k < a.nlm.dev.L; k++) K2_REQUIRE(a.nlm.dev.wcat[k] && a.nlm.dev.bias[k], "beam search: neural LM fusion: layer %d has no weights", k);
+    for (int k = 0; nlm && k < a.nlm.dev.L; k++) K2_REQUIRE((a.nlm.dev.wcat[k] || a.nlm.dev.wcat_h[k]) && a.nlm.dev.bias[k], "beam search: neural LM fusion: layer %d has no weights", k);
     K2_REQUIRE(!a.lm.states || (a.lm.arc_tok && a.lm.arc_lp && a.lm.arc_next && a.lm.uni_lp && a.lm.uni_next), "beam search: incomplete n-gram LM tables");
     K2_REQUIRE(!(a.lm.states && a.rin) || (a.lst_in && a.lst_out), "beam search: the resumed search with an n-gram LM needs its LM state blocks");
     K2_REQUIRE(!a.lodr.states || nlm, "beam search: LODR runs only beside the neural LM fusion");
@@ -1187,7 +1187,7 @@ void beam_search(const Ctx& ctx, const DecJoinW& w, const BeamArgs& a) {
             const int cur = t & 1, nxt = cur ^ 1;
             for (int k = 0; k < nd.L; k++) {
                 NlmAdvance v;
-                v.wcat = nd.wcat[k]; v.bias = nd.bias[k];
+                v.wcat = nd.wcat[k]; v.wcat_h = nd.wcat_h[k]; v.bias = nd.bias[k];
                 v.emb = k == 0 ? nd.emb : nullptr;
                 v.x_rows = k == 0 ? nullptr : nh + nxt * nst + (int64_t)(k - 1) * M * nd.H;
                 v.h_par = nh + cur * nst + (int64_t)k * M * nd.H; v.c_par = nc + cur * nst + (int64_t)k * M * nd.H;

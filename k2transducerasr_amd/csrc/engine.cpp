@@ -3132,8 +3132,10 @@ void Engine::debug_op_host(const char* op, const int64_t* iargs, int n_iargs, vo
                 K2_REQUIRE(static_cast<const int*>(bufs[3])[i] >= 0 && static_cast<const int*>(bufs[3])[i] < V, "debug_op_run rnn_lm_score: target %d of row %lld",
                            static_cast<const int*>(bufs[3])[i], i);
             rnn_lm_score_rows(c, y, okn, ob, tgt, lp, R, H, V, Vp);
-        } else if (name == "nlm_advance") {
-            // ints M, in, H, use_emb, V (rows of emb), live (-1: no flag, else the flag's value)
+        } else if (name == "nlm_advance" || name == "nlm_advance_f16") {
+            // ints M, in, H, use_emb, V (rows of emb), live (-1: no flag, else the flag's value); "_f16": the panel buffer holds the f16
+            // layout (RnnLmDev::wcat_h), half the bytes
+            const bool half = name == "nlm_advance_f16";
             const int M = I(), in = I(), H = I(), use_emb = I(), V = I(), live = I();
             float *wcat = P(), *bias = P(), *x = P(), *hp = P(), *cp = P(), *ho = P(), *co = P();
             const int* par = reinterpret_cast<const int*>(P());
@@ -3142,7 +3144,7 @@ void Engine::debug_op_host(const char* op, const int64_t* iargs, int n_iargs, vo
             long long* work = reinterpret_cast<long long*>(P());
             K2_REQUIRE(M > 0 && in > 0 && H > 0 && V > 0, "debug_op_run nlm_advance: bad shape");
             const long long Kc = (in + 31) / 32 * 32 + H, xrows = use_emb ? V : M;
-            K2_REQUIRE(wcat && bias && x && hp && cp && ho && co && par && tok && flag && work && buf_bytes[0] >= 16LL * H * Kc && buf_bytes[1] >= 16LL * H &&
+            K2_REQUIRE(wcat && bias && x && hp && cp && ho && co && par && tok && flag && work && buf_bytes[0] >= (half ? 8LL : 16LL) * H * Kc && buf_bytes[1] >= 16LL * H &&
                            buf_bytes[2] >= 4LL * xrows * in && buf_bytes[3] >= 4LL * M * H && buf_bytes[4] >= 4LL * M * H && buf_bytes[5] >= 4LL * M * H &&
                            buf_bytes[6] >= 4LL * M * H && buf_bytes[7] >= 4LL * M && buf_bytes[8] >= 4LL * M && buf_bytes[9] >= 4 && buf_bytes[10] >= 16,
                        "debug_op_run nlm_advance: the buffers are short of %d rows, input %d, hidden_dim %d", M, in, H);
@@ -3152,7 +3154,9 @@ void Engine::debug_op_host(const char* op, const int64_t* iargs, int n_iargs, vo
             }
             if (live >= 0) K2_HIP(hipMemsetD32Async((hipDeviceptr_t)flag, live, 1, stream_));
             NlmAdvance a;
-            a.wcat = wcat; a.bias = bias;
+            if (half) a.wcat_h = reinterpret_cast<const uint16_t*>(wcat);
+            else a.wcat = wcat;
+            a.bias = bias;
             a.emb = use_emb ? x : nullptr; a.x_rows = use_emb ? nullptr : x;
             a.h_par = hp; a.c_par = cp; a.h_out = ho; a.c_out = co;
             a.par = par; a.tok = tok; a.live = live >= 0 ? flag : nullptr; a.work = work;

@@ -266,12 +266,18 @@ class Engine {
     // the fused search's layouts of the attached LM (rnn_lm_fusion_upload): built when fusion is first switched on, never for a model
     // that only rescores; ONE more device allocation that the caller owns, *io = the attached LM's tables, completed
     void* rnn_lm_fusion_upload(const RnnLm& lm, RnnLmDev* io);
+    // k2hip_set_rnn_lm_fusion_precision: the NEXT rnn_lm_fusion_upload builds f16 panels (RnnLmDev::wcat_h) in place of the float32
+    // ones and refuses an LM with a weight that is not finite in f16 before any device work; the searches pick k_nlm_advance_f16 by
+    // what the upload holds.  Rescoring never reads the panels.
+    void set_rnn_lm_fusion_half(bool half) { rnn_fuse_half_ = half; }
     const RnnLmDev& rnn_lm_dev() const { return rnn_dev_; }
     // k_nlm_advance launches of this model's LM that swept their weights / that only moved state (k2hip_debug.h)
     void rnn_lm_fusion_work(int64_t* swept, int64_t* idle);
     // tuning record: milliseconds per k_nlm_advance launch of `rows` rows that all append, input and hidden width H (a layer above the
     // first: 2 H products per gate), a scattered parent map, pseudo-random operands, `iters` launches between two events
     void nlm_advance_bench(int rows, int H, int iters, float* ms);
+    // the same launches through k_nlm_advance_f16: the same draw of weights rounded to f16, everything else as above
+    void nlm_advance_bench_f16(int rows, int H, int iters, float* ms);
     // Hn hypotheses back to back in `tokens` (hypothesis i at [offsets[i], offsets[i + 1])) scored by the attached LM: one upload (ids,
     // targets, descriptors), the launches of the plan (rnn_lm_plan.h), one download.  token_log_probs (may be null) packed per hypothesis
     // in the caller's order, totals [Hn].  Everything is checked on the host before any device work; a call without a position issues
@@ -584,6 +590,8 @@ class Engine {
     RnnLmDev rnn_dev_;
     bool rnn_fusion_ = false;
     bool rnn_stream_fusion_ = false;
+    bool rnn_fuse_half_ = false;
+    void nlm_advance_bench_impl(int rows, int H, int iters, bool half, float* ms);
     const NlmStreamIO* nlm_io_host_ = nullptr;
     float rnn_fuse_scale_ = 0.f;
     int64_t rnn_calls_ = 0;

@@ -496,6 +496,13 @@ struct RnnLmDev {
     // for the GEMM launcher; the start hypothesis' state after sos h0 / c0 [L][H] and its row q0 [V], computed on the device at upload;
     // work [2]: debug counters of k_nlm_advance launches that swept their weights / that only moved state
     const float* wcat[8] = {};
+    // the same with half-precision weights (k2hip_set_rnn_lm_fusion_precision; rnn_lm_fuse_f16.hip): while it is on, wcat_h holds the
+    // layers' panels IN PLACE OF wcat (which is then null) -- the same concatenation and the same panels of 32 columns, every weight
+    // rounded to f16 (nearest even), k in chunks of 32 as [Kc / 32][j: 2][hh: 2][32][e: 8]: element (k, c) of a panel sits at
+    // ((((k / 32) 2 + k % 16 / 8) 2 + k % 32 / 16) 32 + c) 8 + k % 8 (rnn_lm_fuse_layout.h), so a lane's B operand of ONE
+    // v_mfma_f32_32x32x16_f16 (its eight k = 32 q + 16 hh + 8 j + e) is one 16-byte load and a wave's load is 1 KiB contiguous.
+    // Everything else of the LM -- bias, embedding, w_out, h0 / c0 / q0 -- stays float32.
+    const uint16_t* wcat_h[8] = {};
     const float* w_out = nullptr;
     float* h0 = nullptr;
     float* c0 = nullptr;
@@ -520,8 +527,13 @@ void rnn_lm_score_rows(const Ctx& ctx, const float* y, const float* out_kn, cons
 // h_out[m] = h_par[par[m]], c_out[m] = c_par[par[m]], bit for bit.  A workgroup owns 8 hidden columns x four gates and walks every
 // 32-row strip of up to 256 rows against each weight it loads ONCE; strips without an appended row issue no matrix work, and with
 // *live == 0 (null: live) the launch reads no weight at all.  in % 4 == 0, H % 32 == 0; par in [0, M), tok in [-1, V): the caller's.
+// With wcat_h set in place of wcat the launch is k_nlm_advance_f16 (rnn_lm_fuse_f16.hip): the same contract, except that the weights are
+// the f16 panels and [x ; h_par] is rounded to f16 (nearest even) on its way into the matrix pipe; products are exact in and summed in
+// float32, and bias, cell and state stay float32.  There k is split over the four waves of a workgroup, each wave holding accumulators
+// of every strip, and the partial sums meet in LDS before the cell.
 struct NlmAdvance {
     const float* wcat = nullptr;    // the layer's panels (RnnLmDev::wcat)
+    const uint16_t* wcat_h = nullptr;   // ... or its f16 panels (RnnLmDev::wcat_h): exactly one of the two
     const float* bias = nullptr;    // [4H]
     const float* emb = nullptr;     // [V][in] (layer 0) or null
     const float* x_rows = nullptr;  // [M][in] (the layer below's new h) when emb is null
@@ -536,6 +548,8 @@ struct NlmAdvance {
     int M = 0, in = 0, H = 0;
 };
 void nlm_advance(const Ctx& ctx, const NlmAdvance& a);
+// the launch behind nlm_advance when a.wcat_h is set (rnn_lm_fuse_f16.hip); nlm_advance has checked the arguments
+void nlm_advance_f16(const Ctx& ctx, const NlmAdvance& a);
 // The LM rows of frame t + 1: q_out[m] = log_softmax(h[m] . W_out^T + b_out) over V for the slots that appended (the GEMM launcher,
 // skipped on the device when *live == 0, then one workgroup per row), q_out[m] = q_par[par[m]] for the others.  Rows are V floats.
 void nlm_rows(const Ctx& ctx, const float* h, const float* w_out, const float* out_b, const float* q_par, float* q_out, const int* par,

@@ -61,8 +61,16 @@ void* Engine::rnn_lm_fusion_upload(const RnnLm& m, RnnLmDev* io) {
     const int V = m.V, H = m.H, L = m.L;
     K2_REQUIRE(io && io->emb && io->L == L && io->H == H && io->V == V, "rnn lm fusion: the tables are not those of the attached LM");
     auto al = [](int64_t n) { return align_up(n, 64); };
+    const bool half = rnn_fuse_half_;   // (k2hip_set_rnn_lm_fusion_precision: f16 panels in place of the float32 ones, half their floats)
+    // the f16 panels are laid out -- and every weight checked -- before any device work
+    std::vector<std::vector<uint16_t>> kh((size_t)(half ? L : 0));
+    for (int k = 0; half && k < L; k++) {
+        kh[(size_t)k].resize((size_t)rnn_lm_panel_halves(m, k));
+        if (!rnn_lm_panels_f16(m, k, kh[(size_t)k].data()))
+            failf(K2HIP_ERR_INVALID, "rnn lm fusion: layer %d has a weight that is not finite in half precision (k2hip_set_rnn_lm_fusion_precision)", k);
+    }
     int64_t total = al((int64_t)V * H) + 2 * al((int64_t)L * H) + al(V) + al(4);
-    for (int k = 0; k < L; k++) total += al(rnn_lm_panel_floats(m, k));
+    for (int k = 0; k < L; k++) total += al(half ? (rnn_lm_panel_halves(m, k) + 1) / 2 : rnn_lm_panel_floats(m, k));
     float* base = static_cast<float*>(dev_alloc((int64_t)sizeof(float) * total));
     try {
         RnnLmDev d = *io;
@@ -74,6 +82,15 @@ void* Engine::rnn_lm_fusion_upload(const RnnLm& m, RnnLmDev* io) {
         };
         std::vector<float> kn;
         for (int k = 0; k < L; k++) {
+            d.wcat[k] = nullptr;
+            d.wcat_h[k] = nullptr;
+            if (half) {
+                const std::vector<uint16_t>& h = kh[(size_t)k];
+                float* at = room(((int64_t)h.size() + 1) / 2);
+                dev_upload(at, h.data(), (int64_t)sizeof(uint16_t) * (int64_t)h.size());
+                d.wcat_h[k] = reinterpret_cast<const uint16_t*>(at);
+                continue;
+            }
             kn.resize((size_t)rnn_lm_panel_floats(m, k));
             rnn_lm_panels(m, k, kn.data());
             float* at = room((int64_t)kn.size());
@@ -109,7 +126,9 @@ void Engine::rnn_lm_fusion_work(int64_t* swept, int64_t* idle) {
     if (idle) *idle = w[1];
 }
 
-void Engine::nlm_advance_bench(int rows, int H, int iters, float* ms) {
+void Engine::nlm_advance_bench(int rows, int H, int iters, float* ms) { nlm_advance_bench_impl(rows, H, iters, false, ms); }
+void Engine::nlm_advance_bench_f16(int rows, int H, int iters, float* ms) { nlm_advance_bench_impl(rows, H, iters, true, ms); }
+void Engine::nlm_advance_bench_impl(int rows, int H, int iters, bool half, float* ms) {
     K2_REQUIRE(rows > 0 && rows <= 4096 && H > 0 && H <= 8192 && H % 32 == 0 && iters > 0 && iters <= 10000 && ms, "nlm_advance_bench: %d rows, hidden_dim %d, %d launches",
                rows, H, iters);
     K2_HIP(hipSetDevice(device_));
@@ -137,7 +156,18 @@ void Engine::nlm_advance_bench(int rows, int H, int iters, float* ms) {
     // a layer above the first: x = rows of width H, so the launch sums 2 H products per gate (the rescoring step sums H: its input
     // products are one GEMM per time block)
     const float ws = 1.f / sqrtf(2.f * (float)H);
-    float *w = b.take(8LL * H * H, ws), *bias = b.take(4LL * H, 1.f), *x = b.take((int64_t)rows * H, 1.f);
+    // (f16: the same draw rounded to half precision, two to a float of the buffer; the panels' order does not matter to a timing)
+    float* w = nullptr;
+    if (half) {
+        std::vector<uint16_t> hb((size_t)8 * H * H);
+        uint32_t st = 54321u;
+        for (size_t i = 0; i < hb.size(); i++) { st = st * 1664525u + 1013904223u; hb[i] = rnn_lm_f16_bits((((st >> 8) * (1.0f / 8388608.0f)) - 1.0f) * ws); }
+        w = b.take(4LL * H * H, 0.f);
+        K2_HIP(copy_blocking(w, hb.data(), sizeof(uint16_t) * hb.size(), hipMemcpyHostToDevice));
+    } else {
+        w = b.take(8LL * H * H, ws);
+    }
+    float *bias = b.take(4LL * H, 1.f), *x = b.take((int64_t)rows * H, 1.f);
     float *h0 = b.take((int64_t)rows * H, 1.f), *h1 = b.take((int64_t)rows * H, 1.f), *c0 = b.take((int64_t)rows * H, 1.f), *c1 = b.take((int64_t)rows * H, 1.f);
     int* idx = reinterpret_cast<int*>(b.take(2LL * rows, 0.f));
     std::vector<int> hi((size_t)2 * rows);
@@ -150,7 +180,9 @@ void Engine::nlm_advance_bench(int rows, int H, int iters, float* ms) {
     c.stats = nullptr;
     auto one = [&](int i) {
         NlmAdvance a;
-        a.wcat = w; a.bias = bias; a.x_rows = x;
+        if (half) a.wcat_h = reinterpret_cast<const uint16_t*>(w);
+        else a.wcat = w;
+        a.bias = bias; a.x_rows = x;
         a.h_par = i & 1 ? h1 : h0; a.c_par = i & 1 ? c1 : c0;
         a.h_out = i & 1 ? h0 : h1; a.c_out = i & 1 ? c0 : c1;
         a.par = idx; a.tok = idx + rows;

@@ -257,9 +257,10 @@ void nlm_store_streams(const Ctx& ctx, const RnnLmDev& d, const NlmStreamIO* io,
 void nlm_advance(const Ctx& ctx, const NlmAdvance& a) {
     K2_REQUIRE(a.M > 0 && a.H > 0 && a.H % 32 == 0 && a.in > 0 && a.in % 4 == 0, "nlm_advance: %d rows, input %d (a multiple of 4), hidden_dim %d (a multiple of 32)",
                a.M, a.in, a.H);
-    K2_REQUIRE(ctx.dry || (a.wcat && a.bias && (a.emb || a.x_rows) && a.h_par && a.c_par && a.h_out && a.c_out && a.par && a.tok), "nlm_advance: null argument");
+    K2_REQUIRE(ctx.dry || ((a.wcat != nullptr) != (a.wcat_h != nullptr) && a.bias && (a.emb || a.x_rows) && a.h_par && a.c_par && a.h_out && a.c_out && a.par && a.tok), "nlm_advance: null argument");
     K2_REQUIRE(a.h_out != a.h_par && a.c_out != a.c_par, "nlm_advance: the new state must not overwrite the state it is gathered from");
     if (ctx.dry) return;
+    if (a.wcat_h) return nlm_advance_f16(ctx, a);   // (the upload's precision picks the kernel)
     const int rows = std::min(a.M, NMAXR), strips = cdiv(rows, 32);
     const dim3 grid(a.H / 8, cdiv(a.M, NMAXR)), block(NT);
     if (strips <= 1) hipLaunchKernelGGL(k_nlm_advance<1>, grid, block, 0, ctx.stream, a);
@@ -304,7 +305,7 @@ void nlm_start_state(const Ctx& ctx, const RnnLmDev& d) {
     }
     for (int k = 0; k < L; k++) {
         NlmAdvance a;
-        a.wcat = d.wcat[k]; a.bias = d.bias[k];
+        a.wcat = d.wcat[k]; a.wcat_h = d.wcat_h[k]; a.bias = d.bias[k];
         a.emb = k == 0 ? d.emb : nullptr;
         a.x_rows = k == 0 ? nullptr : d.h0 + (long long)(k - 1) * H;
         a.h_par = zero; a.c_par = zero;

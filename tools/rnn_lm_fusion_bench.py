@@ -7,6 +7,9 @@ The encoder output of `batch` synthetic utterances of `seconds` seconds is compu
   plain_ms            the plain search in the form the shape selects (one kernel per batch)
   plain_launches_ms   the plain search under K2HIP_BEAM_LAUNCHES=1 (four launches per frame: the form a fused search always takes)
   fused_ms            the fused search (k2hip_set_rnn_lm_fusion): per frame L k_nlm_advance launches and the LM rows behind the step
+  fused_f16_ms        the fused search under k2hip_set_rnn_lm_fusion_precision(1) (k_nlm_advance_f16 over f16 panels).  The two fused legs are
+                      interleaved -- float32, f16, float32, f16, each time a warm-up search (which rebuilds the panels) and the rounds --
+                      and reported as medians with their spread (largest minus smallest round): fused_spread_ms, fused_f16_spread_ms
   rescored_ms         the plain search with N-best 4 followed by Model.rnn_lm_score of all its alternatives with eos
   lm_share_us_per_frame   (fused_ms - plain_launches_ms) / T'
   swept / idle        per-layer LM launches of one fused search that read their weights / that only moved state
@@ -14,7 +17,8 @@ The encoder output of `batch` synthetic utterances of `seconds` seconds is compu
                       one more wave-walk per selected candidate inside the step; lodr_share_us_per_frame = (fused_lodr_ms - fused_ms) / T'
 and, per LM width H, ONE launch at 128 rows: k_nlm_advance (2 H products per gate: input and recurrent), the rescoring step
 k_lm_lstm_step and the step composed from the GEMM launcher and the cell kernel (H products per gate: their input products are a
-separate GEMM per time block).  One JSON line on stdout.  There is no time gate: DESIGN.md "Neural LM shallow fusion" has the runs."""
+separate GEMM per time block); and k_nlm_advance against k_nlm_advance_f16 at 128 and 512 rows, five interleaved rounds of 200 launches
+each, medians and spreads (`kernel`).  One JSON line on stdout.  There is no time gate: DESIGN.md "Neural LM shallow fusion" has the runs."""
 import json
 import os
 import sys
@@ -60,13 +64,17 @@ def bigram(plain, V, seed=7):
 
 
 def timed(fn):
+    return float(np.median(walls_of(fn)))
+
+
+def walls_of(fn):
     walls = []
     for i in range(WARMUP + ROUNDS):
         t0 = time.perf_counter()
         fn()
         if i >= WARMUP:
             walls.append((time.perf_counter() - t0) * 1e3)
-    return float(np.median(walls))
+    return walls
 
 
 def main():
@@ -103,7 +111,14 @@ def main():
             r["rescored_ms"] = timed(rescored)
             m.set_rnn_lm_fusion(True)
             try:
-                r["fused_ms"] = timed(lambda: m.beam_search(enc, BEAM))
+                fused = {False: [], True: []}
+                for _ in range(2):
+                    for half in (False, True):
+                        m.set_rnn_lm_fusion_precision(half)
+                        fused[half] += walls_of(lambda: m.beam_search(enc, BEAM))
+                m.set_rnn_lm_fusion_precision(False)
+                r.update(fused_ms=float(np.median(fused[False])), fused_spread_ms=float(np.ptp(fused[False])),
+                         fused_f16_ms=float(np.median(fused[True])), fused_f16_spread_ms=float(np.ptp(fused[True])))
                 s0 = m.rnn_lm_fusion_stats()
                 m.beam_search(enc, BEAM)
                 s1 = m.rnn_lm_fusion_stats()
@@ -124,6 +139,14 @@ def main():
             step = m.rnn_lm_step_bench(ROWS, H, 200)
             r.update(rows=ROWS, launches=200, nlm_advance_ms=m.nlm_advance_bench(ROWS, H, 200), lm_lstm_step_ms=step["fused_ms"],
                      composed_step_ms=step["composed_ms"])
+            r["kernel"] = []
+            for rows in (ROWS, 512):
+                t = {False: [], True: []}
+                for _ in range(5):
+                    t[False].append(m.nlm_advance_bench(rows, H, 200))
+                    t[True].append(m.nlm_advance_f16_bench(rows, H, 200))
+                r["kernel"].append(dict(rows=rows, f32_ms=float(np.median(t[False])), f32_spread_ms=float(np.ptp(t[False])),
+                                        f16_ms=float(np.median(t[True])), f16_spread_ms=float(np.ptp(t[True]))))
             m.set_rnn_lm(None)
             out["lms"].append(r)
         m.close()

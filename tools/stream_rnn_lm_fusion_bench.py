@@ -10,6 +10,9 @@ the device hits all of them alike, and reports the median ms per tick of each le
   plain_launches   the unfused tick under K2HIP_BEAM_LAUNCHES=1 (four launches per frame: the form a fused tick always takes)
   fused LxH        k2hip_set_rnn_lm_stream_fusion with a synthetic L x H LM of scale 0.5: per frame L k_nlm_advance launches and the LM
                    rows over all streams x beam slots, per tick the two movers (k_nlm_load_streams / k_nlm_store_streams)
+  fused LxH +f16   the same under k2hip_set_rnn_lm_fusion_precision(1): k_nlm_advance_f16 over f16 panels; reported as fused_f16_ms next to
+                   fused_ms, each with its spread (largest minus smallest tick of the leg after dropping the leg's first tick of every
+                   round, which carries the upload of the panels)
   fused LxH +lodr  (--lodr) the same with a bi-gram LODR LM at weight -0.5 beside it (k2hip_set_lodr_lm): one more wave-walk per selected
                    candidate in the step and one more plane of carried states; reported as fused_lodr_ms next to fused_ms
 and per fused leg lm_share_us_per_frame = (fused - plain_launches) / frames per tick, the block pool's bytes, and whether the fused
@@ -96,8 +99,9 @@ def main():
                     return run(rec, feats)
                 finally:
                     set_switch("K2HIP_BEAM_LAUNCHES", 0)
-            with_lodr = name.endswith("+lodr")
-            m.set_rnn_lm(handles[name[:-5] if with_lodr else name], 0.5)
+            with_lodr, half = name.endswith("+lodr"), name.endswith("+f16")
+            m.set_rnn_lm_fusion_precision(half)
+            m.set_rnn_lm(handles[name[:-5] if with_lodr else name[:-4] if half else name], 0.5)
             m.set_rnn_lm_stream_fusion(True)
             if with_lodr:
                 m.set_lodr_lm(lodr, -0.5)
@@ -107,16 +111,17 @@ def main():
                 m.set_lodr_lm(None)
                 m.set_rnn_lm_stream_fusion(False)
                 m.set_rnn_lm(None)
+                m.set_rnn_lm_fusion_precision(False)
 
         lodr = NgramLm(bigram(m.vocab_size), m.vocab_size) if LODR else None
-        legs = ["plain", "plain_launches"] + lms + ([s + "+lodr" for s in lms] if LODR else [])
+        legs = ["plain", "plain_launches"] + [x for s in lms for x in (s, s + "+f16")] + ([s + "+lodr" for s in lms] if LODR else [])
         run(rec, feats[: min(N, 8)])          # warm-up: arenas, decoder tables
         ms = {k: [] for k in legs}
         res = {}
         for _ in range(rounds):
             for k in legs:
                 t, r = leg(k)
-                ms[k] += t
+                ms[k] += t[1:] if k.endswith("+f16") or k in lms else t   # (a fused leg's first tick uploads the LM's panels)
                 res[k] = r
         out["frames_per_tick"] = rec.frames_per_chunk
         out["ticks_per_leg"] = len(ms["plain"])
@@ -125,8 +130,9 @@ def main():
         assert res["plain"] == res["plain_launches"]
         out["lms"] = []
         for spec in lms:
-            f = float(np.median(ms[spec]))
-            out["lms"].append(dict(lm=spec, fused_ms=f, lm_share_us_per_frame=(f - out["plain_launches_ms"]) * 1e3 / rec.frames_per_chunk,
+            f, f16 = float(np.median(ms[spec])), float(np.median(ms[spec + "+f16"]))
+            out["lms"].append(dict(lm=spec, fused_ms=f, fused_spread_ms=float(np.ptp(ms[spec])), fused_f16_ms=f16, fused_f16_spread_ms=float(np.ptp(ms[spec + "+f16"])),
+                                   streams_moved_by_f16=sum(a != b for a, b in zip(res[spec + "+f16"], res[spec])), lm_share_us_per_frame=(f - out["plain_launches_ms"]) * 1e3 / rec.frames_per_chunk,
                                    streams_moved=sum(a != b for a, b in zip(res[spec], res["plain"]))))
             if LODR:
                 g = float(np.median(ms[spec + "+lodr"]))
