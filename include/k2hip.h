@@ -1159,13 +1159,33 @@ int32_t k2hip_set_rnn_lm_stream_fusion(k2hip_model_t* model, int32_t on);
  * the carried states, the output layer, the embedding table and the LM rows stay float32.  Per model, 0 (float32) by default;
  * K2HIP_ERR_INVALID while submitted batches are in flight.  It is a different arithmetic, hence opt-in: results are held to a twin that
  * rounds the same operands, not to the float32 search.  With the value 0 every call issues the launches and gives the bits of before.
- * ONLY THE FUSED SEARCHES: rescoring (k2hip_rnn_lm_score, the re-ordering in k2hip_offline_recognizer_get_results) stays float32.
+ * ONLY THE FUSED SEARCHES: rescoring (k2hip_rnn_lm_score, the re-ordering in k2hip_offline_recognizer_get_results) stays float32
+ * under this switch (it has one of its own: k2hip_set_rnn_lm_rescoring_precision below).
  * A CALL THAT CHANGES THE VALUE IS A NEW LM SETTING, exactly as a k2hip_set_rnn_lm call is: the fused layouts are dropped and the next
  * fused search builds them in the new precision, the start state after sos included; a fused stream that started under the other
  * precision gets K2HIP_ERR_INVALID ("reset the stream first") on its next chunk.  A call with the current value does nothing.
  * AN LM THAT DOES NOT FIT: a weight of W_ih / W_hh that is not finite in f16 (|w| >= 65520, or not finite to begin with) is
  * K2HIP_ERR_INVALID from the first fused search under half precision, before any device work; the model still decodes under float32. */
 int32_t k2hip_set_rnn_lm_fusion_precision(k2hip_model_t* model, int32_t half);
+
+/* ---- Half-precision LSTM step in the rescoring ---------------------------------------------------------------------------------------
+ * (no reference counterpart; DESIGN.md "Half-precision LSTM step in the rescoring".)
+ * half != 0: for every layer and position > 0 of k2hip_rnn_lm_score and of the re-ordering in k2hip_offline_recognizer_get_results
+ *     gates = GX + f16(h_{t-1}) . f16(W_hh)^T
+ * -- both operands of the recurrent product rounded to f16 (nearest even, subnormals kept), the products summed in float32.  GX = x W_ih^T
+ * + (b_ih + b_hh) stays the float32 GEMM of before, its input for layers > 0 the UNROUNDED float32 h; c, the cell, the stored h, the
+ * embedding, the output layer, the log-softmax and the totals stay float32.  Position 0 has no product, as before.  Per model, 0 (float32)
+ * by default; K2HIP_ERR_INVALID while submitted batches are in flight; a call with the current value does nothing.  It is a different
+ * arithmetic, hence opt-in: results are held to a twin that rounds the same operands, not to the float32 scores.  With the value 0 every
+ * call issues the launches and gives the bits of before.
+ * INDEPENDENT OF k2hip_set_rnn_lm_fusion_precision, which keeps its meaning: the fused searches do not read this switch, the rescoring
+ * does not read that one.  k2hip_rnn_lm_score_host stays the float32 reference and reads neither.
+ * AN LM THAT DOES NOT FIT: a weight of W_hh that is not finite in f16 (|w| >= 65520, or not finite to begin with) is K2HIP_ERR_INVALID
+ * from the first scoring call under half precision, before any device work; the model still scores under float32.
+ * RESIDENCY: the f16 panels of W_hh live in a device allocation of their own, built by the first half-precision scoring call and dropped
+ * when the LM is replaced or cleared or the switch returns to 0; the float32 W_hh stays resident.  A model that never turns the switch
+ * on builds nothing. */
+int32_t k2hip_set_rnn_lm_rescoring_precision(k2hip_model_t* model, int32_t half);
 
 /* ---- LODR: low-order density ratio beside the neural LM ------------------------------------------------------------------------------
  * (no reference counterpart; the project's own semantics after icefall's modified_beam_search_LODR / modified_beam_search_lm_rescore_LODR

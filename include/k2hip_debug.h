@@ -267,10 +267,15 @@ int32_t k2hip_debug_rnn_lm_timing(k2hip_model_t* model, int32_t on, double* ms4)
 /* milliseconds per recurrent step of `rows` rows at hidden width H on pseudo-random operands, `iters` launches between two events: the
  * fused step kernel, and the step composed from the GEMM launcher and the cell kernel as the LSTM encoder's lstm_layer does */
 int32_t k2hip_debug_rnn_lm_step_bench(k2hip_model_t* model, int32_t rows, int32_t H, int32_t iters, float* fused_ms, float* composed_ms);
+/* the same step through k_lm_lstm_step_f16 (k2hip_set_rnn_lm_rescoring_precision): the same operand draw rounded to f16 */
+int32_t k2hip_debug_rnn_lm_step_f16_bench(k2hip_model_t* model, int32_t rows, int32_t H, int32_t iters, float* ms);
 /* k2hip_debug_op_run ops, each ONE launch on the caller's buffers:
  *   "rnn_lm_embed"  ints R, E; bufs emb [V][E], ids [R] (int32, in [0,V): not checked), x0 [R][E] (out)
  *   "rnn_lm_step"   ints a, H, first (1: h = 0, h_prev is not read); bufs h_prev [a][H], whh_kn [H][4H], gx [rows][4H], c [rows][H]
  *                   (in / out), h_out [rows][H] (out): rows >= a of c and h_out stay as they were
+ *   "rnn_lm_step_f16"  ints a, H, first (1: h = 0, the mirror of h_prev is not read); bufs the f16 mirror of h_prev [a][H] (2 bytes per
+ *                   value), the f16 panels of W_hh (kernels.h RnnLmDev::whh_h, 4 H H halves), gx [rows][4H], c [rows][H] (in / out), h_out
+ *                   [rows][H] (out), the f16 mirror of h_out [rows][H] (out): rows >= a of the three outputs stay as they were
  *   "rnn_lm_score"  ints R, H, V, Vp; bufs y [R][H], out_kn [H][Vp], out_b [V], target [R] (int32), lp [R] (out) */
 
 /* ---- neural LM shallow fusion (k2hip.h "Neural LM shallow fusion"; tests/test_rnn_lm_fusion_gpu.py, tools/rnn_lm_fusion_bench.py) ---- */

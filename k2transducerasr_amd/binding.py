@@ -299,6 +299,8 @@ def _bind_rnn_lm(L):
     L.k2hip_debug_nlm_advance_bench.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, fp]
     L.k2hip_debug_nlm_advance_f16_bench.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, fp]
     L.k2hip_set_rnn_lm_fusion_precision.argtypes = [vp, C.c_int32]
+    L.k2hip_set_rnn_lm_rescoring_precision.argtypes = [vp, C.c_int32]
+    L.k2hip_debug_rnn_lm_step_f16_bench.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, fp]
     L.k2hip_set_rnn_lm_stream_fusion.argtypes = [vp, C.c_int32]
     L.k2hip_debug_rnn_lm_stream_fusion_stats.argtypes = [vp, lp, lp, lp]
     L._rnn_lm_bound = True
@@ -1047,6 +1049,13 @@ class Model:
         _bind_rnn_lm(self._L)
         self._chk(self._L.k2hip_set_rnn_lm_fusion_precision(self._h, int(bool(half))))
 
+    def set_rnn_lm_rescoring_precision(self, half: bool):
+        """k2hip_set_rnn_lm_rescoring_precision: rnn_lm_score and the re-ordering of the N-best lists round both operands of the
+        recurrent product h . W_hh^T to f16 with float32 sums (k_lm_lstm_step_f16); the input products, cell, state, output layer and
+        the fused searches are untouched.  The f16 panels are built by the first scoring call and dropped when the switch returns."""
+        _bind_rnn_lm(self._L)
+        self._chk(self._L.k2hip_set_rnn_lm_rescoring_precision(self._h, int(bool(half))))
+
     def rnn_lm_stream_fusion_stats(self) -> dict:
         """fused chunk calls enqueued by the process; state blocks this model's streams hold; bytes of the model's block pool"""
         _bind_rnn_lm(self._L)
@@ -1074,6 +1083,13 @@ class Model:
         a, b = C.c_float(), C.c_float()
         self._chk(self._L.k2hip_debug_rnn_lm_step_bench(self._h, int(rows), int(hidden_dim), int(iters), C.byref(a), C.byref(b)))
         return dict(fused_ms=a.value, composed_ms=b.value)
+
+    def rnn_lm_step_f16_bench(self, rows: int, hidden_dim: int, iters: int = 200) -> float:
+        """milliseconds per k_lm_lstm_step_f16 launch (k2hip_debug_rnn_lm_step_f16_bench)"""
+        _bind_rnn_lm(self._L)
+        ms = C.c_float()
+        self._chk(self._L.k2hip_debug_rnn_lm_step_f16_bench(self._h, int(rows), int(hidden_dim), int(iters), C.byref(ms)))
+        return float(ms.value)
 
     # ---- F3
     def pad_sequence(self, feats: Sequence[np.ndarray], tail_frames: int = 19) -> np.ndarray:
@@ -1696,15 +1712,19 @@ class OfflineRecognizer:
     RnnLm that rescores the N-best lists of get_results with weight rnn_lm_scale (sherpa's RNN LM rescoring); needs nbest > 1, the
     alternatives then carry lm_score.  rnn_lm_fusion=True: the LM is fused into modified_beam_search instead (Model.set_rnn_lm_fusion):
     its term is added during the search, any nbest, and the lists are not rescored; rnn_lm_half=True: the fused search reads the LSTM weights in
-    f16 (Model.set_rnn_lm_fusion_precision).  lodr_lm: an NgramLm (usually a bi-gram) subtracted
+    f16 (Model.set_rnn_lm_fusion_precision); rnn_lm_rescore_half=True: the rescoring's recurrent product runs in f16
+    (Model.set_rnn_lm_rescoring_precision), the fused search is untouched by it.  lodr_lm: an NgramLm (usually a bi-gram) subtracted
     with weight lodr_scale <= 0 wherever rnn_lm acts, in the rescoring or in the fused search (Model.set_lodr_lm)."""
 
     def __init__(self, weights_path: str, device: int = 0, decoding_method: str = "greedy_search", beam: int = 4, hotwords=None,
                  hotwords_score: float = 1.5, nbest: int = 1, ngram_lm: Optional["NgramLm"] = None, ngram_lm_scale: float = 0.3,
                  ctc_prefix_biasing: bool = False, rnn_lm: Optional["RnnLm"] = None, rnn_lm_scale: float = 0.5, rnn_lm_fusion: bool = False,
-                 lodr_lm: Optional["NgramLm"] = None, lodr_scale: float = -0.1, rnn_lm_half: bool = False):
+                 lodr_lm: Optional["NgramLm"] = None, lodr_scale: float = -0.1, rnn_lm_half: bool = False,
+                 rnn_lm_rescore_half: bool = False):
         self.model = Model(weights_path, device)
         self.model.set_decoding_method(decoding_method, beam)
+        if rnn_lm_rescore_half:
+            self.model.set_rnn_lm_rescoring_precision(True)
         if nbest != 1:   # (streams then carry .alternatives() / .token_log_probs() after get_results)
             self.model.set_nbest(nbest)
         if hotwords is not None:

@@ -151,6 +151,27 @@ struct k2hip_model {
         rnn_fuse_dev = engine.rnn_lm_fusion_upload(*rnn_lm, &tables);
         engine.set_rnn_lm(rnn_lm.get(), tables);
     }
+    // k2hip_set_rnn_lm_rescoring_precision: the recurrent product of the rescoring in f16.  rnn_resc_dev holds W_hh's f16 panels, built
+    // by the first scoring call under the switch (rnn_rescore_ensure, called with the engine's lock held in front of every scoring call;
+    // an LM that does not fit f16 is refused there) and dropped with the LM or when the switch returns to 0.
+    bool rnn_resc_half = false;
+    void* rnn_resc_dev = nullptr;
+    void rnn_rescore_ensure() {
+        if (!rnn_resc_half || !rnn_lm || rnn_resc_dev) return;
+        RnnLmDev tables = engine.rnn_lm_dev();
+        rnn_resc_dev = engine.rnn_lm_rescore_upload(*rnn_lm, &tables);
+        engine.set_rnn_lm(rnn_lm.get(), tables);
+    }
+    void rnn_rescore_drop() {
+        if (!rnn_resc_dev) return;
+        RnnLmDev tables = engine.rnn_lm_dev();
+        for (int k = 0; k < 8; k++) tables.whh_h[k] = nullptr;
+        engine.set_rnn_lm(rnn_lm.get(), tables);
+        void* old = rnn_resc_dev;
+        rnn_resc_dev = nullptr;
+        engine.synchronize();
+        engine.dev_free(old);
+    }
     // k2hip_set_nbest: 1 = off (the engine keeps nothing beyond the best hypothesis), n > 1 = alternatives and token log-probs are kept
     std::atomic<int> nbest{1};
     // the graphs attached to this model's streams (HwResident), by serial number; hw_uploads counts the uploads (k2hip_debug.h)
@@ -219,11 +240,12 @@ struct k2hip_model {
             }
             nlm_pool->shutdown();
         }
-        if (rnn_dev || rnn_fuse_dev) {
+        if (rnn_dev || rnn_fuse_dev || rnn_resc_dev) {
             try {
                 engine.synchronize();
                 if (rnn_dev) engine.dev_free(rnn_dev);
                 if (rnn_fuse_dev) engine.dev_free(rnn_fuse_dev);
+                if (rnn_resc_dev) engine.dev_free(rnn_resc_dev);
             } catch (...) {
             }
         }
@@ -1580,6 +1602,7 @@ static void rnn_lm_rescore(k2hip_model* model, k2hip_offline_stream_t* const* st
     const int Hn = (int)off.size() - 1;
     if (Hn == 0) return;
     std::vector<float> totals((size_t)Hn);
+    model->rnn_rescore_ensure();
     e.rnn_lm_score_host(ids.data(), off.data(), Hn, true, nullptr, totals.data());
     const float scale = model->rnn_scale;
     // LODR: lodr_i on the host, the model's scaled automaton walked over the alternative's tokens (a list is at most 8 short hypotheses)
@@ -3906,19 +3929,22 @@ int32_t k2hip_set_rnn_lm(k2hip_model_t* model, const k2hip_rnn_lm_t* lm, float s
                 throw;
             }
         }
-        void *old = model->rnn_dev, *old_fuse = model->rnn_fuse_dev;
+        // (the replaced LM's f16 rescoring panels go with it; the next half-precision scoring call builds the new LM's)
+        void *old = model->rnn_dev, *old_fuse = model->rnn_fuse_dev, *old_resc = model->rnn_resc_dev;
         model->rnn_dev = dev;
         model->rnn_fuse_dev = fuse;
+        model->rnn_resc_dev = nullptr;
         model->rnn_lm = lm ? lm->lm : nullptr;
         model->rnn_scale = lm ? scale : 0.f;
         model->rnn_serial++;   // (streams that carry the replaced LM's state refuse their next chunk until they are reset)
         e.set_rnn_lm(model->rnn_lm.get(), tables);
         e.set_rnn_lm_fusion(model->rnn_fusion, model->rnn_scale);
         e.set_rnn_lm_stream_fusion(model->rnn_stream_fusion);
-        if (old || old_fuse) {
+        if (old || old_fuse || old_resc) {
             e.synchronize();
             if (old) e.dev_free(old);
             if (old_fuse) e.dev_free(old_fuse);
+            if (old_resc) e.dev_free(old_resc);
         }
     });
 }
@@ -3975,6 +4001,18 @@ int32_t k2hip_set_rnn_lm_fusion_precision(k2hip_model_t* model, int32_t half) {
         }
     });
 }
+int32_t k2hip_set_rnn_lm_rescoring_precision(k2hip_model_t* model, int32_t half) {
+    return guard([&] {
+        NEED(model);
+        Engine& e = model->engine;
+        EngineLock lk(e);
+        K2_REQUIRE(e.batches_in_flight() == 0, "set_rnn_lm_rescoring_precision: %d submitted batches are in flight; wait for them first", e.batches_in_flight());
+        if (model->rnn_resc_half == (half != 0)) return;
+        model->rnn_resc_half = half != 0;
+        e.set_rnn_lm_rescoring_half(model->rnn_resc_half);
+        if (!model->rnn_resc_half) model->rnn_rescore_drop();   // (the float32 whh_kn stayed resident: nothing to build)
+    });
+}
 int32_t k2hip_debug_rnn_lm_stream_fusion_stats(k2hip_model_t* model, int64_t* chunk_calls, int64_t* live_blocks, int64_t* pool_bytes) {
     return guard([&] {
         NEED(model);
@@ -3994,6 +4032,7 @@ int32_t k2hip_rnn_lm_score(k2hip_model_t* model, const int64_t* tokens, const in
         K2_REQUIRE(model->engine.has_rnn_lm(), "rnn_lm_score: no LM is attached to the model (k2hip_set_rnn_lm)");
         if (Hn == 0) return;
         NEED(offsets); NEED(totals);
+        model->rnn_rescore_ensure();
         model->engine.rnn_lm_score_host(tokens, offsets, Hn, with_eos != 0, token_log_probs, totals);
     });
 }
@@ -4075,6 +4114,13 @@ int32_t k2hip_debug_rnn_lm_timing(k2hip_model_t* model, int32_t on, double* ms4)
         model->engine.set_rnn_lm_timing(on != 0);
         if (ms4)
             for (int i = 0; i < 4; i++) ms4[i] = model->engine.rnn_lm_last_ms()[(size_t)i];
+    });
+}
+int32_t k2hip_debug_rnn_lm_step_f16_bench(k2hip_model_t* model, int32_t rows, int32_t H, int32_t iters, float* ms) {
+    return guard([&] {
+        NEED(model); NEED(ms);
+        EngineLock lk(model->engine);
+        model->engine.rnn_lm_step_bench_f16(rows, H, iters, ms);
     });
 }
 int32_t k2hip_debug_rnn_lm_step_bench(k2hip_model_t* model, int32_t rows, int32_t H, int32_t iters, float* fused_ms, float* composed_ms) {

@@ -3119,6 +3119,18 @@ void Engine::debug_op_host(const char* op, const int64_t* iargs, int n_iargs, vo
                            buf_bytes[3] >= 4LL * a * H && buf_bytes[4] >= 4LL * a * H,
                        "debug_op_run rnn_lm_step: the buffers are short of %d rows of hidden_dim %d", a, H);
             rnn_lm_step(c, first ? nullptr : hp, w, gx, cc, ho, a, H);
+        } else if (name == "rnn_lm_step_f16") {
+            // ints a, H, first; bufs the f16 mirror of h_prev [a][H], the f16 panels of W_hh (RnnLmDev::whh_h, 4 H H halves), gx, c,
+            // h_out, the f16 mirror out [rows][H]
+            const int a = I(), H = I(), first = I();
+            const uint16_t* hp = reinterpret_cast<const uint16_t*>(P());
+            const uint16_t* w = reinterpret_cast<const uint16_t*>(P());
+            float *gx = P(), *cc = P(), *ho = P();
+            uint16_t* mo = reinterpret_cast<uint16_t*>(P());
+            K2_REQUIRE(hp && w && gx && cc && ho && mo && a > 0 && H > 0 && buf_bytes[0] >= 2LL * a * H && buf_bytes[1] >= 8LL * H * H && buf_bytes[2] >= 16LL * a * H &&
+                           buf_bytes[3] >= 4LL * a * H && buf_bytes[4] >= 4LL * a * H && buf_bytes[5] >= 2LL * a * H,
+                       "debug_op_run rnn_lm_step_f16: the buffers are short of %d rows of hidden_dim %d", a, H);
+            rnn_lm_step_f16(c, first ? nullptr : hp, w, gx, cc, ho, mo, a, H);
         } else if (name == "rnn_lm_score") {
             const long long R = L();
             const int H = I(), V = I(), Vp = I();

@@ -271,6 +271,14 @@ class Engine {
     // what the upload holds.  Rescoring never reads the panels.
     void set_rnn_lm_fusion_half(bool half) { rnn_fuse_half_ = half; }
     const RnnLmDev& rnn_lm_dev() const { return rnn_dev_; }
+    // k2hip_set_rnn_lm_rescoring_precision: while on, and with the f16 panels of W_hh resident (rnn_lm_rescore_upload: ONE more device
+    // allocation that the caller owns, built by the first half-precision scoring call, *io = the attached LM's tables with whh_h
+    // filled in; an LM with a W_hh weight that is not finite in f16 is refused before any device work), rnn_lm_score_host runs every
+    // position > 0 through k_lm_lstm_step_f16.  The fused searches never read the switch or the panels.
+    void set_rnn_lm_rescoring_half(bool half) { rnn_resc_half_ = half; }
+    void* rnn_lm_rescore_upload(const RnnLm& lm, RnnLmDev* io);
+    // tuning record: milliseconds per k_lm_lstm_step_f16 launch, the operand draw of rnn_lm_step_bench rounded to f16
+    void rnn_lm_step_bench_f16(int a, int H, int iters, float* ms);
     // k_nlm_advance launches of this model's LM that swept their weights / that only moved state (k2hip_debug.h)
     void rnn_lm_fusion_work(int64_t* swept, int64_t* idle);
     // tuning record: milliseconds per k_nlm_advance launch of `rows` rows that all append, input and hidden width H (a layer above the
@@ -591,6 +599,7 @@ class Engine {
     bool rnn_fusion_ = false;
     bool rnn_stream_fusion_ = false;
     bool rnn_fuse_half_ = false;
+    bool rnn_resc_half_ = false;
     void nlm_advance_bench_impl(int rows, int H, int iters, bool half, float* ms);
     const NlmStreamIO* nlm_io_host_ = nullptr;
     float rnn_fuse_scale_ = 0.f;

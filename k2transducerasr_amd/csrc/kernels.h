@@ -489,6 +489,10 @@ struct RnnLmDev {
     const float* whh_kn[8] = {};
     const float* out_kn = nullptr;
     const float* out_b = nullptr;
+    // half-precision rescoring (k2hip_set_rnn_lm_rescoring_precision; rnn_lm_f16.hip): per layer W_hh alone rounded to f16 in the
+    // panels of wcat_h below with an input width of 0 -- panel jb = the four gates of hidden columns 8 jb .. as [H / 32][j: 2][hh: 2]
+    // [32][e: 8], k = 32 q + 16 hh + 8 j + e.  An allocation of its own, built by the first half-precision scoring call; null otherwise.
+    const uint16_t* whh_h[8] = {};
     // shallow fusion (rnn_lm_fuse.hip): per layer [W_ih ; W_hh] concatenated along k and re-laid in panels -- panel jb holds the four
     // gates of the 8 hidden columns 8 jb .. (column c = gate c / 8 of hidden column 8 jb + c % 8) over all k as [Kc / 4][32][4], Kc =
     // in rounded up to 32 (zero rows) + H, so a lane's B operand of
@@ -516,6 +520,14 @@ void rnn_lm_embed(const Ctx& ctx, const float* emb, const int* ids, float* x0, l
 // h_out [a][H].  gx rows are 4 H floats.  h_prev == nullptr: the first position (h = 0, the product is skipped).  Rows >= a of c and
 // h_out are not touched; gates never reach memory.
 void rnn_lm_step(const Ctx& ctx, const float* h_prev, const float* whh_kn, const float* gx, float* c, float* h_out, int a, int H);
+// The same position with a half-precision recurrent product (k2hip_set_rnn_lm_rescoring_precision; rnn_lm_f16.hip): gates = gx[row] +
+// f16(h_prev[row]) . f16(W_hh)^T, products exact in and summed in float32; gx, the cell, c and h_out stay float32.  whh_h: the layer's
+// f16 panels (RnnLmDev::whh_h).  h_prev16 [a][H]: the previous position's h as f16 bit patterns -- what that position's launch stored
+// into its h_out16 -- or nullptr at the first position; h_out16 [a][H] receives f16(h_out) (nearest even) for the next one.  A
+// workgroup owns 8 hidden columns x four gates and a row block of up to 256 rows, k split over its four waves; rows >= a of c, h_out
+// and h_out16 are not touched, rows >= a of h_prev16 are not read; gates never reach memory.
+void rnn_lm_step_f16(const Ctx& ctx, const uint16_t* h_prev16, const uint16_t* whh_h, const float* gx, float* c, float* h_out, uint16_t* h_out16,
+                     int a, int H);
 // lp [R] = log_softmax(y[row] . W_out^T + b)[target[row]]: strips of 32 rows against out_kn with an online log-sum-exp, the logits never
 // stored; columns >= V never enter the sum
 void rnn_lm_score_rows(const Ctx& ctx, const float* y, const float* out_kn, const float* out_b, const int* target, float* lp, long long R, int H,

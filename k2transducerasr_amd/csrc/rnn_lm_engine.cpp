@@ -115,6 +115,29 @@ void* Engine::rnn_lm_fusion_upload(const RnnLm& m, RnnLmDev* io) {
     return base;
 }
 
+// What the half-precision rescoring needs beyond the rescoring layouts (k2hip_set_rnn_lm_rescoring_precision), built by the first scoring
+// call under the switch: a third allocation that the caller owns -- per layer W_hh alone in the f16 panels of rnn_lm_fuse_layout.h (an
+// input width of 0).  Every weight is rounded and checked before any device work.  *io: the attached LM's tables, completed.
+void* Engine::rnn_lm_rescore_upload(const RnnLm& m, RnnLmDev* io) {
+    K2_HIP(hipSetDevice(device_));
+    const int H = m.H, L = m.L;
+    K2_REQUIRE(io && io->emb && io->L == L && io->H == H && io->V == m.V, "rnn lm rescoring: the tables are not those of the attached LM");
+    const int64_t per = (int64_t)4 * H * H;   // halves per layer: a multiple of 4096
+    std::vector<uint16_t> kh((size_t)(per * L));
+    for (int k = 0; k < L; k++)
+        if (!rnn_lm_panels_f16(m, k, kh.data() + (size_t)(per * k), 0))
+            failf(K2HIP_ERR_INVALID, "rnn lm rescoring: layer %d has a weight that is not finite in half precision (k2hip_set_rnn_lm_rescoring_precision)", k);
+    uint16_t* base = static_cast<uint16_t*>(dev_alloc((int64_t)sizeof(uint16_t) * per * L));
+    try {
+        dev_upload(base, kh.data(), (int64_t)sizeof(uint16_t) * per * L);
+    } catch (...) {
+        try { dev_free(base); } catch (...) {}
+        throw;
+    }
+    for (int k = 0; k < 8; k++) io->whh_h[k] = k < L ? base + per * k : nullptr;
+    return base;
+}
+
 void Engine::rnn_lm_fusion_work(int64_t* swept, int64_t* idle) {
     long long w[2] = {0, 0};
     if (rnn_host_ && rnn_dev_.work) {
@@ -209,6 +232,9 @@ void Engine::rnn_lm_score_host(const int64_t* tokens, const int64_t* offsets, in
     const RnnLmPlan p = rnn_lm_plan(offsets, Hn, with_eos, d.H, cap);
     for (int i = 0; i < Hn; i++) totals[i] = 0.f;
     if (p.R == 0) return;   // (nothing but empty hypotheses without eos: no device work)
+    // k2hip_set_rnn_lm_rescoring_precision: the recurrence through k_lm_lstm_step_f16; a missing panel is an error, never float32
+    const bool half = rnn_resc_half_;
+    K2_REQUIRE(!half || d.whh_h[0], "rnn_lm_score: half-precision rescoring is on and the f16 panels of W_hh were not built");
     K2_HIP(hipSetDevice(device_));
     const int64_t R = p.R;
     const int H = d.H, E = d.E, L = d.L, G = 4 * H, T = p.T;
@@ -269,6 +295,8 @@ void Engine::rnn_lm_score_host(const int64_t* tokens, const int64_t* offsets, in
         float* lp = ar.take<float>(R);
         d_tlp = ar.take<float>(R);
         d_tot = ar.take<float>(Hn);
+        // the f16 mirror of the layer's output rows: step t reads the rows step t - 1 stored (one buffer serves every layer in turn)
+        uint16_t* y16 = half ? ar.take<uint16_t>(R * H) : nullptr;
         if (!c.dry) K2_HIP(hipMemcpyAsync(blob, pin, (size_t)nb, hipMemcpyHostToDevice, c.stream));
         mark(c, -1);
         rnn_lm_embed(c, d.emb, ids, x0, R, E);
@@ -284,7 +312,10 @@ void Engine::rnn_lm_score_host(const int64_t* tokens, const int64_t* offsets, in
                 mark(c, -1);
                 linear(c, in + r0 * in_dim, in_dim, d.w_ih[k], d.bias[k], gx, G, (int)rows, in_dim, G);
                 mark(c, 1);
-                for (int t = t0; t < t1; t++)
+                for (int t = t0; half && t < t1; t++)
+                    rnn_lm_step_f16(c, t ? y16 + p.base[(size_t)t - 1] * H : nullptr, d.whh_h[k], gx + (p.base[(size_t)t] - r0) * G, cst,
+                                    out + p.base[(size_t)t] * H, y16 + p.base[(size_t)t] * H, p.active[(size_t)t], H);
+                for (int t = t0; !half && t < t1; t++)
                     rnn_lm_step(c, t ? out + p.base[(size_t)t - 1] * H : nullptr, d.whh_kn[k], gx + (p.base[(size_t)t] - r0) * G, cst,
                                 out + p.base[(size_t)t] * H, p.active[(size_t)t], H);
                 mark(c, 2);
@@ -374,6 +405,60 @@ void Engine::rnn_lm_step_bench(int a, int H, int iters, float* fused_ms, float* 
     };
     if (fused_ms) *fused_ms = timed(true);
     if (composed_ms) *composed_ms = timed(false);
+}
+
+void Engine::rnn_lm_step_bench_f16(int a, int H, int iters, float* ms) {
+    K2_REQUIRE(a > 0 && a <= 4096 && H > 0 && H <= 8192 && H % 32 == 0 && iters > 0 && iters <= 10000 && ms, "rnn_lm_step_bench_f16: %d rows, hidden_dim %d, %d launches",
+               a, H, iters);
+    K2_HIP(hipSetDevice(device_));
+    const int64_t G = 4LL * H;
+    struct Bufs {
+        hipStream_t s;
+        std::vector<void*> p;
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        ~Bufs() {
+            (void)hipStreamSynchronize(s);
+            for (void* q : p) (void)hipFree(q);
+            if (e0) (void)hipEventDestroy(e0);
+            if (e1) (void)hipEventDestroy(e1);
+        }
+        // rnn_lm_step_bench's draw: n values of buffer number p.size(), as float32 or rounded to f16 (n halves)
+        void* take(int64_t n, float scale, bool f16) {
+            void* q = nullptr;
+            K2_HIP(hipMalloc(&q, (f16 ? sizeof(uint16_t) : sizeof(float)) * (size_t)n));
+            p.push_back(q);
+            std::vector<float> h((size_t)n);
+            uint32_t st = 12345u + (uint32_t)p.size();
+            for (auto& v : h) { st = st * 1664525u + 1013904223u; v = (((st >> 8) * (1.0f / 8388608.0f)) - 1.0f) * scale; }
+            if (f16) {
+                std::vector<uint16_t> hb((size_t)n);
+                for (size_t i = 0; i < hb.size(); i++) hb[i] = rnn_lm_f16_bits(h[i]);
+                K2_HIP(copy_blocking(q, hb.data(), sizeof(uint16_t) * (size_t)n, hipMemcpyHostToDevice));
+            } else {
+                K2_HIP(copy_blocking(q, h.data(), sizeof(float) * (size_t)n, hipMemcpyHostToDevice));
+            }
+            return q;
+        }
+    } b{stream_, {}};
+    // (the panels' order does not matter to a timing: the float32 bench's weights in its order, rounded)
+    const uint16_t* w = static_cast<const uint16_t*>(b.take(G * H, 1.f / sqrtf((float)H), true));
+    uint16_t *m0 = static_cast<uint16_t*>(b.take((int64_t)a * H, 1.f, true)), *m1 = static_cast<uint16_t*>(b.take((int64_t)a * H, 1.f, true));
+    float *gx = static_cast<float*>(b.take((int64_t)a * G, 1.f, false)), *h1 = static_cast<float*>(b.take((int64_t)a * H, 1.f, false)),
+          *cst = static_cast<float*>(b.take((int64_t)a * H, 1.f, false));
+    K2_HIP(hipEventCreate(&b.e0));
+    K2_HIP(hipEventCreate(&b.e1));
+    Ctx c = make_ctx(false);
+    c.instrument = false;
+    c.stats = nullptr;
+    auto one = [&](int i) { rnn_lm_step_f16(c, i & 1 ? m1 : m0, w, gx, cst, h1, i & 1 ? m0 : m1, a, H); };
+    for (int i = 0; i < 3; i++) one(i);
+    K2_HIP(hipEventRecord(b.e0, stream_));
+    for (int i = 0; i < iters; i++) one(i);
+    K2_HIP(hipEventRecord(b.e1, stream_));
+    K2_HIP(hipEventSynchronize(b.e1));
+    float t = 0.f;
+    K2_HIP(hipEventElapsedTime(&t, b.e0, b.e1));
+    *ms = t / iters;
 }
 
 }  // namespace k2hip

@@ -59,10 +59,12 @@ inline int64_t rnn_lm_panel_halves(const RnnLm& m, int k) { return rnn_lm_panel_
 inline size_t rnn_lm_panel_f16_at(int k, int c) { return ((((size_t)(k / 32) * 2 + (size_t)(k % 16 / 8)) * 2 + (size_t)(k % 32 / 16)) * 32 + (size_t)c) * 8 + (size_t)(k % 8); }
 // out: rnn_lm_panel_halves(m, k) f16 bit patterns, every one of them written.  False: a weight is not finite in f16 (the caller refuses
 // the LM); out is then unspecified.
-inline bool rnn_lm_panels_f16(const RnnLm& m, int k, uint16_t* out) {
-    const int H = m.H, I = m.in_dim(k), Ip = (I + 31) / 32 * 32, Kc = Ip + H;
+// I: the input width that is laid out in front of W_hh -- the layer's (the fused searches) or 0 (the rescoring step, whose input
+// products are a GEMM of their own: the panels are then W_hh's alone, [H / 32][j][hh][32][e], 4 H H halves)
+inline bool rnn_lm_panels_f16(const RnnLm& m, int k, uint16_t* out, int I) {
+    const int H = m.H, Ip = (I + 31) / 32 * 32, Kc = Ip + H;
     const float *wi = m.w_ih[(size_t)k].data(), *wh = m.w_hh[(size_t)k].data();
-    for (int64_t i = 0, n = rnn_lm_panel_halves(m, k); i < n; i++) out[i] = 0;
+    for (int64_t i = 0, n = (int64_t)4 * H * Kc; i < n; i++) out[i] = 0;
     bool finite = true;
     auto put = [&](uint16_t* panel, int kk, int c, float w) {
         const uint16_t h = rnn_lm_f16_bits(w);
@@ -79,5 +81,6 @@ inline bool rnn_lm_panels_f16(const RnnLm& m, int k, uint16_t* out) {
     }
     return finite;
 }
+inline bool rnn_lm_panels_f16(const RnnLm& m, int k, uint16_t* out) { return rnn_lm_panels_f16(m, k, out, m.in_dim(k)); }
 
 }  // namespace k2hip

@@ -9,8 +9,13 @@ model's vocabulary) through Model.rnn_lm_score with the leg timing on (k2hip_deb
 milliseconds of embed, GX (the time-parallel input products through the GEMM launcher), steps (one fused launch per layer and
 position) and score (the output sweep and the totals), and of the whole call on the host clock.  The same tool times ONE recurrent
 step at the call's widest shape (rows = the hypothesis count, H) both ways (k2hip_debug_rnn_lm_step_bench): the fused kernel, and the
-step composed from the GEMM launcher and the cell kernel as the LSTM encoder's lstm_layer does.  One JSON line on stdout.  There is no
-time gate: DESIGN.md "Neural LM rescoring" has the runs taken so far."""
+step composed from the GEMM launcher and the cell kernel as the LSTM encoder's lstm_layer does.  Every round scores the batch twice in
+the same process, float32 and then under Model.set_rnn_lm_rescoring_precision(True) (k_lm_lstm_step_f16): the half-precision leg is
+reported as half_call_ms and half_<leg>, every median with its [min, max] spread.  "step_shapes" holds the one-step milliseconds of the
+float32 kernel, the composed step and the f16 kernel (k2hip_debug_rnn_lm_step_f16_bench) at (rows, H) = (117, 512), (117, 2048),
+(32, 2048), (8, 2048): medians of STEP_ROUNDS rounds of 200 launches, the three interleaved in every round; --steps-only skips the rest.
+One JSON line on stdout.  There is no time gate: DESIGN.md "Neural LM rescoring" and "Half-precision LSTM step in the rescoring" have the
+runs taken so far."""
 import json
 import os
 import sys
@@ -22,7 +27,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT]
 
-from k2transducerasr_amd import OfflineRecognizer, RnnLm  # noqa: E402
+from k2transducerasr_amd import Model, OfflineRecognizer, RnnLm  # noqa: E402
 from k2transducerasr_amd.synth import synth_utterance, write_synthetic_model, write_synthetic_rnn_lm  # noqa: E402
 
 argv = [a for a in sys.argv[1:] if not a.startswith("--")]
@@ -31,10 +36,29 @@ preset = argv[0] if len(argv) > 0 else "zipformer2-large-en"
 batch = int(argv[1]) if len(argv) > 1 else 32
 seconds = float(argv[2]) if len(argv) > 2 else 10.0
 ROUNDS, WARMUP = 7, 2
+STEP_SHAPES, STEP_ROUNDS = ((117, 512), (117, 2048), (32, 2048), (8, 2048)), 5
 
 
 def med(v):
     return float(np.median(v))
+
+
+def spread(v):
+    return [float(np.min(v)), float(np.max(v))]
+
+
+def step_shapes(model):
+    res = []
+    for rows, H in STEP_SHAPES:
+        f, c, h = [], [], []
+        for _ in range(STEP_ROUNDS):
+            st = model.rnn_lm_step_bench(rows, H, 200)
+            f.append(st["fused_ms"])
+            c.append(st["composed_ms"])
+            h.append(model.rnn_lm_step_f16_bench(rows, H, 200))
+        res.append(dict(rows=rows, H=H, f32_ms=med(f), f32_spread=spread(f), composed_ms=med(c), composed_spread=spread(c), f16_ms=med(h),
+                        f16_spread=spread(h), panel_bytes=8 * H * H))
+    return res
 
 
 def main():
@@ -42,6 +66,11 @@ def main():
     with tempfile.TemporaryDirectory() as d:
         path = os.path.join(d, f"{preset}.k2w")
         write_synthetic_model(path, preset)
+        if "--steps-only" in sys.argv:
+            m = Model(path, 0)
+            print(json.dumps(dict(step_shapes=step_shapes(m), step_rounds=STEP_ROUNDS)))
+            m.close()
+            return
         rec = OfflineRecognizer(path, 0, "modified_beam_search", 4, nbest=4)
         utts = [synth_utterance(u, seconds) for u in range(batch)]
         walls, hyps = [], []
@@ -67,19 +96,31 @@ def main():
             rec.model.set_rnn_lm(lm, 0.0)
             lm.close()
             rec.model.rnn_lm_timing(True)
-            legs, calls = [], []
+            legs, calls = {False: [], True: []}, {False: [], True: []}
             for i in range(WARMUP + ROUNDS):
-                t0 = time.perf_counter()
-                rec.model.rnn_lm_score(hyps, True)
-                wall = (time.perf_counter() - t0) * 1e3
-                if i >= WARMUP:
-                    calls.append(wall)
-                    legs.append(rec.model.rnn_lm_timing(True))
+                for half in (False, True):   # (interleaved: both precisions see the same clocks)
+                    rec.model.set_rnn_lm_rescoring_precision(half)
+                    if half:   # (the switch's return to 0 dropped the f16 panels: the first call builds them again, not timed)
+                        rec.model.rnn_lm_score(hyps[:1], True)
+                    t0 = time.perf_counter()
+                    rec.model.rnn_lm_score(hyps, True)
+                    wall = (time.perf_counter() - t0) * 1e3
+                    if i >= WARMUP:
+                        calls[half].append(wall)
+                        legs[half].append(rec.model.rnn_lm_timing(True))
+            rec.model.set_rnn_lm_rescoring_precision(False)
             rec.model.rnn_lm_timing(False)
             step = rec.model.rnn_lm_step_bench(len(hyps), H, 200)
-            out["lms"].append(dict(lm=spec, call_ms=med(calls), **{k: med([g[k] for g in legs]) for k in legs[0]},
-                                   step_fused_ms=step["fused_ms"], step_composed_ms=step["composed_ms"], step_rows=len(hyps), step_launches=200))
+            out["lms"].append(dict(lm=spec, call_ms=med(calls[False]), call_spread=spread(calls[False]),
+                                   **{k: med([g[k] for g in legs[False]]) for k in legs[False][0]},
+                                   steps_spread=spread([g["steps_ms"] for g in legs[False]]),
+                                   half_call_ms=med(calls[True]), half_call_spread=spread(calls[True]),
+                                   **{"half_" + k: med([g[k] for g in legs[True]]) for k in legs[True][0]},
+                                   half_steps_spread=spread([g["steps_ms"] for g in legs[True]]),
+                                   step_fused_ms=step["fused_ms"], step_composed_ms=step["composed_ms"],
+                                   step_f16_ms=rec.model.rnn_lm_step_f16_bench(len(hyps), H, 200), step_rows=len(hyps), step_launches=200))
             rec.model.set_rnn_lm(None)
+        out["step_shapes"] = step_shapes(rec.model)
         rec.model.close()
     print(json.dumps(out))
 
