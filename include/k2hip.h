@@ -1187,6 +1187,26 @@ int32_t k2hip_set_rnn_lm_fusion_precision(k2hip_model_t* model, int32_t half);
  * on builds nothing. */
 int32_t k2hip_set_rnn_lm_rescoring_precision(k2hip_model_t* model, int32_t half);
 
+/* ---- Half-precision operands in the encoder's linear layers ---------------------------------------------------------------------------
+ * (no reference counterpart; DESIGN.md "Half-precision operands in the encoder's linear layers".)
+ * half != 0: the linear layers of the OFFLINE Zipformer2 encoder's layers (model types zipformer2 and zipformer2ctc) -- the feed-forward,
+ * attention value / output, NonlinAttention and conv-module projections that run as plain Linear launches with K % 32 == 0 -- compute
+ *     C = epilogue(f16(A) . f16(W)^T)
+ * with both operands rounded to f16 (nearest even, subnormals kept) and the products summed in float32 (v_mfma_f32_32x32x16_f16).  W is
+ * rounded ONCE, when the switch is turned on, into panels resident beside the float32 weights; the float32 activation A is rounded on
+ * its way into the matrix pipe.  Bias, activation, residual, every tensor in memory, encoder_embed, the attention scores, the
+ * convolutions, the norms, the launches with a gated, bypass or batched epilogue, the encoder's output projection, decoder, joiner, CTC
+ * head and every search stay float32 arithmetic on whatever the encoder produced.  Per model, 0 (float32) by default;
+ * K2HIP_ERR_INVALID while submitted batches are in flight; a call with the current value does nothing.  It is a different arithmetic,
+ * hence opt-in: with the value 0 every call issues the launches and gives the bits of before.
+ * OVERFLOW: an activation beyond the f16 range (|a| >= 65520) becomes an infinity as the hardware conversion makes it, and the sums it
+ * enters become infinite or NaN; a NaN stays a NaN.  Nothing is clamped or rescaled.
+ * A MODEL THAT DOES NOT FIT: a covered weight that is not finite in f16 (|w| >= 65520, or not finite to begin with) refuses the switch
+ * with K2HIP_ERR_INVALID, the message naming the tensor, before any device work; the model stays on float32.
+ * SCOPE: the streaming step (k2hip_online_*) never reads the switch.  Conformer, Zipformer v1, LSTM and streaming-export models:
+ * K2HIP_ERR_UNSUPPORTED.  Turning the switch off frees the panels. */
+int32_t k2hip_set_encoder_precision(k2hip_model_t* model, int32_t half);
+
 /* ---- LODR: low-order density ratio beside the neural LM ------------------------------------------------------------------------------
  * (no reference counterpart; the project's own semantics after icefall's modified_beam_search_LODR / modified_beam_search_lm_rescore_LODR
  * and sherpa's lodr_fst / lodr_scale.  DESIGN.md "LODR".)  A low-order n-gram LM, usually a bi-gram trained on the acoustic model's own

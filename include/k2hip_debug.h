@@ -65,6 +65,18 @@ int32_t k2hip_debug_gemm_run(k2hip_model_t* model, const float* A, const float* 
  * that does not run on one of these tiles or whose tile does not hold a stream, the switch K2HIP_NO_FUSED_CONV
  * (tests/test_conv_fused_plan.py). */
 int32_t k2hip_debug_conv_fused_plan(int32_t B, int32_t T, int32_t D, int32_t K, int32_t streaming, int32_t* entry);
+/* The half-precision GEMM (csrc/gemm_f16.hip; k2hip_set_encoder_precision), host side, no model and no device
+ * (tests/test_encoder_half.py):
+ * k2hip_debug_gemm_f16_plan: fields = M, N, K, lda, ldc, glu, mul, byp_orig, w_kn, cv_Fout, nb0, nb1, res_div, skip_if_zero, cf_pool, dw_w
+ *   (16 values; a pointer field as 0 / 1 = null / set).  *form = gemm_f16_form() of those GemmArgs; plan[3] = plan_gemm_f16()'s table
+ *   index, BM, BN for them (force: a table index, -1 = the plan's choice), or -1s when the form is refused.
+ * k2hip_debug_gemm_f16_pack: the panels (csrc/gemm_f16_layout.h) of the float32 matrix W [N, K] into out (cap_halves >= 32 K
+ *   ceil(N / 32) f16 bit patterns); *finite = 0 when a weight is not finite in f16.
+ * k2hip_debug_encoder_f16_stats: gemm_f16_mfma launches of the model since its switch was last turned on, resident panels (weights) and
+ *   their bytes; zeros while the switch is off.  Each out pointer may be NULL. */
+int32_t k2hip_debug_gemm_f16_plan(const int64_t* fields, int32_t n_fields, int32_t force, int32_t* form, int32_t* plan);
+int32_t k2hip_debug_gemm_f16_pack(const float* W, int32_t N, int32_t K, uint16_t* out, int64_t cap_halves, int32_t* finite);
+int32_t k2hip_debug_encoder_f16_stats(k2hip_model_t* model, int64_t* launches, int64_t* panels, int64_t* panel_bytes);
 /* ---- other encoder kernels ---------------------------------------------------------------------- */
 /* ONE launch of the launcher named `op` (csrc/kernels.h: attn_scores_softmax, attn_av_out, attn_av_out_ring, attn_proj_av_out_ring,
  * nonlin_av_out_ring, attn_stream_ring, attn_stream, glu_causal_conv, biasnorm, bypass, biasnorm_bypass, biasnorm_bypass_downsample,
@@ -109,6 +121,11 @@ int32_t k2hip_debug_conv_fused_plan(int32_t B, int32_t T, int32_t D, int32_t K, 
  *     k2hip_debug_conv_fused_plan's entry for the shape; ints B, T, D, K.  entry >= 0: ONE launch (gemm_glu_dwconv1d); -1: the two
  *     launches -- the GLU GEMM + dwconv1d_swoosh from 256 rows on, else the plain in_proj (the hook puts the rows back in value | gate
  *     order) + glu_dwconv1d_swoosh.  The switch K2HIP_NO_FUSED_CONV keeps the two launches.
+ *   "gemm_f16" (tests/test_encoder_half_gpu.py): ONE launch of gemm_f16_mfma, C = epilogue(f16(A) . f16(W)^T).  ints M, N, K, lda, ldc,
+ *     ldr, act, act_cols, act_after_res, res_is_C (1: the residual is C's own buffer; no res buffer then), cfg (the tile's index in
+ *     K2_F16_TABLE: 0 128 x 128, 1 128 x 64, 2 64 x 64; -1 = plan_gemm_f16's choice).  bufs A, W (float32 [N, K], K % 32 == 0: packed by
+ *     the engine's own packer inside the hook), bias, res, C, then a buffer of 3 int32 the hook fills with the plan (table index, BM,
+ *     BN).  A W that is not finite in f16 is K2HIP_ERR_INVALID.
  * The two kernels of the forced alignment (csrc/align.hip, tests/test_align_gpu.py); every stream's plane [T_b][U_b + 1] lies back to
  * back in stream order, T_b = n_frames[b] (a null buffer: Tp), U_b = lens[b]; cells outside the reachable band keep what they held:
  *   "lattice_logprobs": buffers enc [B][Tp][J], n_frames [B] int32, ids (int64, the targets back to back), lens [B] int32, stay, emit

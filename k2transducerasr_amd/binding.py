@@ -1056,6 +1056,23 @@ class Model:
         _bind_rnn_lm(self._L)
         self._chk(self._L.k2hip_set_rnn_lm_rescoring_precision(self._h, int(bool(half))))
 
+    def set_encoder_precision(self, half: bool):
+        """k2hip_set_encoder_precision: the plain linear layers of the offline Zipformer2 encoder's layers (K % 32 == 0) round both
+        operands to f16 with float32 sums (gemm_f16_mfma); the weights' f16 panels are built here and freed when the switch returns.
+        Epilogues, every other kernel and the search stay float32.  K2HipError (unsupported) for other model families; (invalid,
+        naming the tensor) for a weight that is not finite in f16 -- the model then stays on float32."""
+        self._L.k2hip_set_encoder_precision.argtypes = [C.c_void_p, C.c_int32]
+        self._L.k2hip_set_encoder_precision.restype = C.c_int32
+        self._chk(self._L.k2hip_set_encoder_precision(self._h, int(bool(half))))
+
+    def encoder_f16_stats(self) -> dict:
+        """gemm_f16_mfma launches since the switch was last turned on; resident weight panels; their bytes"""
+        self._L.k2hip_debug_encoder_f16_stats.argtypes = [C.c_void_p] + [C.POINTER(C.c_int64)] * 3
+        self._L.k2hip_debug_encoder_f16_stats.restype = C.c_int32
+        n, p, b = C.c_int64(), C.c_int64(), C.c_int64()
+        self._chk(self._L.k2hip_debug_encoder_f16_stats(self._h, C.byref(n), C.byref(p), C.byref(b)))
+        return dict(launches=n.value, panels=p.value, panel_bytes=b.value)
+
     def rnn_lm_stream_fusion_stats(self) -> dict:
         """fused chunk calls enqueued by the process; state blocks this model's streams hold; bytes of the model's block pool"""
         _bind_rnn_lm(self._L)
@@ -1714,15 +1731,18 @@ class OfflineRecognizer:
     its term is added during the search, any nbest, and the lists are not rescored; rnn_lm_half=True: the fused search reads the LSTM weights in
     f16 (Model.set_rnn_lm_fusion_precision); rnn_lm_rescore_half=True: the rescoring's recurrent product runs in f16
     (Model.set_rnn_lm_rescoring_precision), the fused search is untouched by it.  lodr_lm: an NgramLm (usually a bi-gram) subtracted
-    with weight lodr_scale <= 0 wherever rnn_lm acts, in the rescoring or in the fused search (Model.set_lodr_lm)."""
+    with weight lodr_scale <= 0 wherever rnn_lm acts, in the rescoring or in the fused search (Model.set_lodr_lm).  encoder_half=True:
+    the offline Zipformer2 encoder's plain linear layers run with f16 operands and float32 sums (Model.set_encoder_precision)."""
 
     def __init__(self, weights_path: str, device: int = 0, decoding_method: str = "greedy_search", beam: int = 4, hotwords=None,
                  hotwords_score: float = 1.5, nbest: int = 1, ngram_lm: Optional["NgramLm"] = None, ngram_lm_scale: float = 0.3,
                  ctc_prefix_biasing: bool = False, rnn_lm: Optional["RnnLm"] = None, rnn_lm_scale: float = 0.5, rnn_lm_fusion: bool = False,
                  lodr_lm: Optional["NgramLm"] = None, lodr_scale: float = -0.1, rnn_lm_half: bool = False,
-                 rnn_lm_rescore_half: bool = False):
+                 rnn_lm_rescore_half: bool = False, encoder_half: bool = False):
         self.model = Model(weights_path, device)
         self.model.set_decoding_method(decoding_method, beam)
+        if encoder_half:
+            self.model.set_encoder_precision(True)
         if rnn_lm_rescore_half:
             self.model.set_rnn_lm_rescoring_precision(True)
         if nbest != 1:   # (streams then carry .alternatives() / .token_log_probs() after get_results)

@@ -13,6 +13,7 @@
 
 #include "text.h"
 #include "engine.h"
+#include "gemm_f16_layout.h"
 #include "beam_hist.h"
 #include "ctc_prefix_hist.h"
 #include "hotwords.h"
@@ -3196,6 +3197,41 @@ int32_t k2hip_debug_conv_fused_plan(int32_t B, int32_t T, int32_t D, int32_t K, 
         *entry = glu_dwconv_pipe_entry(B, T, D, K, streaming != 0);
     });
 }
+// the half-precision GEMM's form predicate and tile plan (gemm_plan.cpp) and its panel packer (gemm_f16_layout.h): host only, no model
+int32_t k2hip_debug_gemm_f16_plan(const int64_t* f, int32_t n_fields, int32_t force, int32_t* form, int32_t* plan) {
+    return guard([&] {
+        NEED(f); NEED(form); NEED(plan);
+        K2_REQUIRE(n_fields == 16, "debug_gemm_f16_plan: 16 fields, not %d", n_fields);
+        static const float dummy = 0.f;
+        static const int idummy = 0;
+        GemmArgs a;
+        a.M = (int)f[0]; a.N = (int)f[1]; a.K = (int)f[2]; a.lda = (int)f[3]; a.ldc = (int)f[4]; a.ldw = a.K;
+        a.glu = (int)f[5]; a.mul = f[6] ? &dummy : nullptr; a.byp_orig = f[7] ? &dummy : nullptr; a.w_kn = (int)f[8]; a.cv_Fout = (int)f[9];
+        a.nb0 = (int)f[10]; a.nb1 = (int)f[11]; a.res_div = (int)f[12]; a.skip_if_zero = f[13] ? &idummy : nullptr;
+        a.cf_pool = f[14] ? const_cast<float*>(&dummy) : nullptr; a.dw_w = f[15] ? &dummy : nullptr;
+        *form = gemm_f16_form(a) ? 1 : 0;
+        plan[0] = plan[1] = plan[2] = -1;
+        if (*form) {
+            const GemmF16Plan p = plan_gemm_f16(a, force);
+            plan[0] = p.idx; plan[1] = p.BM; plan[2] = p.BN;
+        }
+    });
+}
+int32_t k2hip_debug_gemm_f16_pack(const float* W, int32_t N, int32_t K, uint16_t* out, int64_t cap_halves, int32_t* finite) {
+    return guard([&] {
+        NEED(W); NEED(out); NEED(finite);
+        K2_REQUIRE(N >= 1 && K >= 32 && K % 32 == 0, "debug_gemm_f16_pack: N %d, K %d (K %% 32 == 0)", N, K);
+        K2_REQUIRE(cap_halves >= gemm_f16_panel_halves(N, K), "debug_gemm_f16_pack: %lld halves are needed", (long long)gemm_f16_panel_halves(N, K));
+        *finite = gemm_f16_pack(W, N, K, out) ? 1 : 0;
+    });
+}
+int32_t k2hip_debug_encoder_f16_stats(k2hip_model_t* model, int64_t* launches, int64_t* panels, int64_t* panel_bytes) {
+    return guard([&] {
+        NEED(model);
+        EngineLock lk(model->engine);
+        model->engine.encoder_f16_stats(launches, panels, panel_bytes);
+    });
+}
 int32_t k2hip_debug_gemm(k2hip_model_t* model, int32_t M, int32_t N, int32_t K,
                                                                  int32_t act, int32_t with_res, int32_t cfg, int32_t iters, float* ms) {
     return guard([&] {
@@ -4011,6 +4047,15 @@ int32_t k2hip_set_rnn_lm_rescoring_precision(k2hip_model_t* model, int32_t half)
         model->rnn_resc_half = half != 0;
         e.set_rnn_lm_rescoring_half(model->rnn_resc_half);
         if (!model->rnn_resc_half) model->rnn_rescore_drop();   // (the float32 whh_kn stayed resident: nothing to build)
+    });
+}
+int32_t k2hip_set_encoder_precision(k2hip_model_t* model, int32_t half) {
+    return guard([&] {
+        NEED(model);
+        Engine& e = model->engine;
+        EngineLock lk(e);
+        K2_REQUIRE(e.batches_in_flight() == 0, "set_encoder_precision: %d submitted batches are in flight; wait for them first", e.batches_in_flight());
+        e.set_encoder_precision(half != 0);
     });
 }
 int32_t k2hip_debug_rnn_lm_stream_fusion_stats(k2hip_model_t* model, int64_t* chunk_calls, int64_t* live_blocks, int64_t* pool_bytes) {

@@ -2,6 +2,7 @@
 #include <thread>
 
 #include "engine.h"
+#include "gemm_f16_layout.h"
 #include "lattice_ref.h"
 #include "ctc_lattice_ref.h"
 #include "kws_ref.h"
@@ -65,6 +66,7 @@ Engine::~Engine() {
         if (sl.stream) { (void)hipStreamSynchronize(sl.stream); (void)hipStreamDestroy(sl.stream); }
         sl.arena.release();
     }
+    if (enc_f16_dev_) (void)hipFree(enc_f16_dev_);
     if (stream2_) (void)hipStreamDestroy(stream2_);
     for (auto& kv : pe_cache_) (void)hipFree(kv.second);
     for (auto& kv : pp_cache_) (void)hipFree(kv.second);
@@ -668,7 +670,9 @@ float* Engine::encoder_forward(const Ctx& c, const float* x, int B, int T, int* 
         return nullptr;
     }
     FullDimSegs segs;
-    if (encoder_stacks(c, x0, B, T50, nullptr, tap, tap_ptr, tap_dim, &segs)) return nullptr;
+    Ctx cs = c;   // the stacks' launches read the half-precision panels while the switch is on (k2hip_set_encoder_precision)
+    cs.f16 = enc_f16_dev_ ? &enc_f16_ : nullptr;
+    if (encoder_stacks(cs, x0, B, T50, nullptr, tap, tap_ptr, tap_dim, &segs)) return nullptr;
     *Tp = Tpp;
     return encoder_head(c, segs, B, T50, enc_out);
 }
@@ -2355,6 +2359,35 @@ void Engine::debug_op_host(const char* op, const int64_t* iargs, int n_iargs, vo
             const int rep[5] = {(int)pl.family, pl.idx, pl.BM, pl.BN, pl.mode};
             K2_HIP(copy_blocking(plan_out, rep, sizeof rep, hipMemcpyHostToDevice));
             gemm(c, g);
+        } else if (name == "gemm_f16") {
+            // ONE launch of gemm_f16_mfma: W (float32 [N, K]) is packed by the engine's own packer (gemm_f16_layout.h) from the caller's
+            // host copy; cfg = the tile's table index, -1 = plan_gemm_f16's choice; the plan (index, BM, BN) goes back in the last buffer
+            GemmArgs g;
+            g.M = I(); g.N = I(); g.K = I();
+            g.lda = I(); g.ldc = I(); g.ldr = I();
+            g.act = I(); g.act_cols = I(); g.act_after_res = I();
+            const int res_is_C = I(), cfg = I();
+            const int w_k = nbuf + 1;   // (the host copy of W)
+            float *A = P(), *W = P(), *bias = P(), *res = P(), *C = P();
+            int* plan_out = reinterpret_cast<int*>(P());
+            K2_REQUIRE(A && W && C && plan_out && buf_bytes[n_bufs - 1] >= 12, "debug_op_run gemm_f16: A, W, C and a plan buffer of 3 ints are needed");
+            K2_REQUIRE(!(res_is_C && res), "debug_op_run gemm_f16: res_is_C takes no res buffer");
+            K2_REQUIRE(g.M >= 1 && g.N >= 1 && g.K >= 32 && g.K % 32 == 0 && buf_bytes[w_k] == (int64_t)sizeof(float) * g.N * g.K,
+                       "debug_op_run gemm_f16: W must be a float32 [N, K] matrix with K %% 32 == 0 (N %d, K %d)", g.N, g.K);
+            g.A = A; g.W = W; g.ldw = g.K; g.bias = bias; g.res = res_is_C ? C : res; g.C = C;
+            K2_REQUIRE(gemm_f16_fits(g), "gemm_f16: not a form the half-precision kernel takes");
+            std::vector<uint16_t> panels((size_t)gemm_f16_panel_halves(g.N, g.K));
+            if (!gemm_f16_pack(static_cast<const float*>(bufs[w_k]), g.N, g.K, panels.data()))
+                failf(K2HIP_ERR_INVALID, "debug_op_run gemm_f16: W has a weight that is not finite in half precision");
+            char* pp = nullptr;
+            K2_HIP(hipMalloc(&pp, panels.size() * sizeof(uint16_t)));
+            d.base.push_back(pp);
+            K2_HIP(copy_blocking(pp, panels.data(), panels.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+            const GemmF16Plan pl = plan_gemm_f16(g, cfg);
+            const int rep[3] = {pl.idx, pl.BM, pl.BN};
+            K2_HIP(copy_blocking(plan_out, rep, sizeof rep, hipMemcpyHostToDevice));
+            gemm_f16_launch(c, g, reinterpret_cast<const uint16_t*>(pp), pl);
+            K2_HIP(hipGetLastError());
         } else if (name == "gemm_glu_causal_conv") {
             float *x = P(), *wg = P(), *bg = P(), *pool = P();
             const long long ss = L(), off = L();
@@ -3372,6 +3405,43 @@ void Engine::debug_gemm_trace(int M, int N, int K, int act, bool with_res, int c
     gemm(c, g);
     K2_HIP(hipStreamSynchronize(stream_));
     K2_HIP(copy_blocking(out, dbg, sizeof(unsigned long long) * (size_t)words, hipMemcpyDeviceToHost));
+}
+
+void Engine::set_encoder_precision(bool half) {
+    K2_HIP(hipSetDevice(device_));
+    if (half == (enc_f16_dev_ != nullptr)) {
+        if (!half) encoder_half_pack(*model_, nullptr, nullptr);   // (off on a model that has no such switch: still UNSUPPORTED)
+        return;
+    }
+    if (!half) {
+        synchronize();
+        K2_HIP(hipFree(enc_f16_dev_));
+        enc_f16_dev_ = nullptr;
+        enc_f16_bytes_ = 0;
+        enc_f16_ = GemmF16Map();
+        return;
+    }
+    std::vector<uint16_t> blob;
+    std::vector<EncoderHalfEntry> entries;
+    encoder_half_pack(*model_, &blob, &entries);   // throws before any device work
+    K2_REQUIRE(!entries.empty(), "set_encoder_precision: the model has no encoder weight with K %% 32 == 0");
+    void* p = nullptr;
+    K2_HIP(hipMalloc(&p, blob.size() * sizeof(uint16_t)));
+    const hipError_t rc = copy_blocking(p, blob.data(), blob.size() * sizeof(uint16_t), hipMemcpyHostToDevice);
+    if (rc != hipSuccess) {
+        (void)hipFree(p);
+        K2_HIP(rc);
+    }
+    GemmF16Map map;
+    for (const EncoderHalfEntry& e : entries) map.by_weight[e.dev] = {static_cast<const uint16_t*>(p) + e.off, e.N, e.K};
+    enc_f16_ = std::move(map);
+    enc_f16_dev_ = p;
+    enc_f16_bytes_ = (int64_t)(blob.size() * sizeof(uint16_t));
+}
+void Engine::encoder_f16_stats(int64_t* launches, int64_t* panels, int64_t* panel_bytes) const {
+    if (launches) *launches = enc_f16_.launches;
+    if (panels) *panels = (int64_t)enc_f16_.by_weight.size();
+    if (panel_bytes) *panel_bytes = enc_f16_bytes_;
 }
 
 void* Engine::dev_alloc(int64_t bytes) {

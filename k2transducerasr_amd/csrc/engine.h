@@ -39,6 +39,19 @@ struct OfflineResult {
     std::vector<std::vector<int32_t>> timestamps;
 };
 
+// One weight of the half-precision encoder switch (encoder_half.cpp): its name, float32 device pointer, shape, and where its f16
+// panels (gemm_f16_layout.h) start in the blob, in halves
+struct EncoderHalfEntry {
+    std::string name;
+    const float* dev = nullptr;
+    int N = 0, K = 0;
+    int64_t off = 0;
+};
+// The panels of every 2-D encoder.* weight with K % 32 == 0 that the offline Zipformer2 layer body hands to linear(), back to back in
+// *blob, from the model's host views.  Host only.  Throws K2HIP_ERR_UNSUPPORTED for a model that is not an offline Zipformer2 and
+// K2HIP_ERR_INVALID, naming the tensor, for a weight that is not finite in f16.
+void encoder_half_pack(const Model& m, std::vector<uint16_t>* blob, std::vector<EncoderHalfEntry>* entries);
+
 class Engine {
   public:
     Engine(const std::string& weights, const char* overrides, int device);
@@ -374,6 +387,14 @@ class Engine {
     void online_step_ctc_prefix_bias(const int* slots, const float* const* chunks, const long long* plens, const int* nchunks, int B, int K,
                                      const int* cp_in, int* cp_out, const CtcPrefixBiasIO& bias, const int* fifo_heads = nullptr);
 
+    // k2hip_set_encoder_precision (semantics in include/k2hip.h).  On: packs the f16 panels (encoder_half_pack), uploads them in ONE
+    // device allocation and fills the map that encoder_forward hands to the Ctx of the offline Zipformer2 stacks -- gemm() then runs
+    // every covered launch (gemm_f16_form) over one of those weights through gemm_f16_mfma.  A refusal leaves the engine on float32
+    // with nothing allocated.  Off: the panels are freed.  No batch may be in flight.
+    void set_encoder_precision(bool half);
+    bool encoder_half() const { return enc_f16_dev_ != nullptr; }
+    // gemm_f16_mfma launches since the switch was last turned on, resident panels and their bytes (k2hip_debug.h)
+    void encoder_f16_stats(int64_t* launches, int64_t* panels, int64_t* panel_bytes) const;
     void set_instrument(bool on) { instrument_ = on; }
     const std::vector<GemmLaunchRec>& gemm_log() const { return gemm_log_; }
     // decoding method of the batch entry points: 0 = greedy_search (the reference's only method), K >= 1 = modified beam
@@ -594,6 +615,9 @@ class Engine {
     void vad_device_call(VadJob* jobs, int B, const std::function<void(const Ctx&, std::vector<const float*>&)>& prepare);
     VadTaps vad_taps_;
     std::array<double, 3> long_ms_{};
+    GemmF16Map enc_f16_;
+    void* enc_f16_dev_ = nullptr;
+    int64_t enc_f16_bytes_ = 0;
     const RnnLm* rnn_host_ = nullptr;
     RnnLmDev rnn_dev_;
     bool rnn_fusion_ = false;

@@ -229,6 +229,45 @@ int gemm_kind(const GemmArgs& a, const GemmPlan& p) {
     return base;
 }
 
+// ---- the half-precision-operand GEMM (gemm_f16.hip) ----------------------------------------------------------------------------
+bool gemm_f16_fits(const GemmArgs& a) {
+    if (a.M < 1 || a.N < 1 || a.K < 32 || a.K % 32 != 0 || a.lda % 4 != 0 || a.lda < a.K) return false;
+    if (a.glu || a.mul || a.byp_orig || a.w_kn || a.cv_Fout > 0 || a.nb0 * a.nb1 != 1 || a.res_div != 1 || a.skip_if_zero) return false;
+    if (a.cf_pool || a.dw_w) return false;   // the fused conv tails
+    // (the epilogue's 32-bit lane offsets and the kernel's row offsets)
+    return (long long)a.M * a.lda < (1ll << 29) && (long long)a.M * a.ldc < (1ll << 29);
+}
+
+bool gemm_f16_form(const GemmArgs& a) {
+    if (!gemm_f16_fits(a)) return false;
+    // Few output columns over a long K (the attention value projections, N = heads x 12): the launch reads M x K floats of A to write a
+    // sliver of C, which half-precision operands do not shrink, and the float32 kernels' 16-row column-chunk tiles split it over more
+    // workgroups than a 64-column tile does.  Measured slower in f16 (tools/encoder_half_bench.py zipformer2-large-en 32 10, us summed
+    // over the batch's launches, f32 -> f16): 4064 x 48 x 512 196.9 -> 230.4, 8096 x 48 x 256 84.0 -> 92.8, 2048 x 96 x 768 167.3 ->
+    // 169.0; 16160 x 48 x 192 (60.1 -> 46.4) is faster and stays.
+    return !(a.N <= 96 && a.K >= 256);
+}
+
+// Largest tile that still puts a workgroup on each of the 256 CUs; below that the 64 x 64 tile, whose grid is the largest the table has.
+// (Two workgroups of any tile fit a CU, so a grid of 256 .. 511 large tiles runs as one round.)
+GemmF16Plan plan_gemm_f16(const GemmArgs& a, int force) {
+    static const GemmF16Plan table[] = {
+#define X(i, bm, bn) {i, bm, bn},
+        K2_F16_TABLE(X)
+#undef X
+    };
+    constexpr int n = (int)(sizeof(table) / sizeof(table[0]));
+    if (force >= 0) {
+        K2_REQUIRE(force < n, "no f16 gemm tile %d", force);
+        return table[force];
+    }
+    for (int i = 0; i < n - 1; i++)
+        if ((long long)cdiv(a.M, table[i].BM) * cdiv(a.N, table[i].BN) >= 256) return table[i];
+    return table[n - 1];
+}
+
+int gemm_kind_f16(const GemmF16Plan& p) { return 128 + 256 * (p.BM / 32) + 4096 * (p.BN / 32) + (1 << 21); }
+
 int glu_conv_ring_entry(int B, int Tc, int D, int K) {
     const int M = B * Tc, N = 2 * D;
     // tiles: 32 / 64 rows of whole streams (Tc | 32), 32 / 64 GEMM columns of whole (value | gate) blocks

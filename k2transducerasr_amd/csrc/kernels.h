@@ -2,6 +2,8 @@
 // returns immediately; in a dry run (ctx.dry) nothing is launched -- the dry
 // pass only sizes the arena.
 #pragma once
+#include <unordered_map>
+
 #include "ctc_prefix_layout.h"
 #include "common.h"
 
@@ -72,8 +74,21 @@ struct GemmLaunchRec {  // one row per GEMM launch of an instrumented call
     float us;
 };
 
+// Half-precision weight panels of the offline Zipformer2 encoder's linear layers (Engine::set_encoder_precision; gemm_f16_layout.h):
+// float32 device pointer of a [N, K] weight -> its f16 panels.  A Ctx that carries the map sends every gemm() of the covered form
+// (gemm_f16_form) whose W is in it to gemm_f16_mfma; every other launch, and every Ctx without a map, takes the float32 path.
+struct GemmF16Panel {
+    const uint16_t* panels;
+    int N, K;
+};
+struct GemmF16Map {
+    std::unordered_map<const float*, GemmF16Panel> by_weight;
+    mutable int64_t launches = 0;   // gemm_f16_mfma launches since the map was built
+};
+
 struct GreedyLaunch;
 struct Ctx {
+    const GemmF16Map* f16 = nullptr;     // the offline Zipformer2 encoder pass under the half-precision switch only
     std::vector<GemmLaunchRec>* gemm_log = nullptr;  // instrumented runs only
     GreedyLaunch* greedy_rec = nullptr;  // greedy_loop notes its launch here, so that the engine can repeat it with one part per stream
     hipStream_t stream = nullptr;
@@ -260,6 +275,23 @@ struct GemmForceGuard {  // forces cfg code `code` for its lifetime, automatic a
     GemmForceGuard(const GemmForceGuard&) = delete;
     GemmForceGuard& operator=(const GemmForceGuard&) = delete;
 };
+// ---- the half-precision-operand GEMM (gemm_f16.hip): C = epilogue(f16(A) . f16(W)^T), float32 sums on v_mfma_f32_32x32x16_f16, A
+// rounded to nearest even on its way into LDS, W read from the panels of gemm_f16_layout.h.  Workgroup tiles: BM, BN (four waves as 2 x 2)
+#define K2_F16_TABLE(X) X(0, 128, 128) X(1, 128, 64) X(2, 64, 64)
+struct GemmF16Plan {
+    int idx = 0, BM = 0, BN = 0;
+};
+// what the kernel can compute: one plain [M, K] x [N, K] problem with K % 32 == 0 and lda % 4 == 0; bias, act, act_cols, res (in
+// place too) and act_after_res in the epilogue; nothing else (gemm_plan.cpp)
+bool gemm_f16_fits(const GemmArgs& a);
+// what gemm() sends to it: a call that fits, less the shapes that measured slower than the float32 kernels (few columns over a long K)
+bool gemm_f16_form(const GemmArgs& a);
+// the tile of a covered launch: forced (a table index) or, force < 0, by workgroup count against the 256 CUs; throws for a bad index
+GemmF16Plan plan_gemm_f16(const GemmArgs& a, int force = -1);
+int gemm_kind_f16(const GemmF16Plan& p);   // GemmLaunchRec.kind of such a launch: bit 21 + the tile in the pipelined kernels' bits
+// ONE launch of table entry p.idx; a.W is not read.  The caller has checked gemm_f16_fits(a) and that the panels are those of a [a.N, a.K] matrix
+void gemm_f16_launch(const Ctx& ctx, const GemmArgs& a, const uint16_t* panels, const GemmF16Plan& p);
+
 // convenience: plain Linear  C = act(A W^T + b) (+res)
 void linear(const Ctx& ctx, const float* A, int lda, const float* W, const float* bias, float* C, int ldc, int M, int K,
             int N, int act = ACT_NONE, const float* res = nullptr, int ldr = 0);
