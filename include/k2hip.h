@@ -1203,6 +1203,14 @@ int32_t k2hip_set_rnn_lm_rescoring_precision(k2hip_model_t* model, int32_t half)
  * enters become infinite or NaN; a NaN stays a NaN.  Nothing is clamped or rescaled.
  * A MODEL THAT DOES NOT FIT: a covered weight that is not finite in f16 (|w| >= 65520, or not finite to begin with) refuses the switch
  * with K2HIP_ERR_INVALID, the message naming the tensor, before any device work; the model stays on float32.
+ * LEVEL 2 (half == 2; every other non-zero value is level 1, whose launches, panels and bits are as described above): everything level 1
+ * covers, plus, under the same K % 32 == 0 condition, the layer's remaining weight launches -- the stacked feed_forward1.in_proj /
+ * attention-weights in_proj (SwooshL on the feed-forward columns only; the attention scores then read an f16-operand product), the
+ * gated in_proj launches of NonlinAttention (x * tanh(s)) and of the conv modules (GLU), feed_forward2.out_proj with its in-place
+ * residual and bypass mix, and the conv modules' one-launch form in_proj + GLU + depthwise conv + SwooshR (the convolution itself is
+ * float32 arithmetic on the float32 gated values, in the float32 kernel's order).  Level 2 builds more panels; a newly covered weight
+ * that is not finite in f16 refuses it with K2HIP_ERR_INVALID, naming the checkpoint tensor, and the model stays at the level it had.
+ * Going from 2 to 1 or 0 frees the panels level 2 added.
  * SCOPE: the streaming step (k2hip_online_*) never reads the switch.  Conformer, Zipformer v1, LSTM and streaming-export models:
  * K2HIP_ERR_UNSUPPORTED.  Turning the switch off frees the panels. */
 int32_t k2hip_set_encoder_precision(k2hip_model_t* model, int32_t half);

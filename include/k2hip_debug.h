@@ -69,12 +69,18 @@ int32_t k2hip_debug_conv_fused_plan(int32_t B, int32_t T, int32_t D, int32_t K, 
  * (tests/test_encoder_half.py):
  * k2hip_debug_gemm_f16_plan: fields = M, N, K, lda, ldc, glu, mul, byp_orig, w_kn, cv_Fout, nb0, nb1, res_div, skip_if_zero, cf_pool, dw_w
  *   (16 values; a pointer field as 0 / 1 = null / set).  *form = gemm_f16_form() of those GemmArgs; plan[3] = plan_gemm_f16()'s table
- *   index, BM, BN for them (force: a table index, -1 = the plan's choice), or -1s when the form is refused.
+ *   index, BM, BN for them (force: a table index, -1 = the plan's choice), or -1s when the form is refused.  With 20 values -- those,
+ *   then the level of the switch (1 / 2), glu_cols, dw_K, dw_T -- the predicate is asked at that level (tests/test_encoder_half_wide.py).
+ * k2hip_debug_conv_f16_plan: the offline conv module under level 2 (csrc/gemm_plan.cpp) for B streams of T frames, D channels, K taps:
+ *   *entry = glu_dwconv_f16_entry (the K2_F16_TABLE index of the fused f16 launch's tile, 1: 128 x 64, 2: 64 x 64; -1: none holds the
+ *   stream), *route = glu_dwconv_f16_route (1 the fused f16 launch, 2 the gated f16 GEMM + dwconv1d_swoosh, 3 what level 1 does; the
+ *   switch K2HIP_F16_CONV forces 1 / 2 / 3).
  * k2hip_debug_gemm_f16_pack: the panels (csrc/gemm_f16_layout.h) of the float32 matrix W [N, K] into out (cap_halves >= 32 K
  *   ceil(N / 32) f16 bit patterns); *finite = 0 when a weight is not finite in f16.
  * k2hip_debug_encoder_f16_stats: gemm_f16_mfma launches of the model since its switch was last turned on, resident panels (weights) and
  *   their bytes; zeros while the switch is off.  Each out pointer may be NULL. */
 int32_t k2hip_debug_gemm_f16_plan(const int64_t* fields, int32_t n_fields, int32_t force, int32_t* form, int32_t* plan);
+int32_t k2hip_debug_conv_f16_plan(int32_t B, int32_t T, int32_t D, int32_t K, int32_t* entry, int32_t* route);
 int32_t k2hip_debug_gemm_f16_pack(const float* W, int32_t N, int32_t K, uint16_t* out, int64_t cap_halves, int32_t* finite);
 int32_t k2hip_debug_encoder_f16_stats(k2hip_model_t* model, int64_t* launches, int64_t* panels, int64_t* panel_bytes);
 /* ---- other encoder kernels ---------------------------------------------------------------------- */
@@ -126,6 +132,10 @@ int32_t k2hip_debug_encoder_f16_stats(k2hip_model_t* model, int64_t* launches, i
  *     K2_F16_TABLE: 0 128 x 128, 1 128 x 64, 2 64 x 64; -1 = plan_gemm_f16's choice).  bufs A, W (float32 [N, K], K % 32 == 0: packed by
  *     the engine's own packer inside the hook), bias, res, C, then a buffer of 3 int32 the hook fills with the plan (table index, BM,
  *     BN).  A W that is not finite in f16 is K2HIP_ERR_INVALID.
+ *   "gemm_f16_form" (tests/test_encoder_half_wide_gpu.py): the same launch in the forms of the switch's level 2.  ints as "gemm_f16",
+ *     then glu, glu_cols, ld_orig, dw_K, dw_T; bufs A, W, bias, res, C, byp_orig, byp_scale, the conv taps [dw_K][N / 2] and the conv
+ *     bias [N / 2] (each optional; with the taps C is y [M, N / 2] and cfg 1 / 2 / -1 names the tile that holds dw_T frames), then the
+ *     plan buffer.
  * The two kernels of the forced alignment (csrc/align.hip, tests/test_align_gpu.py); every stream's plane [T_b][U_b + 1] lies back to
  * back in stream order, T_b = n_frames[b] (a null buffer: Tp), U_b = lens[b]; cells outside the reachable band keep what they held:
  *   "lattice_logprobs": buffers enc [B][Tp][J], n_frames [B] int32, ids (int64, the targets back to back), lens [B] int32, stay, emit

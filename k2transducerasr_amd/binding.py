@@ -1056,14 +1056,16 @@ class Model:
         _bind_rnn_lm(self._L)
         self._chk(self._L.k2hip_set_rnn_lm_rescoring_precision(self._h, int(bool(half))))
 
-    def set_encoder_precision(self, half: bool):
+    def set_encoder_precision(self, half):
         """k2hip_set_encoder_precision: the plain linear layers of the offline Zipformer2 encoder's layers (K % 32 == 0) round both
         operands to f16 with float32 sums (gemm_f16_mfma); the weights' f16 panels are built here and freed when the switch returns.
         Epilogues, every other kernel and the search stay float32.  K2HipError (unsupported) for other model families; (invalid,
-        naming the tensor) for a weight that is not finite in f16 -- the model then stays on float32."""
+        naming the tensor) for a weight that is not finite in f16 -- the model then stays as it was.  half: False / 0 off, True / 1 the
+        plain linear layers, 2 also the stacked feed_forward1 / attention in_proj, the gated in_proj launches (with the conv modules'
+        fused depthwise-conv tail) and feed_forward2.out_proj with its bypass mix."""
         self._L.k2hip_set_encoder_precision.argtypes = [C.c_void_p, C.c_int32]
         self._L.k2hip_set_encoder_precision.restype = C.c_int32
-        self._chk(self._L.k2hip_set_encoder_precision(self._h, int(bool(half))))
+        self._chk(self._L.k2hip_set_encoder_precision(self._h, int(half)))
 
     def encoder_f16_stats(self) -> dict:
         """gemm_f16_mfma launches since the switch was last turned on; resident weight panels; their bytes"""
@@ -1732,17 +1734,18 @@ class OfflineRecognizer:
     f16 (Model.set_rnn_lm_fusion_precision); rnn_lm_rescore_half=True: the rescoring's recurrent product runs in f16
     (Model.set_rnn_lm_rescoring_precision), the fused search is untouched by it.  lodr_lm: an NgramLm (usually a bi-gram) subtracted
     with weight lodr_scale <= 0 wherever rnn_lm acts, in the rescoring or in the fused search (Model.set_lodr_lm).  encoder_half=True:
-    the offline Zipformer2 encoder's plain linear layers run with f16 operands and float32 sums (Model.set_encoder_precision)."""
+    the offline Zipformer2 encoder's plain linear layers run with f16 operands and float32 sums (Model.set_encoder_precision);
+    encoder_half=2: its gated, stacked, bypass and conv-tail launches too."""
 
     def __init__(self, weights_path: str, device: int = 0, decoding_method: str = "greedy_search", beam: int = 4, hotwords=None,
                  hotwords_score: float = 1.5, nbest: int = 1, ngram_lm: Optional["NgramLm"] = None, ngram_lm_scale: float = 0.3,
                  ctc_prefix_biasing: bool = False, rnn_lm: Optional["RnnLm"] = None, rnn_lm_scale: float = 0.5, rnn_lm_fusion: bool = False,
                  lodr_lm: Optional["NgramLm"] = None, lodr_scale: float = -0.1, rnn_lm_half: bool = False,
-                 rnn_lm_rescore_half: bool = False, encoder_half: bool = False):
+                 rnn_lm_rescore_half: bool = False, encoder_half=False):
         self.model = Model(weights_path, device)
         self.model.set_decoding_method(decoding_method, beam)
         if encoder_half:
-            self.model.set_encoder_precision(True)
+            self.model.set_encoder_precision(encoder_half)
         if rnn_lm_rescore_half:
             self.model.set_rnn_lm_rescoring_precision(True)
         if nbest != 1:   # (streams then carry .alternatives() / .token_log_probs() after get_results)

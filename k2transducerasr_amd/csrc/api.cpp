@@ -3201,7 +3201,7 @@ int32_t k2hip_debug_conv_fused_plan(int32_t B, int32_t T, int32_t D, int32_t K, 
 int32_t k2hip_debug_gemm_f16_plan(const int64_t* f, int32_t n_fields, int32_t force, int32_t* form, int32_t* plan) {
     return guard([&] {
         NEED(f); NEED(form); NEED(plan);
-        K2_REQUIRE(n_fields == 16, "debug_gemm_f16_plan: 16 fields, not %d", n_fields);
+        K2_REQUIRE(n_fields == 16 || n_fields == 20, "debug_gemm_f16_plan: 16 or 20 fields, not %d", n_fields);
         static const float dummy = 0.f;
         static const int idummy = 0;
         GemmArgs a;
@@ -3209,12 +3209,25 @@ int32_t k2hip_debug_gemm_f16_plan(const int64_t* f, int32_t n_fields, int32_t fo
         a.glu = (int)f[5]; a.mul = f[6] ? &dummy : nullptr; a.byp_orig = f[7] ? &dummy : nullptr; a.w_kn = (int)f[8]; a.cv_Fout = (int)f[9];
         a.nb0 = (int)f[10]; a.nb1 = (int)f[11]; a.res_div = (int)f[12]; a.skip_if_zero = f[13] ? &idummy : nullptr;
         a.cf_pool = f[14] ? const_cast<float*>(&dummy) : nullptr; a.dw_w = f[15] ? &dummy : nullptr;
-        *form = gemm_f16_form(a) ? 1 : 0;
+        int level = 1;
+        if (n_fields == 20) {   // the level of the switch, glu_cols, and the conv tail's taps and frames per stream
+            level = (int)f[16]; a.glu_cols = (int)f[17]; a.dw_K = (int)f[18]; a.dw_T = (int)f[19];
+            a.byp_scale = a.byp_orig; a.dw_b = a.dw_w;
+        }
+        *form = gemm_f16_form(a, level) ? 1 : 0;
         plan[0] = plan[1] = plan[2] = -1;
         if (*form) {
             const GemmF16Plan p = plan_gemm_f16(a, force);
             plan[0] = p.idx; plan[1] = p.BM; plan[2] = p.BN;
         }
+    });
+}
+int32_t k2hip_debug_conv_f16_plan(int32_t B, int32_t T, int32_t D, int32_t K, int32_t* entry, int32_t* route) {
+    return guard([&] {
+        NEED(entry); NEED(route);
+        tunables_init_from_env();
+        *entry = glu_dwconv_f16_entry(B, T, D, K);
+        *route = glu_dwconv_f16_route(B, T, D, K);
     });
 }
 int32_t k2hip_debug_gemm_f16_pack(const float* W, int32_t N, int32_t K, uint16_t* out, int64_t cap_halves, int32_t* finite) {
@@ -4055,7 +4068,7 @@ int32_t k2hip_set_encoder_precision(k2hip_model_t* model, int32_t half) {
         Engine& e = model->engine;
         EngineLock lk(e);
         K2_REQUIRE(e.batches_in_flight() == 0, "set_encoder_precision: %d submitted batches are in flight; wait for them first", e.batches_in_flight());
-        e.set_encoder_precision(half != 0);
+        e.set_encoder_level(half);
     });
 }
 int32_t k2hip_debug_rnn_lm_stream_fusion_stats(k2hip_model_t* model, int64_t* chunk_calls, int64_t* live_blocks, int64_t* pool_bytes) {

@@ -16,18 +16,40 @@ static const char* const kHalfSuffixes[] = {
     "conv_module2.in_proj", "conv_module2.out_proj",
 };
 
-void encoder_half_pack(const Model& m, std::vector<uint16_t>* blob, std::vector<EncoderHalfEntry>* entries) {
+// Level 2 adds the weights of the layer body's other launches, under the names the engine asks the model for: the stacked
+// [feed_forward1.in_proj ; self_attn_weights.in_proj] and the row-interleaved "#glu" in_proj copies (model.cpp add_repacks keeps their
+// host copies, so the panels hold exactly the rows the float32 launches read), and feed_forward2.out_proj.
+static const char* const kHalfNames2[] = {
+    "#ff1_attn_in.weight", "nonlin_attention.in_proj.weight#glu", "conv_module1.in_proj.weight#glu", "conv_module2.in_proj.weight#glu",
+    "feed_forward2.out_proj.weight",
+};
+
+// The checkpoint tensor behind row `row` of a repacked weight, for the refusal's message.
+static std::string source_name(const Model& m, const std::string& prefix, const std::string& suffix, int row) {
+    if (suffix == "#ff1_attn_in.weight") {
+        const int F1 = (int)m.tensor(prefix + "feed_forward1.in_proj.weight").dims[0];
+        return prefix + (row < F1 ? "feed_forward1.in_proj.weight" : "self_attn_weights.in_proj.weight");
+    }
+    const size_t cut = suffix.find("#glu");
+    return prefix + (cut == std::string::npos ? suffix : suffix.substr(0, cut));
+}
+
+void encoder_half_pack(const Model& m, std::vector<uint16_t>* blob, std::vector<EncoderHalfEntry>* entries, int level) {
     const Config& cf = m.cfg();
     if (cf.conformer || cf.zip1 || cf.lstm || cf.streaming)
         failf(K2HIP_ERR_UNSUPPORTED, "set_encoder_precision: only the offline Zipformer2 encoder (zipformer2, zipformer2ctc) has half-precision linear layers");
     if (!blob || !entries) return;   // (the model check alone)
     blob->clear();
     entries->clear();
+    std::vector<std::string> suffixes;
+    for (const char* suffix : kHalfSuffixes) suffixes.push_back(std::string(suffix) + ".weight");
+    if (level >= 2) suffixes.insert(suffixes.end(), std::begin(kHalfNames2), std::end(kHalfNames2));
     for (int si = 0; si < cf.ns; si++)
         for (int li = 0; li < cf.nlayer[si]; li++)
-            for (const char* suffix : kHalfSuffixes) {
-                char name[160];
-                snprintf(name, sizeof name, "encoder.encoders.%d.layers.%d.%s.weight", si, li, suffix);
+            for (const std::string& suffix : suffixes) {
+                char prefix[96];
+                snprintf(prefix, sizeof prefix, "encoder.encoders.%d.layers.%d.", si, li);
+                const std::string name = prefix + suffix;
                 if (!m.has(name)) continue;
                 const Tensor& t = m.tensor(name);
                 if (t.ndim != 2 || t.dims[1] % 32 != 0 || t.dims[1] < 32 || !t.host) continue;   // other K stay on float32
@@ -38,8 +60,13 @@ void encoder_half_pack(const Model& m, std::vector<uint16_t>* blob, std::vector<
                 e.K = (int)t.dims[1];
                 e.off = (int64_t)blob->size();
                 blob->resize(blob->size() + (size_t)gemm_f16_panel_halves(e.N, e.K));
-                if (!gemm_f16_pack(t.host, e.N, e.K, blob->data() + e.off))
-                    failf(K2HIP_ERR_INVALID, "set_encoder_precision: %s has a weight that is not finite in half precision; the model stays on float32", name);
+                if (!gemm_f16_pack(t.host, e.N, e.K, blob->data() + e.off)) {
+                    int row = 0;   // the first row with such a weight: which checkpoint tensor a repacked row came from
+                    std::vector<uint16_t> one((size_t)gemm_f16_panel_halves(1, e.K));
+                    while (row < e.N - 1 && gemm_f16_pack(t.host + (size_t)row * e.K, 1, e.K, one.data())) row++;
+                    failf(K2HIP_ERR_INVALID, "set_encoder_precision: %s has a weight that is not finite in half precision; the model stays as it was",
+                          source_name(m, prefix, suffix, row).c_str());
+                }
                 entries->push_back(std::move(e));
             }
 }

@@ -2388,6 +2388,40 @@ void Engine::debug_op_host(const char* op, const int64_t* iargs, int n_iargs, vo
             K2_HIP(copy_blocking(plan_out, rep, sizeof rep, hipMemcpyHostToDevice));
             gemm_f16_launch(c, g, reinterpret_cast<const uint16_t*>(pp), pl);
             K2_HIP(hipGetLastError());
+        } else if (name == "gemm_f16_form") {
+            // ONE launch of gemm_f16_mfma in the forms of the switch's level 2: "gemm_f16"'s arguments, then glu, glu_cols, ld_orig, dw_K,
+            // dw_T and behind C the bypass original, its scale, the conv taps [dw_K][N / 2] and the conv bias
+            GemmArgs g;
+            g.M = I(); g.N = I(); g.K = I();
+            g.lda = I(); g.ldc = I(); g.ldr = I();
+            g.act = I(); g.act_cols = I(); g.act_after_res = I();
+            const int res_is_C = I(), cfg = I();
+            g.glu = I(); g.glu_cols = I(); g.ld_orig = I(); g.dw_K = I(); g.dw_T = I();
+            const int w_k = nbuf + 1;   // (the host copy of W)
+            float *A = P(), *W = P(), *bias = P(), *res = P(), *C = P(), *orig = P(), *scale = P(), *dw_w = P(), *dw_b = P();
+            int* plan_out = reinterpret_cast<int*>(P());
+            K2_REQUIRE(A && W && C && plan_out && buf_bytes[n_bufs - 1] >= 12, "debug_op_run gemm_f16_form: A, W, C and a plan buffer of 3 ints are needed");
+            K2_REQUIRE(!(res_is_C && res), "debug_op_run gemm_f16_form: res_is_C takes no res buffer");
+            K2_REQUIRE(g.M >= 1 && g.N >= 1 && g.K >= 32 && g.K % 32 == 0 && buf_bytes[w_k] == (int64_t)sizeof(float) * g.N * g.K,
+                       "debug_op_run gemm_f16_form: W must be a float32 [N, K] matrix with K %% 32 == 0 (N %d, K %d)", g.N, g.K);
+            g.A = A; g.W = W; g.ldw = g.K; g.bias = bias; g.res = res_is_C ? C : res; g.C = C;
+            g.byp_orig = orig; g.byp_scale = scale; g.dw_w = dw_w; g.dw_b = dw_b;
+            K2_REQUIRE(gemm_f16_fits(g, 2), "gemm_f16_form: not a form the half-precision kernel takes");
+            K2_REQUIRE(!dw_w || (buf_bytes[w_k + 6] >= (int64_t)sizeof(float) * g.dw_K * (g.N / 2) && buf_bytes[w_k + 7] >= (int64_t)sizeof(float) * (g.N / 2) && bias),
+                       "debug_op_run gemm_f16_form: the conv tail needs taps [dw_K][N / 2], a conv bias [N / 2] and the GEMM bias");
+            std::vector<uint16_t> panels((size_t)gemm_f16_panel_halves(g.N, g.K));
+            if (!gemm_f16_pack(static_cast<const float*>(bufs[w_k]), g.N, g.K, panels.data()))
+                failf(K2HIP_ERR_INVALID, "debug_op_run gemm_f16_form: W has a weight that is not finite in half precision");
+            char* pp = nullptr;
+            K2_HIP(hipMalloc(&pp, panels.size() * sizeof(uint16_t)));
+            d.base.push_back(pp);
+            K2_HIP(copy_blocking(pp, panels.data(), panels.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+            const GemmF16Plan pl = plan_gemm_f16(g, dw_w && cfg < 0 ? (g.dw_T <= 64 ? 2 : 1) : cfg);
+            K2_REQUIRE(!dw_w || ((pl.idx == 1 || pl.idx == 2) && g.dw_T <= pl.BM), "gemm_f16_form: tile %d does not hold a stream of %d frames", pl.idx, g.dw_T);
+            const int rep[3] = {pl.idx, pl.BM, pl.BN};
+            K2_HIP(copy_blocking(plan_out, rep, sizeof rep, hipMemcpyHostToDevice));
+            gemm_f16_launch(c, g, reinterpret_cast<const uint16_t*>(pp), pl);
+            K2_HIP(hipGetLastError());
         } else if (name == "gemm_glu_causal_conv") {
             float *x = P(), *wg = P(), *bg = P(), *pool = P();
             const long long ss = L(), off = L();
@@ -3409,7 +3443,7 @@ void Engine::debug_gemm_trace(int M, int N, int K, int act, bool with_res, int c
 
 void Engine::set_encoder_precision(bool half) {
     K2_HIP(hipSetDevice(device_));
-    if (half == (enc_f16_dev_ != nullptr)) {
+    if (half == (enc_f16_dev_ != nullptr) && (!half || enc_f16_.level == enc_f16_want_)) {
         if (!half) encoder_half_pack(*model_, nullptr, nullptr);   // (off on a model that has no such switch: still UNSUPPORTED)
         return;
     }
@@ -3423,7 +3457,7 @@ void Engine::set_encoder_precision(bool half) {
     }
     std::vector<uint16_t> blob;
     std::vector<EncoderHalfEntry> entries;
-    encoder_half_pack(*model_, &blob, &entries);   // throws before any device work
+    encoder_half_pack(*model_, &blob, &entries, enc_f16_want_);   // throws before any device work
     K2_REQUIRE(!entries.empty(), "set_encoder_precision: the model has no encoder weight with K %% 32 == 0");
     void* p = nullptr;
     K2_HIP(hipMalloc(&p, blob.size() * sizeof(uint16_t)));
@@ -3432,7 +3466,12 @@ void Engine::set_encoder_precision(bool half) {
         (void)hipFree(p);
         K2_HIP(rc);
     }
+    if (enc_f16_dev_) {   // the other level's panels
+        synchronize();
+        (void)hipFree(enc_f16_dev_);
+    }
     GemmF16Map map;
+    map.level = enc_f16_want_;
     for (const EncoderHalfEntry& e : entries) map.by_weight[e.dev] = {static_cast<const uint16_t*>(p) + e.off, e.N, e.K};
     enc_f16_ = std::move(map);
     enc_f16_dev_ = p;

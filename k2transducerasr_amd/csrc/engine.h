@@ -49,8 +49,9 @@ struct EncoderHalfEntry {
 };
 // The panels of every 2-D encoder.* weight with K % 32 == 0 that the offline Zipformer2 layer body hands to linear(), back to back in
 // *blob, from the model's host views.  Host only.  Throws K2HIP_ERR_UNSUPPORTED for a model that is not an offline Zipformer2 and
-// K2HIP_ERR_INVALID, naming the tensor, for a weight that is not finite in f16.
-void encoder_half_pack(const Model& m, std::vector<uint16_t>* blob, std::vector<EncoderHalfEntry>* entries);
+// K2HIP_ERR_INVALID, naming the tensor, for a weight that is not finite in f16.  level 2: also the stacked "#ff1_attn_in", the "#glu"
+// in_proj repacks and feed_forward2.out_proj (a refusal names the checkpoint tensor the offending row came from).
+void encoder_half_pack(const Model& m, std::vector<uint16_t>* blob, std::vector<EncoderHalfEntry>* entries, int level = 1);
 
 class Engine {
   public:
@@ -391,7 +392,13 @@ class Engine {
     // device allocation and fills the map that encoder_forward hands to the Ctx of the offline Zipformer2 stacks -- gemm() then runs
     // every covered launch (gemm_f16_form) over one of those weights through gemm_f16_mfma.  A refusal leaves the engine on float32
     // with nothing allocated.  Off: the panels are freed.  No batch may be in flight.
+    // The level turned on is the one set_encoder_level asked for last (1 until then).  A change between the levels 1 and 2 packs the
+    // new level's panels first: a refusal leaves the engine at the level it had.
     void set_encoder_precision(bool half);
+    void set_encoder_level(int level) {   // 0 = off, 2 = level 2, any other value = level 1
+        enc_f16_want_ = level == 2 ? 2 : 1;
+        set_encoder_precision(level != 0);
+    }
     bool encoder_half() const { return enc_f16_dev_ != nullptr; }
     // gemm_f16_mfma launches since the switch was last turned on, resident panels and their bytes (k2hip_debug.h)
     void encoder_f16_stats(int64_t* launches, int64_t* panels, int64_t* panel_bytes) const;
@@ -618,6 +625,7 @@ class Engine {
     GemmF16Map enc_f16_;
     void* enc_f16_dev_ = nullptr;
     int64_t enc_f16_bytes_ = 0;
+    int enc_f16_want_ = 1;
     const RnnLm* rnn_host_ = nullptr;
     RnnLmDev rnn_dev_;
     bool rnn_fusion_ = false;

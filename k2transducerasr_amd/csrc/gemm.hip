@@ -1641,7 +1641,7 @@ void gemm(const Ctx& ctx, const GemmArgs& a) {
     if (ctx.instrument) K2_HIP(hipEventRecord(ctx.next_event(), ctx.stream));
     // Half-precision operands (Engine::set_encoder_precision): a Ctx that carries the panel map, W in it as this [N, K] matrix, and a
     // call of the covered form.  Everything else -- every Ctx without a map -- takes exactly the float32 path below.
-    if (ctx.f16 && gemm_f16_form(a)) {
+    if (ctx.f16 && gemm_f16_form(a, ctx.f16->level)) {
         const auto it = ctx.f16->by_weight.find(a.W);
         if (it != ctx.f16->by_weight.end() && it->second.N == a.N && it->second.K == a.K && a.ldw == a.K) {
             const GemmF16Plan hp = plan_gemm_f16(a);
@@ -1740,6 +1740,29 @@ bool gemm_glu_causal_conv(const Ctx& ctx, const float* x, const float* wg, const
 bool gemm_glu_dwconv1d(const Ctx& ctx, const float* x, const float* wg, const float* bg, const float* wd, const float* bd, float* y, int B, int T,
                        int D, int K) {
     const int M = B * T, N = 2 * D;
+    // Level 2 of the half-precision switch, the "#glu" in_proj among the panels: glu_dwconv_f16_route names the launches -- the fused
+    // f16 form here, or (return false) the caller's gated GEMM, which gemm() then sends to gemm_f16_mfma, + dwconv1d_swoosh
+    if (ctx.f16 && ctx.f16->level >= 2 && M >= 256) {
+        const auto it = ctx.f16->by_weight.find(wg);
+        const int route = it != ctx.f16->by_weight.end() && it->second.N == N && it->second.K == D ? glu_dwconv_f16_route(B, T, D, K) : 3;
+        if (route == 2) return false;
+        if (route == 1) {
+            ctx.add_flops(2.0 * M * (double)N * D, 2.0 * M * (double)D * K, 1);
+            if (ctx.dry) return true;
+            GemmArgs g;
+            g.A = x; g.lda = D; g.W = wg; g.ldw = D; g.bias = bg; g.C = y; g.ldc = D; g.M = M; g.N = N; g.K = D; g.glu = 1;
+            g.dw_w = wd; g.dw_b = bd; g.dw_K = K; g.dw_T = T;
+            g.xcd_panels = tunables().xcd_panels;
+            const GemmF16Plan hp = plan_gemm_f16(g, glu_dwconv_f16_entry(B, T, D, K));
+            if (ctx.instrument) K2_HIP(hipEventRecord(ctx.next_event(), ctx.stream));
+            if (ctx.instrument && ctx.gemm_log) ctx.gemm_log->push_back({M, N, D, 1, 0, 0, gemm_kind_f16(hp), 0.f});
+            gemm_f16_launch(ctx, g, it->second.panels, hp);
+            ctx.f16->launches++;
+            K2_HIP(hipGetLastError());
+            if (ctx.instrument) K2_HIP(hipEventRecord(ctx.next_event(), ctx.stream));
+            return true;
+        }
+    }
     const int entry = glu_dwconv_pipe_entry(B, T, D, K, false);
     if (entry < 0) return false;
     // (tallied as the two launches it replaces tally themselves, one launch fewer)

@@ -31,7 +31,25 @@
 // barrier per stage.  K % 32 == 0: an odd chunk count ends in a half stage whose second chunk is neither loaded nor multiplied.
 //
 // Epilogue: the C/D layout of 32x32x16_f16 is that of 32x32x2_f32, so it is gemm_epilogue.h's epilogue_rows<16, Rows32> -- bias, every
-// act, act_cols, res (in place too), act_after_res.  Everything else stays on the float32 kernels (gemm_plan.cpp gemm_f16_form).
+// act, act_cols, res (in place too), act_after_res and, at level 2 of the switch, glu / glu_cols and the bypass mix.  Everything else
+// stays on the float32 kernels (gemm_plan.cpp gemm_f16_form).
+//
+// DWK > 0 (15 or 31; BN = 64 only): the offline conv module's form at level 2 -- in_proj + GLU + depthwise Conv1d over time + bias +
+// SwooshR in one launch, the f16 counterpart of gemm_f32_mfma_pipe<..., DWK>.  One M tile per STREAM: the tile of stream b starts at row
+// b dw_T (dw_T <= BM; rows >= dw_T of the tile are staged like any rows -- clamped to M - 1 -- and never used).  A workgroup owns the 32
+// channels of its 64 GEMM columns.  After the K loop, in the stage memory (every wave has passed the loop's last barrier):
+//   xs   [BM + DWK - 1][32] floats: bias + GLU formed operation for operation as epilogue_rows forms them, the value lanes writing frame
+//        t to row DWK / 2 + t; the DWK / 2 rows in front of and behind the stream are zeroed -- the conv's padding.  Rows past
+//        dw_T + DWK - 1 keep whatever the stages left: they feed only frames >= dw_T, which are not stored.
+//   taps [DWK][32] floats behind it.  The float32 form keeps a thread's DWK taps in registers from in front of the K loop; here that
+//        would put 31 more registers on a loop that runs at 142 (128 x 64) -- past the 168 that three waves per SIMD allow.  Instead
+//        every thread requests <= 4 elements of the workgroup's tap tile and its channel's conv bias in front of the K loop (5 registers
+//        across it) and drops the taps into LDS behind the loop.
+//   Thread (channel = tid % 32, frame group = tid / 32) forms FT = BM / 8 consecutive frames (16 / 8) of its channel.  Taps ascending:
+//   tap q is one LDS read (32 lanes, 32 consecutive floats), the input window slides by one row -- one more LDS read -- and every output
+//   takes one fmaf: each sum starts from the conv bias and takes its taps in ascending order, the order and the operations of
+//   k_glu_dwconv1d.  2 LDS reads per FT fmas; live registers FT outputs + FT window.  Then SwooshR and the store to C = y [M, N / 2]
+//   (a 32-lane half writes 128 contiguous bytes).  Frame groups that start at or past dw_T do nothing.
 #include "gemm_epilogue.h"
 #include "kernels.h"
 
@@ -46,13 +64,16 @@ __device__ __forceinline__ f16x8 round8(const float4& lo, const float4& hi) {   
     return f16x8{(_Float16)lo.x, (_Float16)lo.y, (_Float16)lo.z, (_Float16)lo.w, (_Float16)hi.x, (_Float16)hi.y, (_Float16)hi.z, (_Float16)hi.w};
 }
 
-template <int BM, int BN>
+template <int BM, int BN, int DWK = 0>
 __global__ __launch_bounds__(256) void gemm_f16_mfma(GemmArgs g, const uint16_t* __restrict__ panels) {
     constexpr int MT = BM / 64, NT = BN / 64;        // 32 x 32 accumulator tiles of a wave
     constexpr int NU = BM / 64;                      // A runs of 16 floats per thread and stage
     constexpr int NWL = BN / 32;                     // W 16-byte pieces per thread and stage: one per column block
     constexpr int A_HALVES = BM * 64, STAGE = (BM + BN) * 64;
     static_assert(BM % 64 == 0 && BN % 64 == 0, "f16 gemm: four waves of whole 32 x 32 tiles");
+    constexpr int DW_CH = 32, DW_FT = BM / 8, DW_HALF = DWK / 2, DW_XS = (BM + DWK - 1) * DW_CH;   // the conv tail's LDS image, in floats
+    constexpr int DW_NTAP = (DWK * DW_CH + 255) / 256;                                            // tap elements a thread stages
+    static_assert(DWK == 0 || (BN == 64 && DWK % 2 == 1 && (DW_XS + DWK * DW_CH) * 4 <= 2 * STAGE * 2), "f16 gemm: conv tail's tile form");
     extern __shared__ __attribute__((aligned(16))) _Float16 smem_h[];   // [2][STAGE]: the A image, then the W image
 
     const int tid = threadIdx.x;
@@ -61,7 +82,7 @@ __global__ __launch_bounds__(256) void gemm_f16_mfma(GemmArgs g, const uint16_t*
     const int li = lane & 31, lh = lane >> 5;
     int mb_, nb_;
     xcd_tile(mb_, nb_, g.xcd_panels == 1 ? 0 : g.M, g.N);
-    const int m0 = mb_ * BM, n0 = nb_ * BN;
+    const int m0 = DWK > 0 ? mb_ * g.dw_T : mb_ * BM, n0 = nb_ * BN;
     const int K = g.K, nk = K / 32, ns = (nk + 1) / 2;
     const int NB = (g.N + 31) / 32;                  // column blocks the panels hold
 
@@ -119,6 +140,18 @@ __global__ __launch_bounds__(256) void gemm_f16_mfma(GemmArgs g, const uint16_t*
 #pragma unroll
     for (int j = 0; j < NT; j++) bias_pre[j] = g.bias ? g.bias[min(n0 + (wc * NT + j) * 32 + li, g.N - 1)] : 0.f;
 
+    // (DWK: this thread's share of the workgroup's tap tile [DWK][32] and its channel's conv bias, in flight under the K loop)
+    float dw_stage[DWK > 0 ? DW_NTAP : 1], dw_bias = 0.f;
+    if constexpr (DWK > 0) {
+        const int ch0 = n0 >> 1, D = g.N >> 1;   // (N % BN == 0: every channel of the tile exists)
+        dw_bias = g.dw_b[ch0 + (tid & (DW_CH - 1))];
+#pragma unroll
+        for (int i = 0; i < DW_NTAP; i++) {
+            const int e = tid + 256 * i;
+            dw_stage[i] = e < DWK * DW_CH ? g.dw_w[(long long)(e >> 5) * D + ch0 + (e & (DW_CH - 1))] : 0.f;
+        }
+    }
+
     f32x16 acc[MT][NT];
 #pragma unroll
     for (int i = 0; i < MT; i++)
@@ -162,6 +195,56 @@ __global__ __launch_bounds__(256) void gemm_f16_mfma(GemmArgs g, const uint16_t*
         __syncthreads();   // stage s + 1 is whole; everyone has left stage s, which the next iteration's stores overwrite
     }
 
+    if constexpr (DWK > 0) {
+        const int T = g.dw_T;
+        float* xs = reinterpret_cast<float*>(smem_h);   // behind the loop's last barrier nobody reads the stages any more
+        float* taps = xs + DW_XS;
+#pragma unroll
+        for (int i = 0; i < DW_NTAP; i++)
+            if (tid + 256 * i < DWK * DW_CH) taps[tid + 256 * i] = dw_stage[i];
+        for (int e = tid; e < 2 * DW_HALF * DW_CH; e += 256) {   // the time halo
+            const int r = e >> 5;
+            xs[((r < DW_HALF ? r : T + r) << 5) + (e & (DW_CH - 1))] = 0.f;
+        }
+#pragma unroll
+        for (int n = 0; n < NT; n++)
+#pragma unroll
+            for (int i = 0; i < MT; i++) {
+                // (value | gate) blocks of 32 columns: the value lanes (li & 16) == 0 hold channel 16 (column / 32) + (li & 15)
+                const int ch = (wc * NT + n) * 16 + (li & 15), lrow0 = (wr * MT + i) * 32 + 4 * lh;
+#pragma unroll
+                for (int r = 0; r < 16; r++) {
+                    const float v = acc[i][n][r] + bias_pre[n];
+                    const float other = __shfl_xor(v, 16, 64);
+                    const float gated = v * (1.0f / (1.0f + __expf(-other)));   // epilogue_rows' GLU, operation for operation
+                    const int lrow = lrow0 + Rows32::off(r);
+                    if ((li & 16) == 0 && lrow < T) xs[((DW_HALF + lrow) << 5) + ch] = gated;
+                }
+            }
+        __syncthreads();
+        const int ch = tid & (DW_CH - 1), t0 = (tid >> 5) * DW_FT;
+        if (t0 >= T) return;
+        const float* xp = xs + (t0 << 5) + ch;   // rows t0 .. t0 + DW_FT + DWK - 2 <= BM + DWK - 2: inside xs
+        float o[DW_FT], win[DW_FT];
+#pragma unroll
+        for (int i = 0; i < DW_FT; i++) {
+            o[i] = dw_bias;
+            win[i] = xp[i << 5];
+        }
+#pragma unroll
+        for (int q = 0; q < DWK; q++) {   // window slot (q + i) % DW_FT holds input row t0 + q + i
+            const float tq = taps[(q << 5) + ch];
+#pragma unroll
+            for (int i = 0; i < DW_FT; i++) o[i] = __builtin_fmaf(tq, win[(q + i) % DW_FT], o[i]);
+            if (q + 1 < DWK) win[q % DW_FT] = xp[(q + DW_FT) << 5];
+        }
+        float* yp = g.C + (long long)(m0 + t0) * g.ldc + (n0 >> 1) + ch;
+#pragma unroll
+        for (int i = 0; i < DW_FT; i++)
+            if (t0 + i < T) yp[(long long)i * g.ldc] = swoosh_r(o[i]);
+        return;
+    }
+
 #pragma unroll
     for (int n = 0; n < NT; n++)
 #pragma unroll
@@ -183,10 +266,28 @@ void launch_f16(const Ctx& ctx, const GemmArgs& a, const uint16_t* panels) {
     hipLaunchKernelGGL((gemm_f16_mfma<BM, BN>), grid, dim3(256), lds, ctx.stream, a, panels);
 }
 
+// the conv-tail form: one M tile per stream
+template <int BM, int DWK>
+void launch_f16_dwconv(const Ctx& ctx, const GemmArgs& a, const uint16_t* panels) {
+    K2_REQUIRE(a.dw_K == DWK && a.dw_T >= 1 && a.dw_T <= BM && a.M % a.dw_T == 0 && a.N % 64 == 0 && a.ldc >= a.N / 2 && a.dw_w && a.dw_b && a.bias,
+               "gemm_f16: conv tail needs whole streams of <= %d frames and whole column tiles (T %d, M %d, N %d)", BM, a.dw_T, a.M, a.N);
+    dim3 grid(a.N / 64, a.M / a.dw_T, 1);
+    const size_t lds = sizeof(uint16_t) * 2 * (BM + 64) * 64;
+    static LdsAttrOnce lds_attr;
+    lds_attr.ensure(gemm_f16_mfma<BM, 64, DWK>, (int)lds);
+    hipLaunchKernelGGL((gemm_f16_mfma<BM, 64, DWK>), grid, dim3(256), lds, ctx.stream, a, panels);
+}
+
 }  // namespace
 
 void gemm_f16_launch(const Ctx& ctx, const GemmArgs& a, const uint16_t* panels, const GemmF16Plan& p) {
-    K2_REQUIRE(panels && gemm_f16_fits(a), "gemm_f16: %d x %d x %d (lda %d) is not a form the half-precision kernel takes", a.M, a.N, a.K, a.lda);
+    K2_REQUIRE(panels && gemm_f16_fits(a, 2), "gemm_f16: %d x %d x %d (lda %d) is not a form the half-precision kernel takes", a.M, a.N, a.K, a.lda);
+    if (a.dw_w) {
+        K2_REQUIRE((p.idx == 1 || p.idx == 2) && a.dw_T <= p.BM, "gemm_f16: tile %d does not hold a stream of %d frames", p.idx, a.dw_T);
+        if (p.idx == 1) a.dw_K == 15 ? launch_f16_dwconv<128, 15>(ctx, a, panels) : launch_f16_dwconv<128, 31>(ctx, a, panels);
+        else a.dw_K == 15 ? launch_f16_dwconv<64, 15>(ctx, a, panels) : launch_f16_dwconv<64, 31>(ctx, a, panels);
+        return;
+    }
     switch (p.idx) {
 #define X(i, bm, bn) case i: launch_f16<bm, bn>(ctx, a, panels); break;
         K2_F16_TABLE(X)

@@ -230,16 +230,25 @@ int gemm_kind(const GemmArgs& a, const GemmPlan& p) {
 }
 
 // ---- the half-precision-operand GEMM (gemm_f16.hip) ----------------------------------------------------------------------------
-bool gemm_f16_fits(const GemmArgs& a) {
+bool gemm_f16_fits(const GemmArgs& a, int level) {
     if (a.M < 1 || a.N < 1 || a.K < 32 || a.K % 32 != 0 || a.lda % 4 != 0 || a.lda < a.K) return false;
-    if (a.glu || a.mul || a.byp_orig || a.w_kn || a.cv_Fout > 0 || a.nb0 * a.nb1 != 1 || a.res_div != 1 || a.skip_if_zero) return false;
-    if (a.cf_pool || a.dw_w) return false;   // the fused conv tails
+    if (a.mul || a.w_kn || a.cv_Fout > 0 || a.nb0 * a.nb1 != 1 || a.res_div != 1 || a.skip_if_zero || a.cf_pool) return false;
+    if (level < 2 && (a.glu || a.byp_orig || a.dw_w)) return false;
+    if (a.glu) {   // the gated epilogue as gemm() takes it: whole (value | gate) blocks of 32 columns and no other epilogue term
+        const int gc = a.glu_cols > 0 ? a.glu_cols : a.N;
+        if ((a.glu != 1 && a.glu != 2) || gc % 32 != 0 || gc > a.N || a.res || a.byp_orig || a.act != ACT_NONE) return false;
+    }
+    if (a.byp_orig && !a.byp_scale) return false;
+    if (a.dw_w) {  // the conv tail: whole streams, one per M tile of at most 128 rows; whole 64-column tiles of (value | gate) blocks
+        if (a.glu != 1 || a.glu_cols != 0 || !a.dw_b || (a.dw_K != 15 && a.dw_K != 31)) return false;
+        if (a.dw_T < 1 || a.dw_T > 128 || a.M % a.dw_T != 0 || a.N % 64 != 0 || a.ldc < a.N / 2) return false;
+    }
     // (the epilogue's 32-bit lane offsets and the kernel's row offsets)
     return (long long)a.M * a.lda < (1ll << 29) && (long long)a.M * a.ldc < (1ll << 29);
 }
 
-bool gemm_f16_form(const GemmArgs& a) {
-    if (!gemm_f16_fits(a)) return false;
+bool gemm_f16_form(const GemmArgs& a, int level) {
+    if (!gemm_f16_fits(a, level)) return false;
     // Few output columns over a long K (the attention value projections, N = heads x 12): the launch reads M x K floats of A to write a
     // sliver of C, which half-precision operands do not shrink, and the float32 kernels' 16-row column-chunk tiles split it over more
     // workgroups than a 64-column tile does.  Measured slower in f16 (tools/encoder_half_bench.py zipformer2-large-en 32 10, us summed
@@ -302,6 +311,27 @@ int glu_dwconv_pipe_entry(int B, int T, int D, int K, bool streaming) {
     const long long cols = a.N / p.BN;
     if (cdiv((long long)B * cols, 256ll) > cdiv((long long)cdiv(M, (long long)p.BM) * cols, 256ll)) return -1;
     return p.idx;
+}
+
+// The same module under level 2 of the encoder's half-precision switch.  gemm_f16_mfma's conv tail works on 32 channels per workgroup
+// (a 64-column tile of (value | gate) blocks), so its tiles are the table's 128 x 64 and 64 x 64 entries: the smallest that holds a stream.
+int glu_dwconv_f16_entry(int B, int T, int D, int K) {
+    if (B < 1 || T < 1 || T > 128 || D < 32 || D % 32 != 0 || (K != 15 && K != 31)) return -1;
+    if ((long long)B * T * D >= (1ll << 29)) return -1;
+    return T <= 64 ? 2 : 1;
+}
+
+int glu_dwconv_f16_route(int B, int T, int D, int K) {
+    const int e = glu_dwconv_f16_entry(B, T, D, K);
+    const int forced = tunables().f16_conv;
+    if (forced == 1) return e >= 0 ? 1 : 2;
+    if (forced == 2 || forced == 3) return forced;
+    if (tunables().no_fused_conv || tunables().no_glu_epilogue) return 2;   // (the cross-check switches keep the launches apart)
+    if (e < 0) return 2;
+    // one tile per stream must not add a round of the 256 CUs over the packed gated GEMM's grid, as glu_dwconv_pipe_entry requires
+    const long long cols = 2 * D / 64, BM = e == 1 ? 128 : 64;
+    if (cdiv((long long)B * cols, 256ll) > cdiv(cdiv((long long)B * T, BM) * cols, 256ll)) return 2;
+    return 1;
 }
 
 }  // namespace k2hip

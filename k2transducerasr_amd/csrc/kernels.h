@@ -31,6 +31,9 @@ struct Tunables {
                                   // (offline: the low-rate stacks' GLU GEMM + depthwise conv as two launches instead of gemm_glu_dwconv1d)
     int conformer_gemm_scores = 0;  // K2HIP_CONFORMER_GEMM_SCORES: two batched GEMMs + gather/softmax (the long-utterance form)
     int dw7_tiled = 0;            // K2HIP_DW7_TILED: the one-shot LDS-tiled 7x7 depthwise conv also for long inputs (default: the sliding LDS-DMA form)
+    int f16_conv = 0;             // K2HIP_F16_CONV: the offline conv modules' in_proj + conv at level 2 of the encoder's half-precision switch: 0 = by
+                                  // glu_dwconv_f16_route's rule, 1 = the fused f16 launch wherever it has a tile, 2 = the gated f16 GEMM + dwconv1d_swoosh,
+                                  // 3 = as at level 1 (tools/encoder_half_bench.py compares the routes with it)
     int dw1d_tt = 0;              // K2HIP_DW1D_TT: outputs per thread of the depthwise Conv1d (8 / 4 / 2; 0 = by grid size; tests/test_kernels_gpu.py forces each)
     int lstm_seq = 0;             // K2HIP_LSTM_SEQ: layer-by-layer LSTM instead of the layer wavefront
     int greedy_one_part = 0;      // K2HIP_GREEDY_ONE_PART: one workgroup per stream in the search
@@ -83,6 +86,7 @@ struct GemmF16Panel {
 };
 struct GemmF16Map {
     std::unordered_map<const float*, GemmF16Panel> by_weight;
+    int level = 1;                  // 2: the gated, stacked, bypass and conv-tail launches too (gemm_f16_fits)
     mutable int64_t launches = 0;   // gemm_f16_mfma launches since the map was built
 };
 
@@ -282,14 +286,23 @@ struct GemmF16Plan {
     int idx = 0, BM = 0, BN = 0;
 };
 // what the kernel can compute: one plain [M, K] x [N, K] problem with K % 32 == 0 and lda % 4 == 0; bias, act, act_cols, res (in
-// place too) and act_after_res in the epilogue; nothing else (gemm_plan.cpp)
-bool gemm_f16_fits(const GemmArgs& a);
+// place too) and act_after_res in the epilogue; nothing else (gemm_plan.cpp).  level 2 (k2hip_set_encoder_precision's second level)
+// adds the gated epilogue (glu 1 / 2 over whole blocks of 32 columns, nothing else beside it), the bypass mix, and the conv tail
+// (dw_w: glu = 1, dw_K 15 / 31, whole streams of dw_T <= 128 frames, N % 64 == 0, no other epilogue term).
+bool gemm_f16_fits(const GemmArgs& a, int level = 1);
 // what gemm() sends to it: a call that fits, less the shapes that measured slower than the float32 kernels (few columns over a long K)
-bool gemm_f16_form(const GemmArgs& a);
+bool gemm_f16_form(const GemmArgs& a, int level = 1);
+// The conv-tail form of gemm_f16_mfma (level 2): the table entry (1: 128 x 64, 2: 64 x 64) whose M tile holds a stream of T frames of D
+// channels under K taps, -1 = no tile (T > 128, D % 32 != 0, taps other than 15 / 31).
+int glu_dwconv_f16_entry(int B, int T, int D, int K);
+// How a level-2 pass runs the offline conv module's in_proj + GLU + depthwise conv: 1 = the fused f16 launch (glu_dwconv_f16_entry's
+// tile), 2 = the gated f16 GEMM + dwconv1d_swoosh, 3 = what level 1 does (the float32 fused launch where it exists).  By measurement.
+int glu_dwconv_f16_route(int B, int T, int D, int K);
 // the tile of a covered launch: forced (a table index) or, force < 0, by workgroup count against the 256 CUs; throws for a bad index
 GemmF16Plan plan_gemm_f16(const GemmArgs& a, int force = -1);
 int gemm_kind_f16(const GemmF16Plan& p);   // GemmLaunchRec.kind of such a launch: bit 21 + the tile in the pipelined kernels' bits
-// ONE launch of table entry p.idx; a.W is not read.  The caller has checked gemm_f16_fits(a) and that the panels are those of a [a.N, a.K] matrix
+// ONE launch of table entry p.idx; a.W is not read.  The caller has checked gemm_f16_fits(a, 2) and that the panels are those of a [a.N, a.K]
+// matrix.  a.dw_w: the conv-tail form, p.idx 1 or 2 with a.dw_T <= p.BM.
 void gemm_f16_launch(const Ctx& ctx, const GemmArgs& a, const uint16_t* panels, const GemmF16Plan& p);
 
 // convenience: plain Linear  C = act(A W^T + b) (+res)

@@ -1,16 +1,20 @@
-"""The offline batch with the encoder's half-precision switch off and on (Model.set_encoder_precision; csrc/gemm_f16.hip).
+"""The offline batch with the encoder's half-precision switch off, at level 1 and at level 2 (Model.set_encoder_precision;
+csrc/gemm_f16.hip).
 
-    python tools/encoder_half_bench.py [preset] [batch] [seconds]      (defaults: zipformer2-large-en 32 10)
+    python tools/encoder_half_bench.py [preset] [batch] [seconds] [conv route]      (defaults: zipformer2-large-en 32 10 0)
 
 A batch of `batch` synthetic utterances of `seconds` seconds is decoded from samples (offline_greedy_from_samples) ROUNDS times with
-the switch off and on, interleaved round by round in one process after WARMUP rounds of each: "off_ms" / "on_ms" are the medians of
-the calls' total_ms (device events around the whole call), with their [min, max] spread, and encoder_ms beside them.  Then one
-instrumented call each way (every GEMM launch bracketed by events): the launch logs have the same rows in the same order, and the rows
-whose kind carries the f16 family's bit when the switch is on are the covered launches.  "shapes" lists them grouped by (M, N, K, act,
+the switch off, at 1 and at 2, interleaved round by round in one process after WARMUP rounds of each: "off_ms" / "on_ms" / "on2_ms" are
+the medians of the calls' total_ms (device events around the whole call), with their [min, max] spread, and encoder_ms beside them.
+Then one instrumented call each way (every GEMM launch bracketed by events): the launch logs have the same rows in the same order, and
+the rows whose kind carries the f16 family's bit at level 1 are the covered launches.  "shapes" lists them grouped by (M, N, K, act,
 residual): launches per call, microseconds summed over them in float32 and in f16, and the f16 tile.  "covered_f32_ms" / "covered_f16_ms"
-sum those, "gemm_f32_ms" / "gemm_on_ms" are all GEMM launches of the call.  "same_tokens" counts the utterances whose token lists are
-identical off and on.  One JSON line on stdout; there is no time gate (DESIGN.md "Half-precision operands in the encoder's linear
-layers" has the runs taken so far)."""
+sum those, "gemm_f32_ms" / "gemm_on_ms" / "gemm_on2_ms" are all GEMM launches of the call.  "shapes2" / "covered2_*" are the same for the
+launches that carry the bit at level 2 only -- the newly covered ones (a conv module's fused launch counts its convolution on both
+sides; where level 2 takes the gated f16 GEMM + dwconv1d_swoosh in place of a float32 fused launch the f16 side lacks the convolution's
+launch, so such a route is judged by the batch figures).  `conv route` forces K2HIP_F16_CONV for the run (1 fused f16, 2 gated f16 GEMM
++ conv, 3 as level 1).  "same_tokens" / "same_tokens2" count the utterances whose token lists are identical off and on.  One JSON line on
+stdout; there is no time gate (DESIGN.md "Half-precision operands in the encoder's linear layers" has the runs taken so far)."""
 import json
 import os
 import sys
@@ -21,49 +25,24 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT]
 
-from k2transducerasr_amd import Model  # noqa: E402
+from k2transducerasr_amd import Model, set_switch  # noqa: E402
 from k2transducerasr_amd.synth import synth_utterance, write_synthetic_model  # noqa: E402
 
 argv = sys.argv[1:]
 preset = argv[0] if len(argv) > 0 else "zipformer2-large-en"
 batch = int(argv[1]) if len(argv) > 1 else 32
 seconds = float(argv[2]) if len(argv) > 2 else 10.0
+route = int(argv[3]) if len(argv) > 3 else 0
+LEVELS = (0, 1, 2)
 ROUNDS, WARMUP = 9, 2
 F16_BIT = 1 << 21
 
 
-def main():
-    with tempfile.TemporaryDirectory() as d:
-        path = os.path.join(d, "m.k2w")
-        write_synthetic_model(path, preset)
-        model = Model(path, 0)
-        utts = [synth_utterance(u, seconds) for u in range(batch)]
-        total = {False: [], True: []}
-        enc = {False: [], True: []}
-        tokens = {}
-        for r in range(WARMUP + ROUNDS):
-            for half in (False, True):
-                model.set_encoder_precision(half)
-                tokens[half] = model.offline_greedy_from_samples(utts)
-                t = model.timing()
-                if r >= WARMUP:
-                    total[half].append(t["total_ms"])
-                    enc[half].append(t["encoder_ms"])
-        prof = {}
-        model.set_instrument(True)
-        for half in (False, True):
-            model.set_encoder_precision(half)
-            model.offline_greedy_from_samples(utts)
-            prof[half] = model.gemm_profile().copy()
-        model.set_instrument(False)
-        stats = model.encoder_f16_stats()
-        model.set_encoder_precision(False)
-        model.close()
-    off, on = prof[False], prof[True]
-    assert off.shape == on.shape and np.array_equal(off[:, :6], on[:, :6]), "the two launch logs do not line up"
+def shape_table(off, on, skip):
+    """the launches that are f16 in `on` and not in `skip`, grouped by shape: float32 (off) against f16 microseconds"""
     shapes = {}
-    for a, b in zip(off, on):
-        if not int(b[6]) & F16_BIT:
+    for a, b, c in zip(off, on, skip):
+        if not int(b[6]) & F16_BIT or (skip is not off and int(c[6]) & F16_BIT):
             continue
         key = tuple(int(v) for v in b[:3]) + (int(b[4]), int(b[5]))
         s = shapes.setdefault(key, dict(M=key[0], N=key[1], K=key[2], act=key[3], res=key[4], launches=0, f32_us=0.0, f16_us=0.0,
@@ -74,17 +53,59 @@ def main():
     rows = sorted(shapes.values(), key=lambda s: -s["f32_us"])
     for s in rows:
         s["f32_us"], s["f16_us"] = round(s["f32_us"], 1), round(s["f16_us"], 1)
+    return rows
+
+
+def main():
+    set_switch("K2HIP_F16_CONV", route)
+    with tempfile.TemporaryDirectory() as d:
+        path = os.path.join(d, "m.k2w")
+        write_synthetic_model(path, preset)
+        model = Model(path, 0)
+        utts = [synth_utterance(u, seconds) for u in range(batch)]
+        total = {v: [] for v in LEVELS}
+        enc = {v: [] for v in LEVELS}
+        tokens = {}
+        for r in range(WARMUP + ROUNDS):
+            for half in LEVELS:
+                model.set_encoder_precision(half)
+                tokens[half] = model.offline_greedy_from_samples(utts)
+                t = model.timing()
+                if r >= WARMUP:
+                    total[half].append(t["total_ms"])
+                    enc[half].append(t["encoder_ms"])
+        prof = {}
+        model.set_instrument(True)
+        stats = {}
+        for half in LEVELS:
+            model.set_encoder_precision(half)
+            model.offline_greedy_from_samples(utts)
+            prof[half] = model.gemm_profile().copy()
+            stats[half] = model.encoder_f16_stats()
+        model.set_instrument(False)
+        model.set_encoder_precision(False)
+        model.close()
+    off, on, on2 = prof[0], prof[1], prof[2]
+    for p in (on, on2):
+        assert off.shape == p.shape and np.array_equal(off[:, :6], p[:, :6]), "the launch logs do not line up"
+    rows, rows2 = shape_table(off, on, off), shape_table(off, on2, on)
     spread = lambda v: [round(float(np.min(v)), 3), round(float(np.max(v)), 3)]   # noqa: E731
     print(json.dumps(dict(
-        preset=preset, batch=batch, seconds=seconds, rounds=ROUNDS,
-        off_ms=round(float(np.median(total[False])), 3), off_spread=spread(total[False]),
-        on_ms=round(float(np.median(total[True])), 3), on_spread=spread(total[True]),
-        off_encoder_ms=round(float(np.median(enc[False])), 3), on_encoder_ms=round(float(np.median(enc[True])), 3),
+        preset=preset, batch=batch, seconds=seconds, rounds=ROUNDS, conv_route=route,
+        off_ms=round(float(np.median(total[0])), 3), off_spread=spread(total[0]),
+        on_ms=round(float(np.median(total[1])), 3), on_spread=spread(total[1]),
+        on2_ms=round(float(np.median(total[2])), 3), on2_spread=spread(total[2]),
+        off_encoder_ms=round(float(np.median(enc[0])), 3), on_encoder_ms=round(float(np.median(enc[1])), 3),
+        on2_encoder_ms=round(float(np.median(enc[2])), 3),
         gemm_f32_ms=round(float(off[:, 7].sum()) / 1e3, 3), gemm_on_ms=round(float(on[:, 7].sum()) / 1e3, 3),
+        gemm_on2_ms=round(float(on2[:, 7].sum()) / 1e3, 3),
         covered_launches=int(sum(s["launches"] for s in rows)),
         covered_f32_ms=round(sum(s["f32_us"] for s in rows) / 1e3, 3), covered_f16_ms=round(sum(s["f16_us"] for s in rows) / 1e3, 3),
-        panels=stats["panels"], panel_bytes=stats["panel_bytes"],
-        same_tokens=int(sum(a == b for a, b in zip(tokens[False], tokens[True]))), utterances=batch, shapes=rows)), flush=True)
+        covered2_launches=int(sum(s["launches"] for s in rows2)),
+        covered2_f32_ms=round(sum(s["f32_us"] for s in rows2) / 1e3, 3), covered2_f16_ms=round(sum(s["f16_us"] for s in rows2) / 1e3, 3),
+        panels=stats[1]["panels"], panel_bytes=stats[1]["panel_bytes"], panels2=stats[2]["panels"], panel_bytes2=stats[2]["panel_bytes"],
+        same_tokens=int(sum(a == b for a, b in zip(tokens[0], tokens[1]))),
+        same_tokens2=int(sum(a == b for a, b in zip(tokens[0], tokens[2]))), utterances=batch, shapes=rows, shapes2=rows2)), flush=True)
 
 
 if __name__ == "__main__":
