@@ -1203,7 +1203,7 @@ int32_t k2hip_set_rnn_lm_rescoring_precision(k2hip_model_t* model, int32_t half)
  * enters become infinite or NaN; a NaN stays a NaN.  Nothing is clamped or rescaled.
  * A MODEL THAT DOES NOT FIT: a covered weight that is not finite in f16 (|w| >= 65520, or not finite to begin with) refuses the switch
  * with K2HIP_ERR_INVALID, the message naming the tensor, before any device work; the model stays on float32.
- * LEVEL 2 (half == 2; every other non-zero value is level 1, whose launches, panels and bits are as described above): everything level 1
+ * LEVEL 2 (half == 2; every non-zero value other than 2 and 3 is level 1, whose launches, panels and bits are as described above): everything level 1
  * covers, plus, under the same K % 32 == 0 condition, the layer's remaining weight launches -- the stacked feed_forward1.in_proj /
  * attention-weights in_proj (SwooshL on the feed-forward columns only; the attention scores then read an f16-operand product), the
  * gated in_proj launches of NonlinAttention (x * tanh(s)) and of the conv modules (GLU), feed_forward2.out_proj with its in-place
@@ -1211,6 +1211,14 @@ int32_t k2hip_set_rnn_lm_rescoring_precision(k2hip_model_t* model, int32_t half)
  * float32 arithmetic on the float32 gated values, in the float32 kernel's order).  Level 2 builds more panels; a newly covered weight
  * that is not finite in f16 refuses it with K2HIP_ERR_INVALID, naming the checkpoint tensor, and the model stays at the level it had.
  * Going from 2 to 1 or 0 frees the panels level 2 added.
+ * LEVEL 3 (half == 3): everything level 2 covers, plus the matrix work of encoder_embed in front of the layers -- the third
+ * convolution (conv.7, an implicit GEMM whose 3 x 3 windows are gathered and rounded on their way into LDS), the ConvNeXt pointwise
+ * pair as ONE launch (pointwise_conv1 + SwooshL + pointwise_conv2 + residual; the hidden activations are rounded to f16 and kept
+ * on chip, the result is bit for bit that of two f16-operand launches with a float32 hidden tensor between them) and the output
+ * Linear where it is not a few columns over a long K (N <= 96 with K >= 256 stays float32).  conv.0, conv.4 and the 7 x 7
+ * depthwise convolution stay float32.  Four more panels; the same refusal, naming the checkpoint tensor, for a weight among them
+ * that is not finite in f16, and the model stays at the level it had.  The levels 0, 1 and 2 issue exactly the launches and give
+ * exactly the bits they gave before level 3 existed.
  * SCOPE: the streaming step (k2hip_online_*) never reads the switch.  Conformer, Zipformer v1, LSTM and streaming-export models:
  * K2HIP_ERR_UNSUPPORTED.  Turning the switch off frees the panels. */
 int32_t k2hip_set_encoder_precision(k2hip_model_t* model, int32_t half);

@@ -70,7 +70,13 @@ int32_t k2hip_debug_conv_fused_plan(int32_t B, int32_t T, int32_t D, int32_t K, 
  * k2hip_debug_gemm_f16_plan: fields = M, N, K, lda, ldc, glu, mul, byp_orig, w_kn, cv_Fout, nb0, nb1, res_div, skip_if_zero, cf_pool, dw_w
  *   (16 values; a pointer field as 0 / 1 = null / set).  *form = gemm_f16_form() of those GemmArgs; plan[3] = plan_gemm_f16()'s table
  *   index, BM, BN for them (force: a table index, -1 = the plan's choice), or -1s when the form is refused.  With 20 values -- those,
- *   then the level of the switch (1 / 2), glu_cols, dw_K, dw_T -- the predicate is asked at that level (tests/test_encoder_half_wide.py).
+ *   then the level of the switch (1 / 2 / 3), glu_cols, dw_K, dw_T -- the predicate is asked at that level (tests/test_encoder_half_wide.py).
+ *   With 24 values -- those, then seg_len, seg_stride, cv_C of a conv gather (cv_Fout > 0; asked as one frame per stream) and
+ *   pair_npix -- level 3's conv-gather form is asked too; pair_npix != 0 asks nothing of that and returns in *form the route of the
+ *   embed's ConvNeXt pointwise pair over that many pixels (convnext_f16_route: 1 the fused launch of csrc/convnext_f16.hip, 2 two
+ *   gemm_f16_mfma launches, 3 float32; the switch K2HIP_F16_CONVNEXT forces 1 / 2 / 3), plan = -1s (tests/test_encoder_half_embed.py).
+ *   k2hip_debug_op_run has the two level-3 launches alone: "gemm_f16_gather" and "convnext_f16" (csrc/engine.cpp lists their arguments).
+ *   GemmLaunchRec.kind of the fused pair's row: the f16 family's bit 21, a 128 x 128 tile and bit 22; its K is 128 + 384.
  * k2hip_debug_conv_f16_plan: the offline conv module under level 2 (csrc/gemm_plan.cpp) for B streams of T frames, D channels, K taps:
  *   *entry = glu_dwconv_f16_entry (the K2_F16_TABLE index of the fused f16 launch's tile, 1: 128 x 64, 2: 64 x 64; -1: none holds the
  *   stream), *route = glu_dwconv_f16_route (1 the fused f16 launch, 2 the gated f16 GEMM + dwconv1d_swoosh, 3 what level 1 does; the

@@ -3201,7 +3201,13 @@ int32_t k2hip_debug_conv_fused_plan(int32_t B, int32_t T, int32_t D, int32_t K, 
 int32_t k2hip_debug_gemm_f16_plan(const int64_t* f, int32_t n_fields, int32_t force, int32_t* form, int32_t* plan) {
     return guard([&] {
         NEED(f); NEED(form); NEED(plan);
-        K2_REQUIRE(n_fields == 16 || n_fields == 20, "debug_gemm_f16_plan: 16 or 20 fields, not %d", n_fields);
+        K2_REQUIRE(n_fields == 16 || n_fields == 20 || n_fields == 24, "debug_gemm_f16_plan: 16, 20 or 24 fields, not %d", n_fields);
+        if (n_fields == 24 && f[23] != 0) {   // the ConvNeXt pointwise pair's route over f[23] pixels, nothing else
+            tunables_init_from_env();
+            *form = convnext_f16_route(f[23]);
+            plan[0] = plan[1] = plan[2] = -1;
+            return;
+        }
         static const float dummy = 0.f;
         static const int idummy = 0;
         GemmArgs a;
@@ -3210,9 +3216,13 @@ int32_t k2hip_debug_gemm_f16_plan(const int64_t* f, int32_t n_fields, int32_t fo
         a.nb0 = (int)f[10]; a.nb1 = (int)f[11]; a.res_div = (int)f[12]; a.skip_if_zero = f[13] ? &idummy : nullptr;
         a.cf_pool = f[14] ? const_cast<float*>(&dummy) : nullptr; a.dw_w = f[15] ? &dummy : nullptr;
         int level = 1;
-        if (n_fields == 20) {   // the level of the switch, glu_cols, and the conv tail's taps and frames per stream
+        if (n_fields >= 20) {   // the level of the switch, glu_cols, and the conv tail's taps and frames per stream
             level = (int)f[16]; a.glu_cols = (int)f[17]; a.dw_K = (int)f[18]; a.dw_T = (int)f[19];
             a.byp_scale = a.byp_orig; a.dw_b = a.dw_w;
+        }
+        if (n_fields == 24) {   // the conv gather's segment length and stride and its channels; one frame per stream, windows of stride 1
+            a.seg_len = (int)f[20]; a.seg_stride = (int)f[21]; a.cv_C = (int)f[22];
+            a.cv_Tout = a.cv_Tin = 1; a.cv_Fin = a.cv_Fout;
         }
         *form = gemm_f16_form(a, level) ? 1 : 0;
         plan[0] = plan[1] = plan[2] = -1;

@@ -24,6 +24,14 @@ static const char* const kHalfNames2[] = {
     "feed_forward2.out_proj.weight",
 };
 
+// Level 3 adds encoder_embed's matrix work (Engine::encoder_embed): the third convolution as the engine's implicit GEMM reads it
+// ("#ohwi": [Co][kt][kf][ci]), the ConvNeXt pointwise pair (1 x 1 convolutions: [N, K, 1, 1] is the [N, K] matrix) and the output Linear
+// in NHWC flatten order ("#fc").  conv.4 (K = 72) and conv.0 have no f16 form.
+static const char* const kHalfEmbed3[] = {
+    "encoder_embed.conv.7.weight#ohwi", "encoder_embed.convnext.pointwise_conv1.weight", "encoder_embed.convnext.pointwise_conv2.weight",
+    "encoder_embed.out.weight#fc",
+};
+
 // The checkpoint tensor behind row `row` of a repacked weight, for the refusal's message.
 static std::string source_name(const Model& m, const std::string& prefix, const std::string& suffix, int row) {
     if (suffix == "#ff1_attn_in.weight") {
@@ -44,31 +52,39 @@ void encoder_half_pack(const Model& m, std::vector<uint16_t>* blob, std::vector<
     std::vector<std::string> suffixes;
     for (const char* suffix : kHalfSuffixes) suffixes.push_back(std::string(suffix) + ".weight");
     if (level >= 2) suffixes.insert(suffixes.end(), std::begin(kHalfNames2), std::end(kHalfNames2));
+    // one weight: N = its rows, K = everything behind them; `source(row)` names the checkpoint tensor of a row for the refusal
+    auto add = [&](const std::string& name, auto&& source) {
+        if (!m.has(name)) return;
+        const Tensor& t = m.tensor(name);
+        int64_t K = 1;
+        for (int d = 1; d < t.ndim; d++) K *= t.dims[d];
+        const bool matrix = t.ndim == 2 || (t.ndim == 4 && t.dims[2] == 1 && t.dims[3] == 1);
+        if (!matrix || K % 32 != 0 || K < 32 || !t.host) return;   // other K stay on float32
+        EncoderHalfEntry e;
+        e.name = name;
+        e.dev = t.dev;
+        e.N = (int)t.dims[0];
+        e.K = (int)K;
+        e.off = (int64_t)blob->size();
+        blob->resize(blob->size() + (size_t)gemm_f16_panel_halves(e.N, e.K));
+        if (!gemm_f16_pack(t.host, e.N, e.K, blob->data() + e.off)) {
+            int row = 0;   // the first row with such a weight: which checkpoint tensor a repacked row came from
+            std::vector<uint16_t> one((size_t)gemm_f16_panel_halves(1, e.K));
+            while (row < e.N - 1 && gemm_f16_pack(t.host + (size_t)row * e.K, 1, e.K, one.data())) row++;
+            failf(K2HIP_ERR_INVALID, "set_encoder_precision: %s has a weight that is not finite in half precision; the model stays as it was",
+                  source(row).c_str());
+        }
+        entries->push_back(std::move(e));
+    };
     for (int si = 0; si < cf.ns; si++)
         for (int li = 0; li < cf.nlayer[si]; li++)
             for (const std::string& suffix : suffixes) {
                 char prefix[96];
                 snprintf(prefix, sizeof prefix, "encoder.encoders.%d.layers.%d.", si, li);
-                const std::string name = prefix + suffix;
-                if (!m.has(name)) continue;
-                const Tensor& t = m.tensor(name);
-                if (t.ndim != 2 || t.dims[1] % 32 != 0 || t.dims[1] < 32 || !t.host) continue;   // other K stay on float32
-                EncoderHalfEntry e;
-                e.name = name;
-                e.dev = t.dev;
-                e.N = (int)t.dims[0];
-                e.K = (int)t.dims[1];
-                e.off = (int64_t)blob->size();
-                blob->resize(blob->size() + (size_t)gemm_f16_panel_halves(e.N, e.K));
-                if (!gemm_f16_pack(t.host, e.N, e.K, blob->data() + e.off)) {
-                    int row = 0;   // the first row with such a weight: which checkpoint tensor a repacked row came from
-                    std::vector<uint16_t> one((size_t)gemm_f16_panel_halves(1, e.K));
-                    while (row < e.N - 1 && gemm_f16_pack(t.host + (size_t)row * e.K, 1, e.K, one.data())) row++;
-                    failf(K2HIP_ERR_INVALID, "set_encoder_precision: %s has a weight that is not finite in half precision; the model stays as it was",
-                          source_name(m, prefix, suffix, row).c_str());
-                }
-                entries->push_back(std::move(e));
+                add(prefix + suffix, [&](int row) { return source_name(m, prefix, suffix, row); });
             }
+    if (level >= 3)
+        for (const std::string name : kHalfEmbed3) add(name, [&](int) { return name.substr(0, name.find('#')); });
 }
 
 }  // namespace k2hip

@@ -305,11 +305,30 @@ float* Engine::encoder_embed(const Ctx& c, const float* x, int B, int T, int* T5
     float* dw = ar.take<float>((int64_t)npix * 128);
     dwconv7x7(c, a3, m.w("encoder_embed.convnext.depthwise_conv.weight#kc"), m.w("encoder_embed.convnext.depthwise_conv.bias"),
               dw, B, T3, T3, 3, F3, 128);
-    float* hid = ar.take<float>((int64_t)npix * 384);
-    linear(c, dw, 128, m.w("encoder_embed.convnext.pointwise_conv1.weight"), m.w("encoder_embed.convnext.pointwise_conv1.bias"),
-           hid, 384, npix, 128, 384, ACT_SWOOSH_L);
-    linear(c, hid, 384, m.w("encoder_embed.convnext.pointwise_conv2.weight"), m.w("encoder_embed.convnext.pointwise_conv2.bias"),
-           a3, 128, npix, 384, 128, ACT_NONE, a3, 128);
+    float* hid = ar.take<float>((int64_t)npix * 384);   // (taken on every route: the arena's size does not depend on the switch)
+    const float *w1 = m.w("encoder_embed.convnext.pointwise_conv1.weight"), *w2 = m.w("encoder_embed.convnext.pointwise_conv2.weight");
+    // Level 3 of the half-precision switch (c.f16 is set for this call at that level only) and both panels resident: the pair as ONE
+    // launch that keeps the f16 hidden values in LDS (route 1), as two gemm_f16_mfma launches (2: linear() finds the panels) or in
+    // float32 (3)
+    int route = 0;
+    if (c.f16) {
+        const auto p1 = c.f16->by_weight.find(w1), p2 = c.f16->by_weight.end() == p1 ? p1 : c.f16->by_weight.find(w2);
+        const bool have = p2 != c.f16->by_weight.end() && p1->second.N == 384 && p1->second.K == 128 && p2->second.N == 128 && p2->second.K == 384;
+        route = have ? convnext_f16_route(npix) : 3;
+        if (route == 1) {
+            ConvnextF16Args f;
+            f.X = dw; f.ldx = 128; f.p1 = p1->second.panels; f.p2 = p2->second.panels;
+            f.b1 = m.w("encoder_embed.convnext.pointwise_conv1.bias"); f.b2 = m.w("encoder_embed.convnext.pointwise_conv2.bias");
+            f.R = a3; f.ldr = 128; f.C = a3; f.ldc = 128; f.M = npix;
+            convnext_f16(c, f);
+        }
+    }
+    if (route != 1) {
+        Ctx cp = c;
+        if (route == 3) cp.f16 = nullptr;
+        linear(cp, dw, 128, w1, m.w("encoder_embed.convnext.pointwise_conv1.bias"), hid, 384, npix, 128, 384, ACT_SWOOSH_L);
+        linear(cp, hid, 384, w2, m.w("encoder_embed.convnext.pointwise_conv2.bias"), a3, 128, npix, 384, 128, ACT_NONE, a3, 128);
+    }
     // (b,t,f,c) flatten == [B*T3, F3*128] with the repacked out.weight
     float* lin = ar.take<float>((int64_t)B * T3 * D0);
     linear(c, a3, F3 * 128, m.w("encoder_embed.out.weight#fc"), m.w("encoder_embed.out.bias"), lin, D0, B * T3, F3 * 128, D0);
@@ -662,7 +681,9 @@ float* Engine::encoder_forward(const Ctx& c, const float* x, int B, int T, int* 
     K2_REQUIRE(T50_pre > 0, "encoder: %d input frames are too few", T);
     int Tpp = (T50_pre + 1) / 2;
     float* enc_out = ar.take<float>((int64_t)B * Tpp * cf.enc_dim());
-    float* x0 = encoder_embed(c, x, B, T, &T50);
+    Ctx cs = c;   // the stacks' launches read the half-precision panels while the switch is on (k2hip_set_encoder_precision)
+    cs.f16 = enc_f16_dev_ ? &enc_f16_ : nullptr;
+    float* x0 = encoder_embed(cs.f16 && cs.f16->level >= 3 ? cs : c, x, B, T, &T50);   // level 3: the embed's launches too
     if (tap_rows) *tap_rows = B * T50;
     if (tap == 0) {
         *tap_ptr = x0;
@@ -670,8 +691,6 @@ float* Engine::encoder_forward(const Ctx& c, const float* x, int B, int T, int* 
         return nullptr;
     }
     FullDimSegs segs;
-    Ctx cs = c;   // the stacks' launches read the half-precision panels while the switch is on (k2hip_set_encoder_precision)
-    cs.f16 = enc_f16_dev_ ? &enc_f16_ : nullptr;
     if (encoder_stacks(cs, x0, B, T50, nullptr, tap, tap_ptr, tap_dim, &segs)) return nullptr;
     *Tp = Tpp;
     return encoder_head(c, segs, B, T50, enc_out);
@@ -2422,6 +2441,64 @@ void Engine::debug_op_host(const char* op, const int64_t* iargs, int n_iargs, vo
             K2_HIP(copy_blocking(plan_out, rep, sizeof rep, hipMemcpyHostToDevice));
             gemm_f16_launch(c, g, reinterpret_cast<const uint16_t*>(pp), pl);
             K2_HIP(hipGetLastError());
+        } else if (name == "gemm_f16_gather") {
+            // ONE launch of gemm_f16_mfma's conv-gather form (level 3): ints M, N, K, ldc, act, cfg, then cv_Fout, cv_Tout, cv_Tin, cv_Fin,
+            // cv_C, cv_st, cv_sf, seg_len, seg_stride; bufs the NHWC input, W (float32 [N, K], packed here from the host copy), bias, C,
+            // the plan (index, BM, BN)
+            GemmArgs g;
+            g.M = I(); g.N = I(); g.K = I(); g.ldc = I(); g.act = I();
+            const int cfg = I();
+            g.cv_Fout = I(); g.cv_Tout = I(); g.cv_Tin = I(); g.cv_Fin = I(); g.cv_C = I(); g.cv_st = I(); g.cv_sf = I();
+            g.seg_len = I(); g.seg_stride = I();
+            const int a_k = nbuf, w_k = nbuf + 1;
+            float *A = P(), *W = P(), *bias = P(), *C = P();
+            int* plan_out = reinterpret_cast<int*>(P());
+            K2_REQUIRE(A && W && C && plan_out && buf_bytes[n_bufs - 1] >= 12, "debug_op_run gemm_f16_gather: A, W, C and a plan buffer of 3 ints are needed");
+            g.A = A; g.W = W; g.ldw = g.K; g.bias = bias; g.C = C;
+            K2_REQUIRE(g.cv_Fout > 0 && gemm_f16_fits(g, 3), "gemm_f16_gather: not a conv gather the half-precision kernel takes");
+            K2_REQUIRE(buf_bytes[w_k] == (int64_t)sizeof(float) * g.N * g.K, "debug_op_run gemm_f16_gather: W must be a float32 [N, K] matrix (N %d, K %d)", g.N, g.K);
+            {   // the last float the last row's last segment reads lies inside the input
+                const long long r = g.M - 1, f = r % g.cv_Fout, bt = r / g.cv_Fout, t = bt % g.cv_Tout, b = bt / g.cv_Tout;
+                const long long last = ((b * g.cv_Tin + t * g.cv_st) * g.cv_Fin + f * g.cv_sf) * g.cv_C + (long long)(g.K / g.seg_len - 1) * g.seg_stride + g.seg_len;
+                K2_REQUIRE(g.K % g.seg_len == 0 && last * 4 <= buf_bytes[a_k], "debug_op_run gemm_f16_gather: the gather reads %lld floats, the input has %lld bytes",
+                           last, (long long)buf_bytes[a_k]);
+            }
+            std::vector<uint16_t> panels((size_t)gemm_f16_panel_halves(g.N, g.K));
+            if (!gemm_f16_pack(static_cast<const float*>(bufs[w_k]), g.N, g.K, panels.data()))
+                failf(K2HIP_ERR_INVALID, "debug_op_run gemm_f16_gather: W has a weight that is not finite in half precision");
+            char* pp = nullptr;
+            K2_HIP(hipMalloc(&pp, panels.size() * sizeof(uint16_t)));
+            d.base.push_back(pp);
+            K2_HIP(copy_blocking(pp, panels.data(), panels.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+            const GemmF16Plan pl = plan_gemm_f16(g, cfg);
+            const int rep[3] = {pl.idx, pl.BM, pl.BN};
+            K2_HIP(copy_blocking(plan_out, rep, sizeof rep, hipMemcpyHostToDevice));
+            gemm_f16_launch(c, g, reinterpret_cast<const uint16_t*>(pp), pl);
+            K2_HIP(hipGetLastError());
+        } else if (name == "convnext_f16") {
+            // ONE launch of the fused ConvNeXt pointwise pair (convnext_f16.hip): ints M, ldx, ldc; bufs X [M, ldx], W1 (float32 [384, 128]),
+            // b1, W2 (float32 [128, 384]), b2, C [M, ldc] (the residual, updated in place).  Both weights are packed here from the host copies.
+            ConvnextF16Args f;
+            f.M = I(); f.ldx = I(); f.ldc = I();
+            const int x_k = nbuf, w1_k = nbuf + 1, w2_k = nbuf + 3, c_k = nbuf + 5;
+            float *X = P(), *W1 = P(), *b1 = P(), *W2 = P(), *b2 = P(), *C = P();
+            K2_REQUIRE(X && W1 && b1 && W2 && b2 && C && f.M >= 1 && f.ldx >= kConvnextC && f.ldc >= kConvnextC, "debug_op_run convnext_f16: X, W1, b1, W2, b2 and C are needed");
+            const int64_t wb = (int64_t)sizeof(float) * kConvnextC * kConvnextH;
+            K2_REQUIRE(buf_bytes[w1_k] == wb && buf_bytes[w2_k] == wb && buf_bytes[w1_k + 1] >= 4 * kConvnextH && buf_bytes[w2_k + 1] >= 4 * kConvnextC &&
+                           buf_bytes[x_k] >= 4ll * ((int64_t)(f.M - 1) * f.ldx + kConvnextC) && buf_bytes[c_k] >= 4ll * ((int64_t)(f.M - 1) * f.ldc + kConvnextC),
+                       "debug_op_run convnext_f16: W1 [384, 128], W2 [128, 384], b1 [384], b2 [128], X and C of %d rows", f.M);
+            const size_t half = (size_t)gemm_f16_panel_halves(kConvnextH, kConvnextC);   // (= that of [128, 384])
+            std::vector<uint16_t> panels(2 * half);
+            if (!gemm_f16_pack(static_cast<const float*>(bufs[w1_k]), kConvnextH, kConvnextC, panels.data()) ||
+                !gemm_f16_pack(static_cast<const float*>(bufs[w2_k]), kConvnextC, kConvnextH, panels.data() + half))
+                failf(K2HIP_ERR_INVALID, "debug_op_run convnext_f16: a weight is not finite in half precision");
+            char* pp = nullptr;
+            K2_HIP(hipMalloc(&pp, panels.size() * sizeof(uint16_t)));
+            d.base.push_back(pp);
+            K2_HIP(copy_blocking(pp, panels.data(), panels.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+            f.X = X; f.b1 = b1; f.b2 = b2; f.R = C; f.C = C; f.ldr = f.ldc;
+            f.p1 = reinterpret_cast<const uint16_t*>(pp); f.p2 = f.p1 + half;
+            convnext_f16(c, f);
         } else if (name == "gemm_glu_causal_conv") {
             float *x = P(), *wg = P(), *bg = P(), *pool = P();
             const long long ss = L(), off = L();

@@ -50,7 +50,8 @@ struct EncoderHalfEntry {
 // The panels of every 2-D encoder.* weight with K % 32 == 0 that the offline Zipformer2 layer body hands to linear(), back to back in
 // *blob, from the model's host views.  Host only.  Throws K2HIP_ERR_UNSUPPORTED for a model that is not an offline Zipformer2 and
 // K2HIP_ERR_INVALID, naming the tensor, for a weight that is not finite in f16.  level 2: also the stacked "#ff1_attn_in", the "#glu"
-// in_proj repacks and feed_forward2.out_proj (a refusal names the checkpoint tensor the offending row came from).
+// in_proj repacks and feed_forward2.out_proj (a refusal names the checkpoint tensor the offending row came from).  level 3: also
+// encoder_embed's conv.7 ("#ohwi"), ConvNeXt pointwise_conv1 / 2 and out ("#fc"), refused under the checkpoint tensor's name.
 void encoder_half_pack(const Model& m, std::vector<uint16_t>* blob, std::vector<EncoderHalfEntry>* entries, int level = 1);
 
 class Engine {
@@ -395,8 +396,8 @@ class Engine {
     // The level turned on is the one set_encoder_level asked for last (1 until then).  A change between the levels 1 and 2 packs the
     // new level's panels first: a refusal leaves the engine at the level it had.
     void set_encoder_precision(bool half);
-    void set_encoder_level(int level) {   // 0 = off, 2 = level 2, any other value = level 1
-        enc_f16_want_ = level == 2 ? 2 : 1;
+    void set_encoder_level(int level) {   // 0 = off, 2 = level 2, 3 = level 3 (encoder_embed too), any other value = level 1
+        enc_f16_want_ = level == 2 || level == 3 ? level : 1;
         set_encoder_precision(level != 0);
     }
     bool encoder_half() const { return enc_f16_dev_ != nullptr; }

@@ -34,6 +34,12 @@
 // act, act_cols, res (in place too), act_after_res and, at level 2 of the switch, glu / glu_cols and the bypass mix.  Everything else
 // stays on the float32 kernels (gemm_plan.cpp gemm_f16_form).
 //
+// GATHER (level 3; every tile): the conv-gather form of gemm.hip's MODE_CONV -- A is an NHWC tensor, row r's window starts at the
+// base GemmArgs cv_* name and k sits at (k / seg_len) seg_stride + k % seg_len.  Only the ADDRESS of a thread's run of 16 consecutive
+// floats changes (seg_len % 16 == 0: a run never straddles a segment; cv_C, seg_stride % 4 == 0: its float4 loads stay aligned): the
+// row base once, the segment of the run's k stage by stage.  Everything behind the LDS store is the loop and the epilogue below.
+// encoder_embed.conv.7: K = 288 = three segments of 96, nine chunks (a half-stage tail).
+//
 // DWK > 0 (15 or 31; BN = 64 only): the offline conv module's form at level 2 -- in_proj + GLU + depthwise Conv1d over time + bias +
 // SwooshR in one launch, the f16 counterpart of gemm_f32_mfma_pipe<..., DWK>.  One M tile per STREAM: the tile of stream b starts at row
 // b dw_T (dw_T <= BM; rows >= dw_T of the tile are staged like any rows -- clamped to M - 1 -- and never used).  A workgroup owns the 32
@@ -64,7 +70,7 @@ __device__ __forceinline__ f16x8 round8(const float4& lo, const float4& hi) {   
     return f16x8{(_Float16)lo.x, (_Float16)lo.y, (_Float16)lo.z, (_Float16)lo.w, (_Float16)hi.x, (_Float16)hi.y, (_Float16)hi.z, (_Float16)hi.w};
 }
 
-template <int BM, int BN, int DWK = 0>
+template <int BM, int BN, int DWK = 0, bool GATHER = false>
 __global__ __launch_bounds__(256) void gemm_f16_mfma(GemmArgs g, const uint16_t* __restrict__ panels) {
     constexpr int MT = BM / 64, NT = BN / 64;        // 32 x 32 accumulator tiles of a wave
     constexpr int NU = BM / 64;                      // A runs of 16 floats per thread and stage
@@ -73,6 +79,7 @@ __global__ __launch_bounds__(256) void gemm_f16_mfma(GemmArgs g, const uint16_t*
     static_assert(BM % 64 == 0 && BN % 64 == 0, "f16 gemm: four waves of whole 32 x 32 tiles");
     constexpr int DW_CH = 32, DW_FT = BM / 8, DW_HALF = DWK / 2, DW_XS = (BM + DWK - 1) * DW_CH;   // the conv tail's LDS image, in floats
     constexpr int DW_NTAP = (DWK * DW_CH + 255) / 256;                                            // tap elements a thread stages
+    static_assert(!GATHER || DWK == 0, "f16 gemm: the conv-gather form has the plain epilogue");
     static_assert(DWK == 0 || (BN == 64 && DWK % 2 == 1 && (DW_XS + DWK * DW_CH) * 4 <= 2 * STAGE * 2), "f16 gemm: conv tail's tile form");
     extern __shared__ __attribute__((aligned(16))) _Float16 smem_h[];   // [2][STAGE]: the A image, then the W image
 
@@ -90,10 +97,15 @@ __global__ __launch_bounds__(256) void gemm_f16_mfma(GemmArgs g, const uint16_t*
     const float* ap[NU];
     int a_dst[NU];      // halves from the stage's start, instruction j = 0 (j = 1: + 2 * 32 * 8)
     int a_q[NU];
+    const int a_k0 = 16 * (tid & 3);   // GATHER: k of this thread's runs in stage 0 (seg = tid & 3 for every i)
 #pragma unroll
     for (int i = 0; i < NU; i++) {
         const int u = tid + 256 * i, row = u >> 2, seg = u & 3, q = seg >> 1, hh = seg & 1;
-        ap[i] = g.A + (long long)min(m0 + row, g.M - 1) * g.lda + 32 * q + 16 * hh;
+        if constexpr (GATHER) {   // the row's window in the NHWC input (kernels.h GemmArgs cv_*); the k offset is added stage by stage
+            const int r = min(m0 + row, g.M - 1), f = r % g.cv_Fout, bt = r / g.cv_Fout, t = bt % g.cv_Tout, b = bt / g.cv_Tout;
+            ap[i] = g.A + (((long long)b * g.cv_Tin + (long long)t * g.cv_st) * g.cv_Fin + (long long)f * g.cv_sf) * g.cv_C;
+        } else
+            ap[i] = g.A + (long long)min(m0 + row, g.M - 1) * g.lda + 32 * q + 16 * hh;
         a_dst[i] = ((((row >> 5) * 2 + q) * 4 + hh) * 32 + (((row & 31) + 4 * seg) & 31)) * 8;
         a_q[i] = q;
     }
@@ -107,10 +119,13 @@ __global__ __launch_bounds__(256) void gemm_f16_mfma(GemmArgs g, const uint16_t*
     f16x8 wraw[NWL];
     auto load_stage = [&](int s) {
         const int left = nk - 2 * s;   // chunks of stage s: 1 or >= 2
+        // GATHER: k -> (k / seg_len) seg_stride + k % seg_len; seg_len % 16 == 0, so the run of 16 stays inside its segment
+        const int gk = a_k0 + 64 * s, gseg = GATHER ? gk / g.seg_len : 0;
+        const long long koff = GATHER ? (long long)gseg * g.seg_stride + (gk - gseg * g.seg_len) : 64 * s;
 #pragma unroll
         for (int i = 0; i < NU; i++) {
             if (a_q[i] < left) {
-                const float4* p = reinterpret_cast<const float4*>(ap[i] + 64 * s);
+                const float4* p = reinterpret_cast<const float4*>(ap[i] + koff);
 #pragma unroll
                 for (int v = 0; v < 4; v++) araw[i][v] = p[v];
             } else {
@@ -257,13 +272,13 @@ __global__ __launch_bounds__(256) void gemm_f16_mfma(GemmArgs g, const uint16_t*
         }
 }
 
-template <int BM, int BN>
+template <int BM, int BN, bool GATHER = false>
 void launch_f16(const Ctx& ctx, const GemmArgs& a, const uint16_t* panels) {
     dim3 grid(cdiv(a.N, BN), cdiv(a.M, BM), 1);
     const size_t lds = sizeof(uint16_t) * 2 * (BM + BN) * 64;
     static LdsAttrOnce lds_attr;
-    lds_attr.ensure(gemm_f16_mfma<BM, BN>, (int)lds);
-    hipLaunchKernelGGL((gemm_f16_mfma<BM, BN>), grid, dim3(256), lds, ctx.stream, a, panels);
+    lds_attr.ensure(gemm_f16_mfma<BM, BN, 0, GATHER>, (int)lds);
+    hipLaunchKernelGGL((gemm_f16_mfma<BM, BN, 0, GATHER>), grid, dim3(256), lds, ctx.stream, a, panels);
 }
 
 // the conv-tail form: one M tile per stream
@@ -281,7 +296,17 @@ void launch_f16_dwconv(const Ctx& ctx, const GemmArgs& a, const uint16_t* panels
 }  // namespace
 
 void gemm_f16_launch(const Ctx& ctx, const GemmArgs& a, const uint16_t* panels, const GemmF16Plan& p) {
-    K2_REQUIRE(panels && gemm_f16_fits(a, 2), "gemm_f16: %d x %d x %d (lda %d) is not a form the half-precision kernel takes", a.M, a.N, a.K, a.lda);
+    K2_REQUIRE(panels && gemm_f16_fits(a, 3), "gemm_f16: %d x %d x %d (lda %d) is not a form the half-precision kernel takes", a.M, a.N, a.K, a.lda);
+    if (a.cv_Fout > 0) {
+        K2_REQUIRE(gemm_f16_fits(a, 3), "gemm_f16: not a conv gather the half-precision kernel takes (seg_len %d, seg_stride %d, C %d)", a.seg_len, a.seg_stride, a.cv_C);
+        switch (p.idx) {
+#define X(i, bm, bn) case i: launch_f16<bm, bn, true>(ctx, a, panels); break;
+            K2_F16_TABLE(X)
+#undef X
+            default: failf(K2HIP_ERR_INVALID, "gemm_f16: no tile %d", p.idx);
+        }
+        return;
+    }
     if (a.dw_w) {
         K2_REQUIRE((p.idx == 1 || p.idx == 2) && a.dw_T <= p.BM, "gemm_f16: tile %d does not hold a stream of %d frames", p.idx, a.dw_T);
         if (p.idx == 1) a.dw_K == 15 ? launch_f16_dwconv<128, 15>(ctx, a, panels) : launch_f16_dwconv<128, 31>(ctx, a, panels);

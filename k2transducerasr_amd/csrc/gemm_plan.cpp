@@ -231,8 +231,19 @@ int gemm_kind(const GemmArgs& a, const GemmPlan& p) {
 
 // ---- the half-precision-operand GEMM (gemm_f16.hip) ----------------------------------------------------------------------------
 bool gemm_f16_fits(const GemmArgs& a, int level) {
-    if (a.M < 1 || a.N < 1 || a.K < 32 || a.K % 32 != 0 || a.lda % 4 != 0 || a.lda < a.K) return false;
-    if (a.mul || a.w_kn || a.cv_Fout > 0 || a.nb0 * a.nb1 != 1 || a.res_div != 1 || a.skip_if_zero || a.cf_pool) return false;
+    if (a.M < 1 || a.N < 1 || a.K < 32 || a.K % 32 != 0) return false;
+    if (a.mul || a.w_kn || a.nb0 * a.nb1 != 1 || a.res_div != 1 || a.skip_if_zero || a.cf_pool) return false;
+    if (a.cv_Fout > 0) {
+        // Level 3: the conv-gather form.  A thread's run of 16 consecutive k is 16 consecutive floats of the NHWC input: it must not
+        // straddle a segment (seg_len % 16 == 0) and its float4 loads must be aligned (cv_C, seg_stride % 4 == 0).  Whole streams; the
+        // plain epilogue only.
+        if (level < 3 || a.glu || a.byp_orig || a.dw_w) return false;
+        if (a.seg_len < 16 || a.seg_len % 16 != 0 || a.seg_stride < 4 || a.seg_stride % 4 != 0 || a.cv_C < 4 || a.cv_C % 4 != 0) return false;
+        if (a.cv_Tout < 1 || a.cv_Tin < 1 || a.cv_Fin < 1 || a.cv_st < 1 || a.cv_sf < 1 || a.M % (a.cv_Fout * a.cv_Tout) != 0) return false;
+        const long long in = (long long)(a.M / (a.cv_Fout * a.cv_Tout)) * a.cv_Tin * a.cv_Fin * a.cv_C;
+        return in < (1ll << 29) && (long long)a.M * a.ldc < (1ll << 29);
+    }
+    if (a.lda % 4 != 0 || a.lda < a.K) return false;
     if (level < 2 && (a.glu || a.byp_orig || a.dw_w)) return false;
     if (a.glu) {   // the gated epilogue as gemm() takes it: whole (value | gate) blocks of 32 columns and no other epilogue term
         const int gc = a.glu_cols > 0 ? a.glu_cols : a.N;
@@ -276,6 +287,7 @@ GemmF16Plan plan_gemm_f16(const GemmArgs& a, int force) {
 }
 
 int gemm_kind_f16(const GemmF16Plan& p) { return 128 + 256 * (p.BM / 32) + 4096 * (p.BN / 32) + (1 << 21); }
+int gemm_kind_convnext_f16() { return 128 + 256 * 4 + 4096 * 4 + (1 << 21) + (1 << 22); }
 
 int glu_conv_ring_entry(int B, int Tc, int D, int K) {
     const int M = B * Tc, N = 2 * D;
@@ -319,6 +331,14 @@ int glu_dwconv_f16_entry(int B, int T, int D, int K) {
     if (B < 1 || T < 1 || T > 128 || D < 32 || D % 32 != 0 || (K != 15 && K != 31)) return -1;
     if ((long long)B * T * D >= (1ll << 29)) return -1;
     return T <= 64 ? 2 : 1;
+}
+
+// The embed's ConvNeXt pointwise pair under level 3, npix pixels of 128 channels (hidden 384).
+int convnext_f16_route(long long npix) {
+    const int forced = tunables().f16_convnext;
+    if (forced >= 1 && forced <= 3) return forced;
+    if (npix < 1 || npix * 384 >= (1ll << 29)) return 3;   // (the launches' 32-bit lane offsets)
+    return 1;
 }
 
 int glu_dwconv_f16_route(int B, int T, int D, int K) {

@@ -34,7 +34,9 @@ struct Tunables {
     int f16_conv = 0;             // K2HIP_F16_CONV: the offline conv modules' in_proj + conv at level 2 of the encoder's half-precision switch: 0 = by
                                   // glu_dwconv_f16_route's rule, 1 = the fused f16 launch wherever it has a tile, 2 = the gated f16 GEMM + dwconv1d_swoosh,
                                   // 3 = as at level 1 (tools/encoder_half_bench.py compares the routes with it)
-    int dw1d_tt = 0;              // K2HIP_DW1D_TT: outputs per thread of the depthwise Conv1d (8 / 4 / 2; 0 = by grid size; tests/test_kernels_gpu.py forces each)
+    int f16_convnext = 0;         // K2HIP_F16_CONVNEXT: the embed's ConvNeXt pointwise pair at level 3 of that switch: 0 = by convnext_f16_route's rule,
+                                  // 1 = the fused launch (convnext_f16.hip), 2 = two gemm_f16_mfma launches, 3 = float32 as at level 2
+    int dw1d_tt = 0;             // K2HIP_DW1D_TT: outputs per thread of the depthwise Conv1d (8 / 4 / 2; 0 = by grid size; tests/test_kernels_gpu.py forces each)
     int lstm_seq = 0;             // K2HIP_LSTM_SEQ: layer-by-layer LSTM instead of the layer wavefront
     int greedy_one_part = 0;      // K2HIP_GREEDY_ONE_PART: one workgroup per stream in the search
     int greedy_parts = 0;         // K2HIP_GREEDY_PARTS: vocabulary slabs per stream (0 = automatic)
@@ -86,8 +88,8 @@ struct GemmF16Panel {
 };
 struct GemmF16Map {
     std::unordered_map<const float*, GemmF16Panel> by_weight;
-    int level = 1;                  // 2: the gated, stacked, bypass and conv-tail launches too (gemm_f16_fits)
-    mutable int64_t launches = 0;   // gemm_f16_mfma launches since the map was built
+    int level = 1;                  // 2: the gated, stacked, bypass and conv-tail launches too (gemm_f16_fits); 3: encoder_embed's too
+    mutable int64_t launches = 0;   // gemm_f16_mfma (and convnext_f16) launches since the map was built
 };
 
 struct GreedyLaunch;
@@ -288,7 +290,9 @@ struct GemmF16Plan {
 // what the kernel can compute: one plain [M, K] x [N, K] problem with K % 32 == 0 and lda % 4 == 0; bias, act, act_cols, res (in
 // place too) and act_after_res in the epilogue; nothing else (gemm_plan.cpp).  level 2 (k2hip_set_encoder_precision's second level)
 // adds the gated epilogue (glu 1 / 2 over whole blocks of 32 columns, nothing else beside it), the bypass mix, and the conv tail
-// (dw_w: glu = 1, dw_K 15 / 31, whole streams of dw_T <= 128 frames, N % 64 == 0, no other epilogue term).
+// (dw_w: glu = 1, dw_K 15 / 31, whole streams of dw_T <= 128 frames, N % 64 == 0, no other epilogue term).  level 3 adds the conv
+// gather (cv_Fout > 0) with seg_len % 16 == 0 -- a thread's run of 16 consecutive k never straddles a segment --, seg_stride and cv_C
+// multiples of 4 and the plain epilogue.
 bool gemm_f16_fits(const GemmArgs& a, int level = 1);
 // what gemm() sends to it: a call that fits, less the shapes that measured slower than the float32 kernels (few columns over a long K)
 bool gemm_f16_form(const GemmArgs& a, int level = 1);
@@ -301,9 +305,32 @@ int glu_dwconv_f16_route(int B, int T, int D, int K);
 // the tile of a covered launch: forced (a table index) or, force < 0, by workgroup count against the 256 CUs; throws for a bad index
 GemmF16Plan plan_gemm_f16(const GemmArgs& a, int force = -1);
 int gemm_kind_f16(const GemmF16Plan& p);   // GemmLaunchRec.kind of such a launch: bit 21 + the tile in the pipelined kernels' bits
-// ONE launch of table entry p.idx; a.W is not read.  The caller has checked gemm_f16_fits(a, 2) and that the panels are those of a [a.N, a.K]
+// ONE launch of table entry p.idx; a.W is not read.  The caller has checked gemm_f16_fits(a, 3) and that the panels are those of a [a.N, a.K]
 // matrix.  a.dw_w: the conv-tail form, p.idx 1 or 2 with a.dw_T <= p.BM.
 void gemm_f16_launch(const Ctx& ctx, const GemmArgs& a, const uint16_t* panels, const GemmF16Plan& p);
+
+// ---- level 3: the embed's ConvNeXt pointwise pair as ONE launch (convnext_f16.hip) -----------------------------------------------
+//   C[m, :] = R[m, :] + W2 . f16(SwooshL(W1 . f16(X[m, :]) + b1)) + b2      X [M, 128], hidden 384, C / R [M, 128] (R == C: in place)
+// both products on v_mfma_f32_32x32x16_f16 with float32 sums, k in ascending chunks of 32 in the panels' k order: bit for bit the
+// gemm_f16_mfma launch of W1 with SwooshL into a float32 hidden tensor followed by the launch of W2 that reads it, whatever their tiles.
+// The f16 hidden values live in LDS only.  p1 / p2: the panels (gemm_f16_layout.h) of W1 [384, 128] and W2 [128, 384].
+constexpr int kConvnextC = 128, kConvnextH = 384;
+struct ConvnextF16Args {
+    const float* X = nullptr;
+    const uint16_t* p1 = nullptr;
+    const uint16_t* p2 = nullptr;
+    const float* b1 = nullptr;
+    const float* b2 = nullptr;
+    const float* R = nullptr;
+    float* C = nullptr;
+    int M = 0, ldx = 0, ldr = 0, ldc = 0;
+};
+// How a level-3 pass runs the pair over npix pixels: 1 = the fused launch, 2 = the two gemm_f16_mfma launches, 3 = float32 as at level 2
+// (gemm_plan.cpp; K2HIP_F16_CONVNEXT forces one)
+int convnext_f16_route(long long npix);
+int gemm_kind_convnext_f16();   // GemmLaunchRec.kind of the fused launch: gemm_kind_f16 of a 128 x 128 tile + bit 22
+// ONE launch, tallied as the two GEMMs it replaces less one launch; counts in ctx.f16->launches when the Ctx carries a map
+void convnext_f16(const Ctx& ctx, const ConvnextF16Args& a);
 
 // convenience: plain Linear  C = act(A W^T + b) (+res)
 void linear(const Ctx& ctx, const float* A, int lda, const float* W, const float* bias, float* C, int ldc, int M, int K,

@@ -1,5 +1,5 @@
-"""The offline batch with the encoder's half-precision switch off, at level 1 and at level 2 (Model.set_encoder_precision;
-csrc/gemm_f16.hip).
+"""The offline batch with the encoder's half-precision switch off and at levels 1, 2 and 3 (Model.set_encoder_precision;
+csrc/gemm_f16.hip, csrc/convnext_f16.hip).
 
     python tools/encoder_half_bench.py [preset] [batch] [seconds] [conv route]      (defaults: zipformer2-large-en 32 10 0)
 
@@ -14,7 +14,10 @@ launches that carry the bit at level 2 only -- the newly covered ones (a conv mo
 sides; where level 2 takes the gated f16 GEMM + dwconv1d_swoosh in place of a float32 fused launch the f16 side lacks the convolution's
 launch, so such a route is judged by the batch figures).  `conv route` forces K2HIP_F16_CONV for the run (1 fused f16, 2 gated f16 GEMM
 + conv, 3 as level 1).  "same_tokens" / "same_tokens2" count the utterances whose token lists are identical off and on.  One JSON line on
-stdout; there is no time gate (DESIGN.md "Half-precision operands in the encoder's linear layers" has the runs taken so far)."""
+stdout.  Level 3: "on3_ms" / "on3_encoder_ms" by convnext_f16_route's rule and "on3_two_ms" / "on3_two_encoder_ms" with the embed's ConvNeXt
+pointwise pair forced to the two gemm_f16_mfma launches (K2HIP_F16_CONVNEXT=2), in the same interleaved rounds; "shapes3" are the embed's
+launches that carry the bit at level 3 only, float32 against the two-launch f16 route, and "pair_us" the pointwise pair alone as float32
+(two launches), two f16 launches and the fused launch (the row whose kind carries bit 22).  There is no time gate (DESIGN.md "Half-precision operands in the encoder's linear layers" has the runs taken so far)."""
 import json
 import os
 import sys
@@ -33,9 +36,14 @@ preset = argv[0] if len(argv) > 0 else "zipformer2-large-en"
 batch = int(argv[1]) if len(argv) > 1 else 32
 seconds = float(argv[2]) if len(argv) > 2 else 10.0
 route = int(argv[3]) if len(argv) > 3 else 0
-LEVELS = (0, 1, 2)
+LEVELS = (0, 1, 2, 3, "3two")   # "3two": level 3 with the pointwise pair as two f16 launches
 ROUNDS, WARMUP = 9, 2
-F16_BIT = 1 << 21
+F16_BIT, PAIR_BIT = 1 << 21, 1 << 22
+
+
+def set_level(model, half):
+    set_switch("K2HIP_F16_CONVNEXT", 2 if half == "3two" else 0)
+    model.set_encoder_precision(3 if half == "3two" else half)
 
 
 def shape_table(off, on, skip):
@@ -68,7 +76,7 @@ def main():
         tokens = {}
         for r in range(WARMUP + ROUNDS):
             for half in LEVELS:
-                model.set_encoder_precision(half)
+                set_level(model, half)
                 tokens[half] = model.offline_greedy_from_samples(utts)
                 t = model.timing()
                 if r >= WARMUP:
@@ -78,23 +86,33 @@ def main():
         model.set_instrument(True)
         stats = {}
         for half in LEVELS:
-            model.set_encoder_precision(half)
+            set_level(model, half)
             model.offline_greedy_from_samples(utts)
             prof[half] = model.gemm_profile().copy()
             stats[half] = model.encoder_f16_stats()
         model.set_instrument(False)
         model.set_encoder_precision(False)
         model.close()
-    off, on, on2 = prof[0], prof[1], prof[2]
-    for p in (on, on2):
+    off, on, on2, on3 = prof[0], prof[1], prof[2], prof["3two"]
+    for p in (on, on2, on3):
         assert off.shape == p.shape and np.array_equal(off[:, :6], p[:, :6]), "the launch logs do not line up"
-    rows, rows2 = shape_table(off, on, off), shape_table(off, on2, on)
+    rows, rows2, rows3 = shape_table(off, on, off), shape_table(off, on2, on), shape_table(off, on3, on2)
+    pair = [s for s in rows3 if (s["N"], s["K"]) in ((384, 128), (128, 384))]
+    fused = prof[3][(prof[3][:, 6].astype(np.int64) & PAIR_BIT) != 0]
+    pair_us = dict(f32=round(sum(s["f32_us"] for s in pair), 1), two_f16=round(sum(s["f16_us"] for s in pair), 1),
+                   fused=round(float(fused[:, 7].sum()), 1), fused_launches=int(len(fused)))
     spread = lambda v: [round(float(np.min(v)), 3), round(float(np.max(v)), 3)]   # noqa: E731
     print(json.dumps(dict(
         preset=preset, batch=batch, seconds=seconds, rounds=ROUNDS, conv_route=route,
         off_ms=round(float(np.median(total[0])), 3), off_spread=spread(total[0]),
         on_ms=round(float(np.median(total[1])), 3), on_spread=spread(total[1]),
         on2_ms=round(float(np.median(total[2])), 3), on2_spread=spread(total[2]),
+        on3_ms=round(float(np.median(total[3])), 3), on3_spread=spread(total[3]),
+        on3_two_ms=round(float(np.median(total["3two"])), 3), on3_two_spread=spread(total["3two"]),
+        on3_encoder_ms=round(float(np.median(enc[3])), 3), on3_encoder_spread=spread(enc[3]),
+        on3_two_encoder_ms=round(float(np.median(enc["3two"])), 3), on2_encoder_spread=spread(enc[2]),
+        pair_us=pair_us, panels3=stats[3]["panels"], panel_bytes3=stats[3]["panel_bytes"], launches3=stats[3]["launches"],
+        same_tokens3=int(sum(a == b for a, b in zip(tokens[0], tokens[3]))), shapes3=rows3,
         off_encoder_ms=round(float(np.median(enc[0])), 3), on_encoder_ms=round(float(np.median(enc[1])), 3),
         on2_encoder_ms=round(float(np.median(enc[2])), 3),
         gemm_f32_ms=round(float(off[:, 7].sum()) / 1e3, 3), gemm_on_ms=round(float(on[:, 7].sum()) / 1e3, 3),
