@@ -1203,7 +1203,7 @@ int32_t k2hip_set_rnn_lm_rescoring_precision(k2hip_model_t* model, int32_t half)
  * enters become infinite or NaN; a NaN stays a NaN.  Nothing is clamped or rescaled.
  * A MODEL THAT DOES NOT FIT: a covered weight that is not finite in f16 (|w| >= 65520, or not finite to begin with) refuses the switch
  * with K2HIP_ERR_INVALID, the message naming the tensor, before any device work; the model stays on float32.
- * LEVEL 2 (half == 2; every non-zero value other than 2 and 3 is level 1, whose launches, panels and bits are as described above): everything level 1
+ * LEVEL 2 (half == 2; every non-zero value other than 2, 3 and 4 is level 1, whose launches, panels and bits are as described above): everything level 1
  * covers, plus, under the same K % 32 == 0 condition, the layer's remaining weight launches -- the stacked feed_forward1.in_proj /
  * attention-weights in_proj (SwooshL on the feed-forward columns only; the attention scores then read an f16-operand product), the
  * gated in_proj launches of NonlinAttention (x * tanh(s)) and of the conv modules (GLU), feed_forward2.out_proj with its in-place
@@ -1219,6 +1219,14 @@ int32_t k2hip_set_rnn_lm_rescoring_precision(k2hip_model_t* model, int32_t half)
  * depthwise convolution stay float32.  Four more panels; the same refusal, naming the checkpoint tensor, for a weight among them
  * that is not finite in f16, and the model stays at the level it had.  The levels 0, 1 and 2 issue exactly the launches and give
  * exactly the bits they gave before level 3 existed.
+ * LEVEL 4 (half == 4): everything level 3 covers, plus the self-attention core of every layer whose query head dim is 32, whose value
+ * heads fit the fused apply kernel (value head dim <= 16, heads x value dim <= 128 and a multiple of 4, at most 16 heads) and whose
+ * frame count fits the in-LDS score strip (<= 1276 frames of the stack): q and k are rounded to f16 on their way into the q.k product
+ * (v_mfma_f32_32x32x16_f16, float32 sums; the positional term and the softmax stay float32), the softmax weights are kept in memory
+ * as f16 (half the bytes; NonlinAttention still reads head 0 in float32) and the weights . values product reads them and f16-rounded
+ * values (v_mfma_f32_16x16x32_f16, float32 sums); out_proj, bias and residual behind it stay float32.  The OVERFLOW rule above holds
+ * for q, k and the values.  No new panels: level 4's panels are level 3's.  Other layers run as at level 3.  The levels 0 to 3 issue
+ * exactly the launches and give exactly the bits they gave before level 4 existed.
  * SCOPE: the streaming step (k2hip_online_*) never reads the switch.  Conformer, Zipformer v1, LSTM and streaming-export models:
  * K2HIP_ERR_UNSUPPORTED.  Turning the switch off frees the panels. */
 int32_t k2hip_set_encoder_precision(k2hip_model_t* model, int32_t half);

@@ -77,6 +77,11 @@ int32_t k2hip_debug_conv_fused_plan(int32_t B, int32_t T, int32_t D, int32_t K, 
  *   gemm_f16_mfma launches, 3 float32; the switch K2HIP_F16_CONVNEXT forces 1 / 2 / 3), plan = -1s (tests/test_encoder_half_embed.py).
  *   k2hip_debug_op_run has the two level-3 launches alone: "gemm_f16_gather" and "convnext_f16" (csrc/engine.cpp lists their arguments).
  *   GemmLaunchRec.kind of the fused pair's row: the f16 family's bit 21, a 128 x 128 tile and bit 22; its K is 128 + 384.
+ *   With 7 values -- level, streaming, T, H, qh, vh, D -- *form is the route of a layer's attention core (attn_f16_route: 1 the f16
+ *   kernels of csrc/attn_f16.hip, 3 float32; the switch K2HIP_F16_ATTN forces 1 / 3), plan = -1s (tests/test_encoder_half_attn.py).
+ *   k2hip_debug_op_run has level 4's two launches alone: "attn_scores_softmax_f16" (ints ld, B, T, Tp, H, koff0, poff0; buffers qkp,
+ *   pp, aw16, aw0) and "attn_av_out_f16" (buffers aw16, v, wout, bias, x; ints B, T, KL, Tp16, H, vh, D); aw16 is a buffer of halves
+ *   [H][B][T][Tp16] passed as 4-byte words.
  * k2hip_debug_conv_f16_plan: the offline conv module under level 2 (csrc/gemm_plan.cpp) for B streams of T frames, D channels, K taps:
  *   *entry = glu_dwconv_f16_entry (the K2_F16_TABLE index of the fused f16 launch's tile, 1: 128 x 64, 2: 64 x 64; -1: none holds the
  *   stream), *route = glu_dwconv_f16_route (1 the fused f16 launch, 2 the gated f16 GEMM + dwconv1d_swoosh, 3 what level 1 does; the

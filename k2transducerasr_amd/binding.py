@@ -1063,7 +1063,8 @@ class Model:
         naming the tensor) for a weight that is not finite in f16 -- the model then stays as it was.  half: False / 0 off, True / 1 the
         plain linear layers, 2 also the stacked feed_forward1 / attention in_proj, the gated in_proj launches (with the conv modules'
         fused depthwise-conv tail) and feed_forward2.out_proj with its bypass mix, 3 also encoder_embed's conv.7, its ConvNeXt
-        pointwise pair (one launch, the f16 hidden values kept on chip) and its output Linear."""
+        pointwise pair (one launch, the f16 hidden values kept on chip) and its output Linear, 4 also the layers' self-attention core
+        (q . k and weights . values on the f16 matrix pipe, the softmax weights kept in memory as f16; no new panels)."""
         self._L.k2hip_set_encoder_precision.argtypes = [C.c_void_p, C.c_int32]
         self._L.k2hip_set_encoder_precision.restype = C.c_int32
         self._chk(self._L.k2hip_set_encoder_precision(self._h, int(half)))
@@ -1737,7 +1738,7 @@ class OfflineRecognizer:
     with weight lodr_scale <= 0 wherever rnn_lm acts, in the rescoring or in the fused search (Model.set_lodr_lm).  encoder_half=True:
     the offline Zipformer2 encoder's plain linear layers run with f16 operands and float32 sums (Model.set_encoder_precision);
     encoder_half=2: its gated, stacked, bypass and conv-tail launches too; encoder_half=3: encoder_embed's conv.7, ConvNeXt pointwise
-    pair and output Linear too."""
+    pair and output Linear too; encoder_half=4: the layers' self-attention core (scores, f16 attention weights, apply) too."""
 
     def __init__(self, weights_path: str, device: int = 0, decoding_method: str = "greedy_search", beam: int = 4, hotwords=None,
                  hotwords_score: float = 1.5, nbest: int = 1, ngram_lm: Optional["NgramLm"] = None, ngram_lm_scale: float = 0.3,

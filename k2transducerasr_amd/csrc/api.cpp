@@ -3201,7 +3201,13 @@ int32_t k2hip_debug_conv_fused_plan(int32_t B, int32_t T, int32_t D, int32_t K, 
 int32_t k2hip_debug_gemm_f16_plan(const int64_t* f, int32_t n_fields, int32_t force, int32_t* form, int32_t* plan) {
     return guard([&] {
         NEED(f); NEED(form); NEED(plan);
-        K2_REQUIRE(n_fields == 16 || n_fields == 20 || n_fields == 24, "debug_gemm_f16_plan: 16, 20 or 24 fields, not %d", n_fields);
+        if (n_fields == 7) {   // the attention core's route (attn_f16_route): level, streaming, T, H, qh, vh, D
+            tunables_init_from_env();
+            *form = attn_f16_route((int)f[0], f[1] != 0, (int)f[2], (int)f[3], (int)f[4], (int)f[5], (int)f[6]);
+            plan[0] = plan[1] = plan[2] = -1;
+            return;
+        }
+        K2_REQUIRE(n_fields == 16 || n_fields == 20 || n_fields == 24, "debug_gemm_f16_plan: 7, 16, 20 or 24 fields, not %d", n_fields);
         if (n_fields == 24 && f[23] != 0) {   // the ConvNeXt pointwise pair's route over f[23] pixels, nothing else
             tunables_init_from_env();
             *form = convnext_f16_route(f[23]);

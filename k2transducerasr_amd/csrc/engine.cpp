@@ -406,8 +406,15 @@ void Engine::encoder_layer(const Ctx& c, int si, int li, int gl, float* x, const
     const float* qkp = cat + F1;
     // the layer's positional projection does not depend on the audio: cached per (layer, rows), streaming tables under 1000 + gl
     const float* pp = pos_proj_cached(c, site ? 1000 + gl : gl, pe, cf.pos_dim, w("self_attn_weights.linear_pos.weight"), 2 * T - 1 + L, ph * H);
-    float* aw = ar.take<float>((int64_t)H * B * T * KLp);  // (streaming: columns in ring order)
-    if (site) attn_stream_ring(c, qkp, ldcat, ring(lay_.key[gl]), pp, site->d_plen, aw, B, T, L, KLp, H, cf.ds[si], cf.left[0] * cf.ds[0]);
+    // Level 4 of the half-precision switch, route 1 (attn_f16_route): the weights of all heads as halves for the two self_attn modules
+    // (aw16, half the bytes) and head 0 in float32 for NonlinAttention's product (aw then IS that head: [B][T][KLp]), from
+    // attn_f16.hip's scores kernel; both self_attn modules then run attn_av_out_f16, which the route has checked to fit.
+    const bool attn_f16 = c.f16 && attn_f16_route(c.f16->level, site != nullptr, T, H, qh, vh, D) == 1;
+    const int Tp16 = attn_f16_tp16(T);
+    uint16_t* aw16 = attn_f16 ? ar.take<uint16_t>((int64_t)H * B * T * Tp16) : nullptr;
+    float* aw = ar.take<float>((int64_t)(attn_f16 ? 1 : H) * B * T * KLp);  // (streaming: columns in ring order)
+    if (attn_f16) attn_scores_softmax_f16(c, qkp, ldcat, pp, aw16, aw, B, T, KLp, H);
+    else if (site) attn_stream_ring(c, qkp, ldcat, ring(lay_.key[gl]), pp, site->d_plen, aw, B, T, L, KLp, H, cf.ds[si], cf.left[0] * cf.ds[0]);
     else attn_scores_softmax(c, qkp, ldcat, pp, aw, B, T, KLp, H);
 
     float* src = ar.take<float>((int64_t)M * D);
@@ -462,6 +469,10 @@ void Engine::encoder_layer(const Ctx& c, int si, int li, int gl, float* x, const
         linear(c, src, D, wi, bi, hid, HV, M, D, HV);
         if (site) {   // fused: chunk rows into the value ring, attention apply over the ring, out_proj, residual
             attn_av_out_ring(c, aw, ring(k == 1 ? lay_.val1[gl] : lay_.val2[gl]), hid, wo, bo, src, B, T, KL, KLp, H, vh, D);
+            return;
+        }
+        if (attn_f16) {
+            K2_REQUIRE(attn_av_out_f16(c, aw16, hid, wo, bo, src, B, T, T, Tp16, H, vh, D), "attn_av_out_f16 refused a shape its route took");
             return;
         }
         if (attn_av_out(c, aw, hid, wo, bo, src, B, T, T, KLp, H, vh, D)) return;  // fused attention-apply + out_proj + residual
@@ -2304,6 +2315,15 @@ void Engine::debug_op_host(const char* op, const int64_t* iargs, int n_iargs, vo
             float *aw = P(), *v = P(), *wout = P(), *bias = P(), *x = P();
             const int B = I(), T = I(), KL = I(), Tp = I(), H = I(), vh = I(), D = I();
             took = attn_av_out(c, aw, v, wout, bias, x, B, T, KL, Tp, H, vh, D);
+        } else if (name == "attn_scores_softmax_f16") {   // aw16 as a 4-byte view of [H][B][T][Tp16] halves (Tp16 is even)
+            const int ld = I();
+            float *qkp = P(), *pp = P(), *aw16 = P(), *aw0 = P();
+            const int B = I(), T = I(), Tp = I(), H = I(), koff0 = I(), poff0 = I();
+            attn_scores_softmax_f16(c, qkp, ld, pp, reinterpret_cast<uint16_t*>(aw16), aw0, B, T, Tp, H, koff0, poff0);
+        } else if (name == "attn_av_out_f16") {
+            float *aw16 = P(), *v = P(), *wout = P(), *bias = P(), *x = P();
+            const int B = I(), T = I(), KL = I(), Tp16 = I(), H = I(), vh = I(), D = I();
+            took = attn_av_out_f16(c, reinterpret_cast<const uint16_t*>(aw16), v, wout, bias, x, B, T, KL, Tp16, H, vh, D);
         } else if (name == "attn_av_out_ring") {
             float* aw = P();
             const RingRef r = ring();

@@ -396,8 +396,9 @@ class Engine {
     // The level turned on is the one set_encoder_level asked for last (1 until then).  A change between the levels 1 and 2 packs the
     // new level's panels first: a refusal leaves the engine at the level it had.
     void set_encoder_precision(bool half);
-    void set_encoder_level(int level) {   // 0 = off, 2 = level 2, 3 = level 3 (encoder_embed too), any other value = level 1
-        enc_f16_want_ = level == 2 || level == 3 ? level : 1;
+    void set_encoder_level(int level) {   // 0 = off, 2 = level 2, 3 = level 3 (encoder_embed too), 4 = level 4 (the attention core too;
+                                          // level 3's panels), any other value = level 1
+        enc_f16_want_ = level >= 2 && level <= 4 ? level : 1;
         set_encoder_precision(level != 0);
     }
     bool encoder_half() const { return enc_f16_dev_ != nullptr; }

@@ -341,6 +341,20 @@ int convnext_f16_route(long long npix) {
     return 1;
 }
 
+// A layer's attention core under level 4 (attn_f16.hip): T frames, H heads of query dim qh and value dim vh, model width D.
+int attn_f16_route(int level, bool streaming, int T, int H, int qh, int vh, int D) {
+    const int forced = tunables().f16_attn;
+    if (level != 4 || streaming || forced == 3) return 3;
+    if (T < 1 || H < 1 || qh != 32) return 3;                                   // the scores kernel's one head size
+    const int HV = H * vh;
+    if (tunables().no_fused_av || vh < 1 || vh > 16 || HV % 4 != 0 || HV > 128 || D % 16 != 0) return 3;   // attn_av_out's own fit
+    // the 32-row score strip of float32 in LDS, as attn_scores_softmax sizes it; the two-pass form beyond it stays float32
+    const long long Tp = ((long long)T + 3) & ~3ll;
+    if (tunables().attn_long || 4 * 32 * (Tp + 4) > 160 * 1024) return 3;
+    if (H > 16) return 3;                                                       // heads w, w + 4, .. of the apply kernel's four waves: at most 4 each
+    return 1;   // (no measured rule yet sends a shape back: forced == 1 and the default agree)
+}
+
 int glu_dwconv_f16_route(int B, int T, int D, int K) {
     const int e = glu_dwconv_f16_entry(B, T, D, K);
     const int forced = tunables().f16_conv;

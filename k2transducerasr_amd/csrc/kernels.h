@@ -36,7 +36,9 @@ struct Tunables {
                                   // 3 = as at level 1 (tools/encoder_half_bench.py compares the routes with it)
     int f16_convnext = 0;         // K2HIP_F16_CONVNEXT: the embed's ConvNeXt pointwise pair at level 3 of that switch: 0 = by convnext_f16_route's rule,
                                   // 1 = the fused launch (convnext_f16.hip), 2 = two gemm_f16_mfma launches, 3 = float32 as at level 2
-    int dw1d_tt = 0;             // K2HIP_DW1D_TT: outputs per thread of the depthwise Conv1d (8 / 4 / 2; 0 = by grid size; tests/test_kernels_gpu.py forces each)
+    int f16_attn = 0;             // K2HIP_F16_ATTN: a layer's attention core at level 4 of that switch: 0 = by attn_f16_route's rule, 1 = the f16 kernels
+                                  // (attn_f16.hip) wherever they can run, 3 = float32 as at level 3
+    int dw1d_tt = 0;            // K2HIP_DW1D_TT: outputs per thread of the depthwise Conv1d (8 / 4 / 2; 0 = by grid size; tests/test_kernels_gpu.py forces each)
     int lstm_seq = 0;             // K2HIP_LSTM_SEQ: layer-by-layer LSTM instead of the layer wavefront
     int greedy_one_part = 0;      // K2HIP_GREEDY_ONE_PART: one workgroup per stream in the search
     int greedy_parts = 0;         // K2HIP_GREEDY_PARTS: vocabulary slabs per stream (0 = automatic)
@@ -88,8 +90,9 @@ struct GemmF16Panel {
 };
 struct GemmF16Map {
     std::unordered_map<const float*, GemmF16Panel> by_weight;
-    int level = 1;                  // 2: the gated, stacked, bypass and conv-tail launches too (gemm_f16_fits); 3: encoder_embed's too
-    mutable int64_t launches = 0;   // gemm_f16_mfma (and convnext_f16) launches since the map was built
+    int level = 1;                  // 2: the gated, stacked, bypass and conv-tail launches too (gemm_f16_fits); 3: encoder_embed's too;
+                                    // 4: the offline layers' attention core too (attn_f16.hip)
+    mutable int64_t launches = 0;   // gemm_f16_mfma (convnext_f16, attn_f16.hip) launches since the map was built
 };
 
 struct GreedyLaunch;
@@ -361,6 +364,23 @@ void attn_scores_softmax(const Ctx& ctx, const float* qkp, int ld, const float* 
 // returns false (nothing launched, nothing tallied) when the shape does not fit the kernel -- the caller then takes the GEMM path
 bool attn_av_out(const Ctx& ctx, const float* aw, const float* v, const float* wout, const float* bias, float* x, int B, int T, int KL, int Tp,
                  int H, int vh, int D);
+// ---- level 4 of the encoder's half-precision switch: the offline self-attention core on f16 operands (attn_f16.hip) ----
+// The weights in memory are halves, aw16 [H][B][T][Tp16], Tp16 = T rounded up to 8 (rows 16-byte aligned; pad columns +0).
+inline int attn_f16_tp16(int T) { return (T + 7) & ~7; }
+// attn_scores_softmax for query head dim 32 with q and k rounded to f16 (nearest even) on their way into v_mfma_f32_32x32x16_f16; the
+// positional term, the sums and the softmax are float32.  Writes aw16 and, for NonlinAttention's float32 product, head 0's float32
+// softmax values once more as aw0 [B][T][Tp] (Tp = T rounded up to 4).  T must fit the in-LDS score strip (attn_f16_route).
+void attn_scores_softmax_f16(const Ctx& ctx, const float* qkp, int ld, const float* pp, uint16_t* aw16, float* aw0, int B, int T, int Tp,
+                             int H, int koff0 = -1, int poff0 = -1);
+// attn_av_out over aw16 [H][B][T][Tp16] (KL keys) and values rounded to f16: the context on v_mfma_f32_16x16x32_f16 with float32 sums,
+// out_proj + bias + residual in float32 as attn_av_out.  false (nothing launched or tallied): the shape does not fit.
+bool attn_av_out_f16(const Ctx& ctx, const uint16_t* aw16, const float* v, const float* wout, const float* bias, float* x, int B, int T,
+                     int KL, int Tp16, int H, int vh, int D);
+// How a pass at `level` runs a layer's attention core (gemm_plan.cpp; pure host): 1 = both f16 kernels, 3 = float32 as at level 3.
+// 1 needs level 4, a whole-utterance layer, qh == 32, attn_av_out's fit, a T inside the in-LDS strip and at most 4 heads per wave;
+// K2HIP_F16_ATTN = 3 forces 3, = 1 takes 1 wherever it can run.
+int attn_f16_route(int level, bool streaming, int T, int H, int qh, int vh, int D);
+
 // streaming ring form: values of the left context come from the ring (rows in ring order, like aw's columns); the chunk's value
 // rows (newrows [B*T, H*vh]) are written into the ring by the kernel itself before it reads them.  T <= 16 (one row strip).
 bool attn_av_out_ring(const Ctx& ctx, const float* aw, const RingRef& vals, const float* newrows, const float* wout, const float* bias, float* x,

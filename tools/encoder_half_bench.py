@@ -17,7 +17,15 @@ launch, so such a route is judged by the batch figures).  `conv route` forces K2
 stdout.  Level 3: "on3_ms" / "on3_encoder_ms" by convnext_f16_route's rule and "on3_two_ms" / "on3_two_encoder_ms" with the embed's ConvNeXt
 pointwise pair forced to the two gemm_f16_mfma launches (K2HIP_F16_CONVNEXT=2), in the same interleaved rounds; "shapes3" are the embed's
 launches that carry the bit at level 3 only, float32 against the two-launch f16 route, and "pair_us" the pointwise pair alone as float32
-(two launches), two f16 launches and the fused launch (the row whose kind carries bit 22).  There is no time gate (DESIGN.md "Half-precision operands in the encoder's linear layers" has the runs taken so far)."""
+(two launches), two f16 launches and the fused launch (the row whose kind carries bit 22).  Level 4 (csrc/attn_f16.hip): "on4_ms" /
+"on4_encoder_ms" by attn_f16_route's rule and "on4_r3_ms" / "on4_r3_encoder_ms" with K2HIP_F16_ATTN=3 (level 3's launches), in the same
+rounds, and "same_tokens4".  The attention kernels are no GEMM launches and carry no events; their times come from a kernel trace:
+
+    rocprofv3 --kernel-trace --output-format csv -d DIR -- python tools/encoder_half_bench.py --attn-calls [preset] [batch] [seconds]
+    python tools/encoder_half_bench.py --attn-table DIR/**/*_kernel_trace.csv
+
+The first runs three calls at level 3 and three at level 4 and nothing else; the second prints, per attention kernel and grid (one grid
+per stack: scores cdiv(T, 32) x B x H workgroups, apply cdiv(T, 16) x B x slices), the launches and the median microseconds.  There is no time gate (DESIGN.md "Half-precision operands in the encoder's linear layers" has the runs taken so far)."""
 import json
 import os
 import sys
@@ -32,18 +40,55 @@ from k2transducerasr_amd import Model, set_switch  # noqa: E402
 from k2transducerasr_amd.synth import synth_utterance, write_synthetic_model  # noqa: E402
 
 argv = sys.argv[1:]
+mode = argv.pop(0) if argv and argv[0].startswith("--attn-") else ""
+paths, argv = (argv, []) if mode == "--attn-table" else ([], argv)
 preset = argv[0] if len(argv) > 0 else "zipformer2-large-en"
 batch = int(argv[1]) if len(argv) > 1 else 32
 seconds = float(argv[2]) if len(argv) > 2 else 10.0
 route = int(argv[3]) if len(argv) > 3 else 0
-LEVELS = (0, 1, 2, 3, "3two")   # "3two": level 3 with the pointwise pair as two f16 launches
+LEVELS = (0, 1, 2, 3, "3two", 4, "4r3")   # "3two": level 3 with the pointwise pair as two f16 launches; "4r3": level 4, float32 attention
 ROUNDS, WARMUP = 9, 2
 F16_BIT, PAIR_BIT = 1 << 21, 1 << 22
 
 
 def set_level(model, half):
     set_switch("K2HIP_F16_CONVNEXT", 2 if half == "3two" else 0)
-    model.set_encoder_precision(3 if half == "3two" else half)
+    set_switch("K2HIP_F16_ATTN", 3 if half == "4r3" else 0)
+    model.set_encoder_precision(0)   # ("4r3" after 4 is the same level: the switch is read per call, the counters start here)
+    model.set_encoder_precision({"3two": 3, "4r3": 4}.get(half, half))
+
+
+def attn_calls():
+    """three calls at level 3 and three at level 4, for a kernel trace"""
+    with tempfile.TemporaryDirectory() as d:
+        path = os.path.join(d, "m.k2w")
+        write_synthetic_model(path, preset)
+        model = Model(path, 0)
+        utts = [synth_utterance(u, seconds) for u in range(batch)]
+        for half in (3, 4):
+            model.set_encoder_precision(half)
+            for _ in range(3):
+                model.offline_greedy_from_samples(utts)
+        model.set_encoder_precision(0)
+        model.close()
+
+
+def attn_table(paths):
+    """median microseconds of the attention kernels of kernel-trace CSVs, by kernel and grid"""
+    import csv
+    rows = {}
+    for p in paths:
+        with open(p, newline="") as f:
+            for r in csv.DictReader(f):
+                name = r["Kernel_Name"]
+                if "k_attn_scores_softmax" not in name and "k_attn_av_out" not in name:
+                    continue
+                short = ("scores" if "scores" in name else "apply") + ("_f16" if "_f16" in name else "_f32")
+                grid = tuple(int(r[f"Grid_Size_{a}"]) // int(r[f"Workgroup_Size_{a}"]) for a in "XYZ")
+                rows.setdefault((short, grid), []).append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
+    for (short, grid), us in sorted(rows.items(), key=lambda kv: (kv[0][0].split("_")[0], -kv[0][1][0], kv[0][0])):
+        print(json.dumps(dict(kernel=short, workgroups=grid, launches=len(us), median_us=round(float(np.median(us)), 2),
+                              spread=[round(min(us), 2), round(max(us), 2)])))
 
 
 def shape_table(off, on, skip):
@@ -111,6 +156,11 @@ def main():
         on3_two_ms=round(float(np.median(total["3two"])), 3), on3_two_spread=spread(total["3two"]),
         on3_encoder_ms=round(float(np.median(enc[3])), 3), on3_encoder_spread=spread(enc[3]),
         on3_two_encoder_ms=round(float(np.median(enc["3two"])), 3), on2_encoder_spread=spread(enc[2]),
+        on4_ms=round(float(np.median(total[4])), 3), on4_spread=spread(total[4]),
+        on4_encoder_ms=round(float(np.median(enc[4])), 3), on4_encoder_spread=spread(enc[4]),
+        on4_r3_ms=round(float(np.median(total["4r3"])), 3), on4_r3_spread=spread(total["4r3"]),
+        on4_r3_encoder_ms=round(float(np.median(enc["4r3"])), 3), on4_r3_encoder_spread=spread(enc["4r3"]),
+        launches4=stats[4]["launches"], panels4=stats[4]["panels"], same_tokens4=int(sum(a == b for a, b in zip(tokens[0], tokens[4]))),
         pair_us=pair_us, panels3=stats[3]["panels"], panel_bytes3=stats[3]["panel_bytes"], launches3=stats[3]["launches"],
         same_tokens3=int(sum(a == b for a, b in zip(tokens[0], tokens[3]))), shapes3=rows3,
         off_encoder_ms=round(float(np.median(enc[0])), 3), on_encoder_ms=round(float(np.median(enc[1])), 3),
@@ -127,4 +177,9 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    if mode == "--attn-table":
+        attn_table(paths)
+    elif mode == "--attn-calls":
+        attn_calls()
+    else:
+        main()
