@@ -1227,9 +1227,30 @@ int32_t k2hip_set_rnn_lm_rescoring_precision(k2hip_model_t* model, int32_t half)
  * values (v_mfma_f32_16x16x32_f16, float32 sums); out_proj, bias and residual behind it stay float32.  The OVERFLOW rule above holds
  * for q, k and the values.  No new panels: level 4's panels are level 3's.  Other layers run as at level 3.  The levels 0 to 3 issue
  * exactly the launches and give exactly the bits they gave before level 4 existed.
- * SCOPE: the streaming step (k2hip_online_*) never reads the switch.  Conformer, Zipformer v1, LSTM and streaming-export models:
- * K2HIP_ERR_UNSUPPORTED.  Turning the switch off frees the panels. */
+ * SCOPE: the streaming step (k2hip_online_*) never reads the switch.  Conformer (its switch is k2hip_set_conformer_precision below),
+ * Zipformer v1, LSTM and streaming-export models: K2HIP_ERR_UNSUPPORTED.  Turning the switch off frees the panels. */
 int32_t k2hip_set_encoder_precision(k2hip_model_t* model, int32_t half);
+
+/* ---- half-precision operands in the offline Conformer encoder ------------------------------------------------------------------------
+ * (no reference counterpart; the project's own semantics, those of k2hip_set_encoder_precision above.  DESIGN.md "Half-precision
+ * operands in the offline Conformer encoder".)  Offline `conformer` models only; Zipformer2, Zipformer v1, LSTM and every streaming
+ * export: K2HIP_ERR_UNSUPPORTED.  The streaming Conformer step never reads the switch.  Per model, 0 (float32) by default;
+ * K2HIP_ERR_INVALID while submitted batches are in flight and for a level other than 0, 1 and 2; a call with the current level does
+ * nothing.  With level 0 every call issues the launches and gives the bits of before.
+ * LEVEL 1: in every encoder layer the linear launches -- feed_forward_macaron.0 / .4, feed_forward.0 / .4, self_attn.in_proj,
+ * self_attn.out_proj, conv_module.pointwise_conv1 / pointwise_conv2, each under the K % 32 == 0 rule -- run C = epilogue(f16(A) .
+ * f16(W)^T) with float32 sums, W rounded ONCE into panels resident beside the float32 weights, the float32 activation on its way into
+ * the matrix pipe.  Bias, DoubleSwish, residual, Conv2dSubsampling with its output Linear, linear_pos (its product is cached per
+ * length), the depthwise convolution, BasicNorm, the encoder's output projection, decoder, joiner and every search stay float32.
+ * LEVEL 2: level 1, plus the attention core of every layer whose shape the float32 fused score kernel takes (head size 16, 32 or 64,
+ * at most 1244 frames after subsampling): the operands (q scaling + pos_bias_u), (q scaling + pos_bias_v) -- formed in float32 --, the
+ * keys and the projected positional table are rounded to f16 on their way into both score products (v_mfma_f32_16x16x32_f16, float32
+ * sums; the softmax stays float32), the softmax weights are kept in memory as f16 and the weights . values product reads them and
+ * f16-rounded values (float32 sums).  No new panels.  Other layers (very long utterances) run as at level 1.
+ * OVERFLOW and A MODEL THAT DOES NOT FIT: as above -- an activation beyond the f16 range becomes an infinity, nothing is clamped; a
+ * covered weight that is not finite in f16 refuses the switch with K2HIP_ERR_INVALID, naming the checkpoint tensor, and the model
+ * stays at the level it had.  Level 0 frees the panels. */
+int32_t k2hip_set_conformer_precision(k2hip_model_t* model, int32_t level);
 
 /* ---- LODR: low-order density ratio beside the neural LM ------------------------------------------------------------------------------
  * (no reference counterpart; the project's own semantics after icefall's modified_beam_search_LODR / modified_beam_search_lm_rescore_LODR

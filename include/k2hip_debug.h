@@ -82,6 +82,11 @@ int32_t k2hip_debug_conv_fused_plan(int32_t B, int32_t T, int32_t D, int32_t K, 
  *   k2hip_debug_op_run has level 4's two launches alone: "attn_scores_softmax_f16" (ints ld, B, T, Tp, H, koff0, poff0; buffers qkp,
  *   pp, aw16, aw0) and "attn_av_out_f16" (buffers aw16, v, wout, bias, x; ints B, T, KL, Tp16, H, vh, D); aw16 is a buffer of halves
  *   [H][B][T][Tp16] passed as 4-byte words.
+ *   The offline Conformer's level 2 (k2hip_set_conformer_precision; csrc/conformer_f16.hip; tests/test_conformer_half_gpu.py) likewise:
+ *   "conformer_scores_softmax_f16" (buffers qu, qv, kmat, pp, aw16, bias_u, bias_v; ints ldk, B, H, T, D, ldq, then the bits of the
+ *   float scaling -- conformer_scores_softmax's arguments without Tp) and "conformer_av_f16" (buffers aw16, v, out; ints B, H, T, dk,
+ *   ldv, ldc); aw16 is [B*H][T][Tp16] halves passed as 4-byte words.  The switch K2HIP_F16_CONFORMER_ATTN = 3 keeps the float32 core
+ *   at level 2 (level 1's launches and bits).
  * k2hip_debug_conv_f16_plan: the offline conv module under level 2 (csrc/gemm_plan.cpp) for B streams of T frames, D channels, K taps:
  *   *entry = glu_dwconv_f16_entry (the K2_F16_TABLE index of the fused f16 launch's tile, 1: 128 x 64, 2: 64 x 64; -1: none holds the
  *   stream), *route = glu_dwconv_f16_route (1 the fused f16 launch, 2 the gated f16 GEMM + dwconv1d_swoosh, 3 what level 1 does; the

@@ -1069,6 +1069,16 @@ class Model:
         self._L.k2hip_set_encoder_precision.restype = C.c_int32
         self._chk(self._L.k2hip_set_encoder_precision(self._h, int(half)))
 
+    def set_conformer_precision(self, level):
+        """k2hip_set_conformer_precision: the offline Conformer's half-precision switch.  level 0 off; 1 the layers' linear launches
+        (feed-forward pairs, self_attn.in_proj / out_proj, the conv module's pointwise pair; K % 32 == 0) with f16 operands and float32
+        sums; 2 also the attention core (both score products and weights . values on the f16 matrix pipe, the softmax weights kept in
+        memory as f16; no new panels).  K2HipError (unsupported) for every other model family and for streaming exports; (invalid) for
+        another level, or, naming the tensor, for a weight that is not finite in f16 -- the model then stays as it was."""
+        self._L.k2hip_set_conformer_precision.argtypes = [C.c_void_p, C.c_int32]
+        self._L.k2hip_set_conformer_precision.restype = C.c_int32
+        self._chk(self._L.k2hip_set_conformer_precision(self._h, int(level)))
+
     def encoder_f16_stats(self) -> dict:
         """gemm_f16_mfma launches since the switch was last turned on; resident weight panels; their bytes"""
         self._L.k2hip_debug_encoder_f16_stats.argtypes = [C.c_void_p] + [C.POINTER(C.c_int64)] * 3
@@ -1738,17 +1748,21 @@ class OfflineRecognizer:
     with weight lodr_scale <= 0 wherever rnn_lm acts, in the rescoring or in the fused search (Model.set_lodr_lm).  encoder_half=True:
     the offline Zipformer2 encoder's plain linear layers run with f16 operands and float32 sums (Model.set_encoder_precision);
     encoder_half=2: its gated, stacked, bypass and conv-tail launches too; encoder_half=3: encoder_embed's conv.7, ConvNeXt pointwise
-    pair and output Linear too; encoder_half=4: the layers' self-attention core (scores, f16 attention weights, apply) too."""
+    pair and output Linear too; encoder_half=4: the layers' self-attention core (scores, f16 attention weights, apply) too.
+    conformer_half=1: the offline Conformer's layer linears run with f16 operands and float32 sums (Model.set_conformer_precision);
+    conformer_half=2: its attention core too."""
 
     def __init__(self, weights_path: str, device: int = 0, decoding_method: str = "greedy_search", beam: int = 4, hotwords=None,
                  hotwords_score: float = 1.5, nbest: int = 1, ngram_lm: Optional["NgramLm"] = None, ngram_lm_scale: float = 0.3,
                  ctc_prefix_biasing: bool = False, rnn_lm: Optional["RnnLm"] = None, rnn_lm_scale: float = 0.5, rnn_lm_fusion: bool = False,
                  lodr_lm: Optional["NgramLm"] = None, lodr_scale: float = -0.1, rnn_lm_half: bool = False,
-                 rnn_lm_rescore_half: bool = False, encoder_half=False):
+                 rnn_lm_rescore_half: bool = False, encoder_half=False, conformer_half: int = 0):
         self.model = Model(weights_path, device)
         self.model.set_decoding_method(decoding_method, beam)
         if encoder_half:
             self.model.set_encoder_precision(encoder_half)
+        if conformer_half:
+            self.model.set_conformer_precision(conformer_half)
         if rnn_lm_rescore_half:
             self.model.set_rnn_lm_rescoring_precision(True)
         if nbest != 1:   # (streams then carry .alternatives() / .token_log_probs() after get_results)

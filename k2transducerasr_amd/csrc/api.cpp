@@ -4087,6 +4087,15 @@ int32_t k2hip_set_encoder_precision(k2hip_model_t* model, int32_t half) {
         e.set_encoder_level(half);
     });
 }
+int32_t k2hip_set_conformer_precision(k2hip_model_t* model, int32_t level) {
+    return guard([&] {
+        NEED(model);
+        Engine& e = model->engine;
+        EngineLock lk(e);
+        K2_REQUIRE(e.batches_in_flight() == 0, "set_conformer_precision: %d submitted batches are in flight; wait for them first", e.batches_in_flight());
+        e.set_conformer_precision(level);
+    });
+}
 int32_t k2hip_debug_rnn_lm_stream_fusion_stats(k2hip_model_t* model, int64_t* chunk_calls, int64_t* live_blocks, int64_t* pool_bytes) {
     return guard([&] {
         NEED(model);

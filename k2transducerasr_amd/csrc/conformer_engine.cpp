@@ -102,14 +102,29 @@ void Engine::conformer_layer(const Ctx& c, int li, float* x, const float* pe, in
         linear(c, x, D, w("self_attn.in_proj.weight"), w("self_attn.in_proj.bias"), qkv, 3 * D, M, D, 3 * D);
         const float* pp = pos_proj_cached(c, 3000 + li, pe, D, w("self_attn.linear_pos.weight"), NP, D);
         float* qu = ar.take<float>((int64_t)M * D);
-        float* qv = ar.take<float>((int64_t)M * D);
-        float* ac = ar.take<float>((int64_t)B * H * T * Tp);
-        float* bd = ar.take<float>((int64_t)B * H * T * NPp);
+        const float scaling = 1.0f / sqrtf((float)dk);
+        // Level 2 of the half-precision switch (k2hip_set_conformer_precision): where the float32 fused kernel below would take the shape
+        // (its own launcher says so to a dry Ctx, which launches and tallies nothing), the core runs as conformer_f16.hip's two launches --
+        // the weights as halves, no float32 score or weight tensor.  K2HIP_F16_CONFORMER_ATTN=3 keeps the float32 core.
+        Ctx probe;
+        probe.dry = true;
+        const bool f16core = c.f16 && c.f16->level == 2 && tunables().f16_conformer_attn != 3 &&
+                             conformer_scores_softmax(probe, qkv, nullptr, qkv + D, 3 * D, pp, nullptr, B, H, T, Tp, D, 3 * D,
+                                                      w("self_attn.pos_bias_u"), w("self_attn.pos_bias_v"), scaling);
+        float* qv = f16core ? nullptr : ar.take<float>((int64_t)M * D);
+        float* ac = f16core ? nullptr : ar.take<float>((int64_t)B * H * T * Tp);
+        float* bd = f16core ? nullptr : ar.take<float>((int64_t)B * H * T * NPp);
+        float* ctxv = qu;  // [M, D], column block h
         // scores + softmax in one kernel (no [T,T] / [T,2T-1] score tensors), the two query operands q * scaling + pos_bias_u / _v formed
         // on its way in (round 5: k_conformer_qprep was a launch of its own per layer); the GEMM form below is the fallback for shapes it
         // does not cover (very long utterances, unusual head sizes)
-        const float scaling = 1.0f / sqrtf((float)dk);
-        if (!conformer_scores_softmax(c, qkv, nullptr, qkv + D, 3 * D, pp, ac, B, H, T, Tp, D, 3 * D, w("self_attn.pos_bias_u"), w("self_attn.pos_bias_v"),
+        if (f16core) {
+            uint16_t* aw16 = ar.take<uint16_t>((int64_t)B * H * T * attn_f16_tp16(T));
+            K2_REQUIRE(conformer_scores_softmax_f16(c, qkv, nullptr, qkv + D, 3 * D, pp, aw16, B, H, T, D, 3 * D, w("self_attn.pos_bias_u"),
+                                                    w("self_attn.pos_bias_v"), scaling) &&
+                           conformer_av_f16(c, aw16, qkv + 2 * D, 3 * D, ctxv, D, B, H, T, dk),
+                       "conformer f16 attention refused a shape the float32 kernel takes");
+        } else if (!conformer_scores_softmax(c, qkv, nullptr, qkv + D, 3 * D, pp, ac, B, H, T, Tp, D, 3 * D, w("self_attn.pos_bias_u"), w("self_attn.pos_bias_v"),
                                       scaling)) {
             conformer_qprep(c, qkv, w("self_attn.pos_bias_u"), w("self_attn.pos_bias_v"), qu, qv, M, D, scaling);
             {   // ac[b,h] = qu[b,:,h] . k[b,:,h]^T      z = h + H*b
@@ -130,8 +145,7 @@ void Engine::conformer_layer(const Ctx& c, int li, float* x, const float* pe, in
             }
             conformer_softmax_shift(c, ac, bd, B * H, T, Tp, NPp);
         }
-        float* ctxv = qu;  // [M, D], column block h
-        {   // ctxv[b,:,h] = w[b,h] . v[b,:,h]
+        if (!f16core) {   // ctxv[b,:,h] = w[b,h] . v[b,:,h]
             GemmArgs g;
             g.A = ac; g.lda = Tp; g.sA0 = (long long)T * Tp; g.sA1 = (long long)H * T * Tp;
             g.W = qkv + 2 * D; g.w_kn = 1; g.ldw = 3 * D; g.sW0 = dk; g.sW1 = (long long)T * 3 * D;
@@ -165,13 +179,15 @@ float* Engine::conformer_forward(const Ctx& c, const float* x, int B, int T, int
     float* xe = conformer_embed(c, x, B, T, &T3);
     if (tap_rows) *tap_rows = B * T3;
     const float* pe = c.dry ? nullptr : conformer_pos_emb(T3);
+    Ctx cs = c;   // the layers' launches read the half-precision panels while the switch is on (k2hip_set_conformer_precision)
+    cs.f16 = enc_f16_dev_ ? &enc_f16_ : nullptr;
     for (int li = 0; li <= cf.nlayer[0]; li++) {
         if (tap == li) {
             *tap_ptr = xe;
             *tap_dim = cf.dim[0];
             return nullptr;
         }
-        if (li < cf.nlayer[0]) conformer_layer(c, li, xe, pe, B, T3);
+        if (li < cf.nlayer[0]) conformer_layer(cs, li, xe, pe, B, T3);
     }
     linear(c, xe, cf.dim[0], m.w("joiner.encoder_proj.weight"), m.w("joiner.encoder_proj.bias"), enc_out, cf.J, B * T3, cf.dim[0], cf.J);
     *Tp = T3;

@@ -2639,6 +2639,18 @@ void Engine::debug_op_host(const char* op, const int64_t* iargs, int n_iargs, vo
             float *bu = P(), *bv = P();
             const float scaling = F();
             took = conformer_scores_softmax(c, qu, qv, kmat, ldk, pp, aw, B, H, T, Tp, D, ldq, bu, bv, scaling);
+        } else if (name == "conformer_scores_softmax_f16") {   // aw16 as a 4-byte view of [B*H][T][Tp16] halves (Tp16 is even)
+            float *qu = P(), *qv = P(), *kmat = P();
+            const int ldk = I();
+            float *pp = P(), *aw16 = P();
+            const int B = I(), H = I(), T = I(), D = I(), ldq = I();
+            float *bu = P(), *bv = P();
+            const float scaling = F();
+            took = conformer_scores_softmax_f16(c, qu, qv, kmat, ldk, pp, reinterpret_cast<uint16_t*>(aw16), B, H, T, D, ldq, bu, bv, scaling);
+        } else if (name == "conformer_av_f16") {
+            float *aw16 = P(), *v = P(), *out = P();
+            const int B = I(), H = I(), T = I(), dk = I(), ldv = I(), ldc = I();
+            took = conformer_av_f16(c, reinterpret_cast<const uint16_t*>(aw16), v, ldv, out, ldc, B, H, T, dk);
         } else if (name == "conformer_softmax_shift") {
             float *ac = P(), *bd = P();
             const int Z = I(), T = I(), Tp = I(), NPp = I();
@@ -3540,6 +3552,7 @@ void Engine::debug_gemm_trace(int M, int N, int K, int act, bool with_res, int c
 
 void Engine::set_encoder_precision(bool half) {
     K2_HIP(hipSetDevice(device_));
+    if (model_->cfg().conformer) encoder_half_pack(*model_, nullptr, nullptr);   // (its panels belong to set_conformer_precision: UNSUPPORTED)
     if (half == (enc_f16_dev_ != nullptr) && (!half || enc_f16_.level == enc_f16_want_)) {
         if (!half) encoder_half_pack(*model_, nullptr, nullptr);   // (off on a model that has no such switch: still UNSUPPORTED)
         return;
@@ -3569,6 +3582,43 @@ void Engine::set_encoder_precision(bool half) {
     }
     GemmF16Map map;
     map.level = enc_f16_want_;
+    for (const EncoderHalfEntry& e : entries) map.by_weight[e.dev] = {static_cast<const uint16_t*>(p) + e.off, e.N, e.K};
+    enc_f16_ = std::move(map);
+    enc_f16_dev_ = p;
+    enc_f16_bytes_ = (int64_t)(blob.size() * sizeof(uint16_t));
+}
+void Engine::set_conformer_precision(int level) {
+    K2_HIP(hipSetDevice(device_));
+    conformer_half_pack(*model_, nullptr, nullptr);   // the model check: every other family is UNSUPPORTED, whatever the level
+    K2_REQUIRE(level >= 0 && level <= 2, "set_conformer_precision: level %d (0 = float32, 1 = the linear layers, 2 = the attention core too)", level);
+    const int cur = enc_f16_dev_ ? enc_f16_.level : 0;
+    if (level == cur) return;
+    if (level == 0) {
+        synchronize();
+        K2_HIP(hipFree(enc_f16_dev_));
+        enc_f16_dev_ = nullptr;
+        enc_f16_bytes_ = 0;
+        enc_f16_ = GemmF16Map();
+        return;
+    }
+    if (cur != 0) {   // between 1 and 2: the same panels; the counters start again
+        enc_f16_.level = level;
+        enc_f16_.launches = 0;
+        return;
+    }
+    std::vector<uint16_t> blob;
+    std::vector<EncoderHalfEntry> entries;
+    conformer_half_pack(*model_, &blob, &entries);   // throws before any device work
+    K2_REQUIRE(!entries.empty(), "set_conformer_precision: the model has no layer weight with K %% 32 == 0");
+    void* p = nullptr;
+    K2_HIP(hipMalloc(&p, blob.size() * sizeof(uint16_t)));
+    const hipError_t rc = copy_blocking(p, blob.data(), blob.size() * sizeof(uint16_t), hipMemcpyHostToDevice);
+    if (rc != hipSuccess) {
+        (void)hipFree(p);
+        K2_HIP(rc);
+    }
+    GemmF16Map map;
+    map.level = level;
     for (const EncoderHalfEntry& e : entries) map.by_weight[e.dev] = {static_cast<const uint16_t*>(p) + e.off, e.N, e.K};
     enc_f16_ = std::move(map);
     enc_f16_dev_ = p;

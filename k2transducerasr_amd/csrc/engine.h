@@ -53,6 +53,9 @@ struct EncoderHalfEntry {
 // in_proj repacks and feed_forward2.out_proj (a refusal names the checkpoint tensor the offending row came from).  level 3: also
 // encoder_embed's conv.7 ("#ohwi"), ConvNeXt pointwise_conv1 / 2 and out ("#fc"), refused under the checkpoint tensor's name.
 void encoder_half_pack(const Model& m, std::vector<uint16_t>* blob, std::vector<EncoderHalfEntry>* entries, int level = 1);
+// The same for the offline Conformer (k2hip_set_conformer_precision): per layer the feed-forward pairs, self_attn.in_proj / out_proj and
+// the conv module's pointwise pair, under the K % 32 == 0 rule.  K2HIP_ERR_UNSUPPORTED for every other model, streaming Conformers included.
+void conformer_half_pack(const Model& m, std::vector<uint16_t>* blob, std::vector<EncoderHalfEntry>* entries);
 
 class Engine {
   public:
@@ -401,6 +404,10 @@ class Engine {
         enc_f16_want_ = level >= 2 && level <= 4 ? level : 1;
         set_encoder_precision(level != 0);
     }
+    // k2hip_set_conformer_precision (semantics in include/k2hip.h): the offline Conformer's switch, over the same panel map, blob and
+    // counters (a model is one family).  0 = off, 1 = the layers' linear() launches, 2 = the attention core too (conformer_f16.hip; the
+    // panels of level 1).  Every other value is K2HIP_ERR_INVALID.  A refusal leaves the engine at the level it had.
+    void set_conformer_precision(int level);
     bool encoder_half() const { return enc_f16_dev_ != nullptr; }
     // gemm_f16_mfma launches since the switch was last turned on, resident panels and their bytes (k2hip_debug.h)
     void encoder_f16_stats(int64_t* launches, int64_t* panels, int64_t* panel_bytes) const;

@@ -38,6 +38,8 @@ struct Tunables {
                                   // 1 = the fused launch (convnext_f16.hip), 2 = two gemm_f16_mfma launches, 3 = float32 as at level 2
     int f16_attn = 0;             // K2HIP_F16_ATTN: a layer's attention core at level 4 of that switch: 0 = by attn_f16_route's rule, 1 = the f16 kernels
                                   // (attn_f16.hip) wherever they can run, 3 = float32 as at level 3
+    int f16_conformer_attn = 0;   // K2HIP_F16_CONFORMER_ATTN: a layer's attention core at level 2 of the offline Conformer's switch: 0 = the f16 kernels
+                                  // (conformer_f16.hip) wherever they can run, 3 = float32 as at level 1
     int dw1d_tt = 0;            // K2HIP_DW1D_TT: outputs per thread of the depthwise Conv1d (8 / 4 / 2; 0 = by grid size; tests/test_kernels_gpu.py forces each)
     int lstm_seq = 0;             // K2HIP_LSTM_SEQ: layer-by-layer LSTM instead of the layer wavefront
     int greedy_one_part = 0;      // K2HIP_GREEDY_ONE_PART: one workgroup per stream in the search
@@ -91,8 +93,9 @@ struct GemmF16Panel {
 struct GemmF16Map {
     std::unordered_map<const float*, GemmF16Panel> by_weight;
     int level = 1;                  // 2: the gated, stacked, bypass and conv-tail launches too (gemm_f16_fits); 3: encoder_embed's too;
-                                    // 4: the offline layers' attention core too (attn_f16.hip)
-    mutable int64_t launches = 0;   // gemm_f16_mfma (convnext_f16, attn_f16.hip) launches since the map was built
+                                    // 4: the offline layers' attention core too (attn_f16.hip).  An offline Conformer's map
+                                    // (Engine::set_conformer_precision): 1, or 2: its attention core too (conformer_f16.hip)
+    mutable int64_t launches = 0;   // gemm_f16_mfma (convnext_f16, attn_f16.hip, conformer_f16.hip) launches since the map was built
 };
 
 struct GreedyLaunch;
@@ -473,6 +476,17 @@ void conformer_softmax_shift(const Ctx& ctx, float* ac, const float* bd, int Z, 
 // projected positional table pp [2T-1, D]; false = shape not covered (caller takes the GEMM + conformer_softmax_shift form)
 bool conformer_scores_softmax(const Ctx& ctx, const float* qu, const float* qv, const float* kmat, int ldk, const float* pp, float* aw, int B, int H,
                               int T, int Tp, int D, int ldq = 0, const float* bias_u = nullptr, const float* bias_v = nullptr, float scaling = 1.0f);
+// ---- level 2 of the offline Conformer's half-precision switch: the attention core on f16 operands (conformer_f16.hip) ----
+// conformer_scores_softmax with the two query operands, the keys and the table rows rounded to f16 (nearest even) on their way into
+// v_mfma_f32_16x16x32_f16; float32 sums and softmax.  The weights leave as halves, aw16 [B*H][T][Tp16], Tp16 = attn_f16_tp16(T), pad
+// columns +0; no float32 weight tensor.  Head size D / H: 16, 32, 48 or 64.  false (nothing launched or tallied): another head size, a
+// row stride that is no multiple of 4, or more than 1280 frames (the engine also asks conformer_scores_softmax's own rule before it routes).
+bool conformer_scores_softmax_f16(const Ctx& ctx, const float* qu, const float* qv, const float* kmat, int ldk, const float* pp, uint16_t* aw16,
+                                  int B, int H, int T, int D, int ldq = 0, const float* bias_u = nullptr, const float* bias_v = nullptr,
+                                  float scaling = 1.0f);
+// out[b*T + i, h*dk .. (h+1)*dk) = aw16[b*H + h][i][:] . f16(v[b*T + j, h*dk ..]) (rows of v ldv floats apart, of out ldc) on
+// v_mfma_f32_16x16x32_f16 with float32 sums; nothing else of out is written.  false: dk is no multiple of 16 up to 64, or a stride is odd.
+bool conformer_av_f16(const Ctx& ctx, const uint16_t* aw16, const float* v, int ldv, float* out, int ldc, int B, int H, int T, int dk);
 // Din / Dorig > 0: the input rows are that wide and are zero-extended / truncated to D on the fly (convert_channels folded in)
 void downsample(const Ctx& ctx, const float* x, const float* bias, float* y, int B, int T, int D, int ds, int Din = 0);
 void upsample_combine(const Ctx& ctx, const float* orig, const float* xd, const float* scale, float* y, int B, int T,

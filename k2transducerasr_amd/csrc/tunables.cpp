@@ -79,6 +79,7 @@ const Entry kEntries[] = {
     {"K2HIP_F16_CONV", &Tunables::f16_conv, false},
     {"K2HIP_F16_CONVNEXT", &Tunables::f16_convnext, false},
     {"K2HIP_F16_ATTN", &Tunables::f16_attn, false},
+    {"K2HIP_F16_CONFORMER_ATTN", &Tunables::f16_conformer_attn, false},
     {"K2HIP_LSTM_SEQ", &Tunables::lstm_seq, true},
     {"K2HIP_GREEDY_ONE_PART", &Tunables::greedy_one_part, true},
     {"K2HIP_GREEDY_PARTS", &Tunables::greedy_parts, false},

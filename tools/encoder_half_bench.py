@@ -25,7 +25,17 @@ rounds, and "same_tokens4".  The attention kernels are no GEMM launches and carr
     python tools/encoder_half_bench.py --attn-table DIR/**/*_kernel_trace.csv
 
 The first runs three calls at level 3 and three at level 4 and nothing else; the second prints, per attention kernel and grid (one grid
-per stack: scores cdiv(T, 32) x B x H workgroups, apply cdiv(T, 16) x B x slices), the launches and the median microseconds.  There is no time gate (DESIGN.md "Half-precision operands in the encoder's linear layers" has the runs taken so far)."""
+per stack: scores cdiv(T, 32) x B x H workgroups, apply cdiv(T, 16) x B x slices), the launches and the median microseconds.  There is no time gate (DESIGN.md "Half-precision operands in the encoder's linear layers" has the runs taken so far).
+
+The offline Conformer's switch (Model.set_conformer_precision; csrc/conformer_f16.hip) has a leg of its own:
+
+    python tools/encoder_half_bench.py --conformer [preset] [batch] [seconds]      (defaults: conformer-zh 8 30)
+
+the batch at the levels 0, 1, 2 and 2 with the float32 attention core (K2HIP_F16_CONFORMER_ATTN=3), interleaved round by round: medians
+of total_ms and encoder_ms with [min, max], the counters, the utterances with identical tokens at each level, and from one instrumented
+call at level 1 the float32 value product's batched GEMM launches ("av_gemm_f32_us": count, microseconds summed).  The two new kernels
+against the float32 scores kernel come from a kernel trace: --conformer-calls runs three calls at level 1 and three at level 2 and
+nothing else, --attn-table lists the Conformer kernels too."""
 import json
 import os
 import sys
@@ -40,11 +50,12 @@ from k2transducerasr_amd import Model, set_switch  # noqa: E402
 from k2transducerasr_amd.synth import synth_utterance, write_synthetic_model  # noqa: E402
 
 argv = sys.argv[1:]
-mode = argv.pop(0) if argv and argv[0].startswith("--attn-") else ""
+mode = argv.pop(0) if argv and argv[0].startswith("--") else ""
 paths, argv = (argv, []) if mode == "--attn-table" else ([], argv)
-preset = argv[0] if len(argv) > 0 else "zipformer2-large-en"
-batch = int(argv[1]) if len(argv) > 1 else 32
-seconds = float(argv[2]) if len(argv) > 2 else 10.0
+conformer = mode.startswith("--conformer")
+preset = argv[0] if len(argv) > 0 else ("conformer-zh" if conformer else "zipformer2-large-en")
+batch = int(argv[1]) if len(argv) > 1 else (8 if conformer else 32)
+seconds = float(argv[2]) if len(argv) > 2 else (30.0 if conformer else 10.0)
 route = int(argv[3]) if len(argv) > 3 else 0
 LEVELS = (0, 1, 2, 3, "3two", 4, "4r3")   # "3two": level 3 with the pointwise pair as two f16 launches; "4r3": level 4, float32 attention
 ROUNDS, WARMUP = 9, 2
@@ -59,17 +70,18 @@ def set_level(model, half):
 
 
 def attn_calls():
-    """three calls at level 3 and three at level 4, for a kernel trace"""
+    """three calls at level 3 and three at level 4 (the Conformer: at its levels 1 and 2), for a kernel trace"""
     with tempfile.TemporaryDirectory() as d:
         path = os.path.join(d, "m.k2w")
         write_synthetic_model(path, preset)
         model = Model(path, 0)
         utts = [synth_utterance(u, seconds) for u in range(batch)]
-        for half in (3, 4):
-            model.set_encoder_precision(half)
+        switch = model.set_conformer_precision if conformer else model.set_encoder_precision
+        for half in ((1, 2) if conformer else (3, 4)):
+            switch(half)
             for _ in range(3):
                 model.offline_greedy_from_samples(utts)
-        model.set_encoder_precision(0)
+        switch(0)
         model.close()
 
 
@@ -81,9 +93,9 @@ def attn_table(paths):
         with open(p, newline="") as f:
             for r in csv.DictReader(f):
                 name = r["Kernel_Name"]
-                if "k_attn_scores_softmax" not in name and "k_attn_av_out" not in name:
+                if not any(k in name for k in ("k_attn_scores_softmax", "k_attn_av_out", "k_conformer_scores_softmax", "k_conformer_av")):
                     continue
-                short = ("scores" if "scores" in name else "apply") + ("_f16" if "_f16" in name else "_f32")
+                short = ("conformer_" if "k_conformer" in name else "") + ("scores" if "scores" in name else "apply") + ("_f16" if "_f16" in name else "_f32")
                 grid = tuple(int(r[f"Grid_Size_{a}"]) // int(r[f"Workgroup_Size_{a}"]) for a in "XYZ")
                 rows.setdefault((short, grid), []).append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
     for (short, grid), us in sorted(rows.items(), key=lambda kv: (kv[0][0].split("_")[0], -kv[0][1][0], kv[0][0])):
@@ -107,6 +119,46 @@ def shape_table(off, on, skip):
     for s in rows:
         s["f32_us"], s["f16_us"] = round(s["f32_us"], 1), round(s["f16_us"], 1)
     return rows
+
+
+def conformer_main():
+    levels = (0, 1, 2, "2r3")   # "2r3": level 2 with the float32 attention core
+    spread = lambda v: [round(float(np.min(v)), 3), round(float(np.max(v)), 3)]   # noqa: E731
+
+    def set_level(model, lv):
+        set_switch("K2HIP_F16_CONFORMER_ATTN", 3 if lv == "2r3" else 0)
+        model.set_conformer_precision(0)   # (the counters start here)
+        model.set_conformer_precision(2 if lv == "2r3" else lv)
+
+    with tempfile.TemporaryDirectory() as d:
+        path = os.path.join(d, "m.k2w")
+        write_synthetic_model(path, preset)
+        model = Model(path, 0)
+        utts = [synth_utterance(u, seconds) for u in range(batch)]
+        total, enc, tokens, stats = {v: [] for v in levels}, {v: [] for v in levels}, {}, {}
+        for r in range(WARMUP + ROUNDS):
+            for lv in levels:
+                set_level(model, lv)
+                tokens[lv] = model.offline_greedy_from_samples(utts)
+                t, stats[lv] = model.timing(), model.encoder_f16_stats()
+                if r >= WARMUP:
+                    total[lv].append(t["total_ms"])
+                    enc[lv].append(t["encoder_ms"])
+        model.set_instrument(True)
+        set_level(model, 1)
+        model.offline_greedy_from_samples(utts)
+        prof = model.gemm_profile().copy()
+        model.set_instrument(False)
+        set_level(model, 0)
+        model.close()
+    av = prof[(prof[:, 3] > 1) & (prof[:, 1] < prof[:, 2])]   # batched launches with N = dk < K = T: the weights . values product
+    out = dict(preset=preset, batch=batch, seconds=seconds, rounds=ROUNDS, utterances=batch,
+               av_gemm_f32_us=dict(launches=int(len(av)), us=round(float(av[:, 7].sum()), 1)))
+    for lv in levels:
+        out[f"level{lv}"] = dict(total_ms=round(float(np.median(total[lv])), 3), total_spread=spread(total[lv]),
+                                 encoder_ms=round(float(np.median(enc[lv])), 3), encoder_spread=spread(enc[lv]), **stats[lv],
+                                 same_tokens=int(sum(a == b for a, b in zip(tokens[0], tokens[lv]))))
+    print(json.dumps(out), flush=True)
 
 
 def main():
@@ -179,7 +231,9 @@ def main():
 if __name__ == "__main__":
     if mode == "--attn-table":
         attn_table(paths)
-    elif mode == "--attn-calls":
+    elif mode in ("--attn-calls", "--conformer-calls"):
         attn_calls()
+    elif mode == "--conformer":
+        conformer_main()
     else:
         main()
